@@ -13,13 +13,23 @@ inputs (map, scan, jitter list) are resident in HBM before the timed region.  We
 
 `value` is the SAME form at every N -- the enqueue-only search, nothing returns to the host per step -- so that a 1 -> N curve
 measures the exchange, not a change of form.  The BLOCKING per-scan form (K1, the collective, the reduced key on the host before
-the next step: what a SLAM loop pays, CoreSLAMProcessor.cs:732 -> :750) is measured after the timed region at every N, N = 1
-included, and reported beside it (`config.per_scan_blocking_us_per_step`, `multi_gpu.per_scan_blocking_us_per_step`).
+the next step: what a SLAM loop pays, CoreSLAMProcessor.cs:732 -> :750) is measured with --full after the timed region at every
+N, N = 1 included, and reported beside it (`config.per_scan_blocking_us_per_step`, `multi_gpu.per_scan_blocking_us_per_step`).
 
 Timed region: barrier + device synchronise, t0, K x (one C call: the search's two launches [+ the collective's call]), one event
 record, ONE device synchronise, t1 -- event creation, the first event's record and every other synchronisation sit outside.
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+A plain run does only what `value` needs: set-up, the clock warm-up and the W warm-up steps, the K timed steps, the outputs
+(--dump-outputs) and the line (with `roofline` from the region's two events and the committed profiles).  Everything else this
+file measures or checks -- the cold-clock region, the blocking per-scan form, K1 on a new scan, the N > 1 section (same-form
+single rank, the bare collective, replica checks, the fused per-scan form, the oracle's check of the winner), the other
+configurations (`other_workloads`) and the CPU baseline -- runs only with --full.
+
+--dump-outputs DIR: what the last timed step computed, as a caller of the search receives it (the packed key, decoded by
+slamhip_cs_pose_from_key): DIR/best_distance.npy, DIR/best_index.npy (float64) and DIR/best_pose.npy (float32), rank 0 only.
+The inputs are seeded, so the same arguments give the same inputs in every run.
+
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
          N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                 --master-port P bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line.
@@ -55,6 +65,11 @@ def parse():
     ap.add_argument("--clock-warmup", type=int, default=3000,
                     help="untimed steps in front of the W warm-up steps that bring the device to its sustained clocks (0: none)")
     ap.add_argument("--no-extras", action="store_true", help="skip the other BASELINE.json configurations measured after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline (cold clocks, blocking per-scan form, N > 1 section, "
+                         "other configurations, CPU baseline); a plain run only times the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result (best_distance, best_index, best_pose) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -196,14 +211,14 @@ def main():
     # milliseconds of sustained work to reach what a scan loop that runs for seconds sees (measured on MI355X: 19.2 us per step after 6
     # launches, 18.9 after 20, 17.7 after 2000; 262 144 candidates: 125.8 / 119.4 / 114.9 us).  `value` is a throughput, so the
     # timed region is measured at sustained clocks: `--clock-warmup` untimed steps (default 3000, ~60 ms) run in front of the W
-    # warm-up steps; the same K steps measured BEFORE them, cold, are reported beside it (config.cold_clocks).
+    # warm-up steps; with --full the same K steps measured BEFORE them, cold, are reported beside it (config.cold_clocks).
     cold = None
     # (the interpreter's cyclic garbage collector stays out of the timed regions: with torch imported a full collection is a
     # pause of tens of milliseconds -- it once landed in a loop of 100 blocking calls and read as 440 us per call instead of 70;
     # collected HERE, before the clocks are brought up: a pause of that length lets them fall again)
     gc.collect()
     gc.disable()
-    if a.clock_warmup > 0:
+    if a.clock_warmup > 0 and a.full:
         for _ in range(max(a.warmup, 1)):
             step()
         sync_all()
@@ -216,6 +231,7 @@ def main():
         if world > 1:
             dist.barrier()
         cold = (time.perf_counter() - tc) / a.steps
+    if a.clock_warmup > 0:
         for _ in range(a.clock_warmup):
             step()
         sync_all()
@@ -269,32 +285,41 @@ def main():
         final_key = comm.wait()                                    # (flushes the last batch of keys; the reduced key of the last step)
     else:
         final_key = dev.key_read(ring_slot.value) if step is step_ring else int(key.item())
+    if a.dump_outputs and rank == 0:
+        # the last timed step's key as a caller of the search receives it, decoded by the library (slamhip_cs_pose_from_key)
+        best_pose, best_dist, best_idx = dev.pose_from_key(base, int(final_key))
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "best_distance.npy"), np.array([best_dist], np.float64))
+        np.save(os.path.join(a.dump_outputs, "best_index.npy"), np.array([best_idx], np.float64))
+        np.save(os.path.join(a.dump_outputs, "best_pose.npy"), np.asarray(best_pose, np.float32))
     k1_ms, k1_n = (0.0, 0)
     k1_how = "two HIP events on the operator's stream around the timed region"
     if two_events:
         k1_ms, k1_n = ev0.elapsed_time(ev1), a.steps
-    # ---- after the timed region: the blocking per-scan form, at every N ----------------------------------------------
-    n_ps = max(min(a.steps, 100), 20)
-    for _ in range(3):
-        step_blocking()
-    sync_all()
-    if world > 1:
-        dist.barrier()
-    gc.disable()
-    tb = time.perf_counter()
-    for _ in range(n_ps):
-        k_blocking = step_blocking()
-    dt_ps = time.perf_counter() - tb
-    gc.enable()
-    sync_all()
-    per_scan_us = dt_ps / n_ps * 1e6
-    blocking_key_ok = bool(int(k_blocking) == int(final_key))
+    # ---- after the timed region (--full): the blocking per-scan form, at every N ----------------------------------------------
+    per_scan_us, blocking_key_ok, n_ps = None, None, 0
+    if a.full:
+        n_ps = max(min(a.steps, 100), 20)
+        for _ in range(3):
+            step_blocking()
+        sync_all()
+        if world > 1:
+            dist.barrier()
+        gc.disable()
+        tb = time.perf_counter()
+        for _ in range(n_ps):
+            k_blocking = step_blocking()
+        dt_ps = time.perf_counter() - tb
+        gc.enable()
+        sync_all()
+        per_scan_us = dt_ps / n_ps * 1e6
+        blocking_key_ok = bool(int(k_blocking) == int(final_key))
     # ---- ... and K1 as a per-scan flow sees it: a NEW scan in front of every search (what CoreSLAMProcessor.Update launches: no layout
     # or cut made for this very scan -- the previous scan's are taken over when they are legal -- and a plan whose inputs changed).
     # Eight scans from poses a few centimetres apart, 48 blocking searches, K1's duration from per-launch HIP event pairs (the
     # library's own timers); beside it the same pairs around repeated searches of ONE scan (the headline's launch, same instrument).
     first_search = None
-    if world == 1 and not a.no_kernel_timing:
+    if world == 1 and a.full and not a.no_kernel_timing:
         try:
             rng_f = sim.PCG32(777)
             scans_f = []
@@ -325,7 +350,12 @@ def main():
             first_search = {"error": repr(e)}
         dev.set_scan(xy)
     multi = None
-    if world > 1 or comm is not None:
+    if world > 1 and not a.full:
+        # (a plain run at N > 1: the region's time is the max over ranks, as below)
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t[0].item())
+    if (world > 1 or comm is not None) and a.full:
         # ---- ... and, N > 1: this rank's search alone in the SAME form as the timed region (no collective: what N = 1 runs), K1's launch time where the
         # region could not give it, the bare collective ----------------------
         n_ov = max(a.steps, 100)
@@ -445,9 +475,6 @@ def main():
                        "collective": collective, "collective_ranks": collective_ranks,
                        "timed_region": ("%d steps, each one search launch (+ its plan launch on a stream of its own); one device synchronise inside" % a.steps) if world == 1 else
                                        ("%d steps, each one search launch + the key's all-reduce enqueued behind it -- the same enqueue-only form as N = 1; one device synchronise inside" % a.steps),
-                       "per_scan_blocking_us_per_step": per_scan_us,
-                       "per_scan_blocking_is": "the same search as a BLOCKING call per step (K1%s, the key on the host before the next step): %d steps after the timed region; its key equals the timed region's: %s"
-                                               % (" + the collective" if world > 1 or comm is not None else "", n_ps, blocking_key_ok),
                        "clock_warmup_steps": a.clock_warmup,
                        "cold_clocks": None if cold is None else {
                            "ms_per_step": cold * 1e3, "value": K_total / cold,
@@ -456,10 +483,14 @@ def main():
                        "best_index": final_key & 0xFFFFFFFF, "best_distance": final_key >> 32},
             "roofline": roof,
         }
+        if a.full:
+            out["config"]["per_scan_blocking_us_per_step"] = per_scan_us
+            out["config"]["per_scan_blocking_is"] = ("the same search as a BLOCKING call per step (K1%s, the key on the host before the next step): %d steps after the timed region; its key equals the timed region's: %s"
+                                                     % (" + the collective" if world > 1 or comm is not None else "", n_ps, blocking_key_ok))
         if multi is not None:
             out["multi_gpu"] = multi
         checks = []
-        if world == 1 and not a.no_extras:
+        if world == 1 and a.full and not a.no_extras:
             # the other configurations of BASELINE.json and larger candidate counts, measured in this very process AFTER the
             # timed region (they are not part of `value`): a few seconds in all.  `checks` collects, per configuration, the
             # inputs and the GPU's answer; the CPU leg below compares them with the oracle (the only place it is used).
@@ -468,11 +499,11 @@ def main():
             except Exception as e:                                 # noqa: BLE001 -- extras must never cost the headline line
                 out["other_workloads"] = {"error": repr(e)}
             gc.enable()
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a, dev, xy, base, offs, final_key, checks)
             if "other_workloads" in out and "error" not in out["other_workloads"]:
                 out["other_workloads"]["winners_match_oracle"] = out["cpu_baseline"].pop("other_workloads_match", None)
-        if world > 1:
+        if world > 1 and a.full:
             # N > 1: the reduced key of the last step against ONE oracle search over the whole flat list of K_total candidates
             # (rank 0's host, ~0.3 s at 131 072 candidates), so that a scaling line never carries a winner nobody verified; and
             # the CPU baseline on a short budget (the other ranks wait in the process group's teardown)

@@ -1105,7 +1105,7 @@ def test_bench_two_ranks_share_one_gpu():
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     env = dict(os.environ, SLAMHIP_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
-    common = ["--steps", "20", "--warmup", "3", "--size", "1024", "--map-updates", "8", "--no-cpu-baseline"]
+    common = ["--steps", "20", "--warmup", "3", "--size", "1024", "--map-updates", "8", "--no-cpu-baseline", "--full"]
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                          "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--cands", "4096"] + common,
                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
@@ -1679,7 +1679,7 @@ def test_bench_two_gpus_rccl():
         so.bind(("127.0.0.1", 0))
         port = so.getsockname()[1]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    common = ["--steps", "20", "--warmup", "3", "--size", "1024", "--map-updates", "8", "--no-cpu-baseline"]
+    common = ["--steps", "20", "--warmup", "3", "--size", "1024", "--map-updates", "8", "--no-cpu-baseline", "--full"]
     r2 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                          "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--cands", "4096"] + common,
                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
@@ -1809,7 +1809,7 @@ def test_bench_library_collective_one_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SLAMHIP_BENCH_COLLECTIVE="lib1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "3", "--size", "1024", "--map-updates", "8",
-                        "--cands", "4096", "--no-cpu-baseline", "--no-extras"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--cands", "4096", "--no-cpu-baseline", "--no-extras", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
     j = json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][0])
     assert "libslamhip" in j["config"]["collective"] and j["config"]["collective_ranks"] == 1
@@ -1819,3 +1819,47 @@ def test_bench_library_collective_one_rank():
     assert "its key equals the timed region's: True" in j["config"]["per_scan_blocking_is"]
     f = m["fused_scan_allreduce_and_update"]
     assert f["first_scan_key_equals_search_key"] is True and f["replicas_equal_after"] is True and f["us_per_scan"] > 0, f
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """bench.py without --full: the headline line only (none of the --full sections), and --dump-outputs writes the last timed
+    step's result -- the winner's distance, index and pose -- equal to the line's and the same in a second run (seeded inputs);
+    two ranks sharing this box's GPU (gloo carrying the key) over 2 x 4096 candidates dump the winner of one rank over all 8192."""
+    import json
+    import socket
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    common = ["--steps", "20", "--warmup", "3", "--size", "1024", "--map-updates", "8"]
+
+    def run(name, gpus, cands):
+        d = tmp_path / name
+        cmd = [os.path.join(root, "bench.py"), "--gpus", str(gpus), "--cands", str(cands), "--dump-outputs", str(d)] + common
+        env = dict(os.environ)
+        if gpus > 1:
+            with socket.socket() as so:
+                so.bind(("127.0.0.1", 0))
+                port = so.getsockname()[1]
+            cmd = ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus), "--master-addr", "127.0.0.1",
+                   "--master-port", str(port)] + cmd
+            env.update(SLAMHIP_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
+        r = subprocess.run([sys.executable] + cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
+        lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+        assert len(lines) == 1                                         # rank 0 prints exactly one JSON line
+        j = json.loads(lines[0])
+        for f in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert f in j, f
+        assert j["n_gpus"] == gpus and j["steps"] == 20 and j["value"] > 0 and j["ms_per_step"] > 0
+        assert "cpu_baseline" not in j and "other_workloads" not in j and "multi_gpu" not in j
+        assert "per_scan_blocking_us_per_step" not in j["config"] and j["config"]["cold_clocks"] is None
+        out = {n: np.load(str(d / (n + ".npy"))) for n in ("best_distance", "best_index", "best_pose")}
+        assert out["best_distance"].dtype == np.float64 and out["best_index"].dtype == np.float64 and out["best_pose"].dtype == np.float32
+        assert out["best_pose"].shape == (3,) and np.isfinite(out["best_pose"]).all()
+        assert (int(out["best_index"][0]), int(out["best_distance"][0])) == (j["config"]["best_index"], j["config"]["best_distance"])
+        return out
+
+    first = run("one_rank_a", 1, 8192)
+    for other in (run("one_rank_b", 1, 8192), run("two_ranks", 2, 4096)):
+        for n in first:
+            assert np.array_equal(first[n], other[n]), n

@@ -6,7 +6,7 @@ tag=${1:-k1b}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-bench="python3 $root/bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extras"
+bench="python3 $root/bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extras --full"
 : > $out/k1_budget.txt
 # (the EXP builds compute WRONG results: they are side variants selected with SLAMHIP_LIB -- tools/build_variant.py -- and never replace
 # slam.net_amd/libslamhip.so, so a killed run leaves the tree's library as it was)

@@ -14,13 +14,13 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$tag/prof
 rm -rf $out; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-bench="python3 $root/bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extras"
+bench="python3 $root/bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extras --full"
 SQ1="SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_INST_ANY"
 SQ2="SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM"
 run() { name=$1; shift; timeout 300 rocprofv3 "$@" > $out/$name.out 2> $out/$name.log; }
 # the plain run FIRST: counter passes put the device into the profiler's power state, and what runs on the box for a while afterwards
 # clocks differently (round 6: a native-caller Update of 48.7 us behind the passes, 41.3 - 42.4 us on fresh boxes)
-(cd $root && timeout 600 python3 bench.py > $out/bench.json 2> $out/bench.err)
+(cd $root && timeout 600 python3 bench.py --full > $out/bench.json 2> $out/bench.err)
 run stats     --kernel-trace --stats --output-format csv -d $out/stats -o stats -- $bench
 run stats262k --kernel-trace --stats --output-format csv -d $out/stats262k -o stats -- $bench --cands 262144 --steps 50
 run fetch     --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/fetch -o p -- $bench

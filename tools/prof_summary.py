@@ -111,7 +111,7 @@ if k1:
     json.dump({
         "kernel": k1,
         "workload": {"map": cfg.get("map"), "rays": cfg.get("rays"), "candidates_per_gpu": cfg.get("candidates_per_gpu")},
-        "command": "tools/prof_bench.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE | TCC_HIT TCC_MISS (separate passes) -- python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extras",
+        "command": "tools/prof_bench.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE | TCC_HIT TCC_MISS (separate passes) -- python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extras --full",
         "FETCH_SIZE_KB_per_launch": fs, "WRITE_SIZE_KB_per_launch": ws,
         "hbm_bytes_per_launch_raw": (fs + ws) * 1024.0,
         "hbm_bytes_per_launch_gfx950_corrected": (2.0 * fs + ws) * 1024.0,
@@ -177,7 +177,7 @@ def sq_summary(s1, s2, kernel, avg_ns, grbm=None):
 k1s = k1_of(c["sq1"])
 if k1s:
     json.dump({
-        "command": "tools/prof_bench.sh: rocprofv3 --kernel-trace --pmc <8 SQ counters> (two passes) -- python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extras [--cands 262144 --steps 50]",
+        "command": "tools/prof_bench.sh: rocprofv3 --kernel-trace --pmc <8 SQ counters> (two passes) -- python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-extras --full [--cands 262144 --steps 50]",
         "headline_16384_candidates": sq_summary(c["sq1"], c["sq2"], k1s, float(k1row["AverageNs"]) if k1row else None, c.get("grbm")),
         "at_262144_candidates": sq_summary(c["sq1_262k"], c.get("sq2_262k") or None, k1_of(c["sq1_262k"]) or "", float(k1row262["AverageNs"]) if k1row262 else None, c.get("grbm_262k")),
     }, open(os.path.join(dst, tag + "_k1_sq.json"), "w"), indent=1)
