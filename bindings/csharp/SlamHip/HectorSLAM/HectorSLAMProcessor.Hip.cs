@@ -20,7 +20,9 @@ namespace HectorSLAM.Main
         private readonly Device device;
         private readonly bool ownsDevice;
         private readonly Handle proc;
+        private readonly int numThreads;
         private float minDistanceDiff = 0.3f, minAngleDiff = 0.13f;
+        private bool referenceSummation;
 
         public MapRepMultiMap MapRep { get; private set; }
         public Vector3 LastMapUpdatePose { get; private set; }
@@ -42,15 +44,31 @@ namespace HectorSLAM.Main
             set { minAngleDiff = value; Native.Check(Native.slamhip_hsproc_set_thresholds(proc.Ptr, minDistanceDiff, minAngleDiff)); }
         }
 
+        /// <summary>Match in the reference's summation order for the constructor's numThreads (1..64): the matcher's H, dTr and
+        /// poses are then ScanMatcher(numThreads)'s bits (ScanMatcher.cs:149-195; slamhip_hs_set_match_threads on MapRep).
+        /// false (default): the device's own order, poses within 1e-4 m / 1e-4 rad of the reference's.</summary>
+        public bool ReferenceSummation
+        {
+            get => referenceSummation;
+            set
+            {
+                if (value && (numThreads < 1 || numThreads > 64))
+                    throw new InvalidOperationException("reference summation needs 1..64 threads");
+                Native.Check(Native.slamhip_hs_set_match_threads(MapRep.Pyramid.Ptr, value ? numThreads : 0));
+                referenceSummation = value;
+            }
+        }
+
         public HectorSLAMProcessor(float mapResolution, Point mapSize, Vector3 startPose, int numDepth, int numThreads, ILogger logger = null)
             : this(mapResolution, mapSize, startPose, numDepth, numThreads, logger, null)
         {
         }
 
-        /// <param name="numThreads">the reference's matcher threads (:75); the device needs none</param>
+        /// <param name="numThreads">the reference's matcher threads (:72); the device needs none, and sums in their order only with ReferenceSummation</param>
         public HectorSLAMProcessor(float mapResolution, Point mapSize, Vector3 startPose, int numDepth, int numThreads, ILogger logger, Device device)
         {
             this.logger = logger;
+            this.numThreads = numThreads;
             this.device = device ?? new Device(0);
             ownsDevice = device == null;
             Native.Check(Native.slamhip_hsproc_create(this.device.Ctx.Ptr, mapResolution, mapSize.X, mapSize.Y, startPose, numDepth, out IntPtr h));

@@ -416,6 +416,14 @@ int32_t slamhip_hs_match_level(slamhip_hs *hs, int32_t level, const float hint_p
 int32_t slamhip_hs_match_batch(slamhip_hs *hs, const float *hint_poses, int32_t B, float *out_poses);
 /* GetCompleteHessianDerivs (:135-204) at a map-coordinate pose: H row-major 3x3, dTr 3 */
 int32_t slamhip_hs_hessian(slamhip_hs *hs, int32_t level, const float pose_map[3], float H[9], float dTr[3]);
+/* ScanMatcher(numThreads) (ScanMatcher.cs:28-32,149-195): 0 = the device's own summation order (default);
+ * 1..64 = the reference's: ceil(n/T)-point chunks summed sequentially in binary32, partials added in thread order.
+ * (64: WaitHandle.WaitAll's limit in ParallelWorker.Work, BaseSLAM/ParallelWorker.cs:113-115.)
+ * A host-side setting of this hs, read by every later slamhip_hs_match, _match_level, _match_batch and _hessian and by
+ * slamhip_hsproc_update on the processor's own hs (slamhip_hsproc_hs); it survives slamhip_hs_reset.  With T >= 1, H and
+ * dTr are the reference's binary32 sums bit for bit, and a batch of any size returns the single match's bits.
+ * Any other value: SLAMHIP_ERR_INVALID, the setting unchanged. */
+int32_t slamhip_hs_set_match_threads(slamhip_hs *hs, int32_t num_threads);
 
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */

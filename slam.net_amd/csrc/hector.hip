@@ -69,6 +69,7 @@ struct slamhip_hs {
     // K5 line tables, per level: lines by index, lines sorted by (direction class, slope bucket), bucket starts, header
     void *d_k5_byidx, *d_k5_cand; int *d_k5_start, *d_k5_hdr; int cap_lines;
     int *d_k5_sec; int k5_sec_parity; bool k5_toggle_pending;                        // [2][HS_MAX_LEVELS][K5_SEC] sector records of the cell kernel: an update reads the set the last one wrote
+    int match_threads;                                     // slamhip_hs_set_match_threads: 0 the device's summation order, 1 .. HS_REF_MAX_T the reference's
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -166,6 +167,63 @@ template <int BDIM> struct hs_shape {
     static constexpr int PU = BDIM >= 1024 ? 2 : BDIM >= 512 ? 3 : 5;      // points per lane and pass (1080 rays: one pass)
     static constexpr int RED = 9 * NW;                                     // doubles per reduction block
 };
+
+// the per-iteration transform of GetCompleteHessianDerivs (:139-146), the same in every lane
+struct hs_iter_xf { sh_m3x2 t; float sinRot, cosRot, limx, limy; };
+__device__ static __forceinline__ hs_iter_xf hs_iter_transform(const hs_level_dev &L, const float pose[3])
+{
+    hs_iter_xf X;
+    float s, c;
+    sh_det_sincosf(pose[2], &s, &c);
+    X.t = sh_m3x2_mul(sh_m3x2_mul(hs_rotation_sc(pose[2], s, c),
+                                  sh_m3x2_translation(pose[0] * L.cell, pose[1] * L.cell)),
+                      sh_m3x2_scale(L.stm));                               // :139-142
+    X.sinRot = s * L.stm; X.cosRot = c * L.stm;                            // :145-146
+    X.limx = (float)L.w - 2.0f; X.limy = (float)L.h - 2.0f;               // MapProperties.cs:42
+    return X;
+}
+
+// one scan point i (i >= n: a padding lane, its terms are zero): the point and its four taps, requested without waiting
+struct hs_point { float2 p, r0, r1; float fx, fy; bool ok; };
+__device__ static __forceinline__ void hs_point_taps(const hs_level_dev &L, const float2 *pts, int i, int n, const hs_iter_xf &X, hs_point &q)
+{
+    q.p = i < n ? pts[i] : make_float2(0.f, 0.f);
+    float cx, cy;
+    sh_v2_transform(q.p.x, q.p.y, X.t, &cx, &cy);                          // :161
+    // InterpMapValueWithDerivatives (:211-249), MapProperties.cs:83-87
+    q.ok = i < n && !(!(cx == cx) || !(cy == cy) || cx < 0.0f || cx > X.limx || cy < 0.0f || cy > X.limy);
+    const float fxx = floorf(cx), fyy = floorf(cy);                        // :222
+    const int ix = q.ok ? (int)fxx : 0, iy = q.ok ? (int)fyy : 0;
+    q.fx = cx - fxx; q.fy = cy - fyy;                                      // :225
+    const int idx = iy * L.w + ix;                                         // :227
+#if HS_PROB_MODE == 0
+    __builtin_memcpy(&q.r0, L.prob + idx, sizeof(float2));                 // (two adjacent taps: one 8-byte load)
+    __builtin_memcpy(&q.r1, L.prob + idx + L.w, sizeof(float2));
+#else
+    int4 c0, c1;                                                           // (two adjacent cells {UpdateIndex, Value}: one 16-byte load)
+    __builtin_memcpy(&c0, L.cells + idx, sizeof(int4));
+    __builtin_memcpy(&c1, L.cells + idx + L.w, sizeof(int4));
+    q.r0 = make_float2(hs_prob_tap(__int_as_float(c0.y)), hs_prob_tap(__int_as_float(c0.w)));
+    q.r1 = make_float2(hs_prob_tap(__int_as_float(c1.y)), hs_prob_tap(__int_as_float(c1.w)));
+#endif
+}
+
+// the point's nine terms (:162-180) in the order of sums[]: the interpolation and the products, each a binary32 rounding
+__device__ static __forceinline__ void hs_point_terms(const hs_point &q, const hs_iter_xf &X, float tm[9])
+{
+    const float i0 = q.r0.x, i1 = q.r0.y, i2 = q.r1.x, i3 = q.r1.y;        // :230-233
+    const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;    // :235-239
+    const float xi = 1.0f - q.fx, yi = 1.0f - q.fy;                        // :241-242
+    float P = ((i0 * xi + i1 * q.fx) * yi) + ((i2 * xi + i3 * q.fx) * q.fy);   // :245-246
+    float gx = -((dx1 * xi) + (dx2 * q.fx));                               // :247
+    float gy = -((dy1 * yi) + (dy2 * q.fy));                               // :248
+    if (!q.ok) { P = 0.0f; gx = 0.0f; gy = 0.0f; }                         // :216-219
+    const float fun = 1.0f - P;                                            // :164
+    const float rot = ((-X.sinRot * q.p.x - X.cosRot * q.p.y) * gx + (X.cosRot * q.p.x - X.sinRot * q.p.y) * gy);   // :169-170
+    tm[0] = gx * fun;  tm[1] = gy * fun;  tm[2] = rot * fun;               // :166,:167,:172
+    tm[3] = gx * gx;   tm[4] = gy * gy;   tm[5] = rot * rot;               // :174-176
+    tm[6] = gx * gy;   tm[7] = gx * rot;  tm[8] = gy * rot;                // :178-180
+}
 
 template <int BDIM, bool LDSP>
 __device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, const float2 *pts, int n, const float pose[3],
@@ -276,6 +334,118 @@ __device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, c
 #endif
 }
 
+// ---- the reference's summation order (slamhip_hs_set_match_threads, opt-in) ---------------------------------------------------
+// GetCompleteHessianDerivs with ScanMatcher(numThreads = T) (:149-195): the scan is cut into T chunks of ceil(n / T) points,
+// chunk c = [c * chunk, min(n, (c + 1) * chunk)); each thread sums its chunk's nine terms point after point in binary32 from
+// +0, and the nine totals are 0 + partial[0] + ... + partial[T - 1] in thread order.  Per window of W points (one pass of
+// hs_hessian_block's loop) every lane forms its points' terms -- hs_point_taps / hs_point_terms, the same floats as the
+// default order's -- into LDS as [9][WS]; then lane j < 9T runs chain (c = j / 9, k = j % 9) over the window's part of chunk c,
+// its partial carried in a register from window to window.  No binary64, no tree: the result depends on T alone, not on the
+// workgroup's width, so a batch of any size gives the single match's bits.
+#define HS_REF_MAX_T 64                    // ParallelWorker.Work waits with WaitHandle.WaitAll: at most 64 handles (BaseSLAM/ParallelWorker.cs:113-115)
+template <int BDIM> struct hs_ref_shape {
+    static constexpr int W = BDIM * hs_shape<BDIM>::PU;                    // points per window (1080 rays: one window at any width)
+    static constexpr int WS = W + 4;                                       // row stride in floats: rows 16-B aligned, and the nine rows
+                                                                           // four banks apart (one chunk's nine chains: no conflict)
+    static constexpr int CR = (9 * HS_REF_MAX_T + BDIM - 1) / BDIM;        // chains per lane
+};
+template <int BDIM> struct __attribute__((aligned(16))) hs_ref_lds {
+    float terms[9 * hs_ref_shape<BDIM>::WS];                               // 256 lanes: 46 KB -> 65 KB per workgroup, two per CU
+    float part[9 * HS_REF_MAX_T];                                          // [c][k] the chunks' partials
+    float sums[9];
+};
+// the kernel's one block (a static in a device function: one allocation per kernel that calls it, none in the default kernels)
+template <int BDIM> __device__ static __forceinline__ hs_ref_lds<BDIM> &hs_ref_lds_of()
+{
+    __shared__ hs_ref_lds<BDIM> s;
+    return s;
+}
+
+// acc + row[lo] + row[lo + 1] + ... + row[hi - 1], in that order.  Blocks of 32 in two register sets that take turns: the
+// sixteen values of one set are requested while the other set's sixteen are added (no copies between the sets)
+#define HS_ADD4(v) { acc += (v).x; acc += (v).y; acc += (v).z; acc += (v).w; }
+__device__ static __forceinline__ float hs_chain(const float *row, int lo, int hi, float acc)
+{
+    int i = lo;
+    for (; i < hi && (i & 3); i++) acc += row[i];
+    if (i + 32 <= hi) {
+        float4 a[4], b[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) { a[q] = *(const float4 *)(row + i + 4 * q); b[q] = *(const float4 *)(row + i + 16 + 4 * q); }
+        for (i += 32; i + 32 <= hi; i += 32) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) HS_ADD4(a[q]);
+#pragma unroll
+            for (int q = 0; q < 4; q++) a[q] = *(const float4 *)(row + i + 4 * q);
+#pragma unroll
+            for (int q = 0; q < 4; q++) HS_ADD4(b[q]);
+#pragma unroll
+            for (int q = 0; q < 4; q++) b[q] = *(const float4 *)(row + i + 16 + 4 * q);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; q++) HS_ADD4(a[q]);
+#pragma unroll
+        for (int q = 0; q < 4; q++) HS_ADD4(b[q]);
+    }
+    for (; i + 4 <= hi; i += 4) { const float4 v = *(const float4 *)(row + i); HS_ADD4(v); }
+    for (; i < hi; i++) acc += row[i];
+    return acc;
+}
+#undef HS_ADD4
+
+// sums[9] in the order of hs_hessian_block, uniform in every thread; T in 1 .. HS_REF_MAX_T.  Barriers: one per window after the
+// terms are stored (and one before the store of every window after the first), two for the totals.
+template <int BDIM>
+__device__ static __forceinline__ void hs_hessian_ref(const hs_level_dev &L, const float2 *pts, int n, const float pose[3], int T,
+                                                      hs_ref_lds<BDIM> &S, float sums[9])
+{
+    constexpr int PU = hs_shape<BDIM>::PU, W = hs_ref_shape<BDIM>::W, WS = hs_ref_shape<BDIM>::WS, CR = hs_ref_shape<BDIM>::CR;
+    const hs_iter_xf X = hs_iter_transform(L, pose);
+    const int chunk = (n + T - 1) / T;                                     // :149
+    const int tid = threadIdx.x;
+    float part[CR];
+#pragma unroll
+    for (int r = 0; r < CR; r++) part[r] = 0.0f;                           // :156-157
+    for (int base = 0; base < n; base += W) {
+        hs_point q[PU];
+#pragma unroll
+        for (int u = 0; u < PU; u++) hs_point_taps(L, pts, base + tid + u * BDIM, n, X, q[u]);
+        float tm[PU][9];
+#pragma unroll
+        for (int u = 0; u < PU; u++) hs_point_terms(q[u], X, tm[u]);
+        if (base > 0) __syncthreads();                                     // (the previous window's chains have read their terms)
+#pragma unroll
+        for (int u = 0; u < PU; u++)
+#pragma unroll
+            for (int k = 0; k < 9; k++) S.terms[k * WS + tid + u * BDIM] = tm[u][k];
+        __syncthreads();
+        const int end = min(n, base + W);
+#pragma unroll
+        for (int r = 0; r < CR; r++) {
+            const int j = tid + r * BDIM;
+            if (j < 9 * T) {
+                const int c = j / 9, k = j - 9 * c;
+                const int lo = max(c * chunk, base), hi = min(min(c * chunk + chunk, n), end);   // :159 Skip / Take
+                if (lo < hi) part[r] = hs_chain(S.terms + k * WS, lo - base, hi - base, part[r]);   // :166-180
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < CR; r++) {
+        const int j = tid + r * BDIM;
+        if (j < 9 * T) S.part[j] = part[r];
+    }
+    __syncthreads();
+    if (tid < 9) {
+        float s = 0.0f;                                                    // :188-189
+        for (int c = 0; c < T; c++) s += S.part[9 * c + tid];              // :191-195 (empty chunks: +0)
+        S.sums[tid] = s;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 9; k++) sums[k] = S.sums[k];
+}
+
 // EstimateTransformationLogLh (:93-125) applied by every thread identically (uniform registers)
 __device__ static inline void hs_step(const float sums[9], float est[3])
 {
@@ -295,11 +465,12 @@ __device__ static inline void hs_step(const float sums[9], float est[3])
 
 // MatchData(MapRepMultiMap) (:41-54): one workgroup per hint; levels coarse -> fine.
 // only_level >= 0 restricts to one level with `iters_override` iterations (MatchData(OccGridMap), :64-84).
-template <int BDIM>
+// REF: the reference's summation order for ref_threads = T chunks (hs_hessian_ref); the default instantiations ignore ref_threads.
+template <int BDIM, bool REF>
 __global__ void __launch_bounds__(BDIM)
 k4_match(hs_levels_arg A, const float2 *__restrict__ pts, int n, const float *__restrict__ hints, float3 hint1,
          float *__restrict__ out, int only_level, int iters_override, uint32_t *mail, uint32_t mail_seq,
-         const float2 *up_src, float2 *up_dst, uint32_t *up_flag, uint32_t up_seq, int n_helpers_from)
+         const float2 *up_src, float2 *up_dst, uint32_t *up_flag, uint32_t up_seq, int n_helpers_from, int ref_threads)
 {
     __shared__ double red[2 * hs_shape<BDIM>::RED];
     __shared__ float2 pts_s[HS_LDS_PTS];
@@ -387,9 +558,14 @@ k4_match(hs_levels_arg A, const float2 *__restrict__ pts, int n, const float *__
             const int iters = only_level >= 0 ? iters_override : L.iterations;
             for (int it = 0; it < iters; it++) {                           // :70-73
                 float sums[9];
-                if (in_lds) hs_hessian_block<BDIM, true>(L, pts_s, n, est, red + par, sums);
-                else hs_hessian_block<BDIM, false>(L, pts, n, est, red + par, sums);
-                par ^= hs_shape<BDIM>::RED;                                // (a block is written again two barriers after it was read)
+                if constexpr (REF) {
+                    if (in_lds) hs_hessian_ref<BDIM>(L, pts_s, n, est, ref_threads, hs_ref_lds_of<BDIM>(), sums);
+                    else hs_hessian_ref<BDIM>(L, pts, n, est, ref_threads, hs_ref_lds_of<BDIM>(), sums);
+                } else {
+                    if (in_lds) hs_hessian_block<BDIM, true>(L, pts_s, n, est, red + par, sums);
+                    else hs_hessian_block<BDIM, false>(L, pts, n, est, red + par, sums);
+                    par ^= hs_shape<BDIM>::RED;                            // (a block is written again two barriers after it was read)
+                }
                 hs_step(sums, est);
             }
             est[2] = sh_normalize_angle(est[2]);                           // :76
@@ -406,14 +582,16 @@ k4_match(hs_levels_arg A, const float2 *__restrict__ pts, int n, const float *__
     }
 }
 
+template <bool REF>
 __global__ void __launch_bounds__(256)
 k4_hessian(hs_levels_arg A, int level, const float2 *__restrict__ pts, int n, const float *__restrict__ pose_in,
-           float *__restrict__ out12)
+           float *__restrict__ out12, int ref_threads)
 {
     __shared__ double red[hs_shape<256>::RED];
     float pose[3] = { pose_in[0], pose_in[1], pose_in[2] };
     float sums[9];
-    hs_hessian_block<256, false>(A.lv[level], pts, n, pose, red, sums);
+    if constexpr (REF) hs_hessian_ref<256>(A.lv[level], pts, n, pose, ref_threads, hs_ref_lds_of<256>(), sums);
+    else hs_hessian_block<256, false>(A.lv[level], pts, n, pose, red, sums);
     if (threadIdx.x == 0) {
         out12[0] = sums[3]; out12[1] = sums[6]; out12[2] = sums[7];
         out12[3] = sums[6]; out12[4] = sums[4]; out12[5] = sums[8];
@@ -1392,11 +1570,18 @@ static int32_t run_match(slamhip_hs *hs, const float *hints, int B, float *out, 
         // (a single full match in the per-scan flow brings helper workgroups: k4_match)
         static const int helpers_env = getenv("SLAMHIP_K4_HELPERS") ? atoi(getenv("SLAMHIP_K4_HELPERS")) : 1;
         const int helpers = B == 1 && only_level < 0 && hs->n_levels > 1 && hs->n_points > 0 && helpers_env > 0 ? 8 * helpers_env : 0;
-#define K4_LAUNCH(BD) hipLaunchKernelGGL(k4_match<BD>, dim3(B + helpers), dim3(BD), 0, ctx->stream, levels_arg(hs), hs->d_pts, hs->n_points, d_hints, h1, d_out, \
-                                         only_level, iters, mb, mail_seq, up_src, up_dst, up_flag, up_seq, helpers ? B : 0)
-        if (lanes == 1024) K4_LAUNCH(1024);
-        else if (lanes == 512) K4_LAUNCH(512);
-        else K4_LAUNCH(256);
+        const int T = hs->match_threads;
+#define K4_LAUNCH(BD, REF) hipLaunchKernelGGL((k4_match<BD, REF>), dim3(B + helpers), dim3(BD), 0, ctx->stream, levels_arg(hs), hs->d_pts, hs->n_points, d_hints, \
+                                              h1, d_out, only_level, iters, mb, mail_seq, up_src, up_dst, up_flag, up_seq, helpers ? B : 0, T)
+        if (T == 0) {
+            if (lanes == 1024) K4_LAUNCH(1024, false);
+            else if (lanes == 512) K4_LAUNCH(512, false);
+            else K4_LAUNCH(256, false);
+        } else {                                                          // (the reference's order: the same bits at every width)
+            if (lanes == 1024) K4_LAUNCH(1024, true);
+            else if (lanes == 512) K4_LAUNCH(512, true);
+            else K4_LAUNCH(256, true);
+        }
 #undef K4_LAUNCH
     }
     SH_HIP(hipGetLastError());
@@ -1432,6 +1617,13 @@ static int32_t run_match(slamhip_hs *hs, const float *hints, int B, float *out, 
     return SLAMHIP_OK;
 }
 
+extern "C" int32_t slamhip_hs_set_match_threads(slamhip_hs *hs, int32_t num_threads)
+{
+    SH_CHECK_ARG(hs && num_threads >= 0 && num_threads <= HS_REF_MAX_T);
+    hs->match_threads = num_threads;                                      // (read by the next launch of K4: nothing on the device)
+    return SLAMHIP_OK;
+}
+
 extern "C" int32_t slamhip_hs_match(slamhip_hs *hs, const float hint[3], float out[3])
 {
     SH_CHECK_ARG(hs && hint && out);
@@ -1459,8 +1651,12 @@ extern "C" int32_t slamhip_hs_hessian(slamhip_hs *hs, int32_t level, const float
     SH_TRY(hs_flush_scan(hs));
     memcpy(hs->h_io, pose_map, sizeof(float) * 3);
     SH_HIP(hipMemcpyAsync(hs->d_io, hs->h_io, sizeof(float) * 3, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k4_hessian, dim3(1), dim3(256), 0, ctx->stream, levels_arg(hs), level, hs->d_pts, hs->n_points,
-                       (const float *)hs->d_io, hs->d_io + 16);
+    if (hs->match_threads == 0)
+        hipLaunchKernelGGL(k4_hessian<false>, dim3(1), dim3(256), 0, ctx->stream, levels_arg(hs), level, hs->d_pts, hs->n_points,
+                           (const float *)hs->d_io, hs->d_io + 16, 0);
+    else
+        hipLaunchKernelGGL(k4_hessian<true>, dim3(1), dim3(256), 0, ctx->stream, levels_arg(hs), level, hs->d_pts, hs->n_points,
+                           (const float *)hs->d_io, hs->d_io + 16, hs->match_threads);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(hs->h_io + 16, hs->d_io + 16, sizeof(float) * 12, hipMemcpyDeviceToHost, ctx->stream));
     SH_HIP(hipStreamSynchronize(ctx->stream));

@@ -109,6 +109,11 @@ class MapRepMultiMap:
     def Reset(self):
         capi.call("slamhip_hs_reset", self._h)
 
+    def set_match_threads(self, numThreads):
+        """The matcher's summation order on this pyramid (slamhip_hs_set_match_threads): 0 the device's own (default),
+        1 .. 64 the reference's ScanMatcher(numThreads) chunks (ScanMatcher.cs:149-195), bit for bit."""
+        capi.call("slamhip_hs_set_match_threads", self._h, int(numThreads))
+
     def SetUpdateFactorFree(self, factor):
         self._free = float(factor)
         capi.call("slamhip_hs_set_factors", self._h, C.c_float(factor), C.c_float(getattr(self, "_occ", 0.9)))
@@ -133,14 +138,21 @@ class MapRepMultiMap:
 
 
 class ScanMatcher:
-    """HectorSLAM/Matcher/ScanMatcher.cs:18-271.  numThreads is accepted for source compatibility; the
-    point-chunk fan-out it controlled (:149-185) is the workgroup reduction of kernel K4."""
+    """HectorSLAM/Matcher/ScanMatcher.cs:18-271.  By default numThreads is accepted for source compatibility and the
+    point-chunk fan-out it controlled (:149-185) is the workgroup reduction of kernel K4.  With referenceSummation=True
+    the matcher sums as the reference does with numThreads threads, bit for bit: every match sets that order on its
+    target pyramid first (MapRepMultiMap.set_match_threads); without it every match sets the default order (0)."""
 
-    def __init__(self, numThreads=1, logger=None):
+    def __init__(self, numThreads=1, logger=None, referenceSummation=False):
         self.numThreads = numThreads
+        self.referenceSummation = bool(referenceSummation)
+
+    def _order(self, rep):
+        rep.set_match_threads(self.numThreads if self.referenceSummation else 0)
 
     def MatchData(self, target, scan, hintPose):
         hint = capi.f32(hintPose); out = np.empty(3, np.float32)
+        self._order(target if isinstance(target, MapRepMultiMap) else target._rep)
         if isinstance(target, MapRepMultiMap):                      # :41
             target.set_scan(scan)
             capi.call("slamhip_hs_match", target._h, capi.fptr(hint), capi.fptr(out))
@@ -152,6 +164,7 @@ class ScanMatcher:
 
     def MatchDataBatch(self, rep, scan, hintPoses):
         hints = capi.f32(hintPoses, (-1, 3)); out = np.empty_like(hints)
+        self._order(rep)
         rep.set_scan(scan)
         capi.call("slamhip_hs_match_batch", rep._h, capi.fptr(hints), hints.shape[0], capi.fptr(out))
         return out
@@ -163,7 +176,8 @@ class ScanMatcher:
 class HectorSLAMProcessor:
     """HectorSLAM/Main/HectorSLAMProcessor.cs:17-160"""
 
-    def __init__(self, mapResolution, mapSize, startPose, numDepth, numThreads=1, logger=None, ctx=None):
+    def __init__(self, mapResolution, mapSize, startPose, numDepth, numThreads=1, logger=None, ctx=None,
+                 referenceSummation=False):
         self._own_ctx = ctx is None
         self.ctx = ctx or Context(0)
         sp = capi.f32(startPose)
@@ -173,6 +187,8 @@ class HectorSLAMProcessor:
         hsh = C.c_void_p()
         capi.call("slamhip_hsproc_hs", self._h, C.byref(hsh))
         self.MapRep = MapRepMultiMap(mapResolution, mapSize, numDepth, ctx=self.ctx, _handle=hsh)
+        if referenceSummation:                                      # the processor's matcher, ScanMatcher(numThreads) (:72)
+            self.MapRep.set_match_threads(numThreads)
         self._min_dist, self._min_angle = 0.3, 0.13
 
     def _get(self):

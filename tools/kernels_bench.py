@@ -1,5 +1,7 @@
 """Secondary-kernel timings (K2 HoleMap update, K3 ObstacleMap update, K4 Hector match, K5 Hector grid update,
-fused search+update) on one MI355X, with the algorithmic byte counts of SURVEY.md sec.8d.  Prints one JSON object."""
+fused search+update) on one MI355X, with the algorithmic byte counts of SURVEY.md sec.8d, and the Hector matcher in the
+reference's summation order (ScanMatcher(T, referenceSummation=True), T = 1, 4, 16, beside the default order).  Prints one
+JSON object.  --hector-only: the Hector part alone."""
 import json, math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -8,7 +10,7 @@ import slam.net_amd.capi as capi, slam.net_amd.coreslam as cs, slam.net_amd.hect
 out = {}
 ctx = cs.Context(0)
 segs = sim.default_field()
-for size in (1024, 2048, 4096):
+for size in (() if "--hector-only" in sys.argv else (1024, 2048, 4096)):
     dev = cs.CoreSlamDevice(ctx, 40.0, size, size // 4)
     rng = sim.PCG32(1234); traj = sim.trajectory(40)
     scans = [sim.make_scan(segs, p, 1080, rng)[1] for p in traj]
@@ -81,4 +83,34 @@ out["k4_hector_match_3lvl_2048"] = {"kernel_us_single": ms4 / n4 * 1e3, "blockin
                                     "batch": B, "kernel_us_batch": ms4b / n4b * 1e3, "matches_per_s_batched": B / (ms4b / n4b * 1e-3),
                                     "point_iterations_per_s_batched": B * pt_iters / (ms4b / n4b * 1e-3),
                                     "algorithmic_GBps_batched": B * pt_iters * 24 / (ms4b / n4b * 1e-3) / 1e9}
+
+# the reference's summation order (slamhip_hs_set_match_threads): single match, a 64-hint batch and HectorSLAMProcessor.Update
+# (2048^2 x 3 levels, 1080 rays, 30 matched scans after 10 mapped ones), each beside the default order (T = 0)
+hints64 = hints[:64].copy()
+rs = {}
+for T in (0, 1, 4, 16):
+    m = hs.ScanMatcher(max(T, 1), referenceSummation=T > 0)
+    ctx.timing_enable(-1)
+    for _ in range(3): m.MatchData(rep, scan, hint)
+    ctx.timing_reset()
+    for _ in range(50): m.MatchData(rep, scan, hint)
+    ms1, n1 = ctx.timing_get(capi.K_HS_MATCH)
+    m.MatchDataBatch(rep, scan, hints64); ctx.timing_reset()
+    for _ in range(20): m.MatchDataBatch(rep, scan, hints64)
+    ms64, n64 = ctx.timing_get(capi.K_HS_MATCH)
+    ctx.timing_enable(0)
+    proc = hs.HectorSLAMProcessor(40.0 / 2048, (2048, 2048), scans[0][1], 3, max(T, 1), ctx=ctx, referenceSummation=T > 0)
+    rng = sim.PCG32(77)
+    pscans = [hs.ScanCloud(sim.make_scan(segs, np.array([20 + 0.03 * i, 20 + 0.01 * i, 0.004 * i], np.float32), 1080, rng)[1])
+              for i in range(40)]
+    for i in range(10): proc.Update(pscans[i], proc.MatchPose, True)
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    for i in range(10, 40): proc.Update(pscans[i], proc.MatchPose, False)
+    ctx.synchronize()
+    upd = (time.perf_counter() - t0) / 30
+    proc.Dispose()
+    rs["T%d" % T] = {"kernel_us_single": ms1 / n1 * 1e3, "kernel_us_batch64": ms64 / n64 * 1e3, "processor_update_us": upd * 1e6}
+rep.set_match_threads(0)
+out["k4_hector_match_refsum_3lvl_2048"] = rs
 print(json.dumps(out, indent=1))
