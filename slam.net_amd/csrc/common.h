@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -18,6 +19,13 @@ void slamhip_set_error(const char *fmt, ...);
 #define SH_CHECK_ARG(cond) do { if (!(cond)) { slamhip_set_error("invalid argument: %s (%s:%d)", #cond, __FILE__, __LINE__); \
         return SLAMHIP_ERR_INVALID; } } while (0)
 #define SH_TRY(expr) do { int32_t r_ = (expr); if (r_ != SLAMHIP_OK) return r_; } while (0)
+
+// The SLAMHIP_* runtime options (INTEGRATION.md lists them): every option is read through one of these, at one place in the
+// sources.  A flag counts when the variable is set at all; a number set to the empty string counts as unset.
+static inline bool sh_env_set(const char *name) { return getenv(name) != nullptr; }
+static inline const char *sh_env_str(const char *name) { return getenv(name); }
+static inline long long sh_env_int(const char *name, long long dflt) { const char *v = getenv(name); return v && *v ? atoll(v) : dflt; }
+static inline double sh_env_real(const char *name, double dflt) { const char *v = getenv(name); return v && *v ? atof(v) : dflt; }
 
 struct slamhip_ctx {
     int device;

@@ -77,12 +77,12 @@ extern "C" int32_t slamhip_ctx_create(int32_t device, slamhip_ctx **out)
         pthread_mutex_init(&c->mail_lock, &at);
         pthread_mutexattr_destroy(&at);
     }
-    c->mail_off = getenv("SLAMHIP_NO_HOSTWAIT") && atoi(getenv("SLAMHIP_NO_HOSTWAIT"));
-    c->wait_timeout_ms = getenv("SLAMHIP_WAIT_TIMEOUT_MS") ? atoll(getenv("SLAMHIP_WAIT_TIMEOUT_MS")) : 10000;
+    c->mail_off = (int)sh_env_int("SLAMHIP_NO_HOSTWAIT", 0) != 0;
+    c->wait_timeout_ms = sh_env_int("SLAMHIP_WAIT_TIMEOUT_MS", 10000);
     {
         int lb = 0;
         if (hipDeviceGetAttribute(&lb, hipDeviceAttributeIsLargeBar, device) != hipSuccess) { lb = 0; (void)hipGetLastError(); }
-        c->large_bar = lb != 0 && !c->mail_off && !getenv("SLAMHIP_NO_DIRECT_UPLOAD");
+        c->large_bar = lb != 0 && !c->mail_off && !sh_env_set("SLAMHIP_NO_DIRECT_UPLOAD");
     }
     *out = c;
     return SLAMHIP_OK;

@@ -331,7 +331,7 @@ extern "C" int32_t slamhip_cs_holemap_mirror_wait(slamhip_cs *cs, int32_t out_re
 // staging buffer of the library's own and copied by the HOST in the waiting call, row range by row range.
 static bool mirror_owns_pages(const void *p, size_t bytes)
 {
-    static const bool never = getenv("SLAMHIP_MIRROR_NOREG") != nullptr;
+    static const bool never = sh_env_set("SLAMHIP_MIRROR_NOREG");
     return !never && ((uintptr_t)p & 4095u) == 0 && (bytes & 4095u) == 0 && bytes >= 4096;
 }
 static int32_t mirror_stage(slamhip_cs *cs)
@@ -593,16 +593,14 @@ extern "C" int32_t slamhip_cs_holemap_mirror_async(slamhip_cs *cs, uint16_t *pix
     cs->mirror_user = pix; cs->mirror_direct = direct;
     cs->mirror_on = true;
     if (fresh) SH_TRY(cs_holemap_span_set(cs, true));
-    static const int mirror_lines = getenv("SLAMHIP_MIRROR_LINES") ? atoi(getenv("SLAMHIP_MIRROR_LINES")) : 1;
     hipLaunchKernelGGL(k_mirror_sum_rest, dim3(1), dim3(64), 0, ctx->stream, cs->d_mirror_sum);
     hipLaunchKernelGGL(k_mirror_snapshot, dim3(sh_div_up(cs->hs, 4)), dim3(256), 0, ctx->stream, (const uint16_t *)cs->d_hole, cs->d_hole_shadow,
                        cs->d_hole_span, cs->d_hole_span_snap, cs->d_mirror_mask, cs->mirror_chunks, cs->hs, fresh ? 1 : 0,
-                       (mirror_lines && cs->hs % 32 == 0) ? 1 : 0, cs->d_mirror_sum, cs->d_mirror_rows);
+                       cs->hs % 32 == 0 ? 1 : 0, cs->d_mirror_sum, cs->d_mirror_rows);
     SH_HIP(hipGetLastError());
     SH_HIP(hipEventRecord(cs->ev_snap, ctx->stream));
     SH_HIP(hipStreamWaitEvent(cs->mirror_stream, cs->ev_snap, 0));
-    static const int push_wgs = getenv("SLAMHIP_MIRROR_WGS") ? atoi(getenv("SLAMHIP_MIRROR_WGS")) : 32;
-    hipLaunchKernelGGL(k_mirror_push, dim3(push_wgs > 0 ? push_wgs : 32), dim3(256), 0, cs->mirror_stream, (const uint16_t *)cs->d_hole_shadow,
+    hipLaunchKernelGGL(k_mirror_push, dim3(32), dim3(256), 0, cs->mirror_stream, (const uint16_t *)cs->d_hole_shadow,
                        (const int2 *)cs->d_hole_span_snap, (const unsigned long long *)cs->d_mirror_mask, cs->mirror_chunks, dst, cs->hs,
                        (const int *)cs->d_mirror_sum, cs->h_mirror_sum, (const int2 *)cs->d_mirror_rows, direct ? (int2 *)nullptr : cs->h_mirror_rows);
     SH_HIP(hipGetLastError());
@@ -721,8 +719,7 @@ static int32_t cs_set_scan_finish(slamhip_cs *cs, const float *xy, int32_t n, bo
 #define SH_MAXF(a, b) ((a) > (b) ? (a) : (b))
     bool sane = true;
     std::vector<uint64_t> &keys = cs->h_sort_keys;                 // (kept between scans: no allocation per scan)
-    static const float cell_px = getenv("SLAMHIP_RB_CELL") ? (float)atof(getenv("SLAMHIP_RB_CELL")) : 64.0f;   // (tuning override: the Z-order's cell, pixels)
-    const float icell = cs->hscale / (cell_px >= 8.0f ? cell_px : 64.0f);         // 64-pixel cells per metre (ordering only: any monotone map of the coordinates does)
+    const float icell = cs->hscale / 64.0f;                        // 64-pixel cells per metre (ordering only: any monotone map of the coordinates does)
     // cell coordinates of every point (a branch-free loop over the 2 n floats: vectorised), their minima, and the sanity flag
     std::vector<int> &cellxy = cs->h_cell_xy;
     cellxy.resize((size_t)n * 2);
@@ -820,28 +817,22 @@ static int32_t cs_set_scan_finish(slamhip_cs *cs, const float *xy, int32_t n, bo
     // pixels square and should fit the 60 KB LDS tile (~173 px square) -- at fine map scales the spread (known from the
     // last candidate list, else the reference's default sigma of 0.1 m: ~0.7 m) takes a large part of that.  Measured on
     // MI355X at 4096^2 / 32768 candidates: 96 px blocks are 1.28x faster than 128 px ones.
-    static const int ext_env = getenv("SLAMHIP_RB_EXTENT") ? atoi(getenv("SLAMHIP_RB_EXTENT")) : 0;   // (tuning override)
     float spread_px = 0.7f * cs->hscale;
     for (size_t g = 0; g < cs->h_grp_dxy.size(); g++) if (g == 0 || cs->h_grp_dxy[g] > spread_px) spread_px = g == 0 ? cs->h_grp_dxy[0] : cs->h_grp_dxy[g];
     float ext_px = 165.0f - spread_px;
     if (!(ext_px <= CS_RB_EXTENT_PX)) ext_px = CS_RB_EXTENT_PX;
     if (ext_px < 64.0f) ext_px = 64.0f;
     if (cs->n_offs + 1 >= 131072) ext_px = CS_RB_EXTENT_PX;   // (very many candidates: two bands of a big block beat more, smaller blocks -- measured)
-    if (ext_env > 0) ext_px = (float)ext_env;
     const float ext = ext_px / cs->hscale;                     // block extent limit in metres
     // A block's tile is the box of its end points in the MAP frame, grown by the candidates' translation spread and the arc their
     // theta range sweeps: a block that is large in both directions there -- a corner of the room -- overflows the tile budget even
     // within the extent limit and is staged in bands at more than twice the cost, for every candidate group (seen at the headline
     // size: one such block kept twelve workgroups 17 us in a 19 us launch).  So the limits are tested on the points turned by the
-    // last search heading (the layout's; 0 before the first search), and the box area, margins included, CAN be limited too
-    // (SLAMHIP_RB_AREA = fraction of the tile budget).  Measured at the headline size, us per search: no area limit 18.9, 0.8 of
-    // the budget 20.2 (more, smaller blocks: more tile steps) -- off by default; the ranges' cuts avoid banded pieces instead
-    // (k1_cuts_banded_rays, distance.hip).
-    static const float area_f = getenv("SLAMHIP_RB_AREA") ? (float)atof(getenv("SLAMHIP_RB_AREA")) : 0.0f;    // of the tile budget; <= 0: no area limit (the default: see below)
+    // last search heading (the layout's; 0 before the first search).  (A limit on the box area as well, margins included, measured
+    // slower at the headline size: 0.8 of the tile budget 20.2 us per search against 18.9 without -- more, smaller blocks: more tile
+    // steps; the ranges' cuts avoid banded pieces instead: k1_cuts_banded_rays, distance.hip.)
     const float rth = cs->k1_layout_theta;
     const float rc = cosf(rth), rs = sinf(rth);
-    const float marg = (spread_px + 40.0f) / cs->hscale;       // metres: translation spread + a nominal arc
-    const float amax = area_f > 0.0f ? area_f * (60.0f * 1024.0f / 2.0f) / (cs->hscale * cs->hscale) : 3.0e38f;   // square metres
     for (int j = 0; j < n; j++) {
         const int i = (int)order[(size_t)j];
         const float X = xy[2 * i], Y = xy[2 * i + 1];
@@ -850,7 +841,7 @@ static int32_t cs_set_scan_finish(slamhip_cs *cs, const float *xy, int32_t n, bo
         if (cur > 0) {
             const float nx0 = SH_MINF(bx0, Xr), nx1 = SH_MAXF(bx1, Xr), ny0 = SH_MINF(by0, Yr), ny1 = SH_MAXF(by1, Yr);
             const float ex = nx1 - nx0, ey = ny1 - ny0;
-            if (cur == CS_RB_MAX || !(ex <= ext) || !(ey <= ext) || !((ex + marg) * (ey + marg) <= amax)) { rb.push_back(j); cur = 0; }
+            if (cur == CS_RB_MAX || !(ex <= ext) || !(ey <= ext)) { rb.push_back(j); cur = 0; }
             else { bx0 = nx0; bx1 = nx1; by0 = ny0; by1 = ny1; }
         }
         if (cur == 0) { bx0 = bx1 = Xr; by0 = by1 = Yr; }
@@ -1126,7 +1117,7 @@ static void spec_free(slamhip_cs *cs)
 static int32_t cs_speculate_next(slamhip_cs *cs)
 {
     slamhip_ctx *ctx = cs->ctx;
-    static const bool off = getenv("SLAMHIP_NO_SPECULATION") != nullptr;
+    static const bool off = sh_env_set("SLAMHIP_NO_SPECULATION");
     const int n = cs->n_offs;
     cs->spec_valid = false;
     if (off || !cs->spec_base_ok || !cs->offs_on_device_sorted || cs->gen_pending || n <= 0 || cs->shard_first != 0 || cs->shard_count != n + 1 ||
@@ -1238,7 +1229,7 @@ static int32_t ensure_shard(slamhip_cs *cs, int first, int count)
     // x 1) up to 12 288 candidates -- the groups' theta ranges halve, which is worth more there than the tiles' reuse (1024 ->
     // 512: 4096 candidates 22.7 -> 18.8, the simulator's 4000 candidates on a 256^2 map with 400 rays 14.6 -> 13.3, 8192:
     // 23.2 -> 22.8 (1024^2 map: 22.0 -> 19.0), 12 288: 25.7 -> 24.0, but 16 384: 25.3 -> 26.6).
-    static const int grp_env = getenv("SLAMHIP_K1_GROUP") ? atoi(getenv("SLAMHIP_K1_GROUP")) : 0;
+    static const int grp_env = (int)sh_env_int("SLAMHIP_K1_GROUP", 0);
     // (a heading lattice is laid out for the group size of its full-range search: cs_lattice)
     const k_lattice lat = cs_lattice(cs, cs->n_offs, cs->offs_on_device_sorted && cs->gen_lattice);
     const bool lat_list = lat.cpl != 0;
@@ -1471,8 +1462,6 @@ static int32_t finish_holemap(slamhip_cs *cs)
     SH_TRY(sh_host_wait(cs->ctx));
     const int *m = (const int *)cs->ctx->mailbox;                           // [0] longest ray, [1] conflict pixels, [2] blended pixels
     cs->last_hole_pixels = m[2]; cs->hole_pixels_pending = false;
-    static const bool stats = getenv("SLAMHIP_K2_STATS") != nullptr;        // developer aid
-    if (stats) fprintf(stderr, "[slamhip] K2: reach %d px, %d blended pixels\n", m[0], m[2]);
     return SLAMHIP_OK;
 }
 
@@ -1594,9 +1583,6 @@ extern "C" int32_t slamhip_cs_selfcheck_failures(slamhip_cs *cs, uint32_t *out)
     SH_HIP(hipMemcpyAsync(h, cs->d_verify, sizeof(unsigned int) * 8, hipMemcpyDeviceToHost, cs->ctx->stream));
     SH_HIP(hipStreamSynchronize(cs->ctx->stream));
     *out = h[0];
-    if (getenv("SLAMHIP_K1_STATS"))
-        fprintf(stderr, "[slamhip] K1 step kinds (ray x sub-batch units): group tile %u, sub-batch tiles %u, banded %u, global gathers %u; plan: workgroups with their record %u, without %u\n",
-                h[1], h[2], h[4], h[3], h[5], h[6]);
     return SLAMHIP_OK;
 }
 
@@ -1634,6 +1620,11 @@ extern "C" int32_t slamhip_cs_search_and_update_pxcs(slamhip_cs *cs, const float
     return SLAMHIP_OK;
 }
 
+// Developer switches of the fused scan, for comparison: SLAMHIP_FUSED_WAIT_UPDATES=1 returns after the map updates (the former
+// behaviour), SLAMHIP_FUSED_K1_DELIVERS=1 keeps the search's own delivery of its result (slamhip_cs_search_and_update).
+static bool fused_wait_updates() { static const bool v = sh_env_set("SLAMHIP_FUSED_WAIT_UPDATES"); return v; }
+bool cs_fused_k1_delivers() { static const bool v = sh_env_set("SLAMHIP_FUSED_K1_DELIVERS"); return v; }
+
 // CoreSLAMProcessor.Update's scan (:723 set_scan, :732 search, :746-751 updates) with the SEARCH LAUNCH FIRST.  Between two scans the
 // host's chain -- the pose comes back, the next scan is converted, sorted, cut into blocks and stored, the search is launched -- is a
 // few microseconds longer than the map update the device is still busy with, and a launch that arrives when the queue has just run
@@ -1647,8 +1638,7 @@ int32_t cs_search_and_update_prelaunched(slamhip_cs *cs, const float *xy, int32_
                                          int32_t max_hits, float out_pose[3], int32_t *out_dist, int32_t *out_index, bool *took)
 {
     *took = false;
-    static const bool on = getenv("SLAMHIP_PRELAUNCH") ? atoi(getenv("SLAMHIP_PRELAUNCH")) != 0 : true;
-    static const bool wait_updates = getenv("SLAMHIP_FUSED_WAIT_UPDATES") != nullptr, k1_delivers = getenv("SLAMHIP_FUSED_K1_DELIVERS") != nullptr;
+    static const bool on = (int)sh_env_int("SLAMHIP_PRELAUNCH", 1) != 0;
     slamhip_ctx *ctx = cs->ctx;
     if (g_cst.on) {                                               // (developer aid: why scans take the ordinary order)
         static thread_local unsigned why[8], calls;
@@ -1657,7 +1647,7 @@ int32_t cs_search_and_update_prelaunched(slamhip_cs *cs, const float *xy, int32_
         if ((++calls & 255u) == 0) fprintf(stderr, "[slamhip] prelaunch refused in %u calls: ray count %u, layout dirty %u, points %u, upload pending %u, scan in flight %u, block busy %u, two-launch update %u\n",
                                            calls, why[0], why[1], why[2], why[3], why[4], why[5], why[6]);
     }
-    if (!on || !xy || n <= 0 || n != cs->n_points || n > cs->cap_points || !ctx->large_bar || ctx->mail_off || ctx->timing != 0 || wait_updates || k1_delivers ||
+    if (!on || !xy || n <= 0 || n != cs->n_points || n > cs->cap_points || !ctx->large_bar || ctx->mail_off || ctx->timing != 0 || fused_wait_updates() || cs_fused_k1_delivers() ||
         cs->k1_layout_dirty || !cs->pts_sane || cs->n_offs <= 0 || cs->upload_pending || cs->scan_in_flight || !cs_holemap_one_launch(cs)) { cs->pl_stats[3]++; return SLAMHIP_OK; }
     SH_CHECK_ARG(quality >= 0 && quality <= 256 && max_hits >= -128 && max_hits <= 127);
     SH_HIP(hipSetDevice(ctx->device));
@@ -1771,8 +1761,7 @@ extern "C" int32_t slamhip_cs_search_and_update(slamhip_cs *cs, const float pose
     // (everything that reads the maps afterwards -- the next search, a download, an export -- is ordered behind them on the
     // operator's stream).  Without the mailbox, with per-kernel timing on, or when the search ran on the fallback kernels,
     // one result block comes back after the updates instead.
-    static const bool wait_updates = getenv("SLAMHIP_FUSED_WAIT_UPDATES") != nullptr;      // (the former behaviour, for comparison)
-    const bool early = !ctx->mail_off && ctx->timing == 0 && !wait_updates;
+    const bool early = !ctx->mail_off && ctx->timing == 0 && !fused_wait_updates();
     sh_mail_guard lock(ctx);
     const uint32_t seq = sh_mail_seq_next(ctx);                    // (taken when K1 is armed; the result block's publish reuses it otherwise)
     // The winner decoded by the map update (round 4, late): the search runs in its result-ring form -- its workgroups min their keys
@@ -1782,8 +1771,7 @@ extern "C" int32_t slamhip_cs_search_and_update(slamhip_cs *cs, const float pose
     // decodes it from the key (two loads in a row where it had one, under the 1.3 us its sixteen wavefronts take to start); its
     // first workgroup stores the pose for later readers and delivers key + pose to the mailbox.  One-launch updates only
     // (scans of up to 2048 rays); SLAMHIP_FUSED_K1_DELIVERS=1 keeps the search's own delivery.
-    static const bool k1_delivers = getenv("SLAMHIP_FUSED_K1_DELIVERS") != nullptr;
-    const bool decode = early && !k1_delivers && cs_holemap_one_launch(cs) && cs->n_points > 0;
+    const bool decode = early && !cs_fused_k1_delivers() && cs_holemap_one_launch(cs) && cs->n_points > 0;
     if (decode) {
         cs->k1_ring_request = true;
         const int32_t rc_r = search_enqueue(cs, pose, 0, cs->n_offs + 1, cs->d_key);

@@ -86,12 +86,7 @@ struct slamhip_cs {
     // ray ranges of the uniform part cut by COST (rays + a weight per ray block touched) instead of by count (k1_balanced_cuts):
     // cuts by count of ranges (cuts[0 .. n], n <= the count asked for; empty: none), for scan generation k1_cut_gen at weight k1_cut_w
     std::vector<std::pair<int, std::vector<int>>> k1_cut_cache; uint32_t k1_cut_gen, k1_cut_layout_gen;
-    // ... and for the per-scan flow, where every launch sees a new scan: the uniform part's cut made for the PREVIOUS scan while the host
-    // waited for its pose (cs_layout_idle_refresh), used for the next scan's launch if it is legal for that scan's ray blocks (a cut
-    // only balances the launch: any legal one gives the same sums)
-    std::vector<int> k1_prev_cuts; int k1_prev_cuts_nc; uint32_t k1_prev_cuts_layout_gen; int k1_prev_cuts_points;
-    bool k1_launch_prev_cuts;                   // the search launch now in the stream took them (a prelaunched one: legality is tested when the tables exist)
-    float k1_last_pose[3]; int k1_last_group; bool k1_last_valid;   // the last tiled mode-1 launch: what the idle refresh makes the next cut for
+    float k1_last_pose[3]; bool k1_last_valid;  // the last tiled mode-1 launch: the idle refresh makes the layout for its heading
     uint32_t k1_cut_seen_scan, k1_cut_seen_layout;   // the (scan, layout) of the last tiled launch: cuts are made from the second launch of a pair on
     uint32_t k1_layout_gen;                     // layouts made so far (k1_make_layout)
     std::vector<char> k1_cut_cand;              // per ray block: its tile may exceed the budget (worth the exact box test)
@@ -100,12 +95,12 @@ struct slamhip_cs {
     uint32_t scan_gen;                          // scans set so far (slamhip_cs_set_scan)
     std::vector<float> h_grp_prev; int k1_group_prev;   // the groups' figures before the last ensure_shard (layout kept when unchanged)
     bool k1_layout_dirty, k1_layout_spread; int k1_layout_budget, k1_layout_groups; float k1_layout_theta;
-    bool k1_scan_dirty;                         // a new scan since the layout was made (set_scan): it is kept if still legal, see cs_launch_distance
+    bool k1_scan_dirty;                         // a new scan since the layout was made (set_scan): it is kept if still legal, see k1_layout_choose
     bool k1_prelaunch;                          // the search launch now being made precedes its scan's tables (cs_search_and_update_prelaunched, coreslam.hip): the layout is the last scan's, unchecked
     uint64_t pl_stats[4];                       // slamhip_cs_prelaunch_stats: launched ahead of the tables | abandoned | a new layout was needed | refused (ordinary order)
     uint32_t *d_scan_flag; uint32_t scan_flag_seq;   // ... and waits on the device for this word: the host stores the scan's number there when the tables have landed (or the number | 2^31: abandon the launch)
     bool k1_layout_stale;                       // ... and the one for the scan now set is made in the host's next idle wait (cs_layout_idle_refresh)
-    int k1_layout_target, k1_layout_band_parts;
+    int k1_layout_target;
     float gen_sigma_xy, gen_sigma_theta;        // offsets generated on the device: their distribution
     bool offs_theta_small;        // every |dtheta| <= 1e4: the tiled kernel's trigonometry needs no huge-angle branch
     unsigned int *d_verify;       // [8] SLAMHIP_K1_VERIFY=1: [0] tile self-check failures (must stay 0), [1..4] unit counts per kind
@@ -186,12 +181,13 @@ void cs_layout_idle_refresh(slamhip_cs *cs);   // host only: call between a sear
 int32_t cs_flush_generate(slamhip_cs *cs);
 int32_t cs_side_join(slamhip_cs *cs);
 #define CS_RC_NO_PRELAUNCH 77                   // cs_launch_distance, internal: a prelaunch would need a new layout -- nothing was launched
+bool cs_fused_k1_delivers();                    // coreslam.hip: SLAMHIP_FUSED_K1_DELIVERS (the fused scan's search delivers its own result)
 int32_t cs_search_and_update_prelaunched(slamhip_cs *cs, const float *xy, int32_t n, const float pose[3], float hole_width, int32_t quality,
                                          int32_t max_hits, float out_pose[3], int32_t *out_dist, int32_t *out_index, bool *took);   // coreslam.hip; *took = false: nothing done, the caller takes the ordinary order
 // developer switch SLAMHIP_FUSED_TIMES=1: host clock between the stages of the per-scan calls (mean over 64 calls, stderr)
 struct cs_stage_times {
     bool on; double acc[12], cur[12]; int n; timespec t; const char *what;
-    explicit cs_stage_times(const char *w) : on(getenv("SLAMHIP_FUSED_TIMES") != nullptr), n(0), what(w) { for (double &a : acc) a = 0; for (double &a : cur) a = 0; }
+    explicit cs_stage_times(const char *w) : on(sh_env_set("SLAMHIP_FUSED_TIMES")), n(0), what(w) { for (double &a : acc) a = 0; for (double &a : cur) a = 0; }
     void start() { if (on) clock_gettime(CLOCK_MONOTONIC, &t); }
     void lap(int k) { if (!on) return; timespec u; clock_gettime(CLOCK_MONOTONIC, &u); const double d = (u.tv_sec - t.tv_sec) * 1e6 + (u.tv_nsec - t.tv_nsec) * 1e-3; acc[k] += d; cur[k] += d; t = u; }
     void done()
@@ -199,7 +195,7 @@ struct cs_stage_times {
         if (!on) return;
         {   // (a call that took over half a millisecond -- or SLAMHIP_SLOW_US -- : its own stages, at once)
             double sum = 0; for (double a : cur) sum += a;
-            static const double slow_us = getenv("SLAMHIP_SLOW_US") ? atof(getenv("SLAMHIP_SLOW_US")) : 500.0;
+            static const double slow_us = sh_env_real("SLAMHIP_SLOW_US", 500.0);
             if (sum > slow_us) { fprintf(stderr, "[slamhip] SLOW call (%.0f us), %s:", sum, what); for (double a : cur) fprintf(stderr, " %.1f", a); fprintf(stderr, "\n"); }
             for (double &a : cur) a = 0;
         }

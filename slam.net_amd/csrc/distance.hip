@@ -1110,14 +1110,11 @@ k1_search_tiled(const k1_args a)
 
 // ---- the plan kernel --------------------------------------------------------------------------------------------
 // One launch per search, on a stream of its own beside the search launch (cs_launch_distance): what every workgroup of k1_search_tiled
-// would otherwise work out in front of its first tile, made ONCE and left in device memory (k1_args: plan_rec).
-//   blocks [0, n_wgs)       one wavefront per workgroup of the search launch: its ray range (k1_wg_decode -- the same layout), the group's
-//                           bounds from the jitter bounds, the boxes and step records of its pieces (k1_pieces.inc -- the same text), and
-//                           the record: 16 units of 8 words, [0] = {stamp, steps or -1, ...}, [1 + i] = step i, word 7 of every unit =
-//                           stamp, all 512 bytes in ONE store instruction (a unit never exists without its stamp);
-//   blocks [n_wgs, ...)     256 candidates each: (px, py, c, s) = k1_candidate (the deterministic trigonometry, bit for bit what the search
-//                           kernel's lanes compute), stored THROUGH the L2 to memory (agent-scope stores: the L2 is per XCD) and
-//                           waited for, THEN the stamps of the four 64-candidate runs.
+// would otherwise work out in front of its first tile, made ONCE and left in device memory (k1_args: plan_rec).  The launch has
+// exactly n_wgs blocks, one wavefront per workgroup of the search launch: its ray range (k1_wg_decode -- the same layout), the group's
+// bounds from the jitter bounds, the boxes and step records of its pieces (k1_pieces.inc -- the same text), and the record: 16 units
+// of 8 words, [0] = {stamp, steps or -1, ...}, [1 + i] = step i, word 7 of every unit = stamp, all 512 bytes in ONE store instruction
+// (a unit never exists without its stamp).  (The candidates' (px, py, c, s) are not shared: every search workgroup makes its own.)
 // The search kernel trusts nothing without its stamp, so the launch may be late or missing; a stamp is the search's number, never reused.
 __device__ static inline int k1_plan_slot(const int i) { return i <= K1_PLAN_STEPS ? i : K1_PLAN_STEPS + 1; }
 template <int GROUP, int CPL>
@@ -1226,11 +1223,13 @@ static int32_t ensure_partial(slamhip_cs *cs, size_t bytes)
     return SLAMHIP_OK;
 }
 
-static int env_int(const char *name, int dflt)
-{
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
+// Fixed figures of the layout's and the cuts' cost estimates (measured on MI355X: see where they are used)
+constexpr int K1_BAND_PARTS = 2;            // listed groups on banded tiles: chunks in sets of this many bands
+constexpr float K1_BAND_STAGE = 5.0f;       // cost of staging one band of a banded tile, in ray units (the kernel's a.band_stage too)
+constexpr double K1_CUT_CAND = 0.9;         // a block whose widest tile may exceed this fraction of the budget gets the exact box test
+constexpr double K1_FBAND = 1.9, K1_FGLOBAL = 3.0;   // cost per ray of a banded tile step / a global gather, relative to a plain step
+constexpr double K1_STEPCOST = 8.0;         // a tile step in ray units (the uniform part's count of ray ranges)
+constexpr double K1_TAILW = 1.5;            // weight of the slowest listed group against the uniform part
 
 // Do nc equal ray ranges hold at most K1_MAXR rays and K1_MAXP block pieces each?  (Not monotone in nc: the cuts move.)
 static bool k1_chunks_legal(const slamhip_cs *cs, int nc)
@@ -1292,7 +1291,6 @@ static int k1_legal_chunks(const slamhip_cs *cs, int nc)
     return nc;
 }
 
-static thread_local double g_cut_t[4] = { 0, 0, 0, 0 };   // developer aid (SLAMHIP_K1_CUT_TIMES): host microseconds in weights / balanced cuts / banded check
 static inline double k1_now_us() { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return (double)t.tv_sec * 1e6 + (double)t.tv_nsec * 1e-3; }
 // Ray ranges cut by cost.  A workgroup's compute phase is its rays PLUS its tile steps -- one per ray block it touches -- and a
 // step costs as much as a dozen or two rays of gathers (barrier, tile write, barrier, the next tile's loads; SLAMHIP_K1_TIMES at
@@ -1389,8 +1387,7 @@ static void k1_cut_weights(const slamhip_cs *cs, int n_groups, bool have_spread,
         wb[(size_t)b] = w_fix + w_kb * (2.0 * (w + 8.0) * h / 1024.0);
         // (a first, generous estimate for the widest uniform group picks the blocks worth the exact box below)
         const double ww = ex * c + ey * s + d_w + (mx * s + my * c) * dth_w, hw = ex * s + ey * c + d_w + (mx * c + my * s) * dth_w;
-        static const double cand_f = getenv("SLAMHIP_K1_CUT_CAND") ? atof(getenv("SLAMHIP_K1_CUT_CAND")) : 0.9;
-        cand[(size_t)b] = 2.0 * (ww + 8.0) * hw > cand_f * (double)budget || ww > 440.0;
+        cand[(size_t)b] = 2.0 * (ww + 8.0) * hw > K1_CUT_CAND * (double)budget || ww > 440.0;
     }
 }
 
@@ -1414,7 +1411,7 @@ static k1_host_bounds k1_group_bounds_host(const slamhip_cs *cs, int g, const fl
     b.cmin = (float)cl * scale - pad; b.cmax = (float)ch * scale + pad; b.smin = (float)sl * scale - pad; b.smax = (float)sh * scale + pad;
     return b;
 }
-static int k1_nopad() { static const int v = env_int("SLAMHIP_K1_NOPAD", 0); return v; }     // (tuning: tiles without the pitch padding)
+static int k1_nopad() { static const int v = (int)sh_env_int("SLAMHIP_K1_NOPAD", 0); return v; }     // (tuning: tiles without the pitch padding)
 static bool k1_piece_banded(const slamhip_cs *cs, const k1_host_bounds &b, int r0, int r1, int budget)
 {
     const float *pts = (const float *)((const char *)cs->h_scan_blob + (size_t)cs->cap_points * 24);     // the sorted rays (set_scan's staging block)
@@ -1462,14 +1459,6 @@ static int k1_cuts_banded_rays(const slamhip_cs *cs, const std::vector<int> &cut
     return banded;
 }
 
-// Cost of staging one band of a banded tile, in ray units (measured best on MI355X: 5; a huge value: multi-band tiles
-// never, global gathers instead; a hugely negative one: bands whenever they fit)
-static float k1_band_stage()
-{
-    static const float v = getenv("SLAMHIP_K1_BAND_STAGE") ? (float)atof(getenv("SLAMHIP_K1_BAND_STAGE")) : 5.0f;
-    return v;
-}
-
 // Estimated cost of a group in ray units (tile steps cost 1 per ray): from the theta range and the translation spread
 // of the group (ensure_shard), the bounding box of each ray block (set_scan) and the search pose's heading.  A box
 // beyond the tile budget is staged in bands with range-tested gathers.  Only the balance of the launch depends on
@@ -1492,9 +1481,7 @@ static void k1_block_terms(const slamhip_cs *cs, std::vector<k1_block_term> &t)
 static double k1_group_cost(const slamhip_cs *cs, const std::vector<k1_block_term> &t, int g, int budget)
 {
     const double dth = cs->h_grp_dth[(size_t)g], d = cs->h_grp_dxy[(size_t)g] + 4.0;
-    static const double f_band = getenv("SLAMHIP_K1_FBAND") ? atof(getenv("SLAMHIP_K1_FBAND")) : 1.9;
-    static const double f_glob = getenv("SLAMHIP_K1_FGLOBAL") ? atof(getenv("SLAMHIP_K1_FGLOBAL")) : 3.0;
-    const double stage = (double)k1_band_stage();
+    const double stage = (double)K1_BAND_STAGE;
     double cost = 0.0;
     for (size_t b = 0; b < t.size(); b++) {
         // ... grown by the translation spread and by the arc the centre sweeps over the group's theta range
@@ -1511,8 +1498,8 @@ static double k1_group_cost(const slamhip_cs *cs, const std::vector<k1_block_ter
             // 4096^2 map with 32 768 candidates 68.2 -> 51.5, 4096 candidates 23.8 -> 22.5, the other sizes unchanged; 3.5 and 2.5
             // each have sizes that lose 4-12 us to a second round of workgroups.)
             const double nr = e.nr;
-            const bool pay = bands <= 1.0 || bands * (stage + f_band * nr) < f_glob * nr;
-            f = bands <= K1_MAXBANDS && w <= 504.0 && pay ? f_band * bands + (bands > 1.0 ? bands * fmax(stage, 0.0) / fmax(nr, 1.0) : 0.0) : f_glob;
+            const bool pay = bands <= 1.0 || bands * (stage + K1_FBAND * nr) < K1_FGLOBAL * nr;
+            f = bands <= K1_MAXBANDS && w <= 504.0 && pay ? K1_FBAND * bands + (bands > 1.0 ? bands * stage / fmax(nr, 1.0) : 0.0) : K1_FGLOBAL;
         }
         cost += f * e.nr;
     }
@@ -1521,7 +1508,7 @@ static double k1_group_cost(const slamhip_cs *cs, const std::vector<k1_block_ter
 
 // Launch layout (cs->k1_*): the groups whose estimated cost per ray is well above a plain group's get their own,
 // larger chunk counts (at most K1_TABLE_G groups, the most expensive first); the rest share one count.
-static void k1_make_layout(slamhip_cs *cs, int n_groups, int target_wgs, int budget, bool have_spread, int band_parts)
+static void k1_make_layout(slamhip_cs *cs, int n_groups, int target_wgs, int budget, bool have_spread)
 {
     const int R = cs->n_points;
     cs->k1_tab_group.clear(); cs->k1_tab_nc.clear(); cs->k1_tab_nbp.clear();
@@ -1549,8 +1536,7 @@ static void k1_make_layout(slamhip_cs *cs, int n_groups, int target_wgs, int bud
         for (int g = hi; g < n_groups; g++) total += cost[(size_t)g];
         double per_cost = (double)target_wgs / total;
         uni_want = (int)floor(ref * per_cost + 0.5);
-        static const double step_cost = getenv("SLAMHIP_K1_STEPCOST") ? atof(getenv("SLAMHIP_K1_STEPCOST")) : 8.0;
-        if (n_groups <= K1_TABLE_G && step_cost > 0.0 && uni_want >= 1) {
+        if (n_groups <= K1_TABLE_G && uni_want >= 1) {
             // One round of workgroups: the uniform part's count of ray ranges is the one, near the proportional share, whose slowest
             // range -- steps included -- balances best against the slowest listed group with what is left (weighted 1.5: its
             // gathers miss the L2 on large maps).  Measured against the proportional shares, two runs each, us per launch with
@@ -1564,7 +1550,7 @@ static void k1_make_layout(slamhip_cs *cs, int n_groups, int target_wgs, int bud
             for (int nc = std::max(1, (int)(0.6 * uni_want)); nc <= (int)(1.6 * uni_want) + 1; nc++) {
                 const long long left = (long long)target_wgs - (long long)(hi - lo) * nc;
                 if (nl > 0 ? left < (long long)nl * std::max(2, min_legal) : left < 0) break;
-                const double tu = k1_chunks_score(cs, nc, step_cost) * (ref / (double)R);
+                const double tu = k1_chunks_score(cs, nc, K1_STEPCOST) * (ref / (double)R);
                 if (tu < 0.0) continue;
                 double tt = 0.0;
                 if (nl > 0) {
@@ -1583,8 +1569,7 @@ static void k1_make_layout(slamhip_cs *cs, int n_groups, int target_wgs, int bud
                         if (share[im] <= min_legal) break;
                         share[im]--; sum--;
                     }
-                    static const double tail_w = getenv("SLAMHIP_K1_TAILW") ? atof(getenv("SLAMHIP_K1_TAILW")) : 1.5;
-                    for (size_t i = 0; i < share.size(); i++) tt = std::max(tt, tail_w * lc[i] / (double)share[i] + step_cost);
+                    for (size_t i = 0; i < share.size(); i++) tt = std::max(tt, K1_TAILW * lc[i] / (double)share[i] + K1_STEPCOST);
                 }
                 const double tm = std::max(tu, tt);
                 if (best_nc < 0 || tm < best_t) { best_nc = nc; best_t = tm; }
@@ -1602,8 +1587,7 @@ static void k1_make_layout(slamhip_cs *cs, int n_groups, int target_wgs, int bud
             if (v < 1) v = 1;
             if (v > R / 4) v = R / 4 > 0 ? R / 4 : 1;
             int nbp = 1;                                           // banded tiles (two bands or more on average): chunks in sets
-            static const double f_band = getenv("SLAMHIP_K1_FBAND") ? atof(getenv("SLAMHIP_K1_FBAND")) : 1.9;
-            if (band_parts > 1 && cost[(size_t)g] >= 2.0 * f_band * R && v >= 2 * band_parts) nbp = band_parts;
+            if (cost[(size_t)g] >= 2.0 * K1_FBAND * R && v >= 2 * K1_BAND_PARTS) nbp = K1_BAND_PARTS;
             cs->k1_tab_group.push_back(g); cs->k1_tab_nc.push_back(v); cs->k1_tab_nbp.push_back(nbp);
         }
         (void)n_list;
@@ -1655,8 +1639,9 @@ static void k1_make_layout(slamhip_cs *cs, int n_groups, int target_wgs, int bud
     }
 }
 
-// Are the layout's counts of ray ranges legal for the scan now set (k1_chunks_legal)?
-static bool k1_layout_legal(const slamhip_cs *cs)
+// Are the layout's counts of ray ranges legal for the scan now set (k1_chunks_legal)?  (The search launched ahead of its scan's
+// tables asks when the tables exist.)
+bool cs_k1_layout_legal(const slamhip_cs *cs)
 {
     if (cs->k1_uni_ng > 0 && !k1_chunks_legal(cs, cs->k1_uni_nc)) return false;
     int seen = -1;
@@ -1668,30 +1653,11 @@ static bool k1_layout_legal(const slamhip_cs *cs)
     return true;
 }
 
-// Is a cut -- ray ranges [cuts[c], cuts[c + 1]) -- legal for the scan now set: it covers the scan, and every range holds at most K1_MAXR
-// rays of at most K1_MAXP ray blocks?
-static bool k1_cuts_legal(const slamhip_cs *cs, const std::vector<int> &cuts)
-{
-    const int R = cs->n_points, n_rb = cs->n_rb;
-    const int *rb = cs->h_rb_start.data();
-    if (cuts.size() < 2 || cuts.front() != 0 || cuts.back() != R || n_rb < 1) return false;
-    int b = 0;
-    for (size_t c = 0; c + 1 < cuts.size(); c++) {
-        const int lo = cuts[c], hi = cuts[c + 1];
-        if (hi <= lo || hi - lo > K1_MAXR) return false;
-        while (b + 1 < n_rb && rb[b + 1] <= lo) b++;
-        int e = b;
-        while (e + 1 < n_rb && rb[e + 1] < hi) e++;
-        if (e - b + 1 > K1_MAXP) return false;
-    }
-    return true;
-}
-
-// The weight of a tile step in ray units for the cuts by cost (see cs_launch_distance): 26 where it was calibrated (2048^2 map = 51.2
+// The weight of a tile step in ray units for the cuts by cost (see k1_cuts_select): 26 where it was calibrated (2048^2 map = 51.2
 // pixels per metre, two candidates per lane), less on coarser maps and in proportion to what a ray costs the workgroup.
 static double k1_cut_wfix(const slamhip_cs *cs, int group)
 {
-    static const double cut_w20 = getenv("SLAMHIP_K1_CUT_WFIX") ? atof(getenv("SLAMHIP_K1_CUT_WFIX")) : 26.0;
+    static const double cut_w20 = sh_env_real("SLAMHIP_K1_CUT_WFIX", 26.0);
     const int cpl_group = group == K1_GROUP_BIG ? 4 : group == K1_GROUP_SMALL ? 1 : 2;
     return cut_w20 * std::min(1.0, (double)cs->hscale / 51.2) * 2.0 / (double)cpl_group;
 }
@@ -1700,7 +1666,7 @@ static double k1_cut_wfix(const slamhip_cs *cs, int group)
 // keeps nearly all the ranges asked for; dropped if it puts more rays on banded tiles than the equal-count ranges do).  c: empty = none.
 static void k1_cuts_make(slamhip_cs *cs, int nrc, bool have_spread, const float pose3[3], int budget, std::vector<int> &c)
 {
-    static const int cut_keep = env_int("SLAMHIP_K1_CUT_KEEP", 90);   // per cent of the asked-for ranges a cut must keep
+    static const int cut_keep = (int)sh_env_int("SLAMHIP_K1_CUT_KEEP", 90);   // per cent of the asked-for ranges a cut must keep
     c.clear();
     // The cut must keep (nearly) the asked-for count of ranges: where blocks are long in rays (coarse maps: a 64-ray block is
     // one tile) heavy weights end in one block per range -- 17 ranges for 25 at 1024^2 -- and the workgroups that are not
@@ -1710,9 +1676,7 @@ static void k1_cuts_make(slamhip_cs *cs, int nrc, bool have_spread, const float 
     for (int tries = 0; tries < 6; tries++, scale *= 0.6) {
         wsc.resize(cs->k1_cut_wb.size());
         for (size_t i = 0; i < wsc.size(); i++) wsc[i] = cs->k1_cut_wb[i] * scale;
-        const double tb0 = k1_now_us();
         const int n = k1_balanced_cuts(cs, nrc, wsc, c);
-        g_cut_t[1] += k1_now_us() - tb0;
         if (n < 1) { c.clear(); break; }
         if (n * 100 >= nrc * cut_keep) break;
         c.clear();
@@ -1721,9 +1685,7 @@ static void k1_cuts_make(slamhip_cs *cs, int nrc, bool have_spread, const float 
         // a cut that puts more rays on banded tiles (for the uniform part's outer groups) than the equal-count ranges do is
         // dropped: a banded piece costs its workgroup more than twice a plain one, the launch waits for it (1024^2 map:
         // four workgroups at 19 us in a 21 us launch)
-        const double tc0 = k1_now_us();
         const int banded = k1_cuts_banded_rays(cs, c, pose3, budget, cs->k1_cut_cand);
-        g_cut_t[2] += k1_now_us() - tc0;
         if (banded > 0) {                                  // (seldom: the equal-count ranges are only looked at then)
             std::vector<int> eq((size_t)nrc + 1);
             for (int k = 0; k <= nrc; k++) eq[(size_t)k] = (int)(((long long)k * cs->n_points) / nrc);
@@ -1732,503 +1694,274 @@ static void k1_cuts_make(slamhip_cs *cs, int nrc, bool have_spread, const float 
     }
 }
 
-// Are the layout's counts of ray ranges -- and the cut the launch now in the stream took over from the previous scan -- legal for the
-// scan now set?  (The search launched ahead of its scan's tables asks when the tables exist.)
-bool cs_k1_layout_legal(const slamhip_cs *cs)
-{
-    if (!k1_layout_legal(cs)) return false;
-    return !cs->k1_launch_prev_cuts || k1_cuts_legal(cs, cs->k1_prev_cuts);
-}
 
 // The layout for the scan now set, made while the host has nothing else to do (it waits for a search's result): the launch that
-// just left used the previous scan's (cs_launch_distance) -- and, for the next scan's launch, the uniform part's ray ranges cut by
-// cost (the per-scan flow sees every scan once: its launch takes the cut of the scan before, if legal).  Touches host state only.
+// just left used the previous scan's layout (cs_launch_distance).  Touches host state only.
 void cs_layout_idle_refresh(slamhip_cs *cs)
 {
-    if (cs->k1_layout_dirty || cs->k1_scan_dirty || cs->n_points <= 0) return;
-    if (cs->k1_layout_stale) {
-        // (the layout follows the search heading: a launch-ahead search keeps the last layout only while its heading is within 0.1 rad
-        // of the layout's -- cs_launch_distance -- and a robot that turns half a degree per scan used to lose the launch-ahead flow,
-        // and 15 us, every dozen scans: 11 of 205 in bench.py's trajectory)
-        if (cs->k1_last_valid && cs->k1_layout_spread) cs->k1_layout_theta = cs->k1_last_pose[2];
-        k1_make_layout(cs, cs->k1_layout_groups, cs->k1_layout_target, cs->k1_layout_budget, cs->k1_layout_spread, cs->k1_layout_band_parts);
-        cs->k1_layout_stale = false; cs->k1_layout_gen++;
-    }
-    static const int idle_cuts = env_int("SLAMHIP_K1_IDLE_CUTS", 0);      // (off: measured a LOSS, see below)
-    if (!idle_cuts || !cs->k1_last_valid || cs->k1_uni_ng <= 0 || cs->n_points >= 65536 || !cs->h_scan_blob) return;
-    if (cs->k1_prev_cuts_layout_gen == cs->k1_layout_gen && cs->k1_prev_cuts_points == cs->n_points && cs->k1_prev_cuts_nc == cs->k1_uni_nc &&
-        cs->k1_cut_gen == cs->scan_gen && !cs->k1_prev_cuts.empty()) return;      // (made for this very scan and layout already)
-    static const double cut_wkb = getenv("SLAMHIP_K1_CUT_WKB") ? atof(getenv("SLAMHIP_K1_CUT_WKB")) : 0.0;
-    const double wfix = k1_cut_wfix(cs, cs->k1_last_group);
-    if (!(wfix > 0.0 || cut_wkb > 0.0)) return;
-    cs->k1_cut_cache.clear();
-    cs->k1_cut_gen = cs->scan_gen; cs->k1_cut_layout_gen = cs->k1_layout_gen;
-    k1_cut_weights(cs, cs->k1_layout_groups, cs->k1_layout_spread, wfix, cut_wkb, cs->k1_layout_budget, cs->k1_cut_wb);
-    k1_cuts_make(cs, cs->k1_uni_nc, cs->k1_layout_spread, cs->k1_last_pose, cs->k1_layout_budget, cs->k1_prev_cuts);
-    cs->k1_prev_cuts_nc = cs->k1_uni_nc; cs->k1_prev_cuts_layout_gen = cs->k1_layout_gen; cs->k1_prev_cuts_points = cs->n_points;
-    if (!cs->k1_prev_cuts.empty()) cs->k1_cut_cache.emplace_back(cs->k1_uni_nc, cs->k1_prev_cuts);    // (a second search of THIS scan finds it too)
+    if (cs->k1_layout_dirty || cs->k1_scan_dirty || cs->n_points <= 0 || !cs->k1_layout_stale) return;
+    // (the layout follows the search heading: a launch-ahead search keeps the last layout only while its heading is within 0.1 rad
+    // of the layout's -- cs_launch_distance -- and a robot that turns half a degree per scan used to lose the launch-ahead flow,
+    // and 15 us, every dozen scans: 11 of 205 in bench.py's trajectory)
+    if (cs->k1_last_valid && cs->k1_layout_spread) cs->k1_layout_theta = cs->k1_last_pose[2];
+    k1_make_layout(cs, cs->k1_layout_groups, cs->k1_layout_target, cs->k1_layout_budget, cs->k1_layout_spread);
+    cs->k1_layout_stale = false; cs->k1_layout_gen++;
 }
 
-// K1 over `count` candidates in evaluation order (d_ev_idx maps to flat indices).  mode 0: d_pxcs already holds
-// (px,py,c,s); 1: d_ev_off holds jitters added to `pose`; 2: d_ev_off holds poses.  The packed arg-min key of the
-// launch is written to key_dst.  Asynchronous on the context's stream.
-int32_t cs_launch_distance(slamhip_cs *cs, int mode, const float pose[3], int count, bool want_dist, bool cand_sane,
-                           uint64_t *key_dst)
+// Launch layout of a tiled search: kept, or remade for this launch.  false: a launch ahead of its scan's tables would need a new
+// layout (nothing was changed).
+static bool k1_layout_choose(slamhip_cs *cs, int n_groups, int budget, bool have_spread, float bth)
+{
+    static const int target_wgs = (int)sh_env_int("SLAMHIP_K1_TARGET_WGS", 512);
+    static const int target_wgs_uniform = (int)sh_env_int("SLAMHIP_K1_TARGET_WGS_UNIFORM", 768);
+    // a workgroup's prologue costs as much as ~25 rays of gathers: small searches get fewer, larger chunks (a dozen
+    // rays or more each) rather than a full round of workgroups (measured at 4000 candidates x 400 rays: 21 -> 16 us)
+    int target = n_groups <= K1_TABLE_G ? target_wgs : target_wgs_uniform;
+    const long long by_work = (long long)n_groups * cs->n_points / 12;
+    if (by_work < target) target = (int)(by_work > n_groups ? by_work : n_groups);
+    g_cst.lap(8);
+    bool remake = cs->k1_layout_dirty || cs->k1_layout_groups != n_groups || cs->k1_layout_budget != budget || cs->k1_layout_spread != have_spread ||
+                  cs->k1_layout_target != target || (have_spread && !(fabsf(bth - cs->k1_layout_theta) < 0.1f));
+    if (cs->k1_prelaunch) {
+        // The launch precedes its scan's tables (cs_search_and_update_prelaunched): it keeps the last scan's layout, whose legality
+        // for the new ray blocks the caller tests when they exist (and abandons the launch if it fails); a layout that has to be
+        // remade for another reason needs the new blocks: no prelaunch.
+        if (remake) return false;
+        cs->k1_layout_stale = true;
+    } else
+    if (!remake && cs->k1_scan_dirty) {
+        // A new scan under an unchanged candidate list (the per-scan flow): the layout made for the last scan serves this one
+        // if its counts of ray ranges are legal for the new ray blocks -- only the balance of the launch depends on the layout,
+        // and consecutive scans look alike -- and the one for THIS scan is made while the host waits for the search
+        // (cs_layout_idle_refresh), for the next scan's launch: 8 us of estimate left the host's critical path between two
+        // scans (`CoreSLAMProcessor.Update` 66.6 -> 60 us; SLAMHIP_K1_LAYOUT_SYNC=1 makes every scan's layout before its launch).
+        static const bool layout_sync = (int)sh_env_int("SLAMHIP_K1_LAYOUT_SYNC", 0) != 0;
+        if (layout_sync || !cs_k1_layout_legal(cs)) remake = true;
+        else cs->k1_layout_stale = true;
+    }
+    cs->k1_scan_dirty = false;
+    if (remake) {
+        cs->k1_layout_theta = bth;
+        k1_make_layout(cs, n_groups, target, budget, have_spread);
+        cs->k1_layout_dirty = false; cs->k1_layout_stale = false; cs->k1_layout_gen++;
+        cs->k1_layout_groups = n_groups; cs->k1_layout_budget = budget; cs->k1_layout_spread = have_spread; cs->k1_layout_target = target;
+    }
+    g_cst.lap(9);
+    return true;
+}
+
+// The accumulators count up to 2^14 - 1 arrivals per candidate and sum up to 2^20 rays (pathological scans: fallback kernels).
+static bool k1_layout_fits_acc(const slamhip_cs *cs)
+{
+    int nc_max = cs->k1_uni_nc;
+    for (size_t i = 0; i < cs->k1_tab_nc.size(); i++) nc_max = std::max(nc_max, cs->k1_tab_nc[i]);
+    return nc_max < (1 << (K1_ACC_ARRIVED - K1_ACC_INMAP)) && cs->n_points < (1 << 20);
+}
+
+// The layout's ray ranges into a.cut / a.tab / a.wg_pos.  Ray ranges cut by cost (k1_balanced_cuts), remade when the scan, a count
+// of ranges or the weight changed: the uniform part's and every listed group's (groups with the same count of ranges share the cut).
+// A cut may come out with fewer ranges than asked for: the group then runs with that many workgroups.  Returns the launch's
+// workgroups.
+static int k1_cuts_select(slamhip_cs *cs, k1_args &a, int group, int n_groups, bool have_spread, int budget, const float pose3[3])
+{
+    // The weight of a tile step in ray units: 26 where it was calibrated (2048^2 map = 51.2 pixels per metre, two candidates per
+    // lane), less on coarser maps (smaller tiles, and the 64-ray cap makes blocks long in rays: 1024^2 wants about half, 256^2
+    // none) and in proportion to what a ray costs the workgroup (four candidates per lane: a ray takes twice as long, the step
+    // does not).  SLAMHIP_K1_CUT_WFIX = 0 and SLAMHIP_K1_CUT_WKB = 0: the equal-count formula everywhere.
+    static const double cut_wkb = sh_env_real("SLAMHIP_K1_CUT_WKB", 0.0);
+    const double cut_wfix = k1_cut_wfix(cs, group);
+    static const int cut_tab = (int)sh_env_int("SLAMHIP_K1_CUT_TAB", 0);      // (the listed groups too: measured slower)
+    const int n_tab = (int)cs->k1_tab_group.size();
+    // The cuts cost the host ~7 us (mostly the exact box test of the pieces, k1_cuts_banded_rays) and buy a launch 1 - 2 us.  They
+    // are made when a scan is searched for the SECOND time under one layout -- a list searched from many poses, a benchmark loop --
+    // never on the host's critical path between two scans (measured there: CoreSLAMProcessor.Update 66 -> 77 us per scan); the
+    // per-scan flow, which searches every scan once, runs on the equal-count ranges.  SLAMHIP_K1_CUT_ALWAYS=1: always.
+    static const int cut_always = (int)sh_env_int("SLAMHIP_K1_CUT_ALWAYS", 0);
+    const bool cut_repeat = cut_always || (cs->k1_cut_seen_scan == cs->scan_gen && cs->k1_cut_seen_layout == cs->k1_layout_gen);
+    cs->k1_cut_seen_scan = cs->scan_gen; cs->k1_cut_seen_layout = cs->k1_layout_gen;
+    const bool cuts_on = cut_repeat && (cut_wfix > 0.0 || cut_wkb > 0.0) && cs->n_points < 65536;
+    if (cuts_on && (cs->k1_cut_gen != cs->scan_gen || cs->k1_cut_layout_gen != cs->k1_layout_gen)) {
+        cs->k1_cut_cache.clear();
+        cs->k1_cut_gen = cs->scan_gen; cs->k1_cut_layout_gen = cs->k1_layout_gen;
+        k1_cut_weights(cs, n_groups, have_spread, cut_wfix, cut_wkb, budget, cs->k1_cut_wb);
+    }
+    cs->k1_cut_cache.reserve(K1_TABLE_G + 8);                      // (the entries' addresses are held below: no reallocation)
+    auto cuts_for = [&](int nrc) -> const std::vector<int> * {       // nullptr: no cut for this count (the formula stays)
+        if (!cuts_on || nrc < 2) return nullptr;
+        for (auto &e : cs->k1_cut_cache) if (e.first == nrc) return e.second.empty() ? nullptr : &e.second;
+        cs->k1_cut_cache.emplace_back(nrc, std::vector<int>());
+        std::vector<int> &c = cs->k1_cut_cache.back().second;
+        k1_cuts_make(cs, nrc, have_spread, pose3, budget, c);
+        return c.empty() ? nullptr : &c;
+    };
+    a.uni_cut = 0; a.tab_cut = 0;
+    int n_cut = 0;                                                 // entries of a.cut in use
+    a.uni_g0 = cs->k1_uni_g0; a.uni_ng = cs->k1_uni_ng > 0 ? cs->k1_uni_ng : 1; a.uni_nc = cs->k1_uni_nc;
+    if (cs->k1_uni_ng > 0) {
+        const std::vector<int> *c = cuts_for(cs->k1_uni_nc);
+        if (c && (int)c->size() <= K1_MAXCUT) {
+            for (size_t i = 0; i < c->size(); i++) a.cut[i] = (unsigned short)(*c)[i];
+            n_cut = (int)c->size();
+            a.uni_cut = 1; a.uni_nc = (int)c->size() - 1;
+        }
+    }
+    // the listed groups: all of them from the table, or none
+    std::vector<const std::vector<int> *> tcut((size_t)n_tab, nullptr);
+    bool tab_ok = cut_tab && n_tab > 0;
+    long long tab_wgs = 0;
+    for (int p = 0; p < n_tab && tab_ok; p++) {
+        const int nbp = cs->k1_tab_nbp[(size_t)p] > 0 ? cs->k1_tab_nbp[(size_t)p] : 1;
+        tcut[(size_t)p] = cuts_for(cs->k1_tab_nc[(size_t)p] / nbp);
+        if (!tcut[(size_t)p]) tab_ok = false; else tab_wgs += (long long)(tcut[(size_t)p]->size() - 1) * nbp;
+    }
+    if (tab_ok && n_cut + tab_wgs > K1_MAXCUT) tab_ok = false;
+    unsigned first = 0;
+    for (int p = 0; p < n_tab; p++) {
+        k1_args::tab_rec &rec = a.tab[p];
+        const int nbp = cs->k1_tab_nbp[(size_t)p] > 0 ? cs->k1_tab_nbp[(size_t)p] : 1;
+        const int nc_p = tab_ok ? (int)(tcut[(size_t)p]->size() - 1) * nbp : cs->k1_tab_nc[(size_t)p];
+        rec.group = (unsigned short)cs->k1_tab_group[(size_t)p];
+        rec.nbp = (unsigned short)cs->k1_tab_nbp[(size_t)p];
+        rec.first = (unsigned short)first; rec.nc = (unsigned short)nc_p;
+        if (tab_ok)
+            for (int w = 0; w < nc_p; w++) a.cut[n_cut + (int)first + w] = (unsigned short)(*tcut[(size_t)p])[(size_t)(w / nbp)];
+        first += (unsigned)nc_p;
+    }
+    if (tab_ok) a.tab_cut = n_cut;
+    for (int p = 0; p < n_tab; p++)
+        for (unsigned w = a.tab[p].first; w < (unsigned)a.tab[p].first + a.tab[p].nc; w++) a.wg_pos[w] = (unsigned char)p;
+    a.n_tab_wgs = (int)first;
+    return (int)first + a.uni_nc * cs->k1_uni_ng;
+}
+
+// The per-candidate accumulators (zero at rest) and the running minimum with its count of finished candidates into a.
+static int32_t k1_acc_alloc(slamhip_cs *cs, int count, k1_args &a)
 {
     slamhip_ctx *ctx = cs->ctx;
-    if (cs->n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "no scan set (slamhip_cs_set_scan)");
-    SH_TRY(cs_flush_scan(cs));
-    cs->k1_launch_no = cs->launch_count;
-    static const int force_global = env_int("SLAMHIP_K1_GLOBAL", 0);
-    static const int verify = env_int("SLAMHIP_K1_VERIFY", 0);
-    static const int tile_kb = env_int("SLAMHIP_K1_TILE_KB", 60);
-    static const int target_wgs = env_int("SLAMHIP_K1_TARGET_WGS", 512);
-    static const int target_wgs_uniform = env_int("SLAMHIP_K1_TARGET_WGS_UNIFORM", 768);
-    static const int cpl_env = env_int("SLAMHIP_K1_CPL", 0);           // candidates per lane: 0 = by launch size
-    static const int band_parts = env_int("SLAMHIP_K1_BAND_PARTS", 2);
-    static const int no_table = env_int("SLAMHIP_K1_NOTABLE", 0);
-    const bool sane = cs->pts_sane && cand_sane;
-    const bool tiled = sane && (cs->hs % 8 == 0) && !force_global;
-    if (cs->k1_prelaunch && !tiled) return CS_RC_NO_PRELAUNCH;      // (the fallback kernels read the scan's blocks on the host)
-#ifdef K1_TIMES
-    if (cs->k1_prelaunch) return CS_RC_NO_PRELAUNCH;               // (the developer build synchronises the stream inside this function: a prelaunched search would wait for a host that waits for it)
-#endif
-    const int n_rb = cs->n_rb;
-    int32_t *dist = want_dist ? cs->d_dist : nullptr;
-    unsigned long long *key = (unsigned long long *)key_dst;
-    // a ring launch: the result word is the ring's current slot (all ones now), and the launch rests the next one
-    unsigned long long *ring_slot = nullptr, *ring_reset = nullptr;
-    const bool ring = cs->k1_ring_request;
-    cs->k1_ring_request = false;
-    if (ring) {
-        if (!cs->d_k1_ring) {
-            SH_HIP(hipMalloc(&cs->d_k1_ring, sizeof(uint64_t) * K1_RING_SLOTS));
-            SH_HIP(hipMemsetAsync(cs->d_k1_ring, 0xFF, sizeof(uint64_t) * K1_RING_SLOTS, ctx->stream));
-            cs->k1_ring_pos = 0;
-        }
-        ring_slot = (unsigned long long *)cs->d_k1_ring + cs->k1_ring_pos % K1_RING_SLOTS;
-        ring_reset = (unsigned long long *)cs->d_k1_ring + (cs->k1_ring_pos + 1) % K1_RING_SLOTS;
-        key = ring_slot;
+    if (sh_div_up(count, K1_GROUP) + 2 > cs->k1_cap_groups) {
+        if (cs->d_k1_acc) (void)hipFree(cs->d_k1_acc);
+        cs->d_k1_acc = nullptr; cs->k1_cap_groups = 0;
+        const int cap = sh_div_up(count, K1_GROUP) + sh_div_up(count, K1_GROUP) / 4 + 16;
+        SH_HIP(hipMalloc(&cs->d_k1_acc, sizeof(unsigned long long) * (size_t)cap * K1_GROUP));
+        SH_HIP(hipMemsetAsync(cs->d_k1_acc, 0, sizeof(unsigned long long) * (size_t)cap * K1_GROUP, ctx->stream));
+        cs->k1_cap_groups = cap;
     }
-    const float bx = pose ? pose[0] : 0.f, by = pose ? pose[1] : 0.f, bth = pose ? pose[2] : 0.f;
+    if (!cs->d_k1_gmin) {
+        // the running minimum (all ones at rest) and the count of finished candidates (zero at rest): the launch's last
+        // finisher leaves them so
+        SH_HIP(hipMalloc(&cs->d_k1_gmin, 16));
+        SH_HIP(hipMemsetAsync(cs->d_k1_gmin, 0xff, 8, ctx->stream));
+        SH_HIP(hipMemsetAsync((char *)cs->d_k1_gmin + 8, 0, 8, ctx->stream));
+    }
+    a.gmin = cs->d_k1_gmin; a.done = (unsigned *)((char *)cs->d_k1_gmin + 8); a.acc = cs->d_k1_acc;
+    return SLAMHIP_OK;
+}
 
-    if (tiled) {
-        const int group = mode == 1 && (cs->k1_group == K1_GROUP_BIG || cs->k1_group == K1_GROUP_SMALL) ? cs->k1_group : K1_GROUP;   // (explicit lists: always 1024)
-        const int n_groups = sh_div_up(count, group);
-        int budget = tile_kb * 1024;
-        if (budget > 64 * 1024) budget = 64 * 1024;                // what the staging registers hold per pass
-        const size_t lds = (size_t)K1_TILE_OFS + (size_t)budget;
+// ---- the plan (k1_plan): one launch per search on a stream of its own, beside the search ---------------------------------
+// Made for every search with jitter bounds (mode 1) whose inputs are known to be in memory: the plan launch is not ordered
+// behind the operator's stream, so after a candidate gather or a scan upload in that stream (plan_inputs_after) it waits
+// until a search launch behind them has STARTED (the started word).  A slot of the plan buffers is reused K1_PLAN_SLOTS
+// plans later, when the search that read it has finished -- i.e. a later search launch has started; the host waits for
+// that if it is that far ahead of the device (it then is in nobody's way).  SLAMHIP_K1_PLAN=0: never.
+static int32_t k1_plan_launch(slamhip_cs *cs, k1_args &a, int mode, int group, int n_wgs, bool lat)
+{
+    slamhip_ctx *ctx = cs->ctx;
+    static const int plan_env = (int)sh_env_int("SLAMHIP_K1_PLAN", 1);
+    volatile uint32_t *h_started = (volatile uint32_t *)cs->h_key + 25;
+    a.started = (uint32_t *)cs->h_key + 25; a.launch_no = ++cs->k1_launches;
+    a.plan_rec = nullptr; a.plan_seq = 0;
+    // Which launches get one: those that will WAIT in the stream -- the search launch before this one has not even started
+    // (the started word), so this one is at least a whole search away from running and its plan has time to arrive: the
+    // throughput forms (enqueue-only searches, the batched all-reduce form) once the host runs ahead of the device.  A search
+    // that starts at once -- a blocking call, the first launches behind a synchronise, the per-scan flows, whose search follows
+    // its scan -- gets none: its plan would arrive late and cost the host a launch (measured: a blocking search 27.8 -> 31.6 us
+    // per call with one, the fused scan in the ordinary order 50 -> 54.5 us per scan).  Nor does a search launched ahead of its
+    // scan's tables: the tile steps need the tables.  (Measured and dropped in round 6: the candidates' (px, py, c, s) made once per
+    // search -- by the plan launch, or shared between a group's workgroups inside the search launch through memory -- instead of
+    // by every workgroup: reading them back costs a launch what the trigonometry does, 15.2 us with or without at the headline size.)
+    static const int plan_always = (int)sh_env_int("SLAMHIP_K1_PLAN_ALWAYS", 0);   // (tests: a plan for every eligible launch -- most arrive late, the race the stamps are for)
+    const bool stream_busy = plan_always || (int32_t)(*h_started - (a.launch_no - 1)) < 0;
+    bool plan_on = plan_env && mode == 1 && stream_busy && a.grp_bounds != nullptr && !cs->k1_prelaunch && !lat && !ctx->mail_off;
+    if (plan_on && cs->plan_inputs_after != 0) {
+        if ((int32_t)(*h_started - cs->plan_inputs_after) >= 0) cs->plan_inputs_after = 0;
+        else { plan_on = false; cs->plan_stats[3]++; }
+    }
+    if (plan_on) {
+        if (n_wgs > cs->plan_cap_wgs) {
+            SH_HIP(hipStreamSynchronize(ctx->stream));          // (searches in flight read the buffers)
+            const int cw = std::max(cs->plan_cap_wgs, n_wgs + n_wgs / 4 + 64);
+            cs_plan_free(cs);
+            for (int i = 0; i < K1_PLAN_SLOTS; i++) {
+                SH_HIP(hipMalloc(&cs->d_plan_rec[i], sizeof(uint32_t) * K1_PLAN_REC_WORDS * (size_t)cw));
+                SH_HIP(hipMemsetAsync(cs->d_plan_rec[i], 0, sizeof(uint32_t) * K1_PLAN_REC_WORDS * (size_t)cw, cs->plan_stream));
+            }
+            SH_HIP(hipStreamSynchronize(cs->plan_stream));
+            cs->plan_cap_wgs = cw;
+        }
+        const unsigned slot = cs->plan_count % K1_PLAN_SLOTS;
+        const uint32_t user = cs->plan_slot_user[slot];
+        if (user != 0 && (int32_t)(*h_started - (user + 1)) < 0) {
+            // The host is K1_PLAN_SLOTS - 1 searches ahead of the device: it waits for the slot -- backpressure, the device has
+            // work queued -- but never longer than 20 ms or the context's wait bound; past that the search goes without a plan
+            // (nothing fails because of a plan).
+            cs->plan_stats[2]++;
+            const int64_t bound_us = 1000 * (ctx->wait_timeout_ms > 0 && ctx->wait_timeout_ms < 20 ? ctx->wait_timeout_ms : 20);
+            const double t0w = k1_now_us();
+            for (int spins = 0; (int32_t)(*h_started - (user + 1)) < 0; spins++) {
+                __builtin_ia32_pause();
+                if ((spins & 1023) == 1023 && k1_now_us() - t0w > (double)bound_us) break;
+            }
+            if ((int32_t)(*h_started - (user + 1)) < 0) { plan_on = false; cs->plan_stats[3]++; }
+        }
+    }
+    if (plan_on) {
+        const unsigned slot = cs->plan_count % K1_PLAN_SLOTS;
+        if (++cs->plan_seq == 0) cs->plan_seq = 1;
+        a.plan_rec = cs->d_plan_rec[slot]; a.plan_seq = cs->plan_seq;
+        const dim3 pgrid((unsigned)n_wgs);
+        if (group == K1_GROUP_BIG) hipLaunchKernelGGL((k1_plan<K1_GROUP_BIG, 4>), pgrid, dim3(64), 0, cs->plan_stream, a, n_wgs);
+        else if (group == K1_GROUP_SMALL) hipLaunchKernelGGL((k1_plan<K1_GROUP_SMALL, 1>), pgrid, dim3(64), 0, cs->plan_stream, a, n_wgs);
+        else hipLaunchKernelGGL((k1_plan<K1_GROUP, 2>), pgrid, dim3(64), 0, cs->plan_stream, a, n_wgs);
+        SH_HIP(hipGetLastError());
+        cs->plan_slot_user[slot] = a.launch_no;
+        cs->plan_count++; cs->plan_stats[0]++;
+    }
+    if (!plan_on) cs->plan_stats[1]++;
+    return SLAMHIP_OK;
+}
 
-        k1_args a;
-        a.map = cs->d_hole; a.S = cs->hs; a.pts = cs->d_pts_sorted; a.ray_blk = cs->d_ray_blk; a.n_rays = cs->n_points;
-        a.pxcs = cs->d_pxcs; a.src3 = cs->d_ev_off; a.bx = bx; a.by = by; a.bth = bth; a.scale = cs->hscale;
-        a.count = count; a.n_groups = n_groups; a.budget = budget;
-        a.band_stage = k1_band_stage();
-        static const int noden = env_int("SLAMHIP_K1_NODEN", 0);
-        a.noden = noden;
-        a.nopad = k1_nopad();
-        static const int nosplit = env_int("SLAMHIP_K1_NOSPLIT", 0);
-        a.nosplit = nosplit;
-        a.ev_idx = cs->d_ev_idx; a.dist_out = dist; a.key_out = key; a.verify = cs->d_verify;
-        static const int no_bounds = env_int("SLAMHIP_K1_NOBOUNDS", 0);
-        a.grp_bounds = (mode == 1 && !no_bounds) ? cs->d_grp_bounds : nullptr;
-        a.offs_flat = cs->d_offs_flat; a.best_pose = (mode == 1 && cs->k1_want_pose) ? cs->d_best_pose : nullptr;
-        cs->k1_pose_written = a.best_pose != nullptr;
-        a.done_flag = cs->k1_done_flag; a.done_val = cs->k1_done_val;
-        cs->k1_done_armed = a.done_flag != nullptr;
-        a.sig = cs->k1_sig; a.sig_val = cs->k1_sig_val;
-        cs->k1_sig_armed = a.sig != nullptr;
-        a.ring_slot = ring_slot; a.ring_reset = ring_reset;
-        a.scan_flag = cs->k1_prelaunch ? cs->d_scan_flag : nullptr; a.scan_seq = cs->scan_flag_seq;
-        if (ring && (a.best_pose || a.done_flag || a.sig)) SH_FAIL(SLAMHIP_ERR_STATE, "a ring search delivers nothing but its key");
-
-        // launch layout
-        const bool have_spread = mode == 1 && !no_table && (int)cs->h_grp_dth.size() == n_groups;
-        // a workgroup's prologue costs as much as ~25 rays of gathers: small searches get fewer, larger chunks (a dozen
-        // rays or more each) rather than a full round of workgroups (measured at 4000 candidates x 400 rays: 21 -> 16 us)
-        int target = n_groups <= K1_TABLE_G ? target_wgs : target_wgs_uniform;
-        const long long by_work = (long long)n_groups * cs->n_points / 12;
-        if (by_work < target) target = (int)(by_work > n_groups ? by_work : n_groups);
-        g_cst.lap(8);
-        bool remake = cs->k1_layout_dirty || cs->k1_layout_groups != n_groups || cs->k1_layout_budget != budget || cs->k1_layout_spread != have_spread ||
-                      cs->k1_layout_target != target || (have_spread && !(fabsf(bth - cs->k1_layout_theta) < 0.1f));
-        if (cs->k1_prelaunch) {
-            // The launch precedes its scan's tables (cs_search_and_update_prelaunched): it keeps the last scan's layout, whose legality
-            // for the new ray blocks the caller tests when they exist (and abandons the launch if it fails); a layout that has to be
-            // remade for another reason needs the new blocks: no prelaunch.
-            if (remake) { cs->k1_ring_request = ring; return CS_RC_NO_PRELAUNCH; }
-            cs->k1_layout_stale = true;
-        } else
-        if (!remake && cs->k1_scan_dirty) {
-            // A new scan under an unchanged candidate list (the per-scan flow): the layout made for the last scan serves this one
-            // if its counts of ray ranges are legal for the new ray blocks -- only the balance of the launch depends on the layout,
-            // and consecutive scans look alike -- and the one for THIS scan is made while the host waits for the search
-            // (cs_layout_idle_refresh), for the next scan's launch: 8 us of estimate left the host's critical path between two
-            // scans (`CoreSLAMProcessor.Update` 66.6 -> 60 us; SLAMHIP_K1_LAYOUT_SYNC=1 makes every scan's layout before its launch).
-            static const int layout_sync = env_int("SLAMHIP_K1_LAYOUT_SYNC", 0);
-            if (layout_sync || !k1_layout_legal(cs)) remake = true;
-            else cs->k1_layout_stale = true;
-        }
-        cs->k1_scan_dirty = false;
-        if (remake) {
-            cs->k1_layout_theta = bth;
-            k1_make_layout(cs, n_groups, target, budget, have_spread, band_parts);
-            cs->k1_layout_dirty = false; cs->k1_layout_stale = false; cs->k1_layout_gen++;
-            cs->k1_layout_groups = n_groups; cs->k1_layout_budget = budget; cs->k1_layout_spread = have_spread; cs->k1_layout_target = target;
-            cs->k1_layout_band_parts = band_parts;
-        }
-        g_cst.lap(9);
-        {   // the accumulators count up to 2^14 - 1 arrivals per candidate and sum up to 2^20 rays (pathological scans: fallback kernels)
-            int nc_max = cs->k1_uni_nc;
-            for (size_t i = 0; i < cs->k1_tab_nc.size(); i++) nc_max = std::max(nc_max, cs->k1_tab_nc[i]);
-            if (nc_max >= (1 << (K1_ACC_ARRIVED - K1_ACC_INMAP)) || cs->n_points >= (1 << 20)) goto fallback;
-        }
-        static const int dump = env_int("SLAMHIP_K1_DUMP", 0);
-        if (dump) {                                                // debugging aid: the launch layout and its cost estimates
-            fprintf(stderr, "[slamhip] K1 layout: %d groups, %zu listed, uniform [%d, %d) x %d chunks (slowest range %.0f ray units with 8 per step; %d ray blocks)\n", n_groups, cs->k1_tab_group.size(),
-                    cs->k1_uni_g0, cs->k1_uni_g0 + cs->k1_uni_ng, cs->k1_uni_nc, k1_chunks_score(cs, cs->k1_uni_nc, 8.0), cs->n_rb);
-            for (size_t i = 0; i < cs->k1_tab_group.size(); i++) {
-                const int g = cs->k1_tab_group[i];
-                fprintf(stderr, "   group %3d: chunks %3d, dtheta %.4f rad, spread %.1f px, cost %.0f ray units\n", g, cs->k1_tab_nc[i],
-                        have_spread ? cs->h_grp_dth[(size_t)g] : 0.f, have_spread ? cs->h_grp_dxy[(size_t)g] : 0.f,
-                        have_spread ? k1_group_cost(cs, cs->k1_terms, g, budget) : 0.0);
-            }
-        }
-        // Ray ranges cut by cost (k1_balanced_cuts), remade when the scan, a count of ranges or the weight changed: the uniform
-        // part's and every listed group's (groups with the same count of ranges share the cut).  A cut may come out with fewer
-        // ranges than asked for: the group then runs with that many workgroups.
-        // The weight of a tile step in ray units: 26 where it was calibrated (2048^2 map = 51.2 pixels per metre, two candidates per
-        // lane), less on coarser maps (smaller tiles, and the 64-ray cap makes blocks long in rays: 1024^2 wants about half, 256^2
-        // none) and in proportion to what a ray costs the workgroup (four candidates per lane: a ray takes twice as long, the step
-        // does not).  SLAMHIP_K1_CUT_WFIX = 0 and SLAMHIP_K1_CUT_WKB = 0: the equal-count formula everywhere.
-        static const double cut_wkb = getenv("SLAMHIP_K1_CUT_WKB") ? atof(getenv("SLAMHIP_K1_CUT_WKB")) : 0.0;
-        const double cut_wfix = k1_cut_wfix(cs, group);
-        static const int cut_tab = env_int("SLAMHIP_K1_CUT_TAB", 0);      // (the listed groups too: measured slower)
-        const int n_tab = (int)cs->k1_tab_group.size();
-        const float pose3[3] = { bx, by, bth };
-        // The cuts cost the host ~7 us (mostly the exact box test of the pieces, k1_cuts_banded_rays) and buy a launch 1 - 2 us.  They
-        // are made (a) when a scan is searched for the SECOND time under one layout -- a list searched from many poses, a benchmark
-        // loop -- and (b), round 6, for every scan of the per-scan flow while the host waits for that scan's pose
-        // (cs_layout_idle_refresh: idle time), to be used by the NEXT scan's launch if they are legal for its ray blocks --
-        // consecutive scans look alike, and a cut only balances the launch.  Never on the host's critical path between two scans
-        // (measured there: CoreSLAMProcessor.Update 66 -> 77 us per scan).  SLAMHIP_K1_CUT_ALWAYS=1: always; SLAMHIP_K1_IDLE_CUTS=0: not (b).
-        static const int cut_always = env_int("SLAMHIP_K1_CUT_ALWAYS", 0);
-        const bool cut_repeat = cut_always || (cs->k1_cut_seen_scan == cs->scan_gen && cs->k1_cut_seen_layout == cs->k1_layout_gen);
-        cs->k1_cut_seen_scan = cs->scan_gen; cs->k1_cut_seen_layout = cs->k1_layout_gen;
-        const bool cuts_on = cut_repeat && (cut_wfix > 0.0 || cut_wkb > 0.0) && cs->n_points < 65536;
-        if (cuts_on && (cs->k1_cut_gen != cs->scan_gen || cs->k1_cut_layout_gen != cs->k1_layout_gen)) {
-            cs->k1_cut_cache.clear();
-            cs->k1_cut_gen = cs->scan_gen; cs->k1_cut_layout_gen = cs->k1_layout_gen;
-            const double tw0 = k1_now_us();
-            k1_cut_weights(cs, n_groups, have_spread, cut_wfix, cut_wkb, budget, cs->k1_cut_wb);
-            g_cut_t[0] += k1_now_us() - tw0;
-        }
-        cs->k1_cut_cache.reserve(K1_TABLE_G + 8);                      // (the entries' addresses are held below: no reallocation)
-        auto cuts_for = [&](int nrc) -> const std::vector<int> * {       // nullptr: no cut for this count (the formula stays)
-            if (!cuts_on || nrc < 2) return nullptr;
-            for (auto &e : cs->k1_cut_cache) if (e.first == nrc) return e.second.empty() ? nullptr : &e.second;
-            cs->k1_cut_cache.emplace_back(nrc, std::vector<int>());
-            std::vector<int> &c = cs->k1_cut_cache.back().second;
-            k1_cuts_make(cs, nrc, have_spread, pose3, budget, c);
-            return c.empty() ? nullptr : &c;
-        };
-        static const int cut_times = env_int("SLAMHIP_K1_CUT_TIMES", 0);     // developer aid: host time of the cuts, printed every 64 makes
-        timespec ct0; if (cut_times) clock_gettime(CLOCK_MONOTONIC, &ct0);
-        a.uni_cut = 0; a.tab_cut = 0;
-        int n_cut = 0;                                                 // entries of a.cut in use
-        a.uni_g0 = cs->k1_uni_g0; a.uni_ng = cs->k1_uni_ng > 0 ? cs->k1_uni_ng : 1; a.uni_nc = cs->k1_uni_nc;
-        cs->k1_launch_prev_cuts = false;
-        if (cs->k1_uni_ng > 0) {
-            const std::vector<int> *c = cuts_for(cs->k1_uni_nc);
-            if (!c && !cuts_on && mode == 1 && !cs->k1_prev_cuts.empty() && cs->k1_prev_cuts_nc == cs->k1_uni_nc && cs->k1_prev_cuts_layout_gen == cs->k1_layout_gen &&
-                cs->k1_prev_cuts_points == cs->n_points && (cs->k1_prelaunch || k1_cuts_legal(cs, cs->k1_prev_cuts))) {
-                // the cut made for the scan before (idle refresh): legal for this scan's blocks -- or, for a launch that precedes its
-                // scan's tables, tested when they exist (cs_k1_layout_legal: the launch is abandoned if it is not)
-                c = &cs->k1_prev_cuts;
-                cs->k1_launch_prev_cuts = true;
-            }
-            if (c && (int)c->size() <= K1_MAXCUT) {
-                for (size_t i = 0; i < c->size(); i++) a.cut[i] = (unsigned short)(*c)[i];
-                n_cut = (int)c->size();
-                a.uni_cut = 1; a.uni_nc = (int)c->size() - 1;
-            }
-        }
-        if (cut_times) {
-            static thread_local double acc = 0.0; static thread_local int nacc = 0;   // (per host thread, like g_cut_t: a group drives one thread per GPU)
-            timespec ct1; clock_gettime(CLOCK_MONOTONIC, &ct1);
-            acc += (double)(ct1.tv_sec - ct0.tv_sec) * 1e6 + (double)(ct1.tv_nsec - ct0.tv_nsec) * 1e-3;
-            if (++nacc == 64) {
-                fprintf(stderr, "[slamhip] K1 cuts: %.2f us of host time per launch (uniform part): weights %.2f | balanced cuts %.2f | banded check %.2f\n", acc / nacc,
-                        g_cut_t[0] / nacc, g_cut_t[1] / nacc, g_cut_t[2] / nacc);
-                acc = 0.0; nacc = 0; g_cut_t[0] = g_cut_t[1] = g_cut_t[2] = 0.0;
-            }
-        }
-        // the listed groups: all of them from the table, or none
-        std::vector<const std::vector<int> *> tcut((size_t)n_tab, nullptr);
-        bool tab_ok = cut_tab && n_tab > 0;
-        long long tab_wgs = 0;
-        for (int p = 0; p < n_tab && tab_ok; p++) {
-            const int nbp = cs->k1_tab_nbp[(size_t)p] > 0 ? cs->k1_tab_nbp[(size_t)p] : 1;
-            tcut[(size_t)p] = cuts_for(cs->k1_tab_nc[(size_t)p] / nbp);
-            if (!tcut[(size_t)p]) tab_ok = false; else tab_wgs += (long long)(tcut[(size_t)p]->size() - 1) * nbp;
-        }
-        if (tab_ok && n_cut + tab_wgs > K1_MAXCUT) tab_ok = false;
-        unsigned first = 0;
-        for (int p = 0; p < n_tab; p++) {
-            k1_args::tab_rec &rec = a.tab[p];
-            const int nbp = cs->k1_tab_nbp[(size_t)p] > 0 ? cs->k1_tab_nbp[(size_t)p] : 1;
-            const int nc_p = tab_ok ? (int)(tcut[(size_t)p]->size() - 1) * nbp : cs->k1_tab_nc[(size_t)p];
-            rec.group = (unsigned short)cs->k1_tab_group[(size_t)p];
-            rec.nbp = (unsigned short)cs->k1_tab_nbp[(size_t)p];
-            rec.first = (unsigned short)first; rec.nc = (unsigned short)nc_p;
-            if (tab_ok)
-                for (int w = 0; w < nc_p; w++) a.cut[n_cut + (int)first + w] = (unsigned short)(*tcut[(size_t)p])[(size_t)(w / nbp)];
-            first += (unsigned)nc_p;
-        }
-        if (tab_ok) a.tab_cut = n_cut;
-        if (dump && a.uni_cut) {
-            fprintf(stderr, "   uniform ranges cut by cost (%d of %d asked for; ray blocks start at", a.uni_nc, cs->k1_uni_nc);
-            for (int b = 0; b <= cs->n_rb; b++) fprintf(stderr, " %d", cs->h_rb_start[(size_t)b]);
-            fprintf(stderr, "):");
-            for (int c = 0; c <= a.uni_nc; c++) fprintf(stderr, " %d", (int)a.cut[c]);
-            fprintf(stderr, "\n");
-        }
-        for (int p = 0; p < n_tab; p++)
-            for (unsigned w = a.tab[p].first; w < (unsigned)a.tab[p].first + a.tab[p].nc; w++) a.wg_pos[w] = (unsigned char)p;
-        a.n_tab_wgs = (int)first;
-        const int n_wgs = (int)first + a.uni_nc * cs->k1_uni_ng;
-        // candidates per lane: 2 (512 lanes, 8 waves) measured best or equal from 16k to 256k candidates on MI355X;
-        // 1 (16 waves: slow start) and 4 (4 waves: the VALU starves at 2 waves / SIMD) stay selectable for experiments
-        const int cpl = cpl_env == 1 || cpl_env == 4 ? cpl_env : 2;
-        if (sh_div_up(count, K1_GROUP) + 2 > cs->k1_cap_groups) {
-            if (cs->d_k1_acc) (void)hipFree(cs->d_k1_acc);
-            cs->d_k1_acc = nullptr; cs->k1_cap_groups = 0;
-            const int cap = sh_div_up(count, K1_GROUP) + sh_div_up(count, K1_GROUP) / 4 + 16;
-            SH_HIP(hipMalloc(&cs->d_k1_acc, sizeof(unsigned long long) * (size_t)cap * K1_GROUP));
-            SH_HIP(hipMemsetAsync(cs->d_k1_acc, 0, sizeof(unsigned long long) * (size_t)cap * K1_GROUP, ctx->stream));
-            cs->k1_cap_groups = cap;
-        }
-        if (!cs->d_k1_gmin) {
-            // the running minimum (all ones at rest) and the count of finished candidates (zero at rest): the launch's last
-            // finisher leaves them so
-            SH_HIP(hipMalloc(&cs->d_k1_gmin, 16));
-            SH_HIP(hipMemsetAsync(cs->d_k1_gmin, 0xff, 8, ctx->stream));
-            SH_HIP(hipMemsetAsync((char *)cs->d_k1_gmin + 8, 0, 8, ctx->stream));
-        }
-        a.gmin = cs->d_k1_gmin; a.done = (unsigned *)((char *)cs->d_k1_gmin + 8); a.acc = cs->d_k1_acc;
-        if (mode == 1) { cs->k1_last_pose[0] = bx; cs->k1_last_pose[1] = by; cs->k1_last_pose[2] = bth; cs->k1_last_group = group; cs->k1_last_valid = true; }
-        static const int no_lat = env_int("SLAMHIP_K1_NO_LATTICE", 0);       // (a lattice list through the ordinary kernel: same results, for comparison)
-        const bool lat2 = mode == 1 && !verify && !no_lat && cs->k1_lattice == 2 && group == K1_GROUP && cpl == 2;
-        const bool lat4 = mode == 1 && !verify && !no_lat && cs->k1_lattice == 4 && group == K1_GROUP_BIG;
-        g_cst.lap(1);
-        SH_TRY(cs_side_join(cs));
-        // ---- the plan (k1_plan): one launch per search on a stream of its own, beside the search ---------------------------------
-        // Made for every search with jitter bounds (mode 1) whose inputs are known to be in memory: the plan launch is not ordered
-        // behind the operator's stream, so after a candidate gather or a scan upload in that stream (plan_inputs_after) it waits
-        // until a search launch behind them has STARTED (the started word).  A slot of the plan buffers is reused K1_PLAN_SLOTS
-        // plans later, when the search that read it has finished -- i.e. a later search launch has started; the host waits for
-        // that if it is that far ahead of the device (it then is in nobody's way).  SLAMHIP_K1_PLAN=0: never.
-        static const int plan_env = env_int("SLAMHIP_K1_PLAN", 1);
-        volatile uint32_t *h_started = (volatile uint32_t *)cs->h_key + 25;
-        a.started = (uint32_t *)cs->h_key + 25; a.launch_no = ++cs->k1_launches;
-        a.plan_rec = nullptr; a.plan_seq = 0;
-        // Which launches get one: those that will WAIT in the stream -- the search launch before this one has not even started
-        // (the started word), so this one is at least a whole search away from running and its plan has time to arrive: the
-        // throughput forms (enqueue-only searches, the batched all-reduce form) once the host runs ahead of the device.  A search
-        // that starts at once -- a blocking call, the first launches behind a synchronise, the per-scan flows, whose search follows
-        // its scan -- gets none: its plan would arrive late and cost the host a launch (measured: a blocking search 27.8 -> 31.6 us
-        // per call with one, the fused scan in the ordinary order 50 -> 54.5 us per scan).  Nor does a search launched ahead of its
-        // scan's tables: the tile steps need the tables.  (Measured and dropped in round 6: the candidates' (px, py, c, s) made once per
-        // search -- by the plan launch, or shared between a group's workgroups inside the search launch through memory -- instead of
-        // by every workgroup: reading them back costs a launch what the trigonometry does, 15.2 us with or without at the headline size.)
-        static const int plan_always = env_int("SLAMHIP_K1_PLAN_ALWAYS", 0);   // (tests: a plan for every eligible launch -- most arrive late, the race the stamps are for)
-        const bool stream_busy = plan_always || (int32_t)(*h_started - (a.launch_no - 1)) < 0;
-        bool plan_on = plan_env && mode == 1 && stream_busy && a.grp_bounds != nullptr && !cs->k1_prelaunch && !lat2 && !lat4 && !ctx->mail_off;
-        const int n_plan_wgs = n_wgs;
-        if (plan_on && cs->plan_inputs_after != 0) {
-            if ((int32_t)(*h_started - cs->plan_inputs_after) >= 0) cs->plan_inputs_after = 0;
-            else { plan_on = false; cs->plan_stats[3]++; }
-        }
-        if (plan_on) {
-            if (n_wgs > cs->plan_cap_wgs) {
-                SH_HIP(hipStreamSynchronize(ctx->stream));          // (searches in flight read the buffers)
-                const int cw = std::max(cs->plan_cap_wgs, n_wgs + n_wgs / 4 + 64);
-                cs_plan_free(cs);
-                for (int i = 0; i < K1_PLAN_SLOTS; i++) {
-                    SH_HIP(hipMalloc(&cs->d_plan_rec[i], sizeof(uint32_t) * K1_PLAN_REC_WORDS * (size_t)cw));
-                    SH_HIP(hipMemsetAsync(cs->d_plan_rec[i], 0, sizeof(uint32_t) * K1_PLAN_REC_WORDS * (size_t)cw, cs->plan_stream));
-                }
-                SH_HIP(hipStreamSynchronize(cs->plan_stream));
-                cs->plan_cap_wgs = cw;
-            }
-            const unsigned slot = cs->plan_count % K1_PLAN_SLOTS;
-            const uint32_t user = cs->plan_slot_user[slot];
-            if (user != 0 && (int32_t)(*h_started - (user + 1)) < 0) {
-                // The host is K1_PLAN_SLOTS - 1 searches ahead of the device: it waits for the slot -- backpressure, the device has
-                // work queued -- but never longer than 20 ms or the context's wait bound; past that the search goes without a plan
-                // (nothing fails because of a plan).
-                cs->plan_stats[2]++;
-                const int64_t bound_us = 1000 * (ctx->wait_timeout_ms > 0 && ctx->wait_timeout_ms < 20 ? ctx->wait_timeout_ms : 20);
-                const double t0w = k1_now_us();
-                for (int spins = 0; (int32_t)(*h_started - (user + 1)) < 0; spins++) {
-                    __builtin_ia32_pause();
-                    if ((spins & 1023) == 1023 && k1_now_us() - t0w > (double)bound_us) break;
-                }
-                if ((int32_t)(*h_started - (user + 1)) < 0) { plan_on = false; cs->plan_stats[3]++; }
-            }
-        }
-        if (plan_on) {
-            const unsigned slot = cs->plan_count % K1_PLAN_SLOTS;
-            if (++cs->plan_seq == 0) cs->plan_seq = 1;
-            a.plan_rec = cs->d_plan_rec[slot]; a.plan_seq = cs->plan_seq;
-            const dim3 pgrid((unsigned)n_plan_wgs);
-            if (group == K1_GROUP_BIG) hipLaunchKernelGGL((k1_plan<K1_GROUP_BIG, 4>), pgrid, dim3(64), 0, cs->plan_stream, a, n_plan_wgs);
-            else if (group == K1_GROUP_SMALL) hipLaunchKernelGGL((k1_plan<K1_GROUP_SMALL, 1>), pgrid, dim3(64), 0, cs->plan_stream, a, n_plan_wgs);
-            else if (cpl == 4) hipLaunchKernelGGL((k1_plan<K1_GROUP, 4>), pgrid, dim3(64), 0, cs->plan_stream, a, n_plan_wgs);
-            else if (cpl == 2) hipLaunchKernelGGL((k1_plan<K1_GROUP, 2>), pgrid, dim3(64), 0, cs->plan_stream, a, n_plan_wgs);
-            else hipLaunchKernelGGL((k1_plan<K1_GROUP, 1>), pgrid, dim3(64), 0, cs->plan_stream, a, n_plan_wgs);
-            SH_HIP(hipGetLastError());
-            cs->plan_slot_user[slot] = a.launch_no;
-            cs->plan_count++; cs->plan_stats[0]++;
-        }
-        if (!plan_on) cs->plan_stats[1]++;
-        g_cst.lap(2);
-        {
-            sh_timer t(ctx, SLAMHIP_K_CS_DISTANCE);
+// The search launch: k1_search_tiled for the mode, the check build (SLAMHIP_K1_VERIFY) or a heading lattice, and the group size
+// (candidates per lane: 4 for K1_GROUP_BIG, 1 for K1_GROUP_SMALL, 2 for K1_GROUP -- 512 lanes, 8 waves, measured best or equal
+// from 16k to 256k candidates on MI355X).
+static void k1_search_launch(slamhip_cs *cs, const k1_args &a, int mode, int group, int n_wgs, size_t lds, bool verify, bool lat2, bool lat4)
+{
+    slamhip_ctx *ctx = cs->ctx;
+    sh_timer t(ctx, SLAMHIP_K_CS_DISTANCE);
 #define K1_LAUNCH(M, V, C, G) hipLaunchKernelGGL((k1_search_tiled<M, V, C, G>), dim3(n_wgs), dim3(G / C), lds, ctx->stream, a)
 #define K1_LAUNCH_LAT(C, G) hipLaunchKernelGGL((k1_search_tiled<1, false, C, G, true>), dim3(n_wgs), dim3(G / C), lds, ctx->stream, a)
-#define K1_LAUNCH_C(M, V) { if (group == K1_GROUP_BIG) K1_LAUNCH(M, V, 4, K1_GROUP_BIG); else if (group == K1_GROUP_SMALL) K1_LAUNCH(M, V, 1, K1_GROUP_SMALL); else if (cpl == 4) K1_LAUNCH(M, V, 4, K1_GROUP); else if (cpl == 2) K1_LAUNCH(M, V, 2, K1_GROUP); else K1_LAUNCH(M, V, 1, K1_GROUP); }
-            if (lat2) K1_LAUNCH_LAT(2, K1_GROUP);
-            else if (lat4) K1_LAUNCH_LAT(4, K1_GROUP_BIG);
-            else if (verify) { if (mode == 0) K1_LAUNCH_C(0, true) else if (mode == 1) K1_LAUNCH_C(1, true) else K1_LAUNCH_C(2, true) }
-            else        { if (mode == 0) K1_LAUNCH_C(0, false) else if (mode == 1) K1_LAUNCH_C(1, false) else K1_LAUNCH_C(2, false) }
+#define K1_LAUNCH_C(M, V) { if (group == K1_GROUP_BIG) K1_LAUNCH(M, V, 4, K1_GROUP_BIG); else if (group == K1_GROUP_SMALL) K1_LAUNCH(M, V, 1, K1_GROUP_SMALL); else K1_LAUNCH(M, V, 2, K1_GROUP); }
+    if (lat2) K1_LAUNCH_LAT(2, K1_GROUP);
+    else if (lat4) K1_LAUNCH_LAT(4, K1_GROUP_BIG);
+    else if (verify) { if (mode == 0) K1_LAUNCH_C(0, true) else if (mode == 1) K1_LAUNCH_C(1, true) else K1_LAUNCH_C(2, true) }
+    else        { if (mode == 0) K1_LAUNCH_C(0, false) else if (mode == 1) K1_LAUNCH_C(1, false) else K1_LAUNCH_C(2, false) }
 #undef K1_LAUNCH_C
 #undef K1_LAUNCH_LAT
 #undef K1_LAUNCH
-        }
-        SH_HIP(hipGetLastError());
-        if (ring) { cs->k1_ring_last = (uint64_t *)ring_slot; cs->k1_ring_pos++; }
-#ifdef K1_TIMES
-        {
-            static thread_local int calls = 0;
-            if (++calls == 8) {
-                (void)hipStreamSynchronize(ctx->stream);
-                const int nw = n_wgs < 4096 ? n_wgs : 4096;
-                std::vector<unsigned long long> h((size_t)nw * 16);
-                (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_k1_times), sizeof(unsigned long long) * h.size());
-                unsigned long long t0 = ~0ull, t1 = 0;
-                auto endof = [&](int i) { unsigned long long e = h[i * 16 + 8]; if (h[i * 16 + 9] > e) e = h[i * 16 + 9]; return e; };
-                for (int i = 0; i < nw; i++) { if (h[i * 16] < t0) t0 = h[i * 16]; if (endof(i) > t1) t1 = endof(i); }
-                static const char *nm[9] = { "q", "wred", "bnd", "boxes", "steps", "tile", "compute", "publish", "tail" };
-                double acc[9] = { 0 }; int nlast = 0;
-                for (int i = 0; i < nw; i++) {
-                    for (int k = 0; k < 8; k++) acc[k] += (double)(h[i * 16 + k + 1] - h[i * 16 + k]) * 0.01;
-                    if (h[i * 16 + 9] > h[i * 16 + 8]) { acc[8] += (double)(h[i * 16 + 9] - h[i * 16 + 8]) * 0.01; nlast++; }
-                }
-                fprintf(stderr, "[k1 times] WGs %d (groups %d: %d listed, %d x %d uniform; %d candidates per lane) span %.2f us; mean per WG:", n_wgs, n_groups, n_tab, cs->k1_uni_ng, cs->k1_uni_nc, cpl, (double)(t1 - t0) * 0.01);
-                for (int k = 0; k < 8; k++) fprintf(stderr, " %s %.2f |", nm[k], acc[k] / nw);
-                fprintf(stderr, " reducers (%d) %.2f us\n", nlast, nlast ? acc[8] / nlast : 0.0);
-                {
-                    std::vector<unsigned long long> ws((size_t)nw * 16);
-                    (void)hipMemcpyFromSymbol(ws.data(), HIP_SYMBOL(g_k1_wstart), sizeof(unsigned long long) * ws.size());
-                    double skew = 0, mx = 0;
-                    for (int i = 0; i < nw; i++) {
-                        unsigned long long lo = ~0ull, hi = 0;
-                        for (int w = 0; w < (group != K1_GROUP ? 8 : K1_GROUP / cpl / 64); w++) { lo = std::min(lo, ws[i * 16 + w]); hi = std::max(hi, ws[i * 16 + w]); }
-                        skew += (double)(hi - lo) * 0.01; mx = std::max(mx, (double)(hi - lo) * 0.01);
-                    }
-                    fprintf(stderr, "[k1 times] wave start skew inside a workgroup: mean %.2f us, max %.2f us\n", skew / nw, mx);
-                }
-                std::vector<int> order((size_t)nw);
-                for (int i = 0; i < nw; i++) order[(size_t)i] = i;
-                std::sort(order.begin(), order.end(), [&](int x, int y) { return endof(x) > endof(y); });
-                for (int oi = 0; oi < nw; oi += (oi < 12 ? 1 : nw / 16 > 0 ? nw / 16 : 1)) {
-                    const int i = order[(size_t)oi];
-                    fprintf(stderr, "  wg %4d: start +%6.2f |", i, (double)(h[i * 16] - t0) * 0.01);
-                    for (int k = 0; k < 8; k++) fprintf(stderr, " %s %5.2f", nm[k], (double)(h[i * 16 + k + 1] - h[i * 16 + k]) * 0.01);
-                    fprintf(stderr, " tail %5.2f | end +%6.2f | g %2d nc %2d rays shared %d global %d band %d",
-                            h[i * 16 + 9] > h[i * 16 + 8] ? (double)(h[i * 16 + 9] - h[i * 16 + 8]) * 0.01 : 0.0,
-                            (double)(endof(i) - t0) * 0.01, (int)h[i * 16 + 14], (int)h[i * 16 + 15], (int)h[i * 16 + 11],
-                            (int)h[i * 16 + 12], (int)h[i * 16 + 13]);
-                    {
-                        unsigned long long sbx[8];
-                        (void)hipMemcpyFromSymbol(sbx, HIP_SYMBOL(g_k1_sub), sizeof(sbx), sizeof(unsigned long long) * (size_t)i * 8);
-                        fprintf(stderr, " | steps");
-                        for (int k = 5; k < 8; k++) if (sbx[k]) fprintf(stderr, " [kind %d tile %d x %d, %d rays]", (int)(sbx[k] & 15), (int)((sbx[k] >> 4) & 0xfff), (int)((sbx[k] >> 16) & 0xffff), (int)(sbx[k] >> 32));
-                        fprintf(stderr, "\n");
-                    }
-                }
-                {   // per CU: workgroups hosted and the time the last of them ends
-                    std::vector<unsigned long long> ws((size_t)nw * 16);
-                    (void)hipMemcpyFromSymbol(ws.data(), HIP_SYMBOL(g_k1_wstart), sizeof(unsigned long long) * ws.size());
-                    std::vector<int> cnt(16 * 256, 0); std::vector<double> cend(16 * 256, 0.0), csum(16 * 256, 0.0);
-                    for (int i = 0; i < nw; i++) {
-                        const int cu = (int)(((ws[i * 16 + 15] >> 16) & 15) * 256 + (ws[i * 16 + 15] & 255));
-                        cnt[cu]++; cend[cu] = std::max(cend[cu], (double)(endof(i) - t0) * 0.01);
-                        csum[cu] += (double)(h[i * 16 + 7] - h[i * 16 + 6]) * 0.01;
-                    }
-                    int ncu = 0, hist[8] = { 0 }; double emean = 0, emax = 0, emin = 1e9;
-                    for (int c = 0; c < 16 * 256; c++) if (cnt[c]) { ncu++; hist[cnt[c] < 7 ? cnt[c] : 7]++; emean += cend[c]; emax = std::max(emax, cend[c]); emin = std::min(emin, cend[c]); }
-                    fprintf(stderr, "[k1 times] CUs used %d; workgroups per CU: 1:%d 2:%d 3:%d 4+:%d; CU end time mean %.2f min %.2f max %.2f us\n",
-                            ncu, hist[1], hist[2], hist[3], hist[4] + hist[5] + hist[6] + hist[7], emean / std::max(ncu, 1), emin, emax);
-                    // pairs sharing a CU (workgroups i and i + CUs): compute intervals and a solo estimate (half of the overlap each)
-                    int same = 0;
-                    for (int i = 0; i + 256 < nw; i++) if (ws[i * 16 + 15] == ws[(i + 256) * 16 + 15]) same++;
-                    fprintf(stderr, "[k1 times] pairs (i, i+256) on the same CU: %d\n", same);
-                    for (int i = 0; i + 256 < nw; i++) {
-                        const int j = i + 256;
-                        const double sa = (double)(h[i * 16 + 6] - t0) * 0.01, ea = (double)(h[i * 16 + 7] - t0) * 0.01;
-                        const double sb = (double)(h[j * 16 + 6] - t0) * 0.01, eb = (double)(h[j * 16 + 7] - t0) * 0.01;
-                        const double ov = std::max(0.0, std::min(ea, eb) - std::max(sa, sb));
-                        fprintf(stderr, "PAIR %3d g %2d sh %3d gl %3d bd %3d comp %5.2f solo %5.2f | %3d g %2d sh %3d gl %3d bd %3d comp %5.2f solo %5.2f | end %5.2f\n",
-                                i, (int)h[i * 16 + 14], (int)h[i * 16 + 11], (int)h[i * 16 + 12], (int)h[i * 16 + 13], ea - sa, ea - sa - ov / 2,
-                                j, (int)h[j * 16 + 14], (int)h[j * 16 + 11], (int)h[j * 16 + 12], (int)h[j * 16 + 13], eb - sb, eb - sb - ov / 2,
-                                std::max((double)(endof(i) - t0), (double)(endof(j) - t0)) * 0.01);
-                    }
-                }
-                {   // inside the compute phase (wave 0 of every workgroup): staging of the steps after the first, prefetch issue, gather loops
-                    std::vector<unsigned long long> sb((size_t)nw * 8);
-                    (void)hipMemcpyFromSymbol(sb.data(), HIP_SYMBOL(g_k1_sub), sizeof(unsigned long long) * sb.size());
-                    double a0 = 0, a1 = 0, a2 = 0, a3 = 0, mhz = 0; int nm_ = 0;
-                    for (int i = 0; i < nw; i++) {
-                        a0 += (double)sb[i * 8] * 0.01; a1 += (double)sb[i * 8 + 1] * 0.01; a2 += (double)sb[i * 8 + 2] * 0.01; a3 += (double)sb[i * 8 + 3];
-                        const double comp = (double)(h[i * 16 + 7] - h[i * 16 + 6]) * 0.01;
-                        if (comp > 1.0) { mhz += (double)sb[i * 8 + 4] / (comp + (double)(h[i * 16 + 6] - h[i * 16 + 5]) * 0.01); nm_++; }
-                    }
-                    fprintf(stderr, "[k1 times] compute phase, mean per WG: steps %.2f | restaging %.2f us | prefetch issue %.2f us | gather loops %.2f us | shader clock ~%.0f MHz (steps incl. first staging)\n",
-                            a3 / nw, a0 / nw, a1 / nw, a2 / nw, nm_ ? mhz / nm_ : 0.0);
-                    for (int oi = 0; oi < nw; oi += nw / 24 > 0 ? nw / 24 : 1) {
-                        const int i = order[(size_t)oi];
-                        fprintf(stderr, "  wg %4d g %2d: steps %d restaging %5.2f prefetch %5.2f loops %5.2f | rays shared %d global %d band %d\n", i, (int)h[i * 16 + 14], (int)sb[i * 8 + 3],
-                                (double)sb[i * 8] * 0.01, (double)sb[i * 8 + 1] * 0.01, (double)sb[i * 8 + 2] * 0.01, (int)h[i * 16 + 11], (int)h[i * 16 + 12], (int)h[i * 16 + 13]);
-                    }
-                }
-                // per group: chunks, ray-steps per kind, mean / max compute time
-                for (int g = 0; g < n_groups; g++) {
-                    double cs_ = 0, cm = 0; int n = 0; long long k4[4] = { 0, 0, 0, 0 };
-                    for (int i = 0; i < nw; i++) if ((int)h[i * 16 + 14] == g) {
-                        const double c = (double)(h[i * 16 + 7] - h[i * 16 + 6]) * 0.01;
-                        cs_ += c; cm = std::max(cm, c); n++;
-                        for (int k = 0; k < 4; k++) k4[k] += (long long)h[i * 16 + 10 + k];
-                    }
-                    fprintf(stderr, "  group %2d: chunks %2d | ray-steps own %lld shared %lld global %lld band %lld | compute mean %.2f max %.2f us\n",
-                            g, n, k4[0], k4[1], k4[2], k4[3], n ? cs_ / n : 0.0, cm);
-                }
-            }
-        }
-#endif
-        return SLAMHIP_OK;
-    }
+}
 
-fallback:
-    // ---- fallback: candidate transform, bounds-checked global gathers, reduction -----------------------------------
+// ---- fallback: candidate transform, bounds-checked global gathers, reduction -----------------------------------
+static int32_t k1_launch_fallback(slamhip_cs *cs, int mode, const float p[3], int count, bool sane, int32_t *dist, unsigned long long *key,
+                                  unsigned long long *ring_slot, unsigned long long *ring_reset)
+{
+    slamhip_ctx *ctx = cs->ctx;
+    const int n_rb = cs->n_rb;
     cs->k1_pose_written = false; cs->k1_done_armed = false; cs->k1_sig_armed = false;
     SH_TRY(cs_side_join(cs));
     {
         sh_timer t(ctx, SLAMHIP_K_CS_PREP);
         const dim3 grid(sh_div_up(count, K1_THREADS));
 #define K1_PREP(M) hipLaunchKernelGGL(k1_prep_pxcs<M>, grid, dim3(K1_THREADS), 0, ctx->stream, (const float *)cs->d_ev_off, \
-                       bx, by, bth, cs->hscale, cs->d_pxcs, count, key)
+                       p[0], p[1], p[2], cs->hscale, cs->d_pxcs, count, key)
         if (mode == 0) K1_PREP(0); else if (mode == 1) K1_PREP(1); else K1_PREP(2);
 #undef K1_PREP
     }
@@ -2254,9 +1987,217 @@ fallback:
                            count, cs->n_points, cs->d_ev_idx, dist, key);
     }
     SH_HIP(hipGetLastError());
-    if (ring) {                                                    // (the fallback's first kernel arms its own key; the next slot is rested by a fill)
+    if (ring_slot) {                                               // (the fallback's first kernel arms its own key; the next slot is rested by a fill)
         SH_HIP(hipMemsetAsync(ring_reset, 0xFF, sizeof(uint64_t), ctx->stream));
         cs->k1_ring_last = (uint64_t *)ring_slot; cs->k1_ring_pos++;
     }
     return SLAMHIP_OK;
+}
+
+#ifdef K1_TIMES
+static void k1_times_report(slamhip_cs *cs, int n_wgs, int n_groups, int n_tab, int group)
+{
+    slamhip_ctx *ctx = cs->ctx;
+    const int cpl = 2;                                             // (K1_GROUP's candidates per lane)
+    static thread_local int calls = 0;
+    if (++calls == 8) {
+        (void)hipStreamSynchronize(ctx->stream);
+        const int nw = n_wgs < 4096 ? n_wgs : 4096;
+        std::vector<unsigned long long> h((size_t)nw * 16);
+        (void)hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_k1_times), sizeof(unsigned long long) * h.size());
+        unsigned long long t0 = ~0ull, t1 = 0;
+        auto endof = [&](int i) { unsigned long long e = h[i * 16 + 8]; if (h[i * 16 + 9] > e) e = h[i * 16 + 9]; return e; };
+        for (int i = 0; i < nw; i++) { if (h[i * 16] < t0) t0 = h[i * 16]; if (endof(i) > t1) t1 = endof(i); }
+        static const char *nm[9] = { "q", "wred", "bnd", "boxes", "steps", "tile", "compute", "publish", "tail" };
+        double acc[9] = { 0 }; int nlast = 0;
+        for (int i = 0; i < nw; i++) {
+            for (int k = 0; k < 8; k++) acc[k] += (double)(h[i * 16 + k + 1] - h[i * 16 + k]) * 0.01;
+            if (h[i * 16 + 9] > h[i * 16 + 8]) { acc[8] += (double)(h[i * 16 + 9] - h[i * 16 + 8]) * 0.01; nlast++; }
+        }
+        fprintf(stderr, "[k1 times] WGs %d (groups %d: %d listed, %d x %d uniform; %d candidates per lane) span %.2f us; mean per WG:", n_wgs, n_groups, n_tab, cs->k1_uni_ng, cs->k1_uni_nc, cpl, (double)(t1 - t0) * 0.01);
+        for (int k = 0; k < 8; k++) fprintf(stderr, " %s %.2f |", nm[k], acc[k] / nw);
+        fprintf(stderr, " reducers (%d) %.2f us\n", nlast, nlast ? acc[8] / nlast : 0.0);
+        {
+            std::vector<unsigned long long> ws((size_t)nw * 16);
+            (void)hipMemcpyFromSymbol(ws.data(), HIP_SYMBOL(g_k1_wstart), sizeof(unsigned long long) * ws.size());
+            double skew = 0, mx = 0;
+            for (int i = 0; i < nw; i++) {
+                unsigned long long lo = ~0ull, hi = 0;
+                for (int w = 0; w < (group != K1_GROUP ? 8 : K1_GROUP / cpl / 64); w++) { lo = std::min(lo, ws[i * 16 + w]); hi = std::max(hi, ws[i * 16 + w]); }
+                skew += (double)(hi - lo) * 0.01; mx = std::max(mx, (double)(hi - lo) * 0.01);
+            }
+            fprintf(stderr, "[k1 times] wave start skew inside a workgroup: mean %.2f us, max %.2f us\n", skew / nw, mx);
+        }
+        std::vector<int> order((size_t)nw);
+        for (int i = 0; i < nw; i++) order[(size_t)i] = i;
+        std::sort(order.begin(), order.end(), [&](int x, int y) { return endof(x) > endof(y); });
+        for (int oi = 0; oi < nw; oi += (oi < 12 ? 1 : nw / 16 > 0 ? nw / 16 : 1)) {
+            const int i = order[(size_t)oi];
+            fprintf(stderr, "  wg %4d: start +%6.2f |", i, (double)(h[i * 16] - t0) * 0.01);
+            for (int k = 0; k < 8; k++) fprintf(stderr, " %s %5.2f", nm[k], (double)(h[i * 16 + k + 1] - h[i * 16 + k]) * 0.01);
+            fprintf(stderr, " tail %5.2f | end +%6.2f | g %2d nc %2d rays shared %d global %d band %d",
+                    h[i * 16 + 9] > h[i * 16 + 8] ? (double)(h[i * 16 + 9] - h[i * 16 + 8]) * 0.01 : 0.0,
+                    (double)(endof(i) - t0) * 0.01, (int)h[i * 16 + 14], (int)h[i * 16 + 15], (int)h[i * 16 + 11],
+                    (int)h[i * 16 + 12], (int)h[i * 16 + 13]);
+            {
+                unsigned long long sbx[8];
+                (void)hipMemcpyFromSymbol(sbx, HIP_SYMBOL(g_k1_sub), sizeof(sbx), sizeof(unsigned long long) * (size_t)i * 8);
+                fprintf(stderr, " | steps");
+                for (int k = 5; k < 8; k++) if (sbx[k]) fprintf(stderr, " [kind %d tile %d x %d, %d rays]", (int)(sbx[k] & 15), (int)((sbx[k] >> 4) & 0xfff), (int)((sbx[k] >> 16) & 0xffff), (int)(sbx[k] >> 32));
+                fprintf(stderr, "\n");
+            }
+        }
+        {   // per CU: workgroups hosted and the time the last of them ends
+            std::vector<unsigned long long> ws((size_t)nw * 16);
+            (void)hipMemcpyFromSymbol(ws.data(), HIP_SYMBOL(g_k1_wstart), sizeof(unsigned long long) * ws.size());
+            std::vector<int> cnt(16 * 256, 0); std::vector<double> cend(16 * 256, 0.0), csum(16 * 256, 0.0);
+            for (int i = 0; i < nw; i++) {
+                const int cu = (int)(((ws[i * 16 + 15] >> 16) & 15) * 256 + (ws[i * 16 + 15] & 255));
+                cnt[cu]++; cend[cu] = std::max(cend[cu], (double)(endof(i) - t0) * 0.01);
+                csum[cu] += (double)(h[i * 16 + 7] - h[i * 16 + 6]) * 0.01;
+            }
+            int ncu = 0, hist[8] = { 0 }; double emean = 0, emax = 0, emin = 1e9;
+            for (int c = 0; c < 16 * 256; c++) if (cnt[c]) { ncu++; hist[cnt[c] < 7 ? cnt[c] : 7]++; emean += cend[c]; emax = std::max(emax, cend[c]); emin = std::min(emin, cend[c]); }
+            fprintf(stderr, "[k1 times] CUs used %d; workgroups per CU: 1:%d 2:%d 3:%d 4+:%d; CU end time mean %.2f min %.2f max %.2f us\n",
+                    ncu, hist[1], hist[2], hist[3], hist[4] + hist[5] + hist[6] + hist[7], emean / std::max(ncu, 1), emin, emax);
+            // pairs sharing a CU (workgroups i and i + CUs): compute intervals and a solo estimate (half of the overlap each)
+            int same = 0;
+            for (int i = 0; i + 256 < nw; i++) if (ws[i * 16 + 15] == ws[(i + 256) * 16 + 15]) same++;
+            fprintf(stderr, "[k1 times] pairs (i, i+256) on the same CU: %d\n", same);
+            for (int i = 0; i + 256 < nw; i++) {
+                const int j = i + 256;
+                const double sa = (double)(h[i * 16 + 6] - t0) * 0.01, ea = (double)(h[i * 16 + 7] - t0) * 0.01;
+                const double sb = (double)(h[j * 16 + 6] - t0) * 0.01, eb = (double)(h[j * 16 + 7] - t0) * 0.01;
+                const double ov = std::max(0.0, std::min(ea, eb) - std::max(sa, sb));
+                fprintf(stderr, "PAIR %3d g %2d sh %3d gl %3d bd %3d comp %5.2f solo %5.2f | %3d g %2d sh %3d gl %3d bd %3d comp %5.2f solo %5.2f | end %5.2f\n",
+                        i, (int)h[i * 16 + 14], (int)h[i * 16 + 11], (int)h[i * 16 + 12], (int)h[i * 16 + 13], ea - sa, ea - sa - ov / 2,
+                        j, (int)h[j * 16 + 14], (int)h[j * 16 + 11], (int)h[j * 16 + 12], (int)h[j * 16 + 13], eb - sb, eb - sb - ov / 2,
+                        std::max((double)(endof(i) - t0), (double)(endof(j) - t0)) * 0.01);
+            }
+        }
+        {   // inside the compute phase (wave 0 of every workgroup): staging of the steps after the first, prefetch issue, gather loops
+            std::vector<unsigned long long> sb((size_t)nw * 8);
+            (void)hipMemcpyFromSymbol(sb.data(), HIP_SYMBOL(g_k1_sub), sizeof(unsigned long long) * sb.size());
+            double a0 = 0, a1 = 0, a2 = 0, a3 = 0, mhz = 0; int nm_ = 0;
+            for (int i = 0; i < nw; i++) {
+                a0 += (double)sb[i * 8] * 0.01; a1 += (double)sb[i * 8 + 1] * 0.01; a2 += (double)sb[i * 8 + 2] * 0.01; a3 += (double)sb[i * 8 + 3];
+                const double comp = (double)(h[i * 16 + 7] - h[i * 16 + 6]) * 0.01;
+                if (comp > 1.0) { mhz += (double)sb[i * 8 + 4] / (comp + (double)(h[i * 16 + 6] - h[i * 16 + 5]) * 0.01); nm_++; }
+            }
+            fprintf(stderr, "[k1 times] compute phase, mean per WG: steps %.2f | restaging %.2f us | prefetch issue %.2f us | gather loops %.2f us | shader clock ~%.0f MHz (steps incl. first staging)\n",
+                    a3 / nw, a0 / nw, a1 / nw, a2 / nw, nm_ ? mhz / nm_ : 0.0);
+            for (int oi = 0; oi < nw; oi += nw / 24 > 0 ? nw / 24 : 1) {
+                const int i = order[(size_t)oi];
+                fprintf(stderr, "  wg %4d g %2d: steps %d restaging %5.2f prefetch %5.2f loops %5.2f | rays shared %d global %d band %d\n", i, (int)h[i * 16 + 14], (int)sb[i * 8 + 3],
+                        (double)sb[i * 8] * 0.01, (double)sb[i * 8 + 1] * 0.01, (double)sb[i * 8 + 2] * 0.01, (int)h[i * 16 + 11], (int)h[i * 16 + 12], (int)h[i * 16 + 13]);
+            }
+        }
+        // per group: chunks, ray-steps per kind, mean / max compute time
+        for (int g = 0; g < n_groups; g++) {
+            double cs_ = 0, cm = 0; int n = 0; long long k4[4] = { 0, 0, 0, 0 };
+            for (int i = 0; i < nw; i++) if ((int)h[i * 16 + 14] == g) {
+                const double c = (double)(h[i * 16 + 7] - h[i * 16 + 6]) * 0.01;
+                cs_ += c; cm = std::max(cm, c); n++;
+                for (int k = 0; k < 4; k++) k4[k] += (long long)h[i * 16 + 10 + k];
+            }
+            fprintf(stderr, "  group %2d: chunks %2d | ray-steps own %lld shared %lld global %lld band %lld | compute mean %.2f max %.2f us\n",
+                    g, n, k4[0], k4[1], k4[2], k4[3], n ? cs_ / n : 0.0, cm);
+        }
+    }
+}
+#endif
+
+// K1 over `count` candidates in evaluation order (d_ev_idx maps to flat indices).  mode 0: d_pxcs already holds
+// (px,py,c,s); 1: d_ev_off holds jitters added to `pose`; 2: d_ev_off holds poses.  The packed arg-min key of the
+// launch is written to key_dst.  Asynchronous on the context's stream.
+int32_t cs_launch_distance(slamhip_cs *cs, int mode, const float pose[3], int count, bool want_dist, bool cand_sane,
+                           uint64_t *key_dst)
+{
+    slamhip_ctx *ctx = cs->ctx;
+    if (cs->n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "no scan set (slamhip_cs_set_scan)");
+    SH_TRY(cs_flush_scan(cs));
+    cs->k1_launch_no = cs->launch_count;
+    static const int force_global = (int)sh_env_int("SLAMHIP_K1_GLOBAL", 0);
+    static const int verify = (int)sh_env_int("SLAMHIP_K1_VERIFY", 0);
+    static const int tile_kb = (int)sh_env_int("SLAMHIP_K1_TILE_KB", 60);
+    static const int no_table = (int)sh_env_int("SLAMHIP_K1_NOTABLE", 0);
+    const bool sane = cs->pts_sane && cand_sane;
+    const bool tiled = sane && (cs->hs % 8 == 0) && !force_global;
+    if (cs->k1_prelaunch && !tiled) return CS_RC_NO_PRELAUNCH;      // (the fallback kernels read the scan's blocks on the host)
+#ifdef K1_TIMES
+    if (cs->k1_prelaunch) return CS_RC_NO_PRELAUNCH;               // (the developer build synchronises the stream inside this function: a prelaunched search would wait for a host that waits for it)
+#endif
+    int32_t *dist = want_dist ? cs->d_dist : nullptr;
+    unsigned long long *key = (unsigned long long *)key_dst;
+    // a ring launch: the result word is the ring's current slot (all ones now), and the launch rests the next one
+    unsigned long long *ring_slot = nullptr, *ring_reset = nullptr;
+    const bool ring = cs->k1_ring_request;
+    cs->k1_ring_request = false;
+    if (ring) {
+        if (!cs->d_k1_ring) {
+            SH_HIP(hipMalloc(&cs->d_k1_ring, sizeof(uint64_t) * K1_RING_SLOTS));
+            SH_HIP(hipMemsetAsync(cs->d_k1_ring, 0xFF, sizeof(uint64_t) * K1_RING_SLOTS, ctx->stream));
+            cs->k1_ring_pos = 0;
+        }
+        ring_slot = (unsigned long long *)cs->d_k1_ring + cs->k1_ring_pos % K1_RING_SLOTS;
+        ring_reset = (unsigned long long *)cs->d_k1_ring + (cs->k1_ring_pos + 1) % K1_RING_SLOTS;
+        key = ring_slot;
+    }
+    const float bx = pose ? pose[0] : 0.f, by = pose ? pose[1] : 0.f, bth = pose ? pose[2] : 0.f;
+    const float pose3[3] = { bx, by, bth };
+
+    if (tiled) {
+        const int group = mode == 1 && (cs->k1_group == K1_GROUP_BIG || cs->k1_group == K1_GROUP_SMALL) ? cs->k1_group : K1_GROUP;   // (explicit lists: always 1024)
+        const int n_groups = sh_div_up(count, group);
+        int budget = tile_kb * 1024;
+        if (budget > 64 * 1024) budget = 64 * 1024;                // what the staging registers hold per pass
+        const size_t lds = (size_t)K1_TILE_OFS + (size_t)budget;
+
+        k1_args a;
+        a.map = cs->d_hole; a.S = cs->hs; a.pts = cs->d_pts_sorted; a.ray_blk = cs->d_ray_blk; a.n_rays = cs->n_points;
+        a.pxcs = cs->d_pxcs; a.src3 = cs->d_ev_off; a.bx = bx; a.by = by; a.bth = bth; a.scale = cs->hscale;
+        a.count = count; a.n_groups = n_groups; a.budget = budget;
+        a.band_stage = K1_BAND_STAGE;
+        static const int noden = (int)sh_env_int("SLAMHIP_K1_NODEN", 0);
+        a.noden = noden;
+        a.nopad = k1_nopad();
+        static const int nosplit = (int)sh_env_int("SLAMHIP_K1_NOSPLIT", 0);
+        a.nosplit = nosplit;
+        a.ev_idx = cs->d_ev_idx; a.dist_out = dist; a.key_out = key; a.verify = cs->d_verify;
+        static const int no_bounds = (int)sh_env_int("SLAMHIP_K1_NOBOUNDS", 0);
+        a.grp_bounds = (mode == 1 && !no_bounds) ? cs->d_grp_bounds : nullptr;
+        a.offs_flat = cs->d_offs_flat; a.best_pose = (mode == 1 && cs->k1_want_pose) ? cs->d_best_pose : nullptr;
+        cs->k1_pose_written = a.best_pose != nullptr;
+        a.done_flag = cs->k1_done_flag; a.done_val = cs->k1_done_val;
+        cs->k1_done_armed = a.done_flag != nullptr;
+        a.sig = cs->k1_sig; a.sig_val = cs->k1_sig_val;
+        cs->k1_sig_armed = a.sig != nullptr;
+        a.ring_slot = ring_slot; a.ring_reset = ring_reset;
+        a.scan_flag = cs->k1_prelaunch ? cs->d_scan_flag : nullptr; a.scan_seq = cs->scan_flag_seq;
+        if (ring && (a.best_pose || a.done_flag || a.sig)) SH_FAIL(SLAMHIP_ERR_STATE, "a ring search delivers nothing but its key");
+
+        const bool have_spread = mode == 1 && !no_table && (int)cs->h_grp_dth.size() == n_groups;
+        if (!k1_layout_choose(cs, n_groups, budget, have_spread, bth)) { cs->k1_ring_request = ring; return CS_RC_NO_PRELAUNCH; }
+        if (!k1_layout_fits_acc(cs)) goto fallback;
+        const int n_wgs = k1_cuts_select(cs, a, group, n_groups, have_spread, budget, pose3);
+        SH_TRY(k1_acc_alloc(cs, count, a));
+        if (mode == 1) { cs->k1_last_pose[0] = bx; cs->k1_last_pose[1] = by; cs->k1_last_pose[2] = bth; cs->k1_last_valid = true; }
+        static const int no_lat = (int)sh_env_int("SLAMHIP_K1_NO_LATTICE", 0);       // (a lattice list through the ordinary kernel: same results, for comparison)
+        const bool lat2 = mode == 1 && !verify && !no_lat && cs->k1_lattice == 2 && group == K1_GROUP;
+        const bool lat4 = mode == 1 && !verify && !no_lat && cs->k1_lattice == 4 && group == K1_GROUP_BIG;
+        g_cst.lap(1);
+        SH_TRY(cs_side_join(cs));
+        SH_TRY(k1_plan_launch(cs, a, mode, group, n_wgs, lat2 || lat4));
+        g_cst.lap(2);
+        k1_search_launch(cs, a, mode, group, n_wgs, lds, verify, lat2, lat4);
+        SH_HIP(hipGetLastError());
+        if (ring) { cs->k1_ring_last = (uint64_t *)ring_slot; cs->k1_ring_pos++; }
+#ifdef K1_TIMES
+        k1_times_report(cs, n_wgs, n_groups, (int)cs->k1_tab_group.size(), group);
+#endif
+        return SLAMHIP_OK;
+    }
+
+fallback:
+    return k1_launch_fallback(cs, mode, pose3, count, sane, dist, key, ring_slot, ring_reset);
 }

@@ -187,7 +187,7 @@ extern "C" int32_t slamhip_group_create(const int32_t *devices, int32_t n, float
         ncclResult_t r_ = g->api.CommInitAll(g->comm.data(), n, devs.data());
         if (r_ != ncclSuccess) { slamhip_set_error("ncclCommInitAll failed: %s", g->api.GetErrorString(r_)); rc = SLAMHIP_ERR_RCCL; }
     }
-    if (rc == SLAMHIP_OK && (n > 1 || getenv("SLAMHIP_GROUP_THREADS"))) {
+    if (rc == SLAMHIP_OK && (n > 1 || sh_env_set("SLAMHIP_GROUP_THREADS"))) {
         g->workers = new sh_group_workers();
         g->workers->start(n, std::vector<int>(devices, devices + n));
     }
@@ -389,8 +389,7 @@ extern "C" int32_t slamhip_comm_create(slamhip_ctx *ctx, const uint8_t unique_id
         // only launches the search; every `batch` steps ONE all-reduce takes the keys of all of them (the slots of a batch are
         // consecutive), and slamhip_comm_wait flushes what is left.  Every rank issues the same steps and waits at the same
         // places (as any collective requires), so the batches agree.  SLAMHIP_COMM_BATCH=1: one collective per step.
-        const char *b = getenv("SLAMHIP_COMM_BATCH");
-        int v = b ? atoi(b) : 16;
+        int v = (int)sh_env_int("SLAMHIP_COMM_BATCH", 16);
         if (v < 1) v = 1;
         if (v > SH_COMM_BATCH_MAX) v = SH_COMM_BATCH_MAX;
         while (SH_COMM_BLOCK % v) v--;
@@ -415,7 +414,7 @@ extern "C" int32_t slamhip_comm_create(slamhip_ctx *ctx, const uint8_t unique_id
         // batch (~1 us per step at eight steps) beats the signal: the kernel's store into host-visible signal memory must
         // retire before the launch ends, +3 us per launch (measured on one rank: 25.1 us per step with the signal at one step
         // per collective, 26.3 at eight; 21.9 us without any collective).  SLAMHIP_COMM_DEP=signal keeps the signal.
-        const char *dep = getenv("SLAMHIP_COMM_DEP");
+        const char *dep = sh_env_str("SLAMHIP_COMM_DEP");
         int can = 0;
         if (rc == SLAMHIP_OK && ((dep && strcmp(dep, "signal") == 0) || (c->batch == 1 && !(dep && strcmp(dep, "event") == 0))) &&
             hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, ctx->device) == hipSuccess && can &&
@@ -603,8 +602,7 @@ static int32_t fused_allreduce_scan(slamhip_cs *cs, rccl_api &api, ncclComm_t co
     const uint32_t seq = sh_mail_seq_next(ctx);
     // (the reduced key is decoded by the HoleMap update itself where that is one launch -- every workgroup decodes, the first one
     // delivers key + pose to the mailbox: see slamhip_cs_search_and_update -- and by a launch of its own otherwise)
-    static const bool k1_delivers = getenv("SLAMHIP_FUSED_K1_DELIVERS") != nullptr;
-    const bool decode = !ctx->mail_off && ctx->timing == 0 && rc_local == SLAMHIP_OK && cs->n_points > 0 && cs_holemap_one_launch(cs) && !k1_delivers;
+    const bool decode = !ctx->mail_off && ctx->timing == 0 && rc_local == SLAMHIP_OK && cs->n_points > 0 && cs_holemap_one_launch(cs) && !cs_fused_k1_delivers();
     int32_t rc_u = SLAMHIP_OK;
     if (decode) {
         cs_k2_winner win;

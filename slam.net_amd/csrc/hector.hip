@@ -1561,25 +1561,22 @@ static int32_t run_match(slamhip_hs *hs, const float *hints, int B, float *out, 
         // a single match is a latency chain on one compute unit, bound by VALU issue: 512 lanes (two wavefronts per SIMD, three
         // scan points per lane at 1080 rays; hs_hessian_block -- rocprofv3, 1080 rays, 3 levels: 1024 lanes 33.7 us, 512 23.9,
         // 256 25.9); batches run 256 lanes per hint (many workgroups per CU)
-        static const int lanes1 = [] { const char *e = getenv("SLAMHIP_K4_LANES"); const int v = e ? atoi(e) : 0; return v == 256 || v == 1024 ? v : 512; }();
         const float *d_hints = B > 1 ? (const float *)d_in : (const float *)nullptr;
         const float3 h1 = make_float3(hints[0], hints[1], hints[2]);
         uint32_t *mb = mail1 ? ctx->mailbox : (uint32_t *)nullptr;
         if (mail1) mail_seq = sh_mail_seq_next(ctx);
-        const int lanes = B <= 8 ? lanes1 : 256;
+        const int lanes = B <= 8 ? 512 : 256;
         // (a single full match in the per-scan flow brings helper workgroups: k4_match)
-        static const int helpers_env = getenv("SLAMHIP_K4_HELPERS") ? atoi(getenv("SLAMHIP_K4_HELPERS")) : 1;
+        static const int helpers_env = (int)sh_env_int("SLAMHIP_K4_HELPERS", 1);
         const int helpers = B == 1 && only_level < 0 && hs->n_levels > 1 && hs->n_points > 0 && helpers_env > 0 ? 8 * helpers_env : 0;
         const int T = hs->match_threads;
 #define K4_LAUNCH(BD, REF) hipLaunchKernelGGL((k4_match<BD, REF>), dim3(B + helpers), dim3(BD), 0, ctx->stream, levels_arg(hs), hs->d_pts, hs->n_points, d_hints, \
                                               h1, d_out, only_level, iters, mb, mail_seq, up_src, up_dst, up_flag, up_seq, helpers ? B : 0, T)
         if (T == 0) {
-            if (lanes == 1024) K4_LAUNCH(1024, false);
-            else if (lanes == 512) K4_LAUNCH(512, false);
+            if (lanes == 512) K4_LAUNCH(512, false);
             else K4_LAUNCH(256, false);
         } else {                                                          // (the reference's order: the same bits at every width)
-            if (lanes == 1024) K4_LAUNCH(1024, true);
-            else if (lanes == 512) K4_LAUNCH(512, true);
+            if (lanes == 512) K4_LAUNCH(512, true);
             else K4_LAUNCH(256, true);
         }
 #undef K4_LAUNCH
@@ -1674,10 +1671,11 @@ static void hs_update_commit(slamhip_hs *hs)
     if (hs->k5_toggle_pending) hs->k5_sec_parity ^= 1;       // (the one-launch form wrote the other record set)
     hs->k5_toggle_pending = false;
 }
+static bool k5_two_launches() { static const bool v = sh_env_set("SLAMHIP_K5_TWO_LAUNCHES"); return v; }   // (tests: the large-scan path on ordinary scans)
 static bool hs_update_gateable(slamhip_hs *hs)
 {
-    static const bool two_launch = getenv("SLAMHIP_K5_TWO_LAUNCHES") != nullptr, off = getenv("SLAMHIP_HS_NO_GATED_UPDATE") != nullptr;
-    return !off && !two_launch && hs->n_points > 0 && hs->n_points <= K5_LDS_LINES && hs->ctx->timing == 0 && !hs->ctx->mail_off;
+    static const bool off = sh_env_set("SLAMHIP_HS_NO_GATED_UPDATE");
+    return !off && !k5_two_launches() && hs->n_points > 0 && hs->n_points <= K5_LDS_LINES && hs->ctx->timing == 0 && !hs->ctx->mail_off;
 }
 static int32_t hs_update_enqueue(slamhip_hs *hs, const float pose[3], const k5_gate *gate_in = nullptr)
 {
@@ -1719,16 +1717,14 @@ static int32_t hs_update_enqueue(slamhip_hs *hs, const float pose[3], const k5_g
             // scan touches, which halve from level to level (the zone around the begin cell is the same on every level: a floor
             // of 1/16 each).  (Round 2 shared them out by cell count with a floor of 1/8: 551 workgroups, i.e. a second round that
             // started when the first drained -- half of the kernel's 35 us.)
-            // (every level needs a workgroup on each of the eight XCD sectors its lines are dealt to: below 8 workgroups per level
-            // -- 8 levels x 16 as the floor is a sixteenth -- lines of the missing sectors would not be drawn; the override is clamped)
-            static const int wgs_raw = getenv("SLAMHIP_K5_WGS") ? atoi(getenv("SLAMHIP_K5_WGS")) : 512;
-            static const int wgs_env = wgs_raw < 128 ? 128 : wgs_raw;
+            // (every level needs a workgroup on each of the eight XCD sectors its lines are dealt to: at least 8 per level)
+            constexpr int wgs = 512;
             double tot = 0.0;
             for (int l = 0; l < hs->n_levels; l++) tot += (double)hs->lv[l].w + (double)hs->lv[l].h;
-            int first = 0, left = wgs_env;
+            int first = 0, left = wgs;
             for (int l = 0; l < hs->n_levels; l++) {
-                const int floor_k = wgs_env / 16 > 0 ? wgs_env / 16 : 1;
-                int k = (int)((double)wgs_env * ((double)hs->lv[l].w + (double)hs->lv[l].h) / tot);
+                const int floor_k = wgs / 16;
+                int k = (int)((double)wgs * ((double)hs->lv[l].w + (double)hs->lv[l].h) / tot);
                 if (k < floor_k) k = floor_k;
                 const int must_leave = (hs->n_levels - 1 - l) * floor_k;   // (the levels still to come keep their floor)
                 if (k > left - must_leave) k = left - must_leave > 1 ? left - must_leave : 1;
@@ -1739,14 +1735,13 @@ static int32_t hs_update_enqueue(slamhip_hs *hs, const float pose[3], const k5_g
             cgrid_x = first;
         }
         const dim3 cgrid(cgrid_x);
-        static const bool two_launch = getenv("SLAMHIP_K5_TWO_LAUNCHES") != nullptr;       // (tests: the large-scan path on ordinary scans)
-        const bool build = n <= K5_LDS_LINES && !two_launch;
+        const bool build = n <= K5_LDS_LINES && !k5_two_launches();
         static std::atomic<unsigned long long> attr_set{0};                                             // one bit per device (the attribute is the device's)
         if (!((attr_set.load(std::memory_order_acquire) >> (ctx->device & 63)) & 1ull)) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k5_cells<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)k5_lds_bytes(true, K5_LDS_LINES)); attr_set.fetch_or(1ull << (ctx->device & 63), std::memory_order_release); }
         if (!build)      // all levels in every launch (MapRepMultiMap.cs:76)
             hipLaunchKernelGGL(k5_prepare, dim3(hs->n_levels), dim3(1024), 0, ctx->stream, A, (const float2 *)hs->d_pts, n, hs->origin[0],
                                hs->origin[1], hs->cap_lines, (k5_line *)hs->d_k5_byidx, (k5_line *)hs->d_k5_cand, hs->d_k5_start, hs->d_k5_hdr);
-        static const bool no_sectors = getenv("SLAMHIP_K5_EQUAL_SECTORS") != nullptr;       // (tuning: the sectors of phase 2 by count, as scans too large for the LDS tables have them)
+        static const bool no_sectors = sh_env_set("SLAMHIP_K5_EQUAL_SECTORS");       // (tuning: the sectors of phase 2 by count, as scans too large for the LDS tables have them)
         hs->k5_toggle_pending = build;
         k5_gate gate;
         memset(&gate, 0, sizeof(gate));
@@ -1874,7 +1869,7 @@ extern "C" int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int
 {
     SH_CHECK_ARG(p && hint);
     SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
-    static const bool wait_update = getenv("SLAMHIP_HS_WAIT_UPDATE") != nullptr;
+    static const bool wait_update = sh_env_set("SLAMHIP_HS_WAIT_UPDATE");
     // (worth it when the update does take place: a gated launch that returns at once still costs the stream ~15 us -- 512 workgroups
     // of 1024 lanes are dispatched to find that out -- so the flow is taken while the last two scans both updated the map: measured,
     // every scan updating 70 -> 66 us per scan; one scan in five, where it is never taken, 55 either way, 71 if it always were)

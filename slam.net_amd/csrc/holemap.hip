@@ -1474,9 +1474,11 @@ void cs_holemap_free(slamhip_cs *cs)
 
 // with_obstacle: the ObstacleMap update of this scan rides on the launch (obstacle_dev.h); scans too large for the in-kernel
 // tables take k2_prepare + the pixel kernel, and their ObstacleMap update its own launches
+// SLAMHIP_K2_NCORE: core workgroups per XCD in the pixel kernel (0: no arcs)
+static int k2_ncore() { static const int v = (int)sh_env_int("SLAMHIP_K2_NCORE", 1); return v; }
 bool cs_holemap_one_launch(const slamhip_cs *cs)
 {
-    static const bool two_launch = getenv("SLAMHIP_K2_TWO_LAUNCHES") != nullptr;          // (tests: the large-scan path on ordinary scans)
+    static const bool two_launch = sh_env_set("SLAMHIP_K2_TWO_LAUNCHES");          // (tests: the large-scan path on ordinary scans)
     return cs->n_points > 0 && cs->n_points <= K2_LDS_RAYS && !two_launch;
 }
 
@@ -1512,10 +1514,10 @@ int32_t cs_launch_holemap_update(slamhip_cs *cs, const float *d_pose, float4 h_p
         sc.win_key = (const unsigned long long *)win->d_key; sc.win_offs = win->d_offs_flat; sc.win_n_offs = win->n_offs; sc.win_bx = win->bx; sc.win_by = win->by; sc.win_bth = win->bth;
         sc.win_pose_out = const_cast<float *>(d_pose); sc.win_mail = win->mail; sc.win_seq = win->seq;
     }
-    static const int rb_env = getenv("SLAMHIP_K2_RB") ? atoi(getenv("SLAMHIP_K2_RB")) : 12, ncore_env = getenv("SLAMHIP_K2_NCORE") ? atoi(getenv("SLAMHIP_K2_NCORE")) : 1;
+    static const int rb_env = (int)sh_env_int("SLAMHIP_K2_RB", 12);
     sc.rb_num = rb_env < 1 ? 1 : rb_env;                           // (radius, per 1080 rays, from which a zone pixel is one lane's)
     sc.ncore = 0;                                                  // (set below, once the grid is known)
-    static const int zone_env = getenv("SLAMHIP_K2_ZONE") ? atoi(getenv("SLAMHIP_K2_ZONE")) : 0;
+    static const int zone_env = (int)sh_env_int("SLAMHIP_K2_ZONE", 0);
     sc.zone = zone_env >= 1 ? zone_env : 0;                        // (developer override of the zone's radius; 0: by the ray count)
     {
         sh_timer t(ctx, SLAMHIP_K_CS_HOLEMAP);
@@ -1525,7 +1527,7 @@ int32_t cs_launch_holemap_update(slamhip_cs *cs, const float *d_pose, float4 h_p
                                cs->d_k2_start, cs->d_k2_counters, (int *)cs->d_key + 6, cs->d_hole_dirty);
         // One round of resident workgroups, one per CU (a second round would start when the first drains; with the tables in LDS
         // one workgroup per CU measured best).
-        static const int grid_env = getenv("SLAMHIP_K2_GRID") ? atoi(getenv("SLAMHIP_K2_GRID")) : 0;
+        static const int grid_env = (int)sh_env_int("SLAMHIP_K2_GRID", 0);
         const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
         // (two workgroups per CU -- the 1080-ray tables are 80.7 KB with the 16-bit bucket table, and amdgpu_waves_per_eu(8, 8) brings
         // the kernel under 80 SGPRs -- measured no faster: 23.5 against 23.2 us with one, and the register limit costs the
@@ -1539,7 +1541,7 @@ int32_t cs_launch_holemap_update(slamhip_cs *cs, const float *d_pose, float4 h_p
         {
             const float hw_px = hole_width * cs->hscale * 0.5f;
             const bool hw_ok = hw_px >= 0.0f && hw_px < 8000.0f;
-            const int nc = ncore_env <= 0 ? 0 : 1;                       // (one core workgroup per XCD: it draws its octant's central pixels by counting; SLAMHIP_K2_NCORE=0: no arcs)
+            const int nc = k2_ncore() <= 0 ? 0 : 1;                       // (one core workgroup per XCD: it draws its octant's central pixels by counting; SLAMHIP_K2_NCORE=0: no arcs)
             if (build && nc > 0 && !sc.span && hw_ok && cs->hs <= 16384 && grid % 8 == 0 && grid / 8 >= nc + 1) sc.ncore = nc;
         }
 #define K2_PIXELS(B, T, A) {                                                                                                \
@@ -1586,7 +1588,7 @@ int32_t cs_launch_holemap_update(slamhip_cs *cs, const float *d_pose, float4 h_p
                 std::vector<unsigned long long> f(512 * 8);
                 (void)hipMemcpyFromSymbol(f.data(), HIP_SYMBOL(g_k2_fine), sizeof(unsigned long long) * f.size());
                 for (int role = 0; role < 2; role++) {
-                    static const int nce = getenv("SLAMHIP_K2_NCORE") ? atoi(getenv("SLAMHIP_K2_NCORE")) : 1;
+                    const int nce = k2_ncore();
                     double a[6] = { 0 }; int c = 0;
                     for (int i = 0; i < 512; i++) if (h[i * 8] && h[i * 8 + 5] >= h[i * 8] && h[i * 8 + 6] && f[i * 8] && ((i < 8 * nce) == (role == 0))) {
                         a[0] += (double)(f[i * 8] - h[i * 8 + 6]) * 0.01; a[1] += (double)(f[i * 8 + 1] - f[i * 8]) * 0.01; a[2] += (double)(f[i * 8 + 2] - f[i * 8 + 1]) * 0.01;
@@ -1597,7 +1599,7 @@ int32_t cs_launch_holemap_update(slamhip_cs *cs, const float *d_pose, float4 h_p
                 }
             }
             for (int role = 0; role < 2; role++) {       // core workgroups (the first `ncore` of every XCD: blocks 0 .. 8 * ncore - 1) and sector workgroups apart
-                static const int ncore_env = getenv("SLAMHIP_K2_NCORE") ? atoi(getenv("SLAMHIP_K2_NCORE")) : 1;
+                const int ncore_env = k2_ncore();
                 double a[8] = { 0 }, e5 = 0, m5 = 0; int c = 0;
                 for (int i = 0; i < 512; i++) if (h[i * 8] && h[i * 8 + 5] >= h[i * 8] && h[i * 8 + 6] && ((i < 8 * ncore_env) == (role == 0))) {
                     a[0] += (double)(h[i * 8 + 6] - h[i * 8]) * 0.01; a[1] += (double)(h[i * 8 + 7] - h[i * 8 + 6]) * 0.01; a[2] += (double)(h[i * 8 + 1] - h[i * 8 + 7]) * 0.01;

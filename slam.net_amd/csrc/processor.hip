@@ -14,7 +14,7 @@
 struct proc_times {
     bool on; double acc[6], cur[6]; int n;
     std::chrono::steady_clock::time_point t;
-    proc_times() : on(getenv("SLAMHIP_PROC_TIMES") != nullptr), n(0) { for (double &a : acc) a = 0; for (double &a : cur) a = 0; }
+    proc_times() : on(sh_env_set("SLAMHIP_PROC_TIMES")), n(0) { for (double &a : acc) a = 0; for (double &a : cur) a = 0; }
     void start() { if (on) t = std::chrono::steady_clock::now(); }
     void lap(int k) { if (!on) return; auto u = std::chrono::steady_clock::now(); const double d = std::chrono::duration<double, std::micro>(u - t).count(); acc[k] += d; cur[k] += d; t = u; }
     void done()

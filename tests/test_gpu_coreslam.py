@@ -535,11 +535,11 @@ def test_k1_tile_boxes_selfcheck():
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     sel = "test_distance_golden or test_distance_quirks or test_distance_64bit or test_search_full_size or test_search_changing_scans or test_search_enqueue_ring or test_heading_lattice or test_search_plan_launches"
-    for env_extra in ({"SLAMHIP_K1_VERIFY": "1", "SLAMHIP_K1_CPL": "1"}, {"SLAMHIP_K1_VERIFY": "1", "SLAMHIP_K1_CPL": "2"},
+    for env_extra in ({"SLAMHIP_K1_VERIFY": "1"},
                       {"SLAMHIP_K1_LAYOUT_SYNC": "1", "SLAMHIP_K1_VERIFY": "1"},   # every scan's launch layout made before its launch
-                      {"SLAMHIP_K1_VERIFY": "1", "SLAMHIP_K1_CPL": "4"}, {"SLAMHIP_K1_GLOBAL": "1"},
+                      {"SLAMHIP_K1_GLOBAL": "1"},
                       {"SLAMHIP_K1_TILE_KB": "8", "SLAMHIP_K1_VERIFY": "1"},       # banded tiles and global gathers
-                      {"SLAMHIP_K1_TILE_KB": "24", "SLAMHIP_K1_CPL": "1"}, {"SLAMHIP_K1_TILE_KB": "1"},
+                      {"SLAMHIP_K1_TILE_KB": "24"}, {"SLAMHIP_K1_TILE_KB": "1"},
                       {"SLAMHIP_K1_NOTABLE": "1"},                                 # uniform chunk-major layout
                       {"SLAMHIP_K1_NODEN": "1", "SLAMHIP_K1_VERIFY": "1"},         # tile addresses from the integer coordinates everywhere
                       {"SLAMHIP_K1_GROUP": "2048", "SLAMHIP_K1_VERIFY": "1"},      # groups of 2048 candidates (512 lanes x 4), as large searches use
@@ -560,7 +560,7 @@ def test_k1_tile_boxes_selfcheck():
                       {"SLAMHIP_K1_PLAN_ALWAYS": "1", "SLAMHIP_K1_VERIFY": "1"},   # a plan launch beside EVERY search: most arrive while their search runs
                       {"SLAMHIP_K1_PLAN_ALWAYS": "1", "SLAMHIP_K1_TILE_KB": "16"},  # ... with many banded pieces (records of many steps, some too long for a record)
                       {"SLAMHIP_K1_TARGET_WGS": "64", "SLAMHIP_K1_TARGET_WGS_UNIFORM": "64"},
-                      {"SLAMHIP_K1_TARGET_WGS": "100000", "SLAMHIP_K1_TARGET_WGS_UNIFORM": "100000", "SLAMHIP_K1_CPL": "1"}):
+                      {"SLAMHIP_K1_TARGET_WGS": "100000", "SLAMHIP_K1_TARGET_WGS_UNIFORM": "100000"}):
         env = dict(os.environ); env.update(env_extra); env["SLAMHIP_EXPECT_SELFCHECK"] = "1"
         r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_gpu_coreslam.py"), "-m", "gpu", "-x", "-q",
                             "-k", sel], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
