@@ -59,6 +59,15 @@ namespace HectorSLAM.Main
             }
         }
 
+        /// <summary>Match through the reference's probability cache (MapRep.ReferenceCache; slamhip_hs_set_reference_cache): with
+        /// ReferenceSummation, Update then gives the reference's poses also across Reset, where its cache serves pre-reset
+        /// probabilities (OccGridMap.cs:97-107,248).  false (default): the current probabilities (deviation D5).</summary>
+        public bool ReferenceCache
+        {
+            get => MapRep.ReferenceCache;
+            set => MapRep.ReferenceCache = value;
+        }
+
         public HectorSLAMProcessor(float mapResolution, Point mapSize, Vector3 startPose, int numDepth, int numThreads, ILogger logger = null)
             : this(mapResolution, mapSize, startPose, numDepth, numThreads, logger, null)
         {

@@ -63,6 +63,22 @@ namespace HectorSLAM.Main
             Native.Check(Native.slamhip_hs_set_iterations(Pyramid.Ptr, it));
         }
 
+        private bool referenceCache;
+
+        /// <summary>Serve probabilities through OccGridMap's own cache (OccGridMap.cs:16,97-107; slamhip_hs_set_reference_cache):
+        /// the matcher and GetCachedProbability then read what the reference reads, including the pre-reset values its cache
+        /// keeps across Reset (:248).  Every switch to true starts from a new OccGridMap's cache.  false (default): the current
+        /// probability of every cell (deviation D5).</summary>
+        public bool ReferenceCache
+        {
+            get => referenceCache;
+            set
+            {
+                Native.Check(Native.slamhip_hs_set_reference_cache(Pyramid.Ptr, value ? 1 : 0));
+                referenceCache = value;
+            }
+        }
+
         public void Reset()                                              // MapRepMultiMap.cs:63-66
         {
             Native.Check(Native.slamhip_hs_reset(Pyramid.Ptr));

@@ -82,6 +82,7 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_match_batch(IntPtr hs, Vector3* hints, int count, Vector3* poses);
         // ScanMatcher(numThreads)'s summation order (ScanMatcher.cs:149-195): 0 the device's own, 1..64 the reference's chunks, bit for bit
         [DllImport(Lib)] internal static extern int slamhip_hs_set_match_threads(IntPtr hs, int numThreads);
+        [DllImport(Lib)] internal static extern int slamhip_hs_set_reference_cache(IntPtr hs, int on);
         [DllImport(Lib)] internal static extern int slamhip_hs_update_by_scan(IntPtr hs, in Vector3 robotPoseWorld);
         // HectorSLAM, processor level (HectorSLAMProcessor.cs:66-138): the Update state machine in the library -- match, the gate of :107-109 evaluated
         // on the device, the grid update enqueued behind the match before the pose is back (one blocking wait per scan instead of two)

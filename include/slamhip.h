@@ -379,13 +379,14 @@ int32_t slamhip_scan_segments_to_cloud(const float *seg_poses, const int32_t *se
 int32_t slamhip_hs_create(slamhip_ctx *ctx, float cell_length, int32_t width, int32_t height, int32_t levels,
                           slamhip_hs **out);
 int32_t slamhip_hs_destroy(slamhip_hs *hs);
-int32_t slamhip_hs_reset(slamhip_hs *hs);                                   /* MapRepMultiMap.Reset :63-66; also resets the probabilities (deviation D5, slamhip_hs_probability) */
+int32_t slamhip_hs_reset(slamhip_hs *hs);                                   /* MapRepMultiMap.Reset :63-66; also resets the probabilities and sets the cache epoch to 0 (deviation D5: slamhip_hs_probability, slamhip_hs_set_reference_cache) */
 int32_t slamhip_hs_level_info(slamhip_hs *hs, int32_t level, int32_t *width, int32_t *height, float *cell_length);
 /* SetUpdateFactorFree / SetUpdateFactorOccupied (:83-95; OccGridMap.cs:58-79) */
 int32_t slamhip_hs_set_factors(slamhip_hs *hs, float update_free_factor, float update_occupied_factor);
 /* OccGridMap.EstimateIterations per level (OccGridMap.cs:53; default 3) */
 int32_t slamhip_hs_set_iterations(slamhip_hs *hs, const int32_t *iterations_per_level);
-/* mapArray of one level (GridMap.cs:13): n_cells = width*height LogOddsCell structs */
+/* mapArray of one level (GridMap.cs:13): n_cells = width*height LogOddsCell structs.  An upload leaves the reference's cache
+ * and its epoch as they are (slamhip_hs_set_reference_cache): the reference has no upload, and only its own events move them. */
 int32_t slamhip_hs_cells_upload(slamhip_hs *hs, int32_t level, const slamhip_cell *cells, size_t n_cells);
 int32_t slamhip_hs_cells_download(slamhip_hs *hs, int32_t level, slamhip_cell *cells, size_t n_cells);
 /* GridMap.GetBitmapData (GridMap.cs:104-115) computed on the device */
@@ -396,11 +397,13 @@ int32_t slamhip_hs_map_extends(slamhip_hs *hs, int32_t level, int32_t extends[4]
 /* Replica check, as slamhip_cs_maps_checksum: out[0] over the level's log-odds (OccGridCell.Value, OccGridCell.cs, as its
  * binary32 bit pattern), out[1] over its update indices (OccGridCell.UpdateIndex as uint32) */
 int32_t slamhip_hs_checksum(slamhip_hs *hs, int32_t level, uint64_t out[2]);
-/* OccGridMap.GetCachedProbability (OccGridMap.cs:97-107) for a list of cell indices: exp(v)/(exp(v)+1) of each cell's
- * CURRENT value.  Deviation D5: the reference's cache is not invalidated by Reset (OccGridMap.cs:244-252 resets
- * currCacheIndex but not cacheArray[i].Index, which only the constructor sets to -1, :38-42), so a cell cached in epoch e
- * before a Reset is served its pre-reset probability in epoch e after it; here -- and in the matcher, which reads the same
- * grid -- a probability never outlives the value it was computed from. */
+/* OccGridMap.GetCachedProbability (OccGridMap.cs:97-107) for a list of cell indices.  Deviation D5 -- default: the current
+ * probability; opt-in: the reference's cache.  The reference's cache is not invalidated by Reset (OccGridMap.cs:244-252
+ * resets currCacheIndex but not cacheArray[i].Index, which only the constructor sets to -1, :38-42), so a cell cached in
+ * epoch e before a Reset is served its pre-reset probability in epoch e after it.  By default this -- and the matcher,
+ * which reads the same grid -- returns exp(v)/(exp(v)+1) of each cell's CURRENT value: a probability never outlives the
+ * value it was computed from.  With the reference's cache on (slamhip_hs_set_reference_cache) it answers as that cache does and
+ * fills it as the reference's calls do (repeated indices in one list: as the same calls one after another). */
 int32_t slamhip_hs_probability(slamhip_hs *hs, int32_t level, const int32_t *indices, int32_t n, float *out);
 
 /* The ScanCloud handed to MatchData / UpdateByScan: points + scan.Pose.xy (ScanCloud.cs:15-20) */
@@ -424,6 +427,18 @@ int32_t slamhip_hs_hessian(slamhip_hs *hs, int32_t level, const float pose_map[3
  * dTr are the reference's binary32 sums bit for bit, and a batch of any size returns the single match's bits.
  * Any other value: SLAMHIP_ERR_INVALID, the setting unchanged. */
 int32_t slamhip_hs_set_match_threads(slamhip_hs *hs, int32_t num_threads);
+/* The reference's probability cache (deviation D5; OccGridMap.cs:16-19,38-42,97-107,147,248): on = 1 keeps cacheArray
+ * {Value, Index} per cell and level on the device, and every reader of a probability goes through it as
+ * GetCachedProbability does (:99-106) -- slamhip_hs_match, _match_level, _match_batch, _hessian, slamhip_hs_probability
+ * and slamhip_hsproc_update on the processor's own hs.  A cell cached in epoch e before a slamhip_hs_reset is then served
+ * its pre-reset probability in epoch e after it, as the reference serves it.  on = 0 (default): the current probability.
+ * The epoch (currCacheIndex) is kept in either mode: every grid update that takes place adds 1, slamhip_hs_reset sets 0.
+ * Every switch from off to on sets every entry to Index = -1, the state of a new OccGridMap: fills while the mode was
+ * off were never recorded.  The first switch to on allocates 8 bytes per cell and level (42 MiB at 2048^2 x 3 levels);
+ * if that fails the call returns SLAMHIP_ERR_NOMEM and the setting is unchanged.  A host-side setting of this hs like
+ * slamhip_hs_set_match_threads; it survives slamhip_hs_reset.  Any other value: SLAMHIP_ERR_INVALID, the setting
+ * unchanged. */
+int32_t slamhip_hs_set_reference_cache(slamhip_hs *hs, int32_t on);
 
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */

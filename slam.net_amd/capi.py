@@ -138,6 +138,7 @@ def _declare(L):
         "slamhip_hs_match_batch": (i32, [vp, fp, i32, fp]),
         "slamhip_hs_hessian": (i32, [vp, i32, fp, fp, fp]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
+        "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
         "slamhip_hsproc_create": (i32, [vp, f, i32, i32, fp, i32, vpp]),
         "slamhip_hsproc_destroy": (i32, [vp]),

@@ -8,9 +8,11 @@
 // lanes with the scan's points in LDS, one barrier and one sine / cosine per iteration (hs_hessian_block: round 5).
 // Occupancy probabilities exp(v)/(exp(v)+1) (OccGridMap.GetCachedProbability, OccGridMap.cs:97-107) are READ from a dense
 // per-level grid `prob` that every writer of the log-odds grid keeps current (K5 for the cells it touches, upload and
-// reset for all of them) -- the device's form of the reference's per-cell cache, without its epochs: the value always is
-// the current cell's probability, also across Reset, where the reference's cache can serve pre-reset values (deviation
-// D5: DESIGN.md sec.3 and include/slamhip.h, slamhip_hs_probability).
+// reset for all of them) -- by default the device's form of the reference's per-cell cache, without its epochs: the value
+// always is the current cell's probability, also across Reset, where the reference's cache can serve pre-reset values
+// (deviation D5: DESIGN.md sec.3 and include/slamhip.h, slamhip_hs_probability).  Opt-in (slamhip_hs_set_reference_cache):
+// the reference's cache itself, CachedMapElement {Value, Index} per cell and a per-level epoch (hs_cache_taps), so that
+// the matcher and slamhip_hs_probability serve what the reference serves, stale entries included.
 // Float parity target: pose within 1e-4 m / 1e-4 rad (H6).
 //
 // K5 replaces OccGridMap.UpdateByScan and friends (HectorSLAM/Map/OccGridMap.cs:114-239) for every level of
@@ -39,7 +41,10 @@ struct hs_level {
     slamhip_cell *d_cells;                 // mapArray (GridMap.cs:13) in the reference's own layout, LogOddsCell {UpdateIndex, Value} (LogOddsCell.cs:16-21): the grid
                                            // update reads and writes a cell with ONE 8-byte access (two arrays: 30.8 -> 26.9 us per update with the second one left out)
     float *d_prob;                         // GetCachedProbability of every cell (OccGridMap.cs:97-107), kept current by every writer of d_cells
+    unsigned long long *d_cache;           // cacheArray (OccGridMap.cs:16), one CachedMapElement {Value, Index} per cell as ONE 8-byte word
+                                           // (Value's bits low, Index high); allocated when the reference's cache is first turned on
     int curr_update_index;                 // OccGridMap.cs:20
+    int curr_cache_index;                  // OccGridMap.cs:19, kept in every mode: UpdateByScan +1 (:147), Reset 0 (:248)
     int iterations;                        // EstimateIterations (OccGridMap.cs:53)
 };
 
@@ -70,6 +75,7 @@ struct slamhip_hs {
     void *d_k5_byidx, *d_k5_cand; int *d_k5_start, *d_k5_hdr; int cap_lines;
     int *d_k5_sec; int k5_sec_parity; bool k5_toggle_pending;                        // [2][HS_MAX_LEVELS][K5_SEC] sector records of the cell kernel: an update reads the set the last one wrote
     int match_threads;                                     // slamhip_hs_set_match_threads: 0 the device's summation order, 1 .. HS_REF_MAX_T the reference's
+    int ref_cache;                                         // slamhip_hs_set_reference_cache: 1 every probability reader goes through d_cache
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -183,9 +189,51 @@ __device__ static __forceinline__ hs_iter_xf hs_iter_transform(const hs_level_de
     return X;
 }
 
-// one scan point i (i >= n: a padding lane, its terms are zero): the point and its four taps, requested without waiting
+// ---- the reference's probability cache (slamhip_hs_set_reference_cache, opt-in) ------------------------------------------------
+// OccGridMap.GetCachedProbability (:97-107) literally: cacheArray[i] = CachedMapElement {Value, Index} (OccGridMap.cs:16), epoch
+// currCacheIndex.  A tap loads the entry; Index == epoch: Value (:106); else the current value's probability -- prob[i], which
+// every writer of the cells keeps current -- is stored as {prob[i], epoch} (:101-103) and used.  Race-free without ordering:
+// an entry a lane can observe is either its state before the launch or a fill {current probability, epoch}, and both give
+// the reference's answer; a stale entry (Index == epoch before the launch) is never written.  So the order of fills inside
+// an epoch does not matter, across workgroups, XCDs and batch entries alike.  What would break it is a read that joins one
+// fill's Value to another's Index: the entry is ONE 8-byte word, loaded and stored whole (relaxed, global_load/store_dwordx2).
+// (Workgroup scope: no lane needs another workgroup's fill to be visible -- an unseen fill only means the lane fills
+// again, with the same value -- and the plain loads keep the taps in the L2.)
+struct hs_cache_lv { unsigned long long *c; int epoch; };                 // one level's cacheArray and currCacheIndex
+struct hs_cache_arg { unsigned long long *c[HS_MAX_LEVELS]; int epoch[HS_MAX_LEVELS]; };
+__device__ static __forceinline__ float hs_cache_entry_value(unsigned long long e) { return __uint_as_float((unsigned)e); }
+__device__ static __forceinline__ bool hs_cache_entry_hit(unsigned long long e, int epoch) { return (int)(e >> 32) == epoch; }   // :99
+__device__ static __forceinline__ unsigned long long hs_cache_entry(float v, int epoch)
+{
+    return ((unsigned long long)(unsigned)epoch << 32) | (unsigned long long)__float_as_uint(v);
+}
+// the four taps of an in-range point at cell idx (:230-233) through the cache.  A point outside the map, a NaN point or a
+// padding lane (ok false) reads and fills nothing: the reference returns before its first tap (:216-219).
+__device__ static __forceinline__ void hs_cache_taps(const hs_cache_lv &C, const float *prob, int idx, int w, bool ok, float2 &r0, float2 &r1)
+{
+    float v[4] = { 0.f, 0.f, 0.f, 0.f };
+    if (ok) {
+        const int at[4] = { idx, idx + 1, idx + w, idx + w + 1 };
+        unsigned long long e[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) e[k] = __hip_atomic_load(C.c + at[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        bool miss[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) { miss[k] = !hs_cache_entry_hit(e[k], C.epoch); v[k] = hs_cache_entry_value(e[k]); }
+#pragma unroll
+        for (int k = 0; k < 4; k++) if (miss[k]) v[k] = prob[at[k]];      // :101-102
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (miss[k]) __hip_atomic_store(C.c + at[k], hs_cache_entry(v[k], C.epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // :103
+    }
+    r0 = make_float2(v[0], v[1]); r1 = make_float2(v[2], v[3]);
+}
+
+// one scan point i (i >= n: a padding lane, its terms are zero): the point and its four taps, requested without waiting.
+// RC: the taps through the reference's cache (hs_cache_taps)
 struct hs_point { float2 p, r0, r1; float fx, fy; bool ok; };
-__device__ static __forceinline__ void hs_point_taps(const hs_level_dev &L, const float2 *pts, int i, int n, const hs_iter_xf &X, hs_point &q)
+template <bool RC>
+__device__ static __forceinline__ void hs_point_taps(const hs_level_dev &L, const hs_cache_lv &C, const float2 *pts, int i, int n, const hs_iter_xf &X, hs_point &q)
 {
     q.p = i < n ? pts[i] : make_float2(0.f, 0.f);
     float cx, cy;
@@ -197,8 +245,11 @@ __device__ static __forceinline__ void hs_point_taps(const hs_level_dev &L, cons
     q.fx = cx - fxx; q.fy = cy - fyy;                                      // :225
     const int idx = iy * L.w + ix;                                         // :227
 #if HS_PROB_MODE == 0
-    __builtin_memcpy(&q.r0, L.prob + idx, sizeof(float2));                 // (two adjacent taps: one 8-byte load)
-    __builtin_memcpy(&q.r1, L.prob + idx + L.w, sizeof(float2));
+    if constexpr (RC) hs_cache_taps(C, L.prob, idx, L.w, q.ok, q.r0, q.r1);
+    else {
+        __builtin_memcpy(&q.r0, L.prob + idx, sizeof(float2));             // (two adjacent taps: one 8-byte load)
+        __builtin_memcpy(&q.r1, L.prob + idx + L.w, sizeof(float2));
+    }
 #else
     int4 c0, c1;                                                           // (two adjacent cells {UpdateIndex, Value}: one 16-byte load)
     __builtin_memcpy(&c0, L.cells + idx, sizeof(int4));
@@ -225,8 +276,9 @@ __device__ static __forceinline__ void hs_point_terms(const hs_point &q, const h
     tm[6] = gx * gy;   tm[7] = gx * rot;  tm[8] = gy * rot;                // :178-180
 }
 
-template <int BDIM, bool LDSP>
-__device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, const float2 *pts, int n, const float pose[3],
+// RC: the taps through the reference's cache (hs_cache_taps)
+template <int BDIM, bool LDSP, bool RC>
+__device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, const hs_cache_lv &C, const float2 *pts, int n, const float pose[3],
                                                         double *red /* [hs_shape::RED]: this iteration's block */, float sums[9])
 {
     constexpr int NW = hs_shape<BDIM>::NW, PU = hs_shape<BDIM>::PU;
@@ -257,8 +309,11 @@ __device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, c
             fx[u] = cx - fxx; fy[u] = cy - fyy;                            // :225
             const int idx = iy * L.w + ix;                                 // :227
 #if HS_PROB_MODE == 0
-            __builtin_memcpy(&r0[u], L.prob + idx, sizeof(float2));        // (two adjacent taps: one 8-byte load)
-            __builtin_memcpy(&r1[u], L.prob + idx + L.w, sizeof(float2));
+            if constexpr (RC) hs_cache_taps(C, L.prob, idx, L.w, ok[u], r0[u], r1[u]);
+            else {
+                __builtin_memcpy(&r0[u], L.prob + idx, sizeof(float2));    // (two adjacent taps: one 8-byte load)
+                __builtin_memcpy(&r1[u], L.prob + idx + L.w, sizeof(float2));
+            }
 #else
             int4 c0, c1;                                                   // (two adjacent cells {UpdateIndex, Value}: one 16-byte load)
             __builtin_memcpy(&c0, L.cells + idx, sizeof(int4));
@@ -395,8 +450,8 @@ __device__ static __forceinline__ float hs_chain(const float *row, int lo, int h
 
 // sums[9] in the order of hs_hessian_block, uniform in every thread; T in 1 .. HS_REF_MAX_T.  Barriers: one per window after the
 // terms are stored (and one before the store of every window after the first), two for the totals.
-template <int BDIM>
-__device__ static __forceinline__ void hs_hessian_ref(const hs_level_dev &L, const float2 *pts, int n, const float pose[3], int T,
+template <int BDIM, bool RC>
+__device__ static __forceinline__ void hs_hessian_ref(const hs_level_dev &L, const hs_cache_lv &C, const float2 *pts, int n, const float pose[3], int T,
                                                       hs_ref_lds<BDIM> &S, float sums[9])
 {
     constexpr int PU = hs_shape<BDIM>::PU, W = hs_ref_shape<BDIM>::W, WS = hs_ref_shape<BDIM>::WS, CR = hs_ref_shape<BDIM>::CR;
@@ -409,7 +464,7 @@ __device__ static __forceinline__ void hs_hessian_ref(const hs_level_dev &L, con
     for (int base = 0; base < n; base += W) {
         hs_point q[PU];
 #pragma unroll
-        for (int u = 0; u < PU; u++) hs_point_taps(L, pts, base + tid + u * BDIM, n, X, q[u]);
+        for (int u = 0; u < PU; u++) hs_point_taps<RC>(L, C, pts, base + tid + u * BDIM, n, X, q[u]);
         float tm[PU][9];
 #pragma unroll
         for (int u = 0; u < PU; u++) hs_point_terms(q[u], X, tm[u]);
@@ -466,11 +521,14 @@ __device__ static inline void hs_step(const float sums[9], float est[3])
 // MatchData(MapRepMultiMap) (:41-54): one workgroup per hint; levels coarse -> fine.
 // only_level >= 0 restricts to one level with `iters_override` iterations (MatchData(OccGridMap), :64-84).
 // REF: the reference's summation order for ref_threads = T chunks (hs_hessian_ref); the default instantiations ignore ref_threads.
-template <int BDIM, bool REF>
+// RC: every tap through the reference's cache RCA (hs_cache_taps; the host launches no helper workgroups then); the default
+// instantiations ignore RCA.
+template <int BDIM, bool REF, bool RC>
 __global__ void __launch_bounds__(BDIM)
 k4_match(hs_levels_arg A, const float2 *__restrict__ pts, int n, const float *__restrict__ hints, float3 hint1,
          float *__restrict__ out, int only_level, int iters_override, uint32_t *mail, uint32_t mail_seq,
-         const float2 *up_src, float2 *up_dst, uint32_t *up_flag, uint32_t up_seq, int n_helpers_from, int ref_threads)
+         const float2 *up_src, float2 *up_dst, uint32_t *up_flag, uint32_t up_seq, int n_helpers_from, int ref_threads,
+         hs_cache_arg RCA)
 {
     __shared__ double red[2 * hs_shape<BDIM>::RED];
     __shared__ float2 pts_s[HS_LDS_PTS];
@@ -552,6 +610,8 @@ k4_match(hs_levels_arg A, const float2 *__restrict__ pts, int n, const float *__
         int par = 0;
         for (int l = l_hi; l >= l_lo; l--) {                               // :47
             const hs_level_dev &L = A.lv[l];
+            hs_cache_lv C = { nullptr, 0 };
+            if constexpr (RC) { C.c = RCA.c[l]; C.epoch = RCA.epoch[l]; }
             float est[3];
             sh_v2_transform(est_w[0], est_w[1], L.map_t_world, &est[0], &est[1]);   // :68 GetMapCoordsPose
             est[2] = est_w[2];
@@ -559,11 +619,11 @@ k4_match(hs_levels_arg A, const float2 *__restrict__ pts, int n, const float *__
             for (int it = 0; it < iters; it++) {                           // :70-73
                 float sums[9];
                 if constexpr (REF) {
-                    if (in_lds) hs_hessian_ref<BDIM>(L, pts_s, n, est, ref_threads, hs_ref_lds_of<BDIM>(), sums);
-                    else hs_hessian_ref<BDIM>(L, pts, n, est, ref_threads, hs_ref_lds_of<BDIM>(), sums);
+                    if (in_lds) hs_hessian_ref<BDIM, RC>(L, C, pts_s, n, est, ref_threads, hs_ref_lds_of<BDIM>(), sums);
+                    else hs_hessian_ref<BDIM, RC>(L, C, pts, n, est, ref_threads, hs_ref_lds_of<BDIM>(), sums);
                 } else {
-                    if (in_lds) hs_hessian_block<BDIM, true>(L, pts_s, n, est, red + par, sums);
-                    else hs_hessian_block<BDIM, false>(L, pts, n, est, red + par, sums);
+                    if (in_lds) hs_hessian_block<BDIM, true, RC>(L, C, pts_s, n, est, red + par, sums);
+                    else hs_hessian_block<BDIM, false, RC>(L, C, pts, n, est, red + par, sums);
                     par ^= hs_shape<BDIM>::RED;                            // (a block is written again two barriers after it was read)
                 }
                 hs_step(sums, est);
@@ -582,16 +642,18 @@ k4_match(hs_levels_arg A, const float2 *__restrict__ pts, int n, const float *__
     }
 }
 
-template <bool REF>
+template <bool REF, bool RC>
 __global__ void __launch_bounds__(256)
 k4_hessian(hs_levels_arg A, int level, const float2 *__restrict__ pts, int n, const float *__restrict__ pose_in,
-           float *__restrict__ out12, int ref_threads)
+           float *__restrict__ out12, int ref_threads, hs_cache_arg RCA)
 {
     __shared__ double red[hs_shape<256>::RED];
     float pose[3] = { pose_in[0], pose_in[1], pose_in[2] };
     float sums[9];
-    if constexpr (REF) hs_hessian_ref<256>(A.lv[level], pts, n, pose, ref_threads, hs_ref_lds_of<256>(), sums);
-    else hs_hessian_block<256, false>(A.lv[level], pts, n, pose, red, sums);
+    hs_cache_lv C = { nullptr, 0 };
+    if constexpr (RC) { C.c = RCA.c[level]; C.epoch = RCA.epoch[level]; }
+    if constexpr (REF) hs_hessian_ref<256, RC>(A.lv[level], C, pts, n, pose, ref_threads, hs_ref_lds_of<256>(), sums);
+    else hs_hessian_block<256, false, RC>(A.lv[level], C, pts, n, pose, red, sums);
     if (threadIdx.x == 0) {
         out12[0] = sums[3]; out12[1] = sums[6]; out12[2] = sums[7];
         out12[3] = sums[6]; out12[4] = sums[4]; out12[5] = sums[8];
@@ -1212,6 +1274,28 @@ __global__ void k5_probability(const slamhip_cell *cells, const int32_t *idx, in
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = hs_prob_v(cells[idx[i]].value);                   // OccGridMap.GetCachedProbability (:97-107)
 }
+// ... through the reference's cache (slamhip_hs_set_reference_cache): :99-106 with the fills the matcher's taps make
+// (hs_cache_taps) -- repeated indices in one list give what the reference's sequential calls give, in any order
+__global__ void k5_probability_cached(const float *prob, unsigned long long *cache, int epoch, const int32_t *idx, int n, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = idx[i];
+    const unsigned long long e = __hip_atomic_load(cache + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    float v = hs_cache_entry_value(e);                                     // :106
+    if (!hs_cache_entry_hit(e, epoch)) {                                   // :99
+        v = prob[c];                                                       // :101-102
+        __hip_atomic_store(cache + c, hs_cache_entry(v, epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // :103
+    }
+    out[i] = v;
+}
+// new CachedMapElement[] with every Index = -1 (OccGridMap.cs:38-42): {Value 0, Index -1}
+__global__ void k5_cache_clear(unsigned long long *cache, size_t n)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (; i < n; i += stride) cache[i] = hs_cache_entry(0.0f, -1);
+}
 
 // the two words of slamhip_hs_checksum (common.h: k_checksum's definition, per member of the cell): out[0] over the values' bit
 // patterns, out[1] over the update indices
@@ -1244,13 +1328,21 @@ static hs_levels_arg levels_arg(slamhip_hs *hs)
     return A;
 }
 
+static hs_cache_arg cache_arg(slamhip_hs *hs)
+{
+    hs_cache_arg C;
+    memset(&C, 0, sizeof(C));
+    for (int l = 0; l < hs->n_levels; l++) { C.c[l] = hs->lv[l].d_cache; C.epoch[l] = hs->lv[l].curr_cache_index; }
+    return C;
+}
+
 extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
 {
     if (!hs) return SLAMHIP_OK;
     (void)hipSetDevice(hs->ctx->device);
     (void)hipStreamSynchronize(hs->ctx->stream);
     for (int l = 0; l < hs->n_levels; l++) {
-        (void)hipFree(hs->lv[l].d_cells); (void)hipFree(hs->lv[l].d_prob);
+        (void)hipFree(hs->lv[l].d_cells); (void)hipFree(hs->lv[l].d_prob); (void)hipFree(hs->lv[l].d_cache);
     }
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
@@ -1270,6 +1362,7 @@ extern "C" int32_t slamhip_hs_reset(slamhip_hs *hs)
         hs_level &L = hs->lv[l];
         hipLaunchKernelGGL(k5_fill_cells, dim3(1024), dim3(256), 0, hs->ctx->stream, L.d_cells, L.d_prob, (size_t)L.w * L.h);                   // GridMap.Reset :56-62
         L.curr_update_index = 0;                                           // OccGridMap.Reset :244-252
+        L.curr_cache_index = 0;                                            // :248 (the cache entries are left as they are)
     }
     SH_HIP(hipStreamSynchronize(hs->ctx->stream));
     return SLAMHIP_OK;
@@ -1344,7 +1437,8 @@ extern "C" int32_t slamhip_hs_cells_upload(slamhip_hs *hs, int32_t level, const 
     hs_level &L = hs->lv[level];
     SH_CHECK_ARG(n == (size_t)L.w * L.h);
     SH_HIP(hipSetDevice(hs->ctx->device));
-    // (the device holds the reference's own layout: a plain copy, then the cached probabilities)
+    // (the device holds the reference's own layout: a plain copy, then the cached probabilities.  The reference's cache and its
+    // epoch -- slamhip_hs_set_reference_cache -- are left as they are: the reference has no upload, and only its own events move them)
     SH_HIP(hipMemcpyAsync(L.d_cells, cells, sizeof(slamhip_cell) * n, hipMemcpyHostToDevice, hs->ctx->stream));
     hipLaunchKernelGGL(k5_refresh_prob, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, hs->ctx->stream, (const slamhip_cell *)L.d_cells, L.d_prob, n);
     SH_HIP(hipStreamSynchronize(hs->ctx->stream));
@@ -1439,7 +1533,11 @@ extern "C" int32_t slamhip_hs_probability(slamhip_hs *hs, int32_t level, const i
     hipError_t e = hipMalloc(&dout, sizeof(float) * n);
     if (e == hipSuccess) e = hipMemcpyAsync(di, indices, sizeof(int32_t) * n, hipMemcpyHostToDevice, hs->ctx->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k5_probability, dim3(sh_div_up(n, 256)), dim3(256), 0, hs->ctx->stream, (const slamhip_cell *)L.d_cells, di, n, dout);
+        if (hs->ref_cache)
+            hipLaunchKernelGGL(k5_probability_cached, dim3(sh_div_up(n, 256)), dim3(256), 0, hs->ctx->stream, (const float *)L.d_prob, L.d_cache,
+                               L.curr_cache_index, (const int32_t *)di, n, dout);
+        else
+            hipLaunchKernelGGL(k5_probability, dim3(sh_div_up(n, 256)), dim3(256), 0, hs->ctx->stream, (const slamhip_cell *)L.d_cells, di, n, dout);
         e = hipMemcpyAsync(out, dout, sizeof(float) * n, hipMemcpyDeviceToHost, hs->ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(hs->ctx->stream);
@@ -1567,18 +1665,22 @@ static int32_t run_match(slamhip_hs *hs, const float *hints, int B, float *out, 
         if (mail1) mail_seq = sh_mail_seq_next(ctx);
         const int lanes = B <= 8 ? 512 : 256;
         // (a single full match in the per-scan flow brings helper workgroups: k4_match)
+        // (none with the reference's cache: a helper would have to read the cache entries, and must not fill them)
         static const int helpers_env = (int)sh_env_int("SLAMHIP_K4_HELPERS", 1);
-        const int helpers = B == 1 && only_level < 0 && hs->n_levels > 1 && hs->n_points > 0 && helpers_env > 0 ? 8 * helpers_env : 0;
+        const bool rc = hs->ref_cache != 0;
+        const int helpers = !rc && B == 1 && only_level < 0 && hs->n_levels > 1 && hs->n_points > 0 && helpers_env > 0 ? 8 * helpers_env : 0;
         const int T = hs->match_threads;
-#define K4_LAUNCH(BD, REF) hipLaunchKernelGGL((k4_match<BD, REF>), dim3(B + helpers), dim3(BD), 0, ctx->stream, levels_arg(hs), hs->d_pts, hs->n_points, d_hints, \
-                                              h1, d_out, only_level, iters, mb, mail_seq, up_src, up_dst, up_flag, up_seq, helpers ? B : 0, T)
+#define K4_LAUNCH(BD, REF, RC) hipLaunchKernelGGL((k4_match<BD, REF, RC>), dim3(B + helpers), dim3(BD), 0, ctx->stream, levels_arg(hs), hs->d_pts, hs->n_points, d_hints, \
+                                                  h1, d_out, only_level, iters, mb, mail_seq, up_src, up_dst, up_flag, up_seq, helpers ? B : 0, T, cache_arg(hs))
+#define K4_WIDTHS(REF, RC) { if (lanes == 512) K4_LAUNCH(512, REF, RC); else K4_LAUNCH(256, REF, RC); }
         if (T == 0) {
-            if (lanes == 512) K4_LAUNCH(512, false);
-            else K4_LAUNCH(256, false);
+            if (!rc) K4_WIDTHS(false, false)
+            else K4_WIDTHS(false, true)
         } else {                                                          // (the reference's order: the same bits at every width)
-            if (lanes == 512) K4_LAUNCH(512, true);
-            else K4_LAUNCH(256, true);
+            if (!rc) K4_WIDTHS(true, false)
+            else K4_WIDTHS(true, true)
         }
+#undef K4_WIDTHS
 #undef K4_LAUNCH
     }
     SH_HIP(hipGetLastError());
@@ -1621,6 +1723,35 @@ extern "C" int32_t slamhip_hs_set_match_threads(slamhip_hs *hs, int32_t num_thre
     return SLAMHIP_OK;
 }
 
+extern "C" int32_t slamhip_hs_set_reference_cache(slamhip_hs *hs, int32_t on)
+{
+    SH_CHECK_ARG(hs && (on == 0 || on == 1));
+#if HS_PROB_MODE != 0
+    if (on) SH_FAIL(SLAMHIP_ERR_STATE, "the reference's cache needs the probability grids (HS_PROB_MODE 0)");
+#endif
+    if (on && !hs->ref_cache) {
+        SH_HIP(hipSetDevice(hs->ctx->device));
+        for (int l = 0; l < hs->n_levels; l++) {
+            hs_level &L = hs->lv[l];
+            if (L.d_cache) continue;
+            if (hipMalloc(&L.d_cache, sizeof(unsigned long long) * (size_t)L.w * L.h) != hipSuccess) {
+                (void)hipGetLastError();
+                for (int k = 0; k < hs->n_levels; k++) { (void)hipFree(hs->lv[k].d_cache); hs->lv[k].d_cache = nullptr; }   // (the mode is off: nothing reads them)
+                SH_FAIL(SLAMHIP_ERR_NOMEM, "device allocation of the reference's cache failed (level %d)", l);
+            }
+        }
+        // every switch to on starts from a new OccGridMap's cache (:38-42): fills made while the mode was off were never recorded
+        for (int l = 0; l < hs->n_levels; l++) {
+            hs_level &L = hs->lv[l];
+            const size_t n = (size_t)L.w * L.h;
+            hipLaunchKernelGGL(k5_cache_clear, dim3((unsigned)(n / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, hs->ctx->stream, L.d_cache, n);
+        }
+        SH_HIP(hipGetLastError());
+    }
+    hs->ref_cache = on;                                                   // (read by the next launch of K4 and slamhip_hs_probability)
+    return SLAMHIP_OK;
+}
+
 extern "C" int32_t slamhip_hs_match(slamhip_hs *hs, const float hint[3], float out[3])
 {
     SH_CHECK_ARG(hs && hint && out);
@@ -1648,12 +1779,16 @@ extern "C" int32_t slamhip_hs_hessian(slamhip_hs *hs, int32_t level, const float
     SH_TRY(hs_flush_scan(hs));
     memcpy(hs->h_io, pose_map, sizeof(float) * 3);
     SH_HIP(hipMemcpyAsync(hs->d_io, hs->h_io, sizeof(float) * 3, hipMemcpyHostToDevice, ctx->stream));
-    if (hs->match_threads == 0)
-        hipLaunchKernelGGL(k4_hessian<false>, dim3(1), dim3(256), 0, ctx->stream, levels_arg(hs), level, hs->d_pts, hs->n_points,
-                           (const float *)hs->d_io, hs->d_io + 16, 0);
-    else
-        hipLaunchKernelGGL(k4_hessian<true>, dim3(1), dim3(256), 0, ctx->stream, levels_arg(hs), level, hs->d_pts, hs->n_points,
-                           (const float *)hs->d_io, hs->d_io + 16, hs->match_threads);
+#define K4H_LAUNCH(REF, RC) hipLaunchKernelGGL((k4_hessian<REF, RC>), dim3(1), dim3(256), 0, ctx->stream, levels_arg(hs), level, hs->d_pts, hs->n_points, \
+                                               (const float *)hs->d_io, hs->d_io + 16, hs->match_threads, cache_arg(hs))
+    if (hs->match_threads == 0) {
+        if (!hs->ref_cache) K4H_LAUNCH(false, false);
+        else K4H_LAUNCH(false, true);
+    } else {
+        if (!hs->ref_cache) K4H_LAUNCH(true, false);
+        else K4H_LAUNCH(true, true);
+    }
+#undef K4H_LAUNCH
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(hs->h_io + 16, hs->d_io + 16, sizeof(float) * 12, hipMemcpyDeviceToHost, ctx->stream));
     SH_HIP(hipStreamSynchronize(ctx->stream));
@@ -1664,10 +1799,14 @@ extern "C" int32_t slamhip_hs_hessian(slamhip_hs *hs, int32_t level, const float
 
 // the launches of UpdateByScan on the operator's stream; nothing comes back to the host
 // gate_in: the device-gated form (k5_gate) -- `pose` is then only a stand-in, and the update indices are advanced by
-// hs_update_commit once the host knows that the update took place
+// hs_update_commit once the host knows that the update took place.  (The cache epoch can live on the host: no launch that reads
+// probabilities is ever enqueued between an update and its commit -- the gated form's match is enqueued IN FRONT of its update.)
 static void hs_update_commit(slamhip_hs *hs)
 {
-    for (int l = 0; l < hs->n_levels; l++) hs->lv[l].curr_update_index += 3;   // :144
+    for (int l = 0; l < hs->n_levels; l++) {
+        hs->lv[l].curr_update_index += 3;                                  // :144
+        hs->lv[l].curr_cache_index++;                                      // :147
+    }
     if (hs->k5_toggle_pending) hs->k5_sec_parity ^= 1;       // (the one-launch form wrote the other record set)
     hs->k5_toggle_pending = false;
 }

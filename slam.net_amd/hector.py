@@ -114,6 +114,13 @@ class MapRepMultiMap:
         1 .. 64 the reference's ScanMatcher(numThreads) chunks (ScanMatcher.cs:149-195), bit for bit."""
         capi.call("slamhip_hs_set_match_threads", self._h, int(numThreads))
 
+    def set_reference_cache(self, on):
+        """The reference's probability cache on this pyramid (slamhip_hs_set_reference_cache, deviation D5): 1 every
+        probability the matcher and GetCachedProbability read goes through OccGridMap's cacheArray, stale across Reset as
+        in the reference (OccGridMap.cs:97-107,248); 0 the current probability (default).  Turning it on starts from a
+        new OccGridMap's cache."""
+        capi.call("slamhip_hs_set_reference_cache", self._h, int(on))
+
     def SetUpdateFactorFree(self, factor):
         self._free = float(factor)
         capi.call("slamhip_hs_set_factors", self._h, C.c_float(factor), C.c_float(getattr(self, "_occ", 0.9)))
@@ -177,7 +184,7 @@ class HectorSLAMProcessor:
     """HectorSLAM/Main/HectorSLAMProcessor.cs:17-160"""
 
     def __init__(self, mapResolution, mapSize, startPose, numDepth, numThreads=1, logger=None, ctx=None,
-                 referenceSummation=False):
+                 referenceSummation=False, referenceCache=False):
         self._own_ctx = ctx is None
         self.ctx = ctx or Context(0)
         sp = capi.f32(startPose)
@@ -189,6 +196,8 @@ class HectorSLAMProcessor:
         self.MapRep = MapRepMultiMap(mapResolution, mapSize, numDepth, ctx=self.ctx, _handle=hsh)
         if referenceSummation:                                      # the processor's matcher, ScanMatcher(numThreads) (:72)
             self.MapRep.set_match_threads(numThreads)
+        if referenceCache:                                          # OccGridMap's cacheArray, stale across Reset (deviation D5)
+            self.MapRep.set_reference_cache(1)
         self._min_dist, self._min_angle = 0.3, 0.13
 
     def _get(self):

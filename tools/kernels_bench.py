@@ -1,7 +1,8 @@
 """Secondary-kernel timings (K2 HoleMap update, K3 ObstacleMap update, K4 Hector match, K5 Hector grid update,
 fused search+update) on one MI355X, with the algorithmic byte counts of SURVEY.md sec.8d, and the Hector matcher in the
-reference's summation order (ScanMatcher(T, referenceSummation=True), T = 1, 4, 16, beside the default order).  Prints one
-JSON object.  --hector-only: the Hector part alone."""
+reference's summation order (ScanMatcher(T, referenceSummation=True), T = 1, 4, 16, beside the default order) and through
+the reference's probability cache (T = 0 and 1, beside the default).  Prints one JSON object.  --hector-only: the Hector
+part alone."""
 import json, math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -87,9 +88,11 @@ out["k4_hector_match_3lvl_2048"] = {"kernel_us_single": ms4 / n4 * 1e3, "blockin
 # the reference's summation order (slamhip_hs_set_match_threads): single match, a 64-hint batch and HectorSLAMProcessor.Update
 # (2048^2 x 3 levels, 1080 rays, 30 matched scans after 10 mapped ones), each beside the default order (T = 0)
 hints64 = hints[:64].copy()
-rs = {}
-for T in (0, 1, 4, 16):
+
+
+def match_rows(T, refcache=False):
     m = hs.ScanMatcher(max(T, 1), referenceSummation=T > 0)
+    rep.set_reference_cache(1 if refcache else 0)
     ctx.timing_enable(-1)
     for _ in range(3): m.MatchData(rep, scan, hint)
     ctx.timing_reset()
@@ -99,7 +102,8 @@ for T in (0, 1, 4, 16):
     for _ in range(20): m.MatchDataBatch(rep, scan, hints64)
     ms64, n64 = ctx.timing_get(capi.K_HS_MATCH)
     ctx.timing_enable(0)
-    proc = hs.HectorSLAMProcessor(40.0 / 2048, (2048, 2048), scans[0][1], 3, max(T, 1), ctx=ctx, referenceSummation=T > 0)
+    proc = hs.HectorSLAMProcessor(40.0 / 2048, (2048, 2048), scans[0][1], 3, max(T, 1), ctx=ctx, referenceSummation=T > 0,
+                                  referenceCache=refcache)
     rng = sim.PCG32(77)
     pscans = [hs.ScanCloud(sim.make_scan(segs, np.array([20 + 0.03 * i, 20 + 0.01 * i, 0.004 * i], np.float32), 1080, rng)[1])
               for i in range(40)]
@@ -110,7 +114,15 @@ for T in (0, 1, 4, 16):
     ctx.synchronize()
     upd = (time.perf_counter() - t0) / 30
     proc.Dispose()
-    rs["T%d" % T] = {"kernel_us_single": ms1 / n1 * 1e3, "kernel_us_batch64": ms64 / n64 * 1e3, "processor_update_us": upd * 1e6}
+    rep.set_reference_cache(0)
+    return {"kernel_us_single": ms1 / n1 * 1e3, "kernel_us_batch64": ms64 / n64 * 1e3, "processor_update_us": upd * 1e6}
+
+
+out["k4_hector_match_refsum_3lvl_2048"] = {"T%d" % T: match_rows(T) for T in (0, 1, 4, 16)}
+# the reference's probability cache (slamhip_hs_set_reference_cache), the same three figures beside the default at T = 0 and
+# T = 1.  (The repeated single matches and batches run on one map in one epoch: after the first, their taps hit the entries
+# it filled.  In the processor's flow every update starts a new epoch, so the first iteration on every level fills.)
+out["k4_hector_match_refcache_3lvl_2048"] = {"T%d_%s" % (T, "refcache" if rc else "default"): match_rows(T, rc)
+                                              for T in (0, 1) for rc in (False, True)}
 rep.set_match_threads(0)
-out["k4_hector_match_refsum_3lvl_2048"] = rs
 print(json.dumps(out, indent=1))
