@@ -23,6 +23,7 @@ namespace HectorSLAM.Main
         private readonly int numThreads;
         private float minDistanceDiff = 0.3f, minAngleDiff = 0.13f;
         private bool referenceSummation;
+        private bool matchReport;
 
         public MapRepMultiMap MapRep { get; private set; }
         public Vector3 LastMapUpdatePose { get; private set; }
@@ -68,6 +69,18 @@ namespace HectorSLAM.Main
             set => MapRep.ReferenceCache = value;
         }
 
+        /// <summary>Every Update's match leaves its report (slamhip_hsproc_set_match_report), produced in the match's own launch;
+        /// poses, the gated map update and what Update returns do not change.  false (default): Update launches what it always did.</summary>
+        public bool MatchReport
+        {
+            get => matchReport;
+            set { Native.Check(Native.slamhip_hsproc_set_match_report(proc.Ptr, value ? 1 : 0)); matchReport = value; }
+        }
+
+        /// <summary>The report of the last Update's match, or null: before the first match, after Reset, after an Update with
+        /// mapWithoutMatching, and while MatchReport is off.</summary>
+        public SlamHip.MatchReport? LastMatchReport { get; private set; }   // (qualified: MatchReport alone is the property above)
+
         public HectorSLAMProcessor(float mapResolution, Point mapSize, Vector3 startPose, int numDepth, int numThreads, ILogger logger = null)
             : this(mapResolution, mapSize, startPose, numDepth, numThreads, logger, null)
         {
@@ -105,6 +118,8 @@ namespace HectorSLAM.Main
         {
             Native.Check(Native.slamhip_hsproc_get(proc.Ptr, out Vector3 match, out Vector3 last, out float tm, out float tu));
             MatchPose = match; LastMapUpdatePose = last; MatchTiming = tm; UpdateTiming = tu;
+            Native.Check(Native.slamhip_hsproc_get_report(proc.Ptr, out SlamHip.MatchReport report, out int valid));
+            LastMatchReport = valid != 0 ? report : (SlamHip.MatchReport?)null;
         }
 
         public void Reset()                                              // :131-138

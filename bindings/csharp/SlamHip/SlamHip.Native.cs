@@ -1,7 +1,8 @@
 // SlamHip.Native.cs -- P/Invoke surface of libslamhip.so (include/slamhip.h), one declaration per C entry point the
 // managed shims use.  Every function returns an int32 status (0 = OK); Check() turns anything else into an
 // InvalidOperationException carrying slamhip_last_error().  Structs crossing the boundary are blittable:
-// Vector2 / Vector3 / Vector4 (8 / 12 / 16 bytes) and LogOddsCell {int UpdateIndex; float Value} (8 bytes).
+// Vector2 / Vector3 / Vector4 (8 / 12 / 16 bytes), LogOddsCell {int UpdateIndex; float Value} (8 bytes) and MatchReport
+// (slamhip_match_report: 19 four-byte fields, 76 bytes).
 //
 // Source only: the build image of this repository has no .NET SDK; the same symbols are exercised by the ctypes
 // binding (slam.net_amd/capi.py) and by the GPU tests.
@@ -11,6 +12,27 @@ using System.Runtime.InteropServices;
 
 namespace SlamHip
 {
+    /// <summary>slamhip_match_report (include/slamhip.h): the match evaluated once more at the pose it ends on -- H and dTr of
+    /// GetCompleteHessianDerivs (ScanMatcher.cs:135-204) at PoseMap on the report level, the residual (sum over all scan points of
+    /// (1 - M)^2, a point outside the map adding 1) and how many points fell inside the map.  19 four-byte fields, 76 bytes.
+    /// The library sets no acceptance threshold: what residual means "lost" is the host's decision.</summary>
+    [StructLayout(LayoutKind.Sequential, Pack = 4)]
+    public struct MatchReport
+    {
+        public float PoseMapX, PoseMapY, PoseMapTheta;
+        public float H11, H12, H13, H21, H22, H23, H31, H32, H33;
+        public float DTrX, DTrY, DTrTheta;
+        public float Residual;
+        public int InMapCount;
+        public int PointCount;
+        public int Level;
+
+        public Vector3 PoseMap => new Vector3(PoseMapX, PoseMapY, PoseMapTheta);
+        public Vector3 DTr => new Vector3(DTrX, DTrY, DTrTheta);
+        /// <summary>Residual per scan point: 0 a perfect fit, 0.25 unobserved cells, 1 off the map.</summary>
+        public float ResidualPerPoint => PointCount > 0 ? Residual / PointCount : 0f;
+    }
+
     internal static unsafe class Native
     {
         const string Lib = "slamhip";                                   // libslamhip.so on the library path
@@ -81,6 +103,10 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_match_level(IntPtr hs, int level, in Vector3 hint, int iterations, out Vector3 pose);
         [DllImport(Lib)] internal static extern int slamhip_hs_match_batch(IntPtr hs, Vector3* hints, int count, Vector3* poses);
         // ScanMatcher(numThreads)'s summation order (ScanMatcher.cs:149-195): 0 the device's own, 1..64 the reference's chunks, bit for bit
+        [DllImport(Lib)] internal static extern int slamhip_hs_match_report(IntPtr hs, in Vector3 hint, out Vector3 pose, out MatchReport report);
+        [DllImport(Lib)] internal static extern int slamhip_hs_match_level_report(IntPtr hs, int level, in Vector3 hint, int iterations, out Vector3 pose, out MatchReport report);
+        [DllImport(Lib)] internal static extern int slamhip_hs_match_batch_report(IntPtr hs, Vector3* hints, int count, Vector3* poses, MatchReport* reports);
+        [DllImport(Lib)] internal static extern int slamhip_hs_match_best(IntPtr hs, Vector3* hints, int count, out Vector3 pose, out int index, out MatchReport report);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_match_threads(IntPtr hs, int numThreads);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_reference_cache(IntPtr hs, int on);
         [DllImport(Lib)] internal static extern int slamhip_hs_update_by_scan(IntPtr hs, in Vector3 robotPoseWorld);
@@ -91,6 +117,8 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_reset(IntPtr proc);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_update(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in Vector3 poseHintWorld, int mapWithoutMatching, out int mapUpdated);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_get(IntPtr proc, out Vector3 matchPose, out Vector3 lastMapUpdatePose, out float matchTimingMs, out float updateTimingMs);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_set_match_report(IntPtr proc, int on);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_get_report(IntPtr proc, out MatchReport report, out int valid);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_set_thresholds(IntPtr proc, float minDistanceDiff, float minAngleDiff);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_hs(IntPtr proc, out IntPtr hs);
 

@@ -440,6 +440,46 @@ int32_t slamhip_hs_set_match_threads(slamhip_hs *hs, int32_t num_threads);
  * unchanged. */
 int32_t slamhip_hs_set_reference_cache(slamhip_hs *hs, int32_t on);
 
+/* The match report: what a caller needs to tell a good match from a bad one, evaluated once more at the pose the match ends on.
+ * The report level is level 0 (the finest, the last one matched) for a pyramid match and `level` for slamhip_hs_match_level.
+ * Everything is evaluated at pose_map = GetMapCoordsPose(out_pose) on that level (GridMap.cs:133-137; out_pose the world pose
+ * the call returns, angle already normalised, ScanMatcher.cs:76): H and dTr are GetCompleteHessianDerivs there
+ * (ScanMatcher.cs:135-204) -- what slamhip_hs_hessian(hs, level, pose_map, ...) answers in the same summation mode; H at the
+ * solution is what the original Hector matcher hands on as the pose information matrix.  residual is the sum over ALL scan
+ * points of funVal * funVal, funVal = 1.0f - M (:164-166), subtract and multiply rounded separately in binary32; a point
+ * outside the map has M = 0 (InterpMapValueWithDerivatives returns Vector3.Zero, :214-217) and adds exactly 1, so a pose that
+ * throws the scan off the map scores n_points, and cells never observed (probability 0.5) score 0.25 each.  It is summed as H is
+ * (slamhip_hs_set_match_threads: T >= 1 in ceil(n/T)-point chunks sequentially, partials in thread order; T = 0 in the device's
+ * own order).  n_in_map counts the points for which IsPointOutOfMapBounds is false at pose_map (MapProperties.cs:83-87).
+ * n_points == 0: out_pose is the hint (:83) and H, dTr, residual, n_in_map are zero.  With the reference's cache on
+ * (slamhip_hs_set_reference_cache) the report's taps observe the cache and never fill it -- an entry of the level's epoch is
+ * served, anything else is computed from the cell's current value and not recorded: the reference makes no such evaluation, so
+ * it leaves no trace in state that decides later answers across slamhip_hs_reset.
+ * The library sets no acceptance threshold: what residual means "lost" depends on the map and the sensor and is the host's
+ * decision. */
+typedef struct slamhip_match_report {
+    float   pose_map[3];   /* GetMapCoordsPose(out_pose) on the report level (GridMap.cs:133-137) */
+    float   H[9];          /* row-major 3x3, as slamhip_hs_hessian lays it out (ScanMatcher.cs:198-200) */
+    float   dTr[3];        /* :166-172 */
+    float   residual;      /* sum over all scan points of funVal * funVal, funVal = 1.0f - M (:164-166) */
+    int32_t n_in_map;      /* points for which IsPointOutOfMapBounds is false at pose_map */
+    int32_t n_points;
+    int32_t level;         /* the report level */
+} slamhip_match_report;    /* 19 four-byte fields, sizeof(slamhip_match_report) == 76, no padding */
+/* slamhip_hs_match / _match_level / _match_batch with the report of every match, produced in the same launch by the workgroup
+ * that ran the match; out_pose is bit for bit the plain call's.  out_reports: B of them. */
+int32_t slamhip_hs_match_report(slamhip_hs *hs, const float hint_pose[3], float out_pose[3], slamhip_match_report *out_report);
+int32_t slamhip_hs_match_level_report(slamhip_hs *hs, int32_t level, const float hint_pose[3], int32_t iterations,
+                                      float out_pose[3], slamhip_match_report *out_report);
+int32_t slamhip_hs_match_batch_report(slamhip_hs *hs, const float *hint_poses, int32_t B, float *out_poses,
+                                      slamhip_match_report *out_reports);
+/* Best of batch (relocalisation: many hints, one answer): the B matches of slamhip_hs_match_batch_report, and the winner picked
+ * on the device by a 64-bit minimum over key = (uint64)bits(residual) << 32 | index.  A residual is >= +0, so its bit pattern
+ * orders as its value does; a NaN (only from NaN cells uploaded by the caller) sorts after every number; equal residuals go to
+ * the lowest index.  Only the winner's pose, its index and its report come back to the host. */
+int32_t slamhip_hs_match_best(slamhip_hs *hs, const float *hint_poses, int32_t B, float out_pose[3], int32_t *out_index,
+                              slamhip_match_report *out_report);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -464,6 +504,14 @@ int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int32_t n_poin
                               int32_t *out_map_updated);
 int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last_map_update_pose[3],
                            float *match_timing_ms, float *update_timing_ms);            /* :31-46 */
+/* on = 1: the match of every later slamhip_hsproc_update produces its report in the same launch (slamhip_hs_match_report);
+ * the gated grid update, the launch-ahead order and what Update returns do not change.  on = 0 (default): Update launches what
+ * it launches without this call.  Any other value: SLAMHIP_ERR_INVALID, the setting unchanged. */
+int32_t slamhip_hsproc_set_match_report(slamhip_hsproc *p, int32_t on);
+/* The report of the last slamhip_hsproc_update's match (:93); *out_valid = 0 and *out zeroed before the first match, after
+ * slamhip_hsproc_reset, after an Update with mapWithoutMatching (:100) and while reports are off (switching them off drops the
+ * last report). */
+int32_t slamhip_hsproc_get_report(slamhip_hsproc *p, slamhip_match_report *out, int32_t *out_valid);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -20,6 +20,18 @@ K_CS_PREP, K_CS_DISTANCE, K_CS_REDUCE, K_CS_HOLEMAP, K_CS_OBSTACLE, K_HS_MATCH, 
 CELL_DTYPE = np.dtype([("update_index", np.int32), ("value", np.float32)])
 
 
+class MatchReport(C.Structure):
+    """slamhip_match_report (include/slamhip.h): 19 four-byte fields, 76 bytes, no padding."""
+    _fields_ = [("pose_map", C.c_float * 3), ("H", C.c_float * 9), ("dTr", C.c_float * 3), ("residual", C.c_float),
+                ("n_in_map", C.c_int32), ("n_points", C.c_int32), ("level", C.c_int32)]
+
+
+# ... the same layout for arrays of reports (slamhip_hs_match_batch_report)
+REPORT_DTYPE = np.dtype([("pose_map", np.float32, 3), ("H", np.float32, (3, 3)), ("dTr", np.float32, 3),
+                         ("residual", np.float32), ("n_in_map", np.int32), ("n_points", np.int32), ("level", np.int32)])
+assert C.sizeof(MatchReport) == REPORT_DTYPE.itemsize == 76
+
+
 class SlamhipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("slamhip error %d: %s" % (code, msg))
@@ -53,6 +65,7 @@ def _declare(L):
     i32, u64, i64, f, vp, sz = C.c_int32, C.c_uint64, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
     P = C.POINTER
     fp, ip, u16p, i8p, u8p, u64p, vpp = P(f), P(i32), P(C.c_uint16), P(C.c_int8), P(C.c_uint8), P(u64), P(vp)
+    rp = P(MatchReport)
     sig = {
         "slamhip_version": (C.c_char_p, []),
         "slamhip_last_error": (C.c_char_p, []),
@@ -137,6 +150,10 @@ def _declare(L):
         "slamhip_hs_match_level": (i32, [vp, i32, fp, i32, fp]),
         "slamhip_hs_match_batch": (i32, [vp, fp, i32, fp]),
         "slamhip_hs_hessian": (i32, [vp, i32, fp, fp, fp]),
+        "slamhip_hs_match_report": (i32, [vp, fp, fp, rp]),
+        "slamhip_hs_match_level_report": (i32, [vp, i32, fp, i32, fp, rp]),
+        "slamhip_hs_match_batch_report": (i32, [vp, fp, i32, fp, rp]),
+        "slamhip_hs_match_best": (i32, [vp, fp, i32, fp, ip, rp]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -145,6 +162,8 @@ def _declare(L):
         "slamhip_hsproc_reset": (i32, [vp]),
         "slamhip_hsproc_update": (i32, [vp, fp, i32, fp, fp, i32, ip]),
         "slamhip_hsproc_get": (i32, [vp, fp, fp, fp, fp]),
+        "slamhip_hsproc_set_match_report": (i32, [vp, i32]),
+        "slamhip_hsproc_get_report": (i32, [vp, rp, ip]),
         "slamhip_hsproc_set_thresholds": (i32, [vp, f, f]),
         "slamhip_hsproc_hs": (i32, [vp, vpp]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
@@ -197,6 +216,11 @@ def fptr(a):
 
 def iptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def rptr(a):
+    """A REPORT_DTYPE array as the slamhip_match_report pointer of the C-ABI."""
+    return a.ctypes.data_as(C.POINTER(MatchReport))
 
 
 def f32(a, shape=None):

@@ -76,6 +76,10 @@ struct slamhip_hs {
     int *d_k5_sec; int k5_sec_parity; bool k5_toggle_pending;                        // [2][HS_MAX_LEVELS][K5_SEC] sector records of the cell kernel: an update reads the set the last one wrote
     int match_threads;                                     // slamhip_hs_set_match_threads: 0 the device's summation order, 1 .. HS_REF_MAX_T the reference's
     int ref_cache;                                         // slamhip_hs_set_reference_cache: 1 every probability reader goes through d_cache
+    // the match reports (slamhip_match_report): the batch's reports and the best-of-batch key word in device memory, and a pinned,
+    // device-visible block the host reads them from -- a single blocking match stores its report there itself, in front of the
+    // mailbox's sequence word (the mailbox is 64 B, the report 76)
+    slamhip_match_report *d_rep, *h_rep; int cap_rep; unsigned long long *d_best_key;
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -172,6 +176,7 @@ template <int BDIM> struct hs_shape {
     static constexpr int NW = BDIM >> 6;                                   // wavefronts
     static constexpr int PU = BDIM >= 1024 ? 2 : BDIM >= 512 ? 3 : 5;      // points per lane and pass (1080 rays: one pass)
     static constexpr int RED = 9 * NW;                                     // doubles per reduction block
+    static constexpr int RED_REP = 11 * NW;                                // ... of the match report's pass (hs_hessian_block<REP>)
 };
 
 // the per-iteration transform of GetCompleteHessianDerivs (:139-146), the same in every lane
@@ -209,6 +214,9 @@ __device__ static __forceinline__ unsigned long long hs_cache_entry(float v, int
 }
 // the four taps of an in-range point at cell idx (:230-233) through the cache.  A point outside the map, a NaN point or a
 // padding lane (ok false) reads and fills nothing: the reference returns before its first tap (:216-219).
+// FILL false (the match report's taps, an evaluation the reference does not make): the cache is observed, never filled --
+// an entry of this epoch is served, anything else is computed from the cell's current value and not recorded.
+template <bool FILL = true>
 __device__ static __forceinline__ void hs_cache_taps(const hs_cache_lv &C, const float *prob, int idx, int w, bool ok, float2 &r0, float2 &r1)
 {
     float v[4] = { 0.f, 0.f, 0.f, 0.f };
@@ -222,17 +230,19 @@ __device__ static __forceinline__ void hs_cache_taps(const hs_cache_lv &C, const
         for (int k = 0; k < 4; k++) { miss[k] = !hs_cache_entry_hit(e[k], C.epoch); v[k] = hs_cache_entry_value(e[k]); }
 #pragma unroll
         for (int k = 0; k < 4; k++) if (miss[k]) v[k] = prob[at[k]];      // :101-102
+        if constexpr (FILL) {
 #pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (miss[k]) __hip_atomic_store(C.c + at[k], hs_cache_entry(v[k], C.epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // :103
+            for (int k = 0; k < 4; k++)
+                if (miss[k]) __hip_atomic_store(C.c + at[k], hs_cache_entry(v[k], C.epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // :103
+        }
     }
     r0 = make_float2(v[0], v[1]); r1 = make_float2(v[2], v[3]);
 }
 
 // one scan point i (i >= n: a padding lane, its terms are zero): the point and its four taps, requested without waiting.
-// RC: the taps through the reference's cache (hs_cache_taps)
+// RC: the taps through the reference's cache (hs_cache_taps), FILL as there
 struct hs_point { float2 p, r0, r1; float fx, fy; bool ok; };
-template <bool RC>
+template <bool RC, bool FILL = true>
 __device__ static __forceinline__ void hs_point_taps(const hs_level_dev &L, const hs_cache_lv &C, const float2 *pts, int i, int n, const hs_iter_xf &X, hs_point &q)
 {
     q.p = i < n ? pts[i] : make_float2(0.f, 0.f);
@@ -245,7 +255,7 @@ __device__ static __forceinline__ void hs_point_taps(const hs_level_dev &L, cons
     q.fx = cx - fxx; q.fy = cy - fyy;                                      // :225
     const int idx = iy * L.w + ix;                                         // :227
 #if HS_PROB_MODE == 0
-    if constexpr (RC) hs_cache_taps(C, L.prob, idx, L.w, q.ok, q.r0, q.r1);
+    if constexpr (RC) hs_cache_taps<FILL>(C, L.prob, idx, L.w, q.ok, q.r0, q.r1);
     else {
         __builtin_memcpy(&q.r0, L.prob + idx, sizeof(float2));             // (two adjacent taps: one 8-byte load)
         __builtin_memcpy(&q.r1, L.prob + idx + L.w, sizeof(float2));
@@ -260,7 +270,9 @@ __device__ static __forceinline__ void hs_point_taps(const hs_level_dev &L, cons
 }
 
 // the point's nine terms (:162-180) in the order of sums[]: the interpolation and the products, each a binary32 rounding
-__device__ static __forceinline__ void hs_point_terms(const hs_point &q, const hs_iter_xf &X, float tm[9])
+// NT == 10 (the match report): tm[9] = funVal * funVal, the point's share of the residual
+template <int NT = 9>
+__device__ static __forceinline__ void hs_point_terms(const hs_point &q, const hs_iter_xf &X, float tm[NT])
 {
     const float i0 = q.r0.x, i1 = q.r0.y, i2 = q.r1.x, i3 = q.r1.y;        // :230-233
     const float dx1 = i0 - i1, dx2 = i2 - i3, dy1 = i0 - i2, dy2 = i1 - i3;    // :235-239
@@ -274,14 +286,21 @@ __device__ static __forceinline__ void hs_point_terms(const hs_point &q, const h
     tm[0] = gx * fun;  tm[1] = gy * fun;  tm[2] = rot * fun;               // :166,:167,:172
     tm[3] = gx * gx;   tm[4] = gy * gy;   tm[5] = rot * rot;               // :174-176
     tm[6] = gx * gy;   tm[7] = gx * rot;  tm[8] = gy * rot;                // :178-180
+    if constexpr (NT == 10) tm[9] = fun * fun;
 }
 
 // RC: the taps through the reference's cache (hs_cache_taps)
-template <int BDIM, bool LDSP, bool RC>
+// REP (the match report, slamhip_match_report): two more accumulators through the same reduction -- the residual, the sum of
+// funVal * funVal over ALL points (a point outside the map has M = 0 and adds exactly 1), as sum 9 in binary32 like the others,
+// and the number of points inside the map as an integer, exact -- and with RC taps that fill nothing.  `red` then holds
+// hs_shape::RED_REP doubles.
+template <int BDIM, bool LDSP, bool RC, bool REP = false>
 __device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, const hs_cache_lv &C, const float2 *pts, int n, const float pose[3],
-                                                        double *red /* [hs_shape::RED]: this iteration's block */, float sums[9])
+                                                        double *red /* [hs_shape::RED]: this iteration's block */, float sums[9],
+                                                        float *residual = nullptr, int *n_in_map = nullptr)
 {
     constexpr int NW = hs_shape<BDIM>::NW, PU = hs_shape<BDIM>::PU;
+    constexpr int NS = REP ? 10 : 9;                                       // binary32 sums
     K4_STAMP_BEGIN
     float s, c;
     sh_det_sincosf(pose[2], &s, &c);
@@ -291,7 +310,8 @@ __device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, c
     const float sinRot = s * L.stm, cosRot = c * L.stm;                    // :145-146
     const float limx = (float)L.w - 2.0f, limy = (float)L.h - 2.0f;       // MapProperties.cs:42
     K4_STAMP(0)                                                            // transform + trigonometry
-    float acc[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    float acc[NS] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 };
+    int cnt = 0;
     for (int base = 0; base < n; base += BDIM * PU) {
         float2 p[PU], r0[PU], r1[PU];
         float fx[PU], fy[PU];
@@ -309,7 +329,7 @@ __device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, c
             fx[u] = cx - fxx; fy[u] = cy - fyy;                            // :225
             const int idx = iy * L.w + ix;                                 // :227
 #if HS_PROB_MODE == 0
-            if constexpr (RC) hs_cache_taps(C, L.prob, idx, L.w, ok[u], r0[u], r1[u]);
+            if constexpr (RC) hs_cache_taps<!REP>(C, L.prob, idx, L.w, ok[u], r0[u], r1[u]);
             else {
                 __builtin_memcpy(&r0[u], L.prob + idx, sizeof(float2));    // (two adjacent taps: one 8-byte load)
                 __builtin_memcpy(&r1[u], L.prob + idx + L.w, sizeof(float2));
@@ -336,6 +356,10 @@ __device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, c
             acc[0] += gx * fun;  acc[1] += gy * fun;  acc[2] += rot * fun; // :166,:167,:172
             acc[3] += gx * gx;   acc[4] += gy * gy;   acc[5] += rot * rot; // :174-176
             acc[6] += gx * gy;   acc[7] += gx * rot;  acc[8] += gy * rot;  // :178-180
+            if constexpr (REP) {                                           // (a padding lane is no point: it adds nothing)
+                if (base + (int)threadIdx.x + u * BDIM < n) acc[9] += fun * fun;
+                cnt += ok[u] ? 1 : 0;
+            }
         }
     }
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -345,27 +369,29 @@ __device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, c
     K4_STAMP(1)                                                            // points: taps, interpolation, products
     // the nine trees step by step side by side (independent adds between the steps of one tree), then one store block
 #pragma unroll
-    for (int k = 0; k < 9; k++) acc[k] += hs_dpp_f32<0xB1, 0xf>(acc[k]);          // quad_perm [1,0,3,2]
+    for (int k = 0; k < NS; k++) acc[k] += hs_dpp_f32<0xB1, 0xf>(acc[k]);          // quad_perm [1,0,3,2]
 #pragma unroll
-    for (int k = 0; k < 9; k++) acc[k] += hs_dpp_f32<0x4E, 0xf>(acc[k]);          // quad_perm [2,3,0,1]
+    for (int k = 0; k < NS; k++) acc[k] += hs_dpp_f32<0x4E, 0xf>(acc[k]);          // quad_perm [2,3,0,1]
 #pragma unroll
-    for (int k = 0; k < 9; k++) acc[k] += hs_dpp_f32<0x124, 0xf>(acc[k]);         // row_ror:4
+    for (int k = 0; k < NS; k++) acc[k] += hs_dpp_f32<0x124, 0xf>(acc[k]);         // row_ror:4
 #pragma unroll
-    for (int k = 0; k < 9; k++) acc[k] += hs_dpp_f32<0x128, 0xf>(acc[k]);         // row_ror:8
+    for (int k = 0; k < NS; k++) acc[k] += hs_dpp_f32<0x128, 0xf>(acc[k]);         // row_ror:8
 #pragma unroll
-    for (int k = 0; k < 9; k++) acc[k] += hs_dpp_f32<0x142, 0xa>(acc[k]);         // row_bcast:15 -> rows 1, 3
+    for (int k = 0; k < NS; k++) acc[k] += hs_dpp_f32<0x142, 0xa>(acc[k]);         // row_bcast:15 -> rows 1, 3
 #pragma unroll
-    for (int k = 0; k < 9; k++) acc[k] += hs_dpp_f32<0x143, 0xc>(acc[k]);         // row_bcast:31 -> rows 2, 3
+    for (int k = 0; k < NS; k++) acc[k] += hs_dpp_f32<0x143, 0xc>(acc[k]);         // row_bcast:31 -> rows 2, 3
+    if constexpr (REP) cnt = sh_wave_scan_incl(cnt);                       // (lane 63: the wavefront's count)
     if (lane == 63) {
 #pragma unroll
-        for (int k = 0; k < 9; k++) red[k * NW + wid] = (double)acc[k];
+        for (int k = 0; k < NS; k++) red[k * NW + wid] = (double)acc[k];
+        if constexpr (REP) red[NS * NW + wid] = (double)cnt;
     }
     K4_STAMP(2)                                                            // wave sums + store
     __syncthreads();
     K4_STAMP(3)                                                            // the barrier
     // every wavefront: nine sums over the NW wave partials; value v = k * NW + w sits in lane v & 63 of register v >> 6, so a
     // sum is one aligned group of NW lanes of a DPP row; after the tree the group's first lane holds it
-    constexpr int NV = 9 * NW, NR = (NV + 63) >> 6;
+    constexpr int NV = NS * NW, NR = (NV + 63) >> 6;
     double d[NR];
 #pragma unroll
     for (int r = 0; r < NR; r++) d[r] = lane + 64 * r < NV ? red[lane + 64 * r] : 0.0;
@@ -383,6 +409,13 @@ __device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, c
 #pragma unroll
     for (int k = 0; k < 9; k++)
         sums[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f[(k * NW) >> 6]), (k * NW) & 63));
+    if constexpr (REP) {
+        *residual = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f[(9 * NW) >> 6]), (9 * NW) & 63));
+        int c = 0;
+#pragma unroll
+        for (int w = 0; w < NW; w++) c += (int)red[NS * NW + w];           // (integers below 2^31 in binary64: exact)
+        *n_in_map = c;
+    }
     K4_STAMP(4)                                                            // totals
 #ifdef K4_TIMES
     if (threadIdx.x == 0 && blockIdx.x == 0) g_k4_last = k4_last;          // (stamp 5: from here to the next iteration's start: the step, the level change)
@@ -398,21 +431,26 @@ __device__ static __forceinline__ void hs_hessian_block(const hs_level_dev &L, c
 // its partial carried in a register from window to window.  No binary64, no tree: the result depends on T alone, not on the
 // workgroup's width, so a batch of any size gives the single match's bits.
 #define HS_REF_MAX_T 64                    // ParallelWorker.Work waits with WaitHandle.WaitAll: at most 64 handles (BaseSLAM/ParallelWorker.cs:113-115)
-template <int BDIM> struct hs_ref_shape {
+// The match report (REP, slamhip_match_report) carries a tenth row of terms, funVal * funVal, whose chains give the residual in
+// the same chunk order (NR = 10 rows; a kernel that reports uses the ten-row block for its nine-row iterations too: one
+// allocation), and counts the points inside the map per lane, wavefront and workgroup in integers.
+template <int BDIM, int NR = 9> struct hs_ref_shape {
     static constexpr int W = BDIM * hs_shape<BDIM>::PU;                    // points per window (1080 rays: one window at any width)
     static constexpr int WS = W + 4;                                       // row stride in floats: rows 16-B aligned, and the nine rows
                                                                            // four banks apart (one chunk's nine chains: no conflict)
-    static constexpr int CR = (9 * HS_REF_MAX_T + BDIM - 1) / BDIM;        // chains per lane
+    static constexpr int CR = (NR * HS_REF_MAX_T + BDIM - 1) / BDIM;       // chains per lane
 };
-template <int BDIM> struct __attribute__((aligned(16))) hs_ref_lds {
-    float terms[9 * hs_ref_shape<BDIM>::WS];                               // 256 lanes: 46 KB -> 65 KB per workgroup, two per CU
-    float part[9 * HS_REF_MAX_T];                                          // [c][k] the chunks' partials
-    float sums[9];
+template <int N> struct hs_ref_cnt { int cnt[N]; };                       // (the report: the workgroup's count, then the wavefronts')
+template <> struct hs_ref_cnt<0> {};
+template <int BDIM, int NR = 9> struct __attribute__((aligned(16))) hs_ref_lds : hs_ref_cnt<NR == 9 ? 0 : 1 + hs_shape<BDIM>::NW> {
+    float terms[NR * hs_ref_shape<BDIM>::WS];                              // 256 lanes: 46 KB -> 65 KB per workgroup, two per CU (ten rows: 51 KB -> 70 KB, still two)
+    float part[NR * HS_REF_MAX_T];                                         // [c][k] the chunks' partials
+    float sums[NR];
 };
 // the kernel's one block (a static in a device function: one allocation per kernel that calls it, none in the default kernels)
-template <int BDIM> __device__ static __forceinline__ hs_ref_lds<BDIM> &hs_ref_lds_of()
+template <int BDIM, int NR = 9> __device__ static __forceinline__ hs_ref_lds<BDIM, NR> &hs_ref_lds_of()
 {
-    __shared__ hs_ref_lds<BDIM> s;
+    __shared__ hs_ref_lds<BDIM, NR> s;
     return s;
 }
 
@@ -450,36 +488,44 @@ __device__ static __forceinline__ float hs_chain(const float *row, int lo, int h
 
 // sums[9] in the order of hs_hessian_block, uniform in every thread; T in 1 .. HS_REF_MAX_T.  Barriers: one per window after the
 // terms are stored (and one before the store of every window after the first), two for the totals.
-template <int BDIM, bool RC>
+// REP: as hs_hessian_block's (S is then the ten-row block)
+template <int BDIM, bool RC, bool REP = false, int NRS = 9>
 __device__ static __forceinline__ void hs_hessian_ref(const hs_level_dev &L, const hs_cache_lv &C, const float2 *pts, int n, const float pose[3], int T,
-                                                      hs_ref_lds<BDIM> &S, float sums[9])
+                                                      hs_ref_lds<BDIM, NRS> &S, float sums[9], float *residual = nullptr, int *n_in_map = nullptr)
 {
-    constexpr int PU = hs_shape<BDIM>::PU, W = hs_ref_shape<BDIM>::W, WS = hs_ref_shape<BDIM>::WS, CR = hs_ref_shape<BDIM>::CR;
+    static_assert(!REP || NRS == 10, "the report's pass needs the ten-row block");
+    constexpr int NR = REP ? 10 : 9;                                       // rows of terms = chains per chunk
+    constexpr int PU = hs_shape<BDIM>::PU, W = hs_ref_shape<BDIM>::W, WS = hs_ref_shape<BDIM>::WS, CR = hs_ref_shape<BDIM, NR>::CR;
     const hs_iter_xf X = hs_iter_transform(L, pose);
     const int chunk = (n + T - 1) / T;                                     // :149
     const int tid = threadIdx.x;
     float part[CR];
 #pragma unroll
     for (int r = 0; r < CR; r++) part[r] = 0.0f;                           // :156-157
+    int cnt = 0;
     for (int base = 0; base < n; base += W) {
         hs_point q[PU];
 #pragma unroll
-        for (int u = 0; u < PU; u++) hs_point_taps<RC>(L, C, pts, base + tid + u * BDIM, n, X, q[u]);
-        float tm[PU][9];
+        for (int u = 0; u < PU; u++) hs_point_taps<RC, !REP>(L, C, pts, base + tid + u * BDIM, n, X, q[u]);
+        float tm[PU][NR];
 #pragma unroll
-        for (int u = 0; u < PU; u++) hs_point_terms(q[u], X, tm[u]);
+        for (int u = 0; u < PU; u++) hs_point_terms<NR>(q[u], X, tm[u]);
+        if constexpr (REP) {
+#pragma unroll
+            for (int u = 0; u < PU; u++) cnt += q[u].ok ? 1 : 0;
+        }
         if (base > 0) __syncthreads();                                     // (the previous window's chains have read their terms)
 #pragma unroll
         for (int u = 0; u < PU; u++)
 #pragma unroll
-            for (int k = 0; k < 9; k++) S.terms[k * WS + tid + u * BDIM] = tm[u][k];
+            for (int k = 0; k < NR; k++) S.terms[k * WS + tid + u * BDIM] = tm[u][k];
         __syncthreads();
         const int end = min(n, base + W);
 #pragma unroll
         for (int r = 0; r < CR; r++) {
             const int j = tid + r * BDIM;
-            if (j < 9 * T) {
-                const int c = j / 9, k = j - 9 * c;
+            if (j < NR * T) {
+                const int c = j / NR, k = j - NR * c;
                 const int lo = max(c * chunk, base), hi = min(min(c * chunk + chunk, n), end);   // :159 Skip / Take
                 if (lo < hi) part[r] = hs_chain(S.terms + k * WS, lo - base, hi - base, part[r]);   // :166-180
             }
@@ -488,17 +534,25 @@ __device__ static __forceinline__ void hs_hessian_ref(const hs_level_dev &L, con
 #pragma unroll
     for (int r = 0; r < CR; r++) {
         const int j = tid + r * BDIM;
-        if (j < 9 * T) S.part[j] = part[r];
+        if (j < NR * T) S.part[j] = part[r];
+    }
+    if constexpr (REP) {
+        cnt = sh_wave_scan_incl(cnt);                                      // (lane 63: the wavefront's count)
+        if ((tid & 63) == 63) S.cnt[1 + (tid >> 6)] = cnt;
     }
     __syncthreads();
-    if (tid < 9) {
+    if (tid < NR) {
         float s = 0.0f;                                                    // :188-189
-        for (int c = 0; c < T; c++) s += S.part[9 * c + tid];              // :191-195 (empty chunks: +0)
+        for (int c = 0; c < T; c++) s += S.part[NR * c + tid];             // :191-195 (empty chunks: +0)
         S.sums[tid] = s;
+    }
+    if constexpr (REP) {
+        if (tid == 64) { int c = 0; for (int w = 0; w < hs_shape<BDIM>::NW; w++) c += S.cnt[1 + w]; S.cnt[0] = c; }
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 9; k++) sums[k] = S.sums[k];
+    if constexpr (REP) { *residual = S.sums[9]; *n_in_map = S.cnt[0]; }
 }
 
 // EstimateTransformationLogLh (:93-125) applied by every thread identically (uniform registers)
@@ -523,14 +577,25 @@ __device__ static inline void hs_step(const float sums[9], float est[3])
 // REF: the reference's summation order for ref_threads = T chunks (hs_hessian_ref); the default instantiations ignore ref_threads.
 // RC: every tap through the reference's cache RCA (hs_cache_taps; the host launches no helper workgroups then); the default
 // instantiations ignore RCA.
-template <int BDIM, bool REF, bool RC>
+// REP: the match report (slamhip_match_report) -- after the level loop the workgroup evaluates GetCompleteHessianDerivs once more,
+// at the pose the match ends on and on the report level (level 0, or only_level), with the residual and the in-map count riding
+// through the same reduction (hs_hessian_block / hs_hessian_ref <REP>): one more pass over the points that are still in LDS, in
+// the same launch.  With RC its taps observe the cache and fill nothing: the reference makes no such evaluation, and a fill
+// would decide later answers across Reset.  Lane 0 stores the report to RP.out[b] -- for a single blocking match that is the
+// pyramid's pinned report block, stored before the mailbox's sequence word is released -- and, for slamhip_hs_match_best, puts
+// (bits(residual) << 32 | b) to a 64-bit minimum at agent scope: a residual is >= +0, so its bits order as its value does, a NaN
+// sorts after every number, equal residuals go to the lowest index (K1's packed key).  The default instantiations ignore RP.
+struct hs_report_arg { slamhip_match_report *out; unsigned long long *best_key; };
+template <int BDIM, bool REF, bool RC, bool REP>
 __global__ void __launch_bounds__(BDIM)
 k4_match(hs_levels_arg A, const float2 *__restrict__ pts, int n, const float *__restrict__ hints, float3 hint1,
          float *__restrict__ out, int only_level, int iters_override, uint32_t *mail, uint32_t mail_seq,
          const float2 *up_src, float2 *up_dst, uint32_t *up_flag, uint32_t up_seq, int n_helpers_from, int ref_threads,
-         hs_cache_arg RCA)
+         hs_cache_arg RCA, hs_report_arg RP)
 {
     __shared__ double red[2 * hs_shape<BDIM>::RED];
+    static_assert(2 * hs_shape<BDIM>::RED >= hs_shape<BDIM>::RED_REP, "the report's pass reuses the iterations' reduction blocks");
+    constexpr int NRS = REP ? 10 : 9;                                      // rows of the reference order's block (hs_ref_lds)
     __shared__ float2 pts_s[HS_LDS_PTS];
     const int b = blockIdx.x;
     if (n_helpers_from > 0 && b >= n_helpers_from) {
@@ -619,8 +684,8 @@ k4_match(hs_levels_arg A, const float2 *__restrict__ pts, int n, const float *__
             for (int it = 0; it < iters; it++) {                           // :70-73
                 float sums[9];
                 if constexpr (REF) {
-                    if (in_lds) hs_hessian_ref<BDIM, RC>(L, C, pts_s, n, est, ref_threads, hs_ref_lds_of<BDIM>(), sums);
-                    else hs_hessian_ref<BDIM, RC>(L, C, pts, n, est, ref_threads, hs_ref_lds_of<BDIM>(), sums);
+                    if (in_lds) hs_hessian_ref<BDIM, RC, false>(L, C, pts_s, n, est, ref_threads, hs_ref_lds_of<BDIM, NRS>(), sums);
+                    else hs_hessian_ref<BDIM, RC, false>(L, C, pts, n, est, ref_threads, hs_ref_lds_of<BDIM, NRS>(), sums);
                 } else {
                     if (in_lds) hs_hessian_block<BDIM, true, RC>(L, C, pts_s, n, est, red + par, sums);
                     else hs_hessian_block<BDIM, false, RC>(L, C, pts, n, est, red + par, sums);
@@ -631,6 +696,39 @@ k4_match(hs_levels_arg A, const float2 *__restrict__ pts, int n, const float *__
             est[2] = sh_normalize_angle(est[2]);                           // :76
             sh_v2_transform(est[0], est[1], L.world_t_map, &est_w[0], &est_w[1]);   // :79 GetWorldCoordsPose
             est_w[2] = est[2];
+        }
+    }
+    if constexpr (REP) {
+        const int rl = only_level >= 0 ? only_level : 0;
+        const hs_level_dev &L = A.lv[rl];
+        hs_cache_lv C = { nullptr, 0 };
+        if constexpr (RC) { C.c = RCA.c[rl]; C.epoch = RCA.epoch[rl]; }
+        float pm[3];
+        sh_v2_transform(est_w[0], est_w[1], L.map_t_world, &pm[0], &pm[1]);    // GetMapCoordsPose (GridMap.cs:133-137)
+        pm[2] = est_w[2];
+        float sums[9] = { 0, 0, 0, 0, 0, 0, 0, 0, 0 }, residual = 0.0f;
+        int n_in = 0;
+        if (n > 0) {
+            if constexpr (REF) {
+                if (in_lds) hs_hessian_ref<BDIM, RC, true>(L, C, pts_s, n, pm, ref_threads, hs_ref_lds_of<BDIM, NRS>(), sums, &residual, &n_in);
+                else hs_hessian_ref<BDIM, RC, true>(L, C, pts, n, pm, ref_threads, hs_ref_lds_of<BDIM, NRS>(), sums, &residual, &n_in);
+            } else {
+                __syncthreads();                                           // (every wavefront has read the last iteration's block)
+                if (in_lds) hs_hessian_block<BDIM, true, RC, true>(L, C, pts_s, n, pm, red, sums, &residual, &n_in);
+                else hs_hessian_block<BDIM, false, RC, true>(L, C, pts, n, pm, red, sums, &residual, &n_in);
+            }
+        }
+        if (threadIdx.x == 0) {
+            slamhip_match_report &R = RP.out[b];
+            R.pose_map[0] = pm[0]; R.pose_map[1] = pm[1]; R.pose_map[2] = pm[2];
+            R.H[0] = sums[3]; R.H[1] = sums[6]; R.H[2] = sums[7];          // :198-200, as k4_hessian lays it out
+            R.H[3] = sums[6]; R.H[4] = sums[4]; R.H[5] = sums[8];
+            R.H[6] = sums[7]; R.H[7] = sums[8]; R.H[8] = sums[5];
+            R.dTr[0] = sums[0]; R.dTr[1] = sums[1]; R.dTr[2] = sums[2];
+            R.residual = residual; R.n_in_map = n_in; R.n_points = n; R.level = rl;
+            if (RP.best_key)
+                __hip_atomic_fetch_min(RP.best_key, ((unsigned long long)__float_as_uint(residual) << 32) | (unsigned)b,
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     if (threadIdx.x == 0) {
@@ -659,6 +757,34 @@ k4_hessian(hs_levels_arg A, int level, const float2 *__restrict__ pts, int n, co
         out12[3] = sums[6]; out12[4] = sums[4]; out12[5] = sums[8];
         out12[6] = sums[7]; out12[7] = sums[8]; out12[8] = sums[5];
         out12[9] = sums[0]; out12[10] = sums[1]; out12[11] = sums[2];
+    }
+}
+
+// slamhip_hs_match_best: the winner of the batch that the launch in front of it matched -- the index in the key's low word (k4_match
+// <REP>) -- with its pose and report copied to where the host reads them: four words (pose, index) and the report's nineteen, then
+// the completion word if the call waits on the mailbox.  A launch of its own and not a last-arriving workgroup of the match: the
+// kernel boundary orders every workgroup's report before this read with no fence or counter in the matcher, at the price of one
+// launch boundary (~2 us) on a batch of B matches.  It also puts the key word back to "no candidate" for the next call, in-stream.
+#define HS_KEY_NONE 0xFFFFFFFFFFFFFFFFull
+__global__ void __launch_bounds__(64)
+k4_best_pick(unsigned long long *key, const float *__restrict__ poses, const slamhip_match_report *__restrict__ reps,
+             uint32_t *dst4, uint32_t *dst_report, uint32_t *mail, uint32_t mail_seq)
+{
+    const unsigned idx = (unsigned)*key;
+    const int t = threadIdx.x;
+    constexpr int RW = (int)(sizeof(slamhip_match_report) / 4);
+    // every lane's word into a register first, stores behind the barrier: the destinations may overlap the sources (without the
+    // mailbox the four words go to the head of the I/O block and the report to report 0)
+    uint32_t w = idx;
+    if (t < 3) w = __float_as_uint(poses[3 * (size_t)idx + t]);
+    else if (t >= 32 && t < 32 + RW) w = ((const uint32_t *)(reps + idx))[t - 32];
+    __syncthreads();
+    if (t < 4) dst4[t] = w;
+    else if (t >= 32 && t < 32 + RW) dst_report[t - 32] = w;
+    __syncthreads();                                                       // (one wavefront: every lane has read the key and stored its word)
+    if (t == 0) {
+        *key = HS_KEY_NONE;
+        if (mail) __hip_atomic_store(mail + 15, mail_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
 }
 
@@ -1350,6 +1476,8 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
     (void)hipFree(hs->d_k5_sec);
     (void)hipFree(hs->d_k5_byidx); (void)hipFree(hs->d_k5_cand); (void)hipFree(hs->d_k5_start); (void)hipFree(hs->d_k5_hdr);
     if (hs->h_io) (void)hipHostFree(hs->h_io);
+    (void)hipFree(hs->d_rep); (void)hipFree(hs->d_best_key);
+    if (hs->h_rep) (void)hipHostFree(hs->h_rep);
     free(hs);
     return SLAMHIP_OK;
 }
@@ -1620,25 +1748,52 @@ static int32_t ensure_io(slamhip_hs *hs, int floats)
     return SLAMHIP_OK;
 }
 
+// room for B reports (device and pinned) and the best-of-batch key word, which starts as "no candidate" by a memset on the stream
+static int32_t ensure_rep(slamhip_hs *hs, int B)
+{
+    if (!hs->d_best_key) {
+        SH_HIP(hipMalloc(&hs->d_best_key, sizeof(unsigned long long)));
+        SH_HIP(hipMemsetAsync(hs->d_best_key, 0xFF, sizeof(unsigned long long), hs->ctx->stream));
+    }
+    if (B <= hs->cap_rep) return SLAMHIP_OK;
+    SH_HIP(hipStreamSynchronize(hs->ctx->stream));
+    (void)hipFree(hs->d_rep);
+    if (hs->h_rep) (void)hipHostFree(hs->h_rep);
+    hs->d_rep = nullptr; hs->h_rep = nullptr; hs->cap_rep = 0;
+    const int cap = B < 64 ? 64 : B + B / 4;
+    SH_HIP(hipMalloc(&hs->d_rep, sizeof(slamhip_match_report) * (size_t)cap));
+    SH_HIP(hipHostMalloc(&hs->h_rep, sizeof(slamhip_match_report) * (size_t)cap, hipHostMallocMapped | hipHostMallocCoherent));
+    hs->cap_rep = cap;
+    return SLAMHIP_OK;
+}
+
+// what a match is to report (run_match): out_reports -- B reports, or the winner's alone with best_index set (slamhip_hs_match_best:
+// `out` is then the winner's pose)
+struct hs_report_req { slamhip_match_report *out_reports; int32_t *best_index; };
+
 // defer_seq: (single match through the mailbox only) return after the launch with the completion number in *defer_seq -- the
 // caller holds the mailbox lock, enqueues what it wants behind the match and then calls match_collect
-static int32_t match_collect(slamhip_hs *hs, uint32_t seq, float *out)
+static int32_t match_collect(slamhip_hs *hs, uint32_t seq, float *out, slamhip_match_report *out_report = nullptr)
 {
     slamhip_ctx *ctx = hs->ctx;
     SH_TRY(sh_flag_wait(ctx, ctx->mailbox + 15, seq));
     const volatile float *m = (const volatile float *)ctx->mailbox;
     out[0] = m[0]; out[1] = m[1]; out[2] = m[2];
+    if (out_report) memcpy(out_report, hs->h_rep, sizeof(*out_report));    // (stored in front of the sequence word: k4_match <REP>)
     hs->launch_done = hs->match_launch_no;                                 // (the match has delivered: every launch before it has finished)
     return SLAMHIP_OK;
 }
-static int32_t run_match(slamhip_hs *hs, const float *hints, int B, float *out, int only_level, int iters, uint32_t *defer_seq = nullptr)
+static int32_t run_match(slamhip_hs *hs, const float *hints, int B, float *out, int only_level, int iters, uint32_t *defer_seq = nullptr,
+                         const hs_report_req *rq = nullptr)
 {
     SH_HIP(hipSetDevice(hs->ctx->device));
     slamhip_ctx *ctx = hs->ctx;
     sh_mail_guard lock(ctx);                                              // (the mailbox is the context's: common.h)
     SH_TRY(ensure_io(hs, 6 * B));
+    if (rq) SH_TRY(ensure_rep(hs, B));
+    const bool best = rq && rq->best_index;                               // (its result is delivered by k4_best_pick, not by the match)
     float *d_in = hs->d_io, *d_out = hs->d_io + 3 * (size_t)B;
-    const bool mail1 = B == 1 && !ctx->mail_off;                          // one match: the kernel itself delivers the pose to the host
+    const bool mail1 = B == 1 && !ctx->mail_off && !best;                 // one match: the kernel itself delivers the pose to the host
     // ... and pulls a freshly set scan from the staging block itself (k4_match): no upload launch in the per-scan chain
     const bool pull = B == 1 && hs->upload_pending && hs->n_points > 0 && hs->n_points <= HS_LDS_PTS;
     const float2 *up_src = nullptr; float2 *up_dst = nullptr; uint32_t *up_flag = nullptr; uint32_t up_seq = 0;
@@ -1670,9 +1825,12 @@ static int32_t run_match(slamhip_hs *hs, const float *hints, int B, float *out, 
         const bool rc = hs->ref_cache != 0;
         const int helpers = !rc && B == 1 && only_level < 0 && hs->n_levels > 1 && hs->n_points > 0 && helpers_env > 0 ? 8 * helpers_env : 0;
         const int T = hs->match_threads;
-#define K4_LAUNCH(BD, REF, RC) hipLaunchKernelGGL((k4_match<BD, REF, RC>), dim3(B + helpers), dim3(BD), 0, ctx->stream, levels_arg(hs), hs->d_pts, hs->n_points, d_hints, \
-                                                  h1, d_out, only_level, iters, mb, mail_seq, up_src, up_dst, up_flag, up_seq, helpers ? B : 0, T, cache_arg(hs))
-#define K4_WIDTHS(REF, RC) { if (lanes == 512) K4_LAUNCH(512, REF, RC); else K4_LAUNCH(256, REF, RC); }
+        // (the report of a single blocking match goes straight to the pinned block; a batch's stay on the device until they are asked for)
+        hs_report_arg RP = { rq ? (mail1 ? hs->h_rep : hs->d_rep) : (slamhip_match_report *)nullptr, best ? hs->d_best_key : (unsigned long long *)nullptr };
+#define K4_LAUNCH(BD, REF, RC, REP) hipLaunchKernelGGL((k4_match<BD, REF, RC, REP>), dim3(B + helpers), dim3(BD), 0, ctx->stream, levels_arg(hs), hs->d_pts, hs->n_points, d_hints, \
+                                                  h1, d_out, only_level, iters, mb, mail_seq, up_src, up_dst, up_flag, up_seq, helpers ? B : 0, T, cache_arg(hs), RP)
+#define K4_WIDTHS(REF, RC) { if (!rq) { if (lanes == 512) K4_LAUNCH(512, REF, RC, false); else K4_LAUNCH(256, REF, RC, false); } \
+                             else { if (lanes == 512) K4_LAUNCH(512, REF, RC, true); else K4_LAUNCH(256, REF, RC, true); } }
         if (T == 0) {
             if (!rc) K4_WIDTHS(false, false)
             else K4_WIDTHS(false, true)
@@ -1706,13 +1864,40 @@ static int32_t run_match(slamhip_hs *hs, const float *hints, int B, float *out, 
         }
     }
 #endif
-    if (mail1) {
+    if (mail1 && !best) {
         if (defer_seq) { *defer_seq = mail_seq; return SLAMHIP_OK; }
-        return match_collect(hs, mail_seq, out);
+        return match_collect(hs, mail_seq, out, rq ? rq->out_reports : nullptr);
+    }
+    if (best) {
+        // only the winner travels: k4_best_pick copies its pose, index and report out -- to the mailbox and the pinned report block,
+        // with one wait on the sequence word, or (SLAMHIP_NO_HOSTWAIT) to device memory for a copy and a synchronise
+        uint32_t *d4 = (uint32_t *)hs->d_io, *d19 = (uint32_t *)hs->d_rep;     // (the hints have been read; report 0 is copied in place when it wins)
+        const uint32_t seq = ctx->mail_off ? 0 : sh_mail_seq_next(ctx);
+        hipLaunchKernelGGL(k4_best_pick, dim3(1), dim3(64), 0, ctx->stream, hs->d_best_key, (const float *)d_out, (const slamhip_match_report *)hs->d_rep,
+                           ctx->mail_off ? d4 : ctx->mailbox, ctx->mail_off ? d19 : (uint32_t *)hs->h_rep, ctx->mail_off ? (uint32_t *)nullptr : ctx->mailbox, seq);
+        SH_HIP(hipGetLastError());
+        uint32_t w[4];
+        if (!ctx->mail_off) {
+            SH_TRY(sh_flag_wait(ctx, ctx->mailbox + 15, seq));
+            const volatile uint32_t *m = ctx->mailbox;
+            for (int k = 0; k < 4; k++) w[k] = m[k];
+            hs->launch_done = hs->match_launch_no;
+        } else {
+            SH_HIP(hipMemcpyAsync(hs->h_io, d4, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
+            SH_HIP(hipMemcpyAsync(hs->h_rep, d19, sizeof(slamhip_match_report), hipMemcpyDeviceToHost, ctx->stream));
+            SH_HIP(hipStreamSynchronize(ctx->stream));
+            memcpy(w, hs->h_io, sizeof(w));
+        }
+        memcpy(out, w, sizeof(float) * 3);
+        *rq->best_index = (int32_t)w[3];
+        memcpy(rq->out_reports, hs->h_rep, sizeof(slamhip_match_report));
+        return SLAMHIP_OK;
     }
     SH_HIP(hipMemcpyAsync(hs->h_io + 3 * (size_t)B, d_out, sizeof(float) * 3 * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+    if (rq) SH_HIP(hipMemcpyAsync(hs->h_rep, hs->d_rep, sizeof(slamhip_match_report) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
     SH_HIP(hipStreamSynchronize(ctx->stream));
     memcpy(out, hs->h_io + 3 * (size_t)B, sizeof(float) * 3 * (size_t)B);
+    if (rq) memcpy(rq->out_reports, hs->h_rep, sizeof(slamhip_match_report) * (size_t)B);
     return SLAMHIP_OK;
 }
 
@@ -1768,6 +1953,36 @@ extern "C" int32_t slamhip_hs_match_batch(slamhip_hs *hs, const float *hints, in
 {
     SH_CHECK_ARG(hs && hints && out && B > 0);
     return run_match(hs, hints, B, out, -1, 0);
+}
+
+extern "C" int32_t slamhip_hs_match_report(slamhip_hs *hs, const float hint[3], float out[3], slamhip_match_report *out_report)
+{
+    SH_CHECK_ARG(hs && hint && out && out_report);
+    const hs_report_req rq = { out_report, nullptr };
+    return run_match(hs, hint, 1, out, -1, 0, nullptr, &rq);
+}
+
+extern "C" int32_t slamhip_hs_match_level_report(slamhip_hs *hs, int32_t level, const float hint[3], int32_t iterations, float out[3],
+                                                 slamhip_match_report *out_report)
+{
+    SH_CHECK_ARG(hs && hint && out && out_report && level >= 0 && level < hs->n_levels && iterations >= 0);
+    const hs_report_req rq = { out_report, nullptr };
+    return run_match(hs, hint, 1, out, level, iterations, nullptr, &rq);
+}
+
+extern "C" int32_t slamhip_hs_match_batch_report(slamhip_hs *hs, const float *hints, int32_t B, float *out, slamhip_match_report *out_reports)
+{
+    SH_CHECK_ARG(hs && hints && out && out_reports && B > 0);
+    const hs_report_req rq = { out_reports, nullptr };
+    return run_match(hs, hints, B, out, -1, 0, nullptr, &rq);
+}
+
+extern "C" int32_t slamhip_hs_match_best(slamhip_hs *hs, const float *hints, int32_t B, float out[3], int32_t *out_index,
+                                         slamhip_match_report *out_report)
+{
+    SH_CHECK_ARG(hs && hints && out && out_index && out_report && B > 0);
+    const hs_report_req rq = { out_report, out_index };
+    return run_match(hs, hints, B, out, -1, 0, nullptr, &rq);
 }
 
 extern "C" int32_t slamhip_hs_hessian(slamhip_hs *hs, int32_t level, const float pose_map[3], float H[9], float dTr[3])
@@ -1964,6 +2179,8 @@ struct slamhip_hsproc {
     float match_timing, update_timing;
     float min_dist, min_angle;
     unsigned upd_hist;                                     // the last scans' update decisions, newest in bit 0
+    int want_report, report_valid;                         // slamhip_hsproc_set_match_report; the last Update's match left `report`
+    slamhip_match_report report;
 };
 
 static const float F_MIN = -3.40282347e+38f;       // float.MinValue
@@ -2000,6 +2217,7 @@ extern "C" int32_t slamhip_hsproc_reset(slamhip_hsproc *p)
     memcpy(p->match_pose, p->start_pose, sizeof(float) * 3);              // :136
     p->last_update_pose[0] = p->last_update_pose[1] = p->last_update_pose[2] = F_MIN;   // :137
     p->upd_hist = 0;
+    p->report_valid = 0;
     return SLAMHIP_OK;
 }
 
@@ -2007,6 +2225,8 @@ extern "C" int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int
                                          const float hint[3], int32_t map_without_matching, int32_t *out_updated)
 {
     SH_CHECK_ARG(p && hint);
+    p->report_valid = 0;
+    const hs_report_req rq = { &p->report, nullptr };
     SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
     static const bool wait_update = sh_env_set("SLAMHIP_HS_WAIT_UPDATE");
     // (worth it when the update does take place: a gated launch that returns at once still costs the stream ~15 us -- 512 workgroups
@@ -2020,7 +2240,7 @@ extern "C" int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int
         auto t0 = std::chrono::steady_clock::now();
         float m[3];
         uint32_t seq = 0;
-        SH_TRY(run_match(hs, hint, 1, m, -1, 0, &seq));                   // :93
+        SH_TRY(run_match(hs, hint, 1, m, -1, 0, &seq, p->want_report ? &rq : nullptr));   // :93
         k5_gate g;
         memset(&g, 0, sizeof(g));
         g.d_pose = hs->d_io + 3;                                          // (the single match's result in device memory: run_match)
@@ -2028,8 +2248,9 @@ extern "C" int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int
         g.min_dist = p->min_dist; g.min_angle = p->min_angle;
         const int32_t rc_u = hs_update_enqueue(hs, hint, &g);
         auto t1 = std::chrono::steady_clock::now();
-        SH_TRY(match_collect(hs, seq, m));
+        SH_TRY(match_collect(hs, seq, m, p->want_report ? &p->report : nullptr));
         SH_TRY(rc_u);
+        p->report_valid = p->want_report;
         memcpy(p->match_pose, m, sizeof(m));
         auto t2 = std::chrono::steady_clock::now();
         const float ms_u = std::chrono::duration<float, std::milli>(t1 - t0).count();      // (launches of match + update; the match's share is a few us)
@@ -2049,7 +2270,8 @@ extern "C" int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int
     if (!map_without_matching) {                                          // :89
         auto t0 = std::chrono::steady_clock::now();
         float m[3];
-        SH_TRY(slamhip_hs_match(p->hs, hint, m));                         // :93
+        SH_TRY(run_match(p->hs, hint, 1, m, -1, 0, nullptr, p->want_report ? &rq : nullptr));   // :93
+        p->report_valid = p->want_report;
         memcpy(p->match_pose, m, sizeof(m));
         const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         p->match_timing = (3.0f * p->match_timing + ms) / 4.0f;           // :96
@@ -2082,6 +2304,23 @@ extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], fl
     if (last) memcpy(last, p->last_update_pose, sizeof(float) * 3);
     if (mt) *mt = p->match_timing;
     if (ut) *ut = p->update_timing;
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_set_match_report(slamhip_hsproc *p, int32_t on)
+{
+    SH_CHECK_ARG(p && (on == 0 || on == 1));
+    p->want_report = on;                                                  // (read by the next slamhip_hsproc_update)
+    if (!on) p->report_valid = 0;
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_get_report(slamhip_hsproc *p, slamhip_match_report *out, int32_t *out_valid)
+{
+    SH_CHECK_ARG(p && out && out_valid);
+    *out_valid = p->report_valid;
+    if (p->report_valid) *out = p->report;
+    else memset(out, 0, sizeof(*out));
     return SLAMHIP_OK;
 }
 

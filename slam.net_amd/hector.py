@@ -11,6 +11,25 @@ from . import capi
 from .coreslam import Context
 
 
+def hint_lattice(centre, half_xy, step_xy, half_theta, step_theta):
+    """The (B, 3) float32 hint list of a relocalisation around `centre` = (x, y, theta): every combination of
+    x, y in centre +- k * step_xy (k * step_xy <= half_xy) and theta in centre +- j * step_theta (j * step_theta <=
+    half_theta), B = (2 * floor(half_xy / step_xy) + 1)^2 * (2 * floor(half_theta / step_theta) + 1).  The centre itself
+    comes first (ties in ScanMatcher.MatchDataBest go to the lowest index); the rest follow in x-major, then y, then
+    theta order.  Offsets are formed in binary64 and rounded once to binary32.  Pure host code."""
+    c = np.asarray(centre, np.float64).reshape(3)
+    if not (step_xy > 0 and step_theta > 0 and half_xy >= 0 and half_theta >= 0):
+        raise ValueError("hint_lattice: steps must be positive and half-widths non-negative")
+    nxy = int(np.floor(half_xy / step_xy + 1e-9)); nth = int(np.floor(half_theta / step_theta + 1e-9))
+    out = [c]
+    for i in range(-nxy, nxy + 1):
+        for j in range(-nxy, nxy + 1):
+            for k in range(-nth, nth + 1):
+                if i or j or k:
+                    out.append(c + np.array([i * step_xy, j * step_xy, k * step_theta]))
+    return np.asarray(out, np.float64).astype(np.float32)
+
+
 class ScanCloud:
     """BaseSLAM/ScanCloud.cs:10-21"""
 
@@ -169,6 +188,37 @@ class ScanMatcher:
                       target.EstimateIterations, capi.fptr(out))
         return out
 
+    def MatchDataReport(self, target, scan, hintPose):
+        """MatchData and the match report (slamhip_match_report, a capi.REPORT_DTYPE record): -> (pose, report)."""
+        hint = capi.f32(hintPose); out = np.empty(3, np.float32); rep = np.zeros(1, capi.REPORT_DTYPE)
+        self._order(target if isinstance(target, MapRepMultiMap) else target._rep)
+        if isinstance(target, MapRepMultiMap):
+            target.set_scan(scan)
+            capi.call("slamhip_hs_match_report", target._h, capi.fptr(hint), capi.fptr(out), capi.rptr(rep))
+        else:
+            target._rep.set_scan(scan)
+            capi.call("slamhip_hs_match_level_report", target._rep._h, target.level, capi.fptr(hint),
+                      target.EstimateIterations, capi.fptr(out), capi.rptr(rep))
+        return out, rep[0]
+
+    def MatchDataBatchReport(self, rep, scan, hintPoses):
+        """MatchDataBatch and every match's report: -> (poses (B, 3), reports (B,) of capi.REPORT_DTYPE)."""
+        hints = capi.f32(hintPoses, (-1, 3)); out = np.empty_like(hints); reps = np.zeros(hints.shape[0], capi.REPORT_DTYPE)
+        self._order(rep)
+        rep.set_scan(scan)
+        capi.call("slamhip_hs_match_batch_report", rep._h, capi.fptr(hints), hints.shape[0], capi.fptr(out), capi.rptr(reps))
+        return out, reps
+
+    def MatchDataBest(self, rep, scan, hintPoses):
+        """The best of B hints, picked on the device by the smallest residual, ties to the lowest index
+        (slamhip_hs_match_best): -> (pose, index, report).  Whether that residual is good enough is the caller's call."""
+        hints = capi.f32(hintPoses, (-1, 3)); out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE)
+        idx = C.c_int32(-1)
+        self._order(rep)
+        rep.set_scan(scan)
+        capi.call("slamhip_hs_match_best", rep._h, capi.fptr(hints), hints.shape[0], capi.fptr(out), C.byref(idx), capi.rptr(r))
+        return out, int(idx.value), r[0]
+
     def MatchDataBatch(self, rep, scan, hintPoses):
         hints = capi.f32(hintPoses, (-1, 3)); out = np.empty_like(hints)
         self._order(rep)
@@ -184,7 +234,7 @@ class HectorSLAMProcessor:
     """HectorSLAM/Main/HectorSLAMProcessor.cs:17-160"""
 
     def __init__(self, mapResolution, mapSize, startPose, numDepth, numThreads=1, logger=None, ctx=None,
-                 referenceSummation=False, referenceCache=False):
+                 referenceSummation=False, referenceCache=False, matchReport=False):
         self._own_ctx = ctx is None
         self.ctx = ctx or Context(0)
         sp = capi.f32(startPose)
@@ -198,6 +248,8 @@ class HectorSLAMProcessor:
             self.MapRep.set_match_threads(numThreads)
         if referenceCache:                                          # OccGridMap's cacheArray, stale across Reset (deviation D5)
             self.MapRep.set_reference_cache(1)
+        if matchReport:                                             # every Update's match leaves its report (LastMatchReport)
+            capi.call("slamhip_hsproc_set_match_report", self._h, 1)
         self._min_dist, self._min_angle = 0.3, 0.13
 
     def _get(self):
@@ -209,6 +261,14 @@ class HectorSLAMProcessor:
     LastMapUpdatePose = property(lambda self: self._get()[1])
     MatchTiming = property(lambda self: self._get()[2])
     UpdateTiming = property(lambda self: self._get()[3])
+
+    @property
+    def LastMatchReport(self):
+        """The report of the last Update's match (a capi.REPORT_DTYPE record), or None: before the first match, after
+        Reset, after an Update with mapWithoutMatching, and when the processor was made without matchReport."""
+        r = np.zeros(1, capi.REPORT_DTYPE); valid = C.c_int32()
+        capi.call("slamhip_hsproc_get_report", self._h, capi.rptr(r), C.byref(valid))
+        return r[0] if valid.value else None
 
     @property
     def MinDistanceDiffForMapUpdate(self):

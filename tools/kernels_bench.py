@@ -1,8 +1,10 @@
 """Secondary-kernel timings (K2 HoleMap update, K3 ObstacleMap update, K4 Hector match, K5 Hector grid update,
 fused search+update) on one MI355X, with the algorithmic byte counts of SURVEY.md sec.8d, and the Hector matcher in the
 reference's summation order (ScanMatcher(T, referenceSummation=True), T = 1, 4, 16, beside the default order) and through
-the reference's probability cache (T = 0 and 1, beside the default).  Prints one JSON object.  --hector-only: the Hector
-part alone."""
+the reference's probability cache (T = 0 and 1, beside the default), and with the match report (slamhip_match_report) on and
+off: single match, batches of 256 and 4096, HectorSLAMProcessor.Update, and match_best beside match_batch.  Prints one JSON
+object.  --hector-only: the Hector part alone.  (SLAMHIP_LIB names another build of the library for an A/B on one box; rows that
+need entry points it lacks are left out.)"""
 import json, math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -124,5 +126,49 @@ out["k4_hector_match_refsum_3lvl_2048"] = {"T%d" % T: match_rows(T) for T in (0,
 # it filled.  In the processor's flow every update starts a new epoch, so the first iteration on every level fills.)
 out["k4_hector_match_refcache_3lvl_2048"] = {"T%d_%s" % (T, "refcache" if rc else "default"): match_rows(T, rc)
                                               for T in (0, 1) for rc in (False, True)}
+
+
+# the match report: blocking-call wall time (what a host sees), median of 5 batches of calls, default order and cache off
+def wall_us(fn, calls, batches=5):
+    fn(); ctx.synchronize()
+    ts = []
+    for _ in range(batches):
+        t0 = time.perf_counter()
+        for _ in range(calls): fn()
+        ts.append((time.perf_counter() - t0) / calls)
+    return sorted(ts)[batches // 2] * 1e6
+
+
+def proc_update_us(report):
+    kw = {"matchReport": True} if report else {}
+    proc = hs.HectorSLAMProcessor(40.0 / 2048, (2048, 2048), scans[0][1], 3, 1, ctx=ctx, **kw)
+    rng = sim.PCG32(77)
+    pscans = [hs.ScanCloud(sim.make_scan(segs, np.array([20 + 0.03 * i, 20 + 0.01 * i, 0.004 * i], np.float32), 1080, rng)[1])
+              for i in range(40)]
+    for i in range(10): proc.Update(pscans[i], proc.MatchPose, True)
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    for i in range(10, 40): proc.Update(pscans[i], proc.MatchPose, False)
+    ctx.synchronize()
+    upd = (time.perf_counter() - t0) / 30
+    proc.Dispose()
+    return upd * 1e6
+
+
 rep.set_match_threads(0)
+have_report = hasattr(capi.lib(), "slamhip_hs_match_report")
+m0 = hs.ScanMatcher(1)
+rows = {"single_us": {"off": wall_us(lambda: m0.MatchData(rep, scan, hint), 200)},
+        "processor_update_us": {"off": sorted(proc_update_us(False) for _ in range(3))[1]}}
+if have_report:
+    rows["single_us"]["on"] = wall_us(lambda: m0.MatchDataReport(rep, scan, hint), 200)
+    rows["processor_update_us"]["on"] = sorted(proc_update_us(True) for _ in range(3))[1]
+for Bn in (256, 4096):
+    hb = hints[:Bn].copy()
+    r = {"off": wall_us(lambda: m0.MatchDataBatch(rep, scan, hb), 20 if Bn == 256 else 5)}
+    if have_report:
+        r["on"] = wall_us(lambda: m0.MatchDataBatchReport(rep, scan, hb), 20 if Bn == 256 else 5)
+        r["match_best"] = wall_us(lambda: m0.MatchDataBest(rep, scan, hb), 20 if Bn == 256 else 5)
+    rows["batch%d_us" % Bn] = r
+out["k4_hector_match_report_3lvl_2048"] = rows
 print(json.dumps(out, indent=1))
