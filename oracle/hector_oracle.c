@@ -132,6 +132,8 @@ struct oracle_grid {
     /* the literal cache of OccGridMap.cs:16-19,38-42,97-107 -- kept ONLY for oracle_grid_prob_literal (deviation D5, below);
      * nothing else in the oracle reads it */
     float *cache_val; int *cache_idx; int curr_cache_index;
+    /* test hook (oracle_grid_set_prob_table): while set, oracle_grid_prob reads this table of w*h values; the caller owns it */
+    const float *prob_table;
 };
 
 static float scale_to_map(const oracle_grid *g) { return 1.0f / g->cell_len; } /* MapProperties.cs:32 */
@@ -191,9 +193,17 @@ int oracle_grid_h(const oracle_grid *g) { return g->h; }
  * literally so that tests/test_oracle_kat.py can SHOW the reference's behaviour next to the chosen one. */
 float oracle_grid_prob(oracle_grid *g, int index)
 {
+    if (g->prob_table) return g->prob_table[index];         /* test hook: somebody else's expf, see oracle.h */
     float odds = expf(g->cells[index].value);               /* :101 */
     return odds / (odds + 1.0f);                            /* :102 */
 }
+/* Test hook, not reference behaviour: while `table` (w*h binary32 values, owned by the caller, who keeps it alive and unchanged)
+ * is installed, oracle_grid_prob -- the single funnel of oracle_hs_interp's four taps -- returns table[index] in place of the
+ * expression of :101-102; NULL restores it.  With another implementation's probability grid installed (whose expf may differ
+ * from libm's in the last place) everything downstream of the taps is the same binary32 arithmetic on the same inputs.
+ * oracle_grid_prob_literal (D5) does not look at the table. */
+void oracle_grid_set_prob_table(oracle_grid *g, const float *table) { g->prob_table = table; }
+
 /* OccGridMap.cs:97-107 literally, cache and all (D5: used by no product path and no other oracle function) */
 float oracle_grid_prob_literal(oracle_grid *g, int index)
 {

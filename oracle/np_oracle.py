@@ -377,8 +377,22 @@ class NpGrid:
         self.lo_occ = F(math.log(float(F(F(0.9) / F(F(1.0) - F(0.9))))))    # :47
         self.map_t_world = M32.scale(self.stm) * M32.translation(0, 0)  # GridMap.cs:46
         self.world_t_map = self.map_t_world.invert()
+        self.prob_table = None
+
+    def set_prob_table(self, table):
+        """Test hook (as oracle_c.Grid.set_prob_table): while a table of w*h binary32 values is installed prob() returns
+        table[idx]; None restores the expression.  The table is copied."""
+        if table is None:
+            self.prob_table = None
+            return
+        t = np.array(table, dtype=np.float32).ravel()
+        if t.size != self.w * self.h:
+            raise ValueError("probability table of %d values for a grid of %d cells" % (t.size, self.w * self.h))
+        self.prob_table = t
 
     def prob(self, idx):                                                # OccGridMap.cs:97-107
+        if self.prob_table is not None:
+            return self.prob_table[idx]
         odds = np.exp(self.value[idx].astype(np.float64)).astype(np.float32)
         return (odds / (odds + F(1.0))).astype(np.float32)
 
@@ -440,7 +454,9 @@ class NpGrid:
         z = F(0)
         return np.where(oob, z, P), np.where(oob, z, gx), np.where(oob, z, gy)
 
-    def hessian(self, xy, pose, n_threads=1):                           # ScanMatcher.cs:135-204
+    def hessian_terms(self, xy, pose):                                  # ScanMatcher.cs:139-180
+        """The per-point binary32 terms GetCompleteHessianDerivs sums, (9, n) in the order dTr.x, dTr.y, dTr.z, H11, H22, H33,
+        H12, H13, H23, and the interpolated map value M of every point (n,)."""
         xy = np.asarray(xy, np.float32).reshape(-1, 2)
         t = M32.rotation(pose[2], self.trig) * M32.translation(F(pose[0]) * self.cell, F(pose[1]) * self.cell) \
             * M32.scale(self.stm)
@@ -454,7 +470,13 @@ class NpGrid:
         P, gx, gy = self.interp(mx, my)
         fun = F(1.0) - P
         rot = ((-sinRot * X - cosRot * Y) * gx + (cosRot * X - sinRot * Y) * gy)
-        terms = np.stack([gx * fun, gy * fun, rot * fun, gx * gx, gy * gy, rot * rot, gx * gy, gx * rot, gy * rot])
+        with np.errstate(invalid="ignore", over="ignore"):
+            terms = np.stack([gx * fun, gy * fun, rot * fun, gx * gx, gy * gy, rot * rot, gx * gy, gx * rot, gy * rot])
+        return terms.astype(np.float32).reshape(9, -1), np.asarray(P, np.float32)
+
+    def hessian(self, xy, pose, n_threads=1):                           # ScanMatcher.cs:135-204
+        xy = np.asarray(xy, np.float32).reshape(-1, 2)
+        terms, _ = self.hessian_terms(xy, pose)
         n = xy.shape[0]
         chunk = (n + n_threads - 1) // n_threads
         tot = np.zeros(9, np.float32)

@@ -95,6 +95,7 @@ def _declare(L):
     L.oracle_grid_w.argtypes = [vp]; L.oracle_grid_w.restype = C.c_int
     L.oracle_grid_h.argtypes = [vp]; L.oracle_grid_h.restype = C.c_int
     L.oracle_grid_prob.argtypes = [vp, C.c_int]; L.oracle_grid_prob.restype = f
+    L.oracle_grid_set_prob_table.argtypes = [vp, fp]
     L.oracle_grid_prob_literal.argtypes = [vp, C.c_int]; L.oracle_grid_prob_literal.restype = f
     L.oracle_grid_map_pose.argtypes = [vp, fp, fp]
     L.oracle_grid_world_pose.argtypes = [vp, fp, fp]
@@ -302,10 +303,12 @@ class Grid:
         self._h = lib().oracle_grid_create(C.c_float(cell_len), w, h, C.c_float(off[0]), C.c_float(off[1]))
         if not self._h:
             raise RuntimeError("Map to world matrix is not invertible")
+        self._prob_table = None
 
     def close(self):
         if self._h:
             lib().oracle_grid_destroy(self._h); self._h = None
+        self._prob_table = None
 
     def __del__(self):
         try:
@@ -333,6 +336,21 @@ class Grid:
 
     def prob(self, index):
         return lib().oracle_grid_prob(self._h, int(index))
+
+    def set_prob_table(self, table):
+        """Test hook: while a table of w*h binary32 probabilities is installed, prob() -- and with it every tap of interp,
+        hessian, estimate_step and match -- returns table[index] in place of expf(value) / (expf(value) + 1); None restores
+        the expression.  The table is copied here (a snapshot: later changes of the cells or of the caller's array do not
+        show); prob_literal (D5) is not affected."""
+        if table is None:
+            lib().oracle_grid_set_prob_table(self._h, None)
+            self._prob_table = None
+            return
+        t = np.array(table, dtype=np.float32, order="C").ravel()
+        if t.size != self.w * self.h:
+            raise ValueError("probability table of %d values for a grid of %d cells" % (t.size, self.w * self.h))
+        lib().oracle_grid_set_prob_table(self._h, _p(t, C.c_float))
+        self._prob_table = t                                    # (the C side borrows it)
 
     def prob_literal(self, index):
         """OccGridMap.cs:97-107 with the C# cache restated literally (deviation D5: stale across Reset)"""

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Randomised parity soak (GPU + CPU oracle): random map sizes, poses (also at and beyond the map edge), ray counts, hole
 widths, candidate lists and Hector pyramids; every integer output must equal the oracle's bit for bit, Hector match poses
-within 1e-4.  Prints one line per case and a summary; exit code 1 on the first mismatch.
+within 1e-4 in the device's own summation order, and bit for bit in the reference's order (a random numThreads, the device's
+probabilities installed in the oracle: every Hector case, directly).  Prints one line per case and a summary; exit code 1 on
+the first mismatch.
 
     python tests/fuzz_parity.py [--seconds 120 --seed 1]
 """
@@ -28,8 +30,13 @@ def main():
     import slam.net_amd.coreslam as cs
     import slam.net_amd.hector as hs
     import slam.net_amd.sim as sim
+    from test_gpu_hector_refsum import same_bits
+    from test_gpu_hector_report import chunk_sum, in_map, residual_terms, transform_points
+    import np_oracle as npo
     oc.set_trig_mode(oc.TRIG_DET)
     rng = np.random.default_rng(a.seed)
+    rng_ref = np.random.default_rng([a.seed, 0x4b34])        # the reference-order comparison's own draws: the cases above stay the cases they were
+    n_ref = 0
     segs = sim.default_field()
     ctx = cs.Context(0)
     t_end = time.time() + a.seconds
@@ -298,6 +305,50 @@ def main():
                         n_near += 1
             ok = ok and batch_same
             desc = "hector side %d levels %d rays %d pose %s" % (side, levels, R, np.round(pose, 2))
+            # The reference's summation order, compared directly: the device's probability grids installed in the oracle (the one
+            # legitimate difference, whose expf, is tests/test_gpu_hector_rawparity.py's), a random numThreads, with probability
+            # 0.3 the reference's cache -- then the device and the oracle perform the same binary32 operations, and the single
+            # match, its report and both batch kernels must give the oracle's bits (NaN equal to NaN).  Every case with a scan:
+            # few rays and runaway matches included; no neighbourhood, no envelope.  (After the default-order comparison, whose
+            # oracle calls read libm's probabilities as they always did.)
+            if xy.shape[0] > 0:
+                for l in range(levels):
+                    wl, hl = rep.Maps[l].Dimensions
+                    ref[l].set_prob_table(rep.Maps[l].GetCachedProbability(np.arange(wl * hl, dtype=np.int32)))
+                T = int(rng_ref.choice([1, 2, 3, 4, 5, 7, 8, 13, 16, 31, 64]))
+                rc = bool(rng_ref.random() < 0.3)
+                if rc:
+                    rep.set_reference_cache(1)
+                mr = hs.ScanMatcher(T, referenceSummation=True)
+                scan = hs.ScanCloud(xy)
+                wr = oc.match_pyramid(ref, xy, hint, [3] * levels, T)
+                gr, rr = mr.MatchDataReport(rep, scan, hint)
+                gb3 = mr.MatchDataBatch(rep, scan, np.stack([hint] * 3))
+                gb12 = mr.MatchDataBatch(rep, scan, np.stack([hint] * 12))
+                bad = []
+                if not (same_bits(gr, wr) and same_bits(mr.MatchData(rep, scan, hint), wr)):
+                    bad.append("single %s vs %s" % (gr, wr))
+                if not all(same_bits(gb3[i], wr) for i in range(3)):
+                    bad.append("batch of 3 %s vs %s" % (gb3, wr))
+                if not all(same_bits(gb12[i], wr) for i in range(12)):
+                    bad.append("batch of 12 %s vs %s" % (gb12[:2], wr))
+                pm = ref[0].map_pose(wr)
+                Hr, dr = ref[0].hessian(xy, pm, T)
+                if np.isfinite(pm).all():
+                    mx, my = transform_points(npo, ref[0].cell_len, xy, pm)
+                    Mv = np.array([ref[0].interp(float(u), float(v))[0] for u, v in zip(mx, my)], np.float32).reshape(xy.shape[0])
+                    cnt = int(in_map(ref[0].w, ref[0].h, mx, my).sum())
+                else:                                                  # (NaN or infinite coordinates: every point outside the map)
+                    Mv = np.zeros(xy.shape[0], np.float32); cnt = 0
+                res = chunk_sum(residual_terms(Mv), T)
+                if not (same_bits(rr["pose_map"], pm) and same_bits(rr["H"], Hr) and same_bits(rr["dTr"], dr) and same_bits(rr["residual"], res)
+                        and int(rr["n_in_map"]) == cnt and int(rr["n_points"]) == xy.shape[0]):
+                    bad.append("report %s vs pose_map %s H %s dTr %s residual %s in map %d" % (rr, pm, Hr.ravel(), dr, res, cnt))
+                n_ref += 1
+                desc += " | reference order T %d%s" % (T, " cache" if rc else "")
+                if bad:
+                    ok = False
+                    desc += " DIFFERS: " + "; ".join(bad)
             if not ok:
                 desc += " | cells equal: %s, match %s vs oracle %s (hint %s), batches consistent: %s, batch of 12: %s" % (cells_ok, np.asarray(m), w, hint, batch_same, mb12[0])
                 if a.dump:
@@ -308,7 +359,8 @@ def main():
         if not ok:
             print("MISMATCH after %d cases (seed %d)" % (n_cases, a.seed))
             sys.exit(1)
-    print("fuzz: %d cases, all equal to the oracle (seed %d); %d Hector matches equal to the oracle's for a hint one or two digits away" % (n_cases, a.seed, n_near))
+    print("fuzz: %d cases, all equal to the oracle (seed %d); %d Hector matches equal to the oracle's for a hint one or two digits away; "
+          "%d Hector matches compared in the reference's order, all directly and bit for bit" % (n_cases, a.seed, n_near, n_ref))
     ctx.close()
 
 

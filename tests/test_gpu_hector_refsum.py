@@ -58,19 +58,26 @@ def quantise_cells(cells):
     cells["value"] = np.where(cells["value"] > 0, np.float32(50.0), np.float32(0.0))
 
 
-def build_pyramid(hs_mod, ctx, oc, sim, side, cell, levels, R, n_scans, quantised, with_oracle=True, seed=3):
+def build_pyramid(hs_mod, ctx, oc, sim, side, cell, levels, R, n_scans, quantised, with_oracle=True, seed=3, factors=None,
+                  origin=(0.0, 0.0)):
     """MapRepMultiMap and the oracle's pyramid after n_scans UpdateByScan with the same poses (bit-exact cells), then
-    optionally quantised on both sides."""
+    optionally quantised on both sides.  side: cells along one side of a square map, or (w, h); factors: (free, occupied)
+    update factors in place of the defaults; origin: the scan origin of every update."""
     segs = sim.default_field()
-    rep = hs_mod.MapRepMultiMap(cell, (side, side), levels, ctx=ctx)
-    ref = oc.make_pyramid(cell, side, side, levels) if with_oracle else None
+    w, h = (side, side) if np.isscalar(side) else side
+    rep = hs_mod.MapRepMultiMap(cell, (w, h), levels, ctx=ctx)
+    ref = oc.make_pyramid(cell, w, h, levels) if with_oracle else None
+    if factors is not None:
+        rep.SetUpdateFactorFree(factors[0]); rep.SetUpdateFactorOccupied(factors[1])
+        for g in ref or ():
+            g.set_factors(factors[0], factors[1])
     rng = sim.PCG32(seed)
     for it in range(n_scans):
         p = np.array([20 + 0.05 * it, 20 + 0.02 * it, 0.01 * it], np.float32)
         _, xy = sim.make_scan(segs, p, R, rng)
-        rep.UpdateByScan(hs_mod.ScanCloud(xy), p)
+        rep.UpdateByScan(hs_mod.ScanCloud(xy, (origin[0], origin[1], 0.0)), p)
         for g in ref or ():
-            g.update_by_scan(xy, p)
+            g.update_by_scan(xy, p, origin=origin)
     if quantised:
         for l, m in enumerate(rep.Maps):
             c = m.GetCells()

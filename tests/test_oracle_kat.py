@@ -466,6 +466,110 @@ def test_hector_grid_hostile_points_c_vs_numpy(oc, npo, sim):
 
 
 
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).ravel().view(np.uint32).tolist()
+
+
+def test_hector_prob_table_hook(oc, npo, sim):
+    """Grid.set_prob_table / NpGrid.set_prob_table (a test hook, not reference behaviour): a table read in place of
+    OccGridMap.cs:101-102.  On a rectangular, odd-sided pyramid: the oracle's own probabilities installed change no bit of
+    hessian, match and match_pyramid at T = 1 and 4; one changed cell changes H at a pose whose taps include it and at no
+    pose whose taps do not; None restores the first answers; prob_literal (D5) does not look at the table; the C and the
+    NumPy restatement agree bit for bit with the same table installed."""
+    segs = sim.default_field()
+    oc.set_trig_mode(oc.TRIG_DET)
+    try:
+        w, h, cell, iters = 201, 133, 0.2, [4, 3, 2]
+        lv = oc.make_pyramid(cell, w, h, 3)
+        assert [(g.w, g.h) for g in lv] == [(201, 133), (100, 66), (50, 33)]
+        rng = sim.PCG32(7)
+        for it in range(5):
+            p = np.array([20 + 0.05 * it, 14 + 0.02 * it, 0.01 * it], np.float32)
+            xy = sim.make_scan(segs, p, 180, rng)[1]
+            for g in lv:
+                g.update_by_scan(xy, p)
+        xy = sim.make_scan(segs, (20.3, 14.1, 0.05), 180, rng)[1]
+        hints = [np.array(v, np.float32) for v in ((20.35, 14.05, 0.07), (20.2, 14.3, 0.0), (12.0, 9.0, 2.0))]
+
+        def answers():
+            out = []
+            for T in (1, 4):
+                for hint in hints:
+                    out += _bits(oc.match_pyramid(lv, xy, hint, iters, n_threads=T))
+                    for l, g in enumerate(lv):
+                        H, d = g.hessian(xy, g.map_pose(hint), T)
+                        out += _bits(H) + _bits(d) + _bits(g.match(xy, hint, iters[l], T))
+            return out
+
+        first = answers()
+        own = [np.array([g.prob(i) for i in range(g.w * g.h)], np.float32) for g in lv]
+        assert all(len(np.unique(t)) > 3 for t in own)                    # raw maps: not only 0.5 and two more values
+        for g, t in zip(lv, own):
+            g.set_prob_table(t)
+        assert answers() == first
+        with pytest.raises(ValueError):
+            lv[0].set_prob_table(own[1])
+
+        # one changed cell: a tap of the first in-map point at pose A
+        g = lv[0]
+        pose_a = g.map_pose(hints[0])
+        pose_b = g.map_pose(np.array([23.0, 16.0, 0.9], np.float32))
+
+        def taps(pose_map):
+            t = npo.M32.rotation(pose_map[2], "det") * npo.M32.translation(np.float32(pose_map[0]) * np.float32(cell), np.float32(pose_map[1]) * np.float32(cell)) \
+                * npo.M32.scale(np.float32(1.0) / np.float32(cell))
+            mx, my = t.transform(xy[:, 0], xy[:, 1])
+            ok = ~((mx < 0) | (mx > np.float32(w - 2.0)) | (my < 0) | (my > np.float32(h - 2.0)))
+            idx = (np.floor(my[ok]).astype(np.int64) * w + np.floor(mx[ok]).astype(np.int64))
+            return set(idx.tolist()) | set((idx + 1).tolist()) | set((idx + w).tolist()) | set((idx + w + 1).tolist())
+
+        ta, tb = taps(pose_a), taps(pose_b)
+        assert len(ta) > 100 and len(tb) > 100
+        only_a = sorted(ta - tb)
+        assert only_a
+        cellno = only_a[len(only_a) // 2]
+        Ha, da = g.hessian(xy, pose_a, 1); Hb, db = g.hessian(xy, pose_b, 1)
+        changed = own[0].copy()
+        changed[cellno] = np.float32(0.125) if abs(float(changed[cellno]) - 0.125) > 0.05 else np.float32(0.875)
+        g.set_prob_table(changed)
+        assert g.prob(cellno) == changed[cellno]
+        assert g.prob_literal(cellno) == own[0][cellno]                    # (D5's literal cache: the expression, not the table)
+        Ha2, da2 = g.hessian(xy, pose_a, 1); Hb2, db2 = g.hessian(xy, pose_b, 1)
+        assert _bits(Ha2) != _bits(Ha) and _bits(da2) != _bits(da)
+        assert _bits(Hb2) == _bits(Hb) and _bits(db2) == _bits(db)
+        # the table is a snapshot: neither the caller's array nor the cells show through
+        changed[:] = 0.25
+        saved = g.cells["value"].copy()
+        g.cells["value"][:] = 3.0
+        assert _bits(g.hessian(xy, pose_a, 1)[0]) == _bits(Ha2)
+        g.cells["value"][:] = saved
+
+        # C and NumPy with the same (arbitrary) table installed: the same bits
+        tbl = np.random.default_rng(9).uniform(0, 1, w * h).astype(np.float32)
+        ng = npo.NpGrid(cell, w, h)
+        g.set_prob_table(tbl); ng.set_prob_table(tbl)
+        for pose in (pose_a, pose_b):
+            for T in (1, 4, 7):
+                Hc, dc = g.hessian(xy, pose, T); Hn, dn = ng.hessian(xy, pose, T)
+                assert _bits(Hc) == _bits(Hn) and _bits(dc) == _bits(dn), (pose, T)
+        for cx, cy in ((3.25, 4.75), (198.5, 130.99), (199.0, 131.0), (199.01, 5.0), (0.0, 0.0)):
+            P, gx, gy = ng.interp(np.float32(cx), np.float32(cy))
+            assert _bits(g.interp(cx, cy)) == _bits([P, gx, gy]), (cx, cy)
+        terms, M = ng.hessian_terms(xy, pose_a)
+        assert terms.shape == (9, xy.shape[0]) and M.shape == (xy.shape[0],) and terms.dtype == np.float32
+
+        # None restores the expression
+        ng.set_prob_table(None)
+        ng.value[:] = g.cells["value"]
+        assert np.allclose(ng.prob(np.arange(w * h)), own[0], rtol=0, atol=2e-7)
+        for gg in lv:
+            gg.set_prob_table(None)
+        assert answers() == first
+    finally:
+        oc.set_trig_mode(oc.TRIG_LIBM)
+
+
+
 # ---- the device candidate generator's specification (what stands where FillRandomQueues stood, CoreSLAMProcessor.cs:599-612) -------
 def test_philox4x32_10_known_answers(npo):
     """The NumPy restatement of the generator's integer stream against Random123's published kat_vectors (philox4x32, 10 rounds):
