@@ -83,6 +83,32 @@ namespace CoreSLAM
         /// candidates on, the same localisation quality on the simulator's lap.  Off: every candidate has its own (stratified)
         /// heading, as close to the reference's independent draws as a reproducible generator gets.</summary>
         public bool UseHeadingLattice { get; set; } = false;
+        /// <summary>Opt-in (new): every searching Update keeps the search report of its Monte-Carlo search (slamhip_search_report;
+        /// one GPU, TrigMode.Device).  Pose and maps do not change; the scan takes the library's ordinary launch order (nothing is
+        /// launched ahead).  Switching it off drops the last report.</summary>
+        public bool SearchReport
+        {
+            get => searchReport;
+            set { searchReport = value; if (!value) LastSearchReport = null; }
+        }
+        private bool searchReport = false;
+        /// <summary>The band of the report: scored candidates within this distance of the best form the set the sums run over (0: the ties).</summary>
+        public int ReportBand
+        {
+            get => reportBand;
+            set { if (value < 0) throw new ArgumentOutOfRangeException(nameof(value)); reportBand = value; }
+        }
+        private int reportBand = 0;
+        /// <summary>The report of the last searching Update, or null: before the first searching Update, after Reset, while reports are off.</summary>
+        public SlamHip.SearchReport? LastSearchReport { get; private set; }
+        /// <summary>The distance of every candidate of the last report search, flat order (index 0: the un-jittered search pose).</summary>
+        public unsafe int[] LastSearchDistances()
+        {
+            if (LastSearchReport == null) throw new InvalidOperationException("no search report");
+            int[] d = new int[LastSearchReport.Value.NCandidates];
+            fixed (int* p = d) Native.Check(Native.slamhip_cs_search_distances(cs.Ptr, p, d.Length));
+            return d;
+        }
         /// <summary>When the managed map mirrors (HoleMap.Pixels, ObstacleMap.Pixels) are brought up to date.
         /// OnRead (default): an Update only marks them stale; the `Pixels` getters fetch what changed since their last read --
         /// the HoleMap through slamhip_cs_holemap_mirror_async + _wait (the 16-byte units that changed, ~0.25 ms at 2048 x 2048 for
@@ -175,6 +201,7 @@ namespace CoreSLAM
             Pose = startPose;
             lastOdometryPose = Vector3.Zero;
             scanCount = 0;
+            LastSearchReport = null;
             MapsChanged();
         }
 
@@ -251,6 +278,7 @@ namespace CoreSLAM
                 }
                 scanNumber++;
                 lastOdometryPose = odometry;                                        // :745
+                if (!oneCall || !searchReport) LastSearchReport = null;             // (reports: one GPU, the library's trigonometry)
                 if (TrigMode == TrigMode.Host)
                 {
                     Pose = SearchAndUpdateHostTrig(search);
@@ -271,8 +299,18 @@ namespace CoreSLAM
                 // touches the maps (the next search, the mirrors' downloads below) is ordered behind them on the device
                 Vector3 found;
                 fixed (Vector2* p = CollectionsMarshal.AsSpan(cloud))
+                {
+                    if (searchReport)
+                    {
+                        LastSearchReport = null;
+                        Native.Check(Native.slamhip_cs_scan_search_and_update_report(cs.Ptr, p, cloud.Count, search, reportBand, HoleWidth, Quality, MaxObstacleHits,
+                                                                                     out found, out SlamHip.SearchReport report));
+                        LastSearchReport = report;
+                    }
+                    else
                     Native.Check(Native.slamhip_cs_scan_search_and_update(cs.Ptr, p, cloud.Count, search, HoleWidth, Quality, MaxObstacleHits,
                                                                           out found, out _, out _));
+                }
                 Pose = found;
             }
             else
@@ -286,6 +324,7 @@ namespace CoreSLAM
                 else
                 {
                     p3 = Pose + (odometry - lastOdometryPose);                      // empty cloud: the un-jittered pose wins (:257, :626-628)
+                    LastSearchReport = null;                                        // (nothing was searched)
                 }
                 lastOdometryPose = odometry;
                 p3.Z = MathEx.NormalizeAngle(p3.Z);                                 // :746

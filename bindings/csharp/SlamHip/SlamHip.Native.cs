@@ -1,8 +1,8 @@
 // SlamHip.Native.cs -- P/Invoke surface of libslamhip.so (include/slamhip.h), one declaration per C entry point the
 // managed shims use.  Every function returns an int32 status (0 = OK); Check() turns anything else into an
 // InvalidOperationException carrying slamhip_last_error().  Structs crossing the boundary are blittable:
-// Vector2 / Vector3 / Vector4 (8 / 12 / 16 bytes), LogOddsCell {int UpdateIndex; float Value} (8 bytes) and MatchReport
-// (slamhip_match_report: 19 four-byte fields, 76 bytes).
+// Vector2 / Vector3 / Vector4 (8 / 12 / 16 bytes), LogOddsCell {int UpdateIndex; float Value} (8 bytes), MatchReport
+// (slamhip_match_report: 19 four-byte fields, 76 bytes) and SearchReport (slamhip_search_report: 9 doubles + 12 ints, 120 bytes).
 //
 // Source only: the build image of this repository has no .NET SDK; the same symbols are exercised by the ctypes
 // binding (slam.net_amd/capi.py) and by the GPU tests.
@@ -16,6 +16,24 @@ namespace SlamHip
     /// GetCompleteHessianDerivs (ScanMatcher.cs:135-204) at PoseMap on the report level, the residual (sum over all scan points of
     /// (1 - M)^2, a point outside the map adding 1) and how many points fell inside the map.  19 four-byte fields, 76 bytes.
     /// The library sets no acceptance threshold: what residual means "lost" is the host's decision.</summary>
+    /// <summary>slamhip_search_report: what a caller needs to judge a CoreSLAM Monte-Carlo search (CoreSLAMProcessor.cs:624-710) -- the
+    /// distance of the un-jittered pose (Dist0), the runner-up and the tie count, the candidates without a point in the map, the
+    /// winner's in-map count (:247) against NPoints, and over the band set (scored candidates within Band of the best distance) the
+    /// sums of the jitters and of their products, from which the host forms mean and covariance.  9 doubles + 12 ints, 120 bytes.
+    /// The library sets no threshold: what margin or spread means "lost" is the host's decision.</summary>
+    [StructLayout(LayoutKind.Sequential, Pack = 8)]
+    public struct SearchReport
+    {
+        public double SumDx, SumDy, SumDtheta;
+        public double SumDxDx, SumDxDy, SumDxDtheta, SumDyDy, SumDyDtheta, SumDthetaDtheta;
+        public int BestDist, BestIndex;
+        public int RunnerDist, RunnerIndex;
+        public int Dist0;
+        public int NCandidates, NUnscored, NTies;
+        public int Band, NBand;
+        public int NInMap, NPoints;
+    }
+
     [StructLayout(LayoutKind.Sequential, Pack = 4)]
     public struct MatchReport
     {
@@ -81,6 +99,13 @@ namespace SlamHip
                                                                                  out Vector3 pose, out int dist, out int index);
         [DllImport(Lib)] internal static extern int slamhip_cs_scan_search_and_update(IntPtr cs, Vector2* xy, int nPoints, in Vector3 searchPose, float holeWidth, int quality, int maxObstacleHits,
                                                                                       out Vector3 pose, out int dist, out int index);
+        // the search report (slamhip.h: slamhip_search_report): the plain forms' results, the ordinary launch order
+        [DllImport(Lib)] internal static extern int slamhip_cs_search_report(IntPtr cs, in Vector3 searchPose, int band, out Vector3 pose, out SearchReport report);
+        [DllImport(Lib)] internal static extern int slamhip_cs_search_distances(IntPtr cs, int* dist, int k);
+        [DllImport(Lib)] internal static extern int slamhip_cs_search_and_update_report(IntPtr cs, in Vector3 searchPose, int band, float holeWidth, int quality, int maxObstacleHits,
+                                                                                        out Vector3 pose, out SearchReport report);
+        [DllImport(Lib)] internal static extern int slamhip_cs_scan_search_and_update_report(IntPtr cs, Vector2* xy, int nPoints, in Vector3 searchPose, int band, float holeWidth, int quality,
+                                                                                             int maxObstacleHits, out Vector3 pose, out SearchReport report);
         [DllImport(Lib)] internal static extern int slamhip_cs_search_and_update_pxcs(IntPtr cs, Vector4* pxcsSearch, Vector4* pxcsUpdateHole, Vector4* pxcsUpdateObstacle, int k,
                                                                                       float holeWidth, int quality, int maxObstacleHits, out int index, out int dist);
         [DllImport(Lib)] internal static extern int slamhip_cs_update_maps_pxcs(IntPtr cs, in Vector4 pxcsHole, in Vector4 pxcsObstacle, float holeWidth, int quality, int maxObstacleHits);

@@ -332,6 +332,65 @@ int32_t slamhip_cs_search_and_update_pxcs(slamhip_cs *cs, const float *pxcs_sear
 int32_t slamhip_cs_update_maps_pxcs(slamhip_cs *cs, const float pxcs_hole[4], const float pxcs_obstacle[4], float hole_width,
                                     int32_t quality, int32_t max_obstacle_hits);
 
+/* The search report: what a caller needs to judge a Monte-Carlo search (ParallelMonteCarloSearch, CoreSLAMProcessor.cs:624-710),
+ * which itself returns only the winner.  All K = n_offs + 1 distances of the search are kept on the device, in flat order, and
+ * reduced behind the search launch:
+ *   dist0      the distance of flat candidate 0, the un-jittered search pose (:626-628): best_dist == dist0 with best_index == 0
+ *              means that the search did not improve on the odometry prediction;
+ *   runner_*   the second-smallest packed key (dist << 32 | index), n_ties the candidates at best_dist (the winner included):
+ *              whether the winner stands clear of the field;
+ *   the band set: the SCORED candidates (dist != INT32_MAX) with (int64)dist - best_dist <= band; band = 0 gives the ties.  Over
+ *              it n_band and the sums of the jitters (dx, dy, dtheta; candidate 0 has (0, 0, 0)) and of their six products.
+ *              Every product is formed in binary64 from two binary32 jitters (exact: 48 significant bits), and the terms are
+ *              added in binary64 in an order that depends on K alone (per lane in index order, the lanes and wavefronts of a
+ *              workgroup pairwise, the workgroups' partial sums in workgroup order; no floating-point atomics): the same call
+ *              returns the same bits.  The host forms mean = sum_off / n_band and covariance = sum_off2 / n_band - mean mean^T;
+ *   n_in_map   nb_points (:247) of the WINNER: CalculateDistanceSISD divides by all points (:253) but sums only those that land
+ *              in the map (:244-248), so a pose that throws most of the scan off the map can score deceptively low.  It is
+ *              evaluated once more for the winner alone -- (px, py, c, s) from search_pose + offs[index - 1] as the search forms
+ *              them (:232-235, the library's deterministic cos / sin), :240-244 per ray.
+ * If nothing is scored (best_dist == INT32_MAX; best_index = 0 as in :257): n_band = 0, the nine sums are +0.0,
+ * n_ties = n_unscored = K, n_in_map = 0.  K == 1: runner_dist = INT32_MAX, runner_index = -1.
+ * The library sets no threshold: what margin, spread or in-map share means "lost" depends on the map and the sensor and is the
+ * host's decision.
+ * Scope: full-range searches only.  The shard, all-reduce and slamhip_group_* forms have no report (a report over one shard
+ * describes nothing a caller wants), and the explicit-list calls slamhip_cs_distance_pxcs / _poses return every distance already. */
+typedef struct slamhip_search_report {
+    double  sum_off[3];     /* over the band set: sum of dx, dy, dtheta (the jitter; candidate 0 has (0,0,0)) */
+    double  sum_off2[6];    /* sum of dx*dx, dx*dy, dx*dth, dy*dy, dy*dth, dth*dth */
+    int32_t best_dist, best_index;       /* exactly what the plain search returns (:644-648, :695-705) */
+    int32_t runner_dist, runner_index;   /* second-smallest packed key (dist << 32 | index); K == 1: INT32_MAX, -1 */
+    int32_t dist0;          /* distance of flat candidate 0, the un-jittered search pose (:626-628) */
+    int32_t n_candidates;   /* K = n_offs + 1 */
+    int32_t n_unscored;     /* candidates with distance int.MaxValue (:257) */
+    int32_t n_ties;         /* candidates whose distance == best_dist, the winner included */
+    int32_t band;           /* echo of the argument */
+    int32_t n_band;         /* size of the band set */
+    int32_t n_in_map;       /* nb_points (:247) of the WINNER */
+    int32_t n_points;       /* cloud.Points.Count */
+} slamhip_search_report;    /* 9 doubles + 12 int32, sizeof(slamhip_search_report) == 120, no padding */
+/* slamhip_cs_search with the report: out_pose, best_dist and best_index are bit for bit the plain call's.  The search runs in the
+ * ordinary launch order with its per-candidate distances kept, two small launches behind it on the operator's stream make the
+ * report, and the call makes one wait.  band < 0 or a null out_report: SLAMHIP_ERR_INVALID. */
+int32_t slamhip_cs_search_report(slamhip_cs *cs, const float search_pose[3], int32_t band, float out_pose[3],
+                                 slamhip_search_report *out_report);
+/* The K distances of the last report search on this handle (slamhip_cs_search_report or a fused report form), flat order.
+ * SLAMHIP_ERR_STATE: there has been none, or a search without a report (any form, the explicit-list calls included) ran since;
+ * SLAMHIP_ERR_INVALID: K != n_candidates of that search. */
+int32_t slamhip_cs_search_distances(slamhip_cs *cs, int32_t *out_dist, int32_t K);
+/* slamhip_cs_search_and_update / slamhip_cs_scan_search_and_update with the report: pose, distance, index, both maps and
+ * slamhip_cs_maps_checksum are bit-identical to the plain calls.  The report describes the map that was SEARCHED: its launches
+ * sit between the search and the map updates on the operator's stream.  The report forms take the ordinary launch order -- no
+ * result-ring slot, no plan, no launch of the search ahead of the scan's tables, no candidate list prepared ahead
+ * (slamhip_cs_prelaunch_stats, slamhip_cs_plan_stats and slamhip_cs_prepared_lists do not move); the call still returns as
+ * soon as pose and report are on the host, with the map updates running on. */
+int32_t slamhip_cs_search_and_update_report(slamhip_cs *cs, const float search_pose[3], int32_t band, float hole_width,
+                                            int32_t quality, int32_t max_obstacle_hits, float out_pose[3],
+                                            slamhip_search_report *out_report);
+int32_t slamhip_cs_scan_search_and_update_report(slamhip_cs *cs, const float *xy, int32_t n_points, const float search_pose[3],
+                                                 int32_t band, float hole_width, int32_t quality, int32_t max_obstacle_hits,
+                                                 float out_pose[3], slamhip_search_report *out_report);
+
 /* ------------------------------------------------------------------------------------------------
  * CoreSLAM, processor level (host-side orchestration in C++, mirrors the public C# class)
  * ---------------------------------------------------------------------------------------------- */
@@ -360,6 +419,17 @@ int32_t slamhip_csproc_set_seed(slamhip_csproc *p, uint64_t seed);
 int32_t slamhip_csproc_set_lattice(slamhip_csproc *p, int32_t on);
 /* pin the jitter list used by the next searching Update (parity tests feed the oracle the same list) */
 int32_t slamhip_csproc_set_offsets(slamhip_csproc *p, const float *offs, int32_t n);
+/* on = 1: every later searching slamhip_csproc_update runs slamhip_cs_scan_search_and_update_report with this band and keeps the
+ * report; poses and maps do not change, the launch order does (see there: the ordinary order, nothing launched ahead).
+ * on = 0 (default): Update launches exactly what it launches without this call, and the last report is dropped.  Any other
+ * `on` and any negative band: SLAMHIP_ERR_INVALID, the setting unchanged.
+ * Cost: two short launches per scan and the launch-ahead flow given up (DESIGN.md sec.4 "The search report");
+ * tools/search_report_cost.py measures both modes at 2048^2 / 1080 rays / 16 384 candidates (not measured yet). */
+int32_t slamhip_csproc_set_search_report(slamhip_csproc *p, int32_t on, int32_t band);
+/* The report of the last searching slamhip_csproc_update (:732); *out_valid = 0 and *out zeroed before the first searching
+ * Update (scans before PositionSearchBeginning do not search, :726; nor does a scan with an empty cloud), after
+ * slamhip_csproc_reset and while reports are off. */
+int32_t slamhip_csproc_get_report(slamhip_csproc *p, slamhip_search_report *out, int32_t *out_valid);
 /* the underlying operator-level object (HoleMap / ObstacleMap properties :45,:50) */
 int32_t slamhip_csproc_cs(slamhip_csproc *p, slamhip_cs **out_cs);
 /* ScanSegmentsToCloud (CoreSLAMProcessor.cs:187-207) on its own, as slamhip_csproc_update runs it on the host: every segment's pose relative to

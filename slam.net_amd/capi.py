@@ -32,6 +32,21 @@ REPORT_DTYPE = np.dtype([("pose_map", np.float32, 3), ("H", np.float32, (3, 3)),
 assert C.sizeof(MatchReport) == REPORT_DTYPE.itemsize == 76
 
 
+class SearchReport(C.Structure):
+    """slamhip_search_report (include/slamhip.h): 9 doubles + 12 int32, 120 bytes, no padding."""
+    _fields_ = [("sum_off", C.c_double * 3), ("sum_off2", C.c_double * 6), ("best_dist", C.c_int32), ("best_index", C.c_int32),
+                ("runner_dist", C.c_int32), ("runner_index", C.c_int32), ("dist0", C.c_int32), ("n_candidates", C.c_int32),
+                ("n_unscored", C.c_int32), ("n_ties", C.c_int32), ("band", C.c_int32), ("n_band", C.c_int32),
+                ("n_in_map", C.c_int32), ("n_points", C.c_int32)]
+
+
+SEARCH_REPORT_DTYPE = np.dtype([("sum_off", np.float64, 3), ("sum_off2", np.float64, 6), ("best_dist", np.int32), ("best_index", np.int32),
+                                ("runner_dist", np.int32), ("runner_index", np.int32), ("dist0", np.int32), ("n_candidates", np.int32),
+                                ("n_unscored", np.int32), ("n_ties", np.int32), ("band", np.int32), ("n_band", np.int32),
+                                ("n_in_map", np.int32), ("n_points", np.int32)])
+assert C.sizeof(SearchReport) == SEARCH_REPORT_DTYPE.itemsize == 120
+
+
 class SlamhipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("slamhip error %d: %s" % (code, msg))
@@ -66,6 +81,7 @@ def _declare(L):
     P = C.POINTER
     fp, ip, u16p, i8p, u8p, u64p, vpp = P(f), P(i32), P(C.c_uint16), P(C.c_int8), P(C.c_uint8), P(u64), P(vp)
     rp = P(MatchReport)
+    srp = P(SearchReport)
     sig = {
         "slamhip_version": (C.c_char_p, []),
         "slamhip_last_error": (C.c_char_p, []),
@@ -118,6 +134,10 @@ def _declare(L):
         "slamhip_cs_scan_search_and_update": (i32, [vp, fp, i32, fp, f, i32, i32, fp, ip, ip]),
         "slamhip_cs_search_and_update_pxcs": (i32, [vp, fp, fp, fp, i32, f, i32, i32, ip, ip]),
         "slamhip_cs_update_maps_pxcs": (i32, [vp, fp, fp, f, i32, i32]),
+        "slamhip_cs_search_report": (i32, [vp, fp, i32, fp, srp]),
+        "slamhip_cs_search_distances": (i32, [vp, ip, i32]),
+        "slamhip_cs_search_and_update_report": (i32, [vp, fp, i32, f, i32, i32, fp, srp]),
+        "slamhip_cs_scan_search_and_update_report": (i32, [vp, fp, i32, fp, i32, f, i32, i32, fp, srp]),
         "slamhip_cs_selfcheck_failures": (i32, [vp, P(C.c_uint32)]),
         "slamhip_cs_prelaunch_stats": (i32, [vp, P(C.c_uint64)]),
         "slamhip_cs_plan_stats": (i32, [vp, P(C.c_uint64)]),
@@ -131,6 +151,8 @@ def _declare(L):
         "slamhip_csproc_set_seed": (i32, [vp, u64]),
         "slamhip_csproc_set_lattice": (i32, [vp, i32]),
         "slamhip_csproc_set_offsets": (i32, [vp, fp, i32]),
+        "slamhip_csproc_set_search_report": (i32, [vp, i32, i32]),
+        "slamhip_csproc_get_report": (i32, [vp, srp, ip]),
         "slamhip_csproc_cs": (i32, [vp, vpp]),
         "slamhip_scan_segments_to_cloud": (i32, [fp, ip, i32, fp, fp]),
         "slamhip_hs_create": (i32, [vp, f, i32, i32, i32, vpp]),
@@ -221,6 +243,11 @@ def iptr(a):
 def rptr(a):
     """A REPORT_DTYPE array as the slamhip_match_report pointer of the C-ABI."""
     return a.ctypes.data_as(C.POINTER(MatchReport))
+
+
+def srptr(a):
+    """A SEARCH_REPORT_DTYPE array as the slamhip_search_report pointer of the C-ABI."""
+    return a.ctypes.data_as(C.POINTER(SearchReport))
 
 
 def f32(a, shape=None):

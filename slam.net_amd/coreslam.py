@@ -206,6 +206,20 @@ class CoreSlamDevice:
         capi.call("slamhip_cs_search", self._h, capi.fptr(sp), capi.fptr(pose), C.byref(d), C.byref(i))
         return pose, d.value, i.value
 
+    def search_report(self, search_pose, band=0):
+        """search() with the search report (slamhip_cs_search_report): returns (pose, report), report a SEARCH_REPORT_DTYPE record;
+        pose, report["best_dist"] and report["best_index"] are search()'s."""
+        sp = capi.f32(search_pose)
+        pose = np.empty(3, np.float32); rep = np.zeros(1, capi.SEARCH_REPORT_DTYPE)
+        capi.call("slamhip_cs_search_report", self._h, capi.fptr(sp), int(band), capi.fptr(pose), capi.srptr(rep))
+        return pose, rep[0]
+
+    def search_distances(self):
+        """The distances of every candidate of the last report search, flat order (slamhip_cs_search_distances)."""
+        out = np.empty(self.n_offsets + 1, np.int32)
+        capi.call("slamhip_cs_search_distances", self._h, capi.iptr(out), out.size)
+        return out
+
     def search_shard(self, search_pose, first, count):
         sp = capi.f32(search_pose); key = C.c_uint64()
         capi.call("slamhip_cs_search_shard", self._h, capi.fptr(sp), int(first), int(count), C.byref(key))
@@ -305,6 +319,19 @@ class CoreSlamDevice:
                   int(max_hits), capi.fptr(pose), C.byref(d), C.byref(i))
         return pose, d.value, i.value
 
+    def search_and_update_report(self, search_pose, band=0, hole_width=0.6, quality=50, max_hits=10, xy=None):
+        """search_and_update (xy given: scan_search_and_update) with the search report of the map as searched; returns (pose, report)."""
+        sp = capi.f32(search_pose)
+        pose = np.empty(3, np.float32); rep = np.zeros(1, capi.SEARCH_REPORT_DTYPE)
+        if xy is None:
+            capi.call("slamhip_cs_search_and_update_report", self._h, capi.fptr(sp), int(band), C.c_float(hole_width), int(quality),
+                      int(max_hits), capi.fptr(pose), capi.srptr(rep))
+        else:
+            pts = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+            capi.call("slamhip_cs_scan_search_and_update_report", self._h, capi.fptr(pts), int(pts.shape[0]), capi.fptr(sp), int(band),
+                      C.c_float(hole_width), int(quality), int(max_hits), capi.fptr(pose), capi.srptr(rep))
+        return pose, rep[0]
+
     def search_and_update_pxcs(self, pxcs_search, pxcs_update_hole, pxcs_update_obst=None, hole_width=0.6, quality=50, max_hits=10):
         """The fused scan with the caller's own (px, py, c, s) (slamhip_cs_search_and_update_pxcs): the candidates for the search,
         and their rows -- of the normalised pose -- at both map scales for the updates.  Returns (index, distance) of the first strict
@@ -361,7 +388,7 @@ class CoreSLAMProcessor:
     UnmappedObstacleHits :96, MaxObstacleHits :101, Dispose :757."""
 
     def __init__(self, physicalMapSize, holeMapSize, obstacleMapSize, startPose, sigmaXY, sigmaTheta,
-                 iterationsPerThread, numSearchThreads, ctx=None):
+                 iterationsPerThread, numSearchThreads, ctx=None, searchReport=False, reportBand=0):
         self._own_ctx = ctx is None
         self.ctx = ctx or Context(0)
         sp = capi.f32(startPose)
@@ -379,6 +406,8 @@ class CoreSLAMProcessor:
         self.ObstacleMap = ObstacleMap(self.device)
         self._params = dict(Quality=50, HoleWidth=0.6, PositionSearchBeginning=5, UnmappedObstacleHits=-5,
                             MaxObstacleHits=10)
+        if searchReport:
+            self.SetSearchReport(True, reportBand)
 
     def _push(self):
         p = self._params
@@ -417,6 +446,17 @@ class CoreSLAMProcessor:
     def SetLattice(self, on):
         """Opt-in: the per-scan candidates as a heading lattice (slamhip_csproc_set_lattice)."""
         capi.call("slamhip_csproc_set_lattice", self._h, 1 if on else 0)
+
+    def SetSearchReport(self, on, band=0):
+        """Opt-in: every searching Update keeps its search report (slamhip_csproc_set_search_report)."""
+        capi.call("slamhip_csproc_set_search_report", self._h, 1 if on else 0, int(band))
+
+    @property
+    def LastSearchReport(self):
+        """The report of the last searching Update (a SEARCH_REPORT_DTYPE record), or None when no report is valid."""
+        rep = np.zeros(1, capi.SEARCH_REPORT_DTYPE); valid = C.c_int32()
+        capi.call("slamhip_csproc_get_report", self._h, capi.srptr(rep), C.byref(valid))
+        return rep[0] if valid.value else None
 
     def SetOffsets(self, offs):
         offs = capi.f32(offs, (-1, 3))

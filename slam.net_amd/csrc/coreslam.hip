@@ -218,6 +218,7 @@ extern "C" int32_t slamhip_cs_destroy(slamhip_cs *cs)
     (void)hipFree(cs->d_key); (void)hipFree(cs->d_grp_bounds); (void)hipFree(cs->d_verify);
     (void)hipFree(cs->d_k1_gmin); (void)hipFree(cs->d_k1_acc); (void)hipFree(cs->d_k1_ring);
     if (cs->h_key) (void)hipHostFree(cs->h_key);
+    (void)hipFree(cs->d_rep); if (cs->h_rep) (void)hipHostFree(cs->h_rep);
     // (the helper streams are the context's: what this object put into them is waited for, the streams stay)
     if (!cs->ctx->poisoned) { (void)hipStreamSynchronize(cs->mirror_stream); (void)hipStreamSynchronize(cs->side_stream); }
     (void)hipFree(cs->d_side_arrive);
@@ -1350,7 +1351,7 @@ static int32_t search_enqueue(slamhip_cs *cs, const float pose[3], int first, in
     SH_TRY(ensure_shard(cs, first, count));
     g_cst.lap(0);
     const bool sane = fabsf(pose[0]) < 1.0e6f && fabsf(pose[1]) < 1.0e6f && fabsf(pose[2]) < 1.0e4f && cs->offs_theta_small;
-    return cs_launch_distance(cs, 1, pose, count, false, sane, key_dst);
+    return cs_launch_distance(cs, 1, pose, count, cs->k1_keep_dist, sane, key_dst);
 }
 
 extern "C" int32_t slamhip_cs_search_shard_async(slamhip_cs *cs, const float pose[3], int32_t first, int32_t count,
@@ -1848,4 +1849,103 @@ extern "C" int32_t slamhip_cs_search_and_update(slamhip_cs *cs, const float pose
     if (out_dist) *out_dist = (int32_t)(uint32_t)(key >> 32);
     if (out_index) *out_index = (int32_t)(uint32_t)key;
     return SLAMHIP_OK;
+}
+
+// ---- the search report (slamhip.h: slamhip_search_report) ----------------------------------------------------------------------
+// The report forms take the ordinary launch order: the search with its distances kept (k1_keep_dist) and its key in d_key, the
+// report's two launches (distance.hip: cs_launch_search_report), then -- fused forms -- the map updates.  The report's last launch
+// delivers report, key and pose into the handle's pinned block and releases the block's own completion word: one wait.
+static void report_read(const slamhip_cs *cs, slamhip_search_report *out_report, uint64_t *out_key)
+{
+    memcpy(out_report, (const void *)cs->h_rep, sizeof(slamhip_search_report));
+    memcpy(out_key, (const void *)(cs->h_rep + CS_REP_KEY), sizeof(uint64_t));
+}
+
+extern "C" int32_t slamhip_cs_search_report(slamhip_cs *cs, const float pose[3], int32_t band, float out_pose[3],
+                                            slamhip_search_report *out_report)
+{
+    SH_CHECK_ARG(cs && pose && out_report && band >= 0);
+    slamhip_ctx *ctx = cs->ctx;
+    sh_mail_guard lock(ctx);
+    cs->k1_keep_dist = true;
+    const int32_t rc = search_enqueue(cs, pose, 0, cs->n_offs + 1, cs->d_key);
+    cs->k1_keep_dist = false;
+    SH_TRY(rc);
+    const bool deliver = !ctx->mail_off;
+    SH_TRY(cs_launch_search_report(cs, pose, band, nullptr, deliver));
+    cs_layout_idle_refresh(cs);                                    // (host work under the search)
+    if (deliver) SH_TRY(sh_flag_wait(ctx, cs->h_rep + CS_REP_FLAG, cs->rep_seq));
+    else {
+        SH_TRY(cs_search_report_copy(cs, nullptr));
+        SH_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    uint64_t key = 0;
+    report_read(cs, out_report, &key);
+    return slamhip_cs_pose_from_key(cs, pose, key, out_pose, nullptr, nullptr);      // (as slamhip_cs_search forms the pose)
+}
+
+extern "C" int32_t slamhip_cs_search_distances(slamhip_cs *cs, int32_t *out_dist, int32_t K)
+{
+    SH_CHECK_ARG(cs && out_dist);
+    if (!cs->rep_dist_valid) SH_FAIL(SLAMHIP_ERR_STATE, "no report search on this handle, or a search without a report ran since");
+    SH_CHECK_ARG(K == cs->rep_K);
+    SH_HIP(hipSetDevice(cs->ctx->device));
+    SH_HIP(hipMemcpyAsync(out_dist, cs->d_dist, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost, cs->ctx->stream));
+    SH_HIP(hipStreamSynchronize(cs->ctx->stream));
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_cs_search_and_update_report(slamhip_cs *cs, const float pose[3], int32_t band, float hole_width, int32_t quality,
+                                                       int32_t max_hits, float out_pose[3], slamhip_search_report *out_report)
+{
+    SH_CHECK_ARG(cs && pose && out_report && band >= 0);
+    SH_CHECK_ARG(quality >= 0 && quality <= 256 && max_hits >= -128 && max_hits <= 127);
+    slamhip_ctx *ctx = cs->ctx;
+    // as slamhip_cs_search_and_update without the decoding update: the search leaves the winner's pose on the device, the report is
+    // made from the map as searched, the updates follow; the call returns when the report's last launch has delivered
+    const bool early = !ctx->mail_off && ctx->timing == 0 && !fused_wait_updates();
+    sh_mail_guard lock(ctx);
+    cs->k1_want_pose = true; cs->k1_keep_dist = true;
+    const int32_t rc_s = search_enqueue(cs, pose, 0, cs->n_offs + 1, cs->d_key);
+    cs->k1_want_pose = false; cs->k1_keep_dist = false;
+    SH_TRY(rc_s);
+    if (!cs->k1_pose_written)                                    // (fallback search kernels: decode the key in a launch of its own)
+        hipLaunchKernelGGL(k_best_pose, dim3(1), dim3(1), 0, ctx->stream, (const unsigned long long *)cs->d_key,
+                           cs->d_offs_flat, pose[0], pose[1], pose[2], cs->d_best_pose);
+    SH_TRY(cs_launch_search_report(cs, pose, band, cs->d_best_pose, !ctx->mail_off));
+    int32_t rc_u;                                                // :750-751, as slamhip_cs_search_and_update launches them
+    if (ctx->timing == 0) {
+        rc_u = cs_launch_holemap_update(cs, cs->d_best_pose, make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), hole_width, quality, true, max_hits);
+    } else {
+        rc_u = cs_launch_holemap_update(cs, cs->d_best_pose, make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), hole_width, quality);
+        if (rc_u == SLAMHIP_OK) rc_u = cs_launch_obstacle_update(cs, cs->d_best_pose, make_float4(0, 0, 0, 0), max_hits);
+    }
+    cs_layout_idle_refresh(cs);
+    if (early) {
+        SH_TRY(sh_flag_wait(ctx, cs->h_rep + CS_REP_FLAG, cs->rep_seq));
+        SH_TRY(rc_u);
+        cs->hole_pixels_pending = true;
+        cs->launch_done = cs->k1_launch_no;                      // (the report has delivered: the search and every launch before it have finished)
+    } else {
+        SH_TRY(rc_u);
+        if (ctx->mail_off) SH_TRY(cs_search_report_copy(cs, cs->d_best_pose));
+        SH_TRY(sh_publish(ctx, cs->d_key, 8));
+        SH_TRY(sh_host_wait(ctx));
+        cs->last_hole_pixels = ((const int *)ctx->mailbox)[6]; cs->hole_pixels_pending = false;
+    }
+    uint64_t key = 0;
+    report_read(cs, out_report, &key);
+    const float *hp = (const float *)(cs->h_rep + CS_REP_POSE);
+    if (out_pose) { out_pose[0] = hp[0]; out_pose[1] = hp[1]; out_pose[2] = hp[2]; }
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_cs_scan_search_and_update_report(slamhip_cs *cs, const float *xy, int32_t n, const float pose[3], int32_t band,
+                                                            float hole_width, int32_t quality, int32_t max_hits, float out_pose[3],
+                                                            slamhip_search_report *out_report)
+{
+    SH_CHECK_ARG(cs && pose && out_report && band >= 0 && n >= 0 && (xy || n == 0));
+    SH_CHECK_ARG(quality >= 0 && quality <= 256 && max_hits >= -128 && max_hits <= 127);
+    SH_TRY(slamhip_cs_set_scan(cs, xy, n));                            // :723
+    return slamhip_cs_search_and_update_report(cs, pose, band, hole_width, quality, max_hits, out_pose, out_report);   // :732, :746-751
 }

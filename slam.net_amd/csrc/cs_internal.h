@@ -130,6 +130,11 @@ struct slamhip_cs {
     uint32_t plan_inputs_after;   // the plan kernel reads what launches in the operator's stream wrote (candidate gather, scan upload): it may only be
                                   // launched once the search launch of this number has started (0: nothing pending)
     uint64_t plan_stats[4];       // searches launched with a plan | without | host waits for a free slot | plans skipped because their inputs were still in flight
+    // the search report (slamhip_cs_search_report and the fused report forms; distance.hip): partial slots and the finished report on
+    // the device, a pinned block the last launch delivers into (report | key | pose | its own completion word)
+    void *d_rep; uint32_t *h_rep; uint32_t rep_seq;
+    bool k1_keep_dist;            // the next search launch keeps every candidate's distance in d_dist (a report search)
+    bool rep_dist_valid; int rep_K;   // d_dist holds the rep_K distances of the last report search (no search launch since)
     uint32_t upload_seq;          // set_scan uploads issued (the upload's workgroups store it into words 28 .. 31 of h_key when they have read the staging block)
 
     // ---- K2 HoleMap update -----------------------------------------------------------------------------
@@ -175,6 +180,15 @@ static inline void cs_plan_inputs_pending(slamhip_cs *cs) { cs->plan_inputs_afte
 int32_t cs_flush_scan(slamhip_cs *cs);
 int32_t cs_launch_distance(slamhip_cs *cs, int mode, const float pose[3], int count, bool want_dist, bool cand_sane,
                            uint64_t *key_dst);
+// the report of the search launch just enqueued with k1_keep_dist (its key in d_key): two launches behind it on the operator's
+// stream; d_pose_or_null: the winner's pose on the device (fused forms), delivered with the report.  deliver: the last launch
+// stores report, key and pose into cs->h_rep and then cs->rep_seq (incremented here) into its word CS_REP_FLAG
+#define CS_REP_WORDS 30                         // sizeof(slamhip_search_report) / 4
+#define CS_REP_KEY 30                           // words of h_rep: the key (2), the pose (4: x, y, theta normalised, theta), the completion word
+#define CS_REP_POSE 32
+#define CS_REP_FLAG 63
+int32_t cs_launch_search_report(slamhip_cs *cs, const float pose[3], int32_t band, const float *d_pose_or_null, bool deliver);
+int32_t cs_search_report_copy(slamhip_cs *cs, const float *d_pose_or_null);   // ... or by copies into cs->h_rep (enqueued; without the mailbox)
 bool cs_k1_layout_legal(const slamhip_cs *cs);   // distance.hip: are the layout's counts of ray ranges legal for the scan now set?
 void cs_layout_idle_refresh(slamhip_cs *cs);   // host only: call between a search's enqueue and the wait for its result
 // coreslam.hip: produces a device-generated jitter list that is still pending (slamhip_cs_generate_offsets)

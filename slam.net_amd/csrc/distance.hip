@@ -1208,6 +1208,7 @@ int32_t cs_alloc_candidates(slamhip_cs *cs, int count)
     SH_HIP(hipMalloc(&cs->d_grp_bounds, sizeof(float) * 8 * (size_t)(cap / K1_GROUP_SMALL + 2)));      // (the smallest groups: the most)
     cs->cap_grp = cap / K1_GROUP_SMALL + 2;
     cs->cap_cand = cap;
+    cs->rep_dist_valid = false;
     cs->shard_first = -1; cs->shard_count = -1;
     return SLAMHIP_OK;
 }
@@ -2115,6 +2116,7 @@ int32_t cs_launch_distance(slamhip_cs *cs, int mode, const float pose[3], int co
 {
     slamhip_ctx *ctx = cs->ctx;
     if (cs->n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "no scan set (slamhip_cs_set_scan)");
+    cs->rep_dist_valid = false;                                    // (host state: slamhip_cs_search_distances answers for the last REPORT search only; cs_launch_search_report sets it)
     SH_TRY(cs_flush_scan(cs));
     cs->k1_launch_no = cs->launch_count;
     static const int force_global = (int)sh_env_int("SLAMHIP_K1_GLOBAL", 0);
@@ -2200,4 +2202,170 @@ int32_t cs_launch_distance(slamhip_cs *cs, int mode, const float pose[3], int co
 
 fallback:
     return k1_launch_fallback(cs, mode, pose3, count, sane, dist, key, ring_slot, ring_reset);
+}
+
+// ---- the search report --------------------------------------------------------------------------------------------
+// slamhip_search_report (slamhip.h) of a full-range search whose launch kept every candidate's distance (k1_finish: dist_out, flat
+// order) and left its packed arg-min key in a device word.  Two launches behind the search on the operator's stream, ordered by
+// the stream alone (no hand-off inside a launch, no floating-point atomics):
+//   k1_report_reduce  grid-stride over the K distances and the flat jitter list: counts (unscored, ties, band set), the runner-up
+//                     (64-bit minimum over the keys that differ from the best key) and the nine binary64 sums over the band set,
+//                     per workgroup into the workgroup's own slot.  The workgroup count depends on K alone, a lane adds its terms
+//                     in index order, lanes and wavefronts combine in a fixed tree: the bits do not depend on timing;
+//   k1_report_inmap   one workgroup: nb_points (:247) of the winner over the rays -- (px, py, c, s) by k1_candidate, as the search
+//                     forms a mode-1 candidate, :240-244 per ray -- then the slots in index order, the finished report into device
+//                     memory and, for a blocking caller, report + key + pose into its pinned block, released at system scope.
+// At 16 384 candidates the first launch reads 256 KB: launch-bound, one pass.
+#define K1_REP_THREADS 256
+#define K1_REP_MAX_WGS 64
+#define K1_REP_PER_WG 2048             // candidates per workgroup (up to K1_REP_MAX_WGS workgroups; beyond, the stride grows)
+struct k1_rep_slot {
+    double sum[9];                     // dx, dy, dth, dx*dx, dx*dy, dx*dth, dy*dy, dy*dth, dth*dth over the workgroup's part of the band set
+    unsigned long long runner;         // minimum of its keys != the best key (all ones: none)
+    int n_unscored, n_ties, n_band, pad_;
+};
+static_assert(sizeof(k1_rep_slot) == 96, "slot layout");
+static_assert(sizeof(slamhip_search_report) == 120 && sizeof(slamhip_search_report) == 4 * CS_REP_WORDS, "slamhip_search_report: 9 doubles + 12 int32, no padding");
+static inline int k1_rep_wgs(int K) { const int g = sh_div_up(K, K1_REP_PER_WG); return g < 1 ? 1 : g > K1_REP_MAX_WGS ? K1_REP_MAX_WGS : g; }
+
+__global__ void __launch_bounds__(K1_REP_THREADS)
+k1_report_reduce(const int32_t *__restrict__ dist, const float *__restrict__ offs_flat, int K, const unsigned long long *__restrict__ best_key,
+                 int band, k1_rep_slot *__restrict__ slots)
+{
+    __shared__ double s_sum[K1_REP_THREADS / 64][9];
+    __shared__ unsigned long long s_run[K1_REP_THREADS / 64];
+    __shared__ int s_cnt[K1_REP_THREADS / 64][3];
+    const unsigned long long best = *best_key;
+    const int32_t best_dist = (int32_t)(uint32_t)(best >> 32);
+    double sum[9] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    unsigned long long runner = ~0ull;
+    int n_unscored = 0, n_ties = 0, n_band = 0;
+    for (int i = (int)blockIdx.x * K1_REP_THREADS + (int)threadIdx.x; i < K; i += (int)gridDim.x * K1_REP_THREADS) {
+        const int32_t d = dist[i];
+        const unsigned long long key = ((unsigned long long)(uint32_t)d << 32) | (uint32_t)i;
+        if (key != best && key < runner) runner = key;
+        n_unscored += d == INT32_MAX ? 1 : 0;
+        n_ties += d == best_dist ? 1 : 0;
+        if (d != INT32_MAX && (long long)d - (long long)best_dist <= (long long)band) {
+            n_band++;
+            if (i > 0) {                                           // (candidate 0 is the un-jittered pose: all its terms are zero)
+                const double x = (double)offs_flat[3 * (size_t)(i - 1)], y = (double)offs_flat[3 * (size_t)(i - 1) + 1], t = (double)offs_flat[3 * (size_t)(i - 1) + 2];
+                sum[0] += x; sum[1] += y; sum[2] += t;
+                sum[3] += x * x; sum[4] += x * y; sum[5] += x * t; sum[6] += y * y; sum[7] += y * t; sum[8] += t * t;   // (products of two binary32 values: exact)
+            }
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 9; k++) sum[k] += __shfl_down(sum[k], off, 64);
+        const unsigned long long o = __shfl_down(runner, off, 64);
+        runner = o < runner ? o : runner;
+        n_unscored += __shfl_down(n_unscored, off, 64); n_ties += __shfl_down(n_ties, off, 64); n_band += __shfl_down(n_band, off, 64);
+    }
+    const int lane = (int)threadIdx.x & 63, wv = (int)threadIdx.x >> 6;
+    if (lane == 0) {
+        for (int k = 0; k < 9; k++) s_sum[wv][k] = sum[k];
+        s_run[wv] = runner; s_cnt[wv][0] = n_unscored; s_cnt[wv][1] = n_ties; s_cnt[wv][2] = n_band;
+    }
+    __syncthreads();
+    k1_rep_slot *slot = slots + blockIdx.x;
+    if (threadIdx.x < 9) {
+        double v = s_sum[0][threadIdx.x];
+        for (int w = 1; w < K1_REP_THREADS / 64; w++) v += s_sum[w][threadIdx.x];
+        slot->sum[threadIdx.x] = v;
+    } else if (threadIdx.x == 9) {
+        unsigned long long r = s_run[0];
+        int c[3] = { s_cnt[0][0], s_cnt[0][1], s_cnt[0][2] };
+        for (int w = 1; w < K1_REP_THREADS / 64; w++) { r = s_run[w] < r ? s_run[w] : r; for (int k = 0; k < 3; k++) c[k] += s_cnt[w][k]; }
+        slot->runner = r; slot->n_unscored = c[0]; slot->n_ties = c[1]; slot->n_band = c[2]; slot->pad_ = 0;
+    }
+}
+
+__global__ void __launch_bounds__(K1_REP_THREADS)
+k1_report_inmap(int S, const float2 *__restrict__ pts, int n_points, const float *__restrict__ offs_flat,
+                float bx, float by, float bth, float scale, const int32_t *__restrict__ dist, int K, const unsigned long long *__restrict__ best_key,
+                int band, const k1_rep_slot *__restrict__ slots, int n_slots, const float *__restrict__ pose4,
+                slamhip_search_report *__restrict__ out, uint32_t *__restrict__ host, uint32_t seq)
+{
+    __shared__ int s_in[K1_REP_THREADS / 64];
+    __shared__ slamhip_search_report s_rep;
+    const unsigned long long best = *best_key;
+    const uint32_t flat = (uint32_t)best;
+    float c3[3] = { 0.0f, 0.0f, 0.0f };
+    if (flat > 0 && flat < (uint32_t)K) { c3[0] = offs_flat[3 * (size_t)(flat - 1)]; c3[1] = offs_flat[3 * (size_t)(flat - 1) + 1]; c3[2] = offs_flat[3 * (size_t)(flat - 1) + 2]; }
+    const float4 q = k1_candidate<1, false>(c3, bx, by, bth, scale);          // :232-235, :635-637
+    int n_in = 0;
+    for (int r = (int)threadIdx.x; r < n_points; r += K1_REP_THREADS) {
+        float fx, fy;
+        k1_coords(q, pts[r], fx, fy);                                          // :240-241
+        const int ix = sh_f2i(fx), iy = sh_f2i(fy);
+        n_in += (((unsigned)ix < (unsigned)S) & ((unsigned)iy < (unsigned)S)) ? 1 : 0;   // :244
+    }
+    for (int off = 32; off > 0; off >>= 1) n_in += __shfl_down(n_in, off, 64);
+    if ((threadIdx.x & 63) == 0) s_in[threadIdx.x >> 6] = n_in;
+    __syncthreads();
+    if (threadIdx.x < 9) {                                                     // the slots in index order
+        double v = slots[0].sum[threadIdx.x];
+        for (int g = 1; g < n_slots; g++) v += slots[g].sum[threadIdx.x];
+        if (threadIdx.x < 3) s_rep.sum_off[threadIdx.x] = v; else s_rep.sum_off2[threadIdx.x - 3] = v;
+    } else if (threadIdx.x == 9) {
+        unsigned long long r = ~0ull;
+        int c[3] = { 0, 0, 0 };
+        for (int g = 0; g < n_slots; g++) { r = slots[g].runner < r ? slots[g].runner : r; c[0] += slots[g].n_unscored; c[1] += slots[g].n_ties; c[2] += slots[g].n_band; }
+        int tot = 0;
+        for (int w = 0; w < K1_REP_THREADS / 64; w++) tot += s_in[w];
+        s_rep.best_dist = (int32_t)(uint32_t)(best >> 32); s_rep.best_index = (int32_t)flat;
+        s_rep.runner_dist = r == ~0ull ? INT32_MAX : (int32_t)(uint32_t)(r >> 32); s_rep.runner_index = r == ~0ull ? -1 : (int32_t)(uint32_t)r;
+        s_rep.dist0 = dist[0]; s_rep.n_candidates = K; s_rep.n_unscored = c[0]; s_rep.n_ties = c[1]; s_rep.band = band; s_rep.n_band = c[2];
+        s_rep.n_in_map = tot; s_rep.n_points = n_points;
+    }
+    __syncthreads();
+    if (threadIdx.x >= 64) return;                                             // (one wavefront delivers: its lanes' stores, a barrier of its own, the release)
+    const uint32_t *w = (const uint32_t *)&s_rep;
+    if (threadIdx.x < CS_REP_WORDS) ((uint32_t *)out)[threadIdx.x] = w[threadIdx.x];
+    if (!host) return;
+    if (threadIdx.x < CS_REP_WORDS) host[threadIdx.x] = w[threadIdx.x];
+    else if (threadIdx.x == CS_REP_KEY) host[CS_REP_KEY] = (uint32_t)best;
+    else if (threadIdx.x == CS_REP_KEY + 1) host[CS_REP_KEY + 1] = (uint32_t)(best >> 32);
+    else if (threadIdx.x >= CS_REP_POSE && threadIdx.x < CS_REP_POSE + 4) host[threadIdx.x] = pose4 ? __float_as_uint(pose4[threadIdx.x - CS_REP_POSE]) : 0u;
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (threadIdx.x == 0) __hip_atomic_store(host + CS_REP_FLAG, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+int32_t cs_launch_search_report(slamhip_cs *cs, const float pose[3], int32_t band, const float *d_pose_or_null, bool deliver)
+{
+    slamhip_ctx *ctx = cs->ctx;
+    const int K = cs->n_offs + 1;
+    if (K > cs->cap_cand || !cs->d_dist) SH_FAIL(SLAMHIP_ERR_STATE, "the distance buffer holds %d entries, the report search has %d candidates", cs->cap_cand, K);
+    if (!cs->d_rep) {
+        SH_HIP(hipMalloc(&cs->d_rep, sizeof(k1_rep_slot) * K1_REP_MAX_WGS + 128));
+        SH_HIP(hipHostMalloc((void **)&cs->h_rep, 256, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(cs->h_rep, 0, 256);
+        cs->rep_seq = 0;
+    }
+    k1_rep_slot *slots = (k1_rep_slot *)cs->d_rep;
+    slamhip_search_report *d_out = (slamhip_search_report *)((char *)cs->d_rep + sizeof(k1_rep_slot) * K1_REP_MAX_WGS);
+    const int n_slots = k1_rep_wgs(K);
+    SH_TRY(cs_flush_scan(cs));                                     // (the second launch reads the scan)
+    hipLaunchKernelGGL(k1_report_reduce, dim3(n_slots), dim3(K1_REP_THREADS), 0, ctx->stream, (const int32_t *)cs->d_dist, (const float *)cs->d_offs_flat, K,
+                       (const unsigned long long *)cs->d_key, (int)band, slots);
+    const uint32_t seq = deliver ? ++cs->rep_seq : 0u;
+    hipLaunchKernelGGL(k1_report_inmap, dim3(1), dim3(K1_REP_THREADS), 0, ctx->stream, cs->hs, (const float2 *)cs->d_pts, cs->n_points,
+                       (const float *)cs->d_offs_flat, pose[0], pose[1], pose[2], cs->hscale, (const int32_t *)cs->d_dist, K, (const unsigned long long *)cs->d_key,
+                       (int)band, (const k1_rep_slot *)slots, n_slots, d_pose_or_null, d_out, deliver ? cs->h_rep : (uint32_t *)nullptr, seq);
+    SH_HIP(hipGetLastError());
+    cs->rep_dist_valid = true; cs->rep_K = K;
+    return SLAMHIP_OK;
+}
+
+// the same hand-over by copies (SLAMHIP_NO_HOSTWAIT=1: no launch stores into host memory): enqueued, the caller waits for the stream
+int32_t cs_search_report_copy(slamhip_cs *cs, const float *d_pose_or_null)
+{
+    slamhip_ctx *ctx = cs->ctx;
+    const char *d_out = (const char *)cs->d_rep + sizeof(k1_rep_slot) * K1_REP_MAX_WGS;
+    SH_HIP(hipMemcpyAsync(cs->h_rep, d_out, sizeof(slamhip_search_report), hipMemcpyDeviceToHost, ctx->stream));
+    SH_HIP(hipMemcpyAsync(cs->h_rep + CS_REP_KEY, cs->d_key, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (d_pose_or_null) SH_HIP(hipMemcpyAsync(cs->h_rep + CS_REP_POSE, d_pose_or_null, 4 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    return SLAMHIP_OK;
 }

@@ -42,6 +42,8 @@ struct slamhip_csproc {
     uint64_t seed, scan_no;
     bool pinned;
     bool lattice;                                         // candidates as a heading lattice (slamhip_csproc_set_lattice)
+    bool report_on, report_valid; int32_t report_band;    // slamhip_csproc_set_search_report: the last searching Update's report
+    slamhip_search_report report;
     std::vector<float> cloud;
     // ScanSegmentsToCloud: a lidar's ray angles repeat from scan to scan, so the deterministic sine / cosine of ray r is kept with
     // the angle it was made for and reused while the angle is bit-identical (the same floats by construction; 6 -> 1.5 us per scan)
@@ -63,6 +65,7 @@ extern "C" int32_t slamhip_csproc_reset(slamhip_csproc *p)
     memcpy(p->pose, p->start_pose, sizeof(float) * 3);                    // :172
     p->last_odo[0] = p->last_odo[1] = p->last_odo[2] = 0.0f;              // :173
     p->scan_count = 0;                                                    // :174
+    p->report_valid = false;
     return SLAMHIP_OK;
 }
 
@@ -108,6 +111,23 @@ extern "C" int32_t slamhip_csproc_set_lattice(slamhip_csproc *p, int32_t on)
 {
     SH_CHECK_ARG(p);
     p->lattice = on != 0;
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_csproc_set_search_report(slamhip_csproc *p, int32_t on, int32_t band)
+{
+    SH_CHECK_ARG(p && (on == 0 || on == 1) && band >= 0);
+    p->report_on = on == 1; p->report_band = band;
+    if (!p->report_on) p->report_valid = false;
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_csproc_get_report(slamhip_csproc *p, slamhip_search_report *out, int32_t *out_valid)
+{
+    SH_CHECK_ARG(p && out && out_valid);
+    const bool valid = p->report_on && p->report_valid;
+    if (valid) *out = p->report; else memset(out, 0, sizeof(*out));
+    *out_valid = valid ? 1 : 0;
     return SLAMHIP_OK;
 }
 
@@ -199,6 +219,11 @@ extern "C" int32_t slamhip_csproc_update(slamhip_csproc *p, const float *seg_pos
         }
         g_pt.lap(2);
         // set_scan (:723), search (:732), NormalizeAngle (:746) and both map updates (:750-751): the search launch first where it can
+        if (p->report_on) {                                               // (the report forms: the ordinary launch order, slamhip.h)
+            p->report_valid = false;
+            SH_TRY(slamhip_cs_scan_search_and_update_report(p->cs, p->cloud.data(), n, search, p->report_band, p->hole_width, p->quality, p->max_hits, new_pose, &p->report));
+            p->report_valid = true;
+        } else
         SH_TRY(slamhip_cs_scan_search_and_update(p->cs, p->cloud.data(), n, search, p->hole_width, p->quality, p->max_hits, new_pose, nullptr, nullptr));
         // (state moves only when the scan went through: a failed call leaves the odometry baseline and the list number where they
         // were, as the reference's exception would -- the next Update searches from the same baseline)
@@ -213,6 +238,7 @@ extern "C" int32_t slamhip_csproc_update(slamhip_csproc *p, const float *seg_pos
     if (p->scan_count < p->search_beginning) p->scan_count++;             // :741
     else if (n == 0) {
         // searching scan with an empty cloud: every distance is int.MaxValue, the base pose wins (:257,:626-628)
+        p->report_valid = false;                                          // (nothing was searched)
         for (int i = 0; i < 3; i++) new_pose[i] = p->pose[i] + (odo[i] - p->last_odo[i]);
         memcpy(p->last_odo, odo, sizeof(odo));
         new_pose[2] = sh_normalize_angle(new_pose[2]);
