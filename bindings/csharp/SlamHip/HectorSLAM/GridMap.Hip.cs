@@ -31,7 +31,7 @@ namespace HectorSLAM.Map
         public GridMap(float mapResolution, Point size, Vector2 offset, Device device = null)
         {
             if (offset != Vector2.Zero)
-                throw new NotSupportedException("the device maps have no offset (the reference always passes Vector2.Zero, HectorSLAMProcessor.cs:71)");
+                throw new NotSupportedException("the device maps have no offset (the reference always passes Vector2.Zero, HectorSLAMProcessor.cs:71): move the window with MapRepMultiMap.Shift (slamhip_hs_shift)");
             Device = device ?? new Device(0);
             OwnsDevice = device == null;
             Native.Check(Native.slamhip_hs_create(Device.Ctx.Ptr, mapResolution, size.X, size.Y, 1, out IntPtr h));

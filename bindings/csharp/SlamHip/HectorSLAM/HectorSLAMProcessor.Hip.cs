@@ -24,6 +24,7 @@ namespace HectorSLAM.Main
         private float minDistanceDiff = 0.3f, minAngleDiff = 0.13f;
         private bool referenceSummation;
         private bool matchReport;
+        private int scrollTrigger;
 
         public MapRepMultiMap MapRep { get; private set; }
         public Vector3 LastMapUpdatePose { get; private set; }
@@ -77,6 +78,26 @@ namespace HectorSLAM.Main
             set { Native.Check(Native.slamhip_hsproc_set_match_report(proc.Ptr, value ? 1 : 0)); matchReport = value; }
         }
 
+        /// <summary>Keep the robot in the window (slamhip_hsproc_set_scroll): 0 (default) off; > 0: at the end of an Update whose match
+        /// pose lies more than this many level-0 cells from the window's middle on an axis, the pyramid is shifted on the device
+        /// (MapRepMultiMap.Shift) so that the pose is back near the middle.  Hints, MatchPose and LastMapUpdatePose stay world poses;
+        /// Origin says where the window lies.  Valid: 0 .. min(width, height) / 2 - (1 << (numDepth - 1)) - 1.</summary>
+        public int ScrollTrigger
+        {
+            get => scrollTrigger;
+            set { Native.Check(Native.slamhip_hsproc_set_scroll(proc.Ptr, value)); scrollTrigger = value; }
+        }
+
+        /// <summary>The window's origin in level-0 cells (slamhip_hsproc_get_origin): the sum of all shifts since the last Reset.</summary>
+        public (long X, long Y) Origin
+        {
+            get
+            {
+                Native.Check(Native.slamhip_hsproc_get_origin(proc.Ptr, out long ox, out long oy));
+                return (ox, oy);
+            }
+        }
+
         /// <summary>The report of the last Update's match, or null: before the first match, after Reset, after an Update with
         /// mapWithoutMatching, and while MatchReport is off.</summary>
         public SlamHip.MatchReport? LastMatchReport { get; private set; }   // (qualified: MatchReport alone is the property above)
@@ -108,6 +129,7 @@ namespace HectorSLAM.Main
                 Native.Check(Native.slamhip_hsproc_update(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), poseHintWorld,
                                                           mapWithoutMatching ? 1 : 0, out updated));
             Refresh();
+            if (scrollTrigger != 0) MapRep.MarkStale();                  // (a shift moves the maps whether or not this scan redrew them)
             if (updated == 0) return false;
             MapRep.MarkStale();
             logger?.LogInformation($"Map update at {MatchPose.X:F3} {MatchPose.Y:F3} {MatchPose.Z:F4}");

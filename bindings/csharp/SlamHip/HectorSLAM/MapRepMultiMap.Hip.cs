@@ -25,7 +25,7 @@ namespace HectorSLAM.Main
         public MapRepMultiMap(float mapResolution, Point mapSize, int numDepth, Vector2 startCoords, Device device = null)
         {
             if (startCoords != Vector2.Zero)
-                throw new NotSupportedException("the device maps have no offset");
+                throw new NotSupportedException("the device maps have no offset: move the window with MapRepMultiMap.Shift (slamhip_hs_shift)");
             Device = device ?? new Device(0);
             ownsDevice = device == null;
             Native.Check(Native.slamhip_hs_create(Device.Ctx.Ptr, mapResolution, mapSize.X, mapSize.Y, numDepth, out IntPtr h));
@@ -91,6 +91,26 @@ namespace HectorSLAM.Main
             SetScan(scan);
             Native.Check(Native.slamhip_hs_update_by_scan(Pyramid.Ptr, pose));
             foreach (OccGridMap m in Maps) m.mirrorStale = true;
+        }
+
+        /// <summary>Move the window by (+dx, +dy) level-0 cells on the device, in stream order (slamhip_hs_shift): on level l new cell
+        /// (x, y) holds what old cell (x + (dx >> l), y + (dy >> l)) held, and exposed cells are LogOddsCell.Reset().  dx and dy must be
+        /// multiples of 1 << (NumLevels - 1).  MatchData and UpdateByScan go on working in the window's frame: a world point p lies
+        /// at p - Origin * Maps[0].CellLength there.  Not possible while ReferenceCache is on.</summary>
+        public void Shift(int dx, int dy)
+        {
+            Native.Check(Native.slamhip_hs_shift(Pyramid.Ptr, dx, dy));
+            MarkStale();
+        }
+
+        /// <summary>The sum of all shifts since construction or the last Reset, in level-0 cells (slamhip_hs_origin).</summary>
+        public (long X, long Y) Origin
+        {
+            get
+            {
+                Native.Check(Native.slamhip_hs_origin(Pyramid.Ptr, out long ox, out long oy));
+                return (ox, oy);
+            }
         }
 
         /// <summary>The device maps changed behind this object's back (HectorSLAMProcessor.Update drives the native processor): host mirrors are stale.</summary>

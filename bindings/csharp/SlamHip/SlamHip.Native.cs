@@ -135,6 +135,8 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_set_match_threads(IntPtr hs, int numThreads);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_reference_cache(IntPtr hs, int on);
         [DllImport(Lib)] internal static extern int slamhip_hs_update_by_scan(IntPtr hs, in Vector3 robotPoseWorld);
+        [DllImport(Lib)] internal static extern int slamhip_hs_shift(IntPtr hs, int dx, int dy);
+        [DllImport(Lib)] internal static extern int slamhip_hs_origin(IntPtr hs, out long ox, out long oy);
         // HectorSLAM, processor level (HectorSLAMProcessor.cs:66-138): the Update state machine in the library -- match, the gate of :107-109 evaluated
         // on the device, the grid update enqueued behind the match before the pose is back (one blocking wait per scan instead of two)
         [DllImport(Lib)] internal static extern int slamhip_hsproc_create(IntPtr ctx, float mapResolution, int width, int height, in Vector3 startPose, int numDepth, out IntPtr proc);
@@ -146,6 +148,8 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_get_report(IntPtr proc, out MatchReport report, out int valid);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_set_thresholds(IntPtr proc, float minDistanceDiff, float minAngleDiff);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_hs(IntPtr proc, out IntPtr hs);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_set_scroll(IntPtr proc, int triggerCells);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_get_origin(IntPtr proc, out long ox, out long oy);
 
         // ---- one process, several GPUs -------------------------------------------------------------------------------
         [DllImport(Lib)] internal static extern int slamhip_group_create(int* deviceOrdinals, int n, float physicalMapSize, int holeMapSize, int obstacleMapSize, out IntPtr group);

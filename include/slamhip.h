@@ -554,6 +554,30 @@ int32_t slamhip_hs_match_best(slamhip_hs *hs, const float *hint_poses, int32_t B
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
 
+/* The scrolling window -- something the reference lacks (its `offset`, GridMap.cs:45, is ignored by UpdateByScan,
+ * OccGridMap.cs:120-123, and by the matcher, ScanMatcher.cs:139-142): the contents of the whole pyramid move by an integer
+ * number of cells, on the device, in stream order, so that a robot that drives out of the window can take the window along.
+ * dx, dy are level-0 cells and the window moves by (+dx, +dy): on level l, new cell (x, y) holds what old cell
+ * (x + (dx >> l), y + (dy >> l)) held.  dx and dy must each be a multiple of g = 1 << (levels - 1), so that every level
+ * moves by a whole number of cells (the arithmetic shift is then exact).  A new cell whose source lies outside its level becomes
+ * LogOddsCell.Reset() -- Value 0.0f, UpdateIndex -1 (LogOddsCell.cs:38-42) -- with probability 0.5f; a move by a level's width
+ * or height or more clears that level.  The probabilities move with the cells; update indices and the cache epoch do not
+ * change.
+ * The origin (ox, oy) is the sum of all shifts since slamhip_hs_create or the last slamhip_hs_reset (which sets it to 0: an
+ * empty map has no frame to keep), in level-0 cells; host-side bookkeeping only.  THE CONTRACT: a world point p lies at
+ * p - origin * cell_length(level 0) in the frame that slamhip_hs_match*, slamhip_hs_hessian, slamhip_hs_update_by_scan and
+ * the match reports use -- those calls go on working in the window's frame, with the transforms they always had; the caller
+ * (or slamhip_hsproc_set_scroll) subtracts the offset from hints and poses going in and adds it to poses coming out.
+ * Enqueue-only on the operator's stream: it runs behind every grid update and match already enqueued and ahead of whatever
+ * is enqueued later; no host wait.  One launch moves all levels, cells and probabilities, and writes the exposed bands.
+ * The first shift allocates a second set of arrays, 12 bytes per cell and level (63 MiB at 2048^2 x 3 levels): the launch reads
+ * one set and writes the other, and the two swap roles.  If that allocation fails: SLAMHIP_ERR_NOMEM, nothing changed.
+ * dx == dy == 0: SLAMHIP_OK, no launch.  SLAMHIP_ERR_INVALID, maps and origin unchanged: dx or dy not a multiple of g; the
+ * reference's cache is on (slamhip_hs_set_reference_cache) -- its literal stale entries have no meaning under an operation
+ * the reference lacks.  A poisoned context: SLAMHIP_ERR_TIMEOUT. */
+int32_t slamhip_hs_shift(slamhip_hs *hs, int32_t dx, int32_t dy);
+int32_t slamhip_hs_origin(slamhip_hs *hs, int64_t *ox, int64_t *oy);
+
 /* ------------------------------------------------------------------------------------------------
  * HectorSLAM, processor level
  * ---------------------------------------------------------------------------------------------- */
@@ -581,7 +605,21 @@ int32_t slamhip_hsproc_set_match_report(slamhip_hsproc *p, int32_t on);
 /* The report of the last slamhip_hsproc_update's match (:93); *out_valid = 0 and *out zeroed before the first match, after
  * slamhip_hsproc_reset, after an Update with mapWithoutMatching (:100) and while reports are off (switching them off drops the
  * last report). */
+/* The report's pose_map stays in the WINDOW's frame (slamhip_hsproc_set_scroll, slamhip_hs_shift): map coordinates of the device's
+ * level, as the match saw them. */
 int32_t slamhip_hsproc_get_report(slamhip_hsproc *p, slamhip_match_report *out, int32_t *out_valid);
+/* Keep the robot in the window (slamhip_hs_shift).  trigger_cells = 0 (default): off -- Update issues exactly the launches it
+ * issues without this call.  trigger_cells > 0: at the end of every slamhip_hsproc_update -- the match pose on the host, this
+ * scan's grid update enqueued -- with (lx, ly) the match pose in the window's frame, in binary32: cx = (int)floorf(lx * stm0),
+ * cy likewise (stm0 = 1 / cell_length of level 0); per axis, if |cx - w0 / 2| > trigger_cells then q = ((cx - w0 / 2) / g) * g
+ * (C integer division, toward zero; g = 1 << (levels - 1)), else q = 0; if either q is non-zero, slamhip_hs_shift(qx, qy),
+ * enqueued behind the update.  Poses cross this interface in the WORLD frame whatever the window did: the hint of
+ * slamhip_hsproc_update is taken as hint - (float)origin * cell0, and slamhip_hsproc_get returns the stored window-frame
+ * poses + (float)origin * cell0 (float.MinValue, "never updated", absorbs both).  Valid: 0 <= trigger_cells <
+ * min(w0, h0) / 2 - g; anything else SLAMHIP_ERR_INVALID, the setting unchanged.  The setting survives slamhip_hsproc_reset;
+ * the origin returns to 0 there (slamhip_hs_reset).  slamhip_hsproc_get_origin: slamhip_hs_origin of the processor's own hs. */
+int32_t slamhip_hsproc_set_scroll(slamhip_hsproc *p, int32_t trigger_cells);
+int32_t slamhip_hsproc_get_origin(slamhip_hsproc *p, int64_t *ox, int64_t *oy);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -179,6 +179,8 @@ def _declare(L):
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
+        "slamhip_hs_shift": (i32, [vp, i32, i32]),
+        "slamhip_hs_origin": (i32, [vp, P(i64), P(i64)]),
         "slamhip_hsproc_create": (i32, [vp, f, i32, i32, fp, i32, vpp]),
         "slamhip_hsproc_destroy": (i32, [vp]),
         "slamhip_hsproc_reset": (i32, [vp]),
@@ -188,6 +190,8 @@ def _declare(L):
         "slamhip_hsproc_get_report": (i32, [vp, rp, ip]),
         "slamhip_hsproc_set_thresholds": (i32, [vp, f, f]),
         "slamhip_hsproc_hs": (i32, [vp, vpp]),
+        "slamhip_hsproc_set_scroll": (i32, [vp, i32]),
+        "slamhip_hsproc_get_origin": (i32, [vp, P(i64), P(i64)]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),

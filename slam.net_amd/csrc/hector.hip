@@ -41,6 +41,8 @@ struct hs_level {
     slamhip_cell *d_cells;                 // mapArray (GridMap.cs:13) in the reference's own layout, LogOddsCell {UpdateIndex, Value} (LogOddsCell.cs:16-21): the grid
                                            // update reads and writes a cell with ONE 8-byte access (two arrays: 30.8 -> 26.9 us per update with the second one left out)
     float *d_prob;                         // GetCachedProbability of every cell (OccGridMap.cs:97-107), kept current by every writer of d_cells
+    slamhip_cell *d_cells_alt; float *d_prob_alt;   // the second set slamhip_hs_shift moves the window into (allocated by the first shift); the
+                                           // launch reads d_cells / d_prob, writes these, and the host then swaps the names
     unsigned long long *d_cache;           // cacheArray (OccGridMap.cs:16), one CachedMapElement {Value, Index} per cell as ONE 8-byte word
                                            // (Value's bits low, Index high); allocated when the reference's cache is first turned on
     int curr_update_index;                 // OccGridMap.cs:20
@@ -80,6 +82,7 @@ struct slamhip_hs {
     // device-visible block the host reads them from -- a single blocking match stores its report there itself, in front of the
     // mailbox's sequence word (the mailbox is 64 B, the report 76)
     slamhip_match_report *d_rep, *h_rep; int cap_rep; unsigned long long *d_best_key;
+    int64_t win_ox, win_oy;                                // slamhip_hs_shift: where cell (0, 0) of level 0 lies in the world, in level-0 cells (host-side books only)
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -1437,6 +1440,74 @@ __global__ void __launch_bounds__(256) k5_checksum_cells(const slamhip_cell *__r
     if ((threadIdx.x & 63) == 0) { atomicAdd(out, av); atomicAdd(out + 1, au); }
 }
 
+// ---- K6: the scrolling window (slamhip_hs_shift) -------------------------------------------------------------------------------
+// Something the reference lacks (its `offset`, GridMap.cs:45, is ignored by UpdateByScan and by the matcher): the CONTENTS of every
+// level move by a whole number of cells, so that K4 and K5 go on working in the window's frame with the transforms they have.  On
+// level l new cell (x, y) holds what old cell (x + sx, y + sy) held, sx = dx >> l; a cell whose source lies outside the level
+// becomes LogOddsCell.Reset() (LogOddsCell.cs:38-42) with probability 0.5f -- exp(0) / (exp(0) + 1), what k5_fill_cells and
+// k5_refresh_prob give for Value 0.  Not in place (a workgroup would read what another has overwritten): the launch reads one set
+// of arrays and writes the other, and the host swaps the pointers behind it -- every launch takes its pointers from hs->lv when it
+// is enqueued (levels_arg, hs_update_enqueue's k5_arg, the downloads and reports), none is kept past a call, and the stream orders
+// the launches.  ONE launch for all levels, cells and probabilities, exposed bands included.
+// Lane mapping: a workgroup owns K6_BLOCK consecutive cells of a level's flat array; a lane moves 16-byte units of the DESTINATION,
+// which are always aligned (two cells, four probabilities): one store each, consecutive lanes consecutive units.  A unit that lies
+// in one row with all its sources inside the map is one load as wide as the source's alignment allows -- the source index differs
+// from the destination's by sy * w + sx, a multiple of 4 on level 0 of a pyramid of three levels or more, of 2 on level 1, of
+// anything on the coarsest (which is small); every other unit (a row's end where w is no multiple of the unit, the exposed band,
+// the array's tail) goes element by element with the bounds test per element.
+#define K6_BLOCK 1024
+struct k6_level { int w, h, sx, sy, blk0; const slamhip_cell *src_c; slamhip_cell *dst_c; const float *src_p; float *dst_p; };
+struct k6_arg { k6_level lv[HS_MAX_LEVELS]; int n; };
+
+template <typename T, int N>                   // N elements of T are 16 bytes; i: the unit's first element, a multiple of N
+__device__ static __forceinline__ void k6_unit(const T *__restrict__ src, T *__restrict__ dst, int w, int h, int sx, int sy, int i, int n, const T fill)
+{
+    static_assert(sizeof(T) * N == 16, "a unit is 16 bytes");
+    if (i >= n) return;
+    struct alignas(16) unit { T e[N]; };
+    struct alignas(8) half { T e[N / 2]; };
+    const int y = i / w, x = i - y * w;
+    const int ys = y + sy, xs = x + sx;
+    if (i + N <= n && x + N <= w && ys >= 0 && ys < h && xs >= 0 && xs + N <= w) {
+        const T *s = src + ((size_t)ys * w + xs);                         // (inside the array: 0 <= ys < h, 0 <= xs, xs + N <= w)
+        const unsigned mis = (unsigned)(xs + ys * w) & (N - 1);
+        unit v;
+        if (mis == 0) v = *(const unit *)s;
+        else if (N == 4 && mis == 2) {
+            const half a = *(const half *)s, b = *(const half *)(s + N / 2);
+#pragma unroll
+            for (int k = 0; k < N / 2; k++) { v.e[k] = a.e[k]; v.e[N / 2 + k] = b.e[k]; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < N; k++) v.e[k] = s[k];
+        }
+        *(unit *)(dst + i) = v;
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+        const int ik = i + k;
+        if (ik >= n) break;
+        const int yk = ik / w, xk = ik - yk * w;
+        const int yy = yk + sy, xx = xk + sx;
+        const bool in = yy >= 0 && yy < h && xx >= 0 && xx < w;
+        dst[ik] = in ? src[(size_t)yy * w + xx] : fill;
+    }
+}
+
+__global__ void __launch_bounds__(256) k6_shift(const k6_arg A)
+{
+    int lvl = 0;
+    for (int l = 1; l < A.n; l++) if ((int)blockIdx.x >= A.lv[l].blk0) lvl = l;
+    const k6_level &L = A.lv[lvl];
+    const int n = L.w * L.h;                                               // (<= 2^30: slamhip_hs_create bounds w and h by 32768)
+    const int base = ((int)blockIdx.x - L.blk0) * K6_BLOCK, t = threadIdx.x;
+    slamhip_cell reset; reset.update_index = -1; reset.value = 0.0f;       // LogOddsCell.Reset :38-42
+    k6_unit<slamhip_cell, 2>(L.src_c, L.dst_c, L.w, L.h, L.sx, L.sy, base + 2 * t, n, reset);
+    k6_unit<slamhip_cell, 2>(L.src_c, L.dst_c, L.w, L.h, L.sx, L.sy, base + K6_BLOCK / 2 + 2 * t, n, reset);
+    k6_unit<float, 4>(L.src_p, L.dst_p, L.w, L.h, L.sx, L.sy, base + 4 * t, n, 0.5f);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------
 static float prob_to_logodds(float prob) { const float odds = prob / (1.0f - prob); return logf(odds); }   // OccGridMap.cs:86-90
 
@@ -1469,6 +1540,7 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
     (void)hipStreamSynchronize(hs->ctx->stream);
     for (int l = 0; l < hs->n_levels; l++) {
         (void)hipFree(hs->lv[l].d_cells); (void)hipFree(hs->lv[l].d_prob); (void)hipFree(hs->lv[l].d_cache);
+        (void)hipFree(hs->lv[l].d_cells_alt); (void)hipFree(hs->lv[l].d_prob_alt);
     }
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
@@ -1493,6 +1565,73 @@ extern "C" int32_t slamhip_hs_reset(slamhip_hs *hs)
         L.curr_cache_index = 0;                                            // :248 (the cache entries are left as they are)
     }
     SH_HIP(hipStreamSynchronize(hs->ctx->stream));
+    hs->win_ox = hs->win_oy = 0;                                           // (slamhip_hs_shift: an empty map has no frame to keep)
+    return SLAMHIP_OK;
+}
+
+// The window moves by (+dx, +dy) level-0 cells (K6 above).  Enqueue-only: behind every update and match already on the operator's
+// stream, ahead of whatever is enqueued later; no host wait.
+extern "C" int32_t slamhip_hs_shift(slamhip_hs *hs, int32_t dx, int32_t dy)
+{
+    SH_CHECK_ARG(hs);
+    if (hs->ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
+    const int32_t g = 1 << (hs->n_levels - 1);
+    if ((dx & (g - 1)) != 0 || (dy & (g - 1)) != 0)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_hs_shift: dx = %d and dy = %d must be multiples of %d = 1 << (levels - 1), so that every level moves by whole cells",
+                dx, dy, g);
+    if (hs->ref_cache)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_hs_shift: the reference's cache is on (slamhip_hs_set_reference_cache) -- its literal stale entries have "
+                "no meaning under an operation the reference lacks; turn it off first");
+    if (dx == 0 && dy == 0) return SLAMHIP_OK;
+    SH_HIP(hipSetDevice(hs->ctx->device));
+    if (!hs->lv[0].d_cells_alt) {                                          // the first shift: the second set, all levels or none
+        for (int l = 0; l < hs->n_levels; l++) {
+            hs_level &L = hs->lv[l];
+            const size_t n = (size_t)L.w * L.h;
+            if (hipMalloc(&L.d_cells_alt, sizeof(slamhip_cell) * n) != hipSuccess || hipMalloc(&L.d_prob_alt, sizeof(float) * n) != hipSuccess) {
+                (void)hipGetLastError();
+                for (int k = 0; k < hs->n_levels; k++) {
+                    (void)hipFree(hs->lv[k].d_cells_alt); (void)hipFree(hs->lv[k].d_prob_alt);
+                    hs->lv[k].d_cells_alt = nullptr; hs->lv[k].d_prob_alt = nullptr;
+                }
+                SH_FAIL(SLAMHIP_ERR_NOMEM, "device allocation of the window's second set of arrays failed (level %d)", l);
+            }
+        }
+    }
+    k6_arg A;
+    memset(&A, 0, sizeof(A));
+    A.n = hs->n_levels;
+    int blocks = 0;
+    for (int l = 0; l < hs->n_levels; l++) {
+        const hs_level &L = hs->lv[l];
+        k6_level &K = A.lv[l];
+        K.w = L.w; K.h = L.h;
+        const int sx = dx >> l, sy = dy >> l;                              // (exact: dx and dy are multiples of 1 << (levels - 1); arithmetic shift)
+        // a move by the level's size or more clears the level: every source is then outside it whatever the other axis says, and
+        // the clamp keeps sy * w + sx inside 32 bits
+        K.sx = sx >= L.w ? L.w : sx <= -L.w ? -L.w : sx;
+        K.sy = sy >= L.h ? L.h : sy <= -L.h ? -L.h : sy;
+        K.blk0 = blocks;
+        K.src_c = L.d_cells; K.dst_c = L.d_cells_alt; K.src_p = L.d_prob; K.dst_p = L.d_prob_alt;
+        blocks += (int)(((size_t)L.w * L.h + K6_BLOCK - 1) / K6_BLOCK);
+    }
+    hipLaunchKernelGGL(k6_shift, dim3(blocks), dim3(256), 0, hs->ctx->stream, A);
+    SH_HIP(hipGetLastError());
+    for (int l = 0; l < hs->n_levels; l++) {
+        hs_level &L = hs->lv[l];
+        slamhip_cell *c = L.d_cells; L.d_cells = L.d_cells_alt; L.d_cells_alt = c;
+        float *p = L.d_prob; L.d_prob = L.d_prob_alt; L.d_prob_alt = p;
+    }
+    // K5's sector records (d_k5_sec) stay: they split the NEXT scan's lines, by line index, into eight ranges of equal expected
+    // work -- a balance hint only ("any partition is correct", k5_cells) that says nothing about where cells lie in memory.
+    hs->win_ox += dx; hs->win_oy += dy;
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hs_origin(slamhip_hs *hs, int64_t *ox, int64_t *oy)
+{
+    SH_CHECK_ARG(hs && ox && oy);
+    *ox = hs->win_ox; *oy = hs->win_oy;
     return SLAMHIP_OK;
 }
 
@@ -2181,6 +2320,7 @@ struct slamhip_hsproc {
     unsigned upd_hist;                                     // the last scans' update decisions, newest in bit 0
     int want_report, report_valid;                         // slamhip_hsproc_set_match_report; the last Update's match left `report`
     slamhip_match_report report;
+    int scroll_trigger;                                    // slamhip_hsproc_set_scroll: 0 off.  match_pose and last_update_pose are kept in the WINDOW's frame
 };
 
 static const float F_MIN = -3.40282347e+38f;       // float.MinValue
@@ -2221,10 +2361,17 @@ extern "C" int32_t slamhip_hsproc_reset(slamhip_hsproc *p)
     return SLAMHIP_OK;
 }
 
-extern "C" int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2],
-                                         const float hint[3], int32_t map_without_matching, int32_t *out_updated)
+// (float)origin * cell0 per axis: what takes a world coordinate to the window's frame and back (slamhip_hs_shift's contract)
+static inline void hsproc_window_offset(const slamhip_hsproc *p, float off[2])
 {
-    SH_CHECK_ARG(p && hint);
+    off[0] = (float)p->hs->win_ox * p->hs->lv[0].cell;
+    off[1] = (float)p->hs->win_oy * p->hs->lv[0].cell;
+}
+
+// HectorSLAMProcessor.Update (:83-125) in the window's frame: hint, match_pose and last_update_pose all are window-frame poses
+static int32_t hsproc_update_window(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2],
+                                    const float hint[3], int32_t map_without_matching, int32_t *out_updated)
+{
     p->report_valid = 0;
     const hs_report_req rq = { &p->report, nullptr };
     SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
@@ -2297,11 +2444,77 @@ extern "C" int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int
     return SLAMHIP_OK;
 }
 
+// The scrolling window (slamhip_hsproc_set_scroll), at the end of an Update: the match pose is on the host and this scan's grid
+// update -- gated or not -- is enqueued, with the pose it reads in device memory in THIS scan's window frame; the shift goes
+// behind it on the same stream.  Nothing is enqueued ahead for the next scan: its match and update take the cell pointers and
+// the hint when they are enqueued, after the swap and the re-base below.  All in binary32, one rounding per operation.
+static int32_t hsproc_scroll(slamhip_hsproc *p)
+{
+    slamhip_hs *hs = p->hs;
+    const hs_level &L0 = hs->lv[0];
+    const int g = 1 << (hs->n_levels - 1);
+    const float cf[2] = { floorf(p->match_pose[0] * L0.stm), floorf(p->match_pose[1] * L0.stm) };
+    if (!(fabsf(cf[0]) < 1.0e9f && fabsf(cf[1]) < 1.0e9f)) return SLAMHIP_OK;    // (a pose that is no number or nowhere near any map moves nothing)
+    const int c[2] = { (int)cf[0], (int)cf[1] };
+    const int half[2] = { L0.w / 2, L0.h / 2 };
+    int q[2];
+    for (int a = 0; a < 2; a++) {
+        const int d = c[a] - half[a];
+        q[a] = (d > p->scroll_trigger || -d > p->scroll_trigger) ? (d / g) * g : 0;   // (C division: toward zero)
+    }
+    if (q[0] == 0 && q[1] == 0) return SLAMHIP_OK;
+    SH_TRY(slamhip_hs_shift(hs, q[0], q[1]));
+    for (int a = 0; a < 2; a++) {
+        const float m = (float)q[a] * L0.cell;                             // (the product is rounded, then the difference)
+        p->match_pose[a] = p->match_pose[a] - m;
+        p->last_update_pose[a] = p->last_update_pose[a] - m;               // (float.MinValue absorbs it: "never updated" survives)
+    }
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2],
+                                         const float hint[3], int32_t map_without_matching, int32_t *out_updated)
+{
+    SH_CHECK_ARG(p && hint);
+    if (p->hs->win_ox == 0 && p->hs->win_oy == 0 && p->scroll_trigger == 0)
+        return hsproc_update_window(p, xy, n, origin, hint, map_without_matching, out_updated);
+    float off[2];
+    hsproc_window_offset(p, off);
+    const float hint_w[3] = { hint[0] - off[0], hint[1] - off[1], hint[2] };       // poses cross the C-ABI in the world frame
+    SH_TRY(hsproc_update_window(p, xy, n, origin, hint_w, map_without_matching, out_updated));
+    return p->scroll_trigger > 0 ? hsproc_scroll(p) : SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_set_scroll(slamhip_hsproc *p, int32_t trigger_cells)
+{
+    SH_CHECK_ARG(p);
+    const hs_level &L0 = p->hs->lv[0];
+    const int g = 1 << (p->hs->n_levels - 1);
+    const int lim = (L0.w < L0.h ? L0.w : L0.h) / 2 - g;
+    if (trigger_cells < 0 || trigger_cells >= lim)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_hsproc_set_scroll: trigger_cells = %d is outside [0, min(w0, h0) / 2 - g) = [0, %d)", trigger_cells, lim > 0 ? lim : 0);
+    p->scroll_trigger = trigger_cells;                                    // (read at the end of the next slamhip_hsproc_update)
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_get_origin(slamhip_hsproc *p, int64_t *ox, int64_t *oy)
+{
+    SH_CHECK_ARG(p);
+    return slamhip_hs_origin(p->hs, ox, oy);
+}
+
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)
 {
     SH_CHECK_ARG(p);
-    if (match_pose) memcpy(match_pose, p->match_pose, sizeof(float) * 3);
-    if (last) memcpy(last, p->last_update_pose, sizeof(float) * 3);
+    float off[2];
+    hsproc_window_offset(p, off);
+    if (p->hs->win_ox == 0 && p->hs->win_oy == 0) {                        // (never shifted: the stored bits themselves, -0.0f included)
+        if (match_pose) memcpy(match_pose, p->match_pose, sizeof(float) * 3);
+        if (last) memcpy(last, p->last_update_pose, sizeof(float) * 3);
+        match_pose = last = nullptr;
+    }
+    if (match_pose) { match_pose[0] = p->match_pose[0] + off[0]; match_pose[1] = p->match_pose[1] + off[1]; match_pose[2] = p->match_pose[2]; }
+    if (last) { last[0] = p->last_update_pose[0] + off[0]; last[1] = p->last_update_pose[1] + off[1]; last[2] = p->last_update_pose[2]; }
     if (mt) *mt = p->match_timing;
     if (ut) *ut = p->update_timing;
     return SLAMHIP_OK;

@@ -140,6 +140,21 @@ class MapRepMultiMap:
         new OccGridMap's cache."""
         capi.call("slamhip_hs_set_reference_cache", self._h, int(on))
 
+    def shift(self, dx, dy):
+        """Move the window by (+dx, +dy) level-0 cells on the device, in stream order (slamhip_hs_shift): on level l new
+        cell (x, y) holds what old cell (x + (dx >> l), y + (dy >> l)) held, exposed cells are LogOddsCell.Reset().  dx and dy
+        must be multiples of 1 << (NumLevels - 1).  Matches and updates go on working in the window's frame: a world point
+        p lies at p - origin * CellLength(level 0) there."""
+        capi.call("slamhip_hs_shift", self._h, int(dx), int(dy))
+
+    def origin(self):
+        """(ox, oy): the sum of all shifts since creation or the last Reset, in level-0 cells (slamhip_hs_origin)."""
+        ox, oy = C.c_int64(), C.c_int64()
+        capi.call("slamhip_hs_origin", self._h, C.byref(ox), C.byref(oy))
+        return int(ox.value), int(oy.value)
+
+    Origin = property(origin)
+
     def SetUpdateFactorFree(self, factor):
         self._free = float(factor)
         capi.call("slamhip_hs_set_factors", self._h, C.c_float(factor), C.c_float(getattr(self, "_occ", 0.9)))
@@ -234,7 +249,7 @@ class HectorSLAMProcessor:
     """HectorSLAM/Main/HectorSLAMProcessor.cs:17-160"""
 
     def __init__(self, mapResolution, mapSize, startPose, numDepth, numThreads=1, logger=None, ctx=None,
-                 referenceSummation=False, referenceCache=False, matchReport=False):
+                 referenceSummation=False, referenceCache=False, matchReport=False, scrollTrigger=0):
         self._own_ctx = ctx is None
         self.ctx = ctx or Context(0)
         sp = capi.f32(startPose)
@@ -250,12 +265,26 @@ class HectorSLAMProcessor:
             self.MapRep.set_reference_cache(1)
         if matchReport:                                             # every Update's match leaves its report (LastMatchReport)
             capi.call("slamhip_hsproc_set_match_report", self._h, 1)
+        if scrollTrigger:                                           # keep the robot in the window (slamhip_hsproc_set_scroll)
+            self.set_scroll(scrollTrigger)
         self._min_dist, self._min_angle = 0.3, 0.13
 
     def _get(self):
         m = np.empty(3, np.float32); l = np.empty(3, np.float32); mt, ut = C.c_float(), C.c_float()
         capi.call("slamhip_hsproc_get", self._h, capi.fptr(m), capi.fptr(l), C.byref(mt), C.byref(ut))
         return m, l, mt.value, ut.value
+
+    def set_scroll(self, triggerCells):
+        """Keep the robot in the window (slamhip_hsproc_set_scroll): 0 off (default); > 0: at the end of an Update whose match
+        pose lies more than triggerCells level-0 cells from the window's middle on an axis, the pyramid is shifted on the
+        device so that the pose is back within 1 << (numDepth - 1) cells of the middle.  Hints and poses stay world poses."""
+        capi.call("slamhip_hsproc_set_scroll", self._h, int(triggerCells))
+
+    def get_origin(self):
+        """(ox, oy) of the processor's window in level-0 cells (slamhip_hsproc_get_origin)."""
+        ox, oy = C.c_int64(), C.c_int64()
+        capi.call("slamhip_hsproc_get_origin", self._h, C.byref(ox), C.byref(oy))
+        return int(ox.value), int(oy.value)
 
     MatchPose = property(lambda self: self._get()[0])
     LastMapUpdatePose = property(lambda self: self._get()[1])

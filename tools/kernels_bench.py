@@ -3,9 +3,10 @@ fused search+update) on one MI355X, with the algorithmic byte counts of SURVEY.m
 reference's summation order (ScanMatcher(T, referenceSummation=True), T = 1, 4, 16, beside the default order) and through
 the reference's probability cache (T = 0 and 1, beside the default), and with the match report (slamhip_match_report) on and
 off: single match, batches of 256 and 4096, HectorSLAMProcessor.Update, and match_best beside match_batch.  Prints one JSON
-object.  --hector-only: the Hector part alone.  (SLAMHIP_LIB names another build of the library for an A/B on one box; rows that
+object.  --hector-only: the Hector part alone.  --shift-only: the scrolling window (slamhip_hs_shift) alone, beside a plain
+device-to-device copy of the same arrays and beside the host route (download, np.roll, upload).  (SLAMHIP_LIB names another build of the library for an A/B on one box; rows that
 need entry points it lacks are left out.)"""
-import json, math, os, sys, time
+import ctypes as C, json, math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import slam.net_amd.capi as capi, slam.net_amd.coreslam as cs, slam.net_amd.hector as hs, slam.net_amd.sim as sim
@@ -13,6 +14,93 @@ import slam.net_amd.capi as capi, slam.net_amd.coreslam as cs, slam.net_amd.hect
 out = {}
 ctx = cs.Context(0)
 segs = sim.default_field()
+
+
+def shift_rows(side, levels, cell):
+    """slamhip_hs_shift on a side^2 x levels pyramid: device time per shift between two events on the operator's stream (the
+    call is enqueue-only), for (g, 0), (0, g) and (side / 4, side / 4) taken down to a multiple of g.  The yardstick is not the
+    code under test: hipMemcpyAsync device-to-device of the same levels' cells (8 B) and probabilities (4 B) into buffers of
+    the same size, timed the same way in the same run.  And what a host had to do without the call: cells_download, np.roll,
+    cells_upload per level (wall time)."""
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+    hip.hipEventSynchronize.argtypes = [C.c_void_p]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipFree.argtypes = [C.c_void_p]
+
+    def ok(rc):
+        if rc != 0: raise RuntimeError("HIP error %d" % rc)
+    stream = C.c_void_p(ctx.stream)
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    ok(hip.hipEventCreate(C.byref(e0))); ok(hip.hipEventCreate(C.byref(e1)))
+
+    def device_us(fn, calls, batches=5):
+        for _ in range(10): fn()                                           # warm up (the first shift also allocates)
+        ctx.synchronize()
+        ts = []
+        for _ in range(batches):
+            ok(hip.hipEventRecord(e0, stream))
+            for _ in range(calls): fn()
+            ok(hip.hipEventRecord(e1, stream)); ok(hip.hipEventSynchronize(e1))
+            ms = C.c_float(); ok(hip.hipEventElapsedTime(C.byref(ms), e0, e1))
+            ts.append(ms.value / calls * 1e3)
+        return sorted(ts)[batches // 2]
+
+    rep = hs.MapRepMultiMap(cell, (side, side), levels, ctx=ctx)
+    g = 1 << (levels - 1)
+    s_ = cell * side / 40.0                                                # (the 40 m field shrunk to the window: something to move)
+    rng = sim.PCG32(3)
+    for it in range(4):
+        p = np.array([20 + 0.05 * it, 20 + 0.02 * it, 0.01 * it], np.float32)
+        rep.UpdateByScan(hs.ScanCloud((sim.make_scan(segs, p, 1080, rng)[1] * np.float32(s_)).astype(np.float32)), (p * np.array([s_, s_, 1], np.float32)))
+    cells = sum((side >> l) * (side >> l) for l in range(levels))
+    row = {"cells": cells, "bytes_moved_once": 12 * cells}
+    q = (side // 4) // g * g
+    for name, (dx, dy) in (("shift_g_0", (g, 0)), ("shift_0_g", (0, g)), ("shift_quarter", (q, q))):
+        sign = [1]
+
+        def fn():                                                          # (there and back: the origin stays near 0)
+            rep.shift(sign[0] * dx, sign[0] * dy); sign[0] = -sign[0]
+        row[name + "_us"] = device_us(fn, 50)
+    bufs = []
+    for l in range(levels):
+        n = (side >> l) * (side >> l)
+        for b in (8 * n, 4 * n):
+            a, d = C.c_void_p(), C.c_void_p()
+            ok(hip.hipMalloc(C.byref(a), b)); ok(hip.hipMalloc(C.byref(d), b))
+            bufs.append((a, d, b))
+
+    def copy_all():
+        for a, d, b in bufs: ok(hip.hipMemcpyAsync(d, a, b, 3, stream))    # hipMemcpyDeviceToDevice
+    row["memcpy_d2d_us"] = device_us(copy_all, 50)
+    for a, d, b in bufs: hip.hipFree(a); hip.hipFree(d)
+
+    def host_route():
+        for l, m in enumerate(rep.Maps):
+            w, h = m.Dimensions
+            c = m.GetCells().reshape(h, w)
+            m.SetCells(np.roll(c, (-(g >> l), 0), axis=(1, 0)).ravel())
+    host_route()
+    t0 = time.perf_counter()
+    for _ in range(3): host_route()
+    row["host_download_roll_upload_us"] = (time.perf_counter() - t0) / 3 * 1e6
+    worst = max(row[k] for k in ("shift_g_0_us", "shift_0_g_us", "shift_quarter_us"))
+    row["worst_shift_over_memcpy"] = worst / row["memcpy_d2d_us"]
+    rep.close()
+    return row
+
+
+def shift_section():
+    return {"hs_shift_3lvl_2048": shift_rows(2048, 3, 40.0 / 2048), "hs_shift_4lvl_400": shift_rows(400, 4, 0.1)}
+
+
+if "--shift-only" in sys.argv:
+    print(json.dumps(shift_section(), indent=1))
+    ctx.close()
+    sys.exit(0)
+
 for size in (() if "--hector-only" in sys.argv else (1024, 2048, 4096)):
     dev = cs.CoreSlamDevice(ctx, 40.0, size, size // 4)
     rng = sim.PCG32(1234); traj = sim.trajectory(40)
@@ -171,4 +259,6 @@ for Bn in (256, 4096):
         r["match_best"] = wall_us(lambda: m0.MatchDataBest(rep, scan, hb), 20 if Bn == 256 else 5)
     rows["batch%d_us" % Bn] = r
 out["k4_hector_match_report_3lvl_2048"] = rows
+if hasattr(capi.lib(), "slamhip_hs_shift"):
+    out.update(shift_section())
 print(json.dumps(out, indent=1))
