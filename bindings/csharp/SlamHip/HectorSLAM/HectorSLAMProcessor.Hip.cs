@@ -88,6 +88,20 @@ namespace HectorSLAM.Main
             set { Native.Check(Native.slamhip_hsproc_set_scroll(proc.Ptr, value)); scrollTrigger = value; }
         }
 
+        /// <summary>Keep what ScrollTrigger moves out of the window (MapRep.SetBacking; slamhip_hs_set_backing on the processor's own
+        /// pyramid): (tileCells, maxBytes), or null (default) for off -- a robot that drives a loop then comes home to the map it made.</summary>
+        public (int TileCells, ulong MaxBytes)? ScrollBacking
+        {
+            get => scrollBacking;
+            set
+            {
+                if (value.HasValue) MapRep.SetBacking(value.Value.TileCells, value.Value.MaxBytes);
+                else MapRep.SetBacking(0, 0);
+                scrollBacking = value.HasValue && value.Value.MaxBytes > 0 ? value : null;
+            }
+        }
+        private (int TileCells, ulong MaxBytes)? scrollBacking;
+
         /// <summary>The window's origin in level-0 cells (slamhip_hsproc_get_origin): the sum of all shifts since the last Reset.</summary>
         public (long X, long Y) Origin
         {

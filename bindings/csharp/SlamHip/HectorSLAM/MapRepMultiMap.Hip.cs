@@ -113,6 +113,36 @@ namespace HectorSLAM.Main
             }
         }
 
+        /// <summary>The backing store of the scrolling window (slamhip_hs_set_backing): with maxBytes > 0, what Shift moves out of the
+        /// window is kept in a device pool of at most maxBytes, in world tiles of tileCells x tileCells cells per level (a power of two
+        /// in [8, 256]), and restored when the window returns; a shift never fails for capacity -- pieces that find no slot are dropped
+        /// and counted.  maxBytes = 0 (the default state): off, the pool is freed.  The setting survives Reset, the tiles do not.</summary>
+        public void SetBacking(int tileCells, ulong maxBytes)
+        {
+            Native.Check(Native.slamhip_hs_set_backing(Pyramid.Ptr, tileCells, maxBytes));
+        }
+
+        /// <summary>slamhip_hs_backing_stats: all zero while backing is off.</summary>
+        public BackingStats BackingStats
+        {
+            get
+            {
+                Native.Check(Native.slamhip_hs_backing_stats(Pyramid.Ptr, out BackingStats st));
+                return st;
+            }
+        }
+
+        /// <summary>The rectangle [x0, x0 + w) x [y0, y0 + h) of `level` in WORLD cells, row-major (slamhip_hs_world_cells_download): the
+        /// window's cells from the window, evicted cells from their tiles, LogOddsCell.Reset() everywhere else.  Blocking; w * h at
+        /// most 2^26.  Works with backing off: the window in a frame of Reset cells.</summary>
+        public unsafe LogOddsCell[] WorldCells(int level, long x0, long y0, int w, int h)
+        {
+            var cells = new LogOddsCell[Math.Max(0, (long)w * h)];
+            fixed (LogOddsCell* p = cells)
+                Native.Check(Native.slamhip_hs_world_cells_download(Pyramid.Ptr, level, x0, y0, w, h, p));
+            return cells;
+        }
+
         /// <summary>The device maps changed behind this object's back (HectorSLAMProcessor.Update drives the native processor): host mirrors are stale.</summary>
         internal void MarkStale()
         {

@@ -51,6 +51,17 @@ namespace SlamHip
         public float ResidualPerPoint => PointCount > 0 ? Residual / PointCount : 0f;
     }
 
+    /// <summary>slamhip_backing_stats (include/slamhip.h): the backing store of the scrolling window -- tiles in the directory, bytes of
+    /// the device pool allocated so far, its capacity, and the cells evicted, restored and dropped since backing was switched on
+    /// (host-side sums of job areas).  6 longs + 2 ints, 56 bytes; all zero while backing is off.</summary>
+    [StructLayout(LayoutKind.Sequential, Pack = 8)]
+    public struct BackingStats
+    {
+        public long Tiles, Bytes, CapacityBytes;
+        public long EvictedCells, RestoredCells, DroppedCells;
+        public int Tile, On;
+    }
+
     internal static unsafe class Native
     {
         const string Lib = "slamhip";                                   // libslamhip.so on the library path
@@ -137,6 +148,10 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_update_by_scan(IntPtr hs, in Vector3 robotPoseWorld);
         [DllImport(Lib)] internal static extern int slamhip_hs_shift(IntPtr hs, int dx, int dy);
         [DllImport(Lib)] internal static extern int slamhip_hs_origin(IntPtr hs, out long ox, out long oy);
+        // the scrolling window's backing store: what scrolls out is kept in a device tile pool and restored on return (maxBytes 0 = off)
+        [DllImport(Lib)] internal static extern int slamhip_hs_set_backing(IntPtr hs, int tileCells, ulong maxBytes);
+        [DllImport(Lib)] internal static extern int slamhip_hs_backing_stats(IntPtr hs, out BackingStats stats);
+        [DllImport(Lib)] internal static extern int slamhip_hs_world_cells_download(IntPtr hs, int level, long x0, long y0, int w, int h, HectorSLAM.Map.LogOddsCell* cells);
         // HectorSLAM, processor level (HectorSLAMProcessor.cs:66-138): the Update state machine in the library -- match, the gate of :107-109 evaluated
         // on the device, the grid update enqueued behind the match before the pose is back (one blocking wait per scan instead of two)
         [DllImport(Lib)] internal static extern int slamhip_hsproc_create(IntPtr ctx, float mapResolution, int width, int height, in Vector3 startPose, int numDepth, out IntPtr proc);

@@ -64,6 +64,17 @@ typedef struct slamhip_comm   slamhip_comm;    /* one rank (one process per GPU)
 /* {int UpdateIndex; float Value} -- HectorSLAM/Map/LogOddsCell.cs:16-21 */
 typedef struct { int32_t update_index; float value; } slamhip_cell;
 
+/* One job of the scrolling window's backing store (slamhip_hs_set_backing; the planner, slamhip_debug_backing_plan): the
+ * intersection of one world tile (tx, ty) of `level` with the cells that leave the window (kind SLAMHIP_BACKING_EVICT: wx, wy in
+ * the OLD window's coordinates) or come into it (SLAMHIP_BACKING_RESTORE: in the NEW window's): nx x ny cells from window cell
+ * (wx, wy), which is cell (lx, ly) of the tile; lx + nx <= tile, ly + ny <= tile. */
+enum { SLAMHIP_BACKING_EVICT = 0, SLAMHIP_BACKING_RESTORE = 1 };
+typedef struct slamhip_backing_job {
+    int32_t level, kind, wx, wy, nx, ny;
+    int64_t tx, ty;
+    int32_t lx, ly;
+} slamhip_backing_job;
+
 /* ------------------------------------------------------------------------------------------------
  * Library / context
  * ---------------------------------------------------------------------------------------------- */
@@ -95,6 +106,18 @@ int32_t slamhip_ctx_poisoned(slamhip_ctx *ctx, int32_t *out_flag);
 /* Test hook (no device involved): the wait loop of a blocking call on a caller-owned word -- returns SLAMHIP_OK once *flag has
  * reached `val` (wrap-safe), SLAMHIP_ERR_TIMEOUT after timeout_ms. */
 int32_t slamhip_debug_flag_wait(volatile uint32_t *flag, uint32_t val, int64_t timeout_ms);
+/* Test hook (no device involved): the planner of the scrolling window's backing store (slamhip_hs_set_backing) for one shift by
+ * (dx, dy) of a pyramid of `levels` levels, level 0 w0 x h0, whose window lies at (ox, oy) before the shift, with tiles of
+ * `tile` x `tile` cells.  World cell of window cell (x, y) on level l: ((ox >> l) + x, (oy >> l) + y); tile index floor(X / tile),
+ * local coordinate X - tile * floor(X / tile).  The jobs come in the order the shift uses them (and deals tile slots in): level 0
+ * first; within a level evict jobs, then restore jobs; within each, row-major by tile (ty, tx).  The departing region (and the
+ * arriving one) is the window minus the rectangle both windows share, cut into the band above it, the band below it and the strips
+ * left and right of it; a tile gives one job per rectangle it meets, in that order.  *n_jobs receives the number of jobs; if it
+ * exceeds `cap`, nothing is written and the call returns SLAMHIP_ERR_INVALID (jobs may be NULL when cap is 0).  levels, w0, h0 as
+ * for slamhip_hs_create, tile a power of two in [8, 256]; dx and dy need not be multiples of 1 << (levels - 1) here. */
+int32_t slamhip_debug_backing_plan(int32_t levels, int32_t w0, int32_t h0, int64_t ox, int64_t oy,
+                                   int32_t dx, int32_t dy, int32_t tile,
+                                   slamhip_backing_job *jobs, int32_t cap, int32_t *n_jobs);
 
 /* Kernel timing (the reference only has Stopwatch EMAs, HectorSLAMProcessor.cs:92-96,111-115).
  * When enabled, each kernel class is bracketed by HIP events on the context's stream. */
@@ -577,6 +600,48 @@ int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3
  * the reference lacks.  A poisoned context: SLAMHIP_ERR_TIMEOUT. */
 int32_t slamhip_hs_shift(slamhip_hs *hs, int32_t dx, int32_t dy);
 int32_t slamhip_hs_origin(slamhip_hs *hs, int64_t *ox, int64_t *oy);
+
+/* The backing store of the scrolling window (opt-in): what scrolls out of the window is kept in device memory and restored when the
+ * window returns, so that a robot that drives a loop comes home to the map it made.  The world is cut into tiles of
+ * tile_cells x tile_cells cells per level (world cell of window cell (x, y) on level l: ((ox >> l) + x, (oy >> l) + y)).  A tile
+ * that holds evicted cells occupies a SLOT of a device pool: tile^2 slamhip_cell records followed by tile^2 float probabilities,
+ * 12 * tile^2 bytes -- the probabilities are stored, not recomputed: they move with the cells, as in the shift itself.  The
+ * directory (which tiles exist, in which slot) lives on the host, which knows the origin and every shift: the shift stays
+ * enqueue-only and reads nothing back.  Slots are allocated lazily, in chunks, up to max_bytes, and start as Reset cells
+ * ({-1, 0.0f}, 0.5f): restoring a part of a tile that nothing was evicted into gives exactly what the shift writes without
+ * backing.
+ * With backing on, slamhip_hs_shift enqueues its launch as before and ONE more behind it (none if the shift has nothing to evict
+ * or restore), which copies the departing cells of the old window into their tiles and the tiles' cells into the exposed bands of
+ * the new window; a launch that initialises a new chunk of slots goes ahead of it when one is allocated.  A shift NEVER fails
+ * for capacity: if a departing piece needs a new tile and no slot can be had (the pool is at max_bytes, or the device allocation
+ * of a chunk fails), the cells of that piece are dropped, as all of them are without backing, and counted in dropped_cells.
+ * Slots are dealt in the planner's job order (slamhip_debug_backing_plan), so what is kept is deterministic.  A tile keeps its
+ * copy after a restore; it is overwritten when those cells leave the window again.
+ * slamhip_hs_set_backing: max_bytes == 0 (the default state): off -- every tile is dropped and the pool is freed (the call drains
+ * the operator's stream first); tile_cells is then ignored.  Otherwise tile_cells must be a power of two in [8, 256] and
+ * max_bytes at least one slot, 12 * tile_cells^2; anything else SLAMHIP_ERR_INVALID, the setting unchanged.  While tiles exist,
+ * changing tile_cells, or lowering max_bytes below what the pool already holds, is SLAMHIP_ERR_INVALID: switch backing off first.
+ * The setting survives slamhip_hs_reset; the tiles do not (the directory is dropped, the pool is kept and re-initialised).
+ * slamhip_hs_cells_upload touches the window only.  slamhip_hs_destroy frees the pool.  With backing off nothing is allocated,
+ * no extra launch is issued and nothing is read that is not read without this call.  While the reference's cache is on
+ * (slamhip_hs_set_reference_cache) slamhip_hs_shift refuses as before, with or without backing.
+ * slamhip_hs_backing_stats: tiles in the directory, bytes of the pool allocated so far, capacity_bytes = max_bytes, and the cells
+ * evicted, restored and dropped since backing was switched on -- host-side sums of job areas, no device read-back; all zero
+ * while backing is off. */
+typedef struct slamhip_backing_stats {
+    int64_t tiles, bytes, capacity_bytes;
+    int64_t evicted_cells, restored_cells, dropped_cells;   /* host-side sums of job areas; no device read-back */
+    int32_t tile, on;
+} slamhip_backing_stats;
+int32_t slamhip_hs_set_backing(slamhip_hs *hs, int32_t tile_cells, uint64_t max_bytes);
+int32_t slamhip_hs_backing_stats(slamhip_hs *hs, slamhip_backing_stats *out);
+/* The map of everywhere the window has been: the rectangle [x0, x0 + w) x [y0, y0 + h) of level `level` in WORLD cells, row-major
+ * into out[w * h].  Cells inside the window come from the window (the window wins over a tile's older copy), evicted cells from
+ * their tiles, everything else is LogOddsCell.Reset() {-1, 0.0f}.  Blocking, behind everything already on the operator's stream,
+ * with the context's bounded wait.  w, h >= 1 and w * h <= 2^26 cells (512 MiB of out); anything else SLAMHIP_ERR_INVALID.  Works
+ * with backing off as well: the window in a frame of Reset cells. */
+int32_t slamhip_hs_world_cells_download(slamhip_hs *hs, int32_t level, int64_t x0, int64_t y0,
+                                        int32_t w, int32_t h, slamhip_cell *out);
 
 /* ------------------------------------------------------------------------------------------------
  * HectorSLAM, processor level

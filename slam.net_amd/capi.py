@@ -47,6 +47,24 @@ SEARCH_REPORT_DTYPE = np.dtype([("sum_off", np.float64, 3), ("sum_off2", np.floa
 assert C.sizeof(SearchReport) == SEARCH_REPORT_DTYPE.itemsize == 120
 
 
+class BackingStats(C.Structure):
+    """slamhip_backing_stats (include/slamhip.h): 6 int64 + 2 int32, 56 bytes."""
+    _fields_ = [("tiles", C.c_int64), ("bytes", C.c_int64), ("capacity_bytes", C.c_int64), ("evicted_cells", C.c_int64),
+                ("restored_cells", C.c_int64), ("dropped_cells", C.c_int64), ("tile", C.c_int32), ("on", C.c_int32)]
+
+
+class BackingJob(C.Structure):
+    """slamhip_backing_job (include/slamhip.h): one job of the backing store's planner, 48 bytes."""
+    _fields_ = [("level", C.c_int32), ("kind", C.c_int32), ("wx", C.c_int32), ("wy", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32),
+                ("tx", C.c_int64), ("ty", C.c_int64), ("lx", C.c_int32), ("ly", C.c_int32)]
+
+
+BACKING_EVICT, BACKING_RESTORE = 0, 1
+BACKING_JOB_DTYPE = np.dtype([("level", np.int32), ("kind", np.int32), ("wx", np.int32), ("wy", np.int32), ("nx", np.int32), ("ny", np.int32),
+                              ("tx", np.int64), ("ty", np.int64), ("lx", np.int32), ("ly", np.int32)])
+assert C.sizeof(BackingStats) == 56 and C.sizeof(BackingJob) == BACKING_JOB_DTYPE.itemsize == 48
+
+
 class SlamhipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("slamhip error %d: %s" % (code, msg))
@@ -95,6 +113,7 @@ def _declare(L):
         "slamhip_ctx_poisoned": (i32, [vp, ip]),
         "slamhip_ctx_philox4x32_10": (i32, [vp, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]),
         "slamhip_debug_flag_wait": (i32, [P(C.c_uint32), C.c_uint32, i64]),
+        "slamhip_debug_backing_plan": (i32, [i32, i32, i32, i64, i64, i32, i32, i32, P(BackingJob), i32, ip]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -181,6 +200,9 @@ def _declare(L):
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
         "slamhip_hs_shift": (i32, [vp, i32, i32]),
         "slamhip_hs_origin": (i32, [vp, P(i64), P(i64)]),
+        "slamhip_hs_set_backing": (i32, [vp, i32, u64]),
+        "slamhip_hs_backing_stats": (i32, [vp, P(BackingStats)]),
+        "slamhip_hs_world_cells_download": (i32, [vp, i32, i64, i64, i32, i32, vp]),
         "slamhip_hsproc_create": (i32, [vp, f, i32, i32, fp, i32, vpp]),
         "slamhip_hsproc_destroy": (i32, [vp]),
         "slamhip_hsproc_reset": (i32, [vp]),
@@ -225,6 +247,20 @@ def _declare(L):
         fn.restype = res
         fn.argtypes = args
     L._signatures = sig
+
+
+def backing_plan(levels, w0, h0, ox, oy, dx, dy, tile):
+    """The job list of the backing store's planner for one shift (slamhip_debug_backing_plan; no device involved): a
+    BACKING_JOB_DTYPE array in the order the shift uses."""
+    n = C.c_int32()
+    rc = lib().slamhip_debug_backing_plan(levels, w0, h0, ox, oy, dx, dy, tile, None, 0, C.byref(n))
+    if rc == OK:
+        return np.zeros(0, BACKING_JOB_DTYPE)
+    if n.value <= 0:
+        check(rc)
+    jobs = np.zeros(n.value, BACKING_JOB_DTYPE)
+    call("slamhip_debug_backing_plan", levels, w0, h0, ox, oy, dx, dy, tile, jobs.ctypes.data_as(C.POINTER(BackingJob)), n.value, C.byref(n))
+    return jobs
 
 
 def check(rc):

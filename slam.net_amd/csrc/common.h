@@ -96,6 +96,7 @@ static inline int32_t sh_upload_wait(slamhip_ctx *ctx, volatile uint32_t *h_flag
     for (int p = 0; p < SH_UPLOAD_PARTS; p++) { const int32_t rc = sh_flag_wait(ctx, h_flags + p, seq); if (rc != SLAMHIP_OK) return rc; }
     return SLAMHIP_OK;
 }
+int32_t sh_event_wait(slamhip_ctx *ctx, hipEvent_t ev);                 // until `ev` has completed, with the same bound (and the same poisoning) as sh_flag_wait
 int32_t sh_host_wait(slamhip_ctx *ctx);                                  // until the last sh_publish of this context has landed
 // (a kernel that is the last of its call may write the mailbox itself: words first, then sh_mail_seq_next() into word 15, released at system scope)
 static inline uint32_t sh_mail_seq_next(slamhip_ctx *ctx) { return ++ctx->mail_seq; }

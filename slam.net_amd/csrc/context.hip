@@ -1,5 +1,6 @@
 // context.hip -- library / context entry points of include/slamhip.h (gfx950 only).
 #include "common.h"
+#include "backing_plan.h"
 #include <stdlib.h>
 #include <time.h>
 
@@ -245,6 +246,45 @@ extern "C" int32_t slamhip_debug_flag_wait(volatile uint32_t *flag, uint32_t val
 {
     SH_CHECK_ARG(flag);
     return sh_flag_wait_bounded(nullptr, flag, val, timeout_ms);
+}
+
+// CPU-side test hook: the planner of the backing store (backing_plan.h), as slamhip_hs_shift calls it
+extern "C" int32_t slamhip_debug_backing_plan(int32_t levels, int32_t w0, int32_t h0, int64_t ox, int64_t oy, int32_t dx, int32_t dy,
+                                              int32_t tile, slamhip_backing_job *jobs, int32_t cap, int32_t *n_jobs)
+{
+    SH_CHECK_ARG(n_jobs && cap >= 0 && (jobs || cap == 0));
+    SH_CHECK_ARG(levels >= 1 && levels <= 8 && w0 >= 2 && h0 >= 2 && w0 <= 32768 && h0 <= 32768 && (w0 >> (levels - 1)) >= 2 && (h0 >> (levels - 1)) >= 2);
+    SH_CHECK_ARG(tile >= 8 && tile <= 256 && (tile & (tile - 1)) == 0);
+    std::vector<slamhip_backing_job> plan;
+    bp_plan(levels, w0, h0, ox, oy, dx, dy, tile, plan);
+    if (plan.size() > (size_t)INT32_MAX) SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_debug_backing_plan: %zu jobs", plan.size());
+    *n_jobs = (int32_t)plan.size();
+    if (plan.size() > (size_t)cap)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_debug_backing_plan: the plan has %zu jobs, the caller's array holds %d", plan.size(), cap);
+    if (!plan.empty()) memcpy(jobs, plan.data(), sizeof(slamhip_backing_job) * plan.size());
+    return SLAMHIP_OK;
+}
+
+// The bounded wait on an event (a pinned block that a launch reads may be refilled once the event recorded behind that launch has
+// completed): in steady state the event has long completed and this is one hipEventQuery.
+int32_t sh_event_wait(slamhip_ctx *ctx, hipEvent_t ev)
+{
+    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
+    timespec t0;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (;;) {
+        const hipError_t q = hipEventQuery(ev);
+        if (q == hipSuccess) return SLAMHIP_OK;
+        if (q != hipErrorNotReady) SH_HIP(q);                          // a device fault
+        timespec t1;
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        const int64_t ns = (t1.tv_sec - t0.tv_sec) * 1000000000L + (t1.tv_nsec - t0.tv_nsec);
+        if (ctx->wait_timeout_ms > 0 && ns / 1000000L >= ctx->wait_timeout_ms) {
+            ctx->poisoned = true;
+            SH_FAIL(SLAMHIP_ERR_TIMEOUT, "a blocking wait passed its bound of %lld ms (SLAMHIP_WAIT_TIMEOUT_MS): the event never completed", (long long)ctx->wait_timeout_ms);
+        }
+        if (ns > 300000L) { timespec nap = { 0, 20000 }; nanosleep(&nap, nullptr); }   // (past the spin budget: 20 us naps, as sh_flag_wait)
+    }
 }
 
 int32_t sh_host_wait(slamhip_ctx *ctx)

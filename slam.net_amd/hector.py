@@ -155,6 +155,28 @@ class MapRepMultiMap:
 
     Origin = property(origin)
 
+    def set_backing(self, tile, max_bytes):
+        """The backing store of the scrolling window (slamhip_hs_set_backing): with max_bytes > 0, what a shift scrolls out
+        of the window is kept in a device pool of at most max_bytes, in world tiles of tile x tile cells per level (a power
+        of two in [8, 256]), and restored when the window returns.  max_bytes = 0 (the default state): off, the pool is freed.
+        The setting survives Reset, the tiles do not."""
+        capi.call("slamhip_hs_set_backing", self._h, int(tile), C.c_uint64(int(max_bytes)))
+
+    def backing_stats(self):
+        """slamhip_hs_backing_stats as a dict: tiles, bytes, capacity_bytes, evicted_cells, restored_cells, dropped_cells
+        (host-side sums since backing was switched on), tile, on -- all zero while backing is off."""
+        st = capi.BackingStats()
+        capi.call("slamhip_hs_backing_stats", self._h, C.byref(st))
+        return {name: int(getattr(st, name)) for name, _ in capi.BackingStats._fields_}
+
+    def world_cells(self, level, x0, y0, w, h):
+        """The rectangle [x0, x0 + w) x [y0, y0 + h) of `level` in WORLD cells as an (h, w) array of capi.CELL_DTYPE
+        (slamhip_hs_world_cells_download): the window's cells from the window, evicted cells from their tiles, LogOddsCell.Reset()
+        everywhere else.  Blocking.  Works with backing off: the window in a frame of Reset cells."""
+        out = np.empty((int(h), int(w)), capi.CELL_DTYPE)
+        capi.call("slamhip_hs_world_cells_download", self._h, int(level), int(x0), int(y0), int(w), int(h), out.ctypes.data_as(C.c_void_p))
+        return out
+
     def SetUpdateFactorFree(self, factor):
         self._free = float(factor)
         capi.call("slamhip_hs_set_factors", self._h, C.c_float(factor), C.c_float(getattr(self, "_occ", 0.9)))
@@ -249,7 +271,8 @@ class HectorSLAMProcessor:
     """HectorSLAM/Main/HectorSLAMProcessor.cs:17-160"""
 
     def __init__(self, mapResolution, mapSize, startPose, numDepth, numThreads=1, logger=None, ctx=None,
-                 referenceSummation=False, referenceCache=False, matchReport=False, scrollTrigger=0):
+                 referenceSummation=False, referenceCache=False, matchReport=False, scrollTrigger=0,
+                 scrollBacking=None):
         self._own_ctx = ctx is None
         self.ctx = ctx or Context(0)
         sp = capi.f32(startPose)
@@ -267,6 +290,8 @@ class HectorSLAMProcessor:
             capi.call("slamhip_hsproc_set_match_report", self._h, 1)
         if scrollTrigger:                                           # keep the robot in the window (slamhip_hsproc_set_scroll)
             self.set_scroll(scrollTrigger)
+        if scrollBacking is not None:                               # (tile, max_bytes): keep what scrolls out (MapRep.set_backing)
+            self.set_backing(*scrollBacking)
         self._min_dist, self._min_angle = 0.3, 0.13
 
     def _get(self):
@@ -279,6 +304,14 @@ class HectorSLAMProcessor:
         pose lies more than triggerCells level-0 cells from the window's middle on an axis, the pyramid is shifted on the
         device so that the pose is back within 1 << (numDepth - 1) cells of the middle.  Hints and poses stay world poses."""
         capi.call("slamhip_hsproc_set_scroll", self._h, int(triggerCells))
+
+    def set_backing(self, tile, max_bytes):
+        """The backing store of the processor's own pyramid (MapRepMultiMap.set_backing): what the scroll moves out of the
+        window is kept on the device and restored when the robot returns.  max_bytes = 0: off."""
+        self.MapRep.set_backing(tile, max_bytes)
+
+    def backing_stats(self):
+        return self.MapRep.backing_stats()
 
     def get_origin(self):
         """(ox, oy) of the processor's window in level-0 cells (slamhip_hsproc_get_origin)."""

@@ -4,7 +4,8 @@ reference's summation order (ScanMatcher(T, referenceSummation=True), T = 1, 4, 
 the reference's probability cache (T = 0 and 1, beside the default), and with the match report (slamhip_match_report) on and
 off: single match, batches of 256 and 4096, HectorSLAMProcessor.Update, and match_best beside match_batch.  Prints one JSON
 object.  --hector-only: the Hector part alone.  --shift-only: the scrolling window (slamhip_hs_shift) alone, beside a plain
-device-to-device copy of the same arrays and beside the host route (download, np.roll, upload).  (SLAMHIP_LIB names another build of the library for an A/B on one box; rows that
+device-to-device copy of the same arrays and beside the host route (download, np.roll, upload); with --backing: the shift with the backing store off, on over fresh ground
+and on over ground to restore, beside a device-to-device copy of the evicted plus restored bytes.  (SLAMHIP_LIB names another build of the library for an A/B on one box; rows that
 need entry points it lacks are left out.)"""
 import ctypes as C, json, math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -92,7 +93,84 @@ def shift_rows(side, levels, cell):
     return row
 
 
+def backing_rows(side, levels, cell, tile=64):
+    """slamhip_hs_shift with the backing store (slamhip_hs_set_backing): device time per shift between two events, as in shift_rows,
+    for (g, 0), (0, g) and a quarter window -- backing off (there and back, shift_rows' own figure); backing on while the window
+    moves one way over fresh ground (a band to evict, nothing to restore); and on the way back over the same ground (a band to
+    evict, the full band restored).  The yardstick for the added time is not the code under test: ONE hipMemcpyAsync
+    device-to-device of as many bytes as the shift evicted plus restored (12 per cell, from slamhip_hs_backing_stats), a
+    launch boundary of its own included, timed the same way in the same run."""
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    hip.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+    hip.hipEventSynchronize.argtypes = [C.c_void_p]
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipFree.argtypes = [C.c_void_p]
+
+    def ok(rc):
+        if rc != 0: raise RuntimeError("HIP error %d" % rc)
+    stream = C.c_void_p(ctx.stream)
+    e0, e1 = C.c_void_p(), C.c_void_p()
+    ok(hip.hipEventCreate(C.byref(e0))); ok(hip.hipEventCreate(C.byref(e1)))
+
+    def device_us(fn, calls, batches, warm):
+        for _ in range(warm): fn()
+        ctx.synchronize()
+        ts = []
+        for _ in range(batches):
+            ok(hip.hipEventRecord(e0, stream))
+            for _ in range(calls): fn()
+            ok(hip.hipEventRecord(e1, stream)); ok(hip.hipEventSynchronize(e1))
+            ms = C.c_float(); ok(hip.hipEventElapsedTime(C.byref(ms), e0, e1))
+            ts.append(ms.value / calls * 1e3)
+        return sorted(ts)[batches // 2], (max(ts) - min(ts))
+
+    g = 1 << (levels - 1)
+    s_ = cell * side / 40.0
+    q = (side // 4) // g * g
+    row = {"tile": tile}
+    for name, (dx, dy), calls in (("g_0", (g, 0), 40), ("0_g", (0, g), 40), ("quarter", (q, q), 8)):
+        rep = hs.MapRepMultiMap(cell, (side, side), levels, ctx=ctx)
+        rng = sim.PCG32(3)
+        for it in range(4):
+            p = np.array([20 + 0.05 * it, 20 + 0.02 * it, 0.01 * it], np.float32)
+            rep.UpdateByScan(hs.ScanCloud((sim.make_scan(segs, p, 1080, rng)[1] * np.float32(s_)).astype(np.float32)), (p * np.array([s_, s_, 1], np.float32)))
+        sign = [1]
+
+        def there_and_back():
+            rep.shift(sign[0] * dx, sign[0] * dy); sign[0] = -sign[0]
+        r = {}
+        r["off_us"], r["off_spread_us"] = device_us(there_and_back, 50, 5, 10)
+        rep.set_backing(tile, 3 << 30)
+        batches, warm = 3, 4
+        n = warm + batches * calls
+        st0 = rep.backing_stats()
+        r["on_fresh_us"], r["on_fresh_spread_us"] = device_us(lambda: rep.shift(dx, dy), calls, batches, warm)
+        st1 = rep.backing_stats()
+        r["on_return_us"], r["on_return_spread_us"] = device_us(lambda: rep.shift(-dx, -dy), calls, batches, warm)
+        st2 = rep.backing_stats()
+        for key, a, b in (("fresh", st0, st1), ("return", st1, st2)):
+            cells = (b["evicted_cells"] - a["evicted_cells"] + b["restored_cells"] - a["restored_cells"]) / n
+            r[key + "_evicted_cells_per_shift"] = (b["evicted_cells"] - a["evicted_cells"]) / n
+            r[key + "_restored_cells_per_shift"] = (b["restored_cells"] - a["restored_cells"]) / n
+            nbytes = max(16, int(12 * cells))
+            src, dst = C.c_void_p(), C.c_void_p()
+            ok(hip.hipMalloc(C.byref(src), nbytes)); ok(hip.hipMalloc(C.byref(dst), nbytes))
+            r[key + "_bytes_per_shift"] = nbytes
+            r[key + "_memcpy_same_bytes_us"] = device_us(lambda: ok(hip.hipMemcpyAsync(dst, src, nbytes, 3, stream)), 50, 5, 10)[0]
+            r[key + "_added_us"] = r["on_%s_us" % key] - r["off_us"]
+            hip.hipFree(src); hip.hipFree(dst)
+        r["dropped_cells"] = st2["dropped_cells"]; r["pool_bytes"] = st2["bytes"]; r["tiles"] = st2["tiles"]
+        row[name] = r
+        rep.close()
+    return row
+
+
 def shift_section():
+    if "--backing" in sys.argv:
+        return {"hs_backing_3lvl_2048": backing_rows(2048, 3, 40.0 / 2048), "hs_backing_4lvl_400": backing_rows(400, 4, 0.1)}
+
     return {"hs_shift_3lvl_2048": shift_rows(2048, 3, 40.0 / 2048), "hs_shift_4lvl_400": shift_rows(400, 4, 0.1)}
 
 
