@@ -188,7 +188,7 @@ int oracle_grid_h(const oracle_grid *g) { return g->h; }
  * cell that was cached in epoch e before the Reset is served its PRE-RESET probability when it is queried in epoch e after
  * the Reset -- until the epochs differ again.  That is a reference bug (a matcher reading probabilities of a map that no
  * longer exists), it depends on which cells an earlier match happened to touch, and it is not reproduced: this function,
- * the device's probability grids (hector.hip: refreshed by every writer of the log-odds grid, reset included) and
+ * the device's probability grids (hector.hip, hs_update.hip, hs_window.hip: refreshed by every writer of the log-odds grid, reset included) and
  * slamhip_hs_cell_prob return the current value's probability.  oracle_grid_prob_literal below restates the C# cache
  * literally so that tests/test_oracle_kat.py can SHOW the reference's behaviour next to the chosen one. */
 float oracle_grid_prob(oracle_grid *g, int index)

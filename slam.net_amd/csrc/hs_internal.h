@@ -1,0 +1,126 @@
+// hs_internal.h -- device state of the HectorSLAM operator object (slamhip_hs) and what its units share.
+#pragma once
+#include "common.h"
+#include "m3x2.h"
+#include <stdlib.h>
+
+#define HS_MAX_LEVELS 8
+#define HS_NONE 0xFFFFFFFFu
+// sizes of K4's (hs_match.hip) and K5's (hs_update.hip) LDS tables that host entry points of other units test
+#define HS_LDS_PTS 2048                    // scan points kept in LDS (16 KB); longer scans are read from global memory
+#define HS_REF_MAX_T 64                    // ParallelWorker.Work waits with WaitHandle.WaitAll: at most 64 handles (BaseSLAM/ParallelWorker.cs:113-115)
+#define K5_LDS_LINES 3072
+
+struct hs_level {
+    int w, h; float cell, stm;             // MapProperties: Dimensions, CellLength, ScaleToMap (MapProperties.cs:22-32)
+    sh_m3x2 map_t_world, world_t_map;      // GridMap.cs:46-47
+    slamhip_cell *d_cells;                 // mapArray (GridMap.cs:13) in the reference's own layout, LogOddsCell {UpdateIndex, Value} (LogOddsCell.cs:16-21): the grid
+                                           // update reads and writes a cell with ONE 8-byte access (two arrays: 30.8 -> 26.9 us per update with the second one left out)
+    float *d_prob;                         // GetCachedProbability of every cell (OccGridMap.cs:97-107), kept current by every writer of d_cells
+    slamhip_cell *d_cells_alt; float *d_prob_alt;   // the second set slamhip_hs_shift moves the window into (allocated by the first shift); the
+                                           // launch reads d_cells / d_prob, writes these, and the host then swaps the names
+    unsigned long long *d_cache;           // cacheArray (OccGridMap.cs:16), one CachedMapElement {Value, Index} per cell as ONE 8-byte word
+                                           // (Value's bits low, Index high); allocated when the reference's cache is first turned on
+    int curr_update_index;                 // OccGridMap.cs:20
+    int curr_cache_index;                  // OccGridMap.cs:19, kept in every mode: UpdateByScan +1 (:147), Reset 0 (:248)
+    int iterations;                        // EstimateIterations (OccGridMap.cs:53)
+};
+
+struct hs_level_dev {                      // what the kernels need, by value
+    int w, h; float cell, stm;
+    sh_m3x2 map_t_world, world_t_map;
+    const float *prob;                     // what the matcher's taps read: exp and divide happen when a cell changes, not per tap
+    const slamhip_cell *cells;             // (HS_PROB_MODE 1 / 2, developer experiment: the taps read the cells and form the probabilities themselves)
+    int iterations;
+};
+#ifndef HS_PROB_MODE
+#define HS_PROB_MODE 0                     // 0: the probability grid, kept by every writer of the cells | 1: from the cells, exact expf and division per tap | 2: ... hardware exp and reciprocal
+#endif
+
+struct hs_backing;                         // hs_window.hip
+struct slamhip_hs {
+    slamhip_ctx *ctx;
+    int n_levels;
+    hs_level lv[HS_MAX_LEVELS];
+    float odds_free, odds_occ, lo_free, lo_occ;          // OccGridMap.cs:24-27
+    int n_points, cap_points;
+    float2 *d_pts; float origin[2];
+    float2 *d_pts_base; int pts_buf; uint64_t launch_count, launch_done, pts_use[2], match_launch_no;   // two device blocks used in turn; which launches read which (see slamhip_cs_set_scan)
+    float *h_pts; hipEvent_t ev_pts; bool pts_in_flight;   // pinned staging of the scan: one async copy (or upload launch), no wait in set_scan
+    bool upload_pending; size_t upload_bytes;              // set_scan filled the staging block; the first launch that reads the points issues the upload (hs_flush_scan) -- a single match pulls the block itself
+    uint32_t upload_seq;                                   // upload launches issued; the launch stores it behind the staged points (h_pts + 2 * cap) when it has read them
+    float *d_io; float *h_io; int cap_io;                // hints in / poses out (floats)
+    // K5 line tables, per level: lines by index, lines sorted by (direction class, slope bucket), bucket starts, header
+    void *d_k5_byidx, *d_k5_cand; int *d_k5_start, *d_k5_hdr; int cap_lines;
+    int *d_k5_sec; int k5_sec_parity; bool k5_toggle_pending;                        // [2][HS_MAX_LEVELS][K5_SEC] sector records of the cell kernel: an update reads the set the last one wrote
+    int match_threads;                                     // slamhip_hs_set_match_threads: 0 the device's summation order, 1 .. HS_REF_MAX_T the reference's
+    int ref_cache;                                         // slamhip_hs_set_reference_cache: 1 every probability reader goes through d_cache
+    // the match reports (slamhip_match_report): the batch's reports and the best-of-batch key word in device memory, and a pinned,
+    // device-visible block the host reads them from -- a single blocking match stores its report there itself, in front of the
+    // mailbox's sequence word (the mailbox is 64 B, the report 76)
+    slamhip_match_report *d_rep, *h_rep; int cap_rep; unsigned long long *d_best_key;
+    int64_t win_ox, win_oy;                                // slamhip_hs_shift: where cell (0, 0) of level 0 lies in the world, in level-0 cells (host-side books only)
+    struct hs_backing *bk;                                 // slamhip_hs_set_backing: the tile pool and its host directory; nullptr while backing is off
+};
+
+struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
+struct hs_cache_arg { unsigned long long *c[HS_MAX_LEVELS]; int epoch[HS_MAX_LEVELS]; };
+// what a match is to report (hs_run_match): out_reports -- B reports, or the winner's alone with best_index set (slamhip_hs_match_best:
+// `out` is then the winner's pose)
+struct hs_report_req { slamhip_match_report *out_reports; int32_t *best_index; };
+
+// The update gated on the device (HectorSLAMProcessor's per-scan flow, slamhip_hsproc_update): the launch is enqueued right
+// behind the match, before the host has the pose -- the kernel reads the matched pose the match left in device memory, applies
+// the processor's own test (HectorSLAMProcessor.cs:107-109: moved more than min_dist or turned more than min_angle since the
+// last update) with the very float operations the host applies to the pose it receives, and either returns at once or forms
+// the level transforms (OccGridMap.cs:120-123) itself.  Without it the update waited for host round trip + launch: 11.5 us of
+// idle device between the two kernels of a scan.
+struct k5_gate { const float *d_pose; float last[3]; float min_dist, min_angle; float stm[HS_MAX_LEVELS]; int on; };
+__host__ __device__ static inline float hs_deg_diff(float a, float b)      // MathEx.DegDiff (BaseSLAM/MathEx.cs:69-73)
+{
+    float d = ((a - b) + 180.0f) / 360.0f;
+    return ((d - floorf(d)) * 360.0f) - 180.0f;
+}
+__host__ __device__ static inline bool hs_moved_enough(const float pose[3], const float last[3], float min_dist, float min_angle)
+{
+    const float ddx = pose[0] - last[0], ddy = pose[1] - last[1];
+    const float dist2 = ddx * ddx + ddy * ddy;                            // Vector2.DistanceSquared :107
+    return dist2 > min_dist * min_dist || hs_deg_diff(pose[2], last[2]) > min_angle;   // :108 (radians through DegDiff, as the reference does)
+}
+
+// OccGridMap.GetCachedProbability (:97-107)
+__device__ static inline float hs_prob_v(float v)
+{
+    const float odds = expf(v);                                            // :101
+    return odds / (odds + 1.0f);                                           // :102
+}
+// a CachedMapElement {Value, Index} as one word (hs_cache_taps, hs_match.hip)
+__device__ static __forceinline__ float hs_cache_entry_value(unsigned long long e) { return __uint_as_float((unsigned)e); }
+__device__ static __forceinline__ bool hs_cache_entry_hit(unsigned long long e, int epoch) { return (int)(e >> 32) == epoch; }   // :99
+__device__ static __forceinline__ unsigned long long hs_cache_entry(float v, int epoch)
+{
+    return ((unsigned long long)(unsigned)epoch << 32) | (unsigned long long)__float_as_uint(v);
+}
+// LogOddsCell.Reset (LogOddsCell.cs:38-42), and the probability every writer of the cells keeps beside it: hs_prob_v(0.0f) =
+// exp(0) / (exp(0) + 1), exactly 0.5f
+__host__ __device__ static inline slamhip_cell hs_reset_cell() { slamhip_cell c; c.update_index = -1; c.value = 0.0f; return c; }
+#define HS_RESET_PROB 0.5f
+
+// hector.hip
+// launches the scan upload that slamhip_hs_set_scan left pending (every launch that reads the points calls it first)
+int32_t hs_flush_scan(slamhip_hs *hs);
+// a level's cacheArray := new CachedMapElement[] (enqueued on the operator's stream; slamhip_hs_set_reference_cache)
+void    hs_cache_clear_enqueue(slamhip_hs *hs, int level);
+// hs_match.hip
+int32_t hs_run_match(slamhip_hs *hs, const float *hints, int B, float *out, int only_level, int iters, uint32_t *defer_seq = nullptr,
+                     const hs_report_req *rq = nullptr);
+int32_t hs_match_collect(slamhip_hs *hs, uint32_t seq, float *out, slamhip_match_report *out_report = nullptr);
+// hs_update.hip
+// the launches of UpdateByScan on the operator's stream; gate_in: the device-gated form, committed by hs_update_commit once the
+// host knows that the update took place
+int32_t hs_update_enqueue(slamhip_hs *hs, const float pose[3], const k5_gate *gate_in = nullptr);
+void    hs_update_commit(slamhip_hs *hs);
+bool    hs_update_gateable(slamhip_hs *hs);
+// hs_window.hip
+void    hs_bk_reset(slamhip_hs *hs);        // slamhip_hs_reset with backing on: the directory goes, the pool stays -- every slot Reset again
+void    hs_bk_free(slamhip_hs *hs);         // (the caller has drained the stream)

@@ -1,0 +1,243 @@
+// hs_processor.hip -- HectorSLAMProcessor (slamhip_hsproc_*): the per-scan flow over the operator object.  Host code only.
+#include "hs_internal.h"
+#include <chrono>
+
+// ---- HectorSLAMProcessor (Main/HectorSLAMProcessor.cs) ---------------------------------------------------------------
+struct slamhip_hsproc {
+    slamhip_hs *hs;
+    float start_pose[3], match_pose[3], last_update_pose[3];
+    float match_timing, update_timing;
+    float min_dist, min_angle;
+    unsigned upd_hist;                                     // the last scans' update decisions, newest in bit 0
+    int want_report, report_valid;                         // slamhip_hsproc_set_match_report; the last Update's match left `report`
+    slamhip_match_report report;
+    int scroll_trigger;                                    // slamhip_hsproc_set_scroll: 0 off.  match_pose and last_update_pose are kept in the WINDOW's frame
+};
+
+static const float F_MIN = -3.40282347e+38f;       // float.MinValue
+
+extern "C" int32_t slamhip_hsproc_create(slamhip_ctx *ctx, float res, int32_t w, int32_t h, const float start[3], int32_t depth,
+                                         slamhip_hsproc **out)
+{
+    SH_CHECK_ARG(ctx && start && out);
+    slamhip_hs *hs = nullptr;
+    SH_TRY(slamhip_hs_create(ctx, res, w, h, depth, &hs));                // :71
+    slamhip_hsproc *p = (slamhip_hsproc *)calloc(1, sizeof(*p));
+    if (!p) { slamhip_hs_destroy(hs); SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory"); }
+    p->hs = hs;
+    memcpy(p->start_pose, start, sizeof(float) * 3);
+    memcpy(p->match_pose, start, sizeof(float) * 3);                      // :75
+    p->last_update_pose[0] = p->last_update_pose[1] = p->last_update_pose[2] = F_MIN;   // :76
+    p->min_dist = 0.3f; p->min_angle = 0.13f;                             // :51,:56
+    *out = p;
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_destroy(slamhip_hsproc *p)
+{
+    if (!p) return SLAMHIP_OK;
+    slamhip_hs_destroy(p->hs);
+    free(p);
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_reset(slamhip_hsproc *p)
+{
+    SH_CHECK_ARG(p);
+    SH_TRY(slamhip_hs_reset(p->hs));                                      // :133
+    memcpy(p->match_pose, p->start_pose, sizeof(float) * 3);              // :136
+    p->last_update_pose[0] = p->last_update_pose[1] = p->last_update_pose[2] = F_MIN;   // :137
+    p->upd_hist = 0;
+    p->report_valid = 0;
+    return SLAMHIP_OK;
+}
+
+// (float)origin * cell0 per axis: what takes a world coordinate to the window's frame and back (slamhip_hs_shift's contract)
+static inline void hsproc_window_offset(const slamhip_hsproc *p, float off[2])
+{
+    off[0] = (float)p->hs->win_ox * p->hs->lv[0].cell;
+    off[1] = (float)p->hs->win_oy * p->hs->lv[0].cell;
+}
+
+// HectorSLAMProcessor.Update (:83-125) in the window's frame: hint, match_pose and last_update_pose all are window-frame poses
+static int32_t hsproc_update_window(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2],
+                                    const float hint[3], int32_t map_without_matching, int32_t *out_updated)
+{
+    p->report_valid = 0;
+    const hs_report_req rq = { &p->report, nullptr };
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    static const bool wait_update = sh_env_set("SLAMHIP_HS_WAIT_UPDATE");
+    // (worth it when the update does take place: a gated launch that returns at once still costs the stream ~15 us -- 512 workgroups
+    // of 1024 lanes are dispatched to find that out -- so the flow is taken while the last two scans both updated the map: measured,
+    // every scan updating 70 -> 66 us per scan; one scan in five, where it is never taken, 55 either way, 71 if it always were)
+    if (!map_without_matching && !wait_update && (p->upd_hist & 3u) == 3u && hs_update_gateable(p->hs)) {
+        // The per-scan flow on the device: match, then the grid update gated by the processor's own test (k5_gate) -- both enqueued
+        // before the host has the pose, which it then takes from the mailbox and puts to the same test for its own books.
+        slamhip_hs *hs = p->hs;
+        sh_mail_guard lock(hs->ctx);
+        auto t0 = std::chrono::steady_clock::now();
+        float m[3];
+        uint32_t seq = 0;
+        SH_TRY(hs_run_match(hs, hint, 1, m, -1, 0, &seq, p->want_report ? &rq : nullptr));   // :93
+        k5_gate g;
+        memset(&g, 0, sizeof(g));
+        g.d_pose = hs->d_io + 3;                                          // (the single match's result in device memory: hs_run_match)
+        memcpy(g.last, p->last_update_pose, sizeof(g.last));
+        g.min_dist = p->min_dist; g.min_angle = p->min_angle;
+        const int32_t rc_u = hs_update_enqueue(hs, hint, &g);
+        auto t1 = std::chrono::steady_clock::now();
+        SH_TRY(hs_match_collect(hs, seq, m, p->want_report ? &p->report : nullptr));
+        SH_TRY(rc_u);
+        p->report_valid = p->want_report;
+        memcpy(p->match_pose, m, sizeof(m));
+        auto t2 = std::chrono::steady_clock::now();
+        const float ms_u = std::chrono::duration<float, std::milli>(t1 - t0).count();      // (launches of match + update; the match's share is a few us)
+        const float ms_m = std::chrono::duration<float, std::milli>(t2 - t0).count();
+        p->match_timing = (3.0f * p->match_timing + ms_m) / 4.0f;         // :96
+        int updated = 0;
+        if (hs_moved_enough(p->match_pose, p->last_update_pose, p->min_dist, p->min_angle)) {   // :107-108, as the kernel decided
+            hs_update_commit(hs);
+            p->update_timing = (3.0f * p->update_timing + ms_u) / 4.0f;   // :115 (the time of the enqueue)
+            memcpy(p->last_update_pose, p->match_pose, sizeof(float) * 3);    // :118
+            updated = 1;                                                  // :122
+        } else hs->k5_toggle_pending = false;
+        p->upd_hist = (p->upd_hist << 1) | (unsigned)updated;
+        if (out_updated) *out_updated = updated;
+        return SLAMHIP_OK;
+    }
+    if (!map_without_matching) {                                          // :89
+        auto t0 = std::chrono::steady_clock::now();
+        float m[3];
+        SH_TRY(hs_run_match(p->hs, hint, 1, m, -1, 0, nullptr, p->want_report ? &rq : nullptr));   // :93
+        p->report_valid = p->want_report;
+        memcpy(p->match_pose, m, sizeof(m));
+        const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        p->match_timing = (3.0f * p->match_timing + ms) / 4.0f;           // :96
+    } else {
+        memcpy(p->match_pose, hint, sizeof(float) * 3);                   // :100
+    }
+    int updated = 0;
+    if (hs_moved_enough(p->match_pose, p->last_update_pose, p->min_dist, p->min_angle) ||   // :107-108
+        map_without_matching) {                                           // :109
+        // The grid update returns nothing to the host: it is enqueued and runs on while the caller prepares its next scan --
+        // the next match, a download or an export is ordered behind it on the operator's stream (UpdateTiming :115 is then
+        // the time of the enqueue; SLAMHIP_HS_WAIT_UPDATE=1 waits for the update as before).
+        auto t0 = std::chrono::steady_clock::now();
+        if (wait_update) { SH_TRY(slamhip_hs_update_by_scan(p->hs, p->match_pose)); }   // :112
+        else { SH_TRY(hs_update_enqueue(p->hs, p->match_pose)); }
+        const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        p->update_timing = (3.0f * p->update_timing + ms) / 4.0f;         // :115
+        memcpy(p->last_update_pose, p->match_pose, sizeof(float) * 3);    // :118
+        updated = 1;                                                      // :122
+    }
+    p->upd_hist = (p->upd_hist << 1) | (unsigned)updated;
+    if (out_updated) *out_updated = updated;
+    return SLAMHIP_OK;
+}
+
+// The scrolling window (slamhip_hsproc_set_scroll), at the end of an Update: the match pose is on the host and this scan's grid
+// update -- gated or not -- is enqueued, with the pose it reads in device memory in THIS scan's window frame; the shift goes
+// behind it on the same stream.  Nothing is enqueued ahead for the next scan: its match and update take the cell pointers and
+// the hint when they are enqueued, after the swap and the re-base below.  All in binary32, one rounding per operation.
+static int32_t hsproc_scroll(slamhip_hsproc *p)
+{
+    slamhip_hs *hs = p->hs;
+    const hs_level &L0 = hs->lv[0];
+    const int g = 1 << (hs->n_levels - 1);
+    const float cf[2] = { floorf(p->match_pose[0] * L0.stm), floorf(p->match_pose[1] * L0.stm) };
+    if (!(fabsf(cf[0]) < 1.0e9f && fabsf(cf[1]) < 1.0e9f)) return SLAMHIP_OK;    // (a pose that is no number or nowhere near any map moves nothing)
+    const int c[2] = { (int)cf[0], (int)cf[1] };
+    const int half[2] = { L0.w / 2, L0.h / 2 };
+    int q[2];
+    for (int a = 0; a < 2; a++) {
+        const int d = c[a] - half[a];
+        q[a] = (d > p->scroll_trigger || -d > p->scroll_trigger) ? (d / g) * g : 0;   // (C division: toward zero)
+    }
+    if (q[0] == 0 && q[1] == 0) return SLAMHIP_OK;
+    SH_TRY(slamhip_hs_shift(hs, q[0], q[1]));
+    for (int a = 0; a < 2; a++) {
+        const float m = (float)q[a] * L0.cell;                             // (the product is rounded, then the difference)
+        p->match_pose[a] = p->match_pose[a] - m;
+        p->last_update_pose[a] = p->last_update_pose[a] - m;               // (float.MinValue absorbs it: "never updated" survives)
+    }
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2],
+                                         const float hint[3], int32_t map_without_matching, int32_t *out_updated)
+{
+    SH_CHECK_ARG(p && hint);
+    if (p->hs->win_ox == 0 && p->hs->win_oy == 0 && p->scroll_trigger == 0)
+        return hsproc_update_window(p, xy, n, origin, hint, map_without_matching, out_updated);
+    float off[2];
+    hsproc_window_offset(p, off);
+    const float hint_w[3] = { hint[0] - off[0], hint[1] - off[1], hint[2] };       // poses cross the C-ABI in the world frame
+    SH_TRY(hsproc_update_window(p, xy, n, origin, hint_w, map_without_matching, out_updated));
+    return p->scroll_trigger > 0 ? hsproc_scroll(p) : SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_set_scroll(slamhip_hsproc *p, int32_t trigger_cells)
+{
+    SH_CHECK_ARG(p);
+    const hs_level &L0 = p->hs->lv[0];
+    const int g = 1 << (p->hs->n_levels - 1);
+    const int lim = (L0.w < L0.h ? L0.w : L0.h) / 2 - g;
+    if (trigger_cells < 0 || trigger_cells >= lim)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_hsproc_set_scroll: trigger_cells = %d is outside [0, min(w0, h0) / 2 - g) = [0, %d)", trigger_cells, lim > 0 ? lim : 0);
+    p->scroll_trigger = trigger_cells;                                    // (read at the end of the next slamhip_hsproc_update)
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_get_origin(slamhip_hsproc *p, int64_t *ox, int64_t *oy)
+{
+    SH_CHECK_ARG(p);
+    return slamhip_hs_origin(p->hs, ox, oy);
+}
+
+extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)
+{
+    SH_CHECK_ARG(p);
+    float off[2];
+    hsproc_window_offset(p, off);
+    if (p->hs->win_ox == 0 && p->hs->win_oy == 0) {                        // (never shifted: the stored bits themselves, -0.0f included)
+        if (match_pose) memcpy(match_pose, p->match_pose, sizeof(float) * 3);
+        if (last) memcpy(last, p->last_update_pose, sizeof(float) * 3);
+        match_pose = last = nullptr;
+    }
+    if (match_pose) { match_pose[0] = p->match_pose[0] + off[0]; match_pose[1] = p->match_pose[1] + off[1]; match_pose[2] = p->match_pose[2]; }
+    if (last) { last[0] = p->last_update_pose[0] + off[0]; last[1] = p->last_update_pose[1] + off[1]; last[2] = p->last_update_pose[2]; }
+    if (mt) *mt = p->match_timing;
+    if (ut) *ut = p->update_timing;
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_set_match_report(slamhip_hsproc *p, int32_t on)
+{
+    SH_CHECK_ARG(p && (on == 0 || on == 1));
+    p->want_report = on;                                                  // (read by the next slamhip_hsproc_update)
+    if (!on) p->report_valid = 0;
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_get_report(slamhip_hsproc *p, slamhip_match_report *out, int32_t *out_valid)
+{
+    SH_CHECK_ARG(p && out && out_valid);
+    *out_valid = p->report_valid;
+    if (p->report_valid) *out = p->report;
+    else memset(out, 0, sizeof(*out));
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_dist, float min_angle)
+{
+    SH_CHECK_ARG(p);
+    p->min_dist = min_dist; p->min_angle = min_angle;
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out)
+{
+    SH_CHECK_ARG(p && out);
+    *out = p->hs;
+    return SLAMHIP_OK;
+}

@@ -3,7 +3,7 @@
 K2 (csrc/holemap.hip): after i iterations of the error recurrence of DrawLaserRayOnHoleMap
 (CoreSLAM/CoreSLAMProcessor.cs:394-396,:433-441) the walk has taken
     m(i) = min(i, max(0, ceil((2*dyc*i - dxc) / (2*dxc))))   minor steps.
-K5 (csrc/hector.hip): after i steps of Bresenham2D (HectorSLAM/Map/OccGridMap.cs:220-239) the walk has taken
+K5 (csrc/hs_update.hip): after i steps of Bresenham2D (HectorSLAM/Map/OccGridMap.cs:220-239) the walk has taken
     (e0 + i*db) // da   minor steps, e0 = da // 2, db <= da.
 """
 

@@ -19,7 +19,7 @@ else:
     open(os.path.join(tmp, "include", "slamhip.h"), "wb").write(subprocess.check_output(["git", "-C", root, "show", "%s:include/slamhip.h" % rev]))
 outdir = os.path.join(b.HERE, "build", "variants"); os.makedirs(outdir, exist_ok=True)
 procs, objs = [], []
-for src in b.SOURCES:
+for src in sorted(f for f in os.listdir(os.path.join(tmp, "slam.net_amd", "csrc")) if f.endswith(".hip")):   # (the revision's own units)
     o = os.path.join(tmp, src.replace(".hip", ".o")); objs.append(o)
     procs.append(subprocess.Popen([b.hipcc()] + b.FLAGS + defs + ["-c", os.path.join(tmp, "slam.net_amd", "csrc", src), "-o", o], stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
 for p in procs:
