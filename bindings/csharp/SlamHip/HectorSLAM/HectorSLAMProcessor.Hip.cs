@@ -150,6 +150,22 @@ namespace HectorSLAM.Main
             return true;
         }
 
+        /// <summary>The processor's world -- window and tiles -- as one file (MapRep.SaveWorld).</summary>
+        public void SaveWorld(string path)
+        {
+            MapRep.SaveWorld(path);
+        }
+
+        /// <summary>Resume from a saved world (MapRep.LoadWorld): construct the processor with startPose = the saved pose, LoadWorld,
+        /// Update.  The window moves through slamhip_hsproc_shift, so MatchPose and LastMapUpdatePose stay the world poses they
+        /// were.  Returns the cells dropped.</summary>
+        public long LoadWorld(string path)
+        {
+            long dropped = MapRep.LoadWorld(path, (dx, dy) => Native.Check(Native.slamhip_hsproc_shift(proc.Ptr, dx, dy)));
+            Refresh();
+            return dropped;
+        }
+
         private void Refresh()
         {
             Native.Check(Native.slamhip_hsproc_get(proc.Ptr, out Vector3 match, out Vector3 last, out float tm, out float tu));

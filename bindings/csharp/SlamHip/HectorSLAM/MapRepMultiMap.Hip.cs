@@ -143,6 +143,110 @@ namespace HectorSLAM.Main
             return cells;
         }
 
+        /// <summary>The inverse of WorldCells (slamhip_hs_world_cells_upload): cells[w * h], row-major, replaces the rectangle
+        /// [x0, x0 + w) x [y0, y0 + h) of `level` in WORLD cells -- the window's part in the window, the rest in tile slots when
+        /// backing is on (a tile is made only where the rectangle holds a cell that is not LogOddsCell.Reset()).  Returns the
+        /// non-Reset cells dropped: everything outside the window with backing off, what found no slot with backing on.  Blocking;
+        /// never fails for capacity.</summary>
+        public unsafe long WorldPut(int level, long x0, long y0, int w, int h, LogOddsCell[] cells)
+        {
+            if (cells == null || w < 1 || h < 1 || cells.LongLength != (long)w * h)
+                throw new ArgumentException("WorldPut: cells must hold w * h cells");
+            long dropped;
+            fixed (LogOddsCell* p = cells)
+                Native.Check(Native.slamhip_hs_world_cells_upload(Pyramid.Ptr, level, x0, y0, w, h, p, out dropped));
+            MarkStale();
+            return dropped;
+        }
+
+        /// <summary>The extents of the world on `level`, in WORLD cells, over the cells whose Value != 0 in the window and in every
+        /// tile (slamhip_hs_world_extends); false, and zeros, if there is none.</summary>
+        public unsafe bool WorldExtends(int level, out long xMax, out long yMax, out long xMin, out long yMin)
+        {
+            long* e = stackalloc long[4];
+            Native.Check(Native.slamhip_hs_world_extends(Pyramid.Ptr, level, e, out int found));
+            xMax = e[0]; yMax = e[1]; xMin = e[2]; yMin = e[3];
+            return found != 0;
+        }
+
+        private const ulong WorldMagic = 0x31444C524F574853UL;          // "SHWORLD1"
+        private const int WorldBandCells = 1 << 26;                      // the bound of one world download / upload
+
+        /// <summary>The world as one raw little-endian file (this shim's own format, not the Python binding's .npz): the magic
+        /// "SHWORLD1"; float cell length of level 0; int32 level-0 width, height, levels; int64 origin x, y; int32 tile and uint64
+        /// max_bytes of the backing setting (zeros: off); then per level int64 x0, y0 and int32 w, h of the WorldExtends rectangle
+        /// (all zero for an empty level) followed by its w * h cells {int32 UpdateIndex, float Value}, row-major.</summary>
+        public void SaveWorld(string path)
+        {
+            using var f = new System.IO.BinaryWriter(System.IO.File.Create(path));
+            BackingStats st = BackingStats;
+            (long ox, long oy) = Origin;
+            f.Write(WorldMagic); f.Write(Maps[0].Properties.CellLength);
+            f.Write(Maps[0].Dimensions.X); f.Write(Maps[0].Dimensions.Y); f.Write(NumLevels);
+            f.Write(ox); f.Write(oy); f.Write(st.Tile); f.Write((ulong)st.CapacityBytes);
+            for (int l = 0; l < NumLevels; l++)
+            {
+                if (!WorldExtends(l, out long xMax, out long yMax, out long xMin, out long yMin))
+                {
+                    f.Write(0L); f.Write(0L); f.Write(0); f.Write(0);
+                    continue;
+                }
+                int w = checked((int)(xMax - xMin + 1)), h = checked((int)(yMax - yMin + 1));
+                f.Write(xMin); f.Write(yMin); f.Write(w); f.Write(h);
+                int rows = Math.Max(1, WorldBandCells / w);
+                for (int r = 0; r < h; r += rows)
+                    f.Write(MemoryMarshal.AsBytes(WorldCells(l, xMin, yMin + r, w, Math.Min(rows, h - r)).AsSpan()));
+            }
+        }
+
+        /// <summary>Resume from a file SaveWorld wrote: a geometry that differs from this pyramid's is refused before anything
+        /// changes; the window is shifted to the saved origin (through `shift` if given: HectorSLAMProcessor.LoadWorld keeps its poses
+        /// world poses that way); backing is switched on with the saved setting if it is off here and was on there; every level's
+        /// rectangle is put back with WorldPut.  Returns the cells dropped.</summary>
+        public long LoadWorld(string path, Action<int, int> shift = null)
+        {
+            using var f = new System.IO.BinaryReader(System.IO.File.OpenRead(path));
+            if (f.ReadUInt64() != WorldMagic) throw new System.IO.InvalidDataException("LoadWorld: not a SHWORLD1 file");
+            float cell = f.ReadSingle();
+            int w0 = f.ReadInt32(), h0 = f.ReadInt32(), levels = f.ReadInt32();
+            if (BitConverter.SingleToInt32Bits(cell) != BitConverter.SingleToInt32Bits(Maps[0].Properties.CellLength) ||
+                w0 != Maps[0].Dimensions.X || h0 != Maps[0].Dimensions.Y || levels != NumLevels)
+                throw new System.IO.InvalidDataException($"LoadWorld: the saved pyramid ({cell}, {w0} x {h0} x {levels}) is not this one");
+            long sox = f.ReadInt64(), soy = f.ReadInt64();
+            int tile = f.ReadInt32();
+            ulong maxBytes = f.ReadUInt64();
+            int g = 1 << (NumLevels - 1), step = (1 << 30) / g * g;      // (slamhip_hs_shift takes 32-bit moves)
+            for ((long ox, long oy) = Origin; ox != sox || oy != soy; (ox, oy) = Origin)
+            {
+                int dx = (int)Math.Clamp(sox - ox, -step, step), dy = (int)Math.Clamp(soy - oy, -step, step);
+                if (shift != null) shift(dx, dy); else Shift(dx, dy);
+            }
+            if (maxBytes > 0 && BackingStats.On == 0) SetBacking(tile, maxBytes);   // (after the move: an empty window makes no tiles)
+            long dropped = 0;
+            for (int l = 0; l < NumLevels; l++)
+            {
+                long x0 = f.ReadInt64(), y0 = f.ReadInt64();
+                int w = f.ReadInt32(), h = f.ReadInt32();
+                if (w == 0 || h == 0) continue;
+                int rows = Math.Max(1, WorldBandCells / w);
+                for (int r = 0; r < h; r += rows)
+                {
+                    int n = Math.Min(rows, h - r);
+                    var cells = new LogOddsCell[(long)w * n];
+                    Span<byte> rest = MemoryMarshal.AsBytes(cells.AsSpan());
+                    while (rest.Length > 0)                             // (Stream.Read may return less than it was asked for)
+                    {
+                        int got = f.BaseStream.Read(rest);
+                        if (got <= 0) throw new System.IO.EndOfStreamException("LoadWorld: the file ends inside level " + l);
+                        rest = rest.Slice(got);
+                    }
+                    dropped += WorldPut(l, x0, y0 + r, w, n, cells);
+                }
+            }
+            MarkStale();
+            return dropped;
+        }
+
         /// <summary>The device maps changed behind this object's back (HectorSLAMProcessor.Update drives the native processor): host mirrors are stale.</summary>
         internal void MarkStale()
         {

@@ -152,6 +152,9 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_set_backing(IntPtr hs, int tileCells, ulong maxBytes);
         [DllImport(Lib)] internal static extern int slamhip_hs_backing_stats(IntPtr hs, out BackingStats stats);
         [DllImport(Lib)] internal static extern int slamhip_hs_world_cells_download(IntPtr hs, int level, long x0, long y0, int w, int h, HectorSLAM.Map.LogOddsCell* cells);
+        // ... and back: the inverse of the world download (returns OK whatever the capacity; droppedCells counts what found no place), and the world's extents
+        [DllImport(Lib)] internal static extern int slamhip_hs_world_cells_upload(IntPtr hs, int level, long x0, long y0, int w, int h, HectorSLAM.Map.LogOddsCell* cells, out long droppedCells);
+        [DllImport(Lib)] internal static extern int slamhip_hs_world_extends(IntPtr hs, int level, long* xMaxYMaxXMinYMin, out int found);
         // HectorSLAM, processor level (HectorSLAMProcessor.cs:66-138): the Update state machine in the library -- match, the gate of :107-109 evaluated
         // on the device, the grid update enqueued behind the match before the pose is back (one blocking wait per scan instead of two)
         [DllImport(Lib)] internal static extern int slamhip_hsproc_create(IntPtr ctx, float mapResolution, int width, int height, in Vector3 startPose, int numDepth, out IntPtr proc);
@@ -165,6 +168,7 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_hs(IntPtr proc, out IntPtr hs);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_set_scroll(IntPtr proc, int triggerCells);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_get_origin(IntPtr proc, out long ox, out long oy);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_shift(IntPtr proc, int dx, int dy);
 
         // ---- one process, several GPUs -------------------------------------------------------------------------------
         [DllImport(Lib)] internal static extern int slamhip_group_create(int* deviceOrdinals, int n, float physicalMapSize, int holeMapSize, int obstacleMapSize, out IntPtr group);

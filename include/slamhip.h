@@ -75,6 +75,12 @@ typedef struct slamhip_backing_job {
     int32_t lx, ly;
 } slamhip_backing_job;
 
+/* One job of slamhip_hs_world_cells_upload (the planner, slamhip_debug_world_plan): nx x ny cells of the caller's rectangle from
+ * rectangle cell (sx, sy), which go into the window (kind SLAMHIP_WORLD_WINDOW: (lx, ly) in window coordinates, tx = ty = 0) or
+ * into world tile (tx, ty) (SLAMHIP_WORLD_TILE: (lx, ly) in the tile's local coordinates; lx + nx <= tile, ly + ny <= tile). */
+enum { SLAMHIP_WORLD_WINDOW = 0, SLAMHIP_WORLD_TILE = 1 };
+typedef struct slamhip_world_job { int32_t kind, sx, sy, nx, ny, lx, ly, pad; int64_t tx, ty; } slamhip_world_job;
+
 /* ------------------------------------------------------------------------------------------------
  * Library / context
  * ---------------------------------------------------------------------------------------------- */
@@ -118,6 +124,17 @@ int32_t slamhip_debug_flag_wait(volatile uint32_t *flag, uint32_t val, int64_t t
 int32_t slamhip_debug_backing_plan(int32_t levels, int32_t w0, int32_t h0, int64_t ox, int64_t oy,
                                    int32_t dx, int32_t dy, int32_t tile,
                                    slamhip_backing_job *jobs, int32_t cap, int32_t *n_jobs);
+/* Test hook (no device involved): the planner of slamhip_hs_world_cells_upload for the rectangle [x0, x0 + rw) x [y0, y0 + rh) in
+ * WORLD cells of one level whose window is w x h cells with cell (0, 0) at world cell (OX, OY); tile: the tile side, a power of
+ * two in [8, 256], or 0 for backing off.  The jobs come in the order the upload uses them (and deals tile slots in): the window
+ * job first (at most one; the rectangle's intersection with the window); then, with tile > 0, the part of the rectangle outside
+ * the window, cut as the backing planner cuts a region -- band above the window, band below it, left strip, right strip; the whole
+ * rectangle if it misses the window -- row-major by tile (ty, tx), the jobs of one tile in that rectangle order.  With tile = 0 the
+ * window job is all there is.  Every cell of the rectangle is in exactly one job with tile > 0.  *n_jobs receives the number of
+ * jobs; if it exceeds `cap`, nothing is written and the call returns SLAMHIP_ERR_INVALID (jobs may be NULL when cap is 0).
+ * w, h in [1, 32768]; rw, rh >= 1 with rw * rh <= 2^26; |OX|, |OY|, |x0|, |y0| < 2^60. */
+int32_t slamhip_debug_world_plan(int32_t w, int32_t h, int64_t OX, int64_t OY, int64_t x0, int64_t y0, int32_t rw, int32_t rh,
+                                 int32_t tile, slamhip_world_job *jobs, int32_t cap, int32_t *n_jobs);
 
 /* Kernel timing (the reference only has Stopwatch EMAs, HectorSLAMProcessor.cs:92-96,111-115).
  * When enabled, each kernel class is bracketed by HIP events on the context's stream. */
@@ -642,6 +659,39 @@ int32_t slamhip_hs_backing_stats(slamhip_hs *hs, slamhip_backing_stats *out);
  * with backing off as well: the window in a frame of Reset cells. */
 int32_t slamhip_hs_world_cells_download(slamhip_hs *hs, int32_t level, int64_t x0, int64_t y0,
                                         int32_t w, int32_t h, slamhip_cell *out);
+/* The inverse of the world download: load a saved world back.  cells[w * h], row-major, is the rectangle
+ * [x0, x0 + w) x [y0, y0 + h) of level `level` in WORLD cells.
+ * OVERWRITE: every cell of the rectangle replaces what the world holds at that place.  A cell that lies in the window (level
+ * origin (win_ox >> level, win_oy >> level)) goes into the window's cells, and its probability -- formed on the device by the
+ * function every writer of the cells uses, so the matcher reads the bits it reads after slamhip_hs_cells_upload -- into the
+ * window's probabilities.  The part of a tile that lies under the window is NOT written: the window wins, as it does in the
+ * download, and the tile's copy there is overwritten when those cells next leave the window.
+ * Outside the window with backing on, the cells go into their tiles' slots, cells followed by probabilities.  If a tile does not
+ * exist, a slot is taken as a shift takes one (lazy chunks, max_bytes, initialised on the stream before first use) -- but only if
+ * the piece of the rectangle that falls into that tile (outside the window) holds at least one cell that is not
+ * LogOddsCell.Reset() {-1, 0.0f}, compared as bits: an all-Reset piece takes no slot, so a sparse world loads sparse.  An all-Reset
+ * piece over an EXISTING tile is written (overwrite).  Slots are dealt in the planner's job order (slamhip_debug_world_plan), so
+ * what is kept is deterministic.
+ * An upload never fails for capacity: if no slot can be had (the pool is at max_bytes, or the device allocation of a chunk fails),
+ * the non-Reset cells of that piece are dropped and counted into dropped_cells of slamhip_hs_backing_stats and into *out_dropped,
+ * and the call still returns SLAMHIP_OK; evicted_cells and restored_cells do not move.  With backing off the window part is
+ * written, every non-Reset cell outside it is counted in *out_dropped, and nothing is allocated for tiles.  out_dropped may be NULL.
+ * The level's update index follows the rule of slamhip_hs_cells_upload: with mx the largest update_index in cells[], it becomes at
+ * least (mx / 3 + 1) * 3, so that the next scan's marks exceed every stored index -- a map resumed from a saved world writes the
+ * marks the original writes.  The cache epoch, the reference's cache and the origin are left as they are.
+ * Blocking, behind everything already on the operator's stream, with the context's bounded wait.  The caller's array reaches the
+ * device through a staging buffer the library owns (kept for the next call); ONE launch scatters it.  w, h >= 1 and
+ * w * h <= 2^26 cells, |x0|, |y0| < 2^60; anything else SLAMHIP_ERR_INVALID, nothing changed.  A poisoned context:
+ * SLAMHIP_ERR_TIMEOUT. */
+int32_t slamhip_hs_world_cells_upload(slamhip_hs *hs, int32_t level, int64_t x0, int64_t y0,
+                                      int32_t w, int32_t h, const slamhip_cell *cells, int64_t *out_dropped);
+/* The extents of the world: extends = {xMax, yMax, xMin, yMin} in WORLD cells of level `level`, over the cells whose Value != 0.0f
+ * (a NaN counts, as in GridMap.GetMapExtends, GridMap.cs:161) in the window and in every tile of that level, EXCLUDING the part of
+ * a tile that lies under the window (those copies are stale: the window wins) -- the rectangle a host downloads to save the
+ * world.  If there is no such cell: *found = 0 and extends is zeroed; the reference's quirk of minima that start at 10000
+ * (slamhip_hs_map_extends) does not apply here: the results are 64-bit and any cell counts.  Reduced on the device in ONE launch
+ * over the window and the tiles.  Blocking, with the context's bounded wait.  Works with backing off: the window only. */
+int32_t slamhip_hs_world_extends(slamhip_hs *hs, int32_t level, int64_t extends[4], int32_t *found);
 
 /* ------------------------------------------------------------------------------------------------
  * HectorSLAM, processor level
@@ -685,6 +735,10 @@ int32_t slamhip_hsproc_get_report(slamhip_hsproc *p, slamhip_match_report *out, 
  * the origin returns to 0 there (slamhip_hs_reset).  slamhip_hsproc_get_origin: slamhip_hs_origin of the processor's own hs. */
 int32_t slamhip_hsproc_set_scroll(slamhip_hsproc *p, int32_t trigger_cells);
 int32_t slamhip_hsproc_get_origin(slamhip_hsproc *p, int64_t *ox, int64_t *oy);
+/* slamhip_hs_shift(dx, dy) of the processor's own hs from outside an Update (resuming from a saved world: the window goes to the
+ * saved origin), with the processor's MatchPose and LastMapUpdatePose -- kept in the window's frame -- re-based as the scroll
+ * re-bases them, so that slamhip_hsproc_get goes on answering in the world frame.  Arguments and errors as slamhip_hs_shift. */
+int32_t slamhip_hsproc_shift(slamhip_hsproc *p, int32_t dx, int32_t dy);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -65,6 +65,18 @@ BACKING_JOB_DTYPE = np.dtype([("level", np.int32), ("kind", np.int32), ("wx", np
 assert C.sizeof(BackingStats) == 56 and C.sizeof(BackingJob) == BACKING_JOB_DTYPE.itemsize == 48
 
 
+class WorldJob(C.Structure):
+    """slamhip_world_job (include/slamhip.h): one job of the world upload's planner, 48 bytes."""
+    _fields_ = [("kind", C.c_int32), ("sx", C.c_int32), ("sy", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("lx", C.c_int32),
+                ("ly", C.c_int32), ("pad", C.c_int32), ("tx", C.c_int64), ("ty", C.c_int64)]
+
+
+WORLD_WINDOW, WORLD_TILE = 0, 1
+WORLD_JOB_DTYPE = np.dtype([("kind", np.int32), ("sx", np.int32), ("sy", np.int32), ("nx", np.int32), ("ny", np.int32), ("lx", np.int32),
+                            ("ly", np.int32), ("pad", np.int32), ("tx", np.int64), ("ty", np.int64)])
+assert C.sizeof(WorldJob) == WORLD_JOB_DTYPE.itemsize == 48
+
+
 class SlamhipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("slamhip error %d: %s" % (code, msg))
@@ -114,6 +126,7 @@ def _declare(L):
         "slamhip_ctx_philox4x32_10": (i32, [vp, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]),
         "slamhip_debug_flag_wait": (i32, [P(C.c_uint32), C.c_uint32, i64]),
         "slamhip_debug_backing_plan": (i32, [i32, i32, i32, i64, i64, i32, i32, i32, P(BackingJob), i32, ip]),
+        "slamhip_debug_world_plan": (i32, [i32, i32, i64, i64, i64, i64, i32, i32, i32, P(WorldJob), i32, ip]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -203,6 +216,8 @@ def _declare(L):
         "slamhip_hs_set_backing": (i32, [vp, i32, u64]),
         "slamhip_hs_backing_stats": (i32, [vp, P(BackingStats)]),
         "slamhip_hs_world_cells_download": (i32, [vp, i32, i64, i64, i32, i32, vp]),
+        "slamhip_hs_world_cells_upload": (i32, [vp, i32, i64, i64, i32, i32, vp, P(i64)]),
+        "slamhip_hs_world_extends": (i32, [vp, i32, P(i64), ip]),
         "slamhip_hsproc_create": (i32, [vp, f, i32, i32, fp, i32, vpp]),
         "slamhip_hsproc_destroy": (i32, [vp]),
         "slamhip_hsproc_reset": (i32, [vp]),
@@ -214,6 +229,7 @@ def _declare(L):
         "slamhip_hsproc_hs": (i32, [vp, vpp]),
         "slamhip_hsproc_set_scroll": (i32, [vp, i32]),
         "slamhip_hsproc_get_origin": (i32, [vp, P(i64), P(i64)]),
+        "slamhip_hsproc_shift": (i32, [vp, i32, i32]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -260,6 +276,20 @@ def backing_plan(levels, w0, h0, ox, oy, dx, dy, tile):
         check(rc)
     jobs = np.zeros(n.value, BACKING_JOB_DTYPE)
     call("slamhip_debug_backing_plan", levels, w0, h0, ox, oy, dx, dy, tile, jobs.ctypes.data_as(C.POINTER(BackingJob)), n.value, C.byref(n))
+    return jobs
+
+
+def world_plan(w, h, OX, OY, x0, y0, rw, rh, tile):
+    """The job list of the world upload's planner for one rectangle (slamhip_debug_world_plan; no device involved): a
+    WORLD_JOB_DTYPE array in the order the upload uses."""
+    n = C.c_int32()
+    rc = lib().slamhip_debug_world_plan(w, h, OX, OY, x0, y0, rw, rh, tile, None, 0, C.byref(n))
+    if rc == OK:
+        return np.zeros(0, WORLD_JOB_DTYPE)
+    if n.value <= 0:
+        check(rc)
+    jobs = np.zeros(n.value, WORLD_JOB_DTYPE)
+    call("slamhip_debug_world_plan", w, h, OX, OY, x0, y0, rw, rh, tile, jobs.ctypes.data_as(C.POINTER(WorldJob)), n.value, C.byref(n))
     return jobs
 
 

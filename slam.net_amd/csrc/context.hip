@@ -1,6 +1,7 @@
 // context.hip -- library / context entry points of include/slamhip.h (gfx950 only).
 #include "common.h"
 #include "backing_plan.h"
+#include "world_plan.h"
 #include <stdlib.h>
 #include <time.h>
 
@@ -262,6 +263,24 @@ extern "C" int32_t slamhip_debug_backing_plan(int32_t levels, int32_t w0, int32_
     if (plan.size() > (size_t)cap)
         SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_debug_backing_plan: the plan has %zu jobs, the caller's array holds %d", plan.size(), cap);
     if (!plan.empty()) memcpy(jobs, plan.data(), sizeof(slamhip_backing_job) * plan.size());
+    return SLAMHIP_OK;
+}
+
+// CPU-side test hook: the planner of slamhip_hs_world_cells_upload (world_plan.h), as the upload calls it
+extern "C" int32_t slamhip_debug_world_plan(int32_t w, int32_t h, int64_t OX, int64_t OY, int64_t x0, int64_t y0, int32_t rw, int32_t rh,
+                                            int32_t tile, slamhip_world_job *jobs, int32_t cap, int32_t *n_jobs)
+{
+    const int64_t lim = (int64_t)1 << 60;
+    SH_CHECK_ARG(n_jobs && cap >= 0 && (jobs || cap == 0));
+    SH_CHECK_ARG(w >= 1 && h >= 1 && w <= 32768 && h <= 32768 && rw >= 1 && rh >= 1 && (int64_t)rw * rh <= ((int64_t)1 << 26));
+    SH_CHECK_ARG(OX > -lim && OX < lim && OY > -lim && OY < lim && x0 > -lim && x0 < lim && y0 > -lim && y0 < lim);
+    SH_CHECK_ARG(tile == 0 || (tile >= 8 && tile <= 256 && (tile & (tile - 1)) == 0));
+    std::vector<slamhip_world_job> plan;
+    wp_plan(w, h, OX, OY, x0, y0, rw, rh, tile, plan);
+    *n_jobs = (int32_t)plan.size();                                        // (at most 2^26 + 1 jobs)
+    if (plan.size() > (size_t)cap)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_debug_world_plan: the plan has %zu jobs, the caller's array holds %d", plan.size(), cap);
+    if (!plan.empty()) memcpy(jobs, plan.data(), sizeof(slamhip_world_job) * plan.size());
     return SLAMHIP_OK;
 }
 

@@ -113,6 +113,7 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
         (void)hipFree(hs->lv[l].d_cells_alt); (void)hipFree(hs->lv[l].d_prob_alt);
     }
     hs_bk_free(hs);
+    hs_wp_free(hs);
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
     if (hs->ev_pts) (void)hipEventDestroy(hs->ev_pts);

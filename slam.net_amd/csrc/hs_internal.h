@@ -38,6 +38,7 @@ struct hs_level_dev {                      // what the kernels need, by value
 #endif
 
 struct hs_backing;                         // hs_window.hip
+struct hs_world;                           // hs_window.hip
 struct slamhip_hs {
     slamhip_ctx *ctx;
     int n_levels;
@@ -61,6 +62,7 @@ struct slamhip_hs {
     slamhip_match_report *d_rep, *h_rep; int cap_rep; unsigned long long *d_best_key;
     int64_t win_ox, win_oy;                                // slamhip_hs_shift: where cell (0, 0) of level 0 lies in the world, in level-0 cells (host-side books only)
     struct hs_backing *bk;                                 // slamhip_hs_set_backing: the tile pool and its host directory; nullptr while backing is off
+    struct hs_world *wp;                                   // slamhip_hs_world_cells_upload / _world_extends: their staging buffer, made by the first call, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -124,3 +126,4 @@ bool    hs_update_gateable(slamhip_hs *hs);
 // hs_window.hip
 void    hs_bk_reset(slamhip_hs *hs);        // slamhip_hs_reset with backing on: the directory goes, the pool stays -- every slot Reset again
 void    hs_bk_free(slamhip_hs *hs);         // (the caller has drained the stream)
+void    hs_wp_free(slamhip_hs *hs);         // the staging buffer of the world upload and the world extents (the caller has drained the stream)

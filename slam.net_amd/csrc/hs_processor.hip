@@ -135,6 +135,20 @@ static int32_t hsproc_update_window(slamhip_hsproc *p, const float *xy, int32_t 
     return SLAMHIP_OK;
 }
 
+// slamhip_hs_shift of the processor's own hs with the stored poses, kept in the window's frame, re-based: the one place where the
+// scroll and slamhip_hsproc_shift move the window.  All in binary32, one rounding per operation.
+static int32_t hsproc_shift_rebase(slamhip_hsproc *p, int32_t dx, int32_t dy)
+{
+    SH_TRY(slamhip_hs_shift(p->hs, dx, dy));
+    const int32_t q[2] = { dx, dy };
+    for (int a = 0; a < 2; a++) {
+        const float m = (float)q[a] * p->hs->lv[0].cell;                   // (the product is rounded, then the difference)
+        p->match_pose[a] = p->match_pose[a] - m;
+        p->last_update_pose[a] = p->last_update_pose[a] - m;               // (float.MinValue absorbs it: "never updated" survives)
+    }
+    return SLAMHIP_OK;
+}
+
 // The scrolling window (slamhip_hsproc_set_scroll), at the end of an Update: the match pose is on the host and this scan's grid
 // update -- gated or not -- is enqueued, with the pose it reads in device memory in THIS scan's window frame; the shift goes
 // behind it on the same stream.  Nothing is enqueued ahead for the next scan: its match and update take the cell pointers and
@@ -154,13 +168,7 @@ static int32_t hsproc_scroll(slamhip_hsproc *p)
         q[a] = (d > p->scroll_trigger || -d > p->scroll_trigger) ? (d / g) * g : 0;   // (C division: toward zero)
     }
     if (q[0] == 0 && q[1] == 0) return SLAMHIP_OK;
-    SH_TRY(slamhip_hs_shift(hs, q[0], q[1]));
-    for (int a = 0; a < 2; a++) {
-        const float m = (float)q[a] * L0.cell;                             // (the product is rounded, then the difference)
-        p->match_pose[a] = p->match_pose[a] - m;
-        p->last_update_pose[a] = p->last_update_pose[a] - m;               // (float.MinValue absorbs it: "never updated" survives)
-    }
-    return SLAMHIP_OK;
+    return hsproc_shift_rebase(p, q[0], q[1]);
 }
 
 extern "C" int32_t slamhip_hsproc_update(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2],
@@ -192,6 +200,13 @@ extern "C" int32_t slamhip_hsproc_get_origin(slamhip_hsproc *p, int64_t *ox, int
 {
     SH_CHECK_ARG(p);
     return slamhip_hs_origin(p->hs, ox, oy);
+}
+
+// slamhip_hs_shift from outside an Update, the poses re-based as the scroll re-bases them
+extern "C" int32_t slamhip_hsproc_shift(slamhip_hsproc *p, int32_t dx, int32_t dy)
+{
+    SH_CHECK_ARG(p);
+    return hsproc_shift_rebase(p, dx, dy);
 }
 
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)

@@ -177,6 +177,89 @@ class MapRepMultiMap:
         capi.call("slamhip_hs_world_cells_download", self._h, int(level), int(x0), int(y0), int(w), int(h), out.ctypes.data_as(C.c_void_p))
         return out
 
+    def world_put(self, level, x0, y0, cells):
+        """The inverse of world_cells (slamhip_hs_world_cells_upload): `cells`, an (h, w) array of capi.CELL_DTYPE, replaces the
+        rectangle [x0, x0 + w) x [y0, y0 + h) of `level` in WORLD cells -- the window's part in the window (cells and the
+        probabilities formed from them), the rest in tile slots when backing is on (a tile is made only where the rectangle holds
+        a cell that is not LogOddsCell.Reset()).  -> the number of non-Reset cells dropped: everything outside the window with
+        backing off, what found no slot under max_bytes with backing on.  Blocking; never fails for capacity."""
+        cells = np.ascontiguousarray(cells, capi.CELL_DTYPE)
+        if cells.ndim != 2:
+            raise ValueError("world_put: cells must be an (h, w) array")
+        dropped = C.c_int64()
+        capi.call("slamhip_hs_world_cells_upload", self._h, int(level), int(x0), int(y0), int(cells.shape[1]), int(cells.shape[0]),
+                  cells.ctypes.data_as(C.c_void_p), C.byref(dropped))
+        return int(dropped.value)
+
+    def world_extends(self, level):
+        """(xmax, ymax, xmin, ymin) in WORLD cells of `level` over the cells whose Value != 0 in the window and in every tile (a
+        tile's stale copy under the window excluded), reduced on the device (slamhip_hs_world_extends); None if there is none."""
+        e = (C.c_int64 * 4)()
+        f = C.c_int32()
+        capi.call("slamhip_hs_world_extends", self._h, int(level), e, C.byref(f))
+        return (int(e[0]), int(e[1]), int(e[2]), int(e[3])) if f.value else None
+
+    WORLD_FORMAT = 1
+    _BAND_CELLS = 1 << 26                                           # the bound of one world download / upload
+
+    def _geometry(self):
+        return np.array([self.Maps[0].Dimensions[0], self.Maps[0].Dimensions[1], self.NumLevels], np.int64)
+
+    def save_world(self, path):
+        """The world as one .npz: per level the rectangle of world_extends as downloaded by world_cells (`rect_<l>` =
+        (x0, y0, w, h), all zero for an empty level, and `cells_<l>`), the geometry (`cell_length` of level 0, `geometry` =
+        level-0 width, height and the number of levels), the window's `origin`, the `backing` setting (tile, max_bytes; zeros:
+        off) and the format `version`.  Blocking."""
+        st = self.backing_stats()
+        out = {"version": np.int64(self.WORLD_FORMAT), "cell_length": np.float32(self.Maps[0].CellLength), "geometry": self._geometry(),
+               "origin": np.array(self.origin(), np.int64), "backing": np.array([st["tile"], st["capacity_bytes"]], np.int64)}
+        for l in range(self.NumLevels):
+            e = self.world_extends(l)
+            if e is None:
+                out["rect_%d" % l] = np.zeros(4, np.int64)
+                out["cells_%d" % l] = np.zeros((0, 0), capi.CELL_DTYPE)
+                continue
+            x0, y0, w, h = e[2], e[3], e[0] - e[2] + 1, e[1] - e[3] + 1
+            rows = max(1, self._BAND_CELLS // w)
+            if w > self._BAND_CELLS:
+                raise ValueError("save_world: level %d is %d cells wide, more than one download holds" % (l, w))
+            out["rect_%d" % l] = np.array([x0, y0, w, h], np.int64)
+            out["cells_%d" % l] = np.concatenate([self.world_cells(l, x0, y0 + r, w, min(rows, h - r)) for r in range(0, h, rows)])
+        with open(path, "wb") as f:                                  # (a file object: np.savez would add ".npz" to a bare name)
+            np.savez_compressed(f, **out)
+
+    def load_world(self, path, _shift=None):
+        """Resume from a world that save_world wrote: the window is shifted to the saved origin, then every level's rectangle is
+        put back with world_put.  A file whose version or geometry (cell length, level-0 size, levels) differs from this
+        pyramid's is refused (ValueError) before anything changes.  If backing is off here and was on when the world was saved,
+        it is switched on with the saved setting once the window has moved, so that what lay outside the window is kept.  -> the cells dropped."""
+        with np.load(path) as z:
+            if int(z["version"]) != self.WORLD_FORMAT:
+                raise ValueError("load_world: format version %d, this library reads %d" % (int(z["version"]), self.WORLD_FORMAT))
+            if (np.float32(z["cell_length"]).view(np.uint32) != np.float32(self.Maps[0].CellLength).view(np.uint32)
+                    or not np.array_equal(z["geometry"], self._geometry())):
+                raise ValueError("load_world: the saved pyramid (cell %r, %s) is not this one (cell %r, %s)"
+                                 % (float(z["cell_length"]), z["geometry"].tolist(), self.Maps[0].CellLength, self._geometry().tolist()))
+            origin = tuple(int(v) for v in z["origin"])
+            backing = tuple(int(v) for v in z["backing"])
+            rects = [tuple(int(v) for v in z["rect_%d" % l]) for l in range(self.NumLevels)]
+            cells = [np.ascontiguousarray(z["cells_%d" % l], capi.CELL_DTYPE) for l in range(self.NumLevels)]
+        g = 1 << (self.NumLevels - 1)
+        step = (1 << 30) // g * g                                    # (slamhip_hs_shift takes 32-bit moves)
+        while self.origin() != origin:
+            ox, oy = self.origin()
+            (_shift or self.shift)(max(-step, min(step, origin[0] - ox)), max(-step, min(step, origin[1] - oy)))
+        if backing[1] > 0 and not self.backing_stats()["on"]:        # (after the move: a fresh pyramid makes no tiles of its empty window)
+            self.set_backing(*backing)
+        dropped = 0
+        for l, ((x0, y0, w, h), c) in enumerate(zip(rects, cells)):
+            if w == 0 or h == 0:
+                continue
+            rows = max(1, self._BAND_CELLS // w)
+            for r in range(0, h, rows):
+                dropped += self.world_put(l, x0, y0 + r, c[r:r + rows])
+        return dropped
+
     def SetUpdateFactorFree(self, factor):
         self._free = float(factor)
         capi.call("slamhip_hs_set_factors", self._h, C.c_float(factor), C.c_float(getattr(self, "_occ", 0.9)))
@@ -318,6 +401,20 @@ class HectorSLAMProcessor:
         ox, oy = C.c_int64(), C.c_int64()
         capi.call("slamhip_hsproc_get_origin", self._h, C.byref(ox), C.byref(oy))
         return int(ox.value), int(oy.value)
+
+    def shift(self, dx, dy):
+        """MapRep.shift from outside an Update (slamhip_hsproc_shift): the window moves, MatchPose and LastMapUpdatePose stay
+        the world poses they were."""
+        capi.call("slamhip_hsproc_shift", self._h, int(dx), int(dy))
+
+    def SaveWorld(self, path):
+        """MapRep.save_world: the processor's world -- window and tiles -- as one .npz."""
+        self.MapRep.save_world(path)
+
+    def LoadWorld(self, path):
+        """MapRep.load_world into the processor's own pyramid, the window moved through the processor so that its poses stay
+        world poses: create the processor with startPose = the saved pose, LoadWorld, Update.  -> the cells dropped."""
+        return self.MapRep.load_world(path, _shift=self.shift)
 
     MatchPose = property(lambda self: self._get()[0])
     LastMapUpdatePose = property(lambda self: self._get()[1])

@@ -6,7 +6,8 @@ off: single match, batches of 256 and 4096, HectorSLAMProcessor.Update, and matc
 object.  --hector-only: the Hector part alone.  --shift-only: the scrolling window (slamhip_hs_shift) alone, beside a plain
 device-to-device copy of the same arrays and beside the host route (download, np.roll, upload); with --backing: the shift with the backing store off, on over fresh ground
 and on over ground to restore, beside a device-to-device copy of the evicted plus restored bytes.  (SLAMHIP_LIB names another build of the library for an A/B on one box; rows that
-need entry points it lacks are left out.)"""
+need entry points it lacks are left out.)  --world-only: loading a saved world back (slamhip_hs_world_cells_upload, slamhip_hs_world_extends) for a full level 0 of 2048 x 2048, the
+window part and the tile part separately, beside a plain hipMemcpy of the same bytes."""
 import ctypes as C, json, math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -165,6 +166,69 @@ def backing_rows(side, levels, cell, tile=64):
         row[name] = r
         rep.close()
     return row
+
+
+def world_rows(side, levels, cell, tile=64):
+    """slamhip_hs_world_cells_upload and slamhip_hs_world_extends for one full level 0 (side^2 cells, 8 B each): wall time of the
+    blocking calls, median of 5 after a first call that allocates -- the rectangle that is exactly the window (backing off), and
+    the same rectangle a window's width away (backing on: tiles only; the first call, which takes the slots, is reported apart).
+    The yardstick is not the code under test: a blocking hipMemcpy host-to-device of the same array into a device buffer (what
+    the staging alone costs), and a device-to-device hipMemcpy of the same bytes (what reading them once costs), timed the same
+    way in the same run."""
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipFree.argtypes = [C.c_void_p]
+    hip.hipDeviceSynchronize.argtypes = []
+
+    def ok(rc):
+        if rc != 0: raise RuntimeError("HIP error %d" % rc)
+
+    def wall(fn, n=5):
+        fn(); ctx.synchronize()
+        ts = []
+        for _ in range(n):
+            t0 = time.perf_counter(); fn(); ts.append(time.perf_counter() - t0)
+        return sorted(ts)[n // 2] * 1e6
+
+    rng = np.random.default_rng(5)
+    cells = np.zeros((side, side), capi.CELL_DTYPE)
+    cells["value"] = rng.standard_normal((side, side)).astype(np.float32)
+    cells["update_index"] = rng.integers(0, 40, (side, side))
+    cells["value"][rng.random((side, side)) < 0.5] = 0.0                   # (half of the world never seen)
+    cells["update_index"][cells["value"] == 0] = -1
+    nbytes = cells.nbytes
+    row = {"cells": side * side, "bytes": nbytes, "tile": tile}
+    rep = hs.MapRepMultiMap(cell, (side, side), levels, ctx=ctx)
+    row["window_upload_us"] = wall(lambda: rep.world_put(0, 0, 0, cells))
+    row["window_extends_us"] = wall(lambda: rep.world_extends(0))
+    row["window_cells_upload_us"] = wall(lambda: rep.Maps[0].SetCells(cells.ravel()))        # (slamhip_hs_cells_upload: the window-only call)
+    rep.set_backing(tile, 3 << 30)
+    t0 = time.perf_counter(); dropped = rep.world_put(0, 2 * side, 0, cells); row["tiles_first_upload_us"] = (time.perf_counter() - t0) * 1e6
+    row["tiles_upload_us"] = wall(lambda: rep.world_put(0, 2 * side, 0, cells))
+    row["window_and_tiles_extends_us"] = wall(lambda: rep.world_extends(0))
+    st = rep.backing_stats()
+    row["tiles"] = st["tiles"]; row["pool_bytes"] = st["bytes"]; row["dropped_cells"] = dropped
+    assert rep.world_extends(0) is not None
+    d, d2 = C.c_void_p(), C.c_void_p()
+    ok(hip.hipMalloc(C.byref(d), nbytes)); ok(hip.hipMalloc(C.byref(d2), nbytes))
+    src = cells.ctypes.data_as(C.c_void_p)
+    row["memcpy_h2d_same_bytes_us"] = wall(lambda: ok(hip.hipMemcpy(d, src, nbytes, 1)))     # hipMemcpyHostToDevice, pageable as the caller's array is
+
+    def d2d():
+        ok(hip.hipMemcpy(d2, d, nbytes, 3)); ok(hip.hipDeviceSynchronize())
+    row["memcpy_d2d_same_bytes_us"] = wall(d2d)
+    hip.hipFree(d); hip.hipFree(d2)
+    row["window_upload_over_h2d"] = row["window_upload_us"] / row["memcpy_h2d_same_bytes_us"]
+    row["tiles_upload_over_h2d"] = row["tiles_upload_us"] / row["memcpy_h2d_same_bytes_us"]
+    rep.close()
+    return row
+
+
+if "--world-only" in sys.argv:
+    print(json.dumps({"hs_world_3lvl_2048": world_rows(2048, 3, 40.0 / 2048)}, indent=1))
+    ctx.close()
+    sys.exit(0)
 
 
 def shift_section():
