@@ -12,7 +12,8 @@
 // and right of it -- so a tile in the region's corner gives more than one job.  World coordinates use the unclamped dx >> l: a
 // move by a level's size or more makes the whole old window depart and the whole new one arrive.
 // Order: level 0 first; within a level evict jobs, then restore jobs; within each, row-major by tile (ty, tx); jobs of one tile
-// in the order band above, band below, left strip, right strip.
+// in the order band above, band below, left strip, right strip.  Stated here only, produced by bp_cut_tiles only
+// (the shift's regions below, the world upload's rectangle in world_plan.h).
 #pragma once
 #include <stdint.h>
 #include <algorithm>
@@ -25,46 +26,63 @@ static inline int64_t bp_floor_div(int64_t a, int64_t b)                  // b >
     return (a % b != 0 && a < 0) ? q - 1 : q;
 }
 
-struct bp_rect { int x0, y0, x1, y1; };                                   // [x0, x1) x [y0, y1), window coordinates
+struct bp_rect { int x0, y0, x1, y1; };                                   // [x0, x1) x [y0, y1), frame coordinates
 
-// The jobs of one region of one level: the window w x h, whose cell (0, 0) is world cell (OX, OY), minus the kept rectangle
-// [kx0, kx1) x [ky0, ky1) (empty: the whole window).
-static inline void bp_region_jobs(int level, int kind, int w, int h, int64_t OX, int64_t OY, int kx0, int kx1, int ky0, int ky1,
-                                  int T, std::vector<slamhip_backing_job> &out)
+// A frame of w x h cells minus the kept rectangle [kx0, kx1) x [ky0, ky1) (empty: the whole frame), in the order above.  -> how many
+static inline int bp_frame_rects(int w, int h, int kx0, int kx1, int ky0, int ky1, bp_rect out[4])
+{
+    int nr = 0;
+    if (kx0 >= kx1 || ky0 >= ky1) out[nr++] = { 0, 0, w, h };
+    else {
+        if (ky0 > 0) out[nr++] = { 0, 0, w, ky0 };
+        if (ky1 < h) out[nr++] = { 0, ky1, w, h };
+        if (kx0 > 0) out[nr++] = { 0, ky0, kx0, ky1 };
+        if (kx1 < w) out[nr++] = { kx1, ky0, w, ky1 };
+    }
+    return nr;
+}
+
+// nx x ny cells from frame cell (x0, y0), which is cell (lx, ly) of tile (tx, ty)
+struct bp_piece { int x0, y0, nx, ny, lx, ly; int64_t tx, ty; };
+
+// THE tile cutter: the frame w x h, whose cell (0, 0) is world cell (X0, Y0), minus the kept rectangle, cut by tiles of T cells;
+// emit(const bp_piece &) for every piece, row-major by tile, one tile's pieces in rectangle order.
+template <typename F>
+static inline void bp_cut_tiles(int w, int h, int64_t X0, int64_t Y0, int kx0, int kx1, int ky0, int ky1, int T, F &&emit)
 {
     bp_rect rects[4];
-    int nr = 0;
-    if (kx0 >= kx1 || ky0 >= ky1) rects[nr++] = { 0, 0, w, h };
-    else {
-        if (ky0 > 0) rects[nr++] = { 0, 0, w, ky0 };
-        if (ky1 < h) rects[nr++] = { 0, ky1, w, h };
-        if (kx0 > 0) rects[nr++] = { 0, ky0, kx0, ky1 };
-        if (kx1 < w) rects[nr++] = { kx1, ky0, w, ky1 };
-    }
-    std::vector<slamhip_backing_job> row;
-    const int64_t ty_first = bp_floor_div(OY, T), ty_last = bp_floor_div(OY + h - 1, T);
+    const int nr = bp_frame_rects(w, h, kx0, kx1, ky0, ky1, rects);
+    std::vector<bp_piece> row;
+    const int64_t ty_first = bp_floor_div(Y0, T), ty_last = bp_floor_div(Y0 + h - 1, T);
     for (int64_t ty = ty_first; ty <= ty_last; ty++) {
-        const int64_t ty0 = ty * T - OY;                                  // the tile's first row in window coordinates
+        const int64_t ty0 = ty * T - Y0;                                  // the tile's first row in frame coordinates
         row.clear();
         for (int r = 0; r < nr; r++) {
             const bp_rect &R = rects[r];
             const int y0 = (int)std::max<int64_t>(R.y0, ty0), y1 = (int)std::min<int64_t>(R.y1, ty0 + T);
             if (y0 >= y1) continue;
-            const int64_t tx_first = bp_floor_div(OX + R.x0, T), tx_last = bp_floor_div(OX + R.x1 - 1, T);
+            const int64_t tx_first = bp_floor_div(X0 + R.x0, T), tx_last = bp_floor_div(X0 + R.x1 - 1, T);
             for (int64_t tx = tx_first; tx <= tx_last; tx++) {
-                const int64_t tx0 = tx * T - OX;
+                const int64_t tx0 = tx * T - X0;
                 const int x0 = (int)std::max<int64_t>(R.x0, tx0), x1 = (int)std::min<int64_t>(R.x1, tx0 + T);
-                slamhip_backing_job j;
-                j.level = level; j.kind = kind;
-                j.wx = x0; j.wy = y0; j.nx = x1 - x0; j.ny = y1 - y0;
-                j.tx = tx; j.ty = ty;
-                j.lx = (int32_t)(x0 - tx0); j.ly = (int32_t)(y0 - ty0);
-                row.push_back(j);
+                row.push_back({ x0, y0, x1 - x0, y1 - y0, (int)(x0 - tx0), (int)(y0 - ty0), tx, ty });
             }
         }
-        std::stable_sort(row.begin(), row.end(), [](const slamhip_backing_job &a, const slamhip_backing_job &b) { return a.tx < b.tx; });
-        out.insert(out.end(), row.begin(), row.end());
+        std::stable_sort(row.begin(), row.end(), [](const bp_piece &a, const bp_piece &b) { return a.tx < b.tx; });
+        for (const bp_piece &p : row) emit(p);
     }
+}
+
+// The jobs of one region of one level: the window w x h, whose cell (0, 0) is world cell (OX, OY), minus the kept rectangle.
+static inline void bp_region_jobs(int level, int kind, int w, int h, int64_t OX, int64_t OY, int kx0, int kx1, int ky0, int ky1,
+                                  int T, std::vector<slamhip_backing_job> &out)
+{
+    bp_cut_tiles(w, h, OX, OY, kx0, kx1, ky0, ky1, T, [&](const bp_piece &p) {
+        slamhip_backing_job j;
+        j.level = level; j.kind = kind; j.wx = p.x0; j.wy = p.y0; j.nx = p.nx; j.ny = p.ny;
+        j.tx = p.tx; j.ty = p.ty; j.lx = p.lx; j.ly = p.ly;
+        out.push_back(j);
+    });
 }
 
 // The job list of one shift by (dx, dy) level-0 cells of a pyramid whose level 0 is w0 x h0 (every further level half of it,

@@ -1,6 +1,7 @@
 // hector.hip -- the HectorSLAM operator object (slamhip_hs): create / destroy / reset, the scan, uploads, downloads and the small
 // kernels over a level's cells.  K4 (scan matcher): hs_match.hip; K5 (grid update): hs_update.hip; K6 (scrolling window and its
-// backing store): hs_window.hip; HectorSLAMProcessor: hs_processor.hip; shared state and helpers: hs_internal.h.
+// backing store): hs_window.hip, the world behind them: hs_world.hip; HectorSLAMProcessor: hs_processor.hip; shared state and
+// helpers: hs_internal.h.
 #include "hs_internal.h"
 
 __global__ void k5_fill_cells(slamhip_cell *cells, float *prob, size_t n)

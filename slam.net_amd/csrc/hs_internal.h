@@ -37,8 +37,8 @@ struct hs_level_dev {                      // what the kernels need, by value
 #define HS_PROB_MODE 0                     // 0: the probability grid, kept by every writer of the cells | 1: from the cells, exact expf and division per tap | 2: ... hardware exp and reciprocal
 #endif
 
-struct hs_backing;                         // hs_window.hip
-struct hs_world;                           // hs_window.hip
+struct hs_backing;                         // hs_tiles.h
+struct hs_world;                           // hs_world.hip
 struct slamhip_hs {
     slamhip_ctx *ctx;
     int n_levels;
@@ -126,4 +126,5 @@ bool    hs_update_gateable(slamhip_hs *hs);
 // hs_window.hip
 void    hs_bk_reset(slamhip_hs *hs);        // slamhip_hs_reset with backing on: the directory goes, the pool stays -- every slot Reset again
 void    hs_bk_free(slamhip_hs *hs);         // (the caller has drained the stream)
+// hs_world.hip
 void    hs_wp_free(slamhip_hs *hs);         // the staging buffer of the world upload and the world extents (the caller has drained the stream)

@@ -267,6 +267,41 @@ def test_capacity(hs_mod, ctx, det, sim, dims):
     S.close_all(rep, ref)
 
 
+# ---- 4b. jobs of more than one piece ----------------------------------------------------------------------------------------------
+BIG_DIMS, BIG_TILE, BIG_SHIFT = (128, 128), 64, (-68, 72)
+
+
+@gpu
+@pytest.mark.parametrize("origin", [(0, 0), (-52, -36)], ids=["o0", "oneg"])
+def test_jobs_of_two_pieces(hs_mod, ctx, det, sim, checksum_np, origin):
+    """Tiles of 64 cells under a window of 128: evict and restore jobs of 64 x 64 and 64 x 56 cells (origin (0, 0)) or 64 x 36
+    (origin (-52, -36), from row 28 of their tiles) -- more than the 2048 cells of a piece, so k6_page gets each as two
+    workgroups' pieces, the second from row `rows` of the job and of the tile.  Out and back, cells and probabilities bit for bit."""
+    capi = hs_mod.capi
+    jobs = capi.backing_plan(LEVELS, *BIG_DIMS, *origin, *BIG_SHIFT, BIG_TILE)
+    big = jobs[jobs["nx"].astype(np.int64) * jobs["ny"] > 2048]
+    assert set(big["kind"].tolist()) == {capi.BACKING_EVICT, capi.BACKING_RESTORE}
+    if origin == (0, 0):
+        assert len(jobs) == 24 and {(64, 64), (64, 56)} <= set(zip(big["nx"].tolist(), big["ny"].tolist()))
+    else:
+        assert (big["ly"] > 0).any()                                       # a second piece at ly + r0 with ly > 0
+    rep, ref = build_at(hs_mod, ctx, det, sim, BIG_DIMS, origin, backing=(BIG_TILE, ENOUGH))
+    canvas = Canvas(ref, 4 * BIG_DIMS[0])
+    tables = S.checked_tables(rep, ref)
+    at = origin
+    for dx, dy in (BIG_SHIFT, (-BIG_SHIFT[0], -BIG_SHIFT[1])):
+        rep.shift(dx, dy)
+        tables = canvas.shift(ref, tables, at, dx, dy)
+        at = (at[0] + dx, at[1] + dy)
+        assert rep.origin() == at
+        S.assert_maps_equal(rep, ref, checksum_np, (dx, dy))
+        S.assert_prob_equal(rep, ref, tables, (dx, dy))
+    assert at == origin and np.count_nonzero(ref[0].cells["value"]) > (BIG_DIMS[0] * BIG_DIMS[1]) // 8   # home, with the map
+    st = rep.backing_stats()
+    assert st["dropped_cells"] == 0 and st["restored_cells"] > 0 and st["tile"] == BIG_TILE
+    S.close_all(rep, ref)
+
+
 # ---- 5. off is today -------------------------------------------------------------------------------------------------------------
 ZERO_STATS = dict(tiles=0, bytes=0, capacity_bytes=0, evicted_cells=0, restored_cells=0, dropped_cells=0, tile=0, on=0)
 

@@ -48,13 +48,14 @@ def not_reset(c):
 class World:
     """One level's world cells around the origin: world cell (X, Y) lies at [Y + half, X + half]."""
 
-    def __init__(self, dtype, half):
+    def __init__(self, dtype, half, half_y=None):
         self.half = half
-        self.cells = reset_cells((2 * half, 2 * half), dtype)
+        self.half_y = half if half_y is None else half_y                   # (a wide, low world: fewer rows than columns)
+        self.cells = reset_cells((2 * self.half_y, 2 * half), dtype)
 
     def sl(self, x0, y0, w, h):
-        x, y = x0 + self.half, y0 + self.half
-        assert 0 <= x and x + w <= 2 * self.half and 0 <= y and y + h <= 2 * self.half, (x0, y0, w, h)
+        x, y = x0 + self.half, y0 + self.half_y
+        assert 0 <= x and x + w <= 2 * self.half and 0 <= y and y + h <= 2 * self.half_y, (x0, y0, w, h)
         return (slice(y, y + h), slice(x, x + w))
 
     def put(self, x0, y0, cells):
@@ -172,6 +173,38 @@ def test_put_then_download(hs_mod, ctx, dims, origin):
         after = rep.Maps[l].GetCells()
         ch = S.raw(after) != S.raw(before[l])
         assert ch.any() and set(np.unique(after["update_index"][ch]).tolist()) <= {43, 44}, (l, np.unique(after["update_index"][ch]))
+    rep.close()
+    ref_rep.close()
+
+
+@gpu
+def test_put_wider_than_a_piece(hs_mod, ctx):
+    """One level of 2304 x 8 cells, a put of 2310 x 12 over it: the window job is 2304 cells wide, more than the 2048 of a piece,
+    so k6_world_put -- and k6_world_extends over the window -- get it one row per workgroup; 582 tile jobs behind it."""
+    capi = hs_mod.capi
+    dims, (x0, y0, rw, rh) = (2304, 8), (-3, -2, 2310, 12)
+    jobs = capi.world_plan(*dims, 0, 0, x0, y0, rw, rh, TILE)
+    assert len(jobs) == 583 and jobs[0]["kind"] == capi.WORLD_WINDOW and (jobs[0]["nx"], jobs[0]["ny"]) == dims
+    rng = np.random.default_rng(2304)
+    rep = hs_mod.MapRepMultiMap(CELL, dims, 1, ctx=ctx)
+    ref_rep = hs_mod.MapRepMultiMap(CELL, dims, 1, ctx=ctx)
+    rep.set_backing(TILE, ENOUGH)
+    world = World(capi.CELL_DTYPE, 1200 + dims[0] // 2, 32)                # world cells [-2352, 2352) x [-32, 32)
+    cells = random_cells(rng, rh, rw, capi.CELL_DTYPE)
+    assert rep.world_put(0, x0, y0, cells) == 0
+    world.put(x0, y0, cells)
+    tiles = set()
+    tiles_of_put(tiles, 0, dims, (0, 0), x0, y0, cells)
+    st = rep.backing_stats()
+    assert len(tiles) > 500 and st["tiles"] == len(tiles) and st["bytes"] == pool_bytes(len(tiles), ENOUGH) and st["dropped_cells"] == 0
+    got = rep.world_cells(0, -world.half, -world.half_y, 2 * world.half, 2 * world.half_y)       # a surrounding rectangle
+    assert np.array_equal(S.raw(got), S.raw(world.cells))
+    want = world.get(0, 0, *dims)
+    assert np.array_equal(S.raw(rep.Maps[0].GetCells().reshape(dims[1], dims[0])), S.raw(want))
+    assert S.same_bits(S.device_prob(rep, 0), reference_prob(ref_rep, 0, want))
+    e = rep.world_extends(0)
+    assert e is not None and e == bbox(world.cells, -world.half, -world.half_y)
+    assert e[2] < 0 and e[0] >= dims[0] and e[3] < 0 and e[1] >= dims[1]   # (window and tiles both count)
     rep.close()
     ref_rep.close()
 

@@ -3,6 +3,7 @@ slamhip_hs_world_cells_download, slamhip_debug_backing_plan): exported, declared
 the C# shim; and the planner -- pure host code -- against a brute-force NumPy model that paints every cell of the old and the new
 window with its world coordinate and groups the cells by np.floor_divide.  No compute calls."""
 import ctypes as C
+import hashlib
 import inspect
 import os
 import re
@@ -169,3 +170,21 @@ def test_planner_cap_too_small(capi):
     assert L.slamhip_debug_backing_plan(LEVELS, 70, 46, -52, -36, -2 * G, 3 * G, 8, ptr, need, C.byref(n)) == capi.OK
     assert n.value == need and np.array_equal(buf, jobs)
     assert len(capi.backing_plan(LEVELS, 64, 64, 0, 0, 0, 0, 16)) == 0     # no move, no jobs
+
+
+# ---- the plans, byte for byte ----------------------------------------------------------------------------------------------------
+# The brute-force test pins coverage and order; this pins the bytes -- the byte order deals the slots and so decides what a full
+# pool drops.  SHA-256 over the raw job arrays (jobs.tobytes()) of plan_cases() and then DIGEST_EXTRA, concatenated in that order,
+# as the library of commit 920e200 (the last one with a tile cutter of its own in backing_plan.h) produced them.
+DIGEST_EXTRA = [(128, 128, 64, (0, 0), (-68, 72)), (128, 128, 64, (-52, -36), (-68, 72))]   # test_gpu_hector_backing.py's two-piece jobs
+PLAN_SHA256 = "7687dc55f29f1489d72c0048840d56b35a7573fac9c043ebb0bef3d4ad51263a"
+
+
+def test_plans_are_byte_identical(capi):
+    h = hashlib.sha256()
+    for w0, h0, T, (ox, oy), (dx, dy) in plan_cases() + DIGEST_EXTRA:
+        h.update(capi.backing_plan(LEVELS, w0, h0, ox, oy, dx, dy, T).tobytes())
+    first = capi.backing_plan(LEVELS, *DIGEST_EXTRA[0][:2], *DIGEST_EXTRA[0][3], *DIGEST_EXTRA[0][4], DIGEST_EXTRA[0][2])
+    areas = sorted((first["nx"] * first["ny"]).tolist())
+    assert len(first) == 24 and areas[-1] == 4096 and 3584 in areas        # (jobs of more than 2048 cells: two pieces each)
+    assert h.hexdigest() == PLAN_SHA256

@@ -3,6 +3,7 @@ slamhip_debug_world_plan): exported, declared, stated in the header, mirrored in
 host code -- against a brute-force NumPy model that paints every cell of the rectangle with its world coordinate, classifies it as
 inside or outside the window and groups the outside cells by np.floor_divide.  No compute calls."""
 import ctypes as C
+import hashlib
 import inspect
 import os
 import re
@@ -208,3 +209,20 @@ def test_planner_cap_too_small(capi):
     for j in t:
         per_tile.setdefault((int(j["ty"]), int(j["tx"])), []).append(j)
     assert max(len(v) for v in per_tile.values()) >= 2
+
+
+# ---- the plans, byte for byte ----------------------------------------------------------------------------------------------------
+# The brute-force test pins coverage and order; this pins the bytes -- the byte order deals the slots and so decides what a full
+# pool drops.  SHA-256 over the raw job arrays (jobs.tobytes()) of plan_cases() and then DIGEST_EXTRA, concatenated in that order,
+# as the library of commit 920e200 (the last one with a tile cutter of its own in world_plan.h) produced them.
+DIGEST_EXTRA = [(2304, 8, 0, 0, "wide", -3, -2, 2310, 12, 8), (2304, 8, 0, 0, "wide", -3, -2, 2310, 12, 0)]   # test_gpu_hector_world.py's wide put
+PLAN_SHA256 = "785823b00c208b54205141d70fd0f786f183453687113fa4410429c389c833e2"
+
+
+def test_plans_are_byte_identical(capi):
+    h = hashlib.sha256()
+    for w, hh, OX, OY, _, x0, y0, rw, rh, T in plan_cases() + DIGEST_EXTRA:
+        h.update(capi.world_plan(w, hh, OX, OY, x0, y0, rw, rh, T).tobytes())
+    wide = capi.world_plan(2304, 8, 0, 0, -3, -2, 2310, 12, 8)
+    assert len(wide) == 583 and wide[0]["kind"] == capi.WORLD_WINDOW and wide[0]["nx"] == 2304   # (wider than one piece of 2048 cells)
+    assert h.hexdigest() == PLAN_SHA256
