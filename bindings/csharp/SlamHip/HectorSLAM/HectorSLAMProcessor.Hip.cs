@@ -166,6 +166,22 @@ namespace HectorSLAM.Main
             return dropped;
         }
 
+        /// <summary>Find the robot in the map the window holds (slamhip_hsproc_relocalise; the reference can only Reset): the scan is
+        /// scored against level lattice.Level at every node of the lattice around lattice's centre, a WORLD pose, and the best nodes
+        /// of the maxHints highest-scoring headings are refined by the matcher; the winner is returned with its match report.
+        /// adopt: the pose becomes MatchPose and LastMapUpdatePose -- the next Update matches from it and redraws the map only once
+        /// the robot has moved by the thresholds.  The resume flow: LoadWorld, Relocalise, Update.  The library sets no acceptance
+        /// threshold: whether report.Residual is good enough is the caller's decision.</summary>
+        public unsafe Vector3 Relocalise(ScanCloud scan, LatticeSpec lattice, int maxHints, bool adopt, out SlamHip.MatchReport report, out RelocInfo info)
+        {
+            Vector3 pose;
+            fixed (Vector2* p = CollectionsMarshal.AsSpan(scan.Points))
+                Native.Check(Native.slamhip_hsproc_relocalise(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), lattice, maxHints, adopt ? 1 : 0,
+                                                              out pose, out report, out info));
+            Refresh();
+            return pose;
+        }
+
         private void Refresh()
         {
             Native.Check(Native.slamhip_hsproc_get(proc.Ptr, out Vector3 match, out Vector3 last, out float tm, out float tu));

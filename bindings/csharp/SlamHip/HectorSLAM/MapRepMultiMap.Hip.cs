@@ -103,6 +103,39 @@ namespace HectorSLAM.Main
             MarkStale();
         }
 
+        /// <summary>The pose-lattice search (slamhip_hs_lattice_search; the reference has no counterpart): the scan scored against the
+        /// occupancy grid of level lattice.Level at every node of the lattice, whose centre is a pose in the window's frame.  Returns
+        /// one key per heading -- ((uint)score ^ 0x80000000) &lt;&lt; 32 | (0xFFFFFFFF - flat): the best node of that heading -- and, when
+        /// asked for, the whole score volume [k][iy][ix].  Blocking, behind everything already enqueued.</summary>
+        public unsafe ulong[] LatticeSearch(ScanCloud scan, LatticeSpec lattice, bool wantScores, out int[] scores)
+        {
+            SetScan(scan);
+            var keys = new ulong[Math.Max(0, lattice.NTheta)];
+            scores = wantScores ? new int[(long)Math.Max(0, lattice.NTheta) * (2 * lattice.Ny + 1) * (2 * lattice.Nx + 1)] : null;
+            fixed (ulong* k = keys)
+            fixed (int* s = scores)
+                Native.Check(Native.slamhip_hs_lattice_search(Pyramid.Ptr, lattice, k, s));
+            return keys;
+        }
+
+        /// <summary>The pose of node (k, flat) of that lattice in the window's frame (slamhip_hs_lattice_node_pose).</summary>
+        public Vector3 LatticeNodePose(LatticeSpec lattice, int k, int flat)
+        {
+            Native.Check(Native.slamhip_hs_lattice_node_pose(Pyramid.Ptr, lattice, k, flat, out Vector3 pose));
+            return pose;
+        }
+
+        /// <summary>The search's point cells for one heading, on the host (slamhip_debug_lattice_cells): (gx, gy) per point,
+        /// int.MinValue twice for a point the search ignores.</summary>
+        public static unsafe int[] LatticeCells(float cellLength, Vector3 centre, float theta, Vector2[] points)
+        {
+            var cells = new int[2 * points.Length];
+            fixed (Vector2* p = points)
+            fixed (int* c = cells)
+                Native.Check(Native.slamhip_debug_lattice_cells(cellLength, centre, theta, p, points.Length, c));
+            return cells;
+        }
+
         /// <summary>The sum of all shifts since construction or the last Reset, in level-0 cells (slamhip_hs_origin).</summary>
         public (long X, long Y) Origin
         {

@@ -111,6 +111,16 @@ namespace HectorSLAM.Matcher
             return pose;
         }
 
+        /// <summary>Lattice search, then the best nodes of the maxHints highest-scoring headings refined by MatchDataBest
+        /// (slamhip_hs_relocalise): the winner with its report and where it started from.  Poses in the window's frame.</summary>
+        public unsafe Vector3 Relocalise(MapRepMultiMap multiMap, ScanCloud scan, LatticeSpec lattice, int maxHints, out MatchReport report, out RelocInfo info)
+        {
+            Native.Check(Native.slamhip_hs_set_match_threads(multiMap.Pyramid.Ptr, matchThreads));
+            multiMap.SetScan(scan);
+            Native.Check(Native.slamhip_hs_relocalise(multiMap.Pyramid.Ptr, lattice, maxHints, out Vector3 pose, out report, out info));
+            return pose;
+        }
+
         /// <summary>The hint list of a relocalisation around centre = (x, y, theta): every combination of x, y in centre +- k * stepXy
         /// (k * stepXy &lt;= halfXy) and theta in centre +- j * stepTheta (j * stepTheta &lt;= halfTheta).  The centre itself comes first
         /// (ties in MatchDataBest go to the lowest index); the rest follow in x-major, then y, then theta order.  Pure host code.</summary>

@@ -62,6 +62,30 @@ namespace SlamHip
         public int Tile, On;
     }
 
+    /// <summary>slamhip_lattice_spec (include/slamhip.h): the pose lattice of the relocalisation search -- translations by whole cells
+    /// of pyramid level Level, ix in [-Nx, Nx], iy in [-Ny, Ny], around (CentreX, CentreY), headings CentreTheta + k * DTheta,
+    /// k = 0 .. NTheta - 1.  The centre is a pose in the window's frame (a world pose for HectorSLAMProcessor.Relocalise).
+    /// 8 four-byte fields, 32 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct LatticeSpec
+    {
+        public int Level;
+        public int Nx, Ny;
+        public int NTheta;
+        public float CentreX, CentreY, CentreTheta;
+        public float DTheta;
+    }
+
+    /// <summary>slamhip_reloc_info (include/slamhip.h): the hints a relocalisation handed to the matcher and the lattice node the
+    /// winner started from.  7 ints, 28 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct RelocInfo
+    {
+        public int HintCount, BestHint;
+        public int K, Ix, Iy;
+        public int Score, TopScore;
+    }
+
     internal static unsafe class Native
     {
         const string Lib = "slamhip";                                   // libslamhip.so on the library path
@@ -143,6 +167,11 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_match_level_report(IntPtr hs, int level, in Vector3 hint, int iterations, out Vector3 pose, out MatchReport report);
         [DllImport(Lib)] internal static extern int slamhip_hs_match_batch_report(IntPtr hs, Vector3* hints, int count, Vector3* poses, MatchReport* reports);
         [DllImport(Lib)] internal static extern int slamhip_hs_match_best(IntPtr hs, Vector3* hints, int count, out Vector3 pose, out int index, out MatchReport report);
+        // relocalisation in a loaded map (no reference counterpart): the pose-lattice search, its node poses, and search + best-of-batch match
+        [DllImport(Lib)] internal static extern int slamhip_hs_lattice_search(IntPtr hs, in LatticeSpec spec, ulong* keys, int* scores);
+        [DllImport(Lib)] internal static extern int slamhip_hs_lattice_node_pose(IntPtr hs, in LatticeSpec spec, int k, int flat, out Vector3 pose);
+        [DllImport(Lib)] internal static extern int slamhip_hs_relocalise(IntPtr hs, in LatticeSpec spec, int maxHints, out Vector3 pose, out MatchReport report, out RelocInfo info);
+        [DllImport(Lib)] internal static extern int slamhip_debug_lattice_cells(float cellLength, in Vector3 centre, float theta, Vector2* xy, int n, int* gxgy);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_match_threads(IntPtr hs, int numThreads);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_reference_cache(IntPtr hs, int on);
         [DllImport(Lib)] internal static extern int slamhip_hs_update_by_scan(IntPtr hs, in Vector3 robotPoseWorld);
@@ -169,6 +198,8 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_set_scroll(IntPtr proc, int triggerCells);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_get_origin(IntPtr proc, out long ox, out long oy);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_shift(IntPtr proc, int dx, int dy);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_relocalise(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in LatticeSpec specWorld, int maxHints, int adopt,
+                                                                              out Vector3 poseWorld, out MatchReport report, out RelocInfo info);
 
         // ---- one process, several GPUs -------------------------------------------------------------------------------
         [DllImport(Lib)] internal static extern int slamhip_group_create(int* deviceOrdinals, int n, float physicalMapSize, int holeMapSize, int obstacleMapSize, out IntPtr group);

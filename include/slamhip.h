@@ -136,6 +136,14 @@ int32_t slamhip_debug_backing_plan(int32_t levels, int32_t w0, int32_t h0, int64
 int32_t slamhip_debug_world_plan(int32_t w, int32_t h, int64_t OX, int64_t OY, int64_t x0, int64_t y0, int32_t rw, int32_t rh,
                                  int32_t tile, slamhip_world_job *jobs, int32_t cap, int32_t *n_jobs);
 
+/* Test hook (no device involved): the point-cell arithmetic of the pose-lattice search (slamhip_hs_lattice_search) for ONE heading
+ * on a level of cell length `cell_length` (stm = 1.0f / cell_length, as slamhip_hs_create forms it): theta is the heading theta_k
+ * itself -- (s, c) = the deterministic sine / cosine of theta -- and centre[0], centre[1] the lattice's centre in metres
+ * (centre[2] is not read).  out_gxgy[2 i], out_gxgy[2 i + 1] = (gx, gy) of point i as the search's kernel forms them, or
+ * INT32_MIN twice for a point the search ignores.  n >= 0; xy and out_gxgy may be NULL when n is 0. */
+int32_t slamhip_debug_lattice_cells(float cell_length, const float centre[3], float theta, const float *xy, int32_t n,
+                                    int32_t *out_gxgy);
+
 /* Kernel timing (the reference only has Stopwatch EMAs, HectorSLAMProcessor.cs:92-96,111-115).
  * When enabled, each kernel class is bracketed by HIP events on the context's stream. */
 enum {
@@ -146,7 +154,9 @@ enum {
     SLAMHIP_K_CS_OBSTACLE = 4,  /* K3 */
     SLAMHIP_K_HS_MATCH = 5,     /* K4 */
     SLAMHIP_K_HS_UPDATE = 6,    /* K5 */
-    SLAMHIP_K_COUNT = 7
+    SLAMHIP_K_HS_LATTICE_PACK = 7, /* K7 class-map pack */
+    SLAMHIP_K_HS_LATTICE = 8,   /* K7 pose-lattice search */
+    SLAMHIP_K_COUNT = 9
 };
 /* mask: bit k enables kernel class k (e.g. 1 << SLAMHIP_K_CS_DISTANCE); 0 = off; -1 = all classes */
 int32_t slamhip_ctx_timing_enable(slamhip_ctx *ctx, int32_t mask);
@@ -590,6 +600,63 @@ int32_t slamhip_hs_match_batch_report(slamhip_hs *hs, const float *hint_poses, i
 int32_t slamhip_hs_match_best(slamhip_hs *hs, const float *hint_poses, int32_t B, float out_pose[3], int32_t *out_index,
                               slamhip_match_report *out_report);
 
+/* Relocalisation in a loaded map: the pose-lattice (correlative) search -- no reference counterpart (its HectorSLAMProcessor can
+ * only Reset, Main/HectorSLAMProcessor.cs:131-138).  The scan is scored against the occupancy grid of ONE pyramid level at every
+ * node of a lattice of poses: translations by whole cells of that level around `centre`, headings centre[2] + k * dtheta.  The
+ * score is an exact integer correlation, orders of magnitude cheaper per pose than a Gauss-Newton match; only the best few
+ * nodes then go to the matcher (slamhip_hs_relocalise).
+ * THE DEFINITION (every binary32 operation rounded on its own, no fused multiply-add), with L the level, stm = 1 / cell:
+ *   theta_k = centre[2] + (float)k * dtheta; (s, c) = the library's deterministic sine / cosine of theta_k (no normalisation);
+ *   cxm = centre[0] * stm, cym = centre[1] * stm;
+ *   for a scan point (px, py) in metres, as slamhip_hs_set_scan took it (the scan origin plays no part, as in the matcher):
+ *     rx = c * px - s * py, ry = s * px + c * py; fx = rx * stm + cxm, fy = ry * stm + cym; gx = (int)floorf(fx), gy likewise;
+ *   the point is ignored for this heading unless fabsf(fx) < 16777216.0f && fabsf(fy) < 16777216.0f (a NaN point is ignored);
+ *   cls(x, y) = +1 if the cell's Value > 0.0f (LogOddsCell.IsOccupied), -1 if Value < 0.0f, else 0: +0, -0, NaN, or (x, y)
+ *   outside [0, w) x [0, h);
+ *   score(k, iy, ix) = sum over the points of cls(gx + ix, gy + iy), an int32, ix in [-nx, nx], iy in [-ny, ny]: a translation
+ *   moves every point by whole cells -- this IS the definition, not an approximation of evaluating at the node's pose;
+ *   flat = (iy + ny) * (2 nx + 1) + (ix + nx); key[k] = max over the nodes of
+ *   ((uint64)((uint32)score ^ 0x80000000u) << 32) | (0xFFFFFFFFu - flat): the highest score, ties to the lowest flat -- the mirror
+ *   image of slamhip_hs_match_best's minimum key;
+ *   node pose, in the window's frame: ((cxm + (float)ix) * cell, (cym + (float)iy) * cell, theta_k).
+ * The frame is the one slamhip_hs_match uses -- the WINDOW's (the contract under slamhip_hs_shift).  The search covers the window
+ * only: a host that wants another region of the world moves the window there first (slamhip_hs_shift / slamhip_hsproc_shift). */
+typedef struct slamhip_lattice_spec {
+    int32_t level;        /* pyramid level searched */
+    int32_t nx, ny;       /* half-extents in cells of that level: ix in [-nx, nx], iy in [-ny, ny] */
+    int32_t n_theta;      /* headings k = 0 .. n_theta-1 */
+    float   centre[3];    /* pose (m, m, rad) in the window's frame: translations are centred here, heading 0 is centre[2] */
+    float   dtheta;       /* heading step, rad */
+} slamhip_lattice_spec;   /* 8 four-byte fields, sizeof(slamhip_lattice_spec) == 32, no padding */
+/* What slamhip_hs_relocalise did: the hints it handed to the matcher and the node the winner started from. */
+typedef struct slamhip_reloc_info {
+    int32_t n_hints;      /* min(B, n_theta) */
+    int32_t best_hint;    /* slamhip_hs_match_best's index among the hints */
+    int32_t k, ix, iy;    /* the lattice node of that hint */
+    int32_t score;        /* ... and its score */
+    int32_t top_score;    /* the score of hint 0, the highest of the lattice */
+} slamhip_reloc_info;     /* 7 four-byte fields, sizeof(slamhip_reloc_info) == 28, no padding */
+/* The search.  Two launches on the operator's stream, behind every grid update, shift and upload already enqueued: one packs the
+ * level's cell values into a class map of 2 bits per cell (re-packed on every search; the map belongs to the hs, is allocated by
+ * the first search and freed by slamhip_hs_destroy -- an hs that never searches allocates nothing), one scores the lattice and
+ * reduces key[k] per heading.  out_keys: n_theta keys.  out_scores: NULL, or the whole volume,
+ * n_theta * (2 ny + 1) * (2 nx + 1) scores, k-major, then iy, then ix.  Blocking, with the context's bounded wait; the results
+ * come back through pinned staging that the library owns.  It reads cell values only, never probabilities or the reference's
+ * cache, so it works with slamhip_hs_set_reference_cache on, and after shifts.
+ * SLAMHIP_ERR_INVALID, nothing launched: level out of range, nx or ny outside [0, 4096], n_theta outside [1, 4096], more than
+ * 2^26 nodes, a centre or dtheta that is not finite.  SLAMHIP_ERR_STATE: no scan (n_points == 0).  A poisoned context:
+ * SLAMHIP_ERR_TIMEOUT. */
+int32_t slamhip_hs_lattice_search(slamhip_hs *hs, const slamhip_lattice_spec *spec, uint64_t *out_keys, int32_t *out_scores);
+/* The node pose of the definition above for heading k and flat index `flat` (pure host code: no binding restates it).
+ * SLAMHIP_ERR_INVALID: a spec the search refuses, k outside [0, n_theta), flat outside [0, (2 ny + 1) * (2 nx + 1)). */
+int32_t slamhip_hs_lattice_node_pose(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t k, int32_t flat, float out_pose[3]);
+/* Search, then refine: the n_theta keys are sorted descending on the host (equal keys: the lower k first) and the first
+ * n_hints = min(B, n_theta) -- distinct headings, which is what gives the hints their diversity -- become node poses, in that
+ * order, the hints of slamhip_hs_match_best: out_pose and out_report are exactly what that call returns for them.  1 <= B <= 64.
+ * The library sets no acceptance threshold, as with the match report.  Errors as slamhip_hs_lattice_search. */
+int32_t slamhip_hs_relocalise(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t B, float out_pose[3],
+                              slamhip_match_report *out_report, slamhip_reloc_info *out_info);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -739,6 +806,15 @@ int32_t slamhip_hsproc_get_origin(slamhip_hsproc *p, int64_t *ox, int64_t *oy);
  * saved origin), with the processor's MatchPose and LastMapUpdatePose -- kept in the window's frame -- re-based as the scroll
  * re-bases them, so that slamhip_hsproc_get goes on answering in the world frame.  Arguments and errors as slamhip_hs_shift. */
 int32_t slamhip_hsproc_shift(slamhip_hsproc *p, int32_t dx, int32_t dy);
+/* Relocalise the processor (no reference counterpart): slamhip_hs_set_scan on the processor's own hs, then slamhip_hs_relocalise
+ * with spec_world->centre taken to the window's frame as slamhip_hsproc_update takes its hint (- (float)origin * cell0) and the
+ * result brought back as slamhip_hsproc_get does (+ (float)origin * cell0).  adopt = 1: the result becomes both MatchPose and
+ * LastMapUpdatePose -- the next Update matches from the found pose and the map is not written until the robot has moved by the
+ * thresholds (a relocalisation must not immediately draw into the map); adopt = 0: the processor's state is untouched; any other
+ * value SLAMHIP_ERR_INVALID.  No scroll is issued.  The search covers the window (slamhip_hs_lattice_search). */
+int32_t slamhip_hsproc_relocalise(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
+                                  const slamhip_lattice_spec *spec_world, int32_t B, int32_t adopt, float out_pose_world[3],
+                                  slamhip_match_report *out_report, slamhip_reloc_info *out_info);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -15,7 +15,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "slamhip.h")
 
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_STATE, ERR_RCCL, ERR_TIMEOUT = -1, -2, -3, -4, -5, -6
-K_CS_PREP, K_CS_DISTANCE, K_CS_REDUCE, K_CS_HOLEMAP, K_CS_OBSTACLE, K_HS_MATCH, K_HS_UPDATE = range(7)
+K_CS_PREP, K_CS_DISTANCE, K_CS_REDUCE, K_CS_HOLEMAP, K_CS_OBSTACLE, K_HS_MATCH, K_HS_UPDATE, K_HS_LATTICE_PACK, K_HS_LATTICE = range(9)
 
 CELL_DTYPE = np.dtype([("update_index", np.int32), ("value", np.float32)])
 
@@ -77,6 +77,29 @@ WORLD_JOB_DTYPE = np.dtype([("kind", np.int32), ("sx", np.int32), ("sy", np.int3
 assert C.sizeof(WorldJob) == WORLD_JOB_DTYPE.itemsize == 48
 
 
+class LATTICE_SPEC(C.Structure):
+    """slamhip_lattice_spec (include/slamhip.h): the pose lattice of slamhip_hs_lattice_search, 8 four-byte fields, 32 bytes."""
+    _fields_ = [("level", C.c_int32), ("nx", C.c_int32), ("ny", C.c_int32), ("n_theta", C.c_int32), ("centre", C.c_float * 3),
+                ("dtheta", C.c_float)]
+
+
+class RelocInfo(C.Structure):
+    """slamhip_reloc_info (include/slamhip.h): 7 int32, 28 bytes."""
+    _fields_ = [("n_hints", C.c_int32), ("best_hint", C.c_int32), ("k", C.c_int32), ("ix", C.c_int32), ("iy", C.c_int32),
+                ("score", C.c_int32), ("top_score", C.c_int32)]
+
+
+RELOC_INFO = np.dtype([("n_hints", np.int32), ("best_hint", np.int32), ("k", np.int32), ("ix", np.int32), ("iy", np.int32),
+                       ("score", np.int32), ("top_score", np.int32)])
+assert C.sizeof(LATTICE_SPEC) == 32 and C.sizeof(RelocInfo) == RELOC_INFO.itemsize == 28
+
+
+def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
+    """A LATTICE_SPEC from Python values (centre rounded to binary32 as f32 rounds it)."""
+    c = f32(centre, (3,))
+    return LATTICE_SPEC(int(level), int(nx), int(ny), int(n_theta), (C.c_float * 3)(*[float(v) for v in c]), float(np.float32(dtheta)))
+
+
 class SlamhipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("slamhip error %d: %s" % (code, msg))
@@ -112,6 +135,7 @@ def _declare(L):
     fp, ip, u16p, i8p, u8p, u64p, vpp = P(f), P(i32), P(C.c_uint16), P(C.c_int8), P(C.c_uint8), P(u64), P(vp)
     rp = P(MatchReport)
     srp = P(SearchReport)
+    lsp, rip = P(LATTICE_SPEC), P(RelocInfo)
     sig = {
         "slamhip_version": (C.c_char_p, []),
         "slamhip_last_error": (C.c_char_p, []),
@@ -127,6 +151,7 @@ def _declare(L):
         "slamhip_debug_flag_wait": (i32, [P(C.c_uint32), C.c_uint32, i64]),
         "slamhip_debug_backing_plan": (i32, [i32, i32, i32, i64, i64, i32, i32, i32, P(BackingJob), i32, ip]),
         "slamhip_debug_world_plan": (i32, [i32, i32, i64, i64, i64, i64, i32, i32, i32, P(WorldJob), i32, ip]),
+        "slamhip_debug_lattice_cells": (i32, [f, fp, f, fp, i32, ip]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -208,6 +233,9 @@ def _declare(L):
         "slamhip_hs_match_level_report": (i32, [vp, i32, fp, i32, fp, rp]),
         "slamhip_hs_match_batch_report": (i32, [vp, fp, i32, fp, rp]),
         "slamhip_hs_match_best": (i32, [vp, fp, i32, fp, ip, rp]),
+        "slamhip_hs_lattice_search": (i32, [vp, lsp, u64p, ip]),
+        "slamhip_hs_lattice_node_pose": (i32, [vp, lsp, i32, i32, fp]),
+        "slamhip_hs_relocalise": (i32, [vp, lsp, i32, fp, rp, rip]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -230,6 +258,7 @@ def _declare(L):
         "slamhip_hsproc_set_scroll": (i32, [vp, i32]),
         "slamhip_hsproc_get_origin": (i32, [vp, P(i64), P(i64)]),
         "slamhip_hsproc_shift": (i32, [vp, i32, i32]),
+        "slamhip_hsproc_relocalise": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, rip]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -291,6 +320,15 @@ def world_plan(w, h, OX, OY, x0, y0, rw, rh, tile):
     jobs = np.zeros(n.value, WORLD_JOB_DTYPE)
     call("slamhip_debug_world_plan", w, h, OX, OY, x0, y0, rw, rh, tile, jobs.ctypes.data_as(C.POINTER(WorldJob)), n.value, C.byref(n))
     return jobs
+
+
+def lattice_cells(cell_length, centre, theta, xy):
+    """(gx, gy) of every point of `xy` for one heading of the pose-lattice search (slamhip_debug_lattice_cells; no device involved):
+    an (n, 2) int32 array, INT32_MIN twice for a point the search ignores."""
+    xy = f32(xy, (-1, 2)); c = f32(centre, (3,))
+    out = np.empty((xy.shape[0], 2), np.int32)
+    call("slamhip_debug_lattice_cells", C.c_float(cell_length), fptr(c), C.c_float(theta), fptr(xy), xy.shape[0], iptr(out))
+    return out
 
 
 def check(rc):

@@ -1,6 +1,6 @@
 // hector.hip -- the HectorSLAM operator object (slamhip_hs): create / destroy / reset, the scan, uploads, downloads and the small
 // kernels over a level's cells.  K4 (scan matcher): hs_match.hip; K5 (grid update): hs_update.hip; K6 (scrolling window and its
-// backing store): hs_window.hip, the world behind them: hs_world.hip; HectorSLAMProcessor: hs_processor.hip; shared state and
+// backing store): hs_window.hip, the world behind them: hs_world.hip; K7 (pose-lattice search): hs_lattice.hip; HectorSLAMProcessor: hs_processor.hip; shared state and
 // helpers: hs_internal.h.
 #include "hs_internal.h"
 
@@ -115,6 +115,7 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
     }
     hs_bk_free(hs);
     hs_wp_free(hs);
+    hs_lat_free(hs);
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
     if (hs->ev_pts) (void)hipEventDestroy(hs->ev_pts);

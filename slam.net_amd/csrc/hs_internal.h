@@ -39,6 +39,7 @@ struct hs_level_dev {                      // what the kernels need, by value
 
 struct hs_backing;                         // hs_tiles.h
 struct hs_world;                           // hs_world.hip
+struct hs_lattice;                         // hs_lattice.hip
 struct slamhip_hs {
     slamhip_ctx *ctx;
     int n_levels;
@@ -63,6 +64,7 @@ struct slamhip_hs {
     int64_t win_ox, win_oy;                                // slamhip_hs_shift: where cell (0, 0) of level 0 lies in the world, in level-0 cells (host-side books only)
     struct hs_backing *bk;                                 // slamhip_hs_set_backing: the tile pool and its host directory; nullptr while backing is off
     struct hs_world *wp;                                   // slamhip_hs_world_cells_upload / _world_extends: their staging buffer, made by the first call, kept
+    struct hs_lattice *lat;                                // slamhip_hs_lattice_search: the class map and the result blocks, made by the first search, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -128,3 +130,5 @@ void    hs_bk_reset(slamhip_hs *hs);        // slamhip_hs_reset with backing on:
 void    hs_bk_free(slamhip_hs *hs);         // (the caller has drained the stream)
 // hs_world.hip
 void    hs_wp_free(slamhip_hs *hs);         // the staging buffer of the world upload and the world extents (the caller has drained the stream)
+// hs_lattice.hip
+void    hs_lat_free(slamhip_hs *hs);        // the class map and the result blocks of the pose-lattice search (the caller has drained the stream)

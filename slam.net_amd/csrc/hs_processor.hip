@@ -209,6 +209,28 @@ extern "C" int32_t slamhip_hsproc_shift(slamhip_hsproc *p, int32_t dx, int32_t d
     return hsproc_shift_rebase(p, dx, dy);
 }
 
+// Relocalise in the window: the scan set, the lattice's centre taken to the window's frame as slamhip_hsproc_update takes its hint,
+// the result brought back as slamhip_hsproc_get brings the stored poses back.  No scroll, no grid update.
+extern "C" int32_t slamhip_hsproc_relocalise(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const slamhip_lattice_spec *spec_world,
+                                             int32_t B, int32_t adopt, float out_pose_world[3], slamhip_match_report *out_report, slamhip_reloc_info *out_info)
+{
+    SH_CHECK_ARG(p && spec_world && out_pose_world && out_report && out_info && (adopt == 0 || adopt == 1));
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    const bool moved = p->hs->win_ox != 0 || p->hs->win_oy != 0;
+    float off[2];
+    hsproc_window_offset(p, off);
+    slamhip_lattice_spec S = *spec_world;
+    if (moved) { S.centre[0] = S.centre[0] - off[0]; S.centre[1] = S.centre[1] - off[1]; }
+    float m[3];
+    SH_TRY(slamhip_hs_relocalise(p->hs, &S, B, m, out_report, out_info));
+    if (adopt) {
+        memcpy(p->match_pose, m, sizeof(m));
+        memcpy(p->last_update_pose, m, sizeof(m));
+    }
+    out_pose_world[0] = moved ? m[0] + off[0] : m[0]; out_pose_world[1] = moved ? m[1] + off[1] : m[1]; out_pose_world[2] = m[2];
+    return SLAMHIP_OK;
+}
+
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)
 {
     SH_CHECK_ARG(p);

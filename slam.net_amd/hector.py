@@ -30,6 +30,17 @@ def hint_lattice(centre, half_xy, step_xy, half_theta, step_theta):
     return np.asarray(out, np.float64).astype(np.float32)
 
 
+def decode_lattice_key(key):
+    """A key of MapRepMultiMap.lattice_search -> (score, flat): key = ((uint32)score ^ 0x80000000) << 32 | (0xFFFFFFFF - flat)."""
+    key = int(key)
+    score = ((key >> 32) ^ 0x80000000) & 0xFFFFFFFF
+    return (score - (1 << 32) if score >= (1 << 31) else score), 0xFFFFFFFF - (key & 0xFFFFFFFF)
+
+
+def _reloc_info(info):
+    return np.array([tuple(getattr(info, n) for n, _ in capi.RelocInfo._fields_)], capi.RELOC_INFO)[0]
+
+
 class ScanCloud:
     """BaseSLAM/ScanCloud.cs:10-21"""
 
@@ -268,6 +279,28 @@ class MapRepMultiMap:
         self._occ = float(factor)
         capi.call("slamhip_hs_set_factors", self._h, C.c_float(getattr(self, "_free", 0.4)), C.c_float(factor))
 
+    def lattice_search(self, scan, level, centre, nx, ny, n_theta, dtheta, scores=False):
+        """The pose-lattice search (slamhip_hs_lattice_search; no reference counterpart): `scan` scored against the occupancy
+        grid of `level` at every node of the lattice -- translations ix in [-nx, nx], iy in [-ny, ny] cells of that level around
+        `centre` (a pose in the window's frame), headings centre[2] + k * dtheta, k < n_theta.  -> (keys, scores | None): keys
+        (n_theta,) uint64, per heading the best node (decode_lattice_key); scores the (n_theta, 2 ny + 1, 2 nx + 1) int32 volume
+        when asked for.  Blocking, behind everything already enqueued.  scan = None: the scan already set."""
+        if scan is not None:
+            self.set_scan(scan)
+        spec = capi.lattice_spec(level, centre, nx, ny, n_theta, dtheta)
+        keys = np.zeros(int(n_theta), np.uint64)
+        vol = np.zeros((int(n_theta), 2 * int(ny) + 1, 2 * int(nx) + 1), np.int32) if scores else None
+        capi.call("slamhip_hs_lattice_search", self._h, C.byref(spec), keys.ctypes.data_as(C.POINTER(C.c_uint64)),
+                  capi.iptr(vol) if scores else None)
+        return keys, vol
+
+    def lattice_node_pose(self, level, centre, nx, ny, n_theta, dtheta, k, flat):
+        """The pose of node (k, flat) of that lattice, in the window's frame (slamhip_hs_lattice_node_pose; host code)."""
+        spec = capi.lattice_spec(level, centre, nx, ny, n_theta, dtheta)
+        out = np.empty(3, np.float32)
+        capi.call("slamhip_hs_lattice_node_pose", self._h, C.byref(spec), int(k), int(flat), capi.fptr(out))
+        return out
+
     def set_scan(self, scan):
         org = capi.f32(scan.Pose[:2])
         capi.call("slamhip_hs_set_scan", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org))
@@ -338,6 +371,16 @@ class ScanMatcher:
         rep.set_scan(scan)
         capi.call("slamhip_hs_match_best", rep._h, capi.fptr(hints), hints.shape[0], capi.fptr(out), C.byref(idx), capi.rptr(r))
         return out, int(idx.value), r[0]
+
+    def Relocalise(self, rep, scan, level, centre, nx, ny, n_theta, dtheta, B=16):
+        """Lattice search, then the best of the min(B, n_theta) highest-scoring headings' nodes refined by MatchDataBest
+        (slamhip_hs_relocalise): -> (pose, report, info), info a capi.RELOC_INFO record.  Poses in the window's frame."""
+        spec = capi.lattice_spec(level, centre, nx, ny, n_theta, dtheta)
+        out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); info = capi.RelocInfo()
+        self._order(rep)
+        rep.set_scan(scan)
+        capi.call("slamhip_hs_relocalise", rep._h, C.byref(spec), int(B), capi.fptr(out), capi.rptr(r), C.byref(info))
+        return out, r[0], _reloc_info(info)
 
     def MatchDataBatch(self, rep, scan, hintPoses):
         hints = capi.f32(hintPoses, (-1, 3)); out = np.empty_like(hints)
@@ -415,6 +458,18 @@ class HectorSLAMProcessor:
         """MapRep.load_world into the processor's own pyramid, the window moved through the processor so that its poses stay
         world poses: create the processor with startPose = the saved pose, LoadWorld, Update.  -> the cells dropped."""
         return self.MapRep.load_world(path, _shift=self.shift)
+
+    def Relocalise(self, scan, centreWorld, level, nx, ny, n_theta, dtheta, B=16, adopt=True):
+        """Find the robot in the map the window holds (slamhip_hsproc_relocalise): lattice search around centreWorld (a world
+        pose) on `level`, the best nodes refined by the matcher.  -> (poseWorld, report, info).  adopt=True: the pose becomes
+        MatchPose and LastMapUpdatePose, so the next Update matches from it and writes the map only once the robot has moved;
+        adopt=False: the processor is untouched.  The resume flow: LoadWorld, Relocalise, Update."""
+        spec = capi.lattice_spec(level, centreWorld, nx, ny, n_theta, dtheta)
+        org = capi.f32(scan.Pose[:2])
+        out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); info = capi.RelocInfo()
+        capi.call("slamhip_hsproc_relocalise", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), C.byref(spec),
+                  int(B), 1 if adopt else 0, capi.fptr(out), capi.rptr(r), C.byref(info))
+        return out, r[0], _reloc_info(info)
 
     MatchPose = property(lambda self: self._get()[0])
     LastMapUpdatePose = property(lambda self: self._get()[1])
