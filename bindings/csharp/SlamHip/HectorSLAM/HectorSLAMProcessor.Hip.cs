@@ -182,6 +182,19 @@ namespace HectorSLAM.Main
             return pose;
         }
 
+        /// <summary>Relocalise over the whole saved world (slamhip_hsproc_relocalise_world; backing must be on): the lattice is scored
+        /// against the window and the tiles behind it, the window then moves to the best node (info.Dx, info.Dy) and the matcher
+        /// refines there.  Poses stay world poses.  The resume flow: LoadWorld, RelocaliseWorld, Update.</summary>
+        public unsafe Vector3 RelocaliseWorld(ScanCloud scan, LatticeSpec lattice, int maxHints, bool adopt, out SlamHip.MatchReport report, out WorldRelocInfo info)
+        {
+            Vector3 pose;
+            fixed (Vector2* p = CollectionsMarshal.AsSpan(scan.Points))
+                Native.Check(Native.slamhip_hsproc_relocalise_world(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), lattice, maxHints, adopt ? 1 : 0,
+                                                                    out pose, out report, out info));
+            Refresh();
+            return pose;
+        }
+
         private void Refresh()
         {
             Native.Check(Native.slamhip_hsproc_get(proc.Ptr, out Vector3 match, out Vector3 last, out float tm, out float tu));

@@ -118,6 +118,20 @@ namespace HectorSLAM.Main
             return keys;
         }
 
+        /// <summary>LatticeSearch over the world (slamhip_hs_world_lattice_search): a node's cell outside the window is the cell of the
+        /// backing store's tile that holds it -- LogOddsCell.Reset() where none does -- so the lattice reaches everywhere the window has
+        /// been.  The centre stays a pose in the window's frame.  With backing off the results are LatticeSearch's.</summary>
+        public unsafe ulong[] WorldLatticeSearch(ScanCloud scan, LatticeSpec lattice, bool wantScores, out int[] scores)
+        {
+            SetScan(scan);
+            var keys = new ulong[Math.Max(0, lattice.NTheta)];
+            scores = wantScores ? new int[(long)Math.Max(0, lattice.NTheta) * (2 * lattice.Ny + 1) * (2 * lattice.Nx + 1)] : null;
+            fixed (ulong* k = keys)
+            fixed (int* s = scores)
+                Native.Check(Native.slamhip_hs_world_lattice_search(Pyramid.Ptr, lattice, k, s));
+            return keys;
+        }
+
         /// <summary>The pose of node (k, flat) of that lattice in the window's frame (slamhip_hs_lattice_node_pose).</summary>
         public Vector3 LatticeNodePose(LatticeSpec lattice, int k, int flat)
         {

@@ -121,6 +121,18 @@ namespace HectorSLAM.Matcher
             return pose;
         }
 
+        /// <summary>Relocalise anywhere in the world behind the window (slamhip_hs_relocalise_world; backing must be on): the world
+        /// lattice search, the window shifted to the best node, the best nodes that lie in the new window refined by MatchDataBest.
+        /// The pose is in the NEW window's frame; info.Dx, info.Dy say how the window moved.</summary>
+        public unsafe Vector3 RelocaliseWorld(MapRepMultiMap multiMap, ScanCloud scan, LatticeSpec lattice, int maxHints, out MatchReport report, out WorldRelocInfo info)
+        {
+            Native.Check(Native.slamhip_hs_set_match_threads(multiMap.Pyramid.Ptr, matchThreads));
+            multiMap.SetScan(scan);
+            Native.Check(Native.slamhip_hs_relocalise_world(multiMap.Pyramid.Ptr, lattice, maxHints, out Vector3 pose, out report, out info));
+            multiMap.MarkStale();
+            return pose;
+        }
+
         /// <summary>The hint list of a relocalisation around centre = (x, y, theta): every combination of x, y in centre +- k * stepXy
         /// (k * stepXy &lt;= halfXy) and theta in centre +- j * stepTheta (j * stepTheta &lt;= halfTheta).  The centre itself comes first
         /// (ties in MatchDataBest go to the lowest index); the rest follow in x-major, then y, then theta order.  Pure host code.</summary>

@@ -86,6 +86,18 @@ namespace SlamHip
         public int Score, TopScore;
     }
 
+    /// <summary>slamhip_world_reloc_info (include/slamhip.h): the fields of RelocInfo, then the shift the relocalisation applied
+    /// (level-0 cells) and the hints dropped for lying outside the new window.  10 ints, 40 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct WorldRelocInfo
+    {
+        public int HintCount, BestHint;
+        public int K, Ix, Iy;
+        public int Score, TopScore;
+        public int Dx, Dy;
+        public int FarCount;
+    }
+
     internal static unsafe class Native
     {
         const string Lib = "slamhip";                                   // libslamhip.so on the library path
@@ -171,6 +183,8 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_lattice_search(IntPtr hs, in LatticeSpec spec, ulong* keys, int* scores);
         [DllImport(Lib)] internal static extern int slamhip_hs_lattice_node_pose(IntPtr hs, in LatticeSpec spec, int k, int flat, out Vector3 pose);
         [DllImport(Lib)] internal static extern int slamhip_hs_relocalise(IntPtr hs, in LatticeSpec spec, int maxHints, out Vector3 pose, out MatchReport report, out RelocInfo info);
+        [DllImport(Lib)] internal static extern int slamhip_hs_world_lattice_search(IntPtr hs, in LatticeSpec spec, ulong* keys, int* scores);
+        [DllImport(Lib)] internal static extern int slamhip_hs_relocalise_world(IntPtr hs, in LatticeSpec spec, int maxHints, out Vector3 pose, out MatchReport report, out WorldRelocInfo info);
         [DllImport(Lib)] internal static extern int slamhip_debug_lattice_cells(float cellLength, in Vector3 centre, float theta, Vector2* xy, int n, int* gxgy);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_match_threads(IntPtr hs, int numThreads);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_reference_cache(IntPtr hs, int on);
@@ -200,6 +214,8 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_shift(IntPtr proc, int dx, int dy);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_relocalise(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in LatticeSpec specWorld, int maxHints, int adopt,
                                                                               out Vector3 poseWorld, out MatchReport report, out RelocInfo info);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_relocalise_world(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in LatticeSpec specWorld, int maxHints, int adopt,
+                                                                                    out Vector3 poseWorld, out MatchReport report, out WorldRelocInfo info);
 
         // ---- one process, several GPUs -------------------------------------------------------------------------------
         [DllImport(Lib)] internal static extern int slamhip_group_create(int* deviceOrdinals, int n, float physicalMapSize, int holeMapSize, int obstacleMapSize, out IntPtr group);

@@ -143,6 +143,20 @@ int32_t slamhip_debug_world_plan(int32_t w, int32_t h, int64_t OX, int64_t OY, i
  * INT32_MIN twice for a point the search ignores.  n >= 0; xy and out_gxgy may be NULL when n is 0. */
 int32_t slamhip_debug_lattice_cells(float cell_length, const float centre[3], float theta, const float *xy, int32_t n,
                                     int32_t *out_gxgy);
+/* Test hook (no device involved): the planner of the class map of slamhip_hs_world_lattice_search for one level whose window is
+ * w x h cells with cell (0, 0) at world cell (OX, OY), with tiles of `tile` x `tile` cells; tiles_tytx: n_tiles pairs (ty, tx), the
+ * tiles of that level that exist, distinct, in the directory's order (row-major by (ty, tx)); tile = 0 (backing off): n_tiles = 0.
+ * out_rect = {x0, y0, w, h}: the rectangle R the class map covers, in WINDOW-FRAME cells -- the bounding box of the window and of
+ * every tile, so x0 <= 0 and y0 <= 0.  The jobs, as slamhip_world_job: nx x ny cells that go to R from its cell (sx, sy), read
+ * from the window (kind SLAMHIP_WORLD_WINDOW: always the first job, the whole window, lx = ly = tx = ty = 0) or from tile (tx, ty)
+ * from its local cell (lx, ly) (SLAMHIP_WORLD_TILE).  The window wins: a tile gives the part of it that lies OUTSIDE the window,
+ * cut as the backing planner cuts a region -- band above the window, band below it, left strip, right strip -- and nothing if it
+ * lies wholly under the window; tiles in the order given.  Every cell of R is in at most one job; a cell in none is class 0.
+ * If R has more than 2^28 cells, its rows padded to whole 16-cell words: out_rect is written, *n_jobs = 0, SLAMHIP_ERR_INVALID.
+ * Otherwise *n_jobs receives the number of jobs; if it exceeds `cap`, no job is written and the call returns SLAMHIP_ERR_INVALID
+ * (jobs may be NULL when cap is 0).  w, h in [1, 32768]; |OX|, |OY| < 2^60; |ty|, |tx| < 2^52. */
+int32_t slamhip_debug_world_pack_plan(int32_t w, int32_t h, int64_t OX, int64_t OY, int32_t tile, const int64_t *tiles_tytx,
+                                      int32_t n_tiles, int64_t out_rect[4], slamhip_world_job *jobs, int32_t cap, int32_t *n_jobs);
 
 /* Kernel timing (the reference only has Stopwatch EMAs, HectorSLAMProcessor.cs:92-96,111-115).
  * When enabled, each kernel class is bracketed by HIP events on the context's stream. */
@@ -156,7 +170,8 @@ enum {
     SLAMHIP_K_HS_UPDATE = 6,    /* K5 */
     SLAMHIP_K_HS_LATTICE_PACK = 7, /* K7 class-map pack */
     SLAMHIP_K_HS_LATTICE = 8,   /* K7 pose-lattice search */
-    SLAMHIP_K_COUNT = 9
+    SLAMHIP_K_HS_LATTICE_PACK_WORLD = 9, /* K7 class-map pack of the world search: window and tiles */
+    SLAMHIP_K_COUNT = 10
 };
 /* mask: bit k enables kernel class k (e.g. 1 << SLAMHIP_K_CS_DISTANCE); 0 = off; -1 = all classes */
 int32_t slamhip_ctx_timing_enable(slamhip_ctx *ctx, int32_t mask);
@@ -620,7 +635,14 @@ int32_t slamhip_hs_match_best(slamhip_hs *hs, const float *hint_poses, int32_t B
  *   image of slamhip_hs_match_best's minimum key;
  *   node pose, in the window's frame: ((cxm + (float)ix) * cell, (cym + (float)iy) * cell, theta_k).
  * The frame is the one slamhip_hs_match uses -- the WINDOW's (the contract under slamhip_hs_shift).  The search covers the window
- * only: a host that wants another region of the world moves the window there first (slamhip_hs_shift / slamhip_hsproc_shift). */
+ * only; slamhip_hs_world_lattice_search covers the world behind it.
+ * THE WORLD SEARCH is this definition with ONE change: for a window-frame cell (x, y) of level L outside [0, w) x [0, h),
+ * cls(x, y) is no longer 0 but the class of WORLD cell ((ox >> L) + x, (oy >> L) + y), (ox, oy) the origin (slamhip_hs_origin):
+ * the tile's cell if a tile of the backing store holds it, LogOddsCell.Reset() -- class 0 -- if none does.  Inside the window
+ * it is the window's cell: the window wins over a tile's older copy, as in slamhip_hs_world_cells_download and
+ * slamhip_hs_world_extends.  Everything else is unchanged to the letter -- centre in the window's frame, the binary32 point-cell
+ * arithmetic, the rule |f| >= 2^24, the keys and flat, the node pose -- so with backing off, or with no tile on that level, the
+ * world search equals the window search bit for bit. */
 typedef struct slamhip_lattice_spec {
     int32_t level;        /* pyramid level searched */
     int32_t nx, ny;       /* half-extents in cells of that level: ix in [-nx, nx], iy in [-ny, ny] */
@@ -636,6 +658,16 @@ typedef struct slamhip_reloc_info {
     int32_t score;        /* ... and its score */
     int32_t top_score;    /* the score of hint 0, the highest of the lattice */
 } slamhip_reloc_info;     /* 7 four-byte fields, sizeof(slamhip_reloc_info) == 28, no padding */
+/* What slamhip_hs_relocalise_world did: the fields of slamhip_reloc_info, then the shift. */
+typedef struct slamhip_world_reloc_info {
+    int32_t n_hints;      /* the hints handed to the matcher: min(B, n_theta) - n_far */
+    int32_t best_hint;    /* slamhip_hs_match_best's index among those */
+    int32_t k, ix, iy;    /* the lattice node of that hint */
+    int32_t score;        /* ... and its score */
+    int32_t top_score;    /* the score of the top node, the highest of the lattice */
+    int32_t dx, dy;       /* the shift applied (slamhip_hs_shift), in level-0 cells */
+    int32_t n_far;        /* hints dropped for lying outside the new window */
+} slamhip_world_reloc_info;   /* 10 four-byte fields, sizeof(slamhip_world_reloc_info) == 40, no padding */
 /* The search.  Two launches on the operator's stream, behind every grid update, shift and upload already enqueued: one packs the
  * level's cell values into a class map of 2 bits per cell (re-packed on every search; the map belongs to the hs, is allocated by
  * the first search and freed by slamhip_hs_destroy -- an hs that never searches allocates nothing), one scores the lattice and
@@ -656,6 +688,29 @@ int32_t slamhip_hs_lattice_node_pose(slamhip_hs *hs, const slamhip_lattice_spec 
  * The library sets no acceptance threshold, as with the match report.  Errors as slamhip_hs_lattice_search. */
 int32_t slamhip_hs_relocalise(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t B, float out_pose[3],
                               slamhip_match_report *out_report, slamhip_reloc_info *out_info);
+/* The world search (THE WORLD SEARCH above).  Arguments, results, errors, blocking behaviour and pinned staging as
+ * slamhip_hs_lattice_search.  The class map covers a rectangle R of the level: the bounding box of the window and of every tile of
+ * that level in the host's directory (slamhip_debug_world_pack_plan).  A memset of R's words and ONE pack launch
+ * (SLAMHIP_K_HS_LATTICE_PACK_WORLD) over the window and the tiles' parts outside it take the place of the window's pack launch;
+ * the search launch is the same kernel, told R's origin.  The job records reach the device in a block the library owns.  One more
+ * refusal, nothing launched: SLAMHIP_ERR_INVALID if R has more than 2^28 cells (rows padded to whole 16-cell words: 64 MB of
+ * packed map) -- the message gives R's size.  Works with backing off: R is the window. */
+int32_t slamhip_hs_world_lattice_search(slamhip_hs *hs, const slamhip_lattice_spec *spec, uint64_t *out_keys, int32_t *out_scores);
+/* Relocalise anywhere in the saved world: search the world, bring the window to the winner, refine there.
+ *  1. slamhip_hs_world_lattice_search's keys, sorted as slamhip_hs_relocalise sorts them; the first min(B, n_theta) become node poses.
+ *  2. With (lx, ly) the top node's pose: cx = (int)floorf(lx * stm0), cy likewise (stm0 = 1 / cell_length of level 0); per axis
+ *     q = ((c - w0 / 2) / g) * g (C integer division, toward zero; g = 1 << (levels - 1)) -- slamhip_hsproc_set_scroll's rule with
+ *     trigger 0; q = 0 on both axes if |floorf(.)| >= 1e9 on either.  slamhip_hs_shift(qx, qy): the backing store restores what lies there.
+ *  3. Every node pose is re-based into the new frame: x - (float)qx * cell0, the product rounded first; y likewise.
+ *  4. Hint 0 is kept; a later hint is kept only if fx = x * stm0 and fy = y * stm0 satisfy 0 <= fx < (float)w0 and
+ *     0 <= fy < (float)h0 -- it lies in the new level-0 window; the others are counted in n_far.
+ *  5. slamhip_hs_match_best over the kept hints, in their order: out_pose and out_report are exactly what that call returns.
+ * out_pose is in the NEW window's frame; dx, dy tell the caller how the window moved.  1 <= B <= 64.
+ * Checked before anything is launched or moved -- the map, the origin and the backing statistics stay as they were:
+ * SLAMHIP_ERR_STATE if backing is off (the shift would destroy the map); SLAMHIP_ERR_INVALID if the reference's cache is on (the
+ * shift refuses); the search's own errors. */
+int32_t slamhip_hs_relocalise_world(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t B, float out_pose[3],
+                                    slamhip_match_report *out_report, slamhip_world_reloc_info *out_info);
 
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
@@ -811,10 +866,21 @@ int32_t slamhip_hsproc_shift(slamhip_hsproc *p, int32_t dx, int32_t dy);
  * result brought back as slamhip_hsproc_get does (+ (float)origin * cell0).  adopt = 1: the result becomes both MatchPose and
  * LastMapUpdatePose -- the next Update matches from the found pose and the map is not written until the robot has moved by the
  * thresholds (a relocalisation must not immediately draw into the map); adopt = 0: the processor's state is untouched; any other
- * value SLAMHIP_ERR_INVALID.  No scroll is issued.  The search covers the window (slamhip_hs_lattice_search). */
+ * value SLAMHIP_ERR_INVALID.  No scroll is issued.  The search covers the window (slamhip_hs_lattice_search);
+ * slamhip_hsproc_relocalise_world searches the world and moves the window. */
 int32_t slamhip_hsproc_relocalise(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
                                   const slamhip_lattice_spec *spec_world, int32_t B, int32_t adopt, float out_pose_world[3],
                                   slamhip_match_report *out_report, slamhip_reloc_info *out_info);
+/* slamhip_hsproc_relocalise over the whole world: slamhip_hs_set_scan, then slamhip_hs_relocalise_world with spec_world->centre
+ * taken to the window's frame (- (float)origin * cell0, the origin BEFORE the call).  The processor's MatchPose and
+ * LastMapUpdatePose are re-based by the shift as slamhip_hsproc_shift re-bases them, whether or not adopt is set, so that
+ * slamhip_hsproc_get goes on answering in the world frame; with adopt = 1 both then become the result.  out_pose_world is the
+ * result + (float)origin * cell0 with the origin AFTER the call.  Errors as slamhip_hs_relocalise_world; adopt outside {0, 1}:
+ * SLAMHIP_ERR_INVALID. */
+int32_t slamhip_hsproc_relocalise_world(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
+                                        const slamhip_lattice_spec *spec_world, int32_t B, int32_t adopt,
+                                        float out_pose_world[3], slamhip_match_report *out_report,
+                                        slamhip_world_reloc_info *out_info);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -16,6 +16,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "slamhip.h")
 OK = 0
 ERR_INVALID, ERR_HIP, ERR_NOMEM, ERR_STATE, ERR_RCCL, ERR_TIMEOUT = -1, -2, -3, -4, -5, -6
 K_CS_PREP, K_CS_DISTANCE, K_CS_REDUCE, K_CS_HOLEMAP, K_CS_OBSTACLE, K_HS_MATCH, K_HS_UPDATE, K_HS_LATTICE_PACK, K_HS_LATTICE = range(9)
+K_HS_LATTICE_PACK_WORLD = 9
 
 CELL_DTYPE = np.dtype([("update_index", np.int32), ("value", np.float32)])
 
@@ -94,6 +95,15 @@ RELOC_INFO = np.dtype([("n_hints", np.int32), ("best_hint", np.int32), ("k", np.
 assert C.sizeof(LATTICE_SPEC) == 32 and C.sizeof(RelocInfo) == RELOC_INFO.itemsize == 28
 
 
+class WorldRelocInfo(C.Structure):
+    """slamhip_world_reloc_info (include/slamhip.h): the fields of slamhip_reloc_info, then dx, dy, n_far; 10 int32, 40 bytes."""
+    _fields_ = RelocInfo._fields_ + [("dx", C.c_int32), ("dy", C.c_int32), ("n_far", C.c_int32)]
+
+
+WORLD_RELOC_INFO = np.dtype([(n, np.int32) for n, _ in WorldRelocInfo._fields_])
+assert C.sizeof(WorldRelocInfo) == WORLD_RELOC_INFO.itemsize == 40
+
+
 def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
     """A LATTICE_SPEC from Python values (centre rounded to binary32 as f32 rounds it)."""
     c = f32(centre, (3,))
@@ -135,7 +145,7 @@ def _declare(L):
     fp, ip, u16p, i8p, u8p, u64p, vpp = P(f), P(i32), P(C.c_uint16), P(C.c_int8), P(C.c_uint8), P(u64), P(vp)
     rp = P(MatchReport)
     srp = P(SearchReport)
-    lsp, rip = P(LATTICE_SPEC), P(RelocInfo)
+    lsp, rip, wrip = P(LATTICE_SPEC), P(RelocInfo), P(WorldRelocInfo)
     sig = {
         "slamhip_version": (C.c_char_p, []),
         "slamhip_last_error": (C.c_char_p, []),
@@ -152,6 +162,7 @@ def _declare(L):
         "slamhip_debug_backing_plan": (i32, [i32, i32, i32, i64, i64, i32, i32, i32, P(BackingJob), i32, ip]),
         "slamhip_debug_world_plan": (i32, [i32, i32, i64, i64, i64, i64, i32, i32, i32, P(WorldJob), i32, ip]),
         "slamhip_debug_lattice_cells": (i32, [f, fp, f, fp, i32, ip]),
+        "slamhip_debug_world_pack_plan": (i32, [i32, i32, i64, i64, i32, P(i64), i32, P(i64), P(WorldJob), i32, ip]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -236,6 +247,8 @@ def _declare(L):
         "slamhip_hs_lattice_search": (i32, [vp, lsp, u64p, ip]),
         "slamhip_hs_lattice_node_pose": (i32, [vp, lsp, i32, i32, fp]),
         "slamhip_hs_relocalise": (i32, [vp, lsp, i32, fp, rp, rip]),
+        "slamhip_hs_world_lattice_search": (i32, [vp, lsp, u64p, ip]),
+        "slamhip_hs_relocalise_world": (i32, [vp, lsp, i32, fp, rp, wrip]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -259,6 +272,7 @@ def _declare(L):
         "slamhip_hsproc_get_origin": (i32, [vp, P(i64), P(i64)]),
         "slamhip_hsproc_shift": (i32, [vp, i32, i32]),
         "slamhip_hsproc_relocalise": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, rip]),
+        "slamhip_hsproc_relocalise_world": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, wrip]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -320,6 +334,22 @@ def world_plan(w, h, OX, OY, x0, y0, rw, rh, tile):
     jobs = np.zeros(n.value, WORLD_JOB_DTYPE)
     call("slamhip_debug_world_plan", w, h, OX, OY, x0, y0, rw, rh, tile, jobs.ctypes.data_as(C.POINTER(WorldJob)), n.value, C.byref(n))
     return jobs
+
+
+def world_pack_plan(w, h, OX, OY, tile, tiles):
+    """The plan of the world search's class map for one level (slamhip_debug_world_pack_plan; no device involved): `tiles` the
+    (ty, tx) pairs of the tiles that exist, row-major.  -> ((x0, y0, rw, rh), jobs): the rectangle R in window-frame cells and a
+    WORLD_JOB_DTYPE array in the order the pack launch uses.  An R of more than 2^28 cells raises SlamhipError (ERR_INVALID)."""
+    t = np.ascontiguousarray(tiles, np.int64).reshape(-1, 2)
+    tp = t.ctypes.data_as(C.POINTER(C.c_int64)) if t.shape[0] else None
+    rect = (C.c_int64 * 4)()
+    n = C.c_int32()
+    rc = lib().slamhip_debug_world_pack_plan(w, h, OX, OY, tile, tp, t.shape[0], rect, None, 0, C.byref(n))
+    if n.value <= 0:
+        check(rc)
+    jobs = np.zeros(n.value, WORLD_JOB_DTYPE)
+    call("slamhip_debug_world_pack_plan", w, h, OX, OY, tile, tp, t.shape[0], rect, jobs.ctypes.data_as(C.POINTER(WorldJob)), n.value, C.byref(n))
+    return tuple(int(v) for v in rect), jobs
 
 
 def lattice_cells(cell_length, centre, theta, xy):

@@ -2,6 +2,7 @@
 #include "common.h"
 #include "backing_plan.h"
 #include "world_plan.h"
+#include "world_pack_plan.h"
 #include <stdlib.h>
 #include <time.h>
 
@@ -281,6 +282,31 @@ extern "C" int32_t slamhip_debug_world_plan(int32_t w, int32_t h, int64_t OX, in
     if (plan.size() > (size_t)cap)
         SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_debug_world_plan: the plan has %zu jobs, the caller's array holds %d", plan.size(), cap);
     if (!plan.empty()) memcpy(jobs, plan.data(), sizeof(slamhip_world_job) * plan.size());
+    return SLAMHIP_OK;
+}
+
+// CPU-side test hook: the planner of the world class map (world_pack_plan.h), as slamhip_hs_world_lattice_search calls it
+extern "C" int32_t slamhip_debug_world_pack_plan(int32_t w, int32_t h, int64_t OX, int64_t OY, int32_t tile, const int64_t *tiles_tytx,
+                                                 int32_t n_tiles, int64_t out_rect[4], slamhip_world_job *jobs, int32_t cap, int32_t *n_jobs)
+{
+    const int64_t lim = (int64_t)1 << 52;
+    SH_CHECK_ARG(n_jobs && out_rect && cap >= 0 && (jobs || cap == 0) && n_tiles >= 0 && (tiles_tytx || n_tiles == 0));
+    SH_CHECK_ARG(w >= 1 && h >= 1 && w <= 32768 && h <= 32768 && OX > -lim * 256 && OX < lim * 256 && OY > -lim * 256 && OY < lim * 256);
+    SH_CHECK_ARG(tile == 0 ? n_tiles == 0 : (tile >= 8 && tile <= 256 && (tile & (tile - 1)) == 0));
+    for (int i = 0; i < 2 * n_tiles; i++) SH_CHECK_ARG(tiles_tytx[i] > -lim && tiles_tytx[i] < lim);
+    const wpp_rect R = wpp_bounds(w, h, OX, OY, tile, tiles_tytx, (size_t)n_tiles);
+    out_rect[0] = R.x0; out_rect[1] = R.y0; out_rect[2] = R.w; out_rect[3] = R.h;
+    *n_jobs = 0;
+    if (!wpp_fits(R))
+        SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_debug_world_pack_plan: the rectangle of the window and the tiles is %lld x %lld cells, more than 2^28",
+                (long long)R.w, (long long)R.h);
+    std::vector<slamhip_world_job> plan;
+    wpp_plan(w, h, OX, OY, tile, tiles_tytx, (size_t)n_tiles, R, plan);
+    if (plan.size() > (size_t)INT32_MAX) SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_debug_world_pack_plan: %zu jobs", plan.size());
+    *n_jobs = (int32_t)plan.size();
+    if (plan.size() > (size_t)cap)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_debug_world_pack_plan: the plan has %zu jobs, the caller's array holds %d", plan.size(), cap);
+    memcpy(jobs, plan.data(), sizeof(slamhip_world_job) * plan.size());
     return SLAMHIP_OK;
 }
 

@@ -137,15 +137,19 @@ static int32_t hsproc_update_window(slamhip_hsproc *p, const float *xy, int32_t 
 
 // slamhip_hs_shift of the processor's own hs with the stored poses, kept in the window's frame, re-based: the one place where the
 // scroll and slamhip_hsproc_shift move the window.  All in binary32, one rounding per operation.
-static int32_t hsproc_shift_rebase(slamhip_hsproc *p, int32_t dx, int32_t dy)
+static void hsproc_rebase(slamhip_hsproc *p, int32_t dx, int32_t dy)
 {
-    SH_TRY(slamhip_hs_shift(p->hs, dx, dy));
     const int32_t q[2] = { dx, dy };
     for (int a = 0; a < 2; a++) {
         const float m = (float)q[a] * p->hs->lv[0].cell;                   // (the product is rounded, then the difference)
         p->match_pose[a] = p->match_pose[a] - m;
         p->last_update_pose[a] = p->last_update_pose[a] - m;               // (float.MinValue absorbs it: "never updated" survives)
     }
+}
+static int32_t hsproc_shift_rebase(slamhip_hsproc *p, int32_t dx, int32_t dy)
+{
+    SH_TRY(slamhip_hs_shift(p->hs, dx, dy));
+    hsproc_rebase(p, dx, dy);
     return SLAMHIP_OK;
 }
 
@@ -227,6 +231,32 @@ extern "C" int32_t slamhip_hsproc_relocalise(slamhip_hsproc *p, const float *xy,
         memcpy(p->match_pose, m, sizeof(m));
         memcpy(p->last_update_pose, m, sizeof(m));
     }
+    out_pose_world[0] = moved ? m[0] + off[0] : m[0]; out_pose_world[1] = moved ? m[1] + off[1] : m[1]; out_pose_world[2] = m[2];
+    return SLAMHIP_OK;
+}
+
+// Relocalise in the world: as above, but the window moves to the winner (slamhip_hs_relocalise_world) and the stored poses with it.
+extern "C" int32_t slamhip_hsproc_relocalise_world(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const slamhip_lattice_spec *spec_world,
+                                                   int32_t B, int32_t adopt, float out_pose_world[3], slamhip_match_report *out_report,
+                                                   slamhip_world_reloc_info *out_info)
+{
+    SH_CHECK_ARG(p && spec_world && out_pose_world && out_report && out_info && (adopt == 0 || adopt == 1));
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    float off[2];
+    hsproc_window_offset(p, off);
+    slamhip_lattice_spec S = *spec_world;
+    if (p->hs->win_ox != 0 || p->hs->win_oy != 0) { S.centre[0] = S.centre[0] - off[0]; S.centre[1] = S.centre[1] - off[1]; }
+    float m[3];
+    memset(out_info, 0, sizeof(*out_info));
+    const int32_t rc = slamhip_hs_relocalise_world(p->hs, &S, B, m, out_report, out_info);
+    hsproc_rebase(p, out_info->dx, out_info->dy);                          // (the stored poses follow the window, also if the match behind the shift failed)
+    SH_TRY(rc);
+    if (adopt) {
+        memcpy(p->match_pose, m, sizeof(m));
+        memcpy(p->last_update_pose, m, sizeof(m));
+    }
+    const bool moved = p->hs->win_ox != 0 || p->hs->win_oy != 0;
+    hsproc_window_offset(p, off);
     out_pose_world[0] = moved ? m[0] + off[0] : m[0]; out_pose_world[1] = moved ? m[1] + off[1] : m[1]; out_pose_world[2] = m[2];
     return SLAMHIP_OK;
 }

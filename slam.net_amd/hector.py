@@ -41,6 +41,10 @@ def _reloc_info(info):
     return np.array([tuple(getattr(info, n) for n, _ in capi.RelocInfo._fields_)], capi.RELOC_INFO)[0]
 
 
+def _world_reloc_info(info):
+    return np.array([tuple(getattr(info, n) for n, _ in capi.WorldRelocInfo._fields_)], capi.WORLD_RELOC_INFO)[0]
+
+
 class ScanCloud:
     """BaseSLAM/ScanCloud.cs:10-21"""
 
@@ -294,6 +298,20 @@ class MapRepMultiMap:
                   capi.iptr(vol) if scores else None)
         return keys, vol
 
+    def world_lattice_search(self, scan, level, centre, nx, ny, n_theta, dtheta, scores=False):
+        """lattice_search over the WORLD (slamhip_hs_world_lattice_search): a node's cell outside the window is the cell of the
+        tile that holds it (LogOddsCell.Reset() where none does) instead of nothing, so the lattice may reach anywhere the window
+        has ever been -- `centre` stays a pose in the window's frame and may lie outside the window.  Arguments and results as
+        lattice_search; with backing off, or no tile on `level`, the results are lattice_search's bit for bit."""
+        if scan is not None:
+            self.set_scan(scan)
+        spec = capi.lattice_spec(level, centre, nx, ny, n_theta, dtheta)
+        keys = np.zeros(int(n_theta), np.uint64)
+        vol = np.zeros((int(n_theta), 2 * int(ny) + 1, 2 * int(nx) + 1), np.int32) if scores else None
+        capi.call("slamhip_hs_world_lattice_search", self._h, C.byref(spec), keys.ctypes.data_as(C.POINTER(C.c_uint64)),
+                  capi.iptr(vol) if scores else None)
+        return keys, vol
+
     def lattice_node_pose(self, level, centre, nx, ny, n_theta, dtheta, k, flat):
         """The pose of node (k, flat) of that lattice, in the window's frame (slamhip_hs_lattice_node_pose; host code)."""
         spec = capi.lattice_spec(level, centre, nx, ny, n_theta, dtheta)
@@ -381,6 +399,18 @@ class ScanMatcher:
         rep.set_scan(scan)
         capi.call("slamhip_hs_relocalise", rep._h, C.byref(spec), int(B), capi.fptr(out), capi.rptr(r), C.byref(info))
         return out, r[0], _reloc_info(info)
+
+    def RelocaliseWorld(self, rep, scan, level, centre, nx, ny, n_theta, dtheta, B=16):
+        """Relocalise anywhere in the world behind the window (slamhip_hs_relocalise_world; backing must be on): the world
+        lattice search, the window shifted to the best node -- the backing store restores what lies there -- and the best
+        headings' nodes that lie in the new window refined by MatchDataBest.  -> (pose, report, info): the pose in the NEW
+        window's frame, info a capi.WORLD_RELOC_INFO record whose dx, dy say how the window moved."""
+        spec = capi.lattice_spec(level, centre, nx, ny, n_theta, dtheta)
+        out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); info = capi.WorldRelocInfo()
+        self._order(rep)
+        rep.set_scan(scan)
+        capi.call("slamhip_hs_relocalise_world", rep._h, C.byref(spec), int(B), capi.fptr(out), capi.rptr(r), C.byref(info))
+        return out, r[0], _world_reloc_info(info)
 
     def MatchDataBatch(self, rep, scan, hintPoses):
         hints = capi.f32(hintPoses, (-1, 3)); out = np.empty_like(hints)
@@ -470,6 +500,19 @@ class HectorSLAMProcessor:
         capi.call("slamhip_hsproc_relocalise", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), C.byref(spec),
                   int(B), 1 if adopt else 0, capi.fptr(out), capi.rptr(r), C.byref(info))
         return out, r[0], _reloc_info(info)
+
+    def RelocaliseWorld(self, scan, centreWorld, level, nx, ny, n_theta, dtheta, B=16, adopt=True):
+        """Find the robot anywhere in the saved world (slamhip_hsproc_relocalise_world; backing must be on): as Relocalise, but
+        the lattice is scored against the window AND the tiles behind it, and the window then moves to the best node.
+        -> (poseWorld, report, info), info a capi.WORLD_RELOC_INFO record (dx, dy: the shift).  MatchPose and LastMapUpdatePose
+        stay the world poses they were (adopt=False) or become the result (adopt=True).  The resume flow: LoadWorld,
+        RelocaliseWorld, Update."""
+        spec = capi.lattice_spec(level, centreWorld, nx, ny, n_theta, dtheta)
+        org = capi.f32(scan.Pose[:2])
+        out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); info = capi.WorldRelocInfo()
+        capi.call("slamhip_hsproc_relocalise_world", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), C.byref(spec),
+                  int(B), 1 if adopt else 0, capi.fptr(out), capi.rptr(r), C.byref(info))
+        return out, r[0], _world_reloc_info(info)
 
     MatchPose = property(lambda self: self._get()[0])
     LastMapUpdatePose = property(lambda self: self._get()[1])
