@@ -195,6 +195,21 @@ namespace HectorSLAM.Main
             return pose;
         }
 
+        /// <summary>MapRep.Trace of `scan` at WORLD poses (slamhip_hsproc_trace): what the map of `level` holds along every beam, per
+        /// pose a summary and, when asked for, the beam records [pose][beam], whose Hx, Hy stay window-frame cells of the level
+        /// (world cell = (Origin >> level) + cell).  MatchPose, LastMapUpdatePose and the update gate are untouched.</summary>
+        public unsafe TraceSummary[] Trace(ScanCloud scan, Vector3[] posesWorld, int level, bool world, bool wantBeams, out TraceBeam[] beams)
+        {
+            var sums = new TraceSummary[posesWorld.Length];
+            beams = wantBeams ? new TraceBeam[(long)posesWorld.Length * scan.Points.Count] : null;
+            fixed (Vector2* p = CollectionsMarshal.AsSpan(scan.Points))
+            fixed (Vector3* q = posesWorld)
+            fixed (TraceSummary* s = sums)
+            fixed (TraceBeam* b = beams)
+                Native.Check(Native.slamhip_hsproc_trace(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), q, posesWorld.Length, level, world ? 1 : 0, s, b));
+            return sums;
+        }
+
         private void Refresh()
         {
             Native.Check(Native.slamhip_hsproc_get(proc.Ptr, out Vector3 match, out Vector3 last, out float tm, out float tu));

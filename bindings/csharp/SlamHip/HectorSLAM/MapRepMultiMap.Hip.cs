@@ -150,6 +150,44 @@ namespace HectorSLAM.Main
             return cells;
         }
 
+        /// <summary>The beam trace (slamhip_hs_trace; the reference has no counterpart): what the map of `level` holds along every
+        /// beam of the scan from each of the poses (window frame) -- the grid update's own line from the sensor cell to the beam's end
+        /// cell.  Returns one summary per pose and, when asked for, the beam records [pose][beam] (poses x beams at most 2^20).
+        /// world: a cell outside the window is the cell of the backing store's tile that holds it.  Blocking; it changes nothing.</summary>
+        public unsafe TraceSummary[] Trace(ScanCloud scan, Vector3[] poses, int level, bool world, bool wantBeams, out TraceBeam[] beams)
+        {
+            SetScan(scan);
+            var sums = new TraceSummary[poses.Length];
+            beams = wantBeams ? new TraceBeam[(long)poses.Length * scan.Points.Count] : null;
+            fixed (Vector3* p = poses)
+            fixed (TraceSummary* s = sums)
+            fixed (TraceBeam* b = beams)
+                Native.Check(Native.slamhip_hs_trace(Pyramid.Ptr, level, p, poses.Length, world ? 1 : 0, s, b));
+            return sums;
+        }
+
+        /// <summary>The trace's lines on the host (slamhip_debug_trace_lines): {bx, by, ex, ey, da} per point for one pose on a level
+        /// whose ScaleToMap is scaleToMap; an ignored beam is {0, 0, 0, 0, -1}.</summary>
+        public static unsafe int[] TraceLines(float scaleToMap, Vector3 pose, Vector2 scanOrigin, Vector2[] points)
+        {
+            var lines = new int[5 * points.Length];
+            fixed (Vector2* p = points)
+            fixed (int* l = lines)
+                Native.Check(Native.slamhip_debug_trace_lines(scaleToMap, pose, scanOrigin, p, points.Length, l));
+            return lines;
+        }
+
+        /// <summary>The cells the trace walks from cell (bx, by) to cell (ex, ey), in order, x and y interleaved (slamhip_debug_trace_cells).</summary>
+        public static unsafe int[] TraceCells(int bx, int by, int ex, int ey)
+        {
+            var cells = new int[2 * (Math.Min(Math.Max(Math.Abs((long)ex - bx), Math.Abs((long)ey - by)), 32768) + 1)];
+            int n;
+            fixed (int* c = cells)
+                Native.Check(Native.slamhip_debug_trace_cells(bx, by, ex, ey, c, cells.Length / 2, out n));
+            Array.Resize(ref cells, 2 * n);
+            return cells;
+        }
+
         /// <summary>The sum of all shifts since construction or the last Reset, in level-0 cells (slamhip_hs_origin).</summary>
         public (long X, long Y) Origin
         {

@@ -98,6 +98,28 @@ namespace SlamHip
         public int FarCount;
     }
 
+    /// <summary>slamhip_trace_beam (include/slamhip.h): what the map holds along one beam of a trace.  Da: -1 ignored, 0 the
+    /// sensor's own cell, else the length of the walked line; First: the step of the first occupied cell, or -1; UnknownCount: the
+    /// unknown cells in front of it; EndClass: the class of the end cell (1 occupied, 2 free, 0 neither); Hx, Hy: the cell of
+    /// step First in window-frame cells of the level.  6 ints, 24 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct TraceBeam
+    {
+        public int Da, First, UnknownCount, EndClass;
+        public int Hx, Hy;
+    }
+
+    /// <summary>slamhip_trace_summary (include/slamhip.h): one pose's beams counted -- by status, those that reach an obstacle at
+    /// their end cell, those blocked in front of it, those that end on a free cell -- and the unknown cells they cross.  6 ints and
+    /// a long, 32 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct TraceSummary
+    {
+        public int WalkedCount, SameCount, IgnoredCount;
+        public int EndHitCount, BlockedCount, EndFreeCount;
+        public long UnknownCells;
+    }
+
     internal static unsafe class Native
     {
         const string Lib = "slamhip";                                   // libslamhip.so on the library path
@@ -186,6 +208,10 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_world_lattice_search(IntPtr hs, in LatticeSpec spec, ulong* keys, int* scores);
         [DllImport(Lib)] internal static extern int slamhip_hs_relocalise_world(IntPtr hs, in LatticeSpec spec, int maxHints, out Vector3 pose, out MatchReport report, out WorldRelocInfo info);
         [DllImport(Lib)] internal static extern int slamhip_debug_lattice_cells(float cellLength, in Vector3 centre, float theta, Vector2* xy, int n, int* gxgy);
+        // the beam trace (no reference counterpart): the map along every beam of the scan, at many poses; and its host-side hooks
+        [DllImport(Lib)] internal static extern int slamhip_hs_trace(IntPtr hs, int level, Vector3* poses, int nPoses, int world, TraceSummary* summaries, TraceBeam* beams);
+        [DllImport(Lib)] internal static extern int slamhip_debug_trace_lines(float scaleToMap, in Vector3 pose, in Vector2 origin, Vector2* xy, int n, int* lines);
+        [DllImport(Lib)] internal static extern int slamhip_debug_trace_cells(int bx, int by, int ex, int ey, int* cells, int cap, out int n);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_match_threads(IntPtr hs, int numThreads);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_reference_cache(IntPtr hs, int on);
         [DllImport(Lib)] internal static extern int slamhip_hs_update_by_scan(IntPtr hs, in Vector3 robotPoseWorld);
@@ -214,6 +240,8 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_shift(IntPtr proc, int dx, int dy);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_relocalise(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in LatticeSpec specWorld, int maxHints, int adopt,
                                                                               out Vector3 poseWorld, out MatchReport report, out RelocInfo info);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_trace(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int world,
+                                                                         TraceSummary* summaries, TraceBeam* beams);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_relocalise_world(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in LatticeSpec specWorld, int maxHints, int adopt,
                                                                                     out Vector3 poseWorld, out MatchReport report, out WorldRelocInfo info);
 

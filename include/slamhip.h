@@ -158,6 +158,17 @@ int32_t slamhip_debug_lattice_cells(float cell_length, const float centre[3], fl
 int32_t slamhip_debug_world_pack_plan(int32_t w, int32_t h, int64_t OX, int64_t OY, int32_t tile, const int64_t *tiles_tytx,
                                       int32_t n_tiles, int64_t out_rect[4], slamhip_world_job *jobs, int32_t cap, int32_t *n_jobs);
 
+/* Test hooks (no device involved): the arithmetic of the beam trace (slamhip_hs_trace, THE DEFINITION at slamhip_trace_beam), the
+ * text the kernel runs.  slamhip_debug_trace_lines: steps 1 and 2 for the n scan points xy under pose[3] on a level whose
+ * ScaleToMap is stm, with scan origin origin[2]: out[5 i .. 5 i + 4] = {bx, by, ex, ey, da} of beam i; an ignored beam reports
+ * {0, 0, 0, 0, -1}.  n >= 0; xy and out may be NULL when n is 0.
+ * slamhip_debug_trace_cells: step 3 for the line from cell (bx, by) to cell (ex, ey): the walked cells in order, cell 0 first,
+ * out_xy[2 j], out_xy[2 j + 1] the cell of step j; *out_n = da + 1 of them.  If that exceeds `cap` nothing is written and the
+ * call returns SLAMHIP_ERR_INVALID (out_xy may be NULL when cap is 0).  SLAMHIP_ERR_INVALID, *out_n = 0: |bx|, |by|, |ex| or |ey|
+ * >= 2^24, da = 0, or da > SLAMHIP_TRACE_MAX_DA -- no walked beam has such a line. */
+int32_t slamhip_debug_trace_lines(float stm, const float pose[3], const float origin[2], const float *xy, int32_t n, int32_t *out);
+int32_t slamhip_debug_trace_cells(int32_t bx, int32_t by, int32_t ex, int32_t ey, int32_t *out_xy, int32_t cap, int32_t *out_n);
+
 /* Kernel timing (the reference only has Stopwatch EMAs, HectorSLAMProcessor.cs:92-96,111-115).
  * When enabled, each kernel class is bracketed by HIP events on the context's stream. */
 enum {
@@ -712,6 +723,56 @@ int32_t slamhip_hs_world_lattice_search(slamhip_hs *hs, const slamhip_lattice_sp
 int32_t slamhip_hs_relocalise_world(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t B, float out_pose[3],
                                     slamhip_match_report *out_report, slamhip_world_reloc_info *out_info);
 
+/* The beam trace (K8; no reference counterpart): what the map of ONE level holds ALONG every beam of the scan, from many poses
+ * at once.  The matcher and the lattice search consult the map at beam end points only; this walks the grid update's own line
+ * from the sensor cell to the beam's end cell and reads the class of every cell on it.  One operation, three uses: the check of
+ * a pose that end points cannot give (a pose whose beams pass through walls the map holds: n_blocked), the expected scan (the
+ * range the map predicts for a beam: first, hx, hy), and the unknown cells a pose would see (unknown_cells).
+ * THE DEFINITION (every binary32 operation rounded on its own, no fused multiply-add), for level L with stm = its ScaleToMap, a
+ * pose P = (x, y, theta) in the WINDOW's frame as slamhip_hs_update_by_scan takes it, and the scan and scan origin as
+ * slamhip_hs_set_scan took them:
+ *  1. t = Rotation(theta) * Translation(x, y) * Scale(stm), the Matrix3x2 product the grid update forms (OccGridMap.cs:120-123);
+ *     (bxf, byf) = Transform(origin, t), (exf, eyf) = Transform(point, t); b = (int)rintf(.) of the former, e of the latter:
+ *     banker's rounding, as the update's ToRoundPoint (:127, :134).
+ *  2. The beam is IGNORED (da = -1) if any of the four floats fails fabsf(f) < 16777216.0f (a NaN fails), or if
+ *     max(|ex - bx|, |ey - by|) > SLAMHIP_TRACE_MAX_DA: the cap keeps da / 2 + a * db below 2^31 and bounds the walk.  It is the
+ *     SAME beam (da = 0) if b == e: the update draws nothing (:137).  Otherwise it is WALKED, da = max(|dx|, |dy|) >= 1.
+ *  3. The walk: cell 0 is b; for a = 1 .. da - 1 the cell at major offset a and minor offset sign * ((da / 2 + a * db) / da), db
+ *     the minor length, the major axis x iff |dx| >= |dy| (the closed form of Bresenham2D, :220-239); cell da is e.  This is
+ *     exactly the list of cells the update would touch for that beam, and it is NOT cut at the window: a cell outside
+ *     [0, w) x [0, h) has class 0 (the lattice search's rule).  In the WORLD variant such a cell has the class of world cell
+ *     ((ox >> L) + x, (oy >> L) + y): the tile's cell if a tile of the backing store holds it, else 0 -- THE WORLD SEARCH's rule.
+ *     Classes: 1 occupied (Value > 0.0f), 2 free (Value < 0.0f), 0 neither.
+ *  4. Per beam, slamhip_trace_beam.  5. Per pose, slamhip_trace_summary.  The library sets no threshold and forms no score. */
+#define SLAMHIP_TRACE_MAX_DA 32768
+typedef struct slamhip_trace_beam {
+    int32_t da;           /* -1 ignored, 0 same, else the major length of the walked line */
+    int32_t first;        /* the smallest a in [0, da] whose cell is occupied, or -1 */
+    int32_t n_unknown;    /* the class-0 cells among a < stop, stop = first if first >= 0, else da + 1 */
+    int32_t end_class;    /* the class bits of e */
+    int32_t hx, hy;       /* the cell of step `first` in window-frame cells of the level; 0, 0 if there is none */
+} slamhip_trace_beam;     /* 6 four-byte fields, 24 bytes, no padding; da <= 0: first = -1, every other field 0 */
+typedef struct slamhip_trace_summary {
+    int32_t n_walked, n_same, n_ignored;   /* the beams by status: they sum to n_points */
+    int32_t n_end_hit;    /* first == da: the beam reaches its end cell and the map holds an obstacle there */
+    int32_t n_blocked;    /* 0 <= first < da: the map holds an obstacle in front of the end cell */
+    int32_t n_end_free;   /* first == -1 and end_class == 2: the map says free where the scan saw an obstacle */
+    int64_t unknown_cells;   /* the sum of n_unknown */
+} slamhip_trace_summary;  /* six int32_t, then one int64_t: 32 bytes, no padding */
+/* The trace of the scan that was set, on `level`, at B poses (poses: B x 3 floats, window frame).  world: 0 the window, 1 the
+ * world behind it.  out_summaries: B records.  out_beams: NULL, or B x n_points records, pose-major.
+ * The launches, on the operator's stream behind every grid update, shift and upload already enqueued: the lattice search's class
+ * map of the level, re-packed on every call (its pack launch and timing class for the window; the memset, the planner and the pack
+ * launch of slamhip_hs_world_lattice_search for the world), a memset of the summaries, and ONE trace launch, a beam per lane.  The
+ * blocks belong to the hs, are made by the first trace and freed by slamhip_hs_destroy.  Blocking, with the context's bounded
+ * wait; the results come back through pinned staging that the library owns.  It reads cell values only, so it works with backing
+ * off (world = window), with slamhip_hs_set_reference_cache on, and after shifts; it changes nothing of the map or of any search.
+ * A pose that is not finite is no error: its beams are ignored.
+ * SLAMHIP_ERR_INVALID, nothing launched: level out of range, B outside [1, 65536], out_beams given with B * n_points > 2^20, world
+ * not 0 or 1, the world's rectangle over 2^28 cells.  SLAMHIP_ERR_STATE: no scan.  A poisoned context: SLAMHIP_ERR_TIMEOUT. */
+int32_t slamhip_hs_trace(slamhip_hs *hs, int32_t level, const float *poses, int32_t B, int32_t world,
+                         slamhip_trace_summary *out_summaries, slamhip_trace_beam *out_beams);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -881,6 +942,16 @@ int32_t slamhip_hsproc_relocalise_world(slamhip_hsproc *p, const float *xy, int3
                                         const slamhip_lattice_spec *spec_world, int32_t B, int32_t adopt,
                                         float out_pose_world[3], slamhip_match_report *out_report,
                                         slamhip_world_reloc_info *out_info);
+/* The beam trace through the processor: slamhip_hs_set_scan on the processor's own hs, then slamhip_hs_trace at the B poses of
+ * poses_world (B x 3, WORLD frame), each taken to the window's frame as slamhip_hsproc_relocalise takes its centre
+ * (- (float)origin * cell0 per axis; the bits themselves while the origin is 0).  hx, hy stay in window-frame cells of the level:
+ * slamhip_hsproc_get_origin converts them (world cell = (origin >> level) + cell).  The processor's stored poses, its update gate
+ * and its match report are not touched; the scan that was set is replaced, as every call that takes a scan replaces it.
+ * Errors as slamhip_hs_trace; a call refused for its level, B, world or the 2^20 records leaves the scan that was set (the world's
+ * rectangle is known only once the trace plans it, behind the new scan). */
+int32_t slamhip_hsproc_trace(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
+                             const float *poses_world, int32_t B, int32_t level, int32_t world,
+                             slamhip_trace_summary *out_summaries, slamhip_trace_beam *out_beams);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -104,6 +104,14 @@ WORLD_RELOC_INFO = np.dtype([(n, np.int32) for n, _ in WorldRelocInfo._fields_])
 assert C.sizeof(WorldRelocInfo) == WORLD_RELOC_INFO.itemsize == 40
 
 
+TRACE_MAX_DA = 32768
+TRACE_BEAM = np.dtype([("da", np.int32), ("first", np.int32), ("n_unknown", np.int32), ("end_class", np.int32), ("hx", np.int32),
+                       ("hy", np.int32)])                  # slamhip_trace_beam (include/slamhip.h): 6 int32, 24 bytes
+TRACE_SUMMARY = np.dtype([("n_walked", np.int32), ("n_same", np.int32), ("n_ignored", np.int32), ("n_end_hit", np.int32),
+                          ("n_blocked", np.int32), ("n_end_free", np.int32), ("unknown_cells", np.int64)])   # slamhip_trace_summary: 32 bytes
+assert TRACE_BEAM.itemsize == 24 and TRACE_SUMMARY.itemsize == 32
+
+
 def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
     """A LATTICE_SPEC from Python values (centre rounded to binary32 as f32 rounds it)."""
     c = f32(centre, (3,))
@@ -163,6 +171,8 @@ def _declare(L):
         "slamhip_debug_world_plan": (i32, [i32, i32, i64, i64, i64, i64, i32, i32, i32, P(WorldJob), i32, ip]),
         "slamhip_debug_lattice_cells": (i32, [f, fp, f, fp, i32, ip]),
         "slamhip_debug_world_pack_plan": (i32, [i32, i32, i64, i64, i32, P(i64), i32, P(i64), P(WorldJob), i32, ip]),
+        "slamhip_debug_trace_lines": (i32, [f, fp, fp, fp, i32, ip]),
+        "slamhip_debug_trace_cells": (i32, [i32, i32, i32, i32, ip, i32, ip]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -249,6 +259,7 @@ def _declare(L):
         "slamhip_hs_relocalise": (i32, [vp, lsp, i32, fp, rp, rip]),
         "slamhip_hs_world_lattice_search": (i32, [vp, lsp, u64p, ip]),
         "slamhip_hs_relocalise_world": (i32, [vp, lsp, i32, fp, rp, wrip]),
+        "slamhip_hs_trace": (i32, [vp, i32, fp, i32, i32, vp, vp]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -273,6 +284,7 @@ def _declare(L):
         "slamhip_hsproc_shift": (i32, [vp, i32, i32]),
         "slamhip_hsproc_relocalise": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, rip]),
         "slamhip_hsproc_relocalise_world": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, wrip]),
+        "slamhip_hsproc_trace": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, vp, vp]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -359,6 +371,25 @@ def lattice_cells(cell_length, centre, theta, xy):
     out = np.empty((xy.shape[0], 2), np.int32)
     call("slamhip_debug_lattice_cells", C.c_float(cell_length), fptr(c), C.c_float(theta), fptr(xy), xy.shape[0], iptr(out))
     return out
+
+
+def trace_lines(stm, pose, origin, xy):
+    """{bx, by, ex, ey, da} of every beam of `xy` for one pose of the beam trace (slamhip_debug_trace_lines; no device involved): an
+    (n, 5) int32 array; an ignored beam is (0, 0, 0, 0, -1)."""
+    xy = f32(xy, (-1, 2)); p = f32(pose, (3,)); o = f32(origin, (2,))
+    out = np.empty((xy.shape[0], 5), np.int32)
+    call("slamhip_debug_trace_lines", C.c_float(stm), fptr(p), fptr(o), fptr(xy), xy.shape[0], iptr(out))
+    return out
+
+
+def trace_cells(bx, by, ex, ey):
+    """The cells the beam trace walks from cell (bx, by) to cell (ex, ey), in order (slamhip_debug_trace_cells; no device involved):
+    a (da + 1, 2) int32 array.  A line no walked beam has raises SlamhipError (ERR_INVALID)."""
+    cap = min(max(abs(int(ex) - int(bx)), abs(int(ey) - int(by))), TRACE_MAX_DA) + 1
+    out = np.empty((max(cap, 1), 2), np.int32)
+    n = C.c_int32()
+    call("slamhip_debug_trace_cells", int(bx), int(by), int(ex), int(ey), iptr(out), out.shape[0], C.byref(n))
+    return out[:n.value]
 
 
 def check(rc):

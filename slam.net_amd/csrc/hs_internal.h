@@ -40,6 +40,7 @@ struct hs_level_dev {                      // what the kernels need, by value
 struct hs_backing;                         // hs_tiles.h
 struct hs_world;                           // hs_world.hip
 struct hs_lattice;                         // hs_lattice.hip
+struct hs_trace;                           // hs_trace.hip
 struct slamhip_hs {
     slamhip_ctx *ctx;
     int n_levels;
@@ -65,6 +66,7 @@ struct slamhip_hs {
     struct hs_backing *bk;                                 // slamhip_hs_set_backing: the tile pool and its host directory; nullptr while backing is off
     struct hs_world *wp;                                   // slamhip_hs_world_cells_upload / _world_extends: their staging buffer, made by the first call, kept
     struct hs_lattice *lat;                                // slamhip_hs_lattice_search: the class map and the result blocks, made by the first search, kept
+    struct hs_trace *trc;                                  // slamhip_hs_trace: the poses' and the results' blocks, made by the first trace, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -132,3 +134,11 @@ void    hs_bk_free(slamhip_hs *hs);         // (the caller has drained the strea
 void    hs_wp_free(slamhip_hs *hs);         // the staging buffer of the world upload and the world extents (the caller has drained the stream)
 // hs_lattice.hip
 void    hs_lat_free(slamhip_hs *hs);        // the class map and the result blocks of the pose-lattice search (the caller has drained the stream)
+// K7's class map of one level -- 2 bits per cell, rows of wpr words -- for another launch on the operator's stream: w x h cells
+// whose first is cell (x0, y0) of the window's frame (the window itself, or the world's rectangle R).  _prepare plans and
+// allocates and launches nothing; _enqueue packs.
+struct hs_class_map { const uint32_t *cls; int w, h, wpr, x0, y0; };
+int32_t hs_lat_pack_prepare(slamhip_hs *hs, int level, bool world, hs_class_map *M);
+int32_t hs_lat_pack_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M);
+// hs_trace.hip
+void    hs_trc_free(slamhip_hs *hs);        // the blocks of the beam trace (the caller has drained the stream)

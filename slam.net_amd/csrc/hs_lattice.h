@@ -10,6 +10,7 @@
 #define HS_LAT_MAX_THETA 4096
 #define HS_LAT_MAX_NODES (1 << 26)
 #define HS_LAT_IGNORED INT32_MIN           // what slamhip_debug_lattice_cells reports for an ignored point
+#define K7_RECT_WORDS 12288                // words of the class map a workgroup stages in LDS (48 KB): k7_search, and K8's k8_trace
 
 // one heading of the lattice on one level: the rotation and the centre in map coordinates
 struct hs_lat_heading { float s, c, stm, cxm, cym; };

@@ -39,7 +39,6 @@
 #include <new>
 
 #define K7_LANES 256
-#define K7_RECT_WORDS 12288                // 48 KB of class map
 #define K7_CHUNK 1024                      // points per LDS chunk (8 KB)
 // (gx, gy) of an ignored point in LDS, taken as it is (the origin is not subtracted).  The walk adds dx = ix - rx0 to it with
 // |ix| <= 4096 and 0 <= rx0 < 2^28 (a rectangle starts inside R, and R has at most 2^28 cells): the sum lies in
@@ -296,6 +295,47 @@ static int32_t hs_lat_plan_world(slamhip_hs *hs, hs_lattice *lt, int level, wpp_
     return SLAMHIP_OK;
 }
 
+// The class map of one level for a launch on the operator's stream, in two steps.  hs_lat_pack_prepare: the hs's lattice state made
+// if this is its first use, the world's plan (which refuses before anything is allocated or launched), the map's and the pieces'
+// device blocks grown.  hs_lat_pack_enqueue: the pack launch -- k7_pack for the window, the memset and k7_pack_world for the world.
+int32_t hs_lat_pack_prepare(slamhip_hs *hs, int level, bool world, hs_class_map *M)
+{
+    if (!hs->lat) {
+        hs->lat = new (std::nothrow) hs_lattice();                        // (value-initialised: nothing allocated yet)
+        if (!hs->lat) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
+    }
+    hs_lattice *lt = hs->lat;
+    if (!lt->ev) SH_HIP(hipEventCreateWithFlags(&lt->ev, hipEventDisableTiming));
+    const hs_level &L = hs->lv[level];
+    wpp_rect R = { 0, 0, L.w, L.h };                                       // what the class map covers, in the window's frame
+    if (world) SH_TRY(hs_lat_plan_world(hs, lt, level, &R));               // (refuses before anything is allocated or launched)
+    M->w = (int)R.w; M->h = (int)R.h; M->wpr = (M->w + 15) / 16;
+    M->x0 = (int)R.x0; M->y0 = (int)R.y0;
+    // (the blocks are idle: every search waits for its own launches, and a search that timed out has poisoned the context)
+    SH_TRY(hs_lat_grow((void **)&lt->d_cls, &lt->cap_cls, sizeof(uint32_t) * (size_t)M->wpr * M->h, false));
+    if (world) SH_TRY(hs_lat_grow((void **)&lt->d_pieces, &lt->cap_pieces, sizeof(k7w_piece) * lt->pieces.size(), false));
+    M->cls = lt->d_cls;
+    return SLAMHIP_OK;
+}
+
+int32_t hs_lat_pack_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M)
+{
+    slamhip_ctx *ctx = hs->ctx;
+    hs_lattice *lt = hs->lat;
+    const hs_level &L = hs->lv[level];
+    if (!world) {
+        sh_timer t(ctx, SLAMHIP_K_HS_LATTICE_PACK);
+        hipLaunchKernelGGL(k7_pack, dim3((unsigned)sh_div_up(M->wpr * L.h, 256)), dim3(256), 0, ctx->stream, (const slamhip_cell *)L.d_cells, L.w, L.h, M->wpr, lt->d_cls);
+    } else {
+        SH_HIP(hipMemsetAsync(lt->d_cls, 0, sizeof(uint32_t) * (size_t)M->wpr * M->h, ctx->stream));
+        SH_HIP(hipMemcpyAsync(lt->d_pieces, lt->pieces.data(), sizeof(k7w_piece) * lt->pieces.size(), hipMemcpyHostToDevice, ctx->stream));
+        sh_timer t(ctx, SLAMHIP_K_HS_LATTICE_PACK_WORLD);
+        hipLaunchKernelGGL(k7_pack_world, dim3((unsigned)lt->pieces.size()), dim3(K7W_LANES), 0, ctx->stream, (const k7w_piece *)lt->d_pieces, M->wpr, lt->d_cls);
+    }
+    SH_HIP(hipGetLastError());
+    return SLAMHIP_OK;
+}
+
 // The search into the library's pinned block: *keys (n_theta) and, if asked for, *scores point into it and stay valid until the
 // next search of this hs.  world: the class map covers the window and the level's tiles (k7_pack_world) instead of the window.
 static int32_t hs_lat_run(slamhip_hs *hs, const slamhip_lattice_spec *S, bool want_scores, bool world, const uint64_t **keys, const int32_t **scores)
@@ -305,41 +345,23 @@ static int32_t hs_lat_run(slamhip_hs *hs, const slamhip_lattice_spec *S, bool wa
     slamhip_ctx *ctx = hs->ctx;
     if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
     SH_HIP(hipSetDevice(ctx->device));
-    if (!hs->lat) {
-        hs->lat = new (std::nothrow) hs_lattice();                        // (value-initialised: nothing allocated yet)
-        if (!hs->lat) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-    }
+    hs_class_map M;
+    SH_TRY(hs_lat_pack_prepare(hs, S->level, world, &M));
     hs_lattice *lt = hs->lat;
-    if (!lt->ev) SH_HIP(hipEventCreateWithFlags(&lt->ev, hipEventDisableTiming));
     const hs_level &L = hs->lv[S->level];
-    wpp_rect R = { 0, 0, L.w, L.h };                                       // what the class map covers, in the window's frame
-    if (world) SH_TRY(hs_lat_plan_world(hs, lt, S->level, &R));            // (refuses before anything is allocated or launched)
-    const int mw = (int)R.w, mh = (int)R.h, wpr = (mw + 15) / 16;
-    const size_t cls_bytes = sizeof(uint32_t) * (size_t)wpr * mh;
     const int NX = 2 * S->nx + 1, NY = 2 * S->ny + 1;
     const size_t key_bytes = sizeof(uint64_t) * (size_t)S->n_theta;
     const size_t out_bytes = key_bytes + (want_scores ? sizeof(int32_t) * (size_t)S->n_theta * NX * NY : 0);
     // (the blocks are idle: every search waits for its own launches, and a search that timed out has poisoned the context)
-    SH_TRY(hs_lat_grow((void **)&lt->d_cls, &lt->cap_cls, cls_bytes, false));
-    if (world) SH_TRY(hs_lat_grow((void **)&lt->d_pieces, &lt->cap_pieces, sizeof(k7w_piece) * lt->pieces.size(), false));
     SH_TRY(hs_lat_grow((void **)&lt->d_out, &lt->cap_out, out_bytes, false));
     SH_TRY(hs_lat_grow((void **)&lt->h_out, &lt->cap_h, out_bytes, true));
     SH_TRY(hs_flush_scan(hs));
     SH_HIP(hipMemsetAsync(lt->d_out, 0, key_bytes, ctx->stream));
-    if (!world) {
-        sh_timer t(ctx, SLAMHIP_K_HS_LATTICE_PACK);
-        hipLaunchKernelGGL(k7_pack, dim3((unsigned)sh_div_up(wpr * L.h, 256)), dim3(256), 0, ctx->stream, (const slamhip_cell *)L.d_cells, L.w, L.h, wpr, lt->d_cls);
-    } else {
-        SH_HIP(hipMemsetAsync(lt->d_cls, 0, cls_bytes, ctx->stream));
-        SH_HIP(hipMemcpyAsync(lt->d_pieces, lt->pieces.data(), sizeof(k7w_piece) * lt->pieces.size(), hipMemcpyHostToDevice, ctx->stream));
-        sh_timer t(ctx, SLAMHIP_K_HS_LATTICE_PACK_WORLD);
-        hipLaunchKernelGGL(k7_pack_world, dim3((unsigned)lt->pieces.size()), dim3(K7W_LANES), 0, ctx->stream, (const k7w_piece *)lt->d_pieces, wpr, lt->d_cls);
-    }
-    SH_HIP(hipGetLastError());
+    SH_TRY(hs_lat_pack_enqueue(hs, S->level, world, &M));
     k7_arg A;
     A.pts = hs->d_pts; A.n = hs->n_points;
-    A.cls = lt->d_cls; A.w = mw; A.h = mh; A.wpr = wpr;
-    A.x0 = (int)R.x0; A.y0 = (int)R.y0;
+    A.cls = M.cls; A.w = M.w; A.h = M.h; A.wpr = M.wpr;
+    A.x0 = M.x0; A.y0 = M.y0;
     A.stm = L.stm;
     A.S = *S;
     A.txl = NX > 32 ? 6 : 4;                                               // 64 x 4 translations per workgroup; a narrow lattice 16 x 16

@@ -261,6 +261,30 @@ extern "C" int32_t slamhip_hsproc_relocalise_world(slamhip_hsproc *p, const floa
     return SLAMHIP_OK;
 }
 
+// The beam trace at world poses: the scan set, every pose taken to the window's frame as slamhip_hsproc_relocalise takes its centre.
+// Nothing of the processor's own state is read or written beyond the window's origin.
+extern "C" int32_t slamhip_hsproc_trace(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float *poses_world, int32_t B,
+                                        int32_t level, int32_t world, slamhip_trace_summary *out_summaries, slamhip_trace_beam *out_beams)
+{
+    SH_CHECK_ARG(p && poses_world && out_summaries);
+    // (what slamhip_hs_trace refuses for its arguments alone, ahead of the scan: a refused call leaves the scan that was set)
+    if (level < 0 || level >= p->hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: level %d of %d", level, p->hs->n_levels);
+    if (B < 1 || B > 65536) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: B = %d must lie in [1, 65536]", B);
+    if (world != 0 && world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: world = %d must be 0 (the window) or 1 (the world)", world);
+    if (out_beams && n > 0 && (int64_t)B * n > ((int64_t)1 << 20))
+        SH_FAIL(SLAMHIP_ERR_INVALID, "trace: per-beam records of %d poses x %d points, more than 2^20", B, n);
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    if (p->hs->win_ox == 0 && p->hs->win_oy == 0) return slamhip_hs_trace(p->hs, level, poses_world, B, world, out_summaries, out_beams);
+    float off[2];
+    hsproc_window_offset(p, off);
+    float *w = (float *)malloc(sizeof(float) * 3 * (size_t)B);
+    if (!w) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
+    for (int i = 0; i < B; i++) { w[3 * i] = poses_world[3 * i] - off[0]; w[3 * i + 1] = poses_world[3 * i + 1] - off[1]; w[3 * i + 2] = poses_world[3 * i + 2]; }
+    const int32_t rc = slamhip_hs_trace(p->hs, level, w, B, world, out_summaries, out_beams);
+    free(w);
+    return rc;
+}
+
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)
 {
     SH_CHECK_ARG(p);

@@ -322,6 +322,41 @@ class MapRepMultiMap:
     def set_scan(self, scan):
         org = capi.f32(scan.Pose[:2])
         capi.call("slamhip_hs_set_scan", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org))
+        self._scan_set = (scan.Points.shape[0], org.copy())
+
+    def trace(self, poses, level, world=False, beams=False, scan=None):
+        """The beam trace (slamhip_hs_trace; no reference counterpart): what the map of `level` holds ALONG every beam of the scan
+        from each of the B `poses` ((B, 3), window frame) -- the grid update's own line from the sensor cell to the beam's end cell,
+        the class of every cell on it.  -> (summaries, beams | None): summaries (B,) of capi.TRACE_SUMMARY; beams the (B, n_points)
+        capi.TRACE_BEAM records when asked for (B * n_points <= 2^20).  world=True: a cell outside the window is the cell of the tile
+        that holds it instead of nothing.  Blocking, behind everything already enqueued; it changes nothing.  scan = None: the scan
+        already set through this object."""
+        if scan is not None:
+            self.set_scan(scan)
+        p = capi.f32(poses, (-1, 3))
+        sums = np.zeros(p.shape[0], capi.TRACE_SUMMARY)
+        rec = None
+        if beams:
+            if self._scan_set is None:
+                raise ValueError("trace: beams=True needs the scan set through this object (set_scan, or scan=)")
+            rec = np.zeros((p.shape[0], self._scan_set[0]), capi.TRACE_BEAM)
+        capi.call("slamhip_hs_trace", self._h, int(level), capi.fptr(p), p.shape[0], 1 if world else 0, sums.ctypes.data_as(C.c_void_p),
+                  rec.ctypes.data_as(C.c_void_p) if beams else None)
+        return sums, rec
+
+    def ExpectedScan(self, pose, angles, max_range, level, world=False):
+        """The scan the map of `level` predicts from `pose` (window frame): per angle (rad, sensor frame) the range in metres to the
+        first occupied cell on the beam of length max_range, or inf where the map holds none.  It REPLACES the scan that was set:
+        far points at max_range, the scan origin at the sensor, traced with trace(beams=True); the range is
+        hypot(hx - bx, hy - by) * CellLength, formed on the host in float64 from the hit cell and the sensor's cell."""
+        a = np.asarray(angles, np.float64).reshape(-1)
+        pts = (float(max_range) * np.stack([np.cos(a), np.sin(a)], 1)).astype(np.float32)
+        _, rec = self.trace(np.asarray(pose, np.float32).reshape(1, 3), level, world=world, beams=True, scan=ScanCloud(pts))
+        cell = np.float32(self.Maps[level].CellLength)
+        b = capi.trace_lines(np.float32(1.0) / cell, pose, (0.0, 0.0), [[0.0, 0.0]])[0]          # (the sensor's own cell)
+        r = rec[0]
+        d = np.hypot(r["hx"].astype(np.float64) - float(b[0]), r["hy"].astype(np.float64) - float(b[1])) * float(cell)
+        return np.where(r["first"] >= 0, d, np.inf)
 
     def UpdateByScan(self, scan, pose):
         self.set_scan(scan)
@@ -499,6 +534,7 @@ class HectorSLAMProcessor:
         out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); info = capi.RelocInfo()
         capi.call("slamhip_hsproc_relocalise", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), C.byref(spec),
                   int(B), 1 if adopt else 0, capi.fptr(out), capi.rptr(r), C.byref(info))
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
         return out, r[0], _reloc_info(info)
 
     def RelocaliseWorld(self, scan, centreWorld, level, nx, ny, n_theta, dtheta, B=16, adopt=True):
@@ -512,7 +548,20 @@ class HectorSLAMProcessor:
         out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); info = capi.WorldRelocInfo()
         capi.call("slamhip_hsproc_relocalise_world", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), C.byref(spec),
                   int(B), 1 if adopt else 0, capi.fptr(out), capi.rptr(r), C.byref(info))
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
         return out, r[0], _world_reloc_info(info)
+
+    def Trace(self, scan, posesWorld, level, world=False, beams=False):
+        """MapRep.trace of `scan` at WORLD poses (slamhip_hsproc_trace): the poses are taken to the window's frame as Relocalise takes
+        its centre.  -> (summaries, beams | None); hx, hy of a beam record stay window-frame cells of `level` (get_origin converts:
+        world cell = (origin >> level) + cell).  MatchPose, LastMapUpdatePose and the update gate are untouched."""
+        p = capi.f32(posesWorld, (-1, 3)); org = capi.f32(scan.Pose[:2])
+        sums = np.zeros(p.shape[0], capi.TRACE_SUMMARY)
+        rec = np.zeros((p.shape[0], scan.Points.shape[0]), capi.TRACE_BEAM) if beams else None
+        capi.call("slamhip_hsproc_trace", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), capi.fptr(p), p.shape[0],
+                  int(level), 1 if world else 0, sums.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p) if beams else None)
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
+        return sums, rec
 
     MatchPose = property(lambda self: self._get()[0])
     LastMapUpdatePose = property(lambda self: self._get()[1])
@@ -549,6 +598,7 @@ class HectorSLAMProcessor:
         hint = capi.f32(poseHintWorld); org = capi.f32(scan.Pose[:2]); upd = C.c_int32()
         capi.call("slamhip_hsproc_update", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org),
                   capi.fptr(hint), 1 if mapWithoutMatching else 0, C.byref(upd))
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())      # (what MapRep.trace sizes its beam records by)
         return bool(upd.value)
 
     def Reset(self):
