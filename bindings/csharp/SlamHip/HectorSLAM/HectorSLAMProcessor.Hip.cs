@@ -210,6 +210,22 @@ namespace HectorSLAM.Main
             return sums;
         }
 
+        /// <summary>MapRep.DistanceScore of `scan` at WORLD poses (slamhip_hsproc_distance_score): per pose how far the scan's end
+        /// points lie from the sites of `level` (siteMask 2: mapped obstacles), in squared cells capped at radius^2, and when asked
+        /// for the values [pose][point].  MatchPose, LastMapUpdatePose and the update gate are untouched.</summary>
+        public unsafe DistanceSummary[] DistanceScore(ScanCloud scan, Vector3[] posesWorld, int level, int siteMask, int radius, bool world, bool wantPoints, out ushort[] points)
+        {
+            var sums = new DistanceSummary[posesWorld.Length];
+            points = wantPoints ? new ushort[(long)posesWorld.Length * scan.Points.Count] : null;
+            fixed (Vector2* p = CollectionsMarshal.AsSpan(scan.Points))
+            fixed (Vector3* q = posesWorld)
+            fixed (DistanceSummary* s = sums)
+            fixed (ushort* d = points)
+                Native.Check(Native.slamhip_hsproc_distance_score(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), q, posesWorld.Length, level, world ? 1 : 0,
+                                                                  siteMask, radius, s, d));
+            return sums;
+        }
+
         private void Refresh()
         {
             Native.Check(Native.slamhip_hsproc_get(proc.Ptr, out Vector3 match, out Vector3 last, out float tm, out float tu));

@@ -188,6 +188,45 @@ namespace HectorSLAM.Main
             return cells;
         }
 
+        /// <summary>The distance field (slamhip_hs_distance_field; the reference has no counterpart): for every cell of the rectangle
+        /// (x, y, w, h), window-frame cells of `level`, the squared cell distance to the nearest site, capped at radius^2; [row * w +
+        /// column].  A site is a cell whose class siteMask selects: bit 0 unknown, bit 1 occupied, bit 2 free (2: distance to
+        /// obstacles).  radius in [1, 255].  world: a cell outside the window is the cell of the backing store's tile that holds it.
+        /// Blocking; it changes nothing.</summary>
+        public unsafe ushort[] DistanceField(int level, int x, int y, int w, int h, int siteMask = 2, int radius = 32, bool world = false)
+        {
+            var d2 = new ushort[(long)Math.Max(w, 0) * Math.Max(h, 0)];
+            fixed (ushort* d = d2)
+                Native.Check(Native.slamhip_hs_distance_field(Pyramid.Ptr, level, world ? 1 : 0, siteMask, radius, x, y, w, h, d));
+            return d2;
+        }
+
+        /// <summary>The end-point distance score (slamhip_hs_distance_score): the field's value at the end cell of every point of
+        /// `scan` at each of the poses (window frame).  Returns one summary per pose and, when asked for, the values [pose][point]
+        /// (0xFFFF for an ignored point; poses x points at most 2^22).</summary>
+        public unsafe DistanceSummary[] DistanceScore(ScanCloud scan, Vector3[] poses, int level, int siteMask, int radius, bool world, bool wantPoints, out ushort[] points)
+        {
+            SetScan(scan);
+            var sums = new DistanceSummary[poses.Length];
+            points = wantPoints ? new ushort[(long)poses.Length * scan.Points.Count] : null;
+            fixed (Vector3* p = poses)
+            fixed (DistanceSummary* s = sums)
+            fixed (ushort* q = points)
+                Native.Check(Native.slamhip_hs_distance_score(Pyramid.Ptr, level, world ? 1 : 0, siteMask, radius, p, poses.Length, s, q));
+            return sums;
+        }
+
+        /// <summary>The field of the definition over a caller's class array on the host (slamhip_debug_distance_field): cls is ch rows
+        /// of cw class bytes (1 occupied, 2 free, 0 neither), class 0 outside.</summary>
+        public static unsafe ushort[] DistanceFieldOf(byte[] cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h)
+        {
+            var d2 = new ushort[(long)Math.Max(w, 0) * Math.Max(h, 0)];
+            fixed (byte* c = cls)
+            fixed (ushort* d = d2)
+                Native.Check(Native.slamhip_debug_distance_field(c, cw, ch, siteMask, radius, x, y, w, h, d));
+            return d2;
+        }
+
         /// <summary>The sum of all shifts since construction or the last Reset, in level-0 cells (slamhip_hs_origin).</summary>
         public (long X, long Y) Origin
         {

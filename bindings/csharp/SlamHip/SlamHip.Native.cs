@@ -120,6 +120,17 @@ namespace SlamHip
         public long UnknownCells;
     }
 
+    /// <summary>slamhip_distance_summary (include/slamhip.h): one pose's scan points against the distance field -- counted and
+    /// ignored points, those whose end cell is a site (ZeroCount), those with no site within the radius (CappedCount), and the sum
+    /// of the squared cell distances of the counted points.  4 ints and a long, 24 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct DistanceSummary
+    {
+        public int CountedCount, IgnoredCount;
+        public int ZeroCount, CappedCount;
+        public long SumD2;
+    }
+
     internal static unsafe class Native
     {
         const string Lib = "slamhip";                                   // libslamhip.so on the library path
@@ -212,6 +223,11 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_trace(IntPtr hs, int level, Vector3* poses, int nPoses, int world, TraceSummary* summaries, TraceBeam* beams);
         [DllImport(Lib)] internal static extern int slamhip_debug_trace_lines(float scaleToMap, in Vector3 pose, in Vector2 origin, Vector2* xy, int n, int* lines);
         [DllImport(Lib)] internal static extern int slamhip_debug_trace_cells(int bx, int by, int ex, int ey, int* cells, int cap, out int n);
+        // the distance field and the end-point distance score (no reference counterpart), and the field's host-side hook
+        [DllImport(Lib)] internal static extern int slamhip_hs_distance_field(IntPtr hs, int level, int world, int siteMask, int radius, int x, int y, int w, int h, ushort* d2);
+        [DllImport(Lib)] internal static extern int slamhip_hs_distance_score(IntPtr hs, int level, int world, int siteMask, int radius, Vector3* poses, int nPoses,
+                                                                              DistanceSummary* summaries, ushort* points);
+        [DllImport(Lib)] internal static extern int slamhip_debug_distance_field(byte* cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h, ushort* d2);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_match_threads(IntPtr hs, int numThreads);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_reference_cache(IntPtr hs, int on);
         [DllImport(Lib)] internal static extern int slamhip_hs_update_by_scan(IntPtr hs, in Vector3 robotPoseWorld);
@@ -242,6 +258,8 @@ namespace SlamHip
                                                                               out Vector3 poseWorld, out MatchReport report, out RelocInfo info);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_trace(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int world,
                                                                          TraceSummary* summaries, TraceBeam* beams);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_distance_score(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int world,
+                                                                                  int siteMask, int radius, DistanceSummary* summaries, ushort* pointD2);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_relocalise_world(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in LatticeSpec specWorld, int maxHints, int adopt,
                                                                                     out Vector3 poseWorld, out MatchReport report, out WorldRelocInfo info);
 

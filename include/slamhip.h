@@ -169,6 +169,15 @@ int32_t slamhip_debug_world_pack_plan(int32_t w, int32_t h, int64_t OX, int64_t 
 int32_t slamhip_debug_trace_lines(float stm, const float pose[3], const float origin[2], const float *xy, int32_t n, int32_t *out);
 int32_t slamhip_debug_trace_cells(int32_t bx, int32_t by, int32_t ex, int32_t ey, int32_t *out_xy, int32_t cap, int32_t *out_n);
 
+/* Test hook (no device involved): the distance field (slamhip_hs_distance_field, THE DEFINITION there) over a caller's class array,
+ * by the text the kernels run (the class-to-site test, the nearest site of a row by word, the column minimum).  cls: ch rows of cw
+ * bytes of class bits (1 occupied, 2 free, 0 neither; only the low two bits are read), cell (0, 0) first; every cell outside
+ * [0, cw) x [0, ch) is class 0.  out_d2: h rows of w uint16_t, the field of cells [x, x + w) x [y, y + h) -- any rectangle, the
+ * constant outside E included.  SLAMHIP_ERR_INVALID: site_mask outside [1, 7], radius outside [1, 255], w or h < 1, w * h > 2^24,
+ * cw or ch < 1, cw * ch > 2^26. */
+int32_t slamhip_debug_distance_field(const uint8_t *cls, int32_t cw, int32_t ch, int32_t site_mask, int32_t radius,
+                                     int32_t x, int32_t y, int32_t w, int32_t h, uint16_t *out_d2);
+
 /* Kernel timing (the reference only has Stopwatch EMAs, HectorSLAMProcessor.cs:92-96,111-115).
  * When enabled, each kernel class is bracketed by HIP events on the context's stream. */
 enum {
@@ -773,6 +782,59 @@ typedef struct slamhip_trace_summary {
 int32_t slamhip_hs_trace(slamhip_hs *hs, int32_t level, const float *poses, int32_t B, int32_t world,
                          slamhip_trace_summary *out_summaries, slamhip_trace_beam *out_beams);
 
+/* The distance field of the map and the end-point distance score (K9; no reference counterpart): how far every cell of ONE
+ * level lies from the nearest mapped obstacle (or free cell, or unknown cell), as exact squared cell distances, and how far the end
+ * points of the scan lie from them at many poses -- the likelihood-field (end-point) model's raw material, smooth in the pose where
+ * the lattice search's exact-cell score drops to zero one cell off the wall; the same field gives clearance for obstacle inflation
+ * and, with bit 0 of the site mask, the distance to the unknown.
+ * THE DEFINITION, for level L, world in {0, 1}, site_mask in [1, 7] and radius r in [1, 255]:
+ *  1. cls(x, y), the class of window-frame cell (x, y) of level L, is the beam trace's rule in class bits: 1 occupied (Value >
+ *     0.0f), 2 free (Value < 0.0f), 0 neither.  Window variant: a cell outside [0, w) x [0, h) has class 0.  World variant: such a
+ *     cell has the class of world cell ((ox >> L) + x, (oy >> L) + y): the tile's cell if a tile of the backing store holds it,
+ *     else 0.
+ *  2. A cell is a SITE iff bit cls(x, y) of site_mask is set: bit 0 unknown, bit 1 occupied, bit 2 free.  site_mask = 2 is "distance
+ *     to obstacles", 3 "to obstacles or the unknown", 1 "to the unknown", 7 makes every cell a site.
+ *  3. D2(x, y) = min over all sites (sx, sy) of (sx - x)^2 + (sy - y)^2, and the field is F(x, y) = min(D2(x, y), r^2), a uint16_t
+ *     (r^2 <= 65025), defined for EVERY integer cell of the plane.  It is exact: a site with |dx| > r or |dy| > r has a squared
+ *     distance above r^2 and cannot lower F, so looking only r cells each way is no approximation.
+ *  4. Where it is computed.  Let M = (x0, y0, w, h) be the rectangle of the class map -- the window, or the world's rectangle R (the
+ *     bounding box of the window and of every tile of the level) -- and E be M grown by r cells on every side.  Every cell outside
+ *     M is class 0.  A cell outside E is more than r cells from M on one axis, so no site INSIDE M reaches it; all other cells are
+ *     class 0, sites iff bit 0 of site_mask is set, and then the cell itself is one.  Hence outside E, F is the constant
+ *     (site_mask & 1) ? 0 : r^2.  The device field covers E only, and both calls return that constant outside E.
+ *  5. The end cell of a scan point at a pose P = (x, y, theta) in the WINDOW's frame, as slamhip_hs_update_by_scan takes it:
+ *     t = Rotation(theta) * Translation(x, y) * Scale(stm) as the beam trace forms it, (exf, eyf) = Transform(point, t),
+ *     e = (int)rintf(.), banker's rounding: the cell the grid update would mark.  The point is IGNORED unless both floats satisfy
+ *     fabsf(f) < 16777216.0f (a NaN fails); a NaN point or pose is ignored and is no error.  The scan origin plays no part: a beam
+ *     that the trace ignores for its origin, or for its length, still counts here.
+ *  6. Per pose, slamhip_distance_summary over F(e) of the counted points.  The library sets no threshold. */
+typedef struct slamhip_distance_summary {
+    int32_t n_counted, n_ignored;      /* sum to n_points */
+    int32_t n_zero;                    /* counted points whose end cell is a site (F == 0) */
+    int32_t n_capped;                  /* counted points with F == r*r: no site within the radius */
+    int64_t sum_d2;                    /* sum of F over the counted points */
+} slamhip_distance_summary;            /* 4 int32 + 1 int64: 24 bytes, no padding */
+/* The field of a rectangle: x, y, w, h in window-frame cells of the level, any position (the constant outside E); out_d2: h rows of
+ * w uint16_t.  The launches, on the operator's stream behind every grid update, shift and upload already enqueued: the lattice
+ * search's class map of the level, re-packed on every call (as slamhip_hs_trace packs it), the two launches of the field over E
+ * (rows, then columns) and a gather of the rectangle: E itself is never downloaded.  The blocks belong to the hs, are made by the
+ * first call and freed by slamhip_hs_destroy; an hs that never asks allocates nothing.  Blocking, with the context's bounded wait;
+ * the result comes back through pinned staging that the library owns.  It reads cell values only, so it works with backing off
+ * (world = window), with slamhip_hs_set_reference_cache on, and after shifts; it changes nothing of the map or of any search.
+ * SLAMHIP_ERR_INVALID, nothing launched: level out of range, world not 0 or 1, site_mask outside [1, 7], radius outside [1, 255],
+ * w or h < 1, w * h > 2^24 (32 MB of staging), E over 2^26 cells (1 + 2 bytes per cell: 192 MB; the message gives E's size, and
+ * for the world this is known only once the world is planned).  A poisoned context: SLAMHIP_ERR_TIMEOUT.  The limits are design
+ * conditions, not measurements. */
+int32_t slamhip_hs_distance_field(slamhip_hs *hs, int32_t level, int32_t world, int32_t site_mask, int32_t radius,
+                                  int32_t x, int32_t y, int32_t w, int32_t h, uint16_t *out_d2);
+/* The end-point distance score of the scan that was set, at B poses (poses: B x 3 floats, window frame).  out_summaries: B records.
+ * out_points: NULL, or B x n_points uint16_t, pose-major: F of the point's end cell, 0xFFFF for an ignored point.  The field is
+ * built as for slamhip_hs_distance_field on every call, behind a memset of the summaries; then ONE score launch, a point per lane.
+ * Everything else as slamhip_hs_distance_field.  SLAMHIP_ERR_INVALID in addition: B outside [1, 65536], out_points given with
+ * B * n_points > 2^22.  SLAMHIP_ERR_STATE: no scan. */
+int32_t slamhip_hs_distance_score(slamhip_hs *hs, int32_t level, int32_t world, int32_t site_mask, int32_t radius,
+                                  const float *poses, int32_t B, slamhip_distance_summary *out_summaries, uint16_t *out_points);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -952,6 +1014,15 @@ int32_t slamhip_hsproc_relocalise_world(slamhip_hsproc *p, const float *xy, int3
 int32_t slamhip_hsproc_trace(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
                              const float *poses_world, int32_t B, int32_t level, int32_t world,
                              slamhip_trace_summary *out_summaries, slamhip_trace_beam *out_beams);
+/* The end-point distance score through the processor: slamhip_hs_set_scan on the processor's own hs, then
+ * slamhip_hs_distance_score at the B poses of poses_world (B x 3, WORLD frame), each taken to the window's frame as
+ * slamhip_hsproc_trace takes them (- (float)origin * cell0 per axis; the bits themselves while the origin is 0).  The processor's
+ * stored poses, its update gate and its match report are not touched; the scan that was set is replaced.  Errors as
+ * slamhip_hs_distance_score; a call refused for its level, world, site_mask, radius, B or the 2^22 records leaves the scan that was
+ * set (E's size is known only once the field is planned, behind the new scan). */
+int32_t slamhip_hsproc_distance_score(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
+                                      const float *poses_world, int32_t B, int32_t level, int32_t world, int32_t site_mask,
+                                      int32_t radius, slamhip_distance_summary *out_summaries, uint16_t *out_points);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -110,6 +110,10 @@ TRACE_BEAM = np.dtype([("da", np.int32), ("first", np.int32), ("n_unknown", np.i
 TRACE_SUMMARY = np.dtype([("n_walked", np.int32), ("n_same", np.int32), ("n_ignored", np.int32), ("n_end_hit", np.int32),
                           ("n_blocked", np.int32), ("n_end_free", np.int32), ("unknown_cells", np.int64)])   # slamhip_trace_summary: 32 bytes
 assert TRACE_BEAM.itemsize == 24 and TRACE_SUMMARY.itemsize == 32
+DISTANCE_SUMMARY = np.dtype([("n_counted", np.int32), ("n_ignored", np.int32), ("n_zero", np.int32), ("n_capped", np.int32),
+                             ("sum_d2", np.int64)])            # slamhip_distance_summary (include/slamhip.h): 4 int32 + 1 int64, 24 bytes
+assert DISTANCE_SUMMARY.itemsize == 24
+DISTANCE_IGNORED = 0xFFFF                                      # the per-point record of an ignored point
 
 
 def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
@@ -173,6 +177,7 @@ def _declare(L):
         "slamhip_debug_world_pack_plan": (i32, [i32, i32, i64, i64, i32, P(i64), i32, P(i64), P(WorldJob), i32, ip]),
         "slamhip_debug_trace_lines": (i32, [f, fp, fp, fp, i32, ip]),
         "slamhip_debug_trace_cells": (i32, [i32, i32, i32, i32, ip, i32, ip]),
+        "slamhip_debug_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -260,6 +265,8 @@ def _declare(L):
         "slamhip_hs_world_lattice_search": (i32, [vp, lsp, u64p, ip]),
         "slamhip_hs_relocalise_world": (i32, [vp, lsp, i32, fp, rp, wrip]),
         "slamhip_hs_trace": (i32, [vp, i32, fp, i32, i32, vp, vp]),
+        "slamhip_hs_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "slamhip_hs_distance_score": (i32, [vp, i32, i32, i32, i32, fp, i32, vp, vp]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -285,6 +292,7 @@ def _declare(L):
         "slamhip_hsproc_relocalise": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, rip]),
         "slamhip_hsproc_relocalise_world": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, wrip]),
         "slamhip_hsproc_trace": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, vp, vp]),
+        "slamhip_hsproc_distance_score": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -390,6 +398,18 @@ def trace_cells(bx, by, ex, ey):
     n = C.c_int32()
     call("slamhip_debug_trace_cells", int(bx), int(by), int(ex), int(ey), iptr(out), out.shape[0], C.byref(n))
     return out[:n.value]
+
+
+def debug_distance_field(cls, site_mask, radius, rect):
+    """The distance field of the definition (slamhip_hs_distance_field) over the (h, w) uint8 array `cls` of class bits, class 0
+    outside it, for rect = (x, y, w, h) in the array's cells (slamhip_debug_distance_field; no device involved): an (h, w) uint16
+    array of squared cell distances capped at radius^2."""
+    c = np.ascontiguousarray(cls, np.uint8)
+    x, y, w, h = (int(v) for v in rect)
+    out = np.empty((max(h, 0), max(w, 0)), np.uint16)
+    call("slamhip_debug_distance_field", c.ctypes.data_as(C.c_void_p), c.shape[1], c.shape[0], int(site_mask), int(radius), x, y, w, h,
+         out.ctypes.data_as(C.c_void_p))
+    return out
 
 
 def check(rc):

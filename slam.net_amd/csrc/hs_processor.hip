@@ -285,6 +285,34 @@ extern "C" int32_t slamhip_hsproc_trace(slamhip_hsproc *p, const float *xy, int3
     return rc;
 }
 
+// The end-point distance score at world poses: slamhip_hsproc_trace's shape -- the arguments checked ahead of the scan, the scan
+// set, every pose taken to the window's frame.
+extern "C" int32_t slamhip_hsproc_distance_score(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float *poses_world, int32_t B,
+                                                 int32_t level, int32_t world, int32_t site_mask, int32_t radius,
+                                                 slamhip_distance_summary *out_summaries, uint16_t *out_points)
+{
+    SH_CHECK_ARG(p && poses_world && out_summaries);
+    // (what slamhip_hs_distance_score refuses for its arguments alone, ahead of the scan: a refused call leaves the scan that was set)
+    if (level < 0 || level >= p->hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: level %d of %d", level, p->hs->n_levels);
+    if (world != 0 && world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: world = %d must be 0 (the window) or 1 (the world)", world);
+    if (site_mask < 1 || site_mask > 7) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: site_mask = %d must lie in [1, 7]", site_mask);
+    if (radius < 1 || radius > 255) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: radius = %d must lie in [1, 255]", radius);
+    if (B < 1 || B > 65536) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: B = %d must lie in [1, 65536]", B);
+    if (out_points && n > 0 && (int64_t)B * n > ((int64_t)1 << 22))
+        SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: per-point records of %d poses x %d points, more than 2^22", B, n);
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    if (p->hs->win_ox == 0 && p->hs->win_oy == 0)
+        return slamhip_hs_distance_score(p->hs, level, world, site_mask, radius, poses_world, B, out_summaries, out_points);
+    float off[2];
+    hsproc_window_offset(p, off);
+    float *w = (float *)malloc(sizeof(float) * 3 * (size_t)B);
+    if (!w) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
+    for (int i = 0; i < B; i++) { w[3 * i] = poses_world[3 * i] - off[0]; w[3 * i + 1] = poses_world[3 * i + 1] - off[1]; w[3 * i + 2] = poses_world[3 * i + 2]; }
+    const int32_t rc = slamhip_hs_distance_score(p->hs, level, world, site_mask, radius, w, B, out_summaries, out_points);
+    free(w);
+    return rc;
+}
+
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)
 {
     SH_CHECK_ARG(p);

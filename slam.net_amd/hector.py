@@ -344,6 +344,37 @@ class MapRepMultiMap:
                   rec.ctypes.data_as(C.c_void_p) if beams else None)
         return sums, rec
 
+    def distance_field(self, level, rect, site_mask=2, radius=32, world=False):
+        """The distance field of `level` (slamhip_hs_distance_field; no reference counterpart): for every cell of rect = (x, y, w, h),
+        window-frame cells of the level, the squared cell distance to the nearest site, capped at radius^2 -> (h, w) uint16.  A site
+        is a cell whose class is selected by site_mask: bit 0 unknown, bit 1 occupied, bit 2 free (2: distance to obstacles, 1: to the
+        unknown).  radius in [1, 255].  world=True: a cell outside the window is the cell of the tile that holds it.  rect may lie
+        anywhere.  Blocking, behind everything already enqueued; it changes nothing."""
+        x, y, w, h = (int(v) for v in rect)
+        out = np.empty((max(h, 0), max(w, 0)), np.uint16)
+        capi.call("slamhip_hs_distance_field", self._h, int(level), 1 if world else 0, int(site_mask), int(radius), x, y, w, h,
+                  out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def distance_score(self, poses, level, site_mask=2, radius=32, world=False, points=False, scan=None):
+        """The end-point distance score (slamhip_hs_distance_score): for each of the B `poses` ((B, 3), window frame) the field's
+        value at the end cell of every scan point.  -> (summaries, points | None): summaries (B,) of capi.DISTANCE_SUMMARY
+        (sum_d2 / n_counted is the mean squared cell distance of the scan's end points from the sites); points the (B, n_points)
+        uint16 values when asked for, capi.DISTANCE_IGNORED for an ignored point (B * n_points <= 2^22).  scan = None: the scan
+        already set through this object."""
+        if scan is not None:
+            self.set_scan(scan)
+        p = capi.f32(poses, (-1, 3))
+        sums = np.zeros(p.shape[0], capi.DISTANCE_SUMMARY)
+        rec = None
+        if points:
+            if self._scan_set is None:
+                raise ValueError("distance_score: points=True needs the scan set through this object (set_scan, or scan=)")
+            rec = np.zeros((p.shape[0], self._scan_set[0]), np.uint16)
+        capi.call("slamhip_hs_distance_score", self._h, int(level), 1 if world else 0, int(site_mask), int(radius), capi.fptr(p), p.shape[0],
+                  sums.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p) if points else None)
+        return sums, rec
+
     def ExpectedScan(self, pose, angles, max_range, level, world=False):
         """The scan the map of `level` predicts from `pose` (window frame): per angle (rad, sensor frame) the range in metres to the
         first occupied cell on the beam of length max_range, or inf where the map holds none.  It REPLACES the scan that was set:
@@ -560,6 +591,18 @@ class HectorSLAMProcessor:
         rec = np.zeros((p.shape[0], scan.Points.shape[0]), capi.TRACE_BEAM) if beams else None
         capi.call("slamhip_hsproc_trace", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), capi.fptr(p), p.shape[0],
                   int(level), 1 if world else 0, sums.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p) if beams else None)
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
+        return sums, rec
+
+    def DistanceScore(self, scan, posesWorld, level, site_mask=2, radius=32, world=False, points=False):
+        """MapRep.distance_score of `scan` at WORLD poses (slamhip_hsproc_distance_score): the poses are taken to the window's frame
+        as Trace takes them.  -> (summaries, points | None).  MatchPose, LastMapUpdatePose and the update gate are untouched."""
+        p = capi.f32(posesWorld, (-1, 3)); org = capi.f32(scan.Pose[:2])
+        sums = np.zeros(p.shape[0], capi.DISTANCE_SUMMARY)
+        rec = np.zeros((p.shape[0], scan.Points.shape[0]), np.uint16) if points else None
+        capi.call("slamhip_hsproc_distance_score", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), capi.fptr(p), p.shape[0],
+                  int(level), 1 if world else 0, int(site_mask), int(radius), sums.ctypes.data_as(C.c_void_p),
+                  rec.ctypes.data_as(C.c_void_p) if points else None)
         self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
         return sums, rec
 
