@@ -226,6 +226,30 @@ namespace HectorSLAM.Main
             return sums;
         }
 
+        /// <summary>MapRep.Frontiers in WORLD cells of `level` (slamhip_hsproc_frontiers): seeds, boxes, sums and the summary's map
+        /// rectangle are world cells.  centroids receives each cluster's centre in metres, world frame: the mean cell taken to the
+        /// window's frame of the level, through the level's cell-to-world transform (cell * CellLength) and back by (float)Origin *
+        /// Maps[0].CellLength as every world pose is.  No scan is needed; MatchPose, LastMapUpdatePose and the update gate are
+        /// untouched.</summary>
+        public unsafe FrontierCluster[] Frontiers(int level, out FrontierSummary summary, out Vector2[] centroids, int minCells = 1, int maxClusters = 256, bool world = false)
+        {
+            var rec = new FrontierCluster[Math.Max(maxClusters, 0)];
+            fixed (FrontierCluster* c = rec)
+                Native.Check(Native.slamhip_hsproc_frontiers(proc.Ptr, level, world ? 1 : 0, minCells, maxClusters, out summary, c, 0, 0, 0, 0, null));
+            Array.Resize(ref rec, summary.ReturnedCount);
+            var (ox, oy) = Origin;
+            double cell = MapRep.Maps[level].Properties.CellLength;
+            float cell0 = MapRep.Maps[0].Properties.CellLength;
+            centroids = new Vector2[rec.Length];
+            for (int i = 0; i < rec.Length; i++)
+            {
+                long n = rec[i].CellCount;                               // (the sums back in the window's frame: integers, exact)
+                centroids[i] = new Vector2((float)((rec[i].SumX - n * (ox >> level)) / (double)n * cell + (double)((float)ox * cell0)),
+                                           (float)((rec[i].SumY - n * (oy >> level)) / (double)n * cell + (double)((float)oy * cell0)));
+            }
+            return rec;
+        }
+
         private void Refresh()
         {
             Native.Check(Native.slamhip_hsproc_get(proc.Ptr, out Vector3 match, out Vector3 last, out float tm, out float tu));

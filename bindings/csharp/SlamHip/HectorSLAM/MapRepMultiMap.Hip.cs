@@ -227,6 +227,43 @@ namespace HectorSLAM.Main
             return d2;
         }
 
+        /// <summary>The frontier clusters of `level` (slamhip_hs_frontiers; the reference has no counterpart): the free cells that touch
+        /// the unknown, grouped under 8-connectivity.  Returns the kept clusters (cells >= minCells), largest first, at most
+        /// maxClusters, in window-frame cells of the level.  labelRect = (x, y, w, h), any position: labels receives [row * w + column]
+        /// the label of every cell -- the flat index of its cluster's seed in the summary's map rectangle, -1 where the cell is no
+        /// frontier cell; null: no labels.  Blocking; it changes nothing.</summary>
+        public unsafe FrontierCluster[] Frontiers(int level, out FrontierSummary summary, int minCells = 1, int maxClusters = 256, bool world = false)
+        {
+            return Frontiers(level, out summary, minCells, maxClusters, world, null, out _);
+        }
+
+        public unsafe FrontierCluster[] Frontiers(int level, out FrontierSummary summary, int minCells, int maxClusters, bool world,
+                                                  (int X, int Y, int W, int H)? labelRect, out int[] labels)
+        {
+            var rec = new FrontierCluster[Math.Max(maxClusters, 0)];
+            var r = labelRect ?? (0, 0, 0, 0);
+            labels = labelRect.HasValue ? new int[(long)Math.Max(r.W, 0) * Math.Max(r.H, 0)] : null;
+            fixed (FrontierCluster* c = rec)
+            fixed (int* l = labels)
+                Native.Check(Native.slamhip_hs_frontiers(Pyramid.Ptr, level, world ? 1 : 0, minCells, maxClusters, out summary, c, r.X, r.Y, r.W, r.H, labelRect.HasValue ? l : null));
+            Array.Resize(ref rec, summary.ReturnedCount);
+            return rec;
+        }
+
+        /// <summary>The clusters of the definition over a caller's class array on the host (slamhip_debug_frontiers): cls is ch rows of
+        /// cw class bytes (1 occupied, 2 free, 0 neither), class 0 outside; labels the whole cw x ch array.</summary>
+        public static unsafe FrontierCluster[] FrontiersOf(byte[] cls, int cw, int ch, int minCells, int maxClusters, out FrontierSummary summary, out int[] labels)
+        {
+            var rec = new FrontierCluster[Math.Max(maxClusters, 0)];
+            labels = new int[(long)Math.Max(cw, 0) * Math.Max(ch, 0)];
+            fixed (byte* b = cls)
+            fixed (FrontierCluster* c = rec)
+            fixed (int* l = labels)
+                Native.Check(Native.slamhip_debug_frontiers(b, cw, ch, minCells, maxClusters, out summary, c, l));
+            Array.Resize(ref rec, summary.ReturnedCount);
+            return rec;
+        }
+
         /// <summary>The sum of all shifts since construction or the last Reset, in level-0 cells (slamhip_hs_origin).</summary>
         public (long X, long Y) Origin
         {

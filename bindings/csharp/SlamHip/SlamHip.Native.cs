@@ -131,6 +131,29 @@ namespace SlamHip
         public long SumD2;
     }
 
+    /// <summary>slamhip_frontier_cluster (include/slamhip.h): one connected cluster of frontier cells -- free cells that touch the
+    /// unknown -- of one level: its seed (first cell in row-major order), cells, runs, bounding box (inclusive) and the sums of its
+    /// cells' coordinates (centroid = sum / cells).  8 ints and 2 longs, 48 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct FrontierCluster
+    {
+        public int SeedX, SeedY;
+        public int CellCount, RunCount;
+        public int XMin, YMin, XMax, YMax;
+        public long SumX, SumY;
+    }
+
+    /// <summary>slamhip_frontier_summary (include/slamhip.h): the class map's rectangle, the frontier cells, runs and clusters of the
+    /// whole level, and the clusters kept (cells >= minCells) and returned.  10 ints, 40 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct FrontierSummary
+    {
+        public int MapX0, MapY0, MapWidth, MapHeight;
+        public int FrontierCellCount, RunCount, ClusterCount;
+        public int KeptCount, ReturnedCount;
+        public int KeptCells;
+    }
+
     internal static unsafe class Native
     {
         const string Lib = "slamhip";                                   // libslamhip.so on the library path
@@ -228,6 +251,11 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_distance_score(IntPtr hs, int level, int world, int siteMask, int radius, Vector3* poses, int nPoses,
                                                                               DistanceSummary* summaries, ushort* points);
         [DllImport(Lib)] internal static extern int slamhip_debug_distance_field(byte* cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h, ushort* d2);
+        // the frontier cells and their connected clusters (no reference counterpart), and their host-side hook
+        [DllImport(Lib)] internal static extern int slamhip_hs_frontiers(IntPtr hs, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
+                                                                         int lx, int ly, int lw, int lh, int* labels);
+        [DllImport(Lib)] internal static extern int slamhip_debug_frontiers(byte* cls, int cw, int ch, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
+                                                                            int* labels);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_match_threads(IntPtr hs, int numThreads);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_reference_cache(IntPtr hs, int on);
         [DllImport(Lib)] internal static extern int slamhip_hs_update_by_scan(IntPtr hs, in Vector3 robotPoseWorld);
@@ -260,6 +288,8 @@ namespace SlamHip
                                                                          TraceSummary* summaries, TraceBeam* beams);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_distance_score(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int world,
                                                                                   int siteMask, int radius, DistanceSummary* summaries, ushort* pointD2);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_frontiers(IntPtr proc, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
+                                                                             int lx, int ly, int lw, int lh, int* labels);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_relocalise_world(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in LatticeSpec specWorld, int maxHints, int adopt,
                                                                                     out Vector3 poseWorld, out MatchReport report, out WorldRelocInfo info);
 

@@ -835,6 +835,74 @@ int32_t slamhip_hs_distance_field(slamhip_hs *hs, int32_t level, int32_t world, 
 int32_t slamhip_hs_distance_score(slamhip_hs *hs, int32_t level, int32_t world, int32_t site_mask, int32_t radius,
                                   const float *poses, int32_t B, slamhip_distance_summary *out_summaries, uint16_t *out_points);
 
+/* The frontier cells of the map and their connected clusters (K10; no reference counterpart): where the known free space of ONE
+ * level ends, and which stretches of that boundary hang together -- what an exploring robot chooses its next goal from.  The beam
+ * trace's unknown_cells wants candidate viewpoints and the distance field wants goals to check for clearance: the clusters supply
+ * both.
+ * THE DEFINITION, for level L, world in {0, 1}, min_cells >= 1 and max_clusters in [0, 65536]:
+ *  1. Class map.  cls(x, y) and the class map's rectangle M = (mx0, my0, mw, mh) are steps 1 and 4 of slamhip_hs_distance_field: M
+ *     is the window, or the world's rectangle R.  Every cell outside M is class 0.
+ *  2. Frontier cell.  A cell of M is a frontier cell iff cls = 2 (free) and at least one of its four edge neighbours (x +- 1, y),
+ *     (x, y +- 1) has class 0.  A free cell on M's border therefore is a frontier cell, because beyond it the map knows nothing.
+ *     Occupied cells and cells outside M are never frontier cells.
+ *  3. Cluster.  A cluster is a connected component of frontier cells under 8-connectivity.  Its SEED is its first cell in row-major
+ *     order of M; its LABEL is the seed's flat index (seed_y - my0) * mw + (seed_x - mx0).  Labels do not depend on how they are
+ *     computed.
+ *  4. Run.  A run is a maximal horizontal stretch of frontier cells in one row of M.
+ *  5. Per-cluster record, slamhip_frontier_cluster: cells in window-frame cells of the level.  The centroid is sum / n_cells and is
+ *     the caller's to form.
+ *  6. Kept clusters.  A cluster is KEPT iff n_cells >= min_cells.  The kept clusters are ordered by n_cells descending, equal sizes
+ *     by label ascending; the first min(n_kept, max_clusters) are returned.
+ *  7. Per-call summary, slamhip_frontier_summary.
+ *  8. Labels, on request.  For a caller's rectangle (lx, ly, lw, lh) in window-frame cells at any position: an int32_t per cell,
+ *     the label of the cell's cluster, kept or not; -1 where the cell is not a frontier cell, and outside M.
+ * The library sets no threshold beyond min_cells and ranks nothing by usefulness. */
+#define SLAMHIP_FRONTIER_MAX_CLUSTERS 65536
+typedef struct slamhip_frontier_cluster {
+    int32_t seed_x, seed_y;            /* the cluster's first cell in row-major order of M */
+    int32_t n_cells, n_runs;
+    int32_t x_min, y_min, x_max, y_max;    /* the bounding box, inclusive */
+    int64_t sum_x, sum_y;              /* over the cluster's cells */
+} slamhip_frontier_cluster;            /* 8 int32 + 2 int64: 48 bytes, no padding */
+typedef struct slamhip_frontier_summary {
+    int32_t mx0, my0, mw, mh;          /* M */
+    int32_t n_frontier_cells, n_runs, n_clusters;   /* over ALL components, kept or not */
+    int32_t n_kept, n_returned;
+    int32_t kept_cells;                /* frontier cells of the kept clusters */
+} slamhip_frontier_summary;            /* 10 int32: 40 bytes */
+/* The frontier clusters of `level`.  out_summary: one record.  out_clusters: room for max_clusters records (NULL allowed when
+ * max_clusters is 0); the first n_returned are written.  out_labels: NULL (lx, ly, lw, lh are then ignored), or lh rows of lw
+ * int32_t.
+ * The launches, on the operator's stream behind every grid update, shift and upload already enqueued: the lattice search's class
+ * map of the level, re-packed on every call (as slamhip_hs_trace packs it), then k10_mark (class words to frontier words, 1 bit per
+ * cell; parent and count initialised at every run start), k10_merge (a lock-free union-find over run starts: each run unites itself
+ * with the runs of the row above that touch it, the larger root hung under the smaller by an atomic minimum, so the final root of
+ * a component is its minimum, the label), k10_count (cells per root), k10_slots (a kept root draws a slot of the record block),
+ * k10_stats (one set of atomics per run into its slot), k10_emit (the counters and the drawn slots to pinned memory) and, when
+ * labels are asked for, k10_gather.  Every device loop that follows parent links, retries an atomic or scans words carries a cap
+ * derived from M's size; an overrun sets a flag and the call returns SLAMHIP_ERR_STATE ("frontier labelling did not converge") --
+ * a labelling bug cannot hang the device.  The blocks belong to the hs, are made by the first call and freed by
+ * slamhip_hs_destroy; an hs that never asks allocates nothing.  Blocking, with the context's bounded wait: ONE wait; the results
+ * come back through pinned staging that the library owns, and the host sorts the at most 65536 records by the rule of step 6.  It
+ * reads cell values only, so it works with backing off (world = window), with slamhip_hs_set_reference_cache on, and after shifts;
+ * it changes nothing of the map or of any search.  It has no timing class.
+ * SLAMHIP_ERR_INVALID, nothing launched: level out of range, world not 0 or 1, min_cells < 1, max_clusters outside [0, 65536],
+ * out_clusters NULL with max_clusters > 0, and with labels asked for lw or lh < 1 or lw * lh > 2^24 (64 MB of staging); M over 2^25
+ * cells (8 bytes per cell: 256 MB; the message gives M's size, and for the world this is known only once the world is planned).
+ * SLAMHIP_ERR_INVALID AFTER the launches: more than 65536 clusters are kept -- the message gives n_kept and says to raise
+ * min_cells; out_summary is still filled (n_returned = 0), nothing else is written.  A poisoned context: SLAMHIP_ERR_TIMEOUT.  The
+ * limits are design conditions, not measurements. */
+int32_t slamhip_hs_frontiers(slamhip_hs *hs, int32_t level, int32_t world, int32_t min_cells, int32_t max_clusters,
+                             slamhip_frontier_summary *out_summary, slamhip_frontier_cluster *out_clusters,
+                             int32_t lx, int32_t ly, int32_t lw, int32_t lh, int32_t *out_labels);
+/* Test hook (no device involved): the frontier clusters of the definition over a caller's class array, M = (0, 0, cw, ch).  cls: ch
+ * rows of cw bytes of class bits (only the low two bits are read), packed as the lattice search packs them; the frontier words and
+ * the runs by the text the kernels run, the components by a plain sequential union-find.  out_labels: NULL, or the whole cw x ch
+ * label array.  Everything else as slamhip_hs_frontiers.  SLAMHIP_ERR_INVALID: cw or ch < 1, cw * ch > 2^25, min_cells < 1,
+ * max_clusters outside [0, 65536], out_clusters NULL with max_clusters > 0; more than 65536 kept clusters as there. */
+int32_t slamhip_debug_frontiers(const uint8_t *cls, int32_t cw, int32_t ch, int32_t min_cells, int32_t max_clusters,
+                                slamhip_frontier_summary *out_summary, slamhip_frontier_cluster *out_clusters, int32_t *out_labels);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -1023,6 +1091,13 @@ int32_t slamhip_hsproc_trace(slamhip_hsproc *p, const float *xy, int32_t n_point
 int32_t slamhip_hsproc_distance_score(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
                                       const float *poses_world, int32_t B, int32_t level, int32_t world, int32_t site_mask,
                                       int32_t radius, slamhip_distance_summary *out_summaries, uint16_t *out_points);
+/* The frontier clusters through the processor: slamhip_hs_frontiers on the processor's own hs with every cell field in WORLD cells
+ * of the level.  (lx, ly) is taken as a world cell; (origin >> level) per axis is added to the seeds, the boxes and mx0 / my0, and
+ * n_cells * (origin >> level) to the sums; labels are flat indices into M and need no conversion.  No scan is needed; the
+ * processor's stored poses, its update gate and the scan that was set are not touched.  Errors as slamhip_hs_frontiers. */
+int32_t slamhip_hsproc_frontiers(slamhip_hsproc *p, int32_t level, int32_t world, int32_t min_cells, int32_t max_clusters,
+                                 slamhip_frontier_summary *out_summary, slamhip_frontier_cluster *out_clusters,
+                                 int32_t lx, int32_t ly, int32_t lw, int32_t lh, int32_t *out_labels);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

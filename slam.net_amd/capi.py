@@ -114,6 +114,13 @@ DISTANCE_SUMMARY = np.dtype([("n_counted", np.int32), ("n_ignored", np.int32), (
                              ("sum_d2", np.int64)])            # slamhip_distance_summary (include/slamhip.h): 4 int32 + 1 int64, 24 bytes
 assert DISTANCE_SUMMARY.itemsize == 24
 DISTANCE_IGNORED = 0xFFFF                                      # the per-point record of an ignored point
+FRONTIER_MAX_CLUSTERS = 65536
+FRONTIER_CLUSTER = np.dtype([("seed_x", np.int32), ("seed_y", np.int32), ("n_cells", np.int32), ("n_runs", np.int32), ("x_min", np.int32),
+                             ("y_min", np.int32), ("x_max", np.int32), ("y_max", np.int32), ("sum_x", np.int64),
+                             ("sum_y", np.int64)])             # slamhip_frontier_cluster (include/slamhip.h): 8 int32 + 2 int64, 48 bytes
+FRONTIER_SUMMARY = np.dtype([(n, np.int32) for n in ("mx0", "my0", "mw", "mh", "n_frontier_cells", "n_runs", "n_clusters", "n_kept",
+                                                     "n_returned", "kept_cells")])   # slamhip_frontier_summary: 10 int32, 40 bytes
+assert FRONTIER_CLUSTER.itemsize == 48 and FRONTIER_SUMMARY.itemsize == 40
 
 
 def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
@@ -178,6 +185,7 @@ def _declare(L):
         "slamhip_debug_trace_lines": (i32, [f, fp, fp, fp, i32, ip]),
         "slamhip_debug_trace_cells": (i32, [i32, i32, i32, i32, ip, i32, ip]),
         "slamhip_debug_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "slamhip_debug_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -267,6 +275,7 @@ def _declare(L):
         "slamhip_hs_trace": (i32, [vp, i32, fp, i32, i32, vp, vp]),
         "slamhip_hs_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "slamhip_hs_distance_score": (i32, [vp, i32, i32, i32, i32, fp, i32, vp, vp]),
+        "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -293,6 +302,7 @@ def _declare(L):
         "slamhip_hsproc_relocalise_world": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, wrip]),
         "slamhip_hsproc_trace": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_distance_score": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
+        "slamhip_hsproc_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -410,6 +420,29 @@ def debug_distance_field(cls, site_mask, radius, rect):
     call("slamhip_debug_distance_field", c.ctypes.data_as(C.c_void_p), c.shape[1], c.shape[0], int(site_mask), int(radius), x, y, w, h,
          out.ctypes.data_as(C.c_void_p))
     return out
+
+
+def frontiers_call(name, head, min_cells, max_clusters, labels_shape, rect=None):
+    """One of the three frontier entry points: `head` its leading arguments, rect = (lx, ly, lw, lh) for the two device calls.
+    -> (summary, clusters[, labels]): a FRONTIER_SUMMARY record, the n_returned FRONTIER_CLUSTER records, the int32 label array."""
+    summary = np.zeros(1, FRONTIER_SUMMARY)
+    rec = np.zeros(max(int(max_clusters), 0), FRONTIER_CLUSTER)
+    labels = np.empty(labels_shape, np.int32) if labels_shape is not None else None
+    tail = [labels.ctypes.data_as(C.c_void_p) if labels is not None else None]
+    if rect is not None:
+        tail = [int(v) for v in rect] + tail
+    call(name, *head, int(min_cells), int(max_clusters), summary.ctypes.data_as(C.c_void_p),
+         rec.ctypes.data_as(C.c_void_p) if rec.shape[0] else None, *tail)
+    out = (summary[0], rec[:int(summary[0]["n_returned"])].copy())
+    return out + (labels,) if labels is not None else out
+
+
+def debug_frontiers(cls, min_cells=1, max_clusters=256, labels=True):
+    """The frontier clusters of the definition (slamhip_hs_frontiers) over the (h, w) uint8 array `cls` of class bits, M = (0, 0, w, h)
+    (slamhip_debug_frontiers; no device involved) -> (summary, clusters[, labels]), labels the whole (h, w) int32 array."""
+    c = np.ascontiguousarray(cls, np.uint8)
+    return frontiers_call("slamhip_debug_frontiers", [c.ctypes.data_as(C.c_void_p), c.shape[1], c.shape[0]], min_cells, max_clusters,
+                          c.shape if labels else None)
 
 
 def check(rc):

@@ -42,6 +42,7 @@ struct hs_world;                           // hs_world.hip
 struct hs_lattice;                         // hs_lattice.hip
 struct hs_trace;                           // hs_trace.hip
 struct hs_dfield;                          // hs_dfield.hip
+struct hs_frontier;                        // hs_frontier.hip
 struct slamhip_hs {
     slamhip_ctx *ctx;
     int n_levels;
@@ -69,6 +70,7 @@ struct slamhip_hs {
     struct hs_lattice *lat;                                // slamhip_hs_lattice_search: the class map and the result blocks, made by the first search, kept
     struct hs_trace *trc;                                  // slamhip_hs_trace: the poses' and the results' blocks, made by the first trace, kept
     struct hs_dfield *dfd;                                 // slamhip_hs_distance_field / _score: the field of E and the results' blocks, made by the first call, kept
+    struct hs_frontier *frl;                               // slamhip_hs_frontiers: the frontier words, the union-find's arrays and the results' blocks, made by the first call, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -146,3 +148,5 @@ int32_t hs_lat_pack_enqueue(slamhip_hs *hs, int level, bool world, const hs_clas
 void    hs_trc_free(slamhip_hs *hs);        // the blocks of the beam trace (the caller has drained the stream)
 // hs_dfield.hip
 void    hs_df_free(slamhip_hs *hs);         // the blocks of the distance field (the caller has drained the stream)
+// hs_frontier.hip
+void    hs_fr_free(slamhip_hs *hs);         // the blocks of the frontier labelling (the caller has drained the stream)

@@ -1,5 +1,6 @@
 // hs_processor.hip -- HectorSLAMProcessor (slamhip_hsproc_*): the per-scan flow over the operator object.  Host code only.
 #include "hs_internal.h"
+#include <algorithm>
 #include <chrono>
 
 // ---- HectorSLAMProcessor (Main/HectorSLAMProcessor.cs) ---------------------------------------------------------------
@@ -311,6 +312,30 @@ extern "C" int32_t slamhip_hsproc_distance_score(slamhip_hsproc *p, const float 
     const int32_t rc = slamhip_hs_distance_score(p->hs, level, world, site_mask, radius, w, B, out_summaries, out_points);
     free(w);
     return rc;
+}
+
+// The frontier clusters in WORLD cells of the level: slamhip_hs_frontiers, the label rectangle taken to the window's frame and every
+// cell field of the results taken back ((origin >> level) per axis; the window's origin is a multiple of 1 << (n_levels - 1)).
+extern "C" int32_t slamhip_hsproc_frontiers(slamhip_hsproc *p, int32_t level, int32_t world, int32_t min_cells, int32_t max_clusters,
+                                            slamhip_frontier_summary *out_summary, slamhip_frontier_cluster *out_clusters,
+                                            int32_t lx, int32_t ly, int32_t lw, int32_t lh, int32_t *out_labels)
+{
+    SH_CHECK_ARG(p && out_summary);
+    if (level < 0 || level >= p->hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "frontiers: level %d of %d", level, p->hs->n_levels);
+    const int64_t ox = p->hs->win_ox >> level, oy = p->hs->win_oy >> level;
+    const int64_t far = (int64_t)1 << 30;                                  // (a rectangle that far from the window lies outside M wherever M is)
+    const int64_t wx = std::min(std::max((int64_t)lx - ox, -far), far), wy = std::min(std::max((int64_t)ly - oy, -far), far);
+    slamhip_frontier_summary S;
+    memset(&S, 0, sizeof(S));
+    const int32_t rc = slamhip_hs_frontiers(p->hs, level, world, min_cells, max_clusters, &S, out_clusters, (int32_t)wx, (int32_t)wy, lw, lh, out_labels);
+    if (S.mw > 0) { S.mx0 += (int32_t)ox; S.my0 += (int32_t)oy; *out_summary = S; }   // (filled also when too many clusters are kept; a refused call writes nothing)
+    SH_TRY(rc);
+    for (int i = 0; i < S.n_returned; i++) {
+        slamhip_frontier_cluster *c = out_clusters + i;
+        c->seed_x += (int32_t)ox; c->x_min += (int32_t)ox; c->x_max += (int32_t)ox; c->sum_x += (int64_t)c->n_cells * ox;
+        c->seed_y += (int32_t)oy; c->y_min += (int32_t)oy; c->y_max += (int32_t)oy; c->sum_y += (int64_t)c->n_cells * oy;
+    }
+    return SLAMHIP_OK;
 }
 
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)

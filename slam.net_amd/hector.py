@@ -375,6 +375,17 @@ class MapRepMultiMap:
                   sums.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p) if points else None)
         return sums, rec
 
+    def frontiers(self, level, min_cells=1, max_clusters=256, world=False, labels_rect=None):
+        """The frontier clusters of `level` (slamhip_hs_frontiers; no reference counterpart): the free cells that touch the unknown,
+        grouped under 8-connectivity.  -> (summary, clusters[, labels]): a capi.FRONTIER_SUMMARY record; the kept clusters (n_cells >=
+        min_cells) as capi.FRONTIER_CLUSTER records, largest first, at most max_clusters, in window-frame cells of the level; with
+        labels_rect = (x, y, w, h), any position, the (h, w) int32 labels of its cells (the flat index of the cluster's seed in M, -1
+        where the cell is no frontier cell).  world=True: a cell outside the window is the cell of the tile that holds it.  Blocking,
+        behind everything already enqueued; it changes nothing."""
+        rect = (0, 0, 0, 0) if labels_rect is None else tuple(int(v) for v in labels_rect)
+        shape = None if labels_rect is None else (max(rect[3], 0), max(rect[2], 0))
+        return capi.frontiers_call("slamhip_hs_frontiers", [self._h, int(level), 1 if world else 0], min_cells, max_clusters, shape, rect)
+
     def ExpectedScan(self, pose, angles, max_range, level, world=False):
         """The scan the map of `level` predicts from `pose` (window frame): per angle (rad, sensor frame) the range in metres to the
         first occupied cell on the beam of length max_range, or inf where the map holds none.  It REPLACES the scan that was set:
@@ -605,6 +616,24 @@ class HectorSLAMProcessor:
                   rec.ctypes.data_as(C.c_void_p) if points else None)
         self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
         return sums, rec
+
+    def Frontiers(self, level, min_cells=1, max_clusters=256, world=False, labels_rect=None):
+        """MapRep.frontiers in WORLD cells of `level` (slamhip_hsproc_frontiers): seeds, boxes, sums, mx0 / my0 and labels_rect are world
+        cells.  -> (summary, clusters, centroids[, labels]); centroids the (n, 2) float64 centres of the clusters in metres, world
+        frame: the sums taken to the window's frame of the level (- n_cells * (origin >> level), exact), the mean cell through the
+        level's cell-to-world transform (cell * CellLength, as ExpectedScan forms ranges) and back by (float)origin * cell0 as every
+        world pose is.  No scan is
+        needed; MatchPose, LastMapUpdatePose and the update gate are untouched."""
+        rect = (0, 0, 0, 0) if labels_rect is None else tuple(int(v) for v in labels_rect)
+        shape = None if labels_rect is None else (max(rect[3], 0), max(rect[2], 0))
+        out = capi.frontiers_call("slamhip_hsproc_frontiers", [self._h, int(level), 1 if world else 0], min_cells, max_clusters, shape, rect)
+        rec = out[1]
+        ox, oy = self.get_origin()
+        cell = float(np.float32(self.MapRep.Maps[level].CellLength)); cell0 = np.float32(self.MapRep.Maps[0].CellLength)
+        n = rec["n_cells"].astype(np.int64)                         # (the sums back in the window's frame: integers, exact)
+        cx = (rec["sum_x"] - n * (ox >> level)) / n * cell + float(np.float32(ox) * cell0)
+        cy = (rec["sum_y"] - n * (oy >> level)) / n * cell + float(np.float32(oy) * cell0)
+        return out[:2] + (np.stack([cx, cy], 1),) + out[2:]
 
     MatchPose = property(lambda self: self._get()[0])
     LastMapUpdatePose = property(lambda self: self._get()[1])
