@@ -250,6 +250,54 @@ namespace HectorSLAM.Main
             return rec;
         }
 
+        /// <summary>MapRep.NavField in WORLD cells of `spec.Level` (slamhip_hsproc_nav_field): sources, goals and rect are world cells,
+        /// and so are the goals' cells, the paths and the summary's map rectangle.  No scan is needed; MatchPose, LastMapUpdatePose and
+        /// the update gate are untouched.</summary>
+        public unsafe NavGoalResult[] NavField(NavSpec spec, int[] sources, int[] goals, out NavSummary summary, int nPaths, int maxPathCells,
+                                               out NavPath[] heads, out int[][] paths)
+        {
+            int nGoals = goals == null ? 0 : goals.Length / 4;
+            var res = new NavGoalResult[nGoals];
+            heads = new NavPath[Math.Max(nPaths, 0)];
+            var cells = new int[2L * Math.Max(nPaths, 0) * Math.Max(maxPathCells, 0)];
+            fixed (int* s = sources)
+            fixed (int* g = goals)
+            fixed (NavGoalResult* gr = res)
+            fixed (NavPath* h = heads)
+            fixed (int* pc = cells)
+                Native.Check(Native.slamhip_hsproc_nav_field(proc.Ptr, ref spec, s, sources.Length / 2, g, nGoals, gr, nPaths, maxPathCells, h, pc, 0, 0, 0, 0, null, null, out summary));
+            paths = MapRepMultiMap.NavPaths(heads, cells, maxPathCells);
+            return res;
+        }
+
+        /// <summary>Which frontier to drive to: Frontiers, then NavField from the cell of MatchPose with each returned cluster's
+        /// bounding box, grown by `grow` cells on every side, as a goal (the box, not the cluster's own cells).  Returns the clusters,
+        /// reachable ones first by cost ascending (equal costs in Frontiers' order), the unreachable ones behind them in Frontiers' order;
+        /// results[i] belongs to the i-th returned cluster.  Composition only: no device work of its own.</summary>
+        public FrontierCluster[] ExploreGoals(int level, int clearance, out NavGoalResult[] results, int siteMask = 2, int minCells = 1, int maxClusters = 256, int grow = 0)
+        {
+            var rec = Frontiers(level, out _, out _, minCells, maxClusters);
+            results = new NavGoalResult[rec.Length];
+            if (rec.Length == 0) return rec;
+            var goals = new int[4 * rec.Length];
+            for (int i = 0; i < rec.Length; i++)
+            {
+                goals[4 * i] = rec[i].XMin - grow; goals[4 * i + 1] = rec[i].YMin - grow;
+                goals[4 * i + 2] = rec[i].XMax + grow; goals[4 * i + 3] = rec[i].YMax + grow;
+            }
+            double cell = MapRep.Maps[level].Properties.CellLength;
+            var pose = MatchPose;
+            var source = new[] { (int)Math.Round(pose.X / cell, MidpointRounding.ToEven), (int)Math.Round(pose.Y / cell, MidpointRounding.ToEven) };
+            var spec = new NavSpec { Level = level, World = 0, SiteMask = siteMask, Clearance = clearance, MaxCost = 0 };
+            var res = NavField(spec, source, goals, out _, 0, 1, out _, out _);
+            var order = new int[rec.Length];
+            for (int i = 0; i < order.Length; i++) order[i] = i;
+            Array.Sort(order, (a, b) => res[a].Cost != res[b].Cost ? res[a].Cost.CompareTo(res[b].Cost) : a.CompareTo(b));
+            var sorted = new FrontierCluster[rec.Length];
+            for (int i = 0; i < order.Length; i++) { sorted[i] = rec[order[i]]; results[i] = res[order[i]]; }
+            return sorted;
+        }
+
         private void Refresh()
         {
             Native.Check(Native.slamhip_hsproc_get(proc.Ptr, out Vector3 match, out Vector3 last, out float tm, out float tu));

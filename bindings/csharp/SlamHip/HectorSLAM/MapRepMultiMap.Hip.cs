@@ -264,6 +264,65 @@ namespace HectorSLAM.Main
             return rec;
         }
 
+        /// <summary>The cost-to-go field of `spec.Level` (slamhip_hs_nav_field; the reference has no counterpart): the least 5-7 chamfer
+        /// cost from the sources (x, y pairs, window-frame cells) to every traversable cell over moves that cut no corner.  goals: one
+        /// rectangle {xMin, yMin, xMax, yMax} each, e.g. a frontier cluster's box grown as the caller sees fit; returns one result per
+        /// goal.  The first nPaths goals get their cell path: paths[i] holds min(length, maxPathCells) (x, y) pairs, heads[i] the true
+        /// length.  rect = (x, y, w, h), any position: cost and dir receive [row * w + column]; null: neither.  Blocking; it changes
+        /// nothing.</summary>
+        public unsafe NavGoalResult[] NavField(NavSpec spec, int[] sources, int[] goals, out NavSummary summary, int nPaths, int maxPathCells,
+                                               out NavPath[] heads, out int[][] paths, (int X, int Y, int W, int H)? rect, out uint[] cost, out byte[] dir)
+        {
+            int nGoals = goals == null ? 0 : goals.Length / 4;
+            var res = new NavGoalResult[nGoals];
+            heads = new NavPath[Math.Max(nPaths, 0)];
+            var cells = new int[2L * Math.Max(nPaths, 0) * Math.Max(maxPathCells, 0)];
+            var r = rect ?? (0, 0, 0, 0);
+            cost = rect.HasValue ? new uint[(long)Math.Max(r.W, 0) * Math.Max(r.H, 0)] : null;
+            dir = rect.HasValue ? new byte[(long)Math.Max(r.W, 0) * Math.Max(r.H, 0)] : null;
+            fixed (int* s = sources)
+            fixed (int* g = goals)
+            fixed (NavGoalResult* gr = res)
+            fixed (NavPath* h = heads)
+            fixed (int* pc = cells)
+            fixed (uint* c = cost)
+            fixed (byte* d = dir)
+                Native.Check(Native.slamhip_hs_nav_field(Pyramid.Ptr, ref spec, s, sources.Length / 2, g, nGoals, gr, nPaths, maxPathCells, h, pc, r.X, r.Y, r.W, r.H, c, d, out summary));
+            paths = NavPaths(heads, cells, maxPathCells);
+            return res;
+        }
+
+        internal static int[][] NavPaths(NavPath[] heads, int[] cells, int maxPathCells)
+        {
+            var paths = new int[heads.Length][];
+            for (int i = 0; i < heads.Length; i++)
+            {
+                paths[i] = new int[2 * heads[i].WrittenCount];
+                Array.Copy(cells, 2L * i * maxPathCells, paths[i], 0, paths[i].Length);
+            }
+            return paths;
+        }
+
+        /// <summary>The field of the definition over a caller's class array on the host (slamhip_debug_nav_field): cls is ch rows of cw
+        /// class bytes (1 occupied, 2 free, 0 neither), class 0 outside; cost and dir the whole cw x ch array; the costs come from a
+        /// sequential Dijkstra.</summary>
+        public static unsafe NavGoalResult[] NavFieldOf(byte[] cls, int cw, int ch, int siteMask, int clearance, uint maxCost, int[] sources, int[] goals,
+                                                        out NavSummary summary, out uint[] cost, out byte[] dir)
+        {
+            int nGoals = goals == null ? 0 : goals.Length / 4;
+            var res = new NavGoalResult[nGoals];
+            cost = new uint[(long)Math.Max(cw, 0) * Math.Max(ch, 0)];
+            dir = new byte[cost.Length];
+            fixed (byte* b = cls)
+            fixed (int* s = sources)
+            fixed (int* g = goals)
+            fixed (NavGoalResult* gr = res)
+            fixed (uint* c = cost)
+            fixed (byte* d = dir)
+                Native.Check(Native.slamhip_debug_nav_field(b, cw, ch, siteMask, clearance, maxCost, s, sources.Length / 2, g, nGoals, gr, 0, 1, null, null, 0, 0, cw, ch, c, d, out summary));
+            return res;
+        }
+
         /// <summary>The sum of all shifts since construction or the last Reset, in level-0 cells (slamhip_hs_origin).</summary>
         public (long X, long Y) Origin
         {

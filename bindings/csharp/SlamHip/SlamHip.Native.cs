@@ -154,6 +154,45 @@ namespace SlamHip
         public int KeptCells;
     }
 
+    /// <summary>slamhip_nav_spec (include/slamhip.h): the level, window (0) or world (1), the sites the clearance is kept from (2
+    /// obstacles, 3 obstacles or the unknown), the clearance in cells (0 .. 254) and the cost cap (0: none).  5 words, 20 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NavSpec
+    {
+        public int Level, World, SiteMask, Clearance;
+        public uint MaxCost;
+    }
+
+    /// <summary>slamhip_nav_goal_result (include/slamhip.h): the least cost-to-go over a goal rectangle (Unreached: no reached cell),
+    /// the cell that has it and the reached cells of the rectangle.  16 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NavGoalResult
+    {
+        public const uint Unreached = 0xFFFFFFFFu;
+        public uint Cost;
+        public int BestX, BestY;
+        public int ReachedCount;
+    }
+
+    /// <summary>slamhip_nav_path (include/slamhip.h): a path's true length in cells and the cells written.  8 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NavPath
+    {
+        public int CellCount, WrittenCount;
+    }
+
+    /// <summary>slamhip_nav_summary (include/slamhip.h): the class map's rectangle, the traversable and the reached cells, the sources
+    /// used and blocked, the largest cost reached and the relaxation rounds the device ran.  10 words, 40 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct NavSummary
+    {
+        public int MapX0, MapY0, MapWidth, MapHeight;
+        public int TraversableCount, ReachedCount;
+        public int SourcesUsed, SourcesBlocked;
+        public uint MaxCostReached;
+        public int Rounds;
+    }
+
     internal static unsafe class Native
     {
         const string Lib = "slamhip";                                   // libslamhip.so on the library path
@@ -256,6 +295,13 @@ namespace SlamHip
                                                                          int lx, int ly, int lw, int lh, int* labels);
         [DllImport(Lib)] internal static extern int slamhip_debug_frontiers(byte* cls, int cw, int ch, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
                                                                             int* labels);
+        // the cost-to-go field, goal costs and paths (no reference counterpart), and their host-side hook
+        [DllImport(Lib)] internal static extern int slamhip_hs_nav_field(IntPtr hs, ref NavSpec spec, int* sources, int nSources, int* goals, int nGoals, NavGoalResult* goalResults,
+                                                                        int nPaths, int maxPathCells, NavPath* paths, int* pathCells, int rx, int ry, int rw, int rh, uint* cost, byte* dir,
+                                                                        out NavSummary summary);
+        [DllImport(Lib)] internal static extern int slamhip_debug_nav_field(byte* cls, int cw, int ch, int siteMask, int clearance, uint maxCost, int* sources, int nSources, int* goals,
+                                                                           int nGoals, NavGoalResult* goalResults, int nPaths, int maxPathCells, NavPath* paths, int* pathCells, int rx,
+                                                                           int ry, int rw, int rh, uint* cost, byte* dir, out NavSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_match_threads(IntPtr hs, int numThreads);
         [DllImport(Lib)] internal static extern int slamhip_hs_set_reference_cache(IntPtr hs, int on);
         [DllImport(Lib)] internal static extern int slamhip_hs_update_by_scan(IntPtr hs, in Vector3 robotPoseWorld);
@@ -290,6 +336,9 @@ namespace SlamHip
                                                                                   int siteMask, int radius, DistanceSummary* summaries, ushort* pointD2);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_frontiers(IntPtr proc, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
                                                                              int lx, int ly, int lw, int lh, int* labels);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_nav_field(IntPtr proc, ref NavSpec spec, int* sources, int nSources, int* goals, int nGoals, NavGoalResult* goalResults,
+                                                                            int nPaths, int maxPathCells, NavPath* paths, int* pathCells, int rx, int ry, int rw, int rh, uint* cost,
+                                                                            byte* dir, out NavSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_relocalise_world(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in LatticeSpec specWorld, int maxHints, int adopt,
                                                                                     out Vector3 poseWorld, out MatchReport report, out WorldRelocInfo info);
 

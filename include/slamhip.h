@@ -903,6 +903,103 @@ int32_t slamhip_hs_frontiers(slamhip_hs *hs, int32_t level, int32_t world, int32
 int32_t slamhip_debug_frontiers(const uint8_t *cls, int32_t cw, int32_t ch, int32_t min_cells, int32_t max_clusters,
                                 slamhip_frontier_summary *out_summary, slamhip_frontier_cluster *out_clusters, int32_t *out_labels);
 
+/* The cost-to-go field of the map, goal costs and paths (K11; no reference counterpart): which of the frontier clusters an exploring
+ * robot can reach, how far the drive to each is while keeping a clearance from the walls, and along which cells.  An exact integer
+ * computation: every quantity below is an integer and nothing has a tolerance.
+ * THE DEFINITION, for level L, world in {0, 1}, site_mask in {2, 3}, clearance c in [0, 254] and max_cost (0: no cap):
+ *  1. Class map.  cls(x, y) and the class map's rectangle M = (mx0, my0, mw, mh) are steps 1 and 4 of slamhip_hs_distance_field: M
+ *     is the window, or the world's rectangle R.  Every cell outside M is class 0.
+ *  2. Traversable.  A cell of M is traversable iff cls = 2 (free) and, for c >= 1, no site lies within c cells: F(x, y) > c^2, F the
+ *     field of slamhip_hs_distance_field with radius c + 1 and site_mask (2: obstacles, 3: obstacles or the unknown).  The test is
+ *     exact, because F = min(D2, (c + 1)^2) and c^2 < (c + 1)^2.  With c = 0 no field is built.  Cells outside M are never
+ *     traversable.  With site_mask = 3 and c >= 1 EVERY FRONTIER CELL IS UNTRAVERSABLE, because it touches the unknown: this is why
+ *     goals are rectangles (step 6) and not cells.
+ *  3. Moves.  Eight directions d = 0 .. 7: (+1, 0), (+1, +1), (0, +1), (-1, +1), (-1, 0), (-1, -1), (0, -1), (+1, -1).  The weight
+ *     is 5 for even d and 7 for odd d, the 5-7 chamfer metric, an integer stand-in for 5 x the Euclidean length.  A move between two
+ *     traversable cells is allowed iff, for a diagonal move, both cells that share an edge with both ends are traversable too (no
+ *     corner cutting).  The relation is symmetric.
+ *  4. Sources and cost.  S source cells in window-frame cells of the level.  A source that is not traversable, or lies outside M,
+ *     is counted in n_sources_blocked and plays no part; the others in n_sources_used, a source given twice twice.  C(x, y) is the
+ *     least total weight of a path of allowed moves from any used source, 0 at a source.  With max_cost > 0 a cell whose C exceeds
+ *     max_cost is unreached (exact: every prefix of a shortest path is cheaper than the path).  An unreached cell, an untraversable
+ *     cell and every cell outside M have C = SLAMHIP_NAV_UNREACHED.  C is the unique solution of the shortest-path equations and
+ *     does not depend on how it is computed.
+ *  5. Direction.  A reached cell that is no source has dir = the smallest d such that the move to n = (x + dx_d, y + dy_d) is
+ *     allowed and C(n) + weight_d == C(x, y); a source has dir = 8; everything else 255.  Following dir from a reached cell ends at
+ *     a source after finitely many steps, because C strictly decreases.
+ *  6. Goals.  G rectangles {x_min, y_min, x_max, y_max}, inclusive, in window-frame cells at any position, clipped to M.  Per goal,
+ *     slamhip_nav_goal_result: cost = the least C over the rectangle's cells, (bx, by) = the cell that has it, the first such cell
+ *     in row-major order of M on a tie, n_reached = the reached cells of the rectangle; with no reached cell cost =
+ *     SLAMHIP_NAV_UNREACHED and bx = by = 0.  A single cell is the rectangle with min == max.  A frontier cluster's box (x_min ..
+ *     y_max of slamhip_frontier_cluster), grown by the caller as it sees fit, asks for "the cheapest reachable cell near that
+ *     cluster": THE BOUNDING BOX, NOT THE CLUSTER'S OWN CELLS.
+ *  7. Paths, for the first n_paths goals.  The path of a goal with a reached cell is (bx, by) followed by its dir steps down to a
+ *     source: cell 0 is (bx, by), the last cell a source.  slamhip_nav_path: n_cells the true length (0: no reached cell), n_written
+ *     = min(n_cells, max_path_cells); the first n_written cells go out as int32_t pairs at out_path_cells + 2 * i * max_path_cells.
+ *  8. Per call, slamhip_nav_summary.
+ *  9. On request, for a caller's rectangle (rx, ry, rw, rh) at any position: C and / or dir of its cells, the values of steps 4 and
+ *     5 outside M.
+ * The library ranks nothing and sets no threshold. */
+#define SLAMHIP_NAV_UNREACHED 0xFFFFFFFFu
+typedef struct slamhip_nav_spec {
+    int32_t level, world, site_mask, clearance;
+    uint32_t max_cost;                 /* 0: no cap */
+} slamhip_nav_spec;                    /* 5 words: 20 bytes */
+typedef struct slamhip_nav_goal_result {
+    uint32_t cost;                     /* SLAMHIP_NAV_UNREACHED: no reached cell in the rectangle */
+    int32_t bx, by;                    /* the cheapest reached cell, window-frame cells */
+    int32_t n_reached;
+} slamhip_nav_goal_result;             /* 16 bytes */
+typedef struct slamhip_nav_path {
+    int32_t n_cells, n_written;
+} slamhip_nav_path;                    /* 8 bytes */
+typedef struct slamhip_nav_summary {
+    int32_t mx0, my0, mw, mh;          /* M */
+    int32_t n_traversable, n_reached;
+    int32_t n_sources_used, n_sources_blocked;
+    uint32_t max_cost_reached;         /* 0 if nothing is reached */
+    int32_t rounds;                    /* relaxation rounds the device ran up to the first that changed no tile's border: an
+                                          implementation figure (the test hook returns 0) */
+} slamhip_nav_summary;                 /* 10 words: 40 bytes */
+/* The field of spec->level.  sources: S pairs (x, y); goals: G rectangles of four int32_t (NULL allowed when G is 0);
+ * out_goal_results: G records; out_paths: n_paths records and out_path_cells: n_paths * max_path_cells pairs (both NULL allowed when
+ * n_paths is 0); out_cost: NULL, or rh rows of rw uint32_t; out_dir: NULL, or rh rows of rw bytes (rx .. rh are ignored when both
+ * are NULL); out_summary: one record.
+ * The launches, on the operator's stream behind every grid update, shift and upload already enqueued: the lattice search's class
+ * map of the level, re-packed on every call, and for c >= 1 the two launches of slamhip_hs_distance_field's field; k11_trav (class
+ * words and field to traversable words, 1 bit per cell); a memset of the cost array (one uint32_t per cell of M) and k11_seed;
+ * then k11_relax, ONE LAUNCH PER ROUND, a workgroup per tile of 64 x 64 cells: a tile whose flag is set relaxes its cells in LDS
+ * against a one-cell halo until nothing changes, stores what got lower and flags the neighbouring tiles whose halo changed.  No
+ * workgroup ever waits for another.  The host enqueues the rounds in batches of 8 (measured against 1 and 32:
+ * profiles/r16_hs_nav.json), each batch followed by a one-workgroup launch that stores the round counters to pinned memory, and
+ * waits once per batch with the context's bounded wait; it stops when the last round of a batch flagged no tile.  Rounds are capped
+ * at n_traversable + 1 (a shortest path is simple, so it crosses tile borders fewer times than it has cells) and a tile's passes in
+ * LDS by its cell count + 1; an overrun returns SLAMHIP_ERR_STATE ("navigation field did not converge") -- a relaxation bug cannot
+ * hang the device.  Then k11_dirs (dir, n_reached, max_cost_reached), k11_goals (a workgroup per goal), k11_paths (a lane per
+ * path), k11_gather (the rectangle) and k11_emit (summary, goal results and path heads to pinned memory).  The blocks belong to the
+ * hs, are made by the first call and freed by slamhip_hs_destroy; an hs that never asks allocates nothing.  Blocking.  It reads
+ * cell values only, so it works with backing off (world = window), with slamhip_hs_set_reference_cache on, and after shifts; it
+ * changes nothing of the map or of any search.  It has no timing class.
+ * SLAMHIP_ERR_INVALID, nothing launched, no output written: level out of range, world not 0 or 1, site_mask not 2 or 3, clearance
+ * outside [0, 254], S outside [1, 4096], G outside [0, 4096], n_paths outside [0, min(G, 64)], max_path_cells outside [1, 65536],
+ * n_paths * max_path_cells > 2^20, a NULL where an array is needed, a goal with x_min > x_max or y_min > y_max, with a rectangle
+ * asked for rw or rh < 1 or rw * rh > 2^24; M over 2^25 cells, and for c >= 1 the field's limit on M grown by c + 1 (2^26 cells).
+ * A poisoned context: SLAMHIP_ERR_TIMEOUT.  The limits are design conditions, not measurements. */
+int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, const int32_t *goals,
+                             int32_t G, slamhip_nav_goal_result *out_goal_results, int32_t n_paths, int32_t max_path_cells,
+                             slamhip_nav_path *out_paths, int32_t *out_path_cells, int32_t rx, int32_t ry, int32_t rw, int32_t rh,
+                             uint32_t *out_cost, uint8_t *out_dir, slamhip_nav_summary *out_summary);
+/* Test hook (no device involved): the field of the definition over a caller's class array, M = (0, 0, cw, ch).  cls: ch rows of cw
+ * bytes of class bits (only the low two bits are read), packed as the lattice search packs them; the field for c >= 1 by
+ * slamhip_debug_distance_field; traversable words, moves and dirs by the text the kernels run; the costs by a plain sequential
+ * Dijkstra with a binary heap, not by the tiled relaxation; rounds = 0.  Everything else as slamhip_hs_nav_field.
+ * SLAMHIP_ERR_INVALID: cw or ch < 1, cw * ch > 2^25, and the argument checks of slamhip_hs_nav_field. */
+int32_t slamhip_debug_nav_field(const uint8_t *cls, int32_t cw, int32_t ch, int32_t site_mask, int32_t clearance, uint32_t max_cost,
+                                const int32_t *sources, int32_t S, const int32_t *goals, int32_t G,
+                                slamhip_nav_goal_result *out_goal_results, int32_t n_paths, int32_t max_path_cells,
+                                slamhip_nav_path *out_paths, int32_t *out_path_cells, int32_t rx, int32_t ry, int32_t rw, int32_t rh,
+                                uint32_t *out_cost, uint8_t *out_dir, slamhip_nav_summary *out_summary);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -1098,6 +1195,14 @@ int32_t slamhip_hsproc_distance_score(slamhip_hsproc *p, const float *xy, int32_
 int32_t slamhip_hsproc_frontiers(slamhip_hsproc *p, int32_t level, int32_t world, int32_t min_cells, int32_t max_clusters,
                                  slamhip_frontier_summary *out_summary, slamhip_frontier_cluster *out_clusters,
                                  int32_t lx, int32_t ly, int32_t lw, int32_t lh, int32_t *out_labels);
+/* The cost-to-go field through the processor: slamhip_hs_nav_field on the processor's own hs with every cell in WORLD cells of
+ * spec->level.  Sources, goals and (rx, ry) are taken as world cells ((origin >> level) per axis is subtracted); the same is added to
+ * bx / by of every goal with a reached cell, to the path cells and to mx0 / my0.  No scan is needed; the processor's stored poses,
+ * its update gate and the scan that was set are not touched.  Errors as slamhip_hs_nav_field. */
+int32_t slamhip_hsproc_nav_field(slamhip_hsproc *p, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, const int32_t *goals,
+                                 int32_t G, slamhip_nav_goal_result *out_goal_results, int32_t n_paths, int32_t max_path_cells,
+                                 slamhip_nav_path *out_paths, int32_t *out_path_cells, int32_t rx, int32_t ry, int32_t rw, int32_t rh,
+                                 uint32_t *out_cost, uint8_t *out_dir, slamhip_nav_summary *out_summary);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -121,6 +121,18 @@ FRONTIER_CLUSTER = np.dtype([("seed_x", np.int32), ("seed_y", np.int32), ("n_cel
 FRONTIER_SUMMARY = np.dtype([(n, np.int32) for n in ("mx0", "my0", "mw", "mh", "n_frontier_cells", "n_runs", "n_clusters", "n_kept",
                                                      "n_returned", "kept_cells")])   # slamhip_frontier_summary: 10 int32, 40 bytes
 assert FRONTIER_CLUSTER.itemsize == 48 and FRONTIER_SUMMARY.itemsize == 40
+NAV_UNREACHED = 0xFFFFFFFF                                     # SLAMHIP_NAV_UNREACHED: the cost of an unreached cell
+NAV_DIR_SOURCE, NAV_DIR_NONE = 8, 255
+NAV_DX = (1, 1, 0, -1, -1, -1, 0, 1)                           # the direction table of slamhip_hs_nav_field, step 3
+NAV_DY = (0, 1, 1, 1, 0, -1, -1, -1)
+NAV_MAX_SOURCES, NAV_MAX_GOALS, NAV_MAX_PATHS, NAV_MAX_PATH_CELLS = 4096, 4096, 64, 65536
+NAV_SPEC = np.dtype([("level", np.int32), ("world", np.int32), ("site_mask", np.int32), ("clearance", np.int32),
+                     ("max_cost", np.uint32)])                 # slamhip_nav_spec (include/slamhip.h): 5 words, 20 bytes
+NAV_GOAL_RESULT = np.dtype([("cost", np.uint32), ("bx", np.int32), ("by", np.int32), ("n_reached", np.int32)])   # slamhip_nav_goal_result: 16 bytes
+NAV_PATH = np.dtype([("n_cells", np.int32), ("n_written", np.int32)])                                            # slamhip_nav_path: 8 bytes
+NAV_SUMMARY = np.dtype([(n, np.int32) for n in ("mx0", "my0", "mw", "mh", "n_traversable", "n_reached", "n_sources_used",
+                                                "n_sources_blocked")] + [("max_cost_reached", np.uint32), ("rounds", np.int32)])   # slamhip_nav_summary: 40 bytes
+assert NAV_SPEC.itemsize == 20 and NAV_GOAL_RESULT.itemsize == 16 and NAV_PATH.itemsize == 8 and NAV_SUMMARY.itemsize == 40
 
 
 def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
@@ -186,6 +198,7 @@ def _declare(L):
         "slamhip_debug_trace_cells": (i32, [i32, i32, i32, i32, ip, i32, ip]),
         "slamhip_debug_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "slamhip_debug_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
+        "slamhip_debug_nav_field": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -276,6 +289,7 @@ def _declare(L):
         "slamhip_hs_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "slamhip_hs_distance_score": (i32, [vp, i32, i32, i32, i32, fp, i32, vp, vp]),
         "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
+        "slamhip_hs_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -303,6 +317,7 @@ def _declare(L):
         "slamhip_hsproc_trace": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_distance_score": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
+        "slamhip_hsproc_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -443,6 +458,53 @@ def debug_frontiers(cls, min_cells=1, max_clusters=256, labels=True):
     c = np.ascontiguousarray(cls, np.uint8)
     return frontiers_call("slamhip_debug_frontiers", [c.ctypes.data_as(C.c_void_p), c.shape[1], c.shape[0]], min_cells, max_clusters,
                           c.shape if labels else None)
+
+
+def nav_call(name, head, sources, goals=None, n_paths=0, max_path_cells=1, rect=None, want_cost=True, want_dir=True):
+    """One of the three cost-to-go entry points: `head` its leading arguments (the hs or processor and a NAV_SPEC record's pointer, or
+    the hook's class array and scalars).  sources: (S, 2) cells; goals: (G, 4) rectangles {x_min, y_min, x_max, y_max}; rect = (rx, ry,
+    rw, rh): the rectangle whose costs (want_cost) and dirs (want_dir) are returned.  -> a dict: summary (a NAV_SUMMARY record), goals
+    (G NAV_GOAL_RESULT records), paths (a list of n_paths (n_written, 2) int32 arrays), path_cells (the n_paths true lengths), and with
+    rect, cost ((rh, rw) uint32) and dir ((rh, rw) uint8)."""
+    vp = C.c_void_p
+    src = np.ascontiguousarray(sources, np.int32).reshape(-1, 2)
+    gl = np.ascontiguousarray(goals if goals is not None else np.zeros((0, 4)), np.int32).reshape(-1, 4)
+    res = np.zeros(gl.shape[0], NAV_GOAL_RESULT)
+    heads = np.zeros(max(int(n_paths), 0), NAV_PATH)
+    cells = np.zeros((max(int(n_paths), 0), max(int(max_path_cells), 0), 2), np.int32)
+    summary = np.zeros(1, NAV_SUMMARY)
+    rx, ry, rw, rh = (int(v) for v in rect) if rect is not None else (0, 0, 0, 0)
+    cost = np.empty((max(rh, 0), max(rw, 0)), np.uint32) if rect is not None and want_cost else None
+    dirs = np.empty((max(rh, 0), max(rw, 0)), np.uint8) if rect is not None and want_dir else None
+    ptr = lambda a: a.ctypes.data_as(vp) if a is not None and a.size else None
+    call(name, *head, ptr(src), src.shape[0], ptr(gl), gl.shape[0], ptr(res), int(n_paths), int(max_path_cells), ptr(heads), ptr(cells),
+         rx, ry, rw, rh, cost.ctypes.data_as(vp) if cost is not None else None, dirs.ctypes.data_as(vp) if dirs is not None else None,
+         summary.ctypes.data_as(vp))
+    out = {"summary": summary[0], "goals": res, "path_cells": heads["n_cells"].copy(),
+           "paths": [cells[i, :int(heads[i]["n_written"])].copy() for i in range(heads.shape[0])]}
+    if cost is not None:
+        out["cost"] = cost
+    if dirs is not None:
+        out["dir"] = dirs
+    return out
+
+
+def nav_spec(level, world, site_mask, clearance, max_cost):
+    """A NAV_SPEC record (one-element array) from Python values."""
+    s = np.zeros(1, NAV_SPEC)
+    s[0] = (int(level), 1 if world else 0, int(site_mask), int(clearance), int(max_cost))
+    return s
+
+
+def debug_nav_field(cls, sources, site_mask=2, clearance=0, max_cost=0, goals=None, n_paths=0, max_path_cells=1, rect="all", **kw):
+    """The cost-to-go field of the definition (slamhip_hs_nav_field) over the (h, w) uint8 array `cls` of class bits, M = (0, 0, w, h)
+    (slamhip_debug_nav_field; no device involved; the costs by a sequential Dijkstra) -> nav_call's dict; rect "all": the array's own
+    rectangle."""
+    c = np.ascontiguousarray(cls, np.uint8)
+    if isinstance(rect, str):
+        rect = (0, 0, c.shape[1], c.shape[0])
+    return nav_call("slamhip_debug_nav_field", [c.ctypes.data_as(C.c_void_p), c.shape[1], c.shape[0], int(site_mask), int(clearance), int(max_cost)],
+                    sources, goals, n_paths, max_path_cells, rect, **kw)
 
 
 def check(rc):

@@ -248,6 +248,24 @@ static int32_t hs_df_enqueue(slamhip_hs *hs, int level, bool world, const hs_cla
     return SLAMHIP_OK;
 }
 
+// The field for another unit's launches on the operator's stream (K11's clearance): _prepare is hs_df_plan, _enqueue hs_df_enqueue
+// -- the class map's pack and the two launches, nothing else -- with the plan's geometry formed again from M.
+int32_t hs_df_field_prepare(slamhip_hs *hs, int level, bool world, int site_mask, int radius, hs_class_map *M, hs_field_view *V)
+{
+    k9_geo G; k9_field E;
+    SH_TRY(hs_df_plan(hs, level, world, site_mask, radius, M, &G, &E));
+    V->f = E.f; V->pitch = G.pitch; V->r = radius;
+    return SLAMHIP_OK;
+}
+int32_t hs_df_field_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M, int site_mask, int radius)
+{
+    k9_geo G;
+    G.cls = M->cls; G.w = M->w; G.h = M->h; G.wpr = M->wpr;
+    G.r = radius; G.mask = site_mask;
+    G.ew = M->w + 2 * radius; G.eh = M->h + 2 * radius; G.pitch = (G.ew + 3) & ~3;   // (as hs_df_plan, which has refused an E over 2^26 cells)
+    return hs_df_enqueue(hs, level, world, M, G);
+}
+
 extern "C" int32_t slamhip_hs_distance_field(slamhip_hs *hs, int32_t level, int32_t world, int32_t site_mask, int32_t radius,
                                              int32_t x, int32_t y, int32_t w, int32_t h, uint16_t *out_d2)
 {

@@ -43,6 +43,7 @@ struct hs_lattice;                         // hs_lattice.hip
 struct hs_trace;                           // hs_trace.hip
 struct hs_dfield;                          // hs_dfield.hip
 struct hs_frontier;                        // hs_frontier.hip
+struct hs_nav;                             // hs_nav.hip
 struct slamhip_hs {
     slamhip_ctx *ctx;
     int n_levels;
@@ -71,6 +72,7 @@ struct slamhip_hs {
     struct hs_trace *trc;                                  // slamhip_hs_trace: the poses' and the results' blocks, made by the first trace, kept
     struct hs_dfield *dfd;                                 // slamhip_hs_distance_field / _score: the field of E and the results' blocks, made by the first call, kept
     struct hs_frontier *frl;                               // slamhip_hs_frontiers: the frontier words, the union-find's arrays and the results' blocks, made by the first call, kept
+    struct hs_nav *nav;                                    // slamhip_hs_nav_field: the traversable words, costs, dirs, tile flags and the results' blocks, made by the first call, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -148,5 +150,13 @@ int32_t hs_lat_pack_enqueue(slamhip_hs *hs, int level, bool world, const hs_clas
 void    hs_trc_free(slamhip_hs *hs);        // the blocks of the beam trace (the caller has drained the stream)
 // hs_dfield.hip
 void    hs_df_free(slamhip_hs *hs);         // the blocks of the distance field (the caller has drained the stream)
+// K9's field of one level for another launch on the operator's stream: F over E = M grown by r cells, rows of `pitch` uint16_t; F of
+// M's cell (mx, my) is f[(my + r) * pitch + mx + r].  _prepare plans (the class map too), allocates and launches nothing; _enqueue
+// packs the class map and launches the field's two kernels, exactly as slamhip_hs_distance_field does.
+struct hs_field_view { const uint16_t *f; int pitch, r; };
+int32_t hs_df_field_prepare(slamhip_hs *hs, int level, bool world, int site_mask, int radius, hs_class_map *M, hs_field_view *V);
+int32_t hs_df_field_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M, int site_mask, int radius);
 // hs_frontier.hip
 void    hs_fr_free(slamhip_hs *hs);         // the blocks of the frontier labelling (the caller has drained the stream)
+// hs_nav.hip
+void    hs_nav_free(slamhip_hs *hs);        // the blocks of the cost-to-go field (the caller has drained the stream)

@@ -2,6 +2,7 @@
 #include "hs_internal.h"
 #include <algorithm>
 #include <chrono>
+#include <vector>
 
 // ---- HectorSLAMProcessor (Main/HectorSLAMProcessor.cs) ---------------------------------------------------------------
 struct slamhip_hsproc {
@@ -335,6 +336,44 @@ extern "C" int32_t slamhip_hsproc_frontiers(slamhip_hsproc *p, int32_t level, in
         c->seed_x += (int32_t)ox; c->x_min += (int32_t)ox; c->x_max += (int32_t)ox; c->sum_x += (int64_t)c->n_cells * ox;
         c->seed_y += (int32_t)oy; c->y_min += (int32_t)oy; c->y_max += (int32_t)oy; c->sum_y += (int64_t)c->n_cells * oy;
     }
+    return SLAMHIP_OK;
+}
+
+// The cost-to-go field in WORLD cells of the level: slamhip_hs_nav_field with sources, goals and the rectangle taken to the window's
+// frame ((origin >> level) per axis, clamped where a cell lies too far out to be a cell of M anyway) and the results taken back.
+extern "C" int32_t slamhip_hsproc_nav_field(slamhip_hsproc *p, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, const int32_t *goals,
+                                            int32_t G, slamhip_nav_goal_result *out_goal_results, int32_t n_paths, int32_t max_path_cells,
+                                            slamhip_nav_path *out_paths, int32_t *out_path_cells, int32_t rx, int32_t ry, int32_t rw, int32_t rh,
+                                            uint32_t *out_cost, uint8_t *out_dir, slamhip_nav_summary *out_summary)
+{
+    SH_CHECK_ARG(p && spec && out_summary);
+    if (spec->level < 0 || spec->level >= p->hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: level %d of %d", spec->level, p->hs->n_levels);
+    const int64_t ox = p->hs->win_ox >> spec->level, oy = p->hs->win_oy >> spec->level;
+    if (ox == 0 && oy == 0)
+        return slamhip_hs_nav_field(p->hs, spec, sources, S, goals, G, out_goal_results, n_paths, max_path_cells, out_paths, out_path_cells, rx, ry, rw,
+                                    rh, out_cost, out_dir, out_summary);
+    const int64_t far = (int64_t)1 << 30;                                  // (a cell that far from the window lies outside M wherever M is)
+    auto to_window = [far](int64_t v, int64_t o) { return (int32_t)std::min(std::max(v - o, -far), far); };
+    // (the counts are checked by slamhip_hs_nav_field; here they only bound the copies)
+    const size_t ns = (sources && S >= 1 && S <= 4096) ? (size_t)S : 0, ng = (goals && G >= 1 && G <= 4096) ? (size_t)G : 0;
+    std::vector<int32_t> w(2 * ns + 4 * ng);
+    for (size_t i = 0; i < ns; i++) { w[2 * i] = to_window(sources[2 * i], ox); w[2 * i + 1] = to_window(sources[2 * i + 1], oy); }
+    int32_t *wg = w.data() + 2 * ns;
+    for (size_t i = 0; i < 4 * ng; i++) wg[i] = to_window(goals[i], (i & 1) ? oy : ox);   // (monotonic: an inverted rectangle stays inverted or becomes empty outside M)
+    for (size_t i = 0; i < ng; i++)
+        if (goals[4 * i] > goals[4 * i + 2] || goals[4 * i + 1] > goals[4 * i + 3]) { wg[4 * i] = 1; wg[4 * i + 2] = 0; }   // (refused below, as given)
+    slamhip_nav_summary Sm;
+    SH_TRY(slamhip_hs_nav_field(p->hs, spec, ns ? w.data() : sources, S, ng ? wg : goals, G, out_goal_results, n_paths, max_path_cells, out_paths,
+                                out_path_cells, to_window(rx, ox), to_window(ry, oy), rw, rh, out_cost, out_dir, &Sm));
+    Sm.mx0 += (int32_t)ox; Sm.my0 += (int32_t)oy;
+    *out_summary = Sm;
+    for (int i = 0; i < G; i++)
+        if (out_goal_results[i].cost != SLAMHIP_NAV_UNREACHED) { out_goal_results[i].bx += (int32_t)ox; out_goal_results[i].by += (int32_t)oy; }
+    for (int i = 0; i < n_paths; i++)
+        for (int k = 0; k < out_paths[i].n_written; k++) {
+            out_path_cells[2 * ((size_t)i * max_path_cells + k)] += (int32_t)ox;
+            out_path_cells[2 * ((size_t)i * max_path_cells + k) + 1] += (int32_t)oy;
+        }
     return SLAMHIP_OK;
 }
 

@@ -386,6 +386,19 @@ class MapRepMultiMap:
         shape = None if labels_rect is None else (max(rect[3], 0), max(rect[2], 0))
         return capi.frontiers_call("slamhip_hs_frontiers", [self._h, int(level), 1 if world else 0], min_cells, max_clusters, shape, rect)
 
+    def nav_field(self, level, sources, clearance=0, site_mask=2, max_cost=0, world=False, goals=None, n_paths=0, max_path_cells=1,
+                  rect=None, want_cost=True, want_dir=True):
+        """The cost-to-go field of `level` (slamhip_hs_nav_field; no reference counterpart): the least 5-7 chamfer cost from the
+        `sources` ((S, 2) window-frame cells) to every traversable cell -- free, and with clearance >= 1 more than `clearance` cells
+        from every site (site_mask 2: obstacles, 3: obstacles or the unknown) -- over moves that cut no corner.  goals: (G, 4)
+        rectangles {x_min, y_min, x_max, y_max} (a frontier cluster's box, grown as the caller sees fit); the first n_paths get
+        their cell path, at most max_path_cells cells each.  rect = (x, y, w, h), any position: the costs / dirs of its cells.
+        -> capi.nav_call's dict: summary, goals, paths, path_cells[, cost, dir]; an unreached cell costs capi.NAV_UNREACHED.
+        Blocking, behind everything already enqueued; it changes nothing."""
+        spec = capi.nav_spec(level, world, site_mask, clearance, max_cost)
+        return capi.nav_call("slamhip_hs_nav_field", [self._h, spec.ctypes.data_as(C.c_void_p)], sources, goals, n_paths, max_path_cells, rect,
+                             want_cost, want_dir)
+
     def ExpectedScan(self, pose, angles, max_range, level, world=False):
         """The scan the map of `level` predicts from `pose` (window frame): per angle (rad, sensor frame) the range in metres to the
         first occupied cell on the beam of length max_range, or inf where the map holds none.  It REPLACES the scan that was set:
@@ -634,6 +647,39 @@ class HectorSLAMProcessor:
         cx = (rec["sum_x"] - n * (ox >> level)) / n * cell + float(np.float32(ox) * cell0)
         cy = (rec["sum_y"] - n * (oy >> level)) / n * cell + float(np.float32(oy) * cell0)
         return out[:2] + (np.stack([cx, cy], 1),) + out[2:]
+
+    def NavField(self, level, sources, clearance=0, site_mask=2, max_cost=0, world=False, goals=None, n_paths=0, max_path_cells=1,
+                 rect=None, want_cost=True, want_dir=True):
+        """MapRep.nav_field in WORLD cells of `level` (slamhip_hsproc_nav_field): sources, goals and rect are world cells, and so are
+        the goals' cells, the paths and mx0 / my0 of the summary.  No scan is needed; MatchPose, LastMapUpdatePose and the update gate
+        are untouched."""
+        spec = capi.nav_spec(level, world, site_mask, clearance, max_cost)
+        return capi.nav_call("slamhip_hsproc_nav_field", [self._h, spec.ctypes.data_as(C.c_void_p)], sources, goals, n_paths, max_path_cells, rect,
+                             want_cost, want_dir)
+
+    def ExploreGoals(self, level, clearance, site_mask=2, min_cells=1, max_clusters=256, grow=0, n_paths=0, max_path_cells=1, world=False):
+        """Which frontier to drive to: Frontiers, then NavField from the cell of MatchPose with each returned cluster's bounding box,
+        grown by `grow` cells on every side, as a goal (the box, not the cluster's own cells).  -> (clusters, results, nav): the
+        clusters and their capi.NAV_GOAL_RESULT records, reachable ones first by cost ascending (equal costs in Frontiers' order), the
+        unreachable ones behind them in Frontiers' order; nav is NavField's dict with `order`, the row of Frontiers' list each entry
+        came from -- nav["paths"][k] belongs to Frontiers' cluster k, for k < n_paths.  Composition only: no device work of its
+        own."""
+        rec = self.Frontiers(level, min_cells=min_cells, max_clusters=max_clusters, world=world)[1]
+        if rec.shape[0] == 0:
+            return rec, np.zeros(0, capi.NAV_GOAL_RESULT), None
+        goals = np.stack([rec["x_min"] - grow, rec["y_min"] - grow, rec["x_max"] + grow, rec["y_max"] + grow], 1)
+        nav = self.NavField(level, [self.PoseCell(level)], clearance, site_mask, world=world, goals=goals,
+                            n_paths=min(int(n_paths), goals.shape[0]), max_path_cells=max_path_cells)
+        order = np.argsort(nav["goals"]["cost"], kind="stable")          # (an unreachable goal's cost is the largest uint32)
+        nav["order"] = order
+        return rec[order], nav["goals"][order], nav
+
+    def PoseCell(self, level):
+        """The WORLD cell of `level` that MatchPose lies in: the pose over the level's CellLength, rounded as the grid update rounds
+        an end point (to nearest, ties to even)."""
+        cell = float(np.float32(self.MapRep.Maps[level].CellLength))
+        m = self.MatchPose
+        return int(np.rint(float(m[0]) / cell)), int(np.rint(float(m[1]) / cell))
 
     MatchPose = property(lambda self: self._get()[0])
     LastMapUpdatePose = property(lambda self: self._get()[1])
