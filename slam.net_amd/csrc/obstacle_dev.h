@@ -73,7 +73,8 @@ __device__ static inline void k3_walk_iter(const k3_walk &w, long long i, int si
 }
 
 // one wavefront per (ray, 64 iterations of the walk): w = ray * chunks_per_ray + chunk, one lane per iteration
-// (the part of a walk that can lie in the map is shorter than 2 * size iterations -- host: chunks_per_ray)
+// (every iteration is one step along the major axis, so the part of a walk that can lie in the map is iterations 0 .. size - 1;
+// the host launches chunks_per_ray = ceil((size + 1) / 64) wavefronts per ray: iterations 0 .. size and the rest of the last chunk)
 __device__ static inline void k3_rays_unit(int w, int lane, const float2 *__restrict__ pts, int n_points, int size, float scale,
                                            const float *d_pose, float4 h_pxcs, uint32_t *__restrict__ hits,
                                            uint8_t *__restrict__ nohit, int chunks_per_ray)
