@@ -298,6 +298,47 @@ namespace HectorSLAM.Main
             return sorted;
         }
 
+        /// <summary>MapRep.Rollouts in WORLD cells and the WORLD pose (slamhip_hsproc_rollouts): sources are world cells of
+        /// `spec.Level`, startPose a world pose (null: MatchPose), cmds nRollouts * nCmd pairs (v, w), body pairs of metres in the
+        /// robot's frame (null: none).  The results' poses and the summary's map rectangle are world values.  No scan is needed;
+        /// MatchPose, LastMapUpdatePose and the update gate are untouched.</summary>
+        public unsafe RolloutResult[] Rollouts(NavSpec spec, int[] sources, Vector3? startPose, float dt, float[] body, float[] cmds, int nCmd, int hold,
+                                               out RolloutSummary summary)
+        {
+            int n = nCmd > 0 ? cmds.Length / (2 * nCmd) : 0;
+            var res = new RolloutResult[Math.Max(n, 0)];
+            var start = stackalloc float[3];
+            if (startPose.HasValue) { start[0] = startPose.Value.X; start[1] = startPose.Value.Y; start[2] = startPose.Value.Z; }
+            fixed (int* s = sources)
+            fixed (float* b = body)
+            fixed (float* c = cmds)
+            fixed (RolloutResult* r = res)
+                Native.Check(Native.slamhip_hsproc_rollouts(proc.Ptr, ref spec, s, sources.Length / 2, startPose.HasValue ? start : null, dt, b, body == null ? 0 : body.Length / 2,
+                                                            c, n, nCmd, hold, r, out summary));
+            return res;
+        }
+
+        /// <summary>Which constant command to drive: Rollouts of the outer product of vValues and wValues (command b = (v[b / nw], w[b %
+        /// nw]), nCmd = 1, hold = steps) towards goalCells (world cells).  Returns false when no rollout has a free pose; else the
+        /// command decoded from KeyEnd -- the complete rollout that ends cheapest, fromEnd = true -- or, if nothing completes, from
+        /// KeyMin, with its record.  Composition only: no device work of its own.</summary>
+        public bool DriveCommand(int level, int[] goalCells, int clearance, float[] vValues, float[] wValues, float dt, int steps, float[] body,
+                                 out float v, out float w, out bool fromEnd, out RolloutResult result, out RolloutSummary summary, int siteMask = 2)
+        {
+            var cmds = new float[2 * vValues.Length * wValues.Length];
+            for (int i = 0; i < vValues.Length; i++)
+                for (int j = 0; j < wValues.Length; j++) { cmds[2 * (i * wValues.Length + j)] = vValues[i]; cmds[2 * (i * wValues.Length + j) + 1] = wValues[j]; }
+            var spec = new NavSpec { Level = level, World = 0, SiteMask = siteMask, Clearance = clearance, MaxCost = 0 };
+            var res = Rollouts(spec, goalCells, null, dt, body, cmds, 1, steps, out summary);
+            fromEnd = summary.KeyEnd != RolloutSummary.NoKey;
+            ulong key = fromEnd ? summary.KeyEnd : summary.KeyMin;
+            v = w = 0f; result = default;
+            if (key == RolloutSummary.NoKey) return false;
+            int b = (int)(key & 0xFFFFFFFFul);
+            v = cmds[2 * b]; w = cmds[2 * b + 1]; result = res[b];
+            return true;
+        }
+
         private void Refresh()
         {
             Native.Check(Native.slamhip_hsproc_get(proc.Ptr, out Vector3 match, out Vector3 last, out float tm, out float tu));

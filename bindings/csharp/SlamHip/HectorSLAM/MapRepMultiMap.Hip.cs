@@ -323,6 +323,43 @@ namespace HectorSLAM.Main
             return res;
         }
 
+        /// <summary>Command rollouts over the cost-to-go field of `spec.Level` (slamhip_hs_rollouts; the reference has no counterpart):
+        /// each of the cmds.Length / (2 * nCmd) sequences of nCmd pairs (v, w), each pair held for `hold` steps of dt, is rolled
+        /// forward from startPose (window frame) and cut at the first pose whose centre cell the field of `sources` does not reach or
+        /// one of whose body points (pairs of metres in the robot's frame; null: none) lies on an untraversable cell.  Blocking; it
+        /// changes nothing.</summary>
+        public unsafe RolloutResult[] Rollouts(NavSpec spec, int[] sources, Vector3 startPose, float dt, float[] body, float[] cmds, int nCmd, int hold,
+                                               out RolloutSummary summary)
+        {
+            int n = nCmd > 0 ? cmds.Length / (2 * nCmd) : 0;
+            var res = new RolloutResult[Math.Max(n, 0)];
+            var start = stackalloc float[3] { startPose.X, startPose.Y, startPose.Z };
+            fixed (int* s = sources)
+            fixed (float* b = body)
+            fixed (float* c = cmds)
+            fixed (RolloutResult* r = res)
+                Native.Check(Native.slamhip_hs_rollouts(Pyramid.Ptr, ref spec, s, sources.Length / 2, start, dt, b, body == null ? 0 : body.Length / 2, c, n, nCmd, hold, r, out summary));
+            return res;
+        }
+
+        /// <summary>The rollouts of the definition over a caller's class array on the host (slamhip_debug_rollouts): cls as for
+        /// NavFieldOf, stm = 1 / cell length.</summary>
+        public static unsafe RolloutResult[] RolloutsOf(byte[] cls, int cw, int ch, int siteMask, int clearance, uint maxCost, int[] sources, float stm, Vector3 startPose,
+                                                        float dt, float[] body, float[] cmds, int nCmd, int hold, out RolloutSummary summary)
+        {
+            int n = nCmd > 0 ? cmds.Length / (2 * nCmd) : 0;
+            var res = new RolloutResult[Math.Max(n, 0)];
+            var start = stackalloc float[3] { startPose.X, startPose.Y, startPose.Z };
+            fixed (byte* k = cls)
+            fixed (int* s = sources)
+            fixed (float* b = body)
+            fixed (float* c = cmds)
+            fixed (RolloutResult* r = res)
+                Native.Check(Native.slamhip_debug_rollouts(k, cw, ch, siteMask, clearance, maxCost, s, sources.Length / 2, stm, start, dt, b, body == null ? 0 : body.Length / 2,
+                                                           c, n, nCmd, hold, r, out summary));
+            return res;
+        }
+
         /// <summary>The sum of all shifts since construction or the last Reset, in level-0 cells (slamhip_hs_origin).</summary>
         public (long X, long Y) Origin
         {

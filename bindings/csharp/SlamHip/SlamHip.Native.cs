@@ -193,6 +193,29 @@ namespace SlamHip
         public int Rounds;
     }
 
+    /// <summary>slamhip_rollout_result (include/slamhip.h): the leading free poses of one command rollout, the step and value of the
+    /// least cost-to-go along them, the cost at the last free pose, and that pose.  7 words, 28 bytes, no padding.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct RolloutResult
+    {
+        public const uint Unreached = 0xFFFFFFFFu;
+        public int FreeCount, MinStep;
+        public uint EndCost, MinCost;
+        public float X, Y, Theta;
+    }
+
+    /// <summary>slamhip_rollout_summary (include/slamhip.h): the field's summary, the cost at the start pose, the complete rollouts
+    /// and the two keys (cost &lt;&lt; 32 | b; NoKey: no rollout qualifies).  64 bytes, no padding.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct RolloutSummary
+    {
+        public const ulong NoKey = 0xFFFFFFFFFFFFFFFFul;
+        public NavSummary Nav;
+        public uint StartCost;
+        public int CompleteCount;
+        public ulong KeyEnd, KeyMin;
+    }
+
     internal static unsafe class Native
     {
         const string Lib = "slamhip";                                   // libslamhip.so on the library path
@@ -299,6 +322,11 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_nav_field(IntPtr hs, ref NavSpec spec, int* sources, int nSources, int* goals, int nGoals, NavGoalResult* goalResults,
                                                                         int nPaths, int maxPathCells, NavPath* paths, int* pathCells, int rx, int ry, int rw, int rh, uint* cost, byte* dir,
                                                                         out NavSummary summary);
+        [DllImport(Lib)] internal static extern int slamhip_hs_rollouts(IntPtr hs, ref NavSpec spec, int* sources, int nSources, float* startPose, float dt, float* body, int nBody,
+                                                                       float* cmds, int nRollouts, int nCmd, int hold, RolloutResult* results, out RolloutSummary summary);
+        [DllImport(Lib)] internal static extern int slamhip_debug_rollouts(byte* cls, int cw, int ch, int siteMask, int clearance, uint maxCost, int* sources, int nSources, float stm,
+                                                                          float* startPose, float dt, float* body, int nBody, float* cmds, int nRollouts, int nCmd, int hold,
+                                                                          RolloutResult* results, out RolloutSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_debug_nav_field(byte* cls, int cw, int ch, int siteMask, int clearance, uint maxCost, int* sources, int nSources, int* goals,
                                                                            int nGoals, NavGoalResult* goalResults, int nPaths, int maxPathCells, NavPath* paths, int* pathCells, int rx,
                                                                            int ry, int rw, int rh, uint* cost, byte* dir, out NavSummary summary);
@@ -336,6 +364,8 @@ namespace SlamHip
                                                                                   int siteMask, int radius, DistanceSummary* summaries, ushort* pointD2);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_frontiers(IntPtr proc, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
                                                                              int lx, int ly, int lw, int lh, int* labels);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_rollouts(IntPtr proc, ref NavSpec spec, int* sources, int nSources, float* startPoseWorld, float dt, float* body, int nBody,
+                                                                           float* cmds, int nRollouts, int nCmd, int hold, RolloutResult* results, out RolloutSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_nav_field(IntPtr proc, ref NavSpec spec, int* sources, int nSources, int* goals, int nGoals, NavGoalResult* goalResults,
                                                                             int nPaths, int maxPathCells, NavPath* paths, int* pathCells, int rx, int ry, int rw, int rh, uint* cost,
                                                                             byte* dir, out NavSummary summary);

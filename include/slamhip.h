@@ -1000,6 +1000,81 @@ int32_t slamhip_debug_nav_field(const uint8_t *cls, int32_t cw, int32_t ch, int3
                                 slamhip_nav_path *out_paths, int32_t *out_path_cells, int32_t rx, int32_t ry, int32_t rw, int32_t rh,
                                 uint32_t *out_cost, uint8_t *out_dir, slamhip_nav_summary *out_summary);
 
+/* Command rollouts over the cost-to-go field (K12; no reference counterpart): B sequences of velocity commands rolled forward from
+ * one pose, each cut where the robot's body first touches something, and what the field says along and at the end of each -- the
+ * sampling step of a dynamic-window or sampling-MPC controller, on the map that is already resident.  Cells, counts and costs are
+ * integers; the poses are binary32 with EVERY OPERATION ROUNDED ON ITS OWN (no fused multiply-add), so a result is one defined bit
+ * pattern and nothing has a tolerance.
+ * THE DEFINITION, for a slamhip_nav_spec, S source cells (the goal: cost-to-go 0), a start pose P_0 = (x, y, theta) in the window's
+ * frame, a time step dt, P body points (bx_p, by_p) in metres in the robot's frame, B command sequences of n_cmd pairs (v, w) each,
+ * and hold, the number of steps each pair is held; T = n_cmd * hold:
+ *  1. Field.  M, the traversable cells, C and SLAMHIP_NAV_UNREACHED are steps 1 to 4 of slamhip_hs_nav_field for the spec and the
+ *     sources given; the clearance of the spec is how the caller pads the body.  No goals, paths, dir or rectangle are formed.  No
+ *     used source is no error: nothing is reached.
+ *  2. Poses.  For step i = 0 .. T - 1 the pair is (v, w) = cmd[b][i / hold], (s_i, c_i) = sh_det_sincosf(theta_i), d = v * dt,
+ *     x_{i+1} = x_i + d * c_i, y_{i+1} = y_i + d * s_i, theta_{i+1} = theta_i + w * dt.  Each product is rounded before its sum.
+ *     There is no angle normalisation.  Explicit Euler is the definition, not an approximation of an arc.  (sh_det_sincosf is
+ *     bit-reproducible for |theta| <= 65536; beyond that, and for a theta that is not finite, it is the platform's sinf / cosf.)
+ *  3. Cells.  With stm the level's ScaleToMap, the centre cell of pose i is ((int)rintf(x_i * stm), (int)rintf(y_i * stm)): to
+ *     nearest, ties to even -- the end-point rule of the grid update, of the trace, of the distance score and of PoseCell.  Body
+ *     point p lies at wx = (c_i * bx_p - s_i * by_p) + x_i, wy = (s_i * bx_p + c_i * by_p) + y_i; its cell is (rintf(wx * stm),
+ *     rintf(wy * stm)).  A coordinate f = m * stm that fails fabsf(f) < 16777216.0f has no cell; a NaN fails.
+ *  4. Free pose.  Pose i is FREE iff its centre has a cell with C != SLAMHIP_NAV_UNREACHED (the cell is then traversable and
+ *     connected to a source within max_cost) and every body point has a cell that is traversable.  Cells outside M never are; in
+ *     the world variant M is the world's rectangle, as for the field.
+ *  5. Per rollout, slamhip_rollout_result.  n_free: the number of leading free poses among P_0 .. P_T, in [0, T + 1]; the rollout is
+ *     COMPLETE iff n_free == T + 1.  min_step: the first i < n_free whose centre cell has the least C; min_cost: that C.  end_cost:
+ *     C at the centre of pose n_free - 1.  (x, y, theta): pose n_free - 1.  With n_free == 0: min_step = -1, both costs
+ *     SLAMHIP_NAV_UNREACHED, the pose P_0.
+ *  6. Per call, slamhip_rollout_summary.  nav: the field's summary (max_cost_reached and n_reached counted by a launch of this
+ *     call's own).  start_cost: C at P_0's centre, or SLAMHIP_NAV_UNREACHED.  n_complete.  key_end: the minimum over the complete
+ *     rollouts of ((uint64_t)end_cost << 32) | b; key_min: the same with min_cost over the rollouts with n_free >= 1; either is
+ *     UINT64_MAX if no rollout qualifies.  Equal costs go to the lowest b.
+ * The library weighs nothing against anything else and sets no threshold. */
+typedef struct slamhip_rollout_result {
+    int32_t n_free, min_step;
+    uint32_t end_cost, min_cost;
+    float x, y, theta;
+} slamhip_rollout_result;              /* 7 words: 28 bytes, no padding */
+typedef struct slamhip_rollout_summary {
+    slamhip_nav_summary nav;           /* 40 bytes */
+    uint32_t start_cost;
+    int32_t n_complete;
+    uint64_t key_end, key_min;         /* at offsets 48 and 56 */
+} slamhip_rollout_summary;             /* 64 bytes, no padding */
+/* The rollouts on spec->level.  sources: S pairs (x, y), window-frame cells; start_pose: 3 floats; body: P pairs (NULL allowed when P
+ * is 0); cmds: B * n_cmd pairs (v, w), rollout b's at cmds + 2 * b * n_cmd; out_results: B records; out_summary: one record.
+ * The launches, on the operator's stream behind everything already enqueued: what slamhip_hs_nav_field runs up to the end of its
+ * relaxation, by the same internal function (that call's own launches and results are unchanged), with its batch waits; then
+ * k12_count (n_reached and max_cost_reached: k11_dirs, which counts them for the field, is not run), ONE k12_rollout launch and a
+ * one-workgroup k12_emit, and one bounded wait.  k12_count reads every cell of M (4 bytes each) to fill those two fields.
+ * k12_rollout gives each rollout ONE lane: it integrates the state and tests the centre and then the body points of each pose
+ * one after the other against the costs and the traversable words in global memory, and goes idle as soon as a pose is not free;
+ * the device loop is bounded by T and ends for a wavefront once all its rollouts have.  (A sub-group of lanes per rollout and an
+ * LDS copy of the words around the start were built, measured and not adopted: docs/EXPERIMENTS.md.)  The keys are reduced per
+ * wavefront and merged by one 64-bit agent-scope atomic minimum per wavefront.  Commands and body points reach the device as the trace's poses do (pinned staging, one copy); the results come
+ * back through pinned staging the library owns.  The blocks belong to the hs, are made by the first call and freed by
+ * slamhip_hs_destroy; an hs that never asks allocates nothing.  Blocking.  It reads cell values only, so it works with backing off
+ * (world = window), with slamhip_hs_set_reference_cache on, and after shifts; it changes nothing of the map or of any search.  It
+ * has no timing class.
+ * SLAMHIP_ERR_INVALID, nothing launched, no output written: what slamhip_hs_nav_field refuses for spec and S; B outside [1, 65536];
+ * n_cmd or hold outside [1, 256]; T > 1024; B * n_cmd > 2^22; P outside [0, 32]; a start pose, dt or body point that is not
+ * finite; a NULL where an array is needed.  A command that is not finite is no error: its poses have no cell.  A poisoned context:
+ * SLAMHIP_ERR_TIMEOUT.  The limits are design conditions, not measurements: the sizes of the staging blocks (32 MB of commands, 1.8
+ * MB of results), a sub-group that fits a wavefront, and a device loop with a small fixed bound. */
+int32_t slamhip_hs_rollouts(slamhip_hs *hs, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, const float start_pose[3],
+                            float dt, const float *body, int32_t P, const float *cmds, int32_t B, int32_t n_cmd, int32_t hold,
+                            slamhip_rollout_result *out_results, slamhip_rollout_summary *out_summary);
+/* Test hook (no device involved): the rollouts of the definition over a caller's class array, M = (0, 0, cw, ch), stm the
+ * ScaleToMap (1 / cell length).  The field comes from the function slamhip_debug_nav_field builds its costs with (a sequential
+ * Dijkstra), the rollouts from the header text the kernel runs (hs_rollout.h), in a plain loop; nav.rounds = 0.  Everything else as
+ * slamhip_hs_rollouts.  SLAMHIP_ERR_INVALID: cw or ch < 1, cw * ch > 2^25, stm not finite or <= 0, and the argument checks of
+ * slamhip_hs_rollouts. */
+int32_t slamhip_debug_rollouts(const uint8_t *cls, int32_t cw, int32_t ch, int32_t site_mask, int32_t clearance, uint32_t max_cost,
+                               const int32_t *sources, int32_t S, float stm, const float start_pose[3], float dt, const float *body,
+                               int32_t P, const float *cmds, int32_t B, int32_t n_cmd, int32_t hold,
+                               slamhip_rollout_result *out_results, slamhip_rollout_summary *out_summary);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -1203,6 +1278,15 @@ int32_t slamhip_hsproc_nav_field(slamhip_hsproc *p, const slamhip_nav_spec *spec
                                  int32_t G, slamhip_nav_goal_result *out_goal_results, int32_t n_paths, int32_t max_path_cells,
                                  slamhip_nav_path *out_paths, int32_t *out_path_cells, int32_t rx, int32_t ry, int32_t rw, int32_t rh,
                                  uint32_t *out_cost, uint8_t *out_dir, slamhip_nav_summary *out_summary);
+/* The command rollouts through the processor: slamhip_hs_rollouts on the processor's own hs in WORLD cells and the WORLD pose.
+ * sources are world cells of the level; start_pose_world is a world pose, or NULL for MatchPose.  The pose is taken to the window's
+ * frame as slamhip_hsproc_trace takes its poses (minus (float)origin * cell0 per axis) and the results' poses taken back by the same
+ * offset; nav.mx0 / nav.my0 are re-based by (origin >> level) as slamhip_hsproc_nav_field re-bases them.  With the origin at (0, 0)
+ * every bit passes through.  No scan is needed; MatchPose, LastMapUpdatePose and the update gate are untouched.  Errors as
+ * slamhip_hs_rollouts. */
+int32_t slamhip_hsproc_rollouts(slamhip_hsproc *p, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S,
+                                const float *start_pose_world, float dt, const float *body, int32_t P, const float *cmds, int32_t B,
+                                int32_t n_cmd, int32_t hold, slamhip_rollout_result *out_results, slamhip_rollout_summary *out_summary);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -133,6 +133,13 @@ NAV_PATH = np.dtype([("n_cells", np.int32), ("n_written", np.int32)])           
 NAV_SUMMARY = np.dtype([(n, np.int32) for n in ("mx0", "my0", "mw", "mh", "n_traversable", "n_reached", "n_sources_used",
                                                 "n_sources_blocked")] + [("max_cost_reached", np.uint32), ("rounds", np.int32)])   # slamhip_nav_summary: 40 bytes
 assert NAV_SPEC.itemsize == 20 and NAV_GOAL_RESULT.itemsize == 16 and NAV_PATH.itemsize == 8 and NAV_SUMMARY.itemsize == 40
+ROLLOUT_MAX_B, ROLLOUT_MAX_CMD, ROLLOUT_MAX_T, ROLLOUT_MAX_POINTS = 65536, 256, 1024, 32   # the limits of slamhip_hs_rollouts
+ROLLOUT_RESULT = np.dtype([("n_free", np.int32), ("min_step", np.int32), ("end_cost", np.uint32), ("min_cost", np.uint32),
+                           ("x", np.float32), ("y", np.float32), ("theta", np.float32)])   # slamhip_rollout_result: 7 words, 28 bytes
+ROLLOUT_SUMMARY = np.dtype([("nav", NAV_SUMMARY), ("start_cost", np.uint32), ("n_complete", np.int32), ("key_end", np.uint64),
+                            ("key_min", np.uint64)])           # slamhip_rollout_summary: 64 bytes, no padding
+ROLLOUT_NO_KEY = 0xFFFFFFFFFFFFFFFF                            # key_end / key_min when no rollout qualifies
+assert ROLLOUT_RESULT.itemsize == 28 and ROLLOUT_SUMMARY.itemsize == 64
 
 
 def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
@@ -199,6 +206,7 @@ def _declare(L):
         "slamhip_debug_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "slamhip_debug_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_nav_field": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "slamhip_debug_rollouts": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, C.c_float, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -290,6 +298,7 @@ def _declare(L):
         "slamhip_hs_distance_score": (i32, [vp, i32, i32, i32, i32, fp, i32, vp, vp]),
         "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hs_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "slamhip_hs_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -318,6 +327,7 @@ def _declare(L):
         "slamhip_hsproc_distance_score": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hsproc_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "slamhip_hsproc_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -505,6 +515,41 @@ def debug_nav_field(cls, sources, site_mask=2, clearance=0, max_cost=0, goals=No
         rect = (0, 0, c.shape[1], c.shape[0])
     return nav_call("slamhip_debug_nav_field", [c.ctypes.data_as(C.c_void_p), c.shape[1], c.shape[0], int(site_mask), int(clearance), int(max_cost)],
                     sources, goals, n_paths, max_path_cells, rect, **kw)
+
+
+def rollouts_call(name, head, sources, start_pose, dt, body, cmds, hold=1, stm=None):
+    """One of the three rollout entry points: `head` its leading arguments (the hs or processor and a NAV_SPEC record's pointer, or
+    the hook's class array and scalars; stm: the hook's ScaleToMap, which it takes behind the sources).  sources: (S, 2) cells; start_pose: 3 floats or None (the processor's MatchPose); body: (P, 2) metres in the
+    robot's frame or None; cmds: (B, n_cmd, 2) pairs (v, w).  -> (results, summary): B ROLLOUT_RESULT records and a ROLLOUT_SUMMARY
+    record."""
+    vp = C.c_void_p
+    mid = [C.c_float(stm)] if stm is not None else []
+    src = np.ascontiguousarray(sources, np.int32).reshape(-1, 2)
+    pose = f32(start_pose, (3,)) if start_pose is not None else None
+    bd = f32(body if body is not None else np.zeros((0, 2)), (-1, 2))
+    cm = f32(cmds)
+    if cm.ndim != 3 or cm.shape[2] != 2:
+        raise ValueError("rollouts: cmds must be (B, n_cmd, 2)")
+    res = np.zeros(cm.shape[0], ROLLOUT_RESULT)
+    summary = np.zeros(1, ROLLOUT_SUMMARY)
+    ptr = lambda a: a.ctypes.data_as(vp) if a is not None and a.size else None
+    call(name, *head, ptr(src), src.shape[0], *mid, ptr(pose), C.c_float(dt), ptr(bd), bd.shape[0], ptr(cm), cm.shape[0], cm.shape[1], int(hold),
+         ptr(res), summary.ctypes.data_as(vp))
+    return res, summary[0]
+
+
+def debug_rollouts(cls, sources, stm, start_pose, dt, body, cmds, hold=1, site_mask=2, clearance=0, max_cost=0):
+    """The command rollouts of the definition (slamhip_hs_rollouts) over the (h, w) uint8 array `cls` of class bits, M = (0, 0, w, h),
+    stm = 1 / cell length (slamhip_debug_rollouts; no device involved) -> rollouts_call's pair."""
+    c = np.ascontiguousarray(cls, np.uint8)
+    return rollouts_call("slamhip_debug_rollouts", [c.ctypes.data_as(C.c_void_p), c.shape[1], c.shape[0], int(site_mask), int(clearance), int(max_cost)],
+                         sources, start_pose, dt, body, cmds, hold, stm)
+
+
+def rollout_key(key):
+    """(cost, b) of a key_end / key_min, or None for ROLLOUT_NO_KEY."""
+    key = int(key)
+    return None if key == ROLLOUT_NO_KEY else (key >> 32, key & 0xFFFFFFFF)
 
 
 def check(rc):

@@ -44,6 +44,7 @@ struct hs_trace;                           // hs_trace.hip
 struct hs_dfield;                          // hs_dfield.hip
 struct hs_frontier;                        // hs_frontier.hip
 struct hs_nav;                             // hs_nav.hip
+struct hs_rollout;                         // hs_rollout.hip
 struct slamhip_hs {
     slamhip_ctx *ctx;
     int n_levels;
@@ -73,6 +74,7 @@ struct slamhip_hs {
     struct hs_dfield *dfd;                                 // slamhip_hs_distance_field / _score: the field of E and the results' blocks, made by the first call, kept
     struct hs_frontier *frl;                               // slamhip_hs_frontiers: the frontier words, the union-find's arrays and the results' blocks, made by the first call, kept
     struct hs_nav *nav;                                    // slamhip_hs_nav_field: the traversable words, costs, dirs, tile flags and the results' blocks, made by the first call, kept
+    struct hs_rollout *rol;                                // slamhip_hs_rollouts: the commands', body points' and results' blocks, made by the first call, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -160,3 +162,20 @@ int32_t hs_df_field_enqueue(slamhip_hs *hs, int level, bool world, const hs_clas
 void    hs_fr_free(slamhip_hs *hs);         // the blocks of the frontier labelling (the caller has drained the stream)
 // hs_nav.hip
 void    hs_nav_free(slamhip_hs *hs);        // the blocks of the cost-to-go field (the caller has drained the stream)
+// K11's counter block (k11_peek and k11_emit store it to pinned memory)
+#define K11_C_TRAV 0
+#define K11_C_REACHED 1
+#define K11_C_USED 2
+#define K11_C_BLOCKED 3
+#define K11_C_MAXCOST 4
+#define K11_C_FLAG 5
+#define K11_CTRS 8
+// K11's field of one level for another launch on the operator's stream (slamhip_hs_rollouts): what slamhip_hs_nav_field runs up to
+// the end of its relaxation, by the same function.  _check refuses what that call refuses for spec and sources, nothing launched;
+// _for_rollouts returns with the costs of M final in device memory and the stream drained (the batch waits are the field's own).
+// K11_C_REACHED and K11_C_MAXCOST of ctr are still 0: k11_dirs, which counts them, is not run.
+struct hs_nav_view { const uint32_t *tw; const uint32_t *cost; uint32_t *ctr; int twpr; hs_class_map M; int rounds; };
+int32_t hs_nav_check_field(int n_levels, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S);
+int32_t hs_nav_field_for_rollouts(slamhip_hs *hs, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, hs_nav_view *out);
+// hs_rollout.hip
+void    hs_ro_free(slamhip_hs *hs);         // the blocks of the command rollouts (the caller has drained the stream)

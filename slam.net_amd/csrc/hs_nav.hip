@@ -32,6 +32,7 @@
 //  * k11_emit: the counters, the goal results and the path heads into pinned memory.
 #include "hs_internal.h"
 #include "hs_nav.h"
+#include "hs_nav_host.h"
 #include <algorithm>
 #include <functional>
 #include <new>
@@ -45,14 +46,7 @@
 #define K11_ROWS (K11_TILE * K11_TILE / K11_LANES)   // rows of its column a lane owns
 #define K11_PITCH (K11_TILE + 2)
 #define K11_TW ((K11_PITCH + 31) / 32)     // traversable words of a tile row with its halo
-// the counter block
-#define K11_C_TRAV 0
-#define K11_C_REACHED 1
-#define K11_C_USED 2
-#define K11_C_BLOCKED 3
-#define K11_C_MAXCOST 4
-#define K11_C_FLAG 5
-#define K11_CTRS 8
+// (the counter block, K11_C_* and K11_CTRS: hs_internal.h)
 
 static_assert(sizeof(slamhip_nav_spec) == 20 && sizeof(slamhip_nav_goal_result) == 16 && sizeof(slamhip_nav_path) == 8 &&
               sizeof(slamhip_nav_summary) == 40, "the records of include/slamhip.h");
@@ -401,17 +395,26 @@ static void hs_nav_summary_of(const uint32_t *ctr, int x0, int y0, int w, int h,
     S->max_cost_reached = ctr[K11_C_MAXCOST]; S->rounds = rounds;
 }
 
-extern "C" int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, const int32_t *goals,
-                                        int32_t G, slamhip_nav_goal_result *out_goal_results, int32_t n_paths, int32_t max_path_cells,
-                                        slamhip_nav_path *out_paths, int32_t *out_path_cells, int32_t rx, int32_t ry, int32_t rw, int32_t rh,
-                                        uint32_t *out_cost, uint8_t *out_dir, slamhip_nav_summary *out_summary)
+// What slamhip_hs_nav_field refuses for its spec and sources alone (slamhip_hs_rollouts refuses the same).
+int32_t hs_nav_check_field(int n_levels, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S)
 {
-    SH_CHECK_ARG(hs && spec && out_summary);
-    const int level = spec->level, c = spec->clearance;
-    if (level < 0 || level >= hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: level %d of %d", level, hs->n_levels);
+    if (spec->level < 0 || spec->level >= n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: level %d of %d", spec->level, n_levels);
     if (spec->world != 0 && spec->world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: world = %d must be 0 (the window) or 1 (the world)", spec->world);
+    return hs_nav_check(spec->site_mask, spec->clearance, sources, S, nullptr, 0, nullptr, 0, 1, nullptr, nullptr, 0, 0, nullptr, nullptr);
+}
+
+// what the field's build leaves for the launches behind it
+struct hs_nav_built { k11_geo A; hs_class_map M; int64_t cells; int rounds; const int *d_goals; size_t src_bytes, goal_bytes; };
+
+// Steps 1 to 4 of the definition on the operator's stream -- the class map, the field for a clearance, k11_trav, k11_seed and the
+// relaxation rounds with their batch waits -- for slamhip_hs_nav_field and slamhip_hs_rollouts alike: when it returns the costs of
+// every cell of M are final in device memory and the stream has drained.  The arguments are checked by the caller.  goals: G
+// rectangles copied behind the sources; pc_bytes, rc_bytes, rd_bytes: the path cells and the rectangle the caller will ask for.
+static int32_t hs_nav_build(slamhip_hs *hs, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, const int32_t *goals, int32_t G,
+                            size_t pc_bytes, size_t rc_bytes, size_t rd_bytes, hs_nav_built *out)
+{
+    const int level = spec->level, c = spec->clearance;
     const bool world = spec->world != 0;
-    SH_TRY(hs_nav_check(spec->site_mask, c, sources, S, goals, G, out_goal_results, n_paths, max_path_cells, out_paths, out_path_cells, rw, rh, out_cost, out_dir));
     slamhip_ctx *ctx = hs->ctx;
     if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
     SH_HIP(hipSetDevice(ctx->device));
@@ -434,11 +437,7 @@ extern "C" int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *
     A.tiles_x = sh_div_up(M.w, K11_TILE); A.tiles_y = sh_div_up(M.h, K11_TILE);
     A.max_cost = spec->max_cost; A.x0 = M.x0; A.y0 = M.y0;
     const int nt = A.tiles_x * A.tiles_y;
-    const bool rect = out_cost || out_dir;
-    const int n_rect = rect ? rw * rh : 0;
     const size_t src_bytes = sizeof(int) * 2 * (size_t)S, goal_bytes = sizeof(int) * 4 * (size_t)G;
-    const size_t pc_bytes = sizeof(int) * 2 * (size_t)n_paths * (size_t)max_path_cells;
-    const size_t rc_bytes = out_cost ? sizeof(uint32_t) * (size_t)n_rect : 0, rd_bytes = out_dir ? ((size_t)n_rect + 3) & ~(size_t)3 : 0;
     const size_t act_bytes = ((size_t)2 * nt + 15) & ~(size_t)15;
     // (the blocks are idle: every call waits for its own launches, and a call that timed out has poisoned the context)
     SH_TRY(hs_nav_grow((void **)&nv->d_tw, &nv->cap_tw, sizeof(uint32_t) * (size_t)A.twpr * M.h, false));
@@ -449,14 +448,12 @@ extern "C" int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *
     SH_TRY(hs_nav_grow((void **)&nv->d_batch, &nv->cap_batch, sizeof(uint32_t) * K11_MAX_BATCH, false));
     SH_TRY(hs_nav_grow((void **)&nv->d_in, &nv->cap_in, src_bytes + goal_bytes, false));
     SH_TRY(hs_nav_grow((void **)&nv->d_res, &nv->cap_res, sizeof(slamhip_nav_goal_result) * (size_t)HS_NAV_MAX_GOALS + sizeof(slamhip_nav_path) * HS_NAV_MAX_PATHS, false));
-    if (n_paths) SH_TRY(hs_nav_grow((void **)&nv->d_pcells, &nv->cap_pcells, pc_bytes, false));
-    if (rect) SH_TRY(hs_nav_grow((void **)&nv->d_rect, &nv->cap_rect, rc_bytes + rd_bytes, false));
+    if (pc_bytes) SH_TRY(hs_nav_grow((void **)&nv->d_pcells, &nv->cap_pcells, pc_bytes, false));
+    if (rc_bytes + rd_bytes) SH_TRY(hs_nav_grow((void **)&nv->d_rect, &nv->cap_rect, rc_bytes + rd_bytes, false));
     SH_TRY(hs_nav_grow((void **)&nv->h_head, &nv->cap_head, HS_NAV_HEAD_BYTES, true));
     SH_TRY(hs_nav_grow((void **)&nv->h_io, &nv->cap_io, std::max(src_bytes + goal_bytes, pc_bytes + rc_bytes + rd_bytes), true));
     A.tw = nv->d_tw; A.cost = nv->d_cost; A.dir = nv->d_dir; A.act = nv->d_act; A.ctr = nv->d_ctr;
-    int *d_src = nv->d_in, *d_goals = nv->d_in + 2 * (size_t)S;
-    slamhip_nav_goal_result *d_res = (slamhip_nav_goal_result *)nv->d_res;
-    slamhip_nav_path *d_heads = (slamhip_nav_path *)(nv->d_res + sizeof(slamhip_nav_goal_result) * (size_t)HS_NAV_MAX_GOALS);
+    int *d_src = nv->d_in;
     const int batch = (int)std::min<long long>(std::max<long long>(sh_env_int("SLAMHIP_NAV_BATCH", K11_BATCH), 1), K11_MAX_BATCH);
     hipStream_t st = ctx->stream;
     memcpy(nv->h_io, sources, src_bytes);
@@ -472,7 +469,7 @@ extern "C" int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *
     SH_HIP(hipGetLastError());
     hipLaunchKernelGGL(k11_seed, dim3((unsigned)sh_div_up(S, 256)), dim3(256), 0, st, A, (const int *)d_src, S);
     SH_HIP(hipGetLastError());
-    const uint32_t *peek = nv->h_head, *head = nv->h_head + HS_NAV_PEEK_WORDS;
+    const uint32_t *peek = nv->h_head;
     int rounds = 0;
     for (int64_t issued = 0;;) {
         SH_HIP(hipMemsetAsync(nv->d_batch, 0, sizeof(uint32_t) * K11_MAX_BATCH, st));
@@ -493,6 +490,47 @@ extern "C" int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *
         if (issued > (int64_t)peek[K11_MAX_BATCH + K11_C_TRAV] + 1)        // (a shortest path is simple: it crosses tile borders fewer times than it has cells)
             SH_FAIL(SLAMHIP_ERR_STATE, "navigation field did not converge in %lld rounds (level %d, M of %d x %d cells)", (long long)issued, level, M.w, M.h);
     }
+    out->A = A; out->M = M; out->cells = cells; out->rounds = rounds;
+    out->d_goals = nv->d_in + 2 * (size_t)S; out->src_bytes = src_bytes; out->goal_bytes = goal_bytes;
+    return SLAMHIP_OK;
+}
+
+// The field for slamhip_hs_rollouts (hs_rollout.hip): hs_nav_build with no goals, no paths and no rectangle.
+int32_t hs_nav_field_for_rollouts(slamhip_hs *hs, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, hs_nav_view *out)
+{
+    hs_nav_built Bt;
+    SH_TRY(hs_nav_build(hs, spec, sources, S, nullptr, 0, 0, 0, 0, &Bt));
+    out->tw = Bt.A.tw; out->cost = Bt.A.cost; out->ctr = Bt.A.ctr; out->twpr = Bt.A.twpr; out->M = Bt.M; out->rounds = Bt.rounds;
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, const int32_t *goals,
+                                        int32_t G, slamhip_nav_goal_result *out_goal_results, int32_t n_paths, int32_t max_path_cells,
+                                        slamhip_nav_path *out_paths, int32_t *out_path_cells, int32_t rx, int32_t ry, int32_t rw, int32_t rh,
+                                        uint32_t *out_cost, uint8_t *out_dir, slamhip_nav_summary *out_summary)
+{
+    SH_CHECK_ARG(hs && spec && out_summary);
+    const int level = spec->level;
+    if (level < 0 || level >= hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: level %d of %d", level, hs->n_levels);
+    if (spec->world != 0 && spec->world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: world = %d must be 0 (the window) or 1 (the world)", spec->world);
+    SH_TRY(hs_nav_check(spec->site_mask, spec->clearance, sources, S, goals, G, out_goal_results, n_paths, max_path_cells, out_paths, out_path_cells, rw, rh, out_cost, out_dir));
+    const bool rect = out_cost || out_dir;
+    const int n_rect = rect ? rw * rh : 0;
+    const size_t pc_bytes = sizeof(int) * 2 * (size_t)n_paths * (size_t)max_path_cells;
+    const size_t rc_bytes = out_cost ? sizeof(uint32_t) * (size_t)n_rect : 0, rd_bytes = out_dir ? ((size_t)n_rect + 3) & ~(size_t)3 : 0;
+    hs_nav_built Bt;
+    SH_TRY(hs_nav_build(hs, spec, sources, S, goals, G, pc_bytes, rc_bytes, rd_bytes, &Bt));
+    slamhip_ctx *ctx = hs->ctx;
+    hs_nav *nv = hs->nav;
+    const k11_geo &A = Bt.A;
+    const hs_class_map &M = Bt.M;
+    const int64_t cells = Bt.cells;
+    const int rounds = Bt.rounds;
+    const int *d_goals = Bt.d_goals;
+    slamhip_nav_goal_result *d_res = (slamhip_nav_goal_result *)nv->d_res;
+    slamhip_nav_path *d_heads = (slamhip_nav_path *)(nv->d_res + sizeof(slamhip_nav_goal_result) * (size_t)HS_NAV_MAX_GOALS);
+    hipStream_t st = ctx->stream;
+    const uint32_t *head = nv->h_head + HS_NAV_PEEK_WORDS;
     hipLaunchKernelGGL(k11_dirs, dim3((unsigned)sh_div_up((int)cells, 256)), dim3(256), 0, st, A, (int)cells);
     SH_HIP(hipGetLastError());
     if (G) {
@@ -532,23 +570,15 @@ extern "C" int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *
     return SLAMHIP_OK;
 }
 
-// CPU-side test hook: the field of the definition over a caller's class array, M = (0, 0, cw, ch).  The classes are packed as K7
-// packs them and the field for a clearance comes from slamhip_debug_distance_field; the traversable words, the moves and the dirs
-// are hs_nav.h's -- the text the kernels run -- but the costs come from a plain sequential Dijkstra with a binary heap, not from
-// the tiled relaxation.
-extern "C" int32_t slamhip_debug_nav_field(const uint8_t *cls, int32_t cw, int32_t ch, int32_t site_mask, int32_t clearance, uint32_t max_cost,
-                                           const int32_t *sources, int32_t S, const int32_t *goals, int32_t G,
-                                           slamhip_nav_goal_result *out_goal_results, int32_t n_paths, int32_t max_path_cells,
-                                           slamhip_nav_path *out_paths, int32_t *out_path_cells, int32_t rx, int32_t ry, int32_t rw, int32_t rh,
-                                           uint32_t *out_cost, uint8_t *out_dir, slamhip_nav_summary *out_summary)
+// Steps 1 to 4 over a caller's class array for the two hooks (hs_nav_host.h): the traversable words, the costs by Dijkstra and three
+// of the counters.
+int32_t hs_nav_debug_costs(const uint8_t *cls, int32_t cw, int32_t ch, int32_t site_mask, int32_t clearance, uint32_t max_cost, const int32_t *sources,
+                           int32_t S, std::vector<uint32_t> &tw, std::vector<uint32_t> &cost, uint32_t ctr[K11_CTRS])
 {
-    SH_CHECK_ARG(cls && out_summary);
-    if (cw < 1 || ch < 1 || (int64_t)cw * ch > HS_NAV_MAX_M)
-        SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: a class array of %d x %d cells; cw, ch >= 1 and cw * ch <= 2^25", cw, ch);
-    SH_TRY(hs_nav_check(site_mask, clearance, sources, S, goals, G, out_goal_results, n_paths, max_path_cells, out_paths, out_path_cells, rw, rh, out_cost, out_dir));
     const int wpr = (cw + 15) / 16, twpr = (cw + 31) / 32;
     const size_t cells = (size_t)cw * ch;
-    std::vector<uint32_t> packed((size_t)wpr * ch, 0u), tw((size_t)twpr * ch);
+    std::vector<uint32_t> packed((size_t)wpr * ch, 0u);
+    tw.assign((size_t)twpr * ch, 0u);
     for (int cy = 0; cy < ch; cy++)
         for (int cx = 0; cx < cw; cx++) packed[(size_t)cy * wpr + (cx >> 4)] |= (uint32_t)(cls[(size_t)cy * cw + cx] & 3u) << (2 * (cx & 15));
     std::vector<uint16_t> F;
@@ -556,7 +586,6 @@ extern "C" int32_t slamhip_debug_nav_field(const uint8_t *cls, int32_t cw, int32
         F.resize(cells);
         SH_TRY(slamhip_debug_distance_field(cls, cw, ch, site_mask, clearance + 1, 0, 0, cw, ch, F.data()));
     }
-    uint32_t ctr[K11_CTRS] = { 0 };
     for (int y = 0; y < ch; y++)
         for (int j = 0; j < twpr; j++) {
             const uint32_t t = hs_nav_trav_word(packed.data() + (size_t)y * wpr, cw, 32 * j, clearance >= 1 ? F.data() + (size_t)y * cw + 32 * j : (const uint16_t *)nullptr,
@@ -569,7 +598,7 @@ extern "C" int32_t slamhip_debug_nav_field(const uint8_t *cls, int32_t cw, int32
         const uint32_t *up = y > 0 ? self - twpr : (const uint32_t *)nullptr, *down = y + 1 < ch ? self + twpr : (const uint32_t *)nullptr;
         return hs_nav_moves(hs_nav_bits3(up, twpr, x), hs_nav_bits3(self, twpr, x), hs_nav_bits3(down, twpr, x));
     };
-    std::vector<uint32_t> cost(cells, HS_NAV_UNREACHED);
+    cost.assign(cells, HS_NAV_UNREACHED);
     typedef std::pair<uint32_t, int> item;
     std::priority_queue<item, std::vector<item>, std::greater<item>> heap;
     for (int i = 0; i < S; i++) {
@@ -591,6 +620,33 @@ extern "C" int32_t slamhip_debug_nav_field(const uint8_t *cls, int32_t cw, int32
             if (v < cost[(size_t)n]) { cost[(size_t)n] = v; heap.push(item(v, n)); }
         }
     }
+    return SLAMHIP_OK;
+}
+
+// CPU-side test hook: the field of the definition over a caller's class array, M = (0, 0, cw, ch).  The classes are packed as K7
+// packs them and the field for a clearance comes from slamhip_debug_distance_field; the traversable words, the moves and the dirs
+// are hs_nav.h's -- the text the kernels run -- but the costs come from a plain sequential Dijkstra with a binary heap, not from
+// the tiled relaxation.
+extern "C" int32_t slamhip_debug_nav_field(const uint8_t *cls, int32_t cw, int32_t ch, int32_t site_mask, int32_t clearance, uint32_t max_cost,
+                                           const int32_t *sources, int32_t S, const int32_t *goals, int32_t G,
+                                           slamhip_nav_goal_result *out_goal_results, int32_t n_paths, int32_t max_path_cells,
+                                           slamhip_nav_path *out_paths, int32_t *out_path_cells, int32_t rx, int32_t ry, int32_t rw, int32_t rh,
+                                           uint32_t *out_cost, uint8_t *out_dir, slamhip_nav_summary *out_summary)
+{
+    SH_CHECK_ARG(cls && out_summary);
+    if (cw < 1 || ch < 1 || (int64_t)cw * ch > HS_NAV_MAX_M)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: a class array of %d x %d cells; cw, ch >= 1 and cw * ch <= 2^25", cw, ch);
+    SH_TRY(hs_nav_check(site_mask, clearance, sources, S, goals, G, out_goal_results, n_paths, max_path_cells, out_paths, out_path_cells, rw, rh, out_cost, out_dir));
+    const int twpr = (cw + 31) / 32;
+    const size_t cells = (size_t)cw * ch;
+    std::vector<uint32_t> tw, cost;
+    uint32_t ctr[K11_CTRS] = { 0 };
+    SH_TRY(hs_nav_debug_costs(cls, cw, ch, site_mask, clearance, max_cost, sources, S, tw, cost, ctr));
+    auto moves = [&](int x, int y) {
+        const uint32_t *self = tw.data() + (size_t)y * twpr;
+        const uint32_t *up = y > 0 ? self - twpr : (const uint32_t *)nullptr, *down = y + 1 < ch ? self + twpr : (const uint32_t *)nullptr;
+        return hs_nav_moves(hs_nav_bits3(up, twpr, x), hs_nav_bits3(self, twpr, x), hs_nav_bits3(down, twpr, x));
+    };
     std::vector<uint8_t> dir(cells);
     for (int y = 0; y < ch; y++)
         for (int x = 0; x < cw; x++) {

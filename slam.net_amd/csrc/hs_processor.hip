@@ -377,6 +377,37 @@ extern "C" int32_t slamhip_hsproc_nav_field(slamhip_hsproc *p, const slamhip_nav
     return SLAMHIP_OK;
 }
 
+// The command rollouts in WORLD cells and the WORLD pose: slamhip_hs_rollouts with the sources taken to the window's frame as
+// slamhip_hsproc_nav_field takes them, the start pose as slamhip_hsproc_trace takes its poses (NULL: MatchPose, which is kept in the
+// window's frame), and M and the results' poses taken back.  With the origin at (0, 0) every bit passes through.
+extern "C" int32_t slamhip_hsproc_rollouts(slamhip_hsproc *p, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S,
+                                           const float *start_pose_world, float dt, const float *body, int32_t P, const float *cmds, int32_t B,
+                                           int32_t n_cmd, int32_t hold, slamhip_rollout_result *out_results, slamhip_rollout_summary *out_summary)
+{
+    SH_CHECK_ARG(p && spec && out_summary);
+    if (spec->level < 0 || spec->level >= p->hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: level %d of %d", spec->level, p->hs->n_levels);
+    const bool moved = p->hs->win_ox != 0 || p->hs->win_oy != 0;
+    const int64_t ox = p->hs->win_ox >> spec->level, oy = p->hs->win_oy >> spec->level;
+    float off[2];
+    hsproc_window_offset(p, off);
+    float start[3];
+    if (!start_pose_world) memcpy(start, p->match_pose, sizeof(start));
+    else if (moved) { start[0] = start_pose_world[0] - off[0]; start[1] = start_pose_world[1] - off[1]; start[2] = start_pose_world[2]; }
+    else memcpy(start, start_pose_world, sizeof(start));
+    if (!moved) return slamhip_hs_rollouts(p->hs, spec, sources, S, start, dt, body, P, cmds, B, n_cmd, hold, out_results, out_summary);
+    const int64_t far = (int64_t)1 << 30;                                  // (a cell that far from the window lies outside M wherever M is)
+    auto to_window = [far](int64_t v, int64_t o) { return (int32_t)std::min(std::max(v - o, -far), far); };
+    const size_t ns = (sources && S >= 1 && S <= 4096) ? (size_t)S : 0;    // (the count is checked by slamhip_hs_rollouts; here it only bounds the copy)
+    std::vector<int32_t> w(2 * ns);
+    for (size_t i = 0; i < ns; i++) { w[2 * i] = to_window(sources[2 * i], ox); w[2 * i + 1] = to_window(sources[2 * i + 1], oy); }
+    slamhip_rollout_summary Sm;
+    SH_TRY(slamhip_hs_rollouts(p->hs, spec, ns ? w.data() : sources, S, start, dt, body, P, cmds, B, n_cmd, hold, out_results, &Sm));
+    Sm.nav.mx0 += (int32_t)ox; Sm.nav.my0 += (int32_t)oy;
+    *out_summary = Sm;
+    for (int i = 0; i < B; i++) { out_results[i].x = out_results[i].x + off[0]; out_results[i].y = out_results[i].y + off[1]; }
+    return SLAMHIP_OK;
+}
+
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)
 {
     SH_CHECK_ARG(p);

@@ -399,6 +399,17 @@ class MapRepMultiMap:
         return capi.nav_call("slamhip_hs_nav_field", [self._h, spec.ctypes.data_as(C.c_void_p)], sources, goals, n_paths, max_path_cells, rect,
                              want_cost, want_dir)
 
+    def rollouts(self, level, sources, start_pose, dt, cmds, hold=1, body=None, clearance=0, site_mask=2, max_cost=0, world=False):
+        """Command rollouts over the cost-to-go field of `level` (slamhip_hs_rollouts; no reference counterpart): each of the B
+        sequences cmds[b] ((B, n_cmd, 2) pairs (v, w), each held for `hold` steps of dt) is rolled forward from start_pose
+        (window frame) by explicit Euler steps and cut at the first pose whose centre cell is not reached by the field of
+        `sources` ((S, 2) window-frame cells, the goal) or one of whose `body` points ((P, 2) metres, robot frame) lies on an
+        untraversable cell.  -> (results, summary): B capi.ROLLOUT_RESULT records (n_free, min_step, end_cost, min_cost, x, y, theta)
+        and a capi.ROLLOUT_SUMMARY record (the field's summary under "nav", start_cost, n_complete, key_end, key_min;
+        capi.rollout_key decodes a key).  Blocking, behind everything already enqueued; it changes nothing."""
+        spec = capi.nav_spec(level, world, site_mask, clearance, max_cost)
+        return capi.rollouts_call("slamhip_hs_rollouts", [self._h, spec.ctypes.data_as(C.c_void_p)], sources, start_pose, dt, body, cmds, hold)
+
     def ExpectedScan(self, pose, angles, max_range, level, world=False):
         """The scan the map of `level` predicts from `pose` (window frame): per angle (rad, sensor frame) the range in metres to the
         first occupied cell on the beam of length max_range, or inf where the map holds none.  It REPLACES the scan that was set:
@@ -673,6 +684,31 @@ class HectorSLAMProcessor:
         order = np.argsort(nav["goals"]["cost"], kind="stable")          # (an unreachable goal's cost is the largest uint32)
         nav["order"] = order
         return rec[order], nav["goals"][order], nav
+
+    def Rollouts(self, level, sources, dt, cmds, hold=1, body=None, start_pose=None, clearance=0, site_mask=2, max_cost=0, world=False):
+        """MapRep.rollouts in WORLD cells and the WORLD pose (slamhip_hsproc_rollouts): sources are world cells of `level`,
+        start_pose a world pose (None: MatchPose), and the results' poses and nav.mx0 / nav.my0 are world values.  No scan is needed;
+        MatchPose, LastMapUpdatePose and the update gate are untouched."""
+        spec = capi.nav_spec(level, world, site_mask, clearance, max_cost)
+        return capi.rollouts_call("slamhip_hsproc_rollouts", [self._h, spec.ctypes.data_as(C.c_void_p)], sources, start_pose, dt, body, cmds, hold)
+
+    def DriveCommand(self, level, goal_cells, clearance, v_values, w_values, dt, steps, body=None, start_pose=None, site_mask=2, max_cost=0,
+                     world=False):
+        """Which constant command to drive: Rollouts of the outer product of v_values and w_values (B = len(v) * len(w) commands,
+        command b = (v[b // len(w)], w[b % len(w)]), n_cmd = 1, hold = steps) towards goal_cells ((S, 2) world cells).  -> (v, w,
+        which, result, summary): the command decoded from key_end -- the complete rollout that ends cheapest, which = "end" -- or,
+        if nothing completes, from key_min -- the rollout that comes closest before it is cut, which = "min"; its
+        capi.ROLLOUT_RESULT record and the call's summary.  (None, None, None, None, summary) when no rollout has a free pose.
+        Composition only: no device work of its own."""
+        v = np.asarray(v_values, np.float32).reshape(-1); w = np.asarray(w_values, np.float32).reshape(-1)
+        cmds = np.stack([np.repeat(v, w.shape[0]), np.tile(w, v.shape[0])], 1).reshape(-1, 1, 2)
+        res, summary = self.Rollouts(level, goal_cells, dt, cmds, int(steps), body, start_pose, clearance, site_mask, max_cost, world)
+        for which in ("end", "min"):
+            key = capi.rollout_key(summary["key_" + which])
+            if key is not None:
+                b = key[1]
+                return float(cmds[b, 0, 0]), float(cmds[b, 0, 1]), which, res[b], summary
+        return None, None, None, None, summary
 
     def PoseCell(self, level):
         """The WORLD cell of `level` that MatchPose lies in: the pose over the level's CellLength, rounded as the grid update rounds
