@@ -390,6 +390,15 @@ class NpGrid:
             raise ValueError("probability table of %d values for a grid of %d cells" % (t.size, self.w * self.h))
         self.prob_table = t
 
+    def set_factors(self, free_f, occ_f):                               # OccGridMap.cs:58-79
+        self.lo_free = F(math.log(float(F(F(free_f) / F(F(1.0) - F(free_f))))))
+        self.lo_occ = F(math.log(float(F(F(occ_f) / F(F(1.0) - F(occ_f))))))
+
+    def reset(self):                                                    # GridMap.cs:56-62, OccGridMap.cs:244-252
+        self.value[:] = 0
+        self.upd[:] = -1
+        self.cur = 0
+
     def prob(self, idx):                                                # OccGridMap.cs:97-107
         if self.prob_table is not None:
             return self.prob_table[idx]
@@ -405,37 +414,49 @@ class NpGrid:
         exf, eyf = t.transform(xy[:, 0], xy[:, 1])
         ex = f2i_array(np.rint(exf)); ey = f2i_array(np.rint(eyf))
         W = self.w
-        for i in range(xy.shape[0]):
-            x2, y2 = int(ex[i]), int(ey[i])
-            if (bx, by) == (x2, y2):                                    # :137
-                continue
-            if not (0 <= bx < W and 0 <= by < self.h and 0 <= x2 < W and 0 <= y2 < self.h):   # :158
-                continue
-            dx, dy = x2 - bx, y2 - by
-            adx, ady = abs(dx), abs(dy)
-            odx, ody = sign(dx), sign(dy) * W
-            off = by * W + bx
-            if adx >= ady:
-                da, db, err, oa, ob = adx, ady, adx // 2, odx, ody      # :175-179
-            else:
-                da, db, err, oa, ob = ady, adx, ady // 2, ody, odx      # :180-185
-            cells = [off]
-            for _ in range(da - 1):                                     # :226
-                off += oa; err += db
-                if err >= da:
-                    off += ob; err -= da
-                cells.append(off)
-            for cidx in cells:                                          # BresenhamCellFree :192-199
-                if self.upd[cidx] < mark_free:
-                    self.value[cidx] = self.value[cidx] + self.lo_free
-                    self.upd[cidx] = mark_free
-            e = y2 * W + x2                                             # BresenhamCellOcc :201-218
-            if self.upd[e] < mark_occ:
-                if self.upd[e] == mark_free:
-                    self.value[e] = self.value[e] - self.lo_free
-                if self.value[e] < F(50.0):
-                    self.value[e] = self.value[e] + self.lo_occ
-                self.upd[e] = mark_occ
+        if not (0 <= bx < W and 0 <= by < self.h):                      # :158 (no line of this scan passes)
+            self.cur += 3
+            return
+        dx, dy = ex - bx, ey - by
+        ok = ((dx != 0) | (dy != 0)) & (ex >= 0) & (ex < W) & (ey >= 0) & (ey < self.h)     # :137, :158
+        lines = np.flatnonzero(ok)
+        # The walks of Bresenham2D (:220-239), literally -- offset and error advanced step by step -- for a block of lines at a
+        # time (one NumPy operation per step instead of one Python iteration per cell); the cells are then updated line by
+        # line in scan order, free cells first, end cell last, as the reference does.
+        adx, ady = np.abs(dx[lines]), np.abs(dy[lines])
+        odx, ody = np.sign(dx[lines]), np.sign(dy[lines]) * W
+        xm = adx >= ady                                                 # :175
+        da_all, db_all = np.where(xm, adx, ady), np.where(xm, ady, adx)
+        oa_all, ob_all = np.where(xm, odx, ody), np.where(xm, ody, odx)
+        p0 = 0
+        while p0 < lines.size:
+            p1, longest = p0, 0
+            while p1 < lines.size and (p1 - p0 + 1) * max(longest, int(da_all[p1])) <= (1 << 23):
+                longest = max(longest, int(da_all[p1])); p1 += 1
+            da, db, oa, ob = da_all[p0:p1], db_all[p0:p1], oa_all[p0:p1], ob_all[p0:p1]
+            walk = np.empty((longest, p1 - p0), np.int64)
+            off = np.full(p1 - p0, by * W + bx, np.int64)
+            err = da // 2                                               # :178 / :184
+            walk[0] = off
+            for k in range(1, longest):                                 # :226 (a line's own steps end at da - 1: the rest is not read)
+                off = off + oa; err = err + db                          # :228-229
+                over = err >= da                                        # :231
+                off = off + np.where(over, ob, 0); err = err - np.where(over, da, 0)     # :233-234
+                walk[k] = off
+            for j in range(p1 - p0):
+                cells = walk[:int(da[j]), j]
+                cells = cells[self.upd[cells] < mark_free]              # BresenhamCellFree :192-199 (a line's cells are distinct)
+                self.value[cells] = self.value[cells] + self.lo_free
+                self.upd[cells] = mark_free
+                i = lines[p0 + j]
+                e = int(ey[i]) * W + int(ex[i])                         # BresenhamCellOcc :201-218
+                if self.upd[e] < mark_occ:
+                    if self.upd[e] == mark_free:
+                        self.value[e] = self.value[e] - self.lo_free
+                    if self.value[e] < F(50.0):
+                        self.value[e] = self.value[e] + self.lo_occ
+                    self.upd[e] = mark_occ
+            p0 = p1
         self.cur += 3
 
     def interp(self, cx, cy):                                           # ScanMatcher.cs:211-249

@@ -297,8 +297,8 @@ extern "C" int32_t slamhip_hs_world_cells_upload(slamhip_hs *hs, int32_t level, 
     SH_TRY(hs_world_wait(hs));
     // keep the once-per-scan guards meaningful, as slamhip_hs_cells_upload does: the next scan's marks must exceed every stored index
     if (mx >= 0) {                      // marks of scan k are 3k+1 / 3k+2 (OccGridMap.cs:116-117,:144)
-        const int need = (mx / 3 + 1) * 3;
-        if (need > L.curr_update_index) L.curr_update_index = need;
+        const long long need = ((long long)mx / 3 + 1) * 3;                // (64-bit: an index near INT_MAX has no marks above it and moves nothing)
+        if (need <= 0x7fffffffLL - 2 && need > L.curr_update_index) L.curr_update_index = (int)need;
     }
     return SLAMHIP_OK;
 }
