@@ -318,6 +318,38 @@ namespace HectorSLAM.Main
             return res;
         }
 
+        /// <summary>Start Monte-Carlo localisation: the particle set of the processor's own pyramid (MapRep.MclSet) from WORLD poses, taken
+        /// to the window's frame as Relocalise takes its centre (minus (float)Origin * Maps[0].CellLength per axis).</summary>
+        public void LocaliseInit(Vector3[] posesWorld)
+        {
+            var (ox, oy) = Origin;
+            float cell0 = MapRep.Maps[0].Properties.CellLength;
+            var p = (Vector3[])posesWorld.Clone();
+            if (ox != 0 || oy != 0)
+                for (int i = 0; i < p.Length; i++) { p[i].X = p[i].X - (float)ox * cell0; p[i].Y = p[i].Y - (float)oy * cell0; }
+            MapRep.MclSet(p);
+            mclOrigin = (ox, oy);
+        }
+        private (long X, long Y) mclOrigin;
+
+        /// <summary>One localisation step (slamhip_hsproc_mcl_step): spec's odometry increment is in the robot's frame; its frame offset
+        /// is set here to minus the window's movement since the last step.  Returns the weighted-mean pose in the world frame;
+        /// effectiveCount = A * A / Q.  MatchPose, LastMapUpdatePose, the update gate and the map are untouched; the caller advances
+        /// spec.Stream per step.</summary>
+        public unsafe Vector3 LocaliseStep(ScanCloud scan, MclSpec spec, out double effectiveCount, out MclSummary summary)
+        {
+            var (ox, oy) = Origin;
+            float cell0 = MapRep.Maps[0].Properties.CellLength;
+            spec.FrameOffsetX = -((float)(ox - mclOrigin.X) * cell0); spec.FrameOffsetY = -((float)(oy - mclOrigin.Y) * cell0);
+            fixed (Vector2* p = CollectionsMarshal.AsSpan(scan.Points))
+                Native.Check(Native.slamhip_hsproc_mcl_step(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), spec, out summary));
+            mclOrigin = (ox, oy);
+            double a = summary.A;
+            effectiveCount = a * a / summary.Q;
+            return new Vector3((float)(summary.SumHx / a / 1024.0 + (double)((float)ox * cell0)), (float)(summary.SumHy / a / 1024.0 + (double)((float)oy * cell0)),
+                               (float)Math.Atan2(summary.SumHs, summary.SumHc));
+        }
+
         /// <summary>Which constant command to drive: Rollouts of the outer product of vValues and wValues (command b = (v[b / nw], w[b %
         /// nw]), nCmd = 1, hold = steps) towards goalCells (world cells).  Returns false when no rollout has a free pose; else the
         /// command decoded from KeyEnd -- the complete rollout that ends cheapest, fromEnd = true -- or, if nothing completes, from

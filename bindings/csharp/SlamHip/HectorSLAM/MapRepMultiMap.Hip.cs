@@ -360,6 +360,63 @@ namespace HectorSLAM.Main
             return res;
         }
 
+        /// <summary>The particle set of the localisation filter (slamhip_hs_mcl_set): poses in the window's frame, at most 65536; every
+        /// accumulated cost becomes 0.  It replaces any previous set.</summary>
+        public unsafe void MclSet(Vector3[] poses)
+        {
+            fixed (Vector3* p = poses)
+                Native.Check(Native.slamhip_hs_mcl_set(Pyramid.Ptr, p, poses.Length));
+            mclCount = poses.Length;
+        }
+        private int mclCount;
+
+        /// <summary>One localisation step on the particle set against the scan that was set (slamhip_hs_mcl_step; the reference has no
+        /// counterpart): predict by odometry with noise, weigh against the distance field, resample -- all on the device.  Blocking;
+        /// it changes nothing of the map.</summary>
+        public MclSummary MclStep(in MclSpec spec)
+        {
+            Native.Check(Native.slamhip_hs_mcl_step(Pyramid.Ptr, spec, out MclSummary summary));
+            return summary;
+        }
+
+        /// <summary>The particle set as it stands (slamhip_hs_mcl_get): poses, accumulated costs, the ancestors of the last step.</summary>
+        public unsafe Vector3[] MclGet(out ulong[] acc, out int[] ancestors)
+        {
+            var poses = new Vector3[mclCount];
+            acc = new ulong[mclCount]; ancestors = new int[mclCount];
+            fixed (Vector3* p = poses)
+            fixed (ulong* a = acc)
+            fixed (int* k = ancestors)
+                Native.Check(Native.slamhip_hs_mcl_get(Pyramid.Ptr, p, a, k, mclCount));
+            return poses;
+        }
+
+        /// <summary>One localisation step of the definition over a caller's class array on the host (slamhip_debug_mcl_step): cls as for
+        /// NavFieldOf, stm = 1 / cell length, accIn null for zeros.</summary>
+        public static unsafe Vector3[] MclStepOf(byte[] cls, int cw, int ch, float stm, Vector2[] points, Vector3[] particles, ulong[] accIn, in MclSpec spec,
+                                                 out ulong[] acc, out int[] ancestors, out MclSummary summary)
+        {
+            var res = new Vector3[particles.Length];
+            acc = new ulong[particles.Length]; ancestors = new int[particles.Length];
+            fixed (byte* c = cls)
+            fixed (Vector2* q = points)
+            fixed (Vector3* p = particles)
+            fixed (ulong* ai = accIn)
+            fixed (Vector3* r = res)
+            fixed (ulong* a = acc)
+            fixed (int* k = ancestors)
+                Native.Check(Native.slamhip_debug_mcl_step(c, cw, ch, stm, q, points.Length, p, ai, particles.Length, spec, r, a, k, out summary));
+            return res;
+        }
+
+        /// <summary>The weight table of the localisation step (slamhip_debug_mcl_table).</summary>
+        public static unsafe uint[] MclTable()
+        {
+            var t = new uint[64];
+            fixed (uint* p = t) Native.Check(Native.slamhip_debug_mcl_table(p));
+            return t;
+        }
+
         /// <summary>The sum of all shifts since construction or the last Reset, in level-0 cells (slamhip_hs_origin).</summary>
         public (long X, long Y) Origin
         {

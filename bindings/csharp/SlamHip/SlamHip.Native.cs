@@ -216,6 +216,32 @@ namespace SlamHip
         public ulong KeyEnd, KeyMin;
     }
 
+    /// <summary>slamhip_mcl_spec (include/slamhip.h): one particle-filter localisation step -- the field's level, world, site mask and
+    /// radius, the odometry increment in the robot's frame, the noise scales, the window's movement since the last step, the weight
+    /// scale, the resampling threshold and the Philox key and stream.  72 bytes, no padding.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct MclSpec
+    {
+        public int Level, World, SiteMask, Radius;
+        public float Dx, Dy, Dtheta;
+        public float SigmaX, SigmaY, SigmaTheta;
+        public float FrameOffsetX, FrameOffsetY;
+        public uint Beta;
+        public int MinEffectiveCount;
+        public ulong Seed, Stream;
+    }
+
+    /// <summary>slamhip_mcl_summary (include/slamhip.h): the exact integer sums of one localisation step.  The effective sample size is
+    /// A * A / Q; the weighted-mean pose (SumHx / A / 1024, SumHy / A / 1024, atan2(SumHs, SumHc)).  96 bytes, no padding.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct MclSummary
+    {
+        public ulong W, A, Q, KeyBest;
+        public long SumHx, SumHy, SumHc, SumHs;
+        public ulong CostMin, CostMax;
+        public int Resampled, DistinctCount, UnplacedCount, ParticleCount;
+    }
+
     internal static unsafe class Native
     {
         const string Lib = "slamhip";                                   // libslamhip.so on the library path
@@ -324,6 +350,12 @@ namespace SlamHip
                                                                         out NavSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_hs_rollouts(IntPtr hs, ref NavSpec spec, int* sources, int nSources, float* startPose, float dt, float* body, int nBody,
                                                                        float* cmds, int nRollouts, int nCmd, int hold, RolloutResult* results, out RolloutSummary summary);
+        [DllImport(Lib)] internal static extern int slamhip_hs_mcl_set(IntPtr hs, Vector3* poses, int nParticles);
+        [DllImport(Lib)] internal static extern int slamhip_hs_mcl_step(IntPtr hs, in MclSpec spec, out MclSummary summary);
+        [DllImport(Lib)] internal static extern int slamhip_hs_mcl_get(IntPtr hs, Vector3* poses, ulong* acc, int* ancestors, int nParticles);
+        [DllImport(Lib)] internal static extern int slamhip_debug_mcl_step(byte* cls, int cw, int ch, float stm, Vector2* points, int nPoints, Vector3* particlesIn, ulong* accIn, int nParticles,
+                                                                          in MclSpec spec, Vector3* particlesOut, ulong* accOut, int* ancestorsOut, out MclSummary summary);
+        [DllImport(Lib)] internal static extern int slamhip_debug_mcl_table(uint* table64);
         [DllImport(Lib)] internal static extern int slamhip_debug_rollouts(byte* cls, int cw, int ch, int siteMask, int clearance, uint maxCost, int* sources, int nSources, float stm,
                                                                           float* startPose, float dt, float* body, int nBody, float* cmds, int nRollouts, int nCmd, int hold,
                                                                           RolloutResult* results, out RolloutSummary summary);
@@ -362,6 +394,7 @@ namespace SlamHip
                                                                          TraceSummary* summaries, TraceBeam* beams);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_distance_score(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int world,
                                                                                   int siteMask, int radius, DistanceSummary* summaries, ushort* pointD2);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_mcl_step(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in MclSpec spec, out MclSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_frontiers(IntPtr proc, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
                                                                              int lx, int ly, int lw, int lh, int* labels);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_rollouts(IntPtr proc, ref NavSpec spec, int* sources, int nSources, float* startPoseWorld, float dt, float* body, int nBody,

@@ -1075,6 +1075,94 @@ int32_t slamhip_debug_rollouts(const uint8_t *cls, int32_t cw, int32_t ch, int32
                                int32_t P, const float *cmds, int32_t B, int32_t n_cmd, int32_t hold,
                                slamhip_rollout_result *out_results, slamhip_rollout_summary *out_summary);
 
+/* One particle-filter localisation step on the distance field (K13; no reference counterpart): Monte-Carlo localisation on the
+ * resident map -- a set of N pose hypotheses owned by the hs and kept in device memory is moved by odometry with noise, weighed by
+ * the scan against K9's field, and resampled, without drawing into the map and without the particles crossing the bus.  Every
+ * result is exact: integers, or binary32 with EVERY OPERATION ROUNDED ON ITS OWN (no fused multiply-add), so each output is one
+ * defined bit pattern and nothing has a tolerance.
+ * THE DEFINITION, for a slamhip_mcl_spec, r = radius, stm the level's ScaleToMap, the n points of the scan that was set, particles
+ * (x_i, y_i, theta_i) in the WINDOW's frame with accumulated costs acc_i (uint64), i = 0 .. N - 1:
+ *  1. Noise.  B_j = Philox4x32-10(counter = (i, j, stream lo, stream hi), key = (seed lo, seed hi)) for j = 0, 1.  The eight words,
+ *     B_0's first, give sixteen 16-bit halves h_0 .. h_15: word 0's low half, word 0's high half, word 1's low half, and so on.
+ *     z_m = (float)((h_4m + h_4m+1 + h_4m+2 + h_4m+3) - 131070) * ZS for m = 0, 1, 2, ZS = 0x1.bb67aep-16f, the binary32 nearest
+ *     to sqrt(3 / (2^32 - 1)).  z is a four-term Irwin-Hall variate: mean 0, variance 1, tails cut at about 3.46 sigma.  It is not
+ *     Box-Muller because logf is not bit-reproducible between host and device.
+ *  2. Predict.  ex = dx + sx * z_0, ey = dy + sy * z_1, eth = dth + sth * z_2 (each product rounded before its sum), (s, c) =
+ *     sh_det_sincosf(theta_i), x' = (x_i + fox) + (c * ex - s * ey), y' = (y_i + foy) + (s * ex + c * ey), theta' = theta_i + eth.
+ *     No angle normalisation.  (sh_det_sincosf is bit-reproducible for |theta| <= 65536, the bound K12 states.)
+ *  3. Cost.  cost_i = sum_d2 + r * r * n_ignored of the slamhip_distance_summary that steps 5 and 6 of slamhip_hs_distance_field
+ *     define at pose (x', y', theta') for spec's level, world, site_mask and radius.  An ignored point costs as much as a point
+ *     with no site within the radius, so a particle with no usable end cell is the WORST particle, not the best.
+ *  4. Accumulate.  a_i = acc_i + cost_i; acc'_i = a_i - min_j a_j: bounded, and 0 for the best particle.
+ *  5. Weight.  d = min(acc'_i, 2^32 - 1), e = (d * beta) >> 16 in uint64, k = e >> 6, f = e & 63, w_i = k >= 32 ? 0 : T[f] >> k with
+ *     T[f] = min(2^32 - 1, floor(2^((2048 - f) / 64))) (slamhip_debug_mcl_table): beta counts, in Q16, the 1/64 halvings of the
+ *     weight per unit of cost.  W = sum w_i >= 2^32 - 1.
+ *  6. Summary, slamhip_mcl_summary, all exact integer sums.  h_i = w_i >> 20; A = sum h_i, Q = sum h_i^2: the effective sample
+ *     size is A^2 / Q, the caller's to form.  key_best = min over i of (a_i << 16 | i) (a_i < 2^48 is the caller's to keep: with
+ *     n_eff_min = 0 for ever the costs add up without bound).  sum_hx = sum h_i * (int64)rintf(x' * 1024.0f), sum_hy likewise;
+ *     sum_hc = sum h_i * (int)rintf(c' * 16384.0f), sum_hs likewise, (s', c') = sh_det_sincosf(theta'); only particles whose two
+ *     scaled coordinates satisfy fabsf(.) < 2147483648.0f and whose c', s' are finite contribute to the four, the others are
+ *     counted in n_unplaced.  cost_min, cost_max over cost_i.  With n_unplaced == 0 the weighted-mean pose is (sum_hx / A / 1024,
+ *     sum_hy / A / 1024, atan2(sum_hs, sum_hc)).  With n_unplaced > 0 the divisor A still holds the h of the unplaced particles,
+ *     which the two position sums lack: x and y are then pulled towards 0 by the share of A those particles carry (none once their
+ *     weight is below 2^20; an unplaced particle lies 2^21 m out and costs like a particle with no site in reach).  The summary
+ *     has no sum of h over the placed particles alone; a caller who needs the exact mean then forms it from slamhip_hs_mcl_get.
+ *  7. Resample iff A * A < (uint64)n_eff_min * Q (0: never; N + 1: always, because Q <= A * A <= N * Q).  If not: the particles
+ *     are the predicted ones, acc = acc', the ancestors the identity, n_distinct = N.  If so, systematic resampling: C_i the
+ *     inclusive uint64 prefix sum of w in index order, rr = word 0 of Philox4x32-10((0, 2, stream lo, stream hi), key),
+ *     u = ((W >> 16) * rr) >> 16, T_k = k * W + u, anc_k = the least i with N * C_i > T_k (N * W < 2^64); new particle k is
+ *     predicted particle anc_k, every acc becomes 0, n_distinct is the number of distinct ancestors. */
+typedef struct slamhip_mcl_spec {
+    int32_t level, world, site_mask, radius;   /* as slamhip_hs_distance_score */
+    float delta[3];                    /* odometry increment (dx, dy, dth) in the ROBOT frame since the last step */
+    float sigma[3];                    /* noise scales (sx, sy, sth); the caller scales them by the motion */
+    float frame_offset[2];             /* metres, added to every particle first: the window's movement since the last step, else 0 */
+    uint32_t beta;                     /* Q16 count of 1/64 halvings of weight per unit of cost; not 0 */
+    int32_t n_eff_min;                 /* resample iff the effective sample size is below it: 0 never, N + 1 always */
+    uint64_t seed, stream;             /* Philox key and stream; the caller advances stream per step */
+} slamhip_mcl_spec;                    /* 14 words + 2 uint64 at offsets 56 and 64: 72 bytes, no padding */
+typedef struct slamhip_mcl_summary {
+    uint64_t W, A, Q, key_best;
+    int64_t sum_hx, sum_hy, sum_hc, sum_hs;
+    uint64_t cost_min, cost_max;
+    int32_t resampled, n_distinct, n_unplaced, n_particles;
+} slamhip_mcl_summary;                 /* 10 x 8 + 4 x 4: 96 bytes, no padding */
+/* The particle set of the hs: N particles (poses: N x 3 floats, window frame), N in [1, 65536]; every acc becomes 0, the ancestors
+ * the identity; it replaces any previous set.  The blocks (two particle buffers, acc, a, w, C, ancestors: 3.7 MB, and 1.5 MB of
+ * pinned staging) belong to the hs, are made by the first call and freed by slamhip_hs_destroy.  Blocking.  SLAMHIP_ERR_INVALID:
+ * N out of range, a value that is not finite.  A poisoned context: SLAMHIP_ERR_TIMEOUT. */
+int32_t slamhip_hs_mcl_set(slamhip_hs *hs, const float *poses, int32_t N);
+/* One step.  The launches, on the operator's stream behind everything already enqueued: the field of slamhip_hs_distance_score by
+ * the same internal functions (the class map's pack, k9_rows, k9_cols -- REBUILT ON EVERY STEP, as K9 does, because the map may have
+ * changed: at 2048^2 cells that is most of a step's time, and there is no cache); k13_score -- the scan staged in LDS once per
+ * workgroup, one wavefront per particle at a time, steps 1 and 2 computed uniformly across the wavefront, lanes striding the points
+ * and gathering the uint16 field, a wave reduction, 64-bit agent-scope atomic minima for min a and cost_min; k13_weigh -- a lane per
+ * particle, w, acc', the sums of step 6 reduced per wavefront, one atomic per wavefront per sum; k13_scan -- ONE workgroup, the
+ * inclusive uint64 scan of w in chunks of 4096, skipped when the decision read from device memory is not to resample; k13_resample
+ * -- the decision read from device memory, a binary search per lane over C, the OTHER particle buffer written (the two are used in
+ * turn), the distinct ancestors counted by anc_k != anc_k-1, and the last workgroup to finish stores the summary to pinned memory.
+ * No host round trip inside the step; blocking, ONE bounded wait.  It changes nothing of the map or of any other call.
+ * LDS: the scan's points, 8 bytes each, must fit a 64 KB allocation beside the reductions' words: n_points <= 7680 is a design
+ * condition.  SLAMHIP_ERR_INVALID, nothing launched, no output written: level, world, site_mask, radius as
+ * slamhip_hs_distance_score; a float of the spec that is not finite; beta == 0; n_eff_min outside [0, N + 1]; n_points > 7680; E over
+ * 2^26 cells.  SLAMHIP_ERR_STATE: no particle set, or no scan.  A poisoned context: SLAMHIP_ERR_TIMEOUT.  A step that fails once its
+ * first kernel is enqueued (a launch error, the wait) leaves NO particle set -- the particles are predicted in place, so they are then
+ * neither the old set nor the new one: the next step and slamhip_hs_mcl_get answer SLAMHIP_ERR_STATE until slamhip_hs_mcl_set. */
+int32_t slamhip_hs_mcl_step(slamhip_hs *hs, const slamhip_mcl_spec *spec, slamhip_mcl_summary *out);
+/* The particles (N x 3 floats), acc (N uint64) and the ancestors of the last step (N int32; the identity before any step); any of
+ * the three may be NULL.  N must be the set's.  Blocking.  SLAMHIP_ERR_STATE: no particle set. */
+int32_t slamhip_hs_mcl_get(slamhip_hs *hs, float *poses, uint64_t *acc, int32_t *ancestors, int32_t N);
+/* Test hook (no device involved): one step of the definition over a caller's class array, M = (0, 0, cw, ch), stm the ScaleToMap;
+ * spec->level must be 0.  The field comes from slamhip_debug_distance_field, the step from the header text the kernels run
+ * (hs_mcl.h), in plain loops.  points: n_points pairs; particles_in: N x 3; acc_in: N uint64, or NULL for zeros; the outputs as
+ * slamhip_hs_mcl_get's, none NULL.  SLAMHIP_ERR_INVALID, no output written: cw or ch < 1, stm not finite or <= 0, n_points outside
+ * [1, 7680], N outside [1, 65536], a particle that is not finite, and the spec's refusals of slamhip_hs_mcl_step. */
+int32_t slamhip_debug_mcl_step(const uint8_t *cls, int32_t cw, int32_t ch, float stm, const float *points, int32_t n_points,
+                               const float *particles_in, const uint64_t *acc_in, int32_t N, const slamhip_mcl_spec *spec,
+                               float *particles_out, uint64_t *acc_out, int32_t *ancestors_out, slamhip_mcl_summary *summary);
+/* The weight table T of step 5. */
+int32_t slamhip_debug_mcl_table(uint32_t out[64]);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -1287,6 +1375,13 @@ int32_t slamhip_hsproc_nav_field(slamhip_hsproc *p, const slamhip_nav_spec *spec
 int32_t slamhip_hsproc_rollouts(slamhip_hsproc *p, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S,
                                 const float *start_pose_world, float dt, const float *body, int32_t P, const float *cmds, int32_t B,
                                 int32_t n_cmd, int32_t hold, slamhip_rollout_result *out_results, slamhip_rollout_summary *out_summary);
+/* The localisation step through the processor: slamhip_hs_set_scan on the processor's own hs as slamhip_hsproc_relocalise sets it,
+ * then slamhip_hs_mcl_step with the spec as given -- the particles live in the window's frame, and a caller whose window has scrolled
+ * since the last step passes that movement in frame_offset.  MatchPose, LastMapUpdatePose, the update gate and the map are untouched;
+ * the scan that was set is replaced.  Errors as slamhip_hs_mcl_step; a call refused for its spec or n_points leaves the scan that
+ * was set. */
+int32_t slamhip_hsproc_mcl_step(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
+                                const slamhip_mcl_spec *spec, slamhip_mcl_summary *out);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

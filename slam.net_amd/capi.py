@@ -4,6 +4,7 @@ Loading fails loudly when libslamhip.so is missing (run ``python -m slam.net_amd
 ``__graft_entry__.build()``); there is no CPU fallback in this package.
 """
 import ctypes as C
+import math
 import os
 import re
 
@@ -140,6 +141,14 @@ ROLLOUT_SUMMARY = np.dtype([("nav", NAV_SUMMARY), ("start_cost", np.uint32), ("n
                             ("key_min", np.uint64)])           # slamhip_rollout_summary: 64 bytes, no padding
 ROLLOUT_NO_KEY = 0xFFFFFFFFFFFFFFFF                            # key_end / key_min when no rollout qualifies
 assert ROLLOUT_RESULT.itemsize == 28 and ROLLOUT_SUMMARY.itemsize == 64
+MCL_MAX_N, MCL_MAX_POINTS = 65536, 7680                        # the limits of slamhip_hs_mcl_set / slamhip_hs_mcl_step
+MCL_SPEC = np.dtype([("level", np.int32), ("world", np.int32), ("site_mask", np.int32), ("radius", np.int32), ("delta", np.float32, (3,)),
+                     ("sigma", np.float32, (3,)), ("frame_offset", np.float32, (2,)), ("beta", np.uint32), ("n_eff_min", np.int32),
+                     ("seed", np.uint64), ("stream", np.uint64)])          # slamhip_mcl_spec (include/slamhip.h): 72 bytes, no padding
+MCL_SUMMARY = np.dtype([("W", np.uint64), ("A", np.uint64), ("Q", np.uint64), ("key_best", np.uint64), ("sum_hx", np.int64), ("sum_hy", np.int64),
+                        ("sum_hc", np.int64), ("sum_hs", np.int64), ("cost_min", np.uint64), ("cost_max", np.uint64), ("resampled", np.int32),
+                        ("n_distinct", np.int32), ("n_unplaced", np.int32), ("n_particles", np.int32)])   # slamhip_mcl_summary: 96 bytes
+assert MCL_SPEC.itemsize == 72 and MCL_SUMMARY.itemsize == 96
 
 
 def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
@@ -207,6 +216,8 @@ def _declare(L):
         "slamhip_debug_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_nav_field": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_rollouts": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, C.c_float, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
+        "slamhip_debug_mcl_step": (i32, [vp, i32, i32, C.c_float, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "slamhip_debug_mcl_table": (i32, [vp]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -299,6 +310,9 @@ def _declare(L):
         "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hs_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hs_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
+        "slamhip_hs_mcl_set": (i32, [vp, vp, i32]),
+        "slamhip_hs_mcl_step": (i32, [vp, vp, vp]),
+        "slamhip_hs_mcl_get": (i32, [vp, vp, vp, vp, i32]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -328,6 +342,7 @@ def _declare(L):
         "slamhip_hsproc_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hsproc_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hsproc_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
+        "slamhip_hsproc_mcl_step": (i32, [vp, fp, i32, fp, vp, vp]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -550,6 +565,54 @@ def rollout_key(key):
     """(cost, b) of a key_end / key_min, or None for ROLLOUT_NO_KEY."""
     key = int(key)
     return None if key == ROLLOUT_NO_KEY else (key >> 32, key & 0xFFFFFFFF)
+
+
+def mcl_spec(level, radius, delta, sigma, beta, n_eff_min, seed=0, stream=0, site_mask=2, world=False, frame_offset=(0.0, 0.0)):
+    """A MCL_SPEC record (one-element array) from Python values (the floats rounded to binary32)."""
+    s = np.zeros(1, MCL_SPEC)
+    s["level"] = int(level); s["world"] = 1 if world else 0; s["site_mask"] = int(site_mask); s["radius"] = int(radius)
+    s["delta"][0] = f32(delta, (3,)); s["sigma"][0] = f32(sigma, (3,)); s["frame_offset"][0] = f32(frame_offset, (2,))
+    s["beta"] = int(beta); s["n_eff_min"] = int(n_eff_min)
+    s["seed"] = int(seed) & 0xFFFFFFFFFFFFFFFF; s["stream"] = int(stream) & 0xFFFFFFFFFFFFFFFF
+    return s
+
+
+def mcl_beta(sigma_cells, temper=1.0):
+    """beta of a MCL_SPEC for a Gaussian end-point model: the weight exp(-cost / (2 sigma_cells^2 temper)) halves every
+    2 sigma_cells^2 temper ln 2 units of cost, so beta = round(65536 * 64 * log2(e) / (2 sigma_cells^2 temper)), at least 1."""
+    return max(1, min(0xFFFFFFFF, int(round(65536.0 * 64.0 * math.log2(math.e) / (2.0 * float(sigma_cells) ** 2 * float(temper))))))
+
+
+def mcl_mean(summary, frame_offset=(0.0, 0.0)):
+    """(pose, n_eff) of a MCL_SUMMARY: the weighted-mean pose of the placed particles -- (sum_hx / A' / 1024, sum_hy / A' / 1024,
+    atan2(sum_hs, sum_hc)) in float64, A' = A when nothing is unplaced -- plus frame_offset on x and y, and A^2 / Q."""
+    A, Q = int(summary["A"]), int(summary["Q"])
+    pose = np.array([int(summary["sum_hx"]) / A / 1024.0 + float(frame_offset[0]), int(summary["sum_hy"]) / A / 1024.0 + float(frame_offset[1]),
+                     math.atan2(int(summary["sum_hs"]), int(summary["sum_hc"]))])
+    return pose, A * A / Q
+
+
+def debug_mcl_step(cls, stm, points, particles, spec, acc=None):
+    """One localisation step of the definition (slamhip_hs_mcl_step) over the (h, w) uint8 array `cls` of class bits, M = (0, 0, w, h),
+    stm = 1 / cell length (slamhip_debug_mcl_step; no device involved).  points: (n, 2); particles: (N, 3); spec: mcl_spec's record;
+    acc: (N,) uint64 or None for zeros.  -> (particles, acc, ancestors, summary)."""
+    vp = C.c_void_p
+    c = np.ascontiguousarray(cls, np.uint8)
+    pts = f32(points, (-1, 2)); part = f32(particles, (-1, 3))
+    N = part.shape[0]
+    a_in = np.ascontiguousarray(acc, np.uint64).reshape(N) if acc is not None else None
+    out_p = np.zeros((N, 3), np.float32); out_a = np.zeros(N, np.uint64); out_anc = np.zeros(N, np.int32); summary = np.zeros(1, MCL_SUMMARY)
+    call("slamhip_debug_mcl_step", c.ctypes.data_as(vp), c.shape[1], c.shape[0], C.c_float(stm), pts.ctypes.data_as(vp), pts.shape[0],
+         part.ctypes.data_as(vp), a_in.ctypes.data_as(vp) if a_in is not None else None, N, spec.ctypes.data_as(vp), out_p.ctypes.data_as(vp),
+         out_a.ctypes.data_as(vp), out_anc.ctypes.data_as(vp), summary.ctypes.data_as(vp))
+    return out_p, out_a, out_anc, summary[0]
+
+
+def debug_mcl_table():
+    """The weight table T of slamhip_hs_mcl_step's step 5 (slamhip_debug_mcl_table): 64 uint32."""
+    t = np.zeros(64, np.uint32)
+    call("slamhip_debug_mcl_table", t.ctypes.data_as(C.c_void_p))
+    return t
 
 
 def check(rc):

@@ -1,6 +1,7 @@
 // coreslam.hip -- CoreSLAM operator-level entry points of include/slamhip.h (gfx950 only).
 #include "cs_internal.h"
 #include "det_trig.h"
+#include "philox.h"
 #include "obstacle_dev.h"
 #include <algorithm>
 #include <numeric>
@@ -21,18 +22,6 @@ __global__ void k_pack_holemap(const uint16_t *__restrict__ pix, uint8_t *__rest
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_bytes) return;
     out[i] = (uint8_t)(((pix[i * 2] >> 12) << 4) | (pix[i * 2 + 1] >> 12));      // :51
-}
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3")
-__device__ static inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
-{
-    for (int r = 0; r < 10; r++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
 }
 
 // Device replacement for FillRandomQueues (CoreSLAMProcessor.cs:599-612): jitter i is a pure function of

@@ -197,9 +197,9 @@ static int32_t hs_df_grow(void **p, size_t *cap, size_t want, bool pinned)
     return SLAMHIP_OK;
 }
 
-static int32_t hs_df_check(const slamhip_hs *hs, int32_t level, int32_t world, int32_t site_mask, int32_t radius)
+int32_t hs_df_check(int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius)
 {
-    if (level < 0 || level >= hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: level %d of %d", level, hs->n_levels);
+    if (level < 0 || level >= n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: level %d of %d", level, n_levels);
     if (world != 0 && world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: world = %d must be 0 (the window) or 1 (the world)", world);
     if (site_mask < 1 || site_mask > 7) SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: site_mask = %d must lie in [1, 7]", site_mask);
     if (radius < 1 || radius > HS_DF_MAX_RADIUS) SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: radius = %d must lie in [1, %d]", radius, HS_DF_MAX_RADIUS);
@@ -270,7 +270,7 @@ extern "C" int32_t slamhip_hs_distance_field(slamhip_hs *hs, int32_t level, int3
                                              int32_t x, int32_t y, int32_t w, int32_t h, uint16_t *out_d2)
 {
     SH_CHECK_ARG(hs && out_d2);
-    SH_TRY(hs_df_check(hs, level, world, site_mask, radius));
+    SH_TRY(hs_df_check(hs->n_levels, level, world, site_mask, radius));
     if (w < 1 || h < 1 || (int64_t)w * h > HS_DF_MAX_RECT)
         SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: a rectangle of %d x %d cells; w, h >= 1 and w * h <= 2^24", w, h);
     slamhip_ctx *ctx = hs->ctx;
@@ -298,7 +298,7 @@ extern "C" int32_t slamhip_hs_distance_score(slamhip_hs *hs, int32_t level, int3
                                              const float *poses, int32_t B, slamhip_distance_summary *out_summaries, uint16_t *out_points)
 {
     SH_CHECK_ARG(hs && poses && out_summaries);
-    SH_TRY(hs_df_check(hs, level, world, site_mask, radius));
+    SH_TRY(hs_df_check(hs->n_levels, level, world, site_mask, radius));
     if (B < 1 || B > HS_DF_MAX_POSES) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: B = %d must lie in [1, %d]", B, HS_DF_MAX_POSES);
     if (hs->n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "distance score: no scan (slamhip_hs_set_scan first)");
     const int n = hs->n_points;

@@ -45,6 +45,7 @@ struct hs_dfield;                          // hs_dfield.hip
 struct hs_frontier;                        // hs_frontier.hip
 struct hs_nav;                             // hs_nav.hip
 struct hs_rollout;                         // hs_rollout.hip
+struct hs_mcl;                             // hs_mcl.hip
 struct slamhip_hs {
     slamhip_ctx *ctx;
     int n_levels;
@@ -75,6 +76,7 @@ struct slamhip_hs {
     struct hs_frontier *frl;                               // slamhip_hs_frontiers: the frontier words, the union-find's arrays and the results' blocks, made by the first call, kept
     struct hs_nav *nav;                                    // slamhip_hs_nav_field: the traversable words, costs, dirs, tile flags and the results' blocks, made by the first call, kept
     struct hs_rollout *rol;                                // slamhip_hs_rollouts: the commands', body points' and results' blocks, made by the first call, kept
+    struct hs_mcl *mcl;                                    // slamhip_hs_mcl_set / _step / _get: the particle set and the step's blocks, made by the first set, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -152,6 +154,8 @@ int32_t hs_lat_pack_enqueue(slamhip_hs *hs, int level, bool world, const hs_clas
 void    hs_trc_free(slamhip_hs *hs);        // the blocks of the beam trace (the caller has drained the stream)
 // hs_dfield.hip
 void    hs_df_free(slamhip_hs *hs);         // the blocks of the distance field (the caller has drained the stream)
+// what slamhip_hs_distance_field and _score refuse for level, world, site_mask and radius (K13 refuses the same)
+int32_t hs_df_check(int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius);
 // K9's field of one level for another launch on the operator's stream: F over E = M grown by r cells, rows of `pitch` uint16_t; F of
 // M's cell (mx, my) is f[(my + r) * pitch + mx + r].  _prepare plans (the class map too), allocates and launches nothing; _enqueue
 // packs the class map and launches the field's two kernels, exactly as slamhip_hs_distance_field does.
@@ -179,3 +183,8 @@ int32_t hs_nav_check_field(int n_levels, const slamhip_nav_spec *spec, const int
 int32_t hs_nav_field_for_rollouts(slamhip_hs *hs, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, hs_nav_view *out);
 // hs_rollout.hip
 void    hs_ro_free(slamhip_hs *hs);         // the blocks of the command rollouts (the caller has drained the stream)
+// hs_mcl.hip
+void    hs_mcl_free(slamhip_hs *hs);        // the particle set and the blocks of the localisation step (the caller has drained the stream)
+// what slamhip_hs_mcl_step refuses before it launches anything, for a scan of n_points (scan_is_set false: the caller is about to set
+// one, so its absence is no error)
+int32_t hs_mcl_check_step(const slamhip_hs *hs, const slamhip_mcl_spec *spec, int n_points, bool scan_is_set);

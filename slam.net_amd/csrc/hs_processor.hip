@@ -408,6 +408,18 @@ extern "C" int32_t slamhip_hsproc_rollouts(slamhip_hsproc *p, const slamhip_nav_
     return SLAMHIP_OK;
 }
 
+// The localisation step through the processor: the scan set as slamhip_hsproc_relocalise sets it, then slamhip_hs_mcl_step.  What
+// that call refuses for its spec, the particle set or the scan's size is refused ahead of the scan: such a call leaves the scan that
+// was set.
+extern "C" int32_t slamhip_hsproc_mcl_step(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const slamhip_mcl_spec *spec,
+                                           slamhip_mcl_summary *out)
+{
+    SH_CHECK_ARG(p && spec && out);
+    SH_TRY(hs_mcl_check_step(p->hs, spec, n, false));
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    return slamhip_hs_mcl_step(p->hs, spec, out);
+}
+
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)
 {
     SH_CHECK_ARG(p);

@@ -131,6 +131,7 @@ class MapRepMultiMap:
                       int(numDepth), C.byref(self._h))
         self.Maps = [OccGridMap(self, l) for l in range(numDepth)]
         self._scan_set = None
+        self._mcl_n = 0                                             # particles of the last mcl_set
 
     @property
     def NumLevels(self):
@@ -410,6 +411,38 @@ class MapRepMultiMap:
         spec = capi.nav_spec(level, world, site_mask, clearance, max_cost)
         return capi.rollouts_call("slamhip_hs_rollouts", [self._h, spec.ctypes.data_as(C.c_void_p)], sources, start_pose, dt, body, cmds, hold)
 
+    def mcl_set(self, poses):
+        """The particle set of the localisation filter (slamhip_hs_mcl_set): (N, 3) poses in the window's frame, N <= 65536; every
+        accumulated cost becomes 0.  It replaces any previous set."""
+        p = capi.f32(poses, (-1, 3))
+        capi.call("slamhip_hs_mcl_set", self._h, p.ctypes.data_as(C.c_void_p), p.shape[0])
+        self._mcl_n = p.shape[0]
+
+    def mcl_step(self, spec, scan=None):
+        """One localisation step on the particle set (slamhip_hs_mcl_step; no reference counterpart): predict by spec's odometry
+        increment with noise, weigh by the scan against the distance field, resample when the effective sample size falls below
+        spec's n_eff_min -- all on the device.  spec: capi.mcl_spec's record.  -> a capi.MCL_SUMMARY record (capi.mcl_mean forms the
+        weighted-mean pose and n_eff).  scan = None: the scan already set through this object.  Blocking; it changes nothing of the
+        map."""
+        if scan is not None:
+            self.set_scan(scan)
+        out = np.zeros(1, capi.MCL_SUMMARY)
+        capi.call("slamhip_hs_mcl_step", self._h, spec.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+        return out[0]
+
+    def mcl_get(self, poses=True, acc=True, ancestors=True):
+        """The particle set as it stands (slamhip_hs_mcl_get) -> (poses (N, 3) float32, acc (N,) uint64, ancestors (N,) int32 of the
+        last step); None for what was not asked for."""
+        n = self._mcl_n
+        if not n:
+            raise ValueError("mcl_get: no particle set (mcl_set first)")
+        p = np.zeros((n, 3), np.float32) if poses else None
+        a = np.zeros(n, np.uint64) if acc else None
+        k = np.zeros(n, np.int32) if ancestors else None
+        ptr = lambda v: v.ctypes.data_as(C.c_void_p) if v is not None else None
+        capi.call("slamhip_hs_mcl_get", self._h, ptr(p), ptr(a), ptr(k), n)
+        return p, a, k
+
     def ExpectedScan(self, pose, angles, max_range, level, world=False):
         """The scan the map of `level` predicts from `pose` (window frame): per angle (rad, sensor frame) the range in metres to the
         first occupied cell on the beam of length max_range, or inf where the map holds none.  It REPLACES the scan that was set:
@@ -550,6 +583,7 @@ class HectorSLAMProcessor:
         if scrollBacking is not None:                               # (tile, max_bytes): keep what scrolls out (MapRep.set_backing)
             self.set_backing(*scrollBacking)
         self._min_dist, self._min_angle = 0.3, 0.13
+        self._mcl_origin = None                                     # the window's origin at the last LocaliseInit / LocaliseStep
 
     def _get(self):
         m = np.empty(3, np.float32); l = np.empty(3, np.float32); mt, ut = C.c_float(), C.c_float()
@@ -709,6 +743,45 @@ class HectorSLAMProcessor:
                 b = key[1]
                 return float(cmds[b, 0, 0]), float(cmds[b, 0, 1]), which, res[b], summary
         return None, None, None, None, summary
+
+    def _window_offset(self):
+        """(float)origin * cell0 per axis, as the library forms it: what a world pose loses on its way into the window's frame."""
+        ox, oy = self.get_origin()
+        cell0 = np.float32(self.MapRep.Maps[0].CellLength)
+        return np.float32(ox) * cell0, np.float32(oy) * cell0
+
+    def LocaliseInit(self, poses_world):
+        """Start Monte-Carlo localisation: the particle set of the processor's own pyramid (MapRep.mcl_set) from WORLD poses, taken to
+        the window's frame as Relocalise takes its centre (- (float)origin * cell0 per axis)."""
+        p = capi.f32(poses_world, (-1, 3)).copy()
+        off = self._window_offset()
+        if self.get_origin() != (0, 0):
+            p[:, 0] = p[:, 0] - off[0]; p[:, 1] = p[:, 1] - off[1]
+        self.MapRep.mcl_set(p)
+        self._mcl_origin = self.get_origin()
+
+    def LocaliseStep(self, scan, odometry_delta, sigma, level, beta, n_eff_min, seed=0, stream=0, site_mask=2, radius=32, world=False):
+        """One localisation step (slamhip_hsproc_mcl_step): odometry_delta = (dx, dy, dth) in the robot's frame since the last step,
+        sigma the noise scales.  If the window has scrolled since the last step, the particles -- window-frame poses -- are re-based by
+        frame_offset = -(the window's movement in metres).  -> (poseWorld, n_eff, n_distinct, summary): the weighted-mean pose in
+        the world frame (float64), A^2 / Q, the distinct ancestors, the capi.MCL_SUMMARY record.  MatchPose, LastMapUpdatePose, the
+        update gate and the map are untouched; the caller advances `stream` per step."""
+        if self._mcl_origin is None:
+            raise ValueError("LocaliseStep: no particle set (LocaliseInit first)")
+        org_now = self.get_origin()
+        was = self._mcl_origin
+        cell0 = np.float32(self.MapRep.Maps[0].CellLength)
+        fo = (-(np.float32(org_now[0] - was[0]) * cell0), -(np.float32(org_now[1] - was[1]) * cell0))
+        spec = capi.mcl_spec(level, radius, odometry_delta, sigma, beta, n_eff_min, seed, stream, site_mask, world, fo)
+        org = capi.f32(scan.Pose[:2])
+        out = np.zeros(1, capi.MCL_SUMMARY)
+        capi.call("slamhip_hsproc_mcl_step", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), spec.ctypes.data_as(C.c_void_p),
+                  out.ctypes.data_as(C.c_void_p))
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
+        self._mcl_origin = org_now
+        off = self._window_offset()
+        pose, n_eff = capi.mcl_mean(out[0], (float(off[0]), float(off[1])) if org_now != (0, 0) else (0.0, 0.0))
+        return pose, n_eff, int(out[0]["n_distinct"]), out[0]
 
     def PoseCell(self, level):
         """The WORLD cell of `level` that MatchPose lies in: the pose over the level's CellLength, rounded as the grid update rounds

@@ -66,7 +66,8 @@ def lookups(rep, poses, level, world):
     return n
 
 
-def wall_us(ctx, fn, warm=3, reps=15):
+def wall_us(ctx, fn, warm=3, reps=15, spread=False):
+    """Median microseconds per call; spread=True: a dict with the median, the least and the greatest."""
     for _ in range(warm):
         fn()
     out = []
@@ -75,6 +76,8 @@ def wall_us(ctx, fn, warm=3, reps=15):
         t0 = time.perf_counter()
         fn()
         out.append((time.perf_counter() - t0) * 1e6)
+    if spread:
+        return {"median_us": round(float(np.median(out)), 2), "min_us": round(float(np.min(out)), 2), "max_us": round(float(np.max(out)), 2)}
     return float(np.median(out))
 
 
