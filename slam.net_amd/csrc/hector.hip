@@ -125,6 +125,7 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
     if (hs->ev_pts) (void)hipEventDestroy(hs->ev_pts);
+    if (hs->ev_call) (void)hipEventDestroy(hs->ev_call);
     (void)hipFree(hs->d_k5_sec);
     (void)hipFree(hs->d_k5_byidx); (void)hipFree(hs->d_k5_cand); (void)hipFree(hs->d_k5_start); (void)hipFree(hs->d_k5_hdr);
     if (hs->h_io) (void)hipHostFree(hs->h_io);
@@ -182,6 +183,9 @@ extern "C" int32_t slamhip_hs_create(slamhip_ctx *ctx, float cell_length, int32_
         if (hipMalloc(&hs->d_io, sizeof(float) * hs->cap_io) != hipSuccess || hipHostMalloc(&hs->h_io, sizeof(float) * hs->cap_io) != hipSuccess) {
             slamhip_set_error("device allocation failed"); rc = SLAMHIP_ERR_NOMEM;
         }
+    }
+    if (rc == SLAMHIP_OK && hipEventCreateWithFlags(&hs->ev_call, hipEventDisableTiming) != hipSuccess) {
+        slamhip_set_error("event creation failed"); rc = SLAMHIP_ERR_HIP;
     }
     if (rc == SLAMHIP_OK) rc = slamhip_hs_reset(hs);
     if (rc != SLAMHIP_OK) { slamhip_hs_destroy(hs); return rc; }

@@ -1,5 +1,6 @@
 // hs_dfield.h -- the arithmetic of the distance field (K9, hs_dfield.hip) that host and device share: the kernels k9_rows and
-// k9_cols and the test hook slamhip_debug_distance_field run this text.  Definition: include/slamhip.h, slamhip_hs_distance_field.
+// k9_cols and the test hook slamhip_debug_distance_field run this text, and every reader of the field -- k9_score, k9_gather, K13's
+// k13_score and slamhip_debug_mcl_step -- looks it up through hs_field.  Definition: include/slamhip.h, slamhip_hs_distance_field.
 // Everything here is integer arithmetic; the end cell of a scan point is hs_trace.h's transform.
 #pragma once
 #include "common.h"
@@ -104,4 +105,16 @@ __host__ __device__ static inline uint32_t hs_df_col_min(const uint8_t *g, int s
         if (v < best) best = v;
     }
     return best;
+}
+
+// The field as a launch reads it: F over E = M grown by r cells on every side, rows of `pitch` cells; E's first cell is (e_x0, e_y0)
+// in the window's frame -- r = M's x0 - e_x0 -- and outside E the field is the constant `outside` (hs_df_outside).
+struct hs_field { const uint16_t *f; int ew, eh, pitch, e_x0, e_y0; uint32_t outside; };
+
+// F of window-frame cell (x, y)
+__host__ __device__ static inline uint32_t hs_field_lookup(const hs_field &E, long long x, long long y)
+{
+    const long long ex = x - E.e_x0, ey = y - E.e_y0;
+    const bool in = ex >= 0 && ex < E.ew && ey >= 0 && ey < E.eh;
+    return in ? (uint32_t)E.f[(size_t)ey * (size_t)E.pitch + (size_t)ex] : E.outside;
 }

@@ -22,11 +22,10 @@
 //    agent-scope atomic adds per workgroup into the pose's summary, zeroed in-stream ahead of the launch.
 //  * k9_gather (the field call): the asked rectangle out of E, the constant outside, into the block the result leaves through; E is
 //    never downloaded.
-#include "hs_internal.h"
+#include "hs_blocks.h"
 #include "hs_dfield.h"
 #include "hs_trace.h"
 #include <algorithm>
-#include <new>
 #include <vector>
 
 #define K9_ROW_LANES 128
@@ -95,28 +94,19 @@ __global__ void __launch_bounds__(K9_COL_LANES) k9_cols(const k9_geo A, int tile
         f[(size_t)(ey0 + ly) * A.pitch + ex] = (uint16_t)hs_df_col_min(tile_s + (ly + A.r) * K9_TX + lane, K9_TX, A.r);
 }
 
-// F of window-frame cell (x, y): E's first cell is (e_x0, e_y0)
-struct k9_field { const uint16_t *f; int ew, eh, pitch; int e_x0, e_y0; uint32_t outside; };
-__device__ static __forceinline__ uint32_t k9_lookup(const k9_field &E, long long x, long long y)
-{
-    const long long ex = x - E.e_x0, ey = y - E.e_y0;
-    const bool in = ex >= 0 && ex < E.ew && ey >= 0 && ey < E.eh;
-    return in ? (uint32_t)E.f[(size_t)ey * E.pitch + (size_t)ex] : E.outside;
-}
-
-__global__ void __launch_bounds__(256) k9_gather(const k9_field E, int x, int y, int w, int n, uint16_t *__restrict__ out)
+__global__ void __launch_bounds__(256) k9_gather(const hs_field E, int x, int y, int w, int n, uint16_t *__restrict__ out)
 {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n) return;
     const int ry = j / w, rx = j - ry * w;
-    out[j] = (uint16_t)k9_lookup(E, (long long)x + rx, (long long)y + ry);
+    out[j] = (uint16_t)hs_field_lookup(E, (long long)x + rx, (long long)y + ry);
 }
 
 struct k9s_arg {
     const float2 *pts; int n;
     const float *poses; int chunks;        // B x 3, window frame; workgroups per pose
     float stm;
-    k9_field E;
+    hs_field E;
     int r2;
     slamhip_distance_summary *sums; uint16_t *points;   // points: nullptr, or B x n
 };
@@ -138,7 +128,7 @@ __global__ void __launch_bounds__(K9S_LANES) k9_score(const k9s_arg A)
         float exf, eyf;
         sh_v2_transform(p.x, p.y, t_s, &exf, &eyf);
         counted = hs_trace_counts(exf) && hs_trace_counts(eyf);
-        if (counted) F = k9_lookup(A.E, (long long)sh_f2i(rintf(exf)), (long long)sh_f2i(rintf(eyf)));   // ToRoundPoint (banker's)
+        if (counted) F = hs_field_lookup(A.E, (long long)sh_f2i(rintf(exf)), (long long)sh_f2i(rintf(eyf)));   // ToRoundPoint (banker's)
         if (A.points) A.points[(size_t)pose * (size_t)A.n + (size_t)i] = (uint16_t)F;
     }
     const int cnt[4] = { (int)__popcll(__ballot(counted)), (int)__popcll(__ballot(have && !counted)),
@@ -162,83 +152,80 @@ __global__ void __launch_bounds__(K9S_LANES) k9_score(const k9s_arg A)
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 // What the field needs, made by the first call and kept: g and F of E, the poses in device memory, the device block of the
-// results (summaries and point records, or a field call's rectangle), the pinned block the poses leave and the results reach the
-// host through, and the event the bounded wait polls.
+// results (summaries and point records, or a field call's rectangle), and the pinned block the poses leave and the results reach
+// the host through.
 struct hs_dfield {
     uint8_t *d_g; size_t cap_g;
     uint16_t *d_f; size_t cap_f;
     float *d_poses; size_t cap_poses;
     unsigned char *d_out; size_t cap_out;
     unsigned char *h_io; size_t cap_h;
-    hipEvent_t ev;
 };
 
 void hs_df_free(slamhip_hs *hs)
 {
     hs_dfield *df = hs->dfd;
     if (!df) return;
-    (void)hipFree(df->d_g); (void)hipFree(df->d_f); (void)hipFree(df->d_poses); (void)hipFree(df->d_out);
-    if (df->h_io) (void)hipHostFree(df->h_io);
-    if (df->ev) (void)hipEventDestroy(df->ev);
+    hs_release((void **)&df->d_g, &df->cap_g, HS_MEM_DEVICE);
+    hs_release((void **)&df->d_f, &df->cap_f, HS_MEM_DEVICE);
+    hs_release((void **)&df->d_poses, &df->cap_poses, HS_MEM_DEVICE);
+    hs_release((void **)&df->d_out, &df->cap_out, HS_MEM_DEVICE);
+    hs_release((void **)&df->h_io, &df->cap_h, HS_MEM_PINNED);
     delete df;
     hs->dfd = nullptr;
 }
 
-static int32_t hs_df_grow(void **p, size_t *cap, size_t want, bool pinned)
+int32_t hs_df_check(const char *who, int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius)
 {
-    if (*cap >= want) return SLAMHIP_OK;
-    if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    if ((pinned ? hipHostMalloc(p, want, hipHostMallocDefault) : hipMalloc(p, want)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        SH_FAIL(SLAMHIP_ERR_NOMEM, "distance field: allocation of %zu bytes of %s memory failed", want, pinned ? "pinned host" : "device");
-    }
-    *cap = want;
+    if (level < 0 || level >= n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: level %d of %d", who, level, n_levels);
+    if (world != 0 && world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: world = %d must be 0 (the window) or 1 (the world)", who, world);
+    if (site_mask < 1 || site_mask > 7) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: site_mask = %d must lie in [1, 7]", who, site_mask);
+    if (radius < 1 || radius > HS_DF_MAX_RADIUS) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: radius = %d must lie in [1, %d]", who, radius, HS_DF_MAX_RADIUS);
     return SLAMHIP_OK;
 }
 
-int32_t hs_df_check(int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius)
+int32_t hs_df_check_score(const char *who, int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius, int32_t B, bool want_points,
+                          int n_points, bool scan_is_set)
 {
-    if (level < 0 || level >= n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: level %d of %d", level, n_levels);
-    if (world != 0 && world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: world = %d must be 0 (the window) or 1 (the world)", world);
-    if (site_mask < 1 || site_mask > 7) SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: site_mask = %d must lie in [1, 7]", site_mask);
-    if (radius < 1 || radius > HS_DF_MAX_RADIUS) SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: radius = %d must lie in [1, %d]", radius, HS_DF_MAX_RADIUS);
+    SH_TRY(hs_df_check(who, n_levels, level, world, site_mask, radius));
+    if (B < 1 || B > HS_DF_MAX_POSES) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: B = %d must lie in [1, %d]", B, HS_DF_MAX_POSES);
+    if (scan_is_set && n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "distance score: no scan (slamhip_hs_set_scan first)");
+    if (want_points && (int64_t)B * n_points > HS_DF_MAX_POINTS)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: per-point records of %d poses x %d points, more than 2^22", B, n_points);
     return SLAMHIP_OK;
 }
 
-// The plan of one field: the class map prepared (the world's plan refuses before anything is launched), E sized and refused if too
-// large, the hs's block made if this is its first use, g and F grown.  Nothing is launched.
-static int32_t hs_df_plan(slamhip_hs *hs, int level, bool world, int site_mask, int radius, hs_class_map *M, k9_geo *G, k9_field *E)
+// The plan of one field, for this unit's calls and for other units' launches (K11's clearance, K13's weights): the class map
+// prepared (the world's plan refuses before anything is launched), E sized and refused if too large, the hs's block made if this is
+// its first use, g and F grown.  Nothing is launched.
+int32_t hs_df_field_prepare(slamhip_hs *hs, int level, bool world, int site_mask, int radius, hs_class_map *M, hs_field *E)
 {
     SH_TRY(hs_lat_pack_prepare(hs, level, world, M));
     const int64_t ew = (int64_t)M->w + 2 * radius, eh = (int64_t)M->h + 2 * radius;
     if (ew * eh > HS_DF_MAX_E)
         SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: E, the map of level %d grown by the radius, is %lld x %lld cells, more than 2^26", level,
                 (long long)ew, (long long)eh);
-    if (!hs->dfd) {
-        hs->dfd = new (std::nothrow) hs_dfield();                         // (value-initialised: nothing allocated yet)
-        if (!hs->dfd) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-    }
+    SH_TRY(hs_unit(&hs->dfd));
     hs_dfield *df = hs->dfd;
-    if (!df->ev) SH_HIP(hipEventCreateWithFlags(&df->ev, hipEventDisableTiming));
-    G->cls = M->cls; G->w = M->w; G->h = M->h; G->wpr = M->wpr;
-    G->r = radius; G->mask = site_mask;
-    G->ew = (int)ew; G->eh = (int)eh; G->pitch = ((int)ew + 3) & ~3;
-    // (the blocks are idle: every call waits for its own launches, and a call that timed out has poisoned the context)
-    const size_t cells = (size_t)G->pitch * (size_t)G->eh;
-    SH_TRY(hs_df_grow((void **)&df->d_g, &df->cap_g, cells, false));
-    SH_TRY(hs_df_grow((void **)&df->d_f, &df->cap_f, cells * sizeof(uint16_t), false));
-    E->f = df->d_f; E->ew = G->ew; E->eh = G->eh; E->pitch = G->pitch;
+    E->ew = (int)ew; E->eh = (int)eh; E->pitch = ((int)ew + 3) & ~3;
     E->e_x0 = M->x0 - radius; E->e_y0 = M->y0 - radius;                    // (-2^28 < x0 <= 0: no overflow)
     E->outside = hs_df_outside(site_mask, radius);
+    const size_t cells = (size_t)E->pitch * (size_t)E->eh;
+    SH_TRY(hs_grow((void **)&df->d_g, &df->cap_g, cells, HS_MEM_DEVICE, "distance field"));
+    SH_TRY(hs_grow((void **)&df->d_f, &df->cap_f, cells * sizeof(uint16_t), HS_MEM_DEVICE, "distance field"));
+    E->f = df->d_f;
     return SLAMHIP_OK;
 }
 
-// the class map's pack and the two launches of the field, on the operator's stream (no timing class of their own)
-static int32_t hs_df_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M, const k9_geo &G)
+// the class map's pack and the two launches of the planned field, on the operator's stream (no timing class of their own)
+int32_t hs_df_field_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M, const hs_field *E, int site_mask)
 {
     hs_dfield *df = hs->dfd;
     SH_TRY(hs_lat_pack_enqueue(hs, level, world, M));
+    k9_geo G;
+    G.cls = M->cls; G.w = M->w; G.h = M->h; G.wpr = M->wpr;
+    G.r = M->x0 - E->e_x0; G.mask = site_mask;
+    G.ew = E->ew; G.eh = E->eh; G.pitch = E->pitch;
     const int segs = sh_div_up(G.pitch, K9_SEG), tiles_x = sh_div_up(G.ew, K9_TX), tiles_y = sh_div_up(G.eh, K9_TY);
     // (at most 2^26 cells in E: neither grid reaches 2^31 workgroups)
     hipLaunchKernelGGL(k9_rows, dim3((unsigned)segs * (unsigned)G.eh), dim3(K9_ROW_LANES), 0, hs->ctx->stream, G, segs, df->d_g);
@@ -248,48 +235,27 @@ static int32_t hs_df_enqueue(slamhip_hs *hs, int level, bool world, const hs_cla
     return SLAMHIP_OK;
 }
 
-// The field for another unit's launches on the operator's stream (K11's clearance): _prepare is hs_df_plan, _enqueue hs_df_enqueue
-// -- the class map's pack and the two launches, nothing else -- with the plan's geometry formed again from M.
-int32_t hs_df_field_prepare(slamhip_hs *hs, int level, bool world, int site_mask, int radius, hs_class_map *M, hs_field_view *V)
-{
-    k9_geo G; k9_field E;
-    SH_TRY(hs_df_plan(hs, level, world, site_mask, radius, M, &G, &E));
-    V->f = E.f; V->pitch = G.pitch; V->r = radius;
-    return SLAMHIP_OK;
-}
-int32_t hs_df_field_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M, int site_mask, int radius)
-{
-    k9_geo G;
-    G.cls = M->cls; G.w = M->w; G.h = M->h; G.wpr = M->wpr;
-    G.r = radius; G.mask = site_mask;
-    G.ew = M->w + 2 * radius; G.eh = M->h + 2 * radius; G.pitch = (G.ew + 3) & ~3;   // (as hs_df_plan, which has refused an E over 2^26 cells)
-    return hs_df_enqueue(hs, level, world, M, G);
-}
-
 extern "C" int32_t slamhip_hs_distance_field(slamhip_hs *hs, int32_t level, int32_t world, int32_t site_mask, int32_t radius,
                                              int32_t x, int32_t y, int32_t w, int32_t h, uint16_t *out_d2)
 {
     SH_CHECK_ARG(hs && out_d2);
-    SH_TRY(hs_df_check(hs->n_levels, level, world, site_mask, radius));
+    SH_TRY(hs_df_check("distance field", hs->n_levels, level, world, site_mask, radius));
     if (w < 1 || h < 1 || (int64_t)w * h > HS_DF_MAX_RECT)
         SH_FAIL(SLAMHIP_ERR_INVALID, "distance field: a rectangle of %d x %d cells; w, h >= 1 and w * h <= 2^24", w, h);
     slamhip_ctx *ctx = hs->ctx;
-    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
-    SH_HIP(hipSetDevice(ctx->device));
-    hs_class_map M; k9_geo G; k9_field E;
-    SH_TRY(hs_df_plan(hs, level, world != 0, site_mask, radius, &M, &G, &E));
+    SH_TRY(hs_call_begin(hs));
+    hs_class_map M; hs_field E;
+    SH_TRY(hs_df_field_prepare(hs, level, world != 0, site_mask, radius, &M, &E));
     hs_dfield *df = hs->dfd;
     const int n = w * h;
     const size_t out_bytes = sizeof(uint16_t) * (size_t)n;
-    SH_TRY(hs_df_grow((void **)&df->d_out, &df->cap_out, out_bytes, false));
-    SH_TRY(hs_df_grow((void **)&df->h_io, &df->cap_h, out_bytes, true));
-    SH_TRY(hs_df_enqueue(hs, level, world != 0, &M, G));
+    SH_TRY(hs_grow((void **)&df->d_out, &df->cap_out, out_bytes, HS_MEM_DEVICE, "distance field"));
+    SH_TRY(hs_grow((void **)&df->h_io, &df->cap_h, out_bytes, HS_MEM_PINNED, "distance field"));
+    SH_TRY(hs_df_field_enqueue(hs, level, world != 0, &M, &E, site_mask));
     hipLaunchKernelGGL(k9_gather, dim3((unsigned)sh_div_up(n, 256)), dim3(256), 0, ctx->stream, E, x, y, w, n, (uint16_t *)df->d_out);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(df->h_io, df->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SH_HIP(hipEventRecord(df->ev, ctx->stream));
-    SH_TRY(sh_event_wait(ctx, df->ev));
-    hs->launch_done = hs->launch_count;                                    // (the stream has drained up to here)
+    SH_TRY(hs_call_finish(hs));
     memcpy(out_d2, df->h_io, out_bytes);
     return SLAMHIP_OK;
 }
@@ -298,33 +264,28 @@ extern "C" int32_t slamhip_hs_distance_score(slamhip_hs *hs, int32_t level, int3
                                              const float *poses, int32_t B, slamhip_distance_summary *out_summaries, uint16_t *out_points)
 {
     SH_CHECK_ARG(hs && poses && out_summaries);
-    SH_TRY(hs_df_check(hs->n_levels, level, world, site_mask, radius));
-    if (B < 1 || B > HS_DF_MAX_POSES) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: B = %d must lie in [1, %d]", B, HS_DF_MAX_POSES);
-    if (hs->n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "distance score: no scan (slamhip_hs_set_scan first)");
+    SH_TRY(hs_df_check_score("distance field", hs->n_levels, level, world, site_mask, radius, B, out_points != nullptr, hs->n_points, true));
     const int n = hs->n_points;
-    if (out_points && (int64_t)B * n > HS_DF_MAX_POINTS)
-        SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: per-point records of %d poses x %d points, more than 2^22", B, n);
     slamhip_ctx *ctx = hs->ctx;
-    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
-    SH_HIP(hipSetDevice(ctx->device));
+    SH_TRY(hs_call_begin(hs));
     const int chunks = sh_div_up(n, K9S_LANES);
     if ((int64_t)B * chunks > (int64_t)INT32_MAX) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: %d poses x %d points, more workgroups than one launch takes", B, n);
-    hs_class_map M; k9_geo G; k9_field E;
-    SH_TRY(hs_df_plan(hs, level, world != 0, site_mask, radius, &M, &G, &E));
+    hs_class_map M; hs_field E;
+    SH_TRY(hs_df_field_prepare(hs, level, world != 0, site_mask, radius, &M, &E));
     hs_dfield *df = hs->dfd;
     const size_t pose_bytes = sizeof(float) * 3 * (size_t)B;
     const size_t sum_bytes = sizeof(slamhip_distance_summary) * (size_t)B;
     const size_t pts_bytes = out_points ? sizeof(uint16_t) * (size_t)B * n : 0;
     const size_t out_bytes = (sum_bytes + pts_bytes + 7) & ~(size_t)7;     // (the poses follow, 8-byte aligned)
-    SH_TRY(hs_df_grow((void **)&df->d_poses, &df->cap_poses, pose_bytes, false));
-    SH_TRY(hs_df_grow((void **)&df->d_out, &df->cap_out, out_bytes, false));
-    SH_TRY(hs_df_grow((void **)&df->h_io, &df->cap_h, out_bytes + pose_bytes, true));
+    SH_TRY(hs_grow((void **)&df->d_poses, &df->cap_poses, pose_bytes, HS_MEM_DEVICE, "distance field"));
+    SH_TRY(hs_grow((void **)&df->d_out, &df->cap_out, out_bytes, HS_MEM_DEVICE, "distance field"));
+    SH_TRY(hs_grow((void **)&df->h_io, &df->cap_h, out_bytes + pose_bytes, HS_MEM_PINNED, "distance field"));
     float *h_poses = (float *)(df->h_io + out_bytes);
     memcpy(h_poses, poses, pose_bytes);
     SH_TRY(hs_flush_scan(hs));
     SH_HIP(hipMemcpyAsync(df->d_poses, h_poses, pose_bytes, hipMemcpyHostToDevice, ctx->stream));
     SH_HIP(hipMemsetAsync(df->d_out, 0, sum_bytes, ctx->stream));
-    SH_TRY(hs_df_enqueue(hs, level, world != 0, &M, G));
+    SH_TRY(hs_df_field_enqueue(hs, level, world != 0, &M, &E, site_mask));
     k9s_arg A;
     A.pts = hs->d_pts; A.n = n;
     A.poses = df->d_poses; A.chunks = chunks;
@@ -335,9 +296,7 @@ extern "C" int32_t slamhip_hs_distance_score(slamhip_hs *hs, int32_t level, int3
     hipLaunchKernelGGL(k9_score, dim3((unsigned)(B * chunks)), dim3(K9S_LANES), 0, ctx->stream, A);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(df->h_io, df->d_out, sum_bytes + pts_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SH_HIP(hipEventRecord(df->ev, ctx->stream));
-    SH_TRY(sh_event_wait(ctx, df->ev));
-    hs->launch_done = hs->launch_count;                                    // (the stream has drained up to here)
+    SH_TRY(hs_call_finish(hs));
     memcpy(out_summaries, df->h_io, sum_bytes);
     if (out_points) memcpy(out_points, df->h_io + sum_bytes, pts_bytes);
     return SLAMHIP_OK;

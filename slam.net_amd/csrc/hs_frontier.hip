@@ -27,10 +27,9 @@
 // Every loop that follows parent links or retries an atomic carries the cap G.cap = cells of M + 2: a path is never longer than the
 // number of run starts, and a retry happens only when a root has changed, which it does at most once per run.  Word scans end at
 // the row's ends.  On overrun the lane sets the flag word and leaves the loop; the host then reports SLAMHIP_ERR_STATE.
-#include "hs_internal.h"
+#include "hs_blocks.h"
 #include "hs_frontier.h"
 #include <algorithm>
-#include <new>
 #include <vector>
 
 #define K10_WG_WORDS 16                    // frontier words of one row a workgroup owns: 512 cells
@@ -260,8 +259,8 @@ __global__ void __launch_bounds__(256) k10_gather(const k10_geo G, int gx, int g
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 // What the labelling needs, made by the first call and kept: the frontier words, parent and count over M, the counters and the
-// record block, the labels' device block, the two pinned blocks the results reach the host through (counters and records, stored by k10_emit;
-// the labels, copied), and the event the bounded wait polls.
+// record block, the labels' device block, and the two pinned, device-visible blocks the results reach the host through (counters and
+// records, stored by k10_emit; the labels, copied).
 struct hs_frontier {
     uint32_t *d_fw; size_t cap_fw;
     int *d_parent; size_t cap_parent;
@@ -271,7 +270,6 @@ struct hs_frontier {
     int *d_labels; size_t cap_labels;
     unsigned char *h_head; size_t cap_head;   // device-visible: k10_emit stores into it
     unsigned char *h_labels; size_t cap_hl;
-    hipEvent_t ev;
 };
 #define HS_FR_HEAD_BYTES (sizeof(int) * K10_CTRS + sizeof(slamhip_frontier_cluster) * (size_t)HS_FR_MAX_CLUSTERS)
 
@@ -279,26 +277,16 @@ void hs_fr_free(slamhip_hs *hs)
 {
     hs_frontier *fr = hs->frl;
     if (!fr) return;
-    (void)hipFree(fr->d_fw); (void)hipFree(fr->d_parent); (void)hipFree(fr->d_count); (void)hipFree(fr->d_ctr); (void)hipFree(fr->d_rec);
-    (void)hipFree(fr->d_labels);
-    if (fr->h_head) (void)hipHostFree(fr->h_head);
-    if (fr->h_labels) (void)hipHostFree(fr->h_labels);
-    if (fr->ev) (void)hipEventDestroy(fr->ev);
+    hs_release((void **)&fr->d_fw, &fr->cap_fw, HS_MEM_DEVICE);
+    hs_release((void **)&fr->d_parent, &fr->cap_parent, HS_MEM_DEVICE);
+    hs_release((void **)&fr->d_count, &fr->cap_count, HS_MEM_DEVICE);
+    hs_release((void **)&fr->d_ctr, &fr->cap_ctr, HS_MEM_DEVICE);
+    hs_release((void **)&fr->d_rec, &fr->cap_rec, HS_MEM_DEVICE);
+    hs_release((void **)&fr->d_labels, &fr->cap_labels, HS_MEM_DEVICE);
+    hs_release((void **)&fr->h_head, &fr->cap_head, HS_MEM_PINNED_VISIBLE);
+    hs_release((void **)&fr->h_labels, &fr->cap_hl, HS_MEM_PINNED_VISIBLE);
     delete fr;
     hs->frl = nullptr;
-}
-
-static int32_t hs_fr_grow(void **p, size_t *cap, size_t want, bool pinned)
-{
-    if (*cap >= want) return SLAMHIP_OK;
-    if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    if ((pinned ? hipHostMalloc(p, want, hipHostMallocMapped | hipHostMallocCoherent) : hipMalloc(p, want)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        SH_FAIL(SLAMHIP_ERR_NOMEM, "frontiers: allocation of %zu bytes of %s memory failed", want, pinned ? "pinned host" : "device");
-    }
-    *cap = want;
-    return SLAMHIP_OK;
 }
 
 // what both entry points refuse for their arguments alone
@@ -347,34 +335,28 @@ extern "C" int32_t slamhip_hs_frontiers(slamhip_hs *hs, int32_t level, int32_t w
     if (out_labels && (lw < 1 || lh < 1 || (int64_t)lw * lh > HS_FR_MAX_RECT))
         SH_FAIL(SLAMHIP_ERR_INVALID, "frontiers: a label rectangle of %d x %d cells; lw, lh >= 1 and lw * lh <= 2^24", lw, lh);
     slamhip_ctx *ctx = hs->ctx;
-    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
-    SH_HIP(hipSetDevice(ctx->device));
+    SH_TRY(hs_call_begin(hs));
     hs_class_map M;
     SH_TRY(hs_lat_pack_prepare(hs, level, world != 0, &M));
     const int64_t cells = (int64_t)M.w * M.h;
     if (cells > HS_FR_MAX_M)
         SH_FAIL(SLAMHIP_ERR_INVALID, "frontiers: M, the class map of level %d, is %d x %d cells, more than 2^25", level, M.w, M.h);
-    if (!hs->frl) {
-        hs->frl = new (std::nothrow) hs_frontier();                       // (value-initialised: nothing allocated yet)
-        if (!hs->frl) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-    }
+    SH_TRY(hs_unit(&hs->frl));
     hs_frontier *fr = hs->frl;
-    if (!fr->ev) SH_HIP(hipEventCreateWithFlags(&fr->ev, hipEventDisableTiming));
     k10_geo G;
     G.cls = M.cls; G.w = M.w; G.h = M.h; G.wpr = M.wpr;
     G.fwpr = (M.w + 31) / 32; G.wgx = sh_div_up(G.fwpr, K10_WG_WORDS);
     G.cap = (int)cells + 2; G.min_cells = min_cells;
     const int n_labels = out_labels ? lw * lh : 0;
     const size_t label_bytes = sizeof(int) * (size_t)n_labels;
-    // (the blocks are idle: every call waits for its own launches, and a call that timed out has poisoned the context)
-    SH_TRY(hs_fr_grow((void **)&fr->d_fw, &fr->cap_fw, sizeof(uint32_t) * (size_t)G.fwpr * G.h, false));
-    SH_TRY(hs_fr_grow((void **)&fr->d_parent, &fr->cap_parent, sizeof(int) * (size_t)cells, false));
-    SH_TRY(hs_fr_grow((void **)&fr->d_count, &fr->cap_count, sizeof(int) * (size_t)cells, false));
-    SH_TRY(hs_fr_grow((void **)&fr->d_ctr, &fr->cap_ctr, sizeof(int) * K10_CTRS, false));
-    SH_TRY(hs_fr_grow((void **)&fr->d_rec, &fr->cap_rec, sizeof(slamhip_frontier_cluster) * (size_t)HS_FR_MAX_CLUSTERS, false));
-    if (n_labels) SH_TRY(hs_fr_grow((void **)&fr->d_labels, &fr->cap_labels, label_bytes, false));
-    SH_TRY(hs_fr_grow((void **)&fr->h_head, &fr->cap_head, HS_FR_HEAD_BYTES, true));
-    if (n_labels) SH_TRY(hs_fr_grow((void **)&fr->h_labels, &fr->cap_hl, label_bytes, true));
+    SH_TRY(hs_grow((void **)&fr->d_fw, &fr->cap_fw, sizeof(uint32_t) * (size_t)G.fwpr * G.h, HS_MEM_DEVICE, "frontiers"));
+    SH_TRY(hs_grow((void **)&fr->d_parent, &fr->cap_parent, sizeof(int) * (size_t)cells, HS_MEM_DEVICE, "frontiers"));
+    SH_TRY(hs_grow((void **)&fr->d_count, &fr->cap_count, sizeof(int) * (size_t)cells, HS_MEM_DEVICE, "frontiers"));
+    SH_TRY(hs_grow((void **)&fr->d_ctr, &fr->cap_ctr, sizeof(int) * K10_CTRS, HS_MEM_DEVICE, "frontiers"));
+    SH_TRY(hs_grow((void **)&fr->d_rec, &fr->cap_rec, sizeof(slamhip_frontier_cluster) * (size_t)HS_FR_MAX_CLUSTERS, HS_MEM_DEVICE, "frontiers"));
+    if (n_labels) SH_TRY(hs_grow((void **)&fr->d_labels, &fr->cap_labels, label_bytes, HS_MEM_DEVICE, "frontiers"));
+    SH_TRY(hs_grow((void **)&fr->h_head, &fr->cap_head, HS_FR_HEAD_BYTES, HS_MEM_PINNED_VISIBLE, "frontiers"));
+    if (n_labels) SH_TRY(hs_grow((void **)&fr->h_labels, &fr->cap_hl, label_bytes, HS_MEM_PINNED_VISIBLE, "frontiers"));
     G.fw = fr->d_fw; G.parent = fr->d_parent; G.count = fr->d_count; G.ctr = fr->d_ctr; G.rec = fr->d_rec;
     // (at most 2^25 cells in M: no grid reaches 2^31 workgroups)
     const dim3 grid((unsigned)G.wgx * (unsigned)sh_div_up(G.h, K10_WG_ROWS)), lanes(K10_LANES);
@@ -400,9 +382,7 @@ extern "C" int32_t slamhip_hs_frontiers(slamhip_hs *hs, int32_t level, int32_t w
         SH_HIP(hipGetLastError());
         SH_HIP(hipMemcpyAsync(fr->h_labels, fr->d_labels, label_bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
-    SH_HIP(hipEventRecord(fr->ev, ctx->stream));
-    SH_TRY(sh_event_wait(ctx, fr->ev));
-    hs->launch_done = hs->launch_count;                                    // (the stream has drained up to here)
+    SH_TRY(hs_call_finish(hs));
     const int *ctr = (const int *)fr->h_head;
     if (ctr[K10_C_FLAG]) SH_FAIL(SLAMHIP_ERR_STATE, "frontier labelling did not converge (level %d, M of %d x %d cells)", level, M.w, M.h);
     SH_TRY(hs_fr_finish(ctr, (slamhip_frontier_cluster *)(fr->h_head + sizeof(int) * K10_CTRS), M.x0, M.y0, M.w, M.h, max_clusters, out_summary,

@@ -46,6 +46,7 @@ struct hs_frontier;                        // hs_frontier.hip
 struct hs_nav;                             // hs_nav.hip
 struct hs_rollout;                         // hs_rollout.hip
 struct hs_mcl;                             // hs_mcl.hip
+struct hs_field;                           // hs_dfield.h
 struct slamhip_hs {
     slamhip_ctx *ctx;
     int n_levels;
@@ -68,6 +69,7 @@ struct slamhip_hs {
     // mailbox's sequence word (the mailbox is 64 B, the report 76)
     slamhip_match_report *d_rep, *h_rep; int cap_rep; unsigned long long *d_best_key;
     int64_t win_ox, win_oy;                                // slamhip_hs_shift: where cell (0, 0) of level 0 lies in the world, in level-0 cells (host-side books only)
+    hipEvent_t ev_call;                                    // what the blocking calls of K7 .. K13 record and wait on before they return (hs_call_finish, hs_blocks.h)
     struct hs_backing *bk;                                 // slamhip_hs_set_backing: the tile pool and its host directory; nullptr while backing is off
     struct hs_world *wp;                                   // slamhip_hs_world_cells_upload / _world_extends: their staging buffer, made by the first call, kept
     struct hs_lattice *lat;                                // slamhip_hs_lattice_search: the class map and the result blocks, made by the first search, kept
@@ -152,16 +154,21 @@ int32_t hs_lat_pack_prepare(slamhip_hs *hs, int level, bool world, hs_class_map 
 int32_t hs_lat_pack_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M);
 // hs_trace.hip
 void    hs_trc_free(slamhip_hs *hs);        // the blocks of the beam trace (the caller has drained the stream)
+// what slamhip_hs_trace refuses for its arguments alone, for a scan of n_points (scan_is_set false: the caller is about to set one,
+// so its absence is no error)
+int32_t hs_trc_check(int n_levels, int32_t level, int32_t B, int32_t world, bool want_beams, int n_points, bool scan_is_set);
 // hs_dfield.hip
 void    hs_df_free(slamhip_hs *hs);         // the blocks of the distance field (the caller has drained the stream)
-// what slamhip_hs_distance_field and _score refuse for level, world, site_mask and radius (K13 refuses the same)
-int32_t hs_df_check(int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius);
-// K9's field of one level for another launch on the operator's stream: F over E = M grown by r cells, rows of `pitch` uint16_t; F of
-// M's cell (mx, my) is f[(my + r) * pitch + mx + r].  _prepare plans (the class map too), allocates and launches nothing; _enqueue
-// packs the class map and launches the field's two kernels, exactly as slamhip_hs_distance_field does.
-struct hs_field_view { const uint16_t *f; int pitch, r; };
-int32_t hs_df_field_prepare(slamhip_hs *hs, int level, bool world, int site_mask, int radius, hs_class_map *M, hs_field_view *V);
-int32_t hs_df_field_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M, int site_mask, int radius);
+// what slamhip_hs_distance_field and _score refuse for level, world, site_mask and radius (K13 refuses the same); who: the message's prefix
+int32_t hs_df_check(const char *who, int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius);
+// ... and what slamhip_hs_distance_score refuses for its arguments alone (n_points, scan_is_set: as hs_trc_check)
+int32_t hs_df_check_score(const char *who, int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius, int32_t B, bool want_points,
+                          int n_points, bool scan_is_set);
+// K9's field of one level (hs_field, hs_dfield.h) for another launch on the operator's stream.  _prepare plans (the class map too),
+// allocates and launches nothing; _enqueue packs the class map and launches the field's two kernels.  slamhip_hs_distance_field and
+// _score run these two themselves.
+int32_t hs_df_field_prepare(slamhip_hs *hs, int level, bool world, int site_mask, int radius, hs_class_map *M, hs_field *E);
+int32_t hs_df_field_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M, const hs_field *E, int site_mask);
 // hs_frontier.hip
 void    hs_fr_free(slamhip_hs *hs);         // the blocks of the frontier labelling (the caller has drained the stream)
 // hs_nav.hip

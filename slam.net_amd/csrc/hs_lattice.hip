@@ -31,12 +31,12 @@
 //    their edges fall anywhere in a 16-cell word (a tile's edge, (ox >> level) odd): a lane forms the bits of the up to 16 cells
 //    that one piece row has in one word, stores the word plainly if the row covers all of it, and merges it with a 32-bit atomic
 //    OR otherwise.  No word is both stored and merged: a word that one row covers wholly holds no cell of another piece.
+#include "hs_blocks.h"
 #include "hs_tiles.h"
 #include "hs_lattice.h"
 #include "world_pack_plan.h"
 #include <algorithm>
 #include <math.h>
-#include <new>
 
 #define K7_LANES 256
 #define K7_CHUNK 1024                      // points per LDS chunk (8 KB)
@@ -208,12 +208,11 @@ __global__ void __launch_bounds__(K7_LANES) k7_search(const k7_arg A)
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 // What a search needs, made by the first one and kept: the class map (grown to the largest level searched), the device block of
-// keys and scores, its pinned twin the results reach the host through, and the event the bounded wait polls.
+// keys and scores, and its pinned twin the results reach the host through.
 struct hs_lattice {
     uint32_t *d_cls; size_t cap_cls;                                       // words
     unsigned char *d_out; size_t cap_out;                                  // n_theta keys, then the score volume
     unsigned char *h_out; size_t cap_h;
-    hipEvent_t ev;
     // the world search: the job pieces in device memory, and the host vectors they are planned in
     unsigned char *d_pieces; size_t cap_pieces;
     std::vector<int64_t> tiles;                                            // (ty, tx) of every tile of the level
@@ -225,9 +224,10 @@ void hs_lat_free(slamhip_hs *hs)
 {
     hs_lattice *lt = hs->lat;
     if (!lt) return;
-    (void)hipFree(lt->d_cls); (void)hipFree(lt->d_out); (void)hipFree(lt->d_pieces);
-    if (lt->h_out) (void)hipHostFree(lt->h_out);
-    if (lt->ev) (void)hipEventDestroy(lt->ev);
+    hs_release((void **)&lt->d_cls, &lt->cap_cls, HS_MEM_DEVICE);
+    hs_release((void **)&lt->d_out, &lt->cap_out, HS_MEM_DEVICE);
+    hs_release((void **)&lt->h_out, &lt->cap_h, HS_MEM_PINNED);
+    hs_release((void **)&lt->d_pieces, &lt->cap_pieces, HS_MEM_DEVICE);
     delete lt;
     hs->lat = nullptr;
 }
@@ -243,19 +243,6 @@ static int32_t hs_lat_check_spec(const slamhip_hs *hs, const slamhip_lattice_spe
         SH_FAIL(SLAMHIP_ERR_INVALID, "lattice: %lld nodes, more than 2^26", (long long)S->n_theta * (2 * S->nx + 1) * (2 * S->ny + 1));
     if (!(isfinite(S->centre[0]) && isfinite(S->centre[1]) && isfinite(S->centre[2]) && isfinite(S->dtheta)))
         SH_FAIL(SLAMHIP_ERR_INVALID, "lattice: centre and dtheta must be finite");
-    return SLAMHIP_OK;
-}
-
-static int32_t hs_lat_grow(void **p, size_t *cap, size_t want, bool pinned)
-{
-    if (*cap >= want) return SLAMHIP_OK;
-    if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    if ((pinned ? hipHostMalloc(p, want, hipHostMallocDefault) : hipMalloc(p, want)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        SH_FAIL(SLAMHIP_ERR_NOMEM, "lattice: allocation of %zu bytes of %s memory failed", want, pinned ? "pinned host" : "device");
-    }
-    *cap = want;
     return SLAMHIP_OK;
 }
 
@@ -300,20 +287,15 @@ static int32_t hs_lat_plan_world(slamhip_hs *hs, hs_lattice *lt, int level, wpp_
 // device blocks grown.  hs_lat_pack_enqueue: the pack launch -- k7_pack for the window, the memset and k7_pack_world for the world.
 int32_t hs_lat_pack_prepare(slamhip_hs *hs, int level, bool world, hs_class_map *M)
 {
-    if (!hs->lat) {
-        hs->lat = new (std::nothrow) hs_lattice();                        // (value-initialised: nothing allocated yet)
-        if (!hs->lat) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-    }
+    SH_TRY(hs_unit(&hs->lat));
     hs_lattice *lt = hs->lat;
-    if (!lt->ev) SH_HIP(hipEventCreateWithFlags(&lt->ev, hipEventDisableTiming));
     const hs_level &L = hs->lv[level];
     wpp_rect R = { 0, 0, L.w, L.h };                                       // what the class map covers, in the window's frame
     if (world) SH_TRY(hs_lat_plan_world(hs, lt, level, &R));               // (refuses before anything is allocated or launched)
     M->w = (int)R.w; M->h = (int)R.h; M->wpr = (M->w + 15) / 16;
     M->x0 = (int)R.x0; M->y0 = (int)R.y0;
-    // (the blocks are idle: every search waits for its own launches, and a search that timed out has poisoned the context)
-    SH_TRY(hs_lat_grow((void **)&lt->d_cls, &lt->cap_cls, sizeof(uint32_t) * (size_t)M->wpr * M->h, false));
-    if (world) SH_TRY(hs_lat_grow((void **)&lt->d_pieces, &lt->cap_pieces, sizeof(k7w_piece) * lt->pieces.size(), false));
+    SH_TRY(hs_grow((void **)&lt->d_cls, &lt->cap_cls, sizeof(uint32_t) * (size_t)M->wpr * M->h, HS_MEM_DEVICE, "lattice"));
+    if (world) SH_TRY(hs_grow((void **)&lt->d_pieces, &lt->cap_pieces, sizeof(k7w_piece) * lt->pieces.size(), HS_MEM_DEVICE, "lattice"));
     M->cls = lt->d_cls;
     return SLAMHIP_OK;
 }
@@ -343,8 +325,7 @@ static int32_t hs_lat_run(slamhip_hs *hs, const slamhip_lattice_spec *S, bool wa
     SH_TRY(hs_lat_check_spec(hs, S));
     if (hs->n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "lattice: no scan (slamhip_hs_set_scan first)");
     slamhip_ctx *ctx = hs->ctx;
-    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
-    SH_HIP(hipSetDevice(ctx->device));
+    SH_TRY(hs_call_begin(hs));
     hs_class_map M;
     SH_TRY(hs_lat_pack_prepare(hs, S->level, world, &M));
     hs_lattice *lt = hs->lat;
@@ -352,9 +333,8 @@ static int32_t hs_lat_run(slamhip_hs *hs, const slamhip_lattice_spec *S, bool wa
     const int NX = 2 * S->nx + 1, NY = 2 * S->ny + 1;
     const size_t key_bytes = sizeof(uint64_t) * (size_t)S->n_theta;
     const size_t out_bytes = key_bytes + (want_scores ? sizeof(int32_t) * (size_t)S->n_theta * NX * NY : 0);
-    // (the blocks are idle: every search waits for its own launches, and a search that timed out has poisoned the context)
-    SH_TRY(hs_lat_grow((void **)&lt->d_out, &lt->cap_out, out_bytes, false));
-    SH_TRY(hs_lat_grow((void **)&lt->h_out, &lt->cap_h, out_bytes, true));
+    SH_TRY(hs_grow((void **)&lt->d_out, &lt->cap_out, out_bytes, HS_MEM_DEVICE, "lattice"));
+    SH_TRY(hs_grow((void **)&lt->h_out, &lt->cap_h, out_bytes, HS_MEM_PINNED, "lattice"));
     SH_TRY(hs_flush_scan(hs));
     SH_HIP(hipMemsetAsync(lt->d_out, 0, key_bytes, ctx->stream));
     SH_TRY(hs_lat_pack_enqueue(hs, S->level, world, &M));
@@ -375,9 +355,7 @@ static int32_t hs_lat_run(slamhip_hs *hs, const slamhip_lattice_spec *S, bool wa
     }
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(lt->h_out, lt->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SH_HIP(hipEventRecord(lt->ev, ctx->stream));
-    SH_TRY(sh_event_wait(ctx, lt->ev));
-    hs->launch_done = hs->launch_count;                                    // (the stream has drained up to here)
+    SH_TRY(hs_call_finish(hs));
     *keys = (const uint64_t *)lt->h_out;
     if (scores) *scores = want_scores ? (const int32_t *)(lt->h_out + key_bytes) : (const int32_t *)nullptr;
     return SLAMHIP_OK;

@@ -34,16 +34,6 @@ __host__ __device__ static inline uint32_t hs_mcl_table(int f)
 struct hs_mcl_pose { float x, y, th; };
 // the floats and the generator's words of a slamhip_mcl_spec, by value
 struct hs_mcl_motion { float dx, dy, dth, sx, sy, sth, fox, foy; uint32_t key0, key1, str0, str1; };
-// K9's field as the step reads it: F over E, rows of `pitch` cells, E's first cell (e_x0, e_y0) in the window's frame, the constant outside
-struct hs_mcl_field { const uint16_t *f; int ew, eh, pitch, e_x0, e_y0; uint32_t outside; };
-
-__host__ __device__ static inline uint32_t hs_mcl_lookup(const hs_mcl_field &E, long long x, long long y)
-{
-    const long long ex = x - E.e_x0, ey = y - E.e_y0;
-    const bool in = ex >= 0 && ex < E.ew && ey >= 0 && ey < E.eh;
-    return in ? (uint32_t)E.f[(size_t)ey * (size_t)E.pitch + (size_t)ex] : E.outside;
-}
-
 // step 1: the three variates of particle i
 __host__ __device__ static inline void hs_mcl_noise(const hs_mcl_motion &m, int i, float z[3])
 {
@@ -75,12 +65,12 @@ __host__ __device__ static inline hs_mcl_pose hs_mcl_predict(const hs_mcl_motion
 }
 
 // step 3 for one scan point under t = hs_trace_transform(stm, x', y', theta'): F of its end cell; false: the point is ignored
-__host__ __device__ static inline bool hs_mcl_point(const hs_mcl_field &E, const sh_m3x2 &t, float px, float py, uint32_t *F)
+__host__ __device__ static inline bool hs_mcl_point(const hs_field &E, const sh_m3x2 &t, float px, float py, uint32_t *F)
 {
     float exf, eyf;
     sh_v2_transform(px, py, t, &exf, &eyf);
     if (!(hs_trace_counts(exf) && hs_trace_counts(eyf))) return false;
-    *F = hs_mcl_lookup(E, (long long)sh_f2i(rintf(exf)), (long long)sh_f2i(rintf(eyf)));   // ToRoundPoint (banker's), as k9_score
+    *F = hs_field_lookup(E, (long long)sh_f2i(rintf(exf)), (long long)sh_f2i(rintf(eyf)));   // ToRoundPoint (banker's), as k9_score
     return true;
 }
 

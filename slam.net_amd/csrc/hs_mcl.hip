@@ -4,7 +4,7 @@
 // include/slamhip.h (slamhip_hs_mcl_step); the arithmetic host and device share: hs_mcl.h.
 //
 // The field is K9's (hs_dfield.hip), built by the functions slamhip_hs_distance_score builds it with (hs_df_field_prepare,
-// hs_df_field_enqueue: hs_df_plan and hs_df_enqueue), on every step.  Behind it:
+// hs_df_field_enqueue), on every step.  Behind it:
 //  * k13_score: a workgroup of four wavefronts copies the scan into LDS once, then each wavefront takes one particle at a time --
 //    particle i = 4 * workgroup + wavefront, then on by 4 * workgroups.  Every lane forms the noise, the predicted pose and the
 //    transform of ITS wavefront's particle (the same bits in all 64 lanes: nothing is exchanged), the lanes stride the points and
@@ -19,10 +19,9 @@
 //  * k13_resample: a lane per new particle -- the decision again, the tooth of the comb, a binary search over C, the particle
 //    copied into the OTHER buffer; anc_k != anc_k-1 counted by ballots (lane 0 of a wavefront searches for tooth k - 1 itself).  A
 //    ticket taken per workgroup tells the last one to finish, which stores the summary to pinned memory.
-#include "hs_internal.h"
+#include "hs_blocks.h"
 #include "hs_mcl.h"
 #include <algorithm>
-#include <new>
 #include <stddef.h>
 #include <vector>
 
@@ -57,7 +56,7 @@ struct k13_score_arg {
     float *part; int N;                    // N x 3, predicted in place
     const k13_u64 *acc; k13_u64 *a;
     float stm; uint32_t r2;
-    hs_mcl_field E;
+    hs_field E;
     hs_mcl_motion mo;
     k13_u64 *ctr;
 };
@@ -229,63 +228,52 @@ __global__ void __launch_bounds__(K13_LANES) k13_resample(const k13_res_arg A)
 // ---- host side ---------------------------------------------------------------------------------------------------
 // What the filter needs beyond the field's blocks, made by the first slamhip_hs_mcl_set and kept, all sized for HS_MCL_MAX_N: the
 // two particle buffers used in turn, acc, a, w, C, the ancestors and the counters in device memory, a pinned block the set and the
-// get pass through, a pinned, device-visible record k13_resample stores the summary in, and the event the bounded wait polls.
+// get pass through, and a pinned, device-visible record k13_resample stores the summary in.
 struct hs_mcl {
     float *d_part[2]; int cur;
     k13_u64 *d_acc, *d_a, *d_C, *d_ctr;
     uint32_t *d_w; int32_t *d_anc;
     unsigned char *h_io;
     slamhip_mcl_summary *h_sum;
-    hipEvent_t ev;
     int N;                                 // 0: no set
 };
 #define HS_MCL_IO_BYTES ((size_t)HS_MCL_MAX_N * (3 * sizeof(float) + sizeof(k13_u64) + sizeof(int32_t)))
+
+// the blocks, their fixed sizes and kinds: fn(pointer, bytes, kind) for each, until one fails
+template <typename F>
+static int32_t hs_mcl_each_block(hs_mcl *m, F fn)
+{
+    const size_t n = HS_MCL_MAX_N;
+    SH_TRY(fn((void **)&m->d_part[0], n * 3 * sizeof(float), HS_MEM_DEVICE));
+    SH_TRY(fn((void **)&m->d_part[1], n * 3 * sizeof(float), HS_MEM_DEVICE));
+    SH_TRY(fn((void **)&m->d_acc, n * sizeof(k13_u64), HS_MEM_DEVICE));
+    SH_TRY(fn((void **)&m->d_a, n * sizeof(k13_u64), HS_MEM_DEVICE));
+    SH_TRY(fn((void **)&m->d_C, n * sizeof(k13_u64), HS_MEM_DEVICE));
+    SH_TRY(fn((void **)&m->d_ctr, K13_CTRS * sizeof(k13_u64), HS_MEM_DEVICE));
+    SH_TRY(fn((void **)&m->d_w, n * sizeof(uint32_t), HS_MEM_DEVICE));
+    SH_TRY(fn((void **)&m->d_anc, n * sizeof(int32_t), HS_MEM_DEVICE));
+    SH_TRY(fn((void **)&m->h_io, HS_MCL_IO_BYTES, HS_MEM_PINNED));
+    SH_TRY(fn((void **)&m->h_sum, sizeof(slamhip_mcl_summary), HS_MEM_PINNED_VISIBLE));
+    return SLAMHIP_OK;
+}
 
 void hs_mcl_free(slamhip_hs *hs)
 {
     hs_mcl *m = hs->mcl;
     if (!m) return;
-    (void)hipFree(m->d_part[0]); (void)hipFree(m->d_part[1]); (void)hipFree(m->d_acc); (void)hipFree(m->d_a); (void)hipFree(m->d_C);
-    (void)hipFree(m->d_ctr); (void)hipFree(m->d_w); (void)hipFree(m->d_anc);
-    if (m->h_io) (void)hipHostFree(m->h_io);
-    if (m->h_sum) (void)hipHostFree(m->h_sum);
-    if (m->ev) (void)hipEventDestroy(m->ev);
+    (void)hs_mcl_each_block(m, [](void **p, size_t, hs_mem kind) { hs_release(p, nullptr, kind); return (int32_t)SLAMHIP_OK; });
     delete m;
     hs->mcl = nullptr;
 }
 
-static int32_t hs_mcl_alloc(void **p, size_t bytes, int kind)              // kind 0: device, 1: pinned, 2: pinned and device-visible
-{
-    if (*p) return SLAMHIP_OK;
-    const hipError_t e = kind == 0 ? hipMalloc(p, bytes) : hipHostMalloc(p, bytes, kind == 2 ? (hipHostMallocMapped | hipHostMallocCoherent) : hipHostMallocDefault);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        SH_FAIL(SLAMHIP_ERR_NOMEM, "localisation: allocation of %zu bytes of %s memory failed", bytes, kind ? "pinned host" : "device");
-    }
-    return SLAMHIP_OK;
-}
-
 static int32_t hs_mcl_blocks(slamhip_hs *hs)
 {
-    if (!hs->mcl) {
-        hs->mcl = new (std::nothrow) hs_mcl();                            // (value-initialised: nothing allocated yet)
-        if (!hs->mcl) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-    }
-    hs_mcl *m = hs->mcl;
-    if (!m->ev) SH_HIP(hipEventCreateWithFlags(&m->ev, hipEventDisableTiming));
-    const size_t n = HS_MCL_MAX_N;
-    SH_TRY(hs_mcl_alloc((void **)&m->d_part[0], n * 3 * sizeof(float), 0));
-    SH_TRY(hs_mcl_alloc((void **)&m->d_part[1], n * 3 * sizeof(float), 0));
-    SH_TRY(hs_mcl_alloc((void **)&m->d_acc, n * sizeof(k13_u64), 0));
-    SH_TRY(hs_mcl_alloc((void **)&m->d_a, n * sizeof(k13_u64), 0));
-    SH_TRY(hs_mcl_alloc((void **)&m->d_C, n * sizeof(k13_u64), 0));
-    SH_TRY(hs_mcl_alloc((void **)&m->d_ctr, K13_CTRS * sizeof(k13_u64), 0));
-    SH_TRY(hs_mcl_alloc((void **)&m->d_w, n * sizeof(uint32_t), 0));
-    SH_TRY(hs_mcl_alloc((void **)&m->d_anc, n * sizeof(int32_t), 0));
-    SH_TRY(hs_mcl_alloc((void **)&m->h_io, HS_MCL_IO_BYTES, 1));
-    SH_TRY(hs_mcl_alloc((void **)&m->h_sum, sizeof(slamhip_mcl_summary), 2));
-    return SLAMHIP_OK;
+    SH_TRY(hs_unit(&hs->mcl));
+    // (allocated once: a block that is there has its size)
+    return hs_mcl_each_block(hs->mcl, [](void **p, size_t bytes, hs_mem kind) {
+        size_t cap = *p ? bytes : 0;
+        return hs_grow(p, &cap, bytes, kind, "localisation");
+    });
 }
 
 extern "C" int32_t slamhip_hs_mcl_set(slamhip_hs *hs, const float *poses, int32_t N)
@@ -295,9 +283,7 @@ extern "C" int32_t slamhip_hs_mcl_set(slamhip_hs *hs, const float *poses, int32_
     for (int i = 0; i < 3 * N; i++)
         if (!isfinite(poses[i])) SH_FAIL(SLAMHIP_ERR_INVALID, "localisation: particle %d, (%g, %g, %g), is not finite", i / 3, poses[i - i % 3],
                                          poses[i - i % 3 + 1], poses[i - i % 3 + 2]);
-    slamhip_ctx *ctx = hs->ctx;
-    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
-    SH_HIP(hipSetDevice(ctx->device));
+    SH_TRY(hs_call_begin(hs));
     SH_TRY(hs_mcl_blocks(hs));
     hs_mcl *m = hs->mcl;
     m->N = 0;                                                              // (no set until this one has landed)
@@ -306,13 +292,11 @@ extern "C" int32_t slamhip_hs_mcl_set(slamhip_hs *hs, const float *poses, int32_
     memcpy(m->h_io, poses, pose_bytes);
     int32_t *h_anc = (int32_t *)(m->h_io + pose_bytes);
     for (int i = 0; i < N; i++) h_anc[i] = i;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = hs->ctx->stream;
     SH_HIP(hipMemcpyAsync(m->d_part[m->cur], m->h_io, pose_bytes, hipMemcpyHostToDevice, st));
     SH_HIP(hipMemcpyAsync(m->d_anc, h_anc, anc_bytes, hipMemcpyHostToDevice, st));
     SH_HIP(hipMemsetAsync(m->d_acc, 0, sizeof(k13_u64) * (size_t)N, st));
-    SH_HIP(hipEventRecord(m->ev, st));
-    SH_TRY(sh_event_wait(ctx, m->ev));
-    hs->launch_done = hs->launch_count;                                    // (the stream has drained up to here)
+    SH_TRY(hs_call_finish(hs));
     m->N = N;
     return SLAMHIP_OK;
 }
@@ -323,18 +307,14 @@ extern "C" int32_t slamhip_hs_mcl_get(slamhip_hs *hs, float *poses, uint64_t *ac
     hs_mcl *m = hs->mcl;
     if (!m || m->N == 0) SH_FAIL(SLAMHIP_ERR_STATE, "localisation: no particle set (slamhip_hs_mcl_set first)");
     if (N != m->N) SH_FAIL(SLAMHIP_ERR_INVALID, "localisation: N = %d, but the set holds %d particles", N, m->N);
-    slamhip_ctx *ctx = hs->ctx;
-    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
-    SH_HIP(hipSetDevice(ctx->device));
+    SH_TRY(hs_call_begin(hs));
     const size_t pose_bytes = sizeof(float) * 3 * (size_t)N, acc_bytes = sizeof(k13_u64) * (size_t)N, anc_bytes = sizeof(int32_t) * (size_t)N;
     unsigned char *h_acc = m->h_io, *h_pose = h_acc + acc_bytes, *h_anc = h_pose + pose_bytes;   // (the 8-byte records first)
-    hipStream_t st = ctx->stream;
+    hipStream_t st = hs->ctx->stream;
     if (poses) SH_HIP(hipMemcpyAsync(h_pose, m->d_part[m->cur], pose_bytes, hipMemcpyDeviceToHost, st));
     if (acc) SH_HIP(hipMemcpyAsync(h_acc, m->d_acc, acc_bytes, hipMemcpyDeviceToHost, st));
     if (ancestors) SH_HIP(hipMemcpyAsync(h_anc, m->d_anc, anc_bytes, hipMemcpyDeviceToHost, st));
-    SH_HIP(hipEventRecord(m->ev, st));
-    SH_TRY(sh_event_wait(ctx, m->ev));
-    hs->launch_done = hs->launch_count;                                    // (the stream has drained up to here)
+    SH_TRY(hs_call_finish(hs));
     if (poses) memcpy(poses, h_pose, pose_bytes);
     if (acc) memcpy(acc, h_acc, acc_bytes);
     if (ancestors) memcpy(ancestors, h_anc, anc_bytes);
@@ -344,7 +324,7 @@ extern "C" int32_t slamhip_hs_mcl_get(slamhip_hs *hs, float *poses, uint64_t *ac
 // what every entry point refuses for the spec alone (N: the set's size)
 int32_t hs_mcl_check_spec(int n_levels, const slamhip_mcl_spec *spec, int N)
 {
-    SH_TRY(hs_df_check(n_levels, spec->level, spec->world, spec->site_mask, spec->radius));
+    SH_TRY(hs_df_check("distance field", n_levels, spec->level, spec->world, spec->site_mask, spec->radius));
     const float *f = spec->delta;                                          // delta, sigma, frame_offset: eight consecutive floats
     static_assert(offsetof(slamhip_mcl_spec, frame_offset) + 2 * sizeof(float) == offsetof(slamhip_mcl_spec, delta) + 8 * sizeof(float), "eight floats");
     for (int i = 0; i < 8; i++)
@@ -381,27 +361,24 @@ extern "C" int32_t slamhip_hs_mcl_step(slamhip_hs *hs, const slamhip_mcl_spec *s
 {
     SH_CHECK_ARG(hs && spec && out);
     SH_TRY(hs_mcl_check_step(hs, spec, hs->n_points, true));
-    slamhip_ctx *ctx = hs->ctx;
-    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
-    SH_HIP(hipSetDevice(ctx->device));
+    SH_TRY(hs_call_begin(hs));
     hs_mcl *m = hs->mcl;
     const int N = m->N, n = hs->n_points, r = spec->radius;
-    hs_class_map M; hs_field_view V;
-    SH_TRY(hs_df_field_prepare(hs, spec->level, spec->world != 0, spec->site_mask, r, &M, &V));
-    hipStream_t st = ctx->stream;
+    hs_class_map M; hs_field E;
+    SH_TRY(hs_df_field_prepare(hs, spec->level, spec->world != 0, spec->site_mask, r, &M, &E));
+    hipStream_t st = hs->ctx->stream;
     SH_TRY(hs_flush_scan(hs));
     // (the blocks are idle: every call waits for its own launches, and a call that timed out has poisoned the context)
     SH_HIP(hipMemsetAsync(m->d_ctr, 0xFF, sizeof(k13_u64) * 3, st));      // min a, key_best, cost_min: UINT64_MAX
     SH_HIP(hipMemsetAsync(m->d_ctr + 3, 0, sizeof(k13_u64) * (K13_CTRS - 3), st));
-    SH_TRY(hs_df_field_enqueue(hs, spec->level, spec->world != 0, &M, spec->site_mask, r));
+    SH_TRY(hs_df_field_enqueue(hs, spec->level, spec->world != 0, &M, &E, spec->site_mask));
     float *pred = m->d_part[m->cur], *next = m->d_part[m->cur ^ 1];
     k13_score_arg A;
     A.pts = hs->d_pts; A.n = n;
     A.part = pred; A.N = N;
     A.acc = m->d_acc; A.a = m->d_a;
     A.stm = hs->lv[spec->level].stm; A.r2 = (uint32_t)(r * r);
-    A.E.f = V.f; A.E.pitch = V.pitch; A.E.ew = M.w + 2 * r; A.E.eh = M.h + 2 * r;
-    A.E.e_x0 = M.x0 - r; A.E.e_y0 = M.y0 - r; A.E.outside = hs_df_outside(spec->site_mask, r);
+    A.E = E;
     A.mo = hs_mcl_motion_of(spec);
     A.ctr = m->d_ctr;
     const int score_blocks = std::min(sh_div_up(N, K13_LANES / 64), K13_SCORE_MAX_BLOCKS), blocks = sh_div_up(N, K13_LANES);
@@ -422,9 +399,7 @@ extern "C" int32_t slamhip_hs_mcl_step(slamhip_hs *hs, const slamhip_mcl_spec *s
     R.ctr = m->d_ctr; R.summary = m->h_sum;
     hipLaunchKernelGGL(k13_resample, dim3((unsigned)blocks), dim3(K13_LANES), 0, st, R);
     SH_HIP(hipGetLastError());
-    SH_HIP(hipEventRecord(m->ev, st));
-    SH_TRY(sh_event_wait(ctx, m->ev));
-    hs->launch_done = hs->launch_count;                                    // (the stream has drained up to here)
+    SH_TRY(hs_call_finish(hs));
     m->cur ^= 1;
     m->N = N;
     *out = *m->h_sum;
@@ -445,7 +420,7 @@ extern "C" int32_t slamhip_debug_mcl_step(const uint8_t *cls, int32_t cw, int32_
         if (!isfinite(particles_in[i])) SH_FAIL(SLAMHIP_ERR_INVALID, "localisation: particle %d is not finite", i / 3);
     SH_TRY(hs_mcl_check_spec(1, spec, N));                                 // (the hook has one level)
     const int r = spec->radius;
-    hs_mcl_field E;
+    hs_field E;
     E.ew = cw + 2 * r; E.eh = ch + 2 * r; E.pitch = E.ew; E.e_x0 = -r; E.e_y0 = -r; E.outside = hs_df_outside(spec->site_mask, r);
     std::vector<uint16_t> field((size_t)E.ew * (size_t)E.eh);
     SH_TRY(slamhip_debug_distance_field(cls, cw, ch, spec->site_mask, r, -r, -r, E.ew, E.eh, field.data()));

@@ -30,12 +30,11 @@
 //  * k11_paths: a lane per path follows the dir bytes, capped by n_traversable.
 //  * k11_gather: the caller's rectangle of costs and / or dirs, the outside values outside M.
 //  * k11_emit: the counters, the goal results and the path heads into pinned memory.
-#include "hs_internal.h"
+#include "hs_blocks.h"
 #include "hs_nav.h"
 #include "hs_nav_host.h"
 #include <algorithm>
 #include <functional>
-#include <new>
 #include <queue>
 #include <vector>
 
@@ -317,8 +316,7 @@ __global__ void __launch_bounds__(256) k11_emit(const uint32_t *__restrict__ ctr
 // ---- host side ---------------------------------------------------------------------------------------------------
 // What the field needs, made by the first call and kept: the traversable words, the cost and dir of every cell of M, the tiles'
 // flags, the counters, the sources, goals, goal results, path heads and path cells in device memory, the rectangle's device block,
-// a pinned, device-visible block for what the kernels store (k11_peek, k11_emit), a pinned block for what is copied, and the event
-// the bounded wait polls.
+// a pinned, device-visible block for what the kernels store (k11_peek, k11_emit), and a second one for what is copied.
 struct hs_nav {
     uint32_t *d_tw; size_t cap_tw;
     uint32_t *d_cost; size_t cap_cost;
@@ -332,7 +330,6 @@ struct hs_nav {
     unsigned char *d_rect; size_t cap_rect;   // the rectangle's costs, then its dirs
     uint32_t *h_head; size_t cap_head;     // device-visible: the peek block, then k11_emit's
     unsigned char *h_io; size_t cap_io;    // sources and goals going in; path cells and the rectangle coming out
-    hipEvent_t ev;
 };
 #define HS_NAV_PEEK_WORDS (K11_MAX_BATCH + K11_CTRS)
 #define HS_NAV_HEAD_BYTES (sizeof(uint32_t) * (HS_NAV_PEEK_WORDS + K11_CTRS + 4 * (size_t)HS_NAV_MAX_GOALS + 2 * (size_t)HS_NAV_MAX_PATHS))
@@ -341,26 +338,20 @@ void hs_nav_free(slamhip_hs *hs)
 {
     hs_nav *nv = hs->nav;
     if (!nv) return;
-    (void)hipFree(nv->d_tw); (void)hipFree(nv->d_cost); (void)hipFree(nv->d_dir); (void)hipFree(nv->d_act); (void)hipFree(nv->d_ctr);
-    (void)hipFree(nv->d_batch); (void)hipFree(nv->d_in); (void)hipFree(nv->d_res); (void)hipFree(nv->d_pcells); (void)hipFree(nv->d_rect);
-    if (nv->h_head) (void)hipHostFree(nv->h_head);
-    if (nv->h_io) (void)hipHostFree(nv->h_io);
-    if (nv->ev) (void)hipEventDestroy(nv->ev);
+    hs_release((void **)&nv->d_tw, &nv->cap_tw, HS_MEM_DEVICE);
+    hs_release((void **)&nv->d_cost, &nv->cap_cost, HS_MEM_DEVICE);
+    hs_release((void **)&nv->d_dir, &nv->cap_dir, HS_MEM_DEVICE);
+    hs_release((void **)&nv->d_act, &nv->cap_act, HS_MEM_DEVICE);
+    hs_release((void **)&nv->d_ctr, &nv->cap_ctr, HS_MEM_DEVICE);
+    hs_release((void **)&nv->d_batch, &nv->cap_batch, HS_MEM_DEVICE);
+    hs_release((void **)&nv->d_in, &nv->cap_in, HS_MEM_DEVICE);
+    hs_release((void **)&nv->d_res, &nv->cap_res, HS_MEM_DEVICE);
+    hs_release((void **)&nv->d_pcells, &nv->cap_pcells, HS_MEM_DEVICE);
+    hs_release((void **)&nv->d_rect, &nv->cap_rect, HS_MEM_DEVICE);
+    hs_release((void **)&nv->h_head, &nv->cap_head, HS_MEM_PINNED_VISIBLE);
+    hs_release((void **)&nv->h_io, &nv->cap_io, HS_MEM_PINNED_VISIBLE);
     delete nv;
     hs->nav = nullptr;
-}
-
-static int32_t hs_nav_grow(void **p, size_t *cap, size_t want, bool pinned)
-{
-    if (*cap >= want) return SLAMHIP_OK;
-    if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    if ((pinned ? hipHostMalloc(p, want, hipHostMallocMapped | hipHostMallocCoherent) : hipMalloc(p, want)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        SH_FAIL(SLAMHIP_ERR_NOMEM, "navigation field: allocation of %zu bytes of %s memory failed", want, pinned ? "pinned host" : "device");
-    }
-    *cap = want;
-    return SLAMHIP_OK;
 }
 
 // what both entry points refuse for their arguments alone
@@ -416,42 +407,36 @@ static int32_t hs_nav_build(slamhip_hs *hs, const slamhip_nav_spec *spec, const 
     const int level = spec->level, c = spec->clearance;
     const bool world = spec->world != 0;
     slamhip_ctx *ctx = hs->ctx;
-    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
-    SH_HIP(hipSetDevice(ctx->device));
+    SH_TRY(hs_call_begin(hs));
     hs_class_map M;
-    hs_field_view V = { nullptr, 0, 0 };
-    if (c >= 1) SH_TRY(hs_df_field_prepare(hs, level, world, spec->site_mask, c + 1, &M, &V));
+    hs_field E = { nullptr, 0, 0, 0, 0, 0, 0u };                           // (no clearance: no field)
+    if (c >= 1) SH_TRY(hs_df_field_prepare(hs, level, world, spec->site_mask, c + 1, &M, &E));
     else SH_TRY(hs_lat_pack_prepare(hs, level, world, &M));
     const int64_t cells = (int64_t)M.w * M.h;
     if (cells > HS_NAV_MAX_M) SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: M, the class map of level %d, is %d x %d cells, more than 2^25", level, M.w, M.h);
-    if (!hs->nav) {
-        hs->nav = new (std::nothrow) hs_nav();                            // (value-initialised: nothing allocated yet)
-        if (!hs->nav) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-    }
+    SH_TRY(hs_unit(&hs->nav));
     hs_nav *nv = hs->nav;
-    if (!nv->ev) SH_HIP(hipEventCreateWithFlags(&nv->ev, hipEventDisableTiming));
     k11_geo A;
     A.cls = M.cls; A.w = M.w; A.h = M.h; A.wpr = M.wpr;
-    A.f = V.f; A.fpitch = V.pitch; A.fr = V.r; A.c2 = (uint32_t)(c * c);
+    A.f = E.f; A.fpitch = E.pitch; A.fr = c >= 1 ? c + 1 : 0; A.c2 = (uint32_t)(c * c);
     A.twpr = (M.w + 31) / 32;
     A.tiles_x = sh_div_up(M.w, K11_TILE); A.tiles_y = sh_div_up(M.h, K11_TILE);
     A.max_cost = spec->max_cost; A.x0 = M.x0; A.y0 = M.y0;
     const int nt = A.tiles_x * A.tiles_y;
     const size_t src_bytes = sizeof(int) * 2 * (size_t)S, goal_bytes = sizeof(int) * 4 * (size_t)G;
     const size_t act_bytes = ((size_t)2 * nt + 15) & ~(size_t)15;
-    // (the blocks are idle: every call waits for its own launches, and a call that timed out has poisoned the context)
-    SH_TRY(hs_nav_grow((void **)&nv->d_tw, &nv->cap_tw, sizeof(uint32_t) * (size_t)A.twpr * M.h, false));
-    SH_TRY(hs_nav_grow((void **)&nv->d_cost, &nv->cap_cost, sizeof(uint32_t) * (size_t)cells, false));
-    SH_TRY(hs_nav_grow((void **)&nv->d_dir, &nv->cap_dir, (size_t)cells, false));
-    SH_TRY(hs_nav_grow((void **)&nv->d_act, &nv->cap_act, act_bytes, false));
-    SH_TRY(hs_nav_grow((void **)&nv->d_ctr, &nv->cap_ctr, sizeof(uint32_t) * K11_CTRS, false));
-    SH_TRY(hs_nav_grow((void **)&nv->d_batch, &nv->cap_batch, sizeof(uint32_t) * K11_MAX_BATCH, false));
-    SH_TRY(hs_nav_grow((void **)&nv->d_in, &nv->cap_in, src_bytes + goal_bytes, false));
-    SH_TRY(hs_nav_grow((void **)&nv->d_res, &nv->cap_res, sizeof(slamhip_nav_goal_result) * (size_t)HS_NAV_MAX_GOALS + sizeof(slamhip_nav_path) * HS_NAV_MAX_PATHS, false));
-    if (pc_bytes) SH_TRY(hs_nav_grow((void **)&nv->d_pcells, &nv->cap_pcells, pc_bytes, false));
-    if (rc_bytes + rd_bytes) SH_TRY(hs_nav_grow((void **)&nv->d_rect, &nv->cap_rect, rc_bytes + rd_bytes, false));
-    SH_TRY(hs_nav_grow((void **)&nv->h_head, &nv->cap_head, HS_NAV_HEAD_BYTES, true));
-    SH_TRY(hs_nav_grow((void **)&nv->h_io, &nv->cap_io, std::max(src_bytes + goal_bytes, pc_bytes + rc_bytes + rd_bytes), true));
+    SH_TRY(hs_grow((void **)&nv->d_tw, &nv->cap_tw, sizeof(uint32_t) * (size_t)A.twpr * M.h, HS_MEM_DEVICE, "navigation field"));
+    SH_TRY(hs_grow((void **)&nv->d_cost, &nv->cap_cost, sizeof(uint32_t) * (size_t)cells, HS_MEM_DEVICE, "navigation field"));
+    SH_TRY(hs_grow((void **)&nv->d_dir, &nv->cap_dir, (size_t)cells, HS_MEM_DEVICE, "navigation field"));
+    SH_TRY(hs_grow((void **)&nv->d_act, &nv->cap_act, act_bytes, HS_MEM_DEVICE, "navigation field"));
+    SH_TRY(hs_grow((void **)&nv->d_ctr, &nv->cap_ctr, sizeof(uint32_t) * K11_CTRS, HS_MEM_DEVICE, "navigation field"));
+    SH_TRY(hs_grow((void **)&nv->d_batch, &nv->cap_batch, sizeof(uint32_t) * K11_MAX_BATCH, HS_MEM_DEVICE, "navigation field"));
+    SH_TRY(hs_grow((void **)&nv->d_in, &nv->cap_in, src_bytes + goal_bytes, HS_MEM_DEVICE, "navigation field"));
+    SH_TRY(hs_grow((void **)&nv->d_res, &nv->cap_res, sizeof(slamhip_nav_goal_result) * (size_t)HS_NAV_MAX_GOALS + sizeof(slamhip_nav_path) * HS_NAV_MAX_PATHS, HS_MEM_DEVICE, "navigation field"));
+    if (pc_bytes) SH_TRY(hs_grow((void **)&nv->d_pcells, &nv->cap_pcells, pc_bytes, HS_MEM_DEVICE, "navigation field"));
+    if (rc_bytes + rd_bytes) SH_TRY(hs_grow((void **)&nv->d_rect, &nv->cap_rect, rc_bytes + rd_bytes, HS_MEM_DEVICE, "navigation field"));
+    SH_TRY(hs_grow((void **)&nv->h_head, &nv->cap_head, HS_NAV_HEAD_BYTES, HS_MEM_PINNED_VISIBLE, "navigation field"));
+    SH_TRY(hs_grow((void **)&nv->h_io, &nv->cap_io, std::max(src_bytes + goal_bytes, pc_bytes + rc_bytes + rd_bytes), HS_MEM_PINNED_VISIBLE, "navigation field"));
     A.tw = nv->d_tw; A.cost = nv->d_cost; A.dir = nv->d_dir; A.act = nv->d_act; A.ctr = nv->d_ctr;
     int *d_src = nv->d_in;
     const int batch = (int)std::min<long long>(std::max<long long>(sh_env_int("SLAMHIP_NAV_BATCH", K11_BATCH), 1), K11_MAX_BATCH);
@@ -462,7 +447,7 @@ static int32_t hs_nav_build(slamhip_hs *hs, const slamhip_nav_spec *spec, const 
     SH_HIP(hipMemsetAsync(nv->d_ctr, 0, sizeof(uint32_t) * K11_CTRS, st));
     SH_HIP(hipMemsetAsync(nv->d_act, 0, act_bytes, st));
     SH_HIP(hipMemsetAsync(nv->d_cost, 0xFF, sizeof(uint32_t) * (size_t)cells, st));
-    if (c >= 1) SH_TRY(hs_df_field_enqueue(hs, level, world, &M, spec->site_mask, c + 1));
+    if (c >= 1) SH_TRY(hs_df_field_enqueue(hs, level, world, &M, &E, spec->site_mask));
     else SH_TRY(hs_lat_pack_enqueue(hs, level, world, &M));
     // (at most 2^25 cells in M: no grid reaches 2^31 workgroups)
     hipLaunchKernelGGL(k11_trav, dim3((unsigned)sh_div_up(A.twpr * M.h, 256)), dim3(256), 0, st, A);
@@ -479,9 +464,7 @@ static int32_t hs_nav_build(slamhip_hs *hs, const slamhip_nav_spec *spec, const 
         }
         hipLaunchKernelGGL(k11_peek, dim3(1), dim3(128), 0, st, (const uint32_t *)nv->d_batch, (const uint32_t *)nv->d_ctr, nv->h_head);
         SH_HIP(hipGetLastError());
-        SH_HIP(hipEventRecord(nv->ev, st));
-        SH_TRY(sh_event_wait(ctx, nv->ev));
-        hs->launch_done = hs->launch_count;                                // (the stream has drained up to here)
+        SH_TRY(hs_call_finish(hs));
         if (peek[K11_MAX_BATCH + K11_C_FLAG]) SH_FAIL(SLAMHIP_ERR_STATE, "navigation field did not converge: a tile's relaxation overran (level %d, M of %d x %d cells)", level, M.w, M.h);
         int j = 0;
         while (j < batch && peek[j]) j++;
@@ -553,9 +536,7 @@ extern "C" int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *
     hipLaunchKernelGGL(k11_emit, dim3((unsigned)sh_div_up(K11_CTRS + 4 * G + 2 * n_paths, 256)), dim3(256), 0, st, (const uint32_t *)nv->d_ctr,
                        (const uint32_t *)d_res, 4 * G, (const uint32_t *)d_heads, 2 * n_paths, nv->h_head + HS_NAV_PEEK_WORDS);
     SH_HIP(hipGetLastError());
-    SH_HIP(hipEventRecord(nv->ev, st));
-    SH_TRY(sh_event_wait(ctx, nv->ev));
-    hs->launch_done = hs->launch_count;                                    // (the stream has drained up to here)
+    SH_TRY(hs_call_finish(hs));
     if (head[K11_C_FLAG]) SH_FAIL(SLAMHIP_ERR_STATE, "navigation field did not converge: the costs are no fixed point (level %d, M of %d x %d cells)", level, M.w, M.h);
     hs_nav_summary_of(head, M.x0, M.y0, M.w, M.h, rounds, out_summary);
     if (G) memcpy(out_goal_results, head + K11_CTRS, sizeof(slamhip_nav_goal_result) * (size_t)G);

@@ -2,6 +2,7 @@
 #include "hs_internal.h"
 #include <algorithm>
 #include <chrono>
+#include <stddef.h>
 #include <vector>
 
 // ---- HectorSLAMProcessor (Main/HectorSLAMProcessor.cs) ---------------------------------------------------------------
@@ -59,6 +60,39 @@ static inline void hsproc_window_offset(const slamhip_hsproc *p, float off[2])
 {
     off[0] = (float)p->hs->win_ox * p->hs->lv[0].cell;
     off[1] = (float)p->hs->win_oy * p->hs->lv[0].cell;
+}
+
+// The two frames.  Poses and cells cross the C-ABI in the world's frame; the hs works in the window's.  While the window has never
+// moved the two are one and every bit passes through, -0.0f included; after that a position costs one rounded subtraction on the
+// way in and one rounded addition on the way out, per axis.  The heading is the same in both.
+static inline bool hsproc_moved(const slamhip_hsproc *p) { return p->hs->win_ox != 0 || p->hs->win_oy != 0; }
+static inline void hsproc_pose_to_window(const slamhip_hsproc *p, const float world[3], float out[3])
+{
+    float off[2];
+    hsproc_window_offset(p, off);
+    if (hsproc_moved(p)) { out[0] = world[0] - off[0]; out[1] = world[1] - off[1]; out[2] = world[2]; }
+    else memmove(out, world, sizeof(float) * 3);
+}
+static inline void hsproc_pose_to_world(const slamhip_hsproc *p, const float window[3], float out[3])
+{
+    float off[2];
+    hsproc_window_offset(p, off);
+    if (hsproc_moved(p)) { out[0] = window[0] + off[0]; out[1] = window[1] + off[1]; out[2] = window[2]; }
+    else memmove(out, window, sizeof(float) * 3);
+}
+// B poses: the caller's own array while the window has never moved, else `buf`
+static const float *hsproc_poses_to_window(const slamhip_hsproc *p, const float *world, int32_t B, std::vector<float> &buf)
+{
+    if (!hsproc_moved(p)) return world;
+    buf.resize(3 * (size_t)B);
+    for (int i = 0; i < B; i++) hsproc_pose_to_window(p, world + 3 * i, buf.data() + 3 * i);
+    return buf.data();
+}
+// a cell coordinate of one level, o = origin >> level on its axis: clamped where it lies too far out to be a cell of M wherever M is
+static inline int32_t hsproc_cell_to_window(int64_t v, int64_t o)
+{
+    const int64_t far = (int64_t)1 << 30;
+    return (int32_t)std::min(std::max(v - o, -far), far);
 }
 
 // HectorSLAMProcessor.Update (:83-125) in the window's frame: hint, match_pose and last_update_pose all are window-frame poses
@@ -222,18 +256,15 @@ extern "C" int32_t slamhip_hsproc_relocalise(slamhip_hsproc *p, const float *xy,
 {
     SH_CHECK_ARG(p && spec_world && out_pose_world && out_report && out_info && (adopt == 0 || adopt == 1));
     SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
-    const bool moved = p->hs->win_ox != 0 || p->hs->win_oy != 0;
-    float off[2];
-    hsproc_window_offset(p, off);
     slamhip_lattice_spec S = *spec_world;
-    if (moved) { S.centre[0] = S.centre[0] - off[0]; S.centre[1] = S.centre[1] - off[1]; }
+    hsproc_pose_to_window(p, spec_world->centre, S.centre);
     float m[3];
     SH_TRY(slamhip_hs_relocalise(p->hs, &S, B, m, out_report, out_info));
     if (adopt) {
         memcpy(p->match_pose, m, sizeof(m));
         memcpy(p->last_update_pose, m, sizeof(m));
     }
-    out_pose_world[0] = moved ? m[0] + off[0] : m[0]; out_pose_world[1] = moved ? m[1] + off[1] : m[1]; out_pose_world[2] = m[2];
+    hsproc_pose_to_world(p, m, out_pose_world);
     return SLAMHIP_OK;
 }
 
@@ -244,10 +275,8 @@ extern "C" int32_t slamhip_hsproc_relocalise_world(slamhip_hsproc *p, const floa
 {
     SH_CHECK_ARG(p && spec_world && out_pose_world && out_report && out_info && (adopt == 0 || adopt == 1));
     SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
-    float off[2];
-    hsproc_window_offset(p, off);
     slamhip_lattice_spec S = *spec_world;
-    if (p->hs->win_ox != 0 || p->hs->win_oy != 0) { S.centre[0] = S.centre[0] - off[0]; S.centre[1] = S.centre[1] - off[1]; }
+    hsproc_pose_to_window(p, spec_world->centre, S.centre);
     float m[3];
     memset(out_info, 0, sizeof(*out_info));
     const int32_t rc = slamhip_hs_relocalise_world(p->hs, &S, B, m, out_report, out_info);
@@ -257,9 +286,7 @@ extern "C" int32_t slamhip_hsproc_relocalise_world(slamhip_hsproc *p, const floa
         memcpy(p->match_pose, m, sizeof(m));
         memcpy(p->last_update_pose, m, sizeof(m));
     }
-    const bool moved = p->hs->win_ox != 0 || p->hs->win_oy != 0;
-    hsproc_window_offset(p, off);
-    out_pose_world[0] = moved ? m[0] + off[0] : m[0]; out_pose_world[1] = moved ? m[1] + off[1] : m[1]; out_pose_world[2] = m[2];
+    hsproc_pose_to_world(p, m, out_pose_world);                            // (the window's new frame)
     return SLAMHIP_OK;
 }
 
@@ -270,21 +297,10 @@ extern "C" int32_t slamhip_hsproc_trace(slamhip_hsproc *p, const float *xy, int3
 {
     SH_CHECK_ARG(p && poses_world && out_summaries);
     // (what slamhip_hs_trace refuses for its arguments alone, ahead of the scan: a refused call leaves the scan that was set)
-    if (level < 0 || level >= p->hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: level %d of %d", level, p->hs->n_levels);
-    if (B < 1 || B > 65536) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: B = %d must lie in [1, 65536]", B);
-    if (world != 0 && world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: world = %d must be 0 (the window) or 1 (the world)", world);
-    if (out_beams && n > 0 && (int64_t)B * n > ((int64_t)1 << 20))
-        SH_FAIL(SLAMHIP_ERR_INVALID, "trace: per-beam records of %d poses x %d points, more than 2^20", B, n);
+    SH_TRY(hs_trc_check(p->hs->n_levels, level, B, world, out_beams != nullptr, n, false));
     SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
-    if (p->hs->win_ox == 0 && p->hs->win_oy == 0) return slamhip_hs_trace(p->hs, level, poses_world, B, world, out_summaries, out_beams);
-    float off[2];
-    hsproc_window_offset(p, off);
-    float *w = (float *)malloc(sizeof(float) * 3 * (size_t)B);
-    if (!w) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-    for (int i = 0; i < B; i++) { w[3 * i] = poses_world[3 * i] - off[0]; w[3 * i + 1] = poses_world[3 * i + 1] - off[1]; w[3 * i + 2] = poses_world[3 * i + 2]; }
-    const int32_t rc = slamhip_hs_trace(p->hs, level, w, B, world, out_summaries, out_beams);
-    free(w);
-    return rc;
+    std::vector<float> buf;
+    return slamhip_hs_trace(p->hs, level, hsproc_poses_to_window(p, poses_world, B, buf), B, world, out_summaries, out_beams);
 }
 
 // The end-point distance score at world poses: slamhip_hsproc_trace's shape -- the arguments checked ahead of the scan, the scan
@@ -295,24 +311,10 @@ extern "C" int32_t slamhip_hsproc_distance_score(slamhip_hsproc *p, const float 
 {
     SH_CHECK_ARG(p && poses_world && out_summaries);
     // (what slamhip_hs_distance_score refuses for its arguments alone, ahead of the scan: a refused call leaves the scan that was set)
-    if (level < 0 || level >= p->hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: level %d of %d", level, p->hs->n_levels);
-    if (world != 0 && world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: world = %d must be 0 (the window) or 1 (the world)", world);
-    if (site_mask < 1 || site_mask > 7) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: site_mask = %d must lie in [1, 7]", site_mask);
-    if (radius < 1 || radius > 255) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: radius = %d must lie in [1, 255]", radius);
-    if (B < 1 || B > 65536) SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: B = %d must lie in [1, 65536]", B);
-    if (out_points && n > 0 && (int64_t)B * n > ((int64_t)1 << 22))
-        SH_FAIL(SLAMHIP_ERR_INVALID, "distance score: per-point records of %d poses x %d points, more than 2^22", B, n);
+    SH_TRY(hs_df_check_score("distance score", p->hs->n_levels, level, world, site_mask, radius, B, out_points != nullptr, n, false));
     SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
-    if (p->hs->win_ox == 0 && p->hs->win_oy == 0)
-        return slamhip_hs_distance_score(p->hs, level, world, site_mask, radius, poses_world, B, out_summaries, out_points);
-    float off[2];
-    hsproc_window_offset(p, off);
-    float *w = (float *)malloc(sizeof(float) * 3 * (size_t)B);
-    if (!w) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-    for (int i = 0; i < B; i++) { w[3 * i] = poses_world[3 * i] - off[0]; w[3 * i + 1] = poses_world[3 * i + 1] - off[1]; w[3 * i + 2] = poses_world[3 * i + 2]; }
-    const int32_t rc = slamhip_hs_distance_score(p->hs, level, world, site_mask, radius, w, B, out_summaries, out_points);
-    free(w);
-    return rc;
+    std::vector<float> buf;
+    return slamhip_hs_distance_score(p->hs, level, world, site_mask, radius, hsproc_poses_to_window(p, poses_world, B, buf), B, out_summaries, out_points);
 }
 
 // The frontier clusters in WORLD cells of the level: slamhip_hs_frontiers, the label rectangle taken to the window's frame and every
@@ -324,11 +326,10 @@ extern "C" int32_t slamhip_hsproc_frontiers(slamhip_hsproc *p, int32_t level, in
     SH_CHECK_ARG(p && out_summary);
     if (level < 0 || level >= p->hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "frontiers: level %d of %d", level, p->hs->n_levels);
     const int64_t ox = p->hs->win_ox >> level, oy = p->hs->win_oy >> level;
-    const int64_t far = (int64_t)1 << 30;                                  // (a rectangle that far from the window lies outside M wherever M is)
-    const int64_t wx = std::min(std::max((int64_t)lx - ox, -far), far), wy = std::min(std::max((int64_t)ly - oy, -far), far);
     slamhip_frontier_summary S;
     memset(&S, 0, sizeof(S));
-    const int32_t rc = slamhip_hs_frontiers(p->hs, level, world, min_cells, max_clusters, &S, out_clusters, (int32_t)wx, (int32_t)wy, lw, lh, out_labels);
+    const int32_t rc = slamhip_hs_frontiers(p->hs, level, world, min_cells, max_clusters, &S, out_clusters, hsproc_cell_to_window(lx, ox),
+                                            hsproc_cell_to_window(ly, oy), lw, lh, out_labels);
     if (S.mw > 0) { S.mx0 += (int32_t)ox; S.my0 += (int32_t)oy; *out_summary = S; }   // (filled also when too many clusters are kept; a refused call writes nothing)
     SH_TRY(rc);
     for (int i = 0; i < S.n_returned; i++) {
@@ -352,19 +353,17 @@ extern "C" int32_t slamhip_hsproc_nav_field(slamhip_hsproc *p, const slamhip_nav
     if (ox == 0 && oy == 0)
         return slamhip_hs_nav_field(p->hs, spec, sources, S, goals, G, out_goal_results, n_paths, max_path_cells, out_paths, out_path_cells, rx, ry, rw,
                                     rh, out_cost, out_dir, out_summary);
-    const int64_t far = (int64_t)1 << 30;                                  // (a cell that far from the window lies outside M wherever M is)
-    auto to_window = [far](int64_t v, int64_t o) { return (int32_t)std::min(std::max(v - o, -far), far); };
     // (the counts are checked by slamhip_hs_nav_field; here they only bound the copies)
     const size_t ns = (sources && S >= 1 && S <= 4096) ? (size_t)S : 0, ng = (goals && G >= 1 && G <= 4096) ? (size_t)G : 0;
     std::vector<int32_t> w(2 * ns + 4 * ng);
-    for (size_t i = 0; i < ns; i++) { w[2 * i] = to_window(sources[2 * i], ox); w[2 * i + 1] = to_window(sources[2 * i + 1], oy); }
+    for (size_t i = 0; i < ns; i++) { w[2 * i] = hsproc_cell_to_window(sources[2 * i], ox); w[2 * i + 1] = hsproc_cell_to_window(sources[2 * i + 1], oy); }
     int32_t *wg = w.data() + 2 * ns;
-    for (size_t i = 0; i < 4 * ng; i++) wg[i] = to_window(goals[i], (i & 1) ? oy : ox);   // (monotonic: an inverted rectangle stays inverted or becomes empty outside M)
+    for (size_t i = 0; i < 4 * ng; i++) wg[i] = hsproc_cell_to_window(goals[i], (i & 1) ? oy : ox);   // (monotonic: an inverted rectangle stays inverted or becomes empty outside M)
     for (size_t i = 0; i < ng; i++)
         if (goals[4 * i] > goals[4 * i + 2] || goals[4 * i + 1] > goals[4 * i + 3]) { wg[4 * i] = 1; wg[4 * i + 2] = 0; }   // (refused below, as given)
     slamhip_nav_summary Sm;
     SH_TRY(slamhip_hs_nav_field(p->hs, spec, ns ? w.data() : sources, S, ng ? wg : goals, G, out_goal_results, n_paths, max_path_cells, out_paths,
-                                out_path_cells, to_window(rx, ox), to_window(ry, oy), rw, rh, out_cost, out_dir, &Sm));
+                                out_path_cells, hsproc_cell_to_window(rx, ox), hsproc_cell_to_window(ry, oy), rw, rh, out_cost, out_dir, &Sm));
     Sm.mx0 += (int32_t)ox; Sm.my0 += (int32_t)oy;
     *out_summary = Sm;
     for (int i = 0; i < G; i++)
@@ -386,25 +385,20 @@ extern "C" int32_t slamhip_hsproc_rollouts(slamhip_hsproc *p, const slamhip_nav_
 {
     SH_CHECK_ARG(p && spec && out_summary);
     if (spec->level < 0 || spec->level >= p->hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: level %d of %d", spec->level, p->hs->n_levels);
-    const bool moved = p->hs->win_ox != 0 || p->hs->win_oy != 0;
     const int64_t ox = p->hs->win_ox >> spec->level, oy = p->hs->win_oy >> spec->level;
-    float off[2];
-    hsproc_window_offset(p, off);
     float start[3];
     if (!start_pose_world) memcpy(start, p->match_pose, sizeof(start));
-    else if (moved) { start[0] = start_pose_world[0] - off[0]; start[1] = start_pose_world[1] - off[1]; start[2] = start_pose_world[2]; }
-    else memcpy(start, start_pose_world, sizeof(start));
-    if (!moved) return slamhip_hs_rollouts(p->hs, spec, sources, S, start, dt, body, P, cmds, B, n_cmd, hold, out_results, out_summary);
-    const int64_t far = (int64_t)1 << 30;                                  // (a cell that far from the window lies outside M wherever M is)
-    auto to_window = [far](int64_t v, int64_t o) { return (int32_t)std::min(std::max(v - o, -far), far); };
+    else hsproc_pose_to_window(p, start_pose_world, start);
+    if (!hsproc_moved(p)) return slamhip_hs_rollouts(p->hs, spec, sources, S, start, dt, body, P, cmds, B, n_cmd, hold, out_results, out_summary);
     const size_t ns = (sources && S >= 1 && S <= 4096) ? (size_t)S : 0;    // (the count is checked by slamhip_hs_rollouts; here it only bounds the copy)
     std::vector<int32_t> w(2 * ns);
-    for (size_t i = 0; i < ns; i++) { w[2 * i] = to_window(sources[2 * i], ox); w[2 * i + 1] = to_window(sources[2 * i + 1], oy); }
+    for (size_t i = 0; i < ns; i++) { w[2 * i] = hsproc_cell_to_window(sources[2 * i], ox); w[2 * i + 1] = hsproc_cell_to_window(sources[2 * i + 1], oy); }
     slamhip_rollout_summary Sm;
     SH_TRY(slamhip_hs_rollouts(p->hs, spec, ns ? w.data() : sources, S, start, dt, body, P, cmds, B, n_cmd, hold, out_results, &Sm));
     Sm.nav.mx0 += (int32_t)ox; Sm.nav.my0 += (int32_t)oy;
     *out_summary = Sm;
-    for (int i = 0; i < B; i++) { out_results[i].x = out_results[i].x + off[0]; out_results[i].y = out_results[i].y + off[1]; }
+    static_assert(offsetof(slamhip_rollout_result, theta) == offsetof(slamhip_rollout_result, x) + 2 * sizeof(float), "x, y, theta: a pose");
+    for (int i = 0; i < B; i++) hsproc_pose_to_world(p, &out_results[i].x, &out_results[i].x);
     return SLAMHIP_OK;
 }
 
@@ -423,15 +417,8 @@ extern "C" int32_t slamhip_hsproc_mcl_step(slamhip_hsproc *p, const float *xy, i
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)
 {
     SH_CHECK_ARG(p);
-    float off[2];
-    hsproc_window_offset(p, off);
-    if (p->hs->win_ox == 0 && p->hs->win_oy == 0) {                        // (never shifted: the stored bits themselves, -0.0f included)
-        if (match_pose) memcpy(match_pose, p->match_pose, sizeof(float) * 3);
-        if (last) memcpy(last, p->last_update_pose, sizeof(float) * 3);
-        match_pose = last = nullptr;
-    }
-    if (match_pose) { match_pose[0] = p->match_pose[0] + off[0]; match_pose[1] = p->match_pose[1] + off[1]; match_pose[2] = p->match_pose[2]; }
-    if (last) { last[0] = p->last_update_pose[0] + off[0]; last[1] = p->last_update_pose[1] + off[1]; last[2] = p->last_update_pose[2]; }
+    if (match_pose) hsproc_pose_to_world(p, p->match_pose, match_pose);
+    if (last) hsproc_pose_to_world(p, p->last_update_pose, last);
     if (mt) *mt = p->match_timing;
     if (ut) *ut = p->update_timing;
     return SLAMHIP_OK;

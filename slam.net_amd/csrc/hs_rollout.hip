@@ -18,10 +18,9 @@
 //  * k12_emit, one workgroup: K11's counters, C at P_0's centre, n_complete and the keys into pinned memory.
 // Commands and body points go through the pinned block into device memory with one copy, as K8's poses do; the records come
 // back through the same block.
-#include "hs_internal.h"
+#include "hs_blocks.h"
 #include "hs_nav_host.h"
 #include "hs_rollout.h"
-#include <new>
 
 #define K12_LANES 256
 #define K12_SQ 256                         // the staged square's side in cells (the developer experiment k12_rollout<SG, true>): 256 rows of 8 words, 8 KB of LDS
@@ -153,13 +152,12 @@ __global__ void __launch_bounds__(64) k12_emit(const hs_ro_field F, const hs_ro_
 // ---- host side ---------------------------------------------------------------------------------------------------
 // What the rollouts need beyond the field's blocks, made by the first call and kept: the commands and body points in device
 // memory, the records, the keys and the count of complete rollouts, a pinned block the inputs leave and the records reach the
-// host through, a pinned, device-visible block for what k12_emit stores, and the event the bounded wait polls.
+// host through, and a pinned, device-visible block for what k12_emit stores.
 struct hs_rollout {
     float *d_in; size_t cap_in;            // the commands, then the body points
     unsigned char *d_out; size_t cap_out;  // key_end, key_min, n_complete (24 bytes with padding), then B records
     unsigned char *h_io; size_t cap_io;    // the records; behind them the inputs
     uint32_t *h_head; size_t cap_head;
-    hipEvent_t ev;
 };
 #define HS_RO_OUT_HEAD 32                  // bytes in front of the records in d_out
 
@@ -167,26 +165,12 @@ void hs_ro_free(slamhip_hs *hs)
 {
     hs_rollout *ro = hs->rol;
     if (!ro) return;
-    (void)hipFree(ro->d_in); (void)hipFree(ro->d_out);
-    if (ro->h_io) (void)hipHostFree(ro->h_io);
-    if (ro->h_head) (void)hipHostFree(ro->h_head);
-    if (ro->ev) (void)hipEventDestroy(ro->ev);
+    hs_release((void **)&ro->d_in, &ro->cap_in, HS_MEM_DEVICE);
+    hs_release((void **)&ro->d_out, &ro->cap_out, HS_MEM_DEVICE);
+    hs_release((void **)&ro->h_io, &ro->cap_io, HS_MEM_PINNED);
+    hs_release((void **)&ro->h_head, &ro->cap_head, HS_MEM_PINNED_VISIBLE);
     delete ro;
     hs->rol = nullptr;
-}
-
-static int32_t hs_ro_grow(void **p, size_t *cap, size_t want, int kind)     // kind 0: device, 1: pinned, 2: pinned and device-visible
-{
-    if (*cap >= want) return SLAMHIP_OK;
-    if (*p) { if (kind) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    const hipError_t e = kind == 0 ? hipMalloc(p, want) : hipHostMalloc(p, want, kind == 2 ? (hipHostMallocMapped | hipHostMallocCoherent) : hipHostMallocDefault);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        SH_FAIL(SLAMHIP_ERR_NOMEM, "rollouts: allocation of %zu bytes of %s memory failed", want, kind ? "pinned host" : "device");
-    }
-    *cap = want;
-    return SLAMHIP_OK;
 }
 
 // what both entry points refuse for the rollouts' own arguments
@@ -255,22 +239,16 @@ extern "C" int32_t slamhip_hs_rollouts(slamhip_hs *hs, const slamhip_nav_spec *s
     SH_TRY(hs_nav_check_field(hs->n_levels, spec, sources, S));
     SH_TRY(hs_ro_check(start_pose, dt, body, P, cmds, B, n_cmd, hold, out_results));
     slamhip_ctx *ctx = hs->ctx;
-    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
-    SH_HIP(hipSetDevice(ctx->device));
-    if (!hs->rol) {
-        hs->rol = new (std::nothrow) hs_rollout();                        // (value-initialised: nothing allocated yet)
-        if (!hs->rol) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-    }
+    SH_TRY(hs_call_begin(hs));
+    SH_TRY(hs_unit(&hs->rol));
     hs_rollout *ro = hs->rol;
-    if (!ro->ev) SH_HIP(hipEventCreateWithFlags(&ro->ev, hipEventDisableTiming));
     const size_t cmd_bytes = sizeof(float) * 2 * (size_t)B * (size_t)n_cmd, body_bytes = sizeof(float) * 2 * (size_t)P;
     const size_t in_bytes = cmd_bytes + body_bytes + 8;                    // (never empty, and the body block aligned)
     const size_t rec_bytes = sizeof(slamhip_rollout_result) * (size_t)B, rec_pad = (rec_bytes + 15) & ~(size_t)15;
-    // (the blocks are idle: every call waits for its own launches, and a call that timed out has poisoned the context)
-    SH_TRY(hs_ro_grow((void **)&ro->d_in, &ro->cap_in, in_bytes, 0));
-    SH_TRY(hs_ro_grow((void **)&ro->d_out, &ro->cap_out, HS_RO_OUT_HEAD + rec_bytes, 0));
-    SH_TRY(hs_ro_grow((void **)&ro->h_io, &ro->cap_io, rec_pad + in_bytes, 1));
-    SH_TRY(hs_ro_grow((void **)&ro->h_head, &ro->cap_head, sizeof(uint32_t) * K12_HEAD_WORDS, 2));
+    SH_TRY(hs_grow((void **)&ro->d_in, &ro->cap_in, in_bytes, HS_MEM_DEVICE, "rollouts"));
+    SH_TRY(hs_grow((void **)&ro->d_out, &ro->cap_out, HS_RO_OUT_HEAD + rec_bytes, HS_MEM_DEVICE, "rollouts"));
+    SH_TRY(hs_grow((void **)&ro->h_io, &ro->cap_io, rec_pad + in_bytes, HS_MEM_PINNED, "rollouts"));
+    SH_TRY(hs_grow((void **)&ro->h_head, &ro->cap_head, sizeof(uint32_t) * K12_HEAD_WORDS, HS_MEM_PINNED_VISIBLE, "rollouts"));
     hs_nav_view V;
     SH_TRY(hs_nav_field_for_rollouts(hs, spec, sources, S, &V));
     hipStream_t st = ctx->stream;
@@ -300,9 +278,7 @@ extern "C" int32_t slamhip_hs_rollouts(slamhip_hs *hs, const slamhip_nav_spec *s
                        (const uint32_t *)A.n_complete, ro->h_head);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(ro->h_io, ro->d_out + HS_RO_OUT_HEAD, rec_bytes, hipMemcpyDeviceToHost, st));
-    SH_HIP(hipEventRecord(ro->ev, st));
-    SH_TRY(sh_event_wait(ctx, ro->ev));
-    hs->launch_done = hs->launch_count;                                    // (the stream has drained up to here)
+    SH_TRY(hs_call_finish(hs));
     memcpy(out_results, ro->h_io, rec_bytes);
     hs_ro_summary_of(ro->h_head, V.M.x0, V.M.y0, V.M.w, V.M.h, V.rounds, out_summary);
     return SLAMHIP_OK;

@@ -19,10 +19,9 @@
 //    Lanes of a wavefront walk beams of unequal length: the wavefront runs as long as its longest beam that meets nothing.
 //  * The summary: ballots and one wave sum, the wavefronts' counts through LDS, then ONE set of agent-scope atomic adds per
 //    workgroup into the pose's record, which a memset zeroed in-stream ahead of the launch.
-#include "hs_internal.h"
+#include "hs_blocks.h"
 #include "hs_lattice.h"
 #include "hs_trace.h"
-#include <new>
 
 #define K8_LANES 256
 #define K8_AHEAD 8                         // steps of a walk whose look-ups are issued together
@@ -170,35 +169,32 @@ __global__ void __launch_bounds__(K8_LANES) k8_trace(const k8_arg A)
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 // What a trace needs, made by the first one and kept: the poses in device memory, the device block of summaries and beam records,
-// the pinned block the poses leave and the results reach the host through, and the event the bounded wait polls.
+// and the pinned block the poses leave and the results reach the host through.
 struct hs_trace {
     float *d_poses; size_t cap_poses;
     unsigned char *d_out; size_t cap_out;                                  // B summaries, then the beam records
     unsigned char *h_io; size_t cap_h;                                     // the results; behind them the poses
-    hipEvent_t ev;
 };
 
 void hs_trc_free(slamhip_hs *hs)
 {
     hs_trace *tr = hs->trc;
     if (!tr) return;
-    (void)hipFree(tr->d_poses); (void)hipFree(tr->d_out);
-    if (tr->h_io) (void)hipHostFree(tr->h_io);
-    if (tr->ev) (void)hipEventDestroy(tr->ev);
+    hs_release((void **)&tr->d_poses, &tr->cap_poses, HS_MEM_DEVICE);
+    hs_release((void **)&tr->d_out, &tr->cap_out, HS_MEM_DEVICE);
+    hs_release((void **)&tr->h_io, &tr->cap_h, HS_MEM_PINNED);
     delete tr;
     hs->trc = nullptr;
 }
 
-static int32_t hs_trc_grow(void **p, size_t *cap, size_t want, bool pinned)
+int32_t hs_trc_check(int n_levels, int32_t level, int32_t B, int32_t world, bool want_beams, int n_points, bool scan_is_set)
 {
-    if (*cap >= want) return SLAMHIP_OK;
-    if (*p) { if (pinned) (void)hipHostFree(*p); else (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    if ((pinned ? hipHostMalloc(p, want, hipHostMallocDefault) : hipMalloc(p, want)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        SH_FAIL(SLAMHIP_ERR_NOMEM, "trace: allocation of %zu bytes of %s memory failed", want, pinned ? "pinned host" : "device");
-    }
-    *cap = want;
+    if (level < 0 || level >= n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: level %d of %d", level, n_levels);
+    if (B < 1 || B > HS_TRACE_MAX_POSES) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: B = %d must lie in [1, %d]", B, HS_TRACE_MAX_POSES);
+    if (world != 0 && world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: world = %d must be 0 (the window) or 1 (the world)", world);
+    if (scan_is_set && n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "trace: no scan (slamhip_hs_set_scan first)");
+    if (want_beams && (int64_t)B * n_points > (int64_t)HS_TRACE_MAX_BEAMS)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "trace: per-beam records of %d poses x %d points, more than 2^20", B, n_points);
     return SLAMHIP_OK;
 }
 
@@ -206,33 +202,22 @@ extern "C" int32_t slamhip_hs_trace(slamhip_hs *hs, int32_t level, const float *
                                     slamhip_trace_summary *out_summaries, slamhip_trace_beam *out_beams)
 {
     SH_CHECK_ARG(hs && poses && out_summaries);
-    if (level < 0 || level >= hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: level %d of %d", level, hs->n_levels);
-    if (B < 1 || B > HS_TRACE_MAX_POSES) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: B = %d must lie in [1, %d]", B, HS_TRACE_MAX_POSES);
-    if (world != 0 && world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: world = %d must be 0 (the window) or 1 (the world)", world);
-    if (hs->n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "trace: no scan (slamhip_hs_set_scan first)");
+    SH_TRY(hs_trc_check(hs->n_levels, level, B, world, out_beams != nullptr, hs->n_points, true));
     const int n = hs->n_points;
-    if (out_beams && (int64_t)B * n > (int64_t)HS_TRACE_MAX_BEAMS)
-        SH_FAIL(SLAMHIP_ERR_INVALID, "trace: per-beam records of %d poses x %d points, more than 2^20", B, n);
     slamhip_ctx *ctx = hs->ctx;
-    if (ctx->poisoned) SH_FAIL(SLAMHIP_ERR_TIMEOUT, "the context was poisoned by a blocking wait that timed out; destroy it");
-    SH_HIP(hipSetDevice(ctx->device));
+    SH_TRY(hs_call_begin(hs));
     const int chunks = sh_div_up(n, K8_LANES);
     if ((int64_t)B * chunks > (int64_t)INT32_MAX) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: %d poses x %d points, more workgroups than one launch takes", B, n);
     hs_class_map M;
     SH_TRY(hs_lat_pack_prepare(hs, level, world != 0, &M));                // (the world's plan refuses before anything is launched)
-    if (!hs->trc) {
-        hs->trc = new (std::nothrow) hs_trace();                          // (value-initialised: nothing allocated yet)
-        if (!hs->trc) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-    }
+    SH_TRY(hs_unit(&hs->trc));
     hs_trace *tr = hs->trc;
-    if (!tr->ev) SH_HIP(hipEventCreateWithFlags(&tr->ev, hipEventDisableTiming));
     const size_t pose_bytes = sizeof(float) * 3 * (size_t)B;
     const size_t sum_bytes = sizeof(slamhip_trace_summary) * (size_t)B;
     const size_t out_bytes = sum_bytes + (out_beams ? sizeof(slamhip_trace_beam) * (size_t)B * n : 0);
-    // (the blocks are idle: every trace waits for its own launches, and a trace that timed out has poisoned the context)
-    SH_TRY(hs_trc_grow((void **)&tr->d_poses, &tr->cap_poses, pose_bytes, false));
-    SH_TRY(hs_trc_grow((void **)&tr->d_out, &tr->cap_out, out_bytes, false));
-    SH_TRY(hs_trc_grow((void **)&tr->h_io, &tr->cap_h, out_bytes + pose_bytes, true));
+    SH_TRY(hs_grow((void **)&tr->d_poses, &tr->cap_poses, pose_bytes, HS_MEM_DEVICE, "trace"));
+    SH_TRY(hs_grow((void **)&tr->d_out, &tr->cap_out, out_bytes, HS_MEM_DEVICE, "trace"));
+    SH_TRY(hs_grow((void **)&tr->h_io, &tr->cap_h, out_bytes + pose_bytes, HS_MEM_PINNED, "trace"));
     float *h_poses = (float *)(tr->h_io + out_bytes);                      // (out_bytes is a multiple of 8)
     memcpy(h_poses, poses, pose_bytes);
     SH_TRY(hs_flush_scan(hs));
@@ -250,9 +235,7 @@ extern "C" int32_t slamhip_hs_trace(slamhip_hs *hs, int32_t level, const float *
     hipLaunchKernelGGL(k8_trace, dim3((unsigned)(B * chunks)), dim3(K8_LANES), 0, ctx->stream, A);    // (no timing class of its own)
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(tr->h_io, tr->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SH_HIP(hipEventRecord(tr->ev, ctx->stream));
-    SH_TRY(sh_event_wait(ctx, tr->ev));
-    hs->launch_done = hs->launch_count;                                    // (the stream has drained up to here)
+    SH_TRY(hs_call_finish(hs));
     memcpy(out_summaries, tr->h_io, sum_bytes);
     if (out_beams) memcpy(out_beams, tr->h_io + sum_bytes, out_bytes - sum_bytes);
     return SLAMHIP_OK;
