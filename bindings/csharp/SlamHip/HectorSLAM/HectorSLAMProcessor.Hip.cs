@@ -318,6 +318,32 @@ namespace HectorSLAM.Main
             return res;
         }
 
+        /// <summary>The source map of the merge through the processor (slamhip_hsproc_merge_set_source): as MapRep.MergeSetSource.</summary>
+        public unsafe void MergeSetSource(int level, int ax, int ay, int w, int h, HectorSLAM.Map.LogOddsCell[] cells)
+        {
+            if (cells.Length != w * h) throw new ArgumentException("cells must hold w * h elements");
+            fixed (HectorSLAM.Map.LogOddsCell* c = cells)
+                Native.Check(Native.slamhip_hsproc_merge_set_source(proc.Ptr, level, ax, ay, w, h, c));
+        }
+
+        /// <summary>MapRep.MergeScore at WORLD poses of the source frame's origin (slamhip_hsproc_merge_score).</summary>
+        public unsafe MergeReport[] MergeScore(Vector3[] posesWorld)
+        {
+            var reports = new MergeReport[posesWorld.Length];
+            fixed (Vector3* p = posesWorld)
+            fixed (MergeReport* r = reports)
+                Native.Check(Native.slamhip_hsproc_merge_score(proc.Ptr, p, posesWorld.Length, r));
+            return reports;
+        }
+
+        /// <summary>MapRep.MergeApply at a WORLD pose (slamhip_hsproc_merge_apply).  MatchPose, LastMapUpdatePose and the update gate are
+        /// untouched.</summary>
+        public MergeReport MergeApply(Vector3 poseWorld, int rule, float valueLimit)
+        {
+            Native.Check(Native.slamhip_hsproc_merge_apply(proc.Ptr, poseWorld, rule, valueLimit, out MergeReport report));
+            return report;
+        }
+
         /// <summary>Start Monte-Carlo localisation: the particle set of the processor's own pyramid (MapRep.MclSet) from WORLD poses, taken
         /// to the window's frame as Relocalise takes its centre (minus (float)Origin * Maps[0].CellLength per axis).</summary>
         public void LocaliseInit(Vector3[] posesWorld)

@@ -409,6 +409,60 @@ namespace HectorSLAM.Main
             return res;
         }
 
+        /// <summary>The source map of the merge (slamhip_hs_merge_set_source; the reference has no counterpart): cells, row-major w x h,
+        /// the first source-frame cell (ax, ay) of a grid with the level's cell length -- what DownloadCells or WorldCells of any pyramid
+        /// gives.  It stays in device memory until the next MergeSetSource, MergeClearSource or Reset.</summary>
+        public unsafe void MergeSetSource(int level, int ax, int ay, int w, int h, LogOddsCell[] cells)
+        {
+            if (cells.Length != w * h) throw new ArgumentException("cells must hold w * h elements");
+            fixed (LogOddsCell* c = cells)
+                Native.Check(Native.slamhip_hs_merge_set_source(Pyramid.Ptr, level, ax, ay, w, h, c));
+        }
+
+        /// <summary>Rate candidate alignments of the source with its level (slamhip_hs_merge_score): each pose the origin and heading of
+        /// the SOURCE frame in the window's frame, at most 4096.  Blocking; it changes nothing.</summary>
+        public unsafe MergeReport[] MergeScore(Vector3[] poses)
+        {
+            var reports = new MergeReport[poses.Length];
+            fixed (Vector3* p = poses)
+            fixed (MergeReport* r = reports)
+                Native.Check(Native.slamhip_hs_merge_score(Pyramid.Ptr, p, poses.Length, r));
+            return reports;
+        }
+
+        /// <summary>Fuse the source into its level at one pose on the device (slamhip_hs_merge_apply): rule 0 add (cut to +-valueLimit),
+        /// 1 fill unknown cells, 2 replace.  Blocking.</summary>
+        public MergeReport MergeApply(Vector3 pose, int rule, float valueLimit)
+        {
+            Native.Check(Native.slamhip_hs_merge_apply(Pyramid.Ptr, pose, rule, valueLimit, out MergeReport report));
+            return report;
+        }
+
+        /// <summary>No source from here on (slamhip_hs_merge_clear_source).</summary>
+        public void MergeClearSource() => Native.Check(Native.slamhip_hs_merge_clear_source(Pyramid.Ptr));
+
+        /// <summary>The merge of the definition on the host (slamhip_debug_merge): no device involved.</summary>
+        public static unsafe LogOddsCell[] MergeOf(LogOddsCell[] dst, int dw, int dh, LogOddsCell[] src, int ax, int ay, int sw, int sh, Vector3 pose, float stm, int rule,
+                                                   float valueLimit, out MergeReport report)
+        {
+            var res = new LogOddsCell[dst.Length];
+            fixed (LogOddsCell* d = dst)
+            fixed (LogOddsCell* s = src)
+            fixed (LogOddsCell* r = res)
+                Native.Check(Native.slamhip_debug_merge(d, dw, dh, s, ax, ay, sw, sh, pose, stm, rule, valueLimit, r, out report));
+            return res;
+        }
+
+        /// <summary>The kernels' tile box of a destination tile (slamhip_debug_merge_box): {u0, v0, u1, v1} in cells of the source array,
+        /// or null when no cell of the tile is sourced.</summary>
+        public static unsafe int[] MergeBoxOf(Vector3 pose, float stm, int ax, int ay, int sw, int sh, int x0, int y0, int x1, int y1)
+        {
+            var box = new int[4];
+            int any;
+            fixed (int* b = box) Native.Check(Native.slamhip_debug_merge_box(pose, stm, ax, ay, sw, sh, x0, y0, x1, y1, b, out any));
+            return any != 0 ? box : null;
+        }
+
         /// <summary>The weight table of the localisation step (slamhip_debug_mcl_table).</summary>
         public static unsafe uint[] MclTable()
         {

@@ -216,6 +216,17 @@ namespace SlamHip
         public ulong KeyEnd, KeyMin;
     }
 
+    /// <summary>slamhip_merge_report (include/slamhip.h): the destination cells of a merge counted by their class and their source
+    /// cell's -- Joint(cd, cs), classes 0 neither, 1 occupied, 2 free -- those with no source cell, and what an apply changed and cut.
+    /// 96 bytes, no padding.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public unsafe struct MergeReport
+    {
+        public fixed long JointCounts[9];
+        public long UnsourcedCount, ChangedCount, ClampedCount;
+        public long Joint(int destinationClass, int sourceClass) => JointCounts[3 * destinationClass + sourceClass];
+    }
+
     /// <summary>slamhip_mcl_spec (include/slamhip.h): one particle-filter localisation step -- the field's level, world, site mask and
     /// radius, the odometry increment in the robot's frame, the noise scales, the window's movement since the last step, the weight
     /// scale, the resampling threshold and the Philox key and stream.  72 bytes, no padding.</summary>
@@ -356,6 +367,14 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_debug_mcl_step(byte* cls, int cw, int ch, float stm, Vector2* points, int nPoints, Vector3* particlesIn, ulong* accIn, int nParticles,
                                                                           in MclSpec spec, Vector3* particlesOut, ulong* accOut, int* ancestorsOut, out MclSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_debug_mcl_table(uint* table64);
+        [DllImport(Lib)] internal static extern int slamhip_hs_merge_set_source(IntPtr hs, int level, int ax, int ay, int w, int h, HectorSLAM.Map.LogOddsCell* cells);
+        [DllImport(Lib)] internal static extern int slamhip_hs_merge_score(IntPtr hs, Vector3* poses, int nPoses, MergeReport* reports);
+        [DllImport(Lib)] internal static extern int slamhip_hs_merge_apply(IntPtr hs, in Vector3 pose, int rule, float valueLimit, out MergeReport report);
+        [DllImport(Lib)] internal static extern int slamhip_hs_merge_clear_source(IntPtr hs);
+        [DllImport(Lib)] internal static extern int slamhip_debug_merge(HectorSLAM.Map.LogOddsCell* dst, int dw, int dh, HectorSLAM.Map.LogOddsCell* src, int ax, int ay, int sw, int sh, in Vector3 pose, float stm,
+                                                                       int rule, float valueLimit, HectorSLAM.Map.LogOddsCell* cellsOut, out MergeReport report);
+        [DllImport(Lib)] internal static extern int slamhip_debug_merge_box(in Vector3 pose, float stm, int ax, int ay, int sw, int sh, int x0, int y0, int x1, int y1, int* box4,
+                                                                           out int any);
         [DllImport(Lib)] internal static extern int slamhip_debug_rollouts(byte* cls, int cw, int ch, int siteMask, int clearance, uint maxCost, int* sources, int nSources, float stm,
                                                                           float* startPose, float dt, float* body, int nBody, float* cmds, int nRollouts, int nCmd, int hold,
                                                                           RolloutResult* results, out RolloutSummary summary);
@@ -395,6 +414,9 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_distance_score(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int world,
                                                                                   int siteMask, int radius, DistanceSummary* summaries, ushort* pointD2);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_mcl_step(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in MclSpec spec, out MclSummary summary);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_set_source(IntPtr proc, int level, int ax, int ay, int w, int h, HectorSLAM.Map.LogOddsCell* cells);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_score(IntPtr proc, Vector3* posesWorld, int nPoses, MergeReport* reports);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_apply(IntPtr proc, in Vector3 poseWorld, int rule, float valueLimit, out MergeReport report);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_frontiers(IntPtr proc, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
                                                                              int lx, int ly, int lw, int lh, int* labels);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_rollouts(IntPtr proc, ref NavSpec spec, int* sources, int nSources, float* startPoseWorld, float dt, float* body, int nBody,

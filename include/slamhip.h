@@ -1163,6 +1163,85 @@ int32_t slamhip_debug_mcl_step(const uint8_t *cls, int32_t cw, int32_t ch, float
 /* The weight table T of step 5. */
 int32_t slamhip_debug_mcl_table(uint32_t out[64]);
 
+/* K14 -- merge a second map into the window under a rigid transform (new; no reference counterpart: a map another robot made, a map
+ * an earlier session saved in another frame, or what this session mapped before slamhip_hs_relocalise_world told it where it is).
+ * A SOURCE map is kept in device memory (slamhip_hs_merge_set_source); candidate alignments are RATED without touching either map
+ * (slamhip_hs_merge_score); the source's evidence is FUSED into one level at the chosen alignment (slamhip_hs_merge_apply), after
+ * which the matcher, the grid update and K7 - K13 go on working on the result.
+ *
+ * The definition, shared by score and apply, for level L with ScaleToMap stm and window wd x hd, a source array of w x h cells whose
+ * first is source-frame cell (ax, ay), and a pose T = (tx, ty, theta): the origin and heading of the SOURCE frame in the destination
+ * WINDOW's frame, in metres and radians as every hs pose is.  Every binary32 operation is rounded on its own, no fused multiply-add.
+ *  1. txc = tx * stm, tyc = ty * stm; (c, s) = the cosine and sine the beam trace's Rotation(theta) holds (IEEERemainder by 2 pi, the
+ *     four snapped angles of Matrix3x2.CreateRotation, else the deterministic sine and cosine).
+ *  2. For destination cell (x, y): dxf = (float)x - txc, dyf = (float)y - tyc; u = (c * dxf) + (s * dyf), v = (c * dyf) - (s * dxf).
+ *     The cell is SOURCED iff |u| < 16777216 and |v| < 16777216 (a NaN fails) and (su, sv) = ((int)rintf(u) - ax, (int)rintf(v) - ay)
+ *     lies in [0, w) x [0, h); rintf rounds half to even.  Nearest neighbour, one source cell per destination cell: every destination
+ *     cell has one writer and the result has no holes.  A pose that is not finite is no error: nothing is sourced.
+ *  3. The report counts the destination cells: joint[3 * cd + cs] for a sourced cell, by the class of the destination cell BEFORE the
+ *     call (cd) and of its source cell (cs) -- the trace's classes: 1 if Value > 0.0f, 2 if Value < 0.0f, else 0, so NaN is 0 --
+ *     and n_unsourced for the others.  The library sets no threshold and forms no score.
+ *  4. Apply, for a sourced cell with destination Value d and source Value sv:
+ *       rule 0 ADD      if cs != 0 and d is not NaN: t = d + sv; if t > value_limit, t = value_limit; if t < -value_limit,
+ *                       t = -value_limit; the cell counts in n_clamped when either cut applied.  A NaN d stays as it is.  A sum that
+ *                       is NaN (an infinity met its opposite) is the quiet NaN 0x7FC00000, which no cut applies to.
+ *       rule 1 FILL     if cd == 0 and cs != 0: t = sv.
+ *       rule 2 REPLACE  if cs != 0: t = sv.
+ *     Otherwise the cell is left alone.  UpdateIndex never changes.  The Value is written only where its bits change; such cells
+ *     count in n_changed and get their probability written beside the Value, by the function every writer of the cells uses.  Tiles
+ *     of the backing store and cells outside the window are not touched (the caller scrolls and merges again); the reference cache's
+ *     epoch and the level's current update index are unchanged. */
+typedef struct slamhip_merge_report {
+    int64_t joint[9];                  /* joint[3 * cd + cs]: destination cells whose source cell lies in the source array, by the class of
+                                          the destination cell BEFORE the call (cd) and of the source cell (cs): 0 neither, 1 occupied, 2 free */
+    int64_t n_unsourced;               /* destination cells with no source cell; joint[] and this sum to w * h of the level */
+    int64_t n_changed;                 /* apply only: cells whose Value bits changed */
+    int64_t n_clamped;                 /* apply only, rule ADD: cells whose sum was cut to +-value_limit */
+} slamhip_merge_report;                /* 12 int64_t, 96 bytes, no padding */
+/* The source: cells[w * h], row-major, the first element source-frame cell (ax, ay) of a grid with the cell length of `level` --
+ * what slamhip_hs_cells_download or slamhip_hs_world_cells_download of any hs gives.  The cells pass through staging the library
+ * owns; ONE launch (k14_pack_source) leaves their Values in device memory as float[w * h] and their classes at 2 bits per cell.  The
+ * source's update indices are not kept: they mean nothing in another map's epochs.  The source stays until the next
+ * slamhip_hs_merge_set_source, slamhip_hs_merge_clear_source, slamhip_hs_reset or slamhip_hs_destroy; grid updates, matches and
+ * shifts leave it.  The blocks (16 B of device and 8 B of pinned memory per source cell) belong to the hs, are made by the first call
+ * and freed by slamhip_hs_destroy; an hs that never calls it allocates and launches nothing.  Blocking.  SLAMHIP_ERR_INVALID, nothing
+ * launched, the previous source kept: level out of range; w or h below 1; w * h > 2^26; |ax| or |ay| above 2^30.  A poisoned context:
+ * SLAMHIP_ERR_TIMEOUT. */
+int32_t slamhip_hs_merge_set_source(slamhip_hs *hs, int32_t level, int32_t ax, int32_t ay, int32_t w, int32_t h,
+                                    const slamhip_cell *cells);
+/* B reports (poses: B x 3 floats, B in [1, 4096]) for the source's level, n_changed = n_clamped = 0; nothing is changed.  On the
+ * operator's stream behind everything already enqueued: K7's class map of the destination level (the window's), a memset of the
+ * reports, then ONE launch, k14_score -- the grid is (tiles of 64 x 16 destination cells, chunks of 16 poses); a workgroup holds its
+ * tile's destination classes in registers and loops over its poses; per pose the tile box (step 2's operations on intervals) lets an
+ * unsourced tile leave at once, otherwise every lane gathers its source cells' class bits from the packed source, the ten counts come
+ * from wave ballots, and at the end ONE integer atomic add per workgroup, pose and non-zero counter.  Integers: every order gives the
+ * same bits.  Blocking, the context's bounded wait; the reports come back through pinned staging.  SLAMHIP_ERR_INVALID: B out of
+ * range.  SLAMHIP_ERR_STATE: no source.  A poisoned context: SLAMHIP_ERR_TIMEOUT.  Nothing is launched on any refusal. */
+int32_t slamhip_hs_merge_score(slamhip_hs *hs, const float *poses, int32_t B, slamhip_merge_report *out_reports);
+/* The source fused into its level at one pose, by ONE launch over the window (k14_apply: a workgroup per tile of 64 x 32 destination
+ * cells; a tile whose box of source cells is empty leaves at once, the others gather their source Values from global memory,
+ * bounds-checked -- staging the box in LDS was built and measured and does not win); the report's joint and n_unsourced equal what slamhip_hs_merge_score gives for the same pose just before.  Blocking.
+ * SLAMHIP_ERR_INVALID: rule outside 0 .. 2; value_limit not finite or not above 0 (checked also for rules 1 and 2, which ignore it);
+ * the reference's cache is on (slamhip_hs_set_reference_cache) -- its literal stale entries have no meaning under an operation the
+ * reference lacks, as for slamhip_hs_shift.  SLAMHIP_ERR_STATE: no source.  A poisoned context: SLAMHIP_ERR_TIMEOUT.  Nothing is
+ * launched on any refusal. */
+int32_t slamhip_hs_merge_apply(slamhip_hs *hs, const float pose[3], int32_t rule, float value_limit,
+                               slamhip_merge_report *out_report);
+/* No source from here on (the blocks stay).  Never fails for an hs without one. */
+int32_t slamhip_hs_merge_clear_source(slamhip_hs *hs);
+/* Test hook (no device involved): steps 1 - 4 over a destination array dst[dw * dh] and a source array src[sw * sh] whose first cell
+ * is source-frame cell (ax, ay), from the header text the kernels run (hs_merge.h), in plain loops.  out_cells: dw * dh merged cells;
+ * out_report as slamhip_hs_merge_apply's.  SLAMHIP_ERR_INVALID: a size below 1 or above 2^26 cells, |ax| or |ay| above 2^30, and
+ * the rule's and the limit's refusals of slamhip_hs_merge_apply. */
+int32_t slamhip_debug_merge(const slamhip_cell *dst, int32_t dw, int32_t dh, const slamhip_cell *src, int32_t ax, int32_t ay,
+                            int32_t sw, int32_t sh, const float pose[3], float stm, int32_t rule, float value_limit,
+                            slamhip_cell *out_cells, slamhip_merge_report *out_report);
+/* Test hook: the kernels' tile box of destination tile [x0, x1] x [y0, y1] (0 <= x0 <= x1 < 32768, likewise y) -- out_box = {u0, v0,
+ * u1, v1}, inclusive, in cells of the source ARRAY: every sourced cell of the tile has its source cell in it; *out_any = 0: the box
+ * is empty, no cell of the tile is sourced. */
+int32_t slamhip_debug_merge_box(const float pose[3], float stm, int32_t ax, int32_t ay, int32_t sw, int32_t sh, int32_t x0, int32_t y0,
+                                int32_t x1, int32_t y1, int32_t out_box[4], int32_t *out_any);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -1382,6 +1461,15 @@ int32_t slamhip_hsproc_rollouts(slamhip_hsproc *p, const slamhip_nav_spec *spec,
  * was set. */
 int32_t slamhip_hsproc_mcl_step(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
                                 const slamhip_mcl_spec *spec, slamhip_mcl_summary *out);
+/* The merge through the processor.  _set_source: slamhip_hs_merge_set_source on the processor's own hs, the arguments as given (the
+ * source's frame is its own).  _score and _apply: the poses are WORLD poses of the source frame's origin, taken to the window's frame
+ * as slamhip_hsproc_trace takes its poses (minus (float)origin * cell0 per axis; with the origin at (0, 0) every bit passes through).
+ * MatchPose, LastMapUpdatePose and the update gate are untouched.  Errors as the slamhip_hs_merge_* calls. */
+int32_t slamhip_hsproc_merge_set_source(slamhip_hsproc *p, int32_t level, int32_t ax, int32_t ay, int32_t w, int32_t h,
+                                        const slamhip_cell *cells);
+int32_t slamhip_hsproc_merge_score(slamhip_hsproc *p, const float *poses_world, int32_t B, slamhip_merge_report *out_reports);
+int32_t slamhip_hsproc_merge_apply(slamhip_hsproc *p, const float pose_world[3], int32_t rule, float value_limit,
+                                   slamhip_merge_report *out_report);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -149,6 +149,10 @@ MCL_SUMMARY = np.dtype([("W", np.uint64), ("A", np.uint64), ("Q", np.uint64), ("
                         ("sum_hc", np.int64), ("sum_hs", np.int64), ("cost_min", np.uint64), ("cost_max", np.uint64), ("resampled", np.int32),
                         ("n_distinct", np.int32), ("n_unplaced", np.int32), ("n_particles", np.int32)])   # slamhip_mcl_summary: 96 bytes
 assert MCL_SPEC.itemsize == 72 and MCL_SUMMARY.itemsize == 96
+MERGE_MAX_CELLS, MERGE_MAX_POSES = 1 << 26, 4096                # the limits of slamhip_hs_merge_set_source / slamhip_hs_merge_score
+MERGE_ADD, MERGE_FILL, MERGE_REPLACE = 0, 1, 2                  # the rules of slamhip_hs_merge_apply
+MERGE_REPORT = np.dtype([("joint", np.int64, (9,)), ("n_unsourced", np.int64), ("n_changed", np.int64), ("n_clamped", np.int64)])   # slamhip_merge_report
+assert MERGE_REPORT.itemsize == 96
 
 
 def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
@@ -218,6 +222,8 @@ def _declare(L):
         "slamhip_debug_rollouts": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, C.c_float, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
         "slamhip_debug_mcl_step": (i32, [vp, i32, i32, C.c_float, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]),
         "slamhip_debug_mcl_table": (i32, [vp]),
+        "slamhip_debug_merge": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, fp, C.c_float, i32, C.c_float, vp, vp]),
+        "slamhip_debug_merge_box": (i32, [fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, ip, ip]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -313,6 +319,10 @@ def _declare(L):
         "slamhip_hs_mcl_set": (i32, [vp, vp, i32]),
         "slamhip_hs_mcl_step": (i32, [vp, vp, vp]),
         "slamhip_hs_mcl_get": (i32, [vp, vp, vp, vp, i32]),
+        "slamhip_hs_merge_set_source": (i32, [vp, i32, i32, i32, i32, i32, vp]),
+        "slamhip_hs_merge_score": (i32, [vp, fp, i32, vp]),
+        "slamhip_hs_merge_apply": (i32, [vp, fp, i32, C.c_float, vp]),
+        "slamhip_hs_merge_clear_source": (i32, [vp]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -343,6 +353,9 @@ def _declare(L):
         "slamhip_hsproc_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hsproc_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_mcl_step": (i32, [vp, fp, i32, fp, vp, vp]),
+        "slamhip_hsproc_merge_set_source": (i32, [vp, i32, i32, i32, i32, i32, vp]),
+        "slamhip_hsproc_merge_score": (i32, [vp, fp, i32, vp]),
+        "slamhip_hsproc_merge_apply": (i32, [vp, fp, i32, C.c_float, vp]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -645,3 +658,25 @@ def srptr(a):
 def f32(a, shape=None):
     a = np.ascontiguousarray(a, dtype=np.float32)
     return a if shape is None else a.reshape(shape)
+
+
+def debug_merge(dst, src, ax, ay, pose, stm, rule, value_limit):
+    """The merge of the definition (slamhip_hs_merge_apply, steps 1 - 4) on the host (slamhip_debug_merge; no device involved): dst an
+    (dh, dw) and src an (sh, sw) array of CELL_DTYPE, src's first cell source-frame cell (ax, ay); stm = 1 / cell length.
+    -> (merged cells (dh, dw), a MERGE_REPORT record)."""
+    vp = C.c_void_p
+    d = np.ascontiguousarray(dst, CELL_DTYPE); s = np.ascontiguousarray(src, CELL_DTYPE)
+    assert d.ndim == 2 and s.ndim == 2
+    out = np.empty_like(d); rep = np.zeros(1, MERGE_REPORT)
+    call("slamhip_debug_merge", d.ctypes.data_as(vp), d.shape[1], d.shape[0], s.ctypes.data_as(vp), int(ax), int(ay), s.shape[1], s.shape[0],
+         fptr(f32(pose, (3,))), C.c_float(stm), int(rule), C.c_float(value_limit), out.ctypes.data_as(vp), rep.ctypes.data_as(vp))
+    return out, rep[0]
+
+
+def debug_merge_box(pose, stm, ax, ay, sw, sh, x0, y0, x1, y1):
+    """The kernels' tile box (slamhip_debug_merge_box) of destination tile [x0, x1] x [y0, y1] -> (u0, v0, u1, v1) in cells of the
+    source array, inclusive, or None: no cell of the tile is sourced."""
+    box = (C.c_int32 * 4)(); any_ = C.c_int32()
+    call("slamhip_debug_merge_box", fptr(f32(pose, (3,))), C.c_float(stm), int(ax), int(ay), int(sw), int(sh), int(x0), int(y0), int(x1), int(y1),
+         box, C.byref(any_))
+    return tuple(int(v) for v in box) if any_.value else None

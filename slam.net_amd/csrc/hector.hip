@@ -122,6 +122,7 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
     hs_nav_free(hs);
     hs_ro_free(hs);
     hs_mcl_free(hs);
+    hs_merge_free(hs);
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
     if (hs->ev_pts) (void)hipEventDestroy(hs->ev_pts);
@@ -148,6 +149,7 @@ extern "C" int32_t slamhip_hs_reset(slamhip_hs *hs)
     if (hs->bk) hs_bk_reset(hs);
     SH_HIP(hipStreamSynchronize(hs->ctx->stream));
     hs->win_ox = hs->win_oy = 0;                                           // (slamhip_hs_shift: an empty map has no frame to keep)
+    hs_merge_drop_source(hs);                                              // (slamhip_hs_merge_set_source: a source belongs to the map it was to be merged into)
     return SLAMHIP_OK;
 }
 

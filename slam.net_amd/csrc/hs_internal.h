@@ -46,6 +46,7 @@ struct hs_frontier;                        // hs_frontier.hip
 struct hs_nav;                             // hs_nav.hip
 struct hs_rollout;                         // hs_rollout.hip
 struct hs_mcl;                             // hs_mcl.hip
+struct hs_merge;                           // hs_merge.hip
 struct hs_field;                           // hs_dfield.h
 struct slamhip_hs {
     slamhip_ctx *ctx;
@@ -69,7 +70,7 @@ struct slamhip_hs {
     // mailbox's sequence word (the mailbox is 64 B, the report 76)
     slamhip_match_report *d_rep, *h_rep; int cap_rep; unsigned long long *d_best_key;
     int64_t win_ox, win_oy;                                // slamhip_hs_shift: where cell (0, 0) of level 0 lies in the world, in level-0 cells (host-side books only)
-    hipEvent_t ev_call;                                    // what the blocking calls of K7 .. K13 record and wait on before they return (hs_call_finish, hs_blocks.h)
+    hipEvent_t ev_call;                                    // what the blocking calls of K7 .. K14 record and wait on before they return (hs_call_finish, hs_blocks.h)
     struct hs_backing *bk;                                 // slamhip_hs_set_backing: the tile pool and its host directory; nullptr while backing is off
     struct hs_world *wp;                                   // slamhip_hs_world_cells_upload / _world_extends: their staging buffer, made by the first call, kept
     struct hs_lattice *lat;                                // slamhip_hs_lattice_search: the class map and the result blocks, made by the first search, kept
@@ -79,6 +80,7 @@ struct slamhip_hs {
     struct hs_nav *nav;                                    // slamhip_hs_nav_field: the traversable words, costs, dirs, tile flags and the results' blocks, made by the first call, kept
     struct hs_rollout *rol;                                // slamhip_hs_rollouts: the commands', body points' and results' blocks, made by the first call, kept
     struct hs_mcl *mcl;                                    // slamhip_hs_mcl_set / _step / _get: the particle set and the step's blocks, made by the first set, kept
+    struct hs_merge *mrg;                                  // slamhip_hs_merge_set_source / _score / _apply: the source map and the reports' blocks, made by the first set_source, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -195,3 +197,9 @@ void    hs_mcl_free(slamhip_hs *hs);        // the particle set and the blocks o
 // what slamhip_hs_mcl_step refuses before it launches anything, for a scan of n_points (scan_is_set false: the caller is about to set
 // one, so its absence is no error)
 int32_t hs_mcl_check_step(const slamhip_hs *hs, const slamhip_mcl_spec *spec, int n_points, bool scan_is_set);
+// hs_merge.hip
+void    hs_merge_free(slamhip_hs *hs);      // the source map and the blocks of the merge (the caller has drained the stream)
+void    hs_merge_drop_source(slamhip_hs *hs);   // slamhip_hs_reset, slamhip_hs_merge_clear_source: no source from here on; the blocks stay
+// what slamhip_hs_merge_score and _apply refuse before they launch anything
+int32_t hs_merge_check_score(const slamhip_hs *hs, int32_t B);
+int32_t hs_merge_check_apply(const slamhip_hs *hs, int32_t rule, float value_limit);

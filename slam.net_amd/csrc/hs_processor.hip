@@ -414,6 +414,30 @@ extern "C" int32_t slamhip_hsproc_mcl_step(slamhip_hsproc *p, const float *xy, i
     return slamhip_hs_mcl_step(p->hs, spec, out);
 }
 
+// The merge through the processor: the source as given, the poses taken to the window's frame as slamhip_hsproc_trace takes its poses.
+// What the hs calls refuse for their arguments is refused ahead of the conversion.
+extern "C" int32_t slamhip_hsproc_merge_set_source(slamhip_hsproc *p, int32_t level, int32_t ax, int32_t ay, int32_t w, int32_t h, const slamhip_cell *cells)
+{
+    SH_CHECK_ARG(p);
+    return slamhip_hs_merge_set_source(p->hs, level, ax, ay, w, h, cells);
+}
+
+extern "C" int32_t slamhip_hsproc_merge_score(slamhip_hsproc *p, const float *poses_world, int32_t B, slamhip_merge_report *out_reports)
+{
+    SH_CHECK_ARG(p && poses_world && out_reports);
+    SH_TRY(hs_merge_check_score(p->hs, B));
+    std::vector<float> buf;
+    return slamhip_hs_merge_score(p->hs, hsproc_poses_to_window(p, poses_world, B, buf), B, out_reports);
+}
+
+extern "C" int32_t slamhip_hsproc_merge_apply(slamhip_hsproc *p, const float pose_world[3], int32_t rule, float value_limit, slamhip_merge_report *out_report)
+{
+    SH_CHECK_ARG(p && pose_world && out_report);
+    float pose[3];
+    hsproc_pose_to_window(p, pose_world, pose);
+    return slamhip_hs_merge_apply(p->hs, pose, rule, value_limit, out_report);
+}
+
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)
 {
     SH_CHECK_ARG(p);

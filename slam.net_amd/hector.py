@@ -430,6 +430,37 @@ class MapRepMultiMap:
         capi.call("slamhip_hs_mcl_step", self._h, spec.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
         return out[0]
 
+    def merge_set_source(self, level, ax, ay, cells):
+        """The source map of the merge (slamhip_hs_merge_set_source; no reference counterpart): `cells`, an (h, w) array of
+        capi.CELL_DTYPE whose first element is source-frame cell (ax, ay) of a grid with `level`'s cell length -- what GetCells or
+        world_cells of any pyramid gives.  It stays in device memory until the next merge_set_source, merge_clear_source or Reset."""
+        c = np.ascontiguousarray(cells, capi.CELL_DTYPE)
+        if c.ndim != 2:
+            raise ValueError("merge_set_source: cells must be an (h, w) array")
+        capi.call("slamhip_hs_merge_set_source", self._h, int(level), int(ax), int(ay), c.shape[1], c.shape[0], c.ctypes.data_as(C.c_void_p))
+
+    def merge_score(self, poses):
+        """Rate candidate alignments of the source with its level (slamhip_hs_merge_score): `poses` (B, 3), each the origin and heading
+        of the SOURCE frame in the window's frame, B <= 4096.  -> (B,) capi.MERGE_REPORT records: joint[3 * cd + cs] counts the
+        destination cells by their class and their source cell's (0 neither, 1 occupied, 2 free), n_unsourced those with no source
+        cell.  Blocking; it changes nothing."""
+        p = capi.f32(poses, (-1, 3))
+        out = np.zeros(p.shape[0], capi.MERGE_REPORT)
+        capi.call("slamhip_hs_merge_score", self._h, capi.fptr(p), p.shape[0], out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def merge_apply(self, pose, rule=capi.MERGE_ADD, value_limit=50.0):
+        """Fuse the source into its level at `pose` on the device (slamhip_hs_merge_apply): rule capi.MERGE_ADD (log-odds added, cut to
+        +-value_limit), MERGE_FILL (unknown cells only) or MERGE_REPLACE.  -> a capi.MERGE_REPORT record.  Blocking.  The other levels,
+        the tiles of the backing store and cells outside the window are not touched."""
+        out = np.zeros(1, capi.MERGE_REPORT)
+        capi.call("slamhip_hs_merge_apply", self._h, capi.fptr(capi.f32(pose, (3,))), int(rule), C.c_float(value_limit), out.ctypes.data_as(C.c_void_p))
+        return out[0]
+
+    def merge_clear_source(self):
+        """No source from here on (slamhip_hs_merge_clear_source)."""
+        capi.call("slamhip_hs_merge_clear_source", self._h)
+
     def mcl_get(self, poses=True, acc=True, ancestors=True):
         """The particle set as it stands (slamhip_hs_mcl_get) -> (poses (N, 3) float32, acc (N,) uint64, ancestors (N,) int32 of the
         last step); None for what was not asked for."""
@@ -749,6 +780,32 @@ class HectorSLAMProcessor:
         ox, oy = self.get_origin()
         cell0 = np.float32(self.MapRep.Maps[0].CellLength)
         return np.float32(ox) * cell0, np.float32(oy) * cell0
+
+    def merge_set_source(self, level, ax, ay, cells):
+        """MapRep.merge_set_source through the processor (slamhip_hsproc_merge_set_source): the source's frame is its own."""
+        c = np.ascontiguousarray(cells, capi.CELL_DTYPE)
+        if c.ndim != 2:
+            raise ValueError("merge_set_source: cells must be an (h, w) array")
+        capi.call("slamhip_hsproc_merge_set_source", self._h, int(level), int(ax), int(ay), c.shape[1], c.shape[0], c.ctypes.data_as(C.c_void_p))
+
+    def merge_score(self, posesWorld):
+        """MapRep.merge_score at WORLD poses of the source frame's origin (slamhip_hsproc_merge_score), taken to the window's frame as
+        Trace takes its poses."""
+        p = capi.f32(posesWorld, (-1, 3))
+        out = np.zeros(p.shape[0], capi.MERGE_REPORT)
+        capi.call("slamhip_hsproc_merge_score", self._h, capi.fptr(p), p.shape[0], out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def merge_apply(self, poseWorld, rule=capi.MERGE_ADD, value_limit=50.0):
+        """MapRep.merge_apply at a WORLD pose (slamhip_hsproc_merge_apply).  MatchPose, LastMapUpdatePose and the update gate are
+        untouched."""
+        out = np.zeros(1, capi.MERGE_REPORT)
+        capi.call("slamhip_hsproc_merge_apply", self._h, capi.fptr(capi.f32(poseWorld, (3,))), int(rule), C.c_float(value_limit),
+                  out.ctypes.data_as(C.c_void_p))
+        return out[0]
+
+    def merge_clear_source(self):
+        self.MapRep.merge_clear_source()
 
     def LocaliseInit(self, poses_world):
         """Start Monte-Carlo localisation: the particle set of the processor's own pyramid (MapRep.mcl_set) from WORLD poses, taken to
