@@ -344,6 +344,36 @@ namespace HectorSLAM.Main
             return report;
         }
 
+        /// <summary>MapRep.ViewGain of `scan` at WORLD poses (slamhip_hsproc_view_gain), taken to the window's frame as Trace takes them.
+        /// MatchPose, LastMapUpdatePose and the update gate are untouched.</summary>
+        public unsafe ViewSummary[] ViewGain(ScanCloud scan, Vector3[] posesWorld, int level, int reach, int commit = -1)
+        {
+            var sums = new ViewSummary[posesWorld.Length];
+            fixed (Vector2* p = CollectionsMarshal.AsSpan(scan.Points))
+            fixed (Vector3* q = posesWorld)
+            fixed (ViewSummary* s = sums)
+                Native.Check(Native.slamhip_hsproc_view_gain(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), q, posesWorld.Length, level, reach, commit, s));
+            return sums;
+        }
+
+        /// <summary>MapRep.ViewSelect of `scan` at WORLD poses (slamhip_hsproc_view_select).</summary>
+        public unsafe int[] ViewSelect(ScanCloud scan, Vector3[] posesWorld, int level, int reach, int k, int mode, int minGain, out int[] gains)
+        {
+            var order = new int[k];
+            var gain = new int[k];
+            int n;
+            fixed (Vector2* p = CollectionsMarshal.AsSpan(scan.Points))
+            fixed (Vector3* q = posesWorld)
+            fixed (int* o = order)
+            fixed (int* g = gain)
+                Native.Check(Native.slamhip_hsproc_view_select(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), q, posesWorld.Length, level, reach, mode, minGain, k,
+                                                               o, g, out n));
+            Array.Resize(ref order, n);
+            Array.Resize(ref gain, n);
+            gains = gain;
+            return order;
+        }
+
         /// <summary>Start Monte-Carlo localisation: the particle set of the processor's own pyramid (MapRep.MclSet) from WORLD poses, taken
         /// to the window's frame as Relocalise takes its centre (minus (float)Origin * Maps[0].CellLength per axis).</summary>
         public void LocaliseInit(Vector3[] posesWorld)

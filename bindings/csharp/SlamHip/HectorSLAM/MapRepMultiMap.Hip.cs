@@ -463,6 +463,72 @@ namespace HectorSLAM.Main
             return any != 0 ? box : null;
         }
 
+        /// <summary>The view gain (slamhip_hs_view_gain; the reference has no counterpart): the DISTINCT cells of `level` the scan's beams
+        /// see from each pose (window frame, at most 4096), no further than `reach` cells, by class and against the covered layer as it
+        /// was before the call.  commit: -1 nothing, -2 every pose's cells join the layer, an index that pose's.  Blocking; it changes
+        /// nothing of the map.</summary>
+        public unsafe ViewSummary[] ViewGain(ScanCloud scan, Vector3[] poses, int level, int reach, int commit = -1)
+        {
+            SetScan(scan);
+            var sums = new ViewSummary[poses.Length];
+            fixed (Vector3* p = poses)
+            fixed (ViewSummary* s = sums)
+                Native.Check(Native.slamhip_hs_view_gain(Pyramid.Ptr, level, reach, p, poses.Length, commit, s));
+            return sums;
+        }
+
+        /// <summary>The greedy choice of views (slamhip_hs_view_select): up to k of the poses, each round the one that adds the most new
+        /// cells (mode 0) or new unknown cells (mode 1) to the covered layer, ties to the lowest index, until the best adds fewer than
+        /// minGain.  Returns the chosen pose indices in the order of choice; gains their gains.  The chosen views join the layer.</summary>
+        public unsafe int[] ViewSelect(ScanCloud scan, Vector3[] poses, int level, int reach, int k, int mode, int minGain, out int[] gains)
+        {
+            SetScan(scan);
+            var order = new int[k];
+            var gain = new int[k];
+            int n;
+            fixed (Vector3* p = poses)
+            fixed (int* o = order)
+            fixed (int* g = gain)
+                Native.Check(Native.slamhip_hs_view_select(Pyramid.Ptr, level, reach, mode, minGain, p, poses.Length, k, o, g, out n));
+            Array.Resize(ref order, n);
+            Array.Resize(ref gain, n);
+            gains = gain;
+            return order;
+        }
+
+        /// <summary>Set the covered layer of `level` (slamhip_hs_view_set_covered): rows of (w + 31) / 32 words, cell x bit x &amp; 31 of word
+        /// x >> 5; null: empty.</summary>
+        public unsafe void SetCovered(int level, uint[] bits)
+        {
+            fixed (uint* b = bits) Native.Check(Native.slamhip_hs_view_set_covered(Pyramid.Ptr, level, b));
+        }
+
+        /// <summary>The covered layer of `level` (slamhip_hs_view_get_covered), in SetCovered's layout.</summary>
+        public unsafe uint[] GetCovered(int level)
+        {
+            var dims = Maps[level].Dimensions;
+            var bits = new uint[((dims.X + 31) / 32) * dims.Y];
+            fixed (uint* b = bits) Native.Check(Native.slamhip_hs_view_get_covered(Pyramid.Ptr, level, b));
+            return bits;
+        }
+
+        /// <summary>Free every block of the view gain, the covered layer too (slamhip_hs_view_clear).</summary>
+        public void ViewClear() => Native.Check(Native.slamhip_hs_view_clear(Pyramid.Ptr));
+
+        /// <summary>One pose's seen cells and summary on the host (slamhip_debug_view): no device involved.  values: w * h cell Values,
+        /// row-major; covered: SetCovered's layout or null.</summary>
+        public static unsafe uint[] ViewOf(float[] values, int w, int h, float scaleToMap, Vector3 pose, Vector2 scanOrigin, Vector2[] points, int reach, uint[] covered,
+                                           out ViewSummary summary)
+        {
+            var bits = new uint[((w + 31) / 32) * h];
+            fixed (float* v = values)
+            fixed (Vector2* p = points)
+            fixed (uint* c = covered)
+            fixed (uint* b = bits)
+                Native.Check(Native.slamhip_debug_view(v, w, h, scaleToMap, pose, scanOrigin, p, points.Length, reach, c, b, out summary));
+            return bits;
+        }
+
         /// <summary>The weight table of the localisation step (slamhip_debug_mcl_table).</summary>
         public static unsafe uint[] MclTable()
         {

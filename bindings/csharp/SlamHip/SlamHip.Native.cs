@@ -227,6 +227,18 @@ namespace SlamHip
         public long Joint(int destinationClass, int sourceClass) => JointCounts[3 * destinationClass + sourceClass];
     }
 
+    /// <summary>slamhip_view_summary (include/slamhip.h): the DISTINCT cells one pose's beams see on a level -- the beams by status, the
+    /// cut ones, the seen cells and their split by class, and those not in the covered layer.  Ten int32, 40 bytes, no padding.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ViewSummary
+    {
+        public int WalkedCount, SameCount, IgnoredCount;
+        public int CutCount;
+        public int SeenCount;
+        public int UnknownCount, FreeCount, OccupiedCount;
+        public int NewCount, NewUnknownCount;
+    }
+
     /// <summary>slamhip_mcl_spec (include/slamhip.h): one particle-filter localisation step -- the field's level, world, site mask and
     /// radius, the odometry increment in the robot's frame, the noise scales, the window's movement since the last step, the weight
     /// scale, the resampling threshold and the Philox key and stream.  72 bytes, no padding.</summary>
@@ -375,6 +387,15 @@ namespace SlamHip
                                                                        int rule, float valueLimit, HectorSLAM.Map.LogOddsCell* cellsOut, out MergeReport report);
         [DllImport(Lib)] internal static extern int slamhip_debug_merge_box(in Vector3 pose, float stm, int ax, int ay, int sw, int sh, int x0, int y0, int x1, int y1, int* box4,
                                                                            out int any);
+        // the view gain and the greedy choice of views (no reference counterpart), and their host-side hook
+        [DllImport(Lib)] internal static extern int slamhip_hs_view_set_covered(IntPtr hs, int level, uint* bits);
+        [DllImport(Lib)] internal static extern int slamhip_hs_view_get_covered(IntPtr hs, int level, uint* bits);
+        [DllImport(Lib)] internal static extern int slamhip_hs_view_clear(IntPtr hs);
+        [DllImport(Lib)] internal static extern int slamhip_hs_view_gain(IntPtr hs, int level, int reach, Vector3* poses, int nPoses, int commit, ViewSummary* summaries);
+        [DllImport(Lib)] internal static extern int slamhip_hs_view_select(IntPtr hs, int level, int reach, int mode, int minGain, Vector3* poses, int nPoses, int k, int* order, int* gain,
+                                                                           out int n);
+        [DllImport(Lib)] internal static extern int slamhip_debug_view(float* values, int w, int h, float scaleToMap, in Vector3 pose, in Vector2 origin, Vector2* xy, int n, int reach,
+                                                                       uint* covered, uint* bitsOut, out ViewSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_debug_rollouts(byte* cls, int cw, int ch, int siteMask, int clearance, uint maxCost, int* sources, int nSources, float stm,
                                                                           float* startPose, float dt, float* body, int nBody, float* cmds, int nRollouts, int nCmd, int hold,
                                                                           RolloutResult* results, out RolloutSummary summary);
@@ -417,6 +438,10 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_set_source(IntPtr proc, int level, int ax, int ay, int w, int h, HectorSLAM.Map.LogOddsCell* cells);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_score(IntPtr proc, Vector3* posesWorld, int nPoses, MergeReport* reports);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_apply(IntPtr proc, in Vector3 poseWorld, int rule, float valueLimit, out MergeReport report);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_view_gain(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int reach,
+                                                                             int commit, ViewSummary* summaries);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_view_select(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int reach,
+                                                                               int mode, int minGain, int k, int* order, int* gain, out int n);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_frontiers(IntPtr proc, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
                                                                              int lx, int ly, int lw, int lh, int* labels);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_rollouts(IntPtr proc, ref NavSpec spec, int* sources, int nSources, float* startPoseWorld, float dt, float* body, int nBody,

@@ -752,7 +752,9 @@ int32_t slamhip_hs_relocalise_world(slamhip_hs *hs, const slamhip_lattice_spec *
  *     [0, w) x [0, h) has class 0 (the lattice search's rule).  In the WORLD variant such a cell has the class of world cell
  *     ((ox >> L) + x, (oy >> L) + y): the tile's cell if a tile of the backing store holds it, else 0 -- THE WORLD SEARCH's rule.
  *     Classes: 1 occupied (Value > 0.0f), 2 free (Value < 0.0f), 0 neither.
- *  4. Per beam, slamhip_trace_beam.  5. Per pose, slamhip_trace_summary.  The library sets no threshold and forms no score. */
+ *  4. Per beam, slamhip_trace_beam.  5. Per pose, slamhip_trace_summary.  The library sets no threshold and forms no score.
+ * unknown_cells counts a cell once per beam that crosses it -- the cells next to the sensor hundreds of times -- so it does not
+ * compare two poses; the DISTINCT cells a pose sees are slamhip_hs_view_gain's (K15). */
 #define SLAMHIP_TRACE_MAX_DA 32768
 typedef struct slamhip_trace_beam {
     int32_t da;           /* -1 ignored, 0 same, else the major length of the walked line */
@@ -1242,6 +1244,76 @@ int32_t slamhip_debug_merge(const slamhip_cell *dst, int32_t dw, int32_t dh, con
 int32_t slamhip_debug_merge_box(const float pose[3], float stm, int32_t ax, int32_t ay, int32_t sw, int32_t sh, int32_t x0, int32_t y0,
                                 int32_t x1, int32_t y1, int32_t out_box[4], int32_t *out_any);
 
+/* The view gain (K15; no reference counterpart): the DISTINCT cells of ONE level that the scan's beams would see from a pose, by
+ * class and against a layer of cells already covered, for many poses at once, and the greedy choice of the few poses of a list
+ * that together reveal the most -- what next-best-view exploration and a coverage run ask.  slamhip_trace_summary.unknown_cells
+ * cannot answer it: that figure counts a cell once per beam that crosses it.
+ * THE DEFINITION, for level L of the WINDOW only (there is no world variant), the scan and scan origin as slamhip_hs_set_scan took
+ * them, a pose P in the window's frame, and `reach` in [1, 4096] cells:
+ *  1. Beam.  Beam i is hs_trace_line_of under hs_trace_transform(stm, P): steps 1 - 2 of slamhip_trace_beam, unchanged -- ignored
+ *     (da = -1), same (da = 0), or walked.  Its cells are step 3 there (hs_trace_walk_begin / _next).  Classes are the lattice
+ *     search's: 1 occupied, 2 free, 0 neither.
+ *  2. What a beam sees.  A walked beam SEES the cells of steps a = 0 .. stop, stop = min(first if first >= 0 else da, reach): the
+ *     occupied cell that stops it is seen; the end cell is seen if it is reached.  Step a lies at Chebyshev distance exactly a from
+ *     b, so `reach` is the sensor's range limit in cells and every seen cell lies in the square of side 2 reach + 1 around b.  A
+ *     same beam sees b.  An ignored beam sees nothing.  A cell outside [0, w) x [0, h) is never seen, and the walk goes on through
+ *     it (class 0), as in the trace.  A beam is CUT if it is walked, has da > reach, and has no occupied cell at a step <= reach.
+ *  3. V(P) is the set of cells seen by any beam.
+ *  4. The covered layer C is a set of window cells of ONE level that the slamhip_hs holds; it is empty until set or committed to.
+ *     Its bitmap layout, in and out: row-major, wpr = (w + 31) / 32 uint32_t per row, cell x is bit x & 31 of word x >> 5.
+ *     Padding bits are ignored on input and zero on output.
+ *  5. Per pose, slamhip_view_summary.  C is the layer AS IT WAS BEFORE THE CALL for every pose of the call.  A pose that is not
+ *     finite is no error: all its beams are ignored and every other field is 0.
+ *  6. Greedy choice: rounds j = 1 .. k over the poses not yet chosen.  g(p) = n_new (mode 0) or n_new_unknown (mode 1), counted
+ *     against the CURRENT C.  The best is the largest g, ties to the lowest pose index.  The choice stops when g(best) < min_gain.
+ *     Otherwise the best is recorded with its gain, and ALL of V(best) joins C, in either mode. */
+typedef struct slamhip_view_summary {
+    int32_t n_walked, n_same, n_ignored;   /* the beams by status: they sum to n_points */
+    int32_t n_cut;                         /* the cut beams */
+    int32_t n_seen;                        /* |V| */
+    int32_t n_unknown, n_free, n_occupied; /* V by class: they sum to n_seen */
+    int32_t n_new;                         /* |V \ C| */
+    int32_t n_new_unknown;                 /* the class-0 cells of V \ C */
+} slamhip_view_summary;   /* ten int32_t, 40 bytes, no padding */
+/* The covered layer.  _set_covered makes the layer for `level` from `bits` (step 4's layout; NULL: empty) and stamps it with the
+ * window origin (slamhip_hs_origin); a layer of another level is replaced.  _get_covered downloads it (all zero while there is
+ * none).  _view_clear frees every block of the view gain, the layer too; slamhip_hs_destroy frees them as well, slamhip_hs_reset
+ * leaves the layer alone, and an hs that never asks allocates nothing.  SLAMHIP_ERR_INVALID: level out of range.
+ * SLAMHIP_ERR_STATE (_get_covered): the layer belongs to another level, or the window has moved since it was made. */
+int32_t slamhip_hs_view_set_covered(slamhip_hs *hs, int32_t level, const uint32_t *bits);
+int32_t slamhip_hs_view_get_covered(slamhip_hs *hs, int32_t level, uint32_t *bits);
+int32_t slamhip_hs_view_clear(slamhip_hs *hs);
+/* Step 5 at B poses (poses: B x 3 floats, window frame; B in [1, 4096]); out_summaries: B records.  commit = -1 changes nothing;
+ * -2 adds every pose's V to C after counting; 0 <= commit < B adds that pose's V.  A commit makes the layer if there is none.
+ * The launches, on the operator's stream: the lattice search's class map of the level, re-packed on every call, ONE launch of
+ * k15_view (a workgroup per pose: the pose's seen bitmap in LDS while the box of any pose of the call fits 8704 words -- reach 255
+ * does -- else in a scratch block, zeroed by a memset), and with a commit one launch that ORs the bitmaps into C.  Blocking, with
+ * the context's bounded wait; the results come back through pinned staging that the library owns.  It reads cell values only,
+ * so it works with backing off, with slamhip_hs_set_reference_cache on, and after shifts (once the layer is set again); it
+ * changes nothing of the map or of any search.
+ * SLAMHIP_ERR_INVALID, nothing launched: level, reach, B or commit out of range; the call needs scratch (a commit, or bitmaps
+ * that do not fit LDS) and B x rows x words_per_row exceeds 2^25 words (128 MB), rows = min(2 reach + 1, h), words_per_row =
+ * min((2 reach + 63) / 32, (w + 31) / 32).  SLAMHIP_ERR_STATE: no scan; the layer belongs to another level; the window origin
+ * differs from the layer's stamp (set the layer again; slamhip_hs_shift itself is not changed).  A poisoned context:
+ * SLAMHIP_ERR_TIMEOUT. */
+int32_t slamhip_hs_view_gain(slamhip_hs *hs, int32_t level, int32_t reach, const float *poses, int32_t B, int32_t commit,
+                             slamhip_view_summary *out_summaries);
+/* Step 6 over B poses: k in [1, 64], mode 0 or 1, min_gain >= 1.  out_order and out_gain have k entries: the chosen pose indices in
+ * the order of choice and their gains; entries past *out_n are -1 and 0.  The chosen views are committed to C (the layer is made if
+ * there is none).  The launches: the class map and k15_view as above (the bitmaps always go to the scratch block), then k15_gain
+ * (a workgroup per pose not yet chosen) and k15_pick (one workgroup) k times back to back -- the winner's index never leaves the
+ * device between rounds -- and ONE host wait at the end.  Errors as slamhip_hs_view_gain, and SLAMHIP_ERR_INVALID for k, mode or
+ * min_gain out of range. */
+int32_t slamhip_hs_view_select(slamhip_hs *hs, int32_t level, int32_t reach, int32_t mode, int32_t min_gain, const float *poses,
+                               int32_t B, int32_t k, int32_t *out_order, int32_t *out_gain, int32_t *out_n);
+/* Test hook (no device involved): steps 1 - 5 for one pose over values[w * h] (row-major cell Values), from the header text the
+ * kernels run (hs_view.h), in plain loops.  covered: step 4's bitmap, or NULL (empty).  out_bits: V as a bitmap of step 4's
+ * layout; out_summary as slamhip_hs_view_gain's.  SLAMHIP_ERR_INVALID: a size below 1 or above 2^26 cells, reach outside
+ * [1, 4096]. */
+int32_t slamhip_debug_view(const float *values, int32_t w, int32_t h, float stm, const float pose[3], const float origin[2],
+                           const float *xy, int32_t n_points, int32_t reach, const uint32_t *covered, uint32_t *out_bits,
+                           slamhip_view_summary *out_summary);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -1470,6 +1542,17 @@ int32_t slamhip_hsproc_merge_set_source(slamhip_hsproc *p, int32_t level, int32_
 int32_t slamhip_hsproc_merge_score(slamhip_hsproc *p, const float *poses_world, int32_t B, slamhip_merge_report *out_reports);
 int32_t slamhip_hsproc_merge_apply(slamhip_hsproc *p, const float pose_world[3], int32_t rule, float value_limit,
                                    slamhip_merge_report *out_report);
+/* The view gain through the processor: slamhip_hs_set_scan on the processor's own hs, then slamhip_hs_view_gain / _view_select at
+ * B WORLD poses, taken to the window's frame as slamhip_hsproc_trace takes its poses (minus (float)origin * cell0 per axis; with the
+ * origin at (0, 0) every bit passes through).  The covered layer is the hs's own (slamhip_hsproc_hs).  MatchPose, LastMapUpdatePose,
+ * the update gate and the map are untouched; the scan that was set is replaced.  Errors as the slamhip_hs_view_* calls; a call
+ * refused for its arguments alone leaves the scan that was set. */
+int32_t slamhip_hsproc_view_gain(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
+                                 const float *poses_world, int32_t B, int32_t level, int32_t reach, int32_t commit,
+                                 slamhip_view_summary *out_summaries);
+int32_t slamhip_hsproc_view_select(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
+                                   const float *poses_world, int32_t B, int32_t level, int32_t reach, int32_t mode, int32_t min_gain,
+                                   int32_t k, int32_t *out_order, int32_t *out_gain, int32_t *out_n);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

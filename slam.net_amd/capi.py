@@ -153,6 +153,10 @@ MERGE_MAX_CELLS, MERGE_MAX_POSES = 1 << 26, 4096                # the limits of 
 MERGE_ADD, MERGE_FILL, MERGE_REPLACE = 0, 1, 2                  # the rules of slamhip_hs_merge_apply
 MERGE_REPORT = np.dtype([("joint", np.int64, (9,)), ("n_unsourced", np.int64), ("n_changed", np.int64), ("n_clamped", np.int64)])   # slamhip_merge_report
 assert MERGE_REPORT.itemsize == 96
+VIEW_MAX_REACH, VIEW_MAX_POSES, VIEW_MAX_K, VIEW_LDS_WORDS = 4096, 4096, 64, 8704   # the limits of slamhip_hs_view_gain / _view_select; K15_LDS_WORDS
+VIEW_SUMMARY = np.dtype([(n, np.int32) for n in ("n_walked", "n_same", "n_ignored", "n_cut", "n_seen", "n_unknown", "n_free", "n_occupied", "n_new",
+                                                 "n_new_unknown")])   # slamhip_view_summary: ten int32, 40 bytes
+assert VIEW_SUMMARY.itemsize == 40
 
 
 def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
@@ -224,6 +228,7 @@ def _declare(L):
         "slamhip_debug_mcl_table": (i32, [vp]),
         "slamhip_debug_merge": (i32, [vp, i32, i32, vp, i32, i32, i32, i32, fp, C.c_float, i32, C.c_float, vp, vp]),
         "slamhip_debug_merge_box": (i32, [fp, C.c_float, i32, i32, i32, i32, i32, i32, i32, i32, ip, ip]),
+        "slamhip_debug_view": (i32, [fp, i32, i32, C.c_float, fp, fp, fp, i32, i32, vp, vp, vp]),
         "slamhip_ctx_timing_enable": (i32, [vp, i32]),
         "slamhip_ctx_timing_reset": (i32, [vp]),
         "slamhip_ctx_timing_get": (i32, [vp, i32, P(C.c_double), P(i64)]),
@@ -323,6 +328,11 @@ def _declare(L):
         "slamhip_hs_merge_score": (i32, [vp, fp, i32, vp]),
         "slamhip_hs_merge_apply": (i32, [vp, fp, i32, C.c_float, vp]),
         "slamhip_hs_merge_clear_source": (i32, [vp]),
+        "slamhip_hs_view_set_covered": (i32, [vp, i32, vp]),
+        "slamhip_hs_view_get_covered": (i32, [vp, i32, vp]),
+        "slamhip_hs_view_clear": (i32, [vp]),
+        "slamhip_hs_view_gain": (i32, [vp, i32, i32, fp, i32, i32, vp]),
+        "slamhip_hs_view_select": (i32, [vp, i32, i32, i32, i32, fp, i32, i32, ip, ip, ip]),
         "slamhip_hs_set_match_threads": (i32, [vp, i32]),
         "slamhip_hs_set_reference_cache": (i32, [vp, i32]),
         "slamhip_hs_update_by_scan": (i32, [vp, fp]),
@@ -356,6 +366,8 @@ def _declare(L):
         "slamhip_hsproc_merge_set_source": (i32, [vp, i32, i32, i32, i32, i32, vp]),
         "slamhip_hsproc_merge_score": (i32, [vp, fp, i32, vp]),
         "slamhip_hsproc_merge_apply": (i32, [vp, fp, i32, C.c_float, vp]),
+        "slamhip_hsproc_view_gain": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, vp]),
+        "slamhip_hsproc_view_select": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, i32, ip, ip, ip]),
         "slamhip_group_create": (i32, [ip, i32, f, i32, i32, vpp]),
         "slamhip_group_destroy": (i32, [vp]),
         "slamhip_group_size": (i32, [vp, ip]),
@@ -680,3 +692,37 @@ def debug_merge_box(pose, stm, ax, ay, sw, sh, x0, y0, x1, y1):
     call("slamhip_debug_merge_box", fptr(f32(pose, (3,))), C.c_float(stm), int(ax), int(ay), int(sw), int(sh), int(x0), int(y0), int(x1), int(y1),
          box, C.byref(any_))
     return tuple(int(v) for v in box) if any_.value else None
+
+
+def view_words(w):
+    """uint32 words per row of a covered or seen bitmap of w cells (slamhip_view_summary, step 4)."""
+    return (int(w) + 31) // 32
+
+
+def view_pack(mask):
+    """An (h, w) boolean array -> the (h, view_words(w)) uint32 bitmap of step 4: cell x is bit x & 31 of word x >> 5."""
+    m = np.asarray(mask, bool)
+    h, w = m.shape
+    pad = np.zeros((h, view_words(w) * 32), np.uint8)
+    pad[:, :w] = m
+    return np.ascontiguousarray(np.packbits(pad, axis=1, bitorder="little")).view(np.uint32).reshape(h, view_words(w))
+
+
+def view_unpack(bits, w):
+    """The (h, view_words(w)) uint32 bitmap of step 4 -> an (h, w) boolean array (the padding bits dropped)."""
+    b = np.ascontiguousarray(bits, np.uint32)
+    return np.unpackbits(b.view(np.uint8).reshape(b.shape[0], -1), axis=1, bitorder="little")[:, :w].astype(bool)
+
+
+def debug_view(values, stm, pose, origin, xy, reach, covered=None):
+    """V and the summary of one pose of the view gain (slamhip_debug_view; no device involved): values an (h, w) float32 array of cell
+    Values, covered an (h, view_words(w)) uint32 bitmap or None.  -> (V as such a bitmap, a VIEW_SUMMARY record)."""
+    v = f32(values)
+    assert v.ndim == 2
+    h, w = v.shape
+    xy = f32(xy, (-1, 2))
+    cov = None if covered is None else np.ascontiguousarray(covered, np.uint32).reshape(h, view_words(w))
+    out = np.empty((h, view_words(w)), np.uint32); s = np.zeros(1, VIEW_SUMMARY)
+    call("slamhip_debug_view", fptr(v), w, h, C.c_float(stm), fptr(f32(pose, (3,))), fptr(f32(origin, (2,))), fptr(xy), xy.shape[0], int(reach),
+         None if cov is None else cov.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p))
+    return out, s[0]

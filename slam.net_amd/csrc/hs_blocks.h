@@ -1,4 +1,4 @@
-// hs_blocks.h -- what the host halves of the Hector units K7 .. K14 share: the blocks a unit keeps between calls, the unit's struct
+// hs_blocks.h -- what the host halves of the Hector units K7 .. K15 share: the blocks a unit keeps between calls, the unit's struct
 // made on first use, and the frame of a blocking call.  Host code only.
 #pragma once
 #include "hs_internal.h"

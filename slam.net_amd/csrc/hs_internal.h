@@ -47,6 +47,7 @@ struct hs_nav;                             // hs_nav.hip
 struct hs_rollout;                         // hs_rollout.hip
 struct hs_mcl;                             // hs_mcl.hip
 struct hs_merge;                           // hs_merge.hip
+struct hs_view;                            // hs_view.hip
 struct hs_field;                           // hs_dfield.h
 struct slamhip_hs {
     slamhip_ctx *ctx;
@@ -81,6 +82,7 @@ struct slamhip_hs {
     struct hs_rollout *rol;                                // slamhip_hs_rollouts: the commands', body points' and results' blocks, made by the first call, kept
     struct hs_mcl *mcl;                                    // slamhip_hs_mcl_set / _step / _get: the particle set and the step's blocks, made by the first set, kept
     struct hs_merge *mrg;                                  // slamhip_hs_merge_set_source / _score / _apply: the source map and the reports' blocks, made by the first set_source, kept
+    struct hs_view *vw;                                    // slamhip_hs_view_gain / _select / _set_covered: the covered layer, the slots and the results' blocks, made by the first call, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -203,3 +205,10 @@ void    hs_merge_drop_source(slamhip_hs *hs);   // slamhip_hs_reset, slamhip_hs_
 // what slamhip_hs_merge_score and _apply refuse before they launch anything
 int32_t hs_merge_check_score(const slamhip_hs *hs, int32_t B);
 int32_t hs_merge_check_apply(const slamhip_hs *hs, int32_t rule, float value_limit);
+// hs_view.hip
+void    hs_view_free(slamhip_hs *hs);       // the covered layer and the blocks of the view gain (the caller has drained the stream)
+// what slamhip_hs_view_gain and _view_select refuse for their arguments alone, for a scan of n_points (scan_is_set false: the caller
+// is about to set one, so its absence is no error)
+int32_t hs_view_check_gain(const slamhip_hs *hs, int32_t level, int32_t reach, int32_t B, int32_t commit, int n_points, bool scan_is_set);
+int32_t hs_view_check_select(const slamhip_hs *hs, int32_t level, int32_t reach, int32_t mode, int32_t min_gain, int32_t B, int32_t k, int n_points,
+                             bool scan_is_set);

@@ -438,6 +438,29 @@ extern "C" int32_t slamhip_hsproc_merge_apply(slamhip_hsproc *p, const float pos
     return slamhip_hs_merge_apply(p->hs, pose, rule, value_limit, out_report);
 }
 
+// The view gain through the processor: slamhip_hsproc_trace's shape -- the arguments checked ahead of the scan, the scan set, every
+// pose taken to the window's frame.
+extern "C" int32_t slamhip_hsproc_view_gain(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float *poses_world, int32_t B,
+                                            int32_t level, int32_t reach, int32_t commit, slamhip_view_summary *out_summaries)
+{
+    SH_CHECK_ARG(p && poses_world && out_summaries);
+    SH_TRY(hs_view_check_gain(p->hs, level, reach, B, commit, n, false));
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    std::vector<float> buf;
+    return slamhip_hs_view_gain(p->hs, level, reach, hsproc_poses_to_window(p, poses_world, B, buf), B, commit, out_summaries);
+}
+
+extern "C" int32_t slamhip_hsproc_view_select(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float *poses_world, int32_t B,
+                                              int32_t level, int32_t reach, int32_t mode, int32_t min_gain, int32_t k, int32_t *out_order,
+                                              int32_t *out_gain, int32_t *out_n)
+{
+    SH_CHECK_ARG(p && poses_world && out_order && out_gain && out_n);
+    SH_TRY(hs_view_check_select(p->hs, level, reach, mode, min_gain, B, k, n, false));
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    std::vector<float> buf;
+    return slamhip_hs_view_select(p->hs, level, reach, mode, min_gain, hsproc_poses_to_window(p, poses_world, B, buf), B, k, out_order, out_gain, out_n);
+}
+
 extern "C" int32_t slamhip_hsproc_get(slamhip_hsproc *p, float match_pose[3], float last[3], float *mt, float *ut)
 {
     SH_CHECK_ARG(p);

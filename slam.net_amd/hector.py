@@ -345,6 +345,47 @@ class MapRepMultiMap:
                   rec.ctypes.data_as(C.c_void_p) if beams else None)
         return sums, rec
 
+    def view_gain(self, poses, level, reach, commit=-1, scan=None):
+        """The view gain (slamhip_hs_view_gain; no reference counterpart): the DISTINCT cells of `level` the scan's beams see from each
+        of the B `poses` ((B, 3), window frame, B <= 4096), no further than `reach` cells -> (B,) capi.VIEW_SUMMARY records: n_seen
+        and its split by class, n_new and n_new_unknown against the covered layer as it was before the call.  commit: -1 nothing,
+        -2 every pose's cells join the layer, an index that pose's.  Blocking; it changes nothing of the map."""
+        if scan is not None:
+            self.set_scan(scan)
+        p = capi.f32(poses, (-1, 3))
+        out = np.zeros(p.shape[0], capi.VIEW_SUMMARY)
+        capi.call("slamhip_hs_view_gain", self._h, int(level), int(reach), capi.fptr(p), p.shape[0], int(commit), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def view_select(self, poses, level, reach, k, mode=0, min_gain=1, scan=None):
+        """The greedy choice of views (slamhip_hs_view_select): up to k <= 64 of the B `poses`, each round the pose that adds the most
+        new cells (mode 0) or new unknown cells (mode 1) to the covered layer, ties to the lowest index, until the best adds fewer
+        than min_gain.  -> (order, gain): the chosen pose indices in the order of choice and their gains.  The chosen views are
+        committed to the layer."""
+        if scan is not None:
+            self.set_scan(scan)
+        p = capi.f32(poses, (-1, 3))
+        order = np.zeros(int(k), np.int32); gain = np.zeros(int(k), np.int32); n = C.c_int32()
+        capi.call("slamhip_hs_view_select", self._h, int(level), int(reach), int(mode), int(min_gain), capi.fptr(p), p.shape[0], int(k),
+                  capi.iptr(order), capi.iptr(gain), C.byref(n))
+        assert (order[n.value:] == -1).all() and not gain[n.value:].any()
+        return order[:n.value].copy(), gain[:n.value].copy()
+
+    def covered(self, level, bits=None, clear=False):
+        """The covered layer of `level` (slamhip_hs_view_get_covered) as an (h, capi.view_words(w)) uint32 bitmap (capi.view_unpack
+        makes booleans of it).  bits: set the layer first (slamhip_hs_view_set_covered), from such a bitmap; clear=True: set it empty."""
+        w, h = (int(v) for v in self.Maps[level].Dimensions)
+        if bits is not None or clear:
+            b = None if bits is None else np.ascontiguousarray(bits, np.uint32).reshape(h, capi.view_words(w))
+            capi.call("slamhip_hs_view_set_covered", self._h, int(level), None if b is None else b.ctypes.data_as(C.c_void_p))
+        out = np.empty((h, capi.view_words(w)), np.uint32)
+        capi.call("slamhip_hs_view_get_covered", self._h, int(level), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def view_clear(self):
+        """Free every block of the view gain, the covered layer too (slamhip_hs_view_clear)."""
+        capi.call("slamhip_hs_view_clear", self._h)
+
     def distance_field(self, level, rect, site_mask=2, radius=32, world=False):
         """The distance field of `level` (slamhip_hs_distance_field; no reference counterpart): for every cell of rect = (x, y, w, h),
         window-frame cells of the level, the squared cell distance to the nearest site, capped at radius^2 -> (h, w) uint16.  A site
@@ -693,6 +734,25 @@ class HectorSLAMProcessor:
                   int(level), 1 if world else 0, sums.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p) if beams else None)
         self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
         return sums, rec
+
+    def ViewGain(self, scan, posesWorld, level, reach, commit=-1):
+        """MapRep.view_gain of `scan` at WORLD poses (slamhip_hsproc_view_gain), taken to the window's frame as Trace takes them.
+        MatchPose, LastMapUpdatePose and the update gate are untouched."""
+        p = capi.f32(posesWorld, (-1, 3)); org = capi.f32(scan.Pose[:2])
+        out = np.zeros(p.shape[0], capi.VIEW_SUMMARY)
+        capi.call("slamhip_hsproc_view_gain", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), capi.fptr(p), p.shape[0],
+                  int(level), int(reach), int(commit), out.ctypes.data_as(C.c_void_p))
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
+        return out
+
+    def ViewSelect(self, scan, posesWorld, level, reach, k, mode=0, min_gain=1):
+        """MapRep.view_select of `scan` at WORLD poses (slamhip_hsproc_view_select) -> (order, gain)."""
+        p = capi.f32(posesWorld, (-1, 3)); org = capi.f32(scan.Pose[:2])
+        order = np.zeros(int(k), np.int32); gain = np.zeros(int(k), np.int32); n = C.c_int32()
+        capi.call("slamhip_hsproc_view_select", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), capi.fptr(p), p.shape[0],
+                  int(level), int(reach), int(mode), int(min_gain), int(k), capi.iptr(order), capi.iptr(gain), C.byref(n))
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
+        return order[:n.value].copy(), gain[:n.value].copy()
 
     def DistanceScore(self, scan, posesWorld, level, site_mask=2, radius=32, world=False, points=False):
         """MapRep.distance_score of `scan` at WORLD poses (slamhip_hsproc_distance_score): the poses are taken to the window's frame
