@@ -226,6 +226,37 @@ namespace HectorSLAM.Main
             return sums;
         }
 
+        /// <summary>MapRep.NearestPairs of `scan` at WORLD poses (slamhip_hsproc_nearest_pairs): per pose the nearest site of `level`
+        /// (siteMask 2: mapped obstacles) within `radius` cells of every end cell, as counts and the sums an alignment step needs --
+        /// in window-frame cells -- and when asked for the offsets [2 * (pose * points + point)].  MatchPose, LastMapUpdatePose and
+        /// the update gate are untouched.</summary>
+        public unsafe PairSummary[] NearestPairs(ScanCloud scan, Vector3[] posesWorld, int level, int siteMask, int radius, bool world, bool wantPairs, out short[] pairs)
+        {
+            var sums = new PairSummary[posesWorld.Length];
+            pairs = wantPairs ? new short[2 * (long)posesWorld.Length * scan.Points.Count] : null;
+            fixed (Vector2* p = CollectionsMarshal.AsSpan(scan.Points))
+            fixed (Vector3* q = posesWorld)
+            fixed (PairSummary* s = sums)
+            fixed (short* d = pairs)
+                Native.Check(Native.slamhip_hsproc_nearest_pairs(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), q, posesWorld.Length, level, world ? 1 : 0,
+                                                                 siteMask, radius, s, d));
+            return sums;
+        }
+
+        /// <summary>One point-to-map alignment step of `scan` at a WORLD pose: NearestPairs there, then MapRepMultiMap.AlignStep --
+        /// host arithmetic only -- on the pose in the window's frame (minus (float)Origin * Maps[0].CellLength per axis, as the
+        /// library takes it), handed back as a world pose.  Iteration is the caller's loop: call again with the result until
+        /// summary.ZeroCount == summary.MatchedCount or the step is small enough.  Nothing of the processor changes.</summary>
+        public Vector3 AlignStep(ScanCloud scan, Vector3 poseWorld, int level, out PairSummary summary, int siteMask = 2, int radius = 32, bool world = false)
+        {
+            summary = NearestPairs(scan, new[] { poseWorld }, level, siteMask, radius, world, false, out _)[0];
+            float stm = 1.0f / MapRep.Maps[level].Properties.CellLength;
+            var (ox, oy) = Origin;
+            if (ox == 0 && oy == 0) return MapRepMultiMap.AlignStep(poseWorld, summary, stm);
+            float cell0 = MapRep.Maps[0].Properties.CellLength;
+            return MapRepMultiMap.AlignStep(new Vector3(poseWorld.X - (float)ox * cell0, poseWorld.Y - (float)oy * cell0, poseWorld.Z), summary, stm, poseWorld);
+        }
+
         /// <summary>MapRep.Frontiers in WORLD cells of `level` (slamhip_hsproc_frontiers): seeds, boxes, sums and the summary's map
         /// rectangle are world cells.  centroids receives each cluster's centre in metres, world frame: the mean cell taken to the
         /// window's frame of the level, through the level's cell-to-world transform (cell * CellLength) and back by (float)Origin *

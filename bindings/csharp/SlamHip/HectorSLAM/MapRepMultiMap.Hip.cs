@@ -216,6 +216,75 @@ namespace HectorSLAM.Main
             return sums;
         }
 
+        /// <summary>NearestField / NearestPairs: both components of a pair where no site lies within the radius, and of the
+        /// per-point record of an ignored point.</summary>
+        public const short NearestNone = short.MaxValue, NearestIgnored = short.MinValue;
+
+        /// <summary>The nearest-site field (slamhip_hs_nearest_field; the reference has no counterpart): for every cell of the
+        /// rectangle (x, y, w, h), window-frame cells of `level`, the offset (dx, dy) to the nearest site with dx^2 + dy^2 below
+        /// radius^2 -- ties to the smaller row, then the smaller column -- as [2 * (row * w + column)] and the element behind it;
+        /// NearestNone twice where there is none.  siteMask, radius and world as DistanceField.  Blocking; it changes nothing.</summary>
+        public unsafe short[] NearestField(int level, int x, int y, int w, int h, int siteMask = 2, int radius = 32, bool world = false)
+        {
+            var dxdy = new short[2 * (long)Math.Max(w, 0) * Math.Max(h, 0)];
+            fixed (short* d = dxdy)
+                Native.Check(Native.slamhip_hs_nearest_field(Pyramid.Ptr, level, world ? 1 : 0, siteMask, radius, x, y, w, h, d));
+            return dxdy;
+        }
+
+        /// <summary>The scan-to-map pairs (slamhip_hs_nearest_pairs): the nearest site of the end cell of every point of `scan` at
+        /// each of the poses (window frame).  Returns one summary per pose and, when asked for, the offsets [2 * (pose * points +
+        /// point)] (NearestIgnored twice for an ignored point, NearestNone twice for one without a site within the radius; poses x
+        /// points at most 2^22).</summary>
+        public unsafe PairSummary[] NearestPairs(ScanCloud scan, Vector3[] poses, int level, int siteMask, int radius, bool world, bool wantPairs, out short[] pairs)
+        {
+            SetScan(scan);
+            var sums = new PairSummary[poses.Length];
+            pairs = wantPairs ? new short[2 * (long)poses.Length * scan.Points.Count] : null;
+            fixed (Vector3* p = poses)
+            fixed (PairSummary* s = sums)
+            fixed (short* q = pairs)
+                Native.Check(Native.slamhip_hs_nearest_pairs(Pyramid.Ptr, level, world ? 1 : 0, siteMask, radius, p, poses.Length, s, q));
+            return sums;
+        }
+
+        /// <summary>The nearest-site field of the definition over a caller's class array on the host (slamhip_debug_nearest_field):
+        /// cls is ch rows of cw class bytes (1 occupied, 2 free, 0 neither), class 0 outside.</summary>
+        public static unsafe short[] NearestFieldOf(byte[] cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h)
+        {
+            var dxdy = new short[2 * (long)Math.Max(w, 0) * Math.Max(h, 0)];
+            fixed (byte* c = cls)
+            fixed (short* d = dxdy)
+                Native.Check(Native.slamhip_debug_nearest_field(c, cw, ch, siteMask, radius, x, y, w, h, d));
+            return dxdy;
+        }
+
+        /// <summary>One closed-form 2-D alignment step from ONE summary, host arithmetic only: the rigid motion e' = R(dTheta) e + t,
+        /// in cells, that best takes the matched end cells onto their nearest sites, composed onto `pose` (the frame the summary
+        /// was formed in) through the end cell's own transform e = stm (R(theta) p + T): theta' = theta + dTheta, T' = R(dTheta) T +
+        /// t / stm.  The centred sums n S_ab - S_a S_b are formed exactly (BigInteger), then everything is double, rounded to
+        /// float once.  basePose: the same pose in another frame of the same heading (a processor's world pose): the change T' - T
+        /// is added to it, so a zero step hands it back bit for bit.  MatchedCount 1: a shift alone; 0: the pose as it is.</summary>
+        public static Vector3 AlignStep(Vector3 pose, in PairSummary s, float stm, Vector3? basePose = null)
+        {
+            Vector3 b = basePose ?? pose;
+            long n = s.MatchedCount;
+            if (n < 1) return b;
+            double dTheta = 0.0;
+            if (n >= 2)
+            {
+                BigInteger N = n;
+                var cross = (N * s.SumExQy - (BigInteger)s.SumEx * s.SumQy) - (N * s.SumEyQx - (BigInteger)s.SumEy * s.SumQx);
+                var dot = (N * s.SumExQx - (BigInteger)s.SumEx * s.SumQx) + (N * s.SumEyQy - (BigInteger)s.SumEy * s.SumQy);
+                dTheta = Math.Atan2((double)cross / n, (double)dot / n);
+            }
+            double c = Math.Cos(dTheta), sn = Math.Sin(dTheta);
+            double tx = (s.SumQx - (c * s.SumEx - sn * s.SumEy)) / n;      // mean(q) - R mean(e), divided once: a pure shift comes out exact
+            double ty = (s.SumQy - (sn * s.SumEx + c * s.SumEy)) / n;
+            double x = pose.X, y = pose.Y, k = stm;
+            return new Vector3((float)(b.X + ((c - 1.0) * x - sn * y + tx / k)), (float)(b.Y + (sn * x + (c - 1.0) * y + ty / k)), (float)(b.Z + dTheta));
+        }
+
         /// <summary>The field of the definition over a caller's class array on the host (slamhip_debug_distance_field): cls is ch rows
         /// of cw class bytes (1 occupied, 2 free, 0 neither), class 0 outside.</summary>
         public static unsafe ushort[] DistanceFieldOf(byte[] cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h)

@@ -131,6 +131,20 @@ namespace SlamHip
         public long SumD2;
     }
 
+    /// <summary>slamhip_pair_summary (include/slamhip.h): one pose's scan points against the nearest-site field -- counted, ignored
+    /// and matched points (a site within the radius of the end cell), those whose end cell is a site (ZeroCount), and over the
+    /// matched points the sum of the squared offsets and the sums of the end cells e, their sites q and the four products, in
+    /// window-frame cells of the level: what one closed-form alignment step needs.  4 ints and 9 longs, 88 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PairSummary
+    {
+        public int CountedCount, IgnoredCount;
+        public int MatchedCount, ZeroCount;
+        public long SumD2;
+        public long SumEx, SumEy, SumQx, SumQy;
+        public long SumExQx, SumEyQy, SumExQy, SumEyQx;
+    }
+
     /// <summary>slamhip_frontier_cluster (include/slamhip.h): one connected cluster of frontier cells -- free cells that touch the
     /// unknown -- of one level: its seed (first cell in row-major order), cells, runs, bounding box (inclusive) and the sums of its
     /// cells' coordinates (centroid = sum / cells).  8 ints and 2 longs, 48 bytes.</summary>
@@ -362,6 +376,11 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_distance_score(IntPtr hs, int level, int world, int siteMask, int radius, Vector3* poses, int nPoses,
                                                                               DistanceSummary* summaries, ushort* points);
         [DllImport(Lib)] internal static extern int slamhip_debug_distance_field(byte* cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h, ushort* d2);
+        // the nearest site of every cell and the scan-to-map pairs (no reference counterpart), and the field's host-side hook
+        [DllImport(Lib)] internal static extern int slamhip_hs_nearest_field(IntPtr hs, int level, int world, int siteMask, int radius, int x, int y, int w, int h, short* dxdy);
+        [DllImport(Lib)] internal static extern int slamhip_hs_nearest_pairs(IntPtr hs, int level, int world, int siteMask, int radius, Vector3* poses, int nPoses,
+                                                                             PairSummary* summaries, short* pairs);
+        [DllImport(Lib)] internal static extern int slamhip_debug_nearest_field(byte* cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h, short* dxdy);
         // the frontier cells and their connected clusters (no reference counterpart), and their host-side hook
         [DllImport(Lib)] internal static extern int slamhip_hs_frontiers(IntPtr hs, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
                                                                          int lx, int ly, int lw, int lh, int* labels);
@@ -434,6 +453,8 @@ namespace SlamHip
                                                                          TraceSummary* summaries, TraceBeam* beams);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_distance_score(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int world,
                                                                                   int siteMask, int radius, DistanceSummary* summaries, ushort* pointD2);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_nearest_pairs(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int world,
+                                                                                 int siteMask, int radius, PairSummary* summaries, short* pairs);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_mcl_step(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in MclSpec spec, out MclSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_set_source(IntPtr proc, int level, int ax, int ay, int w, int h, HectorSLAM.Map.LogOddsCell* cells);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_score(IntPtr proc, Vector3* posesWorld, int nPoses, MergeReport* reports);

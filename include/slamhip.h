@@ -1314,6 +1314,66 @@ int32_t slamhip_debug_view(const float *values, int32_t w, int32_t h, float stm,
                            const float *xy, int32_t n_points, int32_t reach, const uint32_t *covered, uint32_t *out_bits,
                            slamhip_view_summary *out_summary);
 
+/* The nearest site of every cell and the scan-to-map pairs (K16; no reference counterpart): WHERE the nearest wall cell lies, not
+ * only how far -- the feature transform of the map.  It gives point-to-map correspondences from up to r cells away (a closed-form
+ * 2-D alignment step from one summary), a gradient of the distance field, and a direction away from the wall.
+ * THE DEFINITION, for level L, world in {0, 1}, site_mask in [1, 7] and radius r in [1, 255].  Classes, sites, M and E, and the end
+ * cell of a scan point are steps 1, 2, 4 and 5 of slamhip_hs_distance_field, unchanged; F is its field.
+ *  1. Nearest site.  For a cell (x, y), N(x, y) is the site (sx, sy) with (sx - x)^2 + (sy - y)^2 < r^2 that minimises the key
+ *     (D2, sy, sx) lexicographically: the squared distance first, then the smaller row, then the smaller column.  The result is the
+ *     offset pair (dx, dy) = (sx - x, sy - y) as two int16_t, |dx|, |dy| <= 254.  If no site has D2 < r^2 the result is NONE =
+ *     (INT16_MAX, INT16_MAX).  By construction dx^2 + dy^2 == F(x, y) wherever F < r^2, and NONE holds exactly where F == r^2.
+ *     Outside E every cell is class 0: the result there is (0, 0) when site_mask & 1 and NONE otherwise, the distance field's
+ *     constant argument.  With bit 0 set the cells outside M are sites and may be the nearest one; the key still decides: a non-site
+ *     cell at M's corner (0, 0) with nothing nearer gets (0, -1), not (-1, 0).
+ *  2. Separable form, exact.  Within one row the site nearest to x minimises D2 for that row, a left/right tie going to the left
+ *     (the smaller sx); across rows equal D2 goes to the smaller sy.  So a row pass that keeps a SIGNED offset o with |o| < r and
+ *     ties to the left, and a column pass that takes the minimum of (o^2 + dy^2, y + dy) over |dy| < r, equal the lexicographic
+ *     arg-min over all sites.
+ *  3. Pairs.  For the scan that was set and a pose P, every counted point (step 5 of slamhip_hs_distance_field; the scan origin
+ *     plays no part) has its end cell e.  The point is MATCHED iff N(e) is not NONE, and then q = e + N(e).  The per-point record
+ *     is (dx, dy): (INT16_MIN, INT16_MIN) for an ignored point, NONE for a counted point that is not matched.
+ *  4. Per pose, slamhip_pair_summary.  Every sum runs over the MATCHED points only; e and q are window-frame cells of the level.
+ *     The sums are accumulated modulo 2^64; nothing wraps for |coordinate| < 2^24 + 255 and at most 16 384 points (a product is
+ *     below 2^49, 2^14 of them below 2^63).  Integer sums are order-free: any reduction tree and any atomic order give the same
+ *     bits.  The library sets no threshold and runs no iteration: the caller's loop does. */
+#define SLAMHIP_NEAREST_NONE 32767         /* INT16_MAX, both components */
+#define SLAMHIP_NEAREST_IGNORED (-32768)   /* INT16_MIN, both components: the per-point record of an ignored point */
+typedef struct slamhip_pair_summary {
+    int32_t n_counted, n_ignored;      /* sum to n_points */
+    int32_t n_matched;                 /* counted points with a site within the radius of their end cell */
+    int32_t n_zero;                    /* matched points with offset (0, 0): the end cell is a site */
+    int64_t sum_d2;                    /* sum of dx^2 + dy^2 over the matched points */
+    int64_t sum_ex, sum_ey, sum_qx, sum_qy;
+    int64_t sum_exqx, sum_eyqy, sum_exqy, sum_eyqx;
+} slamhip_pair_summary;                /* 4 int32 + 9 int64: 88 bytes, no padding */
+/* N of a rectangle: x, y, w, h in window-frame cells of the level, any position (the constant outside E); out_dxdy: h rows of w
+ * pairs (dx, dy) of int16_t.  The launches, on the operator's stream behind every grid update, shift and upload already enqueued:
+ * the lattice search's class map of the level, re-packed on every call (as slamhip_hs_trace packs it), the two launches of the
+ * field over E (rows: one signed int16_t offset per cell; columns: the pair) and a gather of the rectangle: E itself is never
+ * downloaded.  The blocks belong to the hs, are made by the first call and freed by slamhip_hs_destroy; an hs that never asks
+ * allocates nothing, and the distance field's own blocks are not used.  Blocking, with the context's bounded wait; the result comes
+ * back through pinned staging that the library owns.  It reads cell values only, so it works with backing off (world = window),
+ * with slamhip_hs_set_reference_cache on, and after shifts; it changes nothing of the map or of any search.
+ * SLAMHIP_ERR_INVALID, nothing launched: level out of range, world not 0 or 1, site_mask outside [1, 7], radius outside [1, 255],
+ * w or h < 1, w * h > 2^24 (64 MB of staging), E over 2^26 cells (2 + 4 bytes per cell: 384 MB; the message gives E's size, and
+ * for the world this is known only once the world is planned).  A poisoned context: SLAMHIP_ERR_TIMEOUT.  The limits are design
+ * conditions, not measurements. */
+int32_t slamhip_hs_nearest_field(slamhip_hs *hs, int32_t level, int32_t world, int32_t site_mask, int32_t radius,
+                                 int32_t x, int32_t y, int32_t w, int32_t h, int16_t *out_dxdy);
+/* The pairs of the scan that was set, at B poses (poses: B x 3 floats, window frame).  out_summaries: B records.  out_pairs: NULL,
+ * or B x n_points pairs of int16_t, pose-major: step 3's record.  The field is built as for slamhip_hs_nearest_field on every call,
+ * behind a memset of the summaries; then ONE launch, a point per lane, whose workgroups add their partial sums into the summaries
+ * with 64-bit atomic adds.  Everything else as slamhip_hs_nearest_field.  SLAMHIP_ERR_INVALID in addition: B outside [1, 65536],
+ * out_pairs given with B * n_points > 2^22.  SLAMHIP_ERR_STATE: no scan. */
+int32_t slamhip_hs_nearest_pairs(slamhip_hs *hs, int32_t level, int32_t world, int32_t site_mask, int32_t radius,
+                                 const float *poses, int32_t B, slamhip_pair_summary *out_summaries, int16_t *out_pairs);
+/* Test hook (no device involved): N of the definition over cls[cw * ch] (row-major class bits, class 0 outside the array), for the
+ * rectangle x, y, w, h in the array's cells, from the header text the kernels run (hs_nearest.h).  out_dxdy: h rows of w pairs.
+ * SLAMHIP_ERR_INVALID as slamhip_debug_distance_field. */
+int32_t slamhip_debug_nearest_field(const uint8_t *cls, int32_t cw, int32_t ch, int32_t site_mask, int32_t radius,
+                                    int32_t x, int32_t y, int32_t w, int32_t h, int16_t *out_dxdy);
+
 /* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -1553,6 +1613,15 @@ int32_t slamhip_hsproc_view_gain(slamhip_hsproc *p, const float *xy, int32_t n_p
 int32_t slamhip_hsproc_view_select(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
                                    const float *poses_world, int32_t B, int32_t level, int32_t reach, int32_t mode, int32_t min_gain,
                                    int32_t k, int32_t *out_order, int32_t *out_gain, int32_t *out_n);
+/* The scan-to-map pairs through the processor: slamhip_hs_set_scan on the processor's own hs, then slamhip_hs_nearest_pairs at the B
+ * poses of poses_world (B x 3, WORLD frame), each taken to the window's frame as slamhip_hsproc_trace takes them (- (float)origin *
+ * cell0 per axis; the bits themselves while the origin is 0).  The summaries' cell sums stay in window-frame cells of the level.
+ * The processor's stored poses, its update gate and its match report are not touched; the scan that was set is replaced.  Errors as
+ * slamhip_hs_nearest_pairs; a call refused for its level, world, site_mask, radius, B or the 2^22 records leaves the scan that was
+ * set (E's size is known only once the field is planned, behind the new scan). */
+int32_t slamhip_hsproc_nearest_pairs(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
+                                     const float *poses_world, int32_t B, int32_t level, int32_t world, int32_t site_mask,
+                                     int32_t radius, slamhip_pair_summary *out_summaries, int16_t *out_pairs);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

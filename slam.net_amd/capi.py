@@ -115,6 +115,11 @@ DISTANCE_SUMMARY = np.dtype([("n_counted", np.int32), ("n_ignored", np.int32), (
                              ("sum_d2", np.int64)])            # slamhip_distance_summary (include/slamhip.h): 4 int32 + 1 int64, 24 bytes
 assert DISTANCE_SUMMARY.itemsize == 24
 DISTANCE_IGNORED = 0xFFFF                                      # the per-point record of an ignored point
+PAIR_SUMMARY = np.dtype([(n, np.int32) for n in ("n_counted", "n_ignored", "n_matched", "n_zero")] +
+                        [(n, np.int64) for n in ("sum_d2", "sum_ex", "sum_ey", "sum_qx", "sum_qy", "sum_exqx", "sum_eyqy", "sum_exqy",
+                                                 "sum_eyqx")])     # slamhip_pair_summary (include/slamhip.h): 4 int32 + 9 int64, 88 bytes
+assert PAIR_SUMMARY.itemsize == 88
+NEAREST_NONE, NEAREST_IGNORED = 32767, -32768                  # SLAMHIP_NEAREST_NONE / _IGNORED: both components of the pair
 FRONTIER_MAX_CLUSTERS = 65536
 FRONTIER_CLUSTER = np.dtype([("seed_x", np.int32), ("seed_y", np.int32), ("n_cells", np.int32), ("n_runs", np.int32), ("x_min", np.int32),
                              ("y_min", np.int32), ("x_max", np.int32), ("y_max", np.int32), ("sum_x", np.int64),
@@ -221,6 +226,7 @@ def _declare(L):
         "slamhip_debug_trace_lines": (i32, [f, fp, fp, fp, i32, ip]),
         "slamhip_debug_trace_cells": (i32, [i32, i32, i32, i32, ip, i32, ip]),
         "slamhip_debug_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "slamhip_debug_nearest_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "slamhip_debug_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_nav_field": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_rollouts": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, C.c_float, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -318,6 +324,8 @@ def _declare(L):
         "slamhip_hs_trace": (i32, [vp, i32, fp, i32, i32, vp, vp]),
         "slamhip_hs_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "slamhip_hs_distance_score": (i32, [vp, i32, i32, i32, i32, fp, i32, vp, vp]),
+        "slamhip_hs_nearest_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "slamhip_hs_nearest_pairs": (i32, [vp, i32, i32, i32, i32, fp, i32, vp, vp]),
         "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hs_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hs_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -359,6 +367,7 @@ def _declare(L):
         "slamhip_hsproc_relocalise_world": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, wrip]),
         "slamhip_hsproc_trace": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_distance_score": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
+        "slamhip_hsproc_nearest_pairs": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hsproc_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hsproc_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -483,6 +492,18 @@ def debug_distance_field(cls, site_mask, radius, rect):
     x, y, w, h = (int(v) for v in rect)
     out = np.empty((max(h, 0), max(w, 0)), np.uint16)
     call("slamhip_debug_distance_field", c.ctypes.data_as(C.c_void_p), c.shape[1], c.shape[0], int(site_mask), int(radius), x, y, w, h,
+         out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def debug_nearest_field(cls, site_mask, radius, rect):
+    """The nearest-site field of the definition (slamhip_hs_nearest_field) over the (h, w) uint8 array `cls` of class bits, class 0
+    outside it, for rect = (x, y, w, h) in the array's cells (slamhip_debug_nearest_field; no device involved): an (h, w, 2) int16
+    array of offsets (dx, dy), NEAREST_NONE twice where no site lies within the radius."""
+    c = np.ascontiguousarray(cls, np.uint8)
+    x, y, w, h = (int(v) for v in rect)
+    out = np.empty((max(h, 0), max(w, 0), 2), np.int16)
+    call("slamhip_debug_nearest_field", c.ctypes.data_as(C.c_void_p), c.shape[1], c.shape[0], int(site_mask), int(radius), x, y, w, h,
          out.ctypes.data_as(C.c_void_p))
     return out
 

@@ -48,6 +48,7 @@ struct hs_rollout;                         // hs_rollout.hip
 struct hs_mcl;                             // hs_mcl.hip
 struct hs_merge;                           // hs_merge.hip
 struct hs_view;                            // hs_view.hip
+struct hs_nearest;                         // hs_nearest.hip
 struct hs_field;                           // hs_dfield.h
 struct slamhip_hs {
     slamhip_ctx *ctx;
@@ -83,6 +84,7 @@ struct slamhip_hs {
     struct hs_mcl *mcl;                                    // slamhip_hs_mcl_set / _step / _get: the particle set and the step's blocks, made by the first set, kept
     struct hs_merge *mrg;                                  // slamhip_hs_merge_set_source / _score / _apply: the source map and the reports' blocks, made by the first set_source, kept
     struct hs_view *vw;                                    // slamhip_hs_view_gain / _select / _set_covered: the covered layer, the slots and the results' blocks, made by the first call, kept
+    struct hs_nearest *nrs;                                // slamhip_hs_nearest_field / _pairs: the row offsets and the pairs of E and the results' blocks, made by the first call, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -212,3 +214,8 @@ void    hs_view_free(slamhip_hs *hs);       // the covered layer and the blocks 
 int32_t hs_view_check_gain(const slamhip_hs *hs, int32_t level, int32_t reach, int32_t B, int32_t commit, int n_points, bool scan_is_set);
 int32_t hs_view_check_select(const slamhip_hs *hs, int32_t level, int32_t reach, int32_t mode, int32_t min_gain, int32_t B, int32_t k, int n_points,
                              bool scan_is_set);
+// hs_nearest.hip
+void    hs_nr_free(slamhip_hs *hs);         // the blocks of the nearest-site field (the caller has drained the stream)
+// what slamhip_hs_nearest_pairs refuses for its arguments alone (n_points, scan_is_set: as hs_trc_check)
+int32_t hs_nr_check_pairs(int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius, int32_t B, bool want_pairs, int n_points,
+                          bool scan_is_set);

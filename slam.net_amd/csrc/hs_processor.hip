@@ -317,6 +317,19 @@ extern "C" int32_t slamhip_hsproc_distance_score(slamhip_hsproc *p, const float 
     return slamhip_hs_distance_score(p->hs, level, world, site_mask, radius, hsproc_poses_to_window(p, poses_world, B, buf), B, out_summaries, out_points);
 }
 
+// The scan-to-map pairs at world poses: slamhip_hsproc_distance_score's shape.  The summaries' cell sums stay in the window's frame.
+extern "C" int32_t slamhip_hsproc_nearest_pairs(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float *poses_world, int32_t B,
+                                                int32_t level, int32_t world, int32_t site_mask, int32_t radius,
+                                                slamhip_pair_summary *out_summaries, int16_t *out_pairs)
+{
+    SH_CHECK_ARG(p && poses_world && out_summaries);
+    // (what slamhip_hs_nearest_pairs refuses for its arguments alone, ahead of the scan: a refused call leaves the scan that was set)
+    SH_TRY(hs_nr_check_pairs(p->hs->n_levels, level, world, site_mask, radius, B, out_pairs != nullptr, n, false));
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    std::vector<float> buf;
+    return slamhip_hs_nearest_pairs(p->hs, level, world, site_mask, radius, hsproc_poses_to_window(p, poses_world, B, buf), B, out_summaries, out_pairs);
+}
+
 // The frontier clusters in WORLD cells of the level: slamhip_hs_frontiers, the label rectangle taken to the window's frame and every
 // cell field of the results taken back ((origin >> level) per axis; the window's origin is a multiple of 1 << (n_levels - 1)).
 extern "C" int32_t slamhip_hsproc_frontiers(slamhip_hsproc *p, int32_t level, int32_t world, int32_t min_cells, int32_t max_clusters,

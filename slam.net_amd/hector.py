@@ -4,6 +4,7 @@ Mirrors HectorSLAM/Main/MapRepMultiMap.cs, Map/OccGridMap.cs, Matcher/ScanMatche
 Main/HectorSLAMProcessor.cs: same names and argument meaning; all compute is in libslamhip.so.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -43,6 +44,36 @@ def _reloc_info(info):
 
 def _world_reloc_info(info):
     return np.array([tuple(getattr(info, n) for n, _ in capi.WorldRelocInfo._fields_)], capi.WORLD_RELOC_INFO)[0]
+
+
+def align_step(pose, summary, stm, base=None):
+    """One closed-form 2-D alignment step from ONE capi.PAIR_SUMMARY record (slamhip_hs_nearest_pairs) -> (pose', dtheta, (tx, ty)):
+    the rigid motion e' = R(dtheta) e + t, in cells, that best takes the matched end cells e onto their nearest sites q in the least
+    squares sense, composed onto `pose` (the frame the summary was formed in).  Host arithmetic only: the centred sums n S_ab -
+    S_a S_b are formed exactly, as integers, then everything is binary64.  n_matched >= 2: dtheta = atan2(sum(e'x q'y - e'y q'x),
+    sum(e'x q'x + e'y q'y)) over the centred cells; n_matched == 1: dtheta = 0.  t = mean(q) - R(dtheta) mean(e); no matched point:
+    the pose comes back as it is.  The composition follows hs_trace.h's transform, e = stm (R(theta) p + T) for a scan point p and
+    the pose (T, theta): R(dtheta) e + t = stm (R(theta + dtheta) p + R(dtheta) T + t / stm), so theta' = theta + dtheta and
+    T' = R(dtheta) T + t / stm.  base: the same pose in another frame of the same heading (a processor's world pose); the step's
+    change T' - T is added to IT, so a zero step hands `base` back bit for bit.  The result is rounded to binary32 once."""
+    s = summary
+    n = int(s["n_matched"])
+    x, y, th = (float(v) for v in np.asarray(pose, np.float32).reshape(3))
+    bx, by, bth = (x, y, th) if base is None else (float(v) for v in np.asarray(base, np.float32).reshape(3))
+    if n < 1:
+        return np.array([bx, by, bth], np.float32), 0.0, (0.0, 0.0)
+    S = {k: int(s["sum_" + k]) for k in ("ex", "ey", "qx", "qy", "exqx", "eyqy", "exqy", "eyqx")}
+    dth = 0.0
+    if n >= 2:
+        cross = (n * S["exqy"] - S["ex"] * S["qy"]) - (n * S["eyqx"] - S["ey"] * S["qx"])   # n * sum(e'x q'y - e'y q'x), exact
+        dot = (n * S["exqx"] - S["ex"] * S["qx"]) + (n * S["eyqy"] - S["ey"] * S["qy"])     # n * sum(e'x q'x + e'y q'y), exact
+        dth = math.atan2(float(cross) / n, float(dot) / n)
+    c, sn = math.cos(dth), math.sin(dth)
+    tx = (S["qx"] - (c * S["ex"] - sn * S["ey"])) / n               # mean(q) - R mean(e), divided once: a pure shift comes out exact
+    ty = (S["qy"] - (sn * S["ex"] + c * S["ey"])) / n
+    stm = float(np.float32(stm))
+    out = np.array([bx + ((c - 1.0) * x - sn * y + tx / stm), by + (sn * x + (c - 1.0) * y + ty / stm), bth + dth], np.float32)
+    return out, dth, (tx, ty)
 
 
 class ScanCloud:
@@ -417,6 +448,41 @@ class MapRepMultiMap:
                   sums.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p) if points else None)
         return sums, rec
 
+    def nearest_field(self, level, rect, site_mask=2, radius=32, world=False):
+        """The nearest-site field of `level` (slamhip_hs_nearest_field; no reference counterpart): for every cell of rect = (x, y, w,
+        h), window-frame cells of the level, the offset (dx, dy) to the nearest site with dx^2 + dy^2 < radius^2 -- ties to the
+        smaller row, then the smaller column -- -> (h, w, 2) int16, capi.NEAREST_NONE twice where there is none.  site_mask, radius,
+        world and rect as distance_field: dx^2 + dy^2 is that field wherever it is below radius^2.  Blocking, behind everything
+        already enqueued; it changes nothing."""
+        x, y, w, h = (int(v) for v in rect)
+        out = np.empty((max(h, 0), max(w, 0), 2), np.int16)
+        capi.call("slamhip_hs_nearest_field", self._h, int(level), 1 if world else 0, int(site_mask), int(radius), x, y, w, h,
+                  out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def nearest_pairs(self, poses, level, site_mask=2, radius=32, world=False, pairs=False, scan=None):
+        """The scan-to-map pairs (slamhip_hs_nearest_pairs): for each of the B `poses` ((B, 3), window frame) the nearest site of the
+        end cell of every scan point.  -> (summaries, pairs | None): summaries (B,) of capi.PAIR_SUMMARY -- counts, sum_d2 and the
+        sums of e, q and their products over the matched points, what align_step needs; pairs the (B, n_points, 2) int16 offsets
+        when asked for, capi.NEAREST_IGNORED twice for an ignored point, capi.NEAREST_NONE twice for a counted one without a site
+        within the radius (B * n_points <= 2^22).  scan = None: the scan already set through this object."""
+        if scan is not None:
+            self.set_scan(scan)
+        p = capi.f32(poses, (-1, 3))
+        sums = np.zeros(p.shape[0], capi.PAIR_SUMMARY)
+        rec = None
+        if pairs:
+            if self._scan_set is None:
+                raise ValueError("nearest_pairs: pairs=True needs the scan set through this object (set_scan, or scan=)")
+            rec = np.zeros((p.shape[0], self._scan_set[0], 2), np.int16)
+        capi.call("slamhip_hs_nearest_pairs", self._h, int(level), 1 if world else 0, int(site_mask), int(radius), capi.fptr(p), p.shape[0],
+                  sums.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p) if pairs else None)
+        return sums, rec
+
+    def align_step(self, pose, level, summary):
+        """align_step of a window-frame `pose` on `level` from its nearest_pairs summary -> (pose', dtheta, (tx, ty) in cells)."""
+        return align_step(pose, summary, np.float32(1.0) / np.float32(self.Maps[level].CellLength))
+
     def frontiers(self, level, min_cells=1, max_clusters=256, world=False, labels_rect=None):
         """The frontier clusters of `level` (slamhip_hs_frontiers; no reference counterpart): the free cells that touch the unknown,
         grouped under 8-connectivity.  -> (summary, clusters[, labels]): a capi.FRONTIER_SUMMARY record; the kept clusters (n_cells >=
@@ -765,6 +831,36 @@ class HectorSLAMProcessor:
                   rec.ctypes.data_as(C.c_void_p) if points else None)
         self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
         return sums, rec
+
+    def NearestPairs(self, scan, posesWorld, level, site_mask=2, radius=32, world=False, pairs=False):
+        """MapRep.nearest_pairs of `scan` at WORLD poses (slamhip_hsproc_nearest_pairs): the poses are taken to the window's frame as
+        Trace takes them.  -> (summaries, pairs | None); the summaries' cell sums stay window-frame cells of `level`.  MatchPose,
+        LastMapUpdatePose and the update gate are untouched."""
+        p = capi.f32(posesWorld, (-1, 3)); org = capi.f32(scan.Pose[:2])
+        sums = np.zeros(p.shape[0], capi.PAIR_SUMMARY)
+        rec = np.zeros((p.shape[0], scan.Points.shape[0], 2), np.int16) if pairs else None
+        capi.call("slamhip_hsproc_nearest_pairs", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), capi.fptr(p), p.shape[0],
+                  int(level), 1 if world else 0, int(site_mask), int(radius), sums.ctypes.data_as(C.c_void_p),
+                  rec.ctypes.data_as(C.c_void_p) if pairs else None)
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
+        return sums, rec
+
+    def AlignStep(self, scan, poseWorld, level, site_mask=2, radius=32, world=False):
+        """One point-to-map alignment step of `scan` at the WORLD pose poseWorld: NearestPairs at that pose, then align_step -- host
+        arithmetic only -- on the pose in the window's frame (minus (float)origin * cell0 per axis, rounded as the library rounds
+        it), taken back by the same offset.  -> (poseWorld', summary).  Iteration is the caller's loop: call again with the result
+        until summary["n_zero"] == summary["n_matched"] or the step is small enough.  Nothing of the processor changes."""
+        pw = capi.f32(poseWorld, (3,))
+        sums, _ = self.NearestPairs(scan, pw[None, :], level, site_mask=site_mask, radius=radius, world=world)
+        ox, oy = self.get_origin()
+        if not (ox or oy):                                          # (the window has never moved: the two frames are one)
+            return align_step(pw, sums[0], self._stm(level))[0], sums[0]
+        off = self._window_offset()
+        win = np.array([pw[0] - off[0], pw[1] - off[1], pw[2]], np.float32)
+        return align_step(win, sums[0], self._stm(level), base=pw)[0], sums[0]
+
+    def _stm(self, level):
+        return np.float32(1.0) / np.float32(self.MapRep.Maps[level].CellLength)   # ScaleToMap, as the library forms it
 
     def Frontiers(self, level, min_cells=1, max_clusters=256, world=False, labels_rect=None):
         """MapRep.frontiers in WORLD cells of `level` (slamhip_hsproc_frontiers): seeds, boxes, sums, mx0 / my0 and labels_rect are world
