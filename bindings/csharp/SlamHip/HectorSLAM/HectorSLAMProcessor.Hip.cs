@@ -375,6 +375,72 @@ namespace HectorSLAM.Main
             return report;
         }
 
+        /// <summary>MapRep.Hough through the processor (slamhip_hsproc_hough): cells and bins, no pose to convert.</summary>
+        public HoughInfo Hough(int level, int slot = 0, bool world = false, int siteMask = 2, int nAngles = 360, int q = 1, bool wantVotes = false)
+            => MapRep.HoughCall(true, proc.Ptr, level, slot, world, siteMask, nAngles, q, wantVotes);
+
+        /// <summary>MapRep.HoughRotation through the processor (slamhip_hsproc_hough_rotation).</summary>
+        public unsafe ulong[] HoughRotation()
+        {
+            if (MapRep.HoughSlots[0] == null) throw new InvalidOperationException("fill both slots (Hough) first");
+            var cc = new ulong[MapRep.HoughSlots[0].T];
+            fixed (ulong* c = cc)
+                Native.Check(Native.slamhip_hsproc_hough_rotation(proc.Ptr, c));
+            return cc;
+        }
+
+        /// <summary>MapRep.HoughShifts through the processor (slamhip_hsproc_hough_shifts).</summary>
+        public unsafe HoughShift[] HoughShifts(int[] pairs)
+        {
+            var res = new HoughShift[pairs.Length / 2];
+            fixed (int* p = pairs)
+            fixed (HoughShift* r = res)
+                Native.Check(Native.slamhip_hsproc_hough_shifts(proc.Ptr, p, res.Length, r, null));
+            return res;
+        }
+
+        /// <summary>One hypothesis of AlignMaps: the rotation index m (theta = m pi / T), the WORLD pose of the source frame, and its
+        /// merge report.</summary>
+        public struct MapAlignment { public int M; public Vector3 PoseWorld; public MergeReport Report; }
+
+        /// <summary>Align the merge source (MergeSetSource first) with the window's map of its level WITHOUT a scan, by the Hough
+        /// spectrum: both slots filled, the rotation scores' best nRot peaks, each at m and m + T (the pi ambiguity), two row
+        /// correlations per hypothesis in ONE HoughShifts call (rows ka = arg-max HS_d and ka + T/2), the translation from the two
+        /// shifts (MapRepMultiMap.HoughPose) and every hypothesis rated by MergeScore.  Ordered by Report.Joint(1, 1) (occupied on
+        /// occupied) descending, then by index.  Host composition; the library forms no threshold and picks no peak.</summary>
+        public MapAlignment[] AlignMaps(int level, int nAngles = 360, int q = 1, int nRot = 4, int siteMask = 2)
+        {
+            HoughInfo d = Hough(level, 0, false, siteMask, nAngles, q), s = Hough(level, 1, false, siteMask, nAngles, q);
+            int T = nAngles;
+            int[] peaks = MapRepMultiMap.HoughPeaks(HoughRotation(), nRot);
+            int ka = 0;
+            for (int k = 1; k < T; k++) if (d.Spectrum[k] > d.Spectrum[ka]) ka = k;    // (lowest index on ties)
+            int kb = (ka + T / 2) % T;
+            var ms = new int[2 * peaks.Length];
+            var pairs = new int[8 * peaks.Length];
+            for (int i = 0; i < ms.Length; i++) {
+                ms[i] = peaks[i / 2] + (i % 2) * T;
+                pairs[4 * i] = ms[i]; pairs[4 * i + 1] = ka; pairs[4 * i + 2] = ms[i]; pairs[4 * i + 3] = kb;
+            }
+            HoughShift[] recs = HoughShifts(pairs);
+            float stm = 1.0f / MapRep.Maps[level].Properties.CellLength;
+            var (ox, oy) = Origin;
+            float cell0 = MapRep.Maps[0].Properties.CellLength;
+            float offX = ox == 0 && oy == 0 ? 0.0f : (float)ox * cell0, offY = ox == 0 && oy == 0 ? 0.0f : (float)oy * cell0;
+            var poses = new Vector3[ms.Length];
+            for (int i = 0; i < ms.Length; i++) {
+                Vector3 w = MapRepMultiMap.HoughPose(ms[i], recs[2 * i], ka, recs[2 * i + 1], kb, d, s, stm);
+                poses[i] = new Vector3(w.X + offX, w.Y + offY, w.Z);
+            }
+            MergeReport[] reports = MergeScore(poses);
+            var order = new int[ms.Length];
+            for (int i = 0; i < order.Length; i++) order[i] = i;
+            Array.Sort(order, (a, b) => reports[a].Joint(1, 1) != reports[b].Joint(1, 1) ? reports[b].Joint(1, 1).CompareTo(reports[a].Joint(1, 1)) : a.CompareTo(b));
+            var res = new MapAlignment[ms.Length];
+            for (int i = 0; i < res.Length; i++) res[i] = new MapAlignment { M = ms[order[i]], PoseWorld = poses[order[i]], Report = reports[order[i]] };
+            return res;
+        }
+
         /// <summary>MapRep.ViewGain of `scan` at WORLD poses (slamhip_hsproc_view_gain), taken to the window's frame as Trace takes them.
         /// MatchPose, LastMapUpdatePose and the update gate are untouched.</summary>
         public unsafe ViewSummary[] ViewGain(ScanCloud scan, Vector3[] posesWorld, int level, int reach, int commit = -1)

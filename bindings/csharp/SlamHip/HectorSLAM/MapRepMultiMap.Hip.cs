@@ -510,6 +510,93 @@ namespace HectorSLAM.Main
         /// <summary>No source from here on (slamhip_hs_merge_clear_source).</summary>
         public void MergeClearSource() => Native.Check(Native.slamhip_hs_merge_clear_source(Pyramid.Ptr));
 
+        /// <summary>The Hough transform of a map into a slot (slamhip_hs_hough; the reference has no counterpart): slot 0 the map of
+        /// `level` (the window's, or the world rectangle's), slot 1 the merge source (level must be its level, world false).  nAngles a
+        /// multiple of 4 in [4, 1024], bins of 2^q cells.  Blocking; it changes nothing of the map.</summary>
+        public HoughInfo Hough(int level, int slot = 0, bool world = false, int siteMask = 2, int nAngles = 360, int q = 1, bool wantVotes = false)
+            => HoughCall(false, Pyramid.Ptr, level, slot, world, siteMask, nAngles, q, wantVotes);
+
+        internal readonly HoughInfo[] HoughSlots = new HoughInfo[2];       // what the last Hough call of each slot reported
+
+        internal unsafe HoughInfo HoughCall(bool throughProcessor, IntPtr handle, int level, int slot, bool world, int siteMask, int nAngles, int q, bool wantVotes)
+        {
+            var info = stackalloc int[7];
+            var r = new HoughInfo { T = nAngles, Q = q, Spectrum = new ulong[Math.Max(nAngles, 0)] };
+            uint[] votes = wantVotes ? new uint[1 << 24] : null;           // (N is the call's own result: room for the most the limits allow)
+            fixed (ulong* s = r.Spectrum)
+            fixed (uint* v = votes)
+                Native.Check(throughProcessor ? Native.slamhip_hsproc_hough(handle, level, slot, world ? 1 : 0, siteMask, nAngles, q, info, s, v)
+                                              : Native.slamhip_hs_hough(handle, level, slot, world ? 1 : 0, siteMask, nAngles, q, info, s, v));
+            r.W = info[0]; r.H = info[1]; r.X0 = info[2]; r.Y0 = info[3]; r.D = info[4]; r.N = info[5]; r.Sites = info[6];
+            if (wantVotes) { r.Votes = new uint[(long)nAngles * r.N]; Array.Copy(votes, r.Votes, r.Votes.Length); }
+            if (slot == 0 || slot == 1) HoughSlots[slot] = r;
+            return r;
+        }
+
+        /// <summary>The rotation scores CC of the two filled slots (slamhip_hs_hough_rotation): CC peaks where the source frame is
+        /// turned by m pi / T (mod pi) in the destination's frame.</summary>
+        public unsafe ulong[] HoughRotation()
+        {
+            if (HoughSlots[0] == null) throw new InvalidOperationException("fill both slots (Hough) first");
+            var cc = new ulong[HoughSlots[0].T];
+            fixed (ulong* c = cc)
+                Native.Check(Native.slamhip_hs_hough_rotation(Pyramid.Ptr, c));
+            return cc;
+        }
+
+        /// <summary>The row correlations of pairs (m, k), flattened (slamhip_hs_hough_shifts), at most 256 pairs.</summary>
+        public unsafe HoughShift[] HoughShifts(int[] pairs)
+        {
+            var res = new HoughShift[pairs.Length / 2];
+            fixed (int* p = pairs)
+            fixed (HoughShift* r = res)
+                Native.Check(Native.slamhip_hs_hough_shifts(Pyramid.Ptr, p, res.Length, r, null));
+            return res;
+        }
+
+        /// <summary>Free the blocks of the Hough transform (slamhip_hs_hough_clear); both slots are empty afterwards.</summary>
+        public void HoughClear()
+        {
+            Native.Check(Native.slamhip_hs_hough_clear(Pyramid.Ptr));
+            HoughSlots[0] = HoughSlots[1] = null;
+        }
+
+        /// <summary>The rotation hypotheses of AlignMaps from CC: the m with CC[m] > CC[m - 1] and CC[m] >= CC[m + 1], circularly,
+        /// ranked by CC descending then m ascending; the best nRot, or {0} if there is none.</summary>
+        public static int[] HoughPeaks(ulong[] cc, int nRot)
+        {
+            int T = cc.Length;
+            var peaks = new System.Collections.Generic.List<int>();
+            for (int m = 0; m < T; m++)
+                if (cc[m] > cc[(m + T - 1) % T] && cc[m] >= cc[(m + 1) % T]) peaks.Add(m);
+            peaks.Sort((a, b) => cc[a] != cc[b] ? cc[b].CompareTo(cc[a]) : a.CompareTo(b));
+            if (peaks.Count > nRot) peaks.RemoveRange(nRot, peaks.Count - nRot);
+            if (peaks.Count == 0) peaks.Add(0);
+            return peaks.ToArray();
+        }
+
+        /// <summary>The pose (tx, ty, theta) of the source frame in the destination's from the shift records of pairs (m, ka) and
+        /// (m, kb), by the formula of include/slamhip.h (slamhip_hs_hough): binary64 on the host, theta = m pi / T in (-pi, pi].</summary>
+        public static Vector3 HoughPose(int m, HoughShift a, int ka, HoughShift b, int kb, HoughInfo d, HoughInfo s, float stm)
+        {
+            int T = d.T, bin = 1 << d.Q;
+            double theta = m * Math.PI / T;
+            var n = new double[2, 2]; var rhs = new double[2];
+            for (int i = 0; i < 2; i++) {
+                int k = i == 0 ? ka : kb, kk = k - m; bool f = false;
+                while (kk < 0) { kk += T; f = !f; }
+                double psi = k * Math.PI / T;
+                n[i, 0] = Math.Cos(psi); n[i, 1] = Math.Sin(psi);
+                rhs[i] = (double)bin * (i == 0 ? a : b).BestShift + d.X0 * n[i, 0] + d.Y0 * n[i, 1] - s.X0 * Math.Cos(psi - theta) - s.Y0 * Math.Sin(psi - theta)
+                         - d.D + s.D + (f ? bin - 1 - (2 * s.D) % bin : 0);
+            }
+            double det = n[0, 0] * n[1, 1] - n[0, 1] * n[1, 0];
+            double tx = (rhs[0] * n[1, 1] - rhs[1] * n[0, 1]) / det, ty = (n[0, 0] * rhs[1] - n[1, 0] * rhs[0]) / det;
+            double th = Math.IEEERemainder(theta, 2.0 * Math.PI);
+            if (th <= -Math.PI) th += 2.0 * Math.PI;
+            return new Vector3((float)(tx / stm), (float)(ty / stm), (float)th);
+        }
+
         /// <summary>The merge of the definition on the host (slamhip_debug_merge): no device involved.</summary>
         public static unsafe LogOddsCell[] MergeOf(LogOddsCell[] dst, int dw, int dh, LogOddsCell[] src, int ax, int ay, int sw, int sh, Vector3 pose, float stm, int rule,
                                                    float valueLimit, out MergeReport report)

@@ -241,6 +241,24 @@ namespace SlamHip
         public long Joint(int destinationClass, int sourceClass) => JointCounts[3 * destinationClass + sourceClass];
     }
 
+    /// <summary>slamhip_hough_shift (include/slamhip.h): the row correlation of one pair -- the shift at its maximum (ties to the
+    /// smallest), how many shifts reach it, the maximum and the sum over all shifts.  24 bytes, no padding.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct HoughShift
+    {
+        public int BestShift, TieCount;
+        public ulong BestValue, Sum;
+    }
+
+    /// <summary>What slamhip_hs_hough reports of the slot it filled: the map's size and first cell, D = w + h, the bins per angle N,
+    /// the sites, and the spectrum HS (T entries); H (T rows of N) when asked for.</summary>
+    public sealed class HoughInfo
+    {
+        public int W, H, X0, Y0, D, N, Sites, T, Q;
+        public ulong[] Spectrum;
+        public uint[] Votes;
+    }
+
     /// <summary>slamhip_view_summary (include/slamhip.h): the DISTINCT cells one pose's beams see on a level -- the beams by status, the
     /// cut ones, the seen cells and their split by class, and those not in the covered layer.  Ten int32, 40 bytes, no padding.</summary>
     [StructLayout(LayoutKind.Sequential)]
@@ -380,6 +398,11 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_nearest_field(IntPtr hs, int level, int world, int siteMask, int radius, int x, int y, int w, int h, short* dxdy);
         [DllImport(Lib)] internal static extern int slamhip_hs_nearest_pairs(IntPtr hs, int level, int world, int siteMask, int radius, Vector3* poses, int nPoses,
                                                                              PairSummary* summaries, short* pairs);
+        // the Hough transform of a map, the rotation scores and the row correlations (no reference counterpart)
+        [DllImport(Lib)] internal static extern int slamhip_hs_hough(IntPtr hs, int level, int slot, int world, int siteMask, int nAngles, int q, int* info7, ulong* spectrum, uint* votes);
+        [DllImport(Lib)] internal static extern int slamhip_hs_hough_rotation(IntPtr hs, ulong* cc);
+        [DllImport(Lib)] internal static extern int slamhip_hs_hough_shifts(IntPtr hs, int* pairs, int nPairs, HoughShift* shifts, ulong* xc);
+        [DllImport(Lib)] internal static extern int slamhip_hs_hough_clear(IntPtr hs);
         [DllImport(Lib)] internal static extern int slamhip_debug_nearest_field(byte* cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h, short* dxdy);
         // the frontier cells and their connected clusters (no reference counterpart), and their host-side hook
         [DllImport(Lib)] internal static extern int slamhip_hs_frontiers(IntPtr hs, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
@@ -455,6 +478,9 @@ namespace SlamHip
                                                                                   int siteMask, int radius, DistanceSummary* summaries, ushort* pointD2);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_nearest_pairs(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, Vector3* posesWorld, int nPoses, int level, int world,
                                                                                  int siteMask, int radius, PairSummary* summaries, short* pairs);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_hough(IntPtr proc, int level, int slot, int world, int siteMask, int nAngles, int q, int* info7, ulong* spectrum, uint* votes);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_hough_rotation(IntPtr proc, ulong* cc);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_hough_shifts(IntPtr proc, int* pairs, int nPairs, HoughShift* shifts, ulong* xc);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_mcl_step(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in MclSpec spec, out MclSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_set_source(IntPtr proc, int level, int ax, int ay, int w, int h, HectorSLAM.Map.LogOddsCell* cells);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_score(IntPtr proc, Vector3* posesWorld, int nPoses, MergeReport* reports);

@@ -1374,7 +1374,84 @@ int32_t slamhip_hs_nearest_pairs(slamhip_hs *hs, int32_t level, int32_t world, i
 int32_t slamhip_debug_nearest_field(const uint8_t *cls, int32_t cw, int32_t ch, int32_t site_mask, int32_t radius,
                                     int32_t x, int32_t y, int32_t w, int32_t h, int16_t *out_dxdy);
 
-/* MapRepMultiMap.UpdateByScan -> OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
+/* The Hough transform of a map and what a scan-free alignment of two maps takes from it (K17; no reference counterpart).  K14 fuses a
+ * second map at a transform the caller has; K7 and K13 find one only from a scan taken at a known pose in the other map.  Two saved
+ * worlds, or maps of two robots that never exchanged a scan, are aligned by the Hough spectrum (Carpin, "Fast and accurate map merging
+ * for multi-robot systems", 2008): the circular correlation of the two maps' spectra gives the relative rotation, the correlation of
+ * matching Hough rows over rho the translation along that row's direction; slamhip_hs_merge_score then rates the hypotheses.
+ * THE DEFINITION.  The map M is a class map of w x h cells whose first cell is frame cell (x0, y0).  Two slots: slot 0 (destination)
+ * holds level L of the window (world = 0) or of the world rectangle (world = 1), exactly as the lattice search plans it; slot 1
+ * (source) holds the merge source of the hs: its packed classes, w x h, (x0, y0) = (ax, ay).  The sites: site_mask in [1, 7] and the
+ * distance field's rule for which cell is a site, unchanged -- but cells outside M do not exist here: there is no grown E, and bit 0
+ * of the mask makes only M's own class-0 cells sites.  The angle count T is a multiple of 4 in [4, 1024]; the bin width is b = 2^q
+ * cells, q in [0, 3].
+ *  1. Table.  C[0] = 16384, S[0] = 0; C[T/2] = 0, S[T/2] = 16384; for 0 < k < T/2: C[k] = (int)rint(16384 * cos(k pi / T)) and
+ *     S[k] = (int)rint(16384 * sin(k pi / T)), formed in binary64 on the HOST with pi as M_PI and k pi / T as ((double)k * M_PI) /
+ *     (double)T; for T/2 < k < T: C[k] = -C[T - k], S[k] = S[T - k].  The device never forms a sine: the table is an argument of
+ *     the launches.
+ *  2. Vote.  D = w + h, N = ((2 D) >> q) + 1.  A site at array cell (i, j), i in [0, w), j in [0, h), votes once per k into bin
+ *     p = (uint32)(i C[k] + j S[k] + D 16384) >> (14 + q).  The argument is never negative and lies below 2^31 for w, h <= 16384;
+ *     p < N.  H[k][p] is the number of votes, uint32; an entry is at most (2 b + 1) max(w, h) < 2^19.
+ *  3. Spectrum.  HS[k] = sum_p H[k][p]^2, uint64; n_sites = sum_p H[k][p] for every k.
+ *  4. Rotation scores (host arithmetic inside the library; both slots filled with equal L, T, q).  sh_d is the least shift with
+ *     (max_k HS_d[k]) >> sh_d < 2^26, sh_s likewise; CC[m] = sum_k (HS_d[k] >> sh_d) (HS_s[(k - m) mod T] >> sh_s), m in [0, T),
+ *     uint64 (2^52 2^10: nothing wraps).  CC peaks where the source frame is turned by m pi / T (mod pi) in the destination's.
+ *  5. Row correlation of a pair (m, k), m in [0, 2T), k in [0, T).  kk = k - m; add T until kk >= 0, toggling f once per addition
+ *     (0, 1 or 2 additions).  A[p] = H_d[k][p], p in [0, N_d); B[p'] = H_s[kk][f ? N_s - 1 - p' : p'], p' in [0, N_s);
+ *     XC[d] = sum_p' A[p' + d] B[p'] for d in [-(N_s - 1), N_d - 1], terms with p' + d outside A being zero; uint64, nothing
+ *     wraps.  The record: best_shift the arg-max, ties to the smallest d; n_ties how many d reach the maximum (an all-zero XC:
+ *     -(N_s - 1), N_d + N_s - 1, 0); sum = sum_d XC[d] = n_sites_d n_sites_s.
+ * Every quantity is an integer: any vote order, reduction tree or atomic order gives the same bits.  The library forms no
+ * threshold and picks no peak.  From a shift d of pair (m, k), with theta = m pi / T, psi = k pi / T, n(a) = (cos a, sin a), o_d and
+ * o_s the slots' (x0, y0), and the translation t of the source frame in the destination's in cells:
+ *     t . n(psi) = b d + o_d . n(psi) - o_s . n(psi - theta) - D_d + D_s + (f ? b - 1 - ((2 D_s) mod b) : 0)
+ * up to a bin's width (the last term: a flipped row counts its bins from the other end, where the floor of step 2 and N_s - 1 =
+ * (2 D_s) >> q leave that much); two pairs with different k give t. */
+typedef struct slamhip_hough_shift {
+    int32_t best_shift;                /* the arg-max of XC, ties to the smallest d */
+    int32_t n_ties;                    /* how many d reach the maximum */
+    uint64_t best_value;               /* XC[best_shift] */
+    uint64_t sum;                      /* sum_d XC[d] */
+} slamhip_hough_shift;                 /* 24 bytes, no padding */
+/* Fill a slot.  out_info = {w, h, x0, y0, D, N, n_sites}; out_spectrum: uint64[T]; out_H: NULL or uint32[T * N], row k at k * N.  For
+ * slot 1, level must be the source's level and world 0.  On the operator's stream behind everything already enqueued: the table's
+ * copy, for slot 0 the lattice search's class map of the level (re-packed on every call), a memset of H, then k17_vote -- the grid is
+ * (tiles of 64 x 64 cells, chunks of 64 angles); a tile without a site leaves at once; the others list their sites in LDS and keep a
+ * histogram of 96 bins per angle there (a tile's votes at one angle span at most (91 >> q) + 2 bins), a wavefront takes a site and
+ * its lanes the 64 angles, so no two lanes share an address; the non-zero bins go out as 32-bit atomic adds -- and k17_spectrum, a
+ * workgroup per angle.  H, the spectrum and every row's non-zero extent stay in device memory, with a host copy of the spectrum,
+ * until the slot is filled again; slamhip_hs_merge_set_source, _merge_clear_source and slamhip_hs_reset empty slot 1,
+ * slamhip_hs_reset slot 0 too; a refused call leaves the slot as it was.  The blocks belong to the hs, are made by the first call
+ * and freed by slamhip_hs_hough_clear or slamhip_hs_destroy; an hs that never calls it allocates nothing.  Blocking, the context's
+ * bounded wait; results come back through pinned staging.  SLAMHIP_ERR_INVALID, nothing launched: level, slot, world, site_mask, T or
+ * q out of range; slot 1 with world != 0 or a level that is not the source's; w or h above 16384; T * N > 2^24.  SLAMHIP_ERR_STATE:
+ * slot 1 without a source.  A poisoned context: SLAMHIP_ERR_TIMEOUT.  The limits are design conditions, not measurements. */
+int32_t slamhip_hs_hough(slamhip_hs *hs, int32_t level, int32_t slot, int32_t world, int32_t site_mask, int32_t T, int32_t q,
+                         int32_t out_info[7], uint64_t *out_spectrum, uint32_t *out_H);
+/* Step 4: out_cc = uint64[T].  It launches nothing.  SLAMHIP_ERR_STATE unless both slots are filled with equal level, T, q. */
+int32_t slamhip_hs_hough_rotation(slamhip_hs *hs, uint64_t *out_cc);
+/* Step 5 for P pairs (pairs: P x 2 int32_t, (m, k); P in [1, 256]): out_shifts, P records; out_xc: NULL, or the P arrays XC of
+ * N_d + N_s - 1 entries each, one after another, entry d + N_s - 1 the shift d.  k17_xcorr: the grid is (pair, block of 256 shifts);
+ * both rows trimmed to their non-zero extents, B's through LDS in pieces (flipped on the way in), a shift per lane along A,
+ * 32 x 32 -> 64-bit products, a partial record per block; k17_xcorr_finish merges them, a wavefront per pair.  Blocking, as
+ * slamhip_hs_hough.  SLAMHIP_ERR_INVALID, nothing launched: P out of range; an m outside [0, 2T) or a k outside [0, T); out_xc given
+ * with P * (N_d + N_s - 1) > 2^22.  SLAMHIP_ERR_STATE as slamhip_hs_hough_rotation.  A poisoned context: SLAMHIP_ERR_TIMEOUT. */
+int32_t slamhip_hs_hough_shifts(slamhip_hs *hs, const int32_t *pairs, int32_t P, slamhip_hough_shift *out_shifts, uint64_t *out_xc);
+/* Free the unit's blocks; both slots are empty afterwards.  Never fails for an hs that has none. */
+int32_t slamhip_hs_hough_clear(slamhip_hs *hs);
+/* Test hooks (no device involved), each running the header text the kernels run (hs_hough.h) in plain loops.  _table: step 1,
+ * out_cs = int32[2T], C then S.  _hough: steps 1 - 3 over cls[cw * ch] (row-major class bits); out_H uint32[T * N] or NULL,
+ * out_spectrum uint64[T] or NULL, not both NULL; the refusals of slamhip_hs_hough for site_mask, T, q, the size and T * N.
+ * _hough_rotation: step 4 over two spectra of T entries.  _hough_xcorr: step 5 over A[Nd] and the source ROW B[Ns] (the flip is
+ * applied inside); out_xc uint64[Nd + Ns - 1] or NULL; Nd, Ns in [1, 65537]. */
+int32_t slamhip_debug_hough_table(int32_t T, int32_t *out_cs);
+int32_t slamhip_debug_hough(const uint8_t *cls, int32_t cw, int32_t ch, int32_t site_mask, int32_t T, int32_t q, uint32_t *out_H,
+                            uint64_t *out_spectrum);
+int32_t slamhip_debug_hough_rotation(const uint64_t *spectrum_d, const uint64_t *spectrum_s, int32_t T, uint64_t *out_cc);
+int32_t slamhip_debug_hough_xcorr(const uint32_t *A, int32_t Nd, const uint32_t *B, int32_t Ns, int32_t flip, uint64_t *out_xc,
+                                  slamhip_hough_shift *out_shift);
+
+/* MapRepMultiMap.UpdateByScan ->OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
 
@@ -1622,6 +1699,13 @@ int32_t slamhip_hsproc_view_select(slamhip_hsproc *p, const float *xy, int32_t n
 int32_t slamhip_hsproc_nearest_pairs(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
                                      const float *poses_world, int32_t B, int32_t level, int32_t world, int32_t site_mask,
                                      int32_t radius, slamhip_pair_summary *out_summaries, int16_t *out_pairs);
+/* The Hough transform through the processor: slamhip_hs_hough, _hough_rotation and _hough_shifts on the processor's own hs, the
+ * arguments as given (cells and bins have no world pose to convert; out_info's x0, y0 stay window-frame cells).  The processor's
+ * stored poses, its update gate, its match report and the scan that was set are not touched.  Errors as the slamhip_hs_hough* calls. */
+int32_t slamhip_hsproc_hough(slamhip_hsproc *p, int32_t level, int32_t slot, int32_t world, int32_t site_mask, int32_t T, int32_t q,
+                             int32_t out_info[7], uint64_t *out_spectrum, uint32_t *out_H);
+int32_t slamhip_hsproc_hough_rotation(slamhip_hsproc *p, uint64_t *out_cc);
+int32_t slamhip_hsproc_hough_shifts(slamhip_hsproc *p, const int32_t *pairs, int32_t P, slamhip_hough_shift *out_shifts, uint64_t *out_xc);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -158,6 +158,9 @@ MERGE_MAX_CELLS, MERGE_MAX_POSES = 1 << 26, 4096                # the limits of 
 MERGE_ADD, MERGE_FILL, MERGE_REPLACE = 0, 1, 2                  # the rules of slamhip_hs_merge_apply
 MERGE_REPORT = np.dtype([("joint", np.int64, (9,)), ("n_unsourced", np.int64), ("n_changed", np.int64), ("n_clamped", np.int64)])   # slamhip_merge_report
 assert MERGE_REPORT.itemsize == 96
+HOUGH_MAX_T, HOUGH_MAX_Q, HOUGH_MAX_DIM, HOUGH_MAX_BINS, HOUGH_MAX_PAIRS, HOUGH_MAX_XC = 1024, 3, 16384, 1 << 24, 256, 1 << 22   # the limits of slamhip_hs_hough / _hough_shifts
+HOUGH_SHIFT = np.dtype([("best_shift", np.int32), ("n_ties", np.int32), ("best_value", np.uint64), ("sum", np.uint64)])   # slamhip_hough_shift
+assert HOUGH_SHIFT.itemsize == 24
 VIEW_MAX_REACH, VIEW_MAX_POSES, VIEW_MAX_K, VIEW_LDS_WORDS = 4096, 4096, 64, 8704   # the limits of slamhip_hs_view_gain / _view_select; K15_LDS_WORDS
 VIEW_SUMMARY = np.dtype([(n, np.int32) for n in ("n_walked", "n_same", "n_ignored", "n_cut", "n_seen", "n_unknown", "n_free", "n_occupied", "n_new",
                                                  "n_new_unknown")])   # slamhip_view_summary: ten int32, 40 bytes
@@ -227,6 +230,10 @@ def _declare(L):
         "slamhip_debug_trace_cells": (i32, [i32, i32, i32, i32, ip, i32, ip]),
         "slamhip_debug_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "slamhip_debug_nearest_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+        "slamhip_debug_hough_table": (i32, [i32, vp]),
+        "slamhip_debug_hough": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
+        "slamhip_debug_hough_rotation": (i32, [vp, vp, i32, vp]),
+        "slamhip_debug_hough_xcorr": (i32, [vp, i32, vp, i32, i32, vp, vp]),
         "slamhip_debug_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_nav_field": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_rollouts": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, C.c_float, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -326,6 +333,10 @@ def _declare(L):
         "slamhip_hs_distance_score": (i32, [vp, i32, i32, i32, i32, fp, i32, vp, vp]),
         "slamhip_hs_nearest_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "slamhip_hs_nearest_pairs": (i32, [vp, i32, i32, i32, i32, fp, i32, vp, vp]),
+        "slamhip_hs_hough": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "slamhip_hs_hough_rotation": (i32, [vp, vp]),
+        "slamhip_hs_hough_shifts": (i32, [vp, vp, i32, vp, vp]),
+        "slamhip_hs_hough_clear": (i32, [vp]),
         "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hs_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hs_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -368,6 +379,9 @@ def _declare(L):
         "slamhip_hsproc_trace": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_distance_score": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_nearest_pairs": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
+        "slamhip_hsproc_hough": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "slamhip_hsproc_hough_rotation": (i32, [vp, vp]),
+        "slamhip_hsproc_hough_shifts": (i32, [vp, vp, i32, vp, vp]),
         "slamhip_hsproc_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hsproc_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hsproc_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -704,6 +718,123 @@ def debug_merge(dst, src, ax, ay, pose, stm, rule, value_limit):
     call("slamhip_debug_merge", d.ctypes.data_as(vp), d.shape[1], d.shape[0], s.ctypes.data_as(vp), int(ax), int(ay), s.shape[1], s.shape[0],
          fptr(f32(pose, (3,))), C.c_float(stm), int(rule), C.c_float(value_limit), out.ctypes.data_as(vp), rep.ctypes.data_as(vp))
     return out, rep[0]
+
+
+def hough_bins(w, h, q):
+    """D and N of step 2 of slamhip_hs_hough for a w x h map."""
+    D = int(w) + int(h)
+    return D, ((2 * D) >> int(q)) + 1
+
+
+def debug_hough_table(T):
+    """Step 1 of slamhip_hs_hough (slamhip_debug_hough_table) -> (C, S), two (T,) int32 arrays."""
+    cs = np.zeros(2 * int(T), np.int32)
+    call("slamhip_debug_hough_table", int(T), cs.ctypes.data_as(C.c_void_p))
+    return cs[:int(T)].copy(), cs[int(T):].copy()
+
+
+def debug_hough(cls, site_mask, T, q):
+    """Steps 1 - 3 of slamhip_hs_hough over the (h, w) uint8 array `cls` of class bits (slamhip_debug_hough; no device involved)
+    -> (H (T, N) uint32, HS (T,) uint64)."""
+    c = np.ascontiguousarray(cls, np.uint8)
+    _, N = hough_bins(c.shape[1], c.shape[0], q)
+    H = np.zeros((int(T), N), np.uint32); HS = np.zeros(int(T), np.uint64)
+    call("slamhip_debug_hough", c.ctypes.data_as(C.c_void_p), c.shape[1], c.shape[0], int(site_mask), int(T), int(q), H.ctypes.data_as(C.c_void_p),
+         HS.ctypes.data_as(C.c_void_p))
+    return H, HS
+
+
+def debug_hough_rotation(spectrum_d, spectrum_s):
+    """Step 4 of slamhip_hs_hough over two spectra (slamhip_debug_hough_rotation) -> CC (T,) uint64."""
+    a = np.ascontiguousarray(spectrum_d, np.uint64); b = np.ascontiguousarray(spectrum_s, np.uint64)
+    assert a.shape == b.shape and a.ndim == 1
+    cc = np.zeros(a.shape[0], np.uint64)
+    call("slamhip_debug_hough_rotation", a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), a.shape[0], cc.ctypes.data_as(C.c_void_p))
+    return cc
+
+
+def debug_hough_xcorr(A, B, flip):
+    """Step 5 of slamhip_hs_hough over a destination row A and a source ROW B, flipped inside when `flip` (slamhip_debug_hough_xcorr)
+    -> (XC (Nd + Ns - 1,) uint64, a HOUGH_SHIFT record)."""
+    a = np.ascontiguousarray(A, np.uint32); b = np.ascontiguousarray(B, np.uint32)
+    xc = np.zeros(a.shape[0] + b.shape[0] - 1, np.uint64); rec = np.zeros(1, HOUGH_SHIFT)
+    call("slamhip_debug_hough_xcorr", a.ctypes.data_as(C.c_void_p), a.shape[0], b.ctypes.data_as(C.c_void_p), b.shape[0], int(bool(flip)),
+         xc.ctypes.data_as(C.c_void_p), rec.ctypes.data_as(C.c_void_p))
+    return xc, rec[0]
+
+
+def hough_call(name, handle, level, slot, world, site_mask, T, q, want_H):
+    """slamhip_hs_hough / slamhip_hsproc_hough -> (info dict, HS (T,) uint64, H (T, N) uint32 or None).  N is known only from the
+    call's own info, so H is asked for in a second call's worth of room: the buffer is sized by the largest N the limits allow for T."""
+    info = np.zeros(7, np.int32); HS = np.zeros(int(T), np.uint64)
+    H = np.zeros(HOUGH_MAX_BINS, np.uint32) if want_H else None
+    call(name, handle, int(level), int(slot), int(bool(world)) if world in (True, False) else int(world), int(site_mask), int(T), int(q),
+         info.ctypes.data_as(C.c_void_p), HS.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p) if want_H else None)
+    d = dict(zip(("w", "h", "x0", "y0", "D", "N", "n_sites"), (int(v) for v in info)))
+    if want_H:
+        H = H[:int(T) * d["N"]].reshape(int(T), d["N"]).copy()
+    return d, HS, H
+
+
+def hough_shifts_call(name, handle, pairs, n_xc):
+    """slamhip_hs_hough_shifts / slamhip_hsproc_hough_shifts: pairs (P, 2) of (m, k); n_xc: None, or N_d + N_s - 1 to get the XC arrays
+    -> ((P,) HOUGH_SHIFT records, XC (P, n_xc) uint64 or None)."""
+    p = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    rec = np.zeros(p.shape[0], HOUGH_SHIFT)
+    xc = np.zeros((p.shape[0], int(n_xc)), np.uint64) if n_xc else None
+    call(name, handle, p.ctypes.data_as(C.c_void_p), p.shape[0], rec.ctypes.data_as(C.c_void_p), xc.ctypes.data_as(C.c_void_p) if n_xc else None)
+    return rec, xc
+
+
+def hough_peaks(cc, n_rot):
+    """The rotation hypotheses of AlignMaps from CC: the m with CC[m] > CC[m - 1] and CC[m] >= CC[m + 1], circularly, ranked by CC
+    descending then m ascending; the best n_rot, or [0] if there is none."""
+    c = [int(v) for v in cc]
+    T = len(c)
+    peaks = [m for m in range(T) if c[m] > c[m - 1] and c[m] >= c[(m + 1) % T]]
+    peaks.sort(key=lambda m: (-c[m], m))
+    return peaks[:int(n_rot)] or [0]
+
+
+def hough_pose(m, T, q, recs, ks, info_d, info_s, stm):
+    """The pose (tx, ty, theta) of the source frame in the destination's from the two shift records `recs` of pairs (m, ks[0]) and
+    (m, ks[1]), by the formula of include/slamhip.h (slamhip_hs_hough): float64 on the host, theta = m pi / T taken to (-pi, pi]."""
+    b = 1 << int(q)
+    theta = m * math.pi / T
+    rows, rhs = [], []
+    for rec, k in zip(recs, ks):
+        psi = k * math.pi / T
+        kk, f = k - m, 0
+        while kk < 0:
+            kk += T; f ^= 1
+        n_d = (math.cos(psi), math.sin(psi)); n_s = (math.cos(psi - theta), math.sin(psi - theta))
+        r = (b * int(rec["best_shift"]) + info_d["x0"] * n_d[0] + info_d["y0"] * n_d[1] - info_s["x0"] * n_s[0] - info_s["y0"] * n_s[1]
+             - info_d["D"] + info_s["D"] + ((b - 1 - (2 * info_s["D"]) % b) if f else 0))
+        rows.append(n_d); rhs.append(r)
+    det = rows[0][0] * rows[1][1] - rows[0][1] * rows[1][0]
+    tx = (rhs[0] * rows[1][1] - rhs[1] * rows[0][1]) / det
+    ty = (rows[0][0] * rhs[1] - rows[1][0] * rhs[0]) / det
+    th = math.remainder(theta, 2.0 * math.pi)
+    if th <= -math.pi:
+        th += 2.0 * math.pi
+    return tx / stm, ty / stm, th
+
+
+def align_maps(T, q, n_rot, hs_d, hs_s, info_d, info_s, stm, rotation, shifts, score):
+    """The host composition of HectorSLAMProcessor.AlignMaps over three callables -- rotation() -> CC, shifts(pairs) -> HOUGH_SHIFT
+    records, score(poses) -> MERGE_REPORT records -- so that the device calls and the host hooks run the same text.
+    -> a list of dicts (m, pose, shifts, report), ordered by report.joint[4] descending, then by index."""
+    peaks = hough_peaks(rotation(), n_rot)
+    ms = [m + e for m in peaks for e in (0, T)]                            # the pi ambiguity
+    ka = int(np.argmax(np.asarray(hs_d, np.uint64)))                       # (lowest index on ties)
+    kb = (ka + T // 2) % T
+    pairs = np.array([[m, k] for m in ms for k in (ka, kb)], np.int32)
+    recs = shifts(pairs)
+    poses = np.array([hough_pose(m, T, q, (recs[2 * i], recs[2 * i + 1]), (ka, kb), info_d, info_s, stm) for i, m in enumerate(ms)], np.float32)
+    reps = score(poses)
+    out = [{"m": m, "pose": poses[i].copy(), "shifts": (recs[2 * i].copy(), recs[2 * i + 1].copy()), "report": reps[i].copy()} for i, m in enumerate(ms)]
+    out.sort(key=lambda h: -int(h["report"]["joint"][4]))                  # (stable: ties keep the index order)
+    return out
 
 
 def debug_merge_box(pose, stm, ax, ay, sw, sh, x0, y0, x1, y1):

@@ -125,6 +125,7 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
     hs_merge_free(hs);
     hs_view_free(hs);
     hs_nr_free(hs);
+    hs_hg_free(hs);
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
     if (hs->ev_pts) (void)hipEventDestroy(hs->ev_pts);
@@ -152,6 +153,7 @@ extern "C" int32_t slamhip_hs_reset(slamhip_hs *hs)
     SH_HIP(hipStreamSynchronize(hs->ctx->stream));
     hs->win_ox = hs->win_oy = 0;                                           // (slamhip_hs_shift: an empty map has no frame to keep)
     hs_merge_drop_source(hs);                                              // (slamhip_hs_merge_set_source: a source belongs to the map it was to be merged into)
+    hs_hg_drop_slot(hs, 0);                                                // (slamhip_hs_hough: slot 0 held the map that is gone; the source's drop emptied slot 1)
     return SLAMHIP_OK;
 }
 

@@ -49,6 +49,7 @@ struct hs_mcl;                             // hs_mcl.hip
 struct hs_merge;                           // hs_merge.hip
 struct hs_view;                            // hs_view.hip
 struct hs_nearest;                         // hs_nearest.hip
+struct hs_hough;                           // hs_hough.hip
 struct hs_field;                           // hs_dfield.h
 struct slamhip_hs {
     slamhip_ctx *ctx;
@@ -85,6 +86,7 @@ struct slamhip_hs {
     struct hs_merge *mrg;                                  // slamhip_hs_merge_set_source / _score / _apply: the source map and the reports' blocks, made by the first set_source, kept
     struct hs_view *vw;                                    // slamhip_hs_view_gain / _select / _set_covered: the covered layer, the slots and the results' blocks, made by the first call, kept
     struct hs_nearest *nrs;                                // slamhip_hs_nearest_field / _pairs: the row offsets and the pairs of E and the results' blocks, made by the first call, kept
+    struct hs_hough *hgh;                                  // slamhip_hs_hough / _hough_rotation / _hough_shifts: the two slots' votes, spectra and row extents and the results' blocks, made by the first call, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -207,6 +209,9 @@ void    hs_merge_drop_source(slamhip_hs *hs);   // slamhip_hs_reset, slamhip_hs_
 // what slamhip_hs_merge_score and _apply refuse before they launch anything
 int32_t hs_merge_check_score(const slamhip_hs *hs, int32_t B);
 int32_t hs_merge_check_apply(const slamhip_hs *hs, int32_t rule, float value_limit);
+// the merge source's packed classes as a class map whose first cell is source-frame cell (ax, ay), and its level, for another launch
+// on the operator's stream (K17's slot 1); SLAMHIP_ERR_STATE without a source
+int32_t hs_merge_source_map(const slamhip_hs *hs, hs_class_map *M, int *level);
 // hs_view.hip
 void    hs_view_free(slamhip_hs *hs);       // the covered layer and the blocks of the view gain (the caller has drained the stream)
 // what slamhip_hs_view_gain and _view_select refuse for their arguments alone, for a scan of n_points (scan_is_set false: the caller
@@ -219,3 +224,6 @@ void    hs_nr_free(slamhip_hs *hs);         // the blocks of the nearest-site fi
 // what slamhip_hs_nearest_pairs refuses for its arguments alone (n_points, scan_is_set: as hs_trc_check)
 int32_t hs_nr_check_pairs(int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius, int32_t B, bool want_pairs, int n_points,
                           bool scan_is_set);
+// hs_hough.hip
+void    hs_hg_free(slamhip_hs *hs);         // the blocks of the Hough transform (the caller has drained the stream)
+void    hs_hg_drop_slot(slamhip_hs *hs, int slot);   // slamhip_hs_reset (both), slamhip_hs_merge_set_source / _clear_source (slot 1): the slot is empty from here on; the blocks stay

@@ -244,7 +244,21 @@ void hs_merge_free(slamhip_hs *hs)
     hs->mrg = nullptr;
 }
 
-void hs_merge_drop_source(slamhip_hs *hs) { if (hs->mrg) hs->mrg->have = false; }
+void hs_merge_drop_source(slamhip_hs *hs)
+{
+    if (hs->mrg) hs->mrg->have = false;
+    hs_hg_drop_slot(hs, 1);                                                // (K17's slot 1 is the Hough transform of THIS source)
+}
+
+int32_t hs_merge_source_map(const slamhip_hs *hs, hs_class_map *M, int *level)
+{
+    const hs_merge *m = hs->mrg;
+    if (!m || !m->have) SH_FAIL(SLAMHIP_ERR_STATE, "merge: no source (slamhip_hs_merge_set_source first)");
+    M->cls = m->d_cls; M->w = m->S.w; M->h = m->S.h; M->wpr = m->wpr;
+    M->x0 = m->S.ax; M->y0 = m->S.ay;
+    *level = m->level;
+    return SLAMHIP_OK;
+}
 
 extern "C" int32_t slamhip_hs_merge_set_source(slamhip_hs *hs, int32_t level, int32_t ax, int32_t ay, int32_t w, int32_t h, const slamhip_cell *cells)
 {
@@ -258,6 +272,7 @@ extern "C" int32_t slamhip_hs_merge_set_source(slamhip_hs *hs, int32_t level, in
     SH_TRY(hs_unit(&hs->mrg));
     hs_merge *m = hs->mrg;
     m->have = false;                                                       // (no source until this one has landed)
+    hs_hg_drop_slot(hs, 1);
     const size_t n = (size_t)w * h;
     const int wpr = (w + 15) / 16;
     // (the blocks are idle: every call waits for its own launches, and a call that timed out has poisoned the context)

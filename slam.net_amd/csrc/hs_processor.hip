@@ -451,6 +451,26 @@ extern "C" int32_t slamhip_hsproc_merge_apply(slamhip_hsproc *p, const float pos
     return slamhip_hs_merge_apply(p->hs, pose, rule, value_limit, out_report);
 }
 
+// The Hough transform through the processor: cells and bins, no pose to convert -- the calls of the processor's own hs as they are
+extern "C" int32_t slamhip_hsproc_hough(slamhip_hsproc *p, int32_t level, int32_t slot, int32_t world, int32_t site_mask, int32_t T, int32_t q,
+                                        int32_t out_info[7], uint64_t *out_spectrum, uint32_t *out_H)
+{
+    SH_CHECK_ARG(p);
+    return slamhip_hs_hough(p->hs, level, slot, world, site_mask, T, q, out_info, out_spectrum, out_H);
+}
+
+extern "C" int32_t slamhip_hsproc_hough_rotation(slamhip_hsproc *p, uint64_t *out_cc)
+{
+    SH_CHECK_ARG(p);
+    return slamhip_hs_hough_rotation(p->hs, out_cc);
+}
+
+extern "C" int32_t slamhip_hsproc_hough_shifts(slamhip_hsproc *p, const int32_t *pairs, int32_t P, slamhip_hough_shift *out_shifts, uint64_t *out_xc)
+{
+    SH_CHECK_ARG(p);
+    return slamhip_hs_hough_shifts(p->hs, pairs, P, out_shifts, out_xc);
+}
+
 // The view gain through the processor: slamhip_hsproc_trace's shape -- the arguments checked ahead of the scan, the scan set, every
 // pose taken to the window's frame.
 extern "C" int32_t slamhip_hsproc_view_gain(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float *poses_world, int32_t B,

@@ -568,6 +568,46 @@ class MapRepMultiMap:
         """No source from here on (slamhip_hs_merge_clear_source)."""
         capi.call("slamhip_hs_merge_clear_source", self._h)
 
+    def _hough(self, name, handle, level, slot, world, site_mask, T, q, H):
+        info, HS, Hm = capi.hough_call(name, handle, level, slot, world, site_mask, T, q, H)
+        if not hasattr(self, "_hough_info"):
+            self._hough_info = {}
+        self._hough_info[int(slot)] = dict(info, T=int(T), q=int(q), spectrum=HS)
+        return info, HS, Hm
+
+    def hough(self, level, slot=0, world=False, site_mask=2, T=360, q=1, H=False):
+        """The Hough transform of a map into a slot (slamhip_hs_hough; no reference counterpart): slot 0 the map of `level` (the
+        window's, or with `world` the world rectangle's), slot 1 the merge source (level must be its level).  T angles (a multiple of
+        4), bins of 2^q cells.  -> (info, HS, H): info a dict of w, h, x0, y0, D, N, n_sites; HS (T,) uint64 the spectrum; H (T, N)
+        uint32 the votes if asked for, else None.  Blocking; it changes nothing of the map."""
+        return self._hough("slamhip_hs_hough", self._h, level, slot, world, site_mask, T, q, H)
+
+    def _hough_both(self):
+        """What the last fills through this object reported, per slot -- only to size the result arrays: whether the slots ARE filled
+        is the library's to say (SLAMHIP_ERR_STATE).  Unknown: the largest T, and no XC arrays."""
+        info = getattr(self, "_hough_info", {})
+        unknown = {"T": capi.HOUGH_MAX_T, "N": 0}
+        return info.get(0, unknown), info.get(1, unknown)
+
+    def hough_rotation(self):
+        """The rotation scores CC (T,) uint64 of the two filled slots (slamhip_hs_hough_rotation): CC peaks where the source frame is
+        turned by m pi / T (mod pi) in the destination's frame."""
+        d, _ = self._hough_both()
+        cc = np.zeros(d["T"], np.uint64)
+        capi.call("slamhip_hs_hough_rotation", self._h, cc.ctypes.data_as(C.c_void_p))
+        return cc
+
+    def hough_shifts(self, pairs, xc=False):
+        """The row correlations of pairs (P, 2) of (m, k) (slamhip_hs_hough_shifts) -> ((P,) capi.HOUGH_SHIFT records, XC (P, N_d + N_s
+        - 1) uint64 if asked for, else None; entry d + N_s - 1 is the shift d)."""
+        d, s = self._hough_both()
+        return capi.hough_shifts_call("slamhip_hs_hough_shifts", self._h, pairs, d["N"] + s["N"] - 1 if xc and d["N"] and s["N"] else None)
+
+    def hough_clear(self):
+        """Free the blocks of the Hough transform (slamhip_hs_hough_clear); both slots are empty afterwards."""
+        capi.call("slamhip_hs_hough_clear", self._h)
+        self._hough_info = {}
+
     def mcl_get(self, poses=True, acc=True, ancestors=True):
         """The particle set as it stands (slamhip_hs_mcl_get) -> (poses (N, 3) float32, acc (N,) uint64, ancestors (N,) int32 of the
         last step); None for what was not asked for."""
@@ -962,6 +1002,43 @@ class HectorSLAMProcessor:
 
     def merge_clear_source(self):
         self.MapRep.merge_clear_source()
+
+    def hough(self, level, slot=0, world=False, site_mask=2, T=360, q=1, H=False):
+        """MapRep.hough through the processor (slamhip_hsproc_hough): cells and bins, no pose to convert."""
+        return self.MapRep._hough("slamhip_hsproc_hough", self._h, level, slot, world, site_mask, T, q, H)
+
+    def hough_rotation(self):
+        """MapRep.hough_rotation through the processor (slamhip_hsproc_hough_rotation)."""
+        d, _ = self.MapRep._hough_both()
+        cc = np.zeros(d["T"], np.uint64)
+        capi.call("slamhip_hsproc_hough_rotation", self._h, cc.ctypes.data_as(C.c_void_p))
+        return cc
+
+    def hough_shifts(self, pairs, xc=False):
+        """MapRep.hough_shifts through the processor (slamhip_hsproc_hough_shifts)."""
+        d, s = self.MapRep._hough_both()
+        return capi.hough_shifts_call("slamhip_hsproc_hough_shifts", self._h, pairs, d["N"] + s["N"] - 1 if xc and d["N"] and s["N"] else None)
+
+    def AlignMaps(self, level, T=360, q=1, n_rot=4, site_mask=2):
+        """Align the merge source (merge_set_source first) with the window's map of its level WITHOUT a scan, by the Hough spectrum:
+        both slots filled (hough), the rotation scores' best n_rot peaks, each at m and m + T (the pi ambiguity), two row correlations
+        per hypothesis in ONE hough_shifts call (rows ka = arg-max HS_d and ka + T/2), the translation from the two shifts
+        (capi.hough_pose), and every hypothesis rated by merge_score.  -> a list of dicts (m, pose, shifts, report), poses in the
+        WORLD frame, ordered by report.joint[4] (occupied on occupied) descending, then by index.  Host composition
+        (capi.align_maps); the library forms no threshold and picks no peak."""
+        info_d, hs_d, _ = self.hough(level, 0, False, site_mask, T, q)
+        info_s, hs_s, _ = self.hough(level, 1, False, site_mask, T, q)
+        stm = float(np.float32(1.0) / np.float32(self.MapRep.Maps[level].CellLength))
+        off = self._window_offset() if self.get_origin() != (0, 0) else (np.float32(0.0), np.float32(0.0))
+
+        def score(poses):                                                  # (window-frame poses -> world poses, as merge_score takes them)
+            p = poses.copy()
+            p[:, 0] += off[0]; p[:, 1] += off[1]
+            return self.merge_score(p)
+        out = capi.align_maps(int(T), int(q), n_rot, hs_d, hs_s, info_d, info_s, stm, self.hough_rotation, lambda pairs: self.hough_shifts(pairs)[0], score)
+        for h in out:
+            h["pose"][0] += off[0]; h["pose"][1] += off[1]
+        return out
 
     def LocaliseInit(self, poses_world):
         """Start Monte-Carlo localisation: the particle set of the processor's own pyramid (MapRep.mcl_set) from WORLD poses, taken to
