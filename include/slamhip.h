@@ -357,6 +357,15 @@ int32_t slamhip_cs_maps_checksum(slamhip_cs *cs, uint64_t out[2]);
  * the box reasoning holds; the parity tests assert it).  Returns the count accumulated so far. */
 int32_t slamhip_cs_selfcheck_failures(slamhip_cs *cs, uint32_t *out_failures);
 
+/* The whole self-check block, read-only (same copy as slamhip_cs_selfcheck_failures).  The words move only under
+ * SLAMHIP_K1_VERIFY=1 and accumulate over the handle's life:
+ *   [0] failures (the word slamhip_cs_selfcheck_failures returns; must stay 0)
+ *   [1] ray units of SHARED tile steps    [3] ray units of GLOBAL steps    [4] ray units of BAND steps
+ *       (a step of n rays adds 4 n, once per workgroup that runs it)
+ *   [5] search workgroups that found their plan record, [6] that did not (searches launched with a plan only)
+ *   [2], [7] unused (0). */
+int32_t slamhip_cs_selfcheck_counts(slamhip_cs *cs, uint32_t out[8]);
+
 /* Diagnostics of slamhip_cs_scan_search_and_update / slamhip_csproc_update (CoreSLAMProcessor.cs:717-752): the search launch of a scan goes
  * into the stream BEFORE the scan's tables are made and waits for them on the device (DESIGN.md sec.4 "The per-scan flow").
  * out[0] scans searched that way, out[1] such launches abandoned (the last scan's launch layout did not serve the new scan: searched

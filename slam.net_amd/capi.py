@@ -286,6 +286,7 @@ def _declare(L):
         "slamhip_cs_search_and_update_report": (i32, [vp, fp, i32, f, i32, i32, fp, srp]),
         "slamhip_cs_scan_search_and_update_report": (i32, [vp, fp, i32, fp, i32, f, i32, i32, fp, srp]),
         "slamhip_cs_selfcheck_failures": (i32, [vp, P(C.c_uint32)]),
+        "slamhip_cs_selfcheck_counts": (i32, [vp, P(C.c_uint32)]),
         "slamhip_cs_prelaunch_stats": (i32, [vp, P(C.c_uint64)]),
         "slamhip_cs_plan_stats": (i32, [vp, P(C.c_uint64)]),
         "slamhip_cs_prepared_lists": (i32, [vp, P(C.c_uint64), P(C.c_uint64)]),

@@ -302,6 +302,14 @@ class CoreSlamDevice:
         capi.call("slamhip_cs_selfcheck_failures", self._h, C.byref(v))
         return v.value
 
+    @property
+    def selfcheck_counts(self):
+        """The eight self-check words (slamhip_cs_selfcheck_counts): [0] failures, [1] / [3] / [4] ray units of SHARED / GLOBAL / BAND
+        steps, [5] / [6] plan records found / missed; they move under SLAMHIP_K1_VERIFY=1 only."""
+        v = (C.c_uint32 * 8)()
+        capi.call("slamhip_cs_selfcheck_counts", self._h, v)
+        return tuple(int(x) for x in v)
+
     def search_and_update(self, search_pose, hole_width=0.6, quality=50, max_hits=10):
         sp = capi.f32(search_pose)
         pose = np.empty(3, np.float32); d, i = C.c_int32(), C.c_int32()

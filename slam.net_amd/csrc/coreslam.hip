@@ -1576,6 +1576,18 @@ extern "C" int32_t slamhip_cs_selfcheck_failures(slamhip_cs *cs, uint32_t *out)
     return SLAMHIP_OK;
 }
 
+// All eight words of the self-check block (slamhip.h): the same copy, read-only.
+extern "C" int32_t slamhip_cs_selfcheck_counts(slamhip_cs *cs, uint32_t out[8])
+{
+    SH_CHECK_ARG(cs && out);
+    SH_HIP(hipSetDevice(cs->ctx->device));
+    unsigned int *h = (unsigned int *)(cs->h_key + 8);
+    SH_HIP(hipMemcpyAsync(h, cs->d_verify, sizeof(unsigned int) * 8, hipMemcpyDeviceToHost, cs->ctx->stream));
+    SH_HIP(hipStreamSynchronize(cs->ctx->stream));
+    for (int k = 0; k < 8; k++) out[k] = h[k];
+    return SLAMHIP_OK;
+}
+
 // Both map updates of one pose from the caller's (px, py, c, s) at either scale (slamhip.h): enqueued back to back, one wait.
 extern "C" int32_t slamhip_cs_update_maps_pxcs(slamhip_cs *cs, const float pxcs_hole[4], const float pxcs_obstacle[4], float hole_width,
                                                int32_t quality, int32_t max_obstacle_hits)

@@ -150,12 +150,16 @@ __global__ void __launch_bounds__(256)
 k1_reduce(const uint2 *__restrict__ partial, int n_chunks, int count, int n_points, const int *__restrict__ ev_idx,
           int32_t *__restrict__ dist_out, unsigned long long *__restrict__ key_out)
 {
-    __shared__ uint32_t ssum[4][64], scnt[4][64];
+    // (64-bit sums: a wave adds a quarter of the chunks, and from 262 148 rays on a quarter of the rays at 65535 each passes 2^32 --
+    // tests/test_gpu_search_edges.py, e_ray_limit_at_65535: 2^20 rays came out as a quarter of their distance)
+    __shared__ uint64_t ssum[4][64];
+    __shared__ uint32_t scnt[4][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     unsigned long long key = ~0ull;
     for (int base = blockIdx.x * 64; base < count; base += gridDim.x * 64) {
         const int j = base + lane;
-        uint32_t sum = 0, cnt = 0;
+        uint64_t sum = 0;
+        uint32_t cnt = 0;
         if (j < count)
             for (int c = w; c < n_chunks; c += 4) {
                 const uint2 p = partial[(size_t)c * count + j];
@@ -164,7 +168,7 @@ k1_reduce(const uint2 *__restrict__ partial, int n_chunks, int count, int n_poin
         ssum[w][lane] = sum; scnt[w][lane] = cnt;
         __syncthreads();
         if (w == 0 && j < count) {
-            const uint64_t s = (uint64_t)ssum[0][lane] + ssum[1][lane] + ssum[2][lane] + ssum[3][lane];
+            const uint64_t s = ssum[0][lane] + ssum[1][lane] + ssum[2][lane] + ssum[3][lane];
             const uint32_t c = scnt[0][lane] + scnt[1][lane] + scnt[2][lane] + scnt[3][lane];
             const unsigned long long k = k1_finish(s, c, n_points, ev_idx ? ev_idx[j] : j, dist_out);
             key = k < key ? k : key;
@@ -1969,6 +1973,8 @@ static int32_t k1_launch_fallback(slamhip_cs *cs, int mode, const float p[3], in
     int bpc = (int)(((long long)sh_div_up(count, K1_THREADS) * n_rb) / 4096);
     if (bpc < 1) bpc = 1;
     if (bpc > n_rb) bpc = n_rb;
+    static_assert(1023ull * CS_RB_MAX * 65535ull < (1ull << 32), "a chunk's 32-bit partial sum holds 1023 full ray blocks of 65535");
+    if (bpc > 1023) bpc = 1023;                                    // (a chunk's partial sum is 32 bits wide: fewer than 65 537 rays of 65535 each)
     const int n_chunks = sh_div_up(n_rb, bpc);
     SH_TRY(ensure_partial(cs, sizeof(uint2) * (size_t)n_chunks * count));
     {
