@@ -399,6 +399,58 @@ namespace HectorSLAM.Main
             return res;
         }
 
+        /// <summary>One loop candidate: the hit and the pose guess (x_k, y_k, theta_k - Shift * 2 pi / 64) from the keyframe's stored
+        /// WORLD pose.</summary>
+        public struct LoopCandidate { public SigHit Hit; public Vector3 PoseGuess; }
+
+        /// <summary>The signature of `scan` appended to the keyframe store with its WORLD pose (slamhip_hsproc_sig_add;
+        /// MapRep.SigConfigure first).  MatchPose, LastMapUpdatePose and the update gate are untouched.</summary>
+        public unsafe int AddKeyframe(ScanCloud scan, Vector3 poseWorld)
+        {
+            int index;
+            fixed (Vector2* p = CollectionsMarshal.AsSpan(scan.Points))
+                Native.Check(Native.slamhip_hsproc_sig_add(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), poseWorld, out index, null, out _));
+            return index;
+        }
+
+        /// <summary>The keyframes `scan` resembles most over all 64 headings (slamhip_hsproc_sig_query over [0, count -
+        /// excludeRecent)), higher score first.  Candidates only: VerifyLoop checks one against the map.</summary>
+        public unsafe LoopCandidate[] LoopCandidates(ScanCloud scan, int maxHits = 16, int excludeRecent = 0)
+        {
+            var hits = new SigHit[16];
+            int n, last = Math.Max(MapRep.SigCount - excludeRecent, 0);
+            fixed (Vector2* p = CollectionsMarshal.AsSpan(scan.Points))
+            fixed (SigHit* h = hits)
+                Native.Check(Native.slamhip_hsproc_sig_query(proc.Ptr, p, scan.Points.Count, new Vector2(scan.Pose.X, scan.Pose.Y), 0, last, maxHits, h, out n, null, out _));
+            var res = new LoopCandidate[n];
+            for (int i = 0; i < n; i++)
+            {
+                MapRep.SigDownload(hits[i].Index, 1, out _, out Vector3[] pose);
+                double th = Math.IEEERemainder(pose[0].Z - hits[i].Shift * 2.0 * Math.PI / 64.0, 2.0 * Math.PI);
+                if (th <= -Math.PI) th += 2.0 * Math.PI;
+                res[i] = new LoopCandidate { Hit = hits[i], PoseGuess = new Vector3(pose[0].X, pose[0].Y, (float)th) };
+            }
+            return res;
+        }
+
+        /// <summary>MapRep.SigSelf through the processor (slamhip_hsproc_sig_self).</summary>
+        public unsafe SigHit[] SelfLoopCandidates(int first, int last, int minGap)
+        {
+            var hits = new SigHit[Math.Max(last - first, 1)];
+            fixed (SigHit* h = hits)
+                Native.Check(Native.slamhip_hsproc_sig_self(proc.Ptr, first, last, minGap, h));
+            Array.Resize(ref hits, Math.Max(last - first, 0));
+            return hits;
+        }
+
+        /// <summary>Check one loop candidate against the map: Relocalise centred on its pose guess, nothing adopted.  Host
+        /// composition only; the caller judges the report.</summary>
+        public Vector3 VerifyLoop(ScanCloud scan, LoopCandidate candidate, LatticeSpec lattice, int maxHints, out SlamHip.MatchReport report, out RelocInfo info)
+        {
+            lattice.CentreX = candidate.PoseGuess.X; lattice.CentreY = candidate.PoseGuess.Y; lattice.CentreTheta = candidate.PoseGuess.Z;
+            return Relocalise(scan, lattice, maxHints, false, out report, out info);
+        }
+
         /// <summary>One hypothesis of AlignMaps: the rotation index m (theta = m pi / T), the WORLD pose of the source frame, and its
         /// merge report.</summary>
         public struct MapAlignment { public int M; public Vector3 PoseWorld; public MergeReport Report; }

@@ -554,6 +554,93 @@ namespace HectorSLAM.Main
             return res;
         }
 
+        internal int SigRings;                                             // n_ring of the last SigConfigure: sizes the word arrays
+
+        /// <summary>Set the spec of the scan signatures and EMPTY the keyframe store (slamhip_hs_sig_configure; the reference has no
+        /// counterpart): ringCount rings of ringCells cells each, 64 sectors, `scale` cells per metre.</summary>
+        public void SigConfigure(float scale, int ringCount, int ringCells)
+        {
+            var spec = new SigSpec { Scale = scale, RingCount = ringCount, RingCells = ringCells };
+            Native.Check(Native.slamhip_hs_sig_configure(Pyramid.Ptr, spec));
+            SigRings = ringCount;
+        }
+
+        /// <summary>The signature of the scan SetScan took, appended to the store with `pose` (opaque to the library;
+        /// slamhip_hs_sig_add).  Returns the new keyframe's index.</summary>
+        public unsafe int SigAdd(Vector3 pose, out ulong[] signature, out SigInfo info)
+        {
+            signature = new ulong[SigRings];
+            int index;
+            fixed (ulong* s = signature)
+                Native.Check(Native.slamhip_hs_sig_add(Pyramid.Ptr, pose, out index, s, out info));
+            return index;
+        }
+
+        /// <summary>Many scans of a log appended in ONE launch (slamhip_hs_sig_add_scans): scan b is points[offsets[b] .. offsets[b + 1]).
+        /// Returns the first new index.</summary>
+        public unsafe int SigAddScans(Vector2[] points, int[] offsets, Vector3[] poses)
+        {
+            int first;
+            fixed (Vector2* p = points)
+            fixed (int* o = offsets)
+            fixed (Vector3* q = poses)
+                Native.Check(Native.slamhip_hs_sig_add_scans(Pyramid.Ptr, p, o, poses.Length, q, out first));
+            return first;
+        }
+
+        public int SigCount
+        {
+            get { Native.Check(Native.slamhip_hs_sig_count(Pyramid.Ptr, out int n)); return n; }
+        }
+
+        /// <summary>The scan SetScan took against the keyframes [first, last) over all 64 headings (slamhip_hs_sig_query): at most
+        /// maxHits (up to 16) hits, higher score first, then lower index.  Nothing is appended.</summary>
+        public unsafe SigHit[] SigQuery(int first, int last, int maxHits)
+        {
+            var hits = new SigHit[16];
+            int n;
+            fixed (SigHit* h = hits)
+                Native.Check(Native.slamhip_hs_sig_query(Pyramid.Ptr, first, last, maxHits, h, out n, null, out _));
+            Array.Resize(ref hits, n);
+            return hits;
+        }
+
+        /// <summary>Every keyframe i of [first, last) against the keyframes [first, i - minGap] (slamhip_hs_sig_self): one hit per
+        /// keyframe, Index -1 where that range is empty.</summary>
+        public unsafe SigHit[] SigSelf(int first, int last, int minGap)
+        {
+            var hits = new SigHit[Math.Max(last - first, 1)];
+            fixed (SigHit* h = hits)
+                Native.Check(Native.slamhip_hs_sig_self(Pyramid.Ptr, first, last, minGap, h));
+            Array.Resize(ref hits, Math.Max(last - first, 0));
+            return hits;
+        }
+
+        /// <summary>Keyframes [first, first + n) out of the store, key-major words and poses (slamhip_hs_sig_download).</summary>
+        public unsafe void SigDownload(int first, int n, out ulong[] signatures, out Vector3[] poses)
+        {
+            signatures = new ulong[Math.Max(n, 0) * SigRings + 1]; poses = new Vector3[Math.Max(n, 0) + 1];
+            fixed (ulong* s = signatures)
+            fixed (Vector3* p = poses)
+                Native.Check(Native.slamhip_hs_sig_download(Pyramid.Ptr, first, n, s, p));
+            Array.Resize(ref signatures, Math.Max(n, 0) * SigRings); Array.Resize(ref poses, Math.Max(n, 0));
+        }
+
+        /// <summary>Keyframes appended from what SigDownload gave (slamhip_hs_sig_upload); the library counts the bits itself.</summary>
+        public unsafe void SigUpload(ulong[] signatures, Vector3[] poses)
+        {
+            fixed (ulong* s = signatures)
+            fixed (Vector3* p = poses)
+                Native.Check(Native.slamhip_hs_sig_upload(Pyramid.Ptr, poses.Length, s, p));
+        }
+
+        /// <summary>Free the blocks of the scan signatures and forget the spec (slamhip_hs_sig_clear).</summary>
+        public void SigClear()
+        {
+            Native.Check(Native.slamhip_hs_sig_clear(Pyramid.Ptr));
+            SigRings = 0;
+        }
+
         /// <summary>Free the blocks of the Hough transform (slamhip_hs_hough_clear); both slots are empty afterwards.</summary>
         public void HoughClear()
         {

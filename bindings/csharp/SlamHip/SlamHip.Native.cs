@@ -250,6 +250,34 @@ namespace SlamHip
         public ulong BestValue, Sum;
     }
 
+    /// <summary>slamhip_sig_spec (include/slamhip.h): the spec of the scan signatures -- cells per metre, the rings and the cells of a
+    /// ring's width; 64 sectors always.  12 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SigSpec
+    {
+        public float Scale;
+        public int RingCount, RingCells;
+    }
+
+    /// <summary>slamhip_sig_info (include/slamhip.h): the points of a scan, those ignored, those beyond the last ring, and the bits
+    /// set in its signature.  16 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SigInfo
+    {
+        public int PointCount, IgnoredCount, FarCount, SetCount;
+    }
+
+    /// <summary>slamhip_sig_hit (include/slamhip.h): one keyframe a scan resembles -- the score (Jaccard index in 16.16, at most
+    /// 65536), the keyframe's index (-1: none), the shift in sectors (the query's heading is the keyframe's minus Shift * 2 pi / 64),
+    /// the common and the united bits and the keyframe's own.  16 bytes, no padding.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SigHit
+    {
+        public uint Score;
+        public int Index;
+        public short Shift, Inter, Union, KeySetCount;
+    }
+
     /// <summary>What slamhip_hs_hough reports of the slot it filled: the map's size and first cell, D = w + h, the bins per angle N,
     /// the sites, and the spectrum HS (T entries); H (T rows of N) when asked for.</summary>
     public sealed class HoughInfo
@@ -403,6 +431,16 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_hough_rotation(IntPtr hs, ulong* cc);
         [DllImport(Lib)] internal static extern int slamhip_hs_hough_shifts(IntPtr hs, int* pairs, int nPairs, HoughShift* shifts, ulong* xc);
         [DllImport(Lib)] internal static extern int slamhip_hs_hough_clear(IntPtr hs);
+        // scan signatures and the keyframe store for loop candidates (no reference counterpart)
+        [DllImport(Lib)] internal static extern int slamhip_hs_sig_configure(IntPtr hs, in SigSpec spec);
+        [DllImport(Lib)] internal static extern int slamhip_hs_sig_add(IntPtr hs, in Vector3 pose, out int index, ulong* sig, out SigInfo info);
+        [DllImport(Lib)] internal static extern int slamhip_hs_sig_add_scans(IntPtr hs, Vector2* points, int* offsets, int nScans, Vector3* poses, out int first);
+        [DllImport(Lib)] internal static extern int slamhip_hs_sig_query(IntPtr hs, int first, int last, int maxHits, SigHit* hits, out int n, ulong* sig, out SigInfo info);
+        [DllImport(Lib)] internal static extern int slamhip_hs_sig_self(IntPtr hs, int first, int last, int minGap, SigHit* hits);
+        [DllImport(Lib)] internal static extern int slamhip_hs_sig_count(IntPtr hs, out int count);
+        [DllImport(Lib)] internal static extern int slamhip_hs_sig_download(IntPtr hs, int first, int n, ulong* sig, Vector3* poses);
+        [DllImport(Lib)] internal static extern int slamhip_hs_sig_upload(IntPtr hs, int n, ulong* sig, Vector3* poses);
+        [DllImport(Lib)] internal static extern int slamhip_hs_sig_clear(IntPtr hs);
         [DllImport(Lib)] internal static extern int slamhip_debug_nearest_field(byte* cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h, short* dxdy);
         // the frontier cells and their connected clusters (no reference counterpart), and their host-side hook
         [DllImport(Lib)] internal static extern int slamhip_hs_frontiers(IntPtr hs, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
@@ -481,6 +519,11 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_hough(IntPtr proc, int level, int slot, int world, int siteMask, int nAngles, int q, int* info7, ulong* spectrum, uint* votes);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_hough_rotation(IntPtr proc, ulong* cc);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_hough_shifts(IntPtr proc, int* pairs, int nPairs, HoughShift* shifts, ulong* xc);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_sig_add(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in Vector3 poseWorld, out int index, ulong* sig,
+                                                                           out SigInfo info);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_sig_query(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, int first, int last, int maxHits, SigHit* hits,
+                                                                             out int n, ulong* sig, out SigInfo info);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_sig_self(IntPtr proc, int first, int last, int minGap, SigHit* hits);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_mcl_step(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in MclSpec spec, out MclSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_set_source(IntPtr proc, int level, int ax, int ay, int w, int h, HectorSLAM.Map.LogOddsCell* cells);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_score(IntPtr proc, Vector3* posesWorld, int nPoses, MergeReport* reports);

@@ -1460,6 +1460,115 @@ int32_t slamhip_debug_hough_rotation(const uint64_t *spectrum_d, const uint64_t 
 int32_t slamhip_debug_hough_xcorr(const uint32_t *A, int32_t Nd, const uint32_t *B, int32_t Ns, int32_t flip, uint64_t *out_xc,
                                   slamhip_hough_shift *out_shift);
 
+/* Scan signatures and a keyframe store for loop candidates (K18; no reference counterpart).  Every unit above scores a scan against
+ * the MAP; none compares a scan with earlier scans, and the lattice search finds a pose only near a centre the caller supplies.  A
+ * signature is a rotation-invariant summary of one scan: which of n_ring x 64 polar cells round the sensor hold an end point.  A ring
+ * is one 64-bit word, so a turn of the scan by one sector is a rotate of every word by one bit, and two scans are compared over all
+ * 64 headings with AND, rotate and popcount alone.  The store keeps the signatures of keyframes in device memory; a query ranks the
+ * keyframes against the scan that was set, the self search every keyframe against the earlier ones.  The hits are CANDIDATES: the
+ * caller verifies one with slamhip_hs_relocalise round the pose guess (HectorSLAMProcessor.VerifyLoop in the mirrors).
+ * THE DEFINITION.  SLAMHIP_SIG_SECTORS = 64.  The spec: Rg = n_ring in [1, 32]; rc = ring_cells >= 1 with 2 rc Rg <= 32768; scale a
+ * finite binary32 > 0, in cells per metre -- the caller's choice, unrelated to any level of the map.
+ *  1. Table.  For k in [0, 16): C[k] = (int)rint(16384 * cos(a)), S[k] = (int)rint(16384 * sin(a)) with a = ((double)k * M_PI) / 32.0,
+ *     formed in binary64 on the HOST; for k >= 16: C[k] = -S[k - 16], S[k] = C[k - 16], so a quarter turn is exact.  The device never
+ *     forms a sine: the table is an argument of the launches.
+ *  2. Cell of a point.  (px, py) is the scan point slamhip_hs_set_scan took; the scan origin plays no part.  fx = px * scale,
+ *     fy = py * scale, each ONE binary32 multiply rounded on its own.  A point with a NaN or |f| >= 2^14 on either axis is IGNORED.
+ *     u = 2 floor(fx) + 1, v = 2 floor(fy) + 1: odd doubled coordinates -- the cell's centre, never the origin, never on an axis.
+ *  3. Ring.  d2 = u^2 + v^2 (below 2^31); ring = the number of j in [1, Rg] with (2 rc j)^2 <= d2.  ring == Rg: the point is FAR --
+ *     counted, not set.
+ *  4. Sector.  The one k with C[k] v - S[k] u >= 0 and C[k+1 mod 64] v - S[k+1 mod 64] u < 0.  int32; the magnitudes stay below 2^30.
+ *     Exactly one k exists for every odd (u, v) because cross(d_k, d_{k+1}) > 0 for all k (tests/test_hs_sig_abi.py proves it).
+ *  5. Signature.  sig[r], r in [0, Rg), uint64: bit k is set iff some point has (ring r, sector k).  slamhip_sig_info: n_points,
+ *     n_ignored, n_far, n_set = the total popcount (at most 2048).
+ *  6. Match of query q against key k at shift s in [0, 64): inter(s) = sum_r popcount(q[r] & rotl(k[r], s)); shift = the SMALLEST s
+ *     that maximises inter; uni = n_set(q) + n_set(k) - inter; score = uni ? (inter << 16) / uni : 0 -- integer division, at most
+ *     65536 (the Jaccard index of the two bit sets in 16.16 fixed point).  uni falls as inter rises, so the maximal inter is the
+ *     maximal score: one division per pair.  THE SIGN: q == rotl(k, s) means that the query sees everything s sectors FURTHER ROUND
+ *     (counter-clockwise) than the key did, so the query's heading is theta_k - s * 2 pi / 64.
+ *  7. Query over the keyframes with index in [first, last): the B <= 16 best, ordered by higher score, then lower index.  Fewer than B
+ *     keyframes in the range: fewer hits; out_n holds the count.
+ *  8. Self search over [first, last) with min_gap >= 1: for every keyframe i of the range ONE hit, the best j in [first, i - min_gap]
+ *     by rule 7 with B = 1 (query i, key j); index = -1, score = 0 and every other field 0 if that range is empty.
+ * Every quantity behind rule 2's two multiplies is an integer: any order of atomics and reductions gives the same bits.
+ * The self search merges by a 64-bit atomic max on a packed key, low bits first: shift 6 bits, (2^20 - 1 - index) 20 bits, score 17
+ * bits, then one bit every real pair has (an empty slot is 0): 44 bits in all. */
+#define SLAMHIP_SIG_SECTORS 64
+#define SLAMHIP_SIG_MAX_RINGS 32
+#define SLAMHIP_SIG_MAX_HITS 16
+#define SLAMHIP_SIG_MAX_KEYS (1 << 20)
+typedef struct slamhip_sig_spec {
+    float scale;                       /* cells per metre */
+    int32_t n_ring;                    /* Rg */
+    int32_t ring_cells;                /* rc: a ring is rc cells wide */
+} slamhip_sig_spec;                    /* 12 bytes */
+typedef struct slamhip_sig_info {
+    int32_t n_points, n_ignored, n_far, n_set;
+} slamhip_sig_info;                    /* 16 bytes */
+typedef struct slamhip_sig_hit {
+    uint32_t score;                    /* rule 6, at most 65536 */
+    int32_t index;                     /* the keyframe; -1: no hit */
+    int16_t shift, inter, uni, n_set_key;
+} slamhip_sig_hit;                     /* 16 bytes, no padding */
+/* Set the spec and EMPTY the store (signatures of another spec do not compare).  The table goes to device memory here.  The unit's
+ * blocks belong to the hs, are made by this call and later ones and freed by slamhip_hs_sig_clear or slamhip_hs_destroy; an hs that
+ * never calls it allocates nothing.  SLAMHIP_ERR_INVALID: a spec outside the definition's ranges.  Every other slamhip_hs_sig_* call
+ * gives SLAMHIP_ERR_STATE before this one (and after slamhip_hs_sig_clear).  All of them but _sig_count are blocking with the
+ * context's bounded wait (a poisoned context: SLAMHIP_ERR_TIMEOUT), run on the operator's stream behind everything already enqueued
+ * and bring their results back through pinned staging. */
+int32_t slamhip_hs_sig_configure(slamhip_hs *hs, const slamhip_sig_spec *spec);
+/* Rules 2 - 5 over the scan slamhip_hs_set_scan took (no scan, or one of 0 points: the empty signature), appended to the store as
+ * keyframe *out_index = the count before the call.  pose: three floats, opaque to the library, kept on the host and handed back by
+ * slamhip_hs_sig_download.  out_index, out_sig (uint64[n_ring]) and out_info may be NULL.  k18_sig: a workgroup of 256 lanes per
+ * scan, a point per lane and pass; the ring by a hardware square root with an exact integer fix-up, the sector by the quadrant of
+ * the signs and four steps with exact cross products; the words in LDS, filled by 64-bit LDS atomic OR; the counts by ballot.
+ * The store: blocks of 64 keyframes, ring r of a block's 64 keyframes contiguous (sig[block][r][64]), n_set as uint16 beside them;
+ * it grows by whole blocks, the earlier blocks copied as they are.  SLAMHIP_ERR_INVALID: the store holds 2^20 keyframes.
+ * slamhip_hs_reset empties the store and keeps the blocks and the spec; slamhip_hs_shift and the other window calls do not touch it
+ * (the poses are the caller's). */
+int32_t slamhip_hs_sig_add(slamhip_hs *hs, const float pose[3], int32_t *out_index, uint64_t *out_sig, slamhip_sig_info *out_info);
+/* B scans of a log appended in one launch, a workgroup per scan: scan b is the points xy[2 offsets[b]] .. xy[2 offsets[b + 1]) (x, y
+ * pairs), offsets = B + 1 entries, offsets[0] = 0, non-decreasing; poses = B x 3 floats; *out_first (may be NULL) = the first new
+ * index.  The scan that slamhip_hs_set_scan took is not touched.  SLAMHIP_ERR_INVALID, nothing launched: B outside [1, 4096]; bad
+ * offsets; more than 2^24 points; more than 2^20 keyframes afterwards. */
+int32_t slamhip_hs_sig_add_scans(slamhip_hs *hs, const float *xy, const int32_t *offsets /* B + 1 */, int32_t B, const float *poses,
+                                 int32_t *out_first);
+/* Rule 7: the scan slamhip_hs_set_scan took against the keyframes [first, last); nothing is appended.  out_hits: room for B records;
+ * *out_n of them are written.  out_sig (uint64[n_ring]) and out_info: the query's own signature, or NULL.  k18_query: a key per
+ * lane; the 64 rotations of the query are formed once per workgroup in LDS (at most 16 KB) and read as broadcasts; per lane a
+ * running (inter, shift) with ties to the smaller s, then one division; the workgroup's B best by repeated wavefront arg-max on
+ * score << 32 | ~index.  k18_query_finish, one workgroup, merges the workgroups' lists.  SLAMHIP_ERR_INVALID, nothing launched: B
+ * outside [1, 16]; not 0 <= first <= last <= count. */
+int32_t slamhip_hs_sig_query(slamhip_hs *hs, int32_t first, int32_t last, int32_t B, slamhip_sig_hit *out_hits, int32_t *out_n,
+                             uint64_t *out_sig, slamhip_sig_info *out_info);
+/* Rule 8: out_hits = last - first records, record i - first for keyframe i.  k18_self: the grid is (tile of 64 queries, tile of 64
+ * keys); tile pairs wholly above the diagonal band leave at once; the key tile is staged in LDS, a query per lane rotates its own
+ * words in registers; the best per query is merged across key tiles by a 64-bit agent-scope atomic max on the packed key above;
+ * k18_self_finish forms inter and uni of the winners again.  SLAMHIP_ERR_INVALID: min_gap < 1; not 0 <= first <= last <= count. */
+int32_t slamhip_hs_sig_self(slamhip_hs *hs, int32_t first, int32_t last, int32_t min_gap, slamhip_sig_hit *out_hits);
+/* The number of keyframes in the store.  It launches nothing. */
+int32_t slamhip_hs_sig_count(slamhip_hs *hs, int32_t *out_count);
+/* Keyframes [first, first + n) out of the store: sig = uint64[n * n_ring], KEY-MAJOR (keyframe i's words at (i - first) * n_ring), or
+ * NULL; poses = float[n * 3] or NULL; not both NULL.  SLAMHIP_ERR_INVALID: a range outside the store. */
+int32_t slamhip_hs_sig_download(slamhip_hs *hs, int32_t first, int32_t n, uint64_t *sig, float *poses);
+/* n keyframes APPENDED from key-major words and poses (what slamhip_hs_sig_download gave: keyframes are saved and loaded beside a
+ * saved world); the library counts the popcounts itself.  SLAMHIP_ERR_INVALID: n < 0 or more than 2^20 keyframes afterwards. */
+int32_t slamhip_hs_sig_upload(slamhip_hs *hs, int32_t n, const uint64_t *sig, const float *poses);
+/* Free the unit's blocks and forget the spec.  Never fails for an hs that has none. */
+int32_t slamhip_hs_sig_clear(slamhip_hs *hs);
+/* Test hooks (no device involved), each running the header text the kernels run (hs_sig.h) in plain loops.  _table: rule 1, C then
+ * S.  _sig: rules 2 - 5 over n points (x, y pairs); out_info may be NULL; the refusals of slamhip_hs_sig_configure.  _sig_ring: rule 3
+ * as the kernel forms it (square root and fix-up) for n values of d2 >= 0.  _sig_sector: rule 4 as the kernel forms it (quadrant and
+ * four steps) for n pairs (u, v), both odd and within +-32767.  _sig_search: rule 7 (query_sig = uint64[n_ring]) or, with query_sig
+ * NULL, rule 8 (B ignored; *out_n = last - first) over a KEY-MAJOR store of N keyframes with their popcounts n_set;
+ * SLAMHIP_ERR_INVALID as the device calls, and for an n_set entry of the range that disagrees with its words. */
+int32_t slamhip_debug_sig_table(int32_t out_cs[128]);
+int32_t slamhip_debug_sig(const float *xy, int32_t n, const slamhip_sig_spec *spec, uint64_t *out_sig, slamhip_sig_info *out_info);
+int32_t slamhip_debug_sig_ring(const int32_t *d2, int32_t n, int32_t n_ring, int32_t ring_cells, int32_t *out_ring);
+int32_t slamhip_debug_sig_sector(const int32_t *uv, int32_t n, int32_t *out_sector);
+int32_t slamhip_debug_sig_search(const uint64_t *query_sig, const uint64_t *store_sig, const uint16_t *n_set, int32_t N, int32_t n_ring,
+                                 int32_t first, int32_t last, int32_t min_gap, int32_t B, slamhip_sig_hit *out_hits, int32_t *out_n);
+
 /* MapRepMultiMap.UpdateByScan ->OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
@@ -1715,6 +1824,16 @@ int32_t slamhip_hsproc_hough(slamhip_hsproc *p, int32_t level, int32_t slot, int
                              int32_t out_info[7], uint64_t *out_spectrum, uint32_t *out_H);
 int32_t slamhip_hsproc_hough_rotation(slamhip_hsproc *p, uint64_t *out_cc);
 int32_t slamhip_hsproc_hough_shifts(slamhip_hsproc *p, const int32_t *pairs, int32_t P, slamhip_hough_shift *out_shifts, uint64_t *out_xc);
+/* The scan signatures through the processor: the scan set as slamhip_hsproc_relocalise sets it, then slamhip_hs_sig_add /
+ * _sig_query on the processor's own hs; slamhip_hs_sig_self as it is.  pose_world is stored as given (the library never reads it), so
+ * keyframes keep their WORLD poses when the window moves.  What the hs call refuses for the spec's absence, B, the range or a full
+ * store is refused ahead of the scan: such a call leaves the scan that was set.  The processor's stored poses, its update gate and
+ * its match report are not touched.  The store is configured, read and cleared through slamhip_hsproc_hs. */
+int32_t slamhip_hsproc_sig_add(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2], const float pose_world[3],
+                               int32_t *out_index, uint64_t *out_sig, slamhip_sig_info *out_info);
+int32_t slamhip_hsproc_sig_query(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2], int32_t first, int32_t last,
+                                 int32_t B, slamhip_sig_hit *out_hits, int32_t *out_n, uint64_t *out_sig, slamhip_sig_info *out_info);
+int32_t slamhip_hsproc_sig_self(slamhip_hsproc *p, int32_t first, int32_t last, int32_t min_gap, slamhip_sig_hit *out_hits);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -161,6 +161,12 @@ assert MERGE_REPORT.itemsize == 96
 HOUGH_MAX_T, HOUGH_MAX_Q, HOUGH_MAX_DIM, HOUGH_MAX_BINS, HOUGH_MAX_PAIRS, HOUGH_MAX_XC = 1024, 3, 16384, 1 << 24, 256, 1 << 22   # the limits of slamhip_hs_hough / _hough_shifts
 HOUGH_SHIFT = np.dtype([("best_shift", np.int32), ("n_ties", np.int32), ("best_value", np.uint64), ("sum", np.uint64)])   # slamhip_hough_shift
 assert HOUGH_SHIFT.itemsize == 24
+SIG_SECTORS, SIG_MAX_RINGS, SIG_MAX_HITS, SIG_MAX_KEYS, SIG_MAX_SCANS = 64, 32, 16, 1 << 20, 4096   # the limits of slamhip_hs_sig_*
+SIG_SPEC = np.dtype([("scale", np.float32), ("n_ring", np.int32), ("ring_cells", np.int32)])            # slamhip_sig_spec: 12 bytes
+SIG_INFO = np.dtype([(n, np.int32) for n in ("n_points", "n_ignored", "n_far", "n_set")])              # slamhip_sig_info: 16 bytes
+SIG_HIT_DTYPE = np.dtype([("score", np.uint32), ("index", np.int32), ("shift", np.int16), ("inter", np.int16), ("uni", np.int16),
+                          ("n_set_key", np.int16)])                                                     # slamhip_sig_hit: 16 bytes
+assert SIG_SPEC.itemsize == 12 and SIG_INFO.itemsize == 16 and SIG_HIT_DTYPE.itemsize == 16
 VIEW_MAX_REACH, VIEW_MAX_POSES, VIEW_MAX_K, VIEW_LDS_WORDS = 4096, 4096, 64, 8704   # the limits of slamhip_hs_view_gain / _view_select; K15_LDS_WORDS
 VIEW_SUMMARY = np.dtype([(n, np.int32) for n in ("n_walked", "n_same", "n_ignored", "n_cut", "n_seen", "n_unknown", "n_free", "n_occupied", "n_new",
                                                  "n_new_unknown")])   # slamhip_view_summary: ten int32, 40 bytes
@@ -234,6 +240,11 @@ def _declare(L):
         "slamhip_debug_hough": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_debug_hough_rotation": (i32, [vp, vp, i32, vp]),
         "slamhip_debug_hough_xcorr": (i32, [vp, i32, vp, i32, i32, vp, vp]),
+        "slamhip_debug_sig_table": (i32, [vp]),
+        "slamhip_debug_sig": (i32, [vp, i32, vp, vp, vp]),
+        "slamhip_debug_sig_ring": (i32, [vp, i32, i32, i32, vp]),
+        "slamhip_debug_sig_sector": (i32, [vp, i32, vp]),
+        "slamhip_debug_sig_search": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_debug_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_nav_field": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_rollouts": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, C.c_float, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -338,6 +349,15 @@ def _declare(L):
         "slamhip_hs_hough_rotation": (i32, [vp, vp]),
         "slamhip_hs_hough_shifts": (i32, [vp, vp, i32, vp, vp]),
         "slamhip_hs_hough_clear": (i32, [vp]),
+        "slamhip_hs_sig_configure": (i32, [vp, vp]),
+        "slamhip_hs_sig_add": (i32, [vp, fp, ip, vp, vp]),
+        "slamhip_hs_sig_add_scans": (i32, [vp, fp, vp, i32, fp, ip]),
+        "slamhip_hs_sig_query": (i32, [vp, i32, i32, i32, vp, ip, vp, vp]),
+        "slamhip_hs_sig_self": (i32, [vp, i32, i32, i32, vp]),
+        "slamhip_hs_sig_count": (i32, [vp, ip]),
+        "slamhip_hs_sig_download": (i32, [vp, i32, i32, vp, vp]),
+        "slamhip_hs_sig_upload": (i32, [vp, i32, vp, vp]),
+        "slamhip_hs_sig_clear": (i32, [vp]),
         "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hs_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hs_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -383,6 +403,9 @@ def _declare(L):
         "slamhip_hsproc_hough": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hsproc_hough_rotation": (i32, [vp, vp]),
         "slamhip_hsproc_hough_shifts": (i32, [vp, vp, i32, vp, vp]),
+        "slamhip_hsproc_sig_add": (i32, [vp, fp, i32, fp, fp, ip, vp, vp]),
+        "slamhip_hsproc_sig_query": (i32, [vp, fp, i32, fp, i32, i32, i32, vp, ip, vp, vp]),
+        "slamhip_hsproc_sig_self": (i32, [vp, i32, i32, i32, vp]),
         "slamhip_hsproc_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hsproc_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hsproc_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -836,6 +859,107 @@ def align_maps(T, q, n_rot, hs_d, hs_s, info_d, info_s, stm, rotation, shifts, s
     out = [{"m": m, "pose": poses[i].copy(), "shifts": (recs[2 * i].copy(), recs[2 * i + 1].copy()), "report": reps[i].copy()} for i, m in enumerate(ms)]
     out.sort(key=lambda h: -int(h["report"]["joint"][4]))                  # (stable: ties keep the index order)
     return out
+
+
+def sig_spec(scale, n_ring, ring_cells):
+    """A slamhip_sig_spec record (a (1,) SIG_SPEC array; scale rounded to binary32)."""
+    sp = np.zeros(1, SIG_SPEC)
+    sp["scale"] = np.float32(scale); sp["n_ring"] = int(n_ring); sp["ring_cells"] = int(ring_cells)
+    return sp
+
+
+def debug_sig_table():
+    """Rule 1 of slamhip_hs_sig_add (slamhip_debug_sig_table) -> (C, S), two (64,) int32 arrays."""
+    cs = np.zeros(2 * SIG_SECTORS, np.int32)
+    call("slamhip_debug_sig_table", cs.ctypes.data_as(C.c_void_p))
+    return cs[:SIG_SECTORS].copy(), cs[SIG_SECTORS:].copy()
+
+
+def debug_sig(xy, spec):
+    """Rules 2 - 5 of slamhip_hs_sig_add over the (n, 2) float32 points (slamhip_debug_sig; no device involved)
+    -> (sig (n_ring,) uint64, a SIG_INFO record)."""
+    p = f32(xy, (-1, 2))
+    sig = np.zeros(SIG_MAX_RINGS, np.uint64); info = np.zeros(1, SIG_INFO)   # (room for the most a spec the library accepts can ask for)
+    call("slamhip_debug_sig", p.ctypes.data_as(C.c_void_p) if p.shape[0] else None, p.shape[0], spec.ctypes.data_as(C.c_void_p),
+         sig.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p))
+    return sig[:int(spec["n_ring"][0])].copy(), info[0]
+
+
+def debug_sig_ring(d2, n_ring, ring_cells):
+    """Rule 3 as the kernel forms it (slamhip_debug_sig_ring) for an int32 array of d2 -> rings, int32."""
+    d = np.ascontiguousarray(d2, np.int32).ravel()
+    out = np.zeros(d.shape[0], np.int32)
+    call("slamhip_debug_sig_ring", d.ctypes.data_as(C.c_void_p), d.shape[0], int(n_ring), int(ring_cells), out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def debug_sig_sector(uv):
+    """Rule 4 as the kernel forms it (slamhip_debug_sig_sector) for an (n, 2) int32 array of odd (u, v) -> sectors, int32."""
+    a = np.ascontiguousarray(uv, np.int32).reshape(-1, 2)
+    out = np.zeros(a.shape[0], np.int32)
+    call("slamhip_debug_sig_sector", a.ctypes.data_as(C.c_void_p), a.shape[0], out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def sig_popcounts(store):
+    """n_set of every keyframe of a key-major (N, n_ring) uint64 store -> (N,) uint16."""
+    s = np.ascontiguousarray(store, np.uint64)
+    return np.unpackbits(s.view(np.uint8).reshape(s.shape[0], 8 * s.shape[1]), axis=1).sum(axis=1).astype(np.uint16)
+
+
+def debug_sig_search(query, store, first, last, min_gap=1, B=1, n_set=None):
+    """Rule 7 (query a (n_ring,) uint64 array) or rule 8 (query None) of slamhip_hs_sig_add over a key-major (N, n_ring) uint64 store
+    (slamhip_debug_sig_search; no device involved) -> the SIG_HIT_DTYPE records."""
+    s = np.ascontiguousarray(store, np.uint64)
+    assert s.ndim == 2
+    ns = sig_popcounts(s) if n_set is None else np.ascontiguousarray(n_set, np.uint16)
+    q = None if query is None else np.ascontiguousarray(query, np.uint64)
+    room = max(int(B), 1) if q is not None else max(int(last) - int(first), 1)
+    hits = np.zeros(room, SIG_HIT_DTYPE); n = C.c_int32()
+    call("slamhip_debug_sig_search", None if q is None else q.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p) if s.shape[0] else None,
+         ns.ctypes.data_as(C.c_void_p) if s.shape[0] else None, s.shape[0], s.shape[1], int(first), int(last), int(min_gap), int(B),
+         hits.ctypes.data_as(C.c_void_p), C.byref(n))
+    return hits[:n.value].copy()
+
+
+def sig_add_call(name, handle, pose, n_ring, scan=None):
+    """slamhip_hs_sig_add (scan None) / slamhip_hsproc_sig_add (scan = (xy, origin)) -> (index, sig (n_ring,) uint64, SIG_INFO record)."""
+    idx = C.c_int32(); sig = np.zeros(int(n_ring), np.uint64); info = np.zeros(1, SIG_INFO)
+    tail = (fptr(f32(pose, (3,))), C.byref(idx), sig.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p))
+    if scan is None:
+        call(name, handle, *tail)
+    else:
+        xy = f32(scan[0], (-1, 2))
+        call(name, handle, fptr(xy) if xy.shape[0] else None, xy.shape[0], fptr(f32(scan[1], (2,))), *tail)
+    return idx.value, sig, info[0]
+
+
+def sig_query_call(name, handle, first, last, B, n_ring, scan=None):
+    """slamhip_hs_sig_query (scan None) / slamhip_hsproc_sig_query (scan = (xy, origin))
+    -> (hits SIG_HIT_DTYPE, the query's sig (n_ring,) uint64, its SIG_INFO record)."""
+    hits = np.zeros(SIG_MAX_HITS, SIG_HIT_DTYPE); n = C.c_int32(); sig = np.zeros(int(n_ring), np.uint64); info = np.zeros(1, SIG_INFO)
+    tail = (int(first), int(last), int(B), hits.ctypes.data_as(C.c_void_p), C.byref(n), sig.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p))
+    if scan is None:
+        call(name, handle, *tail)
+    else:
+        xy = f32(scan[0], (-1, 2))
+        call(name, handle, fptr(xy) if xy.shape[0] else None, xy.shape[0], fptr(f32(scan[1], (2,))), *tail)
+    return hits[:n.value].copy(), sig, info[0]
+
+
+def sig_self_call(name, handle, first, last, min_gap):
+    """slamhip_hs_sig_self / slamhip_hsproc_sig_self -> (last - first,) SIG_HIT_DTYPE records."""
+    hits = np.zeros(max(int(last) - int(first), 1), SIG_HIT_DTYPE)
+    call(name, handle, int(first), int(last), int(min_gap), hits.ctypes.data_as(C.c_void_p))
+    return hits[:max(int(last) - int(first), 0)].copy()
+
+
+def sig_pose_guess(key_pose, shift):
+    """The pose guess of a hit: the keyframe's position and theta_k - shift * 2 pi / 64 (rule 6's sign), theta taken to (-pi, pi]."""
+    th = math.remainder(float(key_pose[2]) - int(shift) * 2.0 * math.pi / SIG_SECTORS, 2.0 * math.pi)
+    if th <= -math.pi:
+        th += 2.0 * math.pi
+    return float(key_pose[0]), float(key_pose[1]), th
 
 
 def debug_merge_box(pose, stm, ax, ay, sw, sh, x0, y0, x1, y1):

@@ -50,6 +50,7 @@ struct hs_merge;                           // hs_merge.hip
 struct hs_view;                            // hs_view.hip
 struct hs_nearest;                         // hs_nearest.hip
 struct hs_hough;                           // hs_hough.hip
+struct hs_sig;                             // hs_sig.hip
 struct hs_field;                           // hs_dfield.h
 struct slamhip_hs {
     slamhip_ctx *ctx;
@@ -87,6 +88,7 @@ struct slamhip_hs {
     struct hs_view *vw;                                    // slamhip_hs_view_gain / _select / _set_covered: the covered layer, the slots and the results' blocks, made by the first call, kept
     struct hs_nearest *nrs;                                // slamhip_hs_nearest_field / _pairs: the row offsets and the pairs of E and the results' blocks, made by the first call, kept
     struct hs_hough *hgh;                                  // slamhip_hs_hough / _hough_rotation / _hough_shifts: the two slots' votes, spectra and row extents and the results' blocks, made by the first call, kept
+    struct hs_sig *sig;                                    // slamhip_hs_sig_configure / _sig_add / _sig_query / _sig_self: the spec, the store of keyframe signatures, the poses and the results' blocks, made by configure, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -227,3 +229,9 @@ int32_t hs_nr_check_pairs(int n_levels, int32_t level, int32_t world, int32_t si
 // hs_hough.hip
 void    hs_hg_free(slamhip_hs *hs);         // the blocks of the Hough transform (the caller has drained the stream)
 void    hs_hg_drop_slot(slamhip_hs *hs, int slot);   // slamhip_hs_reset (both), slamhip_hs_merge_set_source / _clear_source (slot 1): the slot is empty from here on; the blocks stay
+// hs_sig.hip
+void    hs_sg_free(slamhip_hs *hs);         // the store and the blocks of the scan signatures (the caller has drained the stream)
+void    hs_sg_reset(slamhip_hs *hs);        // slamhip_hs_reset: the store is empty from here on; the blocks and the spec stay
+// what slamhip_hs_sig_add and _sig_query refuse before they launch anything
+int32_t hs_sg_check_add(const slamhip_hs *hs);
+int32_t hs_sg_check_query(const slamhip_hs *hs, int32_t first, int32_t last, int32_t B);

@@ -471,6 +471,33 @@ extern "C" int32_t slamhip_hsproc_hough_shifts(slamhip_hsproc *p, const int32_t 
     return slamhip_hs_hough_shifts(p->hs, pairs, P, out_shifts, out_xc);
 }
 
+// The scan signatures through the processor: the scan set as slamhip_hsproc_relocalise sets it -- what the hs call refuses for its
+// arguments or the store's state ahead of it: a refused call leaves the scan that was set -- then the call of the processor's own hs.
+// The pose is the caller's WORLD pose, stored as given.
+extern "C" int32_t slamhip_hsproc_sig_add(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float pose_world[3], int32_t *out_index,
+                                          uint64_t *out_sig, slamhip_sig_info *out_info)
+{
+    SH_CHECK_ARG(p && pose_world);
+    SH_TRY(hs_sg_check_add(p->hs));
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    return slamhip_hs_sig_add(p->hs, pose_world, out_index, out_sig, out_info);
+}
+
+extern "C" int32_t slamhip_hsproc_sig_query(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], int32_t first, int32_t last, int32_t B,
+                                            slamhip_sig_hit *out_hits, int32_t *out_n, uint64_t *out_sig, slamhip_sig_info *out_info)
+{
+    SH_CHECK_ARG(p && out_hits && out_n);
+    SH_TRY(hs_sg_check_query(p->hs, first, last, B));
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    return slamhip_hs_sig_query(p->hs, first, last, B, out_hits, out_n, out_sig, out_info);
+}
+
+extern "C" int32_t slamhip_hsproc_sig_self(slamhip_hsproc *p, int32_t first, int32_t last, int32_t min_gap, slamhip_sig_hit *out_hits)
+{
+    SH_CHECK_ARG(p);
+    return slamhip_hs_sig_self(p->hs, first, last, min_gap, out_hits);
+}
+
 // The view gain through the processor: slamhip_hsproc_trace's shape -- the arguments checked ahead of the scan, the scan set, every
 // pose taken to the window's frame.
 extern "C" int32_t slamhip_hsproc_view_gain(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float *poses_world, int32_t B,

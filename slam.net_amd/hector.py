@@ -608,6 +608,69 @@ class MapRepMultiMap:
         capi.call("slamhip_hs_hough_clear", self._h)
         self._hough_info = {}
 
+    def SigConfigure(self, scale, n_ring, ring_cells):
+        """Set the spec of the scan signatures and EMPTY the keyframe store (slamhip_hs_sig_configure; no reference counterpart):
+        n_ring rings of ring_cells cells each, 64 sectors, `scale` cells per metre -- the caller's choice, unrelated to any level."""
+        sp = capi.sig_spec(scale, n_ring, ring_cells)
+        capi.call("slamhip_hs_sig_configure", self._h, sp.ctypes.data_as(C.c_void_p))
+        self._sig_rings = int(n_ring)
+
+    def _sig_n_ring(self):
+        """n_ring of the last SigConfigure through this object -- only to size the result arrays; without one the largest."""
+        return getattr(self, "_sig_rings", capi.SIG_MAX_RINGS)
+
+    def SigAdd(self, pose):
+        """The signature of the scan set_scan took, appended to the store with `pose` (opaque to the library; slamhip_hs_sig_add)
+        -> (index, sig (n_ring,) uint64, a capi.SIG_INFO record)."""
+        return capi.sig_add_call("slamhip_hs_sig_add", self._h, pose, self._sig_n_ring())
+
+    def SigAddScans(self, scans, poses):
+        """Many scans of a log appended in ONE launch (slamhip_hs_sig_add_scans): scans a list of (n_i, 2) point arrays, poses (B, 3)
+        -> the first new index.  The scan that set_scan took is not touched."""
+        pts = [capi.f32(s, (-1, 2)) for s in scans]
+        off = np.zeros(len(pts) + 1, np.int32)
+        off[1:] = np.cumsum([p.shape[0] for p in pts])
+        xy = np.ascontiguousarray(np.concatenate(pts, axis=0)) if pts and off[-1] else np.zeros((0, 2), np.float32)
+        p = capi.f32(poses, (-1, 3))
+        assert p.shape[0] == len(pts)
+        first = C.c_int32()
+        capi.call("slamhip_hs_sig_add_scans", self._h, capi.fptr(xy) if xy.shape[0] else None, off.ctypes.data_as(C.c_void_p), len(pts), capi.fptr(p),
+                  C.byref(first))
+        return first.value
+
+    def SigCount(self):
+        n = C.c_int32()
+        capi.call("slamhip_hs_sig_count", self._h, C.byref(n))
+        return n.value
+
+    def SigQuery(self, B=capi.SIG_MAX_HITS, first=0, last=None):
+        """The scan set_scan took against the keyframes [first, last) over all 64 headings (slamhip_hs_sig_query); nothing is appended
+        -> (hits, the query's sig, its info): hits capi.SIG_HIT_DTYPE records, higher score first, then lower index."""
+        return capi.sig_query_call("slamhip_hs_sig_query", self._h, first, self.SigCount() if last is None else last, B, self._sig_n_ring())
+
+    def SigSelf(self, min_gap, first=0, last=None):
+        """Every keyframe i of [first, last) against the keyframes [first, i - min_gap] (slamhip_hs_sig_self) -> one hit per keyframe,
+        index -1 where that range is empty."""
+        return capi.sig_self_call("slamhip_hs_sig_self", self._h, first, self.SigCount() if last is None else last, min_gap)
+
+    def SigDownload(self, first=0, n=None):
+        """Keyframes [first, first + n) out of the store (slamhip_hs_sig_download) -> (sig (n, n_ring) uint64 key-major, poses (n, 3))."""
+        n = self.SigCount() - int(first) if n is None else int(n)
+        sig = np.zeros((max(n, 0), self._sig_n_ring()), np.uint64); poses = np.zeros((max(n, 0), 3), np.float32)
+        capi.call("slamhip_hs_sig_download", self._h, int(first), n, sig.ctypes.data_as(C.c_void_p), poses.ctypes.data_as(C.c_void_p))
+        return sig, poses
+
+    def SigUpload(self, sig, poses):
+        """Keyframes appended from what SigDownload gave (slamhip_hs_sig_upload); the library counts the popcounts itself."""
+        s = np.ascontiguousarray(sig, np.uint64).reshape(-1, self._sig_n_ring()); p = capi.f32(poses, (-1, 3))
+        assert s.shape[0] == p.shape[0]
+        capi.call("slamhip_hs_sig_upload", self._h, s.shape[0], s.ctypes.data_as(C.c_void_p), capi.fptr(p))
+
+    def SigClear(self):
+        """Free the blocks of the scan signatures and forget the spec (slamhip_hs_sig_clear)."""
+        capi.call("slamhip_hs_sig_clear", self._h)
+        self.__dict__.pop("_sig_rings", None)
+
     def mcl_get(self, poses=True, acc=True, ancestors=True):
         """The particle set as it stands (slamhip_hs_mcl_get) -> (poses (N, 3) float32, acc (N,) uint64, ancestors (N,) int32 of the
         last step); None for what was not asked for."""
@@ -1039,6 +1102,37 @@ class HectorSLAMProcessor:
         for h in out:
             h["pose"][0] += off[0]; h["pose"][1] += off[1]
         return out
+
+    def AddKeyframe(self, scan, poseWorld):
+        """The signature of `scan` appended to the keyframe store with its WORLD pose (slamhip_hsproc_sig_add; MapRep.SigConfigure
+        first) -> (index, sig, info).  MatchPose, LastMapUpdatePose and the update gate are untouched."""
+        org = capi.f32(scan.Pose[:2])
+        out = capi.sig_add_call("slamhip_hsproc_sig_add", self._h, poseWorld, self.MapRep._sig_n_ring(), (scan.Points, org))
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
+        return out
+
+    def LoopCandidates(self, scan, B=capi.SIG_MAX_HITS, exclude_recent=0):
+        """The keyframes `scan` resembles most, over all 64 headings (slamhip_hsproc_sig_query over [0, count - exclude_recent))
+        -> a list of dicts (hit: the capi.SIG_HIT_DTYPE record, pose: the guess (x_k, y_k, theta_k - shift 2 pi / 64) from the
+        keyframe's stored pose), higher score first.  Candidates only: VerifyLoop checks one against the map."""
+        org = capi.f32(scan.Pose[:2])
+        last = max(self.MapRep.SigCount() - int(exclude_recent), 0)
+        hits, _, _ = capi.sig_query_call("slamhip_hsproc_sig_query", self._h, 0, last, B, self.MapRep._sig_n_ring(), (scan.Points, org))
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
+        out = []
+        for h in hits:
+            _, pose = self.MapRep.SigDownload(int(h["index"]), 1)
+            out.append({"hit": h.copy(), "pose": capi.sig_pose_guess(pose[0], h["shift"])})
+        return out
+
+    def SelfLoopCandidates(self, min_gap, first=0, last=None):
+        """MapRep.SigSelf through the processor (slamhip_hsproc_sig_self)."""
+        return capi.sig_self_call("slamhip_hsproc_sig_self", self._h, first, self.MapRep.SigCount() if last is None else last, min_gap)
+
+    def VerifyLoop(self, scan, hit, level, nx, ny, n_theta, dtheta, B=16):
+        """Check one loop candidate (an entry of LoopCandidates) against the map: Relocalise centred on the candidate's pose guess,
+        adopt=False.  -> (poseWorld, report, info) as Relocalise.  Host composition only; the caller judges the report."""
+        return self.Relocalise(scan, hit["pose"], level, nx, ny, n_theta, dtheta, B=B, adopt=False)
 
     def LocaliseInit(self, poses_world):
         """Start Monte-Carlo localisation: the particle set of the processor's own pyramid (MapRep.mcl_set) from WORLD poses, taken to
