@@ -451,6 +451,45 @@ namespace HectorSLAM.Main
             return Relocalise(scan, lattice, maxHints, false, out report, out info);
         }
 
+        /// <summary>One verified loop for RelaxKeyframes: keyframe J seen in keyframe I's frame at Z = (x, y, theta), with the diagonal
+        /// weights W, as the caller derives them from VerifyLoop.</summary>
+        public struct LoopEdge { public int I, J; public Vector3 Z, W; }
+
+        /// <summary>Spread verified loops over the keyframe store's poses: nodes are the stored poses, an odometry edge joins every
+        /// pair of consecutive keyframes (its measurement formed from their stored poses, odomW its weights), one more edge per loop,
+        /// node 0 fixed; then MapRep.PgSet, PgRelax, PgGet, PgResiduals and SigSetPoses.  Host composition only.  Returns the relaxed
+        /// poses as they were written back to the store; chi2 holds the odometry edges first, then the loops.</summary>
+        public Vector3[] RelaxKeyframes(LoopEdge[] loops, Vector3 odomW, PgSpec spec, out PgIter[] iters, out double[] chi2)
+        {
+            int n = MapRep.SigCount, e = Math.Max(n - 1, 0) + loops.Length;
+            MapRep.SigDownload(0, n, out _, out Vector3[] kp);
+            var poses = new double[3 * n]; var ij = new int[2 * e]; var z = new double[3 * e]; var w = new double[3 * e];
+            for (int k = 0; k < n; k++) { poses[3 * k] = kp[k].X; poses[3 * k + 1] = kp[k].Y; poses[3 * k + 2] = kp[k].Z; }
+            for (int k = 0; k + 1 < n; k++)
+            {
+                double c = Math.Cos(poses[3 * k + 2]), s = Math.Sin(poses[3 * k + 2]);
+                double dx = poses[3 * k + 3] - poses[3 * k], dy = poses[3 * k + 4] - poses[3 * k + 1];
+                ij[2 * k] = k; ij[2 * k + 1] = k + 1;
+                z[3 * k] = c * dx + s * dy; z[3 * k + 1] = c * dy - s * dx;
+                z[3 * k + 2] = Math.IEEERemainder(poses[3 * k + 5] - poses[3 * k + 2], 2.0 * Math.PI);
+                w[3 * k] = odomW.X; w[3 * k + 1] = odomW.Y; w[3 * k + 2] = odomW.Z;
+            }
+            for (int l = 0, k = Math.Max(n - 1, 0); l < loops.Length; l++, k++)
+            {
+                ij[2 * k] = loops[l].I; ij[2 * k + 1] = loops[l].J;
+                z[3 * k] = loops[l].Z.X; z[3 * k + 1] = loops[l].Z.Y; z[3 * k + 2] = loops[l].Z.Z;
+                w[3 * k] = loops[l].W.X; w[3 * k + 1] = loops[l].W.Y; w[3 * k + 2] = loops[l].W.Z;
+            }
+            MapRep.PgSet(poses, null, ij, z, w);
+            iters = MapRep.PgRelax(spec, out _);
+            double[] relaxed = MapRep.PgGet();
+            MapRep.PgResiduals(out _, out chi2);
+            var res = new Vector3[n];
+            for (int k = 0; k < n; k++) res[k] = new Vector3((float)relaxed[3 * k], (float)relaxed[3 * k + 1], (float)relaxed[3 * k + 2]);
+            MapRep.SigSetPoses(0, res);
+            return res;
+        }
+
         /// <summary>One hypothesis of AlignMaps: the rotation index m (theta = m pi / T), the WORLD pose of the source frame, and its
         /// merge report.</summary>
         public struct MapAlignment { public int M; public Vector3 PoseWorld; public MergeReport Report; }

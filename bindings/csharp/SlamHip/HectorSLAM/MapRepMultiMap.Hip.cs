@@ -634,6 +634,64 @@ namespace HectorSLAM.Main
                 Native.Check(Native.slamhip_hs_sig_upload(Pyramid.Ptr, poses.Length, s, p));
         }
 
+        /// <summary>Overwrite the stored poses of keyframes [first, first + poses.Length) (slamhip_hs_sig_set_poses; host-side, nothing
+        /// is launched).</summary>
+        public unsafe void SigSetPoses(int first, Vector3[] poses)
+        {
+            fixed (Vector3* p = poses)
+                Native.Check(Native.slamhip_hs_sig_set_poses(Pyramid.Ptr, first, poses.Length, p));
+        }
+
+        /// <summary>Nodes and edges of the pose graph PgSet took.</summary>
+        public int PgNodes { get; private set; }
+        public int PgEdges { get; private set; }
+
+        /// <summary>Take a pose graph, replacing any earlier one (slamhip_hs_pg_set): poses = N x 3 doubles (x, y, theta), isFixed a
+        /// byte per node or null (node 0 alone), ij = E x 2, z and w = E x 3.</summary>
+        public unsafe void PgSet(double[] poses, byte[] isFixed, int[] ij, double[] z, double[] w)
+        {
+            int n = poses.Length / 3, e = ij.Length / 2;
+            fixed (double* pp = poses, pz = z, pw = w)
+            fixed (byte* pf = isFixed)
+            fixed (int* pe = ij)
+                Native.Check(Native.slamhip_hs_pg_set(Pyramid.Ptr, pp, pf, n, pe, pz, pw, e));
+            PgNodes = n; PgEdges = e;
+        }
+
+        /// <summary>spec.OuterCount Gauss-Newton steps from the poses as they stand (slamhip_hs_pg_relax).</summary>
+        public unsafe PgIter[] PgRelax(PgSpec spec, out double chi2Final)
+        {
+            var iters = new PgIter[Math.Max(spec.OuterCount, 1)];
+            fixed (PgIter* p = iters)
+                Native.Check(Native.slamhip_hs_pg_relax(Pyramid.Ptr, in spec, p, out chi2Final));
+            return iters;
+        }
+
+        /// <summary>The graph's poses as they stand (slamhip_hs_pg_get): N x 3 doubles.</summary>
+        public unsafe double[] PgGet()
+        {
+            var poses = new double[Math.Max(PgNodes, 1) * 3];
+            fixed (double* p = poses)
+                Native.Check(Native.slamhip_hs_pg_get(Pyramid.Ptr, p, PgNodes));
+            return poses;
+        }
+
+        /// <summary>Residuals (E x 3) and chi2 per edge at the poses as they stand (slamhip_hs_pg_residuals).</summary>
+        public unsafe void PgResiduals(out double[] r, out double[] chi2)
+        {
+            r = new double[Math.Max(PgEdges, 1) * 3]; chi2 = new double[Math.Max(PgEdges, 1)];
+            fixed (double* pr = r, pc = chi2)
+                Native.Check(Native.slamhip_hs_pg_residuals(Pyramid.Ptr, pr, pc));
+            Array.Resize(ref r, PgEdges * 3); Array.Resize(ref chi2, PgEdges);
+        }
+
+        /// <summary>Free the blocks of the pose graph (slamhip_hs_pg_clear).</summary>
+        public void PgClear()
+        {
+            Native.Check(Native.slamhip_hs_pg_clear(Pyramid.Ptr));
+            PgNodes = PgEdges = 0;
+        }
+
         /// <summary>Free the blocks of the scan signatures and forget the spec (slamhip_hs_sig_clear).</summary>
         public void SigClear()
         {

@@ -278,6 +278,25 @@ namespace SlamHip
         public short Shift, Inter, Union, KeySetCount;
     }
 
+    /// <summary>slamhip_pg_spec (include/slamhip.h): the Gauss-Newton steps, the most PCG iterations of a step, the iterations enqueued
+    /// between two reads of the stop word (no result depends on it), 0, lambda and the tolerance of rule 7.  32 bytes: four int32 at
+    /// offsets 0, 4, 8, 12, two doubles at 16 and 24.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PgSpec
+    {
+        public int OuterCount, CgCount, CheckEvery, Reserved;
+        public double Lambda, Tolerance;
+    }
+
+    /// <summary>slamhip_pg_iter (include/slamhip.h): chi2 before the step, rz0, the last rz, the PCG iterations completed and why they
+    /// stopped (0 tolerance reached, 1 CgCount reached, 2 breakdown).  32 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PgIter
+    {
+        public double Chi2, Rz0, Rz;
+        public int CgIterations, Stopped;
+    }
+
     /// <summary>What slamhip_hs_hough reports of the slot it filled: the map's size and first cell, D = w + h, the bins per angle N,
     /// the sites, and the spectrum HS (T entries); H (T rows of N) when asked for.</summary>
     public sealed class HoughInfo
@@ -441,6 +460,13 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_sig_download(IntPtr hs, int first, int n, ulong* sig, Vector3* poses);
         [DllImport(Lib)] internal static extern int slamhip_hs_sig_upload(IntPtr hs, int n, ulong* sig, Vector3* poses);
         [DllImport(Lib)] internal static extern int slamhip_hs_sig_clear(IntPtr hs);
+        [DllImport(Lib)] internal static extern int slamhip_hs_sig_set_poses(IntPtr hs, int first, int n, Vector3* poses);
+        // relaxation of a pose graph of keyframes (no reference counterpart)
+        [DllImport(Lib)] internal static extern int slamhip_hs_pg_set(IntPtr hs, double* poses, byte* isFixed, int nNodes, int* ij, double* z, double* w, int nEdges);
+        [DllImport(Lib)] internal static extern int slamhip_hs_pg_relax(IntPtr hs, in PgSpec spec, PgIter* iters, out double chi2Final);
+        [DllImport(Lib)] internal static extern int slamhip_hs_pg_get(IntPtr hs, double* poses, int nNodes);
+        [DllImport(Lib)] internal static extern int slamhip_hs_pg_residuals(IntPtr hs, double* r, double* chi2);
+        [DllImport(Lib)] internal static extern int slamhip_hs_pg_clear(IntPtr hs);
         [DllImport(Lib)] internal static extern int slamhip_debug_nearest_field(byte* cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h, short* dxdy);
         // the frontier cells and their connected clusters (no reference counterpart), and their host-side hook
         [DllImport(Lib)] internal static extern int slamhip_hs_frontiers(IntPtr hs, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,

@@ -1569,6 +1569,106 @@ int32_t slamhip_debug_sig_sector(const int32_t *uv, int32_t n, int32_t *out_sect
 int32_t slamhip_debug_sig_search(const uint64_t *query_sig, const uint64_t *store_sig, const uint16_t *n_set, int32_t N, int32_t n_ring,
                                  int32_t first, int32_t last, int32_t min_gap, int32_t B, slamhip_sig_hit *out_hits, int32_t *out_n);
 
+/* Overwrite the poses of keyframes [first, first + n) of the store (K18): what slamhip_hs_sig_download hands back from here on.  The
+ * poses live on the host: nothing is launched.  It is how a correction (slamhip_hs_pg_relax below) is taken back into the store.
+ * SLAMHIP_ERR_STATE before slamhip_hs_sig_configure; SLAMHIP_ERR_INVALID: a range outside the store. */
+int32_t slamhip_hs_sig_set_poses(slamhip_hs *hs, int32_t first, int32_t n, const float *poses);
+
+/* Relaxation of a 2-D pose graph on the device (K19; no reference counterpart).  K18 finds loop candidates and K7 verifies one; a
+ * verified loop says that the keyframe poses are inconsistent, and this unit spreads that error over the trajectory: Gauss-Newton
+ * steps, each solved matrix-free by block-Jacobi preconditioned conjugate gradients (PCG).  slamhip_hs_update_by_scan and the
+ * processor's per-scan call never enter it.
+ * THE DEFINITION.  All arithmetic is binary64 + - * / and rint, ONE rounding per operation (no fused multiply-add), evaluated in the
+ * order the parentheses give; there is no sqrt, no libm and no floating-point atomic.
+ *  1. Graph.  N nodes (x, y, theta) as doubles, N in [1, 2^20], every value finite and |theta| <= 65536.  `fixed`: a byte per node,
+ *     non-zero = the node does not move; NULL = node 0 alone is fixed; at least one node is fixed.  E edges (i, j), i != j, E in
+ *     [0, 2^22], each with a measurement z = (zx, zy, zt) -- node j seen in node i's frame -- and a diagonal weight w = (wx, wy, wt),
+ *     every weight finite and > 0.  Duplicate edges are allowed: they are two edges.
+ *  2. Trig.  (s, c) = sh_det_sincos(theta) (det_trig.h): the binary64 Cody-Waite reduction by pi / 2 and the degree-13 / 14 kernels of
+ *     sh_det_sincosf without the final rounding to binary32; contract |theta| <= 65536; at most 2 ulp from NumPy's binary64 sin / cos
+ *     on 10^5 angles (measured; tests/test_hs_pg_abi.py).  wrap(a) = a - TWO_PI * rint(a / TWO_PI), TWO_PI = 6.283185307179586 (the binary64
+ *     nearest 2 pi).
+ *  3. Edge record, formed once per outer iteration from the poses as they stand: (s, c) of theta_i; dx = x_j - x_i, dy = y_j - y_i;
+ *     ux = c * dx + s * dy, uy = c * dy - s * dx; r = (ux - zx, uy - zy, wrap((theta_j - theta_i) - zt));
+ *     A = dr / d(node i) = [[-c, -s, uy], [s, -c, -ux], [0, 0, -1]], B = dr / d(node j) = [[c, s, 0], [-s, c, 0], [0, 0, 1]] (row k:
+ *     residual k; column a: the node's variable a); chi2_e = (wx * (r0 * r0) + wy * (r1 * r1)) + wt * (r2 * r2).
+ *  4. Sums over a node's edges run in increasing EDGE INDEX -- and for one edge the i side before the j side, which cannot occur
+ *     because i != j.  J is A where the node is the edge's i, B where it is its j; the 0 and 1 entries of A and B take part in the
+ *     products like any other value.  D_n starts as lambda on the diagonal and +0 elsewhere; per incident edge, for a <= b:
+ *       D[a][b] = D[a][b] + (((J[0][a] * wx) * J[0][b] + (J[1][a] * wy) * J[1][b]) + (J[2][a] * wt) * J[2][b]);   D[b][a] = D[a][b].
+ *     g_n starts as +0; per incident edge, with v = (wx * r0, wy * r1, wt * r2):
+ *       g[a] = g[a] + ((J[0][a] * v0 + J[1][a] * v1) + J[2][a] * v2).
+ *     M_n = D_n^-1 by the adjugate over the determinant: c00 = d11 * d22 - d12 * d12, c01 = d02 * d12 - d01 * d22,
+ *     c02 = d01 * d12 - d02 * d11, c11 = d00 * d22 - d02 * d02, c12 = d01 * d02 - d00 * d12, c22 = d00 * d11 - d01 * d01,
+ *     det = (d00 * c00 + d01 * c01) + d02 * c02, M[a][b] = M[b][a] = cab / det.  M_n = 0 unless det > 0: a free node with no edge and
+ *     lambda = 0 has M = 0 and does not move.  A fixed node has M = 0 and g = 0.
+ *     M v, for z = M res:  out[a] = (M[a][0] * v0 + M[a][1] * v1) + M[a][2] * v2.
+ *  5. Operator q = H p.  Per edge t_e[k] = w_k * (((A[k][0] * pi0 + A[k][1] * pi1) + A[k][2] * pi2) + ((B[k][0] * pj0 + B[k][1] * pj1)
+ *     + B[k][2] * pj2)), then q_n[a] starts as lambda * p_n[a] and takes, in rule 4's order, q[a] = q[a] + ((J[0][a] * t0 + J[1][a] * t1)
+ *     + J[2][a] * t2).  The rows of fixed nodes are 0.  (The kernel forms t_e again at each end of an edge: the same bits.)
+ *  6. Dot products -- the one reduction shape.  A field's term of a node is (u0 * v0 + u1 * v1) + u2 * v2.  The sum of a sequence of
+ *     length L: pad with +0.0 to a multiple of 256 (L = 0: to 256); in every block of 256, t[k] = t[k] + t[k + h] for k < h, for
+ *     h = 128, 64, .. 1; the blocks' t[0] are the next sequence; repeat while more than one value is left.  chi2 = the sum of chi2_e
+ *     over the edges by the same shape.  Nothing depends on the grid, the order of workgroups or check_every.
+ *  7. PCG, per outer iteration: x = 0, res = -g, z = M res, p = z, rz = res . z, rz0 = rz.  Before iteration k = 0, 1, ..: stop with
+ *     `stopped` = 0 if rz <= (tol * tol) * rz0 or rz <= 0; else stop with `stopped` = 1 if k == n_cg.  One iteration: q = H p,
+ *     pq = p . q; unless pq > 0 stop with `stopped` = 2 (breakdown; x stays as it was); alpha = rz / pq; x[a] = x[a] + alpha * p[a],
+ *     res[a] = res[a] - alpha * q[a]; z = M res; rz' = res . z; beta = rz' / rz; p[a] = z[a] + beta * p[a]; rz = rz'.  Then, for every
+ *     free node, pose[a] = pose[a] + x[a] and theta = wrap(theta); a fixed node is not touched.
+ *  8. Output per outer iteration, slamhip_pg_iter: chi2 BEFORE the step, rz0, the last rz, cg_iters (the iterations completed),
+ *     stopped.  chi2 after the last step comes beside the array.
+ * Block-Jacobi sees one node at a time, so on chain-like graphs PCG needs a number of iterations of the order of the chain's length
+ * (about 3 N for a ring closed by one loop): DESIGN.md section 4 "K19" says what that costs. */
+#define SLAMHIP_PG_MAX_NODES (1 << 20)
+#define SLAMHIP_PG_MAX_EDGES (1 << 22)
+#define SLAMHIP_PG_MAX_OUTER 64
+#define SLAMHIP_PG_MAX_CG (1 << 20)
+typedef struct slamhip_pg_spec {
+    int32_t n_outer;                   /* offset 0: Gauss-Newton steps, [1, 64] */
+    int32_t n_cg;                      /* offset 4: the most PCG iterations of a step, [1, 2^20] */
+    int32_t check_every;               /* offset 8: >= 1, PCG iterations the host enqueues between two reads of the stop word; no result depends on it */
+    int32_t reserved;                  /* offset 12: 0 */
+    double lambda;                     /* offset 16: >= 0, added to every diagonal entry of H */
+    double tol;                        /* offset 24: >= 0, rule 7 */
+} slamhip_pg_spec;                     /* 32 bytes */
+typedef struct slamhip_pg_iter {
+    double chi2, rz0, rz;              /* offsets 0, 8, 16 */
+    int32_t cg_iters, stopped;         /* offsets 24, 28; stopped: 0 tolerance reached, 1 n_cg reached, 2 breakdown */
+} slamhip_pg_iter;                     /* 32 bytes */
+/* Take a graph (rule 1), replacing any earlier one.  Everything is validated on the host before anything is launched:
+ * SLAMHIP_ERR_INVALID for N or E outside their ranges, an index outside [0, N), i == j, a value that is not finite, |theta| > 65536,
+ * a weight <= 0, a `fixed` array without a non-zero byte.  The host builds the node -> (edge, side) lists by a counting sort that
+ * keeps the edge order; the graph goes to ONE device block through pinned staging.  poses = N x 3 doubles, ij = E x 2 int32,
+ * z and w = E x 3 doubles (all three may be NULL when E == 0).  The unit's blocks belong to the hs, are made by this call and freed by
+ * slamhip_hs_pg_clear or slamhip_hs_destroy; slamhip_hs_reset drops the graph and keeps the blocks.  A call that validation refuses
+ * leaves the earlier graph as it was; after SLAMHIP_ERR_NOMEM or SLAMHIP_ERR_HIP the earlier graph is GONE.  Blocking, as every call below,
+ * with the context's bounded wait, on the operator's stream behind everything already enqueued. */
+int32_t slamhip_hs_pg_set(slamhip_hs *hs, const double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z,
+                          const double *w, int32_t E);
+/* Rules 3 - 8: spec->n_outer Gauss-Newton steps from the poses as they stand in device memory -- a second call continues from the
+ * relaxed poses.  out_iters: n_outer records; *out_chi2_final: chi2 after the last step.  k19_linearise (a lane per edge), k19_diag
+ * (a lane per node), k19_begin (one workgroup, once per step), then per PCG iteration k19_apply, k19_step, k19_dir (a lane per node
+ * each; every workgroup finishes rule 6's tree itself, so alpha and beta need no launch of their own), k19_update.  Rule 7's stop is
+ * decided ON THE DEVICE, by the same comparisons, into a word the later launches read: a launch enqueued behind the stop leaves at
+ * once.  The host enqueues check_every iterations (at most 1024, whatever check_every says), reads the word, and goes on or not.  SLAMHIP_ERR_INVALID, nothing launched and
+ * nothing written: a spec outside the ranges above, reserved != 0.  SLAMHIP_ERR_STATE: no graph. */
+int32_t slamhip_hs_pg_relax(slamhip_hs *hs, const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final);
+/* The poses as they stand: N x 3 doubles; N must be the graph's.  SLAMHIP_ERR_STATE: no graph. */
+int32_t slamhip_hs_pg_get(slamhip_hs *hs, double *poses, int32_t N);
+/* Rule 3 at the poses as they stand: out_r = E x 3 doubles, out_chi2 = E doubles (chi2_e); either may be NULL, not both.  A caller
+ * throws a bad loop edge out by its chi2 and relaxes again.  SLAMHIP_ERR_STATE: no graph. */
+int32_t slamhip_hs_pg_residuals(slamhip_hs *hs, double *out_r, double *out_chi2);
+/* Free the unit's blocks.  Never fails for an hs that has none. */
+int32_t slamhip_hs_pg_clear(slamhip_hs *hs);
+/* Test hooks (no device involved).  _pg_relax: the whole definition over the caller's arrays, from the header text the kernels run
+ * (hs_pg.h) in plain loops; poses are relaxed IN PLACE; out_r (E x 3) and out_chi2 (E), rule 3 at the final poses, may be NULL; the
+ * refusals of slamhip_hs_pg_set and _pg_relax, nothing written.  _pg_sum: rule 6 over L >= 0 values.  _sincos: rule 2 for n angles. */
+int32_t slamhip_debug_pg_relax(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w,
+                               int32_t E, const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final,
+                               double *out_r, double *out_chi2);
+int32_t slamhip_debug_pg_sum(const double *v, int32_t L, double *out);
+int32_t slamhip_debug_sincos(const double *a, int32_t n, double *out_s, double *out_c);
+
 /* MapRepMultiMap.UpdateByScan ->OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);

@@ -167,6 +167,11 @@ SIG_INFO = np.dtype([(n, np.int32) for n in ("n_points", "n_ignored", "n_far", "
 SIG_HIT_DTYPE = np.dtype([("score", np.uint32), ("index", np.int32), ("shift", np.int16), ("inter", np.int16), ("uni", np.int16),
                           ("n_set_key", np.int16)])                                                     # slamhip_sig_hit: 16 bytes
 assert SIG_SPEC.itemsize == 12 and SIG_INFO.itemsize == 16 and SIG_HIT_DTYPE.itemsize == 16
+PG_MAX_NODES, PG_MAX_EDGES, PG_MAX_OUTER, PG_MAX_CG = 1 << 20, 1 << 22, 64, 1 << 20   # the limits of slamhip_hs_pg_*
+PG_SPEC = np.dtype([("n_outer", np.int32), ("n_cg", np.int32), ("check_every", np.int32), ("reserved", np.int32), ("lambda", np.float64),
+                    ("tol", np.float64)])                                                           # slamhip_pg_spec: 32 bytes
+PG_ITER = np.dtype([("chi2", np.float64), ("rz0", np.float64), ("rz", np.float64), ("cg_iters", np.int32), ("stopped", np.int32)])   # slamhip_pg_iter: 32 bytes
+assert PG_SPEC.itemsize == 32 and PG_ITER.itemsize == 32
 VIEW_MAX_REACH, VIEW_MAX_POSES, VIEW_MAX_K, VIEW_LDS_WORDS = 4096, 4096, 64, 8704   # the limits of slamhip_hs_view_gain / _view_select; K15_LDS_WORDS
 VIEW_SUMMARY = np.dtype([(n, np.int32) for n in ("n_walked", "n_same", "n_ignored", "n_cut", "n_seen", "n_unknown", "n_free", "n_occupied", "n_new",
                                                  "n_new_unknown")])   # slamhip_view_summary: ten int32, 40 bytes
@@ -245,6 +250,9 @@ def _declare(L):
         "slamhip_debug_sig_ring": (i32, [vp, i32, i32, i32, vp]),
         "slamhip_debug_sig_sector": (i32, [vp, i32, vp]),
         "slamhip_debug_sig_search": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
+        "slamhip_debug_pg_relax": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "slamhip_debug_pg_sum": (i32, [vp, i32, vp]),
+        "slamhip_debug_sincos": (i32, [vp, i32, vp, vp]),
         "slamhip_debug_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_nav_field": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_rollouts": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, C.c_float, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -358,6 +366,12 @@ def _declare(L):
         "slamhip_hs_sig_download": (i32, [vp, i32, i32, vp, vp]),
         "slamhip_hs_sig_upload": (i32, [vp, i32, vp, vp]),
         "slamhip_hs_sig_clear": (i32, [vp]),
+        "slamhip_hs_sig_set_poses": (i32, [vp, i32, i32, fp]),
+        "slamhip_hs_pg_set": (i32, [vp, vp, vp, i32, vp, vp, vp, i32]),
+        "slamhip_hs_pg_relax": (i32, [vp, vp, vp, vp]),
+        "slamhip_hs_pg_get": (i32, [vp, vp, i32]),
+        "slamhip_hs_pg_residuals": (i32, [vp, vp, vp]),
+        "slamhip_hs_pg_clear": (i32, [vp]),
         "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hs_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hs_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -960,6 +974,62 @@ def sig_pose_guess(key_pose, shift):
     if th <= -math.pi:
         th += 2.0 * math.pi
     return float(key_pose[0]), float(key_pose[1]), th
+
+
+def pg_spec(n_outer, n_cg, check_every=None, lam=0.0, tol=1e-6, reserved=0):
+    """A slamhip_pg_spec record (a (1,) PG_SPEC array); check_every defaults to min(n_cg, 64)."""
+    sp = np.zeros(1, PG_SPEC)
+    sp["n_outer"] = int(n_outer); sp["n_cg"] = int(n_cg); sp["check_every"] = min(int(n_cg), 64) if check_every is None else int(check_every)
+    sp["reserved"] = int(reserved); sp["lambda"] = float(lam); sp["tol"] = float(tol)
+    return sp
+
+
+def pg_graph(poses, fixed, ij, z, w):
+    """The arrays of a pose graph as the library takes them -> (poses (N, 3) float64, fixed (N,) uint8 or None, ij (E, 2) int32,
+    z (E, 3) float64, w (E, 3) float64), each contiguous and a copy."""
+    p = np.array(poses, np.float64).reshape(-1, 3)
+    fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed).astype(bool).astype(np.uint8))
+    e = np.array(ij, np.int32).reshape(-1, 2)
+    return p, fx, e, np.array(z, np.float64).reshape(-1, 3), np.array(w, np.float64).reshape(-1, 3)
+
+
+def _vp(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
+
+
+def debug_pg_relax(poses, fixed, ij, z, w, spec):
+    """The whole definition of slamhip_hs_pg_relax on the host (slamhip_debug_pg_relax; no device involved)
+    -> (poses (N, 3), iters PG_ITER (n_outer,), chi2_final, r (E, 3), chi2_e (E,)).  The caller's arrays are not written."""
+    p, fx, e, zz, ww = pg_graph(poses, fixed, ij, z, w)
+    assert e.shape[0] == zz.shape[0] == ww.shape[0] and (fx is None or fx.shape[0] == p.shape[0])
+    iters = np.zeros(max(int(spec["n_outer"][0]), 1), PG_ITER); fin = C.c_double(0.0)
+    r = np.zeros((e.shape[0], 3), np.float64); c2 = np.zeros(e.shape[0], np.float64)
+    call("slamhip_debug_pg_relax", _vp(p), _vp(fx), p.shape[0], _vp(e), _vp(zz), _vp(ww), e.shape[0], spec.ctypes.data_as(C.c_void_p),
+         iters.ctypes.data_as(C.c_void_p), C.byref(fin), _vp(r), _vp(c2))
+    return p, iters[:int(spec["n_outer"][0])].copy(), fin.value, r, c2
+
+
+def debug_pg_sum(v):
+    """Rule 6 of slamhip_hs_pg_relax over a float64 array (slamhip_debug_pg_sum)."""
+    a = np.ascontiguousarray(v, np.float64).ravel(); out = C.c_double(0.0)
+    call("slamhip_debug_pg_sum", _vp(a), a.shape[0], C.byref(out))
+    return out.value
+
+
+def debug_sincos(a):
+    """Rule 2 of slamhip_hs_pg_relax, sh_det_sincos, for a float64 array (slamhip_debug_sincos) -> (sin, cos)."""
+    x = np.ascontiguousarray(a, np.float64).ravel(); s = np.zeros_like(x); c = np.zeros_like(x)
+    call("slamhip_debug_sincos", _vp(x), x.shape[0], _vp(s), _vp(c))
+    return s, c
+
+
+def pg_edge_between(pose_i, pose_j):
+    """The measurement z of an edge (i, j) that the two poses satisfy exactly up to rounding: node j in node i's frame, libm trig in
+    binary64 (host composition: HectorSLAMProcessor.RelaxKeyframes forms its odometry edges with it)."""
+    xi, yi, ti = (float(v) for v in pose_i); xj, yj, tj = (float(v) for v in pose_j)
+    c, s = math.cos(ti), math.sin(ti)
+    dx, dy = xj - xi, yj - yi
+    return c * dx + s * dy, c * dy - s * dx, math.remainder(tj - ti, 2.0 * math.pi)
 
 
 def debug_merge_box(pose, stm, ax, ay, sw, sh, x0, y0, x1, y1):

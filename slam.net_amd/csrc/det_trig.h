@@ -7,6 +7,10 @@
 // kernels, IEEE + - * rint only (the build uses -ffp-contract=off), one final rounding to binary32.
 // The result is the correctly rounded float sin/cos except with probability ~2^-28 per call, and is
 // bit-identical on host and device.  Entry points that take (px,py,c,s) leave trig to the caller.
+//
+// sh_det_sincos is the binary64 entry point (K19, hs_pg.h): the same reduction and kernels on a double argument, WITHOUT the final
+// rounding.  Contract: |a| <= 65536.  Measured against NumPy's binary64 sin / cos on 10^5 angles uniform in +-65536
+// (tests/test_hs_pg_abi.py): at most 2 ulp.  Beyond the contract (and for NaN) it falls to libm, as sh_det_sincosf does.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -24,7 +28,8 @@ __host__ __device__ static inline void sh_det_sincosf(float a, float *s, float *
     sh_det_sincosf_small(a, s, c);
 }
 
-__host__ __device__ static inline void sh_det_sincosf_small(float a, float *s, float *c)
+// the reduction and the two kernels on a binary64 argument, |x| <= 65536: what both entry points run
+__host__ __device__ static inline void sh_det_sincos_small(double x, double *s, double *c)
 {
     const double TWO_OVER_PI = 6.36619772367581382433e-01;
     const double P1 = 1.57079632673412561417e+00, P2 = 6.07710050630396597660e-11, P2T = 2.02226624879595063154e-21;
@@ -32,7 +37,6 @@ __host__ __device__ static inline void sh_det_sincosf_small(float a, float *s, f
                  S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
     const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
                  C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-    double x = (double)a;
     double k = rint(x * TWO_OVER_PI);
     double r = ((x - k * P1) - k * P2) - k * P2T;
     double z = r * r;
@@ -41,15 +45,30 @@ __host__ __device__ static inline void sh_det_sincosf_small(float a, float *s, f
     double pc = z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))));
     double cs = 1.0 - (0.5 * z - z * pc);
     const int q = (int)k;                 // |k| <= 41722: exact
-    double so, co;
     switch (q & 3) {
-    case 0:  so = sn;  co = cs;  break;
-    case 1:  so = cs;  co = -sn; break;
-    case 2:  so = -sn; co = -cs; break;
-    default: so = -cs; co = sn;  break;
+    case 0:  *s = sn;  *c = cs;  break;
+    case 1:  *s = cs;  *c = -sn; break;
+    case 2:  *s = -sn; *c = -cs; break;
+    default: *s = -cs; *c = sn;  break;
     }
+}
+
+__host__ __device__ static inline void sh_det_sincosf_small(float a, float *s, float *c)
+{
+    double so, co;
+    sh_det_sincos_small((double)a, &so, &co);
     *s = (float)so;
     *c = (float)co;
+}
+
+__host__ __device__ static inline void sh_det_sincos(double a, double *s, double *c)
+{
+    if (!(fabs(a) <= 65536.0)) {          // huge / inf / NaN: outside the deterministic contract
+        *s = sin(a);
+        *c = cos(a);
+        return;
+    }
+    sh_det_sincos_small(a, s, c);
 }
 
 // MathEx.NormalizeAngle (BaseSLAM/MathEx.cs:116-138); C# '%' on float == fmodf (exact operation).

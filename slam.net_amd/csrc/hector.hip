@@ -127,6 +127,7 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
     hs_nr_free(hs);
     hs_hg_free(hs);
     hs_sg_free(hs);
+    hs_pg_free(hs);
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
     if (hs->ev_pts) (void)hipEventDestroy(hs->ev_pts);
@@ -156,6 +157,7 @@ extern "C" int32_t slamhip_hs_reset(slamhip_hs *hs)
     hs_merge_drop_source(hs);                                              // (slamhip_hs_merge_set_source: a source belongs to the map it was to be merged into)
     hs_hg_drop_slot(hs, 0);                                                // (slamhip_hs_hough: slot 0 held the map that is gone; the source's drop emptied slot 1)
     hs_sg_reset(hs);                                                       // (slamhip_hs_sig_add: the keyframes belonged to the map that is gone)
+    hs_pg_reset(hs);                                                       // (slamhip_hs_pg_set: so did the graph of their poses)
     return SLAMHIP_OK;
 }
 

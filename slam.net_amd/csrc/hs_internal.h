@@ -51,6 +51,7 @@ struct hs_view;                            // hs_view.hip
 struct hs_nearest;                         // hs_nearest.hip
 struct hs_hough;                           // hs_hough.hip
 struct hs_sig;                             // hs_sig.hip
+struct hs_pg;                              // hs_pg.hip
 struct hs_field;                           // hs_dfield.h
 struct slamhip_hs {
     slamhip_ctx *ctx;
@@ -89,6 +90,7 @@ struct slamhip_hs {
     struct hs_nearest *nrs;                                // slamhip_hs_nearest_field / _pairs: the row offsets and the pairs of E and the results' blocks, made by the first call, kept
     struct hs_hough *hgh;                                  // slamhip_hs_hough / _hough_rotation / _hough_shifts: the two slots' votes, spectra and row extents and the results' blocks, made by the first call, kept
     struct hs_sig *sig;                                    // slamhip_hs_sig_configure / _sig_add / _sig_query / _sig_self: the spec, the store of keyframe signatures, the poses and the results' blocks, made by configure, kept
+    struct hs_pg *pg;                                      // slamhip_hs_pg_set / _pg_relax / _pg_get / _pg_residuals: the pose graph's one device block and its pinned staging, made by the first set, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -235,3 +237,6 @@ void    hs_sg_reset(slamhip_hs *hs);        // slamhip_hs_reset: the store is em
 // what slamhip_hs_sig_add and _sig_query refuse before they launch anything
 int32_t hs_sg_check_add(const slamhip_hs *hs);
 int32_t hs_sg_check_query(const slamhip_hs *hs, int32_t first, int32_t last, int32_t B);
+// hs_pg.hip
+void    hs_pg_free(slamhip_hs *hs);         // the pose graph's blocks (the caller has drained the stream)
+void    hs_pg_reset(slamhip_hs *hs);        // slamhip_hs_reset: no graph from here on; the blocks stay

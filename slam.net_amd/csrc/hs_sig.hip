@@ -2,7 +2,7 @@
 // the signature of a scan (rings x 64 sectors of occupied cells round the sensor, a 64-bit word per ring, so that a turn of the
 // scan by one sector is a rotate of every word by one bit), the store, the search of one scan against the store over all 64
 // headings and the search of the store against itself (slamhip_hs_sig_configure, _sig_add, _sig_add_scans, _sig_query, _sig_self,
-// _sig_count, _sig_download, _sig_upload, _sig_clear, slamhip_debug_sig_table, _sig, _sig_ring, _sig_sector, _sig_search).  No
+// _sig_count, _sig_download, _sig_upload, _sig_set_poses, _sig_clear, slamhip_debug_sig_table, _sig, _sig_ring, _sig_sector, _sig_search).  No
 // reference counterpart.  Definition: include/slamhip.h (slamhip_hs_sig_add); the arithmetic host and device share: hs_sig.h.
 //
 // The store: blocks of 64 keyframes; within a block ring r of the 64 keyframes is contiguous (sig[block][r][64], hs_sig_at), so a
@@ -599,6 +599,17 @@ extern "C" int32_t slamhip_hs_sig_download(slamhip_hs *hs, int32_t first, int32_
     SH_HIP(hipMemcpyAsync(g->h_io, g->d_in, bytes, hipMemcpyDeviceToHost, ctx->stream));
     SH_TRY(hs_call_finish(hs));
     memcpy(sig, g->h_io, bytes);
+    return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hs_sig_set_poses(slamhip_hs *hs, int32_t first, int32_t n, const float *poses)
+{
+    SH_CHECK_ARG(hs && (poses || n == 0));
+    SH_TRY(hs_sg_need(hs, "signature set_poses"));
+    hs_sig *g = hs->sig;
+    if (first < 0 || n < 0 || first > g->count || n > g->count - first)
+        SH_FAIL(SLAMHIP_ERR_INVALID, "signature set_poses: %d keyframes from %d of %d", n, first, g->count);
+    if (n) memcpy(g->poses.data() + 3 * (size_t)first, poses, sizeof(float) * 3 * (size_t)n);   // (host-side books: nothing is launched)
     return SLAMHIP_OK;
 }
 

@@ -666,6 +666,45 @@ class MapRepMultiMap:
         assert s.shape[0] == p.shape[0]
         capi.call("slamhip_hs_sig_upload", self._h, s.shape[0], s.ctypes.data_as(C.c_void_p), capi.fptr(p))
 
+    def SigSetPoses(self, poses, first=0):
+        """Overwrite the stored poses of keyframes [first, first + len(poses)) (slamhip_hs_sig_set_poses; host-side, no launch)."""
+        p = capi.f32(poses, (-1, 3))
+        capi.call("slamhip_hs_sig_set_poses", self._h, int(first), p.shape[0], capi.fptr(p) if p.shape[0] else None)
+
+    def PgSet(self, poses, fixed, ij, z, w):
+        """Take a pose graph, replacing any earlier one (slamhip_hs_pg_set; no reference counterpart): poses (N, 3), fixed (N,) bools
+        or None (node 0 alone), ij (E, 2), z and w (E, 3), all binary64."""
+        p, fx, e, zz, ww = capi.pg_graph(poses, fixed, ij, z, w)
+        assert e.shape[0] == zz.shape[0] == ww.shape[0] and (fx is None or fx.shape[0] == p.shape[0])
+        capi.call("slamhip_hs_pg_set", self._h, capi._vp(p), capi._vp(fx), p.shape[0], capi._vp(e), capi._vp(zz), capi._vp(ww), e.shape[0])
+        self._pg_sizes = (p.shape[0], e.shape[0])
+
+    def PgRelax(self, spec):
+        """spec["n_outer"] Gauss-Newton steps from the poses as they stand (slamhip_hs_pg_relax) -> (iters capi.PG_ITER records,
+        chi2 after the last step)."""
+        iters = np.zeros(max(int(spec["n_outer"][0]), 1), capi.PG_ITER); fin = C.c_double(0.0)
+        capi.call("slamhip_hs_pg_relax", self._h, spec.ctypes.data_as(C.c_void_p), iters.ctypes.data_as(C.c_void_p), C.byref(fin))
+        return iters[:int(spec["n_outer"][0])].copy(), fin.value
+
+    def PgGet(self):
+        """The graph's poses as they stand (slamhip_hs_pg_get) -> (N, 3) float64."""
+        N = getattr(self, "_pg_sizes", (1, 0))[0]
+        p = np.zeros((N, 3), np.float64)
+        capi.call("slamhip_hs_pg_get", self._h, p.ctypes.data_as(C.c_void_p), N)
+        return p
+
+    def PgResiduals(self):
+        """Rule 3 at the poses as they stand (slamhip_hs_pg_residuals) -> (r (E, 3), chi2_e (E,)) float64."""
+        E = getattr(self, "_pg_sizes", (1, 0))[1]
+        r = np.zeros((max(E, 1), 3), np.float64); c2 = np.zeros(max(E, 1), np.float64)
+        capi.call("slamhip_hs_pg_residuals", self._h, r.ctypes.data_as(C.c_void_p), c2.ctypes.data_as(C.c_void_p))
+        return r[:E].copy(), c2[:E].copy()
+
+    def PgClear(self):
+        """Free the blocks of the pose graph (slamhip_hs_pg_clear)."""
+        capi.call("slamhip_hs_pg_clear", self._h)
+        self.__dict__.pop("_pg_sizes", None)
+
     def SigClear(self):
         """Free the blocks of the scan signatures and forget the spec (slamhip_hs_sig_clear)."""
         capi.call("slamhip_hs_sig_clear", self._h)
@@ -1133,6 +1172,28 @@ class HectorSLAMProcessor:
         """Check one loop candidate (an entry of LoopCandidates) against the map: Relocalise centred on the candidate's pose guess,
         adopt=False.  -> (poseWorld, report, info) as Relocalise.  Host composition only; the caller judges the report."""
         return self.Relocalise(scan, hit["pose"], level, nx, ny, n_theta, dtheta, B=B, adopt=False)
+
+    def RelaxKeyframes(self, loops, odom_w, spec, fixed=None):
+        """Spread verified loops over the keyframe store's poses (host composition of slamhip_hs_pg_set, _pg_relax, _pg_get,
+        _pg_residuals and slamhip_hs_sig_set_poses; no reference counterpart).  Nodes: the store's poses; an odometry edge joins every
+        pair of consecutive keyframes, its z formed from their stored poses (capi.pg_edge_between), its weights odom_w = (wx, wy,
+        wtheta); one more edge per entry (i, j, z, w) of `loops`, as the caller derives it from VerifyLoop; node 0 is fixed unless
+        `fixed` says otherwise.  The relaxed poses are written back to the store (rounded to binary32, as it keeps them)
+        -> (poses (N, 3) float64, iters, per-edge chi2 at the relaxed poses: the N - 1 odometry edges, then the loops)."""
+        rep = self.MapRep
+        _, kp = rep.SigDownload()
+        N = kp.shape[0]
+        poses = kp.astype(np.float64)
+        ij = [(k, k + 1) for k in range(N - 1)]; z = [capi.pg_edge_between(poses[k], poses[k + 1]) for k in range(N - 1)]
+        w = [tuple(float(v) for v in odom_w)] * (N - 1)
+        for (i, j, zl, wl) in loops:
+            ij.append((int(i), int(j))); z.append(tuple(float(v) for v in zl)); w.append(tuple(float(v) for v in wl))
+        rep.PgSet(poses, fixed, np.array(ij, np.int32).reshape(-1, 2), np.array(z, np.float64).reshape(-1, 3), np.array(w, np.float64).reshape(-1, 3))
+        iters, _ = rep.PgRelax(spec)
+        out = rep.PgGet()
+        _, chi2 = rep.PgResiduals()
+        rep.SigSetPoses(out.astype(np.float32))
+        return out, iters, chi2
 
     def LocaliseInit(self, poses_world):
         """Start Monte-Carlo localisation: the particle set of the processor's own pyramid (MapRep.mcl_set) from WORLD poses, taken to
