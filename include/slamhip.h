@@ -320,10 +320,17 @@ int32_t slamhip_cs_search_shard_async(slamhip_cs *cs, const float search_pose[3]
  * key once the stream reaches that point -- one of a ring of 4 words, valid until three further RING LAUNCHES on the handle have
  * been enqueued: calls of this function, fused scans (slamhip_cs_search_and_update and its _pxcs form) and the all-reduce forms
  * (slamhip_cs_search_allreduce*, which also overwrite the slot in place with the reduced key) all advance the same ring.  A caller
- * that keeps a word across such calls copies it first (slamhip_cs_key_read).  No caller memory is involved, so the kernel needs no final arriver: the workgroups that complete
+ * that keeps a word across such calls copies it first (slamhip_cs_key_read).  In RING MODE (the fused scans, the all-reduce forms, SLAMHIP_K1_OVERLAP=0; for this function's default see WHICH STREAM below) no caller memory is involved, so the kernel needs no final arriver: the workgroups that complete
  * candidates min their keys straight into the word (the previous call's launch left it all ones), and the end of the launch is
  * the completion (the cross-thread arg-min of :695-705 as fire-and-forget atomics).  slamhip_cs_key_read waits for the handle's
  * stream and copies one such word to the host.
+ * WHICH STREAM: consecutive calls of this function overlap on the device -- every other launch runs in a second stream of the
+ * context, not in slamhip_ctx_stream, and the launch's last finisher stores the key into the word (SLAMHIP_K1_OVERLAP=0: all in
+ * the operator's stream, the ring mode above).  The word is therefore NOT ordered in slamhip_ctx_stream by this call alone: it is
+ * once any other call on the handle has been made (each orders the operator's stream behind the handle's searches first), after
+ * slamhip_cs_key_read, and after slamhip_ctx_synchronize, which waits for both streams.  A caller's own work in
+ * slamhip_ctx_stream that reads a word goes behind one of those.  The ring's size and the words' validity are unchanged; the fused
+ * scans and the all-reduce forms keep their launches in the operator's stream.
  * Backpressure (round 6): every such launch is accompanied by its plan (slamhip_cs_plan_stats), whose buffers exist eight times, so
  * a caller that enqueues searches faster than the device runs them is held in this call until the search seven launches back has
  * started (the device still has six searches queued: nothing idles) -- at most 20 ms or the context's wait bound, whichever is

@@ -124,6 +124,7 @@ extern "C" int32_t slamhip_ctx_synchronize(slamhip_ctx *c)
 {
     SH_CHECK_ARG(c);
     SH_HIP(hipStreamSynchronize(c->stream));
+    SH_HIP(hipStreamSynchronize(c->side_stream));                 // (every other enqueue-only search of the context's operator objects runs there; idle otherwise)
     return SLAMHIP_OK;
 }
 

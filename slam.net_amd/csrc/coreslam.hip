@@ -196,8 +196,12 @@ extern "C" int32_t slamhip_cs_destroy(slamhip_cs *cs)
 {
     if (!cs) return SLAMHIP_OK;
     (void)hipSetDevice(cs->ctx->device);
-    if (!cs->ctx->poisoned) (void)hipStreamSynchronize(cs->ctx->stream);     // (a poisoned context's stream may never drain: slamhip_ctx_destroy bounds that wait)
+    // (a poisoned context's stream may never drain: slamhip_ctx_destroy bounds that wait.  The helper streams are the context's:
+    // what this object put into them -- searches in the side stream among it -- is waited for BEFORE anything is freed, the streams stay)
+    if (!cs->ctx->poisoned) { (void)hipStreamSynchronize(cs->ctx->stream); (void)hipStreamSynchronize(cs->side_stream); (void)hipStreamSynchronize(cs->mirror_stream); }
     cs_plan_free(cs);
+    if (cs->ev_ov_op) (void)hipEventDestroy(cs->ev_ov_op);
+    if (cs->ev_ov_side) (void)hipEventDestroy(cs->ev_ov_side);
     (void)hipFree(cs->d_hole); (void)hipFree(cs->d_obst);
     (void)hipFree(cs->d_scan_blob); if (cs->h_scan_blob) (void)hipHostFree(cs->h_scan_blob);
     (void)hipFree(cs->d_scan_flag);
@@ -208,8 +212,6 @@ extern "C" int32_t slamhip_cs_destroy(slamhip_cs *cs)
     (void)hipFree(cs->d_k1_gmin); (void)hipFree(cs->d_k1_acc); (void)hipFree(cs->d_k1_ring);
     if (cs->h_key) (void)hipHostFree(cs->h_key);
     (void)hipFree(cs->d_rep); if (cs->h_rep) (void)hipHostFree(cs->h_rep);
-    // (the helper streams are the context's: what this object put into them is waited for, the streams stay)
-    if (!cs->ctx->poisoned) { (void)hipStreamSynchronize(cs->mirror_stream); (void)hipStreamSynchronize(cs->side_stream); }
     (void)hipFree(cs->d_side_arrive);
     (void)hipFree(cs->spec_offs_flat); (void)hipFree(cs->spec_ev_off); (void)hipFree(cs->spec_ev_idx); (void)hipFree(cs->spec_grp_bounds);
     (void)hipFree(cs->cool_offs_flat); (void)hipFree(cs->cool_ev_off); (void)hipFree(cs->cool_ev_idx); (void)hipFree(cs->cool_grp_bounds);
@@ -277,6 +279,7 @@ extern "C" int32_t slamhip_cs_reset(slamhip_cs *cs, int32_t unmapped)
     SH_CHECK_ARG(unmapped >= -128 && unmapped <= 127);
     SH_HIP(hipSetDevice(cs->ctx->device));
     const size_t n = (size_t)cs->hs * cs->hs;
+    SH_TRY(cs_overlap_join(cs));
     hipLaunchKernelGGL(k_fill_u16, dim3(1024), dim3(256), 0, cs->ctx->stream, cs->d_hole, n,
                        (uint16_t)((0 + 65500) / 2));                       // :169 (TS_OBSTACLE + TS_NO_OBSTACLE) / 2
     SH_TRY(cs_obstacle_flush(cs));
@@ -292,6 +295,7 @@ extern "C" int32_t slamhip_cs_holemap_upload(slamhip_cs *cs, const uint16_t *pix
 {
     SH_CHECK_ARG(cs && pix && n == (size_t)cs->hs * cs->hs);
     SH_HIP(hipSetDevice(cs->ctx->device));
+    SH_TRY(cs_overlap_join(cs));
     SH_HIP(hipMemcpyAsync(cs->d_hole, pix, n * sizeof(uint16_t), hipMemcpyHostToDevice, cs->ctx->stream));
     SH_TRY(cs_holemap_dirty_set(cs, true));
     SH_TRY(cs_holemap_span_set(cs, true));
@@ -302,6 +306,7 @@ extern "C" int32_t slamhip_cs_holemap_download(slamhip_cs *cs, uint16_t *pix, si
 {
     SH_CHECK_ARG(cs && pix && n == (size_t)cs->hs * cs->hs);
     SH_HIP(hipSetDevice(cs->ctx->device));
+    SH_TRY(cs_overlap_join(cs));
     SH_HIP(hipMemcpyAsync(pix, cs->d_hole, n * sizeof(uint16_t), hipMemcpyDeviceToHost, cs->ctx->stream));
     SH_HIP(hipStreamSynchronize(cs->ctx->stream));
     return SLAMHIP_OK;
@@ -647,6 +652,7 @@ static inline uint32_t part1by1(uint32_t x)
 static int32_t cs_set_scan_begin(slamhip_cs *cs, int32_t n)
 {
     g_sst.start();
+    SH_TRY(cs_overlap_join(cs));                       // (searches in the side stream read the blocks and tables rewritten below)
     cs->n_points = 0;                                  // (stays "no scan" if anything below fails)
     cs->n_rb = 0;
     if (n > cs->cap_points) {
@@ -926,6 +932,7 @@ int32_t cs_flush_scan(slamhip_cs *cs)
 {
     cs->blob_use[cs->scan_buf] = ++cs->launch_count;             // (called by every launcher that reads the scan)
     if (!cs->upload_pending) return SLAMHIP_OK;
+    SH_TRY(cs_overlap_join(cs));                                 // (a search in the side stream may still read the block the upload writes)
     // (the upload state is committed once the launch that carries it is in the stream: on an error the scan stays pending)
     SH_TRY(sh_upload(cs->ctx, cs->h_scan_blob, cs->d_scan_cur, cs->upload_bytes, (uint32_t *)cs->h_key + 28, cs->upload_seq + 1));
     cs_plan_inputs_pending(cs);
@@ -966,6 +973,7 @@ extern "C" int32_t slamhip_cs_distance_pxcs(slamhip_cs *cs, const float *pxcs, i
     bool sane = true;
     for (size_t i = 0; i < (size_t)K * 4; i++) if (!(fabsf(pxcs[i]) < 1.0e9f)) { sane = false; break; }
     cs->shard_first = cs->shard_count = -1;        // evaluation buffers no longer hold the offset shard
+    SH_TRY(cs_overlap_join(cs));
     SH_HIP(hipMemcpyAsync(cs->d_pxcs, pxcs, sizeof(float) * 4 * (size_t)K, hipMemcpyHostToDevice, cs->ctx->stream));
     int *saved = cs->d_ev_idx; cs->d_ev_idx = nullptr;          // identity: evaluation order == flat order
     int32_t rc = cs_launch_distance(cs, 0, nullptr, K, out_dist != nullptr, sane, cs->d_key);
@@ -984,6 +992,7 @@ extern "C" int32_t slamhip_cs_distance_poses(slamhip_cs *cs, const float *poses,
     bool sane = true;
     for (size_t i = 0; i < (size_t)K * 3; i++) if (!(fabsf(poses[i]) < (i % 3 == 2 ? 6.0e4f : 1.0e6f))) { sane = false; break; }
     cs->shard_first = cs->shard_count = -1;
+    SH_TRY(cs_overlap_join(cs));                   // (a search in the side stream may still read the list)
     // stage the poses in d_ev_off (same 3-float layout)
     SH_HIP(hipMemcpyAsync(cs->d_ev_off, poses, sizeof(float) * 3 * (size_t)K, hipMemcpyHostToDevice, cs->ctx->stream));
     int *saved = cs->d_ev_idx; cs->d_ev_idx = nullptr;
@@ -1009,6 +1018,7 @@ extern "C" int32_t slamhip_cs_set_offsets(slamhip_cs *cs, const float *offs, int
 {
     SH_CHECK_ARG(cs && n >= 0 && (offs || n == 0));
     SH_HIP(hipSetDevice(cs->ctx->device));
+    SH_TRY(cs_overlap_join(cs));
     SH_HIP(hipStreamSynchronize(cs->ctx->stream));
     SH_TRY(ensure_offsets_capacity(cs, n));
     cs->n_offs = n;
@@ -1049,6 +1059,7 @@ static int32_t cs_generate(slamhip_cs *cs, int32_t n, float sigma_xy, float sigm
 {
     SH_CHECK_ARG(cs && n >= 0);
     SH_HIP(hipSetDevice(cs->ctx->device));
+    SH_TRY(cs_overlap_join(cs));
     if (n != cs->n_offs || !cs->d_offs_flat) {
         SH_HIP(hipStreamSynchronize(cs->ctx->stream));
         SH_TRY(ensure_offsets_capacity(cs, n));
@@ -1154,6 +1165,7 @@ extern "C" int32_t slamhip_cs_prepared_lists(slamhip_cs *cs, uint64_t *out_serve
 int32_t cs_flush_generate(slamhip_cs *cs)
 {
     if (!cs->gen_pending) return SLAMHIP_OK;
+    SH_TRY(cs_overlap_join(cs));
     cs->gen_pending = false;
     hipLaunchKernelGGL(k_generate_offsets, dim3(sh_div_up(cs->n_offs, 256)), dim3(256), 0, cs->ctx->stream,
                        cs->d_offs_flat, cs->n_offs, cs->gen_sigma_xy, cs->gen_sigma_theta, cs->gen_seed, cs->gen_stream,
@@ -1246,6 +1258,7 @@ static int32_t ensure_shard(slamhip_cs *cs, int first, int count)
         return memcmp(p.data(), cs->h_grp_dth.data(), 4 * a) != 0 || memcmp(p.data() + a, cs->h_grp_dxy.data(), 4 * b) != 0 ||
                memcmp(p.data() + a + b, cs->h_grp_lohi.data(), 4 * c) != 0;
     };
+    SH_TRY(cs_overlap_join(cs));                                   // (a search in the side stream may still read the evaluation list rewritten below)
     cs_plan_inputs_pending(cs);                                    // (every branch below launches the gather in the operator's stream)
     // a pending scan upload rides on the gather launch as one more workgroup
     const int up_wg = cs->upload_pending ? SH_UPLOAD_PARTS : 0;
@@ -1350,18 +1363,26 @@ extern "C" int32_t slamhip_cs_search_shard_async(slamhip_cs *cs, const float pos
     return search_enqueue(cs, pose, first, count, d_out_key);     // prep arms the key, K1/K1r min into it
 }
 
-// Enqueue-only form whose result word the handle owns (a ring of K1_RING_SLOTS words): K1 needs no last finisher for it -- the
-// finishing workgroups min straight into the word, which the previous ring launch left all ones (distance.hip, ring mode).
-extern "C" int32_t slamhip_cs_search_shard_enqueue(slamhip_cs *cs, const float pose[3], int32_t first, int32_t count,
-                                                   const uint64_t **d_key)
+// Enqueue-only form whose result word the handle owns (a ring of K1_RING_SLOTS words).  By default consecutive calls alternate
+// between the operator's stream and the context's side stream, so that their launches overlap on the device, and the launch's LAST
+// FINISHER stores the key into the word (the chain of the _async form: a word cannot be rested from another stream; distance.hip,
+// cs_launch_distance); every other call of the handle, and slamhip_ctx_synchronize, orders itself behind both streams.
+// overlap = false or SLAMHIP_K1_OVERLAP=0: ring mode in the operator's stream -- no last finisher, the finishing workgroups min
+// straight into the word, which the previous ring launch left all ones.
+int32_t cs_search_shard_enqueue(slamhip_cs *cs, const float pose[3], int32_t first, int32_t count, const uint64_t **d_key, bool overlap)
 {
     SH_CHECK_ARG(cs && d_key);
-    cs->k1_ring_request = true;
+    cs->k1_ring_request = true; cs->k1_ring_may_overlap = overlap;
     const int32_t rc = search_enqueue(cs, pose, first, count, nullptr);
-    cs->k1_ring_request = false;
+    cs->k1_ring_request = false; cs->k1_ring_may_overlap = false;
     SH_TRY(rc);
     *d_key = cs->k1_ring_last;
     return SLAMHIP_OK;
+}
+extern "C" int32_t slamhip_cs_search_shard_enqueue(slamhip_cs *cs, const float pose[3], int32_t first, int32_t count,
+                                                   const uint64_t **d_key)
+{
+    return cs_search_shard_enqueue(cs, pose, first, count, d_key, true);
 }
 
 // Waits for the handle's stream and reads one result word of the ring (or any 8-byte device word of this context).
@@ -1369,6 +1390,7 @@ extern "C" int32_t slamhip_cs_key_read(slamhip_cs *cs, const uint64_t *d_key, ui
 {
     SH_CHECK_ARG(cs && d_key && out_key);
     SH_HIP(hipSetDevice(cs->ctx->device));
+    SH_TRY(cs_overlap_join(cs));                                   // (the word may be a slot of a search in the side stream)
     SH_HIP(hipMemcpyAsync(cs->h_key + 8, d_key, sizeof(uint64_t), hipMemcpyDeviceToHost, cs->ctx->stream));
     SH_HIP(hipStreamSynchronize(cs->ctx->stream));
     *out_key = cs->h_key[8];
@@ -1570,6 +1592,7 @@ extern "C" int32_t slamhip_cs_selfcheck_failures(slamhip_cs *cs, uint32_t *out)
     SH_CHECK_ARG(cs && out);
     SH_HIP(hipSetDevice(cs->ctx->device));
     unsigned int *h = (unsigned int *)(cs->h_key + 8);
+    SH_TRY(cs_overlap_join(cs));                                   // (searches in the side stream count into the block too)
     SH_HIP(hipMemcpyAsync(h, cs->d_verify, sizeof(unsigned int) * 8, hipMemcpyDeviceToHost, cs->ctx->stream));
     SH_HIP(hipStreamSynchronize(cs->ctx->stream));
     *out = h[0];
@@ -1582,6 +1605,7 @@ extern "C" int32_t slamhip_cs_selfcheck_counts(slamhip_cs *cs, uint32_t out[8])
     SH_CHECK_ARG(cs && out);
     SH_HIP(hipSetDevice(cs->ctx->device));
     unsigned int *h = (unsigned int *)(cs->h_key + 8);
+    SH_TRY(cs_overlap_join(cs));                                   // (searches in the side stream count into the block too)
     SH_HIP(hipMemcpyAsync(h, cs->d_verify, sizeof(unsigned int) * 8, hipMemcpyDeviceToHost, cs->ctx->stream));
     SH_HIP(hipStreamSynchronize(cs->ctx->stream));
     for (int k = 0; k < 8; k++) out[k] = h[k];

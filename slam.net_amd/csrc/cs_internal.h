@@ -73,8 +73,9 @@ struct slamhip_cs {
     int cap_cand;
     float4 *d_pxcs;               // [cap_cand] (px,py,c,s) in evaluation order
     void *d_partial; size_t cap_partial;       // K1 partial rows (bytes)
-    unsigned long long *d_k1_gmin;              // K1: [0] running minimum of the finished candidates' keys (all ones between launches), [1] their count (zero)
-    unsigned long long *d_k1_acc;               // K1: per-candidate accumulators [groups][K1_GROUP] (zero between launches)
+    unsigned long long *d_k1_gmin;              // K1: [0] running minimum of the finished candidates' keys (all ones between launches), [1] their count (zero); [2], [3]: the same for searches in the side stream
+    unsigned long long *d_k1_acc;               // K1: per-candidate accumulators [2][groups][K1_GROUP] (zero between launches): two sets -- searches on the side stream
+                                                // (below: overlap) add into set 1, everything else into set 0, so two launches in flight never share a word
     int k1_cap_groups;                          // (in units of K1_GROUP candidates)
     int k1_group;                               // candidates per group of the materialised evaluation list (its jitter bounds are per group)
     // K1 launch layout: per group of 1024 evaluation-order candidates the theta range (rad) and translation spread
@@ -114,10 +115,23 @@ struct slamhip_cs {
     unsigned *k1_done_flag; unsigned k1_done_val;   // the next search launch ends with k1_done_val -> *k1_done_flag (pinned host word), if set
     bool k1_done_armed;           // ... and it will (tiled kernel)
     unsigned long long *k1_sig; unsigned long long k1_sig_val; bool k1_sig_armed;   // the same for an HSA signal (slamhip_comm: the collectives' stream waits for it)
-    // enqueue-only searches (slamhip_cs_search_shard_enqueue): a ring of result words, all ones at rest; a ring launch mins into
-    // slot k1_ring_pos and leaves slot k1_ring_pos + 1 all ones for the next ring launch (distance.hip)
-    uint64_t *d_k1_ring; unsigned k1_ring_pos;
+    // enqueue-only searches (slamhip_cs_search_shard_enqueue): a ring of result words.  A ring launch either MINS into slot
+    // k1_ring_pos, which must be all ones, and leaves slot k1_ring_pos + 1 all ones for the next ring launch (distance.hip, ring
+    // mode) -- or, where consecutive launches overlap in two streams (below), has its last finisher STORE the key there: a slot is
+    // then never rested from another stream.  k1_ring_rested: the ring position whose slot is known to be all ones (a ring-mode
+    // launch behind a storing one rests its own slot by a fill first).
+    uint64_t *d_k1_ring; unsigned k1_ring_pos, k1_ring_rested;
+    // Overlap of consecutive enqueue-only searches (distance.hip, cs_launch_distance): ring launches at odd ring positions go into the
+    // context's side stream, everything else stays in the operator's stream.  The two streams are tied lazily, by at most one event
+    // per change of direction and none between back-to-back ring launches:
+    //   ov_op_dirty       the operator's stream has had work since the side stream last waited for it (anything a search may read:
+    //                     scan upload, candidate gather or generation, map update, upload, fills) -- the next side launch waits first;
+    //   ov_side_unjoined  the side stream holds searches the operator's stream is not ordered behind -- cs_overlap_join ties them
+    //                     before any other work of this handle enters the operator's stream and in every call that waits or reads.
+    bool ov_op_dirty, ov_side_unjoined;
+    hipEvent_t ev_ov_op, ev_ov_side;
     bool k1_ring_request;         // the next search launch is a ring launch ...
+    bool k1_ring_may_overlap;     // ... whose slot nothing in the operator's stream reads right behind it: it may go into the side stream (slamhip_cs_search_shard_enqueue)
     uint64_t *k1_ring_last;       // ... and this is the slot it used
     // the search's plan (distance.hip, k1_plan): K1_PLAN_SLOTS sets of buffers used in turn, filled on a stream of their own
     hipStream_t plan_stream;
@@ -125,10 +139,15 @@ struct slamhip_cs {
     int plan_cap_wgs;
     uint32_t plan_seq;            // stamps handed out (a stamp is never 0 and never reused while its slot holds it)
     uint32_t plan_count;          // plans launched (slot = plan_count % K1_PLAN_SLOTS)
-    uint32_t k1_launches;         // tiled search launches so far: each stores its number into word 25 of h_key when it STARTS (k1_args::started)
-    uint32_t plan_slot_user[K1_PLAN_SLOTS];   // the number of the search launch that read the slot last
+    uint32_t k1_launches;         // tiled search launches so far: each stores its number into the started word of ITS stream when it STARTS
+                                  // (k1_args::started; words 25 -- the operator's stream -- and 26 -- the side stream -- of h_key): everything before it in that stream has finished
+    int k1_last_stream;           // the stream of the newest tiled search launch (0 the operator's, 1 the side stream)
+    uint32_t k1_cross_no[2];      // [s] = n: a join has ordered every launch of the OTHER stream numbered >= n behind the launches of stream s numbered < n (0: none)
+    uint32_t plan_slot_user[K1_PLAN_SLOTS];   // the number of the search launch that read the slot last ...
+    uint8_t plan_slot_stream[K1_PLAN_SLOTS];  // ... and the stream it was put into (0 operator's, 1 side)
     uint32_t plan_inputs_after;   // the plan kernel reads what launches in the operator's stream wrote (candidate gather, scan upload): it may only be
-                                  // launched once the search launch of this number has started (0: nothing pending)
+                                  // launched once a search launch of this number or later has started, in either stream -- a side launch of that
+                                  // number waits for the operator's stream first (ov_op_dirty) -- (0: nothing pending)
     uint64_t plan_stats[4];       // searches launched with a plan | without | host waits for a free slot | plans skipped because their inputs were still in flight
     // the search report (slamhip_cs_search_report and the fused report forms; distance.hip): partial slots and the finished report on
     // the device, a pinned block the last launch delivers into (report | key | pose | its own completion word)
@@ -175,7 +194,10 @@ int32_t cs_alloc_candidates(slamhip_cs *cs, int count);
 int32_t cs_plan_drain(slamhip_cs *cs);
 void    cs_plan_free(slamhip_cs *cs);
 // a launch in the operator's stream writes what the next plan launches read (candidate gather, scan upload): see plan_inputs_after
-static inline void cs_plan_inputs_pending(slamhip_cs *cs) { cs->plan_inputs_after = cs->k1_launches + 1; }
+static inline void cs_plan_inputs_pending(slamhip_cs *cs) { cs->plan_inputs_after = cs->k1_launches + 1; cs->ov_op_dirty = true; }
+// Before work of this handle other than an enqueue-only search enters the operator's stream, and before any wait or read: the
+// operator's stream is ordered behind the searches in the side stream (one event, only if there are any) and noted as changed
+int32_t cs_overlap_join(slamhip_cs *cs);
 // launches the scan upload that slamhip_cs_set_scan left pending (every launch that reads the scan calls it first)
 int32_t cs_flush_scan(slamhip_cs *cs);
 int32_t cs_launch_distance(slamhip_cs *cs, int mode, const float pose[3], int count, bool want_dist, bool cand_sane,
@@ -194,6 +216,8 @@ void cs_layout_idle_refresh(slamhip_cs *cs);   // host only: call between a sear
 // coreslam.hip: produces a device-generated jitter list that is still pending (slamhip_cs_generate_offsets)
 int32_t cs_flush_generate(slamhip_cs *cs);
 int32_t cs_side_join(slamhip_cs *cs);
+// slamhip_cs_search_shard_enqueue; overlap = false: the launch stays in the operator's stream (a caller that consumes the slot there at once)
+int32_t cs_search_shard_enqueue(slamhip_cs *cs, const float pose[3], int32_t first, int32_t count, const uint64_t **d_key, bool overlap);
 #define CS_RC_NO_PRELAUNCH 77                   // cs_launch_distance, internal: a prelaunch would need a new layout -- nothing was launched
 bool cs_fused_k1_delivers();                    // coreslam.hip: SLAMHIP_FUSED_K1_DELIVERS (the fused scan's search delivers its own result)
 int32_t cs_search_and_update_prelaunched(slamhip_cs *cs, const float *xy, int32_t n, const float pose[3], float hole_width, int32_t quality,

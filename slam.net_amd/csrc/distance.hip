@@ -237,7 +237,8 @@ struct k1_args {
                                                 // words 0-1 and done_val into word 15 -- or null
     // Enqueue-only search (slamhip_cs_search_shard_enqueue): the result word is a slot of the handle's ring, all ones when the launch
     // starts -- the workgroups that finish candidates min their keys straight into it (no return, no count, no last finisher: the
-    // END OF THE LAUNCH is the completion) -- and this launch leaves the NEXT slot all ones for the next one.  Null: key_out + the chain.
+    // END OF THE LAUNCH is the completion) -- and this launch leaves the NEXT slot all ones for the next one.  Null: key_out + the chain
+    // (the enqueue-only searches that overlap in two streams, cs_launch_distance: key_out is the slot, nothing is rested).
     unsigned long long *ring_slot, *ring_reset;
     // The PLAN of a search (k1_plan, launched beside the search on a stream of its own, round 6): every workgroup's step records
     // (bounds -> boxes -> tile steps: what its prologue used to work out before its first tile), left in device memory and STAMPED
@@ -245,7 +246,7 @@ struct k1_args {
     // itself as before (a plan that is late, or was never made, costs time, never a result).  plan_rec: K1_PLAN_REC_WORDS words per
     // workgroup, every 8-word unit carrying its own stamp (see k1_plan).  Null: no plan.
     uint2 *plan_rec; uint32_t plan_seq;
-    uint32_t *started; uint32_t launch_no;          // workgroup 0 stores launch_no here when the launch starts (pinned host word): everything before it in the stream has finished
+    uint32_t *started; uint32_t launch_no;          // workgroup 0 stores launch_no here when the launch starts (pinned host word, one per stream): everything before it in ITS stream has finished
     const uint32_t *scan_flag; uint32_t scan_seq;   // a launch that precedes its scan's tables (cs_search_and_update_prelaunched): wait here for scan_seq; bit 31 set: leave
     // launch layout: first the workgroups of the listed groups (expensive ones: more, smaller chunks), then the
     // groups [uni_g0, uni_g0 + uni_ng) with uni_nc chunks each, chunk-major (neighbouring groups work on the same
@@ -1177,6 +1178,18 @@ k1_plan(const k1_args a, const int n_wgs)
 }
 
 // ---- host side --------------------------------------------------------------------------------------
+int32_t cs_overlap_join(slamhip_cs *cs)
+{
+    cs->ov_op_dirty = true;                                        // (the caller is about to put work into the operator's stream)
+    if (!cs->ov_side_unjoined) return SLAMHIP_OK;
+    if (!cs->ev_ov_side) SH_HIP(hipEventCreateWithFlags(&cs->ev_ov_side, hipEventDisableTiming));
+    SH_HIP(hipEventRecord(cs->ev_ov_side, cs->side_stream));
+    SH_HIP(hipStreamWaitEvent(cs->ctx->stream, cs->ev_ov_side, 0));
+    cs->ov_side_unjoined = false;
+    cs->k1_cross_no[1] = cs->k1_launches + 1;                      // (the next launch's number: in the operator's stream it starts behind every launch the side stream holds now)
+    return SLAMHIP_OK;
+}
+
 int32_t cs_plan_drain(slamhip_cs *cs)
 {
     if (cs->plan_stream) SH_HIP(hipStreamSynchronize(cs->plan_stream));
@@ -1840,42 +1853,62 @@ static int k1_cuts_select(slamhip_cs *cs, k1_args &a, int group, int n_groups, b
 }
 
 // The per-candidate accumulators (zero at rest) and the running minimum with its count of finished candidates into a.
-static int32_t k1_acc_alloc(slamhip_cs *cs, int count, k1_args &a)
+// set: 1 for a search put into the side stream, 0 for every other (two launches in flight never add into the same words).
+static int32_t k1_acc_alloc(slamhip_cs *cs, int count, int set, k1_args &a)
 {
     slamhip_ctx *ctx = cs->ctx;
     if (sh_div_up(count, K1_GROUP) + 2 > cs->k1_cap_groups) {
-        if (cs->d_k1_acc) (void)hipFree(cs->d_k1_acc);
+        SH_TRY(cs_overlap_join(cs));                               // (searches in the side stream use the block freed here; the fill below is work of the operator's stream)
+        if (cs->d_k1_acc) { SH_HIP(hipStreamSynchronize(ctx->stream)); (void)hipFree(cs->d_k1_acc); }
         cs->d_k1_acc = nullptr; cs->k1_cap_groups = 0;
         const int cap = sh_div_up(count, K1_GROUP) + sh_div_up(count, K1_GROUP) / 4 + 16;
-        SH_HIP(hipMalloc(&cs->d_k1_acc, sizeof(unsigned long long) * (size_t)cap * K1_GROUP));
-        SH_HIP(hipMemsetAsync(cs->d_k1_acc, 0, sizeof(unsigned long long) * (size_t)cap * K1_GROUP, ctx->stream));
+        SH_HIP(hipMalloc(&cs->d_k1_acc, sizeof(unsigned long long) * 2 * (size_t)cap * K1_GROUP));
+        SH_HIP(hipMemsetAsync(cs->d_k1_acc, 0, sizeof(unsigned long long) * 2 * (size_t)cap * K1_GROUP, ctx->stream));
         cs->k1_cap_groups = cap;
     }
     if (!cs->d_k1_gmin) {
         // the running minimum (all ones at rest) and the count of finished candidates (zero at rest): the launch's last
         // finisher leaves them so
-        SH_HIP(hipMalloc(&cs->d_k1_gmin, 16));
-        SH_HIP(hipMemsetAsync(cs->d_k1_gmin, 0xff, 8, ctx->stream));
-        SH_HIP(hipMemsetAsync((char *)cs->d_k1_gmin + 8, 0, 8, ctx->stream));
+        SH_HIP(hipMalloc(&cs->d_k1_gmin, 32));
+        for (int s = 0; s < 2; s++) {
+            SH_HIP(hipMemsetAsync((char *)cs->d_k1_gmin + 16 * s, 0xff, 8, ctx->stream));
+            SH_HIP(hipMemsetAsync((char *)cs->d_k1_gmin + 16 * s + 8, 0, 8, ctx->stream));
+        }
+        cs->ov_op_dirty = true;
     }
-    a.gmin = cs->d_k1_gmin; a.done = (unsigned *)((char *)cs->d_k1_gmin + 8); a.acc = cs->d_k1_acc;
+    a.gmin = cs->d_k1_gmin + 2 * set; a.done = (unsigned *)((char *)cs->d_k1_gmin + 16 * set + 8);
+    a.acc = cs->d_k1_acc + (size_t)set * (size_t)cs->k1_cap_groups * K1_GROUP;
     return SLAMHIP_OK;
 }
 
 // ---- the plan (k1_plan): one launch per search on a stream of its own, beside the search ---------------------------------
 // Made for every search with jitter bounds (mode 1) whose inputs are known to be in memory: the plan launch is not ordered
 // behind the operator's stream, so after a candidate gather or a scan upload in that stream (plan_inputs_after) it waits
-// until a search launch behind them has STARTED (the started word).  A slot of the plan buffers is reused K1_PLAN_SLOTS
-// plans later, when the search that read it has finished -- i.e. a later search launch has started; the host waits for
-// that if it is that far ahead of the device (it then is in nobody's way).  SLAMHIP_K1_PLAN=0: never.
-static int32_t k1_plan_launch(slamhip_cs *cs, k1_args &a, int mode, int group, int n_wgs, bool lat)
+// until a search launch behind them has STARTED (the started words).  A slot of the plan buffers is reused K1_PLAN_SLOTS
+// plans later, when the search that read it has finished -- i.e. a later search launch OF ITS STREAM has started
+// (k1_launch_finished); the host waits for that if it is that far ahead of the device (it then is in nobody's way).
+// SLAMHIP_K1_PLAN=0: never.
+// The search launches run in two streams (cs_launch_distance), each with a started word of its own: a launch that has started
+// says nothing about the other stream's launches, whatever their numbers.
+static inline volatile uint32_t *k1_started_word(const slamhip_cs *cs, int s) { return (volatile uint32_t *)cs->h_key + 25 + s; }
+// Has search launch `no` of stream s finished?  Yes once a later launch of its stream has started, or a launch of the other
+// stream that a join (k1_cross_no) ordered behind it.
+static inline bool k1_launch_finished(const slamhip_cs *cs, int s, uint32_t no)
+{
+    if ((int32_t)(*k1_started_word(cs, s) - (no + 1)) >= 0) return true;
+    const uint32_t x = cs->k1_cross_no[s];
+    return x != 0 && (int32_t)(x - no) > 0 && (int32_t)(*k1_started_word(cs, s ^ 1) - x) >= 0;
+}
+// s: the stream the search launch goes into (0 the operator's, 1 the side stream)
+static int32_t k1_plan_launch(slamhip_cs *cs, k1_args &a, int mode, int group, int n_wgs, bool lat, int s)
 {
     slamhip_ctx *ctx = cs->ctx;
     static const int plan_env = (int)sh_env_int("SLAMHIP_K1_PLAN", 1);
-    volatile uint32_t *h_started = (volatile uint32_t *)cs->h_key + 25;
-    a.started = (uint32_t *)cs->h_key + 25; a.launch_no = ++cs->k1_launches;
+    const uint32_t prev_no = cs->k1_launches; const int prev_s = cs->k1_last_stream;   // the search launch before this one, in whichever stream
+    a.started = (uint32_t *)cs->h_key + 25 + s; a.launch_no = ++cs->k1_launches;
+    cs->k1_last_stream = s;
     a.plan_rec = nullptr; a.plan_seq = 0;
-    // Which launches get one: those that will WAIT in the stream -- the search launch before this one has not even started
+    // Which launches get one: those that will WAIT -- the search launch before this one (the word of ITS stream) has not even started
     // (the started word), so this one is at least a whole search away from running and its plan has time to arrive: the
     // throughput forms (enqueue-only searches, the batched all-reduce form) once the host runs ahead of the device.  A search
     // that starts at once -- a blocking call, the first launches behind a synchronise, the per-scan flows, whose search follows
@@ -1885,15 +1918,16 @@ static int32_t k1_plan_launch(slamhip_cs *cs, k1_args &a, int mode, int group, i
     // search -- by the plan launch, or shared between a group's workgroups inside the search launch through memory -- instead of
     // by every workgroup: reading them back costs a launch what the trigonometry does, 15.2 us with or without at the headline size.)
     static const int plan_always = (int)sh_env_int("SLAMHIP_K1_PLAN_ALWAYS", 0);   // (tests: a plan for every eligible launch -- most arrive late, the race the stamps are for)
-    const bool stream_busy = plan_always || (int32_t)(*h_started - (a.launch_no - 1)) < 0;
+    const bool stream_busy = plan_always || (prev_no != 0 && (int32_t)(*k1_started_word(cs, prev_s) - prev_no) < 0);
     bool plan_on = plan_env && mode == 1 && stream_busy && a.grp_bounds != nullptr && !cs->k1_prelaunch && !lat && !ctx->mail_off;
     if (plan_on && cs->plan_inputs_after != 0) {
-        if ((int32_t)(*h_started - cs->plan_inputs_after) >= 0) cs->plan_inputs_after = 0;
+        if ((int32_t)(*k1_started_word(cs, 0) - cs->plan_inputs_after) >= 0 || (int32_t)(*k1_started_word(cs, 1) - cs->plan_inputs_after) >= 0) cs->plan_inputs_after = 0;
         else { plan_on = false; cs->plan_stats[3]++; }
     }
     if (plan_on) {
         if (n_wgs > cs->plan_cap_wgs) {
-            SH_HIP(hipStreamSynchronize(ctx->stream));          // (searches in flight read the buffers)
+            SH_TRY(cs_overlap_join(cs));
+            SH_HIP(hipStreamSynchronize(ctx->stream));          // (searches in flight, in either stream, read the buffers)
             const int cw = std::max(cs->plan_cap_wgs, n_wgs + n_wgs / 4 + 64);
             cs_plan_free(cs);
             for (int i = 0; i < K1_PLAN_SLOTS; i++) {
@@ -1905,18 +1939,19 @@ static int32_t k1_plan_launch(slamhip_cs *cs, k1_args &a, int mode, int group, i
         }
         const unsigned slot = cs->plan_count % K1_PLAN_SLOTS;
         const uint32_t user = cs->plan_slot_user[slot];
-        if (user != 0 && (int32_t)(*h_started - (user + 1)) < 0) {
+        const int us = cs->plan_slot_stream[slot];
+        if (user != 0 && !k1_launch_finished(cs, us, user)) {
             // The host is K1_PLAN_SLOTS - 1 searches ahead of the device: it waits for the slot -- backpressure, the device has
             // work queued -- but never longer than 20 ms or the context's wait bound; past that the search goes without a plan
             // (nothing fails because of a plan).
             cs->plan_stats[2]++;
             const int64_t bound_us = 1000 * (ctx->wait_timeout_ms > 0 && ctx->wait_timeout_ms < 20 ? ctx->wait_timeout_ms : 20);
             const double t0w = k1_now_us();
-            for (int spins = 0; (int32_t)(*h_started - (user + 1)) < 0; spins++) {
+            for (int spins = 0; !k1_launch_finished(cs, us, user); spins++) {
                 __builtin_ia32_pause();
                 if ((spins & 1023) == 1023 && k1_now_us() - t0w > (double)bound_us) break;
             }
-            if ((int32_t)(*h_started - (user + 1)) < 0) { plan_on = false; cs->plan_stats[3]++; }
+            if (!k1_launch_finished(cs, us, user)) { plan_on = false; cs->plan_stats[3]++; }
         }
     }
     if (plan_on) {
@@ -1928,7 +1963,7 @@ static int32_t k1_plan_launch(slamhip_cs *cs, k1_args &a, int mode, int group, i
         else if (group == K1_GROUP_SMALL) hipLaunchKernelGGL((k1_plan<K1_GROUP_SMALL, 1>), pgrid, dim3(64), 0, cs->plan_stream, a, n_wgs);
         else hipLaunchKernelGGL((k1_plan<K1_GROUP, 2>), pgrid, dim3(64), 0, cs->plan_stream, a, n_wgs);
         SH_HIP(hipGetLastError());
-        cs->plan_slot_user[slot] = a.launch_no;
+        cs->plan_slot_user[slot] = a.launch_no; cs->plan_slot_stream[slot] = (uint8_t)s;
         cs->plan_count++; cs->plan_stats[0]++;
     }
     if (!plan_on) cs->plan_stats[1]++;
@@ -1938,12 +1973,12 @@ static int32_t k1_plan_launch(slamhip_cs *cs, k1_args &a, int mode, int group, i
 // The search launch: k1_search_tiled for the mode, the check build (SLAMHIP_K1_VERIFY) or a heading lattice, and the group size
 // (candidates per lane: 4 for K1_GROUP_BIG, 1 for K1_GROUP_SMALL, 2 for K1_GROUP -- 512 lanes, 8 waves, measured best or equal
 // from 16k to 256k candidates on MI355X).
-static void k1_search_launch(slamhip_cs *cs, const k1_args &a, int mode, int group, int n_wgs, size_t lds, bool verify, bool lat2, bool lat4)
+static void k1_search_launch(slamhip_cs *cs, const k1_args &a, int mode, int group, int n_wgs, size_t lds, bool verify, bool lat2, bool lat4, hipStream_t st)
 {
     slamhip_ctx *ctx = cs->ctx;
-    sh_timer t(ctx, SLAMHIP_K_CS_DISTANCE);
-#define K1_LAUNCH(M, V, C, G) hipLaunchKernelGGL((k1_search_tiled<M, V, C, G>), dim3(n_wgs), dim3(G / C), lds, ctx->stream, a)
-#define K1_LAUNCH_LAT(C, G) hipLaunchKernelGGL((k1_search_tiled<1, false, C, G, true>), dim3(n_wgs), dim3(G / C), lds, ctx->stream, a)
+    sh_timer t(ctx, SLAMHIP_K_CS_DISTANCE);                        // (timed launches are never put into the side stream)
+#define K1_LAUNCH(M, V, C, G) hipLaunchKernelGGL((k1_search_tiled<M, V, C, G>), dim3(n_wgs), dim3(G / C), lds, st, a)
+#define K1_LAUNCH_LAT(C, G) hipLaunchKernelGGL((k1_search_tiled<1, false, C, G, true>), dim3(n_wgs), dim3(G / C), lds, st, a)
 #define K1_LAUNCH_C(M, V) { if (group == K1_GROUP_BIG) K1_LAUNCH(M, V, 4, K1_GROUP_BIG); else if (group == K1_GROUP_SMALL) K1_LAUNCH(M, V, 1, K1_GROUP_SMALL); else K1_LAUNCH(M, V, 2, K1_GROUP); }
     if (lat2) K1_LAUNCH_LAT(2, K1_GROUP);
     else if (lat4) K1_LAUNCH_LAT(4, K1_GROUP_BIG);
@@ -1962,6 +1997,7 @@ static int32_t k1_launch_fallback(slamhip_cs *cs, int mode, const float p[3], in
     const int n_rb = cs->n_rb;
     cs->k1_pose_written = false; cs->k1_done_armed = false; cs->k1_sig_armed = false;
     SH_TRY(cs_side_join(cs));
+    SH_TRY(cs_overlap_join(cs));                                   // (always in the operator's stream: candidates and partial sums have one set of buffers)
     {
         sh_timer t(ctx, SLAMHIP_K_CS_PREP);
         const dim3 grid(sh_div_up(count, K1_THREADS));
@@ -1996,7 +2032,7 @@ static int32_t k1_launch_fallback(slamhip_cs *cs, int mode, const float p[3], in
     SH_HIP(hipGetLastError());
     if (ring_slot) {                                               // (the fallback's first kernel arms its own key; the next slot is rested by a fill)
         SH_HIP(hipMemsetAsync(ring_reset, 0xFF, sizeof(uint64_t), ctx->stream));
-        cs->k1_ring_last = (uint64_t *)ring_slot; cs->k1_ring_pos++;
+        cs->k1_ring_last = (uint64_t *)ring_slot; cs->k1_ring_pos++; cs->k1_ring_rested = cs->k1_ring_pos;
     }
     return SLAMHIP_OK;
 }
@@ -2145,12 +2181,29 @@ int32_t cs_launch_distance(slamhip_cs *cs, int mode, const float pose[3], int co
         if (!cs->d_k1_ring) {
             SH_HIP(hipMalloc(&cs->d_k1_ring, sizeof(uint64_t) * K1_RING_SLOTS));
             SH_HIP(hipMemsetAsync(cs->d_k1_ring, 0xFF, sizeof(uint64_t) * K1_RING_SLOTS, ctx->stream));
-            cs->k1_ring_pos = 0;
+            cs->k1_ring_pos = 0; cs->k1_ring_rested = 0; cs->ov_op_dirty = true;
         }
         ring_slot = (unsigned long long *)cs->d_k1_ring + cs->k1_ring_pos % K1_RING_SLOTS;
         ring_reset = (unsigned long long *)cs->d_k1_ring + (cs->k1_ring_pos + 1) % K1_RING_SLOTS;
         key = ring_slot;
     }
+    // Consecutive enqueue-only searches OVERLAP: the launches of slamhip_cs_search_shard_enqueue at odd ring positions go into the
+    // context's side stream, so search n + 1 is not ordered behind search n and its workgroups take the compute-unit slots that
+    // search n's workgroups free -- one launch's ragged tail lies under the next one's ramp.  Only the plain enqueue-only search
+    // alternates -- the tiled kernel, no scan flag (a launch ahead of its scan), no distances kept, no timing; SLAMHIP_K1_OVERLAP=0:
+    // none does, and every ring launch is in ring mode.  What two launches in flight would share is kept apart: the accumulators,
+    // the running minimum and its count (a set per stream, k1_acc_alloc), the started word and the plan slots (k1_plan_launch).  A
+    // ring slot cannot be rested across streams -- the launches of the two streams start in no defined order -- so these launches
+    // do not min into their slot: their last finisher STORES the key there (key_out + the chain, as the _async form), whose
+    // latency at the launch's end the other stream's launch covers.  Everything else enters the operator's stream behind a join
+    // (cs_overlap_join), and a side launch waits for the operator's stream first if that has had work since the last wait
+    // (ov_op_dirty): back-to-back enqueue-only searches record no event at all.
+    static const int overlap_env = (int)sh_env_int("SLAMHIP_K1_OVERLAP", 1);
+    const bool stores = ring && cs->k1_ring_may_overlap && overlap_env != 0 && tiled;    // (the fallback kernels arm and write their key themselves)
+    bool side = stores && (cs->k1_ring_pos & 1u) != 0 && !cs->k1_prelaunch && !want_dist && !cs->k1_keep_dist && ctx->timing == 0;
+#ifdef K1_TIMES
+    side = false;                                                  // (the developer build reads its stamps behind the operator's stream)
+#endif
     const float bx = pose ? pose[0] : 0.f, by = pose ? pose[1] : 0.f, bth = pose ? pose[2] : 0.f;
     const float pose3[3] = { bx, by, bth };
 
@@ -2180,7 +2233,7 @@ int32_t cs_launch_distance(slamhip_cs *cs, int mode, const float pose[3], int co
         cs->k1_done_armed = a.done_flag != nullptr;
         a.sig = cs->k1_sig; a.sig_val = cs->k1_sig_val;
         cs->k1_sig_armed = a.sig != nullptr;
-        a.ring_slot = ring_slot; a.ring_reset = ring_reset;
+        a.ring_slot = stores ? nullptr : ring_slot; a.ring_reset = stores ? nullptr : ring_reset;
         a.scan_flag = cs->k1_prelaunch ? cs->d_scan_flag : nullptr; a.scan_seq = cs->scan_flag_seq;
         if (ring && (a.best_pose || a.done_flag || a.sig)) SH_FAIL(SLAMHIP_ERR_STATE, "a ring search delivers nothing but its key");
 
@@ -2188,18 +2241,35 @@ int32_t cs_launch_distance(slamhip_cs *cs, int mode, const float pose[3], int co
         if (!k1_layout_choose(cs, n_groups, budget, have_spread, bth)) { cs->k1_ring_request = ring; return CS_RC_NO_PRELAUNCH; }
         if (!k1_layout_fits_acc(cs)) goto fallback;
         const int n_wgs = k1_cuts_select(cs, a, group, n_groups, have_spread, budget, pose3);
-        SH_TRY(k1_acc_alloc(cs, count, a));
+        // (an enqueue-only search at an even position shares nothing with those in the side stream -- set 0, a word that only launches
+        // of the operator's stream store into -- and writes nothing they read: no join.  One at an ODD position that stays in the
+        // operator's stream (timing switched on in the middle of a queue) stores into a word of the side stream's launches, and a
+        // ring-mode launch rests the next slot, which may be a side launch's: both join.)
+        if (!stores || (!side && (cs->k1_ring_pos & 1u) != 0)) SH_TRY(cs_overlap_join(cs));
+        if (ring && !stores && cs->k1_ring_rested != cs->k1_ring_pos)   // (behind storing launches: nobody has rested this launch's slot)
+            SH_HIP(hipMemsetAsync(ring_slot, 0xFF, sizeof(uint64_t), ctx->stream));
+        SH_TRY(k1_acc_alloc(cs, count, side ? 1 : 0, a));
         if (mode == 1) { cs->k1_last_pose[0] = bx; cs->k1_last_pose[1] = by; cs->k1_last_pose[2] = bth; cs->k1_last_valid = true; }
         static const int no_lat = (int)sh_env_int("SLAMHIP_K1_NO_LATTICE", 0);       // (a lattice list through the ordinary kernel: same results, for comparison)
         const bool lat2 = mode == 1 && !verify && !no_lat && cs->k1_lattice == 2 && group == K1_GROUP;
         const bool lat4 = mode == 1 && !verify && !no_lat && cs->k1_lattice == 4 && group == K1_GROUP_BIG;
         g_cst.lap(1);
         SH_TRY(cs_side_join(cs));
-        SH_TRY(k1_plan_launch(cs, a, mode, group, n_wgs, lat2 || lat4));
+        if (side) {
+            if (cs->ov_op_dirty) {                                 // the side stream waits for what the operator's stream holds: this launch's inputs, the rested slots
+                if (!cs->ev_ov_op) SH_HIP(hipEventCreateWithFlags(&cs->ev_ov_op, hipEventDisableTiming));
+                SH_HIP(hipEventRecord(cs->ev_ov_op, ctx->stream));
+                SH_HIP(hipStreamWaitEvent(cs->side_stream, cs->ev_ov_op, 0));
+                cs->ov_op_dirty = false;
+                cs->k1_cross_no[0] = cs->k1_launches + 1;          // (this launch's number: it and its successors there start behind every earlier launch of the operator's stream)
+            }
+            cs->ov_side_unjoined = true;
+        }
+        SH_TRY(k1_plan_launch(cs, a, mode, group, n_wgs, lat2 || lat4, side ? 1 : 0));
         g_cst.lap(2);
-        k1_search_launch(cs, a, mode, group, n_wgs, lds, verify, lat2, lat4);
+        k1_search_launch(cs, a, mode, group, n_wgs, lds, verify, lat2, lat4, side ? cs->side_stream : ctx->stream);
         SH_HIP(hipGetLastError());
-        if (ring) { cs->k1_ring_last = (uint64_t *)ring_slot; cs->k1_ring_pos++; }
+        if (ring) { cs->k1_ring_last = (uint64_t *)ring_slot; cs->k1_ring_pos++; if (!stores) cs->k1_ring_rested = cs->k1_ring_pos; }
 #ifdef K1_TIMES
         k1_times_report(cs, n_wgs, n_groups, (int)cs->k1_tab_group.size(), group);
 #endif

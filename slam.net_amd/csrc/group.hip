@@ -539,7 +539,7 @@ extern "C" int32_t slamhip_cs_search_allreduce(slamhip_cs *cs, slamhip_comm *c, 
     uint64_t *d_key = c->d_sync_key;
     if (count > 0) {
         const uint64_t *slot = nullptr;
-        rc_local = slamhip_cs_search_shard_enqueue(cs, pose, first, count, &slot);
+        rc_local = cs_search_shard_enqueue(cs, pose, first, count, &slot, false);      // (in the operator's stream: the collective behind it reads the slot)
         if (rc_local != SLAMHIP_OK) err = slamhip_last_error(); else d_key = (uint64_t *)slot;
     }
     if (count <= 0 || rc_local != SLAMHIP_OK) (void)hipMemsetAsync(d_key, 0xFF, sizeof(uint64_t), ctx->stream);       // (the neutral key)
@@ -591,7 +591,7 @@ static int32_t fused_allreduce_scan(slamhip_cs *cs, rccl_api &api, ncclComm_t co
     uint64_t *d_key = d_neutral;
     if (count > 0) {
         const uint64_t *slot = nullptr;
-        rc_local = slamhip_cs_search_shard_enqueue(cs, pose, first, count, &slot);        // (into the handle's result ring: no final arriver in the kernel)
+        rc_local = cs_search_shard_enqueue(cs, pose, first, count, &slot, false);         // (into the handle's result ring: no final arriver in the kernel; in the operator's stream: the collective behind it reads the slot)
         if (rc_local != SLAMHIP_OK) err = slamhip_last_error(); else d_key = (uint64_t *)slot;
     } else rc_local = cs_flush_generate(cs);                      // (a rank without candidates still decodes the winner from the list)
     if (count <= 0 || rc_local != SLAMHIP_OK) (void)hipMemsetAsync(d_key, 0xFF, sizeof(uint64_t), ctx->stream);

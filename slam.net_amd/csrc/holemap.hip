@@ -1488,6 +1488,7 @@ int32_t cs_launch_holemap_update(slamhip_cs *cs, const float *d_pose, float4 h_p
     slamhip_ctx *ctx = cs->ctx;
     const int n = cs->n_points;
     if (n <= 0) return SLAMHIP_OK;
+    SH_TRY(cs_overlap_join(cs));                                   // (enqueue-only searches in the side stream read the map this update writes)
     SH_TRY(cs_flush_scan(cs));
     const bool build = cs_holemap_one_launch(cs);
     if (win && (!build || !d_pose)) SH_FAIL(SLAMHIP_ERR_STATE, "the key-decoding update needs the one-launch form and a pose buffer");
