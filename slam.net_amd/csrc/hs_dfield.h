@@ -1,6 +1,6 @@
 // hs_dfield.h -- the arithmetic of the distance field (K9, hs_dfield.hip) that host and device share: the kernels k9_rows and
-// k9_cols and the test hook slamhip_debug_distance_field run this text, and every reader of the field -- k9_score, k9_gather, K13's
-// k13_score and slamhip_debug_mcl_step -- looks it up through hs_field.  Definition: include/slamhip.h, slamhip_hs_distance_field.
+// k9_cols and the test hook slamhip_debug_distance_field run this text, and every reader of a field over E -- k9_score, k16_pairs,
+// hs_field_gather, K13's k13_score and slamhip_debug_mcl_step -- looks it up through hs_field_lookup.  Definition: include/slamhip.h, slamhip_hs_distance_field.
 // Everything here is integer arithmetic; the end cell of a scan point is hs_trace.h's transform.
 #pragma once
 #include "common.h"
@@ -107,12 +107,16 @@ __host__ __device__ static inline uint32_t hs_df_col_min(const uint8_t *g, int s
     return best;
 }
 
-// The field as a launch reads it: F over E = M grown by r cells on every side, rows of `pitch` cells; E's first cell is (e_x0, e_y0)
-// in the window's frame -- r = M's x0 - e_x0 -- and outside E the field is the constant `outside` (hs_df_outside).
-struct hs_field { const uint16_t *f; int ew, eh, pitch, e_x0, e_y0; uint32_t outside; };
+// A field over E as a launch reads it -- K9's F (hs_field, uint16_t) or K16's N (hs_nfield, hs_nearest.h) -- E = M grown by r cells on
+// every side, rows of `pitch` cells; E's first cell is (e_x0, e_y0) in the window's frame -- r = M's x0 - e_x0 -- and outside E the
+// field is the constant `outside` (hs_df_outside, hs_nr_outside).  The kernels and the host plan that make one: hs_field.h.
+template <typename T>
+struct hs_field_of { const T *f; int ew, eh, pitch, e_x0, e_y0; uint32_t outside; };
+typedef hs_field_of<uint16_t> hs_field;
 
-// F of window-frame cell (x, y)
-__host__ __device__ static inline uint32_t hs_field_lookup(const hs_field &E, long long x, long long y)
+// the field's value at window-frame cell (x, y)
+template <typename T>
+__host__ __device__ static inline uint32_t hs_field_lookup(const hs_field_of<T> &E, long long x, long long y)
 {
     const long long ex = x - E.e_x0, ey = y - E.e_y0;
     const bool in = ex >= 0 && ex < E.ew && ey >= 0 && ey < E.eh;

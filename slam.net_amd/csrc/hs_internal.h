@@ -40,19 +40,19 @@ struct hs_level_dev {                      // what the kernels need, by value
 struct hs_backing;                         // hs_tiles.h
 struct hs_world;                           // hs_world.hip
 struct hs_lattice;                         // hs_lattice.hip
-struct hs_trace;                           // hs_trace.hip
-struct hs_dfield;                          // hs_dfield.hip
+struct hs_pose_batch;                      // hs_blocks.h
+struct hs_field_unit;                      // hs_field.h
 struct hs_frontier;                        // hs_frontier.hip
 struct hs_nav;                             // hs_nav.hip
 struct hs_rollout;                         // hs_rollout.hip
 struct hs_mcl;                             // hs_mcl.hip
 struct hs_merge;                           // hs_merge.hip
 struct hs_view;                            // hs_view.hip
-struct hs_nearest;                         // hs_nearest.hip
 struct hs_hough;                           // hs_hough.hip
 struct hs_sig;                             // hs_sig.hip
 struct hs_pg;                              // hs_pg.hip
-struct hs_field;                           // hs_dfield.h
+template <typename T> struct hs_field_of;  // hs_dfield.h
+typedef hs_field_of<uint16_t> hs_field;
 struct slamhip_hs {
     slamhip_ctx *ctx;
     int n_levels;
@@ -79,15 +79,15 @@ struct slamhip_hs {
     struct hs_backing *bk;                                 // slamhip_hs_set_backing: the tile pool and its host directory; nullptr while backing is off
     struct hs_world *wp;                                   // slamhip_hs_world_cells_upload / _world_extends: their staging buffer, made by the first call, kept
     struct hs_lattice *lat;                                // slamhip_hs_lattice_search: the class map and the result blocks, made by the first search, kept
-    struct hs_trace *trc;                                  // slamhip_hs_trace: the poses' and the results' blocks, made by the first trace, kept
-    struct hs_dfield *dfd;                                 // slamhip_hs_distance_field / _score: the field of E and the results' blocks, made by the first call, kept
+    struct hs_pose_batch *trc;                                  // slamhip_hs_trace: the poses' and the results' blocks, made by the first trace, kept
+    struct hs_field_unit *dfd;                                 // slamhip_hs_distance_field / _score: the field of E and the results' blocks, made by the first call, kept
     struct hs_frontier *frl;                               // slamhip_hs_frontiers: the frontier words, the union-find's arrays and the results' blocks, made by the first call, kept
     struct hs_nav *nav;                                    // slamhip_hs_nav_field: the traversable words, costs, dirs, tile flags and the results' blocks, made by the first call, kept
     struct hs_rollout *rol;                                // slamhip_hs_rollouts: the commands', body points' and results' blocks, made by the first call, kept
     struct hs_mcl *mcl;                                    // slamhip_hs_mcl_set / _step / _get: the particle set and the step's blocks, made by the first set, kept
     struct hs_merge *mrg;                                  // slamhip_hs_merge_set_source / _score / _apply: the source map and the reports' blocks, made by the first set_source, kept
     struct hs_view *vw;                                    // slamhip_hs_view_gain / _select / _set_covered: the covered layer, the slots and the results' blocks, made by the first call, kept
-    struct hs_nearest *nrs;                                // slamhip_hs_nearest_field / _pairs: the row offsets and the pairs of E and the results' blocks, made by the first call, kept
+    struct hs_field_unit *nrs;                                // slamhip_hs_nearest_field / _pairs: the row offsets and the pairs of E and the results' blocks, made by the first call, kept
     struct hs_hough *hgh;                                  // slamhip_hs_hough / _hough_rotation / _hough_shifts: the two slots' votes, spectra and row extents and the results' blocks, made by the first call, kept
     struct hs_sig *sig;                                    // slamhip_hs_sig_configure / _sig_add / _sig_query / _sig_self: the spec, the store of keyframe signatures, the poses and the results' blocks, made by configure, kept
     struct hs_pg *pg;                                      // slamhip_hs_pg_set / _pg_relax / _pg_get / _pg_residuals: the pose graph's one device block and its pinned staging, made by the first set, kept

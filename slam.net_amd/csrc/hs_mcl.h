@@ -67,10 +67,9 @@ __host__ __device__ static inline hs_mcl_pose hs_mcl_predict(const hs_mcl_motion
 // step 3 for one scan point under t = hs_trace_transform(stm, x', y', theta'): F of its end cell; false: the point is ignored
 __host__ __device__ static inline bool hs_mcl_point(const hs_field &E, const sh_m3x2 &t, float px, float py, uint32_t *F)
 {
-    float exf, eyf;
-    sh_v2_transform(px, py, t, &exf, &eyf);
-    if (!(hs_trace_counts(exf) && hs_trace_counts(eyf))) return false;
-    *F = hs_field_lookup(E, (long long)sh_f2i(rintf(exf)), (long long)sh_f2i(rintf(eyf)));   // ToRoundPoint (banker's), as k9_score
+    int ex, ey;
+    if (!hs_trace_end_cell(t, px, py, &ex, &ey)) return false;
+    *F = hs_field_lookup(E, (long long)ex, (long long)ey);
     return true;
 }
 

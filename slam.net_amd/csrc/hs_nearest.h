@@ -1,5 +1,5 @@
 // hs_nearest.h -- the arithmetic of the nearest-site field (K16, hs_nearest.hip) that host and device share: the kernels k16_rows,
-// k16_cols, k16_gather and k16_pairs and the test hook slamhip_debug_nearest_field run this text.  Definition: include/slamhip.h,
+// k16_cols and k16_pairs and the test hook slamhip_debug_nearest_field run this text.  Definition: include/slamhip.h,
 // slamhip_hs_nearest_field.  Everything here is integer arithmetic on top of hs_dfield.h's site words; the end cell of a scan point
 // is hs_trace.h's transform.
 #pragma once
@@ -73,14 +73,5 @@ __host__ __device__ static inline int hs_nr_col_argmin(const uint8_t *m, int str
     return bdy;
 }
 
-// The nearest-site field as a launch reads it: N over E = M grown by r cells on every side, rows of `pitch` pairs; E's first cell is
-// (e_x0, e_y0) in the window's frame, and outside E the pair is the constant `outside` (hs_nr_outside).
-struct hs_nfield { const uint32_t *n; int ew, eh, pitch, e_x0, e_y0; uint32_t outside; };
-
-// N of window-frame cell (x, y), packed
-__host__ __device__ static inline uint32_t hs_nearest_lookup(const hs_nfield &E, long long x, long long y)
-{
-    const long long ex = x - E.e_x0, ey = y - E.e_y0;
-    const bool in = ex >= 0 && ex < E.ew && ey >= 0 && ey < E.eh;
-    return in ? E.n[(size_t)ey * (size_t)E.pitch + (size_t)ex] : E.outside;
-}
+// The nearest-site field as a launch reads it: N over E, a packed pair per cell, `outside` hs_nr_outside (hs_field_of, hs_dfield.h)
+typedef hs_field_of<uint32_t> hs_nfield;

@@ -17,6 +17,17 @@ __host__ __device__ static inline sh_m3x2 hs_trace_transform(float stm, float x,
 
 __host__ __device__ static inline bool hs_trace_counts(float f) { return fabsf(f) < 16777216.0f; }    // (a NaN fails)
 
+// The end cell of scan point (px, py) under t, for the units that look a field up there (k9_score, k16_pairs, hs_mcl_point); false:
+// the point is ignored, as hs_trace_line_of ignores its beam, and the cell is not written.
+__host__ __device__ static inline bool hs_trace_end_cell(const sh_m3x2 &t, float px, float py, int *ex, int *ey)
+{
+    float exf, eyf;
+    sh_v2_transform(px, py, t, &exf, &eyf);
+    if (!(hs_trace_counts(exf) && hs_trace_counts(eyf))) return false;
+    *ex = sh_f2i(rintf(exf)); *ey = sh_f2i(rintf(eyf));                    // ToRoundPoint (banker's)
+    return true;
+}
+
 // the beam from scan origin (ox, oy) to scan point (px, py) under t
 __host__ __device__ static inline hs_trace_line hs_trace_line_of(const sh_m3x2 &t, float ox, float oy, float px, float py)
 {

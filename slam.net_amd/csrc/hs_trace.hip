@@ -26,7 +26,7 @@
 #define K8_LANES 256
 #define K8_AHEAD 8                         // steps of a walk whose look-ups are issued together
 #define HS_TRACE_MAX_POSES 65536
-#define HS_TRACE_MAX_BEAMS (1 << 20)       // B * n_points with per-beam records (24 MB of them)
+#define HS_TRACE_LOG2_MAX_BEAMS 20         // B * n_points with per-beam records (24 MB of them)
 
 static_assert(sizeof(slamhip_trace_beam) == 24 && sizeof(slamhip_trace_summary) == 32, "the records of include/slamhip.h");
 
@@ -168,34 +168,20 @@ __global__ void __launch_bounds__(K8_LANES) k8_trace(const k8_arg A)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-// What a trace needs, made by the first one and kept: the poses in device memory, the device block of summaries and beam records,
-// and the pinned block the poses leave and the results reach the host through.
-struct hs_trace {
-    float *d_poses; size_t cap_poses;
-    unsigned char *d_out; size_t cap_out;                                  // B summaries, then the beam records
-    unsigned char *h_io; size_t cap_h;                                     // the results; behind them the poses
-};
-
+// What a trace needs, made by the first one and kept: hs->trc, the blocks of a pose batch (hs_blocks.h) -- B summaries, then the
+// beam records.
 void hs_trc_free(slamhip_hs *hs)
 {
-    hs_trace *tr = hs->trc;
-    if (!tr) return;
-    hs_release((void **)&tr->d_poses, &tr->cap_poses, HS_MEM_DEVICE);
-    hs_release((void **)&tr->d_out, &tr->cap_out, HS_MEM_DEVICE);
-    hs_release((void **)&tr->h_io, &tr->cap_h, HS_MEM_PINNED);
-    delete tr;
+    if (!hs->trc) return;
+    hs_pose_batch_release(hs->trc);
+    delete hs->trc;
     hs->trc = nullptr;
 }
 
 int32_t hs_trc_check(int n_levels, int32_t level, int32_t B, int32_t world, bool want_beams, int n_points, bool scan_is_set)
 {
     if (level < 0 || level >= n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: level %d of %d", level, n_levels);
-    if (B < 1 || B > HS_TRACE_MAX_POSES) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: B = %d must lie in [1, %d]", B, HS_TRACE_MAX_POSES);
-    if (world != 0 && world != 1) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: world = %d must be 0 (the window) or 1 (the world)", world);
-    if (scan_is_set && n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "trace: no scan (slamhip_hs_set_scan first)");
-    if (want_beams && (int64_t)B * n_points > (int64_t)HS_TRACE_MAX_BEAMS)
-        SH_FAIL(SLAMHIP_ERR_INVALID, "trace: per-beam records of %d poses x %d points, more than 2^20", B, n_points);
-    return SLAMHIP_OK;
+    return hs_pose_batch_check("trace", B, HS_TRACE_MAX_POSES, world, "per-beam", want_beams, n_points, scan_is_set, HS_TRACE_LOG2_MAX_BEAMS);
 }
 
 extern "C" int32_t slamhip_hs_trace(slamhip_hs *hs, int32_t level, const float *poses, int32_t B, int32_t world,
@@ -204,25 +190,16 @@ extern "C" int32_t slamhip_hs_trace(slamhip_hs *hs, int32_t level, const float *
     SH_CHECK_ARG(hs && poses && out_summaries);
     SH_TRY(hs_trc_check(hs->n_levels, level, B, world, out_beams != nullptr, hs->n_points, true));
     const int n = hs->n_points;
-    slamhip_ctx *ctx = hs->ctx;
     SH_TRY(hs_call_begin(hs));
-    const int chunks = sh_div_up(n, K8_LANES);
-    if ((int64_t)B * chunks > (int64_t)INT32_MAX) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: %d poses x %d points, more workgroups than one launch takes", B, n);
+    int chunks;
+    SH_TRY(hs_pose_batch_chunks("trace", B, n, K8_LANES, &chunks));
     hs_class_map M;
     SH_TRY(hs_lat_pack_prepare(hs, level, world != 0, &M));                // (the world's plan refuses before anything is launched)
     SH_TRY(hs_unit(&hs->trc));
-    hs_trace *tr = hs->trc;
-    const size_t pose_bytes = sizeof(float) * 3 * (size_t)B;
+    hs_pose_batch *tr = hs->trc;
     const size_t sum_bytes = sizeof(slamhip_trace_summary) * (size_t)B;
-    const size_t out_bytes = sum_bytes + (out_beams ? sizeof(slamhip_trace_beam) * (size_t)B * n : 0);
-    SH_TRY(hs_grow((void **)&tr->d_poses, &tr->cap_poses, pose_bytes, HS_MEM_DEVICE, "trace"));
-    SH_TRY(hs_grow((void **)&tr->d_out, &tr->cap_out, out_bytes, HS_MEM_DEVICE, "trace"));
-    SH_TRY(hs_grow((void **)&tr->h_io, &tr->cap_h, out_bytes + pose_bytes, HS_MEM_PINNED, "trace"));
-    float *h_poses = (float *)(tr->h_io + out_bytes);                      // (out_bytes is a multiple of 8)
-    memcpy(h_poses, poses, pose_bytes);
-    SH_TRY(hs_flush_scan(hs));
-    SH_HIP(hipMemcpyAsync(tr->d_poses, h_poses, pose_bytes, hipMemcpyHostToDevice, ctx->stream));
-    SH_HIP(hipMemsetAsync(tr->d_out, 0, sum_bytes, ctx->stream));
+    const size_t beam_bytes = out_beams ? sizeof(slamhip_trace_beam) * (size_t)B * n : 0;   // (both multiples of 8)
+    SH_TRY(hs_pose_batch_begin(hs, tr, "trace", poses, B, sum_bytes, beam_bytes));
     SH_TRY(hs_lat_pack_enqueue(hs, level, world != 0, &M));
     k8_arg A;
     A.pts = hs->d_pts; A.n = n; A.ox = hs->origin[0]; A.oy = hs->origin[1];
@@ -232,13 +209,9 @@ extern "C" int32_t slamhip_hs_trace(slamhip_hs *hs, int32_t level, const float *
     A.stm = hs->lv[level].stm;
     A.sums = (slamhip_trace_summary *)tr->d_out;
     A.beams = out_beams ? (slamhip_trace_beam *)(tr->d_out + sum_bytes) : (slamhip_trace_beam *)nullptr;
-    hipLaunchKernelGGL(k8_trace, dim3((unsigned)(B * chunks)), dim3(K8_LANES), 0, ctx->stream, A);    // (no timing class of its own)
+    hipLaunchKernelGGL(k8_trace, dim3((unsigned)(B * chunks)), dim3(K8_LANES), 0, hs->ctx->stream, A);    // (no timing class of its own)
     SH_HIP(hipGetLastError());
-    SH_HIP(hipMemcpyAsync(tr->h_io, tr->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    SH_TRY(hs_call_finish(hs));
-    memcpy(out_summaries, tr->h_io, sum_bytes);
-    if (out_beams) memcpy(out_beams, tr->h_io + sum_bytes, out_bytes - sum_bytes);
-    return SLAMHIP_OK;
+    return hs_pose_batch_finish(hs, tr, sum_bytes, beam_bytes, out_summaries, out_beams);
 }
 
 // CPU-side test hooks: hs_trace_line_of and hs_trace_walk, the text the kernel runs

@@ -381,6 +381,20 @@ def test_separable_restatement_equals_brute_force(r):
         assert np.array_equal(np_nearest(c, mask, r, rect), np_nearest_brute(c, mask, r, rect)), (mask, r)
 
 
+# ---- the two hooks run one skeleton: their fields agree cell for cell ---------------------------------------------------------------
+@pytest.mark.parametrize("r", [1, 16, 17, 40])
+def test_hook_identity_with_the_distance_field(capi, r):
+    """min(r^2, dx^2 + dy^2) of the nearest-site hook, NONE standing for r^2, is the distance field's hook: the identity the device
+    test asserts, over a rectangle that reaches past E on all four sides, for every mask."""
+    c = D.random_classes(np.random.default_rng(9), 21, 37)
+    rect = (-r - 3, -r - 3, 37 + 2 * r + 6, 21 + 2 * r + 6)
+    for mask in range(1, 8):
+        d2, none = d2_of(capi.debug_nearest_field(c, mask, r, rect))
+        want = capi.debug_distance_field(c, mask, r, rect).astype(np.int64)
+        got = np.minimum(np.where(none, r * r, d2), r * r)
+        assert np.array_equal(got, want), (mask, r, np.argwhere(got != want)[:5].tolist())
+
+
 def test_pair_summary_restatement():
     pairs = np.array([(IGNORED, IGNORED), (NONE, NONE), (0, 0), (-3, 4), (2, -1)], np.int16)
     ex = np.array([0, 5, 7, -2, 1 << 24]); ey = np.array([0, 5, -7, 3, -(1 << 24)])
