@@ -443,6 +443,22 @@ namespace HectorSLAM.Main
             return hits;
         }
 
+        /// <summary>The scan that is set on the processor's pyramid -- the one the last Update or AddKeyframe took -- appended to the
+        /// scan store (slamhip_hsproc_scans_add): call it right after AddKeyframe, the two stores' indices then agree.</summary>
+        public int KeepKeyframeScan()
+        {
+            Native.Check(Native.slamhip_hsproc_scans_add(proc.Ptr, out int index));
+            return index;
+        }
+
+        /// <summary>Draw the stored keyframe scans [first, last) into the map at WORLD poses -- those RelaxKeyframes returned -- in one
+        /// call (slamhip_hsproc_render).  Without keep the map is cleared first.  MatchPose, LastMapUpdatePose and the gate stay.</summary>
+        public unsafe void RenderKeyframes(Vector3[] posesWorld, int first, int last, bool keep = false)
+        {
+            Vector3[] p = posesWorld != null && posesWorld.Length > 0 ? posesWorld : new Vector3[1];
+            fixed (Vector3* pp = p) Native.Check(Native.slamhip_hsproc_render(proc.Ptr, first, last, pp, keep ? 1 : 0));
+        }
+
         /// <summary>Check one loop candidate against the map: Relocalise centred on its pose guess, nothing adopted.  Host
         /// composition only; the caller judges the report.</summary>
         public Vector3 VerifyLoop(ScanCloud scan, LoopCandidate candidate, LatticeSpec lattice, int maxHints, out SlamHip.MatchReport report, out RelocInfo info)

@@ -692,6 +692,47 @@ namespace HectorSLAM.Main
             PgNodes = PgEdges = 0;
         }
 
+        /// <summary>Append a scan to the device-resident scan store (slamhip_hs_scans_add): null = the scan SetScan took.
+        /// Returns its index; HectorSLAMProcessor keeps it equal to the keyframe's index in the signature store.</summary>
+        public unsafe int ScansAdd(ScanCloud scan = null)
+        {
+            int index;
+            if (scan == null) { Native.Check(Native.slamhip_hs_scans_add(Pyramid.Ptr, null, 0, null, out index)); return index; }
+            Vector2[] pts = scan.Points.Count > 0 ? scan.Points.ToArray() : new Vector2[1];
+            Vector2 origin = new Vector2(scan.Pose.X, scan.Pose.Y);
+            fixed (Vector2* p = pts) Native.Check(Native.slamhip_hs_scans_add(Pyramid.Ptr, p, scan.Points.Count, &origin, out index));
+            return index;
+        }
+
+        public int ScansCount
+        {
+            get { Native.Check(Native.slamhip_hs_scans_count(Pyramid.Ptr, out int n)); return n; }
+        }
+
+        /// <summary>Scan k of the store (slamhip_hs_scans_info, slamhip_hs_scans_download).</summary>
+        public unsafe Vector2[] ScansGet(int k, out Vector2 scanOrigin)
+        {
+            Native.Check(Native.slamhip_hs_scans_info(Pyramid.Ptr, k, out int n, out scanOrigin));
+            var pts = new Vector2[Math.Max(n, 1)];
+            fixed (Vector2* p = pts) Native.Check(Native.slamhip_hs_scans_download(Pyramid.Ptr, k, p, n));
+            Array.Resize(ref pts, n);
+            return pts;
+        }
+
+        /// <summary>Free the scan store (slamhip_hs_scans_clear).</summary>
+        public void ScansClear()
+        {
+            Native.Check(Native.slamhip_hs_scans_clear(Pyramid.Ptr));
+        }
+
+        /// <summary>Draw scans [first, last) of the scan store into the pyramid at the given window-frame poses, as that many SetScan +
+        /// UpdateByScan calls in order would, in one call (slamhip_hs_render).  Without keep the map is cleared first.</summary>
+        public unsafe void Render(Vector3[] poses, int first, int last, bool keep = false)
+        {
+            Vector3[] p = poses != null && poses.Length > 0 ? poses : new Vector3[1];
+            fixed (Vector3* pp = p) Native.Check(Native.slamhip_hs_render(Pyramid.Ptr, first, last, pp, keep ? 1 : 0));
+        }
+
         /// <summary>Free the blocks of the scan signatures and forget the spec (slamhip_hs_sig_clear).</summary>
         public void SigClear()
         {

@@ -467,6 +467,12 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_get(IntPtr hs, double* poses, int nNodes);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_residuals(IntPtr hs, double* r, double* chi2);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_clear(IntPtr hs);
+        [DllImport(Lib)] internal static extern int slamhip_hs_scans_add(IntPtr hs, Vector2* points, int nPoints, Vector2* scanOrigin, out int index);
+        [DllImport(Lib)] internal static extern int slamhip_hs_scans_count(IntPtr hs, out int count);
+        [DllImport(Lib)] internal static extern int slamhip_hs_scans_info(IntPtr hs, int k, out int nPoints, out Vector2 scanOrigin);
+        [DllImport(Lib)] internal static extern int slamhip_hs_scans_download(IntPtr hs, int k, Vector2* points, int cap);
+        [DllImport(Lib)] internal static extern int slamhip_hs_scans_clear(IntPtr hs);
+        [DllImport(Lib)] internal static extern int slamhip_hs_render(IntPtr hs, int first, int last, Vector3* poses, int flags);
         [DllImport(Lib)] internal static extern int slamhip_debug_nearest_field(byte* cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h, short* dxdy);
         // the frontier cells and their connected clusters (no reference counterpart), and their host-side hook
         [DllImport(Lib)] internal static extern int slamhip_hs_frontiers(IntPtr hs, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
@@ -550,6 +556,8 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_sig_query(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, int first, int last, int maxHits, SigHit* hits,
                                                                              out int n, ulong* sig, out SigInfo info);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_sig_self(IntPtr proc, int first, int last, int minGap, SigHit* hits);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_scans_add(IntPtr proc, out int index);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_render(IntPtr proc, int first, int last, Vector3* poses, int flags);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_mcl_step(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in MclSpec spec, out MclSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_set_source(IntPtr proc, int level, int ax, int ay, int w, int h, HectorSLAM.Map.LogOddsCell* cells);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_score(IntPtr proc, Vector3* posesWorld, int nPoses, MergeReport* reports);

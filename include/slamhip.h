@@ -1680,6 +1680,68 @@ int32_t slamhip_debug_sincos(const double *a, int32_t n, double *out_s, double *
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);
 
+/* The map drawn again from stored scans at poses given per scan (K20; no reference counterpart).  K18 finds loop candidates, K7
+ * verifies one, K19 spreads the error over the keyframe poses; the pyramid still holds every scan at the pose it was first drawn at.
+ * This unit keeps the keyframes' SCANS on the device and draws a range of them into the pyramid at corrected poses in one call.
+ * slamhip_hs_update_by_scan and the processor's per-scan call never enter it.
+ * THE DEFINITION.  slamhip_hs_render(hs, first, last, poses, flags) draws scans first .. last - 1 of the scan store; poses holds
+ * 3 * (last - first) floats in the window's frame, the frame slamhip_hs_update_by_scan takes.  Afterwards curr_update_index and
+ * curr_cache_index of every level, and on every level each cell's update_index, the bits of its value and every probability, equal
+ * bit for bit what this sequence leaves:
+ *  1. Unless flags & SLAMHIP_RENDER_KEEP: every cell of every level becomes LogOddsCell.Reset() {-1, 0.0f} with probability 0.5f; each
+ *     level's update index and cache epoch take the values slamhip_hs_reset gives them (0, 0); the backing directory is dropped as
+ *     slamhip_hs_reset drops it (the setting and the pool stay, the tiles go: a tile drawn at the old poses must not scroll back in).
+ *     NOT touched: the scan store, the signature store, the pose graph, the window's origin, the factors, the iterations and the
+ *     handle's current scan -- which is why this is not slamhip_hs_reset.
+ *  2. For k = first .. last - 1 in order: slamhip_hs_set_scan(points_k, n_k, origin_k), then slamhip_hs_update_by_scan(pose_k).  A
+ *     stored scan of 0 points still advances the update index by 3 and the epoch by 1.
+ *  3. With KEEP the start state is whatever the pyramid holds.  The kernel applies the reference's literal tests update_index <
+ *     mark_free and update_index < mark_occ (OccGridMap.cs:192-218): they hold for cells uploaded with indices above the marks, and
+ *     for INT_MAX, as they hold in slamhip_hs_update_by_scan.
+ *  4. The per-(scan, level) matrices are formed on the host exactly as slamhip_hs_update_by_scan forms them: rotation(theta) *
+ *     translation(x, y) * scale(ScaleToMap) in binary32, in that order (OccGridMap.cs:120-123).
+ *  5. first == last without KEEP clears (rule 1 alone); with KEEP it returns SLAMHIP_OK and launches nothing.
+ *  6. Blocking: on the operator's stream behind everything already enqueued, with the context's bounded wait, no timing class.  A
+ *     range is drawn in launches of at most 16384 scans (SLAMHIP_K20_CHUNK in the environment changes that; each later launch is a KEEP
+ *     render of its own), and the call waits for EACH launch with the bound: the bound (default 10 s) is per 16384 scans, not per
+ *     call.  A launch's time goes with the scans that reach its busiest tile; at the measured 22 us per scan (DESIGN.md section 4 "K20") 16384
+ *     scans of 1080 points on one spot take about 0.36 s, far below the default bound, and a render of 2^20 scans is 64 such waits: in the worst case
+ *     the call blocks for 64 times the bound before it fails with SLAMHIP_ERR_TIMEOUT.  Scans of many
+ *     times 1080 points on one spot can pass it: raise the bound (slamhip_ctx_set_wait_timeout) or lower the chunk.
+ *  7. SLAMHIP_ERR_INVALID with nothing changed: first < 0, last < first, last > count, flags with other bits, a pose component that is
+ *     not finite, curr_update_index + 3 * (last - first) past INT_MAX on any level (0 stands for curr_update_index without KEEP), the
+ *     reference's cache on (slamhip_hs_set_reference_cache), as slamhip_hs_shift refuses.  SLAMHIP_ERR_NOMEM / SLAMHIP_ERR_HIP from an
+ *     allocation, a copy or a launch that did not reach the stream: the map, the indices and the directory are as they were before
+ *     the launch of the chunk that failed (earlier chunks of a long range stay drawn, with their indices).  SLAMHIP_ERR_TIMEOUT
+ *     poisons the context as everywhere; the map is then undefined.
+ * THE SCAN STORE.  The points of all scans live in ONE device pool that grows by doubling, the front copied as it is; a record per
+ * scan (on the host) holds the offset, the count and the origin.  slamhip_hs_destroy frees it; slamhip_hs_reset empties it and keeps
+ * its allocation, as it does the signature store, so the indices of the two stores stay aligned; window shifts do not touch it.
+ *  8. slamhip_hs_scans_add appends a scan and gives its index; xy == NULL appends the scan that is set on the handle (n_points and
+ *     scan_origin are not read).  The point limits of slamhip_hs_set_scan; at most 2^20 scans (SLAMHIP_ERR_INVALID beyond).
+ *  9. _scans_count: the scans held (0 without a store).  _scans_info: one scan's point count and origin.  _scans_download: one scan's
+ *     points into room for `cap` points (SLAMHIP_ERR_INVALID: k outside the store, cap below the count).  _scans_clear frees the store. */
+#define SLAMHIP_RENDER_KEEP 1
+int32_t slamhip_hs_scans_add(slamhip_hs *hs, const float *xy, int32_t n_points, const float scan_origin[2], int32_t *out_index);
+int32_t slamhip_hs_scans_count(slamhip_hs *hs, int32_t *out_count);
+int32_t slamhip_hs_scans_info(slamhip_hs *hs, int32_t k, int32_t *out_n, float out_origin[2]);
+int32_t slamhip_hs_scans_download(slamhip_hs *hs, int32_t k, float *out_xy, int32_t cap);
+int32_t slamhip_hs_scans_clear(slamhip_hs *hs);
+int32_t slamhip_hs_render(slamhip_hs *hs, int32_t first, int32_t last, const float *poses, int32_t flags);
+/* Test hooks (no device involved).  _render: the definition over the caller's arrays, line by line as the reference walks
+ * (UpdateLineBresenhami, Bresenham2D step by step -- not the closed form the kernel clips by), from the header text the kernels run
+ * (hs_render.h).  dims: (w, h) per level; cell_length: level 0's, doubled per level as slamhip_hs_create doubles it; cells: all
+ * levels' cells one behind the other, IN and OUT; update_index, cache_index: per level, IN and OUT; the factors as
+ * slamhip_hs_set_factors takes them; xy: all scans' points, offsets: N + 1 entries, origins: N x 2, poses: N x 3.  Rule 7's refusals for
+ * the poses, the flags and the indices.  _render_clip: for a line of major length da and minor length db, the steps i of [0, da]
+ * whose cell (i, (da / 2 + i * db) / da) lies in the window of T x T offsets whose first is (a0[k], b0[k]) -- [out_i0[k], out_i1[k]],
+ * empty when out_i0[k] > out_i1[k]; the interval the tile kernel walks. */
+int32_t slamhip_debug_render(int32_t n_levels, const int32_t *dims, float cell_length, slamhip_cell *cells, int32_t *update_index,
+                             int32_t *cache_index, float free_factor, float occ_factor, const float *xy, const int32_t *offsets,
+                             const float *origins, const float *poses, int32_t N, int32_t flags);
+int32_t slamhip_debug_render_clip(int32_t da, int32_t db, int32_t T, int32_t n, const int32_t *a0, const int32_t *b0, int32_t *out_i0,
+                                  int32_t *out_i1);
+
 /* The scrolling window -- something the reference lacks (its `offset`, GridMap.cs:45, is ignored by UpdateByScan,
  * OccGridMap.cs:120-123, and by the matcher, ScanMatcher.cs:139-142): the contents of the whole pyramid move by an integer
  * number of cells, on the device, in stream order, so that a robot that drives out of the window can take the window along.
@@ -1941,6 +2003,13 @@ int32_t slamhip_hsproc_sig_add(slamhip_hsproc *p, const float *xy, int32_t n_poi
 int32_t slamhip_hsproc_sig_query(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2], int32_t first, int32_t last,
                                  int32_t B, slamhip_sig_hit *out_hits, int32_t *out_n, uint64_t *out_sig, slamhip_sig_info *out_info);
 int32_t slamhip_hsproc_sig_self(slamhip_hsproc *p, int32_t first, int32_t last, int32_t min_gap, slamhip_sig_hit *out_hits);
+/* The scan store and the render through the processor.  _scans_add appends the scan that is set on the processor's hs -- the one the
+ * last slamhip_hsproc_update, _sig_add or any other call that takes a scan left -- as slamhip_hs_scans_add with xy == NULL.  _render:
+ * slamhip_hs_render at WORLD poses, each taken to the window's frame as slamhip_hsproc_trace takes its poses (minus (float)origin *
+ * cell0 per axis; with the origin at (0, 0) every bit passes through).  MatchPose, LastMapUpdatePose and the update gate are left
+ * alone.  Errors as the slamhip_hs_* calls. */
+int32_t slamhip_hsproc_scans_add(slamhip_hsproc *p, int32_t *out_index);
+int32_t slamhip_hsproc_render(slamhip_hsproc *p, int32_t first, int32_t last, const float *poses_world, int32_t flags);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

@@ -167,6 +167,8 @@ SIG_INFO = np.dtype([(n, np.int32) for n in ("n_points", "n_ignored", "n_far", "
 SIG_HIT_DTYPE = np.dtype([("score", np.uint32), ("index", np.int32), ("shift", np.int16), ("inter", np.int16), ("uni", np.int16),
                           ("n_set_key", np.int16)])                                                     # slamhip_sig_hit: 16 bytes
 assert SIG_SPEC.itemsize == 12 and SIG_INFO.itemsize == 16 and SIG_HIT_DTYPE.itemsize == 16
+RENDER_KEEP = 1                                                # SLAMHIP_RENDER_KEEP: slamhip_hs_render starts from what the pyramid holds
+RENDER_MAX_SCANS = 1 << 20                                     # the scan store's limit
 PG_MAX_NODES, PG_MAX_EDGES, PG_MAX_OUTER, PG_MAX_CG = 1 << 20, 1 << 22, 64, 1 << 20   # the limits of slamhip_hs_pg_*
 PG_SPEC = np.dtype([("n_outer", np.int32), ("n_cg", np.int32), ("check_every", np.int32), ("reserved", np.int32), ("lambda", np.float64),
                     ("tol", np.float64)])                                                           # slamhip_pg_spec: 32 bytes
@@ -252,6 +254,8 @@ def _declare(L):
         "slamhip_debug_sig_search": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_debug_pg_relax": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "slamhip_debug_pg_sum": (i32, [vp, i32, vp]),
+        "slamhip_debug_render": (i32, [i32, vp, f, vp, vp, vp, f, f, vp, vp, vp, vp, i32, i32]),
+        "slamhip_debug_render_clip": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),
         "slamhip_debug_sincos": (i32, [vp, i32, vp, vp]),
         "slamhip_debug_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_nav_field": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -372,6 +376,12 @@ def _declare(L):
         "slamhip_hs_pg_get": (i32, [vp, vp, i32]),
         "slamhip_hs_pg_residuals": (i32, [vp, vp, vp]),
         "slamhip_hs_pg_clear": (i32, [vp]),
+        "slamhip_hs_scans_add": (i32, [vp, vp, i32, vp, ip]),
+        "slamhip_hs_scans_count": (i32, [vp, ip]),
+        "slamhip_hs_scans_info": (i32, [vp, i32, ip, vp]),
+        "slamhip_hs_scans_download": (i32, [vp, i32, vp, i32]),
+        "slamhip_hs_scans_clear": (i32, [vp]),
+        "slamhip_hs_render": (i32, [vp, i32, i32, vp, i32]),
         "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hs_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hs_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -420,6 +430,8 @@ def _declare(L):
         "slamhip_hsproc_sig_add": (i32, [vp, fp, i32, fp, fp, ip, vp, vp]),
         "slamhip_hsproc_sig_query": (i32, [vp, fp, i32, fp, i32, i32, i32, vp, ip, vp, vp]),
         "slamhip_hsproc_sig_self": (i32, [vp, i32, i32, i32, vp]),
+        "slamhip_hsproc_scans_add": (i32, [vp, ip]),
+        "slamhip_hsproc_render": (i32, [vp, i32, i32, vp, i32]),
         "slamhip_hsproc_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hsproc_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hsproc_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -1073,3 +1085,38 @@ def debug_view(values, stm, pose, origin, xy, reach, covered=None):
     call("slamhip_debug_view", fptr(v), w, h, C.c_float(stm), fptr(f32(pose, (3,))), fptr(f32(origin, (2,))), fptr(xy), xy.shape[0], int(reach),
          None if cov is None else cov.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p), s.ctypes.data_as(C.c_void_p))
     return out, s[0]
+
+
+def debug_render(dims, cell_length, cells, update_index, cache_index, scans, origins, poses, keep=False, factors=(0.4, 0.9), flags=None):
+    """The definition of slamhip_hs_render on the host (slamhip_debug_render; no device involved): dims a list of (w, h) per level,
+    cells a list of CELL_DTYPE arrays per level (copied), update_index / cache_index per level, scans a list of (n_i, 2) point
+    arrays, origins (N, 2), poses (N, 3) -> (cells per level, update_index list, cache_index list)."""
+    d = np.ascontiguousarray(dims, np.int32).reshape(-1, 2)
+    allc = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(c, CELL_DTYPE).reshape(-1) for c in cells]))
+    assert allc.size == int((d[:, 0].astype(np.int64) * d[:, 1]).sum())
+    ui = np.array(update_index, np.int32).reshape(-1).copy(); ci = np.array(cache_index, np.int32).reshape(-1).copy()
+    assert ui.size == ci.size == d.shape[0]
+    pts = [f32(s, (-1, 2)) for s in scans]
+    off = np.zeros(len(pts) + 1, np.int32)
+    off[1:] = np.cumsum([p.shape[0] for p in pts])
+    xy = np.ascontiguousarray(np.concatenate(pts, axis=0)) if pts and off[-1] else np.zeros((1, 2), np.float32)
+    og = f32(origins, (-1, 2)) if len(pts) else np.zeros((1, 2), np.float32)
+    ps = f32(poses, (-1, 3)) if len(pts) else np.zeros((1, 3), np.float32)
+    assert len(pts) == 0 or (og.shape[0] == ps.shape[0] == len(pts))
+    fl = (RENDER_KEEP if keep else 0) if flags is None else int(flags)
+    call("slamhip_debug_render", d.shape[0], _vp(d), C.c_float(cell_length), _vp(allc), _vp(ui), _vp(ci), C.c_float(factors[0]), C.c_float(factors[1]),
+         _vp(xy), _vp(off), _vp(og), _vp(ps), len(pts), fl)
+    out, at = [], 0
+    for w, h in d:
+        out.append(allc[at:at + int(w) * int(h)].copy()); at += int(w) * int(h)
+    return out, [int(v) for v in ui], [int(v) for v in ci]
+
+
+def debug_render_clip(da, db, T, a0, b0):
+    """The steps of a (da, db) line inside windows of T x T offsets whose first are (a0[k], b0[k]) (slamhip_debug_render_clip)
+    -> (i0, i1) int32 arrays; empty where i0 > i1."""
+    a = np.ascontiguousarray(a0, np.int32).reshape(-1); b = np.ascontiguousarray(b0, np.int32).reshape(-1)
+    assert a.size == b.size
+    i0 = np.zeros(max(a.size, 1), np.int32); i1 = np.zeros(max(a.size, 1), np.int32)
+    call("slamhip_debug_render_clip", int(da), int(db), int(T), a.size, _vp(a) if a.size else _vp(i0), _vp(b) if b.size else _vp(i0), _vp(i0), _vp(i1))
+    return i0[:a.size], i1[:a.size]

@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(256) k5_checksum_cells(const slamhip_cell *__r
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-static float prob_to_logodds(float prob) { const float odds = prob / (1.0f - prob); return logf(odds); }   // OccGridMap.cs:86-90
+static float prob_to_logodds(float prob) { return hs_prob_to_logodds(prob); }   // OccGridMap.cs:86-90 (hs_internal.h: slamhip_debug_render forms them by the same text)
 
 extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
 {
@@ -128,6 +128,7 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
     hs_hg_free(hs);
     hs_sg_free(hs);
     hs_pg_free(hs);
+    hs_scn_free(hs);
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
     if (hs->ev_pts) (void)hipEventDestroy(hs->ev_pts);
@@ -158,6 +159,7 @@ extern "C" int32_t slamhip_hs_reset(slamhip_hs *hs)
     hs_hg_drop_slot(hs, 0);                                                // (slamhip_hs_hough: slot 0 held the map that is gone; the source's drop emptied slot 1)
     hs_sg_reset(hs);                                                       // (slamhip_hs_sig_add: the keyframes belonged to the map that is gone)
     hs_pg_reset(hs);                                                       // (slamhip_hs_pg_set: so did the graph of their poses)
+    hs_scn_reset(hs);                                                      // (slamhip_hs_scans_add: and their scans -- the two stores' indices stay aligned)
     return SLAMHIP_OK;
 }
 

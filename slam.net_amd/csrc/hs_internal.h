@@ -51,6 +51,7 @@ struct hs_view;                            // hs_view.hip
 struct hs_hough;                           // hs_hough.hip
 struct hs_sig;                             // hs_sig.hip
 struct hs_pg;                              // hs_pg.hip
+struct hs_scans;                           // hs_render.hip
 template <typename T> struct hs_field_of;  // hs_dfield.h
 typedef hs_field_of<uint16_t> hs_field;
 struct slamhip_hs {
@@ -90,6 +91,7 @@ struct slamhip_hs {
     struct hs_field_unit *nrs;                                // slamhip_hs_nearest_field / _pairs: the row offsets and the pairs of E and the results' blocks, made by the first call, kept
     struct hs_hough *hgh;                                  // slamhip_hs_hough / _hough_rotation / _hough_shifts: the two slots' votes, spectra and row extents and the results' blocks, made by the first call, kept
     struct hs_sig *sig;                                    // slamhip_hs_sig_configure / _sig_add / _sig_query / _sig_self: the spec, the store of keyframe signatures, the poses and the results' blocks, made by configure, kept
+    struct hs_scans *scn;                                  // slamhip_hs_scans_add / slamhip_hs_render: the store of keyframe scans -- the records on the host, the points in one device pool -- and the blocks of a render, made by the first call, kept
     struct hs_pg *pg;                                      // slamhip_hs_pg_set / _pg_relax / _pg_get / _pg_residuals: the pose graph's one device block and its pinned staging, made by the first set, kept
 };
 
@@ -135,6 +137,8 @@ __device__ static __forceinline__ unsigned long long hs_cache_entry(float v, int
 // exp(0) / (exp(0) + 1), exactly 0.5f
 __host__ __device__ static inline slamhip_cell hs_reset_cell() { slamhip_cell c; c.update_index = -1; c.value = 0.0f; return c; }
 #define HS_RESET_PROB 0.5f
+// OccGridMap.ProbToLogOdds (OccGridMap.cs:86-90), on the host: what slamhip_hs_create and slamhip_hs_set_factors form lo_free and lo_occ by
+static inline float hs_prob_to_logodds(float prob) { const float odds = prob / (1.0f - prob); return logf(odds); }
 
 // hector.hip
 // launches the scan upload that slamhip_hs_set_scan left pending (every launch that reads the points calls it first)
@@ -240,3 +244,6 @@ int32_t hs_sg_check_query(const slamhip_hs *hs, int32_t first, int32_t last, int
 // hs_pg.hip
 void    hs_pg_free(slamhip_hs *hs);         // the pose graph's blocks (the caller has drained the stream)
 void    hs_pg_reset(slamhip_hs *hs);        // slamhip_hs_reset: no graph from here on; the blocks stay
+// hs_render.hip
+void    hs_scn_free(slamhip_hs *hs);        // the store of keyframe scans and the blocks of a render (the caller has drained the stream)
+void    hs_scn_reset(slamhip_hs *hs);       // slamhip_hs_reset: the store is empty from here on; the pool and the blocks stay

@@ -498,6 +498,25 @@ extern "C" int32_t slamhip_hsproc_sig_self(slamhip_hsproc *p, int32_t first, int
     return slamhip_hs_sig_self(p->hs, first, last, min_gap, out_hits);
 }
 
+// The scan store and the render through the processor: the scan that is set on the processor's own hs appended; the render's WORLD
+// poses taken to the window's frame.  Nothing of the processor's own state is read or written beyond the window's origin.
+extern "C" int32_t slamhip_hsproc_scans_add(slamhip_hsproc *p, int32_t *out_index)
+{
+    SH_CHECK_ARG(p);
+    return slamhip_hs_scans_add(p->hs, nullptr, 0, nullptr, out_index);
+}
+
+extern "C" int32_t slamhip_hsproc_render(slamhip_hsproc *p, int32_t first, int32_t last, const float *poses_world, int32_t flags)
+{
+    SH_CHECK_ARG(p);
+    std::vector<float> buf;
+    int32_t count = 0;
+    SH_TRY(slamhip_hs_scans_count(p->hs, &count));
+    // (a range outside the store reads no pose here: slamhip_hs_render refuses it without touching the caller's array)
+    const bool have = poses_world && first >= 0 && last > first && last <= count;
+    return slamhip_hs_render(p->hs, first, last, have ? hsproc_poses_to_window(p, poses_world, last - first, buf) : poses_world, flags);
+}
+
 // The view gain through the processor: slamhip_hsproc_trace's shape -- the arguments checked ahead of the scan, the scan set, every
 // pose taken to the window's frame.
 extern "C" int32_t slamhip_hsproc_view_gain(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float *poses_world, int32_t B,

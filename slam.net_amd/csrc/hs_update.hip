@@ -123,6 +123,9 @@ k5_prepare(k5_arg A, const float2 *__restrict__ pts, int n, float ox, float oy, 
 // the state transitions of one cell: BresenhamCellFree (:192-199) by the first line that crosses it, then
 // BresenhamCellOcc (:201-218) by the first line that ends in it; a cell first touched by an end point is not
 // marked free any more (the mark_occ update index is above mark_free)
+// (hs_render.h holds a TWIN of this function, hs_cell_transition, and of the line-making of k5_prepare / k5_cells<true>, hs_line_make,
+// for K20: change one and change the other -- DESIGN.md section 4 "K20" says why they are two; tests/test_gpu_hector_render.py holds
+// them to == on every cell)
 __device__ static inline void k5_transition(const k5_level &L, float &v, int &u, int first_free, int first_occ, float lo_free, float lo_occ)
 {
     if (first_free < first_occ && u < L.mark_free) { v += lo_free; u = L.mark_free; }     // :192-199

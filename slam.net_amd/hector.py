@@ -705,6 +705,43 @@ class MapRepMultiMap:
         capi.call("slamhip_hs_pg_clear", self._h)
         self.__dict__.pop("_pg_sizes", None)
 
+    def ScansAdd(self, scan=None):
+        """Append a scan to the device-resident scan store (slamhip_hs_scans_add; no reference counterpart): a ScanCloud (its points
+        and Pose[:2] as the scan origin), or None for the scan that is set on this pyramid -> its index."""
+        k = C.c_int32()
+        if scan is None:
+            capi.call("slamhip_hs_scans_add", self._h, None, 0, None, C.byref(k))
+        else:
+            pts = capi.f32(scan.Points, (-1, 2)); org = capi.f32(scan.Pose[:2])
+            keep = np.zeros((1, 2), np.float32) if pts.shape[0] == 0 else pts          # (an empty scan still needs a non-NULL xy)
+            capi.call("slamhip_hs_scans_add", self._h, capi._vp(keep), pts.shape[0], capi._vp(org), C.byref(k))
+        return k.value
+
+    def ScansCount(self):
+        n = C.c_int32()
+        capi.call("slamhip_hs_scans_count", self._h, C.byref(n))
+        return n.value
+
+    def ScansGet(self, k):
+        """Scan k of the store (slamhip_hs_scans_info, _scans_download) -> (points (n, 2) float32, origin (2,) float32)."""
+        n = C.c_int32(); org = np.zeros(2, np.float32)
+        capi.call("slamhip_hs_scans_info", self._h, int(k), C.byref(n), capi._vp(org))
+        pts = np.zeros((max(n.value, 1), 2), np.float32)
+        capi.call("slamhip_hs_scans_download", self._h, int(k), capi._vp(pts), n.value)
+        return pts[:n.value].copy(), org
+
+    def ScansClear(self):
+        """Free the scan store (slamhip_hs_scans_clear)."""
+        capi.call("slamhip_hs_scans_clear", self._h)
+
+    def Render(self, poses, first=0, last=None, keep=False):
+        """Draw scans [first, last) of the scan store into the pyramid at `poses` ((last - first, 3), window frame), as that many
+        set_scan + UpdateByScan calls in order would, in one call (slamhip_hs_render).  Without keep the map is cleared first."""
+        last = self.ScansCount() if last is None else int(last)
+        p = capi.f32(poses, (-1, 3)) if last > first else np.zeros((1, 3), np.float32)
+        assert last <= first or p.shape[0] == last - first
+        capi.call("slamhip_hs_render", self._h, int(first), last, capi._vp(p), capi.RENDER_KEEP if keep else 0)
+
     def SigClear(self):
         """Free the blocks of the scan signatures and forget the spec (slamhip_hs_sig_clear)."""
         capi.call("slamhip_hs_sig_clear", self._h)
@@ -1142,13 +1179,29 @@ class HectorSLAMProcessor:
             h["pose"][0] += off[0]; h["pose"][1] += off[1]
         return out
 
-    def AddKeyframe(self, scan, poseWorld):
+    def AddKeyframe(self, scan, poseWorld, keep_scan=False):
         """The signature of `scan` appended to the keyframe store with its WORLD pose (slamhip_hsproc_sig_add; MapRep.SigConfigure
-        first) -> (index, sig, info).  MatchPose, LastMapUpdatePose and the update gate are untouched."""
+        first) -> (index, sig, info).  With keep_scan the scan itself is appended to the scan store too (slamhip_hsproc_scans_add),
+        under the same index: what RenderKeyframes draws from.  MatchPose, LastMapUpdatePose and the update gate are untouched."""
         org = capi.f32(scan.Pose[:2])
         out = capi.sig_add_call("slamhip_hsproc_sig_add", self._h, poseWorld, self.MapRep._sig_n_ring(), (scan.Points, org))
         self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
+        if keep_scan:
+            k = C.c_int32()
+            capi.call("slamhip_hsproc_scans_add", self._h, C.byref(k))
+            assert k.value == out[0], (k.value, out[0])             # (the two stores' indices agree)
         return out
+
+    def RenderKeyframes(self, poses=None, first=0, last=None, keep=False):
+        """Draw the stored keyframe scans [first, last) into the map at WORLD poses (slamhip_hsproc_render) -- by default the poses
+        of the signature store, which RelaxKeyframes has just corrected.  Without keep the map is cleared first."""
+        last = self.MapRep.ScansCount() if last is None else int(last)
+        if poses is None:
+            _, kp = self.MapRep.SigDownload()
+            poses = kp[first:last]
+        p = capi.f32(poses, (-1, 3)) if last > first else np.zeros((1, 3), np.float32)
+        assert last <= first or p.shape[0] == last - first
+        capi.call("slamhip_hsproc_render", self._h, int(first), last, capi._vp(p), capi.RENDER_KEEP if keep else 0)
 
     def LoopCandidates(self, scan, B=capi.SIG_MAX_HITS, exclude_recent=0):
         """The keyframes `scan` resembles most, over all 64 headings (slamhip_hsproc_sig_query over [0, count - exclude_recent))
