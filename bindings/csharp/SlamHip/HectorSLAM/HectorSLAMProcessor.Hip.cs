@@ -506,6 +506,50 @@ namespace HectorSLAM.Main
             return res;
         }
 
+        /// <summary>MapRep.ScansMatch through the processor (slamhip_hsproc_scans_match): relative poses, no frame to convert.</summary>
+        public unsafe ScanMatchResult[] ScansMatch(ScanMatchSpec spec, ScanPair[] pairs)
+        {
+            var res = new ScanMatchResult[Math.Max(pairs.Length, 1)];
+            ScanPair[] pr = pairs.Length > 0 ? pairs : new ScanPair[1];
+            fixed (ScanPair* p = pr) fixed (ScanMatchResult* r = res)
+                Native.Check(Native.slamhip_hsproc_scans_match(proc.Ptr, spec, p, pairs.Length, r));
+            Array.Resize(ref res, pairs.Length);
+            return res;
+        }
+
+        /// <summary>Close the loops of the keyframe store (host composition; KeepKeyframeScan after every AddKeyframe first):
+        /// SelfLoopCandidates names one candidate per keyframe, its guess (0, 0, -Shift 2 pi / 64) by K18's sign rule; ScansMatch and
+        /// MapRepMultiMap.ScansEdges turn the candidates into edges (keyframe hit.Index to keyframe i); accept, the caller's predicate
+        /// over a result's Score, QueryCount and Count, filters them -- the library sets no threshold; RelaxKeyframes adds the
+        /// odometry edges, relaxes and writes the poses back; with render the stored scans are drawn again at them.  Returns the
+        /// accepted edges; relaxed is null when there is none.</summary>
+        public LoopEdge[] CloseLoops(int minGap, ScanMatchSpec spec, Func<ScanMatchResult, bool> accept, Vector3 odomW, PgSpec pg, bool render, out Vector3[] relaxed)
+        {
+            relaxed = null;
+            int n = MapRep.SigCount;
+            SigHit[] hits = SelfLoopCandidates(0, n, minGap);
+            var pairs = new System.Collections.Generic.List<ScanPair>();
+            for (int i = 0; i < hits.Length; i++)
+            {
+                if (hits[i].Index < 0) continue;
+                float th = (float)Math.IEEERemainder(-hits[i].Shift * 2.0 * Math.PI / 64.0, 2.0 * Math.PI);
+                pairs.Add(new ScanPair { Ref = hits[i].Index, Query = i, Guess = new Vector3(0f, 0f, th) });
+            }
+            if (pairs.Count == 0) return new LoopEdge[0];
+            ScanPair[] pr = pairs.ToArray();
+            ScanMatchResult[] res = ScansMatch(spec, pr);
+            MapRepMultiMap.ScansEdges(spec, pr, res, out double[] z, out double[] w, out bool[] valid);
+            var loops = new System.Collections.Generic.List<LoopEdge>();
+            for (int k = 0; k < pr.Length; k++)
+                if (valid[k] && accept(res[k]))
+                    loops.Add(new LoopEdge { I = pr[k].Ref, J = pr[k].Query, Z = new Vector3((float)z[3 * k], (float)z[3 * k + 1], (float)z[3 * k + 2]),
+                                             W = new Vector3((float)w[3 * k], (float)w[3 * k + 1], (float)w[3 * k + 2]) });
+            if (loops.Count == 0) return new LoopEdge[0];
+            relaxed = RelaxKeyframes(loops.ToArray(), odomW, pg, out _, out _);
+            if (render) RenderKeyframes(relaxed, 0, n);
+            return loops.ToArray();
+        }
+
         /// <summary>One hypothesis of AlignMaps: the rotation index m (theta = m pi / T), the WORLD pose of the source frame, and its
         /// merge report.</summary>
         public struct MapAlignment { public int M; public Vector3 PoseWorld; public MergeReport Report; }

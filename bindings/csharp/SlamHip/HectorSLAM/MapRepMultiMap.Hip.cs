@@ -733,6 +733,43 @@ namespace HectorSLAM.Main
             fixed (Vector3* pp = p) Native.Check(Native.slamhip_hs_render(Pyramid.Ptr, first, last, pp, keep ? 1 : 0));
         }
 
+        /// <summary>Match stored scans pairwise (slamhip_hs_scans_match): per pair the best node of the lattice round its guess, an
+        /// integer score and the moments of the near-optimal nodes.</summary>
+        public unsafe ScanMatchResult[] ScansMatch(ScanMatchSpec spec, ScanPair[] pairs)
+        {
+            var res = new ScanMatchResult[Math.Max(pairs.Length, 1)];
+            ScanPair[] pr = pairs.Length > 0 ? pairs : new ScanPair[1];
+            fixed (ScanPair* p = pr) fixed (ScanMatchResult* r = res)
+                Native.Check(Native.slamhip_hs_scans_match(Pyramid.Ptr, spec, p, pairs.Length, r));
+            Array.Resize(ref res, pairs.Length);
+            return res;
+        }
+
+        /// <summary>The results of ScansMatch as pose-graph edges (slamhip_hs_scans_edges; host only): z and w hold three doubles
+        /// per pair, valid one flag.</summary>
+        public static unsafe void ScansEdges(ScanMatchSpec spec, ScanPair[] pairs, ScanMatchResult[] results, out double[] z, out double[] w, out bool[] valid)
+        {
+            int n = pairs.Length;
+            z = new double[3 * Math.Max(n, 1)]; w = new double[3 * Math.Max(n, 1)];
+            var v = new int[Math.Max(n, 1)];
+            fixed (ScanPair* p = pairs) fixed (ScanMatchResult* r = results) fixed (double* pz = z, pw = w) fixed (int* pv = v)
+                Native.Check(Native.slamhip_hs_scans_edges(spec, p, r, n, pz, pw, pv));
+            valid = new bool[n];
+            for (int i = 0; i < n; i++) valid[i] = v[i] != 0;
+        }
+
+        /// <summary>Rules 1 - 5 of slamhip_hs_scans_match on the host (slamhip_debug_scans_match; no device involved): points holds all
+        /// scans one behind the other, offsets their starts and the total.</summary>
+        public static unsafe ScanMatchResult[] DebugScansMatch(Vector2[] points, int[] offsets, ScanMatchSpec spec, ScanPair[] pairs)
+        {
+            var res = new ScanMatchResult[Math.Max(pairs.Length, 1)];
+            Vector2[] pts = points.Length > 0 ? points : new Vector2[1];
+            fixed (Vector2* xy = pts) fixed (int* off = offsets) fixed (ScanPair* p = pairs) fixed (ScanMatchResult* r = res)
+                Native.Check(Native.slamhip_debug_scans_match(xy, off, offsets.Length - 1, spec, p, pairs.Length, r));
+            Array.Resize(ref res, pairs.Length);
+            return res;
+        }
+
         /// <summary>Free the blocks of the scan signatures and forget the spec (slamhip_hs_sig_clear).</summary>
         public void SigClear()
         {

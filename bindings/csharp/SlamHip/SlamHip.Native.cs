@@ -288,6 +288,34 @@ namespace SlamHip
         public double Lambda, Tolerance;
     }
 
+    /// <summary>slamhip_scanmatch_spec (include/slamhip.h): cells per metre, the raster's half side H (a multiple of 16 in [16, 192]),
+    /// the lattice's half widths (each at most 64), the heading step, the margin of the near-optimal set, 0.  32 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ScanMatchSpec
+    {
+        public float Scale;
+        public int Half, Nx, Ny, Nt;
+        public float DTheta;
+        public int Margin, Reserved;
+    }
+
+    /// <summary>slamhip_scan_pair: two indices into the scan store and the guess, the QUERY's pose in the REFERENCE's frame.  20 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ScanPair
+    {
+        public int Ref, Query;
+        public Vector3 Guess;
+    }
+
+    /// <summary>slamhip_scanmatch_result: the best node and its score, the points that counted, the size of the near-optimal set and
+    /// its nine integer moments.  104 bytes, no padding.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct ScanMatchResult
+    {
+        public int K, Ix, Iy, Score, RefCount, QueryCount, Count, Reserved;
+        public long SumX, SumY, SumK, SumXX, SumYY, SumKK, SumXY, SumXK, SumYK;
+    }
+
     /// <summary>slamhip_pg_iter (include/slamhip.h): chi2 before the step, rz0, the last rz, the PCG iterations completed and why they
     /// stopped (0 tolerance reached, 1 CgCount reached, 2 breakdown).  32 bytes.</summary>
     [StructLayout(LayoutKind.Sequential)]
@@ -473,6 +501,10 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_scans_download(IntPtr hs, int k, Vector2* points, int cap);
         [DllImport(Lib)] internal static extern int slamhip_hs_scans_clear(IntPtr hs);
         [DllImport(Lib)] internal static extern int slamhip_hs_render(IntPtr hs, int first, int last, Vector3* poses, int flags);
+        // stored scans matched pairwise (no reference counterpart), the edge rule and the host-side hook
+        [DllImport(Lib)] internal static extern int slamhip_hs_scans_match(IntPtr hs, in ScanMatchSpec spec, ScanPair* pairs, int nPairs, ScanMatchResult* results);
+        [DllImport(Lib)] internal static extern int slamhip_hs_scans_edges(in ScanMatchSpec spec, ScanPair* pairs, ScanMatchResult* results, int n, double* z, double* w, int* valid);
+        [DllImport(Lib)] internal static extern int slamhip_debug_scans_match(Vector2* points, int* offsets, int nScans, in ScanMatchSpec spec, ScanPair* pairs, int nPairs, ScanMatchResult* results);
         [DllImport(Lib)] internal static extern int slamhip_debug_nearest_field(byte* cls, int cw, int ch, int siteMask, int radius, int x, int y, int w, int h, short* dxdy);
         // the frontier cells and their connected clusters (no reference counterpart), and their host-side hook
         [DllImport(Lib)] internal static extern int slamhip_hs_frontiers(IntPtr hs, int level, int world, int minCells, int maxClusters, out FrontierSummary summary, FrontierCluster* clusters,
@@ -558,6 +590,7 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hsproc_sig_self(IntPtr proc, int first, int last, int minGap, SigHit* hits);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_scans_add(IntPtr proc, out int index);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_render(IntPtr proc, int first, int last, Vector3* poses, int flags);
+        [DllImport(Lib)] internal static extern int slamhip_hsproc_scans_match(IntPtr proc, in ScanMatchSpec spec, ScanPair* pairs, int nPairs, ScanMatchResult* results);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_mcl_step(IntPtr proc, Vector2* points, int nPoints, in Vector2 scanOrigin, in MclSpec spec, out MclSummary summary);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_set_source(IntPtr proc, int level, int ax, int ay, int w, int h, HectorSLAM.Map.LogOddsCell* cells);
         [DllImport(Lib)] internal static extern int slamhip_hsproc_merge_score(IntPtr proc, Vector3* posesWorld, int nPoses, MergeReport* reports);

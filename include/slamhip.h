@@ -1742,6 +1742,87 @@ int32_t slamhip_debug_render(int32_t n_levels, const int32_t *dims, float cell_l
 int32_t slamhip_debug_render_clip(int32_t da, int32_t db, int32_t T, int32_t n, const int32_t *a0, const int32_t *b0, int32_t *out_i0,
                                   int32_t *out_i1);
 
+/* Stored scans matched pairwise (K21; no reference counterpart).  K18 names loop CANDIDATES between keyframes, K19 spreads a loop's
+ * error over the keyframe poses and asks per edge for a measurement z -- node j seen in node i's frame -- and a weight w; K20 keeps
+ * the keyframes' scans in a device pool.  This unit matches scan against scan for a whole list of (reference, query) pairs of that
+ * pool in ONE call, by a correlative search over a small pose lattice round a guess per pair, and returns per pair the best node, an
+ * integer score and integer moments of the near-optimal nodes; a host rule turns those into (z, w).  The map takes no part: it is
+ * the drifted one a loop is meant to correct.  slamhip_hs_update_by_scan and the processor's per-scan call never enter the unit.
+ * THE DEFINITION.  Everything behind the few binary32 operations that place a point in a cell is an integer, so no order of atomics
+ * or reductions changes a bit.  H = spec->half; a pair is (ref, query, guess), the guess being the QUERY's pose in the REFERENCE's
+ * frame -- K19's direction with ref = edge end i and query = end j.  A scan's stored origin plays no part.
+ *  1. Reference raster, 2H x 2H cells.  For a stored point (px, py) of scan `ref`: fx = px * scale, fy = py * scale, one binary32
+ *     multiply each.  A point with a NaN or with |f| >= 2^14 on either axis is IGNORED (K18's rule 2).  Its cell is (floor(fx) + H,
+ *     floor(fy) + H); a cell outside [0, 2H)^2 marks nothing.  hit(x, y): some point has that cell.  near(x, y): some cell of the
+ *     3 x 3 block round (x, y), clipped to the grid, is hit.  val = 2 if hit, else 1 if near, else 0; outside the grid val = 0.
+ *     n_ref = the points that were not ignored (inside the grid or not).
+ *  2. Query cells: K7's arithmetic to the letter (slamhip_lattice_spec) with ScaleToMap = scale.  theta_k = guess[2] + (float)k *
+ *     dtheta for k in [-nt, nt]; (s, c) = sh_det_sincosf(theta_k); cxm = guess[0] * scale, cym = guess[1] * scale; per query point
+ *     rx = c * qx - s * qy, ry = s * qx + c * qy; fx = rx * scale + cxm, fy = ry * scale + cym, every operation rounded on its own.
+ *     The point is IGNORED for this heading unless |fx| < 2^24 and |fy| < 2^24 (a NaN fails).  gx = (int)floorf(fx) + H, gy likewise.
+ *  3. score(k, iy, ix) = the sum of val(gx + ix, gy + iy) over the points used, an int32; ix in [-nx, nx], iy in [-ny, ny].
+ *     flat = ((k + nt) * (2 ny + 1) + (iy + ny)) * (2 nx + 1) + (ix + nx).  The best node has the highest score, ties to the lowest
+ *     flat: the largest packed key (score ^ 0x80000000) << 32 | (0xFFFFFFFF - flat), K7's form.  n_query = the points used at the
+ *     best node's heading, so score <= 2 * n_query.
+ *  4. Moments.  b = the best score.  N = the nodes with score >= b - margin and score > 0.  cnt = |N|; nine int64 sums over N:
+ *     ix, iy, k, ix^2, iy^2, k^2, ix * iy, ix * k, iy * k.  If b == 0: cnt = 0, the sums are 0 and the pair is INVALID (the best
+ *     node is then flat 0: k = -nt, iy = -ny, ix = -nx).
+ *  5. The result: slamhip_scanmatch_result below, 104 bytes, no padding.
+ *  6. Edge rule (slamhip_hs_scans_edges), host code in binary64, one rounding per operation, no fused multiply-add:
+ *       zx = ((double)cxm + (double)ix) / (double)scale,  zy = ((double)cym + (double)iy) / (double)scale  (cxm, cym: rule 2's binary32
+ *       values),  zt = (double)theta_k  (rule 2's binary32 value).
+ *     Per axis a with sums S1 = sum a, S2 = sum a^2 and n = (double)cnt:  m = (double)S1 / n;  q = (double)S2 / n;  v = q - (m * m);
+ *     v = 0 unless v > 0;  u2 = u * u;  variance = (v * u2) + (u2 / 12.0);  w_a = 1.0 / variance.  u = 1.0 / (double)scale for x
+ *     and y -- the near-optimal nodes' spread plus the variance of a uniform error over one cell.  For the heading u =
+ *     |(double)dtheta|, EXCEPT when nt == 0 or dtheta == 0: then the lattice says nothing about the heading and u = 6.283185307179586
+ *     / 64.0, K18's sector, the resolution of the candidate's shift the guess came from.  With scale and dtheta binary32 values and
+ *     |a| <= 64 no u2 underflows and no variance overflows in binary64: every weight of a valid pair is finite and > 0, as
+ *     slamhip_hs_pg_set demands.  valid = cnt > 0; an invalid pair gets its best node's z, w = (0, 0, 0) and valid = 0, and must
+ *     not become an edge.  The three cross sums are delivered and not used: K19 takes diagonal weights.
+ *  7. SLAMHIP_ERR_INVALID, nothing launched and nothing written: scale not finite or <= 0; half no multiple of 16 in [16, 192]; nx,
+ *     ny or nt outside [0, 64]; dtheta not finite; margin < 0; reserved != 0; n_pairs outside [1, 4096]; more than 2^20 nodes per
+ *     pair or 2^26 in the call; a guess component that is not finite; a scan index outside the store.  SLAMHIP_ERR_STATE: no scan
+ *     store, or an empty one (tested behind the spec, the count and the guesses, ahead of the indices).
+ * Blocking, with the context's bounded wait, on the operator's stream behind everything already enqueued; the pairs go out and the
+ * results come back through pinned staging the unit owns (freed by slamhip_hs_destroy).  Two launches of one kernel: the first
+ * leaves every pair's best key, the second -- which forms the scores again rather than keep a volume of up to 2^26 of them -- the
+ * moments and n_query.  A workgroup of 256 lanes owns (pair, block of headings): it builds the reference raster in LDS (2 bits per
+ * cell, 36 KB at H = 192; LDS atomic OR, then the dilation behind a barrier), stages a heading's query cells in chunks of 1024, and
+ * a lane walks the points for one translation at a time.  The map, the signature store, the pose graph and the scan that is set
+ * are neither read nor written. */
+typedef struct slamhip_scanmatch_spec {
+    float scale;                       /* offset 0: cells per metre, finite and > 0; the caller's choice, unrelated to any map level */
+    int32_t half;                      /* offset 4: H, a multiple of 16 in [16, 192] */
+    int32_t nx, ny;                    /* offsets 8, 12: each in [0, 64] */
+    int32_t nt;                        /* offset 16: in [0, 64] */
+    float dtheta;                      /* offset 20: finite */
+    int32_t margin;                    /* offset 24: >= 0 */
+    int32_t reserved;                  /* offset 28: 0 */
+} slamhip_scanmatch_spec;              /* 32 bytes */
+typedef struct slamhip_scan_pair {
+    int32_t ref, query;                /* offsets 0, 4: indices into the scan store */
+    float guess[3];                    /* offset 8: the query's pose in the reference's frame */
+} slamhip_scan_pair;                   /* 20 bytes */
+typedef struct slamhip_scanmatch_result {
+    int32_t k, ix, iy, score;          /* offsets 0, 4, 8, 12: the best node and its score */
+    int32_t n_ref, n_query, cnt;       /* offsets 16, 20, 24 */
+    int32_t reserved;                  /* offset 28: 0 */
+    int64_t sum_x, sum_y, sum_k;       /* offsets 32, 40, 48: sums over N of ix, iy, k */
+    int64_t sum_xx, sum_yy, sum_kk;    /* offsets 56, 64, 72 */
+    int64_t sum_xy, sum_xk, sum_yk;    /* offsets 80, 88, 96 */
+} slamhip_scanmatch_result;            /* 104 bytes */
+int32_t slamhip_hs_scans_match(slamhip_hs *hs, const slamhip_scanmatch_spec *spec, const slamhip_scan_pair *pairs, int32_t n_pairs,
+                               slamhip_scanmatch_result *out_results);
+/* Rule 6 for n results: out_z and out_w n x 3 doubles, out_valid n int32.  Touches no device.  SLAMHIP_ERR_INVALID, nothing written:
+ * rule 7's refusals for the spec, n and the guesses; a result whose node lies outside the lattice. */
+int32_t slamhip_hs_scans_edges(const slamhip_scanmatch_spec *spec, const slamhip_scan_pair *pairs, const slamhip_scanmatch_result *results,
+                               int32_t n, double *out_z, double *out_w, int32_t *out_valid);
+/* Test hook (no device involved): rules 1 - 5 over the caller's arrays in plain loops, from the header text the kernels run
+ * (hs_scanmatch.h).  xy: all scans' points; offsets: N + 1 entries, the first 0, ascending; the scan store is those N scans (N = 0:
+ * SLAMHIP_ERR_STATE).  Rule 7's refusals, nothing written. */
+int32_t slamhip_debug_scans_match(const float *xy, const int32_t *offsets, int32_t N, const slamhip_scanmatch_spec *spec,
+                                  const slamhip_scan_pair *pairs, int32_t n_pairs, slamhip_scanmatch_result *out_results);
+
 /* The scrolling window -- something the reference lacks (its `offset`, GridMap.cs:45, is ignored by UpdateByScan,
  * OccGridMap.cs:120-123, and by the matcher, ScanMatcher.cs:139-142): the contents of the whole pyramid move by an integer
  * number of cells, on the device, in stream order, so that a robot that drives out of the window can take the window along.
@@ -2010,6 +2091,11 @@ int32_t slamhip_hsproc_sig_self(slamhip_hsproc *p, int32_t first, int32_t last, 
  * alone.  Errors as the slamhip_hs_* calls. */
 int32_t slamhip_hsproc_scans_add(slamhip_hsproc *p, int32_t *out_index);
 int32_t slamhip_hsproc_render(slamhip_hsproc *p, int32_t first, int32_t last, const float *poses_world, int32_t flags);
+/* The scan-to-scan match through the processor: slamhip_hs_scans_match on the processor's own hs, the arguments as given -- a guess
+ * and a result are RELATIVE poses and need no frame conversion.  The processor's stored poses, its update gate, its match report and
+ * the scan that was set are not touched. */
+int32_t slamhip_hsproc_scans_match(slamhip_hsproc *p, const slamhip_scanmatch_spec *spec, const slamhip_scan_pair *pairs, int32_t n_pairs,
+                                   slamhip_scanmatch_result *out_results);
 /* MinDistanceDiffForMapUpdate :51, MinAngleDiffForMapUpdate :56 */
 int32_t slamhip_hsproc_set_thresholds(slamhip_hsproc *p, float min_distance_diff, float min_angle_diff);
 int32_t slamhip_hsproc_hs(slamhip_hsproc *p, slamhip_hs **out_hs);                       /* MapRep :26 */

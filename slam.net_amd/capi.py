@@ -174,6 +174,13 @@ PG_SPEC = np.dtype([("n_outer", np.int32), ("n_cg", np.int32), ("check_every", n
                     ("tol", np.float64)])                                                           # slamhip_pg_spec: 32 bytes
 PG_ITER = np.dtype([("chi2", np.float64), ("rz0", np.float64), ("rz", np.float64), ("cg_iters", np.int32), ("stopped", np.int32)])   # slamhip_pg_iter: 32 bytes
 assert PG_SPEC.itemsize == 32 and PG_ITER.itemsize == 32
+SCANMATCH_MAX_HALF, SCANMATCH_MAX_N, SCANMATCH_MAX_PAIRS, SCANMATCH_MAX_NODES, SCANMATCH_MAX_CALL_NODES = 192, 64, 4096, 1 << 20, 1 << 26   # the limits of slamhip_hs_scans_match
+SCANMATCH_SPEC = np.dtype([("scale", np.float32), ("half", np.int32), ("nx", np.int32), ("ny", np.int32), ("nt", np.int32), ("dtheta", np.float32),
+                           ("margin", np.int32), ("reserved", np.int32)])                                # slamhip_scanmatch_spec: 32 bytes
+SCAN_PAIR = np.dtype([("ref", np.int32), ("query", np.int32), ("guess", np.float32, (3,))])             # slamhip_scan_pair: 20 bytes
+SCANMATCH_RESULT = np.dtype([(n, np.int32) for n in ("k", "ix", "iy", "score", "n_ref", "n_query", "cnt", "reserved")] +
+                            [(n, np.int64) for n in ("sum_x", "sum_y", "sum_k", "sum_xx", "sum_yy", "sum_kk", "sum_xy", "sum_xk", "sum_yk")])   # slamhip_scanmatch_result: 104 bytes
+assert SCANMATCH_SPEC.itemsize == 32 and SCAN_PAIR.itemsize == 20 and SCANMATCH_RESULT.itemsize == 104
 VIEW_MAX_REACH, VIEW_MAX_POSES, VIEW_MAX_K, VIEW_LDS_WORDS = 4096, 4096, 64, 8704   # the limits of slamhip_hs_view_gain / _view_select; K15_LDS_WORDS
 VIEW_SUMMARY = np.dtype([(n, np.int32) for n in ("n_walked", "n_same", "n_ignored", "n_cut", "n_seen", "n_unknown", "n_free", "n_occupied", "n_new",
                                                  "n_new_unknown")])   # slamhip_view_summary: ten int32, 40 bytes
@@ -254,6 +261,7 @@ def _declare(L):
         "slamhip_debug_sig_search": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_debug_pg_relax": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "slamhip_debug_pg_sum": (i32, [vp, i32, vp]),
+        "slamhip_debug_scans_match": (i32, [vp, vp, i32, vp, vp, i32, vp]),
         "slamhip_debug_render": (i32, [i32, vp, f, vp, vp, vp, f, f, vp, vp, vp, vp, i32, i32]),
         "slamhip_debug_render_clip": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),
         "slamhip_debug_sincos": (i32, [vp, i32, vp, vp]),
@@ -382,6 +390,8 @@ def _declare(L):
         "slamhip_hs_scans_download": (i32, [vp, i32, vp, i32]),
         "slamhip_hs_scans_clear": (i32, [vp]),
         "slamhip_hs_render": (i32, [vp, i32, i32, vp, i32]),
+        "slamhip_hs_scans_match": (i32, [vp, vp, vp, i32, vp]),
+        "slamhip_hs_scans_edges": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hs_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hs_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -432,6 +442,7 @@ def _declare(L):
         "slamhip_hsproc_sig_self": (i32, [vp, i32, i32, i32, vp]),
         "slamhip_hsproc_scans_add": (i32, [vp, ip]),
         "slamhip_hsproc_render": (i32, [vp, i32, i32, vp, i32]),
+        "slamhip_hsproc_scans_match": (i32, [vp, vp, vp, i32, vp]),
         "slamhip_hsproc_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hsproc_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hsproc_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -1120,3 +1131,54 @@ def debug_render_clip(da, db, T, a0, b0):
     i0 = np.zeros(max(a.size, 1), np.int32); i1 = np.zeros(max(a.size, 1), np.int32)
     call("slamhip_debug_render_clip", int(da), int(db), int(T), a.size, _vp(a) if a.size else _vp(i0), _vp(b) if b.size else _vp(i0), _vp(i0), _vp(i1))
     return i0[:a.size], i1[:a.size]
+
+
+def scanmatch_spec(scale, half, nx, ny, nt, dtheta, margin=0, reserved=0):
+    """A slamhip_scanmatch_spec record (a (1,) SCANMATCH_SPEC array)."""
+    sp = np.zeros(1, SCANMATCH_SPEC)
+    sp["scale"] = np.float32(scale); sp["half"] = int(half); sp["nx"] = int(nx); sp["ny"] = int(ny); sp["nt"] = int(nt)
+    sp["dtheta"] = np.float32(dtheta); sp["margin"] = int(margin); sp["reserved"] = int(reserved)
+    return sp
+
+
+def scan_pairs(pairs):
+    """(ref, query, (gx, gy, gtheta)) tuples, or a SCAN_PAIR array -> a contiguous SCAN_PAIR array (a copy)."""
+    if isinstance(pairs, np.ndarray) and pairs.dtype == SCAN_PAIR:
+        return np.ascontiguousarray(pairs).reshape(-1).copy()
+    out = np.zeros(len(pairs), SCAN_PAIR)
+    for i, (r, q, g) in enumerate(pairs):
+        out[i]["ref"] = int(r); out[i]["query"] = int(q); out[i]["guess"] = f32(g, (3,))
+    return out
+
+
+def scans_match_call(name, handle, spec, pairs):
+    """slamhip_hs_scans_match / slamhip_hsproc_scans_match -> a SCANMATCH_RESULT array, one record per pair."""
+    pr = scan_pairs(pairs)
+    out = np.zeros(max(pr.shape[0], 1), SCANMATCH_RESULT)
+    call(name, handle, spec.ctypes.data_as(C.c_void_p), pr.ctypes.data_as(C.c_void_p), pr.shape[0], out.ctypes.data_as(C.c_void_p))
+    return out[:pr.shape[0]].copy()
+
+
+def scans_edges(spec, pairs, results):
+    """Rule 6 of slamhip_hs_scans_match (slamhip_hs_scans_edges; no device involved) -> (z (n, 3), w (n, 3) float64, valid (n,) bool)."""
+    pr = scan_pairs(pairs); rs = np.ascontiguousarray(results, SCANMATCH_RESULT).reshape(-1)
+    assert pr.shape[0] == rs.shape[0]
+    n = pr.shape[0]
+    z = np.zeros((max(n, 1), 3), np.float64); w = np.zeros((max(n, 1), 3), np.float64); v = np.zeros(max(n, 1), np.int32)
+    call("slamhip_hs_scans_edges", spec.ctypes.data_as(C.c_void_p), pr.ctypes.data_as(C.c_void_p), rs.ctypes.data_as(C.c_void_p), n,
+         z.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p))
+    return z[:n].copy(), w[:n].copy(), v[:n].astype(bool)
+
+
+def debug_scans_match(scans, spec, pairs):
+    """Rules 1 - 5 of slamhip_hs_scans_match on the host (slamhip_debug_scans_match; no device involved): scans a list of (n_i, 2)
+    point arrays standing for the scan store -> a SCANMATCH_RESULT array, one record per pair."""
+    pts = [f32(s, (-1, 2)) for s in scans]
+    off = np.zeros(len(pts) + 1, np.int32)
+    off[1:] = np.cumsum([p.shape[0] for p in pts])
+    xy = np.ascontiguousarray(np.concatenate(pts, axis=0)) if pts and off[-1] else np.zeros((1, 2), np.float32)
+    pr = scan_pairs(pairs)
+    out = np.zeros(max(pr.shape[0], 1), SCANMATCH_RESULT)
+    call("slamhip_debug_scans_match", _vp(xy), _vp(off), len(pts), spec.ctypes.data_as(C.c_void_p), pr.ctypes.data_as(C.c_void_p), pr.shape[0],
+         out.ctypes.data_as(C.c_void_p))
+    return out[:pr.shape[0]].copy()

@@ -51,7 +51,8 @@ struct hs_view;                            // hs_view.hip
 struct hs_hough;                           // hs_hough.hip
 struct hs_sig;                             // hs_sig.hip
 struct hs_pg;                              // hs_pg.hip
-struct hs_scans;                           // hs_render.hip
+struct hs_scans;                           // hs_scans.h
+struct hs_scanmatch;                       // hs_scanmatch.hip
 template <typename T> struct hs_field_of;  // hs_dfield.h
 typedef hs_field_of<uint16_t> hs_field;
 struct slamhip_hs {
@@ -93,6 +94,7 @@ struct slamhip_hs {
     struct hs_sig *sig;                                    // slamhip_hs_sig_configure / _sig_add / _sig_query / _sig_self: the spec, the store of keyframe signatures, the poses and the results' blocks, made by configure, kept
     struct hs_scans *scn;                                  // slamhip_hs_scans_add / slamhip_hs_render: the store of keyframe scans -- the records on the host, the points in one device pool -- and the blocks of a render, made by the first call, kept
     struct hs_pg *pg;                                      // slamhip_hs_pg_set / _pg_relax / _pg_get / _pg_residuals: the pose graph's one device block and its pinned staging, made by the first set, kept
+    struct hs_scanmatch *smt;                              // slamhip_hs_scans_match: the pairs' and the results' device blocks and their pinned staging, made by the first call, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -247,3 +249,5 @@ void    hs_pg_reset(slamhip_hs *hs);        // slamhip_hs_reset: no graph from h
 // hs_render.hip
 void    hs_scn_free(slamhip_hs *hs);        // the store of keyframe scans and the blocks of a render (the caller has drained the stream)
 void    hs_scn_reset(slamhip_hs *hs);       // slamhip_hs_reset: the store is empty from here on; the pool and the blocks stay
+// hs_scanmatch.hip
+void    hs_smt_free(slamhip_hs *hs);        // the blocks of the scan-to-scan match (the caller has drained the stream)

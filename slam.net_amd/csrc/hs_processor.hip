@@ -506,6 +506,13 @@ extern "C" int32_t slamhip_hsproc_scans_add(slamhip_hsproc *p, int32_t *out_inde
     return slamhip_hs_scans_add(p->hs, nullptr, 0, nullptr, out_index);
 }
 
+extern "C" int32_t slamhip_hsproc_scans_match(slamhip_hsproc *p, const slamhip_scanmatch_spec *spec, const slamhip_scan_pair *pairs, int32_t n_pairs,
+                                              slamhip_scanmatch_result *out_results)
+{
+    SH_CHECK_ARG(p);
+    return slamhip_hs_scans_match(p->hs, spec, pairs, n_pairs, out_results);   // (relative poses: no frame to convert)
+}
+
 extern "C" int32_t slamhip_hsproc_render(slamhip_hsproc *p, int32_t first, int32_t last, const float *poses_world, int32_t flags)
 {
     SH_CHECK_ARG(p);

@@ -19,6 +19,7 @@
 //    No global atomic, no wait on another workgroup: a cell has one writer.
 #include "hs_blocks.h"
 #include "hs_render.h"
+#include "hs_scans.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -29,9 +30,8 @@
 
 static_assert(SLAMHIP_RENDER_KEEP == 1, "the flag of include/slamhip.h");
 
-struct k20_scan { long long off; int n; float ox, oy; int pad; };          // a stored scan: where its points lie in the pool, how many, its origin
 struct k20_box { short x0, y0, x1, y1, bx, by; int nv; };                  // per (scan, level); nv == 0: no valid line, the rest is not read
-static_assert(sizeof(k20_scan) == 24 && sizeof(k20_box) == 16, "the records the kernels read");
+static_assert(sizeof(k20_box) == 16, "the record the kernels read");       // (k20_scan, a stored scan's record: hs_scans.h)
 
 struct k20_level { int w, h; slamhip_cell *cells; float *prob; int base; int tiles_x, tile0; };    // base: the level's update index in front of the launch's first scan
 struct k20_arg {
@@ -161,14 +161,7 @@ __global__ void __launch_bounds__(K20_LANES) k20_render(const k20_arg A)
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
-// What the unit keeps: the records, the pool, and the blocks of a render -- the launch's records, matrices and boxes in device
-// memory and the pinned block the first two leave the host through (a download's points arrive in it).
-struct hs_scans {
-    std::vector<k20_scan> recs;
-    float2 *d_pool; size_t cap_pts, used_pts;
-    unsigned char *d_in; size_t cap_in;
-    unsigned char *h_io; size_t cap_h;
-};
+// What the unit keeps: struct hs_scans, hs_scans.h (K21 reads the pool and the records).
 
 void hs_scn_free(slamhip_hs *hs)
 {

@@ -742,6 +742,17 @@ class MapRepMultiMap:
         assert last <= first or p.shape[0] == last - first
         capi.call("slamhip_hs_render", self._h, int(first), last, capi._vp(p), capi.RENDER_KEEP if keep else 0)
 
+    def scans_match(self, spec, pairs):
+        """Match stored scans pairwise (slamhip_hs_scans_match; no reference counterpart): spec a capi.scanmatch_spec record, pairs
+        (ref, query, guess) tuples or a capi.SCAN_PAIR array, the guess being the query's pose in the reference's frame -> a
+        capi.SCANMATCH_RESULT array, one record per pair."""
+        return capi.scans_match_call("slamhip_hs_scans_match", self._h, spec, pairs)
+
+    @staticmethod
+    def scans_edges(spec, pairs, results):
+        """The results of scans_match as pose-graph edges (slamhip_hs_scans_edges; host only) -> (z (n, 3), w (n, 3), valid (n,))."""
+        return capi.scans_edges(spec, pairs, results)
+
     def SigClear(self):
         """Free the blocks of the scan signatures and forget the spec (slamhip_hs_sig_clear)."""
         capi.call("slamhip_hs_sig_clear", self._h)
@@ -1247,6 +1258,49 @@ class HectorSLAMProcessor:
         _, chi2 = rep.PgResiduals()
         rep.SigSetPoses(out.astype(np.float32))
         return out, iters, chi2
+
+    def scans_match(self, spec, pairs):
+        """MapRep.scans_match through the processor (slamhip_hsproc_scans_match): relative poses, no frame to convert."""
+        return capi.scans_match_call("slamhip_hsproc_scans_match", self._h, spec, pairs)
+
+    def close_loops(self, min_gap, spec, accept, odom_w=(400.0, 400.0, 2500.0), pg=None, render=False, guess_from_poses=False):
+        """Close the loops of the keyframe store (host composition; AddKeyframe with keep_scan first): SelfLoopCandidates(min_gap) names
+        one candidate per keyframe; its guess is (0, 0, -shift 2 pi / 64) by K18's sign rule -- or, with guess_from_poses, the
+        translation between the two stored poses in the candidate's frame; scans_match turns the candidates into edges (keyframe
+        hit.index -> keyframe i) and `accept`, the caller's predicate over a capi.SCANMATCH_RESULT record (score, n_query, cnt), filters
+        them: the library sets no threshold.  RelaxKeyframes then adds the odometry edges of consecutive stored poses (weights odom_w),
+        relaxes (pg: a capi.pg_spec record; default 5 steps of 4 N iterations) and writes the poses back; render=True draws the
+        stored scans again at them (RenderKeyframes).  -> dict(pairs, results, z, w, accepted (bool array), poses, iters, chi2);
+        without an accepted edge nothing is relaxed and poses is None."""
+        hits = self.SelfLoopCandidates(min_gap)
+        _, kp = self.MapRep.SigDownload()
+        pairs = []
+        for i, h in enumerate(hits):
+            j = int(h["index"])
+            if j < 0:
+                continue
+            th = -int(h["shift"]) * 2.0 * math.pi / capi.SIG_SECTORS
+            g = (0.0, 0.0, math.remainder(th, 2.0 * math.pi))
+            if guess_from_poses:
+                zz = capi.pg_edge_between(kp[j], kp[i])
+                g = (zz[0], zz[1], g[2])
+            pairs.append((j, i, g))
+        out = dict(pairs=pairs, results=None, z=None, w=None, accepted=np.zeros(0, bool), poses=None, iters=None, chi2=None)
+        if not pairs:
+            return out
+        res = self.scans_match(spec, pairs)
+        z, w, valid = capi.scans_edges(spec, pairs, res)
+        ok = np.array([bool(valid[n]) and bool(accept(res[n])) for n in range(len(pairs))], bool)
+        out.update(results=res, z=z, w=w, accepted=ok)
+        loops = [(pairs[n][0], pairs[n][1], z[n], w[n]) for n in range(len(pairs)) if ok[n]]
+        if not loops:
+            return out
+        N = kp.shape[0]
+        poses, iters, chi2 = self.RelaxKeyframes(loops, odom_w, capi.pg_spec(5, 4 * N, tol=1e-8) if pg is None else pg)
+        out.update(poses=poses, iters=iters, chi2=chi2)
+        if render:
+            self.RenderKeyframes()
+        return out
 
     def LocaliseInit(self, poses_world):
         """Start Monte-Carlo localisation: the particle set of the processor's own pyramid (MapRep.mcl_set) from WORLD poses, taken to
