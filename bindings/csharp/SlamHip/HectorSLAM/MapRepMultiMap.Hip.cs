@@ -667,6 +667,27 @@ namespace HectorSLAM.Main
             return iters;
         }
 
+        /// <summary>PgRelax with the odometry-chain preconditioner when tri is true (slamhip_hs_pg_relax_tri: the block-tridiagonal part
+        /// of H, the one for a chain of keyframes closed by a few loops); block-Jacobi otherwise.</summary>
+        public unsafe PgIter[] PgRelax(PgSpec spec, bool tri, out double chi2Final)
+        {
+            if (!tri) return PgRelax(spec, out chi2Final);
+            var iters = new PgIter[Math.Max(spec.OuterCount, 1)];
+            fixed (PgIter* p = iters)
+                Native.Check(Native.slamhip_hs_pg_relax_tri(Pyramid.Ptr, in spec, p, out chi2Final));
+            return iters;
+        }
+
+        /// <summary>z = T^-1 rhs at the poses as they stand (slamhip_hs_pg_tri_apply): N x 3 doubles in, N x 3 doubles out.</summary>
+        public unsafe double[] PgTriApply(double lambda, double[] rhs)
+        {
+            if (rhs.Length != Math.Max(PgNodes, 1) * 3) throw new ArgumentException("rhs: N x 3 doubles");
+            var z = new double[rhs.Length];
+            fixed (double* r = rhs, o = z)
+                Native.Check(Native.slamhip_hs_pg_tri_apply(Pyramid.Ptr, lambda, r, o));
+            return z;
+        }
+
         /// <summary>The graph's poses as they stand (slamhip_hs_pg_get): N x 3 doubles.</summary>
         public unsafe double[] PgGet()
         {

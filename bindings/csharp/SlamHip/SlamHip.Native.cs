@@ -492,6 +492,8 @@ namespace SlamHip
         // relaxation of a pose graph of keyframes (no reference counterpart)
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_set(IntPtr hs, double* poses, byte* isFixed, int nNodes, int* ij, double* z, double* w, int nEdges);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_relax(IntPtr hs, in PgSpec spec, PgIter* iters, out double chi2Final);
+        [DllImport(Lib)] internal static extern int slamhip_hs_pg_relax_tri(IntPtr hs, in PgSpec spec, PgIter* iters, out double chi2Final);
+        [DllImport(Lib)] internal static extern int slamhip_hs_pg_tri_apply(IntPtr hs, double lambda, double* rhs, double* z);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_get(IntPtr hs, double* poses, int nNodes);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_residuals(IntPtr hs, double* r, double* chi2);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_clear(IntPtr hs);

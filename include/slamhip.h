@@ -1625,7 +1625,8 @@ int32_t slamhip_hs_sig_set_poses(slamhip_hs *hs, int32_t first, int32_t n, const
  *  8. Output per outer iteration, slamhip_pg_iter: chi2 BEFORE the step, rz0, the last rz, cg_iters (the iterations completed),
  *     stopped.  chi2 after the last step comes beside the array.
  * Block-Jacobi sees one node at a time, so on chain-like graphs PCG needs a number of iterations of the order of the chain's length
- * (about 3 N for a ring closed by one loop): DESIGN.md section 4 "K19" says what that costs. */
+ * (about 3 N for a ring closed by one loop): DESIGN.md section 4 "K19" says what that costs, and slamhip_hs_pg_relax_tri below is the
+ * preconditioner for that graph. */
 #define SLAMHIP_PG_MAX_NODES (1 << 20)
 #define SLAMHIP_PG_MAX_EDGES (1 << 22)
 #define SLAMHIP_PG_MAX_OUTER 64
@@ -1675,6 +1676,65 @@ int32_t slamhip_debug_pg_relax(double *poses, const uint8_t *fixed, int32_t N, c
                                double *out_r, double *out_chi2);
 int32_t slamhip_debug_pg_sum(const double *v, int32_t L, double *out);
 int32_t slamhip_debug_sincos(const double *a, int32_t n, double *out_s, double *out_c);
+
+/* The odometry-chain preconditioner of the relaxation (K22; no reference counterpart).  The graph this library itself builds
+ * (HectorSLAMProcessor.RelaxKeyframes, close_loops) has an edge (k, k + 1) for every pair of consecutive keyframes and a few loop
+ * edges.  Here PCG is preconditioned by T, the BLOCK-TRIDIAGONAL part of H (the diagonal blocks and the blocks H[n][n + 1],
+ * H[n + 1][n]), solved exactly by block cyclic reduction.  With L' edges that are not chain edges and join two free nodes, H - T has
+ * rank <= 6 L', so PCG ends in at most 6 L' + 1 iterations in exact arithmetic, whatever N is.
+ * THE DEFINITION.  Rules 1 - 3, 5, 6 and 8 of slamhip_hs_pg_relax hold unchanged; rule 4's M and the "z = M res" of rule 7 are
+ * replaced by z = T^-1 res as rules T1 - T5 say.  Binary64 + - * / only, one rounding per operation, in the order the parentheses give.
+ * A symmetric 3 x 3 is computed for a <= b and mirrored; U, W are general 3 x 3.
+ *  T1. Live and dead nodes.  A node is LIVE if it is free and rule 4's det of D_n is > 0; else it is DEAD.  A live node's diagonal
+ *      block is rule 4's D_n (lambda included) and its P_n is rule 4's M_n.  A dead node's diagonal block and P are the identity, its
+ *      couplings are 0, and its z is +0 whatever the right-hand side says.
+ *  T2. Coupling.  For n in [0, N - 1), U_n = H[n][n + 1] starts as +0.  If n and n + 1 are both live: for every edge that joins n and
+ *      n + 1, in either direction, in increasing edge index, with Jn the edge's Jacobian (A or B) at node n and Jm its other one:
+ *        U[a][b] = U[a][b] + (((Jn[0][a] * wx) * Jm[0][b] + (Jn[1][a] * wy) * Jm[1][b]) + (Jn[2][a] * wt) * Jm[2][b]).
+ *      Below the diagonal stands U_n^T.  A missing chain edge or a dead neighbour leaves U_n = 0: the chain falls into segments.
+ *  T3. Factorisation, once per outer iteration: block cyclic reduction.  Level 0 has n_0 = N blocks D_k, U_k and P_k (T1); level l + 1
+ *      has n_{l+1} = ceil(n_l / 2) blocks, until one block is left.  Block m of level l + 1 comes from block k = 2 m of level l:
+ *        D' = D_k;
+ *        if k >= 1:      W = P_{k-1} U_{k-1};   D'[a][b] = D'[a][b] - ((U_{k-1}[0][a] * W[0][b] + U_{k-1}[1][a] * W[1][b]) + U_{k-1}[2][a] * W[2][b]);
+ *        if k + 1 < n_l: W = P_{k+1} U_k^T;     D'[a][b] = D'[a][b] - ((U_k[a][0] * W[0][b] + U_k[a][1] * W[1][b]) + U_k[a][2] * W[2][b]);
+ *        if k + 2 < n_l: W = P_{k+1} U_{k+1};   U'[a][b] = 0 - ((U_k[a][0] * W[0][b] + U_k[a][1] * W[1][b]) + U_k[a][2] * W[2][b]);  else U' = +0;
+ *      where W = P X means W[a][b] = (P[a][0] * X[0][b] + P[a][1] * X[1][b]) + P[a][2] * X[2][b] (X^T: X[b][0], X[b][1], X[b][2]).
+ *      A term whose `if` fails is not subtracted at all.  P' = D'^-1 by rule 4's adjugate over the determinant, P' = 0 unless
+ *      det > 0: nothing ever divides by a determinant that is not positive.
+ *  T4. Solve, z = T^-1 r, once per PCG iteration.  Forward, level l -> l + 1, k = 2 m, with y = P v by rule 4's "M v":
+ *        r' = r_k;
+ *        if k >= 1:      y = P_{k-1} r_{k-1};   r'[a] = r'[a] - ((U_{k-1}[0][a] * y0 + U_{k-1}[1][a] * y1) + U_{k-1}[2][a] * y2);
+ *        if k + 1 < n_l: y = P_{k+1} r_{k+1};   r'[a] = r'[a] - ((U_k[a][0] * y0 + U_k[a][1] * y1) + U_k[a][2] * y2).
+ *      At the last level z = P r.  Backward, level l + 1 -> l: an even k takes z of block k / 2 of level l + 1; an odd k
+ *        t = r_k;   t[a] = t[a] - ((U_{k-1}[0][a] * zl0 + U_{k-1}[1][a] * zl1) + U_{k-1}[2][a] * zl2),            zl = z_{k-1};
+ *        if k + 1 < n_l: t[a] = t[a] - ((U_k[a][0] * zr0 + U_k[a][1] * zr1) + U_k[a][2] * zr2),                  zr = z_{k+1};
+ *        z_k = P_k t.
+ *      At level 0 the z of a dead node is +0 (T1).
+ *  T5. PCG: rule 7 with z = T^-1 res in both places, the same stop rules, the same outputs.  If T is not positive definite -- a chain
+ *      segment with neither a fixed neighbour nor an edge out of it, and lambda = 0 -- pivots of T3 become 0 and PCG may stop with
+ *      `stopped` = 2; block-Jacobi cannot make that graph converge either.  Where no chain edge joins two live nodes T is rule 4's
+ *      block diagonal, and every value equals slamhip_hs_pg_relax's under == (a zero may differ in its sign).
+ * Nothing depends on the grid, the launch shape, check_every or the developer's SLAMHIP_K22_TAIL.
+ * slamhip_hs_pg_relax_tri: the spec, the outputs and the refusals of slamhip_hs_pg_relax; it continues from the poses as they stand, and
+ * calls of either kind may follow one another on one graph.  The levels' blocks (D, P, U and the right-hand sides of about 2 N blocks:
+ * 361 bytes per node, 379 MB at N = 2^20) are made by the first call of this or of _pg_tri_apply, grown with N, and freed by
+ * slamhip_hs_pg_clear / _destroy; a caller that uses neither allocates nothing.  After SLAMHIP_ERR_NOMEM the graph is as it was and
+ * slamhip_hs_pg_relax still runs.  Launches: k22_diag and k22_coupling (a lane per node), k22_reduce (one per level of more than S = 1024
+ * blocks) and k22_factor_tail (ONE workgroup, the levels of at most S blocks) once per outer iteration; per PCG iteration k19_apply,
+ * k22_axpy, then k22_forward per large level, k22_solve_tail (one workgroup, the small levels in LDS) and k22_backward per large level
+ * -- 2 ceil(log2(N / S)) + 1 launches, ONE for N <= S; the last of them leaves the block sums of res . z -- and k19_dir.  The stop word
+ * works as in slamhip_hs_pg_relax.  SLAMHIP_K22_TAIL (developer, read at every call, [1, 1024]) sets S.
+ * slamhip_hs_pg_tri_apply: T1 - T4 alone at the poses as they stand, for one right-hand side: rhs and out = N x 3 doubles.  Blocking.
+ * SLAMHIP_ERR_INVALID: lambda not finite or < 0; SLAMHIP_ERR_STATE: no graph. */
+int32_t slamhip_hs_pg_relax_tri(slamhip_hs *hs, const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final);
+int32_t slamhip_hs_pg_tri_apply(slamhip_hs *hs, double lambda, const double *rhs, double *out);
+/* Test hooks (no device involved), from the header text the kernels run (hs_pg_tri.h) in plain loops.  _pg_relax_tri: the arguments and
+ * refusals of slamhip_debug_pg_relax.  _pg_tri_apply: the graph of slamhip_hs_pg_set, then lambda, rhs and out of slamhip_hs_pg_tri_apply. */
+int32_t slamhip_debug_pg_relax_tri(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w,
+                                   int32_t E, const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final,
+                                   double *out_r, double *out_chi2);
+int32_t slamhip_debug_pg_tri_apply(const double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z,
+                                   const double *w, int32_t E, double lambda, const double *rhs, double *out);
 
 /* MapRepMultiMap.UpdateByScan ->OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */

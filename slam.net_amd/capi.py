@@ -261,6 +261,8 @@ def _declare(L):
         "slamhip_debug_sig_search": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_debug_pg_relax": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "slamhip_debug_pg_sum": (i32, [vp, i32, vp]),
+        "slamhip_debug_pg_relax_tri": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "slamhip_debug_pg_tri_apply": (i32, [vp, vp, i32, vp, vp, vp, i32, C.c_double, vp, vp]),
         "slamhip_debug_scans_match": (i32, [vp, vp, i32, vp, vp, i32, vp]),
         "slamhip_debug_render": (i32, [i32, vp, f, vp, vp, vp, f, f, vp, vp, vp, vp, i32, i32]),
         "slamhip_debug_render_clip": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),
@@ -381,6 +383,8 @@ def _declare(L):
         "slamhip_hs_sig_set_poses": (i32, [vp, i32, i32, fp]),
         "slamhip_hs_pg_set": (i32, [vp, vp, vp, i32, vp, vp, vp, i32]),
         "slamhip_hs_pg_relax": (i32, [vp, vp, vp, vp]),
+        "slamhip_hs_pg_relax_tri": (i32, [vp, vp, vp, vp]),
+        "slamhip_hs_pg_tri_apply": (i32, [vp, C.c_double, vp, vp]),
         "slamhip_hs_pg_get": (i32, [vp, vp, i32]),
         "slamhip_hs_pg_residuals": (i32, [vp, vp, vp]),
         "slamhip_hs_pg_clear": (i32, [vp]),
@@ -1020,16 +1024,33 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None and a.size else None
 
 
-def debug_pg_relax(poses, fixed, ij, z, w, spec):
+def debug_pg_relax(poses, fixed, ij, z, w, spec, entry="slamhip_debug_pg_relax"):
     """The whole definition of slamhip_hs_pg_relax on the host (slamhip_debug_pg_relax; no device involved)
     -> (poses (N, 3), iters PG_ITER (n_outer,), chi2_final, r (E, 3), chi2_e (E,)).  The caller's arrays are not written."""
     p, fx, e, zz, ww = pg_graph(poses, fixed, ij, z, w)
     assert e.shape[0] == zz.shape[0] == ww.shape[0] and (fx is None or fx.shape[0] == p.shape[0])
     iters = np.zeros(max(int(spec["n_outer"][0]), 1), PG_ITER); fin = C.c_double(0.0)
     r = np.zeros((e.shape[0], 3), np.float64); c2 = np.zeros(e.shape[0], np.float64)
-    call("slamhip_debug_pg_relax", _vp(p), _vp(fx), p.shape[0], _vp(e), _vp(zz), _vp(ww), e.shape[0], spec.ctypes.data_as(C.c_void_p),
+    call(entry, _vp(p), _vp(fx), p.shape[0], _vp(e), _vp(zz), _vp(ww), e.shape[0], spec.ctypes.data_as(C.c_void_p),
          iters.ctypes.data_as(C.c_void_p), C.byref(fin), _vp(r), _vp(c2))
     return p, iters[:int(spec["n_outer"][0])].copy(), fin.value, r, c2
+
+
+def debug_pg_relax_tri(poses, fixed, ij, z, w, spec):
+    """The whole definition of slamhip_hs_pg_relax_tri on the host (slamhip_debug_pg_relax_tri; no device involved): what
+    debug_pg_relax returns, with the odometry-chain preconditioner (rules T1 - T5)."""
+    return debug_pg_relax(poses, fixed, ij, z, w, spec, entry="slamhip_debug_pg_relax_tri")
+
+
+def debug_pg_tri_apply(poses, fixed, ij, z, w, lam, rhs):
+    """Rules T1 - T4 on the host (slamhip_debug_pg_tri_apply; no device involved): z = T^-1 rhs at the given poses -> (N, 3) float64."""
+    p, fx, e, zz, ww = pg_graph(poses, fixed, ij, z, w)
+    assert e.shape[0] == zz.shape[0] == ww.shape[0] and (fx is None or fx.shape[0] == p.shape[0])
+    b = np.array(rhs, np.float64).reshape(-1, 3)
+    assert b.shape[0] == p.shape[0]
+    out = np.zeros_like(b)
+    call("slamhip_debug_pg_tri_apply", _vp(p), _vp(fx), p.shape[0], _vp(e), _vp(zz), _vp(ww), e.shape[0], float(lam), _vp(b), _vp(out))
+    return out
 
 
 def debug_pg_sum(v):

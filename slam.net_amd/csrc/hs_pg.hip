@@ -19,6 +19,7 @@
 // workgroup (through LDS, so a workgroup never splits on it) and leaves.  No kernel waits on another workgroup.
 #include "hs_blocks.h"
 #include "hs_pg.h"
+#include "hs_pg_tri.h"
 #include <algorithm>
 #include <string.h>
 #include <vector>
@@ -318,6 +319,8 @@ struct hs_pg {
     k19_arg A;
     unsigned char *d_blob; size_t cap_blob;
     unsigned char *h_io; size_t cap_h;
+    unsigned char *d_tri; size_t cap_tri;                  // K22 (hs_pg_tri.inc): the levels' blocks, made by the first _pg_relax_tri / _pg_tri_apply
+    hs_tri_plan T;
 };
 
 void hs_pg_free(slamhip_hs *hs)
@@ -326,6 +329,7 @@ void hs_pg_free(slamhip_hs *hs)
     if (!g) return;
     hs_release((void **)&g->d_blob, &g->cap_blob, HS_MEM_DEVICE);
     hs_release((void **)&g->h_io, &g->cap_h, HS_MEM_PINNED);
+    hs_release((void **)&g->d_tri, &g->cap_tri, HS_MEM_DEVICE);
     delete g;
     hs->pg = nullptr;
 }
@@ -661,3 +665,5 @@ extern "C" int32_t slamhip_debug_sincos(const double *a, int32_t n, double *out_
     for (int i = 0; i < n; i++) sh_det_sincos(a[i], &out_s[i], &out_c[i]);
     return SLAMHIP_OK;
 }
+
+#include "hs_pg_tri.inc"

@@ -679,12 +679,27 @@ class MapRepMultiMap:
         capi.call("slamhip_hs_pg_set", self._h, capi._vp(p), capi._vp(fx), p.shape[0], capi._vp(e), capi._vp(zz), capi._vp(ww), e.shape[0])
         self._pg_sizes = (p.shape[0], e.shape[0])
 
-    def PgRelax(self, spec):
-        """spec["n_outer"] Gauss-Newton steps from the poses as they stand (slamhip_hs_pg_relax) -> (iters capi.PG_ITER records,
-        chi2 after the last step)."""
+    PG_PRECOND = {"jacobi": "slamhip_hs_pg_relax", "tri": "slamhip_hs_pg_relax_tri"}
+
+    def PgRelax(self, spec, precond="jacobi"):
+        """spec["n_outer"] Gauss-Newton steps from the poses as they stand -> (iters capi.PG_ITER records, chi2 after the last step).
+        precond: "jacobi" (slamhip_hs_pg_relax, a node's own 3 x 3 block) or "tri" (slamhip_hs_pg_relax_tri, the odometry chain's
+        block-tridiagonal part of H: the one for a chain of keyframes closed by a few loops)."""
+        if precond not in self.PG_PRECOND:
+            raise ValueError("precond = %r: one of %s" % (precond, sorted(self.PG_PRECOND)))
         iters = np.zeros(max(int(spec["n_outer"][0]), 1), capi.PG_ITER); fin = C.c_double(0.0)
-        capi.call("slamhip_hs_pg_relax", self._h, spec.ctypes.data_as(C.c_void_p), iters.ctypes.data_as(C.c_void_p), C.byref(fin))
+        capi.call(self.PG_PRECOND[precond], self._h, spec.ctypes.data_as(C.c_void_p), iters.ctypes.data_as(C.c_void_p), C.byref(fin))
         return iters[:int(spec["n_outer"][0])].copy(), fin.value
+
+    def PgTriApply(self, lam, rhs):
+        """z = T^-1 rhs at the poses as they stand (slamhip_hs_pg_tri_apply): the odometry-chain preconditioner alone, lambda = lam on
+        the diagonal, rhs (N, 3) -> (N, 3) float64."""
+        N = getattr(self, "_pg_sizes", (1, 0))[0]
+        b = np.array(rhs, np.float64).reshape(-1, 3)
+        assert b.shape[0] == N
+        out = np.zeros_like(b)
+        capi.call("slamhip_hs_pg_tri_apply", self._h, float(lam), b.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+        return out
 
     def PgGet(self):
         """The graph's poses as they stand (slamhip_hs_pg_get) -> (N, 3) float64."""
@@ -1237,12 +1252,12 @@ class HectorSLAMProcessor:
         adopt=False.  -> (poseWorld, report, info) as Relocalise.  Host composition only; the caller judges the report."""
         return self.Relocalise(scan, hit["pose"], level, nx, ny, n_theta, dtheta, B=B, adopt=False)
 
-    def RelaxKeyframes(self, loops, odom_w, spec, fixed=None):
+    def RelaxKeyframes(self, loops, odom_w, spec, fixed=None, precond="jacobi"):
         """Spread verified loops over the keyframe store's poses (host composition of slamhip_hs_pg_set, _pg_relax, _pg_get,
         _pg_residuals and slamhip_hs_sig_set_poses; no reference counterpart).  Nodes: the store's poses; an odometry edge joins every
         pair of consecutive keyframes, its z formed from their stored poses (capi.pg_edge_between), its weights odom_w = (wx, wy,
         wtheta); one more edge per entry (i, j, z, w) of `loops`, as the caller derives it from VerifyLoop; node 0 is fixed unless
-        `fixed` says otherwise.  The relaxed poses are written back to the store (rounded to binary32, as it keeps them)
+        `fixed` says otherwise; precond as MapRepMultiMap.PgRelax takes it ("tri" fits this graph).  The relaxed poses are written back to the store (rounded to binary32, as it keeps them)
         -> (poses (N, 3) float64, iters, per-edge chi2 at the relaxed poses: the N - 1 odometry edges, then the loops)."""
         rep = self.MapRep
         _, kp = rep.SigDownload()
@@ -1253,7 +1268,7 @@ class HectorSLAMProcessor:
         for (i, j, zl, wl) in loops:
             ij.append((int(i), int(j))); z.append(tuple(float(v) for v in zl)); w.append(tuple(float(v) for v in wl))
         rep.PgSet(poses, fixed, np.array(ij, np.int32).reshape(-1, 2), np.array(z, np.float64).reshape(-1, 3), np.array(w, np.float64).reshape(-1, 3))
-        iters, _ = rep.PgRelax(spec)
+        iters, _ = rep.PgRelax(spec, precond=precond)
         out = rep.PgGet()
         _, chi2 = rep.PgResiduals()
         rep.SigSetPoses(out.astype(np.float32))
@@ -1263,13 +1278,13 @@ class HectorSLAMProcessor:
         """MapRep.scans_match through the processor (slamhip_hsproc_scans_match): relative poses, no frame to convert."""
         return capi.scans_match_call("slamhip_hsproc_scans_match", self._h, spec, pairs)
 
-    def close_loops(self, min_gap, spec, accept, odom_w=(400.0, 400.0, 2500.0), pg=None, render=False, guess_from_poses=False):
+    def close_loops(self, min_gap, spec, accept, odom_w=(400.0, 400.0, 2500.0), pg=None, render=False, guess_from_poses=False, precond="jacobi"):
         """Close the loops of the keyframe store (host composition; AddKeyframe with keep_scan first): SelfLoopCandidates(min_gap) names
         one candidate per keyframe; its guess is (0, 0, -shift 2 pi / 64) by K18's sign rule -- or, with guess_from_poses, the
         translation between the two stored poses in the candidate's frame; scans_match turns the candidates into edges (keyframe
         hit.index -> keyframe i) and `accept`, the caller's predicate over a capi.SCANMATCH_RESULT record (score, n_query, cnt), filters
         them: the library sets no threshold.  RelaxKeyframes then adds the odometry edges of consecutive stored poses (weights odom_w),
-        relaxes (pg: a capi.pg_spec record; default 5 steps of 4 N iterations) and writes the poses back; render=True draws the
+        relaxes (pg: a capi.pg_spec record; default 5 steps of 4 N iterations; precond: RelaxKeyframes') and writes the poses back; render=True draws the
         stored scans again at them (RenderKeyframes).  -> dict(pairs, results, z, w, accepted (bool array), poses, iters, chi2);
         without an accepted edge nothing is relaxed and poses is None."""
         hits = self.SelfLoopCandidates(min_gap)
@@ -1296,7 +1311,7 @@ class HectorSLAMProcessor:
         if not loops:
             return out
         N = kp.shape[0]
-        poses, iters, chi2 = self.RelaxKeyframes(loops, odom_w, capi.pg_spec(5, 4 * N, tol=1e-8) if pg is None else pg)
+        poses, iters, chi2 = self.RelaxKeyframes(loops, odom_w, capi.pg_spec(5, 4 * N, tol=1e-8) if pg is None else pg, precond=precond)
         out.update(poses=poses, iters=iters, chi2=chi2)
         if render:
             self.RenderKeyframes()

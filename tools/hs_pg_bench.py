@@ -15,7 +15,16 @@ THE SAME RUN.
  * Existing path: HectorSLAMProcessor.Update of the trace bench's scan, blocking, median of 35 scans; the new code is never entered on
    it.  With a build of the parent commit at slam.net_amd/build/variants/parent.so (`python tools/build_variant.py HEAD~1 parent`) the
    figure is taken in alternating fresh interpreters, this tree then the parent, three each (`--update-only` with SLAMHIP_LIB set).
-`python tools/hs_pg_bench.py [out.json]` writes profiles/r25_hs_pg.json by default."""
+`python tools/hs_pg_bench.py [out.json]` writes profiles/r25_hs_pg.json by default.
+
+`python tools/hs_pg_bench.py --precond tri [out.json]` (profiles/r28_hs_pg_tri.json): K22, the odometry-chain preconditioner
+(slamhip_hs_pg_relax_tri, _pg_tri_apply) beside block-Jacobi IN THE SAME RUN.  Graphs: the ring with its closing edge (N - 1, 0) alone
+("fixed": one loop to the fixed node), with one more loop between free nodes ("free") and with 16 of them ("loops16"), and the street
+grid, whose vertical edges -- half of all -- are no chain edges.  Per graph and preconditioner: ONE Gauss-Newton step to tol = 1e-6
+(wall clock of the blocking call, the PCG iterations it took; block-Jacobi is capped at 4 N iterations and left out at 2^20 nodes),
+the same call with n_cg = 1 (linearise, factorisation, the start's solve, one iteration, the copies), the time per PCG iteration as
+the difference of the two over the iterations between them, and for tri one blocking _pg_tri_apply (upload, factorisation, solve,
+download) with its backward error |T z - r| / (|T|_1 |z| + |r|) beside scipy's spsolve on the same sparse T."""
 import hashlib
 import json
 import os
@@ -134,6 +143,99 @@ def variant_figures():
     return out
 
 
+def sparse_T(poses, ij, w):
+    """The block-tridiagonal part of H (node 0 fixed: identity), rule 2's trig from the library, as a scipy CSC matrix."""
+    import scipy.sparse as sp
+    N = poses.shape[0]
+    i, j = ij[:, 0].astype(np.int64), ij[:, 1].astype(np.int64)
+    sn, c = capi.debug_sincos(poses[i, 2])
+    dx, dy = poses[j, 0] - poses[i, 0], poses[j, 1] - poses[i, 1]
+    ux, uy = c * dx + sn * dy, c * dy - sn * dx
+    zero, one = np.zeros(i.shape[0]), np.ones(i.shape[0])
+    A = np.stack([np.stack([-c, -sn, uy], 1), np.stack([sn, -c, -ux], 1), np.stack([zero, zero, -one], 1)], 1)
+    B = np.stack([np.stack([c, sn, zero], 1), np.stack([-sn, c, zero], 1), np.stack([zero, zero, one], 1)], 1)
+    rows, cols, vals = [], [], []
+    for (na, Ja), (nb, Jb) in (((i, A), (i, A)), ((j, B), (j, B)), ((i, A), (j, B)), ((j, B), (i, A))):
+        keep = (np.abs(na - nb) <= 1) & (na != 0) & (nb != 0)
+        blk = np.einsum("eka,ek,ekb->eab", Ja[keep], w[keep], Jb[keep])
+        rows.append((3 * na[keep])[:, None, None] + np.arange(3)[None, :, None] + np.zeros((1, 1, 3), np.int64))
+        cols.append((3 * nb[keep])[:, None, None] + np.arange(3)[None, None, :] + np.zeros((1, 3, 1), np.int64))
+        vals.append(blk)
+    rows.append(np.arange(3)); cols.append(np.arange(3)); vals.append(np.ones(3))
+    return sp.csc_matrix((np.concatenate([v.ravel() for v in vals]), (np.concatenate([r.ravel() for r in rows]), np.concatenate([c_.ravel() for c_ in cols]))),
+                         shape=(3 * N, 3 * N))
+
+
+def timed_relax(rep, g, spec, precond, reps):
+    ts = []
+    for _ in range(reps):
+        rep.PgSet(g[0], None, g[1], g[2], g[3])
+        t0 = time.perf_counter(); it, fin = rep.PgRelax(spec, precond=precond); ts.append(time.perf_counter() - t0)
+    return stats(ts), int(it[0]["cg_iters"]), int(it[0]["stopped"]), float(it[0]["chi2"]), float(fin)
+
+
+def with_loops(make, N, n_loops):
+    """The graph of `make` with n_loops more edges between free nodes, spread over the chain."""
+    poses, ij, z, w = make(N)
+    if n_loops:
+        a = (N // 4 + (N // 2) * np.arange(n_loops) // n_loops).astype(np.int32)
+        b = (N // 8 + (N // 16) * np.arange(n_loops) // n_loops + 1).astype(np.int32)
+        e = np.stack([a, b], axis=1)
+        true = make(N)[0]                                                  # (the noisy poses stand in for the truth: the measurement is what matters)
+        zz = rel(true[e[:, 0]], true[e[:, 1]])
+        ij = np.concatenate([ij, e]).astype(np.int32); z = np.concatenate([z, zz]); w = np.concatenate([w, np.tile(1.0 / SIGMA ** 2, (n_loops, 1))])
+    return poses, ij, z, w
+
+
+def tri_main(out_path):
+    ctx = hs.Context(0)
+    rep = hs.MapRepMultiMap(0.1, (64, 64), 1, ctx=ctx)
+    out = {"graphs": {}}
+    for name, make, n_loops in (("ring_fixed", ring, 0), ("ring_free", ring, 1), ("ring_loops16", ring, 16), ("streets", streets, 0)):
+        for N in (1000, 10000, 100000, 1 << 20):
+            g = with_loops(make, N, n_loops)
+            N = g[0].shape[0]
+            reps = 3 if N > 100000 else 7
+            rec = {"N": int(N), "E": int(g[1].shape[0])}
+            for precond in ("tri", "jacobi"):
+                cap = min(4 * N, 1 << 20)
+                if precond == "jacobi" and N > 100000:
+                    continue
+                one, _, _, _, _ = timed_relax(rep, g, capi.pg_spec(1, 1, check_every=1, tol=1e-6), precond, reps)
+                full, iters, stopped, chi0, chi1 = timed_relax(rep, g, capi.pg_spec(1, cap, check_every=64, tol=1e-6), precond, 1 if precond == "jacobi" and N > 10000 else reps)
+                rec[precond] = {"step_to_tol": full, "cg_iters": iters, "stopped": stopped, "chi2_before": chi0, "chi2_after": chi1, "step_n_cg_1": one,
+                                "us_per_pcg_iteration": (full["median_us"] - one["median_us"]) / (iters - 1) if iters > 1 else None}
+            rep.PgSet(g[0], None, g[1], g[2], g[3])
+            rhs = np.random.Generator(np.random.Philox(N)).standard_normal((N, 3)); rhs[0] = 0.0
+            ts = []
+            for _ in range(reps):
+                t0 = time.perf_counter(); zz = rep.PgTriApply(0.0, rhs); ts.append(time.perf_counter() - t0)
+            rec["tri_apply"] = stats(ts)
+            try:
+                import scipy.sparse.linalg as spl
+                T = sparse_T(g[0], g[1], g[3])
+                r = rhs.ravel()
+                n1 = abs(T).sum(axis=0).max()
+                be = lambda v: float(np.linalg.norm(T @ v - r) / (n1 * np.linalg.norm(v) + np.linalg.norm(r)))
+                rec["backward_error"] = {"tri_apply": be(zz.ravel()), "scipy_spsolve": be(spl.spsolve(T, r))}
+            except ImportError:
+                rec["backward_error"] = None
+            out["graphs"]["%s_%d" % (name, N)] = rec
+            print(name, N, json.dumps(rec), flush=True)
+    rep.close()
+    ctx.close()
+    parent = os.path.join(ROOT, "slam.net_amd", "build", "variants", "parent.so")
+    if os.path.exists(parent):
+        out["update_alternating"] = {"this_tree": [], "parent": []}
+        for _ in range(3):
+            out["update_alternating"]["this_tree"].append(child("--update-only", None)["update"])
+            out["update_alternating"]["parent"].append(child("--update-only", parent)["update"])
+        print(json.dumps(out["update_alternating"]), flush=True)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def child(flag, lib):
     """This script again in a fresh interpreter with `lib` (None: this tree's) -> the JSON object it printed last."""
     env = dict(os.environ)
@@ -150,6 +252,13 @@ def main():
         return
     if "--variant-only" in sys.argv:
         print(json.dumps({"figures": variant_figures(), "lib": os.environ.get("SLAMHIP_LIB", "this tree")}))
+        return
+    if "--precond" in sys.argv:
+        at = sys.argv.index("--precond")
+        if sys.argv[at + 1] != "tri":
+            raise SystemExit("--precond tri is the one there is (block-Jacobi is the default run)")
+        rest = sys.argv[1:at] + sys.argv[at + 2:]
+        tri_main(rest[0] if rest else os.path.join(ROOT, "profiles", "r28_hs_pg_tri.json"))
         return
     out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "r25_hs_pg.json")
     ctx = hs.Context(0)
