@@ -1883,6 +1883,85 @@ int32_t slamhip_hs_scans_edges(const slamhip_scanmatch_spec *spec, const slamhip
 int32_t slamhip_debug_scans_match(const float *xy, const int32_t *offsets, int32_t N, const slamhip_scanmatch_spec *spec,
                                   const slamhip_scan_pair *pairs, int32_t n_pairs, slamhip_scanmatch_result *out_results);
 
+/* The consistent set of loop edges (K23; no reference counterpart).  K18 names loop candidates, K21 matches them and gives (z, w),
+ * K19 / K22 relax the graph, K20 draws the map again; a scan-to-scan score cannot see perceptual aliasing -- two similar corridors
+ * score as well as a true revisit -- and ONE such edge bends the whole relaxed map.  This unit is pairwise consistency maximisation:
+ * two loop edges are consistent if the cycle they form with the odometry chain closes within its uncertainty, and the largest
+ * mutually consistent set found by a greedy search from several starts is kept.  slamhip_hs_update_by_scan and the processor's
+ * per-scan call never enter it, and it reads and writes no state of the hs but its own buffers.
+ * THE DEFINITION.  All floating-point arithmetic is binary64 + - * / and rint, ONE rounding per operation (no fused multiply-add),
+ * in the order the parentheses give; everything behind the one comparison d2 <= gamma is an integer.  Inputs: poses = N x 3 doubles
+ * (x, y, theta), the keyframe chain as it stands, node order = odometry order; L edges (ij, z, w) as slamhip_hs_pg_set takes them
+ * (z: node j seen in node i's frame; w: diagonal weights); `use`, a byte per edge (NULL: every edge is used); the spec below.
+ *  1. Per edge a = (i, j, z, w), with p_i, p_j its nodes' poses:  (sI, cI) = sh_det_sincos(p_i.theta) (rule 2 of slamhip_hs_pg_relax);
+ *       Wx = p_i.x + (cI * z.x - sI * z.y);   Wy = p_i.y + (sI * z.x + cI * z.y);   Wtheta = p_i.theta + z.theta
+ *     -- where the edge puts node j;  (sW, cW) = sh_det_sincos(Wtheta);  (sJ, cJ) = sh_det_sincos(p_j.theta);
+ *       vt = 0.5 * (1 / w.x + 1 / w.y);   vtheta = 1 / w.theta.
+ *  2. Per pair a < b.  The odometry from j_a to j_b, in j_a's frame:
+ *       dx = p_jb.x - p_ja.x;   dy = p_jb.y - p_ja.y;   ux = cJ_a * dx + sJ_a * dy;   uy = cJ_a * dy - sJ_a * dx;   utheta = p_jb.theta - p_ja.theta.
+ *     Node j_b through edge a and that odometry:
+ *       Tx = Wx_a + (cW_a * ux - sW_a * uy);   Ty = Wy_a + (sW_a * ux + cW_a * uy);   Ttheta = Wtheta_a + utheta.
+ *     The residual against edge b:
+ *       ex = Tx - Wx_b;   ey = Ty - Wy_b;   etheta = wrap(Ttheta - Wtheta_b)      (wrap: rule 2 of slamhip_hs_pg_relax).
+ *     The variances, with s = (double)(|j_a - j_b| + |i_a - i_b|) -- the odometry steps the cycle holds -- and rho2 = ux * ux + uy * uy:
+ *       Vt = ((vt_a + vt_b) + s * q_t) + vtheta_a * rho2;   Vtheta = (vtheta_a + vtheta_b) + s * q_theta.
+ *     The test:  d2 = (ex * ex + ey * ey) / Vt + (etheta * etheta) / Vtheta;   bit (a, b) = bit (b, a) = use[a] && use[b] && d2 <= gamma.
+ *     A NaN fails (0 / 0 with every variance 0 included).  The diagonal is 0.  This is the isotropic, diagonal-weight approximation
+ *     of the cycle's covariance: the translational variance is one number (the mean of the two axes, the lever arm rho of a's
+ *     heading error added), no cross terms -- enough for K19's diagonal w.  The translational term being isotropic, the result does
+ *     not depend on the frame of `poses` beyond rounding.
+ *  3. Degrees.  adj[v] = row v of the matrix as bits; deg(v) = popcount(adj[v]).
+ *  4. Starts.  The R = min(n_starts, used edges) USED edges of highest degree, ties to the lower index: start rank 0, 1, .. R - 1.
+ *  5. Greedy set from start v0.  Q = {v0}, S = adj[v0].  While S is not empty: g(v) = popcount(adj[v] & S) for v in S; take the v of
+ *     highest g, ties to the lower index; Q += v; S &= adj[v].  Q is a clique and it is maximal (not necessarily a maximum one).
+ *  6. Result.  The largest Q wins, ties to the lower start rank.  keep[a] = 1 for the edges of the winner if its size >= min_clique,
+ *     else keep is all 0 -- the size is reported all the same.  Outputs: keep = L bytes; deg = L int32; slamhip_loops_info below;
+ *     and with SLAMHIP_LOOPS_ADJ in flags the matrix, L x ceil(L / 64) uint64 row-major, bit (a, b) = bit (b & 63) of word
+ *     a * ceil(L / 64) + (b >> 6), the bits past L zero.  Without a used edge R = 0: size 0, start and rank -1.
+ *  7. SLAMHIP_ERR_INVALID, nothing launched and nothing written: L outside [1, 4096]; N outside [1, 2^20]; an edge end outside [0, N)
+ *     (i == j is allowed); a pose, z or w that is not finite; |theta| of a pose or of a z above 32768 (Wtheta stays inside
+ *     sh_det_sincos's contract); a weight <= 0; gamma, q_t or q_theta not finite or < 0; n_starts outside [1, 64]; min_clique < 1;
+ *     flags with other bits; reserved != 0; SLAMHIP_LOOPS_ADJ without out_adj.  There is no SLAMHIP_ERR_STATE: the unit keeps nothing
+ *     between calls except its buffers.
+ * Nothing depends on the grid or the launch shape.  slamhip_hs_loops_consistent blocks, with the context's bounded wait, on the
+ * operator's stream behind everything already enqueued; the host gathers the two poses of every edge, and edges and results pass
+ * through pinned staging the unit owns (freed by slamhip_hs_loops_clear and slamhip_hs_destroy; slamhip_hs_reset leaves them alone).
+ * Launches: k23_edges (a lane per edge, rule 1), k23_pairs (a lane owns a column b, 64 row records in LDS read as broadcasts, a row's
+ * word is the wavefront's ballot: one 64-bit store per word, no atomics), k23_degree (one workgroup: rule 3, rule 4's ranking by the
+ * packed key (deg << 32) | (0xFFFFFFFF - v)), k23_clique (a workgroup per start: S in LDS, the matrix too where its rows fit in 144 KB
+ * -- L <= 1084 -- else read from global memory; rule 5's arg-max by the same packed key), k23_finish (rule 6). */
+#define SLAMHIP_LOOPS_MAX_EDGES 4096
+#define SLAMHIP_LOOPS_MAX_STARTS 64
+#define SLAMHIP_LOOPS_ADJ 1
+typedef struct slamhip_loops_spec {
+    double gamma;                      /* offset 0: finite, >= 0; d2 has 3 degrees of freedom (11.34 is chi-square's 99 %) */
+    double q_t, q_theta;               /* offsets 8, 16: finite, >= 0; variance one odometry step adds, translation (m^2) and heading (rad^2) */
+    int32_t n_starts;                  /* offset 24: [1, 64] */
+    int32_t min_clique;                /* offset 28: >= 1 */
+    int32_t flags;                     /* offset 32: 0 or SLAMHIP_LOOPS_ADJ */
+    int32_t reserved;                  /* offset 36: 0 */
+} slamhip_loops_spec;                  /* 40 bytes */
+typedef struct slamhip_loops_info {
+    int64_t n_pairs;                   /* offset 0: consistent pairs a < b */
+    int32_t n_used;                    /* offset 8: edges with a non-zero use byte */
+    int32_t size;                      /* offset 12: |Q| of the winner (0 without a used edge) */
+    int32_t start;                     /* offset 16: the winner's start edge, -1 without one */
+    int32_t rank;                      /* offset 20: its start rank, -1 without one */
+    int32_t n_starts;                  /* offset 24: R */
+    int32_t reserved;                  /* offset 28: 0 */
+} slamhip_loops_info;                  /* 32 bytes */
+int32_t slamhip_hs_loops_consistent(slamhip_hs *hs, const double *poses, int32_t N, const int32_t *ij, const double *z, const double *w,
+                                    const uint8_t *use, int32_t L, const slamhip_loops_spec *spec, uint8_t *out_keep, int32_t *out_deg,
+                                    slamhip_loops_info *out_info, uint64_t *out_adj);
+/* Free the unit's buffers.  Never fails for an hs that has none. */
+int32_t slamhip_hs_loops_clear(slamhip_hs *hs);
+/* Test hook (no device involved): rules 1 - 6 over the caller's arrays in plain loops, from the header text the kernels run
+ * (hs_loops.h); rule 7's refusals, nothing written.  out_adj is written whenever it is given.  out_d2 (optional): L x L doubles,
+ * rule 2's d2 of the pair (min, max) at [a][b] and [b][a] whatever `use` says, 0 on the diagonal. */
+int32_t slamhip_debug_loops_consistent(const double *poses, int32_t N, const int32_t *ij, const double *z, const double *w,
+                                       const uint8_t *use, int32_t L, const slamhip_loops_spec *spec, uint8_t *out_keep, int32_t *out_deg,
+                                       slamhip_loops_info *out_info, uint64_t *out_adj, double *out_d2);
+
 /* The scrolling window -- something the reference lacks (its `offset`, GridMap.cs:45, is ignored by UpdateByScan,
  * OccGridMap.cs:120-123, and by the matcher, ScanMatcher.cs:139-142): the contents of the whole pyramid move by an integer
  * number of cells, on the device, in stream order, so that a robot that drives out of the window can take the window along.

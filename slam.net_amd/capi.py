@@ -181,6 +181,13 @@ SCAN_PAIR = np.dtype([("ref", np.int32), ("query", np.int32), ("guess", np.float
 SCANMATCH_RESULT = np.dtype([(n, np.int32) for n in ("k", "ix", "iy", "score", "n_ref", "n_query", "cnt", "reserved")] +
                             [(n, np.int64) for n in ("sum_x", "sum_y", "sum_k", "sum_xx", "sum_yy", "sum_kk", "sum_xy", "sum_xk", "sum_yk")])   # slamhip_scanmatch_result: 104 bytes
 assert SCANMATCH_SPEC.itemsize == 32 and SCAN_PAIR.itemsize == 20 and SCANMATCH_RESULT.itemsize == 104
+LOOPS_MAX_EDGES, LOOPS_MAX_NODES, LOOPS_MAX_STARTS, LOOPS_ADJ = 4096, 1 << 20, 64, 1          # the limits of slamhip_hs_loops_consistent; SLAMHIP_LOOPS_ADJ
+LOOPS_LDS_ADJ_BYTES = 144 * 1024                               # HS_LP_LDS_ADJ_BYTES: k23_clique keeps the matrix in LDS while L * (ceil(L / 64) | 1) * 8 is at most this
+LOOPS_SPEC = np.dtype([("gamma", np.float64), ("q_t", np.float64), ("q_theta", np.float64), ("n_starts", np.int32), ("min_clique", np.int32),
+                       ("flags", np.int32), ("reserved", np.int32)])                                    # slamhip_loops_spec: 40 bytes
+LOOPS_INFO = np.dtype([("n_pairs", np.int64), ("n_used", np.int32), ("size", np.int32), ("start", np.int32), ("rank", np.int32),
+                       ("n_starts", np.int32), ("reserved", np.int32)])                                 # slamhip_loops_info: 32 bytes
+assert LOOPS_SPEC.itemsize == 40 and LOOPS_INFO.itemsize == 32
 VIEW_MAX_REACH, VIEW_MAX_POSES, VIEW_MAX_K, VIEW_LDS_WORDS = 4096, 4096, 64, 8704   # the limits of slamhip_hs_view_gain / _view_select; K15_LDS_WORDS
 VIEW_SUMMARY = np.dtype([(n, np.int32) for n in ("n_walked", "n_same", "n_ignored", "n_cut", "n_seen", "n_unknown", "n_free", "n_occupied", "n_new",
                                                  "n_new_unknown")])   # slamhip_view_summary: ten int32, 40 bytes
@@ -264,6 +271,7 @@ def _declare(L):
         "slamhip_debug_pg_relax_tri": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "slamhip_debug_pg_tri_apply": (i32, [vp, vp, i32, vp, vp, vp, i32, C.c_double, vp, vp]),
         "slamhip_debug_scans_match": (i32, [vp, vp, i32, vp, vp, i32, vp]),
+        "slamhip_debug_loops_consistent": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
         "slamhip_debug_render": (i32, [i32, vp, f, vp, vp, vp, f, f, vp, vp, vp, vp, i32, i32]),
         "slamhip_debug_render_clip": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),
         "slamhip_debug_sincos": (i32, [vp, i32, vp, vp]),
@@ -396,6 +404,8 @@ def _declare(L):
         "slamhip_hs_render": (i32, [vp, i32, i32, vp, i32]),
         "slamhip_hs_scans_match": (i32, [vp, vp, vp, i32, vp]),
         "slamhip_hs_scans_edges": (i32, [vp, vp, vp, i32, vp, vp, vp]),
+        "slamhip_hs_loops_consistent": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "slamhip_hs_loops_clear": (i32, [vp]),
         "slamhip_hs_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hs_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_hs_rollouts": (i32, [vp, vp, vp, i32, vp, C.c_float, vp, i32, vp, i32, i32, i32, vp, vp]),
@@ -1203,3 +1213,52 @@ def debug_scans_match(scans, spec, pairs):
     call("slamhip_debug_scans_match", _vp(xy), _vp(off), len(pts), spec.ctypes.data_as(C.c_void_p), pr.ctypes.data_as(C.c_void_p), pr.shape[0],
          out.ctypes.data_as(C.c_void_p))
     return out[:pr.shape[0]].copy()
+
+
+def loops_spec(gamma, q_t, q_theta, n_starts=8, min_clique=1, flags=0, reserved=0):
+    """A slamhip_loops_spec record (a (1,) LOOPS_SPEC array)."""
+    sp = np.zeros(1, LOOPS_SPEC)
+    sp["gamma"] = float(gamma); sp["q_t"] = float(q_t); sp["q_theta"] = float(q_theta); sp["n_starts"] = int(n_starts)
+    sp["min_clique"] = int(min_clique); sp["flags"] = int(flags); sp["reserved"] = int(reserved)
+    return sp
+
+
+def loops_words(L):
+    """Words of a row of the consistency matrix: ceil(L / 64)."""
+    return (int(L) + 63) // 64
+
+
+def loops_call(name, handle, poses, ij, z, w, spec, use=None, adj=False, d2=False):
+    """slamhip_hs_loops_consistent (handle: the hs) or slamhip_debug_loops_consistent (handle None; no device involved) ->
+    dict(keep (L,) bool, deg (L,) int32, info a LOOPS_INFO record, adj (L, ceil(L / 64)) uint64 or None[, d2 (L, L) float64: the hook's]).
+    adj=True sets SLAMHIP_LOOPS_ADJ in a copy of the spec."""
+    p = np.array(poses, np.float64).reshape(-1, 3)
+    e = np.array(ij, np.int32).reshape(-1, 2); zz = np.array(z, np.float64).reshape(-1, 3); ww = np.array(w, np.float64).reshape(-1, 3)
+    L = e.shape[0]
+    assert zz.shape[0] == L and ww.shape[0] == L
+    u = None if use is None else np.ascontiguousarray(np.asarray(use).astype(bool).astype(np.uint8))
+    assert u is None or u.shape == (L,)
+    sp = spec.copy()
+    if adj:
+        sp["flags"] |= LOOPS_ADJ
+    keep = np.zeros(max(L, 1), np.uint8); deg = np.zeros(max(L, 1), np.int32); info = np.zeros(1, LOOPS_INFO)
+    A = np.zeros((max(L, 1), max(loops_words(L), 1)), np.uint64) if adj else None
+    args = [_vp(p), p.shape[0], _vp(e), _vp(zz), _vp(ww), _vp(u), L, sp.ctypes.data_as(C.c_void_p), _vp(keep), _vp(deg),
+            info.ctypes.data_as(C.c_void_p), _vp(A)]
+    out = dict(adj=None)
+    if handle is None:
+        D = np.zeros((max(L, 1), max(L, 1)), np.float64) if d2 else None
+        call(name, *args, _vp(D))
+        if d2:
+            out["d2"] = D[:L, :L]
+    else:
+        call(name, handle, *args)
+    out.update(keep=keep[:L].astype(bool), deg=deg[:L].copy(), info=info[0].copy())
+    if adj:
+        out["adj"] = A[:L]
+    return out
+
+
+def debug_loops_consistent(poses, ij, z, w, spec, use=None, adj=True, d2=False):
+    """Rules 1 - 6 of slamhip_hs_loops_consistent on the host (slamhip_debug_loops_consistent; no device involved): loops_call's dict."""
+    return loops_call("slamhip_debug_loops_consistent", None, poses, ij, z, w, spec, use=use, adj=adj, d2=d2)

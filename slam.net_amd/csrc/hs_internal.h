@@ -53,6 +53,7 @@ struct hs_sig;                             // hs_sig.hip
 struct hs_pg;                              // hs_pg.hip
 struct hs_scans;                           // hs_scans.h
 struct hs_scanmatch;                       // hs_scanmatch.hip
+struct hs_loops;                           // hs_loops.hip
 template <typename T> struct hs_field_of;  // hs_dfield.h
 typedef hs_field_of<uint16_t> hs_field;
 struct slamhip_hs {
@@ -95,6 +96,7 @@ struct slamhip_hs {
     struct hs_scans *scn;                                  // slamhip_hs_scans_add / slamhip_hs_render: the store of keyframe scans -- the records on the host, the points in one device pool -- and the blocks of a render, made by the first call, kept
     struct hs_pg *pg;                                      // slamhip_hs_pg_set / _pg_relax / _pg_get / _pg_residuals: the pose graph's one device block and its pinned staging, made by the first set, kept
     struct hs_scanmatch *smt;                              // slamhip_hs_scans_match: the pairs' and the results' device blocks and their pinned staging, made by the first call, kept
+    struct hs_loops *lps;                                  // slamhip_hs_loops_consistent: the edges', the matrix's and the results' device block and its pinned staging, made by the first call, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -251,3 +253,5 @@ void    hs_scn_free(slamhip_hs *hs);        // the store of keyframe scans and t
 void    hs_scn_reset(slamhip_hs *hs);       // slamhip_hs_reset: the store is empty from here on; the pool and the blocks stay
 // hs_scanmatch.hip
 void    hs_smt_free(slamhip_hs *hs);        // the blocks of the scan-to-scan match (the caller has drained the stream)
+// hs_loops.hip
+void    hs_lp_free(slamhip_hs *hs);         // the blocks of the consistent set of loop edges (the caller has drained the stream)

@@ -768,6 +768,17 @@ class MapRepMultiMap:
         """The results of scans_match as pose-graph edges (slamhip_hs_scans_edges; host only) -> (z (n, 3), w (n, 3), valid (n,))."""
         return capi.scans_edges(spec, pairs, results)
 
+    def LoopsConsistent(self, poses, ij, z, w, spec, use=None, adj=False):
+        """The largest mutually consistent set of loop edges found (slamhip_hs_loops_consistent; no reference counterpart): poses
+        (N, 3) the keyframe chain in odometry order, ij (L, 2), z and w (L, 3) as PgSet takes them, spec a capi.loops_spec record, use
+        (L,) bools or None (all) -> dict(keep (L,) bool, deg (L,) int32, info a capi.LOOPS_INFO record, adj the consistency matrix as
+        (L, ceil(L / 64)) uint64 with adj=True, else None).  Reads and writes nothing of the map, the stores or the pose graph."""
+        return capi.loops_call("slamhip_hs_loops_consistent", self._h, poses, ij, z, w, spec, use=use, adj=adj)
+
+    def LoopsClear(self):
+        """Free the buffers of LoopsConsistent (slamhip_hs_loops_clear)."""
+        capi.call("slamhip_hs_loops_clear", self._h)
+
     def SigClear(self):
         """Free the blocks of the scan signatures and forget the spec (slamhip_hs_sig_clear)."""
         capi.call("slamhip_hs_sig_clear", self._h)
@@ -1274,11 +1285,19 @@ class HectorSLAMProcessor:
         rep.SigSetPoses(out.astype(np.float32))
         return out, iters, chi2
 
+    def ConsistentLoops(self, loops, spec):
+        """MapRep.LoopsConsistent over the keyframe store's poses as they stand: loops as RelaxKeyframes takes them, entries
+        (i, j, z, w); spec a capi.loops_spec record -> LoopsConsistent's dict.  keep says which entries to hand to RelaxKeyframes."""
+        _, kp = self.MapRep.SigDownload()
+        ij = np.array([(int(l[0]), int(l[1])) for l in loops], np.int32).reshape(-1, 2)
+        z = np.array([l[2] for l in loops], np.float64).reshape(-1, 3); w = np.array([l[3] for l in loops], np.float64).reshape(-1, 3)
+        return self.MapRep.LoopsConsistent(kp.astype(np.float64), ij, z, w, spec)
+
     def scans_match(self, spec, pairs):
         """MapRep.scans_match through the processor (slamhip_hsproc_scans_match): relative poses, no frame to convert."""
         return capi.scans_match_call("slamhip_hsproc_scans_match", self._h, spec, pairs)
 
-    def close_loops(self, min_gap, spec, accept, odom_w=(400.0, 400.0, 2500.0), pg=None, render=False, guess_from_poses=False, precond="jacobi"):
+    def close_loops(self, min_gap, spec, accept, odom_w=(400.0, 400.0, 2500.0), pg=None, render=False, guess_from_poses=False, precond="jacobi", consistency=None):
         """Close the loops of the keyframe store (host composition; AddKeyframe with keep_scan first): SelfLoopCandidates(min_gap) names
         one candidate per keyframe; its guess is (0, 0, -shift 2 pi / 64) by K18's sign rule -- or, with guess_from_poses, the
         translation between the two stored poses in the candidate's frame; scans_match turns the candidates into edges (keyframe
@@ -1286,7 +1305,9 @@ class HectorSLAMProcessor:
         them: the library sets no threshold.  RelaxKeyframes then adds the odometry edges of consecutive stored poses (weights odom_w),
         relaxes (pg: a capi.pg_spec record; default 5 steps of 4 N iterations; precond: RelaxKeyframes') and writes the poses back; render=True draws the
         stored scans again at them (RenderKeyframes).  -> dict(pairs, results, z, w, accepted (bool array), poses, iters, chi2);
-        without an accepted edge nothing is relaxed and poses is None."""
+        without an accepted edge nothing is relaxed and poses is None.  consistency: a capi.loops_spec record -- the accepted edges are
+        then cut down to their largest mutually consistent set (ConsistentLoops) before they are relaxed, and the dict gains
+        consistent (bool array over the pairs: accepted and kept) and loops_info (the capi.LOOPS_INFO record); None: no such step."""
         hits = self.SelfLoopCandidates(min_gap)
         _, kp = self.MapRep.SigDownload()
         pairs = []
@@ -1308,6 +1329,13 @@ class HectorSLAMProcessor:
         ok = np.array([bool(valid[n]) and bool(accept(res[n])) for n in range(len(pairs))], bool)
         out.update(results=res, z=z, w=w, accepted=ok)
         loops = [(pairs[n][0], pairs[n][1], z[n], w[n]) for n in range(len(pairs)) if ok[n]]
+        if consistency is not None:
+            out.update(consistent=np.zeros(len(pairs), bool), loops_info=None)
+            if loops:
+                cl = self.ConsistentLoops(loops, consistency)
+                out["consistent"][np.flatnonzero(ok)[cl["keep"]]] = True
+                out["loops_info"] = cl["info"]
+                loops = [l for l, k in zip(loops, cl["keep"]) if k]
         if not loops:
             return out
         N = kp.shape[0]
