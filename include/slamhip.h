@@ -748,6 +748,75 @@ int32_t slamhip_hs_world_lattice_search(slamhip_hs *hs, const slamhip_lattice_sp
 int32_t slamhip_hs_relocalise_world(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t B, float out_pose[3],
                                     slamhip_match_report *out_report, slamhip_world_reloc_info *out_info);
 
+/* The branch-and-bound pose-lattice search (K24; no reference counterpart): slamhip_hs_lattice_search's keys WITHOUT scoring every
+ * node, for lattices far beyond K7's 2^26 nodes.  K7's score is an integer sum of cell classes in {+1, 0, -1}, and a translation
+ * moves every point by whole cells; so the sum, over the points, of the HIGHEST class in the 2^h x 2^h window that starts at each
+ * point's cell bounds the score of every node of a 2^h x 2^h block of translations from above -- exactly, no tolerance, no floating
+ * point.  A search that prunes by that bound returns K7's keys bit for bit, the ties to the lowest flat included.
+ * Everything of slamhip_lattice_spec keeps its meaning to the letter: the point-cell arithmetic, ignored points, cls, score, flat,
+ * key, the node pose, the window frame, the world variant of cls.
+ *  1. Refusals -- SLAMHIP_ERR_INVALID, nothing launched and nothing written: anything slamhip_hs_lattice_search refuses EXCEPT the
+ *     2^26-node rule; top outside [0, 8]; world not 0 or 1; reserved != 0; max_blocks < 0 (0 means 2^26); with s = 2^top,
+ *     ceil((2 nx + 1) / s) * ceil((2 ny + 1) / s) * n_theta > max_blocks; for world = 1, R of more than 2^28 cells, as
+ *     slamhip_hs_world_lattice_search refuses it.  SLAMHIP_ERR_STATE without a scan.
+ *  2. Pooled maps.  For h in [0, top] and ALL integer (x, y): P_h(x, y) = max over 0 <= u, v < 2^h of cls(x + u, y + v), cls being 0
+ *     outside the map (outside R for the world search).  P_0 = cls.
+ *  3. Blocks.  A block is (k, a, b, h), a and b multiples of 2^h, 0 <= a <= 2 nx, 0 <= b <= 2 ny.  It stands for the nodes
+ *     ix = a - nx + u, iy = b - ny + v, 0 <= u, v < 2^h, that lie in the lattice.  U(block) = sum over heading k's non-ignored points
+ *     of P_h(gx + a - nx, gy + b - ny); E(block) = the same sum with P_0: the exact score of the block's ORIGIN node (u = v = 0),
+ *     which always lies in the lattice.  Both are int32.
+ *  4. The levels, for h = top down to 0.  F_top is every block of rule 3's grid for every heading.  For every block of F_h:
+ *     key[k] = max(key[k], key of (E, flat of the origin node)).  When ALL of F_h has been scored, best[k] = the score in key[k].  A
+ *     block SURVIVES iff h > 0 and U >= best[k] -- equality survives, because a tie may hold a lower flat; the comparison uses the
+ *     keys as they stand after the whole level, neither fresher nor staler ones, which makes the counts of rule 6 deterministic.
+ *     F_(h-1) is the up to four children (k, a + {0, 2^(h-1)}, b + {0, 2^(h-1)}, h - 1) of the survivors whose origin lies in the
+ *     lattice.  At h = 0, U = E: one evaluation serves.
+ *  5. Capacity.  If |F_(h-1)| > max_blocks the call ends with SLAMHIP_ERR_INVALID after the launches so far; the message gives
+ *     h - 1 and the count and says to raise max_blocks or top.  out_keys and out_info are not written.
+ *  6. Results.  out_keys: n_theta keys; by rule 2 they equal slamhip_lattice_spec's definition for ANY lattice.  out_info:
+ *     blocks[h] = |F_h|, kept[h] = the survivors of level h, entries above top 0, evaluated = the sum of blocks[h], n_levels = top + 1.
+ *  7. Blocking and memory.  The call blocks with the context's bounded wait, one wait per level (slamhip_hs_nav_field's batches are
+ *     the precedent for several waits in one call); results come back through pinned staging; a poisoned context returns
+ *     SLAMHIP_ERR_TIMEOUT.  The unit's blocks belong to the hs: made on first use, freed by slamhip_hs_destroy; an hs that never
+ *     calls this allocates nothing.
+ * Why the bound holds: a node (u, v) of the block reads cls(gx + a - nx + u, gy + b - ny + v) for each point, one of the cells P_h
+ * takes its maximum over; a sum of maxima bounds the sum.  A pruned block has U < best[k] <= the final key's score, so none of its
+ * nodes can hold the key; a block with U == best[k] may hold a node of equal score and lower flat and is kept -- on a map where all
+ * scores tie (an empty map) nothing is pruned, and the search costs top + 1 times the origin nodes on top of K7's work.
+ * Launches per call: K7's pack (window or world) into K7's class map; k24_pool once per height (height 0 copies the class map into
+ * the frame with its zero margin, height h doubles the window on the packed words: the maximum by value of the 2-bit codes is the OR
+ * of the low bits and the AND of the high bits, a lane per 16-cell word, no unpacking); per level k24_score (a lane per block, the
+ * heading's point cells in LDS chunk by chunk, P_h and P_0 gathered from global memory; a wave maximum, then one 64-bit maximum
+ * per workgroup on key[k] as in K7), then for h > 0 k24_filter (survivors and children per heading), the counts to the host -- the
+ * level's wait; the host forms the per-heading segments and the job table and checks rule 5 -- and k24_emit (the children into
+ * their heading's segment; the order inside a segment is free, no output depends on it). */
+typedef struct slamhip_bnb_spec {
+    slamhip_lattice_spec lattice;      /* offset 0: K7's lattice, every field as there */
+    int32_t top;                       /* offset 32: the top height, [0, 8]: top blocks are 2^top x 2^top translations */
+    int32_t world;                     /* offset 36: 0 the window (slamhip_hs_lattice_search), 1 the world (slamhip_hs_world_lattice_search) */
+    int32_t max_blocks;                /* offset 40: capacity of a level's frontier; 0 means 2^26 */
+    int32_t reserved;                  /* offset 44: 0 */
+} slamhip_bnb_spec;                    /* sizeof(slamhip_bnb_spec) == 48, no padding */
+typedef struct slamhip_bnb_info {
+    int32_t top;                       /* offset 0 */
+    int32_t n_levels;                  /* offset 4: top + 1 */
+    int64_t evaluated;                 /* offset 8: the sum of blocks[h] */
+    int32_t blocks[9];                 /* offset 16: |F_h| */
+    int32_t kept[9];                   /* offset 52: the survivors of level h */
+} slamhip_bnb_info;                    /* sizeof(slamhip_bnb_info) == 88, no padding */
+int32_t slamhip_hs_lattice_search_bnb(slamhip_hs *hs, const slamhip_bnb_spec *spec, uint64_t *out_keys, slamhip_bnb_info *out_info);
+/* slamhip_hs_relocalise (world = 0: out_info is a slamhip_reloc_info) or slamhip_hs_relocalise_world (world = 1: steps 1 - 5 with
+ * the same pre-checks; out_info is a slamhip_world_reloc_info), fed from the keys of slamhip_hs_lattice_search_bnb: the same host
+ * text runs behind both searches, so pose, report and info are those calls' bit for bit wherever K7 accepts the lattice.
+ * out_bnb: the search's info.  1 <= B <= 64. */
+int32_t slamhip_hs_relocalise_bnb(slamhip_hs *hs, const slamhip_bnb_spec *spec, int32_t B, float out_pose[3],
+                                  slamhip_match_report *out_report, void *out_info, slamhip_bnb_info *out_bnb);
+/* Test hook (no device involved): rules 1 - 6 over a plain array of w x h cell values (row-major, as slamhip_hs_cells_download gives
+ * them) of cell_length metres, the window case (world must be 0; lattice.level is not looked at), for the n points of xy.  It shares
+ * the pooling step and the block arithmetic (hs_bnb.h) with the kernels. */
+int32_t slamhip_debug_lattice_bnb(const float *values, int32_t w, int32_t h, float cell_length, const slamhip_bnb_spec *spec,
+                                  const float *xy, int32_t n, uint64_t *out_keys, slamhip_bnb_info *out_info);
+
 /* The beam trace (K8; no reference counterpart): what the map of ONE level holds ALONG every beam of the scan, from many poses
  * at once.  The matcher and the lattice search consult the map at beam end points only; this walks the grid update's own line
  * from the sensor cell to the beam's end cell and reads the class of every cell on it.  One operation, three uses: the check of
@@ -2127,6 +2196,12 @@ int32_t slamhip_hsproc_relocalise_world(slamhip_hsproc *p, const float *xy, int3
                                         const slamhip_lattice_spec *spec_world, int32_t B, int32_t adopt,
                                         float out_pose_world[3], slamhip_match_report *out_report,
                                         slamhip_world_reloc_info *out_info);
+/* slamhip_hsproc_relocalise (spec_world->world = 0: out_info is a slamhip_reloc_info) or slamhip_hsproc_relocalise_world (world = 1:
+ * a slamhip_world_reloc_info) with the branch-and-bound search (slamhip_hs_relocalise_bnb) in place of the exhaustive one: frame
+ * conversion, the re-basing of the stored poses and adopt exactly as in those two calls.  out_bnb: the search's info. */
+int32_t slamhip_hsproc_relocalise_bnb(slamhip_hsproc *p, const float *xy, int32_t n_points, const float scan_origin[2],
+                                      const slamhip_bnb_spec *spec_world, int32_t B, int32_t adopt, float out_pose_world[3],
+                                      slamhip_match_report *out_report, void *out_info, slamhip_bnb_info *out_bnb);
 /* The beam trace through the processor: slamhip_hs_set_scan on the processor's own hs, then slamhip_hs_trace at the B poses of
  * poses_world (B x 3, WORLD frame), each taken to the window's frame as slamhip_hsproc_relocalise takes its centre
  * (- (float)origin * cell0 per axis; the bits themselves while the origin is 0).  hx, hy stay in window-frame cells of the level:

@@ -105,6 +105,23 @@ WORLD_RELOC_INFO = np.dtype([(n, np.int32) for n, _ in WorldRelocInfo._fields_])
 assert C.sizeof(WorldRelocInfo) == WORLD_RELOC_INFO.itemsize == 40
 
 
+BNB_MAX_TOP = 8                                                # the limit of slamhip_bnb_spec.top
+
+
+class BNB_SPEC(C.Structure):
+    """slamhip_bnb_spec (include/slamhip.h): the lattice, then top, world, max_blocks, reserved; 48 bytes."""
+    _fields_ = [("lattice", LATTICE_SPEC), ("top", C.c_int32), ("world", C.c_int32), ("max_blocks", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BnbInfo(C.Structure):
+    """slamhip_bnb_info (include/slamhip.h): 88 bytes."""
+    _fields_ = [("top", C.c_int32), ("n_levels", C.c_int32), ("evaluated", C.c_int64), ("blocks", C.c_int32 * 9), ("kept", C.c_int32 * 9)]
+
+
+BNB_INFO = np.dtype([("top", np.int32), ("n_levels", np.int32), ("evaluated", np.int64), ("blocks", np.int32, (9,)), ("kept", np.int32, (9,))])
+assert C.sizeof(BNB_SPEC) == 48 and C.sizeof(BnbInfo) == BNB_INFO.itemsize == 88
+
+
 TRACE_MAX_DA = 32768
 TRACE_BEAM = np.dtype([("da", np.int32), ("first", np.int32), ("n_unknown", np.int32), ("end_class", np.int32), ("hx", np.int32),
                        ("hy", np.int32)])                  # slamhip_trace_beam (include/slamhip.h): 6 int32, 24 bytes
@@ -200,6 +217,16 @@ def lattice_spec(level, centre, nx, ny, n_theta, dtheta):
     return LATTICE_SPEC(int(level), int(nx), int(ny), int(n_theta), (C.c_float * 3)(*[float(v) for v in c]), float(np.float32(dtheta)))
 
 
+def bnb_spec(level, centre, nx, ny, n_theta, dtheta, top, world=False, max_blocks=0, reserved=0):
+    """A BNB_SPEC from Python values: lattice_spec's lattice, then the fields of the branch-and-bound search."""
+    return BNB_SPEC(lattice_spec(level, centre, nx, ny, n_theta, dtheta), int(top), int(world), int(max_blocks), int(reserved))
+
+
+def bnb_info(info):
+    """A BnbInfo as a BNB_INFO record."""
+    return np.frombuffer(bytes(info), BNB_INFO)[0].copy()
+
+
 class SlamhipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("slamhip error %d: %s" % (code, msg))
@@ -236,6 +263,7 @@ def _declare(L):
     rp = P(MatchReport)
     srp = P(SearchReport)
     lsp, rip, wrip = P(LATTICE_SPEC), P(RelocInfo), P(WorldRelocInfo)
+    bsp, bip = P(BNB_SPEC), P(BnbInfo)
     sig = {
         "slamhip_version": (C.c_char_p, []),
         "slamhip_last_error": (C.c_char_p, []),
@@ -252,6 +280,7 @@ def _declare(L):
         "slamhip_debug_backing_plan": (i32, [i32, i32, i32, i64, i64, i32, i32, i32, P(BackingJob), i32, ip]),
         "slamhip_debug_world_plan": (i32, [i32, i32, i64, i64, i64, i64, i32, i32, i32, P(WorldJob), i32, ip]),
         "slamhip_debug_lattice_cells": (i32, [f, fp, f, fp, i32, ip]),
+        "slamhip_debug_lattice_bnb": (i32, [fp, i32, i32, f, bsp, fp, i32, u64p, bip]),
         "slamhip_debug_world_pack_plan": (i32, [i32, i32, i64, i64, i32, P(i64), i32, P(i64), P(WorldJob), i32, ip]),
         "slamhip_debug_trace_lines": (i32, [f, fp, fp, fp, i32, ip]),
         "slamhip_debug_trace_cells": (i32, [i32, i32, i32, i32, ip, i32, ip]),
@@ -370,6 +399,8 @@ def _declare(L):
         "slamhip_hs_relocalise": (i32, [vp, lsp, i32, fp, rp, rip]),
         "slamhip_hs_world_lattice_search": (i32, [vp, lsp, u64p, ip]),
         "slamhip_hs_relocalise_world": (i32, [vp, lsp, i32, fp, rp, wrip]),
+        "slamhip_hs_lattice_search_bnb": (i32, [vp, bsp, u64p, bip]),
+        "slamhip_hs_relocalise_bnb": (i32, [vp, bsp, i32, fp, rp, vp, bip]),
         "slamhip_hs_trace": (i32, [vp, i32, fp, i32, i32, vp, vp]),
         "slamhip_hs_distance_field": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "slamhip_hs_distance_score": (i32, [vp, i32, i32, i32, i32, fp, i32, vp, vp]),
@@ -445,6 +476,7 @@ def _declare(L):
         "slamhip_hsproc_shift": (i32, [vp, i32, i32]),
         "slamhip_hsproc_relocalise": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, rip]),
         "slamhip_hsproc_relocalise_world": (i32, [vp, fp, i32, fp, lsp, i32, i32, fp, rp, wrip]),
+        "slamhip_hsproc_relocalise_bnb": (i32, [vp, fp, i32, fp, bsp, i32, i32, fp, rp, vp, bip]),
         "slamhip_hsproc_trace": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_distance_score": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
         "slamhip_hsproc_nearest_pairs": (i32, [vp, fp, i32, fp, fp, i32, i32, i32, i32, i32, vp, vp]),
@@ -552,6 +584,19 @@ def lattice_cells(cell_length, centre, theta, xy):
     out = np.empty((xy.shape[0], 2), np.int32)
     call("slamhip_debug_lattice_cells", C.c_float(cell_length), fptr(c), C.c_float(theta), fptr(xy), xy.shape[0], iptr(out))
     return out
+
+
+def bnb_call(values, w, h, cell_length, spec, xy):
+    """The branch-and-bound lattice search of the definition (slamhip_bnb_spec, rules 1 - 6) on the host (slamhip_debug_lattice_bnb; no
+    device involved): `values` the w x h cell values of one level, `spec` a BNB_SPEC (bnb_spec), `xy` the scan's points.
+    -> (keys (n_theta,) uint64, a BNB_INFO record).  A refused spec raises SlamhipError."""
+    v = f32(values, (-1,)); xy = f32(xy, (-1, 2))
+    assert v.size == int(w) * int(h)
+    keys = np.zeros(max(int(spec.lattice.n_theta), 1), np.uint64)
+    info = BnbInfo()
+    call("slamhip_debug_lattice_bnb", fptr(v), int(w), int(h), C.c_float(cell_length), C.byref(spec), fptr(xy), xy.shape[0],
+         keys.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(info))
+    return keys, bnb_info(info)
 
 
 def trace_lines(stm, pose, origin, xy):

@@ -131,6 +131,7 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
     hs_scn_free(hs);
     hs_smt_free(hs);
     hs_lp_free(hs);
+    hs_bnb_free(hs);
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
     if (hs->ev_pts) (void)hipEventDestroy(hs->ev_pts);

@@ -54,6 +54,7 @@ struct hs_pg;                              // hs_pg.hip
 struct hs_scans;                           // hs_scans.h
 struct hs_scanmatch;                       // hs_scanmatch.hip
 struct hs_loops;                           // hs_loops.hip
+struct hs_bnb;                             // hs_bnb.hip
 template <typename T> struct hs_field_of;  // hs_dfield.h
 typedef hs_field_of<uint16_t> hs_field;
 struct slamhip_hs {
@@ -97,6 +98,7 @@ struct slamhip_hs {
     struct hs_pg *pg;                                      // slamhip_hs_pg_set / _pg_relax / _pg_get / _pg_residuals: the pose graph's one device block and its pinned staging, made by the first set, kept
     struct hs_scanmatch *smt;                              // slamhip_hs_scans_match: the pairs' and the results' device blocks and their pinned staging, made by the first call, kept
     struct hs_loops *lps;                                  // slamhip_hs_loops_consistent: the edges', the matrix's and the results' device block and its pinned staging, made by the first call, kept
+    struct hs_bnb *bnb;                                    // slamhip_hs_lattice_search_bnb: the pooled maps, the frontiers and the results' blocks, made by the first call, kept
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -172,6 +174,14 @@ void    hs_lat_free(slamhip_hs *hs);        // the class map and the result bloc
 struct hs_class_map { const uint32_t *cls; int w, h, wpr, x0, y0; };
 int32_t hs_lat_pack_prepare(slamhip_hs *hs, int level, bool world, hs_class_map *M);
 int32_t hs_lat_pack_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M);
+// what K7 refuses for a spec alone; cap_nodes false: without the 2^26-node rule (K24)
+int32_t hs_lat_check_spec(const slamhip_hs *hs, const slamhip_lattice_spec *S, bool cap_nodes);
+// what follows the search in slamhip_hs_relocalise and in slamhip_hs_relocalise_world (its pre-checks: _world_check), from n_theta keys
+int32_t hs_lat_reloc_finish(slamhip_hs *hs, const slamhip_lattice_spec *spec, const uint64_t *keys, int32_t B, float out_pose[3],
+                            slamhip_match_report *out_report, slamhip_reloc_info *out_info);
+int32_t hs_lat_reloc_world_check(const slamhip_hs *hs);
+int32_t hs_lat_reloc_world_finish(slamhip_hs *hs, const slamhip_lattice_spec *spec, const uint64_t *keys, int32_t B, float out_pose[3],
+                                  slamhip_match_report *out_report, slamhip_world_reloc_info *out_info);
 // hs_trace.hip
 void    hs_trc_free(slamhip_hs *hs);        // the blocks of the beam trace (the caller has drained the stream)
 // what slamhip_hs_trace refuses for its arguments alone, for a scan of n_points (scan_is_set false: the caller is about to set one,
@@ -255,3 +265,5 @@ void    hs_scn_reset(slamhip_hs *hs);       // slamhip_hs_reset: the store is em
 void    hs_smt_free(slamhip_hs *hs);        // the blocks of the scan-to-scan match (the caller has drained the stream)
 // hs_loops.hip
 void    hs_lp_free(slamhip_hs *hs);         // the blocks of the consistent set of loop edges (the caller has drained the stream)
+// hs_bnb.hip
+void    hs_bnb_free(slamhip_hs *hs);        // the pooled maps, the frontiers and the results' blocks of the branch-and-bound search (the caller has drained the stream)

@@ -232,14 +232,14 @@ void hs_lat_free(slamhip_hs *hs)
     hs->lat = nullptr;
 }
 
-static int32_t hs_lat_check_spec(const slamhip_hs *hs, const slamhip_lattice_spec *S)
+int32_t hs_lat_check_spec(const slamhip_hs *hs, const slamhip_lattice_spec *S, bool cap_nodes)
 {
     SH_CHECK_ARG(hs && S);
     if (S->level < 0 || S->level >= hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "lattice: level %d of %d", S->level, hs->n_levels);
     if (S->nx < 0 || S->nx > HS_LAT_MAX_HALF || S->ny < 0 || S->ny > HS_LAT_MAX_HALF)
         SH_FAIL(SLAMHIP_ERR_INVALID, "lattice: nx = %d, ny = %d must lie in [0, %d]", S->nx, S->ny, HS_LAT_MAX_HALF);
     if (S->n_theta < 1 || S->n_theta > HS_LAT_MAX_THETA) SH_FAIL(SLAMHIP_ERR_INVALID, "lattice: n_theta = %d must lie in [1, %d]", S->n_theta, HS_LAT_MAX_THETA);
-    if ((int64_t)S->n_theta * (2 * S->nx + 1) * (2 * S->ny + 1) > (int64_t)HS_LAT_MAX_NODES)
+    if (cap_nodes && (int64_t)S->n_theta * (2 * S->nx + 1) * (2 * S->ny + 1) > (int64_t)HS_LAT_MAX_NODES)
         SH_FAIL(SLAMHIP_ERR_INVALID, "lattice: %lld nodes, more than 2^26", (long long)S->n_theta * (2 * S->nx + 1) * (2 * S->ny + 1));
     if (!(isfinite(S->centre[0]) && isfinite(S->centre[1]) && isfinite(S->centre[2]) && isfinite(S->dtheta)))
         SH_FAIL(SLAMHIP_ERR_INVALID, "lattice: centre and dtheta must be finite");
@@ -322,7 +322,7 @@ int32_t hs_lat_pack_enqueue(slamhip_hs *hs, int level, bool world, const hs_clas
 // next search of this hs.  world: the class map covers the window and the level's tiles (k7_pack_world) instead of the window.
 static int32_t hs_lat_run(slamhip_hs *hs, const slamhip_lattice_spec *S, bool want_scores, bool world, const uint64_t **keys, const int32_t **scores)
 {
-    SH_TRY(hs_lat_check_spec(hs, S));
+    SH_TRY(hs_lat_check_spec(hs, S, true));
     if (hs->n_points <= 0) SH_FAIL(SLAMHIP_ERR_STATE, "lattice: no scan (slamhip_hs_set_scan first)");
     slamhip_ctx *ctx = hs->ctx;
     SH_TRY(hs_call_begin(hs));
@@ -384,7 +384,7 @@ extern "C" int32_t slamhip_hs_world_lattice_search(slamhip_hs *hs, const slamhip
 extern "C" int32_t slamhip_hs_lattice_node_pose(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t k, int32_t flat, float out_pose[3])
 {
     SH_CHECK_ARG(out_pose);
-    SH_TRY(hs_lat_check_spec(hs, spec));
+    SH_TRY(hs_lat_check_spec(hs, spec, true));
     const int NX = 2 * spec->nx + 1, NY = 2 * spec->ny + 1;
     SH_CHECK_ARG(k >= 0 && k < spec->n_theta && flat >= 0 && flat < NX * NY);
     const hs_level &L = hs->lv[spec->level];
@@ -410,12 +410,11 @@ static int hs_lat_hints(const slamhip_hs *hs, const slamhip_lattice_spec *spec, 
     return nh;
 }
 
-extern "C" int32_t slamhip_hs_relocalise(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t B, float out_pose[3],
-                                         slamhip_match_report *out_report, slamhip_reloc_info *out_info)
+// What follows the search in slamhip_hs_relocalise: sort, hints, slamhip_hs_match_best (K24's slamhip_hs_relocalise_bnb runs the same
+// text on its own keys)
+int32_t hs_lat_reloc_finish(slamhip_hs *hs, const slamhip_lattice_spec *spec, const uint64_t *keys, int32_t B, float out_pose[3],
+                            slamhip_match_report *out_report, slamhip_reloc_info *out_info)
 {
-    SH_CHECK_ARG(hs && spec && out_pose && out_report && out_info && B >= 1 && B <= 64);
-    const uint64_t *keys = nullptr;
-    SH_TRY(hs_lat_run(hs, spec, false, false, &keys, nullptr));
     float hints[3 * 64];
     int node[64][4];
     const int nh = hs_lat_hints(hs, spec, keys, B, hints, node);
@@ -429,19 +428,31 @@ extern "C" int32_t slamhip_hs_relocalise(slamhip_hs *hs, const slamhip_lattice_s
     return SLAMHIP_OK;
 }
 
-// Relocalise anywhere in the world: the world search, the window brought to the best node (slamhip_hs_shift: the backing store
-// restores what lies there), the hints re-based into the new frame, and the match_best path over those that lie in the new window.
-// All in binary32, one rounding per operation.
-extern "C" int32_t slamhip_hs_relocalise_world(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t B, float out_pose[3],
-                                               slamhip_match_report *out_report, slamhip_world_reloc_info *out_info)
+extern "C" int32_t slamhip_hs_relocalise(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t B, float out_pose[3],
+                                         slamhip_match_report *out_report, slamhip_reloc_info *out_info)
 {
     SH_CHECK_ARG(hs && spec && out_pose && out_report && out_info && B >= 1 && B <= 64);
+    const uint64_t *keys = nullptr;
+    SH_TRY(hs_lat_run(hs, spec, false, false, &keys, nullptr));
+    return hs_lat_reloc_finish(hs, spec, keys, B, out_pose, out_report, out_info);
+}
+
+// what slamhip_hs_relocalise_world refuses before anything is launched or moved, beyond the search's own refusals
+int32_t hs_lat_reloc_world_check(const slamhip_hs *hs)
+{
     if (!hs->bk) SH_FAIL(SLAMHIP_ERR_STATE, "slamhip_hs_relocalise_world: backing is off (slamhip_hs_set_backing) -- moving the window would destroy the map");
     if (hs->ref_cache)
         SH_FAIL(SLAMHIP_ERR_INVALID, "slamhip_hs_relocalise_world: the reference's cache is on (slamhip_hs_set_reference_cache) -- slamhip_hs_shift "
                 "refuses; turn it off first");
-    const uint64_t *keys = nullptr;
-    SH_TRY(hs_lat_run(hs, spec, false, true, &keys, nullptr));
+    return SLAMHIP_OK;
+}
+
+// Relocalise anywhere in the world, behind the world search: the window brought to the best node (slamhip_hs_shift: the backing
+// store restores what lies there), the hints re-based into the new frame, and the match_best path over those that lie in the new
+// window.  All in binary32, one rounding per operation.
+int32_t hs_lat_reloc_world_finish(slamhip_hs *hs, const slamhip_lattice_spec *spec, const uint64_t *keys, int32_t B, float out_pose[3],
+                                  slamhip_match_report *out_report, slamhip_world_reloc_info *out_info)
+{
     float hints[3 * 64];
     int node[64][4];
     const int nh = hs_lat_hints(hs, spec, keys, B, hints, node);
@@ -477,6 +488,16 @@ extern "C" int32_t slamhip_hs_relocalise_world(slamhip_hs *hs, const slamhip_lat
     out_info->top_score = node[0][3];
     out_info->n_far = nh - n_kept;
     return SLAMHIP_OK;
+}
+
+extern "C" int32_t slamhip_hs_relocalise_world(slamhip_hs *hs, const slamhip_lattice_spec *spec, int32_t B, float out_pose[3],
+                                               slamhip_match_report *out_report, slamhip_world_reloc_info *out_info)
+{
+    SH_CHECK_ARG(hs && spec && out_pose && out_report && out_info && B >= 1 && B <= 64);
+    SH_TRY(hs_lat_reloc_world_check(hs));
+    const uint64_t *keys = nullptr;
+    SH_TRY(hs_lat_run(hs, spec, false, true, &keys, nullptr));
+    return hs_lat_reloc_world_finish(hs, spec, keys, B, out_pose, out_report, out_info);
 }
 
 // CPU-side test hook: hs_lat_point_cell, the text the kernel runs

@@ -290,6 +290,32 @@ extern "C" int32_t slamhip_hsproc_relocalise_world(slamhip_hsproc *p, const floa
     return SLAMHIP_OK;
 }
 
+// The two calls above with the branch-and-bound search (K24) in place of the exhaustive one: world = 0 follows the first, world = 1 the second.
+extern "C" int32_t slamhip_hsproc_relocalise_bnb(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const slamhip_bnb_spec *spec_world,
+                                                 int32_t B, int32_t adopt, float out_pose_world[3], slamhip_match_report *out_report, void *out_info,
+                                                 slamhip_bnb_info *out_bnb)
+{
+    SH_CHECK_ARG(p && spec_world && out_pose_world && out_report && out_info && out_bnb && (adopt == 0 || adopt == 1));
+    SH_CHECK_ARG(spec_world->world == 0 || spec_world->world == 1);
+    SH_TRY(slamhip_hs_set_scan(p->hs, xy, n, origin));
+    slamhip_bnb_spec S = *spec_world;
+    hsproc_pose_to_window(p, spec_world->lattice.centre, S.lattice.centre);
+    float m[3];
+    if (S.world) {
+        slamhip_world_reloc_info *info = (slamhip_world_reloc_info *)out_info;
+        memset(info, 0, sizeof(*info));
+        const int32_t rc = slamhip_hs_relocalise_bnb(p->hs, &S, B, m, out_report, info, out_bnb);
+        hsproc_rebase(p, info->dx, info->dy);                              // (the stored poses follow the window, also if the match behind the shift failed)
+        SH_TRY(rc);
+    } else SH_TRY(slamhip_hs_relocalise_bnb(p->hs, &S, B, m, out_report, out_info, out_bnb));
+    if (adopt) {
+        memcpy(p->match_pose, m, sizeof(m));
+        memcpy(p->last_update_pose, m, sizeof(m));
+    }
+    hsproc_pose_to_world(p, m, out_pose_world);
+    return SLAMHIP_OK;
+}
+
 // The beam trace at world poses: the scan set, every pose taken to the window's frame as slamhip_hsproc_relocalise takes its centre.
 // Nothing of the processor's own state is read or written beyond the window's origin.
 extern "C" int32_t slamhip_hsproc_trace(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float *poses_world, int32_t B,

@@ -42,6 +42,15 @@ def _reloc_info(info):
     return np.array([tuple(getattr(info, n) for n, _ in capi.RelocInfo._fields_)], capi.RELOC_INFO)[0]
 
 
+BNB_DEFAULT_TOP = 3                                            # what top=None means: the fastest of 3 .. 6 at K7's own configuration (profiles/r30_hs_bnb.json)
+
+
+def _search_kind(search):
+    if search not in ("lattice", "bnb"):
+        raise ValueError('search must be "lattice" or "bnb", not %r' % (search,))
+    return search == "bnb"
+
+
 def _world_reloc_info(info):
     return np.array([tuple(getattr(info, n) for n, _ in capi.WorldRelocInfo._fields_)], capi.WORLD_RELOC_INFO)[0]
 
@@ -343,6 +352,21 @@ class MapRepMultiMap:
         capi.call("slamhip_hs_world_lattice_search", self._h, C.byref(spec), keys.ctypes.data_as(C.POINTER(C.c_uint64)),
                   capi.iptr(vol) if scores else None)
         return keys, vol
+
+    def lattice_search_bnb(self, scan, level, centre, nx, ny, n_theta, dtheta, top, world=False, max_blocks=0):
+        """lattice_search's (world=True: world_lattice_search's) keys by branch and bound (slamhip_hs_lattice_search_bnb): blocks of
+        2^top x 2^top translations are bounded from above through pooled maxima of the class map and only those that can still hold
+        a heading's best node are split, so the lattice may have far more than lattice_search's 2^26 nodes; the keys are the
+        exhaustive search's bit for bit.  max_blocks: the capacity of a level's frontier (0: 2^26).  -> (keys, info): keys
+        (n_theta,) uint64, info a capi.BNB_INFO record (blocks and survivors per height, blocks evaluated).  There is no score
+        volume.  Blocking, one wait per height.  scan = None: the scan already set."""
+        if scan is not None:
+            self.set_scan(scan)
+        spec = capi.bnb_spec(level, centre, nx, ny, n_theta, dtheta, top, world, max_blocks)
+        keys = np.zeros(int(n_theta), np.uint64)
+        info = capi.BnbInfo()
+        capi.call("slamhip_hs_lattice_search_bnb", self._h, C.byref(spec), keys.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(info))
+        return keys, capi.bnb_info(info)
 
     def lattice_node_pose(self, level, centre, nx, ny, n_theta, dtheta, k, flat):
         """The pose of node (k, flat) of that lattice, in the window's frame (slamhip_hs_lattice_node_pose; host code)."""
@@ -878,25 +902,41 @@ class ScanMatcher:
         capi.call("slamhip_hs_match_best", rep._h, capi.fptr(hints), hints.shape[0], capi.fptr(out), C.byref(idx), capi.rptr(r))
         return out, int(idx.value), r[0]
 
-    def Relocalise(self, rep, scan, level, centre, nx, ny, n_theta, dtheta, B=16):
+    def Relocalise(self, rep, scan, level, centre, nx, ny, n_theta, dtheta, B=16, search="lattice", top=None):
         """Lattice search, then the best of the min(B, n_theta) highest-scoring headings' nodes refined by MatchDataBest
-        (slamhip_hs_relocalise): -> (pose, report, info), info a capi.RELOC_INFO record.  Poses in the window's frame."""
+        (slamhip_hs_relocalise): -> (pose, report, info), info a capi.RELOC_INFO record.  Poses in the window's frame.
+        search="bnb": the branch-and-bound search (slamhip_hs_relocalise_bnb; top=None: 3, measured) in place of the exhaustive
+        one -- the same pose, report and info, for lattices of any size -- and -> (pose, report, info, bnb), bnb a capi.BNB_INFO
+        record."""
+        bnb = _search_kind(search)
         spec = capi.lattice_spec(level, centre, nx, ny, n_theta, dtheta)
         out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); info = capi.RelocInfo()
         self._order(rep)
         rep.set_scan(scan)
+        if bnb:
+            bspec = capi.bnb_spec(level, centre, nx, ny, n_theta, dtheta, BNB_DEFAULT_TOP if top is None else top, False)
+            binfo = capi.BnbInfo()
+            capi.call("slamhip_hs_relocalise_bnb", rep._h, C.byref(bspec), int(B), capi.fptr(out), capi.rptr(r), C.byref(info), C.byref(binfo))
+            return out, r[0], _reloc_info(info), capi.bnb_info(binfo)
         capi.call("slamhip_hs_relocalise", rep._h, C.byref(spec), int(B), capi.fptr(out), capi.rptr(r), C.byref(info))
         return out, r[0], _reloc_info(info)
 
-    def RelocaliseWorld(self, rep, scan, level, centre, nx, ny, n_theta, dtheta, B=16):
+    def RelocaliseWorld(self, rep, scan, level, centre, nx, ny, n_theta, dtheta, B=16, search="lattice", top=None):
         """Relocalise anywhere in the world behind the window (slamhip_hs_relocalise_world; backing must be on): the world
         lattice search, the window shifted to the best node -- the backing store restores what lies there -- and the best
         headings' nodes that lie in the new window refined by MatchDataBest.  -> (pose, report, info): the pose in the NEW
-        window's frame, info a capi.WORLD_RELOC_INFO record whose dx, dy say how the window moved."""
+        window's frame, info a capi.WORLD_RELOC_INFO record whose dx, dy say how the window moved.  search="bnb", top: as in
+        Relocalise; -> (pose, report, info, bnb)."""
+        bnb = _search_kind(search)
         spec = capi.lattice_spec(level, centre, nx, ny, n_theta, dtheta)
         out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); info = capi.WorldRelocInfo()
         self._order(rep)
         rep.set_scan(scan)
+        if bnb:
+            bspec = capi.bnb_spec(level, centre, nx, ny, n_theta, dtheta, BNB_DEFAULT_TOP if top is None else top, True)
+            binfo = capi.BnbInfo()
+            capi.call("slamhip_hs_relocalise_bnb", rep._h, C.byref(bspec), int(B), capi.fptr(out), capi.rptr(r), C.byref(info), C.byref(binfo))
+            return out, r[0], _world_reloc_info(info), capi.bnb_info(binfo)
         capi.call("slamhip_hs_relocalise_world", rep._h, C.byref(spec), int(B), capi.fptr(out), capi.rptr(r), C.byref(info))
         return out, r[0], _world_reloc_info(info)
 
@@ -978,11 +1018,25 @@ class HectorSLAMProcessor:
         world poses: create the processor with startPose = the saved pose, LoadWorld, Update.  -> the cells dropped."""
         return self.MapRep.load_world(path, _shift=self.shift)
 
-    def Relocalise(self, scan, centreWorld, level, nx, ny, n_theta, dtheta, B=16, adopt=True):
+    def _relocalise_bnb(self, scan, centreWorld, level, nx, ny, n_theta, dtheta, B, adopt, top, world):
+        spec = capi.bnb_spec(level, centreWorld, nx, ny, n_theta, dtheta, BNB_DEFAULT_TOP if top is None else top, world)
+        org = capi.f32(scan.Pose[:2])
+        out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); binfo = capi.BnbInfo()
+        info = capi.WorldRelocInfo() if world else capi.RelocInfo()
+        capi.call("slamhip_hsproc_relocalise_bnb", self._h, capi.fptr(scan.Points), scan.Points.shape[0], capi.fptr(org), C.byref(spec),
+                  int(B), 1 if adopt else 0, capi.fptr(out), capi.rptr(r), C.byref(info), C.byref(binfo))
+        self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
+        return out, r[0], (_world_reloc_info if world else _reloc_info)(info), capi.bnb_info(binfo)
+
+    def Relocalise(self, scan, centreWorld, level, nx, ny, n_theta, dtheta, B=16, adopt=True, search="lattice", top=None):
         """Find the robot in the map the window holds (slamhip_hsproc_relocalise): lattice search around centreWorld (a world
         pose) on `level`, the best nodes refined by the matcher.  -> (poseWorld, report, info).  adopt=True: the pose becomes
         MatchPose and LastMapUpdatePose, so the next Update matches from it and writes the map only once the robot has moved;
-        adopt=False: the processor is untouched.  The resume flow: LoadWorld, Relocalise, Update."""
+        adopt=False: the processor is untouched.  The resume flow: LoadWorld, Relocalise, Update.  search="bnb": the
+        branch-and-bound search (slamhip_hsproc_relocalise_bnb; top=None: 3, measured), for lattices of any size;
+        -> (poseWorld, report, info, bnb), bnb a capi.BNB_INFO record."""
+        if _search_kind(search):
+            return self._relocalise_bnb(scan, centreWorld, level, nx, ny, n_theta, dtheta, B, adopt, top, False)
         spec = capi.lattice_spec(level, centreWorld, nx, ny, n_theta, dtheta)
         org = capi.f32(scan.Pose[:2])
         out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); info = capi.RelocInfo()
@@ -991,12 +1045,19 @@ class HectorSLAMProcessor:
         self.MapRep._scan_set = (scan.Points.shape[0], org.copy())
         return out, r[0], _reloc_info(info)
 
+    def RelocaliseWorldBnb(self, scan, centreWorld, level, nx, ny, n_theta, dtheta, B=16, adopt=True, top=None):
+        """RelocaliseWorld with the branch-and-bound search (slamhip_hsproc_relocalise_bnb, world = 1; top=None: 3, measured) in place
+        of the exhaustive one, for lattices of any size: -> (poseWorld, report, info, bnb), the first three RelocaliseWorld's bit for
+        bit wherever that call accepts the lattice, bnb a capi.BNB_INFO record.  (A method of its own: RelocaliseWorld's parameter
+        list is pinned.)"""
+        return self._relocalise_bnb(scan, centreWorld, level, nx, ny, n_theta, dtheta, B, adopt, top, True)
+
     def RelocaliseWorld(self, scan, centreWorld, level, nx, ny, n_theta, dtheta, B=16, adopt=True):
         """Find the robot anywhere in the saved world (slamhip_hsproc_relocalise_world; backing must be on): as Relocalise, but
         the lattice is scored against the window AND the tiles behind it, and the window then moves to the best node.
         -> (poseWorld, report, info), info a capi.WORLD_RELOC_INFO record (dx, dy: the shift).  MatchPose and LastMapUpdatePose
         stay the world poses they were (adopt=False) or become the result (adopt=True).  The resume flow: LoadWorld,
-        RelocaliseWorld, Update."""
+        RelocaliseWorld, Update.  RelocaliseWorldBnb: the same by branch and bound."""
         spec = capi.lattice_spec(level, centreWorld, nx, ny, n_theta, dtheta)
         org = capi.f32(scan.Pose[:2])
         out = np.empty(3, np.float32); r = np.zeros(1, capi.REPORT_DTYPE); info = capi.WorldRelocInfo()
@@ -1258,10 +1319,11 @@ class HectorSLAMProcessor:
         """MapRep.SigSelf through the processor (slamhip_hsproc_sig_self)."""
         return capi.sig_self_call("slamhip_hsproc_sig_self", self._h, first, self.MapRep.SigCount() if last is None else last, min_gap)
 
-    def VerifyLoop(self, scan, hit, level, nx, ny, n_theta, dtheta, B=16):
+    def VerifyLoop(self, scan, hit, level, nx, ny, n_theta, dtheta, B=16, search="lattice", top=None):
         """Check one loop candidate (an entry of LoopCandidates) against the map: Relocalise centred on the candidate's pose guess,
-        adopt=False.  -> (poseWorld, report, info) as Relocalise.  Host composition only; the caller judges the report."""
-        return self.Relocalise(scan, hit["pose"], level, nx, ny, n_theta, dtheta, B=B, adopt=False)
+        adopt=False.  -> (poseWorld, report, info) as Relocalise (search="bnb": with the bnb record behind them).  Host composition
+        only; the caller judges the report."""
+        return self.Relocalise(scan, hit["pose"], level, nx, ny, n_theta, dtheta, B=B, adopt=False, search=search, top=top)
 
     def RelaxKeyframes(self, loops, odom_w, spec, fixed=None, precond="jacobi"):
         """Spread verified loops over the keyframe store's poses (host composition of slamhip_hs_pg_set, _pg_relax, _pg_get,
