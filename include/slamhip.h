@@ -1871,6 +1871,50 @@ int32_t slamhip_debug_render(int32_t n_levels, const int32_t *dims, float cell_l
 int32_t slamhip_debug_render_clip(int32_t da, int32_t db, int32_t T, int32_t n, const int32_t *a0, const int32_t *b0, int32_t *out_i0,
                                   int32_t *out_i1);
 
+/* The stored scans drawn into the WHOLE world behind the scrolling window (K25; no reference counterpart).  slamhip_hs_render draws
+ * into the window only: a line whose begin or end cell lies outside the window's w x h is dropped, and without SLAMHIP_RENDER_KEEP the
+ * backing directory goes.  For a robot whose map is larger than its window -- what slamhip_hs_set_backing and the world calls exist
+ * for -- that loses the map outside the window when a loop is closed.  This call draws the same scans into the window AND the tiles.
+ * THE DEFINITION.  The world of level l is an unbounded grid of cells in the window's frame at the time of the call: window cell
+ * (x, y) is world cell ((ox >> l) + x, (oy >> l) + y), as in slamhip_hs_set_backing.  poses: 3 * (last - first) floats in the window's
+ * frame, as slamhip_hs_render takes them.  Afterwards every world cell's update_index, the bits of its value and its probability, and
+ * every level's curr_update_index and curr_cache_index, equal bit for bit what slamhip_hs_render would leave in a single pyramid
+ * large enough to hold every line: the window's clipping disappears, nothing else about the arithmetic changes.
+ *  1. Matrices: slamhip_hs_render's rule 4.  Lines: the arithmetic of slamhip_hs_render's lines (rintf, which is right for negative
+ *     coordinates too), the inside test against w, h replaced by the WORLD BOUND: begin and end cells within +-2^20 cells of window
+ *     cell (0, 0) on each axis.  For scans first .. last - 1 in order every world cell takes the two transitions with K20's marks; the
+ *     indices advance as in slamhip_hs_render's rule 2 (a scan of 0 points: + 3 and + 1).
+ *  2. Where the cells live.  A world cell inside the window is read from and written to the window's arrays (the window wins, as in
+ *     the world download and upload); a cell outside it is read from and written to its tile's slot, cells followed by probabilities.
+ *     The part of a tile under the window is neither read nor written.
+ *  3. Without SLAMHIP_RENDER_KEEP: the window is cleared as in slamhip_hs_render's rule 1 and the directory is dropped; the world is
+ *     then drawn into the window and into freshly taken tiles.  With it: the start state is the window plus the existing tiles; a
+ *     tile that does not exist starts as Reset cells.  first == last: without KEEP the clear alone, with KEEP nothing.
+ *  4. Slots.  A first device pass gives, per (scan, level), the box of the begin cell and the valid end cells and the largest line;
+ *     the host reads the boxes back BEFORE anything is changed.  A slot is taken for every tile not wholly under the window that a
+ *     box meets on its level and that does not exist yet, in the order (level, ty, tx) ascending: the outcome is deterministic.  A
+ *     tile that ends all-Reset KEEPS its slot -- slamhip_hs_backing_stats.tiles counts it (the boxes bound the lines, they are not the
+ *     lines).  evicted_cells, restored_cells and dropped_cells do not move.
+ *  5. SLAMHIP_ERR_INVALID with nothing changed: slamhip_hs_render's rule 7 list; backing off (slamhip_hs_render is the call for a
+ *     window alone); a begin or end cell beyond the world bound -- the begin cell of a scan of 0 points is not asked, a point that
+ *     is not finite ends beyond it; a valid line of more than 32767 cells on any level (the integer clip of a line to a block is
+ *     proven in 32 bits up to there).
+ *  6. SLAMHIP_ERR_NOMEM with nothing changed, the directory, the pool and the stats included: the tiles to take do not fit max_bytes,
+ *     or a chunk's allocation fails.  Unlike slamhip_hs_shift, which never fails for capacity and drops cells: a silently partial
+ *     world after a loop closure is worse than a refusal.  Everything is planned and allocated before the directory is dropped.
+ *  7. Blocking, on the operator's stream, the context's bounded wait, no timing class; chunks as slamhip_hs_render's rule 6
+ *     (SLAMHIP_K20_CHUNK), the wait per chunk and once more per chunk for the boxes' pass.  An error behind the plan leaves what
+ *     slamhip_hs_render's rule 7 says of a failed chunk.
+ * The hook (no device involved): the definition over the caller's arrays.  rects: per level (x0, y0, w, h) in window-frame cells,
+ * w * h <= 2^26; cells: the rectangles' cells one level behind the other, IN and OUT; the other arguments as slamhip_debug_render.  It
+ * walks every line step by step as slamhip_debug_render does, under the world bound, and refuses (SLAMHIP_ERR_INVALID, the arrays
+ * untouched) what rule 5 refuses and a scan whose box leaves its level's rectangle.  With x0 = y0 = 0 and every line inside the
+ * rectangle it equals slamhip_debug_render bit for bit. */
+int32_t slamhip_hs_render_world(slamhip_hs *hs, int32_t first, int32_t last, const float *poses, int32_t flags);
+int32_t slamhip_debug_render_world(int32_t n_levels, const int32_t *rects, float cell_length, slamhip_cell *cells, int32_t *update_index,
+                                   int32_t *cache_index, float free_factor, float occ_factor, const float *xy, const int32_t *offsets,
+                                   const float *origins, const float *poses, int32_t N, int32_t flags);
+
 /* Stored scans matched pairwise (K21; no reference counterpart).  K18 names loop CANDIDATES between keyframes, K19 spreads a loop's
  * error over the keyframe poses and asks per edge for a measurement z -- node j seen in node i's frame -- and a weight w; K20 keeps
  * the keyframes' scans in a device pool.  This unit matches scan against scan for a whole list of (reference, query) pairs of that
@@ -2305,6 +2349,9 @@ int32_t slamhip_hsproc_sig_self(slamhip_hsproc *p, int32_t first, int32_t last, 
  * alone.  Errors as the slamhip_hs_* calls. */
 int32_t slamhip_hsproc_scans_add(slamhip_hsproc *p, int32_t *out_index);
 int32_t slamhip_hsproc_render(slamhip_hsproc *p, int32_t first, int32_t last, const float *poses_world, int32_t flags);
+/* slamhip_hs_render_world at WORLD poses, taken to the window's frame exactly as slamhip_hsproc_render takes them.  MatchPose,
+ * LastMapUpdatePose and the update gate are left alone. */
+int32_t slamhip_hsproc_render_world(slamhip_hsproc *p, int32_t first, int32_t last, const float *poses_world, int32_t flags);
 /* The scan-to-scan match through the processor: slamhip_hs_scans_match on the processor's own hs, the arguments as given -- a guess
  * and a result are RELATIVE poses and need no frame conversion.  The processor's stored poses, its update gate, its match report and
  * the scan that was set are not touched. */

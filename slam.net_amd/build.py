@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libslamhip.so")
 SOURCES = ["context.hip", "distance.hip", "holemap.hip", "obstacle.hip", "coreslam.hip", "processor.hip",
-           "hector.hip", "hs_match.hip", "hs_update.hip", "hs_window.hip", "hs_world.hip", "hs_lattice.hip", "hs_trace.hip", "hs_dfield.hip", "hs_frontier.hip", "hs_nav.hip", "hs_rollout.hip", "hs_mcl.hip", "hs_merge.hip", "hs_view.hip", "hs_nearest.hip", "hs_hough.hip", "hs_sig.hip", "hs_pg.hip", "hs_render.hip", "hs_scanmatch.hip", "hs_loops.hip", "hs_bnb.hip", "hs_processor.hip",
+           "hector.hip", "hs_match.hip", "hs_update.hip", "hs_window.hip", "hs_world.hip", "hs_lattice.hip", "hs_trace.hip", "hs_dfield.hip", "hs_frontier.hip", "hs_nav.hip", "hs_rollout.hip", "hs_mcl.hip", "hs_merge.hip", "hs_view.hip", "hs_nearest.hip", "hs_hough.hip", "hs_sig.hip", "hs_pg.hip", "hs_render.hip", "hs_render_world.hip", "hs_scanmatch.hip", "hs_loops.hip", "hs_bnb.hip", "hs_processor.hip",
            "group.hip"]
 # every source depends on every header: whatever else lies in csrc/, and the public header
 HEADERS = sorted(f for f in os.listdir(CSRC) if not f.endswith(".hip")) + [os.path.join("..", "..", "include", "slamhip.h")]

@@ -303,6 +303,7 @@ def _declare(L):
         "slamhip_debug_loops_consistent": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
         "slamhip_debug_render": (i32, [i32, vp, f, vp, vp, vp, f, f, vp, vp, vp, vp, i32, i32]),
         "slamhip_debug_render_clip": (i32, [i32, i32, i32, i32, vp, vp, vp, vp]),
+        "slamhip_debug_render_world": (i32, [i32, vp, f, vp, vp, vp, f, f, vp, vp, vp, vp, i32, i32]),
         "slamhip_debug_sincos": (i32, [vp, i32, vp, vp]),
         "slamhip_debug_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "slamhip_debug_nav_field": (i32, [vp, i32, i32, i32, i32, C.c_uint32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -433,6 +434,7 @@ def _declare(L):
         "slamhip_hs_scans_download": (i32, [vp, i32, vp, i32]),
         "slamhip_hs_scans_clear": (i32, [vp]),
         "slamhip_hs_render": (i32, [vp, i32, i32, vp, i32]),
+        "slamhip_hs_render_world": (i32, [vp, i32, i32, vp, i32]),
         "slamhip_hs_scans_match": (i32, [vp, vp, vp, i32, vp]),
         "slamhip_hs_scans_edges": (i32, [vp, vp, vp, i32, vp, vp, vp]),
         "slamhip_hs_loops_consistent": (i32, [vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
@@ -488,6 +490,7 @@ def _declare(L):
         "slamhip_hsproc_sig_self": (i32, [vp, i32, i32, i32, vp]),
         "slamhip_hsproc_scans_add": (i32, [vp, ip]),
         "slamhip_hsproc_render": (i32, [vp, i32, i32, vp, i32]),
+        "slamhip_hsproc_render_world": (i32, [vp, i32, i32, vp, i32]),
         "slamhip_hsproc_scans_match": (i32, [vp, vp, vp, i32, vp]),
         "slamhip_hsproc_frontiers": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]),
         "slamhip_hsproc_nav_field": (i32, [vp, vp, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -1195,6 +1198,31 @@ def debug_render(dims, cell_length, cells, update_index, cache_index, scans, ori
          _vp(xy), _vp(off), _vp(og), _vp(ps), len(pts), fl)
     out, at = [], 0
     for w, h in d:
+        out.append(allc[at:at + int(w) * int(h)].copy()); at += int(w) * int(h)
+    return out, [int(v) for v in ui], [int(v) for v in ci]
+
+
+def debug_render_world(rects, cell_length, cells, update_index, cache_index, scans, origins, poses, keep=False, factors=(0.4, 0.9), flags=None):
+    """The definition of slamhip_hs_render_world on the host (slamhip_debug_render_world; no device involved): rects a list of
+    (x0, y0, w, h) per level in window-frame cells, cells a list of CELL_DTYPE arrays per level (copied), the rest as debug_render
+    -> (cells per level, update_index list, cache_index list)."""
+    r = np.ascontiguousarray(rects, np.int32).reshape(-1, 4)
+    allc = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(c, CELL_DTYPE).reshape(-1) for c in cells]))
+    assert allc.size == int((r[:, 2].astype(np.int64) * r[:, 3]).sum())
+    ui = np.array(update_index, np.int32).reshape(-1).copy(); ci = np.array(cache_index, np.int32).reshape(-1).copy()
+    assert ui.size == ci.size == r.shape[0]
+    pts = [f32(s, (-1, 2)) for s in scans]
+    off = np.zeros(len(pts) + 1, np.int32)
+    off[1:] = np.cumsum([p.shape[0] for p in pts])
+    xy = np.ascontiguousarray(np.concatenate(pts, axis=0)) if pts and off[-1] else np.zeros((1, 2), np.float32)
+    og = f32(origins, (-1, 2)) if len(pts) else np.zeros((1, 2), np.float32)
+    ps = f32(poses, (-1, 3)) if len(pts) else np.zeros((1, 3), np.float32)
+    assert len(pts) == 0 or (og.shape[0] == ps.shape[0] == len(pts))
+    fl = (RENDER_KEEP if keep else 0) if flags is None else int(flags)
+    call("slamhip_debug_render_world", r.shape[0], _vp(r), C.c_float(cell_length), _vp(allc), _vp(ui), _vp(ci), C.c_float(factors[0]), C.c_float(factors[1]),
+         _vp(xy), _vp(off), _vp(og), _vp(ps), len(pts), fl)
+    out, at = [], 0
+    for _, _, w, h in r:
         out.append(allc[at:at + int(w) * int(h)].copy()); at += int(w) * int(h)
     return out, [int(v) for v in ui], [int(v) for v in ci]
 

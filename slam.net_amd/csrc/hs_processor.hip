@@ -550,6 +550,16 @@ extern "C" int32_t slamhip_hsproc_render(slamhip_hsproc *p, int32_t first, int32
     return slamhip_hs_render(p->hs, first, last, have ? hsproc_poses_to_window(p, poses_world, last - first, buf) : poses_world, flags);
 }
 
+extern "C" int32_t slamhip_hsproc_render_world(slamhip_hsproc *p, int32_t first, int32_t last, const float *poses_world, int32_t flags)
+{
+    SH_CHECK_ARG(p);
+    std::vector<float> buf;
+    int32_t count = 0;
+    SH_TRY(slamhip_hs_scans_count(p->hs, &count));
+    const bool have = poses_world && first >= 0 && last > first && last <= count;      // (as slamhip_hsproc_render)
+    return slamhip_hs_render_world(p->hs, first, last, have ? hsproc_poses_to_window(p, poses_world, last - first, buf) : poses_world, flags);
+}
+
 // The view gain through the processor: slamhip_hsproc_trace's shape -- the arguments checked ahead of the scan, the scan set, every
 // pose taken to the window's frame.
 extern "C" int32_t slamhip_hsproc_view_gain(slamhip_hsproc *p, const float *xy, int32_t n, const float origin[2], const float *poses_world, int32_t B,

@@ -5,6 +5,8 @@
 #pragma once
 #include "common.h"
 #include "m3x2.h"
+#include <algorithm>
+#include <cmath>
 
 // One line of OccGridMap.UpdateByScan (OccGridMap.cs:130-140, :155-190) on one level: da the major length, sdb the minor length with
 // its sign, flags = valid | major_x << 1 | (smaj + 1) << 2 (smaj: the sign of the major step).  Not valid: the end cell is the begin
@@ -41,6 +43,37 @@ __host__ __device__ static inline hs_line hs_line_make(float px, float py, const
     return e;
 }
 
+// K25 (hs_render_world.hip): the same line on the unbounded grid of the world.  The inside test against w, h is replaced by the world
+// bound -- begin and end cell within +-HS_WORLD_BOUND cells of window cell (0, 0) -- and nothing else changes; rintf is already right
+// for negative coordinates.  A cell beyond the bound makes the line not valid HERE, and the callers refuse the whole render for it
+// (hs_world_cell_ok on the cells this returns).  A copy, not a parameter of hs_line_make: K20's kernels stay the text they were.
+#define HS_WORLD_BOUND (1 << 20)
+__host__ __device__ static inline bool hs_world_cell_ok(int x, int y)
+{
+    return (x >= -HS_WORLD_BOUND) & (x <= HS_WORLD_BOUND) & (y >= -HS_WORLD_BOUND) & (y <= HS_WORLD_BOUND);
+}
+__host__ __device__ static inline hs_line hs_line_make_world(float px, float py, const sh_m3x2 &t, int bx, int by, int *ex_out, int *ey_out)
+{
+    float exf, eyf;
+    sh_v2_transform(px, py, t, &exf, &eyf);                                // :133
+    const int ex = sh_f2i(rintf(exf)), ey = sh_f2i(rintf(eyf));            // :134
+    const bool same = (bx == ex) & (by == ey);                             // :137
+    const bool inside = hs_world_cell_ok(bx, by) & hs_world_cell_ok(ex, ey);
+    hs_line e; e.da = 0; e.sdb = 0; e.flags = 0;
+    if (!same && inside) {                                                 // (|dx|, |dy| <= 2^21)
+        const int dx = ex - bx, dy = ey - by;
+        const int adx = dx < 0 ? -dx : dx, ady = dy < 0 ? -dy : dy;
+        const bool major_x = adx >= ady;                                   // :175
+        e.da = major_x ? adx : ady;
+        e.sdb = major_x ? dy : dx;
+        const int smaj = sh_sign(major_x ? dx : dy);
+        e.flags = 1 | (major_x ? 2 : 0) | ((smaj + 1) << 2);
+    }
+    *ex_out = ex; *ey_out = ey;
+    return e;
+}
+#define HS_LINE_MAX_DA 32767               // what hs_line_clip's 32-bit proof asks of a line; K20's levels give it, K25 refuses a longer line
+
 // Bresenham2D (:220-239) is monotone: step i = 0 .. da of a line lies at major offset i and minor offset (da / 2 + i * db) / da
 // (tests/test_closed_forms.py; the end cell, step da, at minor offset db: da / 2 < da).  The steps whose cell lies at major offsets
 // [A0, A1] and minor offsets [B0, B1] -- both measured from the begin cell along the line's own directions -- are therefore ONE
@@ -73,4 +106,36 @@ __host__ __device__ static inline void hs_cell_transition(float &v, int &u, int 
         if (v < 50.0f) v += lo_occ;                                        // :211-214
         u = mark_occ;                                                      // :216
     }
+}
+
+// ---- host side, shared by K20 (hs_render.hip) and K25 (hs_render_world.hip) ----------------------------------------------------------
+#define K20_MAX_SCANS (1 << 20)
+
+// the matrix of one pose on one level, formed as hs_update_enqueue forms it (OccGridMap.cs:120-123)
+static inline sh_m3x2 k20_matrix(const float pose[3], float stm)
+{
+    return sh_m3x2_mul(sh_m3x2_mul(sh_m3x2_rotation(pose[2]), sh_m3x2_translation(pose[0], pose[1])), sh_m3x2_scale(stm));
+}
+
+// what the renders and their hooks refuse for the range, the poses and the indices; base: the levels' update indices in front of the
+// first scan
+static inline int32_t k20_check(const char *who, int32_t first, int32_t last, int count, const float *poses, int32_t flags, const int *base, int n_levels)
+{
+    if (flags & ~SLAMHIP_RENDER_KEEP) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: flags = %d holds bits other than SLAMHIP_RENDER_KEEP", who, flags);
+    if (first < 0 || last < first || last > count) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: the range [%d, %d) of %d scans", who, first, last, count);
+    if (last > first && !poses) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: no poses", who);
+    for (size_t i = 0; i < 3 * (size_t)(last - first); i++)
+        if (!std::isfinite(poses[i])) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: component %d of pose %d is not finite", who, (int)(i % 3), (int)(i / 3));
+    for (int l = 0; l < n_levels; l++) {
+        const long long b = (flags & SLAMHIP_RENDER_KEEP) ? base[l] : 0;
+        if (b + 3ll * (last - first) > 0x7fffffffll)
+            SH_FAIL(SLAMHIP_ERR_INVALID, "%s: level %d's update index %lld + 3 x %d scans passes INT_MAX", who, l, b, last - first);
+    }
+    return SLAMHIP_OK;
+}
+
+static inline int k20_chunk()      // scans per launch: what bounds the blocks of a render (SLAMHIP_K20_CHUNK: tests put a boundary inside six scans)
+{
+    static const long long v = std::min(std::max(1ll, sh_env_int("SLAMHIP_K20_CHUNK", 16384)), (long long)K20_MAX_SCANS);
+    return (int)v;
 }

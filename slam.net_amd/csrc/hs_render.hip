@@ -26,7 +26,6 @@
 
 #define K20_LANES 256
 #define K20_NONE 0xFFFFFFFFu
-#define K20_MAX_SCANS (1 << 20)
 
 static_assert(SLAMHIP_RENDER_KEEP == 1, "the flag of include/slamhip.h");
 
@@ -286,39 +285,12 @@ extern "C" int32_t slamhip_hs_scans_clear(slamhip_hs *hs)
     return SLAMHIP_OK;
 }
 
-// the matrix of one pose on one level, formed as hs_update_enqueue forms it (OccGridMap.cs:120-123)
-static inline sh_m3x2 k20_matrix(const float pose[3], float stm)
-{
-    return sh_m3x2_mul(sh_m3x2_mul(sh_m3x2_rotation(pose[2]), sh_m3x2_translation(pose[0], pose[1])), sh_m3x2_scale(stm));
-}
-
-// what slamhip_hs_render and slamhip_debug_render refuse for the range, the poses and the indices; base: the levels' update indices
-// in front of the first scan
-static int32_t k20_check(const char *who, int32_t first, int32_t last, int count, const float *poses, int32_t flags, const int *base, int n_levels)
-{
-    if (flags & ~SLAMHIP_RENDER_KEEP) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: flags = %d holds bits other than SLAMHIP_RENDER_KEEP", who, flags);
-    if (first < 0 || last < first || last > count) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: the range [%d, %d) of %d scans", who, first, last, count);
-    if (last > first && !poses) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: no poses", who);
-    for (size_t i = 0; i < 3 * (size_t)(last - first); i++)
-        if (!std::isfinite(poses[i])) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: component %d of pose %d is not finite", who, (int)(i % 3), (int)(i / 3));
-    for (int l = 0; l < n_levels; l++) {
-        const long long b = (flags & SLAMHIP_RENDER_KEEP) ? base[l] : 0;
-        if (b + 3ll * (last - first) > 0x7fffffffll)
-            SH_FAIL(SLAMHIP_ERR_INVALID, "%s: level %d's update index %lld + 3 x %d scans passes INT_MAX", who, l, b, last - first);
-    }
-    return SLAMHIP_OK;
-}
-
 static int k20_tile()       // T: 32, or 64 by SLAMHIP_K20_TILE=64 (both are built; DESIGN.md section 4 "K20")
 {
     static const int v = sh_env_int("SLAMHIP_K20_TILE", 32) == 64 ? 64 : 32;
     return v;
 }
-static int k20_chunk()      // scans per launch: what bounds the blocks of a render (SLAMHIP_K20_CHUNK: tests put a boundary inside six scans)
-{
-    static const long long v = std::min(std::max(1ll, sh_env_int("SLAMHIP_K20_CHUNK", 16384)), (long long)K20_MAX_SCANS);
-    return (int)v;
-}
+// (k20_matrix, k20_check, k20_chunk: hs_render.h -- K25 forms its matrices, refuses and cuts its range by the same text)
 
 extern "C" int32_t slamhip_hs_render(slamhip_hs *hs, int32_t first, int32_t last, const float *poses, int32_t flags)
 {

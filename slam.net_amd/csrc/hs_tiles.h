@@ -24,6 +24,8 @@ static inline void hs_cut_rows(int nx, int ny, F &&fn)
 
 // a slot for a new tile, initialised on the stream before its first use; nullptr if none can be had (hs_window.hip)
 unsigned char *hs_bk_slot(slamhip_hs *hs);
+// n more slots in the pool, all or none: SLAMHIP_ERR_NOMEM leaves the pool and its books as they were (hs_window.hip)
+int32_t hs_bk_reserve(slamhip_hs *hs, size_t n);
 
 // the backing store's books: the pool (chunks of slots), the directory (level, ty, tx) -> slot, and the pinned ring the job
 // tables reach the device from -- a block of the ring is refilled only after the launch that read it has finished (an event per

@@ -195,6 +195,39 @@ unsigned char *hs_bk_slot(slamhip_hs *hs)
     return s;
 }
 
+// n more slots in the pool, ALL of them or none (slamhip_hs_render_world plans before it changes anything): chunks sized as
+// hs_bk_slot sizes them, allocated first and entered into the books only when the last one is there
+int32_t hs_bk_reserve(slamhip_hs *hs, size_t n)
+{
+    hs_backing *bk = hs->bk;
+    std::vector<hs_bk_chunk> got;
+    uint64_t bytes = (uint64_t)bk->bytes;
+    bool ok = true;
+    while (ok && n > 0) {
+        const uint64_t room = bk->max_bytes > bytes ? bk->max_bytes - bytes : 0;
+        size_t k = HS_BK_CHUNK_BYTES / bk->slot_bytes;
+        if (k < 1) k = 1;
+        if ((uint64_t)k > room / bk->slot_bytes) k = (size_t)(room / bk->slot_bytes);
+        hs_bk_chunk c = { nullptr, k };
+        if (k == 0 || hipMalloc(&c.base, k * bk->slot_bytes) != hipSuccess) { (void)hipGetLastError(); ok = false; break; }
+        got.push_back(c);
+        bytes += (uint64_t)(k * bk->slot_bytes);
+        n -= std::min(n, k);
+    }
+    if (!ok) {
+        for (const hs_bk_chunk &c : got) (void)hipFree(c.base);
+        SH_FAIL(SLAMHIP_ERR_NOMEM, "the backing store cannot take %zu more tiles of %zu bytes: max_bytes = %llu with %lld in use, or a chunk's allocation failed",
+                n, bk->slot_bytes, (unsigned long long)bk->max_bytes, (long long)bk->bytes);
+    }
+    for (const hs_bk_chunk &c : got) {
+        bk->chunks.push_back(c);
+        bk->bytes += (int64_t)(c.slots * bk->slot_bytes);
+        hs_bk_fill_chunk(hs, c);
+        hs_bk_push_free(bk, c);
+    }
+    return SLAMHIP_OK;
+}
+
 // (the caller has drained the stream)
 void hs_bk_free(slamhip_hs *hs)
 {

@@ -781,6 +781,15 @@ class MapRepMultiMap:
         assert last <= first or p.shape[0] == last - first
         capi.call("slamhip_hs_render", self._h, int(first), last, capi._vp(p), capi.RENDER_KEEP if keep else 0)
 
+    def RenderWorld(self, poses, first=0, last=None, keep=False):
+        """Render, into the whole world behind the window (slamhip_hs_render_world; set_backing first): lines that leave the window
+        are drawn into the backing store's tiles, which are taken as needed; without keep the window is cleared and the tiles are
+        dropped first.  SlamhipError ERR_NOMEM, nothing changed, if the tiles do not fit the backing store's max_bytes."""
+        last = self.ScansCount() if last is None else int(last)
+        p = capi.f32(poses, (-1, 3)) if last > first else np.zeros((1, 3), np.float32)
+        assert last <= first or p.shape[0] == last - first
+        capi.call("slamhip_hs_render_world", self._h, int(first), last, capi._vp(p), capi.RENDER_KEEP if keep else 0)
+
     def scans_match(self, spec, pairs):
         """Match stored scans pairwise (slamhip_hs_scans_match; no reference counterpart): spec a capi.scanmatch_spec record, pairs
         (ref, query, guess) tuples or a capi.SCAN_PAIR array, the guess being the query's pose in the reference's frame -> a
@@ -1301,6 +1310,17 @@ class HectorSLAMProcessor:
         assert last <= first or p.shape[0] == last - first
         capi.call("slamhip_hsproc_render", self._h, int(first), last, capi._vp(p), capi.RENDER_KEEP if keep else 0)
 
+    def RenderKeyframesWorld(self, poses=None, first=0, last=None, keep=False):
+        """RenderKeyframes into the whole world behind the window (slamhip_hsproc_render_world; set_backing first): what a loop
+        closure needs when the map is larger than the window.  poses as RenderKeyframes takes them."""
+        last = self.MapRep.ScansCount() if last is None else int(last)
+        if poses is None:
+            _, kp = self.MapRep.SigDownload()
+            poses = kp[first:last]
+        p = capi.f32(poses, (-1, 3)) if last > first else np.zeros((1, 3), np.float32)
+        assert last <= first or p.shape[0] == last - first
+        capi.call("slamhip_hsproc_render_world", self._h, int(first), last, capi._vp(p), capi.RENDER_KEEP if keep else 0)
+
     def LoopCandidates(self, scan, B=capi.SIG_MAX_HITS, exclude_recent=0):
         """The keyframes `scan` resembles most, over all 64 headings (slamhip_hsproc_sig_query over [0, count - exclude_recent))
         -> a list of dicts (hit: the capi.SIG_HIT_DTYPE record, pose: the guess (x_k, y_k, theta_k - shift 2 pi / 64) from the
@@ -1366,7 +1386,7 @@ class HectorSLAMProcessor:
         hit.index -> keyframe i) and `accept`, the caller's predicate over a capi.SCANMATCH_RESULT record (score, n_query, cnt), filters
         them: the library sets no threshold.  RelaxKeyframes then adds the odometry edges of consecutive stored poses (weights odom_w),
         relaxes (pg: a capi.pg_spec record; default 5 steps of 4 N iterations; precond: RelaxKeyframes') and writes the poses back; render=True draws the
-        stored scans again at them (RenderKeyframes).  -> dict(pairs, results, z, w, accepted (bool array), poses, iters, chi2);
+        stored scans again at them (RenderKeyframes), render="world" into the window and the backing tiles (RenderKeyframesWorld).  -> dict(pairs, results, z, w, accepted (bool array), poses, iters, chi2);
         without an accepted edge nothing is relaxed and poses is None.  consistency: a capi.loops_spec record -- the accepted edges are
         then cut down to their largest mutually consistent set (ConsistentLoops) before they are relaxed, and the dict gains
         consistent (bool array over the pairs: accepted and kept) and loops_info (the capi.LOOPS_INFO record); None: no such step."""
@@ -1403,7 +1423,11 @@ class HectorSLAMProcessor:
         N = kp.shape[0]
         poses, iters, chi2 = self.RelaxKeyframes(loops, odom_w, capi.pg_spec(5, 4 * N, tol=1e-8) if pg is None else pg, precond=precond)
         out.update(poses=poses, iters=iters, chi2=chi2)
-        if render:
+        if isinstance(render, str):
+            if render != "world":
+                raise ValueError("close_loops: render = %r must be False, True or \"world\"" % (render,))
+            self.RenderKeyframesWorld()
+        elif render:
             self.RenderKeyframes()
         return out
 
