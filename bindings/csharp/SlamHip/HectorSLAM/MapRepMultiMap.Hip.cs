@@ -678,6 +678,23 @@ namespace HectorSLAM.Main
             return iters;
         }
 
+        /// <summary>Damped and robust relaxation from the poses as they stand (slamhip_hs_pg_relax_lm, rules R1 - R4): robust, a byte per
+        /// edge or null for every edge, says which edges the spec's kernel applies to.  Returns one record per attempt made; factors,
+        /// if given (PgEdges entries), receives every edge's factor at the final poses.</summary>
+        public unsafe PgLmIter[] PgRelaxLm(PgLmSpec spec, byte[] robust, out double costFinal, double[] factors = null)
+        {
+            if (robust != null && robust.Length != PgEdges) throw new ArgumentException("robust: one byte per edge");
+            if (factors != null && factors.Length != PgEdges) throw new ArgumentException("factors: one entry per edge");
+            var iters = new PgLmIter[Math.Max(spec.OuterCount, 1)];
+            int count;
+            fixed (PgLmIter* p = iters)
+            fixed (byte* r = robust)
+            fixed (double* f = factors)
+                Native.Check(Native.slamhip_hs_pg_relax_lm(Pyramid.Ptr, in spec, r, p, out count, out costFinal, f));
+            Array.Resize(ref iters, count);
+            return iters;
+        }
+
         /// <summary>z = T^-1 rhs at the poses as they stand (slamhip_hs_pg_tri_apply): N x 3 doubles in, N x 3 doubles out.</summary>
         public unsafe double[] PgTriApply(double lambda, double[] rhs)
         {

@@ -325,6 +325,26 @@ namespace SlamHip
         public int CgIterations, Stopped;
     }
 
+    /// <summary>slamhip_pg_lm_spec (include/slamhip.h): the attempts, the most PCG iterations of one, the iterations between two reads of
+    /// the stop word, the preconditioner (0 block-Jacobi, 1 the odometry chain), the robust kernel (0 none, 1 DCS, 2 Geman-McClure), 0;
+    /// the first lambda, its factors behind a rejected and an accepted attempt, its bounds, rule 7's tolerance, rule R3's, the kernel's
+    /// phi.  88 bytes: six int32 from offset 0, eight doubles from offset 24.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PgLmSpec
+    {
+        public int OuterCount, CgCount, CheckEvery, Precond, Kind, Reserved;
+        public double Lambda0, Up, Down, LambdaMin, LambdaMax, Tolerance, CostTolerance, Phi;
+    }
+
+    /// <summary>slamhip_pg_lm_iter (include/slamhip.h): the cost before the attempt and at its trial poses, the lambda it used, rz0, the
+    /// last rz, the PCG iterations and why they stopped (as PgIter), whether the attempt was accepted, three reserved words.  64 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PgLmIter
+    {
+        public double Cost, TrialCost, Lambda, Rz0, Rz;
+        public int CgIterations, Stopped, Accepted, Reserved0, Reserved1, Reserved2;
+    }
+
     /// <summary>What slamhip_hs_hough reports of the slot it filled: the map's size and first cell, D = w + h, the bins per angle N,
     /// the sites, and the spectrum HS (T entries); H (T rows of N) when asked for.</summary>
     public sealed class HoughInfo
@@ -493,6 +513,7 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_set(IntPtr hs, double* poses, byte* isFixed, int nNodes, int* ij, double* z, double* w, int nEdges);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_relax(IntPtr hs, in PgSpec spec, PgIter* iters, out double chi2Final);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_relax_tri(IntPtr hs, in PgSpec spec, PgIter* iters, out double chi2Final);
+        [DllImport(Lib)] internal static extern int slamhip_hs_pg_relax_lm(IntPtr hs, in PgLmSpec spec, byte* robust, PgLmIter* iters, out int count, out double costFinal, double* factors);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_tri_apply(IntPtr hs, double lambda, double* rhs, double* z);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_get(IntPtr hs, double* poses, int nNodes);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_residuals(IntPtr hs, double* r, double* chi2);

@@ -1805,6 +1805,73 @@ int32_t slamhip_debug_pg_relax_tri(double *poses, const uint8_t *fixed, int32_t 
 int32_t slamhip_debug_pg_tri_apply(const double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z,
                                    const double *w, int32_t E, double lambda, const double *rhs, double *out);
 
+/* Damped (Levenberg-Marquardt) and robust relaxation (K26; no reference counterpart).  slamhip_hs_pg_relax and _relax_tri take plain
+ * Gauss-Newton steps: a step may RAISE chi2 (DESIGN.md section 4 "K22" records it), and every edge counts quadratically, so one false
+ * loop edge bends the whole trajectory.  Here every step is an ATTEMPT that is taken only if it lowers the cost, lambda moves with the
+ * outcome, and an edge's weight may be scaled by a robust factor.  The existing calls and their results do not change.
+ * THE DEFINITION.  Rules 1 - 8 and T1 - T5 above hold as they stand; R1 - R4 say what is put around them.  Binary64 + - * / and rint, one
+ * rounding per operation, in the order the parentheses give; no sqrt and no libm -- which is why the kernels are the rational ones
+ * (dynamic covariance scaling, Geman-McClure) and Cauchy and Huber are not offered.
+ *  R1. Edge cost and factor, at the poses being linearised.  c_e = rule 3's chi2_e with the caller's weights w.  `robust`: a byte per
+ *      edge, non-zero = the edge is robust; NULL = every edge is robust.  An edge that is not robust, or kind NONE: f_e = 1,
+ *      rho_e = c_e.  A robust edge, with phi the spec's:
+ *        DCS:  if c_e <= phi: f_e = 1, rho_e = c_e;
+ *              else s = (2 * phi) / (phi + c_e);   f_e = s * s;   rho_e = (phi * ((3 * c_e) - phi)) / (c_e + phi).
+ *        GM:   s = phi / (phi + c_e);   f_e = s * s;   rho_e = (phi * c_e) / (phi + c_e).
+ *      w_eff = (f_e * wx, f_e * wy, f_e * wt).  F = the sum of rho_e over the edges by rule 6.
+ *  R2. One attempt.  Rules 3 - 7 with w_eff in place of w and the current lambda (precond = 1: rules 3, 5, 6 and T1 - T5) give x.
+ *      trial_n[a] = pose_n[a] + x_n[a] and trial theta = wrap(trial theta) for every free node; a fixed node's trial is its pose.
+ *      F_trial = R1's F at the trial poses (its own c_e, f_e are not kept).  The attempt is ACCEPTED iff F_trial < F.
+ *      Accepted: poses = trial;   lambda = lambda * down;   if lambda < lambda_min: lambda = lambda_min.
+ *      Rejected: the poses stay;  lambda = lambda * up;     if lambda > lambda_max: lambda = lambda_max.
+ *      The first attempt uses lambda0 as it is given.  Every attempt is one outer iteration, accepted or not.
+ *  R3. Stop.  After n_outer attempts; earlier, behind an ACCEPTED attempt with (F - F_trial) <= ftol * F.  *out_n = the attempts made.
+ *  R4. Record per attempt, slamhip_pg_lm_iter: F, F_trial, the lambda the attempt USED, rz0, rz, cg_iters and stopped as
+ *      slamhip_pg_iter has them, accepted (1 or 0), three reserved words (0).  Records behind *out_n are not written.
+ * CONSEQUENCE.  With kind NONE, lambda0 = lambda_min = 0 and every attempt accepted, w_eff = w and lambda = 0 throughout: the poses and
+ * the rz0, rz, cg_iters and stopped of every record equal slamhip_hs_pg_relax's (precond = 1: _relax_tri's) with lambda = 0 under ==,
+ * and F is its chi2.  Behind a rejected attempt the poses, and with them R1's values and rule 3's records, are unchanged: forming them
+ * again or not gives the same bits.  Nothing depends on the grid, the launch shape or check_every. */
+typedef struct slamhip_pg_lm_spec {
+    int32_t n_outer;                   /* offset 0: attempts, [1, 64] */
+    int32_t n_cg;                      /* offset 4: the most PCG iterations of an attempt, [1, 2^20] */
+    int32_t check_every;               /* offset 8: >= 1, as slamhip_pg_spec's; no result depends on it */
+    int32_t precond;                   /* offset 12: 0 block-Jacobi (rule 4), 1 the odometry chain (T1 - T5) */
+    int32_t kind;                      /* offset 16: 0 NONE, 1 DCS, 2 GM */
+    int32_t reserved;                  /* offset 20: 0 */
+    double lambda0;                    /* offset 24: >= 0, the first attempt's lambda */
+    double up;                         /* offset 32: > 1 */
+    double down;                       /* offset 40: in (0, 1] */
+    double lambda_min;                 /* offset 48: >= 0 */
+    double lambda_max;                 /* offset 56: >= lambda_min */
+    double tol;                        /* offset 64: >= 0, rule 7 */
+    double ftol;                       /* offset 72: >= 0, rule R3 */
+    double phi;                        /* offset 80: > 0; not read for kind NONE */
+} slamhip_pg_lm_spec;                  /* 88 bytes */
+typedef struct slamhip_pg_lm_iter {
+    double F, F_trial, lambda, rz0, rz;    /* offsets 0, 8, 16, 24, 32 */
+    int32_t cg_iters, stopped, accepted;   /* offsets 40, 44, 48; stopped as slamhip_pg_iter's */
+    int32_t reserved[3];                   /* offset 52: 0 */
+} slamhip_pg_lm_iter;                  /* 64 bytes */
+/* Rules R1 - R4 from the poses as they stand in device memory; calls of this, slamhip_hs_pg_relax and _relax_tri may follow one another
+ * on one graph.  robust: E bytes or NULL (R1).  out_iters: room for n_outer records; *out_n: how many were written; *out_F_final: F at
+ * the final poses; out_f: E doubles, f_e at the final poses, or NULL.  Launches per attempt: k26_weigh (a lane per edge: R1 at the
+ * poses, w_eff into a second weight array) and k19_linearise -- neither behind a rejected attempt --, then the launches of
+ * slamhip_hs_pg_relax (precond = 1: of _relax_tri) as they are, reading w_eff, up to but without k19_update; k26_trial (a lane per node),
+ * k26_weigh at the trial poses (the cost alone), k26_decide (ONE workgroup: both sums, the comparison, the record, the accept word) and
+ * k26_commit (a lane per node).  The host reads the accept word once per attempt and forms the next lambda by R2.  Its own block (32
+ * bytes per edge and 24 per node) is made by the first call, grown with the graph and freed by slamhip_hs_pg_clear / _destroy; with
+ * precond = 1 the levels' blocks are made as slamhip_hs_pg_relax_tri makes them; after SLAMHIP_ERR_NOMEM the graph is as it was.
+ * Blocking, on the operator's stream, with the context's bounded wait.  SLAMHIP_ERR_INVALID, nothing launched and nothing written: a
+ * spec outside the ranges above, a value that is not finite, reserved != 0.  SLAMHIP_ERR_STATE: no graph. */
+int32_t slamhip_hs_pg_relax_lm(slamhip_hs *hs, const slamhip_pg_lm_spec *spec, const uint8_t *robust, slamhip_pg_lm_iter *out_iters,
+                               int32_t *out_n, double *out_F_final, double *out_f);
+/* Test hook (no device involved), from the header text the kernels run (hs_pg_lm.h, hs_pg.h, hs_pg_tri.h) in plain loops: the graph
+ * arguments and refusals of slamhip_debug_pg_relax, poses relaxed IN PLACE, then the tail and the refusals of slamhip_hs_pg_relax_lm. */
+int32_t slamhip_debug_pg_relax_lm(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w,
+                                  int32_t E, const slamhip_pg_lm_spec *spec, const uint8_t *robust, slamhip_pg_lm_iter *out_iters,
+                                  int32_t *out_n, double *out_F_final, double *out_f);
+
 /* MapRepMultiMap.UpdateByScan ->OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);

@@ -191,6 +191,13 @@ PG_SPEC = np.dtype([("n_outer", np.int32), ("n_cg", np.int32), ("check_every", n
                     ("tol", np.float64)])                                                           # slamhip_pg_spec: 32 bytes
 PG_ITER = np.dtype([("chi2", np.float64), ("rz0", np.float64), ("rz", np.float64), ("cg_iters", np.int32), ("stopped", np.int32)])   # slamhip_pg_iter: 32 bytes
 assert PG_SPEC.itemsize == 32 and PG_ITER.itemsize == 32
+PG_LM_NONE, PG_LM_DCS, PG_LM_GM = 0, 1, 2                                                          # slamhip_pg_lm_spec.kind
+PG_LM_SPEC = np.dtype([("n_outer", np.int32), ("n_cg", np.int32), ("check_every", np.int32), ("precond", np.int32), ("kind", np.int32),
+                       ("reserved", np.int32), ("lambda0", np.float64), ("up", np.float64), ("down", np.float64), ("lambda_min", np.float64),
+                       ("lambda_max", np.float64), ("tol", np.float64), ("ftol", np.float64), ("phi", np.float64)])   # slamhip_pg_lm_spec: 88 bytes
+PG_LM_ITER = np.dtype([("F", np.float64), ("F_trial", np.float64), ("lambda", np.float64), ("rz0", np.float64), ("rz", np.float64),
+                       ("cg_iters", np.int32), ("stopped", np.int32), ("accepted", np.int32), ("reserved", np.int32, (3,))])   # slamhip_pg_lm_iter: 64 bytes
+assert PG_LM_SPEC.itemsize == 88 and PG_LM_ITER.itemsize == 64
 SCANMATCH_MAX_HALF, SCANMATCH_MAX_N, SCANMATCH_MAX_PAIRS, SCANMATCH_MAX_NODES, SCANMATCH_MAX_CALL_NODES = 192, 64, 4096, 1 << 20, 1 << 26   # the limits of slamhip_hs_scans_match
 SCANMATCH_SPEC = np.dtype([("scale", np.float32), ("half", np.int32), ("nx", np.int32), ("ny", np.int32), ("nt", np.int32), ("dtheta", np.float32),
                            ("margin", np.int32), ("reserved", np.int32)])                                # slamhip_scanmatch_spec: 32 bytes
@@ -299,6 +306,7 @@ def _declare(L):
         "slamhip_debug_pg_sum": (i32, [vp, i32, vp]),
         "slamhip_debug_pg_relax_tri": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "slamhip_debug_pg_tri_apply": (i32, [vp, vp, i32, vp, vp, vp, i32, C.c_double, vp, vp]),
+        "slamhip_debug_pg_relax_lm": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
         "slamhip_debug_scans_match": (i32, [vp, vp, i32, vp, vp, i32, vp]),
         "slamhip_debug_loops_consistent": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
         "slamhip_debug_render": (i32, [i32, vp, f, vp, vp, vp, f, f, vp, vp, vp, vp, i32, i32]),
@@ -425,6 +433,7 @@ def _declare(L):
         "slamhip_hs_pg_relax": (i32, [vp, vp, vp, vp]),
         "slamhip_hs_pg_relax_tri": (i32, [vp, vp, vp, vp]),
         "slamhip_hs_pg_tri_apply": (i32, [vp, C.c_double, vp, vp]),
+        "slamhip_hs_pg_relax_lm": (i32, [vp, vp, vp, vp, vp, vp, vp]),
         "slamhip_hs_pg_get": (i32, [vp, vp, i32]),
         "slamhip_hs_pg_residuals": (i32, [vp, vp, vp]),
         "slamhip_hs_pg_clear": (i32, [vp]),
@@ -1098,6 +1107,50 @@ def debug_pg_relax_tri(poses, fixed, ij, z, w, spec):
     """The whole definition of slamhip_hs_pg_relax_tri on the host (slamhip_debug_pg_relax_tri; no device involved): what
     debug_pg_relax returns, with the odometry-chain preconditioner (rules T1 - T5)."""
     return debug_pg_relax(poses, fixed, ij, z, w, spec, entry="slamhip_debug_pg_relax_tri")
+
+
+PG_LM_PRECOND = {"jacobi": 0, "tri": 1}
+PG_LM_KIND = {"none": PG_LM_NONE, "dcs": PG_LM_DCS, "gm": PG_LM_GM}
+
+
+def pg_lm_spec(n_outer, n_cg, check_every=None, precond="jacobi", kind="none", lambda0=1e-3, up=10.0, down=0.1, lambda_min=0.0, lambda_max=1e12,
+               tol=1e-6, ftol=0.0, phi=1.0, reserved=0):
+    """A slamhip_pg_lm_spec record (a (1,) PG_LM_SPEC array); check_every defaults to min(n_cg, 64); precond "jacobi" / "tri" and kind
+    "none" / "dcs" / "gm" by name, or the header's numbers."""
+    sp = np.zeros(1, PG_LM_SPEC)
+    sp["n_outer"] = int(n_outer); sp["n_cg"] = int(n_cg); sp["check_every"] = min(int(n_cg), 64) if check_every is None else int(check_every)
+    sp["precond"] = PG_LM_PRECOND.get(precond, precond); sp["kind"] = PG_LM_KIND.get(kind, kind); sp["reserved"] = int(reserved)
+    for name, v in (("lambda0", lambda0), ("up", up), ("down", down), ("lambda_min", lambda_min), ("lambda_max", lambda_max), ("tol", tol),
+                    ("ftol", ftol), ("phi", phi)):
+        sp[name] = float(v)
+    return sp
+
+
+def pg_robust(robust, E):
+    """The robust bytes of slamhip_hs_pg_relax_lm: None, or (E,) uint8, contiguous."""
+    if robust is None:
+        return None
+    rb = np.ascontiguousarray(np.asarray(robust).astype(bool).astype(np.uint8))
+    assert rb.shape == (E,), (rb.shape, E)
+    return rb
+
+
+def pg_relax_lm_call(entry, head, E, spec, robust):
+    """The tail of slamhip_hs_pg_relax_lm / slamhip_debug_pg_relax_lm behind the arguments `head`
+    -> (iters PG_LM_ITER (*out_n,), F_final, f (E,))."""
+    rb = pg_robust(robust, E)
+    iters = np.zeros(max(int(spec["n_outer"][0]), 1), PG_LM_ITER); n = C.c_int32(0); fin = C.c_double(0.0); f = np.zeros(E, np.float64)
+    call(entry, *head, spec.ctypes.data_as(C.c_void_p), _vp(rb), iters.ctypes.data_as(C.c_void_p), C.byref(n), C.byref(fin), _vp(f))
+    return iters[:n.value].copy(), fin.value, f
+
+
+def debug_pg_relax_lm(poses, fixed, ij, z, w, spec, robust=None):
+    """The whole definition of slamhip_hs_pg_relax_lm on the host (slamhip_debug_pg_relax_lm; no device involved)
+    -> (poses (N, 3), iters PG_LM_ITER (*out_n,), F_final, f (E,)).  The caller's arrays are not written."""
+    p, fx, e, zz, ww = pg_graph(poses, fixed, ij, z, w)
+    assert e.shape[0] == zz.shape[0] == ww.shape[0] and (fx is None or fx.shape[0] == p.shape[0])
+    it, fin, f = pg_relax_lm_call("slamhip_debug_pg_relax_lm", (_vp(p), _vp(fx), p.shape[0], _vp(e), _vp(zz), _vp(ww), e.shape[0]), e.shape[0], spec, robust)
+    return p, it, fin, f
 
 
 def debug_pg_tri_apply(poses, fixed, ij, z, w, lam, rhs):

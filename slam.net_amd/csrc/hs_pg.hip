@@ -20,6 +20,7 @@
 #include "hs_blocks.h"
 #include "hs_pg.h"
 #include "hs_pg_tri.h"
+#include "hs_pg_lm.h"
 #include <algorithm>
 #include <string.h>
 #include <vector>
@@ -321,6 +322,7 @@ struct hs_pg {
     unsigned char *h_io; size_t cap_h;
     unsigned char *d_tri; size_t cap_tri;                  // K22 (hs_pg_tri.inc): the levels' blocks, made by the first _pg_relax_tri / _pg_tri_apply
     hs_tri_plan T;
+    unsigned char *d_lm; size_t cap_lm;                    // K26 (hs_pg_lm.inc): the weights, the trial poses and the records, made by the first _pg_relax_lm
 };
 
 void hs_pg_free(slamhip_hs *hs)
@@ -330,6 +332,7 @@ void hs_pg_free(slamhip_hs *hs)
     hs_release((void **)&g->d_blob, &g->cap_blob, HS_MEM_DEVICE);
     hs_release((void **)&g->h_io, &g->cap_h, HS_MEM_PINNED);
     hs_release((void **)&g->d_tri, &g->cap_tri, HS_MEM_DEVICE);
+    hs_release((void **)&g->d_lm, &g->cap_lm, HS_MEM_DEVICE);
     delete g;
     hs->pg = nullptr;
 }
@@ -561,12 +564,10 @@ static double hs_pg_host_dot(const double *u, const double *v, int N, double *tm
     return hs_pg_tree_sum(tmp, (size_t)N);
 }
 
-extern "C" int32_t slamhip_debug_pg_relax(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
-                                          const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
+// the definition over a graph and a spec that have been checked (K26's hook takes single steps through it, with its own weights)
+static void hs_pg_host_relax(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
+                             const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
 {
-    SH_CHECK_ARG(spec && out_iters && out_chi2_final);
-    SH_TRY(hs_pg_check_spec(spec));
-    SH_TRY(hs_pg_check_graph(poses, fixed, N, ij, z, w, E));
     const size_t n3 = 3 * (size_t)N, pad = HS_PG_BLOCK;
     std::vector<int32_t> off((size_t)N + 1), inc(2 * (size_t)E + 1);
     hs_pg_lists(N, ij, E, off.data(), inc.data());
@@ -647,6 +648,15 @@ extern "C" int32_t slamhip_debug_pg_relax(double *poses, const uint8_t *fixed, i
     *out_chi2_final = hs_pg_host_linearise(poses, ij, z, w, E, rec.data(), r.data(), tmp.data());
     if (out_r && E) memcpy(out_r, r.data(), 24 * (size_t)E);
     if (out_chi2) for (int e = 0; e < E; e++) out_chi2[e] = rec[(size_t)e].chi2;
+}
+
+extern "C" int32_t slamhip_debug_pg_relax(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
+                                          const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
+{
+    SH_CHECK_ARG(spec && out_iters && out_chi2_final);
+    SH_TRY(hs_pg_check_spec(spec));
+    SH_TRY(hs_pg_check_graph(poses, fixed, N, ij, z, w, E));
+    hs_pg_host_relax(poses, fixed, N, ij, z, w, E, spec, out_iters, out_chi2_final, out_r, out_chi2);
     return SLAMHIP_OK;
 }
 
@@ -667,3 +677,4 @@ extern "C" int32_t slamhip_debug_sincos(const double *a, int32_t n, double *out_
 }
 
 #include "hs_pg_tri.inc"
+#include "hs_pg_lm.inc"

@@ -256,10 +256,8 @@ static int32_t hs_tri_blocks(hs_pg *g, const char *who)
 }
 
 // rules T1 - T3 at the poses as they stand (k19_linearise has run)
-static int32_t hs_tri_factor(hs_pg *g, hipStream_t st, double lambda, int start)
+static int32_t hs_tri_factor(const k19_arg &A, const hs_tri_plan &T, hipStream_t st, double lambda, int start)
 {
-    const k19_arg &A = g->A;
-    const hs_tri_plan &T = g->T;
     K19_LAUNCH(k22_diag, A.PN, A, T, lambda, start);
     K19_LAUNCH(k22_coupling, A.PN, A, T);
     for (int l = 0; l < T.lt; l++) K19_LAUNCH(k22_reduce, sh_div_up(T.n[l + 1], K19_LANES), T, l);
@@ -296,7 +294,7 @@ extern "C" int32_t slamhip_hs_pg_relax_tri(slamhip_hs *hs, const slamhip_pg_spec
     const k22_io first = { A.res, A.zv, A.p, A.part_b, nullptr }, io = { A.res, A.zv, nullptr, A.part_b, A.st };
     for (int outer = 0; outer < spec->n_outer; outer++) {
         K19_LAUNCH(k19_linearise, A.PE, A);
-        SH_TRY(hs_tri_factor(g, st, spec->lambda, 1));
+        SH_TRY(hs_tri_factor(A, g->T, st, spec->lambda, 1));
         SH_TRY(hs_tri_solve(g, st, first));                                // rule 7's start: z = T^-1 res, p = z, the block sums of res . z
         K19_LAUNCH(k19_begin, 1, A, 0);
         for (int k = 0; k < spec->n_cg;) {
@@ -341,7 +339,7 @@ extern "C" int32_t slamhip_hs_pg_tri_apply(slamhip_hs *hs, double lambda, const 
     memcpy(g->h_io, rhs, bytes);
     SH_HIP(hipMemcpyAsync(A.res, g->h_io, bytes, hipMemcpyHostToDevice, st));   // (the PCG vectors are free between two calls)
     K19_LAUNCH(k19_linearise, A.PE, A);
-    SH_TRY(hs_tri_factor(g, st, lambda, 0));
+    SH_TRY(hs_tri_factor(A, g->T, st, lambda, 0));
     const k22_io io = { A.res, A.zv, nullptr, nullptr, nullptr };
     SH_TRY(hs_tri_solve(g, st, io));
     SH_HIP(hipMemcpyAsync(g->h_io, A.zv, bytes, hipMemcpyDeviceToHost, st));
@@ -448,12 +446,10 @@ static void hs_tri_host_solve(hs_tri_host &H, const double *r0, double *z0)
         if (!T.live[n]) z0[3 * n] = z0[3 * n + 1] = z0[3 * n + 2] = 0.0;
 }
 
-extern "C" int32_t slamhip_debug_pg_relax_tri(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
-                                              const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
+// the definition over a graph and a spec that have been checked (K26's hook takes single steps through it, with its own weights)
+static void hs_tri_host_relax(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
+                              const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
 {
-    SH_CHECK_ARG(spec && out_iters && out_chi2_final);
-    SH_TRY(hs_pg_check_spec(spec));
-    SH_TRY(hs_pg_check_graph(poses, fixed, N, ij, z, w, E));
     const size_t n3 = 3 * (size_t)N, pad = HS_PG_BLOCK;
     hs_tri_host H;
     hs_tri_host_init(H, fixed, N, ij, E);
@@ -510,6 +506,15 @@ extern "C" int32_t slamhip_debug_pg_relax_tri(double *poses, const uint8_t *fixe
     *out_chi2_final = hs_pg_host_linearise(poses, ij, z, w, E, rec.data(), r.data(), tmp.data());
     if (out_r && E) memcpy(out_r, r.data(), 24 * (size_t)E);
     if (out_chi2) for (int e = 0; e < E; e++) out_chi2[e] = rec[(size_t)e].chi2;
+}
+
+extern "C" int32_t slamhip_debug_pg_relax_tri(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
+                                              const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
+{
+    SH_CHECK_ARG(spec && out_iters && out_chi2_final);
+    SH_TRY(hs_pg_check_spec(spec));
+    SH_TRY(hs_pg_check_graph(poses, fixed, N, ij, z, w, E));
+    hs_tri_host_relax(poses, fixed, N, ij, z, w, E, spec, out_iters, out_chi2_final, out_r, out_chi2);
     return SLAMHIP_OK;
 }
 

@@ -715,6 +715,13 @@ class MapRepMultiMap:
         capi.call(self.PG_PRECOND[precond], self._h, spec.ctypes.data_as(C.c_void_p), iters.ctypes.data_as(C.c_void_p), C.byref(fin))
         return iters[:int(spec["n_outer"][0])].copy(), fin.value
 
+    def PgRelaxLM(self, spec, robust=None):
+        """Damped and robust relaxation from the poses as they stand (slamhip_hs_pg_relax_lm, rules R1 - R4): spec a capi.pg_lm_spec
+        record, robust (E,) bools -- the edges the spec's kernel applies to -- or None for all of them
+        -> (iters capi.PG_LM_ITER records, one per attempt made, F at the final poses, f (E,): every edge's factor there)."""
+        E = getattr(self, "_pg_sizes", (1, 0))[1]
+        return capi.pg_relax_lm_call("slamhip_hs_pg_relax_lm", (self._h,), E, spec, robust)
+
     def PgTriApply(self, lam, rhs):
         """z = T^-1 rhs at the poses as they stand (slamhip_hs_pg_tri_apply): the odometry-chain preconditioner alone, lambda = lam on
         the diagonal, rhs (N, 3) -> (N, 3) float64."""
@@ -1345,13 +1352,16 @@ class HectorSLAMProcessor:
         only; the caller judges the report."""
         return self.Relocalise(scan, hit["pose"], level, nx, ny, n_theta, dtheta, B=B, adopt=False, search=search, top=top)
 
-    def RelaxKeyframes(self, loops, odom_w, spec, fixed=None, precond="jacobi"):
+    def RelaxKeyframes(self, loops, odom_w, spec, fixed=None, precond="jacobi", lm=None):
         """Spread verified loops over the keyframe store's poses (host composition of slamhip_hs_pg_set, _pg_relax, _pg_get,
         _pg_residuals and slamhip_hs_sig_set_poses; no reference counterpart).  Nodes: the store's poses; an odometry edge joins every
         pair of consecutive keyframes, its z formed from their stored poses (capi.pg_edge_between), its weights odom_w = (wx, wy,
         wtheta); one more edge per entry (i, j, z, w) of `loops`, as the caller derives it from VerifyLoop; node 0 is fixed unless
         `fixed` says otherwise; precond as MapRepMultiMap.PgRelax takes it ("tri" fits this graph).  The relaxed poses are written back to the store (rounded to binary32, as it keeps them)
-        -> (poses (N, 3) float64, iters, per-edge chi2 at the relaxed poses: the N - 1 odometry edges, then the loops)."""
+        -> (poses (N, 3) float64, iters, per-edge chi2 at the relaxed poses: the N - 1 odometry edges, then the loops).
+        lm: a capi.pg_lm_spec record -- the graph is then relaxed by MapRepMultiMap.PgRelaxLM instead, `robust` set on exactly the loop
+        edges (spec and precond are not read: the record has its own), iters are capi.PG_LM_ITER records, and a fourth value follows:
+        f, every edge's factor at the relaxed poses in chi2's order."""
         rep = self.MapRep
         _, kp = rep.SigDownload()
         N = kp.shape[0]
@@ -1361,11 +1371,15 @@ class HectorSLAMProcessor:
         for (i, j, zl, wl) in loops:
             ij.append((int(i), int(j))); z.append(tuple(float(v) for v in zl)); w.append(tuple(float(v) for v in wl))
         rep.PgSet(poses, fixed, np.array(ij, np.int32).reshape(-1, 2), np.array(z, np.float64).reshape(-1, 3), np.array(w, np.float64).reshape(-1, 3))
-        iters, _ = rep.PgRelax(spec, precond=precond)
+        f = None
+        if lm is None:
+            iters, _ = rep.PgRelax(spec, precond=precond)
+        else:
+            iters, _, f = rep.PgRelaxLM(lm, robust=np.arange(len(ij)) >= N - 1)
         out = rep.PgGet()
         _, chi2 = rep.PgResiduals()
         rep.SigSetPoses(out.astype(np.float32))
-        return out, iters, chi2
+        return (out, iters, chi2) if lm is None else (out, iters, chi2, f)
 
     def ConsistentLoops(self, loops, spec):
         """MapRep.LoopsConsistent over the keyframe store's poses as they stand: loops as RelaxKeyframes takes them, entries
@@ -1379,7 +1393,7 @@ class HectorSLAMProcessor:
         """MapRep.scans_match through the processor (slamhip_hsproc_scans_match): relative poses, no frame to convert."""
         return capi.scans_match_call("slamhip_hsproc_scans_match", self._h, spec, pairs)
 
-    def close_loops(self, min_gap, spec, accept, odom_w=(400.0, 400.0, 2500.0), pg=None, render=False, guess_from_poses=False, precond="jacobi", consistency=None):
+    def close_loops(self, min_gap, spec, accept, odom_w=(400.0, 400.0, 2500.0), pg=None, render=False, guess_from_poses=False, precond="jacobi", consistency=None, lm=None):
         """Close the loops of the keyframe store (host composition; AddKeyframe with keep_scan first): SelfLoopCandidates(min_gap) names
         one candidate per keyframe; its guess is (0, 0, -shift 2 pi / 64) by K18's sign rule -- or, with guess_from_poses, the
         translation between the two stored poses in the candidate's frame; scans_match turns the candidates into edges (keyframe
@@ -1389,7 +1403,8 @@ class HectorSLAMProcessor:
         stored scans again at them (RenderKeyframes), render="world" into the window and the backing tiles (RenderKeyframesWorld).  -> dict(pairs, results, z, w, accepted (bool array), poses, iters, chi2);
         without an accepted edge nothing is relaxed and poses is None.  consistency: a capi.loops_spec record -- the accepted edges are
         then cut down to their largest mutually consistent set (ConsistentLoops) before they are relaxed, and the dict gains
-        consistent (bool array over the pairs: accepted and kept) and loops_info (the capi.LOOPS_INFO record); None: no such step."""
+        consistent (bool array over the pairs: accepted and kept) and loops_info (the capi.LOOPS_INFO record); None: no such step.
+        lm: a capi.pg_lm_spec record, handed to RelaxKeyframes (pg and precond are then not read); the dict gains f."""
         hits = self.SelfLoopCandidates(min_gap)
         _, kp = self.MapRep.SigDownload()
         pairs = []
@@ -1421,8 +1436,10 @@ class HectorSLAMProcessor:
         if not loops:
             return out
         N = kp.shape[0]
-        poses, iters, chi2 = self.RelaxKeyframes(loops, odom_w, capi.pg_spec(5, 4 * N, tol=1e-8) if pg is None else pg, precond=precond)
-        out.update(poses=poses, iters=iters, chi2=chi2)
+        relaxed = self.RelaxKeyframes(loops, odom_w, capi.pg_spec(5, 4 * N, tol=1e-8) if pg is None else pg, precond=precond, lm=lm)
+        out.update(poses=relaxed[0], iters=relaxed[1], chi2=relaxed[2])
+        if lm is not None:
+            out.update(f=relaxed[3])
         if isinstance(render, str):
             if render != "world":
                 raise ValueError("close_loops: render = %r must be False, True or \"world\"" % (render,))

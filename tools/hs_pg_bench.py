@@ -24,7 +24,10 @@ grid, whose vertical edges -- half of all -- are no chain edges.  Per graph and 
 (wall clock of the blocking call, the PCG iterations it took; block-Jacobi is capped at 4 N iterations and left out at 2^20 nodes),
 the same call with n_cg = 1 (linearise, factorisation, the start's solve, one iteration, the copies), the time per PCG iteration as
 the difference of the two over the iterations between them, and for tri one blocking _pg_tri_apply (upload, factorisation, solve,
-download) with its backward error |T z - r| / (|T|_1 |z| + |r|) beside scipy's spsolve on the same sparse T."""
+download) with its backward error |T z - r| / (|T|_1 |z| + |r|) beside scipy's spsolve on the same sparse T.
+
+`python tools/hs_pg_bench.py --lm [out.json]` (profiles/r32_hs_pg_lm.json): K26, one attempt of slamhip_hs_pg_relax_lm beside one step
+of slamhip_hs_pg_relax / _relax_tri at equal n_cg, and the large rings' first step with and without damping (lm_main)."""
 import hashlib
 import json
 import os
@@ -236,6 +239,58 @@ def tri_main(out_path):
         json.dump(out, f, indent=1)
 
 
+def lm_main(out_path):
+    """K26 (slamhip_hs_pg_relax_lm) beside K19 / K22 IN THE SAME RUN -- their kernels are the parent commit's, instruction for
+    instruction.  Per graph (ring, street grid; 10^3, 10^4, 10^5 nodes) and preconditioner: ONE attempt against ONE step at equal
+    n_cg = 60 with tol = 0 and kind NONE (the same PCG iterations, counted), the graph set again before each, medians of 7 blocking calls after a warm-up.
+    Then the rings whose first undamped step raises chi2 (DESIGN.md section 4 "K22"), once each with LM: F per attempt."""
+    ctx = hs.Context(0)
+    rep = hs.MapRepMultiMap(0.1, (64, 64), 1, ctx=ctx)
+    out = {"graphs": {}, "first_step": {}}
+    for name, make in (("ring", ring), ("streets", streets)):
+        for N in (1000, 10000, 100000):
+            g = make(N)
+            rec = {"N": int(g[0].shape[0]), "E": int(g[1].shape[0])}
+            for precond in ("jacobi", "tri"):
+                step = capi.pg_spec(1, 60, check_every=60, tol=0.0, lam=1e-3)
+                lm = capi.pg_lm_spec(1, 60, check_every=60, precond=precond, kind="none", lambda0=1e-3, tol=0.0)   # (NONE: the step's own arithmetic)
+                ts = {"step": [], "lm_attempt": []}
+                for k in range(8):
+                    rep.PgSet(g[0], None, g[1], g[2], g[3])
+                    t0 = time.perf_counter(); it, _ = rep.PgRelax(step, precond=precond); dt = time.perf_counter() - t0
+                    rep.PgSet(g[0], None, g[1], g[2], g[3])
+                    t1 = time.perf_counter(); lit, _, _ = rep.PgRelaxLM(lm); dl = time.perf_counter() - t1
+                    assert len(lit) == 1 and lit[0]["cg_iters"] == it[0]["cg_iters"] and lit[0]["rz"] == it[0]["rz"], (it, lit)
+                    if k >= 1:
+                        ts["step"].append(dt); ts["lm_attempt"].append(dl)
+                rec[precond] = {k: stats(v) for k, v in ts.items()}
+                rec[precond]["cg_iters"] = int(it[0]["cg_iters"])              # (tri may end below 60: rz <= 0 stops it whatever tol says)
+                rec[precond]["extra_us"] = rec[precond]["lm_attempt"]["median_us"] - rec[precond]["step"]["median_us"]
+            out["graphs"]["%s_%d" % (name, N)] = rec
+            print(name, N, json.dumps(rec), flush=True)
+    for N in (10000, 100000, 1 << 20):
+        g = ring(N)
+        rep.PgSet(g[0], None, g[1], g[2], g[3])
+        it, fin = rep.PgRelax(capi.pg_spec(2, 64, check_every=64, tol=1e-6), precond="tri")
+        rep.PgSet(g[0], None, g[1], g[2], g[3])
+        t0 = time.perf_counter(); lit, F, _ = rep.PgRelaxLM(capi.pg_lm_spec(12, 64, check_every=64, precond="tri", lambda0=1e-3, tol=1e-6)); dt = time.perf_counter() - t0
+        out["first_step"]["ring_%d" % N] = {"gauss_newton_chi2": it["chi2"].tolist() + [fin], "lm_F": lit["F"].tolist() + [F], "lm_accepted": lit["accepted"].tolist(),
+                                           "lm_lambda": lit["lambda"].tolist(), "lm_cg_iters": lit["cg_iters"].tolist(), "lm_call_us": dt * 1e6}
+        print("first_step", N, json.dumps(out["first_step"]["ring_%d" % N]), flush=True)
+    rep.close()
+    ctx.close()
+    parent = os.path.join(ROOT, "slam.net_amd", "build", "variants", "parent.so")
+    if os.path.exists(parent):
+        out["update_alternating"] = {"this_tree": [], "parent": []}
+        for _ in range(3):
+            out["update_alternating"]["this_tree"].append(child("--update-only", None)["update"])
+            out["update_alternating"]["parent"].append(child("--update-only", parent)["update"])
+        print(json.dumps(out["update_alternating"]), flush=True)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def child(flag, lib):
     """This script again in a fresh interpreter with `lib` (None: this tree's) -> the JSON object it printed last."""
     env = dict(os.environ)
@@ -252,6 +307,10 @@ def main():
         return
     if "--variant-only" in sys.argv:
         print(json.dumps({"figures": variant_figures(), "lib": os.environ.get("SLAMHIP_LIB", "this tree")}))
+        return
+    if "--lm" in sys.argv:
+        rest = [a for a in sys.argv[1:] if a != "--lm"]
+        lm_main(rest[0] if rest else os.path.join(ROOT, "profiles", "r32_hs_pg_lm.json"))
         return
     if "--precond" in sys.argv:
         at = sys.argv.index("--precond")
