@@ -1790,7 +1790,7 @@ int32_t slamhip_debug_sincos(const double *a, int32_t n, double *out_s, double *
  * slamhip_hs_pg_clear / _destroy; a caller that uses neither allocates nothing.  After SLAMHIP_ERR_NOMEM the graph is as it was and
  * slamhip_hs_pg_relax still runs.  Launches: k22_diag and k22_coupling (a lane per node), k22_reduce (one per level of more than S = 1024
  * blocks) and k22_factor_tail (ONE workgroup, the levels of at most S blocks) once per outer iteration; per PCG iteration k19_apply,
- * k22_axpy, then k22_forward per large level, k22_solve_tail (one workgroup, the small levels in LDS) and k22_backward per large level
+ * k19_step<false>, then k22_forward per large level, k22_solve_tail (one workgroup, the small levels in LDS) and k22_backward per large level
  * -- 2 ceil(log2(N / S)) + 1 launches, ONE for N <= S; the last of them leaves the block sums of res . z -- and k19_dir.  The stop word
  * works as in slamhip_hs_pg_relax.  SLAMHIP_K22_TAIL (developer, read at every call, [1, 1024]) sets S.
  * slamhip_hs_pg_tri_apply: T1 - T4 alone at the poses as they stand, for one right-hand side: rhs and out = N x 3 doubles.  Blocking.

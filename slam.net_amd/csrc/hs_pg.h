@@ -1,6 +1,7 @@
 // hs_pg.h -- the arithmetic of the pose-graph relaxation (K19, hs_pg.hip) that host and device share: the kernels k19_linearise,
-// k19_diag, k19_apply, k19_step, k19_dir and k19_update and the test hooks slamhip_debug_pg_relax / _pg_sum / _sincos run this text.
-// Definition: include/slamhip.h, slamhip_hs_pg_relax.  Everything here is binary64 + - * / and rint, one rounding per operation (the
+// k19_diag, k19_apply, k19_step, k19_dir and k19_update and the test hooks slamhip_debug_pg_relax / _pg_sum / _sincos run this text,
+// down to the loops over a node's list of rules 4 and 5 (hs_pg_node_diag, hs_pg_node_apply: always inlined, so that a kernel's code is
+// what it was with the loop written in the kernel).  Definition: include/slamhip.h, slamhip_hs_pg_relax.  Everything here is binary64 + - * / and rint, one rounding per operation (the
 // build has -ffp-contract=off); every expression is parenthesised as the definition writes it.
 #pragma once
 #include "common.h"
@@ -106,12 +107,68 @@ __host__ __device__ static inline void hs_pg_edge_t(const hs_pg_rec &R, const do
     }
 }
 
+// The per-node loops run over the node -> (edge, side) lists: node n's entries are inc[off[n] .. off[n + 1]), an entry edge << 1 | side;
+// rec and r are rule 3's records and residuals per edge, ij the edges' (i, j) pairs, a node vector three doubles per node.
+// rule 4 for one free node: D_n = lambda I + sum J^T W J and g_n = sum J^T W r over the node's list
+__host__ __device__ static __forceinline__ void hs_pg_node_diag(double lambda, int n, const int32_t *off, const int32_t *inc, const hs_pg_rec *rec, const double *r,
+                                                                double D[6], double g[3])
+{
+    D[0] = lambda; D[1] = 0.0; D[2] = 0.0; D[3] = lambda; D[4] = 0.0; D[5] = lambda;
+    g[0] = 0.0; g[1] = 0.0; g[2] = 0.0;
+    const int m1 = off[n + 1];
+    for (int m = off[n]; m < m1; m++) {
+        const int e = inc[m] >> 1, side = inc[m] & 1;
+        const hs_pg_rec R = rec[e];
+        const double *re = r + 3 * (size_t)e;
+        double J[3][3];
+        hs_pg_jac(R, side, J);
+        hs_pg_add_jtwj(J, R, D);
+        const double v[3] = { R.wx * re[0], R.wy * re[1], R.wt * re[2] };
+        hs_pg_add_jtv(J, v, g);
+    }
+}
+
+// rule 5 for one free node: q_n = lambda p_n + sum J^T t_e over the node's list.  t_e is formed again at each end of an edge, from
+// (p_i, p_j) in this order at either end: the same bits.  (p_n and the other end's entry are copied before use: a kernel then keeps
+// p_n in registers across the loop.)
+__host__ __device__ static __forceinline__ void hs_pg_node_apply(double lambda, const double *p, int n, const int32_t *off, const int32_t *inc, const hs_pg_rec *rec,
+                                                                 const int32_t *ij, double q[3])
+{
+    const double pn[3] = { p[3 * (size_t)n], p[3 * (size_t)n + 1], p[3 * (size_t)n + 2] };
+    for (int a = 0; a < 3; a++) q[a] = lambda * pn[a];
+    const int m1 = off[n + 1];
+    for (int m = off[n]; m < m1; m++) {
+        const int e = inc[m] >> 1, side = inc[m] & 1;
+        const hs_pg_rec R = rec[e];
+        const int i = ij[2 * (size_t)e], j = ij[2 * (size_t)e + 1];
+        const size_t o = (size_t)(side ? i : j);                           // the edge's other end
+        const double po[3] = { p[3 * o], p[3 * o + 1], p[3 * o + 2] };
+        double t[3], J[3][3];
+        if (side) hs_pg_edge_t(R, po, pn, t); else hs_pg_edge_t(R, pn, po, t);
+        hs_pg_jac(R, side, J);
+        hs_pg_add_jtv(J, t, q);
+    }
+}
+
 // rule 6: a field's term of one node
 __host__ __device__ static inline double hs_pg_dot3(const double u[3], const double v[3]) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
 
 // rule 7: what is tested before iteration k and inside it
 __host__ __device__ static inline bool hs_pg_converged(double rz, double rz0, double tol) { return rz <= (tol * tol) * rz0 || rz <= 0.0; }
 __host__ __device__ static inline bool hs_pg_breakdown(double pq) { return !(pq > 0.0); }
+// slamhip_pg_iter.stopped from the device's stop word.  No stop word after every launch the host had to enqueue: iteration n_cg was
+// reached, and the tolerance is tested first.
+__host__ __device__ static inline int32_t hs_pg_stopped(int32_t stop, double rz, double rz0, double tol)
+{
+    return stop ? stop - 1 : (hs_pg_converged(rz, rz0, tol) ? HS_PG_STOP_TOL : HS_PG_STOP_NCG);
+}
+
+// the end of an outer iteration: pose += x, theta wrapped by rule 2
+__host__ __device__ static inline void hs_pg_add_pose(double pose[3], const double x[3])
+{
+    for (int a = 0; a < 3; a++) pose[a] = pose[a] + x[a];
+    pose[2] = hs_pg_wrap(pose[2]);
+}
 
 // what slamhip_hs_pg_relax refuses of its spec
 static inline bool hs_pg_spec_ok(const slamhip_pg_spec *sp)

@@ -1,7 +1,10 @@
 // hs_pg.hip -- K19, the relaxation of a 2-D pose graph on the device: Gauss-Newton steps, each solved matrix-free by block-Jacobi
 // preconditioned conjugate gradients (slamhip_hs_pg_set, _pg_relax, _pg_get, _pg_residuals, _pg_clear, slamhip_debug_pg_relax, _pg_sum,
 // _sincos).  No reference counterpart.  Definition: include/slamhip.h (slamhip_hs_pg_relax); the arithmetic host and device share:
-// hs_pg.h.
+// hs_pg.h -- the per-node loops of rules 4 and 5 included, so a kernel and the host hook differ only in who walks the nodes.
+// K22 (hs_pg_tri.inc) and K26 (hs_pg_lm.inc) are the later parts of this translation unit.  The three share ONE PCG enqueue loop
+// (hs_pg_pcg), ONE "n_outer steps, final chi2, read-back" (hs_pg_relax_run) and ONE host definition (hs_pg_host_relax), each with the
+// preconditioner as an argument; they stand in hs_pg_tri.inc, behind K22's launch functions and host text, which they call.
 //
 // The graph lies in ONE device block: the poses, the fixed bytes, the edges (ij, z, w) and the node -> (edge, side) lists the host
 // builds by a counting sort that keeps the edge order (off[N + 1], inc[2 E], an entry edge << 1 | side), then what the kernels write.
@@ -10,8 +13,8 @@
 //  * k19_diag: a lane per node, rule 4 over the node's list, M; then rule 7's start (x, res, z, p) and the block sums of res . z.
 //  * k19_begin: ONE workgroup, once per outer iteration: chi2 and rz0 from the block sums, the state's reset.
 //  * k19_apply: a lane per node, rule 5 fused -- t_e is formed again at each end of an edge, the same bits --; block sums of p . q.
-//  * k19_step: every workgroup finishes rule 6's tree of p . q itself (k19_total), so alpha needs no launch of its own; the axpys,
-//    z = M res, block sums of res . z.
+//  * k19_step<true>: every workgroup finishes rule 6's tree of p . q itself (k19_total), so alpha needs no launch of its own; the
+//    axpys, z = M res, block sums of res . z.  k19_step<false> ends behind the axpys: what K22 launches ahead of its own solve.
 //  * k19_dir: every workgroup finishes the tree of res . z, beta, p = z + beta p; workgroup 0 stores rz and the count.
 //  * k19_update: pose += x, wrap; workgroup 0 writes the outer iteration's slamhip_pg_iter.
 // The stop word (k19_state.stop): set by workgroup 0 of k19_apply (tolerance) or k19_step (breakdown) from scalars that earlier launches
@@ -26,12 +29,9 @@
 #include <vector>
 
 #define K19_LANES HS_PG_BLOCK
-// Developer builds for the two timings of docs/EXPERIMENTS.md (tools/build_variant.py WORK <tag> -DK19_...=1); the same bits either way.
+// Developer build for a timing of docs/EXPERIMENTS.md (tools/build_variant.py WORK <tag> -DK19_SCALAR_LAUNCH=1); the same bits either way.
 #ifndef K19_SCALAR_LAUNCH
 #define K19_SCALAR_LAUNCH 0                // 1: alpha, beta and the stop word by a one-workgroup launch behind k19_apply and behind k19_step
-#endif
-#ifndef K19_SOA
-#define K19_SOA 0                          // 1: the node vectors x, res, z, p, q as three arrays of N doubles each
 #endif
 // the most PCG iterations enqueued between two reads of the stop word, whatever check_every says (no result depends on it)
 #define K19_MAX_BATCH 1024
@@ -98,14 +98,6 @@ __device__ static inline bool k19_stopped(const k19_state *st, int *stop_s)
 
 __device__ static inline void k19_load3(const double *a, int n, double v[3]) { v[0] = a[3 * (size_t)n]; v[1] = a[3 * (size_t)n + 1]; v[2] = a[3 * (size_t)n + 2]; }
 __device__ static inline void k19_store3(double *a, int n, const double v[3]) { a[3 * (size_t)n] = v[0]; a[3 * (size_t)n + 1] = v[1]; a[3 * (size_t)n + 2] = v[2]; }
-// a node vector's entry (x, res, z, p, q)
-#if K19_SOA
-__device__ static inline void k19_vload(const double *a, int n, int N, double v[3]) { v[0] = a[n]; v[1] = a[(size_t)N + n]; v[2] = a[2 * (size_t)N + n]; }
-__device__ static inline void k19_vstore(double *a, int n, int N, const double v[3]) { a[n] = v[0]; a[(size_t)N + n] = v[1]; a[2 * (size_t)N + n] = v[2]; }
-#else
-__device__ static inline void k19_vload(const double *a, int n, int, double v[3]) { k19_load3(a, n, v); }
-__device__ static inline void k19_vstore(double *a, int n, int, const double v[3]) { k19_store3(a, n, v); }
-#endif
 
 __global__ void __launch_bounds__(K19_LANES) k19_linearise(const k19_arg A)
 {
@@ -134,26 +126,16 @@ __global__ void __launch_bounds__(K19_LANES) k19_diag(const k19_arg A, double la
     const int n = (int)blockIdx.x * K19_LANES + (int)threadIdx.x;
     double term = 0.0;
     if (n < A.N) {
-        double D[6] = { lambda, 0.0, 0.0, lambda, 0.0, lambda }, g[3] = { 0.0, 0.0, 0.0 }, M[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+        double D[6], g[3] = { 0.0, 0.0, 0.0 }, M[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
         if (!A.fixed[n]) {
-            const int m1 = A.off[n + 1];
-            for (int m = A.off[n]; m < m1; m++) {
-                const int e = A.inc[m] >> 1, side = A.inc[m] & 1;
-                const hs_pg_rec R = A.rec[e];
-                double J[3][3], r[3];
-                hs_pg_jac(R, side, J);
-                hs_pg_add_jtwj(J, R, D);
-                k19_load3(A.r, e, r);
-                const double v[3] = { R.wx * r[0], R.wy * r[1], R.wt * r[2] };
-                hs_pg_add_jtv(J, v, g);
-            }
+            hs_pg_node_diag(lambda, n, A.off, A.inc, A.rec, A.r, D, g);
             (void)hs_pg_inv(D, M);
         }
         for (int m = 0; m < 6; m++) A.M[6 * (size_t)n + m] = M[m];
         const double x[3] = { 0.0, 0.0, 0.0 }, res[3] = { -g[0], -g[1], -g[2] };
         double zv[3];
         hs_pg_mul(M, res, zv);
-        k19_vstore(A.x, n, A.N, x); k19_vstore(A.res, n, A.N, res); k19_vstore(A.zv, n, A.N, zv); k19_vstore(A.p, n, A.N, zv);
+        k19_store3(A.x, n, x); k19_store3(A.res, n, res); k19_store3(A.zv, n, zv); k19_store3(A.p, n, zv);
         term = hs_pg_dot3(res, zv);
     }
     const double sum = k19_block_sum(term, lds);
@@ -191,28 +173,17 @@ __global__ void __launch_bounds__(K19_LANES) k19_apply(const k19_arg A, int k, d
     double term = 0.0;
     if (n < A.N) {
         double pn[3], q[3] = { 0.0, 0.0, 0.0 };
-        k19_vload(A.p, n, A.N, pn);
-        if (!A.fixed[n]) {
-            for (int a = 0; a < 3; a++) q[a] = lambda * pn[a];
-            const int m1 = A.off[n + 1];
-            for (int m = A.off[n]; m < m1; m++) {
-                const int e = A.inc[m] >> 1, side = A.inc[m] & 1;
-                const hs_pg_rec R = A.rec[e];
-                const int2 ij = A.ij[e];
-                double po[3], t[3], J[3][3];
-                k19_vload(A.p, side ? ij.x : ij.y, A.N, po);
-                if (side) hs_pg_edge_t(R, po, pn, t); else hs_pg_edge_t(R, pn, po, t);
-                hs_pg_jac(R, side, J);
-                hs_pg_add_jtv(J, t, q);
-            }
-        }
-        k19_vstore(A.q, n, A.N, q);
+        k19_load3(A.p, n, pn);
+        if (!A.fixed[n]) hs_pg_node_apply(lambda, A.p, n, A.off, A.inc, A.rec, (const int32_t *)A.ij, q);
+        k19_store3(A.q, n, q);
         term = hs_pg_dot3(pn, q);
     }
     const double sum = k19_block_sum(term, lds);
     if (threadIdx.x == 0) A.part_a[blockIdx.x] = sum;
 }
 
+// JACOBI: with rule 7's z = M res and the block sums of res . z; without, another preconditioner's launches form them (K22's solve)
+template <bool JACOBI>
 __global__ void __launch_bounds__(K19_LANES) k19_step(const k19_arg A, int k)
 {
     __shared__ double lds[K19_LANES], lds2[64];
@@ -232,13 +203,17 @@ __global__ void __launch_bounds__(K19_LANES) k19_step(const k19_arg A, int k)
     double term = 0.0;
     if (n < A.N) {
         double x[3], res[3], p[3], q[3], M[6], zv[3];
-        k19_vload(A.x, n, A.N, x); k19_vload(A.res, n, A.N, res); k19_vload(A.p, n, A.N, p); k19_vload(A.q, n, A.N, q);
-        for (int m = 0; m < 6; m++) M[m] = A.M[6 * (size_t)n + m];
+        k19_load3(A.x, n, x); k19_load3(A.res, n, res); k19_load3(A.p, n, p); k19_load3(A.q, n, q);
+        if (JACOBI) for (int m = 0; m < 6; m++) M[m] = A.M[6 * (size_t)n + m];
         for (int a = 0; a < 3; a++) { x[a] = x[a] + alpha * p[a]; res[a] = res[a] - alpha * q[a]; }
-        hs_pg_mul(M, res, zv);
-        k19_vstore(A.x, n, A.N, x); k19_vstore(A.res, n, A.N, res); k19_vstore(A.zv, n, A.N, zv);
-        term = hs_pg_dot3(res, zv);
+        if (JACOBI) hs_pg_mul(M, res, zv);
+        k19_store3(A.x, n, x); k19_store3(A.res, n, res);
+        if (JACOBI) {
+            k19_store3(A.zv, n, zv);
+            term = hs_pg_dot3(res, zv);
+        }
     }
+    if (!JACOBI) return;
     const double sum = k19_block_sum(term, lds);
     if (threadIdx.x == 0) A.part_b[blockIdx.x] = sum;
 }
@@ -257,9 +232,9 @@ __global__ void __launch_bounds__(K19_LANES) k19_dir(const k19_arg A, int k)
     const int n = (int)blockIdx.x * K19_LANES + (int)threadIdx.x;
     if (n < A.N) {
         double p[3], zv[3];
-        k19_vload(A.p, n, A.N, p); k19_vload(A.zv, n, A.N, zv);
+        k19_load3(A.p, n, p); k19_load3(A.zv, n, zv);
         for (int a = 0; a < 3; a++) p[a] = zv[a] + beta * p[a];
-        k19_vstore(A.p, n, A.N, p);
+        k19_store3(A.p, n, p);
     }
 #if !K19_SCALAR_LAUNCH
     if (blockIdx.x == 0 && threadIdx.x == 0) { A.st->rz[(k + 1) & 1] = rzn; A.st->iters = k + 1; }   // (this launch reads rz[k & 1] alone)
@@ -296,18 +271,15 @@ __global__ void __launch_bounds__(K19_LANES) k19_update(const k19_arg A, double 
     const int n = (int)blockIdx.x * K19_LANES + (int)threadIdx.x;
     if (n < A.N && !A.fixed[n]) {
         double pose[3], x[3];
-        k19_load3(A.pose, n, pose); k19_vload(A.x, n, A.N, x);
-        for (int a = 0; a < 3; a++) pose[a] = pose[a] + x[a];
-        pose[2] = hs_pg_wrap(pose[2]);
+        k19_load3(A.pose, n, pose); k19_load3(A.x, n, x);
+        hs_pg_add_pose(pose, x);
         k19_store3(A.pose, n, pose);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         const k19_state *S = A.st;                                         // (read in place: a copy indexed by iters would be put into LDS)
         slamhip_pg_iter I;
         I.chi2 = S->chi2; I.rz0 = S->rz0; I.cg_iters = S->iters; I.rz = S->rz[I.cg_iters & 1];
-        // (no stop word after every launch the host had to enqueue: iteration n_cg was reached; the tolerance is tested first)
-        const int stop = S->stop;
-        I.stopped = stop ? stop - 1 : (hs_pg_converged(I.rz, I.rz0, tol) ? HS_PG_STOP_TOL : HS_PG_STOP_NCG);
+        I.stopped = hs_pg_stopped(S->stop, I.rz, I.rz0, tol);
         A.iters[outer] = I;
     }
 }
@@ -389,6 +361,13 @@ static void hs_pg_lists(int N, const int32_t *ij, int E, int32_t *off, int32_t *
         for (int side = 0; side < 2; side++) inc[at[(size_t)ij[2 * (size_t)e + side]]++] = (e << 1) | side;
 }
 
+// the fixed bytes, N of them: the caller's as 0 / 1, or node 0 alone
+static void hs_pg_fixed_bytes(const uint8_t *fixed, int N, unsigned char *out)
+{
+    if (fixed) for (int n = 0; n < N; n++) out[n] = fixed[n] ? 1 : 0;
+    else { memset(out, 0, (size_t)N); out[0] = 1; }
+}
+
 static inline size_t hs_pg_al(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static int32_t hs_pg_need(const slamhip_hs *hs, const char *who)
@@ -435,8 +414,7 @@ extern "C" int32_t slamhip_hs_pg_set(slamhip_hs *hs, const double *poses, const 
     SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, std::max(in_bytes, 32 * e), HS_MEM_PINNED, "pose graph"));
     unsigned char *h = g->h_io, *d = g->d_blob;
     memcpy(h + o_pose, poses, 24 * n);
-    if (fixed) for (size_t i = 0; i < n; i++) h[o_fixed + i] = fixed[i] ? 1 : 0;
-    else { memset(h + o_fixed, 0, n); h[o_fixed] = 1; }
+    hs_pg_fixed_bytes(fixed, N, h + o_fixed);
     if (E) { memcpy(h + o_ij, ij, 8 * e); memcpy(h + o_z, z, 24 * e); memcpy(h + o_w, w, 24 * e); }
     hs_pg_lists(N, ij, E, (int32_t *)(h + o_off), (int32_t *)(h + o_inc));
     SH_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -457,49 +435,13 @@ extern "C" int32_t slamhip_hs_pg_set(slamhip_hs *hs, const double *poses, const 
 
 #define K19_LAUNCH(kernel, wgs, ...) do { hipLaunchKernelGGL(kernel, dim3((unsigned)(wgs)), dim3(K19_LANES), 0, st, __VA_ARGS__); SH_HIP(hipGetLastError()); } while (0)
 
+// n_outer Gauss-Newton steps, the final chi2, the read-back: behind K22's launch functions in hs_pg_tri.inc, which it calls with tri
+static int32_t hs_pg_relax_run(slamhip_hs *hs, const slamhip_pg_spec *spec, bool tri, const char *who, slamhip_pg_iter *out_iters, double *out_chi2_final);
+
 extern "C" int32_t slamhip_hs_pg_relax(slamhip_hs *hs, const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final)
 {
     SH_CHECK_ARG(hs && spec && out_iters && out_chi2_final);
-    SH_TRY(hs_pg_check_spec(spec));
-    SH_TRY(hs_pg_need(hs, "pose graph relax"));
-    hs_pg *g = hs->pg;
-    const k19_arg &A = g->A;
-    hipStream_t st = hs->ctx->stream;
-    SH_TRY(hs_call_begin(hs));
-    const size_t out_bytes = sizeof(slamhip_pg_iter) * (size_t)spec->n_outer;
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, out_bytes + 8 + sizeof(k19_state), HS_MEM_PINNED, "pose graph relax"));
-    k19_state *h_st = (k19_state *)(g->h_io + out_bytes + 8);
-    for (int outer = 0; outer < spec->n_outer; outer++) {
-        K19_LAUNCH(k19_linearise, A.PE, A);
-        K19_LAUNCH(k19_diag, A.PN, A, spec->lambda);
-        K19_LAUNCH(k19_begin, 1, A, 0);
-        for (int k = 0; k < spec->n_cg;) {
-            const int k1 = (int)std::min<int64_t>((int64_t)k + std::min(spec->check_every, K19_MAX_BATCH), spec->n_cg);
-            for (; k < k1; k++) {
-                K19_LAUNCH(k19_apply, A.PN, A, k, spec->lambda, spec->tol);
-#if K19_SCALAR_LAUNCH
-                K19_LAUNCH(k19_scal_a, 1, A, k);
-#endif
-                K19_LAUNCH(k19_step, A.PN, A, k);
-#if K19_SCALAR_LAUNCH
-                K19_LAUNCH(k19_scal_b, 1, A, k);
-#endif
-                K19_LAUNCH(k19_dir, A.PN, A, k);
-            }
-            SH_HIP(hipMemcpyAsync(h_st, A.st, sizeof(k19_state), hipMemcpyDeviceToHost, st));
-            SH_TRY(hs_call_finish(hs));                                    // (the stop word, between batches)
-            if (h_st->stop) break;
-        }
-        K19_LAUNCH(k19_update, A.PN, A, spec->tol, outer);
-    }
-    K19_LAUNCH(k19_linearise, A.PE, A);
-    K19_LAUNCH(k19_begin, 1, A, 1);
-    SH_HIP(hipMemcpyAsync(g->h_io, A.iters, out_bytes, hipMemcpyDeviceToHost, st));
-    SH_HIP(hipMemcpyAsync(g->h_io + out_bytes, A.final_chi2, 8, hipMemcpyDeviceToHost, st));
-    SH_TRY(hs_call_finish(hs));
-    memcpy(out_iters, g->h_io, out_bytes);
-    memcpy(out_chi2_final, g->h_io + out_bytes, 8);
-    return SLAMHIP_OK;
+    return hs_pg_relax_run(hs, spec, false, "pose graph relax", out_iters, out_chi2_final);
 }
 
 extern "C" int32_t slamhip_hs_pg_get(slamhip_hs *hs, double *poses, int32_t N)
@@ -548,6 +490,16 @@ extern "C" int32_t slamhip_hs_pg_clear(slamhip_hs *hs)
 }
 
 // ---- CPU-side test hooks: hs_pg.h -- the text the kernels run -- in plain loops ------------------------------------------------------
+// what slamhip_hs_pg_set makes of a graph beside its arrays: the node -> (edge, side) lists and the fixed bytes
+struct hs_pg_host_lists { std::vector<int32_t> off, inc; std::vector<unsigned char> fx; };
+
+static void hs_pg_host_lists_init(hs_pg_host_lists &G, const uint8_t *fixed, int N, const int32_t *ij, int E)
+{
+    G.off.resize((size_t)N + 1); G.inc.resize(2 * (size_t)E + 1); G.fx.resize((size_t)N);
+    hs_pg_lists(N, ij, E, G.off.data(), G.inc.data());
+    hs_pg_fixed_bytes(fixed, N, G.fx.data());
+}
+
 // rule 3 over every edge -> chi2 by rule 6
 static double hs_pg_host_linearise(const double *pose, const int32_t *ij, const double *z, const double *w, int E, hs_pg_rec *rec, double *r, double *tmp)
 {
@@ -564,91 +516,10 @@ static double hs_pg_host_dot(const double *u, const double *v, int N, double *tm
     return hs_pg_tree_sum(tmp, (size_t)N);
 }
 
-// the definition over a graph and a spec that have been checked (K26's hook takes single steps through it, with its own weights)
-static void hs_pg_host_relax(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
-                             const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
-{
-    const size_t n3 = 3 * (size_t)N, pad = HS_PG_BLOCK;
-    std::vector<int32_t> off((size_t)N + 1), inc(2 * (size_t)E + 1);
-    hs_pg_lists(N, ij, E, off.data(), inc.data());
-    std::vector<unsigned char> fx((size_t)N, 0);
-    if (fixed) for (int n = 0; n < N; n++) fx[(size_t)n] = fixed[n] ? 1 : 0;
-    else fx[0] = 1;
-    std::vector<hs_pg_rec> rec((size_t)E + 1);
-    std::vector<double> r(3 * (size_t)E + 3), tmp((size_t)std::max(N, E) + pad), M(6 * (size_t)N), x(n3), res(n3), zv(n3), p(n3), q(n3);
-    const double lambda = spec->lambda, tol = spec->tol;
-    for (int outer = 0; outer < spec->n_outer; outer++) {
-        slamhip_pg_iter I;
-        I.chi2 = hs_pg_host_linearise(poses, ij, z, w, E, rec.data(), r.data(), tmp.data());
-        for (int n = 0; n < N; n++) {                                      // rule 4 and rule 7's start
-            double D[6] = { lambda, 0.0, 0.0, lambda, 0.0, lambda }, g[3] = { 0.0, 0.0, 0.0 }, Mn[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-            if (!fx[(size_t)n]) {
-                for (int m = off[(size_t)n]; m < off[(size_t)n + 1]; m++) {
-                    const int e = inc[(size_t)m] >> 1, side = inc[(size_t)m] & 1;
-                    const hs_pg_rec &R = rec[(size_t)e];
-                    double J[3][3];
-                    hs_pg_jac(R, side, J);
-                    hs_pg_add_jtwj(J, R, D);
-                    const double *re = r.data() + 3 * (size_t)e;
-                    const double v[3] = { R.wx * re[0], R.wy * re[1], R.wt * re[2] };
-                    hs_pg_add_jtv(J, v, g);
-                }
-                (void)hs_pg_inv(D, Mn);
-            }
-            for (int m = 0; m < 6; m++) M[6 * (size_t)n + m] = Mn[m];
-            double *xn = x.data() + 3 * (size_t)n, *rn = res.data() + 3 * (size_t)n, *zn = zv.data() + 3 * (size_t)n, *pn = p.data() + 3 * (size_t)n;
-            for (int a = 0; a < 3; a++) { xn[a] = 0.0; rn[a] = -g[a]; }
-            hs_pg_mul(Mn, rn, zn);
-            for (int a = 0; a < 3; a++) pn[a] = zn[a];
-        }
-        double rz = hs_pg_host_dot(res.data(), zv.data(), N, tmp.data());
-        I.rz0 = rz;
-        int k = 0, stopped;
-        for (;; k++) {
-            if (hs_pg_converged(rz, I.rz0, tol)) { stopped = HS_PG_STOP_TOL; break; }
-            if (k == spec->n_cg) { stopped = HS_PG_STOP_NCG; break; }
-            for (int n = 0; n < N; n++) {                                  // rule 5
-                const double *pn = p.data() + 3 * (size_t)n;
-                double *qn = q.data() + 3 * (size_t)n;
-                qn[0] = qn[1] = qn[2] = 0.0;
-                if (fx[(size_t)n]) continue;
-                for (int a = 0; a < 3; a++) qn[a] = lambda * pn[a];
-                for (int m = off[(size_t)n]; m < off[(size_t)n + 1]; m++) {
-                    const int e = inc[(size_t)m] >> 1, side = inc[(size_t)m] & 1;
-                    const hs_pg_rec &R = rec[(size_t)e];
-                    double t[3], J[3][3];
-                    hs_pg_edge_t(R, p.data() + 3 * (size_t)ij[2 * (size_t)e], p.data() + 3 * (size_t)ij[2 * (size_t)e + 1], t);
-                    hs_pg_jac(R, side, J);
-                    hs_pg_add_jtv(J, t, qn);
-                }
-            }
-            const double pq = hs_pg_host_dot(p.data(), q.data(), N, tmp.data());
-            if (hs_pg_breakdown(pq)) { stopped = HS_PG_STOP_BREAKDOWN; break; }
-            const double alpha = rz / pq;
-            for (int n = 0; n < N; n++) {
-                double *xn = x.data() + 3 * (size_t)n, *rn = res.data() + 3 * (size_t)n;
-                const double *pn = p.data() + 3 * (size_t)n, *qn = q.data() + 3 * (size_t)n;
-                for (int a = 0; a < 3; a++) { xn[a] = xn[a] + alpha * pn[a]; rn[a] = rn[a] - alpha * qn[a]; }
-                hs_pg_mul(M.data() + 6 * (size_t)n, rn, zv.data() + 3 * (size_t)n);
-            }
-            const double rzn = hs_pg_host_dot(res.data(), zv.data(), N, tmp.data());
-            const double beta = rzn / rz;
-            for (size_t i = 0; i < n3; i++) p[i] = zv[i] + beta * p[i];
-            rz = rzn;
-        }
-        I.rz = rz; I.cg_iters = k; I.stopped = stopped;
-        out_iters[outer] = I;
-        for (int n = 0; n < N; n++) {
-            if (fx[(size_t)n]) continue;
-            double *pn = poses + 3 * (size_t)n;
-            for (int a = 0; a < 3; a++) pn[a] = pn[a] + x[3 * (size_t)n + a];
-            pn[2] = hs_pg_wrap(pn[2]);
-        }
-    }
-    *out_chi2_final = hs_pg_host_linearise(poses, ij, z, w, E, rec.data(), r.data(), tmp.data());
-    if (out_r && E) memcpy(out_r, r.data(), 24 * (size_t)E);
-    if (out_chi2) for (int e = 0; e < E; e++) out_chi2[e] = rec[(size_t)e].chi2;
-}
+// the definition of K19 and of K22 over a graph and a spec that have been checked: behind K22's host text in hs_pg_tri.inc, which it
+// runs with tri
+static void hs_pg_host_relax(bool tri, double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
+                             const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2);
 
 extern "C" int32_t slamhip_debug_pg_relax(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
                                           const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
@@ -656,7 +527,7 @@ extern "C" int32_t slamhip_debug_pg_relax(double *poses, const uint8_t *fixed, i
     SH_CHECK_ARG(spec && out_iters && out_chi2_final);
     SH_TRY(hs_pg_check_spec(spec));
     SH_TRY(hs_pg_check_graph(poses, fixed, N, ij, z, w, E));
-    hs_pg_host_relax(poses, fixed, N, ij, z, w, E, spec, out_iters, out_chi2_final, out_r, out_chi2);
+    hs_pg_host_relax(false, poses, fixed, N, ij, z, w, E, spec, out_iters, out_chi2_final, out_r, out_chi2);
     return SLAMHIP_OK;
 }
 

@@ -1,8 +1,9 @@
 // hs_pg_lm.inc -- K26, the damped (Levenberg-Marquardt) and robust relaxation of the pose graph: every step of K19 / K22 becomes an
 // ATTEMPT that is taken only if it lowers the cost, lambda moves with the outcome, and an edge's weight is scaled by a rational robust
-// factor (slamhip_hs_pg_relax_lm, slamhip_debug_pg_relax_lm).  The last part of hs_pg.hip's translation unit: it launches the k19_* and
-// k22_* kernels as they are -- with k19_arg.w pointing at the scaled weights -- and shares their device helpers.  Definition:
-// include/slamhip.h, rules R1 - R4; the arithmetic host and device share: hs_pg_lm.h.
+// factor (slamhip_hs_pg_relax_lm, slamhip_debug_pg_relax_lm).  The last part of hs_pg.hip's translation unit: an attempt's PCG is the
+// unit's driver (hs_pg_pcg, hs_pg_tri.inc) over a k19_arg whose w points at the scaled weights, the hook's is a single step of the
+// unit's host definition (hs_pg_host_relax) over the same weights.  Definition: include/slamhip.h, rules R1 - R4; the arithmetic host
+// and device share: hs_pg_lm.h, and hs_pg.h for the stopped code and the "pose + x" that k26_decide and k26_trial need.
 //  * k26_weigh<0>: a lane per edge, rule R1 at the poses: c_e, f_e, w_eff into the second weight array, the block sums of rho_e.
 //  * k26_weigh<1>: the same lane at the trial poses, the cost alone.
 //  * k26_trial: a lane per node, trial = pose + x, theta wrapped; a fixed node's trial is its pose.
@@ -56,9 +57,8 @@ __global__ void __launch_bounds__(K19_LANES) k26_trial(const k19_arg A, const k2
     k19_load3(A.pose, n, pose);
     if (!A.fixed[n]) {
         double x[3];
-        k19_vload(A.x, n, A.N, x);
-        for (int a = 0; a < 3; a++) pose[a] = pose[a] + x[a];
-        pose[2] = hs_pg_wrap(pose[2]);
+        k19_load3(A.x, n, x);
+        hs_pg_add_pose(pose, x);
     }
     k19_store3(L.trial, n, pose);
 }
@@ -79,8 +79,7 @@ __global__ void __launch_bounds__(K19_LANES) k26_decide(const k19_arg A, const k
         slamhip_pg_lm_iter I;
         I.F = F; I.F_trial = Ft; I.lambda = lambda;
         I.rz0 = S->rz0; I.cg_iters = S->iters; I.rz = S->rz[I.cg_iters & 1];
-        const int stop = S->stop;                                          // (as k19_update forms it)
-        I.stopped = stop ? stop - 1 : (hs_pg_converged(I.rz, I.rz0, tol) ? HS_PG_STOP_TOL : HS_PG_STOP_NCG);
+        I.stopped = hs_pg_stopped(S->stop, I.rz, I.rz0, tol);
         I.accepted = hs_lm_accept(F, Ft) ? 1 : 0;
         I.reserved[0] = I.reserved[1] = I.reserved[2] = 0;
         L.iters[outer] = I;
@@ -134,44 +133,12 @@ static int32_t hs_lm_blocks(hs_pg *g, const char *who, k26_arg *L)
     return SLAMHIP_OK;
 }
 
-// rules 3 - 7 (tri: T1 - T5) up to the pose update, over A's weights: what slamhip_hs_pg_relax / _relax_tri enqueue per outer iteration
-static int32_t hs_lm_solve(slamhip_hs *hs, hs_pg *g, const k19_arg &A, const slamhip_pg_lm_spec *spec, double lambda, k19_state *h_st)
-{
-    hipStream_t st = hs->ctx->stream;
-    const bool tri = spec->precond == HS_LM_TRI;
-    const k22_io first = { A.res, A.zv, A.p, A.part_b, nullptr }, io = { A.res, A.zv, nullptr, A.part_b, A.st };
-    if (tri) {
-        SH_TRY(hs_tri_factor(A, g->T, st, lambda, 1));
-        SH_TRY(hs_tri_solve(g, st, first));
-    } else {
-        K19_LAUNCH(k19_diag, A.PN, A, lambda);
-    }
-    K19_LAUNCH(k19_begin, 1, A, 0);
-    for (int k = 0; k < spec->n_cg;) {
-        const int k1 = (int)std::min<int64_t>((int64_t)k + std::min(spec->check_every, K19_MAX_BATCH), spec->n_cg);
-        for (; k < k1; k++) {
-            K19_LAUNCH(k19_apply, A.PN, A, k, lambda, spec->tol);
-            if (tri) {
-                K19_LAUNCH(k22_axpy, A.PN, A, k);
-                SH_TRY(hs_tri_solve(g, st, io));
-            } else {
-                K19_LAUNCH(k19_step, A.PN, A, k);
-            }
-            K19_LAUNCH(k19_dir, A.PN, A, k);
-        }
-        SH_HIP(hipMemcpyAsync(h_st, A.st, sizeof(k19_state), hipMemcpyDeviceToHost, st));
-        SH_TRY(hs_call_finish(hs));                                        // (the stop word, between batches)
-        if (h_st->stop) break;
-    }
-    return SLAMHIP_OK;
-}
-
 extern "C" int32_t slamhip_hs_pg_relax_lm(slamhip_hs *hs, const slamhip_pg_lm_spec *spec, const uint8_t *robust, slamhip_pg_lm_iter *out_iters, int32_t *out_n,
                                           double *out_F_final, double *out_f)
 {
     SH_CHECK_ARG(hs && spec && out_iters && out_n && out_F_final);
-#if K19_SCALAR_LAUNCH || K19_SOA
-    SH_FAIL(SLAMHIP_ERR_STATE, "K26 is not part of the K19_SCALAR_LAUNCH / K19_SOA developer builds");
+#if K19_SCALAR_LAUNCH
+    SH_FAIL(SLAMHIP_ERR_STATE, "K26 is not part of the K19_SCALAR_LAUNCH developer build");
 #endif
     SH_TRY(hs_lm_check_spec(spec));
     SH_TRY(hs_pg_need(hs, "pose graph relax (lm)"));
@@ -205,7 +172,7 @@ extern "C" int32_t slamhip_hs_pg_relax_lm(slamhip_hs *hs, const slamhip_pg_lm_sp
             K19_LAUNCH(k26_weigh<0>, A.PE, A, L);
             K19_LAUNCH(k19_linearise, A.PE, AL);
         }
-        SH_TRY(hs_lm_solve(hs, g, AL, spec, lambda, h_st));
+        SH_TRY(hs_pg_pcg(hs, g, AL, spec->precond == HS_LM_TRI, lambda, spec->n_cg, spec->check_every, spec->tol, h_st));
         K19_LAUNCH(k26_trial, A.PN, A, L);
         K19_LAUNCH(k26_weigh<1>, A.PE, A, L);
         K19_LAUNCH(k26_decide, 1, A, L, lambda, spec->tol, spec->ftol, n, 0);
@@ -266,7 +233,7 @@ extern "C" int32_t slamhip_debug_pg_relax_lm(double *poses, const uint8_t *fixed
         slamhip_pg_iter step;
         double chi2_w;
         one.lambda = lambda;
-        (spec->precond == HS_LM_TRI ? hs_tri_host_relax : hs_pg_host_relax)(trial.data(), fixed, N, ij, z, w_eff.data(), E, &one, &step, &chi2_w, nullptr, nullptr);
+        hs_pg_host_relax(spec->precond == HS_LM_TRI, trial.data(), fixed, N, ij, z, w_eff.data(), E, &one, &step, &chi2_w, nullptr, nullptr);
         const double Ft = hs_lm_host_weigh(trial.data(), ij, z, w, E, robust, spec->kind, spec->phi, nullptr, nullptr, tmp.data());
         slamhip_pg_lm_iter I;
         I.F = F; I.F_trial = Ft; I.lambda = lambda;

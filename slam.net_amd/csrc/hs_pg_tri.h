@@ -1,5 +1,6 @@
 // hs_pg_tri.h -- the arithmetic of the odometry-chain preconditioner of the pose-graph relaxation (K22, hs_pg_tri.inc) that host and
-// device share: the kernels k22_* and the test hooks slamhip_debug_pg_relax_tri / _pg_tri_apply run this text.  Definition:
+// device share: the kernels k22_* and the test hooks slamhip_debug_pg_relax_tri / _pg_tri_apply run this text, down to rule T2's loop
+// over a node's list (hs_tri_node_coupling) and rule T3's block with its choice of neighbours (hs_tri_reduce_block).  Definition:
 // include/slamhip.h, slamhip_hs_pg_relax_tri, rules T1 - T5.  Binary64 + - * / only, one rounding per operation (the build has
 // -ffp-contract=off); every expression is parenthesised as the definition writes it.
 #pragma once
@@ -45,6 +46,29 @@ __host__ __device__ static inline void hs_tri_add_coupling(const double Jn[3][3]
             U[3 * a + b] = U[3 * a + b] + (((Jn[0][a] * R.wx) * Jm[0][b] + (Jn[1][a] * R.wy) * Jm[1][b]) + (Jn[2][a] * R.wt) * Jm[2][b]);
 }
 
+// rule T2 for one node: U_n over the edges of the node's list (hs_pg.h's lists) that join n and n + 1; +0 unless both are live
+__host__ __device__ static __forceinline__ void hs_tri_node_coupling(int n, int N, const unsigned char *live, const int32_t *off, const int32_t *inc,
+                                                                     const hs_pg_rec *rec, const int32_t *ij, double U[9])
+{
+    for (int m = 0; m < 9; m++) U[m] = 0.0;
+    if (!(n + 1 < N && live[n] && live[n + 1])) return;
+    const int m1 = off[n + 1];
+    for (int m = off[n]; m < m1; m++) {
+        const int e = inc[m] >> 1, side = inc[m] & 1;
+        const int i = ij[2 * (size_t)e], j = ij[2 * (size_t)e + 1];
+        if ((side ? i : j) != n + 1) continue;
+        const hs_pg_rec R = rec[e];
+        double Jn[3][3], Jm[3][3];
+        hs_pg_jac(R, side, Jn);
+        hs_pg_jac(R, side ^ 1, Jm);
+        hs_tri_add_coupling(Jn, Jm, R, U);
+    }
+}
+
+// entry i of an array of n doubles per entry (D, P: 6; U: 9)
+__host__ __device__ static inline void hs_tri_load(const double *a, size_t i, int n, double *v) { for (int m = 0; m < n; m++) v[m] = a[(size_t)n * i + m]; }
+__host__ __device__ static inline void hs_tri_store(double *a, size_t i, int n, const double *v) { for (int m = 0; m < n; m++) a[(size_t)n * i + m] = v[m]; }
+
 // rule T3: W = P X (xt false) or W = P X^T (xt true)
 __host__ __device__ static inline void hs_tri_px(const double P[6], const double X[9], bool xt, double W[9])
 {
@@ -81,6 +105,23 @@ __host__ __device__ static inline void hs_tri_reduce(const double Dk[6], bool ha
     } else {
         for (int m = 0; m < 9; m++) Uo[m] = 0.0;
     }
+}
+
+// rule T3 for block m of level l + 1 over the plan's arrays: the neighbours that are there, D', U' and P' = D'^-1
+__host__ __device__ static inline void hs_tri_reduce_block(const hs_tri_plan &T, int l, int m)
+{
+    const int n = T.n[l], k = 2 * m;
+    const size_t o = (size_t)T.off[l] + (size_t)k;
+    const bool have_l = k >= 1, have_r = k + 1 < n, have_n = k + 2 < n;
+    double Dk[6], Ul[9], Pl[6], Uk[9], Pr[6], Un[9], Dn[6], Uo[9], Pn[6];
+    hs_tri_load(T.D, o, 6, Dk);
+    if (have_l) { hs_tri_load(T.U, o - 1, 9, Ul); hs_tri_load(T.P, o - 1, 6, Pl); }
+    if (have_r) { hs_tri_load(T.U, o, 9, Uk); hs_tri_load(T.P, o + 1, 6, Pr); }
+    if (have_n) hs_tri_load(T.U, o + 1, 9, Un);
+    hs_tri_reduce(Dk, have_l, Ul, Pl, have_r, Uk, Pr, have_n, Un, Dn, Uo);
+    (void)hs_pg_inv(Dn, Pn);
+    const size_t o1 = (size_t)T.off[l + 1] + (size_t)m;
+    hs_tri_store(T.D, o1, 6, Dn); hs_tri_store(T.U, o1, 9, Uo); hs_tri_store(T.P, o1, 6, Pn);
 }
 
 // rule T4: v = v - U^T y (the neighbour below: U = U_{k-1}) and v = v - U y (the neighbour above: U = U_k)

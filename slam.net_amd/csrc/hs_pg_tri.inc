@@ -1,13 +1,14 @@
 // hs_pg_tri.inc -- K22, the odometry-chain preconditioner of the pose-graph relaxation: PCG with z = T^-1 res, T the block-tridiagonal
 // part of H, factorised and solved by block cyclic reduction (slamhip_hs_pg_relax_tri, _pg_tri_apply, slamhip_debug_pg_relax_tri,
-// _pg_tri_apply).  The last part of hs_pg.hip's translation unit: it launches k19_linearise, k19_begin, k19_apply, k19_dir and
-// k19_update as they are and shares their device helpers.  Definition: include/slamhip.h, rules T1 - T5; the arithmetic host and
-// device share: hs_pg_tri.h.
+// _pg_tri_apply).  The second part of hs_pg.hip's translation unit: it launches k19_linearise, k19_begin, k19_apply, k19_step<false>,
+// k19_dir and k19_update as they are and shares their device helpers.  Definition: include/slamhip.h, rules T1 - T5; the arithmetic
+// host and device share: hs_pg_tri.h, the per-node loop of rule T2 and rule T3's choice of neighbours included.  Behind K22's launch
+// functions stand the unit's PCG driver and relax call (hs_pg_pcg, hs_pg_relax_run), behind its host text the unit's host definition
+// (hs_pg_host_relax): K19, K22 and K26 all go through them, with the preconditioner as an argument.
 //  * k22_diag: a lane per node, rule 4's D_n and g_n over the node's list, rule T1, P = D^-1; for PCG x = 0 and res = -g.
 //  * k22_coupling: a lane per node, rule T2 over the same list.
 //  * k22_reduce: one launch per level with more than S blocks, a lane per block of the NEXT level, rule T3.
 //  * k22_factor_tail: ONE workgroup, every level from the first with at most S blocks on, a barrier between levels.
-//  * k22_axpy: k19_step without its preconditioner: every workgroup finishes rule 6's tree of p . q, alpha, the axpys.
 //  * k22_forward / k22_backward: one launch per level with more than S blocks, rule T4; level 0's k22_backward stores z and the block
 //    sums of res . z.
 //  * k22_solve_tail: ONE workgroup: forward, last level and backward of every level with at most S blocks, the right-hand sides in LDS;
@@ -17,38 +18,25 @@
 
 static_assert(3 * (2 * HS_TRI_TAIL + 32) * sizeof(double) + (K19_LANES + 64) * sizeof(double) + 64 <= 65536, "the tail's LDS");
 
-__device__ static inline void k22_load(const double *a, size_t i, int n, double *v) { for (int m = 0; m < n; m++) v[m] = a[(size_t)n * i + m]; }
-__device__ static inline void k22_store(double *a, size_t i, int n, const double *v) { for (int m = 0; m < n; m++) a[(size_t)n * i + m] = v[m]; }
-
 __global__ void __launch_bounds__(K19_LANES) k22_diag(const k19_arg A, const hs_tri_plan T, double lambda, int start)
 {
     const int n = (int)blockIdx.x * K19_LANES + (int)threadIdx.x;
     if (n >= A.N) return;
-    double D[6] = { lambda, 0.0, 0.0, lambda, 0.0, lambda }, g[3] = { 0.0, 0.0, 0.0 }, P[6];
+    double D[6], g[3] = { 0.0, 0.0, 0.0 }, P[6];
     bool live = false;
     if (!A.fixed[n]) {
-        const int m1 = A.off[n + 1];
-        for (int m = A.off[n]; m < m1; m++) {
-            const int e = A.inc[m] >> 1, side = A.inc[m] & 1;
-            const hs_pg_rec R = A.rec[e];
-            double J[3][3], r[3];
-            hs_pg_jac(R, side, J);
-            hs_pg_add_jtwj(J, R, D);
-            k19_load3(A.r, e, r);
-            const double v[3] = { R.wx * r[0], R.wy * r[1], R.wt * r[2] };
-            hs_pg_add_jtv(J, v, g);
-        }
+        hs_pg_node_diag(lambda, n, A.off, A.inc, A.rec, A.r, D, g);
         live = hs_pg_inv(D, P);
     }
     if (!live) {                                                           // rule T1: the identity, and g = 0 (fixed, or no edge at all)
         D[0] = D[3] = D[5] = 1.0; D[1] = D[2] = D[4] = 0.0;
         for (int m = 0; m < 6; m++) P[m] = D[m];
     }
-    k22_store(T.D, (size_t)n, 6, D); k22_store(T.P, (size_t)n, 6, P);
+    hs_tri_store(T.D, (size_t)n, 6, D); hs_tri_store(T.P, (size_t)n, 6, P);
     T.live[n] = live ? 1 : 0;
     if (start) {
         const double x[3] = { 0.0, 0.0, 0.0 }, res[3] = { -g[0], -g[1], -g[2] };
-        k19_vstore(A.x, n, A.N, x); k19_vstore(A.res, n, A.N, res);
+        k19_store3(A.x, n, x); k19_store3(A.res, n, res);
     }
 }
 
@@ -56,74 +44,24 @@ __global__ void __launch_bounds__(K19_LANES) k22_coupling(const k19_arg A, const
 {
     const int n = (int)blockIdx.x * K19_LANES + (int)threadIdx.x;
     if (n >= A.N) return;
-    double U[9] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-    if (n + 1 < A.N && T.live[n] && T.live[n + 1]) {
-        const int m1 = A.off[n + 1];
-        for (int m = A.off[n]; m < m1; m++) {
-            const int e = A.inc[m] >> 1, side = A.inc[m] & 1;
-            const int2 ij = A.ij[e];
-            if ((side ? ij.x : ij.y) != n + 1) continue;
-            const hs_pg_rec R = A.rec[e];
-            double Jn[3][3], Jm[3][3];
-            hs_pg_jac(R, side, Jn);
-            hs_pg_jac(R, side ^ 1, Jm);
-            hs_tri_add_coupling(Jn, Jm, R, U);
-        }
-    }
-    k22_store(T.U, (size_t)n, 9, U);
-}
-
-// rule T3 for block m of level l + 1
-__device__ static inline void k22_reduce_block(const hs_tri_plan &T, int l, int m)
-{
-    const int n = T.n[l], k = 2 * m;
-    const size_t o = (size_t)T.off[l] + (size_t)k;
-    const bool have_l = k >= 1, have_r = k + 1 < n, have_n = k + 2 < n;
-    double Dk[6], Ul[9], Pl[6], Uk[9], Pr[6], Un[9], Dn[6], Uo[9], Pn[6];
-    k22_load(T.D, o, 6, Dk);
-    if (have_l) { k22_load(T.U, o - 1, 9, Ul); k22_load(T.P, o - 1, 6, Pl); }
-    if (have_r) { k22_load(T.U, o, 9, Uk); k22_load(T.P, o + 1, 6, Pr); }
-    if (have_n) k22_load(T.U, o + 1, 9, Un);
-    hs_tri_reduce(Dk, have_l, Ul, Pl, have_r, Uk, Pr, have_n, Un, Dn, Uo);
-    (void)hs_pg_inv(Dn, Pn);
-    const size_t o1 = (size_t)T.off[l + 1] + (size_t)m;
-    k22_store(T.D, o1, 6, Dn); k22_store(T.U, o1, 9, Uo); k22_store(T.P, o1, 6, Pn);
+    double U[9];
+    hs_tri_node_coupling(n, A.N, T.live, A.off, A.inc, A.rec, (const int32_t *)A.ij, U);
+    hs_tri_store(T.U, (size_t)n, 9, U);
 }
 
 __global__ void __launch_bounds__(K19_LANES) k22_reduce(const hs_tri_plan T, int l)
 {
     const int m = (int)blockIdx.x * K19_LANES + (int)threadIdx.x;
-    if (m < T.n[l + 1]) k22_reduce_block(T, l, m);
+    if (m < T.n[l + 1]) hs_tri_reduce_block(T, l, m);
 }
 
 // one workgroup: levels lt + 1 .. L - 1 (what a level reads, the level before has stored ahead of the barrier)
 __global__ void __launch_bounds__(K19_LANES) k22_factor_tail(const hs_tri_plan T)
 {
     for (int l = T.lt; l + 1 < T.L; l++) {
-        for (int m = (int)threadIdx.x; m < T.n[l + 1]; m += K19_LANES) k22_reduce_block(T, l, m);
+        for (int m = (int)threadIdx.x; m < T.n[l + 1]; m += K19_LANES) hs_tri_reduce_block(T, l, m);
         __threadfence_block();
         __syncthreads();
-    }
-}
-
-// k19_step without "z = M res" and its block sums
-__global__ void __launch_bounds__(K19_LANES) k22_axpy(const k19_arg A, int k)
-{
-    __shared__ double lds[K19_LANES], lds2[64];
-    __shared__ int stop_s;
-    if (k19_stopped(A.st, &stop_s)) return;
-    const double pq = k19_total(A.part_a, A.PN, lds, lds2);
-    if (hs_pg_breakdown(pq)) {                                             // (the same in every workgroup)
-        if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(&A.st->stop, 1 + HS_PG_STOP_BREAKDOWN, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    const double alpha = A.st->rz[k & 1] / pq;
-    const int n = (int)blockIdx.x * K19_LANES + (int)threadIdx.x;
-    if (n < A.N) {
-        double x[3], res[3], p[3], q[3];
-        k19_vload(A.x, n, A.N, x); k19_vload(A.res, n, A.N, res); k19_vload(A.p, n, A.N, p); k19_vload(A.q, n, A.N, q);
-        for (int a = 0; a < 3; a++) { x[a] = x[a] + alpha * p[a]; res[a] = res[a] - alpha * q[a]; }
-        k19_vstore(A.x, n, A.N, x); k19_vstore(A.res, n, A.N, res);
     }
 }
 
@@ -275,40 +213,60 @@ static int32_t hs_tri_solve(hs_pg *g, hipStream_t st, const k22_io &io)
     return SLAMHIP_OK;
 }
 
-extern "C" int32_t slamhip_hs_pg_relax_tri(slamhip_hs *hs, const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final)
+// The unit's PCG driver: rules 4 - 7 (tri: T1 - T5) up to the pose update, over A's weights at the linearisation k19_linearise has
+// left.  Batches of check_every iterations, the stop word read back into h_st (pinned) between them.
+static int32_t hs_pg_pcg(slamhip_hs *hs, hs_pg *g, const k19_arg &A, bool tri, double lambda, int n_cg, int check_every, double tol, k19_state *h_st)
 {
-    SH_CHECK_ARG(hs && spec && out_iters && out_chi2_final);
-#if K19_SCALAR_LAUNCH || K19_SOA
-    SH_FAIL(SLAMHIP_ERR_STATE, "K22 is not part of the K19_SCALAR_LAUNCH / K19_SOA developer builds");
+    hipStream_t st = hs->ctx->stream;
+    const k22_io first = { A.res, A.zv, A.p, A.part_b, nullptr }, io = { A.res, A.zv, nullptr, A.part_b, A.st };
+    if (tri) {
+        SH_TRY(hs_tri_factor(A, g->T, st, lambda, 1));
+        SH_TRY(hs_tri_solve(g, st, first));                                // rule 7's start: z = T^-1 res, p = z, the block sums of res . z
+    } else {
+        K19_LAUNCH(k19_diag, A.PN, A, lambda);
+    }
+    K19_LAUNCH(k19_begin, 1, A, 0);
+    for (int k = 0; k < n_cg;) {
+        const int k1 = (int)std::min<int64_t>((int64_t)k + std::min(check_every, K19_MAX_BATCH), n_cg);
+        for (; k < k1; k++) {
+            K19_LAUNCH(k19_apply, A.PN, A, k, lambda, tol);
+#if K19_SCALAR_LAUNCH
+            K19_LAUNCH(k19_scal_a, 1, A, k);
 #endif
+            if (tri) {
+                K19_LAUNCH(k19_step<false>, A.PN, A, k);
+                SH_TRY(hs_tri_solve(g, st, io));
+            } else {
+                K19_LAUNCH(k19_step<true>, A.PN, A, k);
+            }
+#if K19_SCALAR_LAUNCH
+            K19_LAUNCH(k19_scal_b, 1, A, k);
+#endif
+            K19_LAUNCH(k19_dir, A.PN, A, k);
+        }
+        SH_HIP(hipMemcpyAsync(h_st, A.st, sizeof(k19_state), hipMemcpyDeviceToHost, st));
+        SH_TRY(hs_call_finish(hs));                                        // (the stop word, between batches)
+        if (h_st->stop) break;
+    }
+    return SLAMHIP_OK;
+}
+
+static int32_t hs_pg_relax_run(slamhip_hs *hs, const slamhip_pg_spec *spec, bool tri, const char *who, slamhip_pg_iter *out_iters, double *out_chi2_final)
+{
     SH_TRY(hs_pg_check_spec(spec));
-    SH_TRY(hs_pg_need(hs, "pose graph relax (tri)"));
+    SH_TRY(hs_pg_need(hs, who));
     hs_pg *g = hs->pg;
     const k19_arg &A = g->A;
     hipStream_t st = hs->ctx->stream;
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_tri_blocks(g, "pose graph relax (tri)"));
+    if (tri) SH_TRY(hs_tri_blocks(g, who));
+    // the pinned block: the records, the final chi2, the stop word's copy
     const size_t out_bytes = sizeof(slamhip_pg_iter) * (size_t)spec->n_outer;
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, out_bytes + 8 + sizeof(k19_state), HS_MEM_PINNED, "pose graph relax (tri)"));
+    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, out_bytes + 8 + sizeof(k19_state), HS_MEM_PINNED, who));
     k19_state *h_st = (k19_state *)(g->h_io + out_bytes + 8);
-    const k22_io first = { A.res, A.zv, A.p, A.part_b, nullptr }, io = { A.res, A.zv, nullptr, A.part_b, A.st };
     for (int outer = 0; outer < spec->n_outer; outer++) {
         K19_LAUNCH(k19_linearise, A.PE, A);
-        SH_TRY(hs_tri_factor(A, g->T, st, spec->lambda, 1));
-        SH_TRY(hs_tri_solve(g, st, first));                                // rule 7's start: z = T^-1 res, p = z, the block sums of res . z
-        K19_LAUNCH(k19_begin, 1, A, 0);
-        for (int k = 0; k < spec->n_cg;) {
-            const int k1 = (int)std::min<int64_t>((int64_t)k + std::min(spec->check_every, K19_MAX_BATCH), spec->n_cg);
-            for (; k < k1; k++) {
-                K19_LAUNCH(k19_apply, A.PN, A, k, spec->lambda, spec->tol);
-                K19_LAUNCH(k22_axpy, A.PN, A, k);
-                SH_TRY(hs_tri_solve(g, st, io));
-                K19_LAUNCH(k19_dir, A.PN, A, k);
-            }
-            SH_HIP(hipMemcpyAsync(h_st, A.st, sizeof(k19_state), hipMemcpyDeviceToHost, st));
-            SH_TRY(hs_call_finish(hs));                                    // (the stop word, between batches)
-            if (h_st->stop) break;
-        }
+        SH_TRY(hs_pg_pcg(hs, g, A, tri, spec->lambda, spec->n_cg, spec->check_every, spec->tol, h_st));
         K19_LAUNCH(k19_update, A.PN, A, spec->tol, outer);
     }
     K19_LAUNCH(k19_linearise, A.PE, A);
@@ -321,11 +279,20 @@ extern "C" int32_t slamhip_hs_pg_relax_tri(slamhip_hs *hs, const slamhip_pg_spec
     return SLAMHIP_OK;
 }
 
+extern "C" int32_t slamhip_hs_pg_relax_tri(slamhip_hs *hs, const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final)
+{
+    SH_CHECK_ARG(hs && spec && out_iters && out_chi2_final);
+#if K19_SCALAR_LAUNCH
+    SH_FAIL(SLAMHIP_ERR_STATE, "K22 is not part of the K19_SCALAR_LAUNCH developer build");
+#endif
+    return hs_pg_relax_run(hs, spec, true, "pose graph relax (tri)", out_iters, out_chi2_final);
+}
+
 extern "C" int32_t slamhip_hs_pg_tri_apply(slamhip_hs *hs, double lambda, const double *rhs, double *out)
 {
     SH_CHECK_ARG(hs && rhs && out);
-#if K19_SCALAR_LAUNCH || K19_SOA
-    SH_FAIL(SLAMHIP_ERR_STATE, "K22 is not part of the K19_SCALAR_LAUNCH / K19_SOA developer builds");
+#if K19_SCALAR_LAUNCH
+    SH_FAIL(SLAMHIP_ERR_STATE, "K22 is not part of the K19_SCALAR_LAUNCH developer build");
 #endif
     if (!isfinite(lambda) || !(lambda >= 0.0)) SH_FAIL(SLAMHIP_ERR_INVALID, "pose graph tri apply: lambda = %g must be finite and >= 0", lambda);
     SH_TRY(hs_pg_need(hs, "pose graph tri apply"));
@@ -353,74 +320,38 @@ struct hs_tri_host {
     hs_tri_plan T;
     std::vector<double> D, P, U, R;
     std::vector<unsigned char> live;
-    std::vector<int32_t> off, inc;
-    std::vector<unsigned char> fx;
 };
 
-static void hs_tri_host_init(hs_tri_host &H, const uint8_t *fixed, int N, const int32_t *ij, int E)
+static void hs_tri_host_init(hs_tri_host &H, int N)
 {
     const size_t tot = (size_t)hs_tri_levels(N, HS_TRI_TAIL, &H.T);
     H.D.assign(6 * tot, 0.0); H.P.assign(6 * tot, 0.0); H.U.assign(9 * tot, 0.0); H.R.assign(3 * (tot - (size_t)N) + 3, 0.0);
     H.live.assign((size_t)N, 0);
-    H.off.resize((size_t)N + 1); H.inc.resize(2 * (size_t)E + 1);
-    hs_pg_lists(N, ij, E, H.off.data(), H.inc.data());
-    H.fx.assign((size_t)N, 0);
-    if (fixed) for (int n = 0; n < N; n++) H.fx[(size_t)n] = fixed[n] ? 1 : 0;
-    else H.fx[0] = 1;
     H.T.D = H.D.data(); H.T.P = H.P.data(); H.T.U = H.U.data(); H.T.R = H.R.data(); H.T.live = H.live.data();
 }
 
 // rules T1 - T3; g (N x 3, or nullptr): rule 4's g_n beside them
-static void hs_tri_host_factor(hs_tri_host &H, int N, const int32_t *ij, const hs_pg_rec *rec, const double *r, double lambda, double *g_out)
+static void hs_tri_host_factor(hs_tri_host &H, const hs_pg_host_lists &G, int N, const int32_t *ij, const hs_pg_rec *rec, const double *r, double lambda, double *g_out)
 {
     const hs_tri_plan &T = H.T;
     for (int n = 0; n < N; n++) {
-        double D[6] = { lambda, 0.0, 0.0, lambda, 0.0, lambda }, g[3] = { 0.0, 0.0, 0.0 }, P[6];
+        double D[6], g[3] = { 0.0, 0.0, 0.0 }, P[6];
         bool live = false;
-        if (!H.fx[(size_t)n]) {
-            for (int m = H.off[(size_t)n]; m < H.off[(size_t)n + 1]; m++) {
-                const int e = H.inc[(size_t)m] >> 1, side = H.inc[(size_t)m] & 1;
-                const hs_pg_rec &R = rec[e];
-                double J[3][3];
-                hs_pg_jac(R, side, J);
-                hs_pg_add_jtwj(J, R, D);
-                const double *re = r + 3 * (size_t)e;
-                const double v[3] = { R.wx * re[0], R.wy * re[1], R.wt * re[2] };
-                hs_pg_add_jtv(J, v, g);
-            }
+        if (!G.fx[(size_t)n]) {
+            hs_pg_node_diag(lambda, n, G.off.data(), G.inc.data(), rec, r, D, g);
             live = hs_pg_inv(D, P);
         }
         if (!live) {
             D[0] = D[3] = D[5] = 1.0; D[1] = D[2] = D[4] = 0.0;
             for (int m = 0; m < 6; m++) P[m] = D[m];
         }
-        for (int m = 0; m < 6; m++) { T.D[6 * (size_t)n + m] = D[m]; T.P[6 * (size_t)n + m] = P[m]; }
+        hs_tri_store(T.D, (size_t)n, 6, D); hs_tri_store(T.P, (size_t)n, 6, P);
         T.live[n] = live ? 1 : 0;
         if (g_out) for (int a = 0; a < 3; a++) g_out[3 * (size_t)n + a] = g[a];
     }
-    for (int n = 0; n < N; n++) {
-        double *U = T.U + 9 * (size_t)n;
-        for (int m = 0; m < 9; m++) U[m] = 0.0;
-        if (!(n + 1 < N && T.live[n] && T.live[n + 1])) continue;
-        for (int m = H.off[(size_t)n]; m < H.off[(size_t)n + 1]; m++) {
-            const int e = H.inc[(size_t)m] >> 1, side = H.inc[(size_t)m] & 1;
-            if (ij[2 * (size_t)e + (side ^ 1)] != n + 1) continue;
-            double Jn[3][3], Jm[3][3];
-            hs_pg_jac(rec[e], side, Jn);
-            hs_pg_jac(rec[e], side ^ 1, Jm);
-            hs_tri_add_coupling(Jn, Jm, rec[e], U);
-        }
-    }
+    for (int n = 0; n < N; n++) hs_tri_node_coupling(n, N, T.live, G.off.data(), G.inc.data(), rec, ij, T.U + 9 * (size_t)n);
     for (int l = 0; l + 1 < T.L; l++)
-        for (int m = 0; m < T.n[l + 1]; m++) {
-            const int n = T.n[l], k = 2 * m;
-            const size_t o = (size_t)T.off[l] + (size_t)k, o1 = (size_t)T.off[l + 1] + (size_t)m;
-            const bool have_l = k >= 1, have_r = k + 1 < n, have_n = k + 2 < n;
-            // (a neighbour that is not there is never read: the pointers stay inside the arrays)
-            hs_tri_reduce(T.D + 6 * o, have_l, T.U + 9 * (have_l ? o - 1 : o), T.P + 6 * (have_l ? o - 1 : o), have_r, T.U + 9 * o, T.P + 6 * (have_r ? o + 1 : o),
-                          have_n, T.U + 9 * (have_n ? o + 1 : o), T.D + 6 * o1, T.U + 9 * o1);
-            (void)hs_pg_inv(T.D + 6 * o1, T.P + 6 * o1);
-        }
+        for (int m = 0; m < T.n[l + 1]; m++) hs_tri_reduce_block(T, l, m);
 }
 
 // rule T4: z = T^-1 r0
@@ -446,22 +377,37 @@ static void hs_tri_host_solve(hs_tri_host &H, const double *r0, double *z0)
         if (!T.live[n]) z0[3 * n] = z0[3 * n + 1] = z0[3 * n + 2] = 0.0;
 }
 
-// the definition over a graph and a spec that have been checked (K26's hook takes single steps through it, with its own weights)
-static void hs_tri_host_relax(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
-                              const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
+// The definition of K19 (block-Jacobi) and of K22 (tri) over a graph and a spec that have been checked; K26's hook takes single steps
+// through it, with its own weights.  tri is read where the preconditioner is made and where z is formed from res, nowhere else.
+static void hs_pg_host_relax(bool tri, double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
+                             const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
 {
     const size_t n3 = 3 * (size_t)N, pad = HS_PG_BLOCK;
+    hs_pg_host_lists G;
+    hs_pg_host_lists_init(G, fixed, N, ij, E);
     hs_tri_host H;
-    hs_tri_host_init(H, fixed, N, ij, E);
+    if (tri) hs_tri_host_init(H, N);
     std::vector<hs_pg_rec> rec((size_t)E + 1);
-    std::vector<double> r(3 * (size_t)E + 3), tmp((size_t)std::max(N, E) + pad), g(n3), x(n3), res(n3), zv(n3), p(n3), q(n3);
+    std::vector<double> r(3 * (size_t)E + 3), tmp((size_t)std::max(N, E) + pad), M(tri ? 0 : 6 * (size_t)N), g(n3), x(n3), res(n3), zv(n3), p(n3), q(n3);
     const double lambda = spec->lambda, tol = spec->tol;
+    auto precondition = [&]() {                                            // z from res
+        if (tri) hs_tri_host_solve(H, res.data(), zv.data());
+        else for (int n = 0; n < N; n++) hs_pg_mul(M.data() + 6 * (size_t)n, res.data() + 3 * (size_t)n, zv.data() + 3 * (size_t)n);
+    };
     for (int outer = 0; outer < spec->n_outer; outer++) {
         slamhip_pg_iter I;
         I.chi2 = hs_pg_host_linearise(poses, ij, z, w, E, rec.data(), r.data(), tmp.data());
-        hs_tri_host_factor(H, N, ij, rec.data(), r.data(), lambda, g.data());
-        for (size_t i = 0; i < n3; i++) { x[i] = 0.0; res[i] = -g[i]; }
-        hs_tri_host_solve(H, res.data(), zv.data());
+        if (tri) hs_tri_host_factor(H, G, N, ij, rec.data(), r.data(), lambda, g.data());
+        else for (int n = 0; n < N; n++) {                                 // rule 4: M = 0 and g = 0 for a fixed node
+            double D[6], *gn = g.data() + 3 * (size_t)n, *Mn = M.data() + 6 * (size_t)n;
+            gn[0] = gn[1] = gn[2] = 0.0;
+            for (int m = 0; m < 6; m++) Mn[m] = 0.0;
+            if (G.fx[(size_t)n]) continue;
+            hs_pg_node_diag(lambda, n, G.off.data(), G.inc.data(), rec.data(), r.data(), D, gn);
+            (void)hs_pg_inv(D, Mn);
+        }
+        for (size_t i = 0; i < n3; i++) { x[i] = 0.0; res[i] = -g[i]; }    // rule 7's start
+        precondition();
         p = zv;
         double rz = hs_pg_host_dot(res.data(), zv.data(), N, tmp.data());
         I.rz0 = rz;
@@ -469,26 +415,16 @@ static void hs_tri_host_relax(double *poses, const uint8_t *fixed, int32_t N, co
         for (;; k++) {
             if (hs_pg_converged(rz, I.rz0, tol)) { stopped = HS_PG_STOP_TOL; break; }
             if (k == spec->n_cg) { stopped = HS_PG_STOP_NCG; break; }
-            for (int n = 0; n < N; n++) {                                  // rule 5
-                const double *pn = p.data() + 3 * (size_t)n;
+            for (int n = 0; n < N; n++) {                                  // rule 5: q = 0 for a fixed node
                 double *qn = q.data() + 3 * (size_t)n;
                 qn[0] = qn[1] = qn[2] = 0.0;
-                if (H.fx[(size_t)n]) continue;
-                for (int a = 0; a < 3; a++) qn[a] = lambda * pn[a];
-                for (int m = H.off[(size_t)n]; m < H.off[(size_t)n + 1]; m++) {
-                    const int e = H.inc[(size_t)m] >> 1, side = H.inc[(size_t)m] & 1;
-                    const hs_pg_rec &R = rec[(size_t)e];
-                    double t[3], J[3][3];
-                    hs_pg_edge_t(R, p.data() + 3 * (size_t)ij[2 * (size_t)e], p.data() + 3 * (size_t)ij[2 * (size_t)e + 1], t);
-                    hs_pg_jac(R, side, J);
-                    hs_pg_add_jtv(J, t, qn);
-                }
+                if (!G.fx[(size_t)n]) hs_pg_node_apply(lambda, p.data(), n, G.off.data(), G.inc.data(), rec.data(), ij, qn);
             }
             const double pq = hs_pg_host_dot(p.data(), q.data(), N, tmp.data());
             if (hs_pg_breakdown(pq)) { stopped = HS_PG_STOP_BREAKDOWN; break; }
             const double alpha = rz / pq;
             for (size_t i = 0; i < n3; i++) { x[i] = x[i] + alpha * p[i]; res[i] = res[i] - alpha * q[i]; }
-            hs_tri_host_solve(H, res.data(), zv.data());
+            precondition();
             const double rzn = hs_pg_host_dot(res.data(), zv.data(), N, tmp.data());
             const double beta = rzn / rz;
             for (size_t i = 0; i < n3; i++) p[i] = zv[i] + beta * p[i];
@@ -496,12 +432,8 @@ static void hs_tri_host_relax(double *poses, const uint8_t *fixed, int32_t N, co
         }
         I.rz = rz; I.cg_iters = k; I.stopped = stopped;
         out_iters[outer] = I;
-        for (int n = 0; n < N; n++) {
-            if (H.fx[(size_t)n]) continue;
-            double *pn = poses + 3 * (size_t)n;
-            for (int a = 0; a < 3; a++) pn[a] = pn[a] + x[3 * (size_t)n + a];
-            pn[2] = hs_pg_wrap(pn[2]);
-        }
+        for (int n = 0; n < N; n++)
+            if (!G.fx[(size_t)n]) hs_pg_add_pose(poses + 3 * (size_t)n, x.data() + 3 * (size_t)n);
     }
     *out_chi2_final = hs_pg_host_linearise(poses, ij, z, w, E, rec.data(), r.data(), tmp.data());
     if (out_r && E) memcpy(out_r, r.data(), 24 * (size_t)E);
@@ -514,7 +446,7 @@ extern "C" int32_t slamhip_debug_pg_relax_tri(double *poses, const uint8_t *fixe
     SH_CHECK_ARG(spec && out_iters && out_chi2_final);
     SH_TRY(hs_pg_check_spec(spec));
     SH_TRY(hs_pg_check_graph(poses, fixed, N, ij, z, w, E));
-    hs_tri_host_relax(poses, fixed, N, ij, z, w, E, spec, out_iters, out_chi2_final, out_r, out_chi2);
+    hs_pg_host_relax(true, poses, fixed, N, ij, z, w, E, spec, out_iters, out_chi2_final, out_r, out_chi2);
     return SLAMHIP_OK;
 }
 
@@ -524,12 +456,14 @@ extern "C" int32_t slamhip_debug_pg_tri_apply(const double *poses, const uint8_t
     SH_CHECK_ARG(rhs && out);
     if (!isfinite(lambda) || !(lambda >= 0.0)) SH_FAIL(SLAMHIP_ERR_INVALID, "pose graph tri apply: lambda = %g must be finite and >= 0", lambda);
     SH_TRY(hs_pg_check_graph(poses, fixed, N, ij, z, w, E));
+    hs_pg_host_lists G;
+    hs_pg_host_lists_init(G, fixed, N, ij, E);
     hs_tri_host H;
-    hs_tri_host_init(H, fixed, N, ij, E);
+    hs_tri_host_init(H, N);
     std::vector<hs_pg_rec> rec((size_t)E + 1);
     std::vector<double> r(3 * (size_t)E + 3), tmp((size_t)E + HS_PG_BLOCK);
     (void)hs_pg_host_linearise(poses, ij, z, w, E, rec.data(), r.data(), tmp.data());
-    hs_tri_host_factor(H, N, ij, rec.data(), r.data(), lambda, nullptr);
+    hs_tri_host_factor(H, G, N, ij, rec.data(), r.data(), lambda, nullptr);
     hs_tri_host_solve(H, rhs, out);
     return SLAMHIP_OK;
 }

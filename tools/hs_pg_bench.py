@@ -7,11 +7,10 @@ THE SAME RUN.
    PCG iteration is the difference of the two medians over 50.  pg_set is timed on its own.
  * Host: the same Gauss-Newton step (libm trig) as a sparse system solved by scipy.sparse.linalg.spsolve, when scipy is there and
    N <= 10^5, once; and slamhip_debug_pg_relax, the library's own host loops, for the same 60 iterations.
- * The two design alternatives, each a developer build of this tree in slam.net_amd/build/variants/ (`python tools/build_variant.py
+ * The design alternative, a developer build of this tree in slam.net_amd/build/variants/ (`python tools/build_variant.py
    WORK k19_scalar -DK19_SCALAR_LAUNCH=1`: alpha, beta and the stop word by a one-workgroup launch behind k19_apply and behind k19_step,
-   five launches per iteration; `... WORK k19_soa -DK19_SOA=1`: the node vectors as three arrays of N doubles), when they are there:
-   the same relax figures at 10^5 and 2^20 nodes, each library in a fresh interpreter (`--variant-only` with SLAMHIP_LIB set), the
-   poses after the 60 iterations hashed and compared with this tree's.
+   five launches per iteration), when it is there: the same relax figures at 10^5 and 2^20 nodes, the library in a fresh interpreter
+   (`--variant-only` with SLAMHIP_LIB set), the poses after the 60 iterations hashed and compared with this tree's.
  * Existing path: HectorSLAMProcessor.Update of the trace bench's scan, blocking, median of 35 scans; the new code is never entered on
    it.  With a build of the parent commit at slam.net_amd/build/variants/parent.so (`python tools/build_variant.py HEAD~1 parent`) the
    figure is taken in alternating fresh interpreters, this tree then the parent, three each (`--update-only` with SLAMHIP_LIB set).
