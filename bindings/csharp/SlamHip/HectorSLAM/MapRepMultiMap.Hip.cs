@@ -695,6 +695,23 @@ namespace HectorSLAM.Main
             return iters;
         }
 
+        /// <summary>Marginal covariances at the poses as they stand (slamhip_hs_pg_marginals, rules M1 - M5): pairs = P x 2 node indices
+        /// (n, m); returns P x 9 doubles, block p = Sigma[n_p][m_p] row-major (+0 where n_p or m_p is fixed).  cols receives one record per
+        /// right-hand side, info what was done.  Neither the poses nor a later relaxation's results change.</summary>
+        public unsafe double[] PgMarginals(PgMargSpec spec, int[] pairs, out PgMargCol[] cols, out PgMargInfo info)
+        {
+            if (pairs == null || pairs.Length < 2 || (pairs.Length & 1) != 0) throw new ArgumentException("pairs: P x 2 node indices");
+            int nPairs = pairs.Length / 2, count;
+            var blocks = new double[9 * nPairs];
+            cols = new PgMargCol[3 * Math.Min(nPairs, 4096)];
+            fixed (int* pr = pairs)
+            fixed (double* b = blocks)
+            fixed (PgMargCol* c = cols)
+                Native.Check(Native.slamhip_hs_pg_marginals(Pyramid.Ptr, in spec, pr, nPairs, b, c, out count, out info));
+            Array.Resize(ref cols, count);
+            return blocks;
+        }
+
         /// <summary>z = T^-1 rhs at the poses as they stand (slamhip_hs_pg_tri_apply): N x 3 doubles in, N x 3 doubles out.</summary>
         public unsafe double[] PgTriApply(double lambda, double[] rhs)
         {

@@ -345,6 +345,34 @@ namespace SlamHip
         public int CgIterations, Stopped, Accepted, Reserved0, Reserved1, Reserved2;
     }
 
+    /// <summary>slamhip_pg_marg_spec (include/slamhip.h): the most PCG iterations of a right-hand side, the iterations between two reads of
+    /// the stop words, the preconditioner (0 block-Jacobi, 1 the odometry chain), a reserved word, lambda, rule 7's tolerance and rule
+    /// M5's bound of the work block in bytes (0: 256 MiB).  40 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PgMargSpec
+    {
+        public int CgCount, CheckEvery, Precond, Reserved;
+        public double Lambda, Tolerance;
+        public long MaxBytes;
+    }
+
+    /// <summary>slamhip_pg_marg_col (include/slamhip.h): one right-hand side e(Node, Component) of a marginals query: rz0, the last rz,
+    /// the PCG iterations and why they stopped (as PgIter).  32 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PgMargCol
+    {
+        public double Rz0, Rz;
+        public int CgIterations, Stopped, Node, Component;
+    }
+
+    /// <summary>slamhip_pg_marg_info (include/slamhip.h): the columns and right-hand sides of a query, the right-hand sides per chunk, the
+    /// chunks, the group size of the kernels, three reserved words.  32 bytes.</summary>
+    [StructLayout(LayoutKind.Sequential)]
+    public struct PgMargInfo
+    {
+        public int Columns, RightHandSides, PerChunk, Chunks, Group, Reserved0, Reserved1, Reserved2;
+    }
+
     /// <summary>What slamhip_hs_hough reports of the slot it filled: the map's size and first cell, D = w + h, the bins per angle N,
     /// the sites, and the spectrum HS (T entries); H (T rows of N) when asked for.</summary>
     public sealed class HoughInfo
@@ -514,6 +542,7 @@ namespace SlamHip
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_relax(IntPtr hs, in PgSpec spec, PgIter* iters, out double chi2Final);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_relax_tri(IntPtr hs, in PgSpec spec, PgIter* iters, out double chi2Final);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_relax_lm(IntPtr hs, in PgLmSpec spec, byte* robust, PgLmIter* iters, out int count, out double costFinal, double* factors);
+        [DllImport(Lib)] internal static extern int slamhip_hs_pg_marginals(IntPtr hs, in PgMargSpec spec, int* pairs, int nPairs, double* blocks, PgMargCol* cols, out int count, out PgMargInfo info);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_tri_apply(IntPtr hs, double lambda, double* rhs, double* z);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_get(IntPtr hs, double* poses, int nNodes);
         [DllImport(Lib)] internal static extern int slamhip_hs_pg_residuals(IntPtr hs, double* r, double* chi2);

@@ -1872,6 +1872,76 @@ int32_t slamhip_debug_pg_relax_lm(double *poses, const uint8_t *fixed, int32_t N
                                   int32_t E, const slamhip_pg_lm_spec *spec, const uint8_t *robust, slamhip_pg_lm_iter *out_iters,
                                   int32_t *out_n, double *out_F_final, double *out_f);
 
+/* Marginal covariances of the pose graph (K27; no reference counterpart).  The relaxation moves the keyframes; this call says how well
+ * they are known: blocks of Sigma = H^-1 at the poses as they stand, H rule 5's operator (lambda included) over the weights of
+ * slamhip_hs_pg_set.  A column of Sigma is one more solve, H x = e, by the PCG of slamhip_hs_pg_relax / _relax_tri -- here for ALL the
+ * right-hand sides of a query at once: the preconditioner is made once, and every PCG phase is ONE launch over the whole batch, each
+ * right-hand side with its own scalars and its own stop word.
+ * THE DEFINITION.  Binary64 + - * / only, one rounding per operation, no fused multiply-add, as in slamhip_hs_pg_relax.
+ *  M1. Query.  pairs = P x 2 int32 (n, m), P in [1, 2^20], both indices in [0, N); duplicates and n == m are allowed.  The COLUMNS are
+ *      the distinct m that are free nodes, in ascending node index: m_0 < m_1 < .. < m_{C-1}, C <= SLAMHIP_PG_MARG_MAX_COLS.
+ *      Right-hand side 3 c + b (b = 0, 1, 2) is e(m_c, b): 1.0 at component b of node m_c and +0 elsewhere.  R = 3 C.
+ *  M2. Per right-hand side: rules 3 - 7 of slamhip_hs_pg_relax, rule 7's start replaced by x = 0, res = e.  precond = 0: z = M res
+ *      (rule 4); precond = 1: z = T^-1 res (T1 - T5), T factored ONCE per call.  lambda, tol, n_cg and check_every as in
+ *      slamhip_pg_spec.  Rule 6's tree runs over the N nodes of that one right-hand side.  Every right-hand side stops by rule 7 on
+ *      its own scalars; one that has stopped is not touched again.  No pose is updated.
+ *  M3. Output.  out_blocks[p][a][b] = component a of node n_p of the x solved for e(m_p, b): P x 9 doubles; the block is +0 when n_p
+ *      or m_p is fixed.  The blocks are the RAW PCG columns: Sigma[n][m] and the transpose of Sigma[m][n] agree to the solve's accuracy
+ *      only, and a diagonal block is symmetric to that accuracy only.
+ *  M4. Record per right-hand side, in M1's order, slamhip_pg_marg_col: rz0, the last rz, cg_iters, stopped (as slamhip_pg_iter's),
+ *      node = m_c, comp = b.  *out_n_cols = R; out_cols has room for 3 * min(P, SLAMHIP_PG_MARG_MAX_COLS) records.
+ *  M5. Memory.  The right-hand sides are solved in chunks of R_c = min(R, floor(budget / B)), budget = max_bytes, or 256 MiB for
+ *      max_bytes = 0 (a default, not a measurement), and
+ *        B = 120 N + 16 ceil(N / 256) + 40 + (precond ? 24 (tot - N) + 24 : 0),   tot = N + ceil(N / 2) + ceil(N / 4) + .. + 1
+ *      the bytes of one right-hand side (five node vectors, two rows of block sums, the scalars and the stop word; the levels'
+ *      right-hand sides of T4).  The query itself (12 P + 4 C bytes), the blocks and the records stand beside that.  R_c = 0:
+ *      SLAMHIP_ERR_NOMEM, nothing changed.  slamhip_pg_marg_info says what was done: n_cols = C, n_rhs = R, rhs_per_chunk = R_c,
+ *      n_chunks = ceil(R / R_c), group = the right-hand sides a lane keeps in registers.  With C = 0 every block is +0, nothing is
+ *      launched, and rhs_per_chunk = n_chunks = 0.
+ * No result depends on the chunking, the group, the grid, check_every or SLAMHIP_K22_TAIL. */
+#define SLAMHIP_PG_MARG_MAX_PAIRS (1 << 20)
+#define SLAMHIP_PG_MARG_MAX_COLS 4096
+typedef struct slamhip_pg_marg_spec {
+    int32_t n_cg;                      /* offset 0: the most PCG iterations of a right-hand side, [1, 2^20] */
+    int32_t check_every;               /* offset 4: >= 1, as slamhip_pg_spec's; no result depends on it */
+    int32_t precond;                   /* offset 8: 0 block-Jacobi (rule 4), 1 the odometry chain (T1 - T5) */
+    int32_t reserved;                  /* offset 12: 0 */
+    double lambda;                     /* offset 16: >= 0, added to every diagonal entry of H */
+    double tol;                        /* offset 24: >= 0, rule 7 */
+    int64_t max_bytes;                 /* offset 32: >= 0, M5; 0: 256 MiB */
+} slamhip_pg_marg_spec;                /* 40 bytes */
+typedef struct slamhip_pg_marg_col {
+    double rz0, rz;                    /* offsets 0, 8 */
+    int32_t cg_iters, stopped;         /* offsets 16, 20; stopped as slamhip_pg_iter's */
+    int32_t node, comp;                /* offsets 24, 28: the right-hand side is e(node, comp) */
+} slamhip_pg_marg_col;                 /* 32 bytes */
+typedef struct slamhip_pg_marg_info {
+    int32_t n_cols, n_rhs, rhs_per_chunk, n_chunks, group;   /* offsets 0 .. 16 */
+    int32_t reserved[3];                                     /* offset 20: 0 */
+} slamhip_pg_marg_info;                /* 32 bytes */
+/* Rules M1 - M5 on the graph of slamhip_hs_pg_set at the poses as they stand.  It changes neither the poses nor anything a later
+ * slamhip_hs_pg_relax* call reads.  Launches: k19_linearise; k19_diag (precond = 1: k22_diag, k22_coupling, k22_reduce, k22_factor_tail)
+ * ONCE; per chunk k27_begin (e, x = 0; precond = 0: the first z, p and the block sums) -- precond = 1: the batched solve below --,
+ * k27_begin_state (a workgroup per right-hand side: rz0, the scalars, the stop word); per PCG iteration k27_apply<G> (grid: node blocks x
+ * ceil(R_c / G); a lane per node with G right-hand sides in registers; an incident edge's record and Jacobians are loaded and formed
+ * once for the G), k27_step<G> and k27_dir<G> (every workgroup finishes rule 6's tree of its G scalars itself), with precond = 1 between
+ * them k27_forward per large level, k27_solve_tail (a workgroup per right-hand side) and k27_backward per large level, the right-hand
+ * side on grid y; per chunk k27_collect (the records and the blocks).  The host enqueues check_every iterations (at most 1024), reads the
+ * chunk's stop words in ONE copy, and goes on until all are set.  No floating-point atomic; no workgroup waits on another.
+ * SLAMHIP_K27_GROUP (developer, read at every call) selects G among the default 1 and 4 (at the sizes measured G = 4 does not beat G = 1:
+ * DESIGN.md section 4 "K27").  The unit's work block is made by the first
+ * call, grown as needed and freed by slamhip_hs_pg_clear / _destroy; a caller that never asks allocates nothing.  Blocking, on the
+ * operator's stream, with the context's bounded wait.  SLAMHIP_ERR_INVALID, nothing launched and nothing written: a spec outside the
+ * ranges above, a value that is not finite, reserved != 0, P or an index out of range, C above the cap.  SLAMHIP_ERR_STATE: no graph. */
+int32_t slamhip_hs_pg_marginals(slamhip_hs *hs, const slamhip_pg_marg_spec *spec, const int32_t *pairs, int32_t P, double *out_blocks,
+                                slamhip_pg_marg_col *out_cols, int32_t *out_n_cols, slamhip_pg_marg_info *out_info);
+/* Test hook (no device involved), from the header text the kernels run (hs_pg.h, hs_pg_tri.h, hs_pg_marg.h) in plain loops, its PCG the
+ * one of slamhip_debug_pg_relax: the graph arguments and refusals of slamhip_debug_pg_relax (the poses are not written), then the tail
+ * and the refusals of slamhip_hs_pg_marginals.  info.group is what the device call would report. */
+int32_t slamhip_debug_pg_marginals(const double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w,
+                                   int32_t E, const slamhip_pg_marg_spec *spec, const int32_t *pairs, int32_t P, double *out_blocks,
+                                   slamhip_pg_marg_col *out_cols, int32_t *out_n_cols, slamhip_pg_marg_info *out_info);
+
 /* MapRepMultiMap.UpdateByScan ->OccGridMap.UpdateByScan on every level (MapRepMultiMap.cs:73-77;
  * OccGridMap.cs:114-239), all levels in one launch sequence. */
 int32_t slamhip_hs_update_by_scan(slamhip_hs *hs, const float robot_pose_world[3]);

@@ -198,6 +198,14 @@ PG_LM_SPEC = np.dtype([("n_outer", np.int32), ("n_cg", np.int32), ("check_every"
 PG_LM_ITER = np.dtype([("F", np.float64), ("F_trial", np.float64), ("lambda", np.float64), ("rz0", np.float64), ("rz", np.float64),
                        ("cg_iters", np.int32), ("stopped", np.int32), ("accepted", np.int32), ("reserved", np.int32, (3,))])   # slamhip_pg_lm_iter: 64 bytes
 assert PG_LM_SPEC.itemsize == 88 and PG_LM_ITER.itemsize == 64
+PG_MARG_MAX_PAIRS, PG_MARG_MAX_COLS, PG_MARG_GROUP = 1 << 20, 4096, 1                              # the limits of slamhip_hs_pg_marginals; k27's default G
+PG_MARG_SPEC = np.dtype([("n_cg", np.int32), ("check_every", np.int32), ("precond", np.int32), ("reserved", np.int32), ("lambda", np.float64),
+                         ("tol", np.float64), ("max_bytes", np.int64)])                            # slamhip_pg_marg_spec: 40 bytes
+PG_MARG_COL = np.dtype([("rz0", np.float64), ("rz", np.float64), ("cg_iters", np.int32), ("stopped", np.int32), ("node", np.int32),
+                        ("comp", np.int32)])                                                        # slamhip_pg_marg_col: 32 bytes
+PG_MARG_INFO = np.dtype([("n_cols", np.int32), ("n_rhs", np.int32), ("rhs_per_chunk", np.int32), ("n_chunks", np.int32), ("group", np.int32),
+                         ("reserved", np.int32, (3,))])                                             # slamhip_pg_marg_info: 32 bytes
+assert PG_MARG_SPEC.itemsize == 40 and PG_MARG_COL.itemsize == 32 and PG_MARG_INFO.itemsize == 32
 SCANMATCH_MAX_HALF, SCANMATCH_MAX_N, SCANMATCH_MAX_PAIRS, SCANMATCH_MAX_NODES, SCANMATCH_MAX_CALL_NODES = 192, 64, 4096, 1 << 20, 1 << 26   # the limits of slamhip_hs_scans_match
 SCANMATCH_SPEC = np.dtype([("scale", np.float32), ("half", np.int32), ("nx", np.int32), ("ny", np.int32), ("nt", np.int32), ("dtheta", np.float32),
                            ("margin", np.int32), ("reserved", np.int32)])                                # slamhip_scanmatch_spec: 32 bytes
@@ -307,6 +315,7 @@ def _declare(L):
         "slamhip_debug_pg_relax_tri": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
         "slamhip_debug_pg_tri_apply": (i32, [vp, vp, i32, vp, vp, vp, i32, C.c_double, vp, vp]),
         "slamhip_debug_pg_relax_lm": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
+        "slamhip_debug_pg_marginals": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]),
         "slamhip_debug_scans_match": (i32, [vp, vp, i32, vp, vp, i32, vp]),
         "slamhip_debug_loops_consistent": (i32, [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]),
         "slamhip_debug_render": (i32, [i32, vp, f, vp, vp, vp, f, f, vp, vp, vp, vp, i32, i32]),
@@ -434,6 +443,7 @@ def _declare(L):
         "slamhip_hs_pg_relax_tri": (i32, [vp, vp, vp, vp]),
         "slamhip_hs_pg_tri_apply": (i32, [vp, C.c_double, vp, vp]),
         "slamhip_hs_pg_relax_lm": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "slamhip_hs_pg_marginals": (i32, [vp, vp, vp, i32, vp, vp, vp, vp]),
         "slamhip_hs_pg_get": (i32, [vp, vp, i32]),
         "slamhip_hs_pg_residuals": (i32, [vp, vp, vp]),
         "slamhip_hs_pg_clear": (i32, [vp]),
@@ -1151,6 +1161,69 @@ def debug_pg_relax_lm(poses, fixed, ij, z, w, spec, robust=None):
     assert e.shape[0] == zz.shape[0] == ww.shape[0] and (fx is None or fx.shape[0] == p.shape[0])
     it, fin, f = pg_relax_lm_call("slamhip_debug_pg_relax_lm", (_vp(p), _vp(fx), p.shape[0], _vp(e), _vp(zz), _vp(ww), e.shape[0]), e.shape[0], spec, robust)
     return p, it, fin, f
+
+
+def pg_marg_spec(n_cg, check_every=None, precond="tri", lam=0.0, tol=1e-9, max_bytes=0, reserved=0):
+    """A slamhip_pg_marg_spec record (a (1,) PG_MARG_SPEC array); check_every defaults to min(n_cg, 64); precond "jacobi" / "tri" by
+    name, or the header's numbers; max_bytes 0: the library's 256 MiB."""
+    sp = np.zeros(1, PG_MARG_SPEC)
+    sp["n_cg"] = int(n_cg); sp["check_every"] = min(int(n_cg), 64) if check_every is None else int(check_every)
+    sp["precond"] = PG_LM_PRECOND.get(precond, precond); sp["reserved"] = int(reserved)
+    sp["lambda"] = float(lam); sp["tol"] = float(tol); sp["max_bytes"] = int(max_bytes)
+    return sp
+
+
+def pg_marg_rhs_bytes(N, precond):
+    """Rule M5's B of slamhip_hs_pg_marginals: the bytes of one right-hand side in the work block."""
+    N = int(N); tot = 0; n = N
+    while True:
+        tot += n
+        if n == 1:
+            break
+        n = (n + 1) // 2
+    return 120 * N + 16 * ((N + 255) // 256) + 40 + (24 * (tot - N) + 24 if PG_LM_PRECOND.get(precond, precond) else 0)
+
+
+def pg_marginals_call(entry, head, spec, pairs):
+    """The tail of slamhip_hs_pg_marginals / slamhip_debug_pg_marginals behind the arguments `head`
+    -> (blocks (P, 3, 3) float64, cols PG_MARG_COL (R,), info: a PG_MARG_INFO record)."""
+    pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+    P = pr.shape[0]
+    blocks = np.zeros((max(P, 1), 3, 3), np.float64); cols = np.zeros(3 * max(min(P, PG_MARG_MAX_COLS), 1), PG_MARG_COL)
+    n = C.c_int32(0); info = np.zeros(1, PG_MARG_INFO)
+    call(entry, *head, spec.ctypes.data_as(C.c_void_p), _vp(pr), P, blocks.ctypes.data_as(C.c_void_p), cols.ctypes.data_as(C.c_void_p), C.byref(n),
+         info.ctypes.data_as(C.c_void_p))
+    return blocks[:P], cols[:n.value].copy(), info[0]
+
+
+def debug_pg_marginals(poses, fixed, ij, z, w, spec, pairs):
+    """The whole definition of slamhip_hs_pg_marginals on the host (slamhip_debug_pg_marginals; no device involved)
+    -> (blocks (P, 3, 3), cols PG_MARG_COL (R,), info).  The caller's arrays are not written."""
+    p, fx, e, zz, ww = pg_graph(poses, fixed, ij, z, w)
+    assert e.shape[0] == zz.shape[0] == ww.shape[0] and (fx is None or fx.shape[0] == p.shape[0])
+    return pg_marginals_call("slamhip_debug_pg_marginals", (_vp(p), _vp(fx), p.shape[0], _vp(e), _vp(zz), _vp(ww), e.shape[0]), spec, pairs)
+
+
+def pg_relative_covariance(pose_i, pose_j, S_ii, S_ij, S_ji, S_jj):
+    """The 3 x 3 covariance of rule 3's predicted measurement of an edge (i, j) -- node j seen in node i's frame -- from the four
+    marginal blocks of the two nodes: A S_ii A^T + A S_ij B^T + B S_ji A^T + B S_jj B^T, A and B rule 3's Jacobians at the two poses.
+    Host NumPy in binary64."""
+    xi, yi, ti = (float(v) for v in pose_i); xj, yj, _ = (float(v) for v in pose_j)
+    c, s = math.cos(ti), math.sin(ti)
+    dx, dy = xj - xi, yj - yi
+    ux, uy = c * dx + s * dy, c * dy - s * dx
+    A = np.array([[-c, -s, uy], [s, -c, -ux], [0.0, 0.0, -1.0]], np.float64)
+    B = np.array([[c, s, 0.0], [-s, c, 0.0], [0.0, 0.0, 1.0]], np.float64)
+    S_ii, S_ij, S_ji, S_jj = (np.asarray(S, np.float64).reshape(3, 3) for S in (S_ii, S_ij, S_ji, S_jj))
+    return A @ S_ii @ A.T + A @ S_ij @ B.T + B @ S_ji @ A.T + B @ S_jj @ B.T
+
+
+def pg_mahalanobis(r, S_rel, w):
+    """r^T (S_rel + diag(1 / w))^-1 r: the squared Mahalanobis distance of an edge's residual r under the graph's relative covariance
+    S_rel (pg_relative_covariance) and the edge's own weights w.  Host NumPy in binary64."""
+    r = np.asarray(r, np.float64).reshape(3)
+    S = np.asarray(S_rel, np.float64).reshape(3, 3) + np.diag(1.0 / np.asarray(w, np.float64).reshape(3))
+    return float(r @ np.linalg.solve(S, r))
 
 
 def debug_pg_tri_apply(poses, fixed, ij, z, w, lam, rhs):

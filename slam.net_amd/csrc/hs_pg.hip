@@ -2,9 +2,10 @@
 // preconditioned conjugate gradients (slamhip_hs_pg_set, _pg_relax, _pg_get, _pg_residuals, _pg_clear, slamhip_debug_pg_relax, _pg_sum,
 // _sincos).  No reference counterpart.  Definition: include/slamhip.h (slamhip_hs_pg_relax); the arithmetic host and device share:
 // hs_pg.h -- the per-node loops of rules 4 and 5 included, so a kernel and the host hook differ only in who walks the nodes.
-// K22 (hs_pg_tri.inc) and K26 (hs_pg_lm.inc) are the later parts of this translation unit.  The three share ONE PCG enqueue loop
-// (hs_pg_pcg), ONE "n_outer steps, final chi2, read-back" (hs_pg_relax_run) and ONE host definition (hs_pg_host_relax), each with the
-// preconditioner as an argument; they stand in hs_pg_tri.inc, behind K22's launch functions and host text, which they call.
+// K22 (hs_pg_tri.inc), K26 (hs_pg_lm.inc) and K27 (hs_pg_marg.inc) are the later parts of this translation unit.  They share ONE PCG
+// enqueue loop (hs_pg_pcg_loop, behind hs_pg_pcg and K27's batch), ONE "n_outer steps, final chi2, read-back" (hs_pg_relax_run) and ONE
+// host definition (hs_pg_host_relax, its PCG hs_pg_host_pcg), each with the preconditioner as an argument; they stand in hs_pg_tri.inc,
+// behind K22's launch functions and host text, which they call.
 //
 // The graph lies in ONE device block: the poses, the fixed bytes, the edges (ij, z, w) and the node -> (edge, side) lists the host
 // builds by a counting sort that keeps the edge order (off[N + 1], inc[2 E], an entry edge << 1 | side), then what the kernels write.
@@ -24,6 +25,7 @@
 #include "hs_pg.h"
 #include "hs_pg_tri.h"
 #include "hs_pg_lm.h"
+#include "hs_pg_marg.h"
 #include <algorithm>
 #include <string.h>
 #include <vector>
@@ -295,6 +297,8 @@ struct hs_pg {
     unsigned char *d_tri; size_t cap_tri;                  // K22 (hs_pg_tri.inc): the levels' blocks, made by the first _pg_relax_tri / _pg_tri_apply
     hs_tri_plan T;
     unsigned char *d_lm; size_t cap_lm;                    // K26 (hs_pg_lm.inc): the weights, the trial poses and the records, made by the first _pg_relax_lm
+    unsigned char *d_marg; size_t cap_marg;                // K27 (hs_pg_marg.inc): the query and the batch's work block, made by the first _pg_marginals
+    std::vector<unsigned char> fx;                         // the fixed bytes as the device has them: K27 forms its columns on the host
 };
 
 void hs_pg_free(slamhip_hs *hs)
@@ -305,6 +309,7 @@ void hs_pg_free(slamhip_hs *hs)
     hs_release((void **)&g->h_io, &g->cap_h, HS_MEM_PINNED);
     hs_release((void **)&g->d_tri, &g->cap_tri, HS_MEM_DEVICE);
     hs_release((void **)&g->d_lm, &g->cap_lm, HS_MEM_DEVICE);
+    hs_release((void **)&g->d_marg, &g->cap_marg, HS_MEM_DEVICE);
     delete g;
     hs->pg = nullptr;
 }
@@ -415,6 +420,7 @@ extern "C" int32_t slamhip_hs_pg_set(slamhip_hs *hs, const double *poses, const 
     unsigned char *h = g->h_io, *d = g->d_blob;
     memcpy(h + o_pose, poses, 24 * n);
     hs_pg_fixed_bytes(fixed, N, h + o_fixed);
+    g->fx.assign(h + o_fixed, h + o_fixed + n);
     if (E) { memcpy(h + o_ij, ij, 8 * e); memcpy(h + o_z, z, 24 * e); memcpy(h + o_w, w, 24 * e); }
     hs_pg_lists(N, ij, E, (int32_t *)(h + o_off), (int32_t *)(h + o_inc));
     SH_HIP(hipMemcpyAsync(d, h, in_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -549,3 +555,4 @@ extern "C" int32_t slamhip_debug_sincos(const double *a, int32_t n, double *out_
 
 #include "hs_pg_tri.inc"
 #include "hs_pg_lm.inc"
+#include "hs_pg_marg.inc"

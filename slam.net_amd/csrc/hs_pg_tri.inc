@@ -3,8 +3,9 @@
 // _pg_tri_apply).  The second part of hs_pg.hip's translation unit: it launches k19_linearise, k19_begin, k19_apply, k19_step<false>,
 // k19_dir and k19_update as they are and shares their device helpers.  Definition: include/slamhip.h, rules T1 - T5; the arithmetic
 // host and device share: hs_pg_tri.h, the per-node loop of rule T2 and rule T3's choice of neighbours included.  Behind K22's launch
-// functions stand the unit's PCG driver and relax call (hs_pg_pcg, hs_pg_relax_run), behind its host text the unit's host definition
-// (hs_pg_host_relax): K19, K22 and K26 all go through them, with the preconditioner as an argument.
+// functions stand the unit's enqueue loop, PCG driver and relax call (hs_pg_pcg_loop, hs_pg_pcg, hs_pg_relax_run), behind its host text
+// the unit's host definition (hs_pg_host_sys, hs_pg_host_pcg, hs_pg_host_relax): K19, K22 and K26 all go through them, with the
+// preconditioner as an argument, and K27 (hs_pg_marg.inc) through the loop and the host PCG.
 //  * k22_diag: a lane per node, rule 4's D_n and g_n over the node's list, rule T1, P = D^-1; for PCG x = 0 and res = -g.
 //  * k22_coupling: a lane per node, rule T2 over the same list.
 //  * k22_reduce: one launch per level with more than S blocks, a lane per block of the NEXT level, rule T3.
@@ -213,8 +214,24 @@ static int32_t hs_tri_solve(hs_pg *g, hipStream_t st, const k22_io &io)
     return SLAMHIP_OK;
 }
 
-// The unit's PCG driver: rules 4 - 7 (tri: T1 - T5) up to the pose update, over A's weights at the linearisation k19_linearise has
-// left.  Batches of check_every iterations, the stop word read back into h_st (pinned) between them.
+// The unit's ONE enqueue loop: batches of check_every PCG iterations (iteration(k) enqueues one), the stop words -- stop_bytes at
+// d_stop -- read back into h_stop (pinned) in one copy between them, until all_stopped() says so or n_cg is reached.  K19, K22 and K26
+// run it over one right-hand side (hs_pg_pcg), K27 over a chunk of them (hs_pg_marg.inc).
+template <class Iteration, class AllStopped>
+static int32_t hs_pg_pcg_loop(slamhip_hs *hs, int n_cg, int check_every, const void *d_stop, void *h_stop, size_t stop_bytes, Iteration iteration, AllStopped all_stopped)
+{
+    for (int k = 0; k < n_cg;) {
+        const int k1 = (int)std::min<int64_t>((int64_t)k + std::min(check_every, K19_MAX_BATCH), n_cg);
+        for (; k < k1; k++) SH_TRY(iteration(k));
+        SH_HIP(hipMemcpyAsync(h_stop, d_stop, stop_bytes, hipMemcpyDeviceToHost, hs->ctx->stream));
+        SH_TRY(hs_call_finish(hs));                                        // (the stop words, between batches)
+        if (all_stopped()) break;
+    }
+    return SLAMHIP_OK;
+}
+
+// The unit's PCG driver for one right-hand side: rules 4 - 7 (tri: T1 - T5) up to the pose update, over A's weights at the
+// linearisation k19_linearise has left.
 static int32_t hs_pg_pcg(slamhip_hs *hs, hs_pg *g, const k19_arg &A, bool tri, double lambda, int n_cg, int check_every, double tol, k19_state *h_st)
 {
     hipStream_t st = hs->ctx->stream;
@@ -226,29 +243,24 @@ static int32_t hs_pg_pcg(slamhip_hs *hs, hs_pg *g, const k19_arg &A, bool tri, d
         K19_LAUNCH(k19_diag, A.PN, A, lambda);
     }
     K19_LAUNCH(k19_begin, 1, A, 0);
-    for (int k = 0; k < n_cg;) {
-        const int k1 = (int)std::min<int64_t>((int64_t)k + std::min(check_every, K19_MAX_BATCH), n_cg);
-        for (; k < k1; k++) {
-            K19_LAUNCH(k19_apply, A.PN, A, k, lambda, tol);
+    auto iteration = [&](int k) -> int32_t {
+        K19_LAUNCH(k19_apply, A.PN, A, k, lambda, tol);
 #if K19_SCALAR_LAUNCH
-            K19_LAUNCH(k19_scal_a, 1, A, k);
+        K19_LAUNCH(k19_scal_a, 1, A, k);
 #endif
-            if (tri) {
-                K19_LAUNCH(k19_step<false>, A.PN, A, k);
-                SH_TRY(hs_tri_solve(g, st, io));
-            } else {
-                K19_LAUNCH(k19_step<true>, A.PN, A, k);
-            }
-#if K19_SCALAR_LAUNCH
-            K19_LAUNCH(k19_scal_b, 1, A, k);
-#endif
-            K19_LAUNCH(k19_dir, A.PN, A, k);
+        if (tri) {
+            K19_LAUNCH(k19_step<false>, A.PN, A, k);
+            SH_TRY(hs_tri_solve(g, st, io));
+        } else {
+            K19_LAUNCH(k19_step<true>, A.PN, A, k);
         }
-        SH_HIP(hipMemcpyAsync(h_st, A.st, sizeof(k19_state), hipMemcpyDeviceToHost, st));
-        SH_TRY(hs_call_finish(hs));                                        // (the stop word, between batches)
-        if (h_st->stop) break;
-    }
-    return SLAMHIP_OK;
+#if K19_SCALAR_LAUNCH
+        K19_LAUNCH(k19_scal_b, 1, A, k);
+#endif
+        K19_LAUNCH(k19_dir, A.PN, A, k);
+        return SLAMHIP_OK;
+    };
+    return hs_pg_pcg_loop(hs, n_cg, check_every, A.st, h_st, sizeof(k19_state), iteration, [&]() { return h_st->stop != 0; });
 }
 
 static int32_t hs_pg_relax_run(slamhip_hs *hs, const slamhip_pg_spec *spec, bool tri, const char *who, slamhip_pg_iter *out_iters, double *out_chi2_final)
@@ -379,65 +391,104 @@ static void hs_tri_host_solve(hs_tri_host &H, const double *r0, double *z0)
 
 // The definition of K19 (block-Jacobi) and of K22 (tri) over a graph and a spec that have been checked; K26's hook takes single steps
 // through it, with its own weights.  tri is read where the preconditioner is made and where z is formed from res, nowhere else.
+// what the host definition keeps of a graph: the lists, one linearisation with its preconditioner, and PCG's vectors
+struct hs_pg_host_sys {
+    bool tri; int N, E; const int32_t *ij; double lambda;
+    hs_pg_host_lists G;
+    hs_tri_host H;
+    std::vector<hs_pg_rec> rec;
+    std::vector<double> r, tmp, M, g, x, res, zv, p, q;
+};
+
+static void hs_pg_host_sys_init(hs_pg_host_sys &S, bool tri, const uint8_t *fixed, int N, const int32_t *ij, int E)
+{
+    const size_t n3 = 3 * (size_t)N;
+    S.tri = tri; S.N = N; S.E = E; S.ij = ij; S.lambda = 0.0;
+    hs_pg_host_lists_init(S.G, fixed, N, ij, E);
+    if (tri) hs_tri_host_init(S.H, N);
+    S.rec.resize((size_t)E + 1);
+    S.r.resize(3 * (size_t)E + 3); S.tmp.resize((size_t)std::max(N, E) + HS_PG_BLOCK); S.M.resize(tri ? 0 : 6 * (size_t)N);
+    for (std::vector<double> *v : { &S.g, &S.x, &S.res, &S.zv, &S.p, &S.q }) v->resize(n3);
+}
+
+// rules 3 and 4 (tri: T1 - T3) at the poses: the records, chi2 (returned), g and the preconditioner for this lambda
+static double hs_pg_host_sys_linearise(hs_pg_host_sys &S, const double *poses, const double *z, const double *w, double lambda)
+{
+    const hs_pg_host_lists &G = S.G;
+    S.lambda = lambda;
+    const double chi2 = hs_pg_host_linearise(poses, S.ij, z, w, S.E, S.rec.data(), S.r.data(), S.tmp.data());
+    if (S.tri) hs_tri_host_factor(S.H, G, S.N, S.ij, S.rec.data(), S.r.data(), lambda, S.g.data());
+    else for (int n = 0; n < S.N; n++) {                                   // rule 4: M = 0 and g = 0 for a fixed node
+        double D[6], *gn = S.g.data() + 3 * (size_t)n, *Mn = S.M.data() + 6 * (size_t)n;
+        gn[0] = gn[1] = gn[2] = 0.0;
+        for (int m = 0; m < 6; m++) Mn[m] = 0.0;
+        if (G.fx[(size_t)n]) continue;
+        hs_pg_node_diag(lambda, n, G.off.data(), G.inc.data(), S.rec.data(), S.r.data(), D, gn);
+        (void)hs_pg_inv(D, Mn);
+    }
+    return chi2;
+}
+
+// THE PCG of the host definition, rule 7 from "z = M res" on: the caller has put rule 7's right-hand side into S.res; x is left in
+// S.x and rz0, rz, cg_iters and stopped in *I.  apply(n, p, q_n) is rule 5 for the free node n.  S.tri is read where z is formed from
+// res, nowhere else.
+template <class Apply>
+static void hs_pg_host_pcg(hs_pg_host_sys &S, int n_cg, double tol, Apply apply, slamhip_pg_iter *I)
+{
+    const int N = S.N;
+    const size_t n3 = 3 * (size_t)N;
+    std::vector<double> &x = S.x, &res = S.res, &zv = S.zv, &p = S.p, &q = S.q, &tmp = S.tmp;
+    auto precondition = [&]() {                                            // z from res
+        if (S.tri) hs_tri_host_solve(S.H, res.data(), zv.data());
+        else for (int n = 0; n < N; n++) hs_pg_mul(S.M.data() + 6 * (size_t)n, res.data() + 3 * (size_t)n, zv.data() + 3 * (size_t)n);
+    };
+    for (size_t i = 0; i < n3; i++) x[i] = 0.0;
+    precondition();
+    p = zv;
+    double rz = hs_pg_host_dot(res.data(), zv.data(), N, tmp.data());
+    I->rz0 = rz;
+    int k = 0, stopped;
+    for (;; k++) {
+        if (hs_pg_converged(rz, I->rz0, tol)) { stopped = HS_PG_STOP_TOL; break; }
+        if (k == n_cg) { stopped = HS_PG_STOP_NCG; break; }
+        for (int n = 0; n < N; n++) {                                      // rule 5: q = 0 for a fixed node
+            double *qn = q.data() + 3 * (size_t)n;
+            qn[0] = qn[1] = qn[2] = 0.0;
+            if (!S.G.fx[(size_t)n]) apply(n, p.data(), qn);
+        }
+        const double pq = hs_pg_host_dot(p.data(), q.data(), N, tmp.data());
+        if (hs_pg_breakdown(pq)) { stopped = HS_PG_STOP_BREAKDOWN; break; }
+        const double alpha = rz / pq;
+        for (size_t i = 0; i < n3; i++) { x[i] = x[i] + alpha * p[i]; res[i] = res[i] - alpha * q[i]; }
+        precondition();
+        const double rzn = hs_pg_host_dot(res.data(), zv.data(), N, tmp.data());
+        const double beta = rzn / rz;
+        for (size_t i = 0; i < n3; i++) p[i] = zv[i] + beta * p[i];
+        rz = rzn;
+    }
+    I->rz = rz; I->cg_iters = k; I->stopped = stopped;
+}
+
 static void hs_pg_host_relax(bool tri, double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,
                              const slamhip_pg_spec *spec, slamhip_pg_iter *out_iters, double *out_chi2_final, double *out_r, double *out_chi2)
 {
-    const size_t n3 = 3 * (size_t)N, pad = HS_PG_BLOCK;
-    hs_pg_host_lists G;
-    hs_pg_host_lists_init(G, fixed, N, ij, E);
-    hs_tri_host H;
-    if (tri) hs_tri_host_init(H, N);
-    std::vector<hs_pg_rec> rec((size_t)E + 1);
-    std::vector<double> r(3 * (size_t)E + 3), tmp((size_t)std::max(N, E) + pad), M(tri ? 0 : 6 * (size_t)N), g(n3), x(n3), res(n3), zv(n3), p(n3), q(n3);
-    const double lambda = spec->lambda, tol = spec->tol;
-    auto precondition = [&]() {                                            // z from res
-        if (tri) hs_tri_host_solve(H, res.data(), zv.data());
-        else for (int n = 0; n < N; n++) hs_pg_mul(M.data() + 6 * (size_t)n, res.data() + 3 * (size_t)n, zv.data() + 3 * (size_t)n);
-    };
+    const size_t n3 = 3 * (size_t)N;
+    hs_pg_host_sys S;
+    hs_pg_host_sys_init(S, tri, fixed, N, ij, E);
+    const hs_pg_host_lists &G = S.G;
+    auto apply = [&](int n, const double *p, double *qn) { hs_pg_node_apply(S.lambda, p, n, G.off.data(), G.inc.data(), S.rec.data(), ij, qn); };
     for (int outer = 0; outer < spec->n_outer; outer++) {
         slamhip_pg_iter I;
-        I.chi2 = hs_pg_host_linearise(poses, ij, z, w, E, rec.data(), r.data(), tmp.data());
-        if (tri) hs_tri_host_factor(H, G, N, ij, rec.data(), r.data(), lambda, g.data());
-        else for (int n = 0; n < N; n++) {                                 // rule 4: M = 0 and g = 0 for a fixed node
-            double D[6], *gn = g.data() + 3 * (size_t)n, *Mn = M.data() + 6 * (size_t)n;
-            gn[0] = gn[1] = gn[2] = 0.0;
-            for (int m = 0; m < 6; m++) Mn[m] = 0.0;
-            if (G.fx[(size_t)n]) continue;
-            hs_pg_node_diag(lambda, n, G.off.data(), G.inc.data(), rec.data(), r.data(), D, gn);
-            (void)hs_pg_inv(D, Mn);
-        }
-        for (size_t i = 0; i < n3; i++) { x[i] = 0.0; res[i] = -g[i]; }    // rule 7's start
-        precondition();
-        p = zv;
-        double rz = hs_pg_host_dot(res.data(), zv.data(), N, tmp.data());
-        I.rz0 = rz;
-        int k = 0, stopped;
-        for (;; k++) {
-            if (hs_pg_converged(rz, I.rz0, tol)) { stopped = HS_PG_STOP_TOL; break; }
-            if (k == spec->n_cg) { stopped = HS_PG_STOP_NCG; break; }
-            for (int n = 0; n < N; n++) {                                  // rule 5: q = 0 for a fixed node
-                double *qn = q.data() + 3 * (size_t)n;
-                qn[0] = qn[1] = qn[2] = 0.0;
-                if (!G.fx[(size_t)n]) hs_pg_node_apply(lambda, p.data(), n, G.off.data(), G.inc.data(), rec.data(), ij, qn);
-            }
-            const double pq = hs_pg_host_dot(p.data(), q.data(), N, tmp.data());
-            if (hs_pg_breakdown(pq)) { stopped = HS_PG_STOP_BREAKDOWN; break; }
-            const double alpha = rz / pq;
-            for (size_t i = 0; i < n3; i++) { x[i] = x[i] + alpha * p[i]; res[i] = res[i] - alpha * q[i]; }
-            precondition();
-            const double rzn = hs_pg_host_dot(res.data(), zv.data(), N, tmp.data());
-            const double beta = rzn / rz;
-            for (size_t i = 0; i < n3; i++) p[i] = zv[i] + beta * p[i];
-            rz = rzn;
-        }
-        I.rz = rz; I.cg_iters = k; I.stopped = stopped;
+        I.chi2 = hs_pg_host_sys_linearise(S, poses, z, w, spec->lambda);
+        for (size_t i = 0; i < n3; i++) S.res[i] = -S.g[i];                // rule 7's start
+        hs_pg_host_pcg(S, spec->n_cg, spec->tol, apply, &I);
         out_iters[outer] = I;
         for (int n = 0; n < N; n++)
-            if (!G.fx[(size_t)n]) hs_pg_add_pose(poses + 3 * (size_t)n, x.data() + 3 * (size_t)n);
+            if (!G.fx[(size_t)n]) hs_pg_add_pose(poses + 3 * (size_t)n, S.x.data() + 3 * (size_t)n);
     }
-    *out_chi2_final = hs_pg_host_linearise(poses, ij, z, w, E, rec.data(), r.data(), tmp.data());
-    if (out_r && E) memcpy(out_r, r.data(), 24 * (size_t)E);
-    if (out_chi2) for (int e = 0; e < E; e++) out_chi2[e] = rec[(size_t)e].chi2;
+    *out_chi2_final = hs_pg_host_linearise(poses, ij, z, w, E, S.rec.data(), S.r.data(), S.tmp.data());
+    if (out_r && E) memcpy(out_r, S.r.data(), 24 * (size_t)E);
+    if (out_chi2) for (int e = 0; e < E; e++) out_chi2[e] = S.rec[(size_t)e].chi2;
 }
 
 extern "C" int32_t slamhip_debug_pg_relax_tri(double *poses, const uint8_t *fixed, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t E,

@@ -722,6 +722,15 @@ class MapRepMultiMap:
         E = getattr(self, "_pg_sizes", (1, 0))[1]
         return capi.pg_relax_lm_call("slamhip_hs_pg_relax_lm", (self._h,), E, spec, robust)
 
+    def PgMarginals(self, pairs, spec, precond="tri"):
+        """Marginal covariances at the poses as they stand (slamhip_hs_pg_marginals, rules M1 - M5): pairs (P, 2) node indices (n, m);
+        spec a capi.pg_marg_spec record, or None for 200 iterations at tol 1e-9 with `precond` ("jacobi" / "tri"; a record has its own)
+        -> (blocks (P, 3, 3) float64: Sigma[n_p][m_p], +0 where either node is fixed; cols capi.PG_MARG_COL (R,): a record per
+        right-hand side; info: a capi.PG_MARG_INFO record).  Neither the poses nor a later PgRelax* change."""
+        if spec is None:
+            spec = capi.pg_marg_spec(200, precond=precond)
+        return capi.pg_marginals_call("slamhip_hs_pg_marginals", (self._h,), spec, pairs)
+
     def PgTriApply(self, lam, rhs):
         """z = T^-1 rhs at the poses as they stand (slamhip_hs_pg_tri_apply): the odometry-chain preconditioner alone, lambda = lam on
         the diagonal, rhs (N, 3) -> (N, 3) float64."""
@@ -1352,6 +1361,52 @@ class HectorSLAMProcessor:
         only; the caller judges the report."""
         return self.Relocalise(scan, hit["pose"], level, nx, ny, n_theta, dtheta, B=B, adopt=False, search=search, top=top)
 
+    def _keyframe_graph(self, loops, odom_w, fixed):
+        """The keyframe store's pose graph, handed to MapRep.PgSet: the store's poses as nodes, an odometry edge per pair of consecutive
+        keyframes (z from their stored poses, weights odom_w), then one edge per entry (i, j, z, w) of `loops` -> (poses, ij, z, w)."""
+        _, kp = self.MapRep.SigDownload()
+        N = kp.shape[0]
+        poses = kp.astype(np.float64)
+        ij = [(k, k + 1) for k in range(N - 1)]; z = [capi.pg_edge_between(poses[k], poses[k + 1]) for k in range(N - 1)]
+        w = [tuple(float(v) for v in odom_w)] * (N - 1)
+        for (i, j, zl, wl) in loops:
+            ij.append((int(i), int(j))); z.append(tuple(float(v) for v in zl)); w.append(tuple(float(v) for v in wl))
+        ij = np.array(ij, np.int32).reshape(-1, 2); z = np.array(z, np.float64).reshape(-1, 3); w = np.array(w, np.float64).reshape(-1, 3)
+        self.MapRep.PgSet(poses, fixed, ij, z, w)
+        return poses, ij, z, w
+
+    def KeyframeCovariances(self, pairs, odom_w, loops=(), spec=None, fixed=None):
+        """How well the keyframes are known relative to one another (host composition of slamhip_hs_pg_set and _pg_marginals; no
+        reference counterpart): the graph RelaxKeyframes builds, at the store's poses as they stand -- nothing is relaxed or written
+        back.  pairs (Q, 2) keyframe indices (i, j); the four marginal blocks of every pair are asked for in one query; spec a
+        capi.pg_marg_spec record (None: MapRep.PgMarginals' default, the odometry-chain preconditioner)
+        -> dict(blocks (Q, 2, 2, 3, 3): [[S_ii, S_ij], [S_ji, S_jj]], rel (Q, 3, 3): capi.pg_relative_covariance of them at the two
+        poses, cols, info)."""
+        poses = self._keyframe_graph(loops, odom_w, fixed)[0]
+        pr = np.asarray(pairs, np.int32).reshape(-1, 2)
+        ask = np.stack([pr[:, [0, 0]], pr[:, [0, 1]], pr[:, [1, 0]], pr[:, [1, 1]]], axis=1).reshape(-1, 2)
+        b, cols, info = self.MapRep.PgMarginals(ask, spec)
+        blocks = b.reshape(-1, 2, 2, 3, 3)
+        rel = np.stack([capi.pg_relative_covariance(poses[i], poses[j], q[0, 0], q[0, 1], q[1, 0], q[1, 1]) for (i, j), q in zip(pr, blocks)]) \
+            if pr.shape[0] else np.zeros((0, 3, 3))
+        return dict(blocks=blocks, rel=rel, cols=cols, info=info)
+
+    def LoopMahalanobis(self, loops, odom_w, accepted=(), spec=None, fixed=None):
+        """The squared Mahalanobis distance of every candidate loop edge (i, j, z, w) of `loops` against the graph WITHOUT that edge --
+        the odometry chain and the `accepted` loops --: rule 3's residual r of the candidate at the store's poses, and
+        capi.pg_mahalanobis(r, S_rel, w) with S_rel the pair's relative covariance (KeyframeCovariances) -> (d2 (len(loops),), the
+        KeyframeCovariances dict).  A candidate that lies within what the trajectory's uncertainty allows has d2 of the order of 3."""
+        loops = list(loops)
+        cov = self.KeyframeCovariances([(int(l[0]), int(l[1])) for l in loops], odom_w, loops=accepted, spec=spec, fixed=fixed)
+        _, kp = self.MapRep.SigDownload()
+        poses = kp.astype(np.float64)
+        d2 = np.zeros(len(loops))
+        for k, (i, j, zl, wl) in enumerate(loops):
+            ux, uy, dt = capi.pg_edge_between(poses[int(i)], poses[int(j)])
+            r = np.array([ux - zl[0], uy - zl[1], math.remainder(dt - zl[2], 2.0 * math.pi)])
+            d2[k] = capi.pg_mahalanobis(r, cov["rel"][k], wl)
+        return d2, cov
+
     def RelaxKeyframes(self, loops, odom_w, spec, fixed=None, precond="jacobi", lm=None):
         """Spread verified loops over the keyframe store's poses (host composition of slamhip_hs_pg_set, _pg_relax, _pg_get,
         _pg_residuals and slamhip_hs_sig_set_poses; no reference counterpart).  Nodes: the store's poses; an odometry edge joins every
@@ -1363,14 +1418,8 @@ class HectorSLAMProcessor:
         edges (spec and precond are not read: the record has its own), iters are capi.PG_LM_ITER records, and a fourth value follows:
         f, every edge's factor at the relaxed poses in chi2's order."""
         rep = self.MapRep
-        _, kp = rep.SigDownload()
-        N = kp.shape[0]
-        poses = kp.astype(np.float64)
-        ij = [(k, k + 1) for k in range(N - 1)]; z = [capi.pg_edge_between(poses[k], poses[k + 1]) for k in range(N - 1)]
-        w = [tuple(float(v) for v in odom_w)] * (N - 1)
-        for (i, j, zl, wl) in loops:
-            ij.append((int(i), int(j))); z.append(tuple(float(v) for v in zl)); w.append(tuple(float(v) for v in wl))
-        rep.PgSet(poses, fixed, np.array(ij, np.int32).reshape(-1, 2), np.array(z, np.float64).reshape(-1, 3), np.array(w, np.float64).reshape(-1, 3))
+        poses, ij, _, _ = self._keyframe_graph(loops, odom_w, fixed)
+        N = poses.shape[0]
         f = None
         if lm is None:
             iters, _ = rep.PgRelax(spec, precond=precond)

@@ -300,7 +300,92 @@ def child(flag, lib):
     return json.loads(r.stdout.decode().strip().splitlines()[-1])
 
 
+def marg_launches(N, precond, cols, info, check_every, n_cg):
+    """The launches the driver of slamhip_hs_pg_marginals enqueues, from its rule: once k19_linearise and the preconditioner; per chunk
+    k27_begin, the start's solve, k27_begin_state, batches of check_every iterations until every right-hand side of the chunk has
+    stopped (three launches each, and the solve's), k27_collect."""
+    lt, n = 0, N
+    while n > 1024:
+        n = (n + 1) // 2; lt += 1
+    solve = 2 * lt + 1 if precond else 0
+    once = 1 + (2 + lt + 1 if precond else 1)                              # k19_linearise; k22_diag, k22_coupling, k22_reduce per large level, k22_factor_tail
+    per_iter = 3 + solve
+    total = once
+    Rc = int(info["rhs_per_chunk"])
+    for r0 in range(0, int(info["n_rhs"]), Rc):
+        c = cols[r0:r0 + Rc]
+        need = int((c["cg_iters"] + (c["stopped"] == 0)).max())            # a tolerance stop is seen by the iteration after it
+        batch = min(check_every, 1024)
+        enq = min(n_cg, -(-max(need, 1) // batch) * batch)
+        total += 2 + solve + enq * per_iter + 1
+    return total
+
+
+def marg_main(out_path, kres_path):
+    """K27 (slamhip_hs_pg_marginals): the ring with 16 loops between free nodes of profiles/r28_hs_pg_tri.json at 10^3 and 10^4 nodes,
+    C = 64 columns spread over the ring (the four blocks of 32 pairs), precond = 1, tol = 1e-9, n_cg = 6 * 16 + 1.  Timed, each a blocking
+    call by the host clock: the default max_bytes with G = 1 (the default) and with G = 4 (SLAMHIP_K27_GROUP), and max_bytes = one right-hand side per
+    chunk -- the same kernels launched per right-hand side, the factorisation still done once.  The three are taken in alternation,
+    7 rounds after 2 warm-up rounds (the one-per-chunk call: 3 after 1), medians; every call's blocks are compared with the first's."""
+    ctx = hs.Context(0)
+    rep = hs.MapRepMultiMap(0.1, (64, 64), 1, ctx=ctx)
+    out = {"points": {}}
+    n_cg = 6 * 16 + 1
+    for N in (1000, 10000):
+        g = with_loops(ring, N, 16)
+        rep.PgSet(g[0], None, g[1], g[2], g[3])
+        nodes = (1 + (N - 2) * np.arange(64) // 64).astype(np.int32)
+        pairs = np.array([(a, b) for i, j in zip(nodes[0::2], nodes[1::2]) for a, b in ((i, i), (i, j), (j, i), (j, j))], np.int32)
+        B = capi.pg_marg_rhs_bytes(N, "tri")
+        runs = {"batched_g1": ("1", 0), "batched_g4": ("4", 0), "one_per_chunk": ("1", B)}
+        ts = {k: [] for k in runs}
+        ref = None; last = {}
+        for rnd in range(9):
+            for key, (G, mb) in runs.items():
+                if key == "one_per_chunk" and rnd not in (0, 2, 5, 8):
+                    continue
+                os.environ["SLAMHIP_K27_GROUP"] = G
+                spec = capi.pg_marg_spec(n_cg, check_every=32, precond="tri", tol=1e-9, max_bytes=mb)
+                t0 = time.perf_counter(); b, cols, info = rep.PgMarginals(pairs, spec); dt = time.perf_counter() - t0
+                ref = b if ref is None else ref
+                assert b.tobytes() == ref.tobytes()
+                last[key] = (cols, info)
+                if rnd >= 2 or (key == "one_per_chunk" and rnd > 0):
+                    ts[key].append(dt)
+        os.environ.pop("SLAMHIP_K27_GROUP", None)
+        rec = {"N": N, "E": int(g[1].shape[0]), "columns": 64, "rhs": 192, "n_cg": n_cg, "check_every": 32, "bytes_per_rhs": int(B)}
+        for key in runs:
+            cols, info = last[key]
+            rec[key] = dict(stats(ts[key]), rhs_per_chunk=int(info["rhs_per_chunk"]), n_chunks=int(info["n_chunks"]), group=int(info["group"]),
+                            launches=marg_launches(N, 1, cols, info, 32, n_cg), cg_iters_min=int(cols["cg_iters"].min()), cg_iters_max=int(cols["cg_iters"].max()),
+                            stopped=sorted(set(cols["stopped"].tolist())))
+        rec["one_per_chunk_over_batched_g1"] = rec["one_per_chunk"]["median_us"] / rec["batched_g1"]["median_us"]
+        rec["batched_g4_over_batched_g1"] = rec["batched_g4"]["median_us"] / rec["batched_g1"]["median_us"]
+        out["points"]["ring_loops16_%d" % N] = rec
+        print(json.dumps(rec), flush=True)
+    rep.close()
+    ctx.close()
+    if kres_path and os.path.exists(kres_path):                           # tools/kres.sh hs_pg.hip k27, one kernel per line
+        import re
+        out["kernel_resources"] = {}
+        for line in open(kres_path):
+            m = re.search(r"Name: (\S+).*?TotalSGPRs: (\d+).*?VGPRs: (\d+).*?ScratchSize \[bytes/lane\]: (\d+).*?Occupancy \[waves/SIMD\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", line)
+            if m:
+                out["kernel_resources"][m.group(1)] = {"sgprs": int(m.group(2)), "vgprs": int(m.group(3)), "scratch_bytes_per_lane": int(m.group(4)),
+                                                      "occupancy_waves_per_simd": int(m.group(5)), "lds_bytes": int(m.group(6))}
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
+    if "--marginals" in sys.argv:
+        rest = [a for a in sys.argv[1:] if a != "--marginals"]
+        kres = None
+        if "--kres" in rest:
+            at = rest.index("--kres"); kres = rest[at + 1]; rest = rest[:at] + rest[at + 2:]
+        marg_main(rest[0] if rest else os.path.join(ROOT, "profiles", "r34_hs_pg_marg.json"), kres)
+        return
     if "--update-only" in sys.argv:
         print(json.dumps({"update": db.update_us(), "lib": os.environ.get("SLAMHIP_LIB", "this tree")}))
         return
