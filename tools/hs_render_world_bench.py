@@ -11,9 +11,11 @@ scans are 64 distinct simulated scans of `rays` points used in turn (hs_render_b
 render's download of that square must equal K20's pyramid on level 0 or the run fails.  Beyond 64 a scan is drawn at poses it was not
 cast from and some lines leave the square: K20 drops them, the world render draws them into further tiles ("tiles" says how many
 exist afterwards; 5376 cover the square on the three levels), so "level0_equal" is reported and not required there.  With
-slam.net_amd/build/variants/parent.so present -- a build of the parent commit -- the EXISTING paths are timed in alternating fresh
-interpreters, this tree then the parent, three each: slamhip_hs_render (lap, N = 1024) and HectorSLAMProcessor.Update per scan
-(hs_dfield_bench.update_us) -> "existing_alternating"."""
+slam.net_amd/build/variants/parent.so present -- a build of the parent commit -- both renders and the processor are timed in
+alternating fresh interpreters, this tree then the parent, three each (--existing-only with SLAMHIP_LIB set): slamhip_hs_render
+on the lap's 2048^2 pyramid and slamhip_hs_render_world in the window, N = 64 and 1024 each, and HectorSLAMProcessor.Update per scan
+(hs_dfield_bench.update_us) -> "existing_alternating"; then slamhip_hs_render alone under SLAMHIP_K20_TILE=64 (--k20-only) ->
+"k20_tile_64_alternating"."""
 import argparse
 import json
 import os
@@ -51,22 +53,40 @@ def setup(rays):
     return lap, base
 
 
-def existing(a):
-    """slamhip_hs_render on the lap, N = 1024, and the processor's Update -> ms and us (whatever library SLAMHIP_LIB names)."""
-    ctx = hs.Context(0)
-    lap, base = setup(a.rays)
-    poses = rb.poses_for("lap", 1024, lap)
-    rep = hs.MapRepMultiMap(CELL, (WORLD, WORLD), LEVELS, ctx=ctx)
-    for k in range(1024):
-        rep.ScansAdd(hs.ScanCloud(base[k % 64]))
+def timed(a, call):
     t = []
     for it in range(a.warmup + a.reps):
         t0 = time.perf_counter()
-        rep.Render(poses)
+        call()
         if it >= a.warmup:
             t.append(time.perf_counter() - t0)
-    rep.close(); ctx.close()
-    return {"render_lap_1024_ms": median_ms(t), "update_us": db.update_us(), "lib": os.path.basename(os.environ.get("SLAMHIP_LIB", "this tree"))}
+    return median_ms(t)
+
+
+def existing(a):
+    """slamhip_hs_render and slamhip_hs_render_world on the lap, N = 64 and 1024, and the processor's Update -> ms and us (whatever
+    library SLAMHIP_LIB names; --k20-only: the first alone, for the other tile side)."""
+    ctx = hs.Context(0)
+    lap, base = setup(a.rays)
+    out = {"lib": os.path.basename(os.environ.get("SLAMHIP_LIB", "this tree")), "k20_tile": int(os.environ.get("SLAMHIP_K20_TILE", "32"))}
+    for n in (64, 1024):
+        poses = rb.poses_for("lap", n, lap)
+        reps = [hs.MapRepMultiMap(CELL, (WORLD, WORLD), LEVELS, ctx=ctx)]
+        if not a.k20_only:
+            reps.append(hs.MapRepMultiMap(CELL, (WIN, WIN), LEVELS, ctx=ctx))
+            reps[1].set_backing(a.tile, 1 << 30)
+        for k in range(n):
+            for rep in reps:
+                rep.ScansAdd(hs.ScanCloud(base[k % 64]))
+        out["render_lap_%d_ms" % n] = timed(a, lambda: reps[0].Render(poses))
+        if not a.k20_only:
+            out["render_world_%d_ms" % n] = timed(a, lambda: reps[1].RenderWorld(poses))
+        for rep in reps:
+            rep.close()
+    ctx.close()
+    if not a.k20_only:
+        out["update_us"] = db.update_us()
+    return out
 
 
 def rows_of(a):
@@ -127,9 +147,11 @@ def rows_of(a):
     return rows
 
 
-def child(args, lib=None):
+def child(args, lib=None, tile=None):
     env = dict(os.environ)
-    env.pop("SLAMHIP_LIB", None)
+    env.pop("SLAMHIP_LIB", None); env.pop("SLAMHIP_K20_TILE", None)
+    if tile:
+        env["SLAMHIP_K20_TILE"] = str(tile)
     if lib:
         env["SLAMHIP_LIB"] = lib
     r = subprocess.run([sys.executable, os.path.abspath(__file__)] + args, env=env, stdout=subprocess.PIPE, timeout=900, check=True)
@@ -145,6 +167,7 @@ def main():
     ap.add_argument("--tile", type=int, default=32)
     ap.add_argument("--out", default=None)
     ap.add_argument("--existing-only", action="store_true")
+    ap.add_argument("--k20-only", action="store_true")
     a = ap.parse_args()
     if a.existing_only:
         print(json.dumps(existing(a)))
@@ -155,12 +178,13 @@ def main():
         print(json.dumps(row), flush=True)
     parent = os.path.join(ROOT, "slam.net_amd", "build", "variants", "parent.so")
     if os.path.exists(parent):
-        common = ["--existing-only", "--reps", str(a.reps), "--warmup", str(a.warmup), "--rays", str(a.rays)]
-        out["existing_alternating"] = {"this_tree": [], "parent": []}
-        for _ in range(3):
-            out["existing_alternating"]["this_tree"].append(child(common))
-            out["existing_alternating"]["parent"].append(child(common, parent))
-        print(json.dumps(out["existing_alternating"]), flush=True)
+        common = ["--existing-only", "--reps", str(a.reps), "--warmup", str(a.warmup), "--rays", str(a.rays), "--tile", str(a.tile)]
+        for key, tile, more in (("existing_alternating", None, []), ("k20_tile_64_alternating", 64, ["--k20-only"])):
+            out[key] = {"this_tree": [], "parent": []}
+            for _ in range(3):
+                out[key]["this_tree"].append(child(common + more, None, tile))
+                out[key]["parent"].append(child(common + more, parent, tile))
+            print(json.dumps(out[key]), flush=True)
     if a.out:
         with open(a.out, "w") as f:
             json.dump(out, f, indent=1)
