@@ -112,6 +112,11 @@ int32_t slamhip_ctx_poisoned(slamhip_ctx *ctx, int32_t *out_flag);
 /* Test hook (no device involved): the wait loop of a blocking call on a caller-owned word -- returns SLAMHIP_OK once *flag has
  * reached `val` (wrap-safe), SLAMHIP_ERR_TIMEOUT after timeout_ms. */
 int32_t slamhip_debug_flag_wait(volatile uint32_t *flag, uint32_t val, int64_t timeout_ms);
+/* Test hook (no device involved): the device and pinned blocks that the Hector units K7 .. K27 of every
+ * slamhip_hs of the process hold at this moment, and their bytes.  A unit's block counts from its allocation to its release;
+ * slamhip_hs_destroy and the *_clear entry points release a unit's blocks.  The operator's own blocks (the levels, the scan, the
+ * K4 / K5 tables), the world staging and the tile pool of slamhip_hs_set_backing are not counted.  Either pointer may be NULL. */
+int32_t slamhip_debug_live_blocks(int64_t *out_blocks, int64_t *out_bytes);
 /* Test hook (no device involved): the planner of the scrolling window's backing store (slamhip_hs_set_backing) for one shift by
  * (dx, dy) of a pyramid of `levels` levels, level 0 w0 x h0, whose window lies at (ox, oy) before the shift, with tiles of
  * `tile` x `tile` cells.  World cell of window cell (x, y) on level l: ((ox >> l) + x, (oy >> l) + y); tile index floor(X / tile),

@@ -292,6 +292,7 @@ def _declare(L):
         "slamhip_ctx_poisoned": (i32, [vp, ip]),
         "slamhip_ctx_philox4x32_10": (i32, [vp, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]),
         "slamhip_debug_flag_wait": (i32, [P(C.c_uint32), C.c_uint32, i64]),
+        "slamhip_debug_live_blocks": (i32, [P(i64), P(i64)]),
         "slamhip_debug_backing_plan": (i32, [i32, i32, i32, i64, i64, i32, i32, i32, P(BackingJob), i32, ip]),
         "slamhip_debug_world_plan": (i32, [i32, i32, i64, i64, i64, i64, i32, i32, i32, P(WorldJob), i32, ip]),
         "slamhip_debug_lattice_cells": (i32, [f, fp, f, fp, i32, ip]),
@@ -553,6 +554,13 @@ def _declare(L):
         fn.restype = res
         fn.argtypes = args
     L._signatures = sig
+
+
+def live_blocks():
+    """(blocks, bytes) that the Hector units of every hs of the process hold right now (slamhip_debug_live_blocks; no device involved)."""
+    n, b = C.c_int64(), C.c_int64()
+    call("slamhip_debug_live_blocks", C.byref(n), C.byref(b))
+    return n.value, b.value
 
 
 def backing_plan(levels, w0, h0, ox, oy, dx, dy, tile):

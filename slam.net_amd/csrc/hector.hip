@@ -2,7 +2,7 @@
 // kernels over a level's cells.  K4 (scan matcher): hs_match.hip; K5 (grid update): hs_update.hip; K6 (scrolling window and its
 // backing store): hs_window.hip, the world behind them: hs_world.hip; K7 (pose-lattice search): hs_lattice.hip; HectorSLAMProcessor: hs_processor.hip; shared state and
 // helpers: hs_internal.h.
-#include "hs_internal.h"
+#include "hs_blocks.h"
 
 __global__ void k5_fill_cells(slamhip_cell *cells, float *prob, size_t n)
 {
@@ -104,6 +104,15 @@ __global__ void __launch_bounds__(256) k5_checksum_cells(const slamhip_cell *__r
 // ---- host side ---------------------------------------------------------------------------------------------------
 static float prob_to_logodds(float prob) { return hs_prob_to_logodds(prob); }   // OccGridMap.cs:86-90 (hs_internal.h: slamhip_debug_render forms them by the same text)
 
+// the units' live blocks (hs_block, hs_blocks.h)
+std::atomic<int64_t> hs_live_blocks{0}, hs_live_bytes{0};
+extern "C" int32_t slamhip_debug_live_blocks(int64_t *out_blocks, int64_t *out_bytes)
+{
+    if (out_blocks) *out_blocks = hs_live_blocks.load(std::memory_order_relaxed);
+    if (out_bytes) *out_bytes = hs_live_bytes.load(std::memory_order_relaxed);
+    return SLAMHIP_OK;
+}
+
 extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
 {
     if (!hs) return SLAMHIP_OK;
@@ -114,24 +123,7 @@ extern "C" int32_t slamhip_hs_destroy(slamhip_hs *hs)
         (void)hipFree(hs->lv[l].d_cells_alt); (void)hipFree(hs->lv[l].d_prob_alt);
     }
     hs_bk_free(hs);
-    hs_wp_free(hs);
-    hs_lat_free(hs);
-    hs_trc_free(hs);
-    hs_df_free(hs);
-    hs_fr_free(hs);
-    hs_nav_free(hs);
-    hs_ro_free(hs);
-    hs_mcl_free(hs);
-    hs_merge_free(hs);
-    hs_view_free(hs);
-    hs_nr_free(hs);
-    hs_hg_free(hs);
-    hs_sg_free(hs);
-    hs_pg_free(hs);
-    hs_scn_free(hs);
-    hs_smt_free(hs);
-    hs_lp_free(hs);
-    hs_bnb_free(hs);
+    hs_units_drop_all(hs);
     (void)hipFree(hs->d_pts_base); (void)hipFree(hs->d_io);
     if (hs->h_pts) (void)hipHostFree(hs->h_pts);
     if (hs->ev_pts) (void)hipEventDestroy(hs->ev_pts);

@@ -215,31 +215,14 @@ __global__ void __launch_bounds__(K24_LANES) k24_emit(const k24_arg A)
 // table's pinned staging; and the control block -- keys | counts | offsets | cursors -- with its pinned twin the results come back
 // through.
 struct hs_bnb {
-    uint32_t *d_maps; size_t cap_maps;
-    uint32_t *d_front[2]; size_t cap_front[2];
-    int32_t *d_u[2]; size_t cap_u[2];
-    unsigned char *d_jobs[2]; size_t cap_jobs[2];
-    unsigned char *h_jobs; size_t cap_hjobs;
-    unsigned char *d_ctl; size_t cap_ctl;
-    unsigned char *h_ctl; size_t cap_hctl;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_maps;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_front[2];
+    hs_block<int32_t, HS_MEM_DEVICE> d_u[2];
+    hs_block<unsigned char, HS_MEM_DEVICE> d_jobs[2];
+    hs_block<unsigned char, HS_MEM_PINNED> h_jobs;
+    hs_block<unsigned char, HS_MEM_DEVICE> d_ctl;
+    hs_block<unsigned char, HS_MEM_PINNED> h_ctl;
 };
-
-void hs_bnb_free(slamhip_hs *hs)
-{
-    hs_bnb *u = hs->bnb;
-    if (!u) return;
-    hs_release((void **)&u->d_maps, &u->cap_maps, HS_MEM_DEVICE);
-    for (int i = 0; i < 2; i++) {
-        hs_release((void **)&u->d_front[i], &u->cap_front[i], HS_MEM_DEVICE);
-        hs_release((void **)&u->d_u[i], &u->cap_u[i], HS_MEM_DEVICE);
-        hs_release((void **)&u->d_jobs[i], &u->cap_jobs[i], HS_MEM_DEVICE);
-    }
-    hs_release((void **)&u->h_jobs, &u->cap_hjobs, HS_MEM_PINNED);
-    hs_release((void **)&u->d_ctl, &u->cap_ctl, HS_MEM_DEVICE);
-    hs_release((void **)&u->h_ctl, &u->cap_hctl, HS_MEM_PINNED);
-    delete u;
-    hs->bnb = nullptr;
-}
 
 // rule 1, what needs no hs: the fields of the bnb record and the top grid against max_blocks (the lattice's own fields have been checked)
 static int32_t k24_check_fields(const char *who, const slamhip_bnb_spec *sp)
@@ -300,14 +283,14 @@ static int32_t k24_run(slamhip_hs *hs, const slamhip_bnb_spec *sp, const uint64_
     const hs_bnb_frame F = hs_bnb_frame_of(M.w, M.h, top);
     if (F.words * (size_t)(top + 1) > ((size_t)1 << 31))
         SH_FAIL(SLAMHIP_ERR_NOMEM, "%s: the %d pooled maps of %d x %d cells would take more than 8 GB", who, top + 1, M.w, M.h);
-    SH_TRY(hs_unit(&hs->bnb));
+    SH_TRY(hs_unit<&slamhip_hs::bnb>(hs));
     hs_bnb *u = hs->bnb;
     // the control block: keys | counts | offsets | cursors
     const size_t key_bytes = sizeof(uint64_t) * (size_t)n_theta, cnt_bytes = sizeof(int32_t) * 2 * (size_t)n_theta, idx_bytes = sizeof(int32_t) * (size_t)n_theta;
     const size_t o_cnt = key_bytes, o_off = o_cnt + cnt_bytes, o_cur = o_off + idx_bytes;
-    SH_TRY(hs_grow((void **)&u->d_maps, &u->cap_maps, sizeof(uint32_t) * F.words * (size_t)(top + 1), HS_MEM_DEVICE, who));
-    SH_TRY(hs_grow((void **)&u->d_ctl, &u->cap_ctl, o_cur + idx_bytes, HS_MEM_DEVICE, who));
-    SH_TRY(hs_grow((void **)&u->h_ctl, &u->cap_hctl, o_cur, HS_MEM_PINNED, who));
+    SH_TRY(u->d_maps.grow(sizeof(uint32_t) * F.words * (size_t)(top + 1), who));
+    SH_TRY(u->d_ctl.grow(o_cur + idx_bytes, who));
+    SH_TRY(u->h_ctl.grow(o_cur, who));
     k24_arg A;
     memset(&A, 0, sizeof(A));
     A.pts = hs->d_pts; A.n = hs->n_points;
@@ -316,7 +299,7 @@ static int32_t k24_run(slamhip_hs *hs, const slamhip_bnb_spec *sp, const uint64_
     A.stm = hs->lv[S->level].stm;
     A.S = *S;
     A.gx = hs_bnb_grid(S->nx, top); A.gcount = A.gx * hs_bnb_grid(S->ny, top);
-    A.keys = (unsigned long long *)u->d_ctl;
+    A.keys = (unsigned long long *)u->d_ctl.p;
     A.counts = (int32_t *)(u->d_ctl + o_cnt); A.off = (const int32_t *)(u->d_ctl + o_off); A.cursor = (int32_t *)(u->d_ctl + o_cur);
     SH_TRY(hs_flush_scan(hs));
     SH_HIP(hipMemsetAsync(u->d_ctl, 0, key_bytes, st));
@@ -331,7 +314,7 @@ static int32_t k24_run(slamhip_hs *hs, const slamhip_bnb_spec *sp, const uint64_
     int count = A.gcount * n_theta;                                        // |F_h| (rule 1: at most max_blocks <= 2^26 at the top)
     dim3 grid((unsigned)sh_div_up(A.gcount, K24_LANES), (unsigned)n_theta);
     std::vector<k24_job> jobs;
-    if (top > 0) SH_TRY(hs_grow((void **)&u->d_u[top & 1], &u->cap_u[top & 1], sizeof(int32_t) * (size_t)count, HS_MEM_DEVICE, who));
+    if (top > 0) SH_TRY(u->d_u[top & 1].grow(sizeof(int32_t) * (size_t)count, who));
     for (int h = top; h >= 0; h--) {
         A.h = h;
         A.u = u->d_u[h & 1];
@@ -351,10 +334,10 @@ static int32_t k24_run(slamhip_hs *hs, const slamhip_bnb_spec *sp, const uint64_
         // the set of level h - 1: whatever read it last (level h + 1) ended before this level's wait
         const int dst = (h - 1) & 1;
         const size_t job_bytes = sizeof(k24_job) * jobs.size();
-        SH_TRY(hs_grow((void **)&u->d_front[dst], &u->cap_front[dst], sizeof(uint32_t) * (size_t)total, HS_MEM_DEVICE, who));
-        if (h > 1) SH_TRY(hs_grow((void **)&u->d_u[dst], &u->cap_u[dst], sizeof(int32_t) * (size_t)total, HS_MEM_DEVICE, who));
-        SH_TRY(hs_grow((void **)&u->d_jobs[dst], &u->cap_jobs[dst], job_bytes, HS_MEM_DEVICE, who));
-        SH_TRY(hs_grow((void **)&u->h_jobs, &u->cap_hjobs, job_bytes, HS_MEM_PINNED, who));
+        SH_TRY(u->d_front[dst].grow(sizeof(uint32_t) * (size_t)total, who));
+        if (h > 1) SH_TRY(u->d_u[dst].grow(sizeof(int32_t) * (size_t)total, who));
+        SH_TRY(u->d_jobs[dst].grow(job_bytes, who));
+        SH_TRY(u->h_jobs.grow(job_bytes, who));
         unsigned char *d_next_jobs = u->d_jobs[dst];
         memcpy(u->h_jobs, jobs.data(), job_bytes);
         SH_HIP(hipMemcpyAsync((void *)A.off, h_off, idx_bytes, hipMemcpyHostToDevice, st));
@@ -369,7 +352,7 @@ static int32_t k24_run(slamhip_hs *hs, const slamhip_bnb_spec *sp, const uint64_
     }
     SH_HIP(hipMemcpyAsync(u->h_ctl, u->d_ctl, key_bytes, hipMemcpyDeviceToHost, st));
     SH_TRY(hs_call_finish(hs));
-    *keys = (const uint64_t *)u->h_ctl;
+    *keys = (const uint64_t *)u->h_ctl.p;
     *info = I;
     return SLAMHIP_OK;
 }

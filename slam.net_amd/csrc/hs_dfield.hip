@@ -110,8 +110,6 @@ __global__ void __launch_bounds__(K9S_LANES) k9_score(const k9s_arg A)
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 // The unit's blocks are hs->dfd, a hs_field_unit (hs_field.h): g and F of E, and the pose batch's.
-void hs_df_free(slamhip_hs *hs) { hs_field_unit_free(&hs->dfd); }
-
 int32_t hs_df_check(const char *who, int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius)
 {
     if (level < 0 || level >= n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "%s: level %d of %d", who, level, n_levels);
@@ -132,7 +130,7 @@ int32_t hs_df_check_score(const char *who, int n_levels, int32_t level, int32_t 
 // hs_field.h's, on this unit's blocks and kernels.
 int32_t hs_df_field_prepare(slamhip_hs *hs, int level, bool world, int site_mask, int radius, hs_class_map *M, hs_field *E)
 {
-    return hs_field_prepare(hs, &hs->dfd, "distance field", sizeof(uint8_t), level, world, radius, hs_df_outside(site_mask, radius), M, E);
+    return hs_field_prepare<&slamhip_hs::dfd>(hs, "distance field", sizeof(uint8_t), level, world, radius, hs_df_outside(site_mask, radius), M, E);
 }
 
 int32_t hs_df_field_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M, const hs_field *E, int site_mask)
@@ -145,7 +143,7 @@ extern "C" int32_t slamhip_hs_distance_field(slamhip_hs *hs, int32_t level, int3
 {
     SH_CHECK_ARG(hs && out_d2);
     SH_TRY(hs_df_check("distance field", hs->n_levels, level, world, site_mask, radius));
-    return hs_field_call(hs, &hs->dfd, "distance field", k9_rows, k9_cols, level, world != 0, site_mask, radius, hs_df_outside(site_mask, radius), x, y, w, h,
+    return hs_field_call<&slamhip_hs::dfd>(hs, "distance field", k9_rows, k9_cols, level, world != 0, site_mask, radius, hs_df_outside(site_mask, radius), x, y, w, h,
                          out_d2);
 }
 
@@ -170,7 +168,7 @@ extern "C" int32_t slamhip_hs_distance_score(slamhip_hs *hs, int32_t level, int3
     A.poses = pb->d_poses; A.chunks = chunks;
     A.stm = hs->lv[level].stm;
     A.E = E; A.r2 = radius * radius;
-    A.sums = (slamhip_distance_summary *)pb->d_out;
+    A.sums = (slamhip_distance_summary *)pb->d_out.p;
     A.points = out_points ? (uint16_t *)(pb->d_out + sum_bytes) : (uint16_t *)nullptr;
     hipLaunchKernelGGL(k9_score, dim3((unsigned)(B * chunks)), dim3(K9S_LANES), 0, hs->ctx->stream, A);
     SH_HIP(hipGetLastError());

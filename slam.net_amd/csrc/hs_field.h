@@ -81,27 +81,16 @@ __global__ void __launch_bounds__(256) hs_field_gather(const hs_field_of<T> E, i
 // What a unit needs, made by its first call and kept: the rows' values and the field of E, and the blocks of a pose batch, through
 // which a field call's rectangle leaves too.
 struct hs_field_unit {
-    void *d_g; size_t cap_g;
-    void *d_f; size_t cap_f;
+    hs_block<void, HS_MEM_DEVICE> d_g;
+    hs_block<void, HS_MEM_DEVICE> d_f;
     hs_pose_batch pb;
 };
-
-static inline void hs_field_unit_free(hs_field_unit **slot)
-{
-    hs_field_unit *u = *slot;
-    if (!u) return;
-    hs_release(&u->d_g, &u->cap_g, HS_MEM_DEVICE);
-    hs_release(&u->d_f, &u->cap_f, HS_MEM_DEVICE);
-    hs_pose_batch_release(&u->pb);
-    delete u;
-    *slot = nullptr;
-}
 
 // The plan of one field: the class map prepared (the world's plan refuses before anything is launched), E sized and refused if too
 // large, the unit's struct made if this is its first use, the rows' values (g_size bytes a cell) and the field grown.  Nothing is
 // launched.
-template <typename T>
-static inline int32_t hs_field_prepare(slamhip_hs *hs, hs_field_unit **slot, const char *who, size_t g_size, int level, bool world, int radius,
+template <auto SLOT, typename T>
+static inline int32_t hs_field_prepare(slamhip_hs *hs, const char *who, size_t g_size, int level, bool world, int radius,
                                        uint32_t outside, hs_class_map *M, hs_field_of<T> *E)
 {
     SH_TRY(hs_lat_pack_prepare(hs, level, world, M));
@@ -109,15 +98,15 @@ static inline int32_t hs_field_prepare(slamhip_hs *hs, hs_field_unit **slot, con
     if (ew * eh > HS_FIELD_MAX_E)
         SH_FAIL(SLAMHIP_ERR_INVALID, "%s: E, the map of level %d grown by the radius, is %lld x %lld cells, more than 2^26", who, level,
                 (long long)ew, (long long)eh);
-    SH_TRY(hs_unit(slot));
-    hs_field_unit *u = *slot;
+    SH_TRY(hs_unit<SLOT>(hs));
+    hs_field_unit *u = hs->*SLOT;
     E->ew = (int)ew; E->eh = (int)eh; E->pitch = ((int)ew + 3) & ~3;
     E->e_x0 = M->x0 - radius; E->e_y0 = M->y0 - radius;                    // (-2^28 < x0 <= 0: no overflow)
     E->outside = outside;
     const size_t cells = (size_t)E->pitch * (size_t)E->eh;
-    SH_TRY(hs_grow(&u->d_g, &u->cap_g, cells * g_size, HS_MEM_DEVICE, who));
-    SH_TRY(hs_grow(&u->d_f, &u->cap_f, cells * sizeof(T), HS_MEM_DEVICE, who));
-    E->f = (const T *)u->d_f;
+    SH_TRY(u->d_g.grow(cells * g_size, who));
+    SH_TRY(u->d_f.grow(cells * sizeof(T), who));
+    E->f = (const T *)u->d_f.p;
     return SLAMHIP_OK;
 }
 
@@ -130,17 +119,17 @@ static inline int32_t hs_field_enqueue(slamhip_hs *hs, hs_field_unit *u, void (*
     const hs_field_geo A = hs_field_geo_of(*M, *E, site_mask);
     const int segs = sh_div_up(A.pitch, HS_FIELD_SEG), tiles_x = sh_div_up(A.ew, HS_FIELD_TX), tiles_y = sh_div_up(A.eh, HS_FIELD_TY);
     // (at most 2^26 cells in E: neither grid reaches 2^31 workgroups)
-    hipLaunchKernelGGL(rows, dim3((unsigned)segs * (unsigned)A.eh), dim3(HS_FIELD_ROW_LANES), 0, hs->ctx->stream, A, segs, (G *)u->d_g);
+    hipLaunchKernelGGL(rows, dim3((unsigned)segs * (unsigned)A.eh), dim3(HS_FIELD_ROW_LANES), 0, hs->ctx->stream, A, segs, (G *)u->d_g.p);
     SH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(cols, dim3((unsigned)tiles_x * (unsigned)tiles_y), dim3(HS_FIELD_COL_LANES), 0, hs->ctx->stream, A, tiles_x, (const G *)u->d_g, (T *)u->d_f);
+    hipLaunchKernelGGL(cols, dim3((unsigned)tiles_x * (unsigned)tiles_y), dim3(HS_FIELD_COL_LANES), 0, hs->ctx->stream, A, tiles_x, (const G *)u->d_g.p, (T *)u->d_f.p);
     SH_HIP(hipGetLastError());
     return SLAMHIP_OK;
 }
 
 // The field call, behind the caller's refusals for level, world, site_mask and radius: the rectangle refused, the frame of a
 // blocking call around the plan, the field, the gather of the rectangle and its way to `out`.
-template <typename G, typename T>
-static inline int32_t hs_field_call(slamhip_hs *hs, hs_field_unit **slot, const char *who, void (*rows)(hs_field_geo, int, G *),
+template <auto SLOT, typename G, typename T>
+static inline int32_t hs_field_call(slamhip_hs *hs, const char *who, void (*rows)(hs_field_geo, int, G *),
                                     void (*cols)(hs_field_geo, int, const G *, T *), int level, bool world, int site_mask, int radius, uint32_t outside,
                                     int x, int y, int w, int h, void *out)
 {
@@ -148,14 +137,14 @@ static inline int32_t hs_field_call(slamhip_hs *hs, hs_field_unit **slot, const 
         SH_FAIL(SLAMHIP_ERR_INVALID, "%s: a rectangle of %d x %d cells; w, h >= 1 and w * h <= 2^24", who, w, h);
     SH_TRY(hs_call_begin(hs));
     hs_class_map M; hs_field_of<T> E;
-    SH_TRY(hs_field_prepare(hs, slot, who, sizeof(G), level, world, radius, outside, &M, &E));
-    hs_pose_batch *pb = &(*slot)->pb;
+    SH_TRY(hs_field_prepare<SLOT>(hs, who, sizeof(G), level, world, radius, outside, &M, &E));
+    hs_pose_batch *pb = &(hs->*SLOT)->pb;
     const int n = w * h;
     const size_t out_bytes = sizeof(T) * (size_t)n;
-    SH_TRY(hs_grow((void **)&pb->d_out, &pb->cap_out, out_bytes, HS_MEM_DEVICE, who));
-    SH_TRY(hs_grow((void **)&pb->h_io, &pb->cap_h, out_bytes, HS_MEM_PINNED, who));
-    SH_TRY(hs_field_enqueue(hs, *slot, rows, cols, level, world, &M, &E, site_mask));
-    hipLaunchKernelGGL(hs_field_gather<T>, dim3((unsigned)sh_div_up(n, 256)), dim3(256), 0, hs->ctx->stream, E, x, y, w, n, (T *)pb->d_out);
+    SH_TRY(pb->d_out.grow(out_bytes, who));
+    SH_TRY(pb->h_io.grow(out_bytes, who));
+    SH_TRY(hs_field_enqueue(hs, hs->*SLOT, rows, cols, level, world, &M, &E, site_mask));
+    hipLaunchKernelGGL(hs_field_gather<T>, dim3((unsigned)sh_div_up(n, 256)), dim3(256), 0, hs->ctx->stream, E, x, y, w, n, (T *)pb->d_out.p);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(pb->h_io, pb->d_out, out_bytes, hipMemcpyDeviceToHost, hs->ctx->stream));
     SH_TRY(hs_call_finish(hs));

@@ -262,32 +262,16 @@ __global__ void __launch_bounds__(256) k10_gather(const k10_geo G, int gx, int g
 // record block, the labels' device block, and the two pinned, device-visible blocks the results reach the host through (counters and
 // records, stored by k10_emit; the labels, copied).
 struct hs_frontier {
-    uint32_t *d_fw; size_t cap_fw;
-    int *d_parent; size_t cap_parent;
-    int *d_count; size_t cap_count;
-    int *d_ctr; size_t cap_ctr;
-    slamhip_frontier_cluster *d_rec; size_t cap_rec;
-    int *d_labels; size_t cap_labels;
-    unsigned char *h_head; size_t cap_head;   // device-visible: k10_emit stores into it
-    unsigned char *h_labels; size_t cap_hl;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_fw;
+    hs_block<int, HS_MEM_DEVICE> d_parent;
+    hs_block<int, HS_MEM_DEVICE> d_count;
+    hs_block<int, HS_MEM_DEVICE> d_ctr;
+    hs_block<slamhip_frontier_cluster, HS_MEM_DEVICE> d_rec;
+    hs_block<int, HS_MEM_DEVICE> d_labels;
+    hs_block<unsigned char, HS_MEM_PINNED_VISIBLE> h_head;   // device-visible: k10_emit stores into it
+    hs_block<unsigned char, HS_MEM_PINNED_VISIBLE> h_labels;
 };
 #define HS_FR_HEAD_BYTES (sizeof(int) * K10_CTRS + sizeof(slamhip_frontier_cluster) * (size_t)HS_FR_MAX_CLUSTERS)
-
-void hs_fr_free(slamhip_hs *hs)
-{
-    hs_frontier *fr = hs->frl;
-    if (!fr) return;
-    hs_release((void **)&fr->d_fw, &fr->cap_fw, HS_MEM_DEVICE);
-    hs_release((void **)&fr->d_parent, &fr->cap_parent, HS_MEM_DEVICE);
-    hs_release((void **)&fr->d_count, &fr->cap_count, HS_MEM_DEVICE);
-    hs_release((void **)&fr->d_ctr, &fr->cap_ctr, HS_MEM_DEVICE);
-    hs_release((void **)&fr->d_rec, &fr->cap_rec, HS_MEM_DEVICE);
-    hs_release((void **)&fr->d_labels, &fr->cap_labels, HS_MEM_DEVICE);
-    hs_release((void **)&fr->h_head, &fr->cap_head, HS_MEM_PINNED_VISIBLE);
-    hs_release((void **)&fr->h_labels, &fr->cap_hl, HS_MEM_PINNED_VISIBLE);
-    delete fr;
-    hs->frl = nullptr;
-}
 
 // what both entry points refuse for their arguments alone
 static int32_t hs_fr_check(int32_t min_cells, int32_t max_clusters, const void *out_clusters)
@@ -341,7 +325,7 @@ extern "C" int32_t slamhip_hs_frontiers(slamhip_hs *hs, int32_t level, int32_t w
     const int64_t cells = (int64_t)M.w * M.h;
     if (cells > HS_FR_MAX_M)
         SH_FAIL(SLAMHIP_ERR_INVALID, "frontiers: M, the class map of level %d, is %d x %d cells, more than 2^25", level, M.w, M.h);
-    SH_TRY(hs_unit(&hs->frl));
+    SH_TRY(hs_unit<&slamhip_hs::frl>(hs));
     hs_frontier *fr = hs->frl;
     k10_geo G;
     G.cls = M.cls; G.w = M.w; G.h = M.h; G.wpr = M.wpr;
@@ -349,14 +333,14 @@ extern "C" int32_t slamhip_hs_frontiers(slamhip_hs *hs, int32_t level, int32_t w
     G.cap = (int)cells + 2; G.min_cells = min_cells;
     const int n_labels = out_labels ? lw * lh : 0;
     const size_t label_bytes = sizeof(int) * (size_t)n_labels;
-    SH_TRY(hs_grow((void **)&fr->d_fw, &fr->cap_fw, sizeof(uint32_t) * (size_t)G.fwpr * G.h, HS_MEM_DEVICE, "frontiers"));
-    SH_TRY(hs_grow((void **)&fr->d_parent, &fr->cap_parent, sizeof(int) * (size_t)cells, HS_MEM_DEVICE, "frontiers"));
-    SH_TRY(hs_grow((void **)&fr->d_count, &fr->cap_count, sizeof(int) * (size_t)cells, HS_MEM_DEVICE, "frontiers"));
-    SH_TRY(hs_grow((void **)&fr->d_ctr, &fr->cap_ctr, sizeof(int) * K10_CTRS, HS_MEM_DEVICE, "frontiers"));
-    SH_TRY(hs_grow((void **)&fr->d_rec, &fr->cap_rec, sizeof(slamhip_frontier_cluster) * (size_t)HS_FR_MAX_CLUSTERS, HS_MEM_DEVICE, "frontiers"));
-    if (n_labels) SH_TRY(hs_grow((void **)&fr->d_labels, &fr->cap_labels, label_bytes, HS_MEM_DEVICE, "frontiers"));
-    SH_TRY(hs_grow((void **)&fr->h_head, &fr->cap_head, HS_FR_HEAD_BYTES, HS_MEM_PINNED_VISIBLE, "frontiers"));
-    if (n_labels) SH_TRY(hs_grow((void **)&fr->h_labels, &fr->cap_hl, label_bytes, HS_MEM_PINNED_VISIBLE, "frontiers"));
+    SH_TRY(fr->d_fw.grow(sizeof(uint32_t) * (size_t)G.fwpr * G.h, "frontiers"));
+    SH_TRY(fr->d_parent.grow(sizeof(int) * (size_t)cells, "frontiers"));
+    SH_TRY(fr->d_count.grow(sizeof(int) * (size_t)cells, "frontiers"));
+    SH_TRY(fr->d_ctr.grow(sizeof(int) * K10_CTRS, "frontiers"));
+    SH_TRY(fr->d_rec.grow(sizeof(slamhip_frontier_cluster) * (size_t)HS_FR_MAX_CLUSTERS, "frontiers"));
+    if (n_labels) SH_TRY(fr->d_labels.grow(label_bytes, "frontiers"));
+    SH_TRY(fr->h_head.grow(HS_FR_HEAD_BYTES, "frontiers"));
+    if (n_labels) SH_TRY(fr->h_labels.grow(label_bytes, "frontiers"));
     G.fw = fr->d_fw; G.parent = fr->d_parent; G.count = fr->d_count; G.ctr = fr->d_ctr; G.rec = fr->d_rec;
     // (at most 2^25 cells in M: no grid reaches 2^31 workgroups)
     const dim3 grid((unsigned)G.wgx * (unsigned)sh_div_up(G.h, K10_WG_ROWS)), lanes(K10_LANES);
@@ -373,8 +357,8 @@ extern "C" int32_t slamhip_hs_frontiers(slamhip_hs *hs, int32_t level, int32_t w
     hipLaunchKernelGGL(k10_stats, grid, lanes, 0, ctx->stream, G);
     SH_HIP(hipGetLastError());
     const int rec_words = HS_FR_MAX_CLUSTERS * (int)(sizeof(slamhip_frontier_cluster) / sizeof(int));
-    hipLaunchKernelGGL(k10_emit, dim3((unsigned)sh_div_up(rec_words, 256)), dim3(256), 0, ctx->stream, (const int *)fr->d_ctr, (const int *)fr->d_rec,
-                       (int *)fr->h_head);
+    hipLaunchKernelGGL(k10_emit, dim3((unsigned)sh_div_up(rec_words, 256)), dim3(256), 0, ctx->stream, (const int *)fr->d_ctr, (const int *)fr->d_rec.p,
+                       (int *)fr->h_head.p);
     SH_HIP(hipGetLastError());
     if (n_labels) {
         hipLaunchKernelGGL(k10_gather, dim3((unsigned)sh_div_up(n_labels, 256)), dim3(256), 0, ctx->stream, G, lx - M.x0, ly - M.y0, lw, n_labels,
@@ -383,7 +367,7 @@ extern "C" int32_t slamhip_hs_frontiers(slamhip_hs *hs, int32_t level, int32_t w
         SH_HIP(hipMemcpyAsync(fr->h_labels, fr->d_labels, label_bytes, hipMemcpyDeviceToHost, ctx->stream));
     }
     SH_TRY(hs_call_finish(hs));
-    const int *ctr = (const int *)fr->h_head;
+    const int *ctr = (const int *)fr->h_head.p;
     if (ctr[K10_C_FLAG]) SH_FAIL(SLAMHIP_ERR_STATE, "frontier labelling did not converge (level %d, M of %d x %d cells)", level, M.w, M.h);
     SH_TRY(hs_fr_finish(ctr, (slamhip_frontier_cluster *)(fr->h_head + sizeof(int) * K10_CTRS), M.x0, M.y0, M.w, M.h, max_clusters, out_summary,
                         out_clusters));

@@ -234,35 +234,18 @@ struct hs_hough_slot {
     int level, world, mask, T, q;
     int w, h, x0, y0, D, N;
     int64_t n_sites;
-    uint32_t *d_H; size_t cap_H;
-    k17_u64 *d_spec; size_t cap_spec;
-    int2 *d_ext; size_t cap_ext;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_H;
+    hs_block<k17_u64, HS_MEM_DEVICE> d_spec;
+    hs_block<int2, HS_MEM_DEVICE> d_ext;
     std::vector<k17_u64> spec;             // HS[T]
 };
 struct hs_hough {
     hs_hough_slot slot[2];
-    int32_t *d_cs; size_t cap_cs;
-    int32_t *d_pairs; size_t cap_pairs;
-    unsigned char *d_out; size_t cap_out;  // records, XC arrays, partial records
-    unsigned char *h_io; size_t cap_h;
+    hs_block<int32_t, HS_MEM_DEVICE> d_cs;
+    hs_block<int32_t, HS_MEM_DEVICE> d_pairs;
+    hs_block<unsigned char, HS_MEM_DEVICE> d_out;  // records, XC arrays, partial records
+    hs_block<unsigned char, HS_MEM_PINNED> h_io;
 };
-
-void hs_hg_free(slamhip_hs *hs)
-{
-    hs_hough *g = hs->hgh;
-    if (!g) return;
-    for (int s = 0; s < 2; s++) {
-        hs_release((void **)&g->slot[s].d_H, &g->slot[s].cap_H, HS_MEM_DEVICE);
-        hs_release((void **)&g->slot[s].d_spec, &g->slot[s].cap_spec, HS_MEM_DEVICE);
-        hs_release((void **)&g->slot[s].d_ext, &g->slot[s].cap_ext, HS_MEM_DEVICE);
-    }
-    hs_release((void **)&g->d_cs, &g->cap_cs, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_pairs, &g->cap_pairs, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_out, &g->cap_out, HS_MEM_DEVICE);
-    hs_release((void **)&g->h_io, &g->cap_h, HS_MEM_PINNED);
-    delete g;
-    hs->hgh = nullptr;
-}
 
 void hs_hg_drop_slot(slamhip_hs *hs, int slot) { if (hs->hgh) hs->hgh->slot[slot].have = false; }
 
@@ -306,18 +289,18 @@ extern "C" int32_t slamhip_hs_hough(slamhip_hs *hs, int32_t level, int32_t slot,
     if (M.w > HS_HG_MAX_DIM || M.h > HS_HG_MAX_DIM) SH_FAIL(SLAMHIP_ERR_INVALID, "hough: a map of %d x %d cells; at most %d each way", M.w, M.h, HS_HG_MAX_DIM);
     const int D = hs_hough_D(M.w, M.h), N = hs_hough_N(D, q);
     if ((int64_t)T * N > HS_HG_MAX_BINS) SH_FAIL(SLAMHIP_ERR_INVALID, "hough: T * N = %d * %d bins, more than 2^24", T, N);
-    SH_TRY(hs_unit(&hs->hgh));
+    SH_TRY(hs_unit<&slamhip_hs::hgh>(hs));
     hs_hough *g = hs->hgh;
     hs_hough_slot &S = g->slot[slot];
     const size_t cs_bytes = sizeof(int32_t) * 2 * (size_t)T, spec_bytes = sizeof(k17_u64) * 2 * (size_t)T;
     const size_t H_bytes = sizeof(uint32_t) * (size_t)T * (size_t)N;
-    SH_TRY(hs_grow((void **)&g->d_cs, &g->cap_cs, cs_bytes, HS_MEM_DEVICE, "hough"));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, cs_bytes + spec_bytes + (out_H ? H_bytes : 0), HS_MEM_PINNED, "hough"));
+    SH_TRY(g->d_cs.grow(cs_bytes, "hough"));
+    SH_TRY(g->h_io.grow(cs_bytes + spec_bytes + (out_H ? H_bytes : 0), "hough"));
     S.have = false;                                                        // (nothing in the slot until this fill has landed)
-    SH_TRY(hs_grow((void **)&S.d_H, &S.cap_H, H_bytes, HS_MEM_DEVICE, "hough"));
-    SH_TRY(hs_grow((void **)&S.d_spec, &S.cap_spec, spec_bytes, HS_MEM_DEVICE, "hough"));
-    SH_TRY(hs_grow((void **)&S.d_ext, &S.cap_ext, sizeof(int2) * (size_t)T, HS_MEM_DEVICE, "hough"));
-    hs_hough_table(T, (int32_t *)g->h_io);
+    SH_TRY(S.d_H.grow(H_bytes, "hough"));
+    SH_TRY(S.d_spec.grow(spec_bytes, "hough"));
+    SH_TRY(S.d_ext.grow(sizeof(int2) * (size_t)T, "hough"));
+    hs_hough_table(T, (int32_t *)g->h_io.p);
     SH_HIP(hipMemcpyAsync(g->d_cs, g->h_io, cs_bytes, hipMemcpyHostToDevice, ctx->stream));
     if (slot == 0) SH_TRY(hs_lat_pack_enqueue(hs, level, world != 0, &M));
     SH_HIP(hipMemsetAsync(S.d_H, 0, H_bytes, ctx->stream));
@@ -392,9 +375,9 @@ extern "C" int32_t slamhip_hs_hough_shifts(slamhip_hs *hs, const int32_t *pairs,
     const int blocks = sh_div_up(NX, K17X_LANES);
     const size_t pair_bytes = sizeof(int32_t) * 2 * (size_t)P, rec_bytes = sizeof(slamhip_hough_shift) * (size_t)P;
     const size_t xc_bytes = out_xc ? sizeof(k17_u64) * (size_t)P * NX : 0, part_bytes = sizeof(k17x_part) * (size_t)P * blocks;
-    SH_TRY(hs_grow((void **)&g->d_pairs, &g->cap_pairs, pair_bytes, HS_MEM_DEVICE, "hough shifts"));
-    SH_TRY(hs_grow((void **)&g->d_out, &g->cap_out, rec_bytes + xc_bytes + part_bytes, HS_MEM_DEVICE, "hough shifts"));   // (every part a multiple of 8 bytes)
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, rec_bytes + xc_bytes + pair_bytes, HS_MEM_PINNED, "hough shifts"));
+    SH_TRY(g->d_pairs.grow(pair_bytes, "hough shifts"));
+    SH_TRY(g->d_out.grow(rec_bytes + xc_bytes + part_bytes, "hough shifts"));   // (every part a multiple of 8 bytes)
+    SH_TRY(g->h_io.grow(rec_bytes + xc_bytes + pair_bytes, "hough shifts"));
     int32_t *h_pairs = (int32_t *)(g->h_io + rec_bytes + xc_bytes);
     memcpy(h_pairs, pairs, pair_bytes);
     SH_HIP(hipMemcpyAsync(g->d_pairs, h_pairs, pair_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -407,7 +390,7 @@ extern "C" int32_t slamhip_hs_hough_shifts(slamhip_hs *hs, const int32_t *pairs,
     // (at most 256 pairs x 513 blocks)
     hipLaunchKernelGGL(k17_xcorr, dim3((unsigned)(P * blocks)), dim3(K17X_LANES), 0, ctx->stream, X);
     SH_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k17_xcorr_finish, dim3((unsigned)P), dim3(64), 0, ctx->stream, (const k17x_part *)X.part, blocks, (slamhip_hough_shift *)g->d_out);
+    hipLaunchKernelGGL(k17_xcorr_finish, dim3((unsigned)P), dim3(64), 0, ctx->stream, (const k17x_part *)X.part, blocks, (slamhip_hough_shift *)g->d_out.p);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(g->h_io, g->d_out, rec_bytes + xc_bytes, hipMemcpyDeviceToHost, ctx->stream));
     SH_TRY(hs_call_finish(hs));
@@ -422,7 +405,7 @@ extern "C" int32_t slamhip_hs_hough_clear(slamhip_hs *hs)
     if (!hs->hgh) return SLAMHIP_OK;
     SH_TRY(hs_call_begin(hs));
     SH_TRY(hs_call_finish(hs));                                            // (the blocks are idle behind it)
-    hs_hg_free(hs);
+    hs_unit_drop<&slamhip_hs::hgh>(hs);
     return SLAMHIP_OK;
 }
 

@@ -1,4 +1,6 @@
-// hs_internal.h -- device state of the HectorSLAM operator object (slamhip_hs) and what its units share.
+// hs_internal.h -- device state of the HectorSLAM operator object (slamhip_hs) and what its units share.  slamhip_hs is a calloc'ed
+// C struct that frees its own blocks by hand (slamhip_hs_destroy); a unit's struct owns its blocks (hs_block, hs_blocks.h) and
+// needs no free function here: it is dropped through the unit table at the struct's end.
 #pragma once
 #include "common.h"
 #include "m3x2.h"
@@ -6,6 +8,7 @@
 
 #define HS_MAX_LEVELS 8
 #define HS_NONE 0xFFFFFFFFu
+#define HS_MAX_UNITS 24                    // slots of slamhip_hs's unit table: one per unit pointer of the struct (18), and room
 // sizes of K4's (hs_match.hip) and K5's (hs_update.hip) LDS tables that host entry points of other units test
 #define HS_LDS_PTS 2048                    // scan points kept in LDS (16 KB); longer scans are read from global memory
 #define HS_REF_MAX_T 64                    // ParallelWorker.Work waits with WaitHandle.WaitAll: at most 64 handles (BaseSLAM/ParallelWorker.cs:113-115)
@@ -99,6 +102,8 @@ struct slamhip_hs {
     struct hs_scanmatch *smt;                              // slamhip_hs_scans_match: the pairs' and the results' device blocks and their pinned staging, made by the first call, kept
     struct hs_loops *lps;                                  // slamhip_hs_loops_consistent: the edges', the matrix's and the results' device block and its pinned staging, made by the first call, kept
     struct hs_bnb *bnb;                                    // slamhip_hs_lattice_search_bnb: the pooled maps, the frontiers and the results' blocks, made by the first call, kept
+    // how to drop each unit above that has been made (hs_unit records it, a slot once; hs_blocks.h): what slamhip_hs_destroy walks
+    void (*unit_drop[HS_MAX_UNITS])(slamhip_hs *); int n_units;
 };
 
 struct hs_levels_arg { hs_level_dev lv[HS_MAX_LEVELS]; int n; };
@@ -164,10 +169,7 @@ bool    hs_update_gateable(slamhip_hs *hs);
 // hs_window.hip
 void    hs_bk_reset(slamhip_hs *hs);        // slamhip_hs_reset with backing on: the directory goes, the pool stays -- every slot Reset again
 void    hs_bk_free(slamhip_hs *hs);         // (the caller has drained the stream)
-// hs_world.hip
-void    hs_wp_free(slamhip_hs *hs);         // the staging buffer of the world upload and the world extents (the caller has drained the stream)
 // hs_lattice.hip
-void    hs_lat_free(slamhip_hs *hs);        // the class map and the result blocks of the pose-lattice search (the caller has drained the stream)
 // K7's class map of one level -- 2 bits per cell, rows of wpr words -- for another launch on the operator's stream: w x h cells
 // whose first is cell (x0, y0) of the window's frame (the window itself, or the world's rectangle R).  _prepare plans and
 // allocates and launches nothing; _enqueue packs.
@@ -183,12 +185,10 @@ int32_t hs_lat_reloc_world_check(const slamhip_hs *hs);
 int32_t hs_lat_reloc_world_finish(slamhip_hs *hs, const slamhip_lattice_spec *spec, const uint64_t *keys, int32_t B, float out_pose[3],
                                   slamhip_match_report *out_report, slamhip_world_reloc_info *out_info);
 // hs_trace.hip
-void    hs_trc_free(slamhip_hs *hs);        // the blocks of the beam trace (the caller has drained the stream)
 // what slamhip_hs_trace refuses for its arguments alone, for a scan of n_points (scan_is_set false: the caller is about to set one,
 // so its absence is no error)
 int32_t hs_trc_check(int n_levels, int32_t level, int32_t B, int32_t world, bool want_beams, int n_points, bool scan_is_set);
 // hs_dfield.hip
-void    hs_df_free(slamhip_hs *hs);         // the blocks of the distance field (the caller has drained the stream)
 // what slamhip_hs_distance_field and _score refuse for level, world, site_mask and radius (K13 refuses the same); who: the message's prefix
 int32_t hs_df_check(const char *who, int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius);
 // ... and what slamhip_hs_distance_score refuses for its arguments alone (n_points, scan_is_set: as hs_trc_check)
@@ -199,10 +199,7 @@ int32_t hs_df_check_score(const char *who, int n_levels, int32_t level, int32_t 
 // _score run these two themselves.
 int32_t hs_df_field_prepare(slamhip_hs *hs, int level, bool world, int site_mask, int radius, hs_class_map *M, hs_field *E);
 int32_t hs_df_field_enqueue(slamhip_hs *hs, int level, bool world, const hs_class_map *M, const hs_field *E, int site_mask);
-// hs_frontier.hip
-void    hs_fr_free(slamhip_hs *hs);         // the blocks of the frontier labelling (the caller has drained the stream)
 // hs_nav.hip
-void    hs_nav_free(slamhip_hs *hs);        // the blocks of the cost-to-go field (the caller has drained the stream)
 // K11's counter block (k11_peek and k11_emit store it to pinned memory)
 #define K11_C_TRAV 0
 #define K11_C_REACHED 1
@@ -218,15 +215,11 @@ void    hs_nav_free(slamhip_hs *hs);        // the blocks of the cost-to-go fiel
 struct hs_nav_view { const uint32_t *tw; const uint32_t *cost; uint32_t *ctr; int twpr; hs_class_map M; int rounds; };
 int32_t hs_nav_check_field(int n_levels, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S);
 int32_t hs_nav_field_for_rollouts(slamhip_hs *hs, const slamhip_nav_spec *spec, const int32_t *sources, int32_t S, hs_nav_view *out);
-// hs_rollout.hip
-void    hs_ro_free(slamhip_hs *hs);         // the blocks of the command rollouts (the caller has drained the stream)
 // hs_mcl.hip
-void    hs_mcl_free(slamhip_hs *hs);        // the particle set and the blocks of the localisation step (the caller has drained the stream)
 // what slamhip_hs_mcl_step refuses before it launches anything, for a scan of n_points (scan_is_set false: the caller is about to set
 // one, so its absence is no error)
 int32_t hs_mcl_check_step(const slamhip_hs *hs, const slamhip_mcl_spec *spec, int n_points, bool scan_is_set);
 // hs_merge.hip
-void    hs_merge_free(slamhip_hs *hs);      // the source map and the blocks of the merge (the caller has drained the stream)
 void    hs_merge_drop_source(slamhip_hs *hs);   // slamhip_hs_reset, slamhip_hs_merge_clear_source: no source from here on; the blocks stay
 // what slamhip_hs_merge_score and _apply refuse before they launch anything
 int32_t hs_merge_check_score(const slamhip_hs *hs, int32_t B);
@@ -235,35 +228,23 @@ int32_t hs_merge_check_apply(const slamhip_hs *hs, int32_t rule, float value_lim
 // on the operator's stream (K17's slot 1); SLAMHIP_ERR_STATE without a source
 int32_t hs_merge_source_map(const slamhip_hs *hs, hs_class_map *M, int *level);
 // hs_view.hip
-void    hs_view_free(slamhip_hs *hs);       // the covered layer and the blocks of the view gain (the caller has drained the stream)
 // what slamhip_hs_view_gain and _view_select refuse for their arguments alone, for a scan of n_points (scan_is_set false: the caller
 // is about to set one, so its absence is no error)
 int32_t hs_view_check_gain(const slamhip_hs *hs, int32_t level, int32_t reach, int32_t B, int32_t commit, int n_points, bool scan_is_set);
 int32_t hs_view_check_select(const slamhip_hs *hs, int32_t level, int32_t reach, int32_t mode, int32_t min_gain, int32_t B, int32_t k, int n_points,
                              bool scan_is_set);
 // hs_nearest.hip
-void    hs_nr_free(slamhip_hs *hs);         // the blocks of the nearest-site field (the caller has drained the stream)
 // what slamhip_hs_nearest_pairs refuses for its arguments alone (n_points, scan_is_set: as hs_trc_check)
 int32_t hs_nr_check_pairs(int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius, int32_t B, bool want_pairs, int n_points,
                           bool scan_is_set);
 // hs_hough.hip
-void    hs_hg_free(slamhip_hs *hs);         // the blocks of the Hough transform (the caller has drained the stream)
 void    hs_hg_drop_slot(slamhip_hs *hs, int slot);   // slamhip_hs_reset (both), slamhip_hs_merge_set_source / _clear_source (slot 1): the slot is empty from here on; the blocks stay
 // hs_sig.hip
-void    hs_sg_free(slamhip_hs *hs);         // the store and the blocks of the scan signatures (the caller has drained the stream)
 void    hs_sg_reset(slamhip_hs *hs);        // slamhip_hs_reset: the store is empty from here on; the blocks and the spec stay
 // what slamhip_hs_sig_add and _sig_query refuse before they launch anything
 int32_t hs_sg_check_add(const slamhip_hs *hs);
 int32_t hs_sg_check_query(const slamhip_hs *hs, int32_t first, int32_t last, int32_t B);
 // hs_pg.hip
-void    hs_pg_free(slamhip_hs *hs);         // the pose graph's blocks (the caller has drained the stream)
 void    hs_pg_reset(slamhip_hs *hs);        // slamhip_hs_reset: no graph from here on; the blocks stay
 // hs_render.hip
-void    hs_scn_free(slamhip_hs *hs);        // the store of keyframe scans and the blocks of a render (the caller has drained the stream)
 void    hs_scn_reset(slamhip_hs *hs);       // slamhip_hs_reset: the store is empty from here on; the pool and the blocks stay
-// hs_scanmatch.hip
-void    hs_smt_free(slamhip_hs *hs);        // the blocks of the scan-to-scan match (the caller has drained the stream)
-// hs_loops.hip
-void    hs_lp_free(slamhip_hs *hs);         // the blocks of the consistent set of loop edges (the caller has drained the stream)
-// hs_bnb.hip
-void    hs_bnb_free(slamhip_hs *hs);        // the pooled maps, the frontiers and the results' blocks of the branch-and-bound search (the caller has drained the stream)

@@ -210,27 +210,15 @@ __global__ void __launch_bounds__(K7_LANES) k7_search(const k7_arg A)
 // What a search needs, made by the first one and kept: the class map (grown to the largest level searched), the device block of
 // keys and scores, and its pinned twin the results reach the host through.
 struct hs_lattice {
-    uint32_t *d_cls; size_t cap_cls;                                       // words
-    unsigned char *d_out; size_t cap_out;                                  // n_theta keys, then the score volume
-    unsigned char *h_out; size_t cap_h;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_cls;                                       // words
+    hs_block<unsigned char, HS_MEM_DEVICE> d_out;                                  // n_theta keys, then the score volume
+    hs_block<unsigned char, HS_MEM_PINNED> h_out;
     // the world search: the job pieces in device memory, and the host vectors they are planned in
-    unsigned char *d_pieces; size_t cap_pieces;
+    hs_block<unsigned char, HS_MEM_DEVICE> d_pieces;
     std::vector<int64_t> tiles;                                            // (ty, tx) of every tile of the level
     std::vector<slamhip_world_job> plan;
     std::vector<k7w_piece> pieces;
 };
-
-void hs_lat_free(slamhip_hs *hs)
-{
-    hs_lattice *lt = hs->lat;
-    if (!lt) return;
-    hs_release((void **)&lt->d_cls, &lt->cap_cls, HS_MEM_DEVICE);
-    hs_release((void **)&lt->d_out, &lt->cap_out, HS_MEM_DEVICE);
-    hs_release((void **)&lt->h_out, &lt->cap_h, HS_MEM_PINNED);
-    hs_release((void **)&lt->d_pieces, &lt->cap_pieces, HS_MEM_DEVICE);
-    delete lt;
-    hs->lat = nullptr;
-}
 
 int32_t hs_lat_check_spec(const slamhip_hs *hs, const slamhip_lattice_spec *S, bool cap_nodes)
 {
@@ -287,15 +275,15 @@ static int32_t hs_lat_plan_world(slamhip_hs *hs, hs_lattice *lt, int level, wpp_
 // device blocks grown.  hs_lat_pack_enqueue: the pack launch -- k7_pack for the window, the memset and k7_pack_world for the world.
 int32_t hs_lat_pack_prepare(slamhip_hs *hs, int level, bool world, hs_class_map *M)
 {
-    SH_TRY(hs_unit(&hs->lat));
+    SH_TRY(hs_unit<&slamhip_hs::lat>(hs));
     hs_lattice *lt = hs->lat;
     const hs_level &L = hs->lv[level];
     wpp_rect R = { 0, 0, L.w, L.h };                                       // what the class map covers, in the window's frame
     if (world) SH_TRY(hs_lat_plan_world(hs, lt, level, &R));               // (refuses before anything is allocated or launched)
     M->w = (int)R.w; M->h = (int)R.h; M->wpr = (M->w + 15) / 16;
     M->x0 = (int)R.x0; M->y0 = (int)R.y0;
-    SH_TRY(hs_grow((void **)&lt->d_cls, &lt->cap_cls, sizeof(uint32_t) * (size_t)M->wpr * M->h, HS_MEM_DEVICE, "lattice"));
-    if (world) SH_TRY(hs_grow((void **)&lt->d_pieces, &lt->cap_pieces, sizeof(k7w_piece) * lt->pieces.size(), HS_MEM_DEVICE, "lattice"));
+    SH_TRY(lt->d_cls.grow(sizeof(uint32_t) * (size_t)M->wpr * M->h, "lattice"));
+    if (world) SH_TRY(lt->d_pieces.grow(sizeof(k7w_piece) * lt->pieces.size(), "lattice"));
     M->cls = lt->d_cls;
     return SLAMHIP_OK;
 }
@@ -312,7 +300,7 @@ int32_t hs_lat_pack_enqueue(slamhip_hs *hs, int level, bool world, const hs_clas
         SH_HIP(hipMemsetAsync(lt->d_cls, 0, sizeof(uint32_t) * (size_t)M->wpr * M->h, ctx->stream));
         SH_HIP(hipMemcpyAsync(lt->d_pieces, lt->pieces.data(), sizeof(k7w_piece) * lt->pieces.size(), hipMemcpyHostToDevice, ctx->stream));
         sh_timer t(ctx, SLAMHIP_K_HS_LATTICE_PACK_WORLD);
-        hipLaunchKernelGGL(k7_pack_world, dim3((unsigned)lt->pieces.size()), dim3(K7W_LANES), 0, ctx->stream, (const k7w_piece *)lt->d_pieces, M->wpr, lt->d_cls);
+        hipLaunchKernelGGL(k7_pack_world, dim3((unsigned)lt->pieces.size()), dim3(K7W_LANES), 0, ctx->stream, (const k7w_piece *)lt->d_pieces.p, M->wpr, lt->d_cls);
     }
     SH_HIP(hipGetLastError());
     return SLAMHIP_OK;
@@ -333,8 +321,8 @@ static int32_t hs_lat_run(slamhip_hs *hs, const slamhip_lattice_spec *S, bool wa
     const int NX = 2 * S->nx + 1, NY = 2 * S->ny + 1;
     const size_t key_bytes = sizeof(uint64_t) * (size_t)S->n_theta;
     const size_t out_bytes = key_bytes + (want_scores ? sizeof(int32_t) * (size_t)S->n_theta * NX * NY : 0);
-    SH_TRY(hs_grow((void **)&lt->d_out, &lt->cap_out, out_bytes, HS_MEM_DEVICE, "lattice"));
-    SH_TRY(hs_grow((void **)&lt->h_out, &lt->cap_h, out_bytes, HS_MEM_PINNED, "lattice"));
+    SH_TRY(lt->d_out.grow(out_bytes, "lattice"));
+    SH_TRY(lt->h_out.grow(out_bytes, "lattice"));
     SH_TRY(hs_flush_scan(hs));
     SH_HIP(hipMemsetAsync(lt->d_out, 0, key_bytes, ctx->stream));
     SH_TRY(hs_lat_pack_enqueue(hs, S->level, world, &M));
@@ -347,7 +335,7 @@ static int32_t hs_lat_run(slamhip_hs *hs, const slamhip_lattice_spec *S, bool wa
     A.txl = NX > 32 ? 6 : 4;                                               // 64 x 4 translations per workgroup; a narrow lattice 16 x 16
     const int TX = 1 << A.txl, TY = K7_LANES >> A.txl;
     A.tiles_x = sh_div_up(NX, TX);
-    A.keys = (unsigned long long *)lt->d_out;
+    A.keys = (unsigned long long *)lt->d_out.p;
     A.scores = want_scores ? (int32_t *)(lt->d_out + key_bytes) : (int32_t *)nullptr;
     {
         sh_timer t(ctx, SLAMHIP_K_HS_LATTICE);
@@ -356,7 +344,7 @@ static int32_t hs_lat_run(slamhip_hs *hs, const slamhip_lattice_spec *S, bool wa
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(lt->h_out, lt->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
     SH_TRY(hs_call_finish(hs));
-    *keys = (const uint64_t *)lt->h_out;
+    *keys = (const uint64_t *)lt->h_out.p;
     if (scores) *scores = want_scores ? (const int32_t *)(lt->h_out + key_bytes) : (const int32_t *)nullptr;
     return SLAMHIP_OK;
 }

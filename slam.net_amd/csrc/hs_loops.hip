@@ -185,19 +185,9 @@ __global__ void __launch_bounds__(K23_LANES) k23_finish(const k23_arg A)
 // What the unit keeps: one device block -- the edges, the records, the searches' rows, then the results -- and its pinned twin of
 // the edges and the results.
 struct hs_loops {
-    unsigned char *d_io; size_t cap_d;
-    unsigned char *h_io; size_t cap_h;
+    hs_block<unsigned char, HS_MEM_DEVICE> d_io;
+    hs_block<unsigned char, HS_MEM_PINNED> h_io;
 };
-
-void hs_lp_free(slamhip_hs *hs)
-{
-    hs_loops *u = hs->lps;
-    if (!u) return;
-    hs_release((void **)&u->d_io, &u->cap_d, HS_MEM_DEVICE);
-    hs_release((void **)&u->h_io, &u->cap_h, HS_MEM_PINNED);
-    delete u;
-    hs->lps = nullptr;
-}
 
 // rule 7
 static int32_t k23_check(const char *who, const double *poses, int32_t N, const int32_t *ij, const double *z, const double *w, int32_t L,
@@ -250,7 +240,7 @@ extern "C" int32_t slamhip_hs_loops_consistent(slamhip_hs *hs, const double *pos
     SH_TRY(k23_check("slamhip_hs_loops_consistent", poses, N, ij, z, w, L, spec, out_adj));
     slamhip_ctx *ctx = hs->ctx;
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_unit(&hs->lps));
+    SH_TRY(hs_unit<&slamhip_hs::lps>(hs));
     hs_loops *u = hs->lps;
     const int W = hs_lp_words(L);
     const bool want_adj = (spec->flags & SLAMHIP_LOOPS_ADJ) != 0;
@@ -262,13 +252,13 @@ extern "C" int32_t slamhip_hs_loops_consistent(slamhip_hs *hs, const double *pos
     const size_t o_rec = in_bytes, o_starts = o_rec + rec_bytes, o_qsize = o_starts + idx_bytes, o_qbits = o_qsize + idx_bytes;
     const size_t o_info = o_qbits + q_bytes, o_deg = o_info + sizeof(slamhip_loops_info), o_keep = o_deg + deg_bytes, o_adj = o_keep + keep_bytes;
     const size_t res_bytes = (o_adj - o_info) + (want_adj ? adj_bytes : 0);
-    SH_TRY(hs_grow((void **)&u->d_io, &u->cap_d, o_adj + adj_bytes, HS_MEM_DEVICE, "slamhip_hs_loops_consistent"));
-    SH_TRY(hs_grow((void **)&u->h_io, &u->cap_h, in_bytes + (o_adj - o_info) + adj_bytes, HS_MEM_PINNED, "slamhip_hs_loops_consistent"));
-    hs_lp_in *hin = (hs_lp_in *)u->h_io;
+    SH_TRY(u->d_io.grow(o_adj + adj_bytes, "slamhip_hs_loops_consistent"));
+    SH_TRY(u->h_io.grow(in_bytes + (o_adj - o_info) + adj_bytes, "slamhip_hs_loops_consistent"));
+    hs_lp_in *hin = (hs_lp_in *)u->h_io.p;
     int n_used = 0;
     for (int e = 0; e < L; e++) { hin[e] = k23_gather(poses, ij, z, w, use, e); n_used += hin[e].use; }
     k23_arg A;
-    A.in = (const hs_lp_in *)u->d_io; A.rec = (hs_lp_rec *)(u->d_io + o_rec); A.starts = (int32_t *)(u->d_io + o_starts);
+    A.in = (const hs_lp_in *)u->d_io.p; A.rec = (hs_lp_rec *)(u->d_io + o_rec); A.starts = (int32_t *)(u->d_io + o_starts);
     A.qsize = (int32_t *)(u->d_io + o_qsize); A.qbits = (hs_lp_u64 *)(u->d_io + o_qbits); A.info = (slamhip_loops_info *)(u->d_io + o_info);
     A.deg = (int32_t *)(u->d_io + o_deg); A.keep = (uint8_t *)(u->d_io + o_keep); A.adj = (hs_lp_u64 *)(u->d_io + o_adj);
     A.L = L; A.W = W; A.R = std::min(spec->n_starts, n_used); A.S = *spec;
@@ -304,7 +294,7 @@ extern "C" int32_t slamhip_hs_loops_clear(slamhip_hs *hs)
     SH_CHECK_ARG(hs);
     SH_HIP(hipSetDevice(hs->ctx->device));
     SH_HIP(hipStreamSynchronize(hs->ctx->stream));
-    hs_lp_free(hs);
+    hs_unit_drop<&slamhip_hs::lps>(hs);
     return SLAMHIP_OK;
 }
 

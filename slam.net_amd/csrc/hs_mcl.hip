@@ -230,50 +230,33 @@ __global__ void __launch_bounds__(K13_LANES) k13_resample(const k13_res_arg A)
 // two particle buffers used in turn, acc, a, w, C, the ancestors and the counters in device memory, a pinned block the set and the
 // get pass through, and a pinned, device-visible record k13_resample stores the summary in.
 struct hs_mcl {
-    float *d_part[2]; int cur;
-    k13_u64 *d_acc, *d_a, *d_C, *d_ctr;
-    uint32_t *d_w; int32_t *d_anc;
-    unsigned char *h_io;
-    slamhip_mcl_summary *h_sum;
+    hs_block<float, HS_MEM_DEVICE> d_part[2]; int cur;
+    hs_block<k13_u64, HS_MEM_DEVICE> d_acc, d_a, d_C, d_ctr;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_w; hs_block<int32_t, HS_MEM_DEVICE> d_anc;
+    hs_block<unsigned char, HS_MEM_PINNED> h_io;
+    hs_block<slamhip_mcl_summary, HS_MEM_PINNED_VISIBLE> h_sum;
     int N;                                 // 0: no set
 };
 #define HS_MCL_IO_BYTES ((size_t)HS_MCL_MAX_N * (3 * sizeof(float) + sizeof(k13_u64) + sizeof(int32_t)))
 
-// the blocks, their fixed sizes and kinds: fn(pointer, bytes, kind) for each, until one fails
-template <typename F>
-static int32_t hs_mcl_each_block(hs_mcl *m, F fn)
-{
-    const size_t n = HS_MCL_MAX_N;
-    SH_TRY(fn((void **)&m->d_part[0], n * 3 * sizeof(float), HS_MEM_DEVICE));
-    SH_TRY(fn((void **)&m->d_part[1], n * 3 * sizeof(float), HS_MEM_DEVICE));
-    SH_TRY(fn((void **)&m->d_acc, n * sizeof(k13_u64), HS_MEM_DEVICE));
-    SH_TRY(fn((void **)&m->d_a, n * sizeof(k13_u64), HS_MEM_DEVICE));
-    SH_TRY(fn((void **)&m->d_C, n * sizeof(k13_u64), HS_MEM_DEVICE));
-    SH_TRY(fn((void **)&m->d_ctr, K13_CTRS * sizeof(k13_u64), HS_MEM_DEVICE));
-    SH_TRY(fn((void **)&m->d_w, n * sizeof(uint32_t), HS_MEM_DEVICE));
-    SH_TRY(fn((void **)&m->d_anc, n * sizeof(int32_t), HS_MEM_DEVICE));
-    SH_TRY(fn((void **)&m->h_io, HS_MCL_IO_BYTES, HS_MEM_PINNED));
-    SH_TRY(fn((void **)&m->h_sum, sizeof(slamhip_mcl_summary), HS_MEM_PINNED_VISIBLE));
-    return SLAMHIP_OK;
-}
-
-void hs_mcl_free(slamhip_hs *hs)
-{
-    hs_mcl *m = hs->mcl;
-    if (!m) return;
-    (void)hs_mcl_each_block(m, [](void **p, size_t, hs_mem kind) { hs_release(p, nullptr, kind); return (int32_t)SLAMHIP_OK; });
-    delete m;
-    hs->mcl = nullptr;
-}
-
 static int32_t hs_mcl_blocks(slamhip_hs *hs)
 {
-    SH_TRY(hs_unit(&hs->mcl));
-    // (allocated once: a block that is there has its size)
-    return hs_mcl_each_block(hs->mcl, [](void **p, size_t bytes, hs_mem kind) {
-        size_t cap = *p ? bytes : 0;
-        return hs_grow(p, &cap, bytes, kind, "localisation");
-    });
+    SH_TRY(hs_unit<&slamhip_hs::mcl>(hs));
+    hs_mcl *m = hs->mcl;
+    const size_t n = HS_MCL_MAX_N;
+    const char *who = "localisation";
+    // (fixed sizes: a block that is there is large enough)
+    SH_TRY(m->d_part[0].grow(n * 3 * sizeof(float), who));
+    SH_TRY(m->d_part[1].grow(n * 3 * sizeof(float), who));
+    SH_TRY(m->d_acc.grow(n * sizeof(k13_u64), who));
+    SH_TRY(m->d_a.grow(n * sizeof(k13_u64), who));
+    SH_TRY(m->d_C.grow(n * sizeof(k13_u64), who));
+    SH_TRY(m->d_ctr.grow(K13_CTRS * sizeof(k13_u64), who));
+    SH_TRY(m->d_w.grow(n * sizeof(uint32_t), who));
+    SH_TRY(m->d_anc.grow(n * sizeof(int32_t), who));
+    SH_TRY(m->h_io.grow(HS_MCL_IO_BYTES, who));
+    SH_TRY(m->h_sum.grow(sizeof(slamhip_mcl_summary), who));
+    return SLAMHIP_OK;
 }
 
 extern "C" int32_t slamhip_hs_mcl_set(slamhip_hs *hs, const float *poses, int32_t N)

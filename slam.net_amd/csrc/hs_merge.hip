@@ -218,31 +218,16 @@ __global__ void __launch_bounds__(K14_LANES) k14_apply(const k14_apply_arg A)
 // What the merge keeps, made by the first slamhip_hs_merge_set_source: the pinned and the device block a source's cells pass
 // through, the source's Values and class words, and the blocks of the poses' constants and the reports of a score or an apply.
 struct hs_merge {
-    slamhip_cell *h_stage; size_t cap_hstage;
-    slamhip_cell *d_stage; size_t cap_dstage;
-    float *d_val; size_t cap_val;
-    uint32_t *d_cls; size_t cap_cls;
-    hs_merge_xf *d_xf; size_t cap_xf;
-    k14_u64 *d_rep; size_t cap_rep;
-    unsigned char *h_io; size_t cap_h;     // the reports; behind them the poses' constants
+    hs_block<slamhip_cell, HS_MEM_PINNED> h_stage;
+    hs_block<slamhip_cell, HS_MEM_DEVICE> d_stage;
+    hs_block<float, HS_MEM_DEVICE> d_val;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_cls;
+    hs_block<hs_merge_xf, HS_MEM_DEVICE> d_xf;
+    hs_block<k14_u64, HS_MEM_DEVICE> d_rep;
+    hs_block<unsigned char, HS_MEM_PINNED> h_io;     // the reports; behind them the poses' constants
     bool have; int level, wpr;
     hs_merge_src S;
 };
-
-void hs_merge_free(slamhip_hs *hs)
-{
-    hs_merge *m = hs->mrg;
-    if (!m) return;
-    hs_release((void **)&m->h_stage, &m->cap_hstage, HS_MEM_PINNED);
-    hs_release((void **)&m->d_stage, &m->cap_dstage, HS_MEM_DEVICE);
-    hs_release((void **)&m->d_val, &m->cap_val, HS_MEM_DEVICE);
-    hs_release((void **)&m->d_cls, &m->cap_cls, HS_MEM_DEVICE);
-    hs_release((void **)&m->d_xf, &m->cap_xf, HS_MEM_DEVICE);
-    hs_release((void **)&m->d_rep, &m->cap_rep, HS_MEM_DEVICE);
-    hs_release((void **)&m->h_io, &m->cap_h, HS_MEM_PINNED);
-    delete m;
-    hs->mrg = nullptr;
-}
 
 void hs_merge_drop_source(slamhip_hs *hs)
 {
@@ -269,17 +254,17 @@ extern "C" int32_t slamhip_hs_merge_set_source(slamhip_hs *hs, int32_t level, in
     if (ax < -HS_MERGE_MAX_ORIGIN || ax > HS_MERGE_MAX_ORIGIN || ay < -HS_MERGE_MAX_ORIGIN || ay > HS_MERGE_MAX_ORIGIN)
         SH_FAIL(SLAMHIP_ERR_INVALID, "merge: the source's first cell (%d, %d) lies more than 2^30 cells from its frame's origin", ax, ay);
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_unit(&hs->mrg));
+    SH_TRY(hs_unit<&slamhip_hs::mrg>(hs));
     hs_merge *m = hs->mrg;
     m->have = false;                                                       // (no source until this one has landed)
     hs_hg_drop_slot(hs, 1);
     const size_t n = (size_t)w * h;
     const int wpr = (w + 15) / 16;
     // (the blocks are idle: every call waits for its own launches, and a call that timed out has poisoned the context)
-    SH_TRY(hs_grow((void **)&m->h_stage, &m->cap_hstage, sizeof(slamhip_cell) * n, HS_MEM_PINNED, "merge"));
-    SH_TRY(hs_grow((void **)&m->d_stage, &m->cap_dstage, sizeof(slamhip_cell) * n, HS_MEM_DEVICE, "merge"));
-    SH_TRY(hs_grow((void **)&m->d_val, &m->cap_val, sizeof(float) * n, HS_MEM_DEVICE, "merge"));
-    SH_TRY(hs_grow((void **)&m->d_cls, &m->cap_cls, sizeof(uint32_t) * (size_t)wpr * h, HS_MEM_DEVICE, "merge"));
+    SH_TRY(m->h_stage.grow(sizeof(slamhip_cell) * n, "merge"));
+    SH_TRY(m->d_stage.grow(sizeof(slamhip_cell) * n, "merge"));
+    SH_TRY(m->d_val.grow(sizeof(float) * n, "merge"));
+    SH_TRY(m->d_cls.grow(sizeof(uint32_t) * (size_t)wpr * h, "merge"));
     memcpy(m->h_stage, cells, sizeof(slamhip_cell) * n);
     hipStream_t st = hs->ctx->stream;
     SH_HIP(hipMemcpyAsync(m->d_stage, m->h_stage, sizeof(slamhip_cell) * n, hipMemcpyHostToDevice, st));
@@ -316,9 +301,9 @@ extern "C" int32_t slamhip_hs_merge_score(slamhip_hs *hs, const float *poses, in
     hs_class_map M;
     SH_TRY(hs_lat_pack_prepare(hs, m->level, false, &M));
     const size_t rep_bytes = sizeof(slamhip_merge_report) * (size_t)B, xf_bytes = sizeof(hs_merge_xf) * (size_t)B;
-    SH_TRY(hs_grow((void **)&m->d_xf, &m->cap_xf, xf_bytes, HS_MEM_DEVICE, "merge"));
-    SH_TRY(hs_grow((void **)&m->d_rep, &m->cap_rep, rep_bytes, HS_MEM_DEVICE, "merge"));
-    SH_TRY(hs_grow((void **)&m->h_io, &m->cap_h, rep_bytes + xf_bytes, HS_MEM_PINNED, "merge"));
+    SH_TRY(m->d_xf.grow(xf_bytes, "merge"));
+    SH_TRY(m->d_rep.grow(rep_bytes, "merge"));
+    SH_TRY(m->h_io.grow(rep_bytes + xf_bytes, "merge"));
     hs_merge_xf *h_xf = (hs_merge_xf *)(m->h_io + rep_bytes);
     for (int i = 0; i < B; i++) h_xf[i] = hs_merge_xf_of(L.stm, poses[3 * i], poses[3 * i + 1], poses[3 * i + 2]);
     hipStream_t st = hs->ctx->stream;
@@ -364,8 +349,8 @@ extern "C" int32_t slamhip_hs_merge_apply(slamhip_hs *hs, const float pose[3], i
     hs_merge *m = hs->mrg;
     hs_level &L = hs->lv[m->level];
     const size_t rep_bytes = sizeof(slamhip_merge_report);
-    SH_TRY(hs_grow((void **)&m->d_rep, &m->cap_rep, rep_bytes, HS_MEM_DEVICE, "merge"));
-    SH_TRY(hs_grow((void **)&m->h_io, &m->cap_h, rep_bytes, HS_MEM_PINNED, "merge"));
+    SH_TRY(m->d_rep.grow(rep_bytes, "merge"));
+    SH_TRY(m->h_io.grow(rep_bytes, "merge"));
     hipStream_t st = hs->ctx->stream;
     SH_HIP(hipMemsetAsync(m->d_rep, 0, rep_bytes, st));
     k14_apply_arg A;

@@ -318,41 +318,21 @@ __global__ void __launch_bounds__(256) k11_emit(const uint32_t *__restrict__ ctr
 // flags, the counters, the sources, goals, goal results, path heads and path cells in device memory, the rectangle's device block,
 // a pinned, device-visible block for what the kernels store (k11_peek, k11_emit), and a second one for what is copied.
 struct hs_nav {
-    uint32_t *d_tw; size_t cap_tw;
-    uint32_t *d_cost; size_t cap_cost;
-    uint8_t *d_dir; size_t cap_dir;
-    uint8_t *d_act; size_t cap_act;
-    uint32_t *d_ctr; size_t cap_ctr;
-    uint32_t *d_batch; size_t cap_batch;
-    int *d_in; size_t cap_in;              // sources, then goals
-    unsigned char *d_res; size_t cap_res;  // goal results, then path heads
-    int *d_pcells; size_t cap_pcells;
-    unsigned char *d_rect; size_t cap_rect;   // the rectangle's costs, then its dirs
-    uint32_t *h_head; size_t cap_head;     // device-visible: the peek block, then k11_emit's
-    unsigned char *h_io; size_t cap_io;    // sources and goals going in; path cells and the rectangle coming out
+    hs_block<uint32_t, HS_MEM_DEVICE> d_tw;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_cost;
+    hs_block<uint8_t, HS_MEM_DEVICE> d_dir;
+    hs_block<uint8_t, HS_MEM_DEVICE> d_act;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_ctr;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_batch;
+    hs_block<int, HS_MEM_DEVICE> d_in;              // sources, then goals
+    hs_block<unsigned char, HS_MEM_DEVICE> d_res;  // goal results, then path heads
+    hs_block<int, HS_MEM_DEVICE> d_pcells;
+    hs_block<unsigned char, HS_MEM_DEVICE> d_rect;   // the rectangle's costs, then its dirs
+    hs_block<uint32_t, HS_MEM_PINNED_VISIBLE> h_head;     // device-visible: the peek block, then k11_emit's
+    hs_block<unsigned char, HS_MEM_PINNED_VISIBLE> h_io;    // sources and goals going in; path cells and the rectangle coming out
 };
 #define HS_NAV_PEEK_WORDS (K11_MAX_BATCH + K11_CTRS)
 #define HS_NAV_HEAD_BYTES (sizeof(uint32_t) * (HS_NAV_PEEK_WORDS + K11_CTRS + 4 * (size_t)HS_NAV_MAX_GOALS + 2 * (size_t)HS_NAV_MAX_PATHS))
-
-void hs_nav_free(slamhip_hs *hs)
-{
-    hs_nav *nv = hs->nav;
-    if (!nv) return;
-    hs_release((void **)&nv->d_tw, &nv->cap_tw, HS_MEM_DEVICE);
-    hs_release((void **)&nv->d_cost, &nv->cap_cost, HS_MEM_DEVICE);
-    hs_release((void **)&nv->d_dir, &nv->cap_dir, HS_MEM_DEVICE);
-    hs_release((void **)&nv->d_act, &nv->cap_act, HS_MEM_DEVICE);
-    hs_release((void **)&nv->d_ctr, &nv->cap_ctr, HS_MEM_DEVICE);
-    hs_release((void **)&nv->d_batch, &nv->cap_batch, HS_MEM_DEVICE);
-    hs_release((void **)&nv->d_in, &nv->cap_in, HS_MEM_DEVICE);
-    hs_release((void **)&nv->d_res, &nv->cap_res, HS_MEM_DEVICE);
-    hs_release((void **)&nv->d_pcells, &nv->cap_pcells, HS_MEM_DEVICE);
-    hs_release((void **)&nv->d_rect, &nv->cap_rect, HS_MEM_DEVICE);
-    hs_release((void **)&nv->h_head, &nv->cap_head, HS_MEM_PINNED_VISIBLE);
-    hs_release((void **)&nv->h_io, &nv->cap_io, HS_MEM_PINNED_VISIBLE);
-    delete nv;
-    hs->nav = nullptr;
-}
 
 // what both entry points refuse for their arguments alone
 static int32_t hs_nav_check(int32_t site_mask, int32_t clearance, const int32_t *sources, int32_t S, const int32_t *goals, int32_t G,
@@ -414,7 +394,7 @@ static int32_t hs_nav_build(slamhip_hs *hs, const slamhip_nav_spec *spec, const 
     else SH_TRY(hs_lat_pack_prepare(hs, level, world, &M));
     const int64_t cells = (int64_t)M.w * M.h;
     if (cells > HS_NAV_MAX_M) SH_FAIL(SLAMHIP_ERR_INVALID, "navigation field: M, the class map of level %d, is %d x %d cells, more than 2^25", level, M.w, M.h);
-    SH_TRY(hs_unit(&hs->nav));
+    SH_TRY(hs_unit<&slamhip_hs::nav>(hs));
     hs_nav *nv = hs->nav;
     k11_geo A;
     A.cls = M.cls; A.w = M.w; A.h = M.h; A.wpr = M.wpr;
@@ -425,18 +405,18 @@ static int32_t hs_nav_build(slamhip_hs *hs, const slamhip_nav_spec *spec, const 
     const int nt = A.tiles_x * A.tiles_y;
     const size_t src_bytes = sizeof(int) * 2 * (size_t)S, goal_bytes = sizeof(int) * 4 * (size_t)G;
     const size_t act_bytes = ((size_t)2 * nt + 15) & ~(size_t)15;
-    SH_TRY(hs_grow((void **)&nv->d_tw, &nv->cap_tw, sizeof(uint32_t) * (size_t)A.twpr * M.h, HS_MEM_DEVICE, "navigation field"));
-    SH_TRY(hs_grow((void **)&nv->d_cost, &nv->cap_cost, sizeof(uint32_t) * (size_t)cells, HS_MEM_DEVICE, "navigation field"));
-    SH_TRY(hs_grow((void **)&nv->d_dir, &nv->cap_dir, (size_t)cells, HS_MEM_DEVICE, "navigation field"));
-    SH_TRY(hs_grow((void **)&nv->d_act, &nv->cap_act, act_bytes, HS_MEM_DEVICE, "navigation field"));
-    SH_TRY(hs_grow((void **)&nv->d_ctr, &nv->cap_ctr, sizeof(uint32_t) * K11_CTRS, HS_MEM_DEVICE, "navigation field"));
-    SH_TRY(hs_grow((void **)&nv->d_batch, &nv->cap_batch, sizeof(uint32_t) * K11_MAX_BATCH, HS_MEM_DEVICE, "navigation field"));
-    SH_TRY(hs_grow((void **)&nv->d_in, &nv->cap_in, src_bytes + goal_bytes, HS_MEM_DEVICE, "navigation field"));
-    SH_TRY(hs_grow((void **)&nv->d_res, &nv->cap_res, sizeof(slamhip_nav_goal_result) * (size_t)HS_NAV_MAX_GOALS + sizeof(slamhip_nav_path) * HS_NAV_MAX_PATHS, HS_MEM_DEVICE, "navigation field"));
-    if (pc_bytes) SH_TRY(hs_grow((void **)&nv->d_pcells, &nv->cap_pcells, pc_bytes, HS_MEM_DEVICE, "navigation field"));
-    if (rc_bytes + rd_bytes) SH_TRY(hs_grow((void **)&nv->d_rect, &nv->cap_rect, rc_bytes + rd_bytes, HS_MEM_DEVICE, "navigation field"));
-    SH_TRY(hs_grow((void **)&nv->h_head, &nv->cap_head, HS_NAV_HEAD_BYTES, HS_MEM_PINNED_VISIBLE, "navigation field"));
-    SH_TRY(hs_grow((void **)&nv->h_io, &nv->cap_io, std::max(src_bytes + goal_bytes, pc_bytes + rc_bytes + rd_bytes), HS_MEM_PINNED_VISIBLE, "navigation field"));
+    SH_TRY(nv->d_tw.grow(sizeof(uint32_t) * (size_t)A.twpr * M.h, "navigation field"));
+    SH_TRY(nv->d_cost.grow(sizeof(uint32_t) * (size_t)cells, "navigation field"));
+    SH_TRY(nv->d_dir.grow((size_t)cells, "navigation field"));
+    SH_TRY(nv->d_act.grow(act_bytes, "navigation field"));
+    SH_TRY(nv->d_ctr.grow(sizeof(uint32_t) * K11_CTRS, "navigation field"));
+    SH_TRY(nv->d_batch.grow(sizeof(uint32_t) * K11_MAX_BATCH, "navigation field"));
+    SH_TRY(nv->d_in.grow(src_bytes + goal_bytes, "navigation field"));
+    SH_TRY(nv->d_res.grow(sizeof(slamhip_nav_goal_result) * (size_t)HS_NAV_MAX_GOALS + sizeof(slamhip_nav_path) * HS_NAV_MAX_PATHS, "navigation field"));
+    if (pc_bytes) SH_TRY(nv->d_pcells.grow(pc_bytes, "navigation field"));
+    if (rc_bytes + rd_bytes) SH_TRY(nv->d_rect.grow(rc_bytes + rd_bytes, "navigation field"));
+    SH_TRY(nv->h_head.grow(HS_NAV_HEAD_BYTES, "navigation field"));
+    SH_TRY(nv->h_io.grow(std::max(src_bytes + goal_bytes, pc_bytes + rc_bytes + rd_bytes), "navigation field"));
     A.tw = nv->d_tw; A.cost = nv->d_cost; A.dir = nv->d_dir; A.act = nv->d_act; A.ctr = nv->d_ctr;
     int *d_src = nv->d_in;
     const int batch = (int)std::min<long long>(std::max<long long>(sh_env_int("SLAMHIP_NAV_BATCH", K11_BATCH), 1), K11_MAX_BATCH);
@@ -510,7 +490,7 @@ extern "C" int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *
     const int64_t cells = Bt.cells;
     const int rounds = Bt.rounds;
     const int *d_goals = Bt.d_goals;
-    slamhip_nav_goal_result *d_res = (slamhip_nav_goal_result *)nv->d_res;
+    slamhip_nav_goal_result *d_res = (slamhip_nav_goal_result *)nv->d_res.p;
     slamhip_nav_path *d_heads = (slamhip_nav_path *)(nv->d_res + sizeof(slamhip_nav_goal_result) * (size_t)HS_NAV_MAX_GOALS);
     hipStream_t st = ctx->stream;
     const uint32_t *head = nv->h_head + HS_NAV_PEEK_WORDS;
@@ -529,7 +509,7 @@ extern "C" int32_t slamhip_hs_nav_field(slamhip_hs *hs, const slamhip_nav_spec *
         const int64_t far = (int64_t)1 << 30;                              // (a rectangle that far from M lies outside it; -2^28 < x0 <= 0)
         const int gx = (int)std::min(std::max((int64_t)rx - M.x0, -far), far), gy = (int)std::min(std::max((int64_t)ry - M.y0, -far), far);
         hipLaunchKernelGGL(k11_gather, dim3((unsigned)sh_div_up(n_rect, 256)), dim3(256), 0, st, A, gx, gy, rw, n_rect,
-                           out_cost ? (uint32_t *)nv->d_rect : (uint32_t *)nullptr, out_dir ? (uint8_t *)(nv->d_rect + rc_bytes) : (uint8_t *)nullptr);
+                           out_cost ? (uint32_t *)nv->d_rect.p : (uint32_t *)nullptr, out_dir ? (uint8_t *)(nv->d_rect + rc_bytes) : (uint8_t *)nullptr);
         SH_HIP(hipGetLastError());
         SH_HIP(hipMemcpyAsync(nv->h_io + pc_bytes, nv->d_rect, rc_bytes + rd_bytes, hipMemcpyDeviceToHost, st));
     }

@@ -160,8 +160,6 @@ __global__ void __launch_bounds__(K16P_LANES) k16_pairs(const k16p_arg A)
 
 // ---- host side ---------------------------------------------------------------------------------------------------
 // The unit's blocks are hs->nrs, a hs_field_unit (hs_field.h): the row offsets and N of E, and the pose batch's.
-void hs_nr_free(slamhip_hs *hs) { hs_field_unit_free(&hs->nrs); }
-
 int32_t hs_nr_check_pairs(int n_levels, int32_t level, int32_t world, int32_t site_mask, int32_t radius, int32_t B, bool want_pairs, int n_points,
                           bool scan_is_set)
 {
@@ -174,7 +172,7 @@ extern "C" int32_t slamhip_hs_nearest_field(slamhip_hs *hs, int32_t level, int32
 {
     SH_CHECK_ARG(hs && out_dxdy);
     SH_TRY(hs_df_check("nearest field", hs->n_levels, level, world, site_mask, radius));
-    return hs_field_call(hs, &hs->nrs, "nearest field", k16_rows, k16_cols, level, world != 0, site_mask, radius, hs_nr_outside(site_mask), x, y, w, h, out_dxdy);
+    return hs_field_call<&slamhip_hs::nrs>(hs, "nearest field", k16_rows, k16_cols, level, world != 0, site_mask, radius, hs_nr_outside(site_mask), x, y, w, h, out_dxdy);
 }
 
 extern "C" int32_t slamhip_hs_nearest_pairs(slamhip_hs *hs, int32_t level, int32_t world, int32_t site_mask, int32_t radius,
@@ -187,7 +185,7 @@ extern "C" int32_t slamhip_hs_nearest_pairs(slamhip_hs *hs, int32_t level, int32
     int chunks;
     SH_TRY(hs_pose_batch_chunks("nearest pairs", B, n, K16P_LANES, &chunks));
     hs_class_map M; hs_nfield E;
-    SH_TRY(hs_field_prepare(hs, &hs->nrs, "nearest field", sizeof(int16_t), level, world != 0, radius, hs_nr_outside(site_mask), &M, &E));
+    SH_TRY(hs_field_prepare<&slamhip_hs::nrs>(hs, "nearest field", sizeof(int16_t), level, world != 0, radius, hs_nr_outside(site_mask), &M, &E));
     hs_pose_batch *pb = &hs->nrs->pb;
     const size_t sum_bytes = sizeof(slamhip_pair_summary) * (size_t)B;     // (a multiple of 8: the pairs behind it stay aligned)
     const size_t pts_bytes = out_pairs ? sizeof(uint32_t) * (size_t)B * n : 0;
@@ -198,7 +196,7 @@ extern "C" int32_t slamhip_hs_nearest_pairs(slamhip_hs *hs, int32_t level, int32
     A.poses = pb->d_poses; A.chunks = chunks;
     A.stm = hs->lv[level].stm;
     A.E = E;
-    A.sums = (slamhip_pair_summary *)pb->d_out;
+    A.sums = (slamhip_pair_summary *)pb->d_out.p;
     A.pairs = out_pairs ? (uint32_t *)(pb->d_out + sum_bytes) : (uint32_t *)nullptr;
     hipLaunchKernelGGL(k16_pairs, dim3((unsigned)(B * chunks)), dim3(K16P_LANES), 0, hs->ctx->stream, A);
     SH_HIP(hipGetLastError());

@@ -292,27 +292,14 @@ __global__ void __launch_bounds__(K19_LANES) k19_update(const k19_arg A, double 
 struct hs_pg {
     bool have;
     k19_arg A;
-    unsigned char *d_blob; size_t cap_blob;
-    unsigned char *h_io; size_t cap_h;
-    unsigned char *d_tri; size_t cap_tri;                  // K22 (hs_pg_tri.inc): the levels' blocks, made by the first _pg_relax_tri / _pg_tri_apply
+    hs_block<unsigned char, HS_MEM_DEVICE> d_blob;
+    hs_block<unsigned char, HS_MEM_PINNED> h_io;
+    hs_block<unsigned char, HS_MEM_DEVICE> d_tri;                  // K22 (hs_pg_tri.inc): the levels' blocks, made by the first _pg_relax_tri / _pg_tri_apply
     hs_tri_plan T;
-    unsigned char *d_lm; size_t cap_lm;                    // K26 (hs_pg_lm.inc): the weights, the trial poses and the records, made by the first _pg_relax_lm
-    unsigned char *d_marg; size_t cap_marg;                // K27 (hs_pg_marg.inc): the query and the batch's work block, made by the first _pg_marginals
+    hs_block<unsigned char, HS_MEM_DEVICE> d_lm;                    // K26 (hs_pg_lm.inc): the weights, the trial poses and the records, made by the first _pg_relax_lm
+    hs_block<unsigned char, HS_MEM_DEVICE> d_marg;                // K27 (hs_pg_marg.inc): the query and the batch's work block, made by the first _pg_marginals
     std::vector<unsigned char> fx;                         // the fixed bytes as the device has them: K27 forms its columns on the host
 };
-
-void hs_pg_free(slamhip_hs *hs)
-{
-    hs_pg *g = hs->pg;
-    if (!g) return;
-    hs_release((void **)&g->d_blob, &g->cap_blob, HS_MEM_DEVICE);
-    hs_release((void **)&g->h_io, &g->cap_h, HS_MEM_PINNED);
-    hs_release((void **)&g->d_tri, &g->cap_tri, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_lm, &g->cap_lm, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_marg, &g->cap_marg, HS_MEM_DEVICE);
-    delete g;
-    hs->pg = nullptr;
-}
 
 void hs_pg_reset(slamhip_hs *hs)
 {
@@ -388,7 +375,7 @@ extern "C" int32_t slamhip_hs_pg_set(slamhip_hs *hs, const double *poses, const 
     SH_TRY(hs_pg_check_graph(poses, fixed, N, ij, z, w, E));
     slamhip_ctx *ctx = hs->ctx;
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_unit(&hs->pg));
+    SH_TRY(hs_unit<&slamhip_hs::pg>(hs));
     hs_pg *g = hs->pg;
     g->have = false;
     const size_t n = (size_t)N, e = (size_t)E;
@@ -415,8 +402,8 @@ extern "C" int32_t slamhip_hs_pg_set(slamhip_hs *hs, const double *poses, const 
     const size_t o_st = o; o += hs_pg_al(sizeof(k19_state));
     const size_t o_it = o; o += hs_pg_al(sizeof(slamhip_pg_iter) * HS_PG_MAX_OUTER);
     const size_t o_fin = o; o += hs_pg_al(8);
-    SH_TRY(hs_grow((void **)&g->d_blob, &g->cap_blob, o, HS_MEM_DEVICE, "pose graph"));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, std::max(in_bytes, 32 * e), HS_MEM_PINNED, "pose graph"));
+    SH_TRY(g->d_blob.grow(o, "pose graph"));
+    SH_TRY(g->h_io.grow(std::max(in_bytes, 32 * e), "pose graph"));
     unsigned char *h = g->h_io, *d = g->d_blob;
     memcpy(h + o_pose, poses, 24 * n);
     hs_pg_fixed_bytes(fixed, N, h + o_fixed);
@@ -458,7 +445,7 @@ extern "C" int32_t slamhip_hs_pg_get(slamhip_hs *hs, double *poses, int32_t N)
     if (N != g->A.N) SH_FAIL(SLAMHIP_ERR_INVALID, "pose graph get: N = %d, but the graph has %d nodes", N, g->A.N);
     SH_TRY(hs_call_begin(hs));
     const size_t bytes = 24 * (size_t)N;
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, bytes, HS_MEM_PINNED, "pose graph get"));
+    SH_TRY(g->h_io.grow(bytes, "pose graph get"));
     SH_HIP(hipMemcpyAsync(g->h_io, g->A.pose, bytes, hipMemcpyDeviceToHost, hs->ctx->stream));
     SH_TRY(hs_call_finish(hs));
     memcpy(poses, g->h_io, bytes);
@@ -475,7 +462,7 @@ extern "C" int32_t slamhip_hs_pg_residuals(slamhip_hs *hs, double *out_r, double
     hipStream_t st = hs->ctx->stream;
     SH_TRY(hs_call_begin(hs));
     const size_t e = (size_t)A.E;
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, 32 * e, HS_MEM_PINNED, "pose graph residuals"));
+    SH_TRY(g->h_io.grow(32 * e, "pose graph residuals"));
     K19_LAUNCH(k19_linearise, A.PE, A);
     SH_HIP(hipMemcpyAsync(g->h_io, A.r, 24 * e, hipMemcpyDeviceToHost, st));
     SH_HIP(hipMemcpyAsync(g->h_io + 24 * e, A.chi2e, 8 * e, hipMemcpyDeviceToHost, st));
@@ -491,7 +478,7 @@ extern "C" int32_t slamhip_hs_pg_clear(slamhip_hs *hs)
     if (!hs->pg) return SLAMHIP_OK;
     SH_TRY(hs_call_begin(hs));
     SH_TRY(hs_call_finish(hs));                                            // (the block is idle behind it)
-    hs_pg_free(hs);
+    hs_unit_drop<&slamhip_hs::pg>(hs);
     return SLAMHIP_OK;
 }
 

@@ -124,7 +124,7 @@ static int32_t hs_lm_blocks(hs_pg *g, const char *who, k26_arg *L)
     const size_t o_st = o; o += hs_pg_al(sizeof(k26_state));
     const size_t o_it = o; o += hs_pg_al(sizeof(slamhip_pg_lm_iter) * HS_PG_MAX_OUTER);
     const size_t o_fin = o; o += hs_pg_al(8);
-    SH_TRY(hs_grow((void **)&g->d_lm, &g->cap_lm, o, HS_MEM_DEVICE, who));
+    SH_TRY(g->d_lm.grow(o, who));
     unsigned char *d = g->d_lm;
     L->robust = d + o_robust;
     L->w_eff = (double *)(d + o_w); L->f = (double *)(d + o_f); L->trial = (double *)(d + o_trial);
@@ -153,7 +153,7 @@ extern "C" int32_t slamhip_hs_pg_relax_lm(slamhip_hs *hs, const slamhip_pg_lm_sp
     // the pinned block: the records, F, f, the two state words' copies, the robust bytes on their way in
     const size_t e = (size_t)A.E, rec_bytes = sizeof(slamhip_pg_lm_iter) * (size_t)spec->n_outer;
     const size_t o_fin = rec_bytes, o_f = o_fin + 8, o_st = o_f + 8 * e, o_lst = o_st + hs_pg_al(sizeof(k19_state)), o_rob = o_lst + hs_pg_al(sizeof(k26_state));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, o_rob + e, HS_MEM_PINNED, "pose graph relax (lm)"));
+    SH_TRY(g->h_io.grow(o_rob + e, "pose graph relax (lm)"));
     k19_state *h_st = (k19_state *)(g->h_io + o_st);
     k26_state *h_lst = (k26_state *)(g->h_io + o_lst);
     if (robust && e) {

@@ -451,10 +451,10 @@ extern "C" int32_t slamhip_hs_pg_marginals(slamhip_hs *hs, const slamhip_pg_marg
     const size_t o_R = o; o += 8 * rs * Rc;
     const size_t o_st = o; o += sizeof(k27_state) * Rc;
     const size_t o_stop = o; o += 8 * Rc;
-    SH_TRY(hs_grow((void **)&g->d_marg, &g->cap_marg, o, HS_MEM_DEVICE, "pose graph marginals"));
+    SH_TRY(g->d_marg.grow(o, "pose graph marginals"));
     // the pinned block: the query on its way in; the blocks, the records and the stop words' copy on their way out
     const size_t h_stop_at = hs_pg_al(std::max(in_bytes, blk_bytes + rec_bytes));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, h_stop_at + 4 * Rc, HS_MEM_PINNED, "pose graph marginals"));
+    SH_TRY(g->h_io.grow(h_stop_at + 4 * Rc, "pose graph marginals"));
     unsigned char *h = g->h_io, *d = g->d_marg;
     memcpy(h + o_cols, Q.cols.data(), 4 * (size_t)C);
     memcpy(h + o_pn, Q.pn.data(), 4 * np);

@@ -188,7 +188,7 @@ static int32_t hs_tri_blocks(hs_pg *g, const char *who)
     const size_t o_U = o; o += hs_pg_al(72 * tot);
     const size_t o_R = o; o += hs_pg_al(24 * (tot - n) + 24);
     const size_t o_live = o; o += hs_pg_al(n);
-    SH_TRY(hs_grow((void **)&g->d_tri, &g->cap_tri, o, HS_MEM_DEVICE, who));
+    SH_TRY(g->d_tri.grow(o, who));
     unsigned char *d = g->d_tri;
     T.D = (double *)(d + o_D); T.P = (double *)(d + o_P); T.U = (double *)(d + o_U); T.R = (double *)(d + o_R); T.live = d + o_live;
     return SLAMHIP_OK;
@@ -274,7 +274,7 @@ static int32_t hs_pg_relax_run(slamhip_hs *hs, const slamhip_pg_spec *spec, bool
     if (tri) SH_TRY(hs_tri_blocks(g, who));
     // the pinned block: the records, the final chi2, the stop word's copy
     const size_t out_bytes = sizeof(slamhip_pg_iter) * (size_t)spec->n_outer;
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, out_bytes + 8 + sizeof(k19_state), HS_MEM_PINNED, who));
+    SH_TRY(g->h_io.grow(out_bytes + 8 + sizeof(k19_state), who));
     k19_state *h_st = (k19_state *)(g->h_io + out_bytes + 8);
     for (int outer = 0; outer < spec->n_outer; outer++) {
         K19_LAUNCH(k19_linearise, A.PE, A);
@@ -314,7 +314,7 @@ extern "C" int32_t slamhip_hs_pg_tri_apply(slamhip_hs *hs, double lambda, const 
     SH_TRY(hs_call_begin(hs));
     SH_TRY(hs_tri_blocks(g, "pose graph tri apply"));
     const size_t bytes = 24 * (size_t)A.N;
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, bytes, HS_MEM_PINNED, "pose graph tri apply"));
+    SH_TRY(g->h_io.grow(bytes, "pose graph tri apply"));
     memcpy(g->h_io, rhs, bytes);
     SH_HIP(hipMemcpyAsync(A.res, g->h_io, bytes, hipMemcpyHostToDevice, st));   // (the PCG vectors are free between two calls)
     K19_LAUNCH(k19_linearise, A.PE, A);

@@ -319,7 +319,7 @@ template <class Arg>
 static inline int32_t hs_render_begin(hs_render_frame &F, Arg &A, const char *who, slamhip_hs *hs, int32_t first, int32_t last, const float *poses, int32_t flags)
 {
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_unit(&hs->scn));
+    SH_TRY(hs_unit<&slamhip_hs::scn>(hs));
     F.hs = hs; F.g = hs->scn; F.who = who; F.poses = poses; F.first = first; F.N = last - first; F.NL = hs->n_levels;
     F.keep = (flags & SLAMHIP_RENDER_KEEP) != 0;
     F.chunk = std::min(k20_chunk(), std::max(F.N, 1));
@@ -336,9 +336,9 @@ static inline int32_t hs_render_lay(const hs_render_frame &F, hs_render_args<Box
 {
     hs_scans *g = F.g;
     const size_t all = F.in_bytes + F.box_bytes + more;
-    SH_TRY(hs_grow((void **)&g->d_in, &g->cap_in, all, HS_MEM_DEVICE, F.who));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, mirror ? all : F.in_bytes, HS_MEM_PINNED, F.who));
-    P.scans = (const k20_scan *)g->d_in; P.mats = (const sh_m3x2 *)(g->d_in + F.scan_bytes); P.boxes = (Box *)(g->d_in + F.in_bytes);
+    SH_TRY(g->d_in.grow(all, F.who));
+    SH_TRY(g->h_io.grow(mirror ? all : F.in_bytes, F.who));
+    P.scans = (const k20_scan *)g->d_in.p; P.mats = (const sh_m3x2 *)(g->d_in + F.scan_bytes); P.boxes = (Box *)(g->d_in + F.in_bytes);
     return SLAMHIP_OK;
 }
 
@@ -346,7 +346,7 @@ static inline int32_t hs_render_lay(const hs_render_frame &F, hs_render_args<Box
 template <class Arg>
 static inline int32_t hs_render_stage(const hs_render_frame &F, Arg &A, int c0, int nc)
 {
-    k20_scan *hr = (k20_scan *)F.g->h_io;
+    k20_scan *hr = (k20_scan *)F.g->h_io.p;
     sh_m3x2 *hm = (sh_m3x2 *)(F.g->h_io + F.scan_bytes);
     for (int k = 0; k < nc; k++) {
         hr[k] = F.g->recs[(size_t)(F.first + c0 + k)];

@@ -48,17 +48,6 @@ __global__ void __launch_bounds__(HS_RENDER_LANES) k20_render(const k20_arg A)
 // ---- host side ---------------------------------------------------------------------------------------------------
 // What the unit keeps: struct hs_scans, hs_scans.h (K21 reads the pool and the records).
 
-void hs_scn_free(slamhip_hs *hs)
-{
-    hs_scans *g = hs->scn;
-    if (!g) return;
-    hs_release((void **)&g->d_pool, nullptr, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_in, &g->cap_in, HS_MEM_DEVICE);
-    hs_release((void **)&g->h_io, &g->cap_h, HS_MEM_PINNED);
-    delete g;
-    hs->scn = nullptr;
-}
-
 void hs_scn_reset(slamhip_hs *hs)
 {
     if (!hs->scn) return;
@@ -73,16 +62,14 @@ static int32_t hs_scn_reserve(slamhip_hs *hs, size_t pts)
     if (pts <= g->cap_pts) return SLAMHIP_OK;
     static const long long first_cap = std::max(1ll, sh_env_int("SLAMHIP_K20_POOL_POINTS", 1 << 16));     // (tests: growth within a few scans)
     const size_t cap = std::max(std::max(pts, 2 * g->cap_pts), (size_t)first_cap);
-    float2 *np = nullptr;
-    size_t c0 = 0;
-    SH_TRY(hs_grow((void **)&np, &c0, sizeof(float2) * cap, HS_MEM_DEVICE, "scan store"));
+    hs_block<float2, HS_MEM_DEVICE> np;                                    // (an early return frees it)
+    SH_TRY(np.grow(sizeof(float2) * cap, "scan store"));
     hipStream_t st = hs->ctx->stream;
     hipError_t e = hipSuccess;
     if (g->used_pts) e = hipMemcpyAsync(np, g->d_pool, sizeof(float2) * g->used_pts, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);                     // (the old pool is idle behind it)
-    if (e != hipSuccess) { (void)hipFree(np); SH_HIP(e); }
-    hs_release((void **)&g->d_pool, nullptr, HS_MEM_DEVICE);
-    g->d_pool = np; g->cap_pts = cap;
+    SH_HIP(e);
+    g->d_pool.swap(np); g->cap_pts = cap;                                  // (the old pool goes with np)
     return SLAMHIP_OK;
 }
 
@@ -93,7 +80,7 @@ extern "C" int32_t slamhip_hs_scans_add(slamhip_hs *hs, const float *xy, int32_t
     if (!own) SH_CHECK_ARG(n_points >= 0);
     if (hs->scn && hs->scn->recs.size() >= (size_t)K20_MAX_SCANS) SH_FAIL(SLAMHIP_ERR_INVALID, "scan store: it holds 2^20 scans");
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_unit(&hs->scn));
+    SH_TRY(hs_unit<&slamhip_hs::scn>(hs));
     hs_scans *g = hs->scn;
     const int n = own ? hs->n_points : n_points;
     k20_scan R;
@@ -107,7 +94,7 @@ extern "C" int32_t slamhip_hs_scans_add(slamhip_hs *hs, const float *xy, int32_t
             SH_TRY(hs_flush_scan(hs));
             SH_HIP(hipMemcpyAsync(g->d_pool + g->used_pts, hs->d_pts, bytes, hipMemcpyDeviceToDevice, hs->ctx->stream));
         } else {
-            SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, bytes, HS_MEM_PINNED, "scan store"));
+            SH_TRY(g->h_io.grow(bytes, "scan store"));
             memcpy(g->h_io, xy, bytes);
             SH_HIP(hipMemcpyAsync(g->d_pool + g->used_pts, g->h_io, bytes, hipMemcpyHostToDevice, hs->ctx->stream));
         }
@@ -154,7 +141,7 @@ extern "C" int32_t slamhip_hs_scans_download(slamhip_hs *hs, int32_t k, float *o
     SH_CHECK_ARG(out_xy);
     SH_TRY(hs_call_begin(hs));
     const size_t bytes = sizeof(float2) * (size_t)R.n;
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, bytes, HS_MEM_PINNED, "scan store download"));
+    SH_TRY(g->h_io.grow(bytes, "scan store download"));
     SH_HIP(hipMemcpyAsync(g->h_io, g->d_pool + R.off, bytes, hipMemcpyDeviceToHost, hs->ctx->stream));
     SH_TRY(hs_call_finish(hs));
     memcpy(out_xy, g->h_io, bytes);
@@ -167,7 +154,7 @@ extern "C" int32_t slamhip_hs_scans_clear(slamhip_hs *hs)
     if (!hs->scn) return SLAMHIP_OK;
     SH_TRY(hs_call_begin(hs));
     SH_TRY(hs_call_finish(hs));                                            // (the blocks are idle behind it)
-    hs_scn_free(hs);
+    hs_unit_drop<&slamhip_hs::scn>(hs);
     return SLAMHIP_OK;
 }
 

@@ -154,24 +154,12 @@ __global__ void __launch_bounds__(64) k12_emit(const hs_ro_field F, const hs_ro_
 // memory, the records, the keys and the count of complete rollouts, a pinned block the inputs leave and the records reach the
 // host through, and a pinned, device-visible block for what k12_emit stores.
 struct hs_rollout {
-    float *d_in; size_t cap_in;            // the commands, then the body points
-    unsigned char *d_out; size_t cap_out;  // key_end, key_min, n_complete (24 bytes with padding), then B records
-    unsigned char *h_io; size_t cap_io;    // the records; behind them the inputs
-    uint32_t *h_head; size_t cap_head;
+    hs_block<float, HS_MEM_DEVICE> d_in;            // the commands, then the body points
+    hs_block<unsigned char, HS_MEM_DEVICE> d_out;  // key_end, key_min, n_complete (24 bytes with padding), then B records
+    hs_block<unsigned char, HS_MEM_PINNED> h_io;    // the records; behind them the inputs
+    hs_block<uint32_t, HS_MEM_PINNED_VISIBLE> h_head;
 };
 #define HS_RO_OUT_HEAD 32                  // bytes in front of the records in d_out
-
-void hs_ro_free(slamhip_hs *hs)
-{
-    hs_rollout *ro = hs->rol;
-    if (!ro) return;
-    hs_release((void **)&ro->d_in, &ro->cap_in, HS_MEM_DEVICE);
-    hs_release((void **)&ro->d_out, &ro->cap_out, HS_MEM_DEVICE);
-    hs_release((void **)&ro->h_io, &ro->cap_io, HS_MEM_PINNED);
-    hs_release((void **)&ro->h_head, &ro->cap_head, HS_MEM_PINNED_VISIBLE);
-    delete ro;
-    hs->rol = nullptr;
-}
 
 // what both entry points refuse for the rollouts' own arguments
 static int32_t hs_ro_check(const float *start_pose, float dt, const float *body, int32_t P, const float *cmds, int32_t B, int32_t n_cmd, int32_t hold,
@@ -240,15 +228,15 @@ extern "C" int32_t slamhip_hs_rollouts(slamhip_hs *hs, const slamhip_nav_spec *s
     SH_TRY(hs_ro_check(start_pose, dt, body, P, cmds, B, n_cmd, hold, out_results));
     slamhip_ctx *ctx = hs->ctx;
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_unit(&hs->rol));
+    SH_TRY(hs_unit<&slamhip_hs::rol>(hs));
     hs_rollout *ro = hs->rol;
     const size_t cmd_bytes = sizeof(float) * 2 * (size_t)B * (size_t)n_cmd, body_bytes = sizeof(float) * 2 * (size_t)P;
     const size_t in_bytes = cmd_bytes + body_bytes + 8;                    // (never empty, and the body block aligned)
     const size_t rec_bytes = sizeof(slamhip_rollout_result) * (size_t)B, rec_pad = (rec_bytes + 15) & ~(size_t)15;
-    SH_TRY(hs_grow((void **)&ro->d_in, &ro->cap_in, in_bytes, HS_MEM_DEVICE, "rollouts"));
-    SH_TRY(hs_grow((void **)&ro->d_out, &ro->cap_out, HS_RO_OUT_HEAD + rec_bytes, HS_MEM_DEVICE, "rollouts"));
-    SH_TRY(hs_grow((void **)&ro->h_io, &ro->cap_io, rec_pad + in_bytes, HS_MEM_PINNED, "rollouts"));
-    SH_TRY(hs_grow((void **)&ro->h_head, &ro->cap_head, sizeof(uint32_t) * K12_HEAD_WORDS, HS_MEM_PINNED_VISIBLE, "rollouts"));
+    SH_TRY(ro->d_in.grow(in_bytes, "rollouts"));
+    SH_TRY(ro->d_out.grow(HS_RO_OUT_HEAD + rec_bytes, "rollouts"));
+    SH_TRY(ro->h_io.grow(rec_pad + in_bytes, "rollouts"));
+    SH_TRY(ro->h_head.grow(sizeof(uint32_t) * K12_HEAD_WORDS, "rollouts"));
     hs_nav_view V;
     SH_TRY(hs_nav_field_for_rollouts(hs, spec, sources, S, &V));
     hipStream_t st = ctx->stream;
@@ -267,7 +255,7 @@ extern "C" int32_t slamhip_hs_rollouts(slamhip_hs *hs, const slamhip_nav_spec *s
     A.p0.x = start_pose[0]; A.p0.y = start_pose[1]; A.p0.th = start_pose[2]; A.dt = dt;
     A.cmds = ro->d_in; A.body = ro->d_in + 2 * (size_t)B * (size_t)n_cmd; A.P = P;
     A.B = B; A.n_cmd = n_cmd; A.hold = hold; A.T = n_cmd * hold;
-    A.keys = (unsigned long long *)ro->d_out; A.n_complete = (uint32_t *)(ro->d_out + 16);
+    A.keys = (unsigned long long *)ro->d_out.p; A.n_complete = (uint32_t *)(ro->d_out + 16);
     A.out = (hs_ro_result *)(ro->d_out + HS_RO_OUT_HEAD);
     const int sg = hs_ro_subgroup(P);
     const unsigned blocks = (unsigned)sh_div_up((int)((int64_t)B * sg), K12_LANES);

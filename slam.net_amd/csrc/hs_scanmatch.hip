@@ -173,19 +173,9 @@ __global__ void __launch_bounds__(K21_LANES) k21_pass(const k21_arg A)
 // ---- host side ---------------------------------------------------------------------------------------------------
 // What the unit keeps: one device block -- the pairs, then the results -- and its pinned twin.
 struct hs_scanmatch {
-    unsigned char *d_io; size_t cap_d;
-    unsigned char *h_io; size_t cap_h;
+    hs_block<unsigned char, HS_MEM_DEVICE> d_io;
+    hs_block<unsigned char, HS_MEM_PINNED> h_io;
 };
-
-void hs_smt_free(slamhip_hs *hs)
-{
-    hs_scanmatch *u = hs->smt;
-    if (!u) return;
-    hs_release((void **)&u->d_io, &u->cap_d, HS_MEM_DEVICE);
-    hs_release((void **)&u->h_io, &u->cap_h, HS_MEM_PINNED);
-    delete u;
-    hs->smt = nullptr;
-}
 
 // rule 7 for the spec, the count and the guesses (slamhip_hs_scans_edges stops here) ...
 static int32_t k21_check_args(const char *who, const slamhip_scanmatch_spec *S, const slamhip_scan_pair *pairs, int32_t n_pairs)
@@ -245,13 +235,13 @@ extern "C" int32_t slamhip_hs_scans_match(slamhip_hs *hs, const slamhip_scanmatc
     SH_TRY(k21_check("slamhip_hs_scans_match", spec, pairs, n_pairs, count));
     slamhip_ctx *ctx = hs->ctx;
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_unit(&hs->smt));
+    SH_TRY(hs_unit<&slamhip_hs::smt>(hs));
     hs_scanmatch *u = hs->smt;
     const hs_scans *g = hs->scn;
     const size_t pair_bytes = sizeof(k21_pair) * (size_t)n_pairs, acc_bytes = sizeof(k21_acc) * (size_t)n_pairs;
-    SH_TRY(hs_grow((void **)&u->d_io, &u->cap_d, pair_bytes + acc_bytes, HS_MEM_DEVICE, "slamhip_hs_scans_match"));
-    SH_TRY(hs_grow((void **)&u->h_io, &u->cap_h, pair_bytes + acc_bytes, HS_MEM_PINNED, "slamhip_hs_scans_match"));
-    k21_pair *hp = (k21_pair *)u->h_io;
+    SH_TRY(u->d_io.grow(pair_bytes + acc_bytes, "slamhip_hs_scans_match"));
+    SH_TRY(u->h_io.grow(pair_bytes + acc_bytes, "slamhip_hs_scans_match"));
+    k21_pair *hp = (k21_pair *)u->h_io.p;
     for (int i = 0; i < n_pairs; i++) {
         const k20_scan &R = g->recs[(size_t)pairs[i].ref], &Q = g->recs[(size_t)pairs[i].query];
         k21_pair p;
@@ -260,7 +250,7 @@ extern "C" int32_t slamhip_hs_scans_match(slamhip_hs *hs, const slamhip_scanmatc
         hp[i] = p;
     }
     k21_arg A;
-    A.pool = g->d_pool; A.pairs = (const k21_pair *)u->d_io; A.acc = (k21_acc *)(u->d_io + pair_bytes);
+    A.pool = g->d_pool; A.pairs = (const k21_pair *)u->d_io.p; A.acc = (k21_acc *)(u->d_io + pair_bytes);
     A.S = *spec;
     const int nth = 2 * spec->nt + 1;
     A.kb = k21_headings_per_block(n_pairs, nth);

@@ -1,7 +1,7 @@
 // hs_scans.h -- the store of keyframe scans (slamhip_hs_scans_add) as its two users see it: K20 (hs_render.hip), which owns and
 // fills it, and K21 (hs_scanmatch.hip), which reads the pool and the records.  Host code only.
 #pragma once
-#include "hs_internal.h"
+#include "hs_blocks.h"
 #include <vector>
 
 struct k20_scan { long long off; int n; float ox, oy; int pad; };          // a stored scan: where its points lie in the pool, how many, its origin
@@ -11,7 +11,7 @@ static_assert(sizeof(k20_scan) == 24, "the record the kernels read");
 // memory and the pinned block the first two leave the host through (a download's points arrive in it).
 struct hs_scans {
     std::vector<k20_scan> recs;
-    float2 *d_pool; size_t cap_pts, used_pts;
-    unsigned char *d_in; size_t cap_in;
-    unsigned char *h_io; size_t cap_h;
+    hs_block<float2, HS_MEM_DEVICE> d_pool; size_t cap_pts, used_pts;   // (points; the block's own cap is bytes)
+    hs_block<unsigned char, HS_MEM_DEVICE> d_in;
+    hs_block<unsigned char, HS_MEM_PINNED> h_io;
 };

@@ -283,31 +283,15 @@ struct hs_sig {
     bool configured;
     slamhip_sig_spec spec;
     int count, cap_blocks;
-    k18_u64 *d_store; uint16_t *d_nset;
+    hs_block<k18_u64, HS_MEM_DEVICE> d_store; hs_block<uint16_t, HS_MEM_DEVICE> d_nset;
     std::vector<float> poses;
-    int32_t *d_cs;
-    unsigned char *d_q; size_t cap_q;          // the scans' words [scans][n_ring], then their infos
-    unsigned char *d_work; size_t cap_work;    // partial lists / packed keys
-    unsigned char *d_out; size_t cap_out;      // hits and the count
-    unsigned char *d_in; size_t cap_in;        // points and offsets of add_scans; words of upload / download
-    unsigned char *h_io; size_t cap_h;
+    hs_block<int32_t, HS_MEM_DEVICE> d_cs;
+    hs_block<unsigned char, HS_MEM_DEVICE> d_q;          // the scans' words [scans][n_ring], then their infos
+    hs_block<unsigned char, HS_MEM_DEVICE> d_work;    // partial lists / packed keys
+    hs_block<unsigned char, HS_MEM_DEVICE> d_out;      // hits and the count
+    hs_block<unsigned char, HS_MEM_DEVICE> d_in;        // points and offsets of add_scans; words of upload / download
+    hs_block<unsigned char, HS_MEM_PINNED> h_io;
 };
-
-void hs_sg_free(slamhip_hs *hs)
-{
-    hs_sig *g = hs->sig;
-    if (!g) return;
-    hs_release((void **)&g->d_store, nullptr, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_nset, nullptr, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_cs, nullptr, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_q, &g->cap_q, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_work, &g->cap_work, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_out, &g->cap_out, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_in, &g->cap_in, HS_MEM_DEVICE);
-    hs_release((void **)&g->h_io, &g->cap_h, HS_MEM_PINNED);
-    delete g;
-    hs->sig = nullptr;
-}
 
 void hs_sg_reset(slamhip_hs *hs)
 {
@@ -340,23 +324,17 @@ static int32_t hs_sg_reserve(slamhip_hs *hs, int keys)
     int cap = std::max(std::max(blocks, 2 * g->cap_blocks), 16);
     if (cap > max_blocks) cap = max_blocks;
     const size_t words = (size_t)cap * g->spec.n_ring * HS_SG_BLOCK, old_words = (size_t)g->cap_blocks * g->spec.n_ring * HS_SG_BLOCK;
-    k18_u64 *ns = nullptr; uint16_t *nn = nullptr;
-    size_t c0 = 0, c1 = 0;
-    SH_TRY(hs_grow((void **)&ns, &c0, sizeof(k18_u64) * words, HS_MEM_DEVICE, "signature store"));
-    if (hs_grow((void **)&nn, &c1, sizeof(uint16_t) * (size_t)cap * HS_SG_BLOCK, HS_MEM_DEVICE, "signature store") != SLAMHIP_OK) {
-        (void)hipFree(ns);
-        return SLAMHIP_ERR_NOMEM;
-    }
+    hs_block<k18_u64, HS_MEM_DEVICE> ns; hs_block<uint16_t, HS_MEM_DEVICE> nn;   // (an early return frees them)
+    SH_TRY(ns.grow(sizeof(k18_u64) * words, "signature store"));
+    SH_TRY(nn.grow(sizeof(uint16_t) * (size_t)cap * HS_SG_BLOCK, "signature store"));
     hipStream_t st = hs->ctx->stream;
     hipError_t e = hipMemsetAsync(ns, 0, sizeof(k18_u64) * words, st);
     if (e == hipSuccess) e = hipMemsetAsync(nn, 0, sizeof(uint16_t) * (size_t)cap * HS_SG_BLOCK, st);
     if (e == hipSuccess && old_words) e = hipMemcpyAsync(ns, g->d_store, sizeof(k18_u64) * old_words, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess && old_words) e = hipMemcpyAsync(nn, g->d_nset, sizeof(uint16_t) * (size_t)g->cap_blocks * HS_SG_BLOCK, hipMemcpyDeviceToDevice, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);                     // (the old blocks are idle behind it)
-    if (e != hipSuccess) { (void)hipFree(ns); (void)hipFree(nn); SH_HIP(e); }
-    hs_release((void **)&g->d_store, nullptr, HS_MEM_DEVICE);
-    hs_release((void **)&g->d_nset, nullptr, HS_MEM_DEVICE);
-    g->d_store = ns; g->d_nset = nn; g->cap_blocks = cap;
+    SH_HIP(e);
+    g->d_store.swap(ns); g->d_nset.swap(nn); g->cap_blocks = cap;          // (the old blocks go with ns and nn)
     return SLAMHIP_OK;
 }
 
@@ -384,19 +362,18 @@ extern "C" int32_t slamhip_hs_sig_configure(slamhip_hs *hs, const slamhip_sig_sp
     SH_TRY(hs_sg_check_spec(spec->scale, spec->n_ring, spec->ring_cells));
     slamhip_ctx *ctx = hs->ctx;
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_unit(&hs->sig));
+    SH_TRY(hs_unit<&slamhip_hs::sig>(hs));
     hs_sig *g = hs->sig;
     const bool relay = g->configured && g->spec.n_ring != spec->n_ring;    // (the blocks' size depends on n_ring)
     g->configured = false;
-    size_t cap_cs = g->d_cs ? sizeof(int32_t) * 2 * HS_SG_SECTORS : 0;
-    SH_TRY(hs_grow((void **)&g->d_cs, &cap_cs, sizeof(int32_t) * 2 * HS_SG_SECTORS, HS_MEM_DEVICE, "signature"));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, sizeof(int32_t) * 2 * HS_SG_SECTORS, HS_MEM_PINNED, "signature"));
-    hs_sig_table((int32_t *)g->h_io);
+    SH_TRY(g->d_cs.grow(sizeof(int32_t) * 2 * HS_SG_SECTORS, "signature"));
+    SH_TRY(g->h_io.grow(sizeof(int32_t) * 2 * HS_SG_SECTORS, "signature"));
+    hs_sig_table((int32_t *)g->h_io.p);
     SH_HIP(hipMemcpyAsync(g->d_cs, g->h_io, sizeof(int32_t) * 2 * HS_SG_SECTORS, hipMemcpyHostToDevice, ctx->stream));
     SH_TRY(hs_call_finish(hs));
     if (relay) {
-        hs_release((void **)&g->d_store, nullptr, HS_MEM_DEVICE);
-        hs_release((void **)&g->d_nset, nullptr, HS_MEM_DEVICE);
+        g->d_store.release();
+        g->d_nset.release();
         g->cap_blocks = 0;
     }
     g->spec = *spec;
@@ -411,14 +388,14 @@ static int32_t hs_sg_enqueue_scan(slamhip_hs *hs, bool append, int first)
 {
     hs_sig *g = hs->sig;
     const size_t sig_bytes = sizeof(k18_u64) * (size_t)g->spec.n_ring;
-    SH_TRY(hs_grow((void **)&g->d_q, &g->cap_q, sig_bytes + sizeof(slamhip_sig_info), HS_MEM_DEVICE, "signature"));
+    SH_TRY(g->d_q.grow(sig_bytes + sizeof(slamhip_sig_info), "signature"));
     if (hs->n_points > 0) SH_TRY(hs_flush_scan(hs));
     k18_sig_arg A;
     A.pts = hs->n_points > 0 ? hs->d_pts : (const float2 *)nullptr; A.offsets = nullptr; A.n = hs->n_points;
     A.scale = g->spec.scale; A.n_ring = g->spec.n_ring; A.ring_cells = g->spec.ring_cells;
     A.cs = g->d_cs;
     A.store = append ? g->d_store : (k18_u64 *)nullptr; A.nset = g->d_nset; A.first = first;
-    A.lin = (k18_u64 *)g->d_q; A.info = (int32_t *)(g->d_q + sig_bytes);
+    A.lin = (k18_u64 *)g->d_q.p; A.info = (int32_t *)(g->d_q + sig_bytes);
     hipLaunchKernelGGL(k18_sig, dim3(1), dim3(K18_LANES), 0, hs->ctx->stream, A);
     SH_HIP(hipGetLastError());
     return SLAMHIP_OK;
@@ -432,7 +409,7 @@ extern "C" int32_t slamhip_hs_sig_add(slamhip_hs *hs, const float pose[3], int32
     SH_TRY(hs_call_begin(hs));
     SH_TRY(hs_sg_reserve(hs, g->count + 1));
     const size_t io_bytes = sizeof(k18_u64) * (size_t)g->spec.n_ring + sizeof(slamhip_sig_info);
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, io_bytes, HS_MEM_PINNED, "signature add"));
+    SH_TRY(g->h_io.grow(io_bytes, "signature add"));
     SH_TRY(hs_sg_enqueue_scan(hs, true, g->count));
     SH_HIP(hipMemcpyAsync(g->h_io, g->d_q, io_bytes, hipMemcpyDeviceToHost, hs->ctx->stream));
     SH_TRY(hs_call_finish(hs));
@@ -461,13 +438,13 @@ extern "C" int32_t slamhip_hs_sig_add_scans(slamhip_hs *hs, const float *xy, con
     SH_TRY(hs_call_begin(hs));
     SH_TRY(hs_sg_reserve(hs, g->count + B));
     const size_t pts_bytes = (sizeof(float) * 2 * (size_t)total + 7) & ~(size_t)7, off_bytes = sizeof(int32_t) * ((size_t)B + 1);
-    SH_TRY(hs_grow((void **)&g->d_in, &g->cap_in, pts_bytes + off_bytes, HS_MEM_DEVICE, "signature add_scans"));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, pts_bytes + off_bytes, HS_MEM_PINNED, "signature add_scans"));
+    SH_TRY(g->d_in.grow(pts_bytes + off_bytes, "signature add_scans"));
+    SH_TRY(g->h_io.grow(pts_bytes + off_bytes, "signature add_scans"));
     if (total) memcpy(g->h_io, xy, sizeof(float) * 2 * (size_t)total);
     memcpy(g->h_io + pts_bytes, offsets, off_bytes);
     SH_HIP(hipMemcpyAsync(g->d_in, g->h_io, pts_bytes + off_bytes, hipMemcpyHostToDevice, ctx->stream));
     k18_sig_arg A;
-    A.pts = (const float2 *)g->d_in; A.offsets = (const int32_t *)(g->d_in + pts_bytes); A.n = 0;
+    A.pts = (const float2 *)g->d_in.p; A.offsets = (const int32_t *)(g->d_in + pts_bytes); A.n = 0;
     A.scale = g->spec.scale; A.n_ring = g->spec.n_ring; A.ring_cells = g->spec.ring_cells;
     A.cs = g->d_cs;
     A.store = g->d_store; A.nset = g->d_nset; A.first = g->count;
@@ -498,17 +475,17 @@ extern "C" int32_t slamhip_hs_sig_query(slamhip_hs *hs, int32_t first, int32_t l
     const int wgs = last > first ? sh_div_up(last - base, K18_LANES) : 0;
     const size_t sig_bytes = sizeof(k18_u64) * (size_t)n_ring, q_bytes = sig_bytes + sizeof(slamhip_sig_info);
     const size_t hit_bytes = sizeof(slamhip_sig_hit) * (size_t)B, out_bytes = hit_bytes + 8;
-    SH_TRY(hs_grow((void **)&g->d_work, &g->cap_work, sizeof(slamhip_sig_hit) * (size_t)B * std::max(wgs, 1), HS_MEM_DEVICE, "signature query"));
-    SH_TRY(hs_grow((void **)&g->d_out, &g->cap_out, out_bytes, HS_MEM_DEVICE, "signature query"));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, out_bytes + q_bytes, HS_MEM_PINNED, "signature query"));
+    SH_TRY(g->d_work.grow(sizeof(slamhip_sig_hit) * (size_t)B * std::max(wgs, 1), "signature query"));
+    SH_TRY(g->d_out.grow(out_bytes, "signature query"));
+    SH_TRY(g->h_io.grow(out_bytes + q_bytes, "signature query"));
     SH_TRY(hs_sg_enqueue_scan(hs, false, 0));
     if (wgs) {
         k18_query_arg Q;
         Q.store = g->d_store; Q.nset = g->d_nset; Q.n_ring = n_ring;
         Q.first = first; Q.last = last; Q.base = base;
-        Q.q = (const k18_u64 *)g->d_q; Q.qinfo = (const int32_t *)(g->d_q + sig_bytes);
+        Q.q = (const k18_u64 *)g->d_q.p; Q.qinfo = (const int32_t *)(g->d_q + sig_bytes);
         Q.B = B;
-        Q.part = (slamhip_sig_hit *)g->d_work;
+        Q.part = (slamhip_sig_hit *)g->d_work.p;
         // (at most 4096 workgroups)
         switch (hs_sg_rg(n_ring)) {
         case 8: hs_sg_launch_query<8>(ctx->stream, wgs, Q); break;
@@ -517,7 +494,7 @@ extern "C" int32_t slamhip_hs_sig_query(slamhip_hs *hs, int32_t first, int32_t l
         default: hs_sg_launch_query<32>(ctx->stream, wgs, Q); break;
         }
         SH_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k18_query_finish, dim3(1), dim3(K18_LANES), 0, ctx->stream, (const slamhip_sig_hit *)g->d_work, wgs * B, B, (slamhip_sig_hit *)g->d_out,
+        hipLaunchKernelGGL(k18_query_finish, dim3(1), dim3(K18_LANES), 0, ctx->stream, (const slamhip_sig_hit *)g->d_work.p, wgs * B, B, (slamhip_sig_hit *)g->d_out.p,
                            (int32_t *)(g->d_out + hit_bytes));
         SH_HIP(hipGetLastError());
         SH_HIP(hipMemcpyAsync(g->h_io, g->d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -545,14 +522,14 @@ extern "C" int32_t slamhip_hs_sig_self(slamhip_hs *hs, int32_t first, int32_t la
     SH_TRY(hs_call_begin(hs));
     const int n = last - first, n_ring = g->spec.n_ring;
     const int tile0 = first / HS_SG_BLOCK, tiles = (last - 1) / HS_SG_BLOCK - tile0 + 1;
-    SH_TRY(hs_grow((void **)&g->d_work, &g->cap_work, sizeof(k18_u64) * (size_t)n, HS_MEM_DEVICE, "signature self search"));
-    SH_TRY(hs_grow((void **)&g->d_out, &g->cap_out, sizeof(slamhip_sig_hit) * (size_t)n, HS_MEM_DEVICE, "signature self search"));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, sizeof(slamhip_sig_hit) * (size_t)n, HS_MEM_PINNED, "signature self search"));
+    SH_TRY(g->d_work.grow(sizeof(k18_u64) * (size_t)n, "signature self search"));
+    SH_TRY(g->d_out.grow(sizeof(slamhip_sig_hit) * (size_t)n, "signature self search"));
+    SH_TRY(g->h_io.grow(sizeof(slamhip_sig_hit) * (size_t)n, "signature self search"));
     SH_HIP(hipMemsetAsync(g->d_work, 0, sizeof(k18_u64) * (size_t)n, ctx->stream));
     k18_self_arg S;
     S.store = g->d_store; S.nset = g->d_nset; S.n_ring = n_ring;
     S.first = first; S.last = last; S.min_gap = min_gap; S.tile0 = tile0;
-    S.best = (k18_u64 *)g->d_work;
+    S.best = (k18_u64 *)g->d_work.p;
     // (at most 16384 x 16384 tile pairs; those above the band leave at once)
     switch (hs_sg_rg(n_ring)) {
     case 8: hs_sg_launch_self<8>(ctx->stream, tiles, S); break;
@@ -562,7 +539,7 @@ extern "C" int32_t slamhip_hs_sig_self(slamhip_hs *hs, int32_t first, int32_t la
     }
     SH_HIP(hipGetLastError());
     hipLaunchKernelGGL(k18_self_finish, dim3((unsigned)sh_div_up(n, K18_LANES)), dim3(K18_LANES), 0, ctx->stream, (const k18_u64 *)g->d_store,
-                       (const uint16_t *)g->d_nset, n_ring, first, last, (const k18_u64 *)g->d_work, (slamhip_sig_hit *)g->d_out);
+                       (const uint16_t *)g->d_nset, n_ring, first, last, (const k18_u64 *)g->d_work.p, (slamhip_sig_hit *)g->d_out.p);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(g->h_io, g->d_out, sizeof(slamhip_sig_hit) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SH_TRY(hs_call_finish(hs));
@@ -591,10 +568,10 @@ extern "C" int32_t slamhip_hs_sig_download(slamhip_hs *hs, int32_t first, int32_
     slamhip_ctx *ctx = hs->ctx;
     SH_TRY(hs_call_begin(hs));
     const size_t bytes = sizeof(k18_u64) * (size_t)n * g->spec.n_ring;
-    SH_TRY(hs_grow((void **)&g->d_in, &g->cap_in, bytes, HS_MEM_DEVICE, "signature download"));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, bytes, HS_MEM_PINNED, "signature download"));
+    SH_TRY(g->d_in.grow(bytes, "signature download"));
+    SH_TRY(g->h_io.grow(bytes, "signature download"));
     hipLaunchKernelGGL(k18_get, dim3((unsigned)sh_div_up(n, K18_LANES)), dim3(K18_LANES), 0, ctx->stream, (const k18_u64 *)g->d_store, n, g->spec.n_ring, first,
-                       (k18_u64 *)g->d_in);
+                       (k18_u64 *)g->d_in.p);
     SH_HIP(hipGetLastError());
     SH_HIP(hipMemcpyAsync(g->h_io, g->d_in, bytes, hipMemcpyDeviceToHost, ctx->stream));
     SH_TRY(hs_call_finish(hs));
@@ -624,11 +601,11 @@ extern "C" int32_t slamhip_hs_sig_upload(slamhip_hs *hs, int32_t n, const uint64
     SH_TRY(hs_call_begin(hs));
     SH_TRY(hs_sg_reserve(hs, g->count + n));
     const size_t bytes = sizeof(k18_u64) * (size_t)n * g->spec.n_ring;
-    SH_TRY(hs_grow((void **)&g->d_in, &g->cap_in, bytes, HS_MEM_DEVICE, "signature upload"));
-    SH_TRY(hs_grow((void **)&g->h_io, &g->cap_h, bytes, HS_MEM_PINNED, "signature upload"));
+    SH_TRY(g->d_in.grow(bytes, "signature upload"));
+    SH_TRY(g->h_io.grow(bytes, "signature upload"));
     memcpy(g->h_io, sig, bytes);
     SH_HIP(hipMemcpyAsync(g->d_in, g->h_io, bytes, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k18_put, dim3((unsigned)sh_div_up(n, K18_LANES)), dim3(K18_LANES), 0, ctx->stream, (const k18_u64 *)g->d_in, n, g->spec.n_ring, g->count,
+    hipLaunchKernelGGL(k18_put, dim3((unsigned)sh_div_up(n, K18_LANES)), dim3(K18_LANES), 0, ctx->stream, (const k18_u64 *)g->d_in.p, n, g->spec.n_ring, g->count,
                        g->d_store, g->d_nset);
     SH_HIP(hipGetLastError());
     SH_TRY(hs_call_finish(hs));
@@ -643,7 +620,7 @@ extern "C" int32_t slamhip_hs_sig_clear(slamhip_hs *hs)
     if (!hs->sig) return SLAMHIP_OK;
     SH_TRY(hs_call_begin(hs));
     SH_TRY(hs_call_finish(hs));                                            // (the blocks are idle behind it)
-    hs_sg_free(hs);
+    hs_unit_drop<&slamhip_hs::sig>(hs);
     return SLAMHIP_OK;
 }
 

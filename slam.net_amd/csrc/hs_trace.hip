@@ -170,14 +170,6 @@ __global__ void __launch_bounds__(K8_LANES) k8_trace(const k8_arg A)
 // ---- host side ---------------------------------------------------------------------------------------------------
 // What a trace needs, made by the first one and kept: hs->trc, the blocks of a pose batch (hs_blocks.h) -- B summaries, then the
 // beam records.
-void hs_trc_free(slamhip_hs *hs)
-{
-    if (!hs->trc) return;
-    hs_pose_batch_release(hs->trc);
-    delete hs->trc;
-    hs->trc = nullptr;
-}
-
 int32_t hs_trc_check(int n_levels, int32_t level, int32_t B, int32_t world, bool want_beams, int n_points, bool scan_is_set)
 {
     if (level < 0 || level >= n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "trace: level %d of %d", level, n_levels);
@@ -195,7 +187,7 @@ extern "C" int32_t slamhip_hs_trace(slamhip_hs *hs, int32_t level, const float *
     SH_TRY(hs_pose_batch_chunks("trace", B, n, K8_LANES, &chunks));
     hs_class_map M;
     SH_TRY(hs_lat_pack_prepare(hs, level, world != 0, &M));                // (the world's plan refuses before anything is launched)
-    SH_TRY(hs_unit(&hs->trc));
+    SH_TRY(hs_unit<&slamhip_hs::trc>(hs));
     hs_pose_batch *tr = hs->trc;
     const size_t sum_bytes = sizeof(slamhip_trace_summary) * (size_t)B;
     const size_t beam_bytes = out_beams ? sizeof(slamhip_trace_beam) * (size_t)B * n : 0;   // (both multiples of 8)
@@ -207,7 +199,7 @@ extern "C" int32_t slamhip_hs_trace(slamhip_hs *hs, int32_t level, const float *
     A.cls = M.cls; A.w = M.w; A.h = M.h; A.wpr = M.wpr;
     A.x0 = M.x0; A.y0 = M.y0;
     A.stm = hs->lv[level].stm;
-    A.sums = (slamhip_trace_summary *)tr->d_out;
+    A.sums = (slamhip_trace_summary *)tr->d_out.p;
     A.beams = out_beams ? (slamhip_trace_beam *)(tr->d_out + sum_bytes) : (slamhip_trace_beam *)nullptr;
     hipLaunchKernelGGL(k8_trace, dim3((unsigned)(B * chunks)), dim3(K8_LANES), 0, hs->ctx->stream, A);    // (no timing class of its own)
     SH_HIP(hipGetLastError());

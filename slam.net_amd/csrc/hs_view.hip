@@ -273,31 +273,16 @@ __global__ void __launch_bounds__(K15_LANES) k15_pick(const k15_sel_arg A)
 // made under, the poses, summaries, slot headers, the scratch block of the slots, the choice's block, and the pinned block the
 // poses leave and the results reach the host through.
 struct hs_view {
-    uint32_t *d_cov; size_t cap_cov;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_cov;
     bool have; int level, cwpr, ch; int64_t ox, oy;
-    float *d_poses; size_t cap_poses;
-    int32_t *d_sums; size_t cap_sums;
-    hs_view_box *d_hdr; size_t cap_hdr;
-    uint32_t *d_slots; size_t cap_slots;
-    int32_t *d_sel; size_t cap_sel;        // chosen[B], gain[B], then order[64], gains[64], state[2]
-    unsigned char *h_io; size_t cap_h;
+    hs_block<float, HS_MEM_DEVICE> d_poses;
+    hs_block<int32_t, HS_MEM_DEVICE> d_sums;
+    hs_block<hs_view_box, HS_MEM_DEVICE> d_hdr;
+    hs_block<uint32_t, HS_MEM_DEVICE> d_slots;
+    hs_block<int32_t, HS_MEM_DEVICE> d_sel;        // chosen[B], gain[B], then order[64], gains[64], state[2]
+    hs_block<unsigned char, HS_MEM_PINNED> h_io;
 };
 #define K15_RES_INTS (2 * HS_VIEW_MAX_K + 2)
-
-void hs_view_free(slamhip_hs *hs)
-{
-    hs_view *v = hs->vw;
-    if (!v) return;
-    hs_release((void **)&v->d_cov, &v->cap_cov, HS_MEM_DEVICE);
-    hs_release((void **)&v->d_poses, &v->cap_poses, HS_MEM_DEVICE);
-    hs_release((void **)&v->d_sums, &v->cap_sums, HS_MEM_DEVICE);
-    hs_release((void **)&v->d_hdr, &v->cap_hdr, HS_MEM_DEVICE);
-    hs_release((void **)&v->d_slots, &v->cap_slots, HS_MEM_DEVICE);
-    hs_release((void **)&v->d_sel, &v->cap_sel, HS_MEM_DEVICE);
-    hs_release((void **)&v->h_io, &v->cap_h, HS_MEM_PINNED);
-    delete v;
-    hs->vw = nullptr;
-}
 
 // the developer switch (tests, tools/hs_view_bench.py): the slots in global scratch at any size
 static bool k15_global() { static const bool v = sh_env_set("SLAMHIP_K15_GLOBAL"); return v; }
@@ -360,7 +345,7 @@ static int32_t k15_layer_make(slamhip_hs *hs, int level, bool zero)
     const int cwpr = (L.w + 31) / 32;
     const size_t bytes = sizeof(uint32_t) * (size_t)cwpr * L.h;
     v->have = false;
-    SH_TRY(hs_grow((void **)&v->d_cov, &v->cap_cov, bytes, HS_MEM_DEVICE, "view"));
+    SH_TRY(v->d_cov.grow(bytes, "view"));
     if (zero) SH_HIP(hipMemsetAsync(v->d_cov, 0, bytes, hs->ctx->stream));
     v->level = level; v->cwpr = cwpr; v->ch = L.h;
     v->ox = hs->win_ox; v->oy = hs->win_oy;
@@ -373,15 +358,15 @@ extern "C" int32_t slamhip_hs_view_set_covered(slamhip_hs *hs, int32_t level, co
     SH_CHECK_ARG(hs);
     if (level < 0 || level >= hs->n_levels) SH_FAIL(SLAMHIP_ERR_INVALID, "view: level %d of %d", level, hs->n_levels);
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_unit(&hs->vw));
+    SH_TRY(hs_unit<&slamhip_hs::vw>(hs));
     hs_view *v = hs->vw;
     const hs_level &L = hs->lv[level];
     const int cwpr = (L.w + 31) / 32;
     const size_t bytes = sizeof(uint32_t) * (size_t)cwpr * L.h;
-    if (bits) SH_TRY(hs_grow((void **)&v->h_io, &v->cap_h, bytes, HS_MEM_PINNED, "view"));
+    if (bits) SH_TRY(v->h_io.grow(bytes, "view"));
     SH_TRY(k15_layer_make(hs, level, bits == nullptr));
     if (bits) {
-        uint32_t *st = (uint32_t *)v->h_io;
+        uint32_t *st = (uint32_t *)v->h_io.p;
         memcpy(st, bits, bytes);
         if (L.w & 31)                                                      // the padding bits are ignored
             for (int y = 0; y < L.h; y++) st[(size_t)y * cwpr + cwpr - 1] &= (1u << (L.w & 31)) - 1u;
@@ -402,7 +387,7 @@ extern "C" int32_t slamhip_hs_view_get_covered(slamhip_hs *hs, int32_t level, ui
     hs_view *v = hs->vw;
     if (!v || !v->have) { memset(bits, 0, bytes); return SLAMHIP_OK; }     // (empty until set or committed to)
     SH_TRY(hs_call_begin(hs));
-    SH_TRY(hs_grow((void **)&v->h_io, &v->cap_h, bytes, HS_MEM_PINNED, "view"));
+    SH_TRY(v->h_io.grow(bytes, "view"));
     SH_HIP(hipMemcpyAsync(v->h_io, v->d_cov, bytes, hipMemcpyDeviceToHost, hs->ctx->stream));
     SH_TRY(hs_call_finish(hs));
     memcpy(bits, v->h_io, bytes);
@@ -415,7 +400,7 @@ extern "C" int32_t slamhip_hs_view_clear(slamhip_hs *hs)
     if (!hs->vw) return SLAMHIP_OK;
     SH_TRY(hs_call_begin(hs));
     SH_HIP(hipStreamSynchronize(hs->ctx->stream));                         // (the blocks are idle after every call of this unit; other units' launches may be in flight)
-    hs_view_free(hs);
+    hs_unit_drop<&slamhip_hs::vw>(hs);
     return SLAMHIP_OK;
 }
 
@@ -425,15 +410,15 @@ static int32_t k15_enqueue_view(slamhip_hs *hs, int level, int reach, const floa
 {
     hs_class_map M;
     SH_TRY(hs_lat_pack_prepare(hs, level, false, &M));
-    SH_TRY(hs_unit(&hs->vw));
+    SH_TRY(hs_unit<&slamhip_hs::vw>(hs));
     hs_view *v = hs->vw;
     const size_t pose_bytes = sizeof(float) * 3 * (size_t)B;
-    SH_TRY(hs_grow((void **)&v->d_poses, &v->cap_poses, pose_bytes, HS_MEM_DEVICE, "view"));
-    SH_TRY(hs_grow((void **)&v->d_sums, &v->cap_sums, sizeof(slamhip_view_summary) * (size_t)B, HS_MEM_DEVICE, "view"));
-    SH_TRY(hs_grow((void **)&v->h_io, &v->cap_h, h_off + pose_bytes, HS_MEM_PINNED, "view"));
+    SH_TRY(v->d_poses.grow(pose_bytes, "view"));
+    SH_TRY(v->d_sums.grow(sizeof(slamhip_view_summary) * (size_t)B, "view"));
+    SH_TRY(v->h_io.grow(h_off + pose_bytes, "view"));
     if (P.slots) {
-        SH_TRY(hs_grow((void **)&v->d_hdr, &v->cap_hdr, sizeof(hs_view_box) * (size_t)B, HS_MEM_DEVICE, "view"));
-        SH_TRY(hs_grow((void **)&v->d_slots, &v->cap_slots, sizeof(uint32_t) * (size_t)B * (size_t)P.slot_words, HS_MEM_DEVICE, "view"));
+        SH_TRY(v->d_hdr.grow(sizeof(hs_view_box) * (size_t)B, "view"));
+        SH_TRY(v->d_slots.grow(sizeof(uint32_t) * (size_t)B * (size_t)P.slot_words, "view"));
     }
     hipStream_t st = hs->ctx->stream;
     if (need_layer && !v->have) SH_TRY(k15_layer_make(hs, level, true));
@@ -493,13 +478,13 @@ extern "C" int32_t slamhip_hs_view_select(slamhip_hs *hs, int32_t level, int32_t
     SH_TRY(hs_call_begin(hs));
     const k15_plan P = k15_plan_of(hs, level, reach, true);
     const size_t res_bytes = sizeof(int32_t) * K15_RES_INTS;
-    SH_TRY(hs_unit(&hs->vw));
+    SH_TRY(hs_unit<&slamhip_hs::vw>(hs));
     hs_view *v = hs->vw;
-    SH_TRY(hs_grow((void **)&v->d_sel, &v->cap_sel, sizeof(int32_t) * (2 * (size_t)B + K15_RES_INTS), HS_MEM_DEVICE, "view"));
+    SH_TRY(v->d_sel.grow(sizeof(int32_t) * (2 * (size_t)B + K15_RES_INTS), "view"));
     k15_arg A;
     SH_TRY(k15_enqueue_view(hs, level, reach, poses, B, P, true, 2 * res_bytes, &A));   // (pinned: the results, their initial values, the poses)
     hipStream_t st = hs->ctx->stream;
-    int32_t *h_res = (int32_t *)v->h_io, *h_init = h_res + K15_RES_INTS;
+    int32_t *h_res = (int32_t *)v->h_io.p, *h_init = h_res + K15_RES_INTS;
     for (int i = 0; i < HS_VIEW_MAX_K; i++) { h_init[i] = -1; h_init[HS_VIEW_MAX_K + i] = 0; }
     h_init[2 * HS_VIEW_MAX_K] = 0; h_init[2 * HS_VIEW_MAX_K + 1] = 0;
     k15_sel_arg S;

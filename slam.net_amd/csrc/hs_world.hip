@@ -1,6 +1,7 @@
 // hs_world.hip -- the world behind the scrolling window of HectorSLAM and its backing store (hs_window.hip), the calls that block:
 // download, upload and extents (slamhip_hs_world_cells_download, _world_cells_upload, _world_extends).
 #include "hs_tiles.h"
+#include "hs_blocks.h"
 #include "world_plan.h"
 
 // ---- K6 world put: load a saved world back (slamhip_hs_world_cells_upload) -------------------------------------------------------
@@ -104,15 +105,17 @@ struct hs_world {
     std::vector<slamhip_world_job> plan;
     std::vector<k6w_piece> pieces;
     std::vector<k6x_job> xjobs;
+    ~hs_world()                                                            // (the caller has drained the stream)
+    {
+        if (d) (void)hipFree(d);
+        if (ev) (void)hipEventDestroy(ev);
+        if (h_ext) (void)hipHostFree(h_ext);
+    }
 };
 
 static int32_t hs_wp_stage(slamhip_hs *hs, size_t bytes)
 {
-    if (!hs->wp) {
-        hs_world *wp = new (std::nothrow) hs_world();                     // (value-initialised: no block, no event yet)
-        if (!wp) SH_FAIL(SLAMHIP_ERR_NOMEM, "out of host memory");
-        hs->wp = wp;
-    }
+    SH_TRY(hs_unit<&slamhip_hs::wp>(hs));                                  // (value-initialised: no block, no event yet)
     hs_world *wp = hs->wp;
     if (!wp->ev) SH_HIP(hipEventCreateWithFlags(&wp->ev, hipEventDisableTiming));
     if (!wp->h_ext) SH_HIP(hipHostMalloc((void **)&wp->h_ext, 8 * sizeof(long long), hipHostMallocDefault));
@@ -122,18 +125,6 @@ static int32_t hs_wp_stage(slamhip_hs *hs, size_t bytes)
         wp->cap = bytes;
     }
     return SLAMHIP_OK;
-}
-
-// (the caller has drained the stream)
-void hs_wp_free(slamhip_hs *hs)
-{
-    hs_world *wp = hs->wp;
-    if (!wp) return;
-    if (wp->d) (void)hipFree(wp->d);
-    if (wp->ev) (void)hipEventDestroy(wp->ev);
-    if (wp->h_ext) (void)hipHostFree(wp->h_ext);
-    delete wp;
-    hs->wp = nullptr;
 }
 
 // what opens every world call behind its argument checks: hs->wp exists from here on, with its event

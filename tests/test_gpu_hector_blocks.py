@@ -1,11 +1,15 @@
-"""What the Hector units K7 .. K13 share on the host (hs_blocks.h): blocks that grow and are then reused while larger than the call
-needs, the one event every blocking call of an hs records and waits on, units made on first use and freed with the hs, and a unit
-whose first call is refused.  Every result is compared with == (field by field, floats by their bits) against the SAME call on a
+"""What the Hector units K7 .. K27 share on the host (hs_blocks.h): blocks that grow and are then reused while larger than the call
+needs, the one event every blocking call of an hs records and waits on, units made on first use and freed with the hs or by their
+*_clear entry point -- every block of theirs, by the count of live blocks (slamhip_debug_live_blocks) -- and a unit whose first
+call is refused.  Every result is compared with == (field by field, floats by their bits) against the SAME call on a
 fresh hs that holds the same map; nothing is compared with an earlier result of the object under test.
 
 Shapes: the 80 x 48 x 2 pyramid of the K9 tests' `small` fixture, holding a room -- walls, a free inside with a pillar, the unknown
 around it, a gap in the wall where free cells touch the unknown -- and a scan of 65 points, a wavefront and one lane more."""
 import math
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -176,9 +180,15 @@ def test_interleaved_units(hs_mod, ctx, ref):
 @gpu
 @pytest.mark.parametrize("used", [[], ["k13_300"], ORDER], ids=["none", "k13", "all"])
 def test_create_and_destroy(hs_mod, ctx, ref, used):
+    for name in used:
+        ref(name)                                                          # (its own hs is gone before the baseline is read)
+    base = hs_mod.capi.live_blocks()
     rep = make(hs_mod, ctx)
     check(hs_mod, rep, ref, used)
+    live = hs_mod.capi.live_blocks()
+    assert (live[0] > base[0] and live[1] > base[1]) if used else live == base, (base, live)
     rep.close()
+    assert hs_mod.capi.live_blocks() == base
     rep = make(hs_mod, ctx)
     check(hs_mod, rep, ref, ["k8_300r"])
     rep.close()
@@ -188,6 +198,8 @@ def test_create_and_destroy(hs_mod, ctx, ref, used):
 @gpu
 @pytest.mark.parametrize("name", ORDER)
 def test_refused_first_use(hs_mod, ctx, ref, name):
+    ref(name)                                                              # (its own hs is gone before the baseline is read)
+    base = hs_mod.capi.live_blocks()
     rep = make(hs_mod, ctx)
     # level = n_levels; K13's set takes no level, so its first use is the refused step itself
     refused = CALLS[name] if name != "k13_300" else lambda m, r, l: r.mcl_step(mcl_spec(m, l, 300))
@@ -196,3 +208,104 @@ def test_refused_first_use(hs_mod, ctx, ref, name):
     assert e.value.code == hs_mod.capi.ERR_INVALID and "level %d of %d" % (LEVELS, LEVELS) in str(e.value)
     check(hs_mod, rep, ref, [name])
     rep.close()
+    assert hs_mod.capi.live_blocks() == base
+
+
+@gpu
+@pytest.mark.parametrize("name", ORDER)
+def test_refused_first_use_then_close(hs_mod, ctx, name):
+    base = hs_mod.capi.live_blocks()
+    rep = make(hs_mod, ctx)
+    refused = CALLS[name] if name != "k13_300" else lambda m, r, l: r.mcl_step(mcl_spec(m, l, 300))
+    with pytest.raises(hs_mod.capi.SlamhipError):
+        refused(hs_mod, rep, LEVELS)
+    rep.close()
+    assert hs_mod.capi.live_blocks() == base
+
+
+# ---- 5. the *_clear entry points -------------------------------------------------------------------------------------------------------
+# name -> (the unit used once at its smallest accepted input, its clear, the calls that warm what the unit shares with another one:
+# K15 and K17 pack K7's class map, whose blocks are K7's and stay)
+def _pg(m, r, l):
+    r.PgSet([[0.0, 0.0, 0.0], [1.0, 0.1, 0.05]], None, [[0, 1]], [[1.1, 0.0, 0.0]], [[400.0, 400.0, 2500.0]])
+    it, fin = r.PgRelax(m.capi.pg_spec(1, 3))
+    return it, fin, r.PgGet()
+
+
+def _scans(m, r, l):
+    k = r.ScansAdd()
+    return (k,) + tuple(r.ScansGet(k))
+
+
+def _loops(m, r, l):
+    return r.LoopsConsistent([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0]], [[0, 1]], [[1.0, 0.0, 0.0]], [[400.0, 400.0, 2500.0]], m.capi.loops_spec(11.34, 1e-3, 1e-4))
+
+
+CLEARS = {
+    "hough": (lambda m, r, l: r.hough(l, T=4), lambda r: r.hough_clear(), ["k7_1"]),
+    "pg": (_pg, lambda r: r.PgClear(), []),
+    "scans": (_scans, lambda r: r.ScansClear(), []),
+    "view": (lambda m, r, l: r.view_gain(poses(1), l, 8), lambda r: r.view_clear(), ["k7_1"]),
+    "loops": (_loops, lambda r: r.LoopsClear(), []),
+}
+
+
+@gpu
+@pytest.mark.parametrize("name", sorted(CLEARS))
+def test_clear_frees_the_unit(hs_mod, ctx, ref, name):
+    use, clear, warm = CLEARS[name]
+    fresh = make(hs_mod, ctx)
+    want = use(hs_mod, fresh, 0)
+    fresh.close()
+    rep = make(hs_mod, ctx)
+    check(hs_mod, rep, ref, warm)
+    before = hs_mod.capi.live_blocks()
+    assert same(use(hs_mod, rep, 0), want)
+    used = hs_mod.capi.live_blocks()
+    assert used[0] > before[0] and used[1] > before[1], (before, used)
+    clear(rep)
+    assert hs_mod.capi.live_blocks() == before
+    assert same(use(hs_mod, rep, 0), want)                                 # the unit works again
+    assert hs_mod.capi.live_blocks() == used
+    rep.close()
+
+
+# ---- 6. the two stores that grow by a new allocation: K18's keyframes, K20's scan pool ---------------------------------------------------
+POOL_ENV = {"SLAMHIP_K20_POOL_POINTS": "64"}                              # (read once per process: the pool of 65 points doubles at the second scan)
+
+
+@gpu
+def test_stores_regrow_child(hs_mod, ctx):
+    """Run by test_stores_regrow_and_close with POOL_ENV set; on its own the scan pool has room and only the keyframe store grows."""
+    capi = hs_mod.capi
+    base = capi.live_blocks()
+    rep = make(hs_mod, ctx)
+    rep.SigConfigure(3.0, 5, 2)
+    rep.SigAdd((0.0, 0.0, 0.0))
+    rep.SigConfigure(3.0, 7, 2)                                            # another n_ring: the store is dropped and laid out anew
+    _, sig0, _ = rep.SigAdd((1.0, 2.0, 3.0))
+    live = capi.live_blocks()
+    B = 16 * 64 + 6                                                        # past the first store of 16 blocks of 64 keyframes
+    rep.SigAddScans([SCAN_XY[:3]] * B, np.zeros((B, 3), F))
+    grown = capi.live_blocks()
+    assert rep.SigCount() == B + 1 and grown[1] > live[1]
+    sig, p = rep.SigDownload(0, 1)
+    assert same(sig[0], sig0) and same(p[0], np.array([1.0, 2.0, 3.0], F))  # the old store is the new one's front
+    for k in range(3):
+        assert rep.ScansAdd() == k
+        if k == 0:
+            blocks = capi.live_blocks()[0]
+    assert capi.live_blocks()[0] == blocks                                  # a larger pool replaces the old one
+    for k in range(3):
+        xy, org = rep.ScansGet(k)
+        assert same(xy, SCAN_XY)
+    rep.close()
+    assert capi.live_blocks() == base
+
+
+@gpu
+def test_stores_regrow_and_close():
+    r = subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-m", "pytest", os.path.abspath(__file__), "-m", "gpu", "-x", "-q", "-k", "stores_regrow_child"],
+                       env=dict(os.environ, **POOL_ENV), stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    out = r.stdout.decode(errors="replace")
+    assert r.returncode == 0 and "1 passed" in out and "failed" not in out, out[-3000:]
